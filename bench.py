@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Benchmark of the hot path: cINN inverse + stage-1 decoder, synthesized frames/sec (BASELINE.json metric).
 
-    python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 [--dump-outputs DIR]
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full   (+ every check and extra measurement listed below)
     python bench.py --gpus N --steps K --warmup W          (plain shell: re-executes itself under torch.distributed.run,
                                                             one process per GPU, 127.0.0.1 rendezvous on a free port)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
@@ -19,7 +20,13 @@ dtdb128 = configs[3] (global batch 256), iper128_t32 = configs[4] (global batch 
 128x128 decoder geometry nf = 32 with E = 128).  --scaling weak (default): the config's batch PER GPU; --scaling strong: the
 config's batch is the GLOBAL batch, sharded over the ranks (the fixed-global-batch jobs of configs[3], configs[4]).
 
-Rank 0 prints ONE JSON line with the contract fields plus
+A plain run (no --full) sets up, warms up, times the steps and prints ONE JSON line on rank 0 with the contract fields
+(metric, value, unit, n_gpus, steps, warmup, ms_per_step, higher_is_better, scaling, vs_baseline, dtype, data, config) and
+value_is -- nothing else is measured or checked.  --dump-outputs DIR writes the frames the last timed step produced to
+DIR/frames.npy (float32 [B, T, 3, H, W]; above 64 MB a fixed, seeded sample of them, DIR/frames_sample.npy), so that two builds
+can be compared output for output on identical seeded inputs.
+
+With --full, rank 0's line carries the contract fields plus
   roofline     THE dominant kernel alone (the one with the largest summed duration among the 3x3x3 Conv3d launches of the
                timed steps; on every shipped config conv_wino4_f16x3_kernel, the Winograd F(4,3) split-fp16 conv): achieved =
                algorithmic FLOPs of its launches / their summed duration, measured with HIP events on the launch stream
@@ -80,6 +87,14 @@ def main():
                     help="weak: the config's batch per GPU; strong: the config's batch is the global batch")
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (weak) / global batch (strong); default: the config's")
     ap.add_argument("--vid-length", type=int, default=0, help="default: the config's (16, or 32 for iper128_t32)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the frames of the last timed step to DIR/frames.npy (float32; above 64 MB a "
+                         "fixed, seeded sample: DIR/frames_sample.npy)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure, check every timed step against a serial reference call and measure everything "
+                         "else the line can carry (rooflines, single call, sustained load, exact fp32, CPU baseline, the second batch and "
+                         "configuration, live HBM traffic, ...).  --no-cpu-baseline, --no-extras, --sustain, --no-exact, --live-traffic, "
+                         "--small-batch, --per-layer, --lean and --no-config-128 shape a --full run and do nothing without it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true",
                     help="skip the post-timing measurements (cINN latency loop, MFMA probe, embedder / encoder latency): use "
@@ -94,7 +109,7 @@ def main():
                          "and says so")
     ap.add_argument("--no-live-traffic", dest="live_traffic", action="store_false")
     ap.add_argument("--small-batch", type=int, default=8,
-                    help="second first-class workload of the default line: the per-GPU share of the BAIR B = 64 job on 8 GPUs (0: skip)")
+                    help="second first-class workload of the --full line: the per-GPU share of the BAIR B = 64 job on 8 GPUs (0: skip)")
     ap.add_argument("--per-layer", type=str, help="write the per-layer table of the 3x3x3 conv launches (CSV) here")
     ap.add_argument("--pipeline", type=int, default=1, choices=[0, 1],
                     help="1 (default): the cINN pass of step k+1 runs on a side stream underneath the decoder of step k "
@@ -117,12 +132,16 @@ def main():
                          "events ProcessGroupNCCL adds are then part of the measurement)")
     ap.add_argument("--lean", action="store_true",
                     help="timed steps, checksums, single_call and the per-layer roofline only (no sustained / exact-fp32 / cINN / probe / "
-                         "embedder legs): what the default run's `config_128` child leg uses")
-    ap.add_argument("--no-config-128", action="store_true", help="skip the Landscape 128x128 child leg of the default line")
+                         "embedder legs): what the --full run's `config_128` child leg uses")
+    ap.add_argument("--no-config-128", action="store_true", help="skip the Landscape 128x128 child leg of the --full line")
     ap.add_argument("--dry", action="store_true",
                     help="CPU / gloo rehearsal of the launch path (self-launch, sharding, collation, JSON line); the step is a "
                          "stand-in without kernels and the line says so")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full and not args.dry and (args.lean or args.no_extras or args.per_layer or args.live_traffic):
+        ap.error("--lean, --no-extras, --per-layer and --live-traffic shape a --full run: add --full")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus))
     if args.dry:
@@ -232,7 +251,8 @@ def main():
         z = z.view(hi - lo, -1)
         last_z["z"] = z
         seq = g.decode_sequence(x0_d, z, vid_length)   # get_model.py:68-73, decoded in place into one [B, vid_length, 3, H, W] buffer
-        step_sums.append(checksum(seq))
+        if args.full:
+            step_sums.append(checksum(seq))
         collator.submit(seq)   # N > 1: all-gather on a side stream, overlapping the next step; N = 1: keeps the tensor
         return seq
 
@@ -277,27 +297,68 @@ def main():
         collator.result()
     barrier()
     del step_sums[:]
-    gen.native().set_profile(True)
+    if args.full:
+        gen.native().set_profile(True)   # (HIP events around every 3x3x3 conv launch: the roofline figures)
     t0 = time.perf_counter()
     run_steps(args.steps)
     out = collator.result()    # the current stream waits for the last gather; the barrier below covers it
     barrier()
     dt = time.perf_counter() - t0
-    prof = gen.native().get_profile()
-    layers = gen.native().get_layer_profile()
-    gen.native().set_profile(False)
-    timed_sums = list(step_sums)
     dt_rank = dt
-    rank_ms = [dt / max(args.steps, 1) * 1e3]
     if multi:
         tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)   # the timing scalar (max over ranks)
         dt = float(tmax.item())
+    frames_per_step = out.shape[0] * out.shape[1]
+    assert out.shape[0] == total, (out.shape, total)
+    nb = hi - lo
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
+
+    def headline():
+        """The contract fields of the line: what a plain run prints, and the first keys of a --full line."""
+        return {
+            "metric": "synthesized frames/sec (BxT): cINN inverse + VAE decoder",
+            "value": frames_per_step * args.steps / dt,
+            "unit": "frames/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": dt / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": args.scaling,
+            "vs_baseline": None,
+            "dtype": "f32" if gen.mma == 0 else "f32 (split-fp16 MFMA: fp16 hi/lo operand pairs, 3 MFMAs per product, fp32 accumulate)" +
+                     ("; auto mode: per-layer fallback to exact fp32 behind the range guard, switched so far: %s" % gen.native().fallback_layers() if gen.mma == 2 else ""),
+            "data": "synthetic (seeded start frames / latents / embeddings, deterministic synthetic weights)",
+            "config": {"workload": f"{cfg['name']}, batch {nb}/GPU (global {total}), vid_length {vid_length}: "
+                                   "20-block cINN inverse + decoder pass(es)" + (" + RCCL all-gather (overlapped)" if multi else ""),
+                       "global_batch": total, "per_gpu_batch": nb, "frames_per_step": frames_per_step,
+                       "parallelism": f"batch-shard x{world}"},
+            "value_is": ("THE METRIC (BASELINE.json: synthesized frames/sec, whole-job throughput over `steps` steps): " +
+                         ("pipelined stream rate -- `steps` cINN passes + `steps` decoder runs, the pass of step k+1 enqueued under the "
+                          "decoder of step k" if args.pipeline else "serial steps") +
+                         (".  `single_call` is SURVEY §8d(i)'s frames/s of ONE call (latency figure, not the metric); both are printed"
+                          if args.full else "")),
+        }
+
+    if not args.full:
+        line = None
+        if rank == 0:
+            result = headline()
+            validate_line(result, extras=False)
+            line = json.dumps(result)
+        return finish(line, multi, rank)
+
+    prof = gen.native().get_profile()
+    layers = gen.native().get_layer_profile()
+    gen.native().set_profile(False)
+    timed_sums = list(step_sums)
+    rank_ms = [dt_rank / args.steps * 1e3]
+    if multi:
         every = torch.zeros(world, dtype=torch.float64, device=dev)
         dist.all_gather_into_tensor(every, torch.tensor([dt_rank], dtype=torch.float64, device=dev))   # (reporting only)
         rank_ms = [float(v) / max(args.steps, 1) * 1e3 for v in every.tolist()]
-    frames_per_step = out.shape[0] * out.shape[1]
-    assert out.shape[0] == total, (out.shape, total)
     # the timed output must be a valid result, not just a fast one
     finite = bool(torch.isfinite(out).all())
     amax = float(out.abs().max())
@@ -331,7 +392,6 @@ def main():
                     "pipelined_latent_equals_serial": z_ok, "status_flags": flags}
     del ref_seq, od
 
-    nb = hi - lo
     single_ms = None if args.no_extras else single_call_ms()   # (every rank: the collation inside is a collective)
     if args.lean:
         args.sustain, args.no_exact, args.small_batch, args.no_cpu_baseline, args.no_config_128 = 0.0, True, 0, True, True
@@ -411,27 +471,7 @@ def main():
     if rank == 0:
         default_workload = args.config == "bair64" and nb == 64 and vid_length == 16
         result = {
-            "metric": "synthesized frames/sec (BxT): cINN inverse + VAE decoder",
-            "value": frames_per_step * args.steps / dt,
-            "unit": "frames/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": args.scaling,
-            "vs_baseline": None,
-            "dtype": "f32" if gen.mma == 0 else "f32 (split-fp16 MFMA: fp16 hi/lo operand pairs, 3 MFMAs per product, fp32 accumulate)" +
-                     ("; auto mode: per-layer fallback to exact fp32 behind the range guard, switched so far: %s" % gen.native().fallback_layers() if gen.mma == 2 else ""),
-            "data": "synthetic (seeded start frames / latents / embeddings, deterministic synthetic weights)",
-            "config": {"workload": f"{cfg['name']}, batch {nb}/GPU (global {total}), vid_length {vid_length}: "
-                                   "20-block cINN inverse + decoder pass(es)" + (" + RCCL all-gather (overlapped)" if multi else ""),
-                       "global_batch": total, "per_gpu_batch": nb, "frames_per_step": frames_per_step,
-                       "parallelism": f"batch-shard x{world}"},
-            "value_is": ("THE METRIC (BASELINE.json: synthesized frames/sec, whole-job throughput over `steps` steps): " +
-                         ("pipelined stream rate -- `steps` cINN passes + `steps` decoder runs, the pass of step k+1 enqueued under the "
-                          "decoder of step k" if args.pipeline else "serial steps") +
-                         ".  `single_call` is SURVEY §8d(i)'s frames/s of ONE call (latency figure, not the metric); both are printed"),
+            **headline(),
             "single_call": None if single_ms is None else {"ms": single_ms, "frames_per_s": frames_per_step / (single_ms * 1e-3),
                                                            "what": "ONE Model.synthesize-equivalent call, median of 3: the cINN pass on a side stream while the "
                                                                    "decoder's SPADE branches (start frame only) are computed, then the rest of the decoder"},
@@ -504,6 +544,11 @@ def main():
             write_per_layer(args.per_layer, layers, args.steps, gen.mma)
         validate_line(result, full=not multi and gen.mma != 0 and not (args.no_extras or args.no_cpu_baseline or args.no_exact or args.sustain < 10))
         line = json.dumps(result)
+    return finish(line if rank == 0 else None, multi, rank)
+
+
+def finish(line, multi, rank):
+    """Tear the process group down, then rank 0 prints its line."""
     if multi:
         dist.barrier()
     if dist.is_available() and dist.is_initialized():
@@ -513,6 +558,24 @@ def main():
         # at exit -- behind a line printed earlier), so the group is torn down and C stdio flushed first
         flush_c_stdio()
         print(line, flush=True)
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6   # --dump-outputs: at most this much in all
+DUMP_SAMPLE = 1 << 23           # elements drawn for the sample of a larger output (32 MiB of float32)
+
+
+def dump_outputs(path, out, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: the frames the last timed step produced, as a caller of the path receives them ([B, T, 3, H, W] float32), to
+    path/frames.npy.  An output above `limit` bytes goes to path/frames_sample.npy instead: the values at the sorted, distinct flat
+    indices among DUMP_SAMPLE draws of numpy's default_rng(0) -- the same elements in every run with the same arguments."""
+    os.makedirs(path, exist_ok=True)
+    out = out.detach()
+    if out.numel() * 4 <= limit:
+        np.save(os.path.join(path, "frames.npy"), out.float().cpu().numpy())
+        return
+    flat = out.reshape(-1)
+    idx = np.unique(np.random.default_rng(0).integers(0, flat.numel(), DUMP_SAMPLE))
+    np.save(os.path.join(path, "frames_sample.npy"), flat[torch.from_numpy(idx).to(flat.device)].float().cpu().numpy())
 
 
 class c_stdout_to_stderr:
@@ -549,14 +612,17 @@ LINE_KEYS_N1 = ("roofline", "roofline_all_conv3", "cpu_baseline", "single_call",
                 "rank_ms_per_step", "roofline_cinn", "output_check")
 
 
-def validate_line(r, full=True):
+def validate_line(r, full=True, extras=True):
     """Schema of the JSON line (the driver's contract + what the round-3 review asked the line to carry).  `full`: a default
-    N = 1 run with all extras; otherwise only the contract keys and the always-present extras are required."""
+    N = 1 run with all extras; otherwise only the contract keys and the always-present extras are required.  `extras=False`:
+    the line of a plain run (no --full), the contract keys alone."""
     for k, t in CONTRACT_KEYS.items():
         if k not in r or not isinstance(r[k], t):
             raise ValueError(f"bench line: key {k!r} missing or not {t.__name__}: {r.get(k)!r}")
     if "workload" not in r["config"]:
         raise ValueError("bench line: config.workload missing")
+    if not extras:
+        return True
     for k in ("roofline", "roofline_all_conv3", "steps_check", "value_is", "rank_ms_per_step", "output_check") + (LINE_KEYS_N1 if full else ()):
         if r.get(k) is None:
             raise ValueError(f"bench line: key {k!r} missing")
@@ -785,11 +851,11 @@ def projected_scaling(n, nb, frames_per_sample, big_single_ms, single_ms, big_pi
 
 def config_128_leg(args):
     """Second workload of the default line (round-5 review: three of five BASELINE configs had never been timed by the driver):
-    BASELINE configs[2], Landscape 128x128x16 nf = 32 E = 128, batch 32 -- run as a CHILD `bench.py --config land128 --lean` (its own
+    BASELINE configs[2], Landscape 128x128x16 nf = 32 E = 128, batch 32 -- run as a CHILD `bench.py --config land128 --full --lean` (its own
     process: its own handles and streams, this process idles meanwhile), 10 timed steps after 3 warm-ups, every step checksummed
     against a serial call, single call, dominant-kernel roofline and the g_4 rows of the per-layer table."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--config", "land128", "--steps", "10", "--warmup", "3", "--lean",
+    cmd = [sys.executable, os.path.abspath(__file__), "--config", "land128", "--steps", "10", "--warmup", "3", "--full", "--lean",
            "--side-stream", args.side_stream, "--pipeline", str(args.pipeline)]
     t0 = time.perf_counter()
     try:

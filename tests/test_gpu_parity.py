@@ -1553,7 +1553,7 @@ def test_bench_multi_gpu_code_paths_on_one_gpu():
     from conftest import REPO
     port = str(29500 + (os.getpid() * 7) % 2000)
     env = dict(os.environ, I2V_BENCH_FORCE_MULTI="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=port, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--batch", "4", "--steps", "3", "--warmup", "1", "--lean"],
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--batch", "4", "--steps", "3", "--warmup", "1", "--full", "--lean"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.strip()]
@@ -1561,6 +1561,44 @@ def test_bench_multi_gpu_code_paths_on_one_gpu():
     line = json.loads(lines[0])
     assert line["ranks_seen"] == 1 and line["rccl_version"] and len(line["rank_ms_per_step"]) == 1
     assert line["streams"]["collation_stream"] == "the cINN prefetch stream" and line["steps_check"]["all_bit_identical_to_serial_reference"]
+
+
+def test_bench_plain_run_dumps_its_outputs(tmp_path):
+    """A plain `bench.py` run (no --full): one JSON line with the contract keys and nothing the --full line adds, `steps` timed steps,
+    and with --dump-outputs the last timed step's frames, which must be what a serial cINN inverse + decoder call computes on the
+    bench's seeded inputs and weights."""
+    import json
+    import subprocess
+    import sys
+    from conftest import REPO
+    from stage1_VAE.modules.decoder import Generator
+    from stage2_cINN.modules.flow_blocks import ConditionalFlow
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--batch", "4", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    lines = [ln for ln in r.stdout.decode().splitlines() if ln.strip()]
+    assert len(lines) == 1, lines[:6]
+    line = json.loads(lines[0])
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["unit"] == "frames/s" and line["higher_is_better"] is True
+    frames = line["config"]["frames_per_step"]
+    assert frames == 4 * 16 and abs(line["value"] * line["ms_per_step"] * 1e-3 - frames) < 1e-6 * frames
+    assert not {"roofline", "steps_check", "single_call", "cpu_baseline", "sustained"} & set(line)
+    seq = np.load(tmp_path / "frames.npy")
+    assert seq.dtype == np.float32 and seq.shape == (4, 16, 3, 64, 64)
+    torch.set_grad_enabled(False)
+    dev = torch.device("cuda:0")
+    fsd = {k: torch.from_numpy(np.asarray(v)) for k, v in synth.flow_state_dict(seed=7, embedding_dim=64).items()}
+    dsd = {k: torch.from_numpy(np.asarray(v)) for k, v in synth.decoder_state_dict(seed=7, channel_factor=64).items()}
+    flow = ConditionalFlow(64, 64, 512, 2, 20, conditioning_option="None")
+    flow.load_state_dict(fsd)
+    gen = Generator({"channel_factor": 64, "z_dim": 64, "upsample_s": [2, 1], "upsample_t": [2, 1], "spectral_norm": True})
+    gen.load_state_dict(dsd)
+    flow, gen = flow.to(dev).eval(), gen.to(dev).eval()
+    x0, residual, embed = synth.bench_inputs(4, 64, 64)
+    z = flow(residual.to(dev), embed.to(dev), reverse=True).view(4, -1)
+    ref = gen.decode_sequence(x0.to(dev), z, 16).cpu().numpy()
+    err = rel_l2(seq, ref)
+    assert err < 1e-6, f"dumped frames vs a serial call: rel-L2 {err:.3e}"
 
 
 def test_smoke_entry():

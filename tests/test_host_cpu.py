@@ -292,6 +292,48 @@ def test_bench_line_schema():
     for path in sorted(glob.glob(os.path.join(REPO, "profiles", "r04_*_bench_bair64.json")))[-1:]:
         with open(path) as f:
             assert bench.validate_line(json.loads(f.read().strip().splitlines()[-1]))
+    # a plain run (no --full) prints the contract keys alone; a missing one still fails
+    plain = {k: line[k] for k in bench.CONTRACT_KEYS}
+    assert bench.validate_line(plain, extras=False)
+    with pytest.raises(ValueError):
+        bench.validate_line(plain)
+    for k in ("ms_per_step", "value", "dtype"):
+        bad = copy.deepcopy(plain)
+        bad.pop(k)
+        with pytest.raises(ValueError):
+            bench.validate_line(bad, extras=False)
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs: the whole output as float32 frames.npy while it fits the limit; above it a seeded sample that is the same
+    from run to run and holds the output's own values."""
+    import importlib.util
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(REPO, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    out = torch.linspace(-1, 1, 2 * 16 * 3 * 4 * 4).reshape(2, 16, 3, 4, 4)
+    bench.dump_outputs(str(tmp_path / "a"), out)
+    full = np.load(tmp_path / "a" / "frames.npy")
+    assert full.dtype == np.float32 and full.shape == (2, 16, 3, 4, 4) and np.array_equal(full, out.numpy())
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), out, limit=1024)
+        assert not (tmp_path / d / "frames.npy").exists()
+    s1, s2 = np.load(tmp_path / "b" / "frames_sample.npy"), np.load(tmp_path / "c" / "frames_sample.npy")
+    assert s1.dtype == np.float32 and np.array_equal(s1, s2) and 0 < s1.size <= out.numel()
+    assert np.isin(s1, out.numpy().ravel()).all()
+    assert bench.DUMP_SAMPLE * 4 <= bench.DUMP_LIMIT_BYTES
+
+
+def test_bench_rejects_full_only_options_without_full():
+    """The options that shape the --full line's extra measurements are refused on a plain run (they would do nothing there), and
+    --steps must set a real number of timed steps; both are decided before any GPU work."""
+    import subprocess
+    import sys
+    for extra in (["--lean"], ["--no-extras"], ["--per-layer", "x.csv"], ["--live-traffic"], ["--steps", "0"]):
+        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1"] + extra, capture_output=True, text=True,
+                           timeout=120)
+        assert r.returncode == 2 and "error" in r.stderr, (extra, r.returncode, r.stderr[-400:])
 
 
 def test_winograd_kernel_keeps_its_hand_counted_waits_valid(tmp_path):

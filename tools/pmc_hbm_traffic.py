@@ -18,7 +18,7 @@ import sys
 def one_pass(outdir, counter, extra, parse_only):
     d = os.path.join(outdir, counter.lower())
     cmd = ["rocprofv3", "--pmc", counter, "--kernel-trace", "--output-format", "csv", "-d", d, "-o", "pmc", "--",
-           sys.executable, "bench.py", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-extras"] + extra
+           sys.executable, "bench.py", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", "--no-extras"] + extra
     if not parse_only:
         env = dict(os.environ, TMPDIR="/tmp")
         with open(os.path.join(outdir, counter.lower() + ".log"), "w") as log:

@@ -1,5 +1,5 @@
 """Idle gaps of the main queue inside ONE steady-state step of the pipelined bench loop (run on the GPU box):
-    rocprofv3 --kernel-trace --output-format csv -d <dir> -o t -- python bench.py --steps 4 --warmup 2 --lean
+    rocprofv3 --kernel-trace --output-format csv -d <dir> -o t -- python bench.py --steps 4 --warmup 2 --full --lean
     python tools/step_gaps.py <dir> [min_gap_us]
 The step = the window between the ends of the last two conv_img launches (one per decoder pass).  Prints, per hardware queue, the summed
 kernel time inside the window, the main queue's busy fraction, and every gap of the main queue above min_gap_us with the launches on

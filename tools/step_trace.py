@@ -1,5 +1,5 @@
 """Per-launch durations of the decoder kernels of ONE bench step (run on the GPU box):
-    rocprofv3 --kernel-trace --output-format csv -d <dir> -o t -- python bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-extras
+    rocprofv3 --kernel-trace --output-format csv -d <dir> -o t -- python bench.py --steps 1 --warmup 1 --full --no-cpu-baseline --no-extras
     python tools/step_trace.py <dir> [min_us]"""
 import csv, glob, sys
 d = sys.argv[1]
