@@ -1131,7 +1131,7 @@ int block_forward(i2v_dec* d, int k, Block& b, const Level& l, const float* x, f
     if (!f0 && !g0 && (rc = tap(k, 1, a, (size_t)B * (tdup ? P / 2 : P) * b.n_in))) return rc;
     const bool fuse = f16_0 && conv16_can_fuse_stats(tdup ? l.T / 2 : l.T, l.H, l.W);
     d->prof_cur_layer = 2 * k;
-    d->prof_cur_kernel = g0 ? 4 : q0 ? 3 : w0 ? 2 : (f16_0 ? 1 : 0);
+    d->prof_cur_kernel = g0 ? 4 : q0 ? 3 : w0 ? 2 : f16_0 ? 1 : f0 ? 5 : 0;
     if (g0) rc = conv3_w4g(d, b.conv0_w4, x, coef, gb, 2, dx, nullptr, 1, 1, B, l, EPI_NONE, st, fuse ? sums2 : nullptr, flag, um0);
     else if (f0) rc = conv3_wf(d, b.conv0_wf, a, w.m6, dx, nullptr, 1, 1, B, l, EPI_NONE, st);
     else if (q0) rc = conv3_w4(d, b.conv0_w4, a, dx, nullptr, 1, 1, B, l, EPI_NONE, st, fuse ? sums2 : nullptr);
@@ -1171,7 +1171,7 @@ int block_forward(i2v_dec* d, int k, Block& b, const Level& l, const float* x, f
     // statistics of the block OUTPUT = the next block's input)
     const bool fuse_out = f16_1 && conv16_can_fuse_stats(l.T, l.H, l.W) && !last;
     d->prof_cur_layer = 2 * k + 1;
-    d->prof_cur_kernel = g1 ? 4 : q1 ? 3 : w1 ? 2 : (f16_1 ? 1 : 0);
+    d->prof_cur_kernel = g1 ? 4 : q1 ? 3 : w1 ? 2 : f16_1 ? 1 : f1 ? 5 : 0;
     if (g1) rc = conv3_w4g(d, b.conv1_w4, dx, coef, nullptr, 1, xn, res, l.ut, l.us, B, l, last ? EPI_LRELU : EPI_NONE, st, fuse_out ? sums_out : nullptr, flag, um1);
     else if (f1) rc = conv3_wf(d, b.conv1_wf, a, w.m6, xn, res, l.ut, l.us, B, l, last ? EPI_LRELU : EPI_NONE, st);
     else if (q1) rc = conv3_w4(d, b.conv1_w4, a, xn, res, l.ut, l.us, B, l, last ? EPI_LRELU : EPI_NONE, st, fuse_out ? sums_out : nullptr);
@@ -1888,6 +1888,9 @@ int i2v_gblock_create(int32_t n_in, int32_t n_out, int32_t z_dim, int32_t spectr
     I2V_REQUIRE(out && n_in > 0 && n_out > 0 && n_in % 8 == 0 && n_out % 8 == 0 && n_in <= 1024 && n_out <= 1024, I2V_E_INVALID,
                 "i2v_gblock_create: channel counts must be multiples of 8 in [8, 1024]");
     I2V_REQUIRE(z_dim > 0 && z_dim % 4 == 0 && (mma == 0 || mma == 1), I2V_E_INVALID, "i2v_gblock_create: bad z_dim / mma");
+    // the learned shortcut's Norm3D is GroupNorm(16, n_in) (normalization_layer.py:31), which needs n_in % 16 == 0
+    I2V_REQUIRE(n_in == n_out || n_in % 16 == 0, I2V_E_INVALID,
+                "i2v_gblock_create: a learned shortcut needs n_in %% 16 == 0 (GroupNorm(16, n_in)), got n_in %d", n_in);
     int ndev = 0;
     I2V_HIP_CHECK(hipGetDeviceCount(&ndev));
     I2V_REQUIRE(ndev > 0, I2V_E_HIP, "i2v_gblock_create: no HIP device");
@@ -2072,7 +2075,8 @@ int i2v_gblock_norm(i2v_gblock* g, int32_t part, const float* x, const float* co
         if ((rc = run_coef(sums, coef, B, C, C, (double)P, F(L.zl), 2 * b.n_mid, 0, nullptr, nullptr, st))) return rc;
         if ((rc = run_modulate(x_cl, coef, nullptr, a, B, t, h, w, C, 1, 1, 0, st))) return rc;
     } else {                // Norm3D.forward(x), normalization_layer.py:33-35
-        I2V_REQUIRE(g->has_norm_s && C % 16 == 0, I2V_E_STATE, "i2v_gblock_norm: Norm3D weights not loaded or C %% 16 != 0");
+        I2V_REQUIRE(C % 16 == 0, I2V_E_INVALID, "i2v_gblock_norm: Norm3D is GroupNorm(16, C), needs C %% 16 == 0, got %d", C);
+        I2V_REQUIRE(g->has_norm_s, I2V_E_STATE, "i2v_gblock_norm: Norm3D weights not loaded");
         if ((rc = run_coef(sums, coef, B, C, 16, (double)P, nullptr, 0, 0, b.gn_w.as<float>(), b.gn_b.as<float>(), st))) return rc;
         if ((rc = run_modulate(x_cl, coef, nullptr, a, B, t, h, w, C, 1, 1, 0, st))) return rc;
     }

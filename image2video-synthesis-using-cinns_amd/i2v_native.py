@@ -343,6 +343,9 @@ class NativeDecoder(_Handle):
                "i2v_dec_get_profile")
         return {"conv3_ms": a.value, "conv3_flops": b.value, "conv3_mfma_flops": e.value, "conv3_launches": c.value}
 
+    # i2v_dec_get_layer_profile's kernel code -> name
+    KERNEL_NAMES = ("conv_mfma_f32", "conv_mfma_f16x3", "conv_wino_f16x3", "conv_wino4_f16x3", "conv_wino4g_f16x3", "conv_wino4_f32")
+
     @_on_device
     def get_layer_profile(self):
         """Per-layer totals of the profiled 3x3x3 conv launches since set_profile(True) (i2v_dec_get_layer_profile)."""
@@ -353,7 +356,7 @@ class NativeDecoder(_Handle):
             _check(lib().i2v_dec_get_layer_profile(self._h, layer, name, 48, ctypes.byref(ms), ctypes.byref(fl), ctypes.byref(ex),
                                                    ctypes.byref(n), ctypes.byref(k)), "i2v_dec_get_layer_profile")
             if n.value:
-                rows.append({"layer": name.value.decode(), "kernel": ("conv_mfma_f32", "conv_mfma_f16x3", "conv_wino_f16x3", "conv_wino4_f16x3", "conv_wino4g_f16x3")[k.value],
+                rows.append({"layer": name.value.decode(), "kernel": self.KERNEL_NAMES[k.value],
                              "launches": int(n.value), "ms": ms.value, "flops": fl.value, "mfma_flops": ex.value})
         return rows
 
@@ -625,9 +628,11 @@ class NativeGBlock(_Handle):
 
     def __init__(self, n_in, n_out, z_dim, spectral_norm=True, mma=None, device=None):
         h = c_void_p()
+        mma = default_mma() if mma is None else parse_mma(mma)
+        if mma == 2:   # auto: a stand-alone block has no re-run loop behind the range guard; it runs split-fp16 (status() reports)
+            mma = 1
         with self._bind(device):
-            _check(lib().i2v_gblock_create(n_in, n_out, z_dim, int(bool(spectral_norm)), default_mma() if mma is None else mma,
-                                           ctypes.byref(h)), "i2v_gblock_create")
+            _check(lib().i2v_gblock_create(n_in, n_out, z_dim, int(bool(spectral_norm)), mma, ctypes.byref(h)), "i2v_gblock_create")
         self._h = h
         self.n_in, self.n_out, self.n_mid, self.z_dim = n_in, n_out, min(n_in, n_out), z_dim
         self._ws = _Workspace()

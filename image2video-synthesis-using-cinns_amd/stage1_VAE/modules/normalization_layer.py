@@ -39,6 +39,8 @@ class Norm3D(NativeBacked):
         super().__init__()
         if num_groups != 16:
             raise NotImplementedError("Norm3D: the decoder only uses 16 groups")
+        if num_features % num_groups != 0:   # nn.GroupNorm(16, C) raises the same
+            raise ValueError(f"Norm3D: num_channels ({num_features}) must be divisible by num_groups ({num_groups})")
         self.num_features = num_features
         self.bn = AffineParams(num_features)
 

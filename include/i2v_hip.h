@@ -218,7 +218,9 @@ int i2v_dec_fallback_layers(i2v_dec* d, int32_t* mask, int32_t* reruns);
 int i2v_dec_set_profile(i2v_dec* d, int32_t on);
 int i2v_dec_get_profile(i2v_dec* d, double* conv3_ms, double* conv3_flops, double* conv3_mfma_flops, int64_t* conv3_launches);
 /* The same totals per layer: layer = 2 * block + {0: conv_0, 1: conv_1}, block 0..5 = head_0, g_0 .. g_4 (decoder.py:74-79).
- * name receives "<block>.conv_<i>"; kernel: 0 = fp32 MFMA implicit GEMM, 1 = split-fp16 direct, 2 = split-fp16 Winograd. */
+ * name receives "<block>.conv_<i>"; kernel: 0 = exact-fp32 MFMA implicit GEMM (direct), 1 = split-fp16 direct, 2 = split-fp16
+ * Winograd F(2,3), 3 = split-fp16 Winograd F(4,3), 4 = split-fp16 F(4,3) with the operand generated in the kernel,
+ * 5 = exact-fp32 Winograd F(4,3). */
 int i2v_dec_get_layer_profile(i2v_dec* d, int32_t layer, char* name, int32_t name_len, double* ms, double* flops,
                               double* mfma_flops, int64_t* launches, int32_t* kernel);
 /* Test hook: during the next forwards copy up to max_floats of one channels-last intermediate of GeneratorBlock
@@ -247,6 +249,8 @@ int i2v_dec_debug_tap(i2v_dec* d, int32_t block, int32_t which, float* dst, size
  * T, H, W must be powers of two (>= 1) so the convolutions tile into bricks.
  * ---------------------------------------------------------------------------------------- */
 typedef struct i2v_gblock i2v_gblock;
+/* mma: 0 (exact fp32) or 1 (split-fp16); a block has no re-run loop, so there is no auto mode.  A learned shortcut (n_in != n_out)
+ * needs n_in % 16 == 0: its Norm3D is GroupNorm(16, n_in).  Both return I2V_E_INVALID otherwise. */
 int i2v_gblock_create(int32_t n_in, int32_t n_out, int32_t z_dim, int32_t spectral_norm, int32_t mma, i2v_gblock** out);
 void i2v_gblock_destroy(i2v_gblock* g);
 /* Keys relative to the block: conv_{0,1,s}.*, norm_0.{conv,conv_gamma,conv_beta}.*, norm_1.linear.*, norm_s.bn.*.

@@ -1010,7 +1010,7 @@ def test_full_size_bair_b8_every_row_vs_oracle():
     x0, residual, _ = synth.bench_inputs(8, 64, 64)
     out = gen(x0.cuda(), residual.cuda())
     assert out.shape == (8, 16, 3, 64, 64) and bool(torch.isfinite(out).all()) and float(out.abs().max()) <= 1.0
-    torch.set_num_threads(min(os.cpu_count() or 1, 64))
+    torch.set_num_threads(min(os.cpu_count() or 1, 16))
     ref = decoder_ref.generator(decoder_ref.fold_spectral_norm(sd), x0, residual, faithful=False)
     for b in range(8):
         assert rel_l2(out[b].cpu(), ref[b]) < TOL, b
@@ -1037,7 +1037,7 @@ def test_cfg1_exact_inputs_vs_oracle():
     x0, residual, embed = synth.bench_inputs(4, 64, 64)
     z = flow(residual.cuda(), embed.cuda(), reverse=True).view(4, -1)
     seq = gen(x0.cuda(), z)
-    torch.set_num_threads(min(os.cpu_count() or 1, 64))
+    torch.set_num_threads(min(os.cpu_count() or 1, 16))
     ref = model_ref.synthesize(fsd, dsd, x0, residual, embed, 16, (2, 1), (2, 1), faithful=True)
     assert seq.shape == tuple(ref.shape) == (4, 16, 3, 64, 64)
     for b in range(4):

@@ -573,3 +573,20 @@ def test_every_environment_switch_is_documented():
     doc = open(os.path.join(REPO, "INTEGRATION.md")).read()
     missing = sorted(n for n in names if n not in doc)
     assert not missing, missing
+
+
+def test_mirror_refuses_a_norm3d_without_16_groups():
+    """Norm3D is GroupNorm(16, C) in the reference (normalization_layer.py:31): nn.GroupNorm raises for C % 16 != 0, and so does the
+    mirror -- before a native handle exists.  A GeneratorBlock with a learned shortcut from 24 channels therefore cannot be built
+    (it used to build, and its native shortcut read group totals that were never written for channels 16..23)."""
+    from stage1_VAE.modules import decoder as dec, normalization_layer as nl
+    with pytest.raises(ValueError):
+        torch.nn.GroupNorm(16, 24)
+    with pytest.raises(ValueError):
+        nl.Norm3D(24)
+    with pytest.raises(ValueError):
+        dec.GeneratorBlock(24, 8, True, 64)
+    assert nl.Norm3D(48).num_features == 48
+    blk = dec.GeneratorBlock(24, 24, True, 64)   # identity shortcut: no Norm3D; SPADE uses 12 groups
+    assert not blk.learned_shortcut and blk.norm_0.num_groups == 12
+    assert dec.GeneratorBlock(48, 24, True, 64).norm_s.num_features == 48

@@ -156,3 +156,44 @@ def test_motion_encoder(name):
     sd = T(synth.encoder3d_state_dict(**a))
     mu, logvar = encoder_ref.encoder(sd, golden_clip(meta, g), a["channels"], a["stride_s"], meta["stride_t"])
     assert rel_l2(mu, g["mu"]) < TOL and rel_l2(logvar, g["logvar"]) < TOL
+
+
+def test_generator_taps_are_the_generator_block_by_block():
+    """oracle.decoder_ref.generator_taps (the per-layer oracle of the decoder's debug-tap tests): in fp32 its frames are
+    generator(faithful=False)'s bit for bit, each block's output tap is the next block's input (re-running a block on the
+    up-sampled previous tap gives the same bits), its shortcut tap is the low-resolution shortcut, and given float64 tensors it
+    runs in float64 throughout."""
+    import torch.nn.functional as F
+    ups, upt = (2, 1), (1, 2)
+    sd = decoder_ref.fold_spectral_norm(T(synth.decoder_state_dict(seed=9, channel_factor=8)))
+    img = 2 * torch.rand(2, 3, 24, 40, generator=torch.Generator().manual_seed(3)) - 1
+    z = torch.randn(2, 64, generator=torch.Generator().manual_seed(4))
+    taps, frames = decoder_ref.generator_taps(sd, img, z, ups, upt)
+    ref = decoder_ref.generator(sd, img, z, ups, upt, faithful=False)
+    assert frames.dtype == torch.float32 and torch.equal(frames, ref)
+    scales = decoder_ref._scales(ups, upt)
+    shapes = ((1, 4), (2, 8), (4, 16), (8, 32), (8, 64), (16, 64))   # (T, H = W) of each block
+    for k, name in enumerate(decoder_ref.BLOCKS):
+        t = taps[k]
+        nin, nout = sd[name + ".conv_0.weight"].shape[1], sd[name + ".conv_1.weight"].shape[0]
+        (Tk, Hk) = shapes[k]
+        assert t[0].shape == (2, Hk, Hk, 2 * nin) and t[5].shape == (2, Tk, Hk, Hk, nout)
+        assert (4 in t) == (nin != nout)
+        if k == 0:
+            continue
+        x = F.interpolate(t_ncdhw(taps[k - 1][5]), scale_factor=scales[k])
+        inter = {}
+        out = decoder_ref.generator_block(sd, name, x, z, img, faithful=False, taps=inter)
+        assert torch.equal(decoder_ref._cl(out), t[5]) and torch.equal(decoder_ref._cl(inter[2]), t[2])
+        if 4 in t:   # the shortcut commutes with the nearest up-sampling
+            xs = F.interpolate(t_ncdhw(t[4]), scale_factor=scales[k])
+            dx = F.conv3d(t_ncdhw(t[3]), sd[name + ".conv_1.weight"], sd[name + ".conv_1.bias"], 1, 1)
+            assert rel_l2(xs, out - dx) < 1e-6
+    sd64 = {k: v.double() for k, v in T(synth.decoder_state_dict(seed=9, channel_factor=8)).items()}
+    taps64, frames64 = decoder_ref.generator_taps(sd64, img.double(), z.double(), ups, upt)
+    assert frames64.dtype == torch.float64 and all(v.dtype == torch.float64 for t in taps64 for v in t.values())
+    assert rel_l2(frames64, frames) < 1e-5
+
+
+def t_ncdhw(x):
+    return x.permute(0, 4, 1, 2, 3).contiguous()

@@ -14,7 +14,6 @@ sys.path.insert(0, os.path.join(REPO, "image2video-synthesis-using-cinns_amd"))
 import i2v_native as native  # noqa: E402
 import i2v_synth as synth  # noqa: E402
 from oracle import decoder_ref, flow_ref  # noqa: E402
-import torch.nn.functional as F  # noqa: E402
 
 torch.set_grad_enabled(False)
 dev = torch.device("cuda:0")
@@ -59,33 +58,6 @@ def diag_flow():
                 print(f"  {tag} round-trip max-abs {float((rt.cpu() - x).abs().max()):.3e}")
 
 
-def oracle_blocks(sd, img, z, ups, upt):
-    """Block-by-block oracle outputs (NCDHW) incl. intermediates of each block."""
-    b = img.size(0)
-    x = F.linear(z, sd["fc.weight"], sd["fc.bias"]).reshape(b, -1, 1, 4, 4)
-    outs = []
-    scales = [None, 2, 2, 2, (upt[0], ups[0], ups[0]), (upt[1], ups[1], ups[1])]
-    for k, name in enumerate(("head_0", "g_0", "g_1", "g_2", "g_3", "g_4")):
-        if scales[k] is not None:
-            x = F.interpolate(x, scale_factor=scales[k])
-        p = name + "."
-        inter = {}
-        a0 = F.leaky_relu(decoder_ref.spade(sd, p + "norm_0.", x, img, faithful=False), 0.2)
-        inter[1] = a0
-        dx = F.conv3d(a0, decoder_ref.sn_weight(sd, p + "conv_0"), sd[p + "conv_0.bias"], 1, 1)
-        inter[2] = dx
-        a1 = F.leaky_relu(decoder_ref.adain(sd, p + "norm_1.", dx, z), 0.2)
-        inter[3] = a1
-        x = decoder_ref.generator_block(sd, name, x, z, img, faithful=False)
-        inter[5] = x
-        outs.append(inter)
-    return outs
-
-
-def cl(x):  # NCDHW -> channels-last flat
-    return x.permute(0, 2, 3, 4, 1).contiguous()
-
-
 def diag_decoder(nf, ups, upt, img_size, B, seed=5, taps=True, mma=0, oracle=True):
     print(f"== decoder nf={nf} ups={ups} img={img_size} B={B} mma={mma}")
     sd = T(synth.decoder_state_dict(seed=seed, channel_factor=nf))
@@ -107,11 +79,10 @@ def diag_decoder(nf, ups, upt, img_size, B, seed=5, taps=True, mma=0, oracle=Tru
         report("final frames vs fp32-MFMA path", out, h0.forward(img_d, z_d))
         del h0
     if taps:
-        folded = decoder_ref.fold_spectral_norm(sd)
-        blocks = oracle_blocks(folded, img, z, ups, upt)
+        blocks, _ = decoder_ref.generator_taps(decoder_ref.fold_spectral_norm(sd), img, z, ups, upt)
         for k in range(6):
             for which, nm in (((1, "lrelu(spade)"), (2, "conv_0"), (3, "lrelu(adain)"), (5, "block out")) if mma == 0 else ((2, "conv_0"), (5, "block out"))):
-                r = cl(blocks[k][which])
+                r = blocks[k][which]
                 dst = torch.zeros(r.numel(), dtype=torch.float32, device=dev)
                 h.debug_tap(k, which, dst)
                 h.forward(img_d, z_d)
