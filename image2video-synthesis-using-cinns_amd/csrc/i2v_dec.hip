@@ -415,22 +415,28 @@ __device__ __forceinline__ void mod_pos4_eval(const ModPos4<GB>& m, const float*
     }
 }
 
-template <bool GB>
+// ONE (mma = 3, the one-term operand of conv_wino4_f16_kernel, i2v_conv16w4h.hip): the same values, rounded to fp16 once -- exactly the
+// hi parts the split writer stores -- into [B][T][CinPad/32][6][H][J][32 channels = 64 B], pieces c0-7 | c16-23 | c8-15 | c24-31 of the
+// 32-channel chunk.  The thread mapping stays that of 16-channel chunks: chunk16 = 2 chunk32 + e writes the 8-byte half-piece
+// (q >> 1) * 32 + e * 16 + (q & 1) * 8 of its row.  C is then CinPad: the chunks at and above the tensor's own channels (Cx) hold zeros.
+// The range guard is the split writer's: bit 0 for |V| > 65504 or non-finite values, the maximum |activation| into the layer's slot.
+template <bool GB, bool ONE = false>
 __global__ __launch_bounds__(256) void modulate_wino4_kernel(const float* __restrict__ x, const float2* __restrict__ coef,
                                                              const float* __restrict__ gb, char* __restrict__ out, int T, int H,
                                                              int W, int C, int ut, int us, int lrelu, int* __restrict__ range_flag,
-                                                             int* __restrict__ umax) {
+                                                             int* __restrict__ umax, int Cx = 0) {
     bool bad = false;
     float vmax = 0.f;
+    if constexpr (!ONE) Cx = C;
     const int C4 = C >> 2, J = W >> 2;
     const int b = blockIdx.y;
     const int per = H * J * C4;        // threads per sample (a multiple of 64: whole waves stay active for the shuffles)
     const int Hl = H / us, Wl = W / us, Tl = T / ut;
-    const float2* cp0 = coef ? coef + (long)b * C : nullptr;
-    const float* xb = x + (long)b * Tl * Hl * Wl * C;
-    const float* gbb = GB ? gb + (long)b * H * W * 2 * C : nullptr;
+    const float2* cp0 = coef ? coef + (long)b * Cx : nullptr;
+    const float* xb = x + (long)b * Tl * Hl * Wl * Cx;
+    const float* gbb = GB ? gb + (long)b * H * W * 2 * Cx : nullptr;
     const int nchunk = C >> 4;
-    const long xstride = (long)Hl * Wl * C;
+    const long xstride = (long)Hl * Wl * Cx;
     const int lane = threadIdx.x & 63, jj = lane >> 2;   // jj: position of the tile inside the wave's 16-tile segment
     for (int i = blockIdx.x * 256 + threadIdx.x; i < per; i += gridDim.x * 256) {
         // i = ((h * nchunk + chunk) * J + j) * 4 + q
@@ -442,9 +448,13 @@ __global__ __launch_bounds__(256) void modulate_wino4_kernel(const float* __rest
         const int chunk = q % nchunk;
         const int h = q / nchunk;
         const int c4 = chunk * 4 + q4;
+        // (ONE: the padding channels at and above Cx are zeros.  Their threads evaluate channel group 0 of the position -- values a
+        //  live thread evaluates too, so the range guard sees nothing new -- and store zeros.)
+        const bool live = !ONE || 4 * c4 < Cx;
+        const int c4x = ONE && !live ? 0 : c4;
         float ca[4], cb[4];
         if (cp0) {
-            const float4* cp = reinterpret_cast<const float4*>(cp0 + 4 * c4);
+            const float4* cp = reinterpret_cast<const float4*>(cp0 + 4 * c4x);
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
                 const float4 ab = cp[k];
@@ -455,20 +465,21 @@ __global__ __launch_bounds__(256) void modulate_wino4_kernel(const float* __rest
             for (int k = 0; k < 4; ++k) { ca[k] = 1.f; cb[k] = 0.f; }
         }
         ModPos4<GB> m1, m2, m3, m4, me;
-        mod_pos4_init<GB>(m1, ca, cb, xb, gbb, h, 4 * j, W, C, c4, us, Wl);
-        mod_pos4_init<GB>(m2, ca, cb, xb, gbb, h, 4 * j + 1, W, C, c4, us, Wl);
-        mod_pos4_init<GB>(m3, ca, cb, xb, gbb, h, 4 * j + 2, W, C, c4, us, Wl);
-        mod_pos4_init<GB>(m4, ca, cb, xb, gbb, h, 4 * j + 3, W, C, c4, us, Wl);
+        mod_pos4_init<GB>(m1, ca, cb, xb, gbb, h, 4 * j, W, Cx, c4x, us, Wl);
+        mod_pos4_init<GB>(m2, ca, cb, xb, gbb, h, 4 * j + 1, W, Cx, c4x, us, Wl);
+        mod_pos4_init<GB>(m3, ca, cb, xb, gbb, h, 4 * j + 2, W, Cx, c4x, us, Wl);
+        mod_pos4_init<GB>(m4, ca, cb, xb, gbb, h, 4 * j + 3, W, Cx, c4x, us, Wl);
         // own positions w = 4j .. 4j+3; the outer neighbours 4j - 1 / 4j + 4 come from lane -+ 4 unless this tile opens / closes the
         // wave's segment (then they are evaluated here) or the row (then they are 0: the conv's zero padding)
         const bool left_row = j == 0, right_row = j == J - 1;
         const bool left_own = !left_row && jj == 0, right_own = !right_row && jj == 15;
         me = m1;
-        if (left_own || right_own) mod_pos4_init<GB>(me, ca, cb, xb, gbb, h, left_own ? 4 * j - 1 : 4 * j + 4, W, C, c4, us, Wl);
+        if (left_own || right_own) mod_pos4_init<GB>(me, ca, cb, xb, gbb, h, left_own ? 4 * j - 1 : 4 * j + 4, W, Cx, c4x, us, Wl);
         float d0[4], d1[4], d2[4], d3[4], d4[4], d5[4], de[4];
         // V row of (t, chunk, plane, h, j): 64 bytes [hi c0-7 | lo c0-7 | hi c8-15 | lo c8-15]; this thread's channels 4 q4 .. 4 q4 + 3
-        char* ob = out + ((((long)b * T * nchunk + chunk) * 6 * H + h) * J + j) * 64 + (q4 >> 1) * 32 + (q4 & 1) * 8;
-        const long ostride_x = (long)H * J * 64, ostride_t = (long)nchunk * 6 * ostride_x;
+        const int nrow = ONE ? nchunk >> 1 : nchunk, crow = ONE ? chunk >> 1 : chunk;   // chunks of the V rows
+        char* ob = out + ((((long)b * T * nrow + crow) * 6 * H + h) * J + j) * 64 + (q4 >> 1) * 32 + (q4 & 1) * 8 + (ONE ? (chunk & 1) * 16 : 0);
+        const long ostride_x = (long)H * J * 64, ostride_t = (long)nrow * 6 * ostride_x;
         for (int t = 0; t < T; ++t) {
             if (t % ut == 0) {
                 const long toff = (long)(t / ut) * xstride;
@@ -501,6 +512,11 @@ __global__ __launch_bounds__(256) void modulate_wino4_kernel(const float* __rest
                     bad |= !(fabsf(v) <= 65504.f);
                     ph[c] = hh;
                     pl[c] = (_Float16)(v - (float)hh);
+                }
+                if constexpr (ONE) {
+                    if (!live) ph = half4_t{0, 0, 0, 0};
+                    *reinterpret_cast<half4_t*>(o + xq * ostride_x) = ph;
+                    continue;
                 }
 #ifdef MOD_NT
                 __builtin_nontemporal_store(ph, reinterpret_cast<half4_t*>(o + xq * ostride_x));
@@ -634,6 +650,7 @@ struct Block {
     Wino4Weights sp_gb_w4;      // ... on the F(4,3) kernel (packed INSTEAD where the shape allows: W % 16 == 0, H % 32 == 0)
     Wino16Weights conv0_w, conv1_w;             // Winograd F(2,3) variants of conv_0 / conv_1 (packed where the shape allows)
     Wino4Weights conv0_w4, conv1_w4;            // Winograd F(4,3) variants (i2v_conv16w4.hip); packed INSTEAD of the F(2,3) ones
+    Wino4hWeights conv0_w4h, conv1_w4h;         // one-term fp16 mode (mma = 3): the F(4,3) convs on fp16 operands (i2v_conv16w4h.hip), packed INSTEAD of conv0_w4 / conv1_w4
     Wino4F32Weights conv0_wf, conv1_wf;         // exact-fp32 mode: Winograd F(4,3) on the fp32 matrix cores (i2v_wino32.hip), next to conv0 / conv1
     bool tdup0 = false;                          // conv_0 runs on the half-rate tensor (x2 temporal up-sampling in front)
     DevBuf gn_w, gn_b;
@@ -701,8 +718,11 @@ struct i2v_dec {
     bool fp32_layer[12] = {};   // layer = 2 * block + (0: conv_0, 1: conv_1)
     bool fp32_all = false;
     int auto_reruns = 0;        // forwards that had to be run again (reporting)
+    // mma = 3 ("fp16"): the launches of mma = 1, except that the 3x3x3 block convs on the F(4,3) kernel run its one-term form
+    // (conv_wino4_f16_kernel: fp16 operands, one MFMA per product) on the one-term operand (modulate_wino4_kernel<GB, true>)
     bool has16() const { return cfg.mma != 0; }                       // split-fp16 weights are packed
-    bool has32() const { return cfg.mma != 1; }                       // exact-fp32 weights are packed
+    bool has32() const { return cfg.mma == 0 || cfg.mma == 2; }       // exact-fp32 weights are packed
+    bool one16() const { return cfg.mma == 3; }                       // the F(4,3) block convs run one-term fp16
     bool aux16() const { return has16() && !fp32_all; }               // SPADE branch, shortcut GEMM, conv_img, resize on the split-fp16 path
     bool layer16(int layer) const { return aux16() && !fp32_layer[layer]; }
     StreamOrder order;   // (capture-aware: i2v_common.h)
@@ -884,6 +904,25 @@ int run_modulate_wino4(const float* x, const float* coef, const float* gb, float
     return I2V_OK;
 }
 
+// the one-term operand (mma = 3): C channels of x, written as CinPad = C rounded up to 64 (the kernel's chunks come in pairs)
+int run_modulate_wino4h(const float* x, const float* coef, const float* gb, float* out, int B, int T, int H, int W, int C, int ut,
+                        int us, int lrelu, hipStream_t st, int* range_flag, int* umax) {
+    I2V_REQUIRE(C % 32 == 0 && W % 4 == 0, I2V_E_INVALID, "modulate (one-term F(4,3) operand): channels %d / width %d", C, W);
+    const int Cp = (C + 63) / 64 * 64;
+    const long per = (long)H * (W / 4) * (Cp / 4);
+    I2V_REQUIRE(per % 64 == 0, I2V_E_INVALID, "modulate (one-term F(4,3) operand): %ld threads per sample (need whole wavefronts)", per);
+    I2V_REQUIRE(per * T * 6 < (1L << 31), I2V_E_INVALID, "modulate: tensor too large");
+    const unsigned gx = (unsigned)std::min<long>((per + 255) / 256, 8192);
+    if (gb)
+        hipLaunchKernelGGL((modulate_wino4_kernel<true, true>), dim3(gx, B), dim3(256), 0, st, x, reinterpret_cast<const float2*>(coef), gb,
+                           reinterpret_cast<char*>(out), T, H, W, Cp, ut, us, lrelu, range_flag, umax, C);
+    else
+        hipLaunchKernelGGL((modulate_wino4_kernel<false, true>), dim3(gx, B), dim3(256), 0, st, x, reinterpret_cast<const float2*>(coef), gb,
+                           reinterpret_cast<char*>(out), T, H, W, Cp, ut, us, lrelu, range_flag, umax, C);
+    I2V_HIP_CHECK(hipGetLastError());
+    return I2V_OK;
+}
+
 int run_modulate_wino(const float* x, const float* coef, const float* gb, float* out, int B, int T, int H, int W, int C, int ut,
                       int us, int lrelu, hipStream_t st, int* range_flag, int* umax = nullptr) {
     I2V_REQUIRE(C % 32 == 0 && W % 2 == 0, I2V_E_INVALID, "modulate (Winograd operand): channels %d / width %d", C, W);
@@ -962,6 +1001,15 @@ int conv3_w4(i2v_dec* d, const Wino4Weights& w, const float* v_hl16, float* out,
     return wino4_forward(w, v_hl16, out, res, rt, rs, B, l.T, l.H, l.W, epi, st, stats);
 }
 
+// one-term fp16 mode (mma = 3): the same F(4,3) products, one fp16 MFMA each
+int conv3_w4h(i2v_dec* d, const Wino4hWeights& w, const float* v16, float* out, const float* res, int rt, int rs, int B,
+              const Level& l, int epi, hipStream_t st, double* stats = nullptr) {
+    if (stats) I2V_HIP_CHECK(hipMemsetAsync(stats, 0, (size_t)B * w.Cout * 16, st));
+    const double fl = 2.0 * B * l.T * l.H * l.W * (double)w.Cin * w.Cout * 27.0;
+    ProfScope ps(d, st, fl, fl * 0.5 * (w.tdup ? 18.0 / 27.0 : 1.0));
+    return wino4h_forward(w, v16, out, res, rt, rs, B, l.T, l.H, l.W, epi, st, stats);
+}
+
 // the same conv with the operand generated in the kernel (no operand-writer launch in front): x = the conv's fp32 input before the
 // modulation, coef / gb as the writer takes them
 int conv3_w4g(i2v_dec* d, const Wino4Weights& w, const float* x, const float* coef, const float* gb, int us, float* out, const float* res, int rt,
@@ -1001,6 +1049,8 @@ bool use_wf_0(const i2v_dec* d, const Block& b, const Level& l) { return b.conv0
 bool use_wf_1(const i2v_dec* d, const Block& b, const Level& l) { return b.conv1_wf.u[0].w.p && want_wf_1(d, b, l); }
 bool use_w4_0(const i2v_dec* d, const Block& b, const Level& l) { return b.conv0_w4.w.p && want_w4_0(d, b, l); }
 bool use_w4_1(const i2v_dec* d, const Block& b, const Level& l) { return b.conv1_w4.w.p && want_w4_1(d, b, l); }
+bool use_w4h_0(const i2v_dec* d, const Block& b, const Level& l) { return b.conv0_w4h.w.p && want_w4_0(d, b, l); }
+bool use_w4h_1(const i2v_dec* d, const Block& b, const Level& l) { return b.conv1_w4h.w.p && want_w4_1(d, b, l); }
 bool use_wino0(const i2v_dec* d, const Block& b, const Level& l) { return b.conv0_w.w.p && want_wino0(d, b, l); }
 bool use_wino1(const i2v_dec* d, const Block& b, const Level& l) { return b.conv1_w.w.p && want_wino1(d, b, l); }
 
@@ -1111,7 +1161,8 @@ int block_forward(i2v_dec* d, int k, Block& b, const Level& l, const float* x, f
     // per conv: split-fp16 or exact fp32 (mma = 0: all fp32; mma = auto: the layers the range guard switched, i2v_dec::fp32_layer)
     const bool f16_0 = d->layer16((2 * k) % 12), f16_1 = d->layer16((2 * k + 1) % 12);
     const bool tdup = f16_0 && b.tdup0;  // a0 is kept at the half temporal rate (its frames 2i and 2i+1 coincide)
-    const bool q0 = f16_0 && use_w4_0(d, b, l), q1 = f16_1 && use_w4_1(d, b, l);          // F(4,3)
+    const bool h0 = f16_0 && use_w4h_0(d, b, l), h1 = f16_1 && use_w4h_1(d, b, l);        // F(4,3), one-term fp16 (mma = 3)
+    const bool q0 = f16_0 && (h0 || use_w4_0(d, b, l)), q1 = f16_1 && (h1 || use_w4_1(d, b, l));          // F(4,3)
     const bool w0 = f16_0 && !q0 && use_wino0(d, b, l), w1 = f16_1 && !q1 && use_wino1(d, b, l);   // F(2,3)
     int* flag = d->status_dev;
     // range guard: the two operand tensors of this block publish their maxima in slots 1 + 2k / 2 + 2k
@@ -1119,20 +1170,23 @@ int block_forward(i2v_dec* d, int k, Block& b, const Level& l, const float* x, f
     int* um1 = f16_1 && flag ? flag + 2 + 2 * (k % 12) : nullptr;
     const bool f0 = !f16_0 && w.m6 && use_wf_0(d, b, l), f1 = !f16_1 && w.m6 && use_wf_1(d, b, l);   // exact fp32: Winograd F(4,3) on the fp32 matrix cores
     // thin F(4,3) layers: the operand is generated by the conv kernel's producer waves (no writer launch, no V tensor)
-    const bool g0 = d->gen == 1 && q0 && !tdup && l.ut == 1 && l.us == 2 && !d->tap_dst && wino4g_supported(b.n_mid, b.n_in, l.T, l.H, l.W, 2);
-    const bool g1 = d->gen && q1 && !d->tap_dst && wino4g_supported(b.n_out, b.n_mid, l.T, l.H, l.W, 1);
+    const bool g0 = d->gen == 1 && q0 && !h0 && !tdup && l.ut == 1 && l.us == 2 && !d->tap_dst && wino4g_supported(b.n_mid, b.n_in, l.T, l.H, l.W, 2);
+    const bool g1 = d->gen && q1 && !h1 && !d->tap_dst && wino4g_supported(b.n_out, b.n_mid, l.T, l.H, l.W, 1);
     if (g0) rc = I2V_OK;
     else if (f0) rc = modulate_wino4_f32(x, coef, gb, a, B, l.T, l.H, l.W, b.n_in, l.ut, l.us, 1, st);
+    else if (h0) rc = run_modulate_wino4h(x, coef, gb, a, B, tdup ? l.T / 2 : l.T, l.H, l.W, b.n_in, tdup ? 1 : l.ut, l.us, 1, st, flag, um0);
     else if (q0) rc = run_modulate_wino4(x, coef, gb, a, B, tdup ? l.T / 2 : l.T, l.H, l.W, b.n_in, tdup ? 1 : l.ut, l.us, 1, st, flag, um0);
     else if (w0) rc = run_modulate_wino(x, coef, gb, a, B, tdup ? l.T / 2 : l.T, l.H, l.W, b.n_in, tdup ? 1 : l.ut, l.us, 1, st, flag, um0);
     else if (tdup) rc = run_modulate(x, coef, gb, a, B, l.T / 2, l.H, l.W, b.n_in, 1, l.us, 1, st, true, flag, um0);
     else rc = run_modulate(x, coef, gb, a, B, l.T, l.H, l.W, b.n_in, l.ut, l.us, 1, st, f16_0, flag, um0);
     if (rc) return rc;
-    if (!f0 && !g0 && (rc = tap(k, 1, a, (size_t)B * (tdup ? P / 2 : P) * b.n_in))) return rc;
+    // (the one-term operand is tapped whole: 3 bytes per activation of CinPad channels)
+    if (!f0 && !g0 && (rc = tap(k, 1, a, h0 ? (size_t)B * (tdup ? P / 2 : P) * b.conv0_w4h.CinPad * 3 / 4 : (size_t)B * (tdup ? P / 2 : P) * b.n_in))) return rc;
     const bool fuse = f16_0 && conv16_can_fuse_stats(tdup ? l.T / 2 : l.T, l.H, l.W);
     d->prof_cur_layer = 2 * k;
-    d->prof_cur_kernel = g0 ? 4 : q0 ? 3 : w0 ? 2 : f16_0 ? 1 : f0 ? 5 : 0;
-    if (g0) rc = conv3_w4g(d, b.conv0_w4, x, coef, gb, 2, dx, nullptr, 1, 1, B, l, EPI_NONE, st, fuse ? sums2 : nullptr, flag, um0);
+    d->prof_cur_kernel = h0 ? 6 : g0 ? 4 : q0 ? 3 : w0 ? 2 : f16_0 ? 1 : f0 ? 5 : 0;
+    if (h0) rc = conv3_w4h(d, b.conv0_w4h, a, dx, nullptr, 1, 1, B, l, EPI_NONE, st, fuse ? sums2 : nullptr);
+    else if (g0) rc = conv3_w4g(d, b.conv0_w4, x, coef, gb, 2, dx, nullptr, 1, 1, B, l, EPI_NONE, st, fuse ? sums2 : nullptr, flag, um0);
     else if (f0) rc = conv3_wf(d, b.conv0_wf, a, w.m6, dx, nullptr, 1, 1, B, l, EPI_NONE, st);
     else if (q0) rc = conv3_w4(d, b.conv0_w4, a, dx, nullptr, 1, 1, B, l, EPI_NONE, st, fuse ? sums2 : nullptr);
     else if (w0) rc = conv3_w(d, b.conv0_w, a, dx, nullptr, 1, 1, B, l, EPI_NONE, st, fuse ? sums2 : nullptr);
@@ -1145,11 +1199,12 @@ int block_forward(i2v_dec* d, int k, Block& b, const Level& l, const float* x, f
     if ((rc = run_coef(sums2, coef, B, b.n_mid, b.n_mid, (double)P, zl, zstride, b.zoff, nullptr, nullptr, st))) return rc;
     if (g1) rc = I2V_OK;
     else if (f1) rc = modulate_wino4_f32(dx, coef, nullptr, a, B, l.T, l.H, l.W, b.n_mid, 1, 1, 1, st);
+    else if (h1) rc = run_modulate_wino4h(dx, coef, nullptr, a, B, l.T, l.H, l.W, b.n_mid, 1, 1, 1, st, flag, um1);
     else if (q1) rc = run_modulate_wino4(dx, coef, nullptr, a, B, l.T, l.H, l.W, b.n_mid, 1, 1, 1, st, flag, um1);
     else if (w1) rc = run_modulate_wino(dx, coef, nullptr, a, B, l.T, l.H, l.W, b.n_mid, 1, 1, 1, st, flag, um1);
     else rc = run_modulate(dx, coef, nullptr, a, B, l.T, l.H, l.W, b.n_mid, 1, 1, 1, st, f16_1, flag, um1);
     if (rc) return rc;
-    if (!f1 && !g1 && (rc = tap(k, 3, a, (size_t)B * P * b.n_mid))) return rc;
+    if (!f1 && !g1 && (rc = tap(k, 3, a, h1 ? (size_t)B * P * b.conv1_w4h.CinPad * 3 / 4 : (size_t)B * P * b.n_mid))) return rc;
     // shortcut (decoder.py:44-49) at low resolution
     const float* res = x;
     if (b.learned && !side_shortcut) {
@@ -1171,8 +1226,9 @@ int block_forward(i2v_dec* d, int k, Block& b, const Level& l, const float* x, f
     // statistics of the block OUTPUT = the next block's input)
     const bool fuse_out = f16_1 && conv16_can_fuse_stats(l.T, l.H, l.W) && !last;
     d->prof_cur_layer = 2 * k + 1;
-    d->prof_cur_kernel = g1 ? 4 : q1 ? 3 : w1 ? 2 : f16_1 ? 1 : f1 ? 5 : 0;
-    if (g1) rc = conv3_w4g(d, b.conv1_w4, dx, coef, nullptr, 1, xn, res, l.ut, l.us, B, l, last ? EPI_LRELU : EPI_NONE, st, fuse_out ? sums_out : nullptr, flag, um1);
+    d->prof_cur_kernel = h1 ? 6 : g1 ? 4 : q1 ? 3 : w1 ? 2 : f16_1 ? 1 : f1 ? 5 : 0;
+    if (h1) rc = conv3_w4h(d, b.conv1_w4h, a, xn, res, l.ut, l.us, B, l, last ? EPI_LRELU : EPI_NONE, st, fuse_out ? sums_out : nullptr);
+    else if (g1) rc = conv3_w4g(d, b.conv1_w4, dx, coef, nullptr, 1, xn, res, l.ut, l.us, B, l, last ? EPI_LRELU : EPI_NONE, st, fuse_out ? sums_out : nullptr, flag, um1);
     else if (f1) rc = conv3_wf(d, b.conv1_wf, a, w.m6, xn, res, l.ut, l.us, B, l, last ? EPI_LRELU : EPI_NONE, st);
     else if (q1) rc = conv3_w4(d, b.conv1_w4, a, xn, res, l.ut, l.us, B, l, last ? EPI_LRELU : EPI_NONE, st, fuse_out ? sums_out : nullptr);
     else if (w1) rc = conv3_w(d, b.conv1_w, a, xn, res, l.ut, l.us, B, l, last ? EPI_LRELU : EPI_NONE, st, fuse_out ? sums_out : nullptr);
@@ -1274,6 +1330,16 @@ int sn_pack_wino(const StateDict& sd, const std::string& name, bool spectral, in
     return tdup ? out.pack_tdup(w, bias, cout, cin, scale) : out.pack(w, bias, cout, cin, 3, scale);
 }
 
+int sn_pack_wino4h(const StateDict& sd, const std::string& name, bool spectral, int cout, int cin, bool tdup, Wino4hWeights& out) {
+    const float* bias = sd.f32(name + ".bias", cout);
+    if (!bias) return I2V_E_MISSING;
+    const float* w = nullptr;
+    double scale = 1.0;
+    int rc = sn_scale(sd, name, spectral, cout, (int64_t)cin * 27, &w, &scale);
+    if (rc) return rc;
+    return tdup ? out.pack_tdup(w, bias, cout, cin, scale) : out.pack(w, bias, cout, cin, scale);
+}
+
 int sn_pack_wino4(const StateDict& sd, const std::string& name, bool spectral, int cout, int cin, bool tdup, Wino4Weights& out) {
     const float* bias = sd.f32(name + ".bias", cout);
     if (!bias) return I2V_E_MISSING;
@@ -1299,7 +1365,7 @@ int i2v_dec_create(const i2v_dec_cfg* cfg, i2v_dec** out) {
         I2V_REQUIRE((s == 1 || s == 2 || s == 4) && (t == 1 || t == 2 || t == 4), I2V_E_INVALID,
                     "i2v_dec_create: upsample factors must be 1, 2 or 4");
     }
-    I2V_REQUIRE(cfg->mma == 0 || cfg->mma == 1 || cfg->mma == 2, I2V_E_INVALID, "i2v_dec_create: unknown mma mode %d (0 fp32, 1 split-fp16, 2 auto)", cfg->mma);
+    I2V_REQUIRE(cfg->mma >= 0 && cfg->mma <= 3, I2V_E_INVALID, "i2v_dec_create: unknown mma mode %d (0 fp32, 1 split-fp16, 2 auto, 3 fp16)", cfg->mma);
     int ndev = 0;
     I2V_HIP_CHECK(hipGetDeviceCount(&ndev));
     I2V_REQUIRE(ndev > 0, I2V_E_HIP, "i2v_dec_create: no HIP device");
@@ -1372,12 +1438,14 @@ int i2v_dec_load(i2v_dec* d, const i2v_tensor* tensors, int32_t n_tensors) {
             // on t): conv_0 runs on the half-rate tensor with two pre-summed 2-tap temporal kernels (-1/3 of its MACs)
             b.tdup0 = d->lvl[k].ut == 2;
             // layers whose shape allows it run on the Winograd kernel (1.5x fewer MFMAs), the rest on the direct one
-            if (want_w4_0(d, b, d->lvl[k])) rc = sn_pack_wino4(sd, p + "conv_0", sn, b.n_mid, b.n_in, b.tdup0, b.conv0_w4);
+            if (want_w4_0(d, b, d->lvl[k]) && d->one16()) rc = sn_pack_wino4h(sd, p + "conv_0", sn, b.n_mid, b.n_in, b.tdup0, b.conv0_w4h);
+            else if (want_w4_0(d, b, d->lvl[k])) rc = sn_pack_wino4(sd, p + "conv_0", sn, b.n_mid, b.n_in, b.tdup0, b.conv0_w4);
             else if (want_wino0(d, b, d->lvl[k])) rc = sn_pack_wino(sd, p + "conv_0", sn, b.n_mid, b.n_in, b.tdup0, b.conv0_w);
             else if (b.tdup0) rc = sn_pack_tdup(sd, p + "conv_0", sn, b.n_mid, b.n_in, b.conv0_16);
             else rc = sn_pack(sd, p + "conv_0", sn, b.n_mid, b.n_in, 3, true, b.conv0_16);
             if (rc) return rc;
-            if (want_w4_1(d, b, d->lvl[k])) rc = sn_pack_wino4(sd, p + "conv_1", sn, b.n_out, b.n_mid, false, b.conv1_w4);
+            if (want_w4_1(d, b, d->lvl[k]) && d->one16()) rc = sn_pack_wino4h(sd, p + "conv_1", sn, b.n_out, b.n_mid, false, b.conv1_w4h);
+            else if (want_w4_1(d, b, d->lvl[k])) rc = sn_pack_wino4(sd, p + "conv_1", sn, b.n_out, b.n_mid, false, b.conv1_w4);
             else if (want_wino1(d, b, d->lvl[k])) rc = sn_pack_wino(sd, p + "conv_1", sn, b.n_out, b.n_mid, false, b.conv1_w);
             else rc = sn_pack(sd, p + "conv_1", sn, b.n_out, b.n_mid, 3, true, b.conv1_16);
             if (rc) return rc;
@@ -1887,7 +1955,7 @@ extern "C" {
 int i2v_gblock_create(int32_t n_in, int32_t n_out, int32_t z_dim, int32_t spectral_norm, int32_t mma, i2v_gblock** out) {
     I2V_REQUIRE(out && n_in > 0 && n_out > 0 && n_in % 8 == 0 && n_out % 8 == 0 && n_in <= 1024 && n_out <= 1024, I2V_E_INVALID,
                 "i2v_gblock_create: channel counts must be multiples of 8 in [8, 1024]");
-    I2V_REQUIRE(z_dim > 0 && z_dim % 4 == 0 && (mma == 0 || mma == 1), I2V_E_INVALID, "i2v_gblock_create: bad z_dim / mma");
+    I2V_REQUIRE(z_dim > 0 && z_dim % 4 == 0 && (mma == 0 || mma == 1 || mma == 3), I2V_E_INVALID, "i2v_gblock_create: bad z_dim / mma (0 fp32, 1 split-fp16, 3 fp16)");
     // the learned shortcut's Norm3D is GroupNorm(16, n_in) (normalization_layer.py:31), which needs n_in % 16 == 0
     I2V_REQUIRE(n_in == n_out || n_in % 16 == 0, I2V_E_INVALID,
                 "i2v_gblock_create: a learned shortcut needs n_in %% 16 == 0 (GroupNorm(16, n_in)), got n_in %d", n_in);
@@ -1923,7 +1991,7 @@ int i2v_gblock_load(i2v_gblock* g, const i2v_tensor* tensors, int32_t n_tensors)
     I2V_REQUIRE_DEVICE(g->ctx.device, "i2v_gblock_load");
     StateDict sd(tensors, n_tensors);
     Block& b = g->b;
-    const bool sn = g->ctx.cfg.spectral_norm != 0, f16 = g->ctx.cfg.mma == 1;
+    const bool sn = g->ctx.cfg.spectral_norm != 0, f16 = g->ctx.cfg.mma == 1 || g->ctx.cfg.mma == 3, one = g->ctx.cfg.mma == 3;
     int rc;
     g->has_convs = g->has_spade = g->has_adain = g->has_norm_s = false;
     if (sd.has(sn ? "conv_0.weight_orig" : "conv_0.weight")) {
@@ -1936,10 +2004,13 @@ int i2v_gblock_load(i2v_gblock* g, const i2v_tensor* tensors, int32_t n_tensors)
             if (g->ctx.wino && wino16_supported(b.n_out, b.n_mid, 16, 64, 64) &&
                 (rc = sn_pack_wino(sd, "conv_1", sn, b.n_out, b.n_mid, false, b.conv1_w))) return rc;
             // ... and the F(4,3) variants (used where the call's geometry gives a sample >= 32 workgroups; I2V_DEC_WINO4=2: always)
+            //     (mma = 3: their one-term form instead)
             if (g->ctx.wino && g->ctx.wino4 && wino4_supported(b.n_mid, b.n_in, 16, 64, 64, 3) &&
-                (rc = sn_pack_wino4(sd, "conv_0", sn, b.n_mid, b.n_in, false, b.conv0_w4))) return rc;
+                (rc = one ? sn_pack_wino4h(sd, "conv_0", sn, b.n_mid, b.n_in, false, b.conv0_w4h)
+                          : sn_pack_wino4(sd, "conv_0", sn, b.n_mid, b.n_in, false, b.conv0_w4))) return rc;
             if (g->ctx.wino && g->ctx.wino4 && wino4_supported(b.n_out, b.n_mid, 16, 64, 64, 3) &&
-                (rc = sn_pack_wino4(sd, "conv_1", sn, b.n_out, b.n_mid, false, b.conv1_w4))) return rc;
+                (rc = one ? sn_pack_wino4h(sd, "conv_1", sn, b.n_out, b.n_mid, false, b.conv1_w4h)
+                          : sn_pack_wino4(sd, "conv_1", sn, b.n_out, b.n_mid, false, b.conv1_w4))) return rc;
         } else {
             if ((rc = sn_pack(sd, "conv_0", sn, b.n_mid, b.n_in, 3, true, b.conv0))) return rc;
             if ((rc = sn_pack(sd, "conv_1", sn, b.n_out, b.n_mid, 3, true, b.conv1))) return rc;
@@ -2022,7 +2093,7 @@ int i2v_gblock_forward(i2v_gblock* g, const float* x, const float* z, const floa
                             false, st)))
         return rc;
     if ((rc = run_transpose(F(L.out_cl), out, batch, b.n_out, P, false, st))) return rc;
-    if (g->ctx.cfg.mma == 1) {
+    if (g->ctx.cfg.mma == 1 || g->ctx.cfg.mma == 3) {
         hipLaunchKernelGGL(status_finish_kernel, dim3(1), dim3(1), 0, st, g->ctx.status_dev);
         I2V_HIP_CHECK(hipGetLastError());
         I2V_HIP_CHECK(hipMemcpyAsync(g->ctx.status_host, g->ctx.status_dev, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -2058,9 +2129,9 @@ int i2v_gblock_norm(i2v_gblock* g, int32_t part, const float* x, const float* co
         if ((rc = run_coef(sums, coef, B, C, b.groups_spade, (double)P, nullptr, 0, 0, nullptr, nullptr, st))) return rc;
         const long tot = (long)B * h * w;
         hipLaunchKernelGGL(resize_kernel, dim3((unsigned)std::min<long>((tot + 255) / 256, 65536)), dim3(256), 0, st, cond, F(L.y0), B,
-                           img_h, img_w, h, w, g->ctx.cfg.mma == 1 ? 1 : 0, g->ctx.status_dev, (long)3 * img_h * img_w);
+                           img_h, img_w, h, w, g->ctx.has16() ? 1 : 0, g->ctx.status_dev, (long)3 * img_h * img_w);
         I2V_HIP_CHECK(hipGetLastError());
-        if (g->ctx.cfg.mma == 1) {
+        if (g->ctx.has16()) {
             if ((rc = conv16_forward(b.sp_conv16, F(L.y0), reinterpret_cast<float*>(F(L.y1)), nullptr, 1, 1, B, 1, h, w,
                                      EPI_LRELU | EPI_HL16, st, nullptr, g->ctx.status_dev))) return rc;
             if ((rc = conv16_forward(b.sp_gb16, F(L.y1), F(L.gb), nullptr, 1, 1, B, 1, h, w, EPI_NONE, st))) return rc;

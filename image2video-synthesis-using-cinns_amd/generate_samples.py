@@ -55,6 +55,9 @@ def main(argv=None):
     parser.add_argument("-img_path", type=str, help="override ./assets/GT_samples/<dataset>/")
     parser.add_argument("-out_path", type=str, help="override ./assets/results/<dataset>/")
     parser.add_argument("-seed", type=int, help="seed the CPU generator the latent residuals are drawn from, right before sampling")
+    parser.add_argument("-dec_mma", type=str, choices=["auto", "0", "1", "fp16"], default=None,
+                        help="decoder matrix-core mode: auto (split-fp16 with the exact-fp32 fallback), 0 exact fp32, 1 split-fp16, "
+                             "fp16 one-term half precision (opt-in).  Default: the YAML's Decoder.mma, else I2V_DEC_MMA, else auto")
     parser.add_argument("-raw_npy", type=str, help="also write the uint8 frame strip [T,H,N*W,3] (the GIF's palette is lossy)")
     args = parser.parse_args(argv)
     os.environ["HIP_VISIBLE_DEVICES"] = args.gpu   # the reference sets CUDA_VISIBLE_DEVICES (generate_samples.py:20)
@@ -71,7 +74,7 @@ def main(argv=None):
     if not img_list:
         raise SystemExit(f"no images found under {img_path}")
 
-    model = Model(ckpt_path, args.seq_length)
+    model = Model(ckpt_path, args.seq_length, mma=args.dec_mma)
     img_res = model.config.Data["img_size"]
     imgs = load_images(img_list, img_res)
     E = model.flow.flow.cond_channels - 3 * model.flow.cond_size  # width of the image embedding (without the control one-hots)

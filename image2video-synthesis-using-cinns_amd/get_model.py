@@ -18,7 +18,7 @@ from stage2_cINN.modules import INN
 
 
 class Model(torch.nn.Module):
-    def __init__(self, model_path, vid_length, transfer=False, embedder=None):
+    def __init__(self, model_path, vid_length, transfer=False, embedder=None, mma=None):
         super().__init__()
         opt = i2v_config.load(os.path.join(model_path, "config_stage2.yaml"))
         path_stage1 = opt.First_stage_model["model_path"] + opt.First_stage_model["model_name"] + "/"
@@ -27,9 +27,12 @@ class Model(torch.nn.Module):
         # Matrix-core mode: the checkpoint's activations are unknown until they have been seen, so the drop-in entry point runs the
         # decoder in AUTO mode (split-fp16 with the per-layer fallback to the exact-fp32 kernels behind the range guard: a checkpoint
         # inside the split format's window runs exactly the default launches, one outside it still returns valid frames -- check()
-        # says which layers were switched) unless the YAML's Decoder section or I2V_DEC_MMA pick a mode.
+        # says which layers were switched) unless the YAML's Decoder section or I2V_DEC_MMA pick a mode.  ``mma`` (not a reference
+        # argument: 0, 1, "auto" or "fp16") overrides both.
         dec_cfg = dict(config.Decoder)
-        if "mma" not in dec_cfg and "I2V_DEC_MMA" not in os.environ:
+        if mma is not None:
+            dec_cfg["mma"] = mma
+        elif "mma" not in dec_cfg and "I2V_DEC_MMA" not in os.environ:
             dec_cfg["mma"] = "auto"
         self.decoder = decoder.Generator(dec_cfg).cuda()
         self.decoder.load_state_dict(torch.load(path_stage1 + opt.First_stage_model["checkpoint_decoder"] + ".pth",
@@ -119,6 +122,20 @@ class Model(torch.nn.Module):
                           f" to the exact-fp32 kernels ({fb['reruns']} forward(s) were run again): this checkpoint's activations leave the window "
                           "the split-fp16 operand format holds 1e-4 in (INTEGRATION.md §3); the frames are valid", RuntimeWarning)
         flags = self.decoder.native().status()
+        if self.decoder.mma == 3:   # one-term fp16: the fallback for either flag is a mode that emulates fp32
+            if flags & 2 and not flags & 1:
+                import warnings
+                self.decoder.native().status(reset=True)
+                warnings.warn("decoder status bit 1 (underflow, mma = fp16): a conv operand tensor lay entirely below 2^-10, next to the "
+                              "fp16 subnormal range (2^-14) where the one-term operands lose relative precision (INTEGRATION.md §3); the "
+                              "frames are finite but less precise -- use Model(..., mma='auto') or Generator(dic['mma'] = 0) / "
+                              "I2V_DEC_MMA=0 for this checkpoint", RuntimeWarning)
+                return
+            if flags:
+                raise RuntimeError(f"decoder status flags {flags}: activations left the fp16 range of the fp16 conv operands (mma = fp16) -- "
+                                   "the frames of this call are invalid; use Model(..., mma='auto') or Generator(dic['mma'] = 0) / "
+                                   "I2V_DEC_MMA=0 for this checkpoint")
+            return
         if flags & 2 and not flags & 1:
             import warnings
             self.decoder.native().status(reset=True)

@@ -344,7 +344,8 @@ class NativeDecoder(_Handle):
         return {"conv3_ms": a.value, "conv3_flops": b.value, "conv3_mfma_flops": e.value, "conv3_launches": c.value}
 
     # i2v_dec_get_layer_profile's kernel code -> name
-    KERNEL_NAMES = ("conv_mfma_f32", "conv_mfma_f16x3", "conv_wino_f16x3", "conv_wino4_f16x3", "conv_wino4g_f16x3", "conv_wino4_f32")
+    KERNEL_NAMES = ("conv_mfma_f32", "conv_mfma_f16x3", "conv_wino_f16x3", "conv_wino4_f16x3", "conv_wino4g_f16x3", "conv_wino4_f32",
+                    "conv_wino4_f16")
 
     @_on_device
     def get_layer_profile(self):
@@ -610,16 +611,21 @@ def default_flow_f16():
 
 
 def parse_mma(v):
-    """0 / 1 / 2 or "auto" (= 2) -> the i2v_dec_cfg.mma value."""
+    """0 / 1 / 2 / 3, "auto" (= 2) or "fp16" (= 3) -> the i2v_dec_cfg.mma value."""
     if isinstance(v, str):
         v = v.strip().lower()
-        return 2 if v == "auto" else int(v)
+        if v == "auto":
+            return 2
+        if v == "fp16":
+            return 3
+        return int(v)
     return int(v)
 
 
 def default_mma():
     """Matrix-core mode of the 3x3x3 convolutions: 1 = split-fp16 (default), 0 = exact fp32 MFMA, 2 / "auto" = split-fp16 with the
-    per-layer fallback to exact fp32 behind the range guard (every forward synchronises); env I2V_DEC_MMA."""
+    per-layer fallback to exact fp32 behind the range guard (every forward synchronises), 3 / "fp16" = opt-in half precision: the F(4,3)
+    block convs on one-term fp16 operands (one MFMA per product); env I2V_DEC_MMA."""
     return parse_mma(os.environ.get("I2V_DEC_MMA", "1"))
 
 

@@ -15,8 +15,9 @@ from stage1_VAE.modules.normalization_layer import ADAIN, Norm3D, Spade
 class GeneratorBlock(NativeBacked):
     """out = shortcut(x) + conv_1(lrelu(ADAIN(conv_0(lrelu(Spade(x, img))), z)))   (reference decoder.py:7-52)."""
 
-    def __init__(self, n_in, n_out, use_spectral, z_dim):
+    def __init__(self, n_in, n_out, use_spectral, z_dim, mma=None):
         super().__init__()
+        self.mma = mma   # not a reference argument: the native block's matrix-core mode (None: I2V_DEC_MMA / default; 0, 1 or "fp16")
         self.learned_shortcut = (n_in != n_out)
         n_middle = min(n_in, n_out)
         self.n_in, self.n_out, self.z_dim, self.use_spectral = n_in, n_out, z_dim, bool(use_spectral)
@@ -30,7 +31,7 @@ class GeneratorBlock(NativeBacked):
             self.norm_s = Norm3D(n_in)
 
     def _build_native(self):
-        h = native.NativeGBlock(self.n_in, self.n_out, self.z_dim, self.use_spectral, device=self.module_device())
+        h = native.NativeGBlock(self.n_in, self.n_out, self.z_dim, self.use_spectral, mma=self.mma, device=self.module_device())
         h.load(self.state_dict())
         return h
 

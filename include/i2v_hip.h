@@ -142,7 +142,11 @@ typedef struct {
                              * per-layer fallback to the exact-fp32 kernels behind the range guard -- both weight sets are packed, every
                              * forward synchronises its stream, looks at the operand maxima the writers published, switches the 3x3x3 convs
                              * whose operand left the window the split format holds 1e-4 in (for the life of the handle) and runs the call
-                             * again; a checkpoint inside the window runs exactly the launches of mma = 1 (i2v_dec_fallback_layers) */
+                             * again; a checkpoint inside the window runs exactly the launches of mma = 1 (i2v_dec_fallback_layers);
+                             * 3 = "fp16": opt-in half precision -- the launches of mma = 1, except that the 3x3x3 block convs on the
+                             * Winograd F(4,3) kernel run its one-term form (conv_wino4_f16_kernel: fp16 operands, ONE MFMA per product,
+                             * fp32 accumulation) on an operand rounded to fp16 once; not an fp32 emulation: frames within ~1e-3 relative
+                             * L2 of the fp32 reference, measured tolerances in INTEGRATION.md §3.  Not combined with auto. */
 } i2v_dec_cfg;
 
 int i2v_dec_create(const i2v_dec_cfg* cfg, i2v_dec** out);
@@ -220,7 +224,7 @@ int i2v_dec_get_profile(i2v_dec* d, double* conv3_ms, double* conv3_flops, doubl
 /* The same totals per layer: layer = 2 * block + {0: conv_0, 1: conv_1}, block 0..5 = head_0, g_0 .. g_4 (decoder.py:74-79).
  * name receives "<block>.conv_<i>"; kernel: 0 = exact-fp32 MFMA implicit GEMM (direct), 1 = split-fp16 direct, 2 = split-fp16
  * Winograd F(2,3), 3 = split-fp16 Winograd F(4,3), 4 = split-fp16 F(4,3) with the operand generated in the kernel,
- * 5 = exact-fp32 Winograd F(4,3). */
+ * 5 = exact-fp32 Winograd F(4,3), 6 = one-term fp16 Winograd F(4,3) (mma = 3: one MFMA product per product is counted). */
 int i2v_dec_get_layer_profile(i2v_dec* d, int32_t layer, char* name, int32_t name_len, double* ms, double* flops,
                               double* mfma_flops, int64_t* launches, int32_t* kernel);
 /* Test hook: during the next forwards copy up to max_floats of one channels-last intermediate of GeneratorBlock
@@ -238,7 +242,12 @@ int i2v_dec_get_layer_profile(i2v_dec* d, int32_t layer, char* name, int32_t nam
  * the largest |activation| they wrote; a non-zero tensor whose maximum is below 2^-10 sets bit 1.  Coverage, as built: the
  * maximum is per operand TENSOR over the whole batch (one normal sample hides an underflowing one in the same call), and SPADE's
  * internal 128-channel operand, the EPI_HL16 conv epilogue and conv_img's input are not watched (they carry bit 0 only).  It is reported by i2v_dec_status only (sticky until reset) and does NOT make the next call fail:
- * the output is finite and merely less precise; mma = 0 is exact there too. */
+ * the output is finite and merely less precise; mma = 0 is exact there too.
+ * mma = 3 ("fp16"): the same status word and the same writers' guard.  Bit 0: a value of a conv operand left the fp16 range (the
+ * one-term operand holds exactly the split format's hi parts, so the same values overflow) -- the output is invalid, use mma = 0 or
+ * auto.  Bit 1 keeps its trigger (a non-zero operand tensor whose maximum is below 2^-10) and means for this format: the operand
+ * reaches towards fp16's subnormal range (below 2^-14), where the one-term values lose relative precision beyond the mode's normal
+ * ~2^-12 per value; a warning, as in mma = 1. */
 int i2v_dec_status(i2v_dec* d, int32_t* flags, int32_t reset, void* stream);
 
 int i2v_dec_debug_tap(i2v_dec* d, int32_t block, int32_t which, float* dst, size_t max_floats);
@@ -249,7 +258,7 @@ int i2v_dec_debug_tap(i2v_dec* d, int32_t block, int32_t which, float* dst, size
  * T, H, W must be powers of two (>= 1) so the convolutions tile into bricks.
  * ---------------------------------------------------------------------------------------- */
 typedef struct i2v_gblock i2v_gblock;
-/* mma: 0 (exact fp32) or 1 (split-fp16); a block has no re-run loop, so there is no auto mode.  A learned shortcut (n_in != n_out)
+/* mma: 0 (exact fp32), 1 (split-fp16) or 3 (fp16, see i2v_dec_cfg.mma); a block has no re-run loop, so there is no auto mode.  A learned shortcut (n_in != n_out)
  * needs n_in % 16 == 0: its Norm3D is GroupNorm(16, n_in).  Both return I2V_E_INVALID otherwise. */
 int i2v_gblock_create(int32_t n_in, int32_t n_out, int32_t z_dim, int32_t spectral_norm, int32_t mma, i2v_gblock** out);
 void i2v_gblock_destroy(i2v_gblock* g);
