@@ -60,9 +60,15 @@ struct Wino4F32Weights {
     int pack(const float* w_src, const float* bias_src, int cout, int cin, double scale);
 };
 bool wino4f32_supported(int cout, int cin, int T, int H, int W);
+// Realizations (i2v_dec_forward_realizations): sample b of a launch reads the gamma' | beta map row (r0 + b) / k of `gb` -- k samples
+// share one start frame; r0 = the launch's first sample's realization index.  k == 1: row b, the launches of the plain forward.
+struct GbRows {
+    int k = 1, r0 = 0;
+    bool shared() const { return k > 1; }
+};
 // V: [6][B][T][H][W/4][C] fp32 = B^T d of act((x A + B) gamma' + beta) read through the nearest up-sampling map (ut, us)
 int modulate_wino4_f32(const float* x, const float* coef, const float* gb, float* V, int B, int T, int H, int W, int C, int ut, int us,
-                       int lrelu, hipStream_t st);
+                       int lrelu, hipStream_t st, GbRows rows = {});
 // M: scratch [6][B][T][H][W/4][Cout]; out: channels-last fp32 [B][T][H][W][Cout]; res as conv_forward
 int wino4f32_forward(const Wino4F32Weights& wts, const float* V, float* M, float* out, const float* res, int rt, int rs, int B, int T, int H,
                      int W, int epi, hipStream_t st);
@@ -172,7 +178,7 @@ int wino4h_forward(const Wino4hWeights& wts, const void* v16, float* out, const 
 bool wino4g_supported(int cout, int cin, int T, int H, int W, int us);
 int wino4g_forward(const Wino4Weights& wts, const float* x, const float* coef, const float* gb, int us, float* out, const float* res, int rt,
                    int rs, int B, int T, int H, int W, int epi, hipStream_t st, double* stats = nullptr, int* range_flag = nullptr,
-                   int* umax = nullptr);
+                   int* umax = nullptr, GbRows rows = {});
 
 // ---- helpers implemented in i2v_dec.hip, shared with the embedder (i2v_embed.hip)
 // per-(b,c) sum / sum of squares (fp64) of a channels-last tensor [B][P][C]

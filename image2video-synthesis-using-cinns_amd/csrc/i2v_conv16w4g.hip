@@ -30,6 +30,7 @@ struct W4GenArgs {
     int us;              // nearest up-sampling in front of the conv along H and W (1 or 2)
     int* range_flag;     // sticky overflow flag of the split-fp16 format (bit 0) or null
     int* umax;           // underflow guard slot (largest |activation| written, float bits) or null
+    int gk, gr0;         // MODE 4 (SPADE, realizations): sample b reads the map row (gr0 + b) / gk -- gk samples share a start frame
 };
 
 constexpr int W4G_THREADS = 768, W4G_PROD = 256;
@@ -247,9 +248,10 @@ __device__ __forceinline__ void w4g_chunk(const W4GenLane<SPADE>& L, const char*
 // 32-channel wave has half the MFMAs per chunk of a 64-channel one to hide the same eight pieces under).  The loader waves do
 // nothing else: 16 (pass A) / 8 (pass B) buffer_load ... lds per chunk from per-lane row offsets computed once per brick, one
 // s_waitcnt, the chunk barrier.  Same V, same tap loops, same bits as the kernels of i2v_conv16w4.hip.
+// MODE 4: the SPADE form on maps shared by realizations (W4GenArgs::gk); the same code as MODE 1 but for the map row of the sample.
 template <int NT, int CIN, int MODE>
 __global__ __launch_bounds__(W4G_THREADS, 1) void conv_wino4g_f16x3_kernel(W4Args a, W4GenArgs g) {
-    constexpr bool SPADE = MODE == 1, LOADER = MODE >= 2, VLOADER = MODE == 3;   // (MODE 3: the loader's requests go through VGPRs + ds_write_b128 instead of LDS-DMA)
+    constexpr bool SPADE = MODE == 1 || MODE == 4, SHARED = MODE == 4, LOADER = MODE == 2 || MODE == 3, VLOADER = MODE == 3;   // (MODE 3: the loader's requests go through VGPRs + ds_write_b128 instead of LDS-DMA)
     static_assert(NT == 9, "the generating kernel exists for the 3x3x3 convs of the last level (no temporal up-sampling in front)");
     using Geo = W4Geo<512>;
     constexpr int NTH = 512, WMA = 2, WMB = 1, KT = NT / 3, NW = 8;
@@ -361,7 +363,7 @@ __global__ __launch_bounds__(W4G_THREADS, 1) void conv_wino4g_f16x3_kernel(W4Arg
         // the sample's tensors (uniform bases; the lane's byte offsets are 32-bit): input, (A, B) pairs of the lane's quad, SPADE maps
         const char* xs = reinterpret_cast<const char*>(g.x + (long)bk.b0 * a.T * (a.H / g.us) * (a.W / g.us) * CIN);
         const float4* cfs = reinterpret_cast<const float4*>(g.coef + (long)bk.b0 * CIN + 4 * (ptid & 3));
-        const char* gbs = SPADE ? reinterpret_cast<const char*>(g.gb + (long)bk.b0 * a.H * a.W * 2 * CIN) : nullptr;
+        const char* gbs = SPADE ? reinterpret_cast<const char*>(g.gb + (long)(SHARED ? (bk.b0 + g.gr0) / g.gk : bk.b0) * a.H * a.W * 2 * CIN) : nullptr;
         float vmaxd = 0.f, vmaxv = 0.f;
         W4GenIn<SPADE> in0;
         w4g_load<CIN, SPADE>(xs, L, 0, in0);
@@ -559,7 +561,7 @@ bool wino4g_supported(int cout, int cin, int T, int H, int W, int us) {
 }
 
 int wino4g_forward(const Wino4Weights& wts, const float* x, const float* coef, const float* gb, int us, float* out, const float* res, int rt, int rs,
-                   int B, int T, int H, int W, int epi, hipStream_t st, double* stats, int* range_flag, int* umax) {
+                   int B, int T, int H, int W, int epi, hipStream_t st, double* stats, int* range_flag, int* umax, GbRows rows) {
     I2V_REQUIRE(wts.w.p && !wts.tdup && wts.KT == 3, I2V_E_STATE, "wino4g: needs 3x3x3 weights packed for the F(4,3) kernel");
     I2V_REQUIRE((epi & ~EPI_LRELU) == 0, I2V_E_INVALID, "wino4g: unsupported epilogue %d", epi);
     I2V_REQUIRE(x && coef && wino4g_supported(wts.Cout, wts.Cin, T, H, W, us) && (gb != nullptr) == (us == 2), I2V_E_INVALID,
@@ -585,16 +587,17 @@ int wino4g_forward(const Wino4Weights& wts, const float* x, const float* coef, c
                 "wino4g: tensor too large for the 32-bit offsets of this kernel");
     a.nvirt = (int)nblk;
     a.tofs = 2 * W4_ROWS_A * 64;
-    W4GenArgs g{x, reinterpret_cast<const float2*>(coef), gb, us, range_flag, umax};
+    W4GenArgs g{x, reinterpret_cast<const float2*>(coef), gb, us, range_flag, umax, rows.k, rows.r0};
     const size_t lds = (size_t)a.tofs + 5 * W4Geo<512>::TILES * 4;
-    static bool attr_set[4][I2V_MAX_DEV] = {};
+    static bool attr_set[6][I2V_MAX_DEV] = {};
     auto launch = [&](auto kern, bool* done) -> int {
         if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), 160 * 1024, done)) return rc;
         hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(W4G_THREADS), lds, st, a, g);
         return I2V_OK;
     };
     int rcl;
-    if (gb) rcl = wts.Cin == 64 ? launch(conv_wino4g_f16x3_kernel<9, 64, 1>, attr_set[0]) : launch(conv_wino4g_f16x3_kernel<9, 32, 1>, attr_set[1]);
+    if (gb && rows.shared()) rcl = wts.Cin == 64 ? launch(conv_wino4g_f16x3_kernel<9, 64, 4>, attr_set[4]) : launch(conv_wino4g_f16x3_kernel<9, 32, 4>, attr_set[5]);
+    else if (gb) rcl = wts.Cin == 64 ? launch(conv_wino4g_f16x3_kernel<9, 64, 1>, attr_set[0]) : launch(conv_wino4g_f16x3_kernel<9, 32, 1>, attr_set[1]);
     else rcl = wts.Cin == 64 ? launch(conv_wino4g_f16x3_kernel<9, 64, 0>, attr_set[2]) : launch(conv_wino4g_f16x3_kernel<9, 32, 0>, attr_set[3]);
     if (rcl) return rcl;
     I2V_HIP_CHECK(hipGetLastError());

@@ -124,6 +124,8 @@ __global__ void coef_kernel(const double* __restrict__ sums, float2* __restrict_
 // loaded once and reused for all T frames, the source row once per `ut` frames; per frame 32 B are stored.
 // blockIdx.y = sample, all per-sample index math in 32 bits.  HL16: write the split-fp16 operand format of
 // i2v_conv16.hip (8 x fp16 hi | 8 x fp16 lo per 8 channels, lo = x - hi) instead of fp32.
+// SH (every SPADE-consuming writer below has it): gk consecutive samples share one start frame (i2v_dec_forward_realizations), sample b
+// reads the map row (gr0 + b) / gk of gb, gr0 = the realization index of the launch's first sample.  SH = false: row b.
 typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
 
 // Underflow side of the range guard.  The lo part of a split-fp16 operand is an fp16 subnormal for |x| < 2^-3, i.e. the format
@@ -157,11 +159,11 @@ __global__ void status_finish_kernel(int* __restrict__ status) {
     if (f) atomicOr(status, f);
 }
 
-template <bool HL16>
+template <bool HL16, bool SH = false>
 __global__ __launch_bounds__(256) void modulate_kernel(const float* __restrict__ x, const float2* __restrict__ coef,
                                                        const float* __restrict__ gb, float* __restrict__ out, int T, int H,
                                                        int W, int C, int ut, int us, int lrelu, int* __restrict__ range_flag,
-                                                       int* __restrict__ umax) {
+                                                       int* __restrict__ umax, int gk = 1, int gr0 = 0) {
     const int C8 = C >> 3;
     const int b = blockIdx.y;
     const int per = H * W * C8;  // threads per sample
@@ -170,7 +172,7 @@ __global__ __launch_bounds__(256) void modulate_kernel(const float* __restrict__
     const int Hl = H / us, Wl = W / us, Tl = T / ut;
     const float2* cp0 = coef + (long)b * C;
     const float* xb = x + (long)b * Tl * Hl * Wl * C;
-    const float* gbb = gb ? gb + (long)b * H * W * 2 * C : nullptr;
+    const float* gbb = gb ? gb + (long)(SH ? (gr0 + b) / gk : b) * H * W * 2 * C : nullptr;
     char* ob = reinterpret_cast<char*>(out) + (long)b * T * per * 32;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < per; i += gridDim.x * 256) {
         const int c8 = i % C8;
@@ -275,10 +277,11 @@ __device__ __forceinline__ void mod_pos_eval(const ModPos& m, long toff, int lre
     }
 }
 
+template <bool SH = false>
 __global__ __launch_bounds__(256) void modulate_wino_kernel(const float* __restrict__ x, const float2* __restrict__ coef,
                                                             const float* __restrict__ gb, char* __restrict__ out, int T, int H,
                                                             int W, int C, int ut, int us, int lrelu, int* __restrict__ range_flag,
-                                                            int* __restrict__ umax) {
+                                                            int* __restrict__ umax, int gk = 1, int gr0 = 0) {
     bool bad = false;
     float vmax = 0.f;
     const int C8 = C >> 3, J = W >> 1;
@@ -290,7 +293,7 @@ __global__ __launch_bounds__(256) void modulate_wino_kernel(const float* __restr
     const int Hl = H / us, Wl = W / us, Tl = T / ut;
     const float2* cp0 = coef ? coef + (long)b * C : nullptr;   // null: identity (the kernel then only formats the operand)
     const float* xb = x + (long)b * Tl * Hl * Wl * C;
-    const float* gbb = gb ? gb + (long)b * H * W * 2 * C : nullptr;
+    const float* gbb = gb ? gb + (long)(SH ? (gr0 + b) / gk : b) * H * W * 2 * C : nullptr;
     const int nchunk = C >> 4;
     const long xstride = (long)Hl * Wl * C;
     const int lane = threadIdx.x & 63, jj = lane >> 2;   // jj: position of the pair inside the wave's 16-pair segment
@@ -420,11 +423,11 @@ __device__ __forceinline__ void mod_pos4_eval(const ModPos4<GB>& m, const float*
 // 32-channel chunk.  The thread mapping stays that of 16-channel chunks: chunk16 = 2 chunk32 + e writes the 8-byte half-piece
 // (q >> 1) * 32 + e * 16 + (q & 1) * 8 of its row.  C is then CinPad: the chunks at and above the tensor's own channels (Cx) hold zeros.
 // The range guard is the split writer's: bit 0 for |V| > 65504 or non-finite values, the maximum |activation| into the layer's slot.
-template <bool GB, bool ONE = false>
+template <bool GB, bool ONE = false, bool SH = false>
 __global__ __launch_bounds__(256) void modulate_wino4_kernel(const float* __restrict__ x, const float2* __restrict__ coef,
                                                              const float* __restrict__ gb, char* __restrict__ out, int T, int H,
                                                              int W, int C, int ut, int us, int lrelu, int* __restrict__ range_flag,
-                                                             int* __restrict__ umax, int Cx = 0) {
+                                                             int* __restrict__ umax, int Cx = 0, int gk = 1, int gr0 = 0) {
     bool bad = false;
     float vmax = 0.f;
     if constexpr (!ONE) Cx = C;
@@ -434,7 +437,7 @@ __global__ __launch_bounds__(256) void modulate_wino4_kernel(const float* __rest
     const int Hl = H / us, Wl = W / us, Tl = T / ut;
     const float2* cp0 = coef ? coef + (long)b * Cx : nullptr;
     const float* xb = x + (long)b * Tl * Hl * Wl * Cx;
-    const float* gbb = GB ? gb + (long)b * H * W * 2 * Cx : nullptr;
+    const float* gbb = GB ? gb + (long)(SH ? (gr0 + b) / gk : b) * H * W * 2 * Cx : nullptr;
     const int nchunk = C >> 4;
     const long xstride = (long)Hl * Wl * Cx;
     const int lane = threadIdx.x & 63, jj = lane >> 2;   // jj: position of the tile inside the wave's 16-tile segment
@@ -683,6 +686,7 @@ struct i2v_dec {
     int wino32 = 1;  // exact-fp32 mode (mma = 0): 1 = 3x3x3 convs from the 8x8 level on run Winograd F(4,3) on the fp32 matrix cores (env I2V_DEC_WINO32=0: direct kernel)
     const float* prep_img = nullptr;   // i2v_dec_prepare: the start frames whose SPADE branches are in the workspace's gbs[] ...
     int prep_B = 0;                    // ... their batch, image size and the workspace they live in (consumed by the next matching forward)
+    int prep_K = 1;                    // ... and the realizations per start frame (i2v_dec_prepare_realizations; prep_B = frames x prep_K)
     int prep_h = 0, prep_w = 0;
     long prep_bstride = 0;
     bool prep_forked = false;          // the prepared maps are being computed on the handle's side stream (ev_lvl[k] mark them complete)
@@ -796,7 +800,9 @@ bool spade_wino_wanted(const i2v_dec* d, const Block& b, const Level& l) {
     return spade_w4_wanted(d, b, l) || (d->has16() && d->wino && d->spw && wino16_supported(2 * b.n_in, 128, 1, l.H, l.W, 1));
 }
 
-DecWs dec_ws(const i2v_dec* d, int B) {
+// B samples; their SPADE maps and scratch (y0, y1, y1v, gb, gbs, py*) are sized for Fg start frames (realizations: Fg = B / K; 0: B)
+DecWs dec_ws(const i2v_dec* d, int B, int Fg = 0) {
+    if (Fg <= 0) Fg = B;
     size_t mx_x = (size_t)16 * d->blk[0].n_in, mx_a = 0, mx_dx = 0, mx_xsin = 0, mx_xslow = 0, mx_y = 0, mx_gb = 0, mx_yv = 0, mx_m6 = 0;
     int cmax = 0;
     for (int k = 0; k < 6; ++k) {
@@ -824,8 +830,8 @@ DecWs dec_ws(const i2v_dec* d, int B) {
     L.xA = take(B * mx_x); L.xB = take(B * mx_x);
     L.a = take(B * mx_a); L.dx = take(B * mx_dx);
     L.xs_in = take(B * mx_xsin); L.xs_low = take(B * mx_xslow);
-    L.y0 = take(B * mx_y * 16); L.y1 = take(B * mx_y * 128); L.gb = take(B * mx_gb);
-    L.y1v = take(B * mx_yv * 256);  // Winograd operand V of SPADE's 128-channel activation (8 bytes per activation)
+    L.y0 = take(Fg * mx_y * 16); L.y1 = take(Fg * mx_y * 128); L.gb = take(Fg * mx_gb);
+    L.y1v = take(Fg * mx_yv * 256);  // Winograd operand V of SPADE's 128-channel activation (8 bytes per activation)
     L.has_y1v = mx_yv > 0;
     L.zl = take((size_t)B * d->Nz);
     L.sums1 = take((size_t)B * cmax * 4); L.sums2 = take((size_t)B * cmax * 4);  // doubles: 2 per channel
@@ -842,8 +848,8 @@ DecWs dec_ws(const i2v_dec* d, int B) {
         L.splitk_floats = (size_t)B * mx;
         L.splitk = take(L.splitk_floats);
     }
-    for (int k = 0; k < 6; ++k) L.gbs[k] = take((size_t)B * d->lvl[k].H * d->lvl[k].W * 2 * d->blk[k].n_in);
-    L.py0 = take(B * mx_y * 16); L.py1 = take(B * mx_y * 128); L.py1v = take(B * mx_yv * 256);
+    for (int k = 0; k < 6; ++k) L.gbs[k] = take((size_t)Fg * d->lvl[k].H * d->lvl[k].W * 2 * d->blk[k].n_in);
+    L.py0 = take(Fg * mx_y * 16); L.py1 = take(Fg * mx_y * 128); L.py1v = take(Fg * mx_yv * 256);
     L.m6 = take(B * mx_m6);   // exact-fp32 Winograd: the six partial outputs M_x
     L.total = o;
     return L;
@@ -872,12 +878,18 @@ int run_coef(const double* sums, float* coef, int B, int C, int groups, double c
 }
 
 int run_modulate(const float* x, const float* coef, const float* gb, float* out, int B, int T, int H, int W, int C, int ut,
-                 int us, int lrelu, hipStream_t st, bool hl16 = false, int* range_flag = nullptr, int* umax = nullptr) {
+                 int us, int lrelu, hipStream_t st, bool hl16 = false, int* range_flag = nullptr, int* umax = nullptr, GbRows rows = {}) {
     I2V_REQUIRE(C % 8 == 0, I2V_E_INVALID, "modulate: channels %d not a multiple of 8", C);
     const long per = (long)H * W * (C / 8);  // threads per sample (each loops over the T frames)
     I2V_REQUIRE(per * T < (1L << 31), I2V_E_INVALID, "modulate: tensor too large");
     const unsigned gx = (unsigned)std::min<long>((per + 255) / 256, 8192);
-    if (hl16)
+    if (gb && rows.shared() && hl16)
+        hipLaunchKernelGGL((modulate_kernel<true, true>), dim3(gx, B), dim3(256), 0, st, x, reinterpret_cast<const float2*>(coef), gb, out,
+                           T, H, W, C, ut, us, lrelu, range_flag, umax, rows.k, rows.r0);
+    else if (gb && rows.shared())
+        hipLaunchKernelGGL((modulate_kernel<false, true>), dim3(gx, B), dim3(256), 0, st, x, reinterpret_cast<const float2*>(coef), gb, out,
+                           T, H, W, C, ut, us, lrelu, range_flag, umax, rows.k, rows.r0);
+    else if (hl16)
         hipLaunchKernelGGL(modulate_kernel<true>, dim3(gx, B), dim3(256), 0, st, x, reinterpret_cast<const float2*>(coef), gb, out,
                            T, H, W, C, ut, us, lrelu, range_flag, umax);
     else
@@ -888,13 +900,16 @@ int run_modulate(const float* x, const float* coef, const float* gb, float* out,
 }
 
 int run_modulate_wino4(const float* x, const float* coef, const float* gb, float* out, int B, int T, int H, int W, int C, int ut,
-                       int us, int lrelu, hipStream_t st, int* range_flag, int* umax = nullptr) {
+                       int us, int lrelu, hipStream_t st, int* range_flag, int* umax = nullptr, GbRows rows = {}) {
     I2V_REQUIRE(C % 32 == 0 && W % 4 == 0, I2V_E_INVALID, "modulate (F(4,3) operand): channels %d / width %d", C, W);
     const long per = (long)H * (W / 4) * (C / 4);   // one thread per (h, tile, 4 channels)
     I2V_REQUIRE(per % 64 == 0, I2V_E_INVALID, "modulate (F(4,3) operand): %ld threads per sample (need whole wavefronts)", per);
     I2V_REQUIRE(per * T * 6 < (1L << 31), I2V_E_INVALID, "modulate: tensor too large");
     const unsigned gx = (unsigned)std::min<long>((per + 255) / 256, 8192);
-    if (gb)
+    if (gb && rows.shared())
+        hipLaunchKernelGGL((modulate_wino4_kernel<true, false, true>), dim3(gx, B), dim3(256), 0, st, x, reinterpret_cast<const float2*>(coef), gb,
+                           reinterpret_cast<char*>(out), T, H, W, C, ut, us, lrelu, range_flag, umax, C, rows.k, rows.r0);
+    else if (gb)
         hipLaunchKernelGGL(modulate_wino4_kernel<true>, dim3(gx, B), dim3(256), 0, st, x, reinterpret_cast<const float2*>(coef), gb,
                            reinterpret_cast<char*>(out), T, H, W, C, ut, us, lrelu, range_flag, umax);
     else
@@ -906,14 +921,17 @@ int run_modulate_wino4(const float* x, const float* coef, const float* gb, float
 
 // the one-term operand (mma = 3): C channels of x, written as CinPad = C rounded up to 64 (the kernel's chunks come in pairs)
 int run_modulate_wino4h(const float* x, const float* coef, const float* gb, float* out, int B, int T, int H, int W, int C, int ut,
-                        int us, int lrelu, hipStream_t st, int* range_flag, int* umax) {
+                        int us, int lrelu, hipStream_t st, int* range_flag, int* umax, GbRows rows = {}) {
     I2V_REQUIRE(C % 32 == 0 && W % 4 == 0, I2V_E_INVALID, "modulate (one-term F(4,3) operand): channels %d / width %d", C, W);
     const int Cp = (C + 63) / 64 * 64;
     const long per = (long)H * (W / 4) * (Cp / 4);
     I2V_REQUIRE(per % 64 == 0, I2V_E_INVALID, "modulate (one-term F(4,3) operand): %ld threads per sample (need whole wavefronts)", per);
     I2V_REQUIRE(per * T * 6 < (1L << 31), I2V_E_INVALID, "modulate: tensor too large");
     const unsigned gx = (unsigned)std::min<long>((per + 255) / 256, 8192);
-    if (gb)
+    if (gb && rows.shared())
+        hipLaunchKernelGGL((modulate_wino4_kernel<true, true, true>), dim3(gx, B), dim3(256), 0, st, x, reinterpret_cast<const float2*>(coef), gb,
+                           reinterpret_cast<char*>(out), T, H, W, Cp, ut, us, lrelu, range_flag, umax, C, rows.k, rows.r0);
+    else if (gb)
         hipLaunchKernelGGL((modulate_wino4_kernel<true, true>), dim3(gx, B), dim3(256), 0, st, x, reinterpret_cast<const float2*>(coef), gb,
                            reinterpret_cast<char*>(out), T, H, W, Cp, ut, us, lrelu, range_flag, umax, C);
     else
@@ -924,14 +942,18 @@ int run_modulate_wino4h(const float* x, const float* coef, const float* gb, floa
 }
 
 int run_modulate_wino(const float* x, const float* coef, const float* gb, float* out, int B, int T, int H, int W, int C, int ut,
-                      int us, int lrelu, hipStream_t st, int* range_flag, int* umax = nullptr) {
+                      int us, int lrelu, hipStream_t st, int* range_flag, int* umax = nullptr, GbRows rows = {}) {
     I2V_REQUIRE(C % 32 == 0 && W % 2 == 0, I2V_E_INVALID, "modulate (Winograd operand): channels %d / width %d", C, W);
     const long per = (long)H * (W / 2) * (C / 8) * 2;
     I2V_REQUIRE(per % 64 == 0, I2V_E_INVALID, "modulate (Winograd operand): %ld threads per sample (need whole wavefronts)", per);
     I2V_REQUIRE(per * T * 4 < (1L << 31), I2V_E_INVALID, "modulate: tensor too large");
     const unsigned gx = (unsigned)std::min<long>((per + 255) / 256, 8192);
-    hipLaunchKernelGGL(modulate_wino_kernel, dim3(gx, B), dim3(256), 0, st, x, reinterpret_cast<const float2*>(coef), gb,
-                       reinterpret_cast<char*>(out), T, H, W, C, ut, us, lrelu, range_flag, umax);
+    if (gb && rows.shared())
+        hipLaunchKernelGGL(modulate_wino_kernel<true>, dim3(gx, B), dim3(256), 0, st, x, reinterpret_cast<const float2*>(coef), gb,
+                           reinterpret_cast<char*>(out), T, H, W, C, ut, us, lrelu, range_flag, umax, rows.k, rows.r0);
+    else
+        hipLaunchKernelGGL(modulate_wino_kernel<false>, dim3(gx, B), dim3(256), 0, st, x, reinterpret_cast<const float2*>(coef), gb,
+                           reinterpret_cast<char*>(out), T, H, W, C, ut, us, lrelu, range_flag, umax);
     I2V_HIP_CHECK(hipGetLastError());
     return I2V_OK;
 }
@@ -1013,11 +1035,11 @@ int conv3_w4h(i2v_dec* d, const Wino4hWeights& w, const float* v16, float* out, 
 // the same conv with the operand generated in the kernel (no operand-writer launch in front): x = the conv's fp32 input before the
 // modulation, coef / gb as the writer takes them
 int conv3_w4g(i2v_dec* d, const Wino4Weights& w, const float* x, const float* coef, const float* gb, int us, float* out, const float* res, int rt,
-              int rs, int B, const Level& l, int epi, hipStream_t st, double* stats, int* flag, int* umax) {
+              int rs, int B, const Level& l, int epi, hipStream_t st, double* stats, int* flag, int* umax, GbRows rows = {}) {
     if (stats) I2V_HIP_CHECK(hipMemsetAsync(stats, 0, (size_t)B * w.Cout * 16, st));
     const double fl = 2.0 * B * l.T * l.H * l.W * (double)w.Cin * w.Cout * 27.0;
     ProfScope ps(d, st, fl, 3.0 * fl * 0.5);
-    return wino4g_forward(w, x, coef, gb, us, out, res, rt, rs, B, l.T, l.H, l.W, epi, st, stats, flag, umax);
+    return wino4g_forward(w, x, coef, gb, us, out, res, rt, rs, B, l.T, l.H, l.W, epi, st, stats, flag, umax, rows);
 }
 
 // which kernel conv_0 / conv_1 of a block use at this geometry (want_*: by shape; use_*: and the weights are packed for it)
@@ -1085,6 +1107,7 @@ struct BlockBufs {
     float* m6 = nullptr;          // exact-fp32 Winograd scratch (six partial outputs); null: the direct kernel is used
     hipStream_t side = nullptr;   // the learned shortcut runs on this stream (events ev_x / ev_s of the handle), with coef_s
     float* coef_s = nullptr;
+    GbRows rows;                  // realizations: rows.k samples share a start frame; img / gb / gb_ready then hold the launch's FRAMES
 };
 
 // SPADE's conditioning branch of one block (normalization_layer.py:20-23): resize(start frame) -> Conv2d(3, 128) + lrelu ->
@@ -1155,9 +1178,12 @@ int block_forward(i2v_dec* d, int k, Block& b, const Level& l, const float* x, f
     }
     // SPADE branch (normalization_layer.py:20-23): depends on the start frame only -- either computed here, or already there
     // (w.gb_ready: i2v_dec_prepare ran it, typically on a side stream underneath the cINN pass)
+    // (realizations: the B samples of this launch span Bg start frames -- the branch runs once per frame)
+    const GbRows rows = w.rows;
+    const int Bg = rows.shared() ? (rows.r0 + B - 1) / rows.k + 1 : B;
     if (w.gb_ready) gb = const_cast<float*>(w.gb_ready);
-    else if ((rc = spade_branch(d, b, l, img, img_h, img_w, B, y0, y1, w.y1v, gb, st))) return rc;
-    if ((rc = tap(k, 0, gb, (size_t)B * l.H * l.W * 2 * b.n_in))) return rc;
+    else if ((rc = spade_branch(d, b, l, img, img_h, img_w, Bg, y0, y1, w.y1v, gb, st))) return rc;
+    if ((rc = tap(k, 0, gb, (size_t)Bg * l.H * l.W * 2 * b.n_in))) return rc;
     // per conv: split-fp16 or exact fp32 (mma = 0: all fp32; mma = auto: the layers the range guard switched, i2v_dec::fp32_layer)
     const bool f16_0 = d->layer16((2 * k) % 12), f16_1 = d->layer16((2 * k + 1) % 12);
     const bool tdup = f16_0 && b.tdup0;  // a0 is kept at the half temporal rate (its frames 2i and 2i+1 coincide)
@@ -1173,12 +1199,12 @@ int block_forward(i2v_dec* d, int k, Block& b, const Level& l, const float* x, f
     const bool g0 = d->gen == 1 && q0 && !h0 && !tdup && l.ut == 1 && l.us == 2 && !d->tap_dst && wino4g_supported(b.n_mid, b.n_in, l.T, l.H, l.W, 2);
     const bool g1 = d->gen && q1 && !h1 && !d->tap_dst && wino4g_supported(b.n_out, b.n_mid, l.T, l.H, l.W, 1);
     if (g0) rc = I2V_OK;
-    else if (f0) rc = modulate_wino4_f32(x, coef, gb, a, B, l.T, l.H, l.W, b.n_in, l.ut, l.us, 1, st);
-    else if (h0) rc = run_modulate_wino4h(x, coef, gb, a, B, tdup ? l.T / 2 : l.T, l.H, l.W, b.n_in, tdup ? 1 : l.ut, l.us, 1, st, flag, um0);
-    else if (q0) rc = run_modulate_wino4(x, coef, gb, a, B, tdup ? l.T / 2 : l.T, l.H, l.W, b.n_in, tdup ? 1 : l.ut, l.us, 1, st, flag, um0);
-    else if (w0) rc = run_modulate_wino(x, coef, gb, a, B, tdup ? l.T / 2 : l.T, l.H, l.W, b.n_in, tdup ? 1 : l.ut, l.us, 1, st, flag, um0);
-    else if (tdup) rc = run_modulate(x, coef, gb, a, B, l.T / 2, l.H, l.W, b.n_in, 1, l.us, 1, st, true, flag, um0);
-    else rc = run_modulate(x, coef, gb, a, B, l.T, l.H, l.W, b.n_in, l.ut, l.us, 1, st, f16_0, flag, um0);
+    else if (f0) rc = modulate_wino4_f32(x, coef, gb, a, B, l.T, l.H, l.W, b.n_in, l.ut, l.us, 1, st, rows);
+    else if (h0) rc = run_modulate_wino4h(x, coef, gb, a, B, tdup ? l.T / 2 : l.T, l.H, l.W, b.n_in, tdup ? 1 : l.ut, l.us, 1, st, flag, um0, rows);
+    else if (q0) rc = run_modulate_wino4(x, coef, gb, a, B, tdup ? l.T / 2 : l.T, l.H, l.W, b.n_in, tdup ? 1 : l.ut, l.us, 1, st, flag, um0, rows);
+    else if (w0) rc = run_modulate_wino(x, coef, gb, a, B, tdup ? l.T / 2 : l.T, l.H, l.W, b.n_in, tdup ? 1 : l.ut, l.us, 1, st, flag, um0, rows);
+    else if (tdup) rc = run_modulate(x, coef, gb, a, B, l.T / 2, l.H, l.W, b.n_in, 1, l.us, 1, st, true, flag, um0, rows);
+    else rc = run_modulate(x, coef, gb, a, B, l.T, l.H, l.W, b.n_in, l.ut, l.us, 1, st, f16_0, flag, um0, rows);
     if (rc) return rc;
     // (the one-term operand is tapped whole: 3 bytes per activation of CinPad channels)
     if (!f0 && !g0 && (rc = tap(k, 1, a, h0 ? (size_t)B * (tdup ? P / 2 : P) * b.conv0_w4h.CinPad * 3 / 4 : (size_t)B * (tdup ? P / 2 : P) * b.n_in))) return rc;
@@ -1186,7 +1212,7 @@ int block_forward(i2v_dec* d, int k, Block& b, const Level& l, const float* x, f
     d->prof_cur_layer = 2 * k;
     d->prof_cur_kernel = h0 ? 6 : g0 ? 4 : q0 ? 3 : w0 ? 2 : f16_0 ? 1 : f0 ? 5 : 0;
     if (h0) rc = conv3_w4h(d, b.conv0_w4h, a, dx, nullptr, 1, 1, B, l, EPI_NONE, st, fuse ? sums2 : nullptr);
-    else if (g0) rc = conv3_w4g(d, b.conv0_w4, x, coef, gb, 2, dx, nullptr, 1, 1, B, l, EPI_NONE, st, fuse ? sums2 : nullptr, flag, um0);
+    else if (g0) rc = conv3_w4g(d, b.conv0_w4, x, coef, gb, 2, dx, nullptr, 1, 1, B, l, EPI_NONE, st, fuse ? sums2 : nullptr, flag, um0, rows);
     else if (f0) rc = conv3_wf(d, b.conv0_wf, a, w.m6, dx, nullptr, 1, 1, B, l, EPI_NONE, st);
     else if (q0) rc = conv3_w4(d, b.conv0_w4, a, dx, nullptr, 1, 1, B, l, EPI_NONE, st, fuse ? sums2 : nullptr);
     else if (w0) rc = conv3_w(d, b.conv0_w, a, dx, nullptr, 1, 1, B, l, EPI_NONE, st, fuse ? sums2 : nullptr);
@@ -1535,6 +1561,12 @@ size_t i2v_dec_workspace_bytes(const i2v_dec* d, int32_t batch, int32_t img_h, i
     return dec_ws(d, batch).total;
 }
 
+size_t i2v_dec_workspace_bytes_realizations(const i2v_dec* d, int32_t frames, int32_t realizations, int32_t img_h, int32_t img_w) {
+    (void)img_h; (void)img_w;
+    if (!d || frames <= 0 || realizations <= 0 || (int64_t)frames * realizations > INT32_MAX) return 0;
+    return dec_ws(d, frames * realizations, frames).total;
+}
+
 double i2v_dec_flops_per_sample(const i2v_dec* d, int32_t img_h, int32_t img_w) {
     (void)img_h; (void)img_w;
     if (!d) return 0.0;
@@ -1660,8 +1692,9 @@ int i2v_dec_forward(i2v_dec* d, const float* img, int32_t img_h, int32_t img_w, 
 
 }  // extern "C"
 
+// batch = samples; K = realizations per start frame: img holds batch / K frames, sample s decodes frame s / K (K = 1: the plain forward)
 static int dec_forward_once(i2v_dec* d, const float* img, int32_t img_h, int32_t img_w, int64_t img_bstride, const float* motion, float* out,
-                            int64_t out_bstride, void* workspace, size_t workspace_bytes, int32_t batch, void* stream) {
+                            int64_t out_bstride, void* workspace, size_t workspace_bytes, int32_t batch, int K, void* stream) {
     // One prepare serves at most the NEXT forward on the handle: whatever happens below (range error of the previous call, bad
     // argument, workspace too small), a prepared set of SPADE maps must never survive into a later call, whose start frames can
     // sit at the same address (caching allocators, buffers refilled in place).
@@ -1672,6 +1705,8 @@ static int dec_forward_once(i2v_dec* d, const float* img, int32_t img_h, int32_t
     I2V_REQUIRE(img && motion && out && workspace && batch > 0 && img_h > 0 && img_w > 0, I2V_E_INVALID,
                 "i2v_dec_forward: null argument or bad size");
     const int B = batch;
+    I2V_REQUIRE(K >= 1 && B % K == 0, I2V_E_INVALID, "i2v_dec_forward: %d samples are not a multiple of %d realizations", B, K);
+    const int Fr = B / K;   // start frames
     {
         const Level& lo = d->lvl[5];
         const int64_t img_dense = (int64_t)3 * img_h * img_w, out_dense = (int64_t)lo.T * 3 * lo.H * lo.W;
@@ -1682,7 +1717,7 @@ static int dec_forward_once(i2v_dec* d, const float* img, int32_t img_h, int32_t
         if (out_bstride == 0) out_bstride = out_dense;
         d->img_bstride = img_bstride;
     }
-    const DecWs L = dec_ws(d, B);
+    const DecWs L = dec_ws(d, B, Fr);
     I2V_REQUIRE(workspace_bytes >= L.total, I2V_E_WORKSPACE, "i2v_dec_forward: workspace %zu < required %zu", workspace_bytes,
                 L.total);
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1704,7 +1739,7 @@ static int dec_forward_once(i2v_dec* d, const float* img, int32_t img_h, int32_t
     bool x_stats_ready = false;
     double* sums3 = reinterpret_cast<double*>(ws + L.sums3);
     // SPADE branches computed ahead by i2v_dec_prepare for exactly these start frames (same pointer, batch, size, workspace)?
-    bool prepared = prep_img == img && d->prep_B == B && d->prep_h == img_h && d->prep_w == img_w && d->prep_ws == workspace &&
+    bool prepared = prep_img == img && d->prep_B == B && d->prep_K == K && d->prep_h == img_h && d->prep_w == img_w && d->prep_ws == workspace &&
                     d->prep_bstride == img_bstride;
     // Prepared on the side stream (i2v_dec_prepare), or not prepared at all: then compute the maps on the handle's side stream now,
     // underneath the first levels (see i2v_dec::overlap).  Either way every block waits for its level's event.
@@ -1717,7 +1752,7 @@ static int dec_forward_once(i2v_dec* d, const float* img, int32_t img_h, int32_t
     if (!forked && d->side_unjoined)
         if (int rcj = d->join_side(st)) return rcj;
     if (!prepared) {
-        if (int rcf = fork_spade(d, L, ws, img, img_h, img_w, B, st, &forked)) return rcf;
+        if (int rcf = fork_spade(d, L, ws, img, img_h, img_w, Fr, st, &forked)) return rcf;
         prepared = forked;
     }
     struct Join {   // an error return below must not leave the caller's stream ahead of the side stream's work on its buffers
@@ -1742,14 +1777,16 @@ static int dec_forward_once(i2v_dec* d, const float* img, int32_t img_h, int32_t
         }
         for (int s0 = 0; s0 < B; s0 += nsub) {
             const int n = std::min(nsub, B - s0);
+            const int f0 = s0 / K;   // the sub-batch's first start frame (K = 1: s0)
             BlockBufs bufs{a, dx, xs_in, xs_low, y0, y1, gb, coef, s_in + (size_t)s0 * b.n_in * 2, sums2, s_out + (size_t)s0 * b.n_out * 2,
                            F(L.splitk), L.splitk_floats, L.has_y1v ? F(L.y1v) : nullptr,
-                           prepared ? F(L.gbs[k]) + (size_t)s0 * l.H * l.W * 2 * b.n_in : nullptr,
+                           prepared ? F(L.gbs[k]) + (size_t)f0 * l.H * l.W * 2 * b.n_in : nullptr,
                            d->has32() && d->wino32 ? F(L.m6) : nullptr,
-                           forked && nsub == B && d->overlap >= 1 && !d->no_side_shortcut ? d->side : nullptr, F(L.coef_s)};
+                           forked && nsub == B && d->overlap >= 1 && !d->no_side_shortcut ? d->side : nullptr, F(L.coef_s),
+                           GbRows{K, s0 % K}};
             bool ready = x_stats_ready;
             if ((rc = block_forward(d, k, d->blk[k], l, x + (size_t)s0 * Pl * b.n_in, xn + (size_t)s0 * P * b.n_out,
-                                    img + (size_t)s0 * (size_t)img_bstride, img_h, img_w, zl + (size_t)s0 * d->Nz, d->Nz, n, bufs, ready, k == 5, st)))
+                                    img + (size_t)f0 * (size_t)img_bstride, img_h, img_w, zl + (size_t)s0 * d->Nz, d->Nz, n, bufs, ready, k == 5, st)))
                 return rc;
             ready_out = ready;
         }
@@ -1795,11 +1832,11 @@ static bool auto_decide(i2v_dec* d) {
     return changed;
 }
 
-extern "C" {
 
-int i2v_dec_forward_strided(i2v_dec* d, const float* img, int32_t img_h, int32_t img_w, int64_t img_bstride, const float* motion, float* out,
-                            int64_t out_bstride, void* workspace, size_t workspace_bytes, int32_t batch, void* stream) {
-    int rc = dec_forward_once(d, img, img_h, img_w, img_bstride, motion, out, out_bstride, workspace, workspace_bytes, batch, stream);
+// one forward; mma = auto: re-run (the same call, shared start frames included) until the range guard is satisfied
+static int dec_forward(i2v_dec* d, const float* img, int32_t img_h, int32_t img_w, int64_t img_bstride, const float* motion, float* out,
+                       int64_t out_bstride, void* workspace, size_t workspace_bytes, int32_t batch, int K, void* stream) {
+    int rc = dec_forward_once(d, img, img_h, img_w, img_bstride, motion, out, out_bstride, workspace, workspace_bytes, batch, K, stream);
     if (rc || !d || d->cfg.mma != 2) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (stream_is_capturing(st)) return rc;   // (a captured forward runs the layer choices made so far; it cannot look at its own flags)
@@ -1813,9 +1850,27 @@ int i2v_dec_forward_strided(i2v_dec* d, const float* img, int32_t img_h, int32_t
         I2V_HIP_CHECK(hipMemsetAsync(d->status_dev, 0, sizeof(int), st));
         *d->status_host = 0;
         d->auto_reruns += 1;
-        if ((rc = dec_forward_once(d, img, img_h, img_w, img_bstride, motion, out, out_bstride, workspace, workspace_bytes, batch, stream))) return rc;
+        if ((rc = dec_forward_once(d, img, img_h, img_w, img_bstride, motion, out, out_bstride, workspace, workspace_bytes, batch, K, stream))) return rc;
     }
     I2V_REQUIRE(false, I2V_E_RANGE, "i2v_dec_forward (mma = auto): the range guard still fires with every layer on the exact-fp32 kernels");
+}
+
+extern "C" {
+
+int i2v_dec_forward_strided(i2v_dec* d, const float* img, int32_t img_h, int32_t img_w, int64_t img_bstride, const float* motion, float* out,
+                            int64_t out_bstride, void* workspace, size_t workspace_bytes, int32_t batch, void* stream) {
+    return dec_forward(d, img, img_h, img_w, img_bstride, motion, out, out_bstride, workspace, workspace_bytes, batch, 1, stream);
+}
+
+int i2v_dec_forward_realizations(i2v_dec* d, const float* img, int32_t img_h, int32_t img_w, int64_t img_bstride, int32_t frames,
+                                 int32_t realizations, const float* motion, float* out, int64_t out_bstride, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+    if (!(frames > 0 && realizations > 0 && (int64_t)frames * realizations <= INT32_MAX)) {
+        if (d) d->prep_img = nullptr;   // (a prepare never survives into a later call: dec_forward_once's rule)
+        I2V_REQUIRE(false, I2V_E_INVALID, "i2v_dec_forward_realizations: %d frames x %d realizations", frames, realizations);
+    }
+    return dec_forward(d, img, img_h, img_w, img_bstride, motion, out, out_bstride, workspace, workspace_bytes, frames * realizations,
+                       realizations, stream);
 }
 
 int i2v_dec_fallback_layers(i2v_dec* d, int32_t* mask, int32_t* reruns) {
@@ -1829,13 +1884,17 @@ int i2v_dec_fallback_layers(i2v_dec* d, int32_t* mask, int32_t* reruns) {
     return I2V_OK;
 }
 
-int i2v_dec_prepare(i2v_dec* d, const float* img, int32_t img_h, int32_t img_w, void* workspace, size_t workspace_bytes, int32_t batch,
-                    void* stream) {
+}  // extern "C"
+
+// batch = samples of the forward this prepares, K = realizations per start frame: the branches run for the batch / K frames of img
+static int dec_prepare(i2v_dec* d, const float* img, int32_t img_h, int32_t img_w, void* workspace, size_t workspace_bytes, int32_t batch,
+                       int K, void* stream) {
     I2V_REQUIRE(d && d->loaded, I2V_E_STATE, "i2v_dec_prepare: weights not loaded");
     if (int rc0 = check_entry(d, "i2v_dec_prepare")) return rc0;
     I2V_REQUIRE(img && workspace && batch > 0 && img_h > 0 && img_w > 0, I2V_E_INVALID, "i2v_dec_prepare: null argument or bad size");
-    const int B = batch;
-    const DecWs L = dec_ws(d, B);
+    I2V_REQUIRE(K >= 1 && batch % K == 0, I2V_E_INVALID, "i2v_dec_prepare: %d samples are not a multiple of %d realizations", batch, K);
+    const int B = batch, Fr = batch / K;
+    const DecWs L = dec_ws(d, B, Fr);
     I2V_REQUIRE(workspace_bytes >= L.total, I2V_E_WORKSPACE, "i2v_dec_prepare: workspace %zu < required %zu", workspace_bytes, L.total);
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (int rco = d->order.entry(st)) return rco;
@@ -1851,15 +1910,29 @@ int i2v_dec_prepare(i2v_dec* d, const float* img, int32_t img_h, int32_t img_w, 
     // on the handle's side stream where possible (ordered behind everything already on `st`): the caller's stream stays free for
     // whatever it can do meanwhile, and the consuming forward waits per level; else inline on `st`
     bool forked = false;
-    if (int rc = fork_spade(d, L, ws, img, img_h, img_w, B, st, &forked)) return rc;
+    if (int rc = fork_spade(d, L, ws, img, img_h, img_w, Fr, st, &forked)) return rc;
     if (!forked)
         for (int k = 0; k < 6; ++k)
-            if (int rc = spade_branch(d, d->blk[k], d->lvl[k], img, img_h, img_w, B, F(L.py0), F(L.py1), L.has_y1v ? F(L.py1v) : nullptr, F(L.gbs[k]), st))
+            if (int rc = spade_branch(d, d->blk[k], d->lvl[k], img, img_h, img_w, Fr, F(L.py0), F(L.py1), L.has_y1v ? F(L.py1v) : nullptr, F(L.gbs[k]), st))
                 return rc;
     d->prep_forked = forked;
-    d->prep_img = img; d->prep_B = B; d->prep_h = img_h; d->prep_w = img_w; d->prep_ws = workspace;
+    d->prep_img = img; d->prep_B = B; d->prep_K = K; d->prep_h = img_h; d->prep_w = img_w; d->prep_ws = workspace;
     d->prep_bstride = (long)3 * img_h * img_w;
     return I2V_OK;
+}
+
+extern "C" {
+
+int i2v_dec_prepare(i2v_dec* d, const float* img, int32_t img_h, int32_t img_w, void* workspace, size_t workspace_bytes, int32_t batch,
+                    void* stream) {
+    return dec_prepare(d, img, img_h, img_w, workspace, workspace_bytes, batch, 1, stream);
+}
+
+int i2v_dec_prepare_realizations(i2v_dec* d, const float* img, int32_t img_h, int32_t img_w, int32_t frames, int32_t realizations,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+    I2V_REQUIRE(frames > 0 && realizations > 0 && (int64_t)frames * realizations <= INT32_MAX, I2V_E_INVALID,
+                "i2v_dec_prepare_realizations: %d frames x %d realizations", frames, realizations);
+    return dec_prepare(d, img, img_h, img_w, workspace, workspace_bytes, frames * realizations, realizations, stream);
 }
 
 int i2v_dec_prepare_cancel(i2v_dec* d) {

@@ -37,15 +37,17 @@ __device__ __forceinline__ void stf4(float* p, f4 v) { *reinterpret_cast<f4*>(p)
 // One thread = one (h, tile j, 4 channels) of one sample, looping over the frames: the per-(sample, channel) coefficients and the
 // SPADE gamma' / beta of its six positions do not depend on t.  x: [B][T/ut][H/us][W/us][C]; coef: per (b, c) pairs (A, B) with
 // norm(x) = x A + B (null: identity); gb: [B][H][W][2C] (gamma' | beta) or null; V: [6][B][T][H][J][C].
+// SH: the maps are shared by gk consecutive samples (realizations); sample b reads map row (gr0 + b) / gk.
+template <bool SH = false>
 __global__ __launch_bounds__(256) void modulate_wino4_f32_kernel(const float* __restrict__ x, const float2* __restrict__ coef,
                                                                  const float* __restrict__ gb, float* __restrict__ V, int T, int H, int W,
-                                                                 int C, int ut, int us, int lrelu, long plane) {
+                                                                 int C, int ut, int us, int lrelu, long plane, int gk = 1, int gr0 = 0) {
     const int C4 = C >> 2, J = W >> 2;
     const int b = blockIdx.y;
     const int per = H * J * C4;
     const int Hl = H / us, Wl = W / us, Tl = T / ut;
     const float* xb = x + (long)b * Tl * Hl * Wl * C;
-    const float* gbb = gb ? gb + (long)b * H * W * 2 * C : nullptr;
+    const float* gbb = gb ? gb + (long)(SH ? (gr0 + b) / gk : b) * H * W * 2 * C : nullptr;
     const long xstride = (long)Hl * Wl * C;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < per; i += gridDim.x * 256) {
         const int c4 = i % C4;
@@ -191,14 +193,18 @@ int Wino4F32Weights::pack(const float* w_src, const float* bias_src, int cout, i
 }
 
 int modulate_wino4_f32(const float* x, const float* coef, const float* gb, float* V, int B, int T, int H, int W, int C, int ut, int us,
-                       int lrelu, hipStream_t st) {
+                       int lrelu, hipStream_t st, GbRows rows) {
     I2V_REQUIRE(C % 4 == 0 && W % 4 == 0, I2V_E_INVALID, "modulate (fp32 F(4,3) operand): channels %d / width %d", C, W);
     const long per = (long)H * (W / 4) * (C / 4);
     I2V_REQUIRE(per < (1L << 31), I2V_E_INVALID, "modulate (fp32 F(4,3) operand): tensor too large");
     const unsigned gx = (unsigned)std::min<long>((per + 255) / 256, 8192);
     const long plane = (long)B * T * H * (W / 4) * C;
-    hipLaunchKernelGGL(modulate_wino4_f32_kernel, dim3(gx, B), dim3(256), 0, st, x, reinterpret_cast<const float2*>(coef), gb, V, T, H, W, C,
-                       ut, us, lrelu, plane);
+    if (gb && rows.shared())
+        hipLaunchKernelGGL(modulate_wino4_f32_kernel<true>, dim3(gx, B), dim3(256), 0, st, x, reinterpret_cast<const float2*>(coef), gb, V, T, H,
+                           W, C, ut, us, lrelu, plane, rows.k, rows.r0);
+    else
+        hipLaunchKernelGGL(modulate_wino4_f32_kernel<false>, dim3(gx, B), dim3(256), 0, st, x, reinterpret_cast<const float2*>(coef), gb, V, T,
+                           H, W, C, ut, us, lrelu, plane);
     I2V_HIP_CHECK(hipGetLastError());
     return I2V_OK;
 }

@@ -12,6 +12,11 @@ embedder that ``Model`` loads from ``Conditioning_Model.model_path`` (row N1, cs
 reference; for checkpoints shipped without it pass ``-embed_npy FILE`` with a precomputed ``[N,E]`` embedding, or
 ``-embed_seed S`` to draw a synthetic one (demo / smoke use).  E is the embedder's width (``Conditioning_Model.z_dim``):
 for endpoint-controlled models the 30 position one-hots are appended by the model, not by the caller.
+
+``-n_realiz K`` (default 1: the reference's strip, byte for byte) samples K videos per start frame through ``Model.sample`` -- the
+embedding and the decoder's SPADE branches run once per frame -- and writes ONE GIF grid: row k is realization k, column i start
+frame i (``utils.auxiliaries.convert_grid2gif``: each row laid out as ``convert_seq2gif`` lays out a strip, one normalisation over
+the whole grid).  The residuals of a batch are drawn as ``Model.sample`` draws them: ``randn(batch * K, z_dim)``, realization fastest.
 """
 import argparse
 import glob
@@ -59,7 +64,10 @@ def main(argv=None):
                         help="decoder matrix-core mode: auto (split-fp16 with the exact-fp32 fallback), 0 exact fp32, 1 split-fp16, "
                              "fp16 one-term half precision (opt-in).  Default: the YAML's Decoder.mma, else I2V_DEC_MMA, else auto")
     parser.add_argument("-raw_npy", type=str, help="also write the uint8 frame strip [T,H,N*W,3] (the GIF's palette is lossy)")
+    parser.add_argument("-n_realiz", type=int, default=1, help="videos per start frame: a GIF grid, row k = realization k")
     args = parser.parse_args(argv)
+    if args.n_realiz < 1:
+        parser.error("-n_realiz must be >= 1")
     os.environ["HIP_VISIBLE_DEVICES"] = args.gpu   # the reference sets CUDA_VISIBLE_DEVICES (generate_samples.py:20)
 
     from get_model import Model
@@ -89,6 +97,23 @@ def main(argv=None):
         torch.manual_seed(args.seed)   # (Model.forward draws torch.randn on the global CPU generator, get_model.py:59)
     bs = args.bs
     length = math.ceil(imgs.size(0) / bs)
+    save_path = args.out_path or f"./assets/results/{path_ds}/"
+    if args.n_realiz > 1:
+        K = args.n_realiz
+        grid = []
+        with torch.no_grad():
+            for i in range(length):
+                batch = imgs[i * bs:(i + 1) * bs].cuda()
+                emb = embeds[i * bs:(i + 1) * bs].cuda() if embeds is not None else None
+                grid.append(model.sample(batch, K, embed=emb).cpu())   # [b, K, T, 3, H, W] (no batch slice: Q3 has no K form)
+                model.check()
+        gif = aux.convert_grid2gif(torch.cat(grid))
+        os.makedirs(os.path.dirname(save_path), exist_ok=True)
+        save_gif(save_path + "results.gif", gif, fps=3)
+        if args.raw_npy:
+            np.save(args.raw_npy, gif.astype(np.uint8))
+        print(f"Animations saved in {save_path}")
+        return
     videos = []
     from i2v_pipeline import LatentPrefetcher
     with torch.no_grad():
@@ -110,7 +135,6 @@ def main(argv=None):
             model.check()   # the .cpu() above synchronised: a range overflow of this batch is reported now, not a call later
     videos = torch.cat(videos)
 
-    save_path = args.out_path or f"./assets/results/{path_ds}/"
     os.makedirs(os.path.dirname(save_path), exist_ok=True)
     gif = aux.convert_seq2gif(videos)
     save_gif(save_path + "results.gif", gif, fps=3)

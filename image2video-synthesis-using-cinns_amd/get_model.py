@@ -6,7 +6,9 @@ Additions over the reference surface (all optional, defaults reproduce the refer
   * ``forward(x_0, cond=None, residual=None, embed=None)``: the latent draw and the conditioning embedding can be
     supplied so that "identical latent samples" is testable (SURVEY §8a M2);
   * ``synthesize(...)``: the same computation WITHOUT the final ``seq[:vid_length]`` slice, which in the reference
-    slices the BATCH dimension (quirk Q3, get_model.py:75); the benchmark and the multi-GPU harness call this."""
+    slices the BATCH dimension (quirk Q3, get_model.py:75); the benchmark and the multi-GPU harness call this;
+  * ``sample(x_0, n, ...)``: n realizations per start frame (``-n_realiz`` of the reference's evaluation scripts), with the
+    start-frame work -- conditioning embedding, the decoder's SPADE branches -- done once per frame."""
 import os
 
 import torch
@@ -89,7 +91,7 @@ class Model(torch.nn.Module):
             return self.decode(x_0, self.sample_latent(x_0, cond, residual, embed))
         import i2v_pipeline
         if self._prefetch is None or self._prefetch.stream.device != x_0.device:
-            self._prefetch = i2v_pipeline.LatentPrefetcher(lambda a, b, c, d: self.sample_latent(a, b, c, d), device=x_0.device)
+            self._prefetch = i2v_pipeline.LatentPrefetcher(self._latent, device=x_0.device)
             # Three streams at every N: the caller's, this prefetch stream, the decoder handle's own side stream.  A rank of a multi-GPU
             # job that collates a STREAM of calls off the compute stream issues its all-gathers on the prefetch stream too
             # (``self.collator(total)``), not on a fourth stream: HIP multiplexes streams onto four hardware queues, and a collation
@@ -101,6 +103,59 @@ class Model(torch.nn.Module):
         self.decoder.prepare(x_0)
         return self.decode(x_0, self._prefetch.get(ticket))
 
+    def _latent(self, x_0, cond, residual, embed, n=1):
+        """The prefetch stream's pass: ``sample_latent``, or for n realizations per frame the embedding of the F frames (embedder and
+        ``cond`` positions at batch F), its rows repeated n times, and the cINN inverse of the F*n residuals."""
+        if n == 1:
+            return self.sample_latent(x_0, cond, residual, embed)
+        emb = self.flow._embed(x_0, [x_0, cond], embed).repeat_interleave(n, 0)   # full width: the flow uses it as is
+        return self.flow(residual, [x_0, cond], reverse=True, embed=emb).view(residual.size(0), -1)
+
+    @staticmethod
+    def _sample_args(x_0, n, residual, z_dim):
+        """Shape checks of ``sample`` (before anything touches a device); returns the residual as [F*n, z_dim] or None."""
+        if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+            raise ValueError(f"sample: n must be an int >= 1, got {n!r}")
+        if x_0.dim() != 4 or x_0.shape[1] != 3:
+            raise ValueError(f"sample: expected start frames x_0 [F,3,H,W], got {tuple(x_0.shape)}")
+        F = x_0.shape[0]
+        if residual is None:
+            return None
+        if tuple(residual.shape) == (F, n, z_dim):
+            return residual.reshape(F * n, z_dim)
+        if tuple(residual.shape) != (F * n, z_dim):
+            raise ValueError(f"sample: residual must be [F*n, {z_dim}] = [{F * n}, {z_dim}] or [F, n, {z_dim}] = [{F}, {n}, {z_dim}], "
+                             f"got {tuple(residual.shape)}")
+        return residual
+
+    @torch.no_grad()
+    def sample(self, x_0, n, cond=None, residual=None, embed=None):
+        """n realizations per start frame: x_0 [F,3,H,W] -> [F, n, 16*ceil(vid_length/16), 3, H, W]; [f, k] is realization k of frame f.
+        The same videos as ``synthesize(x_0.repeat_interleave(n, 0), ...)`` with the same residuals and embeddings, but the start-frame
+        work runs once per frame: the conditioning embedding (``embed`` [F, E] or the embedder at batch F; ``cond`` [F, 3] positions for
+        endpoint-controlled models) -- its rows are then repeated for the cINN at F*n -- and the decoder's SPADE branches
+        (``Generator.forward(..., realizations=n)``).  ``residual``: [F*n, z_dim] (frame-major) or [F, n, z_dim]; None draws
+        ``torch.randn(F*n, z_dim)`` on the CPU generator, as ``synthesize`` does.  n = 1 is ``synthesize(x_0).unsqueeze(1)``, bit for bit.
+        The cINN pass overlaps the decoder's SPADE branches exactly as in ``synthesize``."""
+        residual = self._sample_args(x_0, n, residual, self.z_dim)
+        F = x_0.shape[0]
+        if n == 1:
+            return self.synthesize(x_0, cond, residual, embed).unsqueeze(1)
+        if residual is None:
+            residual = torch.randn(F * n, self.z_dim).cuda()  # CPU generator, like get_model.py:59
+        if not (self.overlap and x_0.is_cuda) or torch.cuda.is_current_stream_capturing():
+            seq = self.decoder.decode_sequence(x_0, self._latent(x_0, cond, residual, embed, n), self.vid_length, realizations=n)
+            return seq.view(F, n, *seq.shape[1:])
+        import i2v_pipeline
+        if self._prefetch is None or self._prefetch.stream.device != x_0.device:
+            self._prefetch = i2v_pipeline.LatentPrefetcher(self._latent, device=x_0.device)
+            self.decoder.share_side_stream(None)   # (see synthesize)
+        x_0 = x_0.contiguous()
+        ticket = self._prefetch.submit(x_0, cond, residual, embed, n=n)
+        self.decoder.prepare(x_0, realizations=n)
+        seq = self.decoder.decode_sequence(x_0, self._prefetch.get(ticket), self.vid_length, realizations=n)
+        return seq.view(F, n, *seq.shape[1:])
+
     def collator(self, total, group=None, device=None):
         """``i2v_dist.OverlappedCollator`` for a stream of ``synthesize`` calls on this rank's shard of a ``total``-sample job: every
         call's all-gather is issued on the stream the cINN prefetch runs on (see ``synthesize``), overlapping the next call."""
@@ -108,7 +163,7 @@ class Model(torch.nn.Module):
         import i2v_pipeline
         if self._prefetch is None:
             dev = device if device is not None else torch.device("cuda", torch.cuda.current_device())
-            self._prefetch = i2v_pipeline.LatentPrefetcher(lambda a, b, c, d: self.sample_latent(a, b, c, d), device=dev)
+            self._prefetch = i2v_pipeline.LatentPrefetcher(self._latent, device=dev)
             self.decoder.share_side_stream(None)
         return i2v_dist.OverlappedCollator(total, group=group, stream=self._prefetch.stream)
 

@@ -101,6 +101,10 @@ SYMBOLS = {
                                           c_int32, c_void_p]),
     "i2v_dec_prepare": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_size_t, c_int32, c_void_p]),
     "i2v_dec_prepare_cancel": (c_int32, [c_void_p]),
+    "i2v_dec_workspace_bytes_realizations": (c_size_t, [c_void_p, c_int32, c_int32, c_int32, c_int32]),
+    "i2v_dec_forward_realizations": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_int64,
+                                               c_void_p, c_size_t, c_void_p]),
+    "i2v_dec_prepare_realizations": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_size_t, c_void_p]),
     "i2v_dec_join": (c_int32, [c_void_p, c_void_p]),
     "i2v_dec_set_side_stream": (c_int32, [c_void_p, c_void_p]),
     "i2v_dec_fallback_layers": (c_int32, [c_void_p, POINTER(c_int32), POINTER(c_int32)]),
@@ -301,6 +305,20 @@ class NativeFlow(_Handle):
         return self._run(x, embed, True)
 
 
+def check_realizations(img, motion, z_dim, realizations):
+    """Arguments of a decoder call with ``realizations`` = K samples per start frame: K an int >= 1, and -- for K > 1, where given --
+    ``img`` [F,3,H,W] with ``motion`` [F*K, z_dim].  Raises I2VError before anything touches a device; returns K.  (K = 1 leaves the
+    shapes to the plain forward's own checks.)"""
+    if isinstance(realizations, bool) or not isinstance(realizations, int) or realizations < 1:
+        raise I2VError(f"decoder: realizations must be an int >= 1, got {realizations!r}")
+    K = realizations
+    if K > 1 and img is not None:
+        if img.dim() != 4 or img.shape[1] != 3 or motion.dim() != 2 or tuple(motion.shape) != (img.shape[0] * K, z_dim):
+            raise I2VError(f"decoder: expected img [F,3,H,W] and motion [F*{K},{z_dim}] for {K} realizations, got {tuple(img.shape)}, "
+                           f"{tuple(motion.shape)}")
+    return K
+
+
 class NativeDecoder(_Handle):
     """Handle for ``i2v_dec_*`` (Generator, decoder.py:55-120)."""
 
@@ -416,17 +434,23 @@ class NativeDecoder(_Handle):
         except RuntimeError:
             return None
 
+    def workspace_bytes(self, frames, img_h, img_w, realizations=1):
+        """Workspace of a forward on ``frames`` start frames with ``realizations`` samples each (i2v_dec_workspace_bytes_realizations)."""
+        return int(lib().i2v_dec_workspace_bytes_realizations(self._h, frames, check_realizations(None, None, None, realizations), img_h, img_w))
+
     @_on_device
-    def prepare(self, img):
+    def prepare(self, img, realizations=1):
         """i2v_dec_prepare: enqueue the SPADE branches of all six blocks (they depend on the start frame only) on the HANDLE's side
         stream, ordered behind everything already on the current stream; the next ``forward`` with the SAME tensor (same storage,
         batch, size) waits for them per level instead of computing them.  The current stream stays free (e.g. for the cINN pass).
         Inference tensors (``torch.inference_mode``) carry no version counter, so an in-place refill between the prepare and its
-        forward could not be detected: for them this is a no-op and the forward computes the branches itself (same bits)."""
+        forward could not be detected: for them this is a no-op and the forward computes the branches itself (same bits).
+        ``realizations``: the prepare serves ``forward(img, motion, realizations=K)`` with the same K (i2v_dec_prepare_realizations)."""
         # every check BEFORE any state changes: a raise must leave the Python side and the C side agreeing (nothing prepared)
         if getattr(self, "_prep", None) is not None:
             self._prep = None
             _check(lib().i2v_dec_prepare_cancel(self._h), "i2v_dec_prepare_cancel")
+        K = check_realizations(None, None, None, realizations)
         _require_gpu(img)
         B = img.shape[0]
         if img.dim() != 4 or img.shape[1] != 3:
@@ -434,10 +458,16 @@ class NativeDecoder(_Handle):
         ver = self._version(img)
         if ver is None:
             return
-        nbytes = lib().i2v_dec_workspace_bytes(self._h, B, img.shape[2], img.shape[3])
-        ws = self._workspace(nbytes, img.device)
-        _check(lib().i2v_dec_prepare(self._h, img.data_ptr(), img.shape[2], img.shape[3], ws.data_ptr(), ws.numel(), B, _stream()),
-               "i2v_dec_prepare")
+        if K == 1:
+            nbytes = lib().i2v_dec_workspace_bytes(self._h, B, img.shape[2], img.shape[3])
+            ws = self._workspace(nbytes, img.device)
+            _check(lib().i2v_dec_prepare(self._h, img.data_ptr(), img.shape[2], img.shape[3], ws.data_ptr(), ws.numel(), B, _stream()),
+                   "i2v_dec_prepare")
+        else:
+            nbytes = lib().i2v_dec_workspace_bytes_realizations(self._h, B, K, img.shape[2], img.shape[3])
+            ws = self._workspace(nbytes, img.device)
+            _check(lib().i2v_dec_prepare_realizations(self._h, img.data_ptr(), img.shape[2], img.shape[3], B, K, ws.data_ptr(), ws.numel(),
+                                                      _stream()), "i2v_dec_prepare_realizations")
         # the C side recognises the prepared frames by ADDRESS; a caching allocator hands the same address to the next same-size
         # tensor and a buffer refilled in place keeps it, so the binding also remembers WHICH tensor (weak) and its version
         self._prep = (weakref.ref(img), ver)
@@ -456,10 +486,14 @@ class NativeDecoder(_Handle):
         return (t.data_ptr(), bs) if bs >= inner else None
 
     @_on_device
-    def forward(self, img, motion, out=None):
+    def forward(self, img, motion, out=None, realizations=1):
         """i2v_dec_forward_strided.  ``img``: [B,3,H,W] whose samples are contiguous [3,H,W] blocks (any sample stride: e.g. the view
         ``seq[:, -1]`` of a [B,T,3,H,W] buffer).  ``out``: optional float32 view [B,T,3,H,W] with contiguous [T,3,H,W] sample blocks
-        (e.g. ``buf[:, 16:32]`` of a [B,32,3,H,W] buffer) that receives the frames; a dense tensor is allocated otherwise."""
+        (e.g. ``buf[:, 16:32]`` of a [B,32,3,H,W] buffer) that receives the frames; a dense tensor is allocated otherwise.
+        ``realizations`` = K > 1 (i2v_dec_forward_realizations): ``img`` holds F start frames, ``motion`` [F*K, z_dim] and ``out`` F*K
+        samples, sample f*K + k = realization k of frame f -- the bits of ``forward(img.repeat_interleave(K, 0), motion)``, with the
+        SPADE branches run once per frame."""
+        K = check_realizations(img, motion, self.z_dim, realizations)
         for t in (img, motion):
             if not t.is_cuda:
                 _require_gpu(t)   # raises: no CPU fallback
@@ -468,7 +502,8 @@ class NativeDecoder(_Handle):
         prep, self._prep = getattr(self, "_prep", None), None
         if prep is not None and (prep[0]() is not img or prep[1] != self._version(img)):
             _check(lib().i2v_dec_prepare_cancel(self._h), "i2v_dec_prepare_cancel")   # another tensor, or this one was written since
-        B = img.shape[0]
+        Fr = img.shape[0]
+        B = Fr * K
         if img.dim() != 4 or img.shape[1] != 3 or motion.shape != (B, self.z_dim):
             raise I2VError(f"decoder: expected img [B,3,H,W] and motion [B,{self.z_dim}], got {tuple(img.shape)}, {tuple(motion.shape)}")
         iv = self._sample_strided(img, img.shape[1:])
@@ -477,7 +512,10 @@ class NativeDecoder(_Handle):
             iv = (img.data_ptr(), 3 * img.shape[2] * img.shape[3])
         if not motion.is_contiguous():
             motion = motion.contiguous()
-        nbytes = lib().i2v_dec_workspace_bytes(self._h, B, img.shape[2], img.shape[3])
+        if K == 1:
+            nbytes = lib().i2v_dec_workspace_bytes(self._h, B, img.shape[2], img.shape[3])
+        else:
+            nbytes = lib().i2v_dec_workspace_bytes_realizations(self._h, Fr, K, img.shape[2], img.shape[3])
         ws = self._workspace(nbytes, img.device)
         T, H, W = self.out_shape
         if out is None:
@@ -486,8 +524,12 @@ class NativeDecoder(_Handle):
         if ov is None:
             raise I2VError(f"decoder: out must be a float32 [B={B},{T},3,{H},{W}] view on {img.device} with contiguous sample blocks, "
                            f"got {tuple(out.shape)} strides {out.stride()}")
-        _check(lib().i2v_dec_forward_strided(self._h, iv[0], img.shape[2], img.shape[3], iv[1], motion.data_ptr(), ov[0], ov[1],
-                                             ws.data_ptr(), ws.numel(), B, _stream()), "i2v_dec_forward_strided")
+        if K == 1:
+            _check(lib().i2v_dec_forward_strided(self._h, iv[0], img.shape[2], img.shape[3], iv[1], motion.data_ptr(), ov[0], ov[1],
+                                                 ws.data_ptr(), ws.numel(), B, _stream()), "i2v_dec_forward_strided")
+        else:
+            _check(lib().i2v_dec_forward_realizations(self._h, iv[0], img.shape[2], img.shape[3], iv[1], Fr, K, motion.data_ptr(), ov[0],
+                                                      ov[1], ws.data_ptr(), ws.numel(), _stream()), "i2v_dec_forward_realizations")
         return out
 
 

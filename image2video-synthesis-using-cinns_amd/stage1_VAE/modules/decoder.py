@@ -75,18 +75,34 @@ class Generator(NativeBacked):
             h.set_side_stream(self._shared_side)
         return h
 
-    def forward(self, img, motion, out=None):
+    def forward(self, img, motion, out=None, realizations=1):
         """decoder.py:97-120.  ``out`` (not a reference argument): a float32 view [B,16,3,H,W] with contiguous sample blocks to
         decode into; ``img`` may be a sample-strided view such as ``seq[:, -1]`` -- together they let the autoregressive loop of
-        ``Model.forward`` (get_model.py:68-73) run without ``torch.cat`` / ``.contiguous()`` copies."""
-        return self.native().forward(img, motion, out=out)
+        ``Model.forward`` (get_model.py:68-73) run without ``torch.cat`` / ``.contiguous()`` copies.
+        ``realizations`` (not a reference argument) = K: ``img`` holds F start frames and ``motion`` F*K latents; sample f*K + k is
+        realization k of frame f.  Same bits as ``forward(img.repeat_interleave(K, 0), motion)``; the SPADE branches run once per frame."""
+        K = native.check_realizations(img, motion, self.z_dim, realizations)
+        if K == 1:
+            return self.native().forward(img, motion, out=out)
+        return self.native().forward(img, motion, out=out, realizations=K)
 
-    def decode_sequence(self, x_0, z, vid_length):
+    def decode_sequence(self, x_0, z, vid_length, realizations=1):
         """get_model.py:68-73 -- ``seq = G(x_0, z); while T < vid_length: seq = cat(seq, G(seq[:, -1], z))`` -- into ONE
         pre-allocated [B, 16*ceil(vid_length/16), 3, H, W] buffer: pass k writes frames [16k, 16k+16) in place and pass k+1 reads
-        its start frames from the strided view seq[:, 16k+15] (i2v_dec_forward_strided).  Same kernels, same bits as the loop."""
+        its start frames from the strided view seq[:, 16k+15] (i2v_dec_forward_strided).  Same kernels, same bits as the loop.
+        ``realizations`` = K: ``x_0`` holds F start frames, ``z`` F*K latents; pass 0 shares each frame's SPADE branches between its K
+        samples, the later passes start from each sample's own last frame (F*K distinct frames, the strided path)."""
+        K = native.check_realizations(x_0, z, self.z_dim, realizations)
         T, H, W = self.native().out_shape
         n = max(1, -(-int(vid_length) // T))
+        if K > 1:
+            if n == 1:
+                return self.forward(x_0, z, realizations=K)
+            seq = torch.empty(x_0.shape[0] * K, n * T, 3, H, W, dtype=torch.float32, device=x_0.device)
+            self.forward(x_0, z, out=seq[:, :T], realizations=K)
+            for k in range(1, n):
+                self.forward(seq[:, k * T - 1], z, out=seq[:, k * T:(k + 1) * T])
+            return seq
         if n == 1:
             return self.forward(x_0, z)
         seq = torch.empty(x_0.shape[0], n * T, 3, H, W, dtype=torch.float32, device=x_0.device)
@@ -102,9 +118,14 @@ class Generator(NativeBacked):
         object.__setattr__(self, "_shared_side", stream)
         self.native().set_side_stream(stream)
 
-    def prepare(self, img):
+    def prepare(self, img, realizations=1):
         """Not a reference method: enqueue the SPADE branches of all blocks for the start frames ``img`` (they do not depend on
         the motion latent) on the native handle's side stream, behind what is already on the current stream.  The next
         ``forward(img, z)`` with the SAME contiguous tensor waits for them level by level instead of computing them
-        (i2v_dec_prepare); ``get_model.Model.synthesize`` uses it to fill the time the cINN pass takes."""
-        self.native().prepare(img.contiguous())
+        (i2v_dec_prepare); ``get_model.Model.synthesize`` uses it to fill the time the cINN pass takes.  ``realizations`` = K: for
+        ``forward(img, z, realizations=K)`` (the branches of the F frames, once each)."""
+        K = native.check_realizations(None, None, None, realizations)
+        if K == 1:
+            self.native().prepare(img.contiguous())
+        else:
+            self.native().prepare(img.contiguous(), realizations=K)

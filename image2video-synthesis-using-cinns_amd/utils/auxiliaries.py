@@ -23,6 +23,37 @@ def convert_seq2gif(sequence):
     return strip * (255.0 / peak)
 
 
+def convert_grid2gif(videos):
+    """``[N, K, T, 3, H, W]`` in [-1, 1] (K realizations of N start frames) -> float array ``[T, K*H, N*W, 3]``: row k is the strip
+    ``convert_seq2gif`` lays out for realization k (the N clips side by side), and ONE normalisation over the whole grid scales its
+    brightest value to 255 (so that the rows stay comparable).  K = 1 is ``convert_seq2gif(videos[:, 0])``."""
+    n, k, t, c, h, w = videos.shape
+    grid = denorm(videos.detach().float().cpu())             # [N, K, T, C, H, W]
+    grid = grid.permute(2, 1, 4, 0, 5, 3).reshape(t, k * h, n * w, c).numpy()
+    peak = float(grid.max())
+    return grid * (255.0 / peak)
+
+
+def tile_images(images, nrow=8, padding=2):
+    """``torchvision.utils.save_image(images, ..., normalize=True)``'s picture as a uint8 array ``[H', W', 3]``: ``images`` [B, 3, H, W]
+    min-max normalised over the whole tensor, tiled ``nrow`` per row with ``padding`` zero pixels around every tile (one image: no
+    padding), rounded as save_image rounds (x * 255 + 0.5, clamped)."""
+    x = images.detach().float().cpu().clone()
+    lo, hi = float(x.min()), float(x.max())
+    x = x.clamp(lo, hi).sub(lo).div(max(hi - lo, 1e-5))
+    b, c, h, w = x.shape
+    if b == 1:
+        grid = x[0]
+    else:
+        xm = min(nrow, b)
+        ym = -(-b // xm)
+        grid = torch.zeros(c, ym * (h + padding) + padding, xm * (w + padding) + padding)
+        for i in range(b):
+            y, xx = divmod(i, xm)
+            grid[:, y * (h + padding) + padding:y * (h + padding) + padding + h, xx * (w + padding) + padding:xx * (w + padding) + padding + w] = x[i]
+    return grid.mul(255).add_(0.5).clamp_(0, 255).permute(1, 2, 0).to(torch.uint8).numpy()
+
+
 @torch.no_grad()
 def sample_prior(dloader, cINN, decoder, z_dim, control=False, generator=None):
     """The sampling loop of the reference's ``evaluate_FVD_prior`` (second caller of cINN^-1 + decoder): for every batch

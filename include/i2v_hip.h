@@ -197,6 +197,22 @@ int i2v_dec_forward_strided(i2v_dec* d, const float* img, int32_t img_h, int32_t
  * that was forked BEFORE the capture began is dropped by it (join it with i2v_dec_join before capturing). */
 int i2v_dec_prepare(i2v_dec* d, const float* img, int32_t img_h, int32_t img_w, void* workspace, size_t workspace_bytes,
                     int32_t batch, void* stream);
+/* Realizations: F start frames, K samples per frame -- sample f*K + k is realization k of frame f (rows frame-major, the
+ * realization index fastest).  img holds the F frames ([F,3,img_h,img_w], frame stride img_bstride: 0 = dense), motion the F*K
+ * latents [F*K][z_dim], out receives F*K samples (out_bstride as for i2v_dec_forward_strided).  The result equals
+ * i2v_dec_forward_strided on the frames repeated K times (repeat_interleave), bit for bit, in every mode; the SPADE conditioning
+ * branches -- they depend on the start frame only -- run once per FRAME, and every SPADE-consuming operand writer reads map row
+ * sample / K.  The workspace holds the gamma | beta maps and the SPADE scratch for F frames, everything else for F*K samples:
+ * i2v_dec_workspace_bytes_realizations(F, K) <= i2v_dec_workspace_bytes(F*K), equal for K = 1.  K = 1 runs the launches of
+ * i2v_dec_forward_strided.  i2v_dec_prepare_realizations is i2v_dec_prepare for such a call (dense frames [F,3,img_h,img_w]); it
+ * serves the next forward only when address, F, K, size and workspace all match, under the rules of i2v_dec_prepare above.
+ * Debug tap 0 (gamma | beta) returns the F frame maps.  No reference counterpart (the reference repeats the frames). */
+size_t i2v_dec_workspace_bytes_realizations(const i2v_dec* d, int32_t frames, int32_t realizations, int32_t img_h, int32_t img_w);
+int i2v_dec_forward_realizations(i2v_dec* d, const float* img, int32_t img_h, int32_t img_w, int64_t img_bstride, int32_t frames,
+                                 int32_t realizations, const float* motion, float* out, int64_t out_bstride, void* workspace,
+                                 size_t workspace_bytes, void* stream);
+int i2v_dec_prepare_realizations(i2v_dec* d, const float* img, int32_t img_h, int32_t img_w, int32_t frames, int32_t realizations,
+                                 void* workspace, size_t workspace_bytes, void* stream);
 /* Drops a pending prepare (no-op without one). */
 int i2v_dec_prepare_cancel(i2v_dec* d);
 /* Makes `stream` wait for everything the handle has enqueued on its own side stream (a forked i2v_dec_prepare that no forward has

@@ -1,0 +1,158 @@
+"""Realizations per start frame, host side: argument checks that raise before anything touches a device, the GIF-grid and
+save_image-style tiling helpers, the new C ABI in the header, and the compiled shared-map operand writers."""
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(REPO, "image2video-synthesis-using-cinns_amd")
+
+
+def test_realization_arguments_are_checked_before_any_device():
+    import i2v_native
+    img, z = torch.zeros(2, 3, 8, 8), torch.zeros(6, 64)
+    for bad in (0, -1, 1.5, True, "2"):
+        with pytest.raises(i2v_native.I2VError, match="realizations"):
+            i2v_native.check_realizations(img, z, 64, bad)
+    assert i2v_native.check_realizations(img, z, 64, 3) == 3
+    with pytest.raises(i2v_native.I2VError, match=r"motion \[F\*4,64\]"):
+        i2v_native.check_realizations(img, z, 64, 4)
+    with pytest.raises(i2v_native.I2VError):
+        i2v_native.check_realizations(img, torch.zeros(6, 32), 64, 3)
+
+
+def test_generator_rejects_bad_realizations_on_the_host():
+    from stage1_VAE.modules.decoder import Generator
+    import i2v_native
+    gen = Generator({"channel_factor": 8, "z_dim": 64, "upsample_s": [2, 1], "upsample_t": [2, 1], "spectral_norm": True, "mma": 1})
+    img = torch.zeros(2, 3, 64, 64)
+    with pytest.raises(i2v_native.I2VError):
+        gen(img, torch.zeros(5, 64), realizations=3)          # 5 != 2 * 3 rows
+    with pytest.raises(i2v_native.I2VError):
+        gen(img, torch.zeros(2, 64), realizations=0)
+    with pytest.raises(i2v_native.I2VError):
+        gen.decode_sequence(img, torch.zeros(4, 64), 32, realizations=3)
+    with pytest.raises(i2v_native.I2VError):
+        gen.prepare(img, realizations=0)
+
+
+def test_model_sample_argument_shapes():
+    from get_model import Model
+    x0 = torch.zeros(2, 3, 64, 64)
+    assert Model._sample_args(x0, 3, None, 64) is None
+    r = torch.arange(2 * 3 * 64, dtype=torch.float32)
+    assert torch.equal(Model._sample_args(x0, 3, r.view(6, 64), 64), r.view(6, 64))
+    assert torch.equal(Model._sample_args(x0, 3, r.view(2, 3, 64), 64), r.view(6, 64))   # [F, n, z]: frame-major rows
+    for bad in (r[:5 * 64].view(5, 64), r.view(3, 2, 64), r.view(6, 32, 2)):
+        with pytest.raises(ValueError, match="residual"):
+            Model._sample_args(x0, 3, bad, 64)
+    for n in (0, -2, 1.0, True):
+        with pytest.raises(ValueError, match="n must be"):
+            Model._sample_args(x0, n, None, 64)
+    with pytest.raises(ValueError, match="x_0"):
+        Model._sample_args(torch.zeros(2, 64, 64), 2, None, 64)
+
+
+def test_grid_gif_layout_and_normalisation():
+    from utils import auxiliaries as aux
+    rng = np.random.default_rng(0)
+    v = torch.from_numpy(rng.uniform(-1, 0.6, (3, 2, 4, 3, 5, 6)).astype(np.float32))   # N = 3 frames, K = 2, T = 4, 5 x 6
+    g = aux.convert_grid2gif(v)
+    assert g.shape == (4, 2 * 5, 3 * 6, 3)
+    assert abs(g.max() - 255.0) < 1e-3                                                  # one peak over the whole grid
+    d = aux.denorm(v).numpy()
+    scale = 255.0 / d.max()
+    for k in range(2):
+        for i in range(3):
+            tile = g[:, k * 5:(k + 1) * 5, i * 6:(i + 1) * 6]                           # row k = realization, column i = frame
+            np.testing.assert_allclose(tile, d[i, k].transpose(0, 2, 3, 1) * scale, rtol=1e-6)
+    # K = 1 is the strip of convert_seq2gif
+    np.testing.assert_allclose(aux.convert_grid2gif(v[:, :1]), aux.convert_seq2gif(v[:, 0]), rtol=1e-6)
+
+
+def test_tile_images_matches_save_image_geometry():
+    from utils import auxiliaries as aux
+    rng = np.random.default_rng(1)
+    x = torch.from_numpy(rng.uniform(-0.7, 0.4, (10, 3, 4, 5)).astype(np.float32))
+    t = aux.tile_images(x)
+    assert t.dtype == np.uint8 and t.shape == (2 * (4 + 2) + 2, 8 * (5 + 2) + 2, 3)   # nrow 8: two rows, padding 2
+    lo, hi = float(x.min()), float(x.max())
+    norm = ((x - lo) / (hi - lo)).numpy()
+    for i in range(10):
+        y, xx = divmod(i, 8)
+        tile = t[2 + y * 6:2 + y * 6 + 4, 2 + xx * 7:2 + xx * 7 + 5]
+        np.testing.assert_array_equal(tile, np.clip(norm[i].transpose(1, 2, 0) * 255 + 0.5, 0, 255).astype(np.uint8))
+    assert t[:2].max() == 0 and t[:, :2].max() == 0                     # padding is zero
+    assert t[2 + 6:, 2 + 2 * 7:].max() == 0                              # the empty slots of the second row
+    assert aux.tile_images(x[:1]).shape == (4, 5, 3)                     # one image: no padding
+    assert aux.tile_images(x[:3]).shape == (4 + 4, 3 * 7 + 2, 3)
+
+
+def test_header_declares_the_realizations_abi():
+    import i2v_native
+    hdr = open(os.path.join(REPO, "include", "i2v_hip.h")).read()
+    for name in ("i2v_dec_workspace_bytes_realizations", "i2v_dec_forward_realizations", "i2v_dec_prepare_realizations"):
+        assert re.search(r"\b%s\(" % name, hdr) and name in i2v_native.SYMBOLS, name
+
+
+def _asm(tmp_path, name, extra=()):
+    import shutil
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("no hipcc")
+    out = tmp_path / (name + ".s")
+    subprocess.run([hipcc, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", *extra, "-I" + os.path.join(PKG, "csrc"), "-S",
+                    "--cuda-device-only", os.path.join(PKG, "csrc", name + ".hip"), "-o", str(out)], check=True, capture_output=True, timeout=900)
+    return out.read_text()
+
+
+def _kernel_bodies(text):
+    return dict(re.findall(r"^(\w+):[^\n]*\n(.*?)\.end_amdhsa_kernel", text, flags=re.S | re.M))
+
+
+def test_shared_map_writers_are_compiled(tmp_path):
+    """Every SPADE-consuming operand writer has its shared-map instantiation (SH = true) next to the plain one, and it needs no more
+    scratch and no more VGPRs than the plain one (the row index is one division per sample, outside the loops)."""
+    bodies = _kernel_bodies(_asm(tmp_path, "i2v_dec"))
+    pairs = [("modulate_kernelILb1ELb1E", "modulate_kernelILb1ELb0E"), ("modulate_kernelILb0ELb1E", "modulate_kernelILb0ELb0E"),
+             ("modulate_wino_kernelILb1E", "modulate_wino_kernelILb0E"),
+             ("modulate_wino4_kernelILb1ELb0ELb1E", "modulate_wino4_kernelILb1ELb0ELb0E"),
+             ("modulate_wino4_kernelILb1ELb1ELb1E", "modulate_wino4_kernelILb1ELb1ELb0E")]
+
+    def use(body):
+        return (int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", body).group(1)),
+                int(re.search(r"\.amdhsa_next_free_vgpr (\d+)", body).group(1)))
+    for sh, plain in pairs:
+        ns, npl = [n for n in bodies if sh in n], [n for n in bodies if plain in n]
+        assert len(ns) == 1 and len(npl) == 1, (sh, ns, npl)
+        (s_sh, v_sh), (s_pl, v_pl) = use(bodies[ns[0]]), use(bodies[npl[0]])
+        assert s_sh <= s_pl and v_sh <= v_pl, (sh, s_sh, v_sh, s_pl, v_pl)
+    f32 = _kernel_bodies(_asm(tmp_path, "i2v_wino32"))
+    assert len([n for n in f32 if "modulate_wino4_f32_kernelILb1E" in n]) == 1
+
+
+def test_wino4g_shared_map_form_static_checks(tmp_path):
+    """The operand-generating F(4,3) kernel's shared-map form (MODE 4) keeps the checks the SPADE form (MODE 1) passes: no scratch,
+    <= 168 VGPRs, two tap loops whose hand-counted waits replay clean and tight, loops entered with nothing in flight."""
+    sys.path.insert(0, os.path.join(REPO, "tools"))
+    import check_asm_waits as caw
+    text = _asm(tmp_path, "i2v_conv16w4g", ("-fno-slp-vectorize",))
+    kernels = re.findall(r"^(_ZN3i2v24conv_wino4g_f16x3_kernelILi9ELi(\d+)ELi4EEEvNS_6W4ArgsENS_9W4GenArgsE):[^\n]*\n(.*?)\.end_amdhsa_kernel",
+                         text, flags=re.S | re.M)
+    assert sorted(k[1] for k in kernels) == ["32", "64"]
+    for name, cin, whole in kernels:
+        assert "scratch_" not in whole and re.search(r"\.amdhsa_private_segment_fixed_size 0\b", whole), name
+        assert int(re.search(r"\.amdhsa_next_free_vgpr (\d+)", whole).group(1)) <= 168, name
+        loops = [m.group(2) for m in re.finditer(r"^(\.LBB\d+_\d+):[^\n]*\n((?:(?!^\.LBB).)*?)s_cbranch_\w+ \1\n", whole, flags=re.S | re.M)
+                 if "v_mfma" in m.group(2)]
+        assert len(loops) == 2, (name, len(loops))
+        for loop, wm in zip(loops, (2, 1)):
+            assert loop.count("v_mfma_f32_32x32x16_f16") == 18 * 3 * wm, name
+            assert caw.check_loop(loop) == [], name
+    assert caw.check_loop_entries(text, r"conv_wino4g_f16x3_kernelILi9ELi\d+ELi4E") == []
+    assert caw.check_scalar_operands(text, r"conv_wino4g_f16x3_kernelILi9ELi\d+ELi4E") == []
