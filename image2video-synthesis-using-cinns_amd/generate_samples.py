@@ -65,6 +65,8 @@ def main(argv=None):
                              "fp16 one-term half precision (opt-in).  Default: the YAML's Decoder.mma, else I2V_DEC_MMA, else auto")
     parser.add_argument("-raw_npy", type=str, help="also write the uint8 frame strip [T,H,N*W,3] (the GIF's palette is lossy)")
     parser.add_argument("-n_realiz", type=int, default=1, help="videos per start frame: a GIF grid, row k = realization k")
+    parser.add_argument("-dev_out", action="store_true",
+                        help="quantise and tile the frames on the GPU (i2v_pipeline.FrameSink): the same bytes, a quarter of the transfer")
     args = parser.parse_args(argv)
     if args.n_realiz < 1:
         parser.error("-n_realiz must be >= 1")
@@ -98,6 +100,8 @@ def main(argv=None):
     bs = args.bs
     length = math.ceil(imgs.size(0) / bs)
     save_path = args.out_path or f"./assets/results/{path_ds}/"
+    if args.dev_out:
+        return _main_dev_out(args, model, imgs, embeds, save_path)
     if args.n_realiz > 1:
         K = args.n_realiz
         grid = []
@@ -140,6 +144,60 @@ def main(argv=None):
     save_gif(save_path + "results.gif", gif, fps=3)
     if args.raw_npy:
         np.save(args.raw_npy, gif.astype(np.uint8))
+    print(f"Animations saved in {save_path}")
+
+
+def _main_dev_out(args, model, imgs, embeds, save_path):
+    """``-dev_out``: the loops of ``main`` with the output routed through a ``FrameSink`` -- the frames stay on the device until the job's
+    peak is known, then ONE uint8 strip (or grid) crosses to the host.  ``model.check()`` still synchronises once per batch.  A job whose
+    frames do not fit the sink's device budget is finished on the host path of ``main`` (same bytes either way)."""
+    from i2v_pipeline import FrameSink, FrameSinkBudgetError, LatentPrefetcher
+    from utils import auxiliaries as aux
+    bs, K = args.bs, args.n_realiz
+    length = math.ceil(imgs.size(0) / bs)
+    sink, host = FrameSink("peak"), None      # host: the batches on the CPU once the sink refused one
+
+    def put(seq):
+        nonlocal host
+        if host is None:
+            try:
+                sink.add(seq)
+                return
+            except FrameSinkBudgetError as e:
+                print(f"-dev_out: {e}")
+                host = [v.cpu() for v in sink.drain()]
+        host.append(seq.cpu())
+
+    def inputs(i):
+        batch = imgs[i * bs:(i + 1) * bs].cuda()
+        return batch, (embeds[i * bs:(i + 1) * bs].cuda() if embeds is not None else None)
+    with torch.no_grad():
+        if K > 1:
+            for i in range(length):
+                batch, emb = inputs(i)
+                put(model.sample(batch, K, embed=emb))
+                model.check()
+        else:
+            pf = LatentPrefetcher(lambda b, e: model.sample_latent(b, embed=e))
+            batch, emb = inputs(0)
+            ticket = pf.submit(batch, emb)
+            for i in range(length):
+                z = pf.get(ticket)
+                cur = batch
+                if i + 1 < length:
+                    batch, emb = inputs(i + 1)
+                    ticket = pf.submit(batch, emb)
+                put(model.decode(cur, z)[:model.vid_length])   # (the BATCH slice of get_model.py:75, Q3)
+                model.check()
+    if host is None:
+        sink.finish()
+        gif = sink.result()
+    else:
+        gif = (aux.convert_grid2gif(torch.cat(host)) if K > 1 else aux.convert_seq2gif(torch.cat(host))).astype(np.uint8)
+    os.makedirs(os.path.dirname(save_path), exist_ok=True)
+    save_gif(save_path + "results.gif", gif, fps=3)
+    if args.raw_npy:
+        np.save(args.raw_npy, gif)
     print(f"Animations saved in {save_path}")
 
 

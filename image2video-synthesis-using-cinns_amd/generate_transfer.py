@@ -26,6 +26,8 @@ def main(argv=None):
     parser.add_argument("-bs", type=int, default=6, help="Batchsize")
     parser.add_argument("-img_path", type=str, help="override ./assets/GT_samples/<dataset>/transfer/")
     parser.add_argument("-out_path", type=str, help="override ./assets/results/<dataset>/")
+    parser.add_argument("-dev_out", action="store_true",
+                        help="quantise and tile the frames on the GPU (i2v_pipeline.FrameSink): the same bytes, a quarter of the transfer")
     args = parser.parse_args(argv)
     os.environ["HIP_VISIBLE_DEVICES"] = args.gpu
 
@@ -52,6 +54,8 @@ def main(argv=None):
     length = math.ceil(videos.size(0) / bs)
     save_path = args.out_path or f"./assets/results/{args.dataset}/"
     os.makedirs(os.path.dirname(save_path), exist_ok=True)
+    if args.dev_out:
+        return _main_dev_out(args, model, videos, save_path)
     for idx, query in enumerate(videos):
         transfer = []
         with torch.no_grad():
@@ -63,6 +67,40 @@ def main(argv=None):
         t = min(transfer.shape[1], query.shape[0])
         transfer = torch.cat((query[None, :t], transfer[:, :t]), dim=0)
         save_gif(save_path + f"transfer_{idx}.gif", aux.convert_seq2gif(transfer), fps=3)
+    print(f"Animations saved in {save_path}")
+
+
+def _main_dev_out(args, model, videos, save_path):
+    """``-dev_out``: per query, the uploaded query clip (column 0) and every transferred batch join one ``FrameSink``; one uint8 strip per
+    GIF crosses to the host.  A job over the sink's device budget is finished on the host path (same bytes)."""
+    from i2v_pipeline import FrameSink, FrameSinkBudgetError
+    from utils import auxiliaries as aux
+    bs = args.bs
+    length = math.ceil(videos.size(0) / bs)
+    sink = FrameSink("peak")
+    for idx, query in enumerate(videos):
+        host = None
+        with torch.no_grad():
+            q = query[None, :].cuda()
+            for i in range(length):
+                out = model.transfer(q, videos[i * bs:(i + 1) * bs, 0].cuda())
+                model.check()
+                t = min(out.shape[1], query.shape[0])
+                for seq in ((q[:, :t], out[:, :t]) if i == 0 else (out[:, :t],)):
+                    if host is None:
+                        try:
+                            sink.add(seq)
+                            continue
+                        except FrameSinkBudgetError as e:
+                            print(f"-dev_out: {e}")
+                            host = [v.cpu() for v in sink.drain()]
+                    host.append(seq.cpu())
+        if host is None:
+            sink.finish()
+            gif = sink.result()
+        else:
+            gif = aux.convert_seq2gif(torch.cat(host)).astype("uint8")
+        save_gif(save_path + f"transfer_{idx}.gif", gif, fps=3)
     print(f"Animations saved in {save_path}")
 
 

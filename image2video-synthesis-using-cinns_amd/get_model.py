@@ -8,7 +8,8 @@ Additions over the reference surface (all optional, defaults reproduce the refer
   * ``synthesize(...)``: the same computation WITHOUT the final ``seq[:vid_length]`` slice, which in the reference
     slices the BATCH dimension (quirk Q3, get_model.py:75); the benchmark and the multi-GPU harness call this;
   * ``sample(x_0, n, ...)``: n realizations per start frame (``-n_realiz`` of the reference's evaluation scripts), with the
-    start-frame work -- conditioning embedding, the decoder's SPADE branches -- done once per frame."""
+    start-frame work -- conditioning embedding, the decoder's SPADE branches -- done once per frame;
+  * ``synthesize_u8(...)`` / ``sample_u8(...)``: the same videos as interleaved uint8 clips, quantised on the device."""
 import os
 
 import torch
@@ -155,6 +156,19 @@ class Model(torch.nn.Module):
         self.decoder.prepare(x_0, realizations=n)
         seq = self.decoder.decode_sequence(x_0, self._prefetch.get(ticket), self.vid_length, realizations=n)
         return seq.view(F, n, *seq.shape[1:])
+
+    @torch.no_grad()
+    def synthesize_u8(self, x_0, cond=None, residual=None, embed=None):
+        """``synthesize`` for callers who want frames and not floats: uint8 ``[B, T', H, W, 3]`` on the device
+        (``utils.auxiliaries.to_uint8_clips`` of the result, quantised by the device kernel on the same stream)."""
+        from utils import auxiliaries as aux
+        return aux.to_uint8_clips(self.synthesize(x_0, cond, residual, embed))
+
+    @torch.no_grad()
+    def sample_u8(self, x_0, n, cond=None, residual=None, embed=None):
+        """``sample`` as uint8 ``[F, n, T', H, W, 3]`` on the device (``to_uint8_clips`` of the result)."""
+        from utils import auxiliaries as aux
+        return aux.to_uint8_clips(self.sample(x_0, n, cond, residual, embed))
 
     def collator(self, total, group=None, device=None):
         """``i2v_dist.OverlappedCollator`` for a stream of ``synthesize`` calls on this rank's shard of a ``total``-sample job: every

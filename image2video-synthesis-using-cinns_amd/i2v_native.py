@@ -41,6 +41,11 @@ class DecCfg(ctypes.Structure):
                 ("upsample_t", c_int32 * 2), ("spectral_norm", c_int32), ("mma", c_int32)]
 
 
+class FramesCfg(ctypes.Structure):
+    _fields_ = [("n", c_int32), ("t", c_int32), ("h", c_int32), ("w", c_int32), ("n_stride", c_int64), ("k", c_int32), ("layout", c_int32),
+                ("dst_row_bytes", c_int64), ("dst_frame_bytes", c_int64), ("dst_bytes", c_int64), ("row0", c_int32), ("col0", c_int32)]
+
+
 class Enc3dCfg(ctypes.Structure):
     _fields_ = [("z_dim", c_int32), ("channels", c_int32 * 5), ("stride_s", c_int32 * 4), ("stride_t", c_int32 * 4),
                 ("use_max_pool", c_int32)]
@@ -114,6 +119,8 @@ SYMBOLS = {
     "i2v_dec_status": (c_int32, [c_void_p, POINTER(c_int32), c_int32, c_void_p]),
     "i2v_dec_get_layer_profile": (c_int32, [c_void_p, c_int32, ctypes.c_char_p, c_int32, POINTER(c_double), POINTER(c_double),
                                             POINTER(c_double), POINTER(c_int64), POINTER(c_int32)]),
+    "i2v_frames_peak": (c_int32, [c_void_p, POINTER(FramesCfg), c_void_p, c_int32, c_void_p]),
+    "i2v_frames_to_u8": (c_int32, [c_void_p, POINTER(FramesCfg), c_void_p, c_void_p, c_int32, c_void_p]),
 }
 
 
@@ -644,6 +651,114 @@ def channel_mean_std(flat):
     with torch.cuda.device(flat.device):
         _check(lib().i2v_row_mean_std(flat.data_ptr(), C, N, mean.data_ptr(), std.data_ptr(), _stream()), "i2v_row_mean_std")
     return mean, std
+
+
+# ---------------------------------------------------------------------------------------------- output stage (csrc/i2v_frames.hip)
+FRAMES_PEAK, FRAMES_UNIT = 0, 1
+FRAMES_STRIP, FRAMES_CLIPS = 0, 1
+
+
+def frames_geometry(x):
+    """Host-side shape check of the output stage's input (before anything touches a device): ``x`` float32 ``[N, T, 3, H, W]`` or
+    ``[F, K, T, 3, H, W]`` whose ``[T, 3, H, W]`` blocks are contiguous, with one element stride between the N (= F*K) samples -- a
+    dense tensor, a ``[:, :16]`` view of a longer buffer, the ``[F, K, ...]`` view of ``Model.sample``.  Returns (n, k, t, h, w, n_stride)."""
+    if not torch.is_tensor(x) or x.dtype != torch.float32 or x.dim() not in (5, 6) or x.shape[-3] != 3 or x.numel() == 0:
+        raise I2VError("frames: expected a non-empty float32 tensor [N,T,3,H,W] or [F,K,T,3,H,W], got "
+                       + (f"{x.dtype} {tuple(x.shape)}" if torch.is_tensor(x) else repr(type(x))))
+    k = x.shape[1] if x.dim() == 6 else 1
+    t, _, h, w = x.shape[-4:]
+    per, inner = t * 3 * h * w, 1
+    for size, stride in zip(reversed(x.shape[-4:]), reversed(x.stride()[-4:])):
+        if size != 1 and stride != inner:
+            raise I2VError(f"frames: the [T,3,H,W] block of a sample must be contiguous (strides {x.stride()})")
+        inner *= size
+    if x.dim() == 6:
+        f = x.shape[0]
+        sk = x.stride(1) if k > 1 else per
+        sf = x.stride(0) if f > 1 else sk * k
+        if sk < per or sf != sk * k:
+            raise I2VError(f"frames: [F,K,...] needs one stride between its F*K samples (strides {x.stride()})")
+        return f * k, k, t, h, w, sk
+    n = x.shape[0]
+    ns = x.stride(0) if n > 1 else per
+    if ns < per:
+        raise I2VError(f"frames: samples overlap (sample stride {ns} < {per})")
+    return n, 1, t, h, w, ns
+
+
+def _frames_peak_cell(out, device):
+    if out is None:
+        return torch.empty(1, dtype=torch.float32, device=device)
+    if not torch.is_tensor(out) or out.dtype != torch.float32 or out.numel() != 1:
+        raise I2VError("frames_peak: out must be a float32 tensor with one element")
+    return out
+
+
+def frames_peak(x, out=None, accumulate=False):
+    """Maximum of all raw values of ``x`` (see ``frames_geometry``) into a one-element float32 DEVICE tensor (i2v_frames_peak; no host
+    round trip).  ``accumulate`` keeps ``max(out, max x)``: one peak for a job converted batch by batch (needs ``out``)."""
+    n, k, t, h, w, ns = frames_geometry(x)
+    if accumulate and out is None:
+        raise I2VError("frames_peak: accumulate=True needs the running peak in out")
+    if out is not None:
+        _frames_peak_cell(out, None)
+    _require_gpu(out)
+    if not x.is_cuda:
+        raise I2VError("frames_peak: libi2v_hip kernels need tensors on a HIP device (got a CPU tensor); this package has no CPU fallback")
+    out = _frames_peak_cell(out, x.device)
+    cfg = FramesCfg(n=n, t=t, h=h, w=w, n_stride=ns, k=1)
+    with torch.cuda.device(x.device):
+        _check(lib().i2v_frames_peak(x.data_ptr(), ctypes.byref(cfg), out.data_ptr(), int(bool(accumulate)), _stream()), "i2v_frames_peak")
+    return out
+
+
+def frames_to_u8(x, peak=None, out=None, mode="peak", layout="strip", row0=0, col0=0):
+    """``x`` (see ``frames_geometry``) -> interleaved uint8 on the device (i2v_frames_to_u8).
+    ``mode`` "peak": GIF semantics of ``convert_seq2gif`` / ``convert_grid2gif``, scaled by the device float ``peak`` of ``frames_peak``
+    (None: the peak of ``x`` itself is taken first); "unit": ``trunc(clamp(denorm(x) * 255 + 0.5, 0, 255))``.
+    ``layout`` "strip": ``[T, K*H, (N/K)*W, 3]`` (a 6-dim ``x`` is a grid: realization k in row k); ``out`` may be a larger contiguous
+    uint8 ``[T, rows, cols, 3]`` tensor of which this call fills the block at pixel (``row0``, ``col0``).  "clips": ``[N, T, H, W, 3]``
+    (``[F, K, T, H, W, 3]`` for a 6-dim ``x``).  Returns ``out``."""
+    n, k, t, h, w, ns = frames_geometry(x)
+    if mode not in ("peak", "unit"):
+        raise I2VError(f"frames_to_u8: mode must be 'peak' or 'unit', got {mode!r}")
+    if layout not in ("strip", "clips"):
+        raise I2VError(f"frames_to_u8: layout must be 'strip' or 'clips', got {layout!r}")
+    if mode == "unit" and peak is not None:
+        raise I2VError("frames_to_u8: mode 'unit' takes no peak")
+    if peak is not None:
+        _frames_peak_cell(peak, None)
+    for name, v in (("row0", row0), ("col0", col0)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+            raise I2VError(f"frames_to_u8: {name} must be an int >= 0, got {v!r}")
+    if layout == "clips":
+        if row0 or col0:
+            raise I2VError("frames_to_u8: the clip layout has no placement (row0 = col0 = 0)")
+        shape = tuple(x.shape[:-4]) + (t, h, w, 3)
+        if out is not None and (out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_contiguous()):
+            raise I2VError(f"frames_to_u8: out must be a contiguous uint8 tensor {shape}")
+    else:
+        shape = (t, k * h, (n // k) * w, 3)
+        if out is not None:
+            if out.dtype != torch.uint8 or out.dim() != 4 or out.shape[0] != t or out.shape[3] != 3 or not out.is_contiguous():
+                raise I2VError(f"frames_to_u8: out must be a contiguous uint8 tensor [{t}, rows, cols, 3], got "
+                               f"{out.dtype} {tuple(out.shape)}")
+            if row0 + k * h > out.shape[1] or col0 + (n // k) * w > out.shape[2]:
+                raise I2VError(f"frames_to_u8: the block [{k * h} x {(n // k) * w}] at ({row0}, {col0}) does not fit out {tuple(out.shape)}")
+    if not x.is_cuda or (out is not None and out.device != x.device) or (peak is not None and peak.device != x.device):
+        raise I2VError("frames_to_u8: libi2v_hip kernels need x, peak and out on one HIP device; this package has no CPU fallback")
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=x.device)
+    if mode == "peak" and peak is None:
+        peak = frames_peak(x)
+    cfg = FramesCfg(n=n, t=t, h=h, w=w, n_stride=ns, k=k if layout == "strip" else 1, layout=FRAMES_STRIP if layout == "strip" else FRAMES_CLIPS,
+                    dst_bytes=out.numel(), row0=row0, col0=col0)
+    if layout == "strip":
+        cfg.dst_row_bytes, cfg.dst_frame_bytes = out.shape[2] * 3, out.shape[1] * out.shape[2] * 3
+    with torch.cuda.device(x.device):
+        _check(lib().i2v_frames_to_u8(x.data_ptr(), ctypes.byref(cfg), peak.data_ptr() if peak is not None else None, out.data_ptr(),
+                                      FRAMES_PEAK if mode == "peak" else FRAMES_UNIT, _stream()), "i2v_frames_to_u8")
+    return out
 
 
 def default_flow_f16():

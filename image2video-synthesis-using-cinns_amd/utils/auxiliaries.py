@@ -34,6 +34,42 @@ def convert_grid2gif(videos):
     return grid * (255.0 / peak)
 
 
+def convert_seq2gif_u8(sequence):
+    """The bytes of ``convert_seq2gif(sequence).astype(np.uint8)``: ``[N, T, 3, H, W]`` -> uint8 ``[T, H, N*W, 3]``.  A CUDA tensor is
+    converted on the device (csrc/i2v_frames.hip: one peak reduction, one interleaving kernel; no host round trip) and a uint8 DEVICE
+    tensor comes back; a CPU tensor takes the numpy path and a numpy array comes back."""
+    if sequence.dim() != 5:
+        raise ValueError(f"convert_seq2gif_u8: expected [N,T,3,H,W], got {tuple(sequence.shape)}")
+    if not sequence.is_cuda:
+        return convert_seq2gif(sequence).astype(np.uint8)
+    import i2v_native
+    return i2v_native.frames_to_u8(sequence.detach(), mode="peak", layout="strip")
+
+
+def convert_grid2gif_u8(videos):
+    """The bytes of ``convert_grid2gif(videos).astype(np.uint8)``: ``[N, K, T, 3, H, W]`` -> uint8 ``[T, K*H, N*W, 3]``; device in, device
+    out, as ``convert_seq2gif_u8``."""
+    if videos.dim() != 6:
+        raise ValueError(f"convert_grid2gif_u8: expected [N,K,T,3,H,W], got {tuple(videos.shape)}")
+    if not videos.is_cuda:
+        return convert_grid2gif(videos).astype(np.uint8)
+    import i2v_native
+    return i2v_native.frames_to_u8(videos.detach(), mode="peak", layout="strip")
+
+
+def to_uint8_clips(sequence):
+    """``[N, T, 3, H, W]`` (or ``[F, K, T, 3, H, W]``) in [-1, 1] -> uint8 ``[N, T, H, W, 3]`` (``[F, K, T, H, W, 3]``): what an encoder or a
+    metric takes.  Fixed scale, rounded as ``tile_images`` rounds: ``denorm(x) * 255 + 0.5``, clamped to [0, 255], truncated.  A CUDA tensor
+    is converted by the device kernel, a CPU tensor by the torch expression; both return a torch tensor on the input's device."""
+    if sequence.dim() not in (5, 6):
+        raise ValueError(f"to_uint8_clips: expected [N,T,3,H,W] or [F,K,T,3,H,W], got {tuple(sequence.shape)}")
+    if sequence.is_cuda:
+        import i2v_native
+        return i2v_native.frames_to_u8(sequence.detach(), mode="unit", layout="clips")
+    x = denorm(sequence.detach().float()).mul(255).add_(0.5).clamp_(0, 255)
+    return x.movedim(-3, -1).to(torch.uint8).contiguous()
+
+
 def tile_images(images, nrow=8, padding=2):
     """``torchvision.utils.save_image(images, ..., normalize=True)``'s picture as a uint8 array ``[H', W', 3]``: ``images`` [B, 3, H, W]
     min-max normalised over the whole tensor, tiled ``nrow`` per row with ``padding`` zero pixels around every tile (one image: no

@@ -42,6 +42,8 @@ def main(argv=None):
     parser.add_argument("-seed", type=int, help="seed the CPU generator the latent residuals are drawn from, right before sampling")
     parser.add_argument("-out_path", type=str, help="override ./assets/results/bair_endpoint/")
     parser.add_argument("-dec_mma", type=str, choices=["auto", "0", "1", "fp16"], default=None, help="decoder matrix-core mode")
+    parser.add_argument("-dev_out", action="store_true",
+                        help="quantise and tile the GIF frames on the GPU (i2v_pipeline.FrameSink): the same bytes, a quarter of the transfer")
     args = parser.parse_args(argv)
     if args.n_realiz < 1 or args.n_samples < 1 or args.bs < 1:
         parser.error("-n_realiz, -n_samples and -bs must be >= 1")
@@ -83,6 +85,8 @@ def main(argv=None):
         torch.manual_seed(args.seed)
     # residual draws in the reference's order (visualize_endpoint.py:37-45): realization outer, batch inner
     res = [[torch.randn(b1 - b0, model.z_dim) for (b0, b1) in batches] for _ in range(K)]
+    if args.dev_out:
+        return _main_dev_out(args, model, imgs, cond, embeds, batches, res)
     videos = []
     with torch.no_grad():
         for j, (b0, b1) in enumerate(batches):
@@ -98,6 +102,37 @@ def main(argv=None):
     for idx, vid in enumerate(videos):
         save_gif(save_path + f"endpoint_{idx}.gif", aux.convert_seq2gif(vid), fps=3)
         Image.fromarray(aux.tile_images(vid[:, -1])).save(save_path + f"endpoint_{idx}.png")
+    print(f"Animations saved in {save_path}")
+
+
+def _main_dev_out(args, model, imgs, cond, embeds, batches, res):
+    """``-dev_out``: every start frame's strip of K realizations (its own peak, as ``convert_seq2gif`` per image) goes through a
+    ``FrameSink`` while the batch's videos stay on the device; only the last frames (``vid[:, -1]``, a sixteenth of the data) are copied
+    as floats, for the ``tile_images`` PNG, whose host code is unchanged."""
+    from PIL import Image
+    from i2v_pipeline import FrameSink, FrameSinkBudgetError
+    from utils import auxiliaries as aux
+    K = args.n_realiz
+    save_path = args.out_path or "./assets/results/bair_endpoint/"
+    os.makedirs(os.path.dirname(save_path), exist_ok=True)
+    sink, idx = FrameSink("peak"), 0
+    with torch.no_grad():
+        for j, (b0, b1) in enumerate(batches):
+            r = torch.stack([res[k][j] for k in range(K)], 1)   # [b, K, z_dim]: realization k of frame f
+            emb = embeds[b0:b1].cuda() if embeds is not None else None
+            vids = model.sample(imgs[b0:b1].cuda(), K, cond=cond[b0:b1], residual=r.cuda(), embed=emb)   # [b, K, T, 3, H, W], device
+            model.check()
+            for vid in vids[:max(0, args.n_samples - idx)]:
+                try:
+                    sink.add(vid)
+                    sink.finish()
+                    gif = sink.result()
+                except FrameSinkBudgetError as e:
+                    print(f"-dev_out: {e}")
+                    gif = aux.convert_seq2gif(vid).astype(np.uint8)
+                save_gif(save_path + f"endpoint_{idx}.gif", gif, fps=3)
+                Image.fromarray(aux.tile_images(vid[:, -1])).save(save_path + f"endpoint_{idx}.png")
+                idx += 1
     print(f"Animations saved in {save_path}")
 
 

@@ -333,6 +333,38 @@ size_t i2v_encoder3d_workspace_bytes(const i2v_encoder3d* e, int32_t batch, int3
 int i2v_encoder3d_forward(i2v_encoder3d* e, const float* x, int32_t t, int32_t h, int32_t w, const float* eps, float* sample,
                           float* mu, float* logvar, void* workspace, size_t workspace_bytes, int32_t batch, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Output stage: decoder frames -> interleaved uint8 on the device (csrc/i2v_frames.hip).  Replaces the host-side tail of every
+ * caller: denorm (utils/auxiliaries.py:53-55), the GIF tiling permute + divide-by-own-maximum (utils/auxiliaries.py:15-22) and the
+ * uint8 cast that follows them, which the reference and the host path of this package run in numpy on a full fp32 copy.
+ * No handle: both calls are stateless, only enqueue on `stream`, never synchronise and can be captured into a graph.
+ * ---------------------------------------------------------------------------------------- */
+#define I2V_FRAMES_PEAK 0   /* GIF semantics: d = min(max(x*0.5f + 0.5f, 0), 1) (multiply and add rounded separately),
+                             * s = (float)(255.0 / (double)d(peak)), u8 = trunc(d * s) */
+#define I2V_FRAMES_UNIT 1   /* u8 = trunc(min(max(d * 255.0f + 0.5f, 0), 255)): the rounding of torchvision's save_image */
+#define I2V_FRAMES_STRIP 0  /* dst [T, rows, cols, 3]: sample s at pixel row row0 + (s % k) * h, pixel column col0 + (s / k) * w */
+#define I2V_FRAMES_CLIPS 1  /* dst [N, T, H, W, 3], dense */
+
+typedef struct {
+    int32_t n, t, h, w;        /* x: N samples of [T, 3, H, W] fp32 planes (what i2v_dec_forward* writes) */
+    int64_t n_stride;          /* floats between two samples of x; 0 = dense (T*3*H*W).  [F, K, ...] blocks are N = F*K samples */
+    int32_t k;                 /* STRIP: grid rows (realizations per start frame); must divide n.  1 = one strip */
+    int32_t layout;            /* I2V_FRAMES_STRIP / I2V_FRAMES_CLIPS */
+    int64_t dst_row_bytes;     /* STRIP: bytes between two pixel rows of dst (>= 3 * (col0 + n/k * w)) */
+    int64_t dst_frame_bytes;   /* STRIP: bytes between two frames of dst (>= (row0 + k*h) * dst_row_bytes) */
+    int64_t dst_bytes;         /* size of the dst allocation, checked against the geometry before the launch */
+    int32_t row0, col0;        /* STRIP: placement of this block inside dst, in pixels (several batches fill ONE job-wide strip) */
+} i2v_frames_cfg;
+
+/* Maximum of all raw values of x into *peak (ONE device float): the maximum that utils/auxiliaries.py:20-21 takes over the
+ * de-normalised strip is clamp(*peak * 0.5 + 0.5) because the de-normalisation is monotone.  accumulate = 0 starts from -inf,
+ * accumulate != 0 keeps max(*peak, max x): a job converted batch by batch is normalised by one peak.  Uses cfg->n, t, h, w, n_stride. */
+int i2v_frames_peak(const float* x, const i2v_frames_cfg* cfg, float* peak, int32_t accumulate, void* stream);
+/* x -> interleaved bytes (utils/auxiliaries.py:15-22 + 53-55 and the cast of their callers).  mode I2V_FRAMES_PEAK reads the scale
+ * from the device float `peak` that i2v_frames_peak wrote (no host round trip between the two launches); I2V_FRAMES_UNIT takes
+ * peak = NULL.  Null pointers, non-positive sizes, k not dividing n, a block that does not fit dst: I2V_E_INVALID before any launch. */
+int i2v_frames_to_u8(const float* x, const i2v_frames_cfg* cfg, const float* peak, uint8_t* dst, int32_t mode, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
