@@ -36,6 +36,11 @@ class FlowCfg(ctypes.Structure):
                                       "control", "activation", "skip_actnorm", "skip_shuffle", "use_graph", "linear_f16")]
 
 
+class AdamTensor(ctypes.Structure):
+    _fields_ = [("param", c_void_p), ("grad", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p), ("max_exp_avg_sq", c_void_p),
+                ("numel", c_int64)]
+
+
 class DecCfg(ctypes.Structure):
     _fields_ = [("channel_factor", c_int32), ("z_dim", c_int32), ("upsample_s", c_int32 * 2),
                 ("upsample_t", c_int32 * 2), ("spectral_norm", c_int32), ("mma", c_int32)]
@@ -65,6 +70,15 @@ SYMBOLS = {
     "i2v_flow_param_bytes": (c_size_t, [c_void_p]),
     "i2v_flow_forward": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int32, c_void_p]),
     "i2v_flow_inverse": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int32, c_void_p]),
+    "i2v_flow_train_create": (c_int32, [POINTER(FlowCfg), POINTER(c_void_p)]),
+    "i2v_flow_train_destroy": (None, [c_void_p]),
+    "i2v_flow_train_bind": (c_int32, [c_void_p, POINTER(_Tensor), POINTER(_Tensor), c_int32]),
+    "i2v_flow_train_saved_bytes": (c_size_t, [c_void_p, c_int32]),
+    "i2v_flow_train_forward": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int32, c_void_p]),
+    "i2v_flow_train_backward": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
+                                          c_void_p]),
+    "i2v_adam_chunk": (c_int32, []),
+    "i2v_adam_step": (c_int32, [c_void_p, c_void_p, c_int32, c_float, c_float, c_float, c_float, c_float, c_int32, c_int64, c_void_p]),
     "i2v_mlp_create": (c_int32, [c_int32, c_int32, c_int32, c_int32, POINTER(c_void_p)]),
     "i2v_mlp_destroy": (None, [c_void_p]),
     "i2v_mlp_load": (c_int32, [c_void_p, POINTER(_Tensor), c_int32]),
@@ -310,6 +324,103 @@ class NativeFlow(_Handle):
 
     def inverse(self, x, embed):
         return self._run(x, embed, True)
+
+
+class NativeFlowTrain(_Handle):
+    """Handle for ``i2v_flow_train_*``: the training path of ConditionalFlow (forward with saved activations, backward).  It packs
+    nothing: ``bind`` hands over the DEVICE pointers of the module's own parameters, which the kernels read in place, so an
+    optimiser step on them needs no re-load.  Gradients go either into bound tensors (``bind(..., grads=...)``) or into one flat
+    buffer per backward call whose layout ``bind`` fixes (``flat_numel`` floats, ``flat_slices[name] = (offset, numel)``)."""
+
+    def __init__(self, in_channels, embedding_dim, hidden_dim, hidden_depth, n_flows, control=0, activation="lrelu",
+                 skip_actnorm=False, skip_shuffle=False, device=None, linear_f16=0):
+        cfg = FlowCfg(in_channels, embedding_dim, hidden_dim, hidden_depth, n_flows, int(control),
+                      1 if activation == "lrelu" else 0, int(skip_actnorm), int(skip_shuffle), 0, int(bool(linear_f16)))
+        h = c_void_p()
+        with self._bind(device):
+            _check(lib().i2v_flow_train_create(ctypes.byref(cfg), ctypes.byref(h)), "i2v_flow_train_create")
+        self._h = h
+        self.embedding_dim = embedding_dim
+        self.flat_numel, self.flat_slices, self.bound_ptrs, self._keep = 0, {}, None, None
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.i2v_flow_train_destroy(self._h)
+            self._h = None
+
+    @staticmethod
+    def pointers(tensors):
+        return tuple(t.data_ptr() for t in tensors.values())
+
+    def bind(self, tensors, grads=None):
+        """tensors: {state_dict key: device tensor} (float32 parameters, int64 Shuffle indices).  grads: {key: gradient tensor} of
+        the float32 entries, or None for the flat layout (every gradient at a 16-byte aligned offset of one buffer)."""
+        with self._on(*tensors.values()):
+            items, gitems, keep, off = [], [], [], 0
+            slices = {}
+            for k, t in tensors.items():
+                if not t.is_cuda or not t.is_contiguous():
+                    raise I2VError(f"flow training: '{k}' must be a contiguous tensor on a HIP device (this package has no CPU fallback)")
+                kb = k.encode()
+                keep.append(kb)
+                if t.dtype == torch.int64:
+                    items.append(_Tensor(kb, t.data_ptr(), t.numel(), I2V_I64))
+                    continue
+                if t.dtype != torch.float32:
+                    continue
+                items.append(_Tensor(kb, t.data_ptr(), t.numel(), I2V_F32))
+                if grads is None:
+                    slices[k] = (off, t.numel())
+                    gitems.append(_Tensor(kb, 4 * off, t.numel(), I2V_F32))
+                    off += (t.numel() + 3) // 4 * 4
+                else:
+                    g = grads[k]
+                    _require_gpu(g)
+                    keep.append(g)
+                    gitems.append(_Tensor(kb, g.data_ptr(), g.numel(), I2V_F32))
+            n = len(items)
+            gitems += [_Tensor(b"", None, 0, I2V_U8)] * (n - len(gitems))
+            _check(lib().i2v_flow_train_bind(self._h, (_Tensor * n)(*items), (_Tensor * n)(*gitems), n), "i2v_flow_train_bind")
+        self.flat_numel, self.flat_slices = (off, slices) if grads is None else (0, {})
+        self.bound_ptrs = self.pointers(tensors)
+        self._keep = (tensors, grads)
+
+    def forward(self, x, embed):
+        """-> (zt [B,64], logdet [B], saved): ``saved`` belongs to this pass and goes to ``backward``."""
+        _require_gpu(x, embed)
+        B = x.shape[0]
+        if x.shape != (B, 64) or embed.shape != (B, self.embedding_dim):
+            raise I2VError(f"flow: expected x [B,64] and embed [B,{self.embedding_dim}], got {tuple(x.shape)}, {tuple(embed.shape)}")
+        with self._on(x, embed):
+            saved = torch.empty(int(lib().i2v_flow_train_saved_bytes(self._h, B)), dtype=torch.uint8, device=x.device)
+            zt = torch.empty_like(x)
+            logdet = torch.empty(B, dtype=torch.float32, device=x.device)
+            _check(lib().i2v_flow_train_forward(self._h, x.data_ptr(), embed.data_ptr(), zt.data_ptr(), logdet.data_ptr(), saved.data_ptr(),
+                                                saved.numel(), B, _stream()), "i2v_flow_train_forward")
+        return zt, logdet, saved
+
+    def backward(self, d_zt, d_logdet, saved, flat_grads=None, accumulate=False, need_dx=False, need_dembed=False):
+        """Writes (accumulate: adds to) the parameter gradients -- into ``flat_grads`` (flat layout) or the bound gradient tensors --
+        and returns (d_x or None, d_embed or None)."""
+        _require_gpu(d_zt, d_logdet, flat_grads)
+        B = d_zt.shape[0]
+        if (flat_grads is None) != (self.flat_numel == 0) or (flat_grads is not None and flat_grads.numel() < self.flat_numel):
+            raise I2VError("flow training: backward needs the flat gradient buffer exactly when bind() was given no gradient tensors")
+        with self._on(d_zt, d_logdet, saved, flat_grads):
+            dx = torch.empty(B, 64, dtype=torch.float32, device=d_zt.device) if need_dx else None
+            de = torch.empty(B, self.embedding_dim, dtype=torch.float32, device=d_zt.device) if need_dembed else None
+            _check(lib().i2v_flow_train_backward(self._h, d_zt.data_ptr(), d_logdet.data_ptr(), saved.data_ptr(), saved.numel(),
+                                                 None if dx is None else dx.data_ptr(), None if de is None else de.data_ptr(),
+                                                 None if flat_grads is None else flat_grads.data_ptr(), int(bool(accumulate)), B, _stream()),
+                   "i2v_flow_train_backward")
+        return dx, de
+
+
+def adam_step(table, chunks, lr, beta1, beta2, eps, weight_decay, amsgrad, step):
+    """One fused Adam launch over a device table of ``AdamTensor`` rows (uint8 tensor) and its chunk list (int32 [n, 2])."""
+    with torch.cuda.device(table.device):
+        _check(lib().i2v_adam_step(table.data_ptr(), chunks.data_ptr(), chunks.shape[0], lr, beta1, beta2, eps, weight_decay,
+                                   int(bool(amsgrad)), int(step), _stream()), "i2v_adam_step")
 
 
 def check_realizations(img, motion, z_dim, realizations):

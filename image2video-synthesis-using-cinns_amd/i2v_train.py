@@ -1,0 +1,151 @@
+"""Training the cINN natively: ``FusedAdam`` (``torch.optim.Adam`` semantics in one multi-tensor HIP launch, ``i2v_adam_step``)
+and ``FlowTrainer`` (forward, loss gradient, backward and optimiser step of the stage-2 trainer, reference
+stage2_cINN/main.py:22-46, without autograd in between).  No CPU fallback: parameters and gradients live on a HIP device."""
+import ctypes
+
+import numpy as np
+import torch
+
+import i2v_native as native
+
+
+def _adam_plan(rows, device):
+    """rows: [(param, grad, exp_avg, exp_avg_sq, max_exp_avg_sq or None)] -> (device table of AdamTensor rows, chunk list)."""
+    chunk = int(native.lib().i2v_adam_chunk())
+    tab = np.zeros((len(rows), 6), dtype=np.int64)
+    chunks = []
+    for i, r in enumerate(rows):
+        tab[i, :5] = [0 if t is None else t.data_ptr() for t in r]
+        tab[i, 5] = r[0].numel()
+        starts = np.arange(0, r[0].numel(), chunk, dtype=np.int32)
+        chunks.append(np.stack([np.full_like(starts, i), starts], axis=1))
+    assert ctypes.sizeof(native.AdamTensor) == 48
+    table = torch.from_numpy(tab.view(np.uint8).reshape(-1)).to(device)
+    return table, torch.from_numpy(np.concatenate(chunks, axis=0)).to(device)
+
+
+class FusedAdam(torch.optim.Optimizer):
+    """``torch.optim.Adam`` with the update of every tensor in ONE launch.  Same constructor arguments, same ``state_dict()``
+    layout (``step``, ``exp_avg``, ``exp_avg_sq``, ``max_exp_avg_sq``), so a checkpoint of one loads into the other and the
+    ``torch.optim.lr_scheduler`` classes work on it.  Parameters without ``.grad`` are skipped like torch skips them."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False):
+        if not 0.0 <= lr or not 0.0 <= eps or not 0.0 <= weight_decay or not all(0.0 <= b < 1.0 for b in betas):
+            raise ValueError(f"FusedAdam: invalid hyper-parameters lr={lr} betas={betas} eps={eps} weight_decay={weight_decay}")
+        # the key set of torch's own Adam (whatever this torch version keeps in a param_group), so state dicts interchange
+        defaults = dict(torch.optim.Adam([torch.zeros(1)], lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad).defaults)
+        super().__init__(params, defaults)
+        self._plans = {}
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        self._plans = {}
+
+    def _rows(self, group):
+        rows, steps = [], []
+        for p in group["params"]:
+            if p.grad is None:
+                continue
+            if p.grad.is_sparse or not p.is_cuda or p.dtype != torch.float32:
+                raise native.I2VError("FusedAdam: dense float32 parameters on a HIP device only (this package has no CPU fallback)")
+            st = self.state[p]
+            if len(st) == 0:
+                st["step"] = torch.tensor(0.0, dtype=torch.float32)
+                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            if group["amsgrad"] and "max_exp_avg_sq" not in st:
+                st["max_exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            g = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
+            rows.append((p.data if p.is_contiguous() else None, g, st["exp_avg"], st["exp_avg_sq"], st.get("max_exp_avg_sq")))
+            if rows[-1][0] is None:
+                raise native.I2VError("FusedAdam: parameters must be contiguous")
+            steps.append(st["step"])
+        return rows, steps
+
+    def _launch(self, gi, group, rows, steps, check=True):
+        """One launch per distinct step count of the group (normally one)."""
+        torch._foreach_add_(steps, 1)
+        counts = [int(s) for s in steps] if check else [int(steps[0])] * len(steps)
+        for count in sorted(set(counts)):
+            sel = [r for r, c in zip(rows, counts) if c == count]
+            key = (gi, count if len(set(counts)) > 1 else 0)
+            ptrs = tuple(t.data_ptr() for r in sel for t in r[:2]) if check else None
+            plan = self._plans.get(key)
+            if plan is None or (check and plan[0] != ptrs):
+                plan = (ptrs,) + _adam_plan(sel, sel[0][0].device) + (sel,)
+                self._plans[key] = plan
+            b1, b2 = group["betas"]
+            native.adam_step(plan[1], plan[2], float(group["lr"]), b1, b2, group["eps"], group["weight_decay"], group["amsgrad"], count)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        for gi, group in enumerate(self.param_groups):
+            if group.get("maximize") or group.get("decoupled_weight_decay"):
+                raise native.I2VError("FusedAdam: maximize / decoupled_weight_decay are not implemented")
+            rows, steps = self._rows(group)
+            if rows:
+                self._launch(gi, group, rows, steps)
+        return loss
+
+
+class FlowTrainer:
+    """The stage-2 training step without autograd: ``step(z, cond_or_embed)`` runs forward (training handle), the FlowLoss
+    gradient ``d_zt = zt / B``, ``d_logdet = -1 / B``, backward into one flat gradient buffer this object owns, and the fused
+    Adam step -- all enqueued on the current stream, no host synchronisation.  ``network``: a ``SupervisedTransformer`` or a
+    ``ConditionalFlow``.  ``.grad`` of every flow parameter is a view of the flat buffer; ``optimizer`` is a ``FusedAdam`` over
+    them (``torch.optim.lr_scheduler`` works on it)."""
+
+    def __init__(self, network, lr=1e-5, betas=(0.9, 0.99), weight_decay=0, amsgrad=True, eps=1e-8):
+        self.network = network
+        self.flow = getattr(network, "flow", network)
+        self.optimizer = FusedAdam(self.flow.parameters(), lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad)
+        self._handle, self._bound, self._flat, self._rows, self._const = None, None, None, None, {}
+
+    def _prepare(self):
+        h = self.flow._train_native()
+        if h is not self._handle or self._bound != h.bound_ptrs:
+            self._handle, self._bound = h, h.bound_ptrs
+            dev = self.flow.module_device()
+            self._flat = torch.zeros(h.flat_numel, dtype=torch.float32, device=dev)
+            for (name, shape), p in zip(self.flow._train_names, self.flow._train_params):
+                off, n = h.flat_slices[name]
+                p.grad = self._flat[off:off + n].view(shape)
+            self._rows = self.optimizer._rows(self.optimizer.param_groups[0])
+            self.optimizer._plans = {}
+        return h
+
+    def step(self, z, cond_or_embed):
+        """One optimisation step on the batch; returns the four FlowLoss numbers as 0-d device tensors."""
+        flow = self.flow
+        with torch.no_grad():
+            z2 = z.reshape(z.shape[0], -1).contiguous()
+            if self.network is not flow:
+                if isinstance(cond_or_embed, (list, tuple)):
+                    e2 = self.network._embed(z2, cond_or_embed, None)
+                elif self.network.control and cond_or_embed.shape[1] != flow.cond_channels:
+                    raise native.I2VError("FlowTrainer.step: with control, pass cond = [x0, pos] or the full-width embedding")
+                else:
+                    e2 = cond_or_embed
+            else:
+                e2 = cond_or_embed
+            e2 = e2.reshape(e2.shape[0], -1).contiguous()
+            flow._check_init(z2, e2)
+            h = self._prepare()
+            flow._invalidate_inference()
+            B = z2.shape[0]
+            zt, logdet, saved = h.forward(z2, e2)
+            d_ld = self._const.get(B)
+            if d_ld is None:
+                d_ld = self._const[B] = torch.full((B,), -1.0 / B, dtype=torch.float32, device=z2.device)
+            h.backward(zt / B, d_ld, saved, self._flat, accumulate=False)
+            rows, steps = self._rows
+            self.optimizer._launch(0, self.optimizer.param_groups[0], rows, steps, check=False)
+            nll_loss = 0.5 * zt.pow(2).sum(1).mean()
+            nlogdet_loss = -logdet.mean()
+            reference_nll_loss = 0.5 * torch.randn_like(zt).pow(2).sum(1).mean()
+        return {"Loss": nll_loss + nlogdet_loss, "reference_nll_loss": reference_nll_loss, "nlogdet_loss": nlogdet_loss,
+                "nll_loss": nll_loss}

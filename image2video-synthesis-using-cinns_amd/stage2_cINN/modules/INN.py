@@ -42,6 +42,15 @@ class SupervisedTransformer(nn.Module):
                 self.embedder.load_state_dict(torch.load(ckpt, map_location="cpu")["state_dict"])  # INN.py:40
                 _ = self.embedder.eval()
 
+    @property
+    def differentiable(self):
+        """Forwarded to ``self.flow`` (the only trained part, stage2_cINN/main.py): True makes ``forward`` differentiable."""
+        return self.flow.differentiable
+
+    @differentiable.setter
+    def differentiable(self, value):
+        self.flow.differentiable = bool(value)
+
     def embed_pos(self, pos):
         """Three one-hots of 10 bins at index floor(pos*10 - 1e-4) (reference INN.py:49-57)."""
         pos = pos.detach().float().cpu() * self.cond_size - 1e-4

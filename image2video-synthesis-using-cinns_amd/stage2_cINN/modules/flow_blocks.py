@@ -16,7 +16,100 @@ def _prefixed(module, prefix):
     return {prefix + k: v for k, v in module.state_dict().items()}
 
 
-class ConditionalFlow(NativeBacked):
+class _FlowTrainFunction(torch.autograd.Function):
+    """forward / backward of a flow module on its training handle (csrc/i2v_flow_train.hip).  The trained parameters are inputs
+    of the Function, so autograd itself accumulates what backward returns into ``.grad`` (``zero_grad``, accumulation and
+    ``set_to_none`` behave as with stock modules); the kernels write every gradient into ONE fresh flat buffer per backward and the
+    returned tensors are views of it."""
+
+    @staticmethod
+    def forward(ctx, module, x, embed, *params):
+        h = module._train_native()
+        zt, logdet, saved = h.forward(x, embed)
+        ctx.handle, ctx.saved, ctx.names = h, saved, module._train_names
+        return zt, logdet
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_zt, d_logdet):
+        h, saved = ctx.handle, ctx.saved
+        dev = saved.device
+        if d_zt is None or d_logdet is None:
+            nb = (d_zt if d_zt is not None else d_logdet).shape[0]
+            d_zt = torch.zeros(nb, 64, device=dev) if d_zt is None else d_zt
+            d_logdet = torch.zeros(nb, device=dev) if d_logdet is None else d_logdet
+        flat = torch.empty(h.flat_numel, dtype=torch.float32, device=dev)
+        dx, de = h.backward(d_zt.contiguous(), d_logdet.contiguous(), saved, flat, accumulate=False,
+                            need_dx=ctx.needs_input_grad[1], need_dembed=ctx.needs_input_grad[2])
+        grads = []
+        for i, (name, shape) in enumerate(ctx.names):
+            if ctx.needs_input_grad[3 + i]:
+                off, n = h.flat_slices[name]
+                grads.append(flat[off:off + n].view(shape))
+            else:
+                grads.append(None)
+        return (None, dx, de, *grads)
+
+
+class _Differentiable:
+    """Training side of a flow module.  ``differentiable`` (plain attribute, default False, not a constructor argument and not
+    in the state_dict): with it set and grad mode on, ``forward`` runs through the training handle and returns tensors with a
+    ``grad_fn``; ``reverse`` never does."""
+
+    _train_prefix = ""
+
+    def _train_cfg(self):  # pragma: no cover - abstract
+        raise NotImplementedError
+
+    def _train_tensors(self):
+        """{key as i2v_flow_load knows it: the module's own float32 parameter / int64 Shuffle index tensor}."""
+        out = {}
+        for k, p in self.named_parameters():
+            out[self._train_prefix + k] = p
+        for k, b in self.named_buffers():
+            if b.dtype == torch.int64:
+                out[self._train_prefix + k] = b
+        return out
+
+    def _train_native(self):
+        """The training handle, bound to the parameter storage as it is now (re-bound when a parameter has moved)."""
+        h = self.__dict__.get("_train")
+        tensors = self._train_tensors()
+        if h is None:
+            h = native.NativeFlowTrain(device=self.module_device(), **self._train_cfg())
+        if h.bound_ptrs != native.NativeFlowTrain.pointers(tensors):
+            h.bind({k: t.detach() for k, t in tensors.items()})
+            object.__setattr__(self, "_train", h)
+            object.__setattr__(self, "_train_params", [p for p in tensors.values() if p.dtype == torch.float32])
+            object.__setattr__(self, "_train_names", [(k, p.shape) for k, p in tensors.items() if p.dtype == torch.float32])
+        return h
+
+    def _invalidate_inference(self):
+        """The packed inference handles (this module's, its sub-modules' and its owners') hold copies of parameters that a training
+        step is about to change: the next reverse / sampling call packs the current ones."""
+        for m in self.modules():
+            if isinstance(m, NativeBacked):
+                object.__setattr__(m, "_native", None)
+        m = self.__dict__.get("_native_parent")
+        while m is not None:
+            object.__setattr__(m, "_native", None)
+            m = m.__dict__.get("_native_parent")
+
+    def _wants_grad(self):
+        return bool(self.__dict__.get("differentiable", False)) and torch.is_grad_enabled()
+
+    def _forward_differentiable(self, x2, e2):
+        if self.__dict__.get("record_intermediates", False):
+            raise native.I2VError("differentiable = True cannot be combined with record_intermediates = True")
+        f16 = self.__dict__.get("linear_f16", 0)
+        if (native.default_flow_f16() if f16 is None else int(bool(f16))):
+            raise native.I2VError("differentiable = True needs the exact-fp32 path: linear_f16 is an inference mode")
+        self._train_native()
+        self._invalidate_inference()
+        return _FlowTrainFunction.apply(self, x2, e2, *self._train_params)
+
+
+class ConditionalFlow(_Differentiable, NativeBacked):
     """Flat conditional flow: n_flows x [ActNorm -> InvLeakyRelu -> double affine coupling -> Shuffle]
     (reference flow_blocks.py:8-60).  forward returns (z~ [B,C,1,1], logdet [B]); reverse returns z [B,C,1,1]."""
 
@@ -50,6 +143,13 @@ class ConditionalFlow(NativeBacked):
         # fp32 matrix cores); 1 = fp16 operands, fp32 accumulation (BASELINE configs[4]'s "fp16 MFMA conditioning GEMM"; outside
         # the 1e-4 fp32 gate).  Set it before the first call (or call refresh_native()).
         self.linear_f16 = None
+        # Not a reference argument: True (and grad mode on) = forward runs on the training handle and is differentiable
+        # (csrc/i2v_flow_train.hip); False = the inference path, unchanged
+        self.differentiable = False
+
+    def _train_cfg(self):
+        return dict(in_channels=self.in_channels, embedding_dim=self.cond_channels, hidden_dim=self.mid_channels,
+                    hidden_depth=self.num_blocks, n_flows=self.n_flows, control=1 if self.control else 0, activation=self.activation)
 
     def _build_native(self):
         h = native.NativeFlow(self.in_channels, self.cond_channels, self.mid_channels, self.num_blocks, self.n_flows,
@@ -68,7 +168,14 @@ class ConditionalFlow(NativeBacked):
 
     def _drop_native(self):
         super()._drop_native()
+        object.__setattr__(self, "_train", None)
         object.__setattr__(self, "_init_checked", False)  # parameters may have changed: look at `initialized` again
+
+    def _check_init(self, x2, e2):
+        if not self._init_checked:
+            if any(int(b.norm_layer.initialized.item()) == 0 for b in self.sub_layers):
+                self._data_dependent_init(x2, e2)
+            object.__setattr__(self, "_init_checked", True)
 
     def _forward_recorded(self, x2, e2):
         """Block-by-block forward that fills last_outs / last_logdets like flow_blocks.py:42-51."""
@@ -88,10 +195,10 @@ class ConditionalFlow(NativeBacked):
         if not reverse:
             # Q1: the `initialized` buffers are looked at on the first FORWARD after every (re)load / move, whether or not a
             # reverse pass has already built the native handle (no per-call device sync afterwards)
-            if not self._init_checked:
-                if any(int(b.norm_layer.initialized.item()) == 0 for b in self.sub_layers):
-                    self._data_dependent_init(x2, e2)
-                object.__setattr__(self, "_init_checked", True)
+            self._check_init(x2, e2)
+            if self._wants_grad():
+                out, logdet = self._forward_differentiable(x2, e2)
+                return out[:, :, None, None], logdet
             if self.record_intermediates:
                 return self._forward_recorded(x2, e2)
             out, logdet = self.native().forward(x2, e2)
@@ -102,7 +209,7 @@ class ConditionalFlow(NativeBacked):
         return self(out, xcond, reverse=True)
 
 
-class ConditionalDoubleVectorCouplingBlock(NativeBacked):
+class ConditionalDoubleVectorCouplingBlock(_Differentiable, NativeBacked):
     """Two affine couplings with half swap (reference flow_blocks.py:63-105)."""
 
     def __init__(self, in_channels, cond_channels, hidden_dim, depth=2, mode="normal"):
@@ -114,6 +221,18 @@ class ConditionalDoubleVectorCouplingBlock(NativeBacked):
                                                        out_dim=in_channels // 2) for _ in range(2)])
         self.mode = mode
         self._geom = (in_channels, cond_channels, hidden_dim, depth)
+        self.differentiable = False
+
+    _train_prefix = "sub_layers.0.coupling."
+
+    def _train_cfg(self):
+        c, e, hdim, depth = self._geom
+        return dict(in_channels=c, embedding_dim=e, hidden_dim=hdim, hidden_depth=depth, n_flows=1,
+                    control=2 if self.mode != "normal" else 0, activation="none", skip_actnorm=True, skip_shuffle=True)
+
+    def _drop_native(self):
+        super()._drop_native()
+        object.__setattr__(self, "_train", None)
 
     def _build_native(self):
         c, e, hdim, depth = self._geom
@@ -128,11 +247,13 @@ class ConditionalDoubleVectorCouplingBlock(NativeBacked):
         x = x.squeeze(-1).squeeze(-1).contiguous()
         xc = xc.squeeze(-1).squeeze(-1).contiguous()
         if not reverse:
+            if self._wants_grad():
+                return self._forward_differentiable(x, xc)
             return self.native().forward(x, xc)
         return self.native().inverse(x, xc)[:, :, None, None]
 
 
-class ConditionalFlatDoubleCouplingFlowBlock(NativeBacked):
+class ConditionalFlatDoubleCouplingFlowBlock(_Differentiable, NativeBacked):
     """ActNorm -> activation -> coupling -> Shuffle, log-dets summed (reference flow_blocks.py:108-139)."""
 
     def __init__(self, in_channels, cond_channels, hidden_dim, hidden_depth, activation="lrelu", mode="normal"):
@@ -143,6 +264,18 @@ class ConditionalFlatDoubleCouplingFlowBlock(NativeBacked):
         self.activation = possible[activation]()
         self.shuffle = Shuffle(in_channels)
         self._geom = (in_channels, cond_channels, hidden_dim, hidden_depth, activation, mode)
+        self.differentiable = False
+
+    _train_prefix = "sub_layers.0."
+
+    def _train_cfg(self):
+        c, e, hdim, depth, act, mode = self._geom
+        return dict(in_channels=c, embedding_dim=e, hidden_dim=hdim, hidden_depth=depth, n_flows=1,
+                    control=2 if mode != "normal" else 0, activation=act)
+
+    def _drop_native(self):
+        super()._drop_native()
+        object.__setattr__(self, "_train", None)
 
     def _build_native(self):
         c, e, hdim, depth, act, mode = self._geom
@@ -158,6 +291,8 @@ class ConditionalFlatDoubleCouplingFlowBlock(NativeBacked):
             if int(self.norm_layer.initialized.item()) == 0:
                 self.norm_layer(x2)  # Q1: initialises loc/scale from this batch
                 self.refresh_native()
+            if self._wants_grad():
+                return self._forward_differentiable(x2, e2)
             return self.native().forward(x2, e2)
         return self.native().inverse(x2, e2)[:, :, None, None]
 

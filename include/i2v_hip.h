@@ -93,6 +93,61 @@ int i2v_flow_inverse(i2v_flow* f, const float* residual, const float* embed, flo
                      void* workspace, size_t workspace_bytes, int32_t batch, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * cINN flow, training path (stage2_cINN/main.py:22-46: forward, FlowLoss, loss.backward(), optimizer.step())
+ *
+ * A second handle next to i2v_flow: it packs nothing.  The parameters are read in place, in their state_dict layout,
+ * through DEVICE pointers bound once, so an optimiser step on them is seen by the next forward without a re-load.
+ * Exact fp32 matrix cores only; every gradient element has one owner and a fixed summation order (no atomics):
+ * the same inputs give the same bits.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct i2v_flow_train i2v_flow_train;
+/* Same cfg as the inference handle (control 0 / 1 / 2, activation, skip_actnorm, skip_shuffle; use_graph is ignored).
+ * Refused with I2V_E_INVALID: linear_f16 = 1, and any geometry outside 64 channels, hidden 128..512 in steps of 128,
+ * depth >= 1, embedding <= 128. */
+int i2v_flow_train_create(const i2v_flow_cfg* cfg, i2v_flow_train** out);
+void i2v_flow_train_destroy(i2v_flow_train* f);
+/* params[i].data: DEVICE pointer of the tensor with state_dict key params[i].name (the keys of i2v_flow_load; the
+ * Shuffle indices as I2V_I64, bound once and not trained).  grads: one entry per trained tensor under the same key; its
+ * `data` is either the device pointer of the gradient tensor, or a BYTE OFFSET into one flat gradient buffer whose base
+ * is passed to each backward call (a caller that allocates a fresh flat buffer per backward never re-binds).  Nothing is
+ * copied; all pointers / offsets must be 16-byte aligned. */
+int i2v_flow_train_bind(i2v_flow_train* f, const i2v_tensor* params, const i2v_tensor* grads, int32_t n);
+/* Size of the `saved` buffer of one forward / backward pair: MLP inputs, hidden activations, s / t of every half-step
+ * and the backward's pre-activation gradients (about 1 MB per sample at 20 flows, hidden 512, depth 2). */
+size_t i2v_flow_train_saved_bytes(const i2v_flow_train* f, int32_t batch);
+/* ConditionalFlow.forward(x, embedding), flow_blocks.py:42-51, keeping in `saved` what the backward needs:
+ * x [B,64], embed [B,E] -> zt [B,64], logdet [B]. */
+int i2v_flow_train_forward(i2v_flow_train* f, const float* x, const float* embed, float* zt, float* logdet, void* saved,
+                           size_t saved_bytes, int32_t batch, void* stream);
+/* Backward of that forward from the same `saved`: given d_zt [B,64] and d_logdet [B], writes (accumulate = 1: adds to)
+ * the gradient of every trained parameter at (char*)grad_base + grads[i].data (grad_base NULL: plain pointers were
+ * bound), and d_x [B,64], d_embed [B,E] when non-null.  Linear layers: dX = dY W on the chain, dW = dY^T X and
+ * db = sum_b dY behind it; affine coupling flow_blocks.py:88-93 (ds = dy x exp(s) + d_logdet, dt = dy, dx = dy exp(s),
+ * conditioner gradient into the kept half and the embedding); ActNorm modules.py:80-89 (d_scale includes
+ * sum_b d_logdet[b] / scale); InvLeakyRelu with its reported log-det of 0 (flow_blocks.py:176-182); Shuffle as the
+ * inverse gather. */
+int i2v_flow_train_backward(i2v_flow_train* f, const float* d_zt, const float* d_logdet, void* saved, size_t saved_bytes,
+                            float* d_x, float* d_embed, void* grad_base, int32_t accumulate, int32_t batch, void* stream);
+
+/* One tensor of a fused optimiser step: device pointers, max_exp_avg_sq may be null without amsgrad. */
+typedef struct {
+    float* param;
+    const float* grad;
+    float* exp_avg;
+    float* exp_avg_sq;
+    float* max_exp_avg_sq;
+    int64_t numel;
+} i2v_adam_tensor;
+/* Elements of one workgroup's chunk in the chunk list below. */
+int32_t i2v_adam_chunk(void);
+/* torch.optim.Adam.step over a DEVICE table of tensors in one launch (the reference trains with lr 1e-5,
+ * betas (0.9, 0.99), weight_decay 0, amsgrad, stage2_cINN/configs): L2 weight_decay added to the gradient, bias
+ * corrections from `step` (the count after this step, >= 1), eps outside the square root.  chunks: device array of
+ * n_chunks pairs (table index, first element); every tensor is covered by ceil(numel / chunk) pairs. */
+int i2v_adam_step(const i2v_adam_tensor* table, const int32_t* chunks, int32_t n_chunks, float lr, float beta1, float beta2,
+                  float eps, float weight_decay, int32_t amsgrad, int64_t step, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Leaf modules of the flow, individually callable (sub-module classes stay usable)
  * ---------------------------------------------------------------------------------------- */
 /* BasicFullyConnectedNet (stage2_cINN/modules/modules.py:9-30): Linear(dim,hidden) -> LeakyReLU(0.01) ->
