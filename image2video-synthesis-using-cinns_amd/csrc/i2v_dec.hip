@@ -640,22 +640,37 @@ using namespace i2v;
 
 namespace {
 
+// The kernel a 3x3x3 block conv runs.  The values are the codes i2v_dec_get_layer_profile reports.
+enum Conv3Kernel : int { K_F32 = 0, K_F16 = 1, K_F23 = 2, K_F43 = 3, K_F43_GEN = 4, K_F32_WINO = 5, K_F43_ONE = 6 };
+constexpr unsigned bit(Conv3Kernel k) { return 1u << k; }
+constexpr bool is_split(Conv3Kernel k) { return k != K_F32 && k != K_F32_WINO; }   // reads a split-fp16 (or one-term fp16) operand
+
+// One 3x3x3 block conv (conv_0 or conv_1) and the weights of every kernel variant packed for it
+struct Conv3 {
+    int cin = 0, cout = 0;
+    // conv_0 behind a x2 temporal up-sampling.  SPADE's output is identical for frames 2i and 2i+1 (gamma/beta do not depend on t):
+    // the split-fp16 variants run on the half-rate tensor with two pre-summed 2-tap temporal kernels (-1/3 of the MACs)
+    bool tdup = false;
+    ConvWeights f32;          // exact fp32, direct 27-tap kernel
+    Wino4F32Weights wf;       // exact fp32, Winograd F(4,3) on the fp32 matrix cores (i2v_wino32.hip), next to f32
+    Conv16Weights d16;        // split-fp16, direct kernel
+    Wino16Weights w23;        // split-fp16, Winograd F(2,3) (packed where the shape allows)
+    Wino4Weights w43;         // split-fp16, Winograd F(4,3) (i2v_conv16w4.hip); packed INSTEAD of the F(2,3) one
+    Wino4hWeights w43h;       // one-term fp16 mode (mma = 3): F(4,3) on fp16 operands (i2v_conv16w4h.hip), packed INSTEAD of w43
+};
+
 struct Block {
     std::string name;
     int n_in = 0, n_out = 0, n_mid = 0;
     bool learned = false;
     int groups_spade = 16;
-    ConvWeights conv0, conv1, convs, sp_conv, sp_gb;
+    Conv3 conv[2];              // conv_0: n_in -> n_mid, conv_1: n_mid -> n_out
+    ConvWeights convs, sp_conv, sp_gb;
     Conv16Weights sp_conv16;  // SPADE's Conv2d(3, 128, 3) with the 3 input channels zero-padded to 8 (split-fp16 mode)
-    Conv16Weights conv0_16, conv1_16, sp_gb16;  // split-fp16 variants (cfg.mma == 1)
+    Conv16Weights sp_gb16;      // split-fp16 variant (cfg.mma == 1)
     Conv16Weights convs16;      // the learned shortcut's 1x1x1 conv on split-fp16 operands (pointwise16_forward)
     Wino16Weights sp_gb_w;      // SPADE's fused gamma|beta Conv2d(128, 2C, 3) on the Winograd kernel (1x3x3 variant)
     Wino4Weights sp_gb_w4;      // ... on the F(4,3) kernel (packed INSTEAD where the shape allows: W % 16 == 0, H % 32 == 0)
-    Wino16Weights conv0_w, conv1_w;             // Winograd F(2,3) variants of conv_0 / conv_1 (packed where the shape allows)
-    Wino4Weights conv0_w4, conv1_w4;            // Winograd F(4,3) variants (i2v_conv16w4.hip); packed INSTEAD of the F(2,3) ones
-    Wino4hWeights conv0_w4h, conv1_w4h;         // one-term fp16 mode (mma = 3): the F(4,3) convs on fp16 operands (i2v_conv16w4h.hip), packed INSTEAD of conv0_w4 / conv1_w4
-    Wino4F32Weights conv0_wf, conv1_wf;         // exact-fp32 mode: Winograd F(4,3) on the fp32 matrix cores (i2v_wino32.hip), next to conv0 / conv1
-    bool tdup0 = false;                          // conv_0 runs on the half-rate tensor (x2 temporal up-sampling in front)
     DevBuf gn_w, gn_b;
     int zoff = 0;  // offset of this block's ADAIN (gamma|beta) in the z-GEMM output
 };
@@ -784,12 +799,30 @@ struct DecWs {
     bool has_y1v = false;
 };
 
-bool want_wino0(const i2v_dec* d, const Block& b, const Level& l);
-bool want_wino1(const i2v_dec* d, const Block& b, const Level& l);
-bool want_w4_0(const i2v_dec* d, const Block& b, const Level& l);
-bool want_w4_1(const i2v_dec* d, const Block& b, const Level& l);
-bool want_wf_0(const i2v_dec* d, const Block& b, const Level& l);
-bool want_wf_1(const i2v_dec* d, const Block& b, const Level& l);
+// F(4,3): its bricks hold 512 output positions x 64 or 32 channels (the launcher picks 32-channel workgroups when 64-channel ones
+// would not fill the chip; both give the same bits) -- wherever one SAMPLE gives >= 16 workgroups of 32 channels, i.e. from the
+// 16x16 level on (round 3 stopped at 32x32: g_1 ran F(2,3); measured at B = 64: g_1.conv_0 1.94 -> 1.49 ms, conv_1 1.47 -> 1.13,
+// at B = 8 equal).  WHETHER a layer runs F(4,3) depends on the layer only; the workgroup width (64 or 32 channels) is chosen by the
+// launcher from batch x bricks against the CU count -- it changes the schedule, not the accumulation order of any output, so
+// shards reproduce the full batch bit for bit (test_f43_tile_width_switch_across_batches crosses the threshold).
+bool w4_fills(const Level& l, int cout) { return (long)l.T * l.H * l.W / 512 * std::max(cout / 32, 1) >= 16; }
+
+// Wanted by shape: would a conv of (cin, cout, tdup) at this level run kernel `kn` (K_F43, K_F23 or K_F32_WINO) under the handle's
+// switches?  (A tdup conv reads the half-rate tensor through pair kernels: T / 2 frames, 2 temporal taps.)
+bool conv3_wants(const i2v_dec* d, const Conv3& c, const Level& l, Conv3Kernel kn) {
+    const int T = c.tdup ? l.T / 2 : l.T, KT = c.tdup ? 2 : 3;
+    switch (kn) {
+    case K_F43: return d->has16() && d->wino && d->wino4 && (d->wino4 == 2 || w4_fills(l, c.cout)) && wino4_supported(c.cout, c.cin, T, l.H, l.W, KT);
+    case K_F23: return d->has16() && d->wino && wino16_supported(c.cout, c.cin, T, l.H, l.W, KT);
+    case K_F32_WINO: return d->has32() && d->wino32 && wino4f32_supported(c.cout, c.cin, l.T, l.H, l.W);
+    default: return false;
+    }
+}
+// ... and the split-fp16 kernel it would run: layers whose shape allows it run on a Winograd kernel (F(4,3) before F(2,3): 1.5x / 2x
+// fewer MFMAs), the rest on the direct one
+Conv3Kernel conv3_split_kernel(const i2v_dec* d, const Conv3& c, const Level& l) {
+    return conv3_wants(d, c, l, K_F43) ? K_F43 : conv3_wants(d, c, l, K_F23) ? K_F23 : K_F16;
+}
 
 // SPADE's gamma|beta Conv2d(128, 2C, 3) on a Winograd kernel (F(4,3) 1x3x3 variant, else F(2,3)): the predicate of
 // i2v_dec_load's packing and of the y1v workspace
@@ -810,12 +843,12 @@ DecWs dec_ws(const i2v_dec* d, int B, int Fg = 0) {
         const Level& l = d->lvl[k];
         const size_t P = (size_t)l.T * l.H * l.W, Pl = P / ((size_t)l.ut * l.us * l.us);
         mx_x = std::max(mx_x, P * b.n_out);
-        // conv operands: hl16 (4 B per element), or the Winograd operand V (4 values per output pair: 8 B per element)
-        mx_a = std::max(mx_a, P * b.n_in * (want_wino0(d, b, l) || want_w4_0(d, b, l) ? 2 : 1));
-        mx_a = std::max(mx_a, P * b.n_mid * (want_wino1(d, b, l) || want_w4_1(d, b, l) ? 2 : 1));
-        // exact-fp32 Winograd: V = 6 planes per 4 positions (1.5 x the activation), M = 6 planes per 4 outputs
-        if (want_wf_0(d, b, l)) { mx_a = std::max(mx_a, P * b.n_in * 3 / 2); mx_m6 = std::max(mx_m6, P * b.n_mid * 3 / 2); }
-        if (want_wf_1(d, b, l)) { mx_a = std::max(mx_a, P * b.n_mid * 3 / 2); mx_m6 = std::max(mx_m6, P * b.n_out * 3 / 2); }
+        for (const Conv3& c : b.conv) {
+            // conv operands: hl16 (4 B per element), or the Winograd operand V (4 values per output pair: 8 B per element)
+            mx_a = std::max(mx_a, P * c.cin * (conv3_split_kernel(d, c, l) != K_F16 ? 2 : 1));
+            // exact-fp32 Winograd: V = 6 planes per 4 positions (1.5 x the activation), M = 6 planes per 4 outputs
+            if (conv3_wants(d, c, l, K_F32_WINO)) { mx_a = std::max(mx_a, P * c.cin * 3 / 2); mx_m6 = std::max(mx_m6, P * c.cout * 3 / 2); }
+        }
         mx_dx = std::max(mx_dx, P * b.n_mid);
         if (b.learned) { mx_xsin = std::max(mx_xsin, Pl * b.n_in); mx_xslow = std::max(mx_xslow, Pl * b.n_out); }
         mx_y = std::max(mx_y, (size_t)l.H * l.W);
@@ -899,44 +932,29 @@ int run_modulate(const float* x, const float* coef, const float* gb, float* out,
     return I2V_OK;
 }
 
+// the F(4,3) operand.  one: the one-term operand (mma = 3) -- C channels of x, written as CinPad = C rounded up to 64 (the kernel's
+// chunks come in pairs)
 int run_modulate_wino4(const float* x, const float* coef, const float* gb, float* out, int B, int T, int H, int W, int C, int ut,
-                       int us, int lrelu, hipStream_t st, int* range_flag, int* umax = nullptr, GbRows rows = {}) {
-    I2V_REQUIRE(C % 32 == 0 && W % 4 == 0, I2V_E_INVALID, "modulate (F(4,3) operand): channels %d / width %d", C, W);
-    const long per = (long)H * (W / 4) * (C / 4);   // one thread per (h, tile, 4 channels)
-    I2V_REQUIRE(per % 64 == 0, I2V_E_INVALID, "modulate (F(4,3) operand): %ld threads per sample (need whole wavefronts)", per);
+                       int us, int lrelu, hipStream_t st, bool one, int* range_flag, int* umax = nullptr, GbRows rows = {}) {
+    const char* what = one ? "one-term F(4,3)" : "F(4,3)";
+    I2V_REQUIRE(C % 32 == 0 && W % 4 == 0, I2V_E_INVALID, "modulate (%s operand): channels %d / width %d", what, C, W);
+    const int Cp = one ? (C + 63) / 64 * 64 : C;
+    const long per = (long)H * (W / 4) * (Cp / 4);   // one thread per (h, tile, 4 channels)
+    I2V_REQUIRE(per % 64 == 0, I2V_E_INVALID, "modulate (%s operand): %ld threads per sample (need whole wavefronts)", what, per);
     I2V_REQUIRE(per * T * 6 < (1L << 31), I2V_E_INVALID, "modulate: tensor too large");
     const unsigned gx = (unsigned)std::min<long>((per + 255) / 256, 8192);
-    if (gb && rows.shared())
-        hipLaunchKernelGGL((modulate_wino4_kernel<true, false, true>), dim3(gx, B), dim3(256), 0, st, x, reinterpret_cast<const float2*>(coef), gb,
-                           reinterpret_cast<char*>(out), T, H, W, C, ut, us, lrelu, range_flag, umax, C, rows.k, rows.r0);
-    else if (gb)
-        hipLaunchKernelGGL(modulate_wino4_kernel<true>, dim3(gx, B), dim3(256), 0, st, x, reinterpret_cast<const float2*>(coef), gb,
-                           reinterpret_cast<char*>(out), T, H, W, C, ut, us, lrelu, range_flag, umax);
-    else
-        hipLaunchKernelGGL(modulate_wino4_kernel<false>, dim3(gx, B), dim3(256), 0, st, x, reinterpret_cast<const float2*>(coef), gb,
-                           reinterpret_cast<char*>(out), T, H, W, C, ut, us, lrelu, range_flag, umax);
-    I2V_HIP_CHECK(hipGetLastError());
-    return I2V_OK;
-}
-
-// the one-term operand (mma = 3): C channels of x, written as CinPad = C rounded up to 64 (the kernel's chunks come in pairs)
-int run_modulate_wino4h(const float* x, const float* coef, const float* gb, float* out, int B, int T, int H, int W, int C, int ut,
-                        int us, int lrelu, hipStream_t st, int* range_flag, int* umax, GbRows rows = {}) {
-    I2V_REQUIRE(C % 32 == 0 && W % 4 == 0, I2V_E_INVALID, "modulate (one-term F(4,3) operand): channels %d / width %d", C, W);
-    const int Cp = (C + 63) / 64 * 64;
-    const long per = (long)H * (W / 4) * (Cp / 4);
-    I2V_REQUIRE(per % 64 == 0, I2V_E_INVALID, "modulate (one-term F(4,3) operand): %ld threads per sample (need whole wavefronts)", per);
-    I2V_REQUIRE(per * T * 6 < (1L << 31), I2V_E_INVALID, "modulate: tensor too large");
-    const unsigned gx = (unsigned)std::min<long>((per + 255) / 256, 8192);
-    if (gb && rows.shared())
-        hipLaunchKernelGGL((modulate_wino4_kernel<true, true, true>), dim3(gx, B), dim3(256), 0, st, x, reinterpret_cast<const float2*>(coef), gb,
-                           reinterpret_cast<char*>(out), T, H, W, Cp, ut, us, lrelu, range_flag, umax, C, rows.k, rows.r0);
-    else if (gb)
-        hipLaunchKernelGGL((modulate_wino4_kernel<true, true>), dim3(gx, B), dim3(256), 0, st, x, reinterpret_cast<const float2*>(coef), gb,
-                           reinterpret_cast<char*>(out), T, H, W, Cp, ut, us, lrelu, range_flag, umax, C);
-    else
-        hipLaunchKernelGGL((modulate_wino4_kernel<false, true>), dim3(gx, B), dim3(256), 0, st, x, reinterpret_cast<const float2*>(coef), gb,
-                           reinterpret_cast<char*>(out), T, H, W, Cp, ut, us, lrelu, range_flag, umax, C);
+    const bool sh = gb && rows.shared();
+    // (the trailing C is the tensor's own channel count Cx of the one-term form; the split form sets Cx = C itself)
+    auto launch = [&](auto* kernel) {
+        hipLaunchKernelGGL(kernel, dim3(gx, B), dim3(256), 0, st, x, reinterpret_cast<const float2*>(coef), gb, reinterpret_cast<char*>(out),
+                           T, H, W, Cp, ut, us, lrelu, range_flag, umax, C, rows.k, rows.r0);
+    };
+    if (!one && sh) launch(modulate_wino4_kernel<true, false, true>);
+    else if (!one && gb) launch(modulate_wino4_kernel<true>);
+    else if (!one) launch(modulate_wino4_kernel<false>);
+    else if (sh) launch(modulate_wino4_kernel<true, true, true>);
+    else if (gb) launch(modulate_wino4_kernel<true, true>);
+    else launch(modulate_wino4_kernel<false, true>);
     I2V_HIP_CHECK(hipGetLastError());
     return I2V_OK;
 }
@@ -979,102 +997,14 @@ struct ProfScope {
     }
 };
 
-int conv3(i2v_dec* d, const ConvWeights& w, const float* in, float* out, const float* res, int rt, int rs, int B,
-          const Level& l, int epi, hipStream_t st) {
-    const double fl = 2.0 * B * l.T * l.H * l.W * (double)w.Cin * w.Cout * 27.0;
-    ProfScope ps(d, st, fl, fl);
-    return conv_forward(w, in, w.Cin, out, res, rt, rs, B, l.T, l.H, l.W, epi, st);
+// resize_kernel's launch: hl16 / flag as the kernel takes them, ibs = floats between the samples of `img`
+int run_resize(const float* img, float* out, int B, int Hi, int Wi, int Ho, int Wo, int hl16, int* flag, long ibs, hipStream_t st) {
+    const long tot = (long)B * Ho * Wo;
+    hipLaunchKernelGGL(resize_kernel, dim3((unsigned)std::min<long>((tot + 255) / 256, 65536)), dim3(256), 0, st, img, out, B, Hi, Wi,
+                       Ho, Wo, hl16, flag, ibs);
+    I2V_HIP_CHECK(hipGetLastError());
+    return I2V_OK;
 }
-
-// exact-fp32 mode, Winograd F(4,3): six 9-tap plane convs + the output transform; matrix-core FLOPs issued = 1/2 of the algorithmic
-int conv3_wf(i2v_dec* d, const Wino4F32Weights& w, const float* V, float* M, float* out, const float* res, int rt, int rs, int B,
-             const Level& l, int epi, hipStream_t st) {
-    const double fl = 2.0 * B * l.T * l.H * l.W * (double)w.Cin * w.Cout * 27.0;
-    ProfScope ps(d, st, fl, 0.5 * fl);
-    return wino4f32_forward(w, V, M, out, res, rt, rs, B, l.T, l.H, l.W, epi, st);
-}
-
-int conv3_16(i2v_dec* d, const Conv16Weights& w, const float* in_hl16, float* out, const float* res, int rt, int rs, int B,
-             const Level& l, int epi, hipStream_t st, double* stats = nullptr, float* splitk = nullptr, size_t splitk_floats = 0) {
-    if (stats) I2V_HIP_CHECK(hipMemsetAsync(stats, 0, (size_t)B * w.Cout * 16, st));
-    // algorithmic FLOPs of the reference's 3x3x3 conv; matrix-core FLOPs actually issued = 3 fp16 MFMAs per product, on
-    // 18 instead of 27 taps in temporal-duplication mode
-    const double fl = 2.0 * B * l.T * l.H * l.W * (double)w.Cin * w.Cout * 27.0;
-    ProfScope ps(d, st, fl, 3.0 * fl * (w.tdup ? 18.0 / 27.0 : 1.0));
-    return conv16_forward(w, in_hl16, out, res, rt, rs, B, l.T, l.H, l.W, epi, st, stats, nullptr, splitk, splitk_floats);
-}
-
-int conv3_w(i2v_dec* d, const Wino16Weights& w, const float* v_hl16, float* out, const float* res, int rt, int rs, int B,
-            const Level& l, int epi, hipStream_t st, double* stats = nullptr) {
-    if (stats) I2V_HIP_CHECK(hipMemsetAsync(stats, 0, (size_t)B * w.Cout * 16, st));
-    // matrix-core FLOPs issued: 4 Winograd products per 2 outputs x 3 kw taps (x 2/3), 3 fp16 MFMAs each, 18 of 27 taps in
-    // temporal-duplication mode
-    const double fl = 2.0 * B * l.T * l.H * l.W * (double)w.Cin * w.Cout * 27.0;
-    ProfScope ps(d, st, fl, 3.0 * fl * (2.0 / 3.0) * (w.tdup ? 18.0 / 27.0 : 1.0));
-    return wino16_forward(w, v_hl16, out, res, rt, rs, B, l.T, l.H, l.W, epi, st, stats);
-}
-
-int conv3_w4(i2v_dec* d, const Wino4Weights& w, const float* v_hl16, float* out, const float* res, int rt, int rs, int B,
-             const Level& l, int epi, hipStream_t st, double* stats = nullptr) {
-    if (stats) I2V_HIP_CHECK(hipMemsetAsync(stats, 0, (size_t)B * w.Cout * 16, st));
-    // matrix-core FLOPs issued: 6 Winograd products per 4 outputs x 3 kw taps (x 1/2), 3 fp16 MFMAs each
-    const double fl = 2.0 * B * l.T * l.H * l.W * (double)w.Cin * w.Cout * 27.0;
-    ProfScope ps(d, st, fl, 3.0 * fl * 0.5 * (w.tdup ? 18.0 / 27.0 : 1.0));
-    return wino4_forward(w, v_hl16, out, res, rt, rs, B, l.T, l.H, l.W, epi, st, stats);
-}
-
-// one-term fp16 mode (mma = 3): the same F(4,3) products, one fp16 MFMA each
-int conv3_w4h(i2v_dec* d, const Wino4hWeights& w, const float* v16, float* out, const float* res, int rt, int rs, int B,
-              const Level& l, int epi, hipStream_t st, double* stats = nullptr) {
-    if (stats) I2V_HIP_CHECK(hipMemsetAsync(stats, 0, (size_t)B * w.Cout * 16, st));
-    const double fl = 2.0 * B * l.T * l.H * l.W * (double)w.Cin * w.Cout * 27.0;
-    ProfScope ps(d, st, fl, fl * 0.5 * (w.tdup ? 18.0 / 27.0 : 1.0));
-    return wino4h_forward(w, v16, out, res, rt, rs, B, l.T, l.H, l.W, epi, st, stats);
-}
-
-// the same conv with the operand generated in the kernel (no operand-writer launch in front): x = the conv's fp32 input before the
-// modulation, coef / gb as the writer takes them
-int conv3_w4g(i2v_dec* d, const Wino4Weights& w, const float* x, const float* coef, const float* gb, int us, float* out, const float* res, int rt,
-              int rs, int B, const Level& l, int epi, hipStream_t st, double* stats, int* flag, int* umax, GbRows rows = {}) {
-    if (stats) I2V_HIP_CHECK(hipMemsetAsync(stats, 0, (size_t)B * w.Cout * 16, st));
-    const double fl = 2.0 * B * l.T * l.H * l.W * (double)w.Cin * w.Cout * 27.0;
-    ProfScope ps(d, st, fl, 3.0 * fl * 0.5);
-    return wino4g_forward(w, x, coef, gb, us, out, res, rt, rs, B, l.T, l.H, l.W, epi, st, stats, flag, umax, rows);
-}
-
-// which kernel conv_0 / conv_1 of a block use at this geometry (want_*: by shape; use_*: and the weights are packed for it)
-bool want_wino0(const i2v_dec* d, const Block& b, const Level& l) {
-    const bool tdup = l.ut == 2;   // conv_0 behind a x2 temporal up-sampling: pair kernels on the half-rate tensor (Block::tdup0)
-    return d->has16() && d->wino && wino16_supported(b.n_mid, b.n_in, tdup ? l.T / 2 : l.T, l.H, l.W, tdup ? 2 : 3);
-}
-bool want_wino1(const i2v_dec* d, const Block& b, const Level& l) {
-    return d->has16() && d->wino && wino16_supported(b.n_out, b.n_mid, l.T, l.H, l.W, 3);
-}
-// F(4,3): its bricks hold 512 output positions x 64 or 32 channels (the launcher picks 32-channel workgroups when 64-channel ones
-// would not fill the chip; both give the same bits) -- wherever one SAMPLE gives >= 16 workgroups of 32 channels, i.e. from the
-// 16x16 level on (round 3 stopped at 32x32: g_1 ran F(2,3); measured at B = 64: g_1.conv_0 1.94 -> 1.49 ms, conv_1 1.47 -> 1.13,
-// at B = 8 equal).  WHETHER a layer runs F(4,3) depends on the layer only; the workgroup width (64 or 32 channels) is chosen by the
-// launcher from batch x bricks against the CU count -- it changes the schedule, not the accumulation order of any output, so
-// shards reproduce the full batch bit for bit (test_f43_tile_width_switch_across_batches crosses the threshold).
-bool w4_fills(const Level& l, int cout) { return (long)l.T * l.H * l.W / 512 * std::max(cout / 32, 1) >= 16; }
-bool want_w4_0(const i2v_dec* d, const Block& b, const Level& l) {
-    const bool tdup = l.ut == 2;
-    return d->has16() && d->wino && d->wino4 && (d->wino4 == 2 || w4_fills(l, b.n_mid)) &&
-           wino4_supported(b.n_mid, b.n_in, tdup ? l.T / 2 : l.T, l.H, l.W, tdup ? 2 : 3);
-}
-bool want_w4_1(const i2v_dec* d, const Block& b, const Level& l) {
-    return d->has16() && d->wino && d->wino4 && (d->wino4 == 2 || w4_fills(l, b.n_out)) && wino4_supported(b.n_out, b.n_mid, l.T, l.H, l.W, 3);
-}
-bool want_wf_0(const i2v_dec* d, const Block& b, const Level& l) { return d->has32() && d->wino32 && wino4f32_supported(b.n_mid, b.n_in, l.T, l.H, l.W); }
-bool want_wf_1(const i2v_dec* d, const Block& b, const Level& l) { return d->has32() && d->wino32 && wino4f32_supported(b.n_out, b.n_mid, l.T, l.H, l.W); }
-bool use_wf_0(const i2v_dec* d, const Block& b, const Level& l) { return b.conv0_wf.u[0].w.p && want_wf_0(d, b, l); }
-bool use_wf_1(const i2v_dec* d, const Block& b, const Level& l) { return b.conv1_wf.u[0].w.p && want_wf_1(d, b, l); }
-bool use_w4_0(const i2v_dec* d, const Block& b, const Level& l) { return b.conv0_w4.w.p && want_w4_0(d, b, l); }
-bool use_w4_1(const i2v_dec* d, const Block& b, const Level& l) { return b.conv1_w4.w.p && want_w4_1(d, b, l); }
-bool use_w4h_0(const i2v_dec* d, const Block& b, const Level& l) { return b.conv0_w4h.w.p && want_w4_0(d, b, l); }
-bool use_w4h_1(const i2v_dec* d, const Block& b, const Level& l) { return b.conv1_w4h.w.p && want_w4_1(d, b, l); }
-bool use_wino0(const i2v_dec* d, const Block& b, const Level& l) { return b.conv0_w.w.p && want_wino0(d, b, l); }
-bool use_wino1(const i2v_dec* d, const Block& b, const Level& l) { return b.conv1_w.w.p && want_wino1(d, b, l); }
 
 }  // namespace
 
@@ -1086,11 +1016,7 @@ int coef_forward(const double* sums, float* coef, int B, int C, int groups, doub
     return run_coef(sums, coef, B, C, groups, count, nullptr, 0, 0, gw, gb, st);
 }
 int resize_forward(const float* img, float* out, int B, int Hi, int Wi, int Ho, int Wo, hipStream_t st) {
-    const long tot = (long)B * Ho * Wo;
-    hipLaunchKernelGGL(resize_kernel, dim3((unsigned)std::min<long>((tot + 255) / 256, 65536)), dim3(256), 0, st, img, out, B, Hi, Wi,
-                       Ho, Wo, 0, static_cast<int*>(nullptr), (long)3 * Hi * Wi);
-    I2V_HIP_CHECK(hipGetLastError());
-    return I2V_OK;
+    return run_resize(img, out, B, Hi, Wi, Ho, Wo, 0, nullptr, (long)3 * Hi * Wi, st);
 }
 }  // namespace i2v
 
@@ -1112,26 +1038,21 @@ struct BlockBufs {
 
 // SPADE's conditioning branch of one block (normalization_layer.py:20-23): resize(start frame) -> Conv2d(3, 128) + lrelu ->
 // fused gamma | beta Conv2d(128, 2C) ("+1" folded into the gamma bias) -> gb [B][H][W][2C].  Depends on the start frame only.
-int spade_branch(i2v_dec* d, Block& b, const Level& l, const float* img, int img_h, int img_w, int B, float* y0, float* y1, float* y1v_,
+int spade_branch(i2v_dec* d, Block& b, const Level& l, const float* img, int img_h, int img_w, int B, float* y0, float* y1, float* y1v,
                  float* gb, hipStream_t st) {
     int rc;
-    struct { float* y1v; } w{y1v_};
-    {
-        const long tot = (long)B * l.H * l.W;
-        hipLaunchKernelGGL(resize_kernel, dim3((unsigned)std::min<long>((tot + 255) / 256, 65536)), dim3(256), 0, st, img, y0,
-                           B, img_h, img_w, l.H, l.W, d->aux16() ? 1 : 0, d->status_dev, d->img_bstride ? d->img_bstride : (long)3 * img_h * img_w);
-        I2V_HIP_CHECK(hipGetLastError());
-    }
-    if (d->aux16() && b.sp_gb_w4.w.p && w.y1v) {
+    if ((rc = run_resize(img, y0, B, img_h, img_w, l.H, l.W, d->aux16() ? 1 : 0, d->status_dev,
+                         d->img_bstride ? d->img_bstride : (long)3 * img_h * img_w, st))) return rc;
+    if (d->aux16() && b.sp_gb_w4.w.p && y1v) {
         if ((rc = conv16_forward(b.sp_conv16, y0, y1, nullptr, 1, 1, B, 1, l.H, l.W, EPI_LRELU, st))) return rc;
-        if ((rc = run_modulate_wino4(y1, nullptr, nullptr, w.y1v, B, 1, l.H, l.W, 128, 1, 1, 0, st, d->status_dev))) return rc;
-        if ((rc = wino4_forward(b.sp_gb_w4, w.y1v, gb, nullptr, 1, 1, B, 1, l.H, l.W, EPI_NONE, st, nullptr))) return rc;
-    } else if (d->aux16() && b.sp_gb_w.w.p && w.y1v) {
+        if ((rc = run_modulate_wino4(y1, nullptr, nullptr, y1v, B, 1, l.H, l.W, 128, 1, 1, 0, st, false, d->status_dev))) return rc;
+        if ((rc = wino4_forward(b.sp_gb_w4, y1v, gb, nullptr, 1, 1, B, 1, l.H, l.W, EPI_NONE, st, nullptr))) return rc;
+    } else if (d->aux16() && b.sp_gb_w.w.p && y1v) {
         // gamma | beta conv on the Winograd kernel: the 128-channel activation goes through fp32 once more (the operand
         // writer needs the w-neighbours of every position, which the producing conv's epilogue does not hold)
         if ((rc = conv16_forward(b.sp_conv16, y0, y1, nullptr, 1, 1, B, 1, l.H, l.W, EPI_LRELU, st))) return rc;
-        if ((rc = run_modulate_wino(y1, nullptr, nullptr, w.y1v, B, 1, l.H, l.W, 128, 1, 1, 0, st, d->status_dev))) return rc;
-        if ((rc = wino16_forward(b.sp_gb_w, w.y1v, gb, nullptr, 1, 1, B, 1, l.H, l.W, EPI_NONE, st, nullptr))) return rc;
+        if ((rc = run_modulate_wino(y1, nullptr, nullptr, y1v, B, 1, l.H, l.W, 128, 1, 1, 0, st, d->status_dev))) return rc;
+        if ((rc = wino16_forward(b.sp_gb_w, y1v, gb, nullptr, 1, 1, B, 1, l.H, l.W, EPI_NONE, st, nullptr))) return rc;
     } else if (d->aux16()) {
         if ((rc = conv16_forward(b.sp_conv16, y0, y1, nullptr, 1, 1, B, 1, l.H, l.W, EPI_LRELU | EPI_HL16, st, nullptr, d->status_dev)))
             return rc;
@@ -1141,6 +1062,80 @@ int spade_branch(i2v_dec* d, Block& b, const Level& l, const float* img, int img
         if ((rc = conv_forward(b.sp_gb, y1, 128, gb, nullptr, 1, 1, B, 1, l.H, l.W, EPI_NONE, st))) return rc;
     }
     return I2V_OK;
+}
+
+// What a block conv is applied to: lrelu((x A + B) gamma' + beta) read through the nearest up-sampling map (ut, us).  x = the fp32 tensor
+// before the modulation, coef = the per-(b, c) (A, B) pairs, gb = SPADE's maps (conv_0) or null (conv_1, behind ADAIN).
+struct Conv3In { const float* x; const float* coef; const float* gb; int ut, us; GbRows rows; };
+
+// The kernel conv `layer` (= 2 * block + (0: conv_0, 1: conv_1)) runs in THIS call: wanted by shape, packed, and the layer on the
+// split-fp16 path (mma = 0: none is; mma = auto: not the layers the range guard switched, i2v_dec::fp32_layer).  m6: the exact-fp32
+// Winograd scratch (null: the direct fp32 kernel is used).
+Conv3Kernel conv3_choose(const i2v_dec* d, const Conv3& c, const Level& l, int layer, const Conv3In& in, const float* m6) {
+    if (!d->layer16(layer)) return m6 && c.wf.u[0].w.p && conv3_wants(d, c, l, K_F32_WINO) ? K_F32_WINO : K_F32;
+    if ((c.w43h.w.p || c.w43.w.p) && conv3_wants(d, c, l, K_F43)) {
+        if (c.w43h.w.p) return K_F43_ONE;
+        // thin F(4,3) layers: the operand is generated by the conv kernel's producer waves (no writer launch, no V tensor).
+        // I2V_DEC_GEN = 1: conv_0 and conv_1 of the thin level, 2: conv_1 only.  conv_0 reads SPADE's maps through a x2 spatial
+        // up-sampling, conv_1 (ADAIN) through none; neither through a temporal one, and the debug tap wants the V tensor.
+        const bool first = !(layer & 1);
+        const bool gen = (first ? d->gen == 1 : d->gen != 0) && !c.tdup && in.ut == 1 && in.us == (first ? 2 : 1) && !d->tap_dst &&
+                         wino4g_supported(c.cout, c.cin, l.T, l.H, l.W, in.us);
+        return gen ? K_F43_GEN : K_F43;
+    }
+    if (c.w23.w.p && conv3_wants(d, c, l, K_F23)) return K_F23;
+    return K_F16;
+}
+
+// Launches the operand writer kernel `kn` reads (K_F43_GEN: none) into `a`; *tap_floats = what it wrote, for the debug tap (0: nothing to
+// tap).  A tdup conv's operand is kept at the half temporal rate (its frames 2i and 2i+1 coincide) -- while the layer is on the
+// split-fp16 path: a layer that `auto` switched to fp32 reads through the real ut.
+// Range guard: the operand tensor of layer i publishes its maximum in slot 1 + i.
+int conv3_write_operand(i2v_dec* d, const Conv3& c, Conv3Kernel kn, const Level& l, int layer, const Conv3In& in, float* a, int B,
+                        hipStream_t st, size_t* tap_floats) {
+    const bool tdup = c.tdup && is_split(kn);
+    const int T = tdup ? l.T / 2 : l.T, ut = tdup ? 1 : in.ut;
+    int* flag = d->status_dev;
+    int* umax = is_split(kn) && flag ? flag + 1 + layer : nullptr;
+    const size_t pos = (size_t)B * T * l.H * l.W;
+    // (the one-term operand is tapped whole: 3 bytes per activation of CinPad channels)
+    *tap_floats = kn == K_F43_GEN || kn == K_F32_WINO ? 0 : kn == K_F43_ONE ? pos * c.w43h.CinPad * 3 / 4 : pos * c.cin;
+    switch (kn) {
+    case K_F43_GEN: return I2V_OK;
+    case K_F32_WINO: return modulate_wino4_f32(in.x, in.coef, in.gb, a, B, T, l.H, l.W, c.cin, ut, in.us, 1, st, in.rows);
+    case K_F43_ONE:
+    case K_F43: return run_modulate_wino4(in.x, in.coef, in.gb, a, B, T, l.H, l.W, c.cin, ut, in.us, 1, st, kn == K_F43_ONE, flag, umax, in.rows);
+    case K_F23: return run_modulate_wino(in.x, in.coef, in.gb, a, B, T, l.H, l.W, c.cin, ut, in.us, 1, st, flag, umax, in.rows);
+    default: return run_modulate(in.x, in.coef, in.gb, a, B, T, l.H, l.W, c.cin, ut, in.us, 1, st, kn == K_F16, flag, umax, in.rows);
+    }
+}
+
+// Runs the conv on kernel `kn`: a = the operand conv3_write_operand wrote (K_F43_GEN: generated in the kernel from `in`, with the
+// writer's range guard); stats = where the epilogue accumulates the output's statistics (null: not fused; never on the fp32 kernels).
+int conv3_run(i2v_dec* d, const Conv3& c, Conv3Kernel kn, const Level& l, int layer, const Conv3In& in, const float* a, float* out,
+              const float* res, int rt, int rs, int B, int epi, double* stats, const BlockBufs& w, hipStream_t st) {
+    if (stats) I2V_HIP_CHECK(hipMemsetAsync(stats, 0, (size_t)B * c.cout * 16, st));
+    // algorithmic FLOPs of the reference's 3x3x3 conv, and the matrix-core FLOPs actually issued: 3 fp16 MFMAs per product on the
+    // split-fp16 kernels, one on the one-term kernel; F(2,3): 4 Winograd products per 2 outputs x 3 kw taps (x 2/3), F(4,3): 6 per
+    // 4 outputs (x 1/2); 18 instead of 27 taps in temporal-duplication mode (the generating kernel never is)
+    const double fl = 2.0 * B * l.T * l.H * l.W * (double)c.cin * c.cout * 27.0, td = c.tdup ? 18.0 / 27.0 : 1.0;
+    const double exec = kn == K_F32 ? fl : kn == K_F32_WINO ? 0.5 * fl : kn == K_F16 ? 3.0 * fl * td : kn == K_F23 ? 3.0 * fl * (2.0 / 3.0) * td :
+                        kn == K_F43 ? 3.0 * fl * 0.5 * td : kn == K_F43_ONE ? fl * 0.5 * td : 3.0 * fl * 0.5;
+    d->prof_cur_layer = layer;
+    d->prof_cur_kernel = kn;
+    ProfScope ps(d, st, fl, exec);
+    int* flag = d->status_dev;
+    switch (kn) {
+    case K_F32: return conv_forward(c.f32, a, c.cin, out, res, rt, rs, B, l.T, l.H, l.W, epi, st);
+    case K_F32_WINO: return wino4f32_forward(c.wf, a, w.m6, out, res, rt, rs, B, l.T, l.H, l.W, epi, st);
+    case K_F16: return conv16_forward(c.d16, a, out, res, rt, rs, B, l.T, l.H, l.W, epi, st, stats, nullptr, w.splitk, w.splitk_floats);
+    case K_F23: return wino16_forward(c.w23, a, out, res, rt, rs, B, l.T, l.H, l.W, epi, st, stats);
+    case K_F43: return wino4_forward(c.w43, a, out, res, rt, rs, B, l.T, l.H, l.W, epi, st, stats);
+    case K_F43_ONE: return wino4h_forward(c.w43h, a, out, res, rt, rs, B, l.T, l.H, l.W, epi, st, stats);
+    case K_F43_GEN: return wino4g_forward(c.w43, in.x, in.coef, in.gb, in.us, out, res, rt, rs, B, l.T, l.H, l.W, epi, st, stats, flag,
+                                          flag ? flag + 1 + layer : nullptr, in.rows);
+    }
+    return I2V_E_INVALID;
 }
 
 // One GeneratorBlock (decoder.py:33-52) on channels-last tensors: x [B][T/ut][H/us][W/us][n_in] -> xn [B][T][H][W][n_out].
@@ -1184,53 +1179,22 @@ int block_forward(i2v_dec* d, int k, Block& b, const Level& l, const float* x, f
     if (w.gb_ready) gb = const_cast<float*>(w.gb_ready);
     else if ((rc = spade_branch(d, b, l, img, img_h, img_w, Bg, y0, y1, w.y1v, gb, st))) return rc;
     if ((rc = tap(k, 0, gb, (size_t)Bg * l.H * l.W * 2 * b.n_in))) return rc;
-    // per conv: split-fp16 or exact fp32 (mma = 0: all fp32; mma = auto: the layers the range guard switched, i2v_dec::fp32_layer)
-    const bool f16_0 = d->layer16((2 * k) % 12), f16_1 = d->layer16((2 * k + 1) % 12);
-    const bool tdup = f16_0 && b.tdup0;  // a0 is kept at the half temporal rate (its frames 2i and 2i+1 coincide)
-    const bool h0 = f16_0 && use_w4h_0(d, b, l), h1 = f16_1 && use_w4h_1(d, b, l);        // F(4,3), one-term fp16 (mma = 3)
-    const bool q0 = f16_0 && (h0 || use_w4_0(d, b, l)), q1 = f16_1 && (h1 || use_w4_1(d, b, l));          // F(4,3)
-    const bool w0 = f16_0 && !q0 && use_wino0(d, b, l), w1 = f16_1 && !q1 && use_wino1(d, b, l);   // F(2,3)
-    int* flag = d->status_dev;
-    // range guard: the two operand tensors of this block publish their maxima in slots 1 + 2k / 2 + 2k
-    int* um0 = f16_0 && flag ? flag + 1 + 2 * (k % 12) : nullptr;
-    int* um1 = f16_1 && flag ? flag + 2 + 2 * (k % 12) : nullptr;
-    const bool f0 = !f16_0 && w.m6 && use_wf_0(d, b, l), f1 = !f16_1 && w.m6 && use_wf_1(d, b, l);   // exact fp32: Winograd F(4,3) on the fp32 matrix cores
-    // thin F(4,3) layers: the operand is generated by the conv kernel's producer waves (no writer launch, no V tensor)
-    const bool g0 = d->gen == 1 && q0 && !h0 && !tdup && l.ut == 1 && l.us == 2 && !d->tap_dst && wino4g_supported(b.n_mid, b.n_in, l.T, l.H, l.W, 2);
-    const bool g1 = d->gen && q1 && !h1 && !d->tap_dst && wino4g_supported(b.n_out, b.n_mid, l.T, l.H, l.W, 1);
-    if (g0) rc = I2V_OK;
-    else if (f0) rc = modulate_wino4_f32(x, coef, gb, a, B, l.T, l.H, l.W, b.n_in, l.ut, l.us, 1, st, rows);
-    else if (h0) rc = run_modulate_wino4h(x, coef, gb, a, B, tdup ? l.T / 2 : l.T, l.H, l.W, b.n_in, tdup ? 1 : l.ut, l.us, 1, st, flag, um0, rows);
-    else if (q0) rc = run_modulate_wino4(x, coef, gb, a, B, tdup ? l.T / 2 : l.T, l.H, l.W, b.n_in, tdup ? 1 : l.ut, l.us, 1, st, flag, um0, rows);
-    else if (w0) rc = run_modulate_wino(x, coef, gb, a, B, tdup ? l.T / 2 : l.T, l.H, l.W, b.n_in, tdup ? 1 : l.ut, l.us, 1, st, flag, um0, rows);
-    else if (tdup) rc = run_modulate(x, coef, gb, a, B, l.T / 2, l.H, l.W, b.n_in, 1, l.us, 1, st, true, flag, um0, rows);
-    else rc = run_modulate(x, coef, gb, a, B, l.T, l.H, l.W, b.n_in, l.ut, l.us, 1, st, f16_0, flag, um0, rows);
-    if (rc) return rc;
-    // (the one-term operand is tapped whole: 3 bytes per activation of CinPad channels)
-    if (!f0 && !g0 && (rc = tap(k, 1, a, h0 ? (size_t)B * (tdup ? P / 2 : P) * b.conv0_w4h.CinPad * 3 / 4 : (size_t)B * (tdup ? P / 2 : P) * b.n_in))) return rc;
-    const bool fuse = f16_0 && conv16_can_fuse_stats(tdup ? l.T / 2 : l.T, l.H, l.W);
-    d->prof_cur_layer = 2 * k;
-    d->prof_cur_kernel = h0 ? 6 : g0 ? 4 : q0 ? 3 : w0 ? 2 : f16_0 ? 1 : f0 ? 5 : 0;
-    if (h0) rc = conv3_w4h(d, b.conv0_w4h, a, dx, nullptr, 1, 1, B, l, EPI_NONE, st, fuse ? sums2 : nullptr);
-    else if (g0) rc = conv3_w4g(d, b.conv0_w4, x, coef, gb, 2, dx, nullptr, 1, 1, B, l, EPI_NONE, st, fuse ? sums2 : nullptr, flag, um0, rows);
-    else if (f0) rc = conv3_wf(d, b.conv0_wf, a, w.m6, dx, nullptr, 1, 1, B, l, EPI_NONE, st);
-    else if (q0) rc = conv3_w4(d, b.conv0_w4, a, dx, nullptr, 1, 1, B, l, EPI_NONE, st, fuse ? sums2 : nullptr);
-    else if (w0) rc = conv3_w(d, b.conv0_w, a, dx, nullptr, 1, 1, B, l, EPI_NONE, st, fuse ? sums2 : nullptr);
-    else if (f16_0) rc = conv3_16(d, b.conv0_16, a, dx, nullptr, 1, 1, B, l, EPI_NONE, st, fuse ? sums2 : nullptr, w.splitk, w.splitk_floats);
-    else rc = conv3(d, b.conv0, a, dx, nullptr, 1, 1, B, l, EPI_NONE, st);
-    if (rc) return rc;
+    // per conv: the kernel it runs in this call, its operand writer, the conv
+    const Conv3 &c0 = b.conv[0], &c1 = b.conv[1];
+    const Conv3In in0{x, coef, gb, l.ut, l.us, rows}, in1{dx, coef, nullptr, 1, 1, {}};
+    const Conv3Kernel k0 = conv3_choose(d, c0, l, 2 * k, in0, w.m6), k1 = conv3_choose(d, c1, l, 2 * k + 1, in1, w.m6);
+    size_t tap_floats = 0;
+    if ((rc = conv3_write_operand(d, c0, k0, l, 2 * k, in0, a, B, st, &tap_floats))) return rc;
+    if (tap_floats && (rc = tap(k, 1, a, tap_floats))) return rc;
+    // (statistics fused into the epilogue: split-fp16 kernels only; a tdup conv_0 is launched on the half-rate geometry)
+    const bool fuse = is_split(k0) && conv16_can_fuse_stats(c0.tdup ? l.T / 2 : l.T, l.H, l.W);
+    if ((rc = conv3_run(d, c0, k0, l, 2 * k, in0, a, dx, nullptr, 1, 1, B, EPI_NONE, fuse ? sums2 : nullptr, w, st))) return rc;
     if ((rc = tap(k, 2, dx, (size_t)B * P * b.n_mid))) return rc;
     // ADAIN (normalization_layer.py:47-51) + leaky_relu
     if (!fuse && (rc = run_stats(dx, sums2, B, P, b.n_mid, st))) return rc;
     if ((rc = run_coef(sums2, coef, B, b.n_mid, b.n_mid, (double)P, zl, zstride, b.zoff, nullptr, nullptr, st))) return rc;
-    if (g1) rc = I2V_OK;
-    else if (f1) rc = modulate_wino4_f32(dx, coef, nullptr, a, B, l.T, l.H, l.W, b.n_mid, 1, 1, 1, st);
-    else if (h1) rc = run_modulate_wino4h(dx, coef, nullptr, a, B, l.T, l.H, l.W, b.n_mid, 1, 1, 1, st, flag, um1);
-    else if (q1) rc = run_modulate_wino4(dx, coef, nullptr, a, B, l.T, l.H, l.W, b.n_mid, 1, 1, 1, st, flag, um1);
-    else if (w1) rc = run_modulate_wino(dx, coef, nullptr, a, B, l.T, l.H, l.W, b.n_mid, 1, 1, 1, st, flag, um1);
-    else rc = run_modulate(dx, coef, nullptr, a, B, l.T, l.H, l.W, b.n_mid, 1, 1, 1, st, f16_1, flag, um1);
-    if (rc) return rc;
-    if (!f1 && !g1 && (rc = tap(k, 3, a, h1 ? (size_t)B * P * b.conv1_w4h.CinPad * 3 / 4 : (size_t)B * P * b.n_mid))) return rc;
+    if ((rc = conv3_write_operand(d, c1, k1, l, 2 * k + 1, in1, a, B, st, &tap_floats))) return rc;
+    if (tap_floats && (rc = tap(k, 3, a, tap_floats))) return rc;
     // shortcut (decoder.py:44-49) at low resolution
     const float* res = x;
     if (b.learned && !side_shortcut) {
@@ -1250,18 +1214,9 @@ int block_forward(i2v_dec* d, int k, Block& b, const Level& l, const float* x, f
     // g_4's output only feeds conv_img(leaky_relu(x)) (decoder.py:117): fuse the activation here
     // (the shortcut's coefficients were derived from sums1 above, so conv_1 may now overwrite sums1 with the
     // statistics of the block OUTPUT = the next block's input)
-    const bool fuse_out = f16_1 && conv16_can_fuse_stats(l.T, l.H, l.W) && !last;
-    d->prof_cur_layer = 2 * k + 1;
-    d->prof_cur_kernel = h1 ? 6 : g1 ? 4 : q1 ? 3 : w1 ? 2 : f16_1 ? 1 : f1 ? 5 : 0;
-    if (h1) rc = conv3_w4h(d, b.conv1_w4h, a, xn, res, l.ut, l.us, B, l, last ? EPI_LRELU : EPI_NONE, st, fuse_out ? sums_out : nullptr);
-    else if (g1) rc = conv3_w4g(d, b.conv1_w4, dx, coef, nullptr, 1, xn, res, l.ut, l.us, B, l, last ? EPI_LRELU : EPI_NONE, st, fuse_out ? sums_out : nullptr, flag, um1);
-    else if (f1) rc = conv3_wf(d, b.conv1_wf, a, w.m6, xn, res, l.ut, l.us, B, l, last ? EPI_LRELU : EPI_NONE, st);
-    else if (q1) rc = conv3_w4(d, b.conv1_w4, a, xn, res, l.ut, l.us, B, l, last ? EPI_LRELU : EPI_NONE, st, fuse_out ? sums_out : nullptr);
-    else if (w1) rc = conv3_w(d, b.conv1_w, a, xn, res, l.ut, l.us, B, l, last ? EPI_LRELU : EPI_NONE, st, fuse_out ? sums_out : nullptr);
-    else if (f16_1) rc = conv3_16(d, b.conv1_16, a, xn, res, l.ut, l.us, B, l, last ? EPI_LRELU : EPI_NONE, st, fuse_out ? sums_out : nullptr,
-                                w.splitk, w.splitk_floats);
-    else rc = conv3(d, b.conv1, a, xn, res, l.ut, l.us, B, l, last ? EPI_LRELU : EPI_NONE, st);
-    if (rc) return rc;
+    const bool fuse_out = is_split(k1) && conv16_can_fuse_stats(l.T, l.H, l.W) && !last;
+    if ((rc = conv3_run(d, c1, k1, l, 2 * k + 1, in1, a, xn, res, l.ut, l.us, B, last ? EPI_LRELU : EPI_NONE, fuse_out ? sums_out : nullptr, w, st)))
+        return rc;
     x_stats_ready = fuse_out;
     if ((rc = tap(k, 5, xn, (size_t)B * P * b.n_out))) return rc;
     return I2V_OK;
@@ -1304,25 +1259,74 @@ int sn_pack(const StateDict& sd, const std::string& name, bool spectral, int cou
     return out.pack(w, bias, cout, cin, k, k, k, scale);
 }
 
-int sn_pack_wf(const StateDict& sd, const std::string& name, bool spectral, int cout, int cin, Wino4F32Weights& out) {
-    const float* bias = sd.f32(name + ".bias", cout);
+// Packs the kernel variants `variants` (bits of Conv3Kernel; K_F43_GEN reads K_F43's weights) of one block conv from the state dict
+int pack_conv3(const StateDict& sd, const std::string& name, bool spectral, Conv3& c, unsigned variants) {
+    const float* bias = sd.f32(name + ".bias", c.cout);
     if (!bias) return I2V_E_MISSING;
     const float* w = nullptr;
     double scale = 1.0;
-    int rc = sn_scale(sd, name, spectral, cout, (int64_t)cin * 27, &w, &scale);
+    int rc = sn_scale(sd, name, spectral, c.cout, (int64_t)c.cin * 27, &w, &scale);
     if (rc) return rc;
-    return out.pack(w, bias, cout, cin, scale);
+    const int co = c.cout, ci = c.cin;
+    if ((variants & bit(K_F32)) && (rc = c.f32.pack(w, bias, co, ci, 3, 3, 3, scale))) return rc;
+    if ((variants & bit(K_F32_WINO)) && (rc = c.wf.pack(w, bias, co, ci, scale))) return rc;
+    // (tdup: packed for the half-rate input, Conv16Weights::pack_tdup)
+    if ((variants & bit(K_F16)) && (rc = c.tdup ? c.d16.pack_tdup(w, bias, co, ci, scale) : c.d16.pack(w, bias, co, ci, 3, 3, 3, scale))) return rc;
+    if ((variants & bit(K_F23)) && (rc = c.tdup ? c.w23.pack_tdup(w, bias, co, ci, scale) : c.w23.pack(w, bias, co, ci, 3, scale))) return rc;
+    if ((variants & bit(K_F43)) && (rc = c.tdup ? c.w43.pack_tdup(w, bias, co, ci, scale) : c.w43.pack(w, bias, co, ci, scale))) return rc;
+    if ((variants & bit(K_F43_ONE)) && (rc = c.tdup ? c.w43h.pack_tdup(w, bias, co, ci, scale) : c.w43h.pack(w, bias, co, ci, scale))) return rc;
+    return I2V_OK;
 }
 
-// conv_0 of a block that sits behind a x2 temporal up-sampling: packed for the half-rate input (Conv16Weights::pack_tdup)
-int sn_pack_tdup(const StateDict& sd, const std::string& name, bool spectral, int cout, int cin, Conv16Weights& out) {
-    const float* bias = sd.f32(name + ".bias", cout);
-    if (!bias) return I2V_E_MISSING;
-    const float* w = nullptr;
-    double scale = 1.0;
-    int rc = sn_scale(sd, name, spectral, cout, (int64_t)cin * 27, &w, &scale);
-    if (rc) return rc;
-    return out.pack_tdup(w, bias, cout, cin, scale);
+// Spade (keys p + "norm_0.*"): Conv2d(3,128,3) then conv_gamma | conv_beta fused as one Conv2d(128, 2C, 3), the latter packed for the
+// kernels the caller names: gb16 / gb32 the direct split-fp16 / fp32 ones, gb_w4 -- else gb_w -- the F(4,3) / F(2,3) Winograd ones
+int pack_spade(const StateDict& sd, const std::string& p, Block& b, bool gb16, bool gb32, bool gb_w4, bool gb_w) {
+    int rc;
+    const float* w1 = sd.f32(p + "norm_0.conv.weight", 128 * 3 * 9);
+    const float* b1 = sd.f32(p + "norm_0.conv.bias", 128);
+    const float* wg = sd.f32(p + "norm_0.conv_gamma.weight", (int64_t)b.n_in * 128 * 9);
+    const float* bg = sd.f32(p + "norm_0.conv_gamma.bias", b.n_in);
+    const float* wb = sd.f32(p + "norm_0.conv_beta.weight", (int64_t)b.n_in * 128 * 9);
+    const float* bb = sd.f32(p + "norm_0.conv_beta.bias", b.n_in);
+    if (!w1 || !b1 || !wg || !bg || !wb || !bb) return I2V_E_MISSING;
+    if ((rc = b.sp_conv.pack(w1, b1, 128, 3, 1, 3, 3, 1.0))) return rc;
+    {   // the same conv for the split-fp16 path: input channels padded 3 -> 16 (the resize kernel's row)
+        std::vector<float> w16((size_t)128 * 16 * 9, 0.f);
+        for (int n = 0; n < 128; ++n)
+            for (int c = 0; c < 3; ++c)
+                for (int t = 0; t < 9; ++t) w16[((size_t)n * 16 + c) * 9 + t] = w1[((size_t)n * 3 + c) * 9 + t];
+        if ((rc = b.sp_conv16.pack(w16.data(), b1, 128, 16, 1, 3, 3, 1.0))) return rc;
+    }
+    std::vector<float> wgb((size_t)2 * b.n_in * 128 * 9), bgb((size_t)2 * b.n_in);
+    std::memcpy(wgb.data(), wg, (size_t)b.n_in * 128 * 9 * 4);
+    std::memcpy(wgb.data() + (size_t)b.n_in * 128 * 9, wb, (size_t)b.n_in * 128 * 9 * 4);
+    for (int c = 0; c < b.n_in; ++c) { bgb[c] = bg[c] + 1.0f; bgb[b.n_in + c] = bb[c]; }  // normalized*(1+gamma)+beta
+    if (gb16 && (rc = b.sp_gb16.pack(wgb.data(), bgb.data(), 2 * b.n_in, 128, 1, 3, 3, 1.0))) return rc;
+    if (gb32 && (rc = b.sp_gb.pack(wgb.data(), bgb.data(), 2 * b.n_in, 128, 1, 3, 3, 1.0))) return rc;
+    if (gb_w4) return b.sp_gb_w4.pack(wgb.data(), bgb.data(), 2 * b.n_in, 128, 1.0, 1);
+    if (gb_w) return b.sp_gb_w.pack(wgb.data(), bgb.data(), 2 * b.n_in, 128, 1, 1.0);
+    return I2V_OK;
+}
+
+// The environment switches of a handle.  A stand-alone block (i2v_gblock; whole = false) reads the three that choose among its conv
+// kernels and keeps the defaults of the rest.
+void read_switches(i2v_dec* d, bool whole) {
+    if (const char* e = std::getenv("I2V_DEC_WINO")) d->wino = std::atoi(e) != 0;
+    if (const char* e = std::getenv("I2V_DEC_WINO4")) d->wino4 = std::atoi(e);
+    if (const char* e = std::getenv("I2V_DEC_PW16")) d->pw16 = std::atoi(e) != 0;
+    if (!whole) return;
+    if (const char* e = std::getenv("I2V_DEC_IMG16")) d->img16 = std::atoi(e);
+    if (const char* e = std::getenv("I2V_DEC_SPW")) d->spw = std::atoi(e) != 0;
+    if (const char* e = std::getenv("I2V_DEC_WINO32")) d->wino32 = std::atoi(e) != 0;
+    if (const char* e = std::getenv("I2V_DEC_GEN")) d->gen = std::atoi(e);   // 1: conv_0 and conv_1 of the thin level, 2: conv_1 only
+    if (const char* e = std::getenv("I2V_DEC_OVERLAP")) { d->overlap = std::atoi(e) != 0; d->no_side_shortcut = std::atoi(e) == 2; }
+    if (const char* e = std::getenv("I2V_DEC_SUB")) d->sub = std::max(0, std::atoi(e));
+}
+
+// the channel counts of a block's two convs; tdup: the block sits behind a x2 temporal up-sampling (Conv3::tdup)
+void init_convs(Block& b, bool tdup) {
+    b.conv[0].cin = b.n_in; b.conv[0].cout = b.conv[1].cin = b.n_mid; b.conv[1].cout = b.n_out;
+    b.conv[0].tdup = tdup;
 }
 
 // device binding + the sticky range flag (device word and pinned host mirror)
@@ -1346,36 +1350,6 @@ int check_entry(i2v_dec* d, const char* what) {
     return I2V_OK;
 }
 
-int sn_pack_wino(const StateDict& sd, const std::string& name, bool spectral, int cout, int cin, bool tdup, Wino16Weights& out) {
-    const float* bias = sd.f32(name + ".bias", cout);
-    if (!bias) return I2V_E_MISSING;
-    const float* w = nullptr;
-    double scale = 1.0;
-    int rc = sn_scale(sd, name, spectral, cout, (int64_t)cin * 27, &w, &scale);
-    if (rc) return rc;
-    return tdup ? out.pack_tdup(w, bias, cout, cin, scale) : out.pack(w, bias, cout, cin, 3, scale);
-}
-
-int sn_pack_wino4h(const StateDict& sd, const std::string& name, bool spectral, int cout, int cin, bool tdup, Wino4hWeights& out) {
-    const float* bias = sd.f32(name + ".bias", cout);
-    if (!bias) return I2V_E_MISSING;
-    const float* w = nullptr;
-    double scale = 1.0;
-    int rc = sn_scale(sd, name, spectral, cout, (int64_t)cin * 27, &w, &scale);
-    if (rc) return rc;
-    return tdup ? out.pack_tdup(w, bias, cout, cin, scale) : out.pack(w, bias, cout, cin, scale);
-}
-
-int sn_pack_wino4(const StateDict& sd, const std::string& name, bool spectral, int cout, int cin, bool tdup, Wino4Weights& out) {
-    const float* bias = sd.f32(name + ".bias", cout);
-    if (!bias) return I2V_E_MISSING;
-    const float* w = nullptr;
-    double scale = 1.0;
-    int rc = sn_scale(sd, name, spectral, cout, (int64_t)cin * 27, &w, &scale);
-    if (rc) return rc;
-    return tdup ? out.pack_tdup(w, bias, cout, cin, scale) : out.pack(w, bias, cout, cin, scale);
-}
-
 }  // namespace
 
 extern "C" {
@@ -1397,15 +1371,7 @@ int i2v_dec_create(const i2v_dec_cfg* cfg, i2v_dec** out) {
     I2V_REQUIRE(ndev > 0, I2V_E_HIP, "i2v_dec_create: no HIP device");
     auto d = std::make_unique<i2v_dec>();
     d->cfg = *cfg;
-    if (const char* e = std::getenv("I2V_DEC_WINO")) d->wino = std::atoi(e) != 0;
-    if (const char* e = std::getenv("I2V_DEC_WINO4")) d->wino4 = std::atoi(e);
-    if (const char* e = std::getenv("I2V_DEC_PW16")) d->pw16 = std::atoi(e) != 0;
-    if (const char* e = std::getenv("I2V_DEC_IMG16")) d->img16 = std::atoi(e);
-    if (const char* e = std::getenv("I2V_DEC_SPW")) d->spw = std::atoi(e) != 0;
-    if (const char* e = std::getenv("I2V_DEC_WINO32")) d->wino32 = std::atoi(e) != 0;
-    if (const char* e = std::getenv("I2V_DEC_GEN")) d->gen = std::atoi(e);   // 1: conv_0 and conv_1 of the thin level, 2: conv_1 only
-    if (const char* e = std::getenv("I2V_DEC_OVERLAP")) { d->overlap = std::atoi(e) != 0; d->no_side_shortcut = std::atoi(e) == 2; }
-    if (const char* e = std::getenv("I2V_DEC_SUB")) d->sub = std::max(0, std::atoi(e));
+    read_switches(d.get(), true);
     if (int rc = init_status(d.get())) return rc;
     const int nf = d->nf = cfg->channel_factor;
     const char* names[6] = {"head_0", "g_0", "g_1", "g_2", "g_3", "g_4"};
@@ -1427,6 +1393,7 @@ int i2v_dec_create(const i2v_dec_cfg* cfg, i2v_dec** out) {
         if (k == 5) { ut = cfg->upsample_t[1]; us = cfg->upsample_s[1]; }          // :114
         T *= ut; S *= us;
         d->lvl[k] = Level{T, S, S, ut, us};
+        init_convs(b, ut == 2);
     }
     d->Nz = zoff;
     *out = d.release();
@@ -1459,29 +1426,18 @@ int i2v_dec_load(i2v_dec* d, const i2v_tensor* tensors, int32_t n_tensors) {
     for (int k = 0; k < 6; ++k) {
         Block& b = d->blk[k];
         const std::string p = b.name + ".";
-        if (d->has16()) {
-            // behind a x2 up-sampling in time, SPADE's output is identical for frames 2i and 2i+1 (gamma/beta do not depend
-            // on t): conv_0 runs on the half-rate tensor with two pre-summed 2-tap temporal kernels (-1/3 of its MACs)
-            b.tdup0 = d->lvl[k].ut == 2;
-            // layers whose shape allows it run on the Winograd kernel (1.5x fewer MFMAs), the rest on the direct one
-            if (want_w4_0(d, b, d->lvl[k]) && d->one16()) rc = sn_pack_wino4h(sd, p + "conv_0", sn, b.n_mid, b.n_in, b.tdup0, b.conv0_w4h);
-            else if (want_w4_0(d, b, d->lvl[k])) rc = sn_pack_wino4(sd, p + "conv_0", sn, b.n_mid, b.n_in, b.tdup0, b.conv0_w4);
-            else if (want_wino0(d, b, d->lvl[k])) rc = sn_pack_wino(sd, p + "conv_0", sn, b.n_mid, b.n_in, b.tdup0, b.conv0_w);
-            else if (b.tdup0) rc = sn_pack_tdup(sd, p + "conv_0", sn, b.n_mid, b.n_in, b.conv0_16);
-            else rc = sn_pack(sd, p + "conv_0", sn, b.n_mid, b.n_in, 3, true, b.conv0_16);
-            if (rc) return rc;
-            if (want_w4_1(d, b, d->lvl[k]) && d->one16()) rc = sn_pack_wino4h(sd, p + "conv_1", sn, b.n_out, b.n_mid, false, b.conv1_w4h);
-            else if (want_w4_1(d, b, d->lvl[k])) rc = sn_pack_wino4(sd, p + "conv_1", sn, b.n_out, b.n_mid, false, b.conv1_w4);
-            else if (want_wino1(d, b, d->lvl[k])) rc = sn_pack_wino(sd, p + "conv_1", sn, b.n_out, b.n_mid, false, b.conv1_w);
-            else rc = sn_pack(sd, p + "conv_1", sn, b.n_out, b.n_mid, 3, true, b.conv1_16);
-            if (rc) return rc;
-        }
-        if (d->has32()) {   // (mma = auto packs both sets)
-            if ((rc = sn_pack(sd, p + "conv_0", sn, b.n_mid, b.n_in, 3, true, b.conv0))) return rc;
-            if ((rc = sn_pack(sd, p + "conv_1", sn, b.n_out, b.n_mid, 3, true, b.conv1))) return rc;
-            // from the 8x8 level on: Winograd F(4,3) on the fp32 matrix cores (half the MFMA work of the 27-tap kernel)
-            if (want_wf_0(d, b, d->lvl[k]) && (rc = sn_pack_wf(sd, p + "conv_0", sn, b.n_mid, b.n_in, b.conv0_wf))) return rc;
-            if (want_wf_1(d, b, d->lvl[k]) && (rc = sn_pack_wf(sd, p + "conv_1", sn, b.n_out, b.n_mid, b.conv1_wf))) return rc;
+        for (int i = 0; i < 2; ++i) {
+            // split-fp16: the one kernel the layer's shape selects (mma = 3: F(4,3) in its one-term form); exact fp32: the direct kernel
+            // and, from the 8x8 level on, Winograd F(4,3) on the fp32 matrix cores (half the MFMA work of the 27-tap kernel).
+            // (mma = auto packs both sets)
+            Conv3& c = b.conv[i];
+            unsigned variants = 0;
+            if (d->has16()) {
+                const Conv3Kernel s = conv3_split_kernel(d, c, d->lvl[k]);
+                variants |= bit(s == K_F43 && d->one16() ? K_F43_ONE : s);
+            }
+            if (d->has32()) variants |= bit(K_F32) | (conv3_wants(d, c, d->lvl[k], K_F32_WINO) ? bit(K_F32_WINO) : 0);
+            if ((rc = pack_conv3(sd, p + (i ? "conv_1" : "conv_0"), sn, c, variants))) return rc;
         }
         if (b.learned) {
             if ((rc = sn_pack(sd, p + "conv_s", sn, b.n_out, b.n_in, 1, false, b.convs))) return rc;
@@ -1492,32 +1448,7 @@ int i2v_dec_load(i2v_dec* d, const i2v_tensor* tensors, int32_t n_tensors) {
             if ((rc = b.gn_w.upload(gw, (size_t)b.n_in * 4))) return rc;
             if ((rc = b.gn_b.upload(gb, (size_t)b.n_in * 4))) return rc;
         }
-        // Spade: Conv2d(3,128,3) then conv_gamma | conv_beta fused as one Conv2d(128, 2C, 3)
-        const float* w1 = sd.f32(p + "norm_0.conv.weight", 128 * 3 * 9);
-        const float* b1 = sd.f32(p + "norm_0.conv.bias", 128);
-        const float* wg = sd.f32(p + "norm_0.conv_gamma.weight", (int64_t)b.n_in * 128 * 9);
-        const float* bg = sd.f32(p + "norm_0.conv_gamma.bias", b.n_in);
-        const float* wb = sd.f32(p + "norm_0.conv_beta.weight", (int64_t)b.n_in * 128 * 9);
-        const float* bb = sd.f32(p + "norm_0.conv_beta.bias", b.n_in);
-        if (!w1 || !b1 || !wg || !bg || !wb || !bb) return I2V_E_MISSING;
-        if ((rc = b.sp_conv.pack(w1, b1, 128, 3, 1, 3, 3, 1.0))) return rc;
-        {   // the same conv for the split-fp16 path: input channels padded 3 -> 16 (the resize kernel's row)
-            std::vector<float> w16((size_t)128 * 16 * 9, 0.f);
-            for (int n = 0; n < 128; ++n)
-                for (int c = 0; c < 3; ++c)
-                    for (int t = 0; t < 9; ++t) w16[((size_t)n * 16 + c) * 9 + t] = w1[((size_t)n * 3 + c) * 9 + t];
-            if ((rc = b.sp_conv16.pack(w16.data(), b1, 128, 16, 1, 3, 3, 1.0))) return rc;
-        }
-        std::vector<float> wgb((size_t)2 * b.n_in * 128 * 9), bgb((size_t)2 * b.n_in);
-        std::memcpy(wgb.data(), wg, (size_t)b.n_in * 128 * 9 * 4);
-        std::memcpy(wgb.data() + (size_t)b.n_in * 128 * 9, wb, (size_t)b.n_in * 128 * 9 * 4);
-        for (int c = 0; c < b.n_in; ++c) { bgb[c] = bg[c] + 1.0f; bgb[b.n_in + c] = bb[c]; }  // normalized*(1+gamma)+beta
-        if (d->has16() && (rc = b.sp_gb16.pack(wgb.data(), bgb.data(), 2 * b.n_in, 128, 1, 3, 3, 1.0))) return rc;
-        if (d->has32() && (rc = b.sp_gb.pack(wgb.data(), bgb.data(), 2 * b.n_in, 128, 1, 3, 3, 1.0))) return rc;
-        if (spade_w4_wanted(d, b, d->lvl[k])) {
-            if ((rc = b.sp_gb_w4.pack(wgb.data(), bgb.data(), 2 * b.n_in, 128, 1.0, 1))) return rc;
-        } else if (spade_wino_wanted(d, b, d->lvl[k]) && (rc = b.sp_gb_w.pack(wgb.data(), bgb.data(), 2 * b.n_in, 128, 1, 1.0)))
-            return rc;
+        if ((rc = pack_spade(sd, p, b, d->has16(), d->has32(), spade_w4_wanted(d, b, d->lvl[k]), spade_wino_wanted(d, b, d->lvl[k])))) return rc;
         // ADAIN linear rows into the shared z-GEMM
         const float* lw = sd.f32(p + "norm_1.linear.weight", (int64_t)2 * b.n_mid * zd);
         const float* lb = sd.f32(p + "norm_1.linear.bias", (int64_t)2 * b.n_mid);
@@ -2040,9 +1971,7 @@ int i2v_gblock_create(int32_t n_in, int32_t n_out, int32_t z_dim, int32_t spectr
     g->ctx.cfg.mma = mma;
     g->ctx.cfg.spectral_norm = spectral_norm;
     g->ctx.cfg.z_dim = z_dim;
-    if (const char* e = std::getenv("I2V_DEC_WINO")) g->ctx.wino = std::atoi(e) != 0;
-    if (const char* e = std::getenv("I2V_DEC_PW16")) g->ctx.pw16 = std::atoi(e) != 0;
-    if (const char* e = std::getenv("I2V_DEC_WINO4")) g->ctx.wino4 = std::atoi(e);
+    read_switches(&g->ctx, false);
     if (int rc = init_status(&g->ctx)) return rc;
     g->z_dim = z_dim;
     Block& b = g->b;
@@ -2053,6 +1982,7 @@ int i2v_gblock_create(int32_t n_in, int32_t n_out, int32_t z_dim, int32_t spectr
     while (n_in % grp) --grp;
     b.groups_spade = grp;
     b.zoff = 0;
+    init_convs(b, false);
     *out = g.release();
     return I2V_OK;
 }
@@ -2068,25 +1998,16 @@ int i2v_gblock_load(i2v_gblock* g, const i2v_tensor* tensors, int32_t n_tensors)
     int rc;
     g->has_convs = g->has_spade = g->has_adain = g->has_norm_s = false;
     if (sd.has(sn ? "conv_0.weight_orig" : "conv_0.weight")) {
-        if (f16) {
-            if ((rc = sn_pack(sd, "conv_0", sn, b.n_mid, b.n_in, 3, true, b.conv0_16))) return rc;
-            if ((rc = sn_pack(sd, "conv_1", sn, b.n_out, b.n_mid, 3, true, b.conv1_16))) return rc;
-            // the geometry is only known at the call: also pack the Winograd variants where the channel counts allow them
-            if (g->ctx.wino && wino16_supported(b.n_mid, b.n_in, 16, 64, 64) &&
-                (rc = sn_pack_wino(sd, "conv_0", sn, b.n_mid, b.n_in, false, b.conv0_w))) return rc;
-            if (g->ctx.wino && wino16_supported(b.n_out, b.n_mid, 16, 64, 64) &&
-                (rc = sn_pack_wino(sd, "conv_1", sn, b.n_out, b.n_mid, false, b.conv1_w))) return rc;
-            // ... and the F(4,3) variants (used where the call's geometry gives a sample >= 32 workgroups; I2V_DEC_WINO4=2: always)
-            //     (mma = 3: their one-term form instead)
-            if (g->ctx.wino && g->ctx.wino4 && wino4_supported(b.n_mid, b.n_in, 16, 64, 64, 3) &&
-                (rc = one ? sn_pack_wino4h(sd, "conv_0", sn, b.n_mid, b.n_in, false, b.conv0_w4h)
-                          : sn_pack_wino4(sd, "conv_0", sn, b.n_mid, b.n_in, false, b.conv0_w4))) return rc;
-            if (g->ctx.wino && g->ctx.wino4 && wino4_supported(b.n_out, b.n_mid, 16, 64, 64, 3) &&
-                (rc = one ? sn_pack_wino4h(sd, "conv_1", sn, b.n_out, b.n_mid, false, b.conv1_w4h)
-                          : sn_pack_wino4(sd, "conv_1", sn, b.n_out, b.n_mid, false, b.conv1_w4))) return rc;
-        } else {
-            if ((rc = sn_pack(sd, "conv_0", sn, b.n_mid, b.n_in, 3, true, b.conv0))) return rc;
-            if ((rc = sn_pack(sd, "conv_1", sn, b.n_out, b.n_mid, 3, true, b.conv1))) return rc;
+        // the geometry is only known at the call: next to the direct kernel, pack the Winograd variants where the channel counts allow
+        // them at a nominal 16 x 64 x 64 -- F(2,3), and F(4,3) (used where the call's geometry gives a sample >= 32 workgroups;
+        // I2V_DEC_WINO4=2: always; mma = 3: its one-term form instead)
+        const Level probe{16, 64, 64, 1, 1};
+        for (int i = 0; i < 2; ++i) {
+            Conv3& c = b.conv[i];
+            unsigned variants = bit(K_F32);
+            if (f16) variants = bit(K_F16) | (conv3_wants(&g->ctx, c, probe, K_F23) ? bit(K_F23) : 0) |
+                                (conv3_wants(&g->ctx, c, probe, K_F43) ? bit(one ? K_F43_ONE : K_F43) : 0);
+            if ((rc = pack_conv3(sd, i ? "conv_1" : "conv_0", sn, c, variants))) return rc;
         }
         if (b.learned && (rc = sn_pack(sd, "conv_s", sn, b.n_out, b.n_in, 1, false, b.convs))) return rc;
         if (b.learned && f16 && g->ctx.pw16 && (rc = sn_pack(sd, "conv_s", sn, b.n_out, b.n_in, 1, false, b.convs16))) return rc;
@@ -2101,28 +2022,7 @@ int i2v_gblock_load(i2v_gblock* g, const i2v_tensor* tensors, int32_t n_tensors)
         g->has_norm_s = true;
     }
     if (sd.has("norm_0.conv.weight")) {
-        const float* w1 = sd.f32("norm_0.conv.weight", 128 * 3 * 9);
-        const float* b1 = sd.f32("norm_0.conv.bias", 128);
-        const float* wg = sd.f32("norm_0.conv_gamma.weight", (int64_t)b.n_in * 128 * 9);
-        const float* bg = sd.f32("norm_0.conv_gamma.bias", b.n_in);
-        const float* wb = sd.f32("norm_0.conv_beta.weight", (int64_t)b.n_in * 128 * 9);
-        const float* bb = sd.f32("norm_0.conv_beta.bias", b.n_in);
-        if (!w1 || !b1 || !wg || !bg || !wb || !bb) return I2V_E_MISSING;
-        if ((rc = b.sp_conv.pack(w1, b1, 128, 3, 1, 3, 3, 1.0))) return rc;
-        {   // the same conv for the split-fp16 path: input channels padded 3 -> 16 (the resize kernel's row)
-            std::vector<float> w16((size_t)128 * 16 * 9, 0.f);
-            for (int n = 0; n < 128; ++n)
-                for (int c = 0; c < 3; ++c)
-                    for (int t = 0; t < 9; ++t) w16[((size_t)n * 16 + c) * 9 + t] = w1[((size_t)n * 3 + c) * 9 + t];
-            if ((rc = b.sp_conv16.pack(w16.data(), b1, 128, 16, 1, 3, 3, 1.0))) return rc;
-        }
-        std::vector<float> wgb((size_t)2 * b.n_in * 128 * 9), bgb((size_t)2 * b.n_in);
-        std::memcpy(wgb.data(), wg, (size_t)b.n_in * 128 * 9 * 4);
-        std::memcpy(wgb.data() + (size_t)b.n_in * 128 * 9, wb, (size_t)b.n_in * 128 * 9 * 4);
-        for (int c = 0; c < b.n_in; ++c) { bgb[c] = bg[c] + 1.0f; bgb[b.n_in + c] = bb[c]; }
-        if (f16) rc = b.sp_gb16.pack(wgb.data(), bgb.data(), 2 * b.n_in, 128, 1, 3, 3, 1.0);
-        else rc = b.sp_gb.pack(wgb.data(), bgb.data(), 2 * b.n_in, 128, 1, 3, 3, 1.0);
-        if (rc) return rc;
+        if ((rc = pack_spade(sd, "", b, f16, !f16, false, false))) return rc;
         g->has_spade = true;
     }
     if (sd.has("norm_1.linear.weight")) {
@@ -2200,18 +2100,7 @@ int i2v_gblock_norm(i2v_gblock* g, int32_t part, const float* x, const float* co
     if (part == 0) {        // Spade.forward(x, img), normalization_layer.py:18-24
         I2V_REQUIRE(g->has_spade && cond, I2V_E_STATE, "i2v_gblock_norm: Spade weights not loaded / no start frame");
         if ((rc = run_coef(sums, coef, B, C, b.groups_spade, (double)P, nullptr, 0, 0, nullptr, nullptr, st))) return rc;
-        const long tot = (long)B * h * w;
-        hipLaunchKernelGGL(resize_kernel, dim3((unsigned)std::min<long>((tot + 255) / 256, 65536)), dim3(256), 0, st, cond, F(L.y0), B,
-                           img_h, img_w, h, w, g->ctx.has16() ? 1 : 0, g->ctx.status_dev, (long)3 * img_h * img_w);
-        I2V_HIP_CHECK(hipGetLastError());
-        if (g->ctx.has16()) {
-            if ((rc = conv16_forward(b.sp_conv16, F(L.y0), reinterpret_cast<float*>(F(L.y1)), nullptr, 1, 1, B, 1, h, w,
-                                     EPI_LRELU | EPI_HL16, st, nullptr, g->ctx.status_dev))) return rc;
-            if ((rc = conv16_forward(b.sp_gb16, F(L.y1), F(L.gb), nullptr, 1, 1, B, 1, h, w, EPI_NONE, st))) return rc;
-        } else {
-            if ((rc = conv_forward(b.sp_conv, F(L.y0), 16, F(L.y1), nullptr, 1, 1, B, 1, h, w, EPI_LRELU, st))) return rc;
-            if ((rc = conv_forward(b.sp_gb, F(L.y1), 128, F(L.gb), nullptr, 1, 1, B, 1, h, w, EPI_NONE, st))) return rc;
-        }
+        if ((rc = spade_branch(&g->ctx, b, Level{t, h, w, 1, 1}, cond, img_h, img_w, B, F(L.y0), F(L.y1), nullptr, F(L.gb), st))) return rc;
         if ((rc = run_modulate(x_cl, coef, F(L.gb), a, B, t, h, w, C, 1, 1, 0, st))) return rc;
     } else if (part == 1) { // ADAIN.forward(x, z), normalization_layer.py:47-51
         I2V_REQUIRE(g->has_adain && cond, I2V_E_STATE, "i2v_gblock_norm: ADAIN weights not loaded / no latent");
