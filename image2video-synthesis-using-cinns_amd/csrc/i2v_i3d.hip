@@ -1,0 +1,572 @@
+// Kinetics-400 I3D (the FVD feature network) and the FVD statistics accumulator.
+//
+// Replaces metrics/PyTorch_FVD/I3D.py (I3D.forward, Unit3Dpy, MaxPool3dTFPadding, Mixed) and the host path in front of it,
+// metrics/PyTorch_FVD/FVD_logging.py:177-203 (preprocess: every frame to the host, a CPU bilinear resize, batches of 20 back).
+// Frames stay on the device: the decoder's [B][T][3][H][W] output is resized (bilinear, align_corners=True) to 224 x 224 and
+// de-normalised in one kernel that writes the channels-last stem input.
+//
+// Convolutions: ONE implicit-GEMM kernel on the exact-fp32 matrix cores (v_mfma_f32_16x16x4_f32).
+//   Out[m = (b,to,ho,wo) flattened][n] = relu(scale[n] * sum_k In[gather(m, k)] * W[k][n] + shift[n])
+// conv_forward (i2v_conv.hip) tiles T, H, W into bricks of 128 positions and pads symmetrically; this network has 14 x 14 and
+// 7 x 7 maps, an asymmetric "TF SAME" stem and Mixed blocks whose branches write channel slices of one tensor.  So here:
+//   * positions are flattened over B * To * Ho * Wo, 128 per workgroup, the last tile masked;
+//   * K is flattened over (tap, channel) in groups of 4 channels: a 16-wide K chunk of the 7x7x7 stem (4 channels: r, g, b, 0)
+//     holds 4 taps, a chunk of a 1x1x1 unit 16 channels -- one gather path for every unit, no padded K work in the stem;
+//   * kernel, stride and per-side padding are arguments; so are the channel stride / offset of the input and of the output
+//     (the four branches of a Mixed block store straight into their slice: there is no concat kernel);
+//   * epilogue: eval-mode BatchNorm3d folded to (scale, shift) at load, ReLU.
+// 4 waves x (32 rows x BN columns) per workgroup, BN in {32, 64, 128}; A and W chunks are double-buffered in LDS (rows of 16
+// floats padded to 20: conflict-free ds_read_b128), the next chunk's global loads are in flight during the MFMAs: one barrier
+// per chunk.  Loads are unconditional with clamped addresses.  The K order of a position does not depend on the batch or on the
+// tile it falls in: batch rows equal their single-sample runs bit for bit, and there are no atomics anywhere.
+//
+// Max pools pad with ZEROS that take part in the maximum (ConstantPad3d(.., 0) in front of MaxPool3d(ceil_mode=True)).
+#include <algorithm>
+#include <cmath>
+#include <memory>
+
+#include "i2v_common.h"
+
+namespace i2v {
+namespace {
+
+constexpr int I3D_BM = 128;
+constexpr int I3D_LS = 20;    // floats per staged row of 16
+constexpr int I3D_SIDE = 224;
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+struct I3dConvArgs {
+    const float* in;     // channels-last [B][Ti][Hi][Wi][inCS], the unit reads channels [inOff, inOff + 4 C4)
+    const float* wp;     // [nchunk][CoutPad][16]
+    const float2* ss;    // [CoutPad] (scale, shift)
+    float* out;          // [M][outCS], the unit writes channels [outOff, outOff + Cout)
+    long M;
+    int Ti, Hi, Wi, To, Ho, Wo;
+    int inCS, inOff, C4, G, nchunk;   // C4: groups of 4 input channels, G = taps * C4
+    int KH, KW, sT, sH, sW, pT, pH, pW;
+    int Cout, CoutPad, outCS, outOff, relu;
+};
+
+template <int NT>   // 16-column tiles per wave: BN = 16 NT
+__global__ __launch_bounds__(256) void i3d_conv_kernel(I3dConvArgs a) {
+    constexpr int BN = 16 * NT;
+    constexpr int WLD = (BN * 4 + 255) / 256;
+    __shared__ __attribute__((aligned(16))) float a_lds[2][I3D_BM * I3D_LS];
+    __shared__ __attribute__((aligned(16))) float w_lds[2][BN * I3D_LS];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lr = lane & 15, kq = lane >> 4;
+    const int nNt = a.CoutPad / BN;
+    const int n0 = (int)(blockIdx.x % nNt) * BN;
+    const long m0 = (long)(blockIdx.x / nNt) * I3D_BM;
+    const int q = tid & 3;
+
+    // the two staged rows of this thread: output position -> first input coordinate of its window
+    int rb[2], rt[2], rh[2], rw[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        long m = m0 + (tid >> 2) + 64 * u;
+        const bool ok = m < a.M;
+        if (!ok) m = 0;
+        const int wo = (int)(m % a.Wo); m /= a.Wo;
+        const int ho = (int)(m % a.Ho); m /= a.Ho;
+        const int to = (int)(m % a.To);
+        rb[u] = ok ? (int)(m / a.To) : -1;
+        rt[u] = to * a.sT - a.pT; rh[u] = ho * a.sH - a.pH; rw[u] = wo * a.sW - a.pW;
+    }
+    const int khw = a.KH * a.KW;
+
+    static_assert(WLD <= 2, "weight pieces per thread");
+    float4 pa0, pa1, pw0, pw1;   // (named, not arrays: arrays written under a branch go to scratch)
+    pw1 = make_float4(0.f, 0.f, 0.f, 0.f);
+    auto request = [&](int ch) {
+        const int g = ch * 4 + q;
+        const bool gok = g < a.G;
+        const int tap = gok ? g / a.C4 : 0;
+        const int c = (g - tap * a.C4) * 4;
+        const int dt = tap / khw, r2 = tap - dt * khw, dh = r2 / a.KW, dw = r2 - dh * a.KW;
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int t = rt[u] + dt, h = rh[u] + dh, w = rw[u] + dw;
+            const bool ok = gok && rb[u] >= 0 && (unsigned)t < (unsigned)a.Ti && (unsigned)h < (unsigned)a.Hi && (unsigned)w < (unsigned)a.Wi;
+            const long off = ok ? ((((long)rb[u] * a.Ti + t) * a.Hi + h) * a.Wi + w) * a.inCS + a.inOff + c : 0;
+            const float4 v = *reinterpret_cast<const float4*>(a.in + off);
+            const float4 z = ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
+            if (u == 0) pa0 = z; else pa1 = z;
+        }
+        const float* wsrc = a.wp + ((long)ch * a.CoutPad + n0) * 16;
+        pw0 = *reinterpret_cast<const float4*>(wsrc + (tid < BN * 4 ? tid : 0) * 4);
+        if constexpr (WLD > 1) pw1 = *reinterpret_cast<const float4*>(wsrc + (tid + 256) * 4);
+    };
+    auto park = [&](int buf) {
+        *reinterpret_cast<float4*>(&a_lds[buf][(tid >> 2) * I3D_LS + 4 * q]) = pa0;
+        *reinterpret_cast<float4*>(&a_lds[buf][((tid >> 2) + 64) * I3D_LS + 4 * q]) = pa1;
+        if (tid < BN * 4) *reinterpret_cast<float4*>(&w_lds[buf][(tid >> 2) * I3D_LS + 4 * q]) = pw0;
+        if constexpr (WLD > 1) *reinterpret_cast<float4*>(&w_lds[buf][((tid + 256) >> 2) * I3D_LS + 4 * q]) = pw1;
+    };
+
+    f32x4 acc[2][NT];
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    request(0);
+    park(0);
+    __syncthreads();
+    for (int ch = 0; ch < a.nchunk; ++ch) {
+        const int buf = ch & 1;
+        request(ch + 1 < a.nchunk ? ch + 1 : ch);
+        // MFMA k-slot (lane >> 4) of step s carries K element 4 (lane >> 4) + s of the chunk, for both operands
+        float4 av[2], bv[NT];
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) av[mt] = *reinterpret_cast<const float4*>(&a_lds[buf][(wave * 32 + 16 * mt + lr) * I3D_LS + 4 * kq]);
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) bv[nt] = *reinterpret_cast<const float4*>(&w_lds[buf][(16 * nt + lr) * I3D_LS + 4 * kq]);
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt) {
+                const float as = s == 0 ? av[mt].x : s == 1 ? av[mt].y : s == 2 ? av[mt].z : av[mt].w;
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) {
+                    const float bs = s == 0 ? bv[nt].x : s == 1 ? bv[nt].y : s == 2 ? bv[nt].z : bv[nt].w;
+                    acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(as, bs, acc[mt][nt], 0, 0, 0);
+                }
+            }
+        if (ch + 1 < a.nchunk) park(buf ^ 1);
+        __syncthreads();
+    }
+
+    // C/D layout of the 16x16 MFMA: column = lane & 15, rows 4 (lane >> 4) + r
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+        const int n = n0 + 16 * nt + lr;
+        if (n >= a.Cout) continue;
+        const float2 ss = a.ss[n];
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const long m = m0 + wave * 32 + 16 * mt + 4 * kq + r;
+                if (m >= a.M) continue;
+                float v = fmaf(acc[mt][nt][r], ss.x, ss.y);
+                if (a.relu) v = fmaxf(v, 0.f);
+                a.out[m * a.outCS + a.outOff + n] = v;
+            }
+    }
+}
+
+// FVD_logging.preprocess fused with the layout change: frames [N = B T][3][Hi][Wi] -> channels-last [N][224][224][4] (channel 3
+// zero), bilinear with align_corners=True in the arithmetic of torch's upsample_bilinear2d, then (x + 1) / 2 when `denorm`.
+__global__ __launch_bounds__(256) void i3d_input_kernel(const float* __restrict__ frames, float* __restrict__ out, long N, int Hi, int Wi,
+                                                        int denorm) {
+    const long total = N * I3D_SIDE * I3D_SIDE;
+    const float sh = (float)(Hi - 1) / (float)(I3D_SIDE - 1), sw = (float)(Wi - 1) / (float)(I3D_SIDE - 1);
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const int w = (int)(i % I3D_SIDE), h = (int)((i / I3D_SIDE) % I3D_SIDE);
+        const long n = i / (I3D_SIDE * I3D_SIDE);
+        const float fh = sh * h, fw = sw * w;
+        const int h0 = (int)fh, w0 = (int)fw;
+        const int h1 = h0 + (h0 < Hi - 1 ? 1 : 0), w1 = w0 + (w0 < Wi - 1 ? 1 : 0);
+        const float lh1 = fh - h0, lh0 = 1.f - lh1, lw1 = fw - w0, lw0 = 1.f - lw1;
+        float v[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float* pl = frames + (n * 3 + c) * (long)Hi * Wi;
+            v[c] = lh0 * (lw0 * pl[h0 * Wi + w0] + lw1 * pl[h0 * Wi + w1]) + lh1 * (lw0 * pl[h1 * Wi + w0] + lw1 * pl[h1 * Wi + w1]);
+            if (denorm) v[c] = (v[c] + 1.0f) / 2.0f;
+        }
+        *reinterpret_cast<float4*>(out + i * 4) = make_float4(v[0], v[1], v[2], 0.f);
+    }
+}
+
+// MaxPool3dTFPadding: ConstantPad3d((p0, p1) per dimension, 0) then MaxPool3d(kernel, stride, ceil_mode=True).  A window position
+// inside the padded extent but outside the tensor contributes 0; one beyond the padded extent (ceil_mode) contributes nothing.
+struct I3dPoolArgs {
+    const float* in; float* out;
+    int B, Ti, Hi, Wi, To, Ho, Wo, C;
+    int kT, kH, kW, sT, sH, sW, pT, pH, pW;   // p*: padding in FRONT
+    int eT, eH, eW;                           // padded extents (front + size + back)
+};
+__global__ __launch_bounds__(256) void i3d_maxpool_kernel(I3dPoolArgs a) {
+    const int C4 = a.C >> 2;
+    const long total = (long)a.B * a.To * a.Ho * a.Wo * C4;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const int c4 = (int)(i % C4);
+        long p = i / C4;
+        const int wo = (int)(p % a.Wo); p /= a.Wo;
+        const int ho = (int)(p % a.Ho); p /= a.Ho;
+        const int to = (int)(p % a.To);
+        const int b = (int)(p / a.To);
+        float4 m = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+        for (int dt = 0; dt < a.kT; ++dt) {
+            const int ut = to * a.sT + dt;
+            if (ut >= a.eT) continue;
+            for (int dh = 0; dh < a.kH; ++dh) {
+                const int uh = ho * a.sH + dh;
+                if (uh >= a.eH) continue;
+                for (int dw = 0; dw < a.kW; ++dw) {
+                    const int uw = wo * a.sW + dw;
+                    if (uw >= a.eW) continue;
+                    const int t = ut - a.pT, h = uh - a.pH, w = uw - a.pW;
+                    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if ((unsigned)t < (unsigned)a.Ti && (unsigned)h < (unsigned)a.Hi && (unsigned)w < (unsigned)a.Wi)
+                        v = *reinterpret_cast<const float4*>(a.in + ((((long)b * a.Ti + t) * a.Hi + h) * a.Wi + w) * a.C + 4 * c4);
+                    m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
+                }
+            }
+        }
+        *reinterpret_cast<float4*>(a.out + i * 4) = m;
+    }
+}
+
+// AvgPool3d((2, 7, 7), stride 1) on [B][T][7][7][C] -> [B][T - 1][C]; fixed summation order
+__global__ __launch_bounds__(256) void i3d_avgpool_kernel(const float* __restrict__ in, float* __restrict__ out, int B, int T, int C) {
+    const long total = (long)B * (T - 1) * C;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const int c = (int)(i % C);
+        const int t = (int)((i / C) % (T - 1));
+        const int b = (int)(i / ((long)C * (T - 1)));
+        const float* p = in + (((long)b * T + t) * 49) * C + c;
+        float s = 0.f;
+        for (int j = 0; j < 98; ++j) s += p[(long)j * C];
+        out[i] = s / 98.f;
+    }
+}
+
+// out.mean(2): logits[b][n] = mean over the remaining time steps of x[b][t][n]
+__global__ __launch_bounds__(256) void i3d_time_mean_kernel(const float* __restrict__ x, float* __restrict__ out, int B, int T, int N) {
+    const long total = (long)B * N;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const int n = (int)(i % N);
+        const int b = (int)(i / N);
+        float s = 0.f;
+        for (int t = 0; t < T; ++t) s += x[((long)b * T + t) * N + n];
+        out[i] = s / (float)T;
+    }
+}
+
+// sum[j] += sum_b f[b][j], gram[i][j] += sum_b f[b][i] f[b][j] in float64: one owner per output element, the batch in order
+__global__ __launch_bounds__(256) void fvd_stats_kernel(const float* __restrict__ f, int n, int D, double* __restrict__ sum,
+                                                        double* __restrict__ gram) {
+    const long total = (long)D * D + D;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        if (i < (long)D * D) {
+            const int r = (int)(i / D), c = (int)(i % D);
+            double s = gram[i];
+            for (int b = 0; b < n; ++b) s += (double)f[(long)b * D + r] * (double)f[(long)b * D + c];
+            gram[i] = s;
+        } else {
+            const int c = (int)(i - (long)D * D);
+            double s = sum[c];
+            for (int b = 0; b < n; ++b) s += (double)f[(long)b * D + c];
+            sum[c] = s;
+        }
+    }
+}
+
+unsigned grid_for(long total) { return (unsigned)std::min<long>((total + 255) / 256, 1L << 20); }
+
+// "TF SAME" padding of one dimension (get_padding_shape): `mod` = input size % stride for the TIME dimension of a strided unit
+void same_pad(int k, int s, int mod, int* front, int* back) {
+    const int along = std::max(mod ? k - mod : k - s, 0);
+    *front = along / 2;
+    *back = along - along / 2;
+}
+// MaxPool3d(ceil_mode=True, padding 0) on an extent e
+int pool_out(int e, int k, int s) {
+    int o = (e - k + s - 1) / s + 1;
+    if ((o - 1) * s >= e) --o;
+    return o;
+}
+
+struct Unit {
+    DevBuf w, ss;
+    int Cin = 0, Cout = 0, CoutPad = 0, BN = 64, K = 1, C4 = 0, nchunk = 0;
+    int pack(const StateDict& sd, const std::string& name, int cin, int cout, int k, bool bn, bool bias);
+};
+
+int Unit::pack(const StateDict& sd, const std::string& name, int cin, int cout, int k, bool bn, bool bias) {
+    Cin = cin; Cout = cout; K = k;
+    const int taps = k * k * k;
+    const float* wsrc = sd.f32(name + ".conv3d.weight", (int64_t)cout * cin * taps);
+    if (!wsrc) return I2V_E_MISSING;
+    // column tile: the one that pads Cout least, the wider on a tie
+    int best = 128;
+    for (int bn_ : {64, 32})
+        if ((cout + bn_ - 1) / bn_ * bn_ < (cout + best - 1) / best * best) best = bn_;
+    BN = best;
+    CoutPad = (cout + BN - 1) / BN * BN;
+    const int CinP = (cin + 3) / 4 * 4;
+    C4 = CinP / 4;
+    const long Kp = (long)taps * CinP;
+    nchunk = (int)((Kp + 15) / 16);
+    std::vector<float> p((size_t)nchunk * CoutPad * 16, 0.f);
+    for (int n = 0; n < cout; ++n)
+        for (int c = 0; c < cin; ++c)
+            for (int tap = 0; tap < taps; ++tap) {
+                const long kk = (long)tap * CinP + c;
+                p[((size_t)(kk / 16) * CoutPad + n) * 16 + kk % 16] = wsrc[((size_t)n * cin + c) * taps + tap];
+            }
+    int rc = w.upload(p.data(), p.size() * 4);
+    if (rc) return rc;
+    std::vector<float> s((size_t)CoutPad * 2, 0.f);
+    if (bn) {   // eval-mode BatchNorm3d, eps = 1e-3 (Unit3Dpy: tf_style_eps): (x - mean) / sqrt(var + eps) * weight + bias
+        const float* g = sd.f32(name + ".batch3d.weight", cout);
+        const float* b = sd.f32(name + ".batch3d.bias", cout);
+        const float* m = sd.f32(name + ".batch3d.running_mean", cout);
+        const float* v = sd.f32(name + ".batch3d.running_var", cout);
+        if (!g || !b || !m || !v) return I2V_E_MISSING;
+        for (int n = 0; n < cout; ++n) {
+            const double a = (double)g[n] / std::sqrt((double)v[n] + 1e-3);
+            s[2 * n] = (float)a;
+            s[2 * n + 1] = (float)((double)b[n] - (double)m[n] * a);
+        }
+    } else {
+        const float* b = bias ? sd.f32(name + ".conv3d.bias", cout) : nullptr;
+        if (bias && !b) return I2V_E_MISSING;
+        for (int n = 0; n < cout; ++n) { s[2 * n] = 1.f; s[2 * n + 1] = b ? b[n] : 0.f; }
+    }
+    return ss.upload(s.data(), s.size() * 4);
+}
+
+struct MixedSpec { const char* name; int cin; int o[6]; };
+const MixedSpec MIXED[9] = {
+    {"mixed_3b", 192, {64, 96, 128, 16, 32, 32}},   {"mixed_3c", 256, {128, 128, 192, 32, 96, 64}},
+    {"mixed_4b", 480, {192, 96, 208, 16, 48, 64}},  {"mixed_4c", 512, {160, 112, 224, 24, 64, 64}},
+    {"mixed_4d", 512, {128, 128, 256, 24, 64, 64}}, {"mixed_4e", 512, {112, 144, 288, 32, 64, 64}},
+    {"mixed_4f", 528, {256, 160, 320, 32, 128, 128}}, {"mixed_5b", 832, {256, 160, 320, 32, 128, 128}},
+    {"mixed_5c", 832, {384, 192, 384, 48, 128, 128}}};
+
+struct Dims { int T, H, W; long pos() const { return (long)T * H * W; } };
+
+}  // namespace
+}  // namespace i2v
+
+using namespace i2v;
+
+struct i2v_i3d {
+    int num_classes = 0, in_channels = 3, device = 0;
+    bool loaded = false;
+    Unit stem, c2b, c2c, head;
+    Unit mixed[9][6];   // branch_0, branch_1.0, branch_1.1, branch_2.0, branch_2.1, branch_3.1
+    StreamOrder order;
+};
+
+namespace {
+
+// One walk of the network serves the workspace size (dry: no buffers, no launches) and the forward.
+struct Walk {
+    const i2v_i3d* net;
+    int B;
+    bool dry;
+    hipStream_t st;
+    size_t act_floats = 0, tmp_floats = 0;   // dry: the largest block-level tensor / branch temporary
+
+    int conv(const Unit& u, const float* in, int inCS, int inOff, Dims di, float* out, int outCS, int outOff, Dims dout, int sT, int s,
+             int pT, int pS, bool relu) {
+        if (dry) return I2V_OK;
+        I3dConvArgs a{};
+        a.in = in; a.wp = u.w.as<float>(); a.ss = u.ss.as<float2>(); a.out = out;
+        a.M = (long)B * dout.pos();
+        a.Ti = di.T; a.Hi = di.H; a.Wi = di.W; a.To = dout.T; a.Ho = dout.H; a.Wo = dout.W;
+        a.inCS = inCS; a.inOff = inOff; a.C4 = u.C4; a.G = u.K * u.K * u.K * u.C4; a.nchunk = u.nchunk;
+        a.KH = u.K; a.KW = u.K; a.sT = sT; a.sH = s; a.sW = s; a.pT = pT; a.pH = pS; a.pW = pS;
+        a.Cout = u.Cout; a.CoutPad = u.CoutPad; a.outCS = outCS; a.outOff = outOff; a.relu = relu ? 1 : 0;
+        I2V_REQUIRE(inCS % 4 == 0 && inOff % 4 == 0 && inOff + 4 * u.C4 <= inCS && outOff + u.Cout <= outCS, I2V_E_INVALID,
+                    "i3d conv: channel slice [%d, +%d) of %d -> [%d, +%d) of %d", inOff, 4 * u.C4, inCS, outOff, u.Cout, outCS);
+        const long nblk = (a.M + I3D_BM - 1) / I3D_BM * (u.CoutPad / u.BN);
+        I2V_REQUIRE(nblk > 0 && nblk < (1L << 31), I2V_E_INVALID, "i3d conv: grid of %ld workgroups", nblk);
+        if (u.BN == 128) hipLaunchKernelGGL(i3d_conv_kernel<8>, dim3((unsigned)nblk), dim3(256), 0, st, a);
+        else if (u.BN == 64) hipLaunchKernelGGL(i3d_conv_kernel<4>, dim3((unsigned)nblk), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(i3d_conv_kernel<2>, dim3((unsigned)nblk), dim3(256), 0, st, a);
+        I2V_HIP_CHECK(hipGetLastError());
+        return I2V_OK;
+    }
+
+    // MaxPool3dTFPadding(kernel (kT, k, k), stride (sT, s, s)); returns the output dims
+    int pool(const float* in, float* out, int C, Dims di, int kT, int k, int sT, int s, Dims* dout) {
+        I3dPoolArgs a{};
+        int bT, bS;
+        same_pad(kT, sT, sT > 1 ? di.T % sT : 0, &a.pT, &bT);
+        same_pad(k, s, 0, &a.pH, &bS);
+        a.pW = a.pH;
+        a.eT = a.pT + di.T + bT; a.eH = a.pH + di.H + bS; a.eW = a.pW + di.W + bS;
+        dout->T = pool_out(a.eT, kT, sT); dout->H = pool_out(a.eH, k, s); dout->W = pool_out(a.eW, k, s);
+        if (dry) return I2V_OK;
+        a.in = in; a.out = out; a.B = B; a.Ti = di.T; a.Hi = di.H; a.Wi = di.W; a.To = dout->T; a.Ho = dout->H; a.Wo = dout->W; a.C = C;
+        a.kT = kT; a.kH = k; a.kW = k; a.sT = sT; a.sH = s; a.sW = s;
+        hipLaunchKernelGGL(i3d_maxpool_kernel, dim3(grid_for((long)B * dout->pos() * (C / 4))), dim3(256), 0, st, a);
+        I2V_HIP_CHECK(hipGetLastError());
+        return I2V_OK;
+    }
+
+    void need(size_t* slot, long floats) { *slot = std::max(*slot, (size_t)floats); }
+
+    // frames -> logits.  inp / x / y / tmp / pooled / cls: workspace buffers (null when dry)
+    int run(const float* frames, int T, int H, int W, int denorm, float* inp, float* x, float* y, float* tmp, float* pooled, float* cls,
+            float* logits, int* t_head) {
+        int rc;
+        Dims d{T, I3D_SIDE, I3D_SIDE};
+        if (!dry) {
+            hipLaunchKernelGGL(i3d_input_kernel, dim3(grid_for((long)B * T * I3D_SIDE * I3D_SIDE)), dim3(256), 0, st, frames, inp, (long)B * T, H, W,
+                               denorm);
+            I2V_HIP_CHECK(hipGetLastError());
+        }
+        // conv3d_1a_7x7: stride 2, SAME = (2, 3) per dimension, (3, 3) in time for an odd T
+        int pT, bT;
+        same_pad(7, 2, T % 2, &pT, &bT);
+        Dims o{(T + pT + bT - 7) / 2 + 1, 112, 112};
+        need(&act_floats, (long)B * o.pos() * 64);
+        if ((rc = conv(net->stem, inp, 4, 0, d, x, 64, 0, o, 2, 2, pT, 2, true))) return rc;
+        d = o;
+        if ((rc = pool(x, y, 64, d, 1, 3, 1, 2, &o))) return rc;                              // maxPool3d_2a_3x3
+        d = o;
+        if ((rc = conv(net->c2b, y, 64, 0, d, x, 64, 0, d, 1, 1, 0, 0, true))) return rc;      // conv3d_2b_1x1
+        need(&act_floats, (long)B * d.pos() * 192);
+        if ((rc = conv(net->c2c, x, 64, 0, d, y, 192, 0, d, 1, 1, 1, 1, true))) return rc;     // conv3d_2c_3x3
+        if ((rc = pool(y, x, 192, d, 1, 3, 1, 2, &o))) return rc;                             // maxPool3d_3a_3x3
+        d = o;
+        int C = 192;
+        for (int i = 0; i < 9; ++i) {
+            const MixedSpec& s = MIXED[i];
+            const Unit* u = net->mixed[i];
+            const int Co = s.o[0] + s.o[2] + s.o[4] + s.o[5];
+            need(&act_floats, (long)B * d.pos() * Co);
+            need(&tmp_floats, (long)B * d.pos() * std::max(std::max(s.o[1], s.o[3]), C));
+            // the branches store into their channel slice of y (torch.cat((out_0, out_1, out_2, out_3), 1))
+            if ((rc = conv(u[0], x, C, 0, d, y, Co, 0, d, 1, 1, 0, 0, true))) return rc;
+            if ((rc = conv(u[1], x, C, 0, d, tmp, s.o[1], 0, d, 1, 1, 0, 0, true))) return rc;
+            if ((rc = conv(u[2], tmp, s.o[1], 0, d, y, Co, s.o[0], d, 1, 1, 1, 1, true))) return rc;
+            if ((rc = conv(u[3], x, C, 0, d, tmp, s.o[3], 0, d, 1, 1, 0, 0, true))) return rc;
+            if ((rc = conv(u[4], tmp, s.o[3], 0, d, y, Co, s.o[0] + s.o[2], d, 1, 1, 1, 1, true))) return rc;
+            Dims po;
+            if ((rc = pool(x, tmp, C, d, 3, 3, 1, 1, &po))) return rc;
+            if ((rc = conv(u[5], tmp, C, 0, d, y, Co, s.o[0] + s.o[2] + s.o[4], d, 1, 1, 0, 0, true))) return rc;
+            std::swap(x, y);
+            C = Co;
+            if (i == 1) { if ((rc = pool(x, y, C, d, 3, 3, 2, 2, &o))) return rc; d = o; std::swap(x, y); }   // maxPool3d_4a_3x3
+            if (i == 6) { if ((rc = pool(x, y, C, d, 2, 2, 2, 2, &o))) return rc; d = o; std::swap(x, y); }   // maxPool3d_5a_2x2
+        }
+        I2V_REQUIRE(d.H == 7 && d.W == 7 && d.T >= 2, I2V_E_INVALID,
+                    "i3d: %d frames leave a [%d, %d, %d] map in front of AvgPool3d((2, 7, 7)); at least 9 frames are needed", T, d.T, d.H, d.W);
+        *t_head = d.T - 1;
+        if (dry) return I2V_OK;
+        hipLaunchKernelGGL(i3d_avgpool_kernel, dim3(grid_for((long)B * (d.T - 1) * 1024)), dim3(256), 0, st, x, pooled, B, d.T, 1024);
+        I2V_HIP_CHECK(hipGetLastError());
+        const Dims dh{d.T - 1, 1, 1};
+        if ((rc = conv(net->head, pooled, 1024, 0, dh, cls, net->num_classes, 0, dh, 1, 1, 0, 0, false))) return rc;   // conv3d_0c_1x1
+        hipLaunchKernelGGL(i3d_time_mean_kernel, dim3(grid_for((long)B * net->num_classes)), dim3(256), 0, st, cls, logits, B, d.T - 1,
+                           net->num_classes);
+        I2V_HIP_CHECK(hipGetLastError());
+        return I2V_OK;
+    }
+};
+
+struct I3dWs { size_t inp, x, y, tmp, pooled, cls, total; };
+
+int i3d_ws(const i2v_i3d* net, int B, int T, int H, int W, I3dWs* L) {
+    Walk wk{net, B, true, nullptr};
+    int th = 0;
+    if (int rc = wk.run(nullptr, T, H, W, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &th)) return rc;
+    size_t o = 0;
+    auto take = [&](size_t floats) { size_t r = o; o = align_up(o + floats * 4, 256); return r; };
+    L->inp = take((size_t)B * T * I3D_SIDE * I3D_SIDE * 4);
+    L->x = take(wk.act_floats);
+    L->y = take(wk.act_floats);
+    L->tmp = take(wk.tmp_floats);
+    L->pooled = take((size_t)B * th * 1024);
+    L->cls = take((size_t)B * th * net->num_classes);
+    L->total = o;
+    return I2V_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int i2v_i3d_create(int32_t num_classes, int32_t in_channels, i2v_i3d** out) {
+    I2V_REQUIRE(out && num_classes > 0, I2V_E_INVALID, "i2v_i3d_create: bad argument");
+    I2V_REQUIRE(in_channels == 3, I2V_E_INVALID, "i2v_i3d_create: only the rgb network (3 input channels) is built, got %d", in_channels);
+    int ndev = 0;
+    I2V_HIP_CHECK(hipGetDeviceCount(&ndev));
+    I2V_REQUIRE(ndev > 0, I2V_E_HIP, "i2v_i3d_create: no HIP device");
+    auto n = std::make_unique<i2v_i3d>();
+    n->num_classes = num_classes;
+    n->in_channels = in_channels;
+    I2V_HIP_CHECK(hipGetDevice(&n->device));
+    *out = n.release();
+    return I2V_OK;
+}
+
+void i2v_i3d_destroy(i2v_i3d* n) { delete n; }
+
+int i2v_i3d_load(i2v_i3d* n, const i2v_tensor* tensors, int32_t n_tensors) {
+    if (n) I2V_REQUIRE_DEVICE(n->device, "i2v_i3d_load");
+    I2V_REQUIRE(n && tensors && n_tensors > 0, I2V_E_INVALID, "i2v_i3d_load: null argument");
+    StateDict sd(tensors, n_tensors);
+    int rc;
+    n->loaded = false;
+    if ((rc = n->stem.pack(sd, "conv3d_1a_7x7", n->in_channels, 64, 7, true, false))) return rc;
+    if ((rc = n->c2b.pack(sd, "conv3d_2b_1x1", 64, 64, 1, true, false))) return rc;
+    if ((rc = n->c2c.pack(sd, "conv3d_2c_3x3", 64, 192, 3, true, false))) return rc;
+    for (int i = 0; i < 9; ++i) {
+        const MixedSpec& s = MIXED[i];
+        const std::string p = std::string(s.name) + ".";
+        Unit* u = n->mixed[i];
+        if ((rc = u[0].pack(sd, p + "branch_0", s.cin, s.o[0], 1, true, false))) return rc;
+        if ((rc = u[1].pack(sd, p + "branch_1.0", s.cin, s.o[1], 1, true, false))) return rc;
+        if ((rc = u[2].pack(sd, p + "branch_1.1", s.o[1], s.o[2], 3, true, false))) return rc;
+        if ((rc = u[3].pack(sd, p + "branch_2.0", s.cin, s.o[3], 1, true, false))) return rc;
+        if ((rc = u[4].pack(sd, p + "branch_2.1", s.o[3], s.o[4], 3, true, false))) return rc;
+        if ((rc = u[5].pack(sd, p + "branch_3.1", s.cin, s.o[5], 1, true, false))) return rc;
+    }
+    if ((rc = n->head.pack(sd, "conv3d_0c_1x1", 1024, n->num_classes, 1, false, true))) return rc;
+    n->loaded = true;
+    return I2V_OK;
+}
+
+size_t i2v_i3d_workspace_bytes(const i2v_i3d* n, int32_t batch, int32_t t, int32_t h, int32_t w) {
+    if (!n || batch <= 0 || t <= 0 || h < 2 || w < 2) return 0;
+    I3dWs L;
+    if (i3d_ws(n, batch, t, h, w, &L)) return 0;
+    return L.total;
+}
+
+int i2v_i3d_forward(i2v_i3d* n, const float* frames, int32_t batch, int32_t t, int32_t h, int32_t w, int32_t denorm, float* logits,
+                    void* workspace, size_t workspace_bytes, void* stream) {
+    if (n) I2V_REQUIRE_DEVICE(n->device, "i2v_i3d_forward");
+    I2V_REQUIRE(n && n->loaded, I2V_E_STATE, "i2v_i3d_forward: weights not loaded");
+    I2V_REQUIRE(frames && logits && workspace && batch > 0 && t > 0 && h >= 2 && w >= 2, I2V_E_INVALID, "i2v_i3d_forward: bad argument");
+    I2V_REQUIRE((long)batch * t * I3D_SIDE * I3D_SIDE * 64 < (1L << 40), I2V_E_INVALID, "i2v_i3d_forward: batch %d x %d frames is too large", batch, t);
+    I3dWs L;
+    if (int rc = i3d_ws(n, batch, t, h, w, &L)) return rc;
+    I2V_REQUIRE(workspace_bytes >= L.total, I2V_E_WORKSPACE, "i2v_i3d_forward: workspace %zu < required %zu", workspace_bytes, L.total);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rco = n->order.entry(st)) return rco;
+    StreamOrderMark mark{&n->order, st};
+    char* ws = static_cast<char*>(workspace);
+    auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    Walk wk{n, batch, false, st};
+    int th = 0;
+    return wk.run(frames, t, h, w, denorm ? 1 : 0, F(L.inp), F(L.x), F(L.y), F(L.tmp), F(L.pooled), F(L.cls), logits, &th);
+}
+
+int i2v_i3d_input_stage(const float* frames, int32_t n_frames, int32_t h, int32_t w, int32_t denorm, float* out, void* stream) {
+    I2V_REQUIRE(frames && out && n_frames > 0 && h >= 2 && w >= 2, I2V_E_INVALID, "i2v_i3d_input_stage: bad argument");
+    hipLaunchKernelGGL(i3d_input_kernel, dim3(grid_for((long)n_frames * I3D_SIDE * I3D_SIDE)), dim3(256), 0, static_cast<hipStream_t>(stream), frames,
+                       out, (long)n_frames, h, w, denorm ? 1 : 0);
+    I2V_HIP_CHECK(hipGetLastError());
+    return I2V_OK;
+}
+
+int i2v_fvd_stats_update(const float* feats, int32_t n, int32_t d, double* sum, double* gram, void* stream) {
+    I2V_REQUIRE(feats && sum && gram && n > 0 && d > 0, I2V_E_INVALID, "i2v_fvd_stats_update: bad argument");
+    hipLaunchKernelGGL(fvd_stats_kernel, dim3(grid_for((long)d * d + d)), dim3(256), 0, static_cast<hipStream_t>(stream), feats, n, d, sum, gram);
+    I2V_HIP_CHECK(hipGetLastError());
+    return I2V_OK;
+}
+
+}  // extern "C"

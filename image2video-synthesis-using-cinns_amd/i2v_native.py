@@ -109,6 +109,13 @@ SYMBOLS = {
     "i2v_encoder3d_workspace_bytes": (c_size_t, [c_void_p, c_int32, c_int32, c_int32, c_int32]),
     "i2v_encoder3d_forward": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_size_t, c_int32, c_void_p]),
+    "i2v_i3d_create": (c_int32, [c_int32, c_int32, POINTER(c_void_p)]),
+    "i2v_i3d_destroy": (None, [c_void_p]),
+    "i2v_i3d_load": (c_int32, [c_void_p, POINTER(_Tensor), c_int32]),
+    "i2v_i3d_workspace_bytes": (c_size_t, [c_void_p, c_int32, c_int32, c_int32, c_int32]),
+    "i2v_i3d_forward": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "i2v_i3d_input_stage": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "i2v_fvd_stats_update": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "i2v_dec_create": (c_int32, [POINTER(DecCfg), POINTER(c_void_p)]),
     "i2v_dec_destroy": (None, [c_void_p]),
     "i2v_dec_load": (c_int32, [c_void_p, POINTER(_Tensor), c_int32]),
@@ -1051,3 +1058,66 @@ class NativeEncoder3D(_Handle):
                                            sample.data_ptr() if sample is not None else None, mu.data_ptr(), logvar.data_ptr(),
                                            ws.data_ptr(), ws.numel(), B, _stream()), "i2v_encoder3d_forward")
         return sample, mu, logvar
+
+
+class NativeI3D(_Handle):
+    """Handle for ``i2v_i3d_*`` (the Kinetics-400 I3D of metrics/PyTorch_FVD/I3D.py with FVD_logging.preprocess as its input stage)."""
+
+    def __init__(self, num_classes, in_channels=3, device=None):
+        h = c_void_p()
+        with self._bind(device):
+            _check(lib().i2v_i3d_create(num_classes, in_channels, ctypes.byref(h)), "i2v_i3d_create")
+        self._h = h
+        self.num_classes = num_classes
+        self._ws = _Workspace()
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.i2v_i3d_destroy(self._h)
+            self._h = None
+
+    @_on_device
+    def load(self, state_dict):
+        arr, keep = _pack_state_dict(state_dict)
+        _check(lib().i2v_i3d_load(self._h, arr, len(arr)), "i2v_i3d_load")
+        del keep
+
+    @_on_device
+    def forward(self, frames, denorm):
+        """frames [B, T, 3, H, W] (the decoder's output layout), ``denorm``: the values are in [-1, 1] -> logits [B, num_classes]."""
+        _require_gpu(frames)
+        if frames.dim() != 5 or frames.shape[2] != 3:
+            raise I2VError(f"i3d: expected frames [B,T,3,H,W], got {tuple(frames.shape)}")
+        B, T, _, H, W = frames.shape
+        nbytes = lib().i2v_i3d_workspace_bytes(self._h, B, T, H, W)
+        if nbytes == 0:
+            raise I2VError(f"i3d: no plan for frames {tuple(frames.shape)} (at least 9 frames of at least 2 x 2 pixels are needed)")
+        ws = self._ws.get(nbytes, frames.device)
+        out = torch.empty(B, self.num_classes, dtype=torch.float32, device=frames.device)
+        _check(lib().i2v_i3d_forward(self._h, frames.data_ptr(), B, T, H, W, int(bool(denorm)), out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                     _stream()), "i2v_i3d_forward")
+        return out
+
+
+def fvd_stats_update(feats, total, gram):
+    """``total`` [D] and ``gram`` [D, D] (float64, device) += the rows of ``feats`` [n, D] fp32 (``i2v_fvd_stats_update``): one owner per
+    output element, the rows in order, no atomics."""
+    _require_gpu(feats)
+    n, d = feats.shape
+    for t, shape in ((total, (d,)), (gram, (d, d))):
+        if not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous() or tuple(t.shape) != shape or t.device != feats.device:
+            raise I2VError(f"fvd_stats_update: expected a contiguous float64 device tensor of shape {shape}")
+    with torch.cuda.device(feats.device):
+        _check(lib().i2v_fvd_stats_update(feats.data_ptr(), n, d, total.data_ptr(), gram.data_ptr(), _stream()), "i2v_fvd_stats_update")
+
+
+def i3d_input_stage(frames, denorm):
+    """``i2v_i3d_input_stage``: frames [N, 3, H, W] on the device -> the stem input [N, 224, 224, 4] (channels-last, channel 3 zero)."""
+    _require_gpu(frames)
+    if frames.dim() != 4 or frames.shape[1] != 3:
+        raise I2VError(f"i3d_input_stage: expected frames [N,3,H,W], got {tuple(frames.shape)}")
+    n, _, h, w = frames.shape
+    out = torch.empty(n, 224, 224, 4, dtype=torch.float32, device=frames.device)
+    with torch.cuda.device(frames.device):
+        _check(lib().i2v_i3d_input_stage(frames.data_ptr(), n, h, w, int(bool(denorm)), out.data_ptr(), _stream()), "i2v_i3d_input_stage")
+    return out

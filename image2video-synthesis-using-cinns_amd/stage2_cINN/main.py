@@ -60,9 +60,11 @@ def validator(cINN, encoder, epoch, data_loader, logger, loss_func, opt):
 
 
 def main(opt=None):
-    raise SystemExit("stage2_cINN/main.py: the reference's main() needs its datasets, omegaconf and the FVD networks, none of which "
+    raise SystemExit("stage2_cINN/main.py: the reference's main() needs its datasets and omegaconf, which do not "
                      "ship with this package; build the models (get_model.py), set cINN.differentiable = True and call "
-                     "trainer(...) / validator(...) on your own iterable of {'seq': ...} batches (README: Training the cINN)")
+                     "trainer(...) / validator(...) on your own iterable of {'seq': ...} batches, then "
+                     "utils.auxiliaries.evaluate_FVD_prior(...) with metrics.PyTorch_FVD.FVD_logging.load_model() to pick the "
+                     "checkpoint (README: Training the cINN, Evaluating FVD)")
 
 
 if __name__ == "__main__":

@@ -2,8 +2,9 @@
 loop that the reference's evaluation runs over a data loader.
 
 Own implementations of the reference behaviour (``utils/auxiliaries.py:15-22`` GIF tiling, ``:53-55`` denormalisation,
-``:87-101`` the sampling loop of ``evaluate_FVD_prior``); the FVD networks, wandb logging and video writers that follow
-that loop in the reference are outside the hot path and are not rebuilt."""
+``:87-101`` the sampling loop of ``evaluate_FVD_prior``) and the FVD evaluation hooks ``evaluate_FVD_prior`` /
+``evaluate_FVD_posterior`` on the device (metrics/PyTorch_FVD); the DTFVD network, wandb logging and video writers of the
+reference are not rebuilt."""
 import numpy as np
 import torch
 
@@ -90,6 +91,25 @@ def tile_images(images, nrow=8, padding=2):
     return grid.mul(255).add_(0.5).clamp_(0, 255).permute(1, 2, 0).to(torch.uint8).numpy()
 
 
+def _prior_batches(dloader, cINN, decoder, z_dim, control=False, generator=None):
+    """The loop body shared by ``sample_prior`` and ``evaluate_FVD_prior``: yields (generated [B, 16, 3, H, W], original seq[:, 1:]) of
+    every batch ON THE DEVICE."""
+    for file in dloader:
+        seq = file["seq"].float().cuda()
+        b = seq.size(0)
+        res = torch.randn(b, z_dim, generator=generator).cuda()
+        x_0 = seq[:, 0].contiguous()
+        cond = [x_0, file["cond"]] if control else [x_0]
+        z = cINN(res, cond, reverse=True).view(b, -1)
+        yield decoder(x_0, z), seq[:, 1:]
+
+
+def _check_decoder_range(decoder, who):
+    if hasattr(decoder, "native") and decoder.native().status():   # range guard of the split-fp16 operands (call after a synchronisation)
+        raise RuntimeError(f"{who}: the decoder's activations left the fp16 range of the split-fp16 conv operands "
+                           "(use mma = 0 for this checkpoint)")
+
+
 @torch.no_grad()
 def sample_prior(dloader, cINN, decoder, z_dim, control=False, generator=None):
     """The sampling loop of the reference's ``evaluate_FVD_prior`` (second caller of cINN^-1 + decoder): for every batch
@@ -98,16 +118,46 @@ def sample_prior(dloader, cINN, decoder, z_dim, control=False, generator=None):
     ``(generated [N, 16, 3, H, W], original seq[:, 1:])`` on the CPU.  ``cINN`` is a ``SupervisedTransformer``-like callable
     ``cINN(res, cond, reverse=True)``, ``decoder`` a ``Generator``-like callable ``decoder(x_0, z)``."""
     gen, orig = [], []
+    for g, o in _prior_batches(dloader, cINN, decoder, z_dim, control, generator):
+        gen.append(g.cpu())
+        _check_decoder_range(decoder, "sample_prior")   # (.cpu() synchronised)
+        orig.append(o.cpu())
+    return torch.cat(gen, dim=0), torch.cat(orig, dim=0)
+
+
+def _fvd_accumulator(I3D, mode, who):
+    if mode != 'FVD':
+        raise NotImplementedError(f"{who}: mode {mode!r} -- only 'FVD' (the Kinetics-400 I3D of metrics/PyTorch_FVD) is built; the DTFVD "
+                                  "network (metrics/DTFVD) is not")
+    from metrics.PyTorch_FVD.FVD_logging import FVDAccumulator
+    return FVDAccumulator(I3D)
+
+
+@torch.no_grad()
+def evaluate_FVD_prior(dloader, cINN, decoder, I3D, z_dim, opt, epoch, mode, control):
+    """PFVD, the reference's checkpoint-selection metric (``utils/auxiliaries.py:83-110``, argument list kept): sample one video per start
+    frame of ``dloader`` from the prior (the ``sample_prior`` loop) and return the FVD between the generated clips and ``seq[:, 1:]``.
+
+    No frame goes to the host: every batch is fed to a ``FVDAccumulator`` on the device as it is decoded.  All clips count (the reference's
+    ``calculate_FVD(.., 20)`` drops the ragged last batch of 20).  The reference's side effects -- the GIF of ten random samples
+    (``plot_vid``) and ``wandb.log`` -- are left out; ``opt`` and ``epoch`` only served them and are unused."""
+    acc = _fvd_accumulator(I3D, mode, "evaluate_FVD_prior")
+    for g, o in _prior_batches(dloader, cINN, decoder, z_dim, control):
+        acc.update(g, "gen")
+        acc.update(o, "orig")
+    value = acc.compute()   # (synchronises)
+    _check_decoder_range(decoder, "evaluate_FVD_prior")
+    return value
+
+
+@torch.no_grad()
+def evaluate_FVD_posterior(dloader, model, encoder, I3D, mode):
+    """FVD of the stage-1 reconstructions (``utils/auxiliaries.py:65-81``, argument list kept): ``model(seq[:, 0], encoder(seq[:, 1:])[0])``
+    against ``seq[:, 1:]``, accumulated on the device like ``evaluate_FVD_prior`` (all clips, no host copy of a frame)."""
+    acc = _fvd_accumulator(I3D, mode, "evaluate_FVD_posterior")
     for file in dloader:
         seq = file["seq"].float().cuda()
-        b = seq.size(0)
-        res = torch.randn(b, z_dim, generator=generator).cuda()
-        x_0 = seq[:, 0].contiguous()
-        cond = [x_0, file["cond"]] if control else [x_0]
-        z = cINN(res, cond, reverse=True).view(b, -1)
-        gen.append(decoder(x_0, z).cpu())
-        if hasattr(decoder, "native") and decoder.native().status():   # (.cpu() synchronised) range guard of the split-fp16 operands
-            raise RuntimeError("sample_prior: the decoder's activations left the fp16 range of the split-fp16 conv operands "
-                               "(use mma = 0 for this checkpoint)")
-        orig.append(seq[:, 1:].cpu())
-    return torch.cat(gen, dim=0), torch.cat(orig, dim=0)
+        motion, *_ = encoder(seq[:, 1:].transpose(1, 2))
+        acc.update(model(seq[:, 0].contiguous(), motion), "gen")
+        acc.update(seq[:, 1:], "orig")
+    return acc.compute()

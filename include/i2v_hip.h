@@ -367,6 +367,34 @@ int i2v_embedder_forward(i2v_embedder* e, const float* img, int32_t h, int32_t w
                          size_t workspace_bytes, int32_t batch, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * FVD feature network: the Kinetics-400 I3D -- metrics/PyTorch_FVD/I3D.py (I3D.forward :273-299, Unit3Dpy :48-131,
+ * MaxPool3dTFPadding :134-154, Mixed :157-191) with the host preprocessing of metrics/PyTorch_FVD/FVD_logging.py:190-206
+ * (bilinear align_corners=True resize to 224 x 224, denorm) fused into its input stage.  rgb only (in_channels = 3).
+ * Keys (the reference state_dict as it is): conv3d_1a_7x7.conv3d.weight, ....batch3d.{weight,bias,running_mean,running_var},
+ * conv3d_2b_1x1.*, conv3d_2c_3x3.*, mixed_{3b,3c,4b..4f,5b,5c}.branch_0.*, .branch_1.{0,1}.*, .branch_2.{0,1}.*, .branch_3.1.*,
+ * conv3d_0c_1x1.conv3d.{weight,bias}; num_batches_tracked is ignored.  Eval-mode BatchNorm3d (eps 1e-3) is folded into a
+ * per-channel scale and shift at load.  Exact fp32 matrix cores; there is no reduced-precision mode.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct i2v_i3d i2v_i3d;
+/* I3D.__init__ (I3D.py:194-271) */
+int i2v_i3d_create(int32_t num_classes, int32_t in_channels, i2v_i3d** out);
+void i2v_i3d_destroy(i2v_i3d* n);
+/* Module.load_state_dict of the reference module (FVD_logging.load_model :208-214) */
+int i2v_i3d_load(i2v_i3d* n, const i2v_tensor* tensors, int32_t n_tensors);
+size_t i2v_i3d_workspace_bytes(const i2v_i3d* n, int32_t batch, int32_t t, int32_t h, int32_t w);
+/* FVD_logging.preprocess + I3D.forward: frames [B][t][3][h][w] fp32 (the decoder's output layout), denorm != 0: the values are
+ * in [-1, 1] and are mapped by (x + 1) / 2 after the resize -> logits [B][num_classes] (out_logits; FVD does not use the
+ * softmax).  t >= 9.  Only enqueues on `stream`: no synchronisation, no environment reads. */
+int i2v_i3d_forward(i2v_i3d* n, const float* frames, int32_t batch, int32_t t, int32_t h, int32_t w, int32_t denorm, float* logits,
+                    void* workspace, size_t workspace_bytes, void* stream);
+/* The input stage of i2v_i3d_forward alone (FVD_logging.preprocess :190-206): frames [n_frames][3][h][w] -> channels-last
+ * [n_frames][224][224][4] (channel 3 zero), bilinear align_corners=True, (x + 1) / 2 when denorm != 0.  For tests and inspection. */
+int i2v_i3d_input_stage(const float* frames, int32_t n_frames, int32_t h, int32_t w, int32_t denorm, float* out, void* stream);
+/* Streaming form of FVD_logging.calculate_activation_statistics (:152-174): sum [d] and gram [d][d] (float64, device) +=
+ * the n rows of feats [n][d] fp32.  One owner per output element, the rows in order, no atomics: two runs give the same bits. */
+int i2v_fvd_stats_update(const float* feats, int32_t n, int32_t d, double* sum, double* gram, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Motion encoder of the transfer path (row N3): Encoder.forward -- stage1_VAE/modules/resnet3D.py:138-219
  * (3D ResNet-18, GroupNorm(16), conv_mu / conv_var).  Model.transfer (get_model.py:87) uses mu.
  * Keys: conv1.weight, norm1.*, layer.{L}.{i}.{conv1,conv2}.weight, .bn{1,2}.*, .downsample.{0.weight,1.*},
