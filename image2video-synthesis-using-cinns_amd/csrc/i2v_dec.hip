@@ -18,6 +18,7 @@
 #include <algorithm>
 #include <cmath>
 #include <memory>
+#include <type_traits>
 
 #include "i2v_conv.h"
 
@@ -371,13 +372,12 @@ __global__ __launch_bounds__(256) void modulate_wino_kernel(const float* __restr
 //   V3 = -2 d1 - d2 + 2 d3 + d4   V4 = 2 d1 - d2 - 2 d3 + d4   V5 = 4 d1 - 5 d3 + d5
 // Same thread mapping as modulate_wino_kernel: one thread = one 16-byte piece of the V rows of one (h, tile) column; it
 // evaluates its OWN four positions (d1..d4), gets d0 / d5 from the neighbouring tiles by lane shuffle and loops over the frames.
-// Thread = (h, chunk, tile j, q): the FOUR channels 4q .. 4q+3 of the chunk, hi AND lo parts: per plane it writes two 8-byte
-// half-pieces (hi at byte (q >> 1) * 32 + (q & 1) * 8 of the 64-byte row, lo 16 bytes behind) with two back-to-back store
-// instructions, so that the four lanes of a tile complete the row within a few cycles (round 3 gave a lane 8 channels of the hi
-// OR the lo part: every value was loaded, evaluated and kept twice -- 215 VGPRs and scratch; now every element is loaded and
-// evaluated once).  GB: SPADE's gamma' / beta are present -- every position then has its own affine (a, b)[4], kept in
-// registers over the frame loop; without them (the ADAIN operand of conv_1, SPADE's own activation) all positions share the
-// sample's (ca, cb).
+// Thread = (h, chunk, tile j, q): the FOUR channels 4q .. 4q+3 of the chunk, hi AND lo parts.  (Round 3 gave a lane 8 channels of
+// the hi OR the lo part: every value was loaded, evaluated and kept twice -- 215 VGPRs and scratch; now every element is loaded and
+// evaluated once.)  Per plane the thread holds two 8-byte half-pieces: hi at byte (q >> 1) * 32 + (q & 1) * 8 of the 64-byte row, lo
+// 16 bytes behind.  They leave as ONE 16-byte piece after an exchange with the other lane of the pair: see MOD4_FORM below.
+// GB: SPADE's gamma' / beta are present -- every position then has its own affine (a, b)[4], kept in registers over the frame loop;
+// without them (the ADAIN operand of conv_1, SPADE's own activation) all positions share the sample's (ca, cb).
 typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
 
 template <bool GB>
@@ -400,15 +400,21 @@ __device__ __forceinline__ void mod_pos4_init(ModPos4<GB>& m, const float* ca, c
     }
 }
 
+// the position's four channels of the frame at `toff`, as they lie in memory
 template <bool GB>
-__device__ __forceinline__ void mod_pos4_eval(const ModPos4<GB>& m, const float* ca, const float* cb, long toff, int lrelu, float* d,
-                                              float& vmax) {
+__device__ __forceinline__ float4 mod_pos4_load(const ModPos4<GB>& m, long toff) {
 #ifdef MOD_NT   // measurement build: the writer's reads and writes are pure streams
     typedef float f4v_ __attribute__((ext_vector_type(4)));
     const f4v_ v0 = __builtin_nontemporal_load(reinterpret_cast<const f4v_*>(m.xp + toff));
+    return make_float4(v0.x, v0.y, v0.z, v0.w);
 #else
-    const float4 v0 = *reinterpret_cast<const float4*>(m.xp + toff);
+    return *reinterpret_cast<const float4*>(m.xp + toff);
 #endif
+}
+
+template <bool GB>
+__device__ __forceinline__ void mod_pos4_eval(const ModPos4<GB>& m, const float* ca, const float* cb, const float4 v0, int lrelu, float* d,
+                                              float& vmax) {
     const float r0[4] = {v0.x, v0.y, v0.z, v0.w};
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
@@ -418,16 +424,74 @@ __device__ __forceinline__ void mod_pos4_eval(const ModPos4<GB>& m, const float*
     }
 }
 
+// Plane XQ of B^T d for the thread's four channels: hi = (half)v, lo = (half)(v - (float)hi); bad: |v| > 65504 or not finite.
+template <int XQ>
+__device__ __forceinline__ void mod4_plane(const float* d0, const float* d1, const float* d2, const float* d3, const float* d4,
+                                           const float* d5, half4_t& ph, half4_t& pl, bool& bad) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        float v;
+        if (XQ == 0) v = fmaf(4.f, d0[c], fmaf(-5.f, d2[c], d4[c]));
+        else if (XQ == 1) v = fmaf(-4.f, d1[c] + d2[c], d3[c] + d4[c]);
+        else if (XQ == 2) v = fmaf(4.f, d1[c] - d2[c], d4[c] - d3[c]);
+        else if (XQ == 3) v = fmaf(2.f, d3[c] - d1[c], d4[c] - d2[c]);
+        else if (XQ == 4) v = fmaf(2.f, d1[c] - d3[c], d4[c] - d2[c]);
+        else v = fmaf(4.f, d1[c], fmaf(-5.f, d3[c], d5[c]));
+        // v is rounded to fp32 first, as a value of its own: without this the compiler may merge the last fmaf and the conversion into
+        // one v_fma_mixlo_f16, which rounds once -- another hi part in rare cases (the lo part's difference is exact either way)
+        asm("" : "+v"(v));
+        const _Float16 hh = (_Float16)v;
+        bad |= !(fabsf(v) <= 65504.f);
+        ph[c] = hh;
+        pl[c] = (_Float16)(v - (float)hh);
+    }
+}
+
+// The 8 bytes `mine` of the other lane of the pair (lanes 2k, 2k + 1): DPP quad_perm [1, 0, 3, 2], no LDS.
+__device__ __forceinline__ uint2 mod4_pair_swap(uint2 mine) {
+    return make_uint2((unsigned)__builtin_amdgcn_update_dpp(0, (int)mine.x, 0xB1, 0xF, 0xF, false),
+                      (unsigned)__builtin_amdgcn_update_dpp(0, (int)mine.y, 0xB1, 0xF, 0xF, false));
+}
+
+__device__ __forceinline__ uint2 mod4_bits(half4_t p) { return __builtin_bit_cast(uint2, p); }
+
+// Stores of the writer, FORM bit 0.
+//   0: every lane stores its own 8-byte half-pieces (two per plane in the split form): a wave instruction covers 1 KB with 8-byte
+//      pieces and 8-byte holes.  The form up to round 6.
+//   1: the two lanes of a pair first exchange 8 bytes, then every lane stores one whole 16-byte piece.  Split form: lane q4 stores
+//      piece q4 of the 64-byte row (q4 even: its hi part + the neighbour's, odd: the neighbour's lo part + its own); a wave
+//      instruction writes 1 KB contiguous, 6 instead of 12 stores per lane and frame.  One-term form: the even lane stores the
+//      pair's piece of the planes 0, 2, 4, the odd lane that of the planes 1, 3, 5; 3 instead of 6 stores.
+// Frame loop, FORM bit 1.
+//   1: the float4 loads of the next input frame are requested before the transform and the stores of the current one.
+// The bytes of V do not depend on FORM.  The production library holds form 1.  The measurement build holds 0, 1 and 3
+// (I2V_MOD4_FORM); 3 measured no gain beyond its own noise on the 128 x 128 configs: profiles/writer_stores_ab.md.
+#ifndef MOD4_FORM
+#define MOD4_FORM 1
+#endif
+
+// A 16-byte piece to global memory (MOD_NT, a measurement build: non-temporal, like the 8-byte stores of form 0 there)
+__device__ __forceinline__ void mod4_store16(char* p, uint4 v) {
+#ifdef MOD_NT
+    typedef unsigned u4v_ __attribute__((ext_vector_type(4)));
+    __builtin_nontemporal_store(u4v_{v.x, v.y, v.z, v.w}, reinterpret_cast<u4v_*>(p));
+#else
+    *reinterpret_cast<uint4*>(p) = v;
+#endif
+}
+
 // ONE (mma = 3, the one-term operand of conv_wino4_f16_kernel, i2v_conv16w4h.hip): the same values, rounded to fp16 once -- exactly the
 // hi parts the split writer stores -- into [B][T][CinPad/32][6][H][J][32 channels = 64 B], pieces c0-7 | c16-23 | c8-15 | c24-31 of the
 // 32-channel chunk.  The thread mapping stays that of 16-channel chunks: chunk16 = 2 chunk32 + e writes the 8-byte half-piece
 // (q >> 1) * 32 + e * 16 + (q & 1) * 8 of its row.  C is then CinPad: the chunks at and above the tensor's own channels (Cx) hold zeros.
 // The range guard is the split writer's: bit 0 for |V| > 65504 or non-finite values, the maximum |activation| into the layer's slot.
-template <bool GB, bool ONE = false, bool SH = false>
+template <bool GB, bool ONE = false, bool SH = false, int FORM = MOD4_FORM>
+__attribute__((amdgpu_waves_per_eu(GB ? 3 : 4)))   // registers for 12 (SPADE maps held per position) / 16 waves per CU in every form
 __global__ __launch_bounds__(256) void modulate_wino4_kernel(const float* __restrict__ x, const float2* __restrict__ coef,
                                                              const float* __restrict__ gb, char* __restrict__ out, int T, int H,
                                                              int W, int C, int ut, int us, int lrelu, int* __restrict__ range_flag,
                                                              int* __restrict__ umax, int Cx = 0, int gk = 1, int gr0 = 0) {
+    constexpr bool ST16 = FORM & 1, AHEAD = FORM & 2;
     bool bad = false;
     float vmax = 0.f;
     if constexpr (!ONE) Cx = C;
@@ -481,16 +545,29 @@ __global__ __launch_bounds__(256) void modulate_wino4_kernel(const float* __rest
         float d0[4], d1[4], d2[4], d3[4], d4[4], d5[4], de[4];
         // V row of (t, chunk, plane, h, j): 64 bytes [hi c0-7 | lo c0-7 | hi c8-15 | lo c8-15]; this thread's channels 4 q4 .. 4 q4 + 3
         const int nrow = ONE ? nchunk >> 1 : nchunk, crow = ONE ? chunk >> 1 : chunk;   // chunks of the V rows
-        char* ob = out + ((((long)b * T * nrow + crow) * 6 * H + h) * J + j) * 64 + (q4 >> 1) * 32 + (q4 & 1) * 8 + (ONE ? (chunk & 1) * 16 : 0);
+        const bool odd = q4 & 1;
+        const int piece = !ST16 ? (q4 >> 1) * 32 + (q4 & 1) * 8 + (ONE ? (chunk & 1) * 16 : 0)
+                                : ONE ? (q4 >> 1) * 32 + (chunk & 1) * 16 : q4 * 16;
         const long ostride_x = (long)H * J * 64, ostride_t = (long)nrow * 6 * ostride_x;
+        char* ob = out + ((((long)b * T * nrow + crow) * 6 * H + h) * J + j) * 64 + piece + (ST16 && ONE && odd ? ostride_x : 0);
+        const bool edge = left_own || right_own;
+        float4 r1, r2, r3, r4, re;
+        auto request = [&](long toff) {   // the float4 loads of one input frame
+            r1 = mod_pos4_load<GB>(m1, toff); r2 = mod_pos4_load<GB>(m2, toff); r3 = mod_pos4_load<GB>(m3, toff); r4 = mod_pos4_load<GB>(m4, toff);
+            if (edge) re = mod_pos4_load<GB>(me, toff);
+        };
+        if constexpr (AHEAD) request(0);
         for (int t = 0; t < T; ++t) {
             if (t % ut == 0) {
                 const long toff = (long)(t / ut) * xstride;
-                mod_pos4_eval<GB>(m1, ca, cb, toff, lrelu, d1, vmax);
-                mod_pos4_eval<GB>(m2, ca, cb, toff, lrelu, d2, vmax);
-                mod_pos4_eval<GB>(m3, ca, cb, toff, lrelu, d3, vmax);
-                mod_pos4_eval<GB>(m4, ca, cb, toff, lrelu, d4, vmax);
-                if (left_own || right_own) mod_pos4_eval<GB>(me, ca, cb, toff, lrelu, de, vmax);
+                if constexpr (!AHEAD) request(toff);
+                mod_pos4_eval<GB>(m1, ca, cb, r1, lrelu, d1, vmax);
+                mod_pos4_eval<GB>(m2, ca, cb, r2, lrelu, d2, vmax);
+                mod_pos4_eval<GB>(m3, ca, cb, r3, lrelu, d3, vmax);
+                mod_pos4_eval<GB>(m4, ca, cb, r4, lrelu, d4, vmax);
+                if (edge) mod_pos4_eval<GB>(me, ca, cb, re, lrelu, de, vmax);
+                // the next input frame's requests go out in front of this frame's transform and stores, and stay in flight under them
+                if constexpr (AHEAD) if (t + ut < T) request(toff + xstride);
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
                     const float up = __shfl_up(d4[c], 4), dn = __shfl_down(d1[c], 4);
@@ -499,36 +576,43 @@ __global__ __launch_bounds__(256) void modulate_wino4_kernel(const float* __rest
                 }
             }
             char* o = ob + (long)t * ostride_t;
-#pragma unroll
-            for (int xq = 0; xq < 6; ++xq) {
-                half4_t ph, pl;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    float v;
-                    if (xq == 0) v = fmaf(4.f, d0[c], fmaf(-5.f, d2[c], d4[c]));
-                    else if (xq == 1) v = fmaf(-4.f, d1[c] + d2[c], d3[c] + d4[c]);
-                    else if (xq == 2) v = fmaf(4.f, d1[c] - d2[c], d4[c] - d3[c]);
-                    else if (xq == 3) v = fmaf(2.f, d3[c] - d1[c], d4[c] - d2[c]);
-                    else if (xq == 4) v = fmaf(2.f, d1[c] - d3[c], d4[c] - d2[c]);
-                    else v = fmaf(4.f, d1[c], fmaf(-5.f, d3[c], d5[c]));
-                    const _Float16 hh = (_Float16)v;
-                    bad |= !(fabsf(v) <= 65504.f);
-                    ph[c] = hh;
-                    pl[c] = (_Float16)(v - (float)hh);
-                }
+            auto planes = [&](auto k) {   // the planes 2k and 2k + 1
+                constexpr int X0 = 2 * decltype(k)::value, X1 = X0 + 1;
+                half4_t ph0, pl0, ph1, pl1;
+                mod4_plane<X0>(d0, d1, d2, d3, d4, d5, ph0, pl0, bad);
+                mod4_plane<X1>(d0, d1, d2, d3, d4, d5, ph1, pl1, bad);
                 if constexpr (ONE) {
-                    if (!live) ph = half4_t{0, 0, 0, 0};
-                    *reinterpret_cast<half4_t*>(o + xq * ostride_x) = ph;
-                    continue;
-                }
+                    if (!live) ph0 = ph1 = half4_t{0, 0, 0, 0};
+                    if constexpr (ST16) {   // even lane: plane 2k = its four channels + the odd lane's; odd lane: plane 2k + 1 (ob holds the + 1)
+                        const uint2 h0 = mod4_bits(ph0), h1 = mod4_bits(ph1);
+                        const uint2 got = mod4_pair_swap(odd ? h0 : h1);
+                        mod4_store16(o + X0 * ostride_x, odd ? make_uint4(got.x, got.y, h1.x, h1.y) : make_uint4(h0.x, h0.y, got.x, got.y));
+                    } else {
+                        *reinterpret_cast<half4_t*>(o + X0 * ostride_x) = ph0;
+                        *reinterpret_cast<half4_t*>(o + X1 * ostride_x) = ph1;
+                    }
+                } else if constexpr (ST16) {   // even lane: hi c0-7 (c8-15) = its hi part + the odd lane's; odd lane: lo = the even lane's + its own
+                    const uint2 h0 = mod4_bits(ph0), l0 = mod4_bits(pl0), h1 = mod4_bits(ph1), l1 = mod4_bits(pl1);
+                    const uint2 g0 = mod4_pair_swap(odd ? h0 : l0), g1 = mod4_pair_swap(odd ? h1 : l1);
+                    mod4_store16(o + X0 * ostride_x, odd ? make_uint4(g0.x, g0.y, l0.x, l0.y) : make_uint4(h0.x, h0.y, g0.x, g0.y));
+                    mod4_store16(o + X1 * ostride_x, odd ? make_uint4(g1.x, g1.y, l1.x, l1.y) : make_uint4(h1.x, h1.y, g1.x, g1.y));
+                } else {
 #ifdef MOD_NT
-                __builtin_nontemporal_store(ph, reinterpret_cast<half4_t*>(o + xq * ostride_x));
-                __builtin_nontemporal_store(pl, reinterpret_cast<half4_t*>(o + xq * ostride_x + 16));
+                    __builtin_nontemporal_store(ph0, reinterpret_cast<half4_t*>(o + X0 * ostride_x));
+                    __builtin_nontemporal_store(pl0, reinterpret_cast<half4_t*>(o + X0 * ostride_x + 16));
+                    __builtin_nontemporal_store(ph1, reinterpret_cast<half4_t*>(o + X1 * ostride_x));
+                    __builtin_nontemporal_store(pl1, reinterpret_cast<half4_t*>(o + X1 * ostride_x + 16));
 #else
-                *reinterpret_cast<half4_t*>(o + xq * ostride_x) = ph;
-                *reinterpret_cast<half4_t*>(o + xq * ostride_x + 16) = pl;
+                    *reinterpret_cast<half4_t*>(o + X0 * ostride_x) = ph0;
+                    *reinterpret_cast<half4_t*>(o + X0 * ostride_x + 16) = pl0;
+                    *reinterpret_cast<half4_t*>(o + X1 * ostride_x) = ph1;
+                    *reinterpret_cast<half4_t*>(o + X1 * ostride_x + 16) = pl1;
 #endif
-            }
+                }
+            };
+            planes(std::integral_constant<int, 0>{});
+            planes(std::integral_constant<int, 1>{});
+            planes(std::integral_constant<int, 2>{});
         }
     }
     if (bad && range_flag) atomicOr(range_flag, 1);
@@ -932,6 +1016,11 @@ int run_modulate(const float* x, const float* coef, const float* gb, float* out,
     return I2V_OK;
 }
 
+#ifdef I2V_MEASURE
+static int mod4_last_form = -1;   // the FORM the last writer launch ran: lets a test see that I2V_MOD4_FORM reached the launch
+extern "C" int i2v_measure_mod4_last_form() { return mod4_last_form; }
+#endif
+
 // the F(4,3) operand.  one: the one-term operand (mma = 3) -- C channels of x, written as CinPad = C rounded up to 64 (the kernel's
 // chunks come in pairs)
 int run_modulate_wino4(const float* x, const float* coef, const float* gb, float* out, int B, int T, int H, int W, int C, int ut,
@@ -949,6 +1038,28 @@ int run_modulate_wino4(const float* x, const float* coef, const float* gb, float
         hipLaunchKernelGGL(kernel, dim3(gx, B), dim3(256), 0, st, x, reinterpret_cast<const float2*>(coef), gb, reinterpret_cast<char*>(out),
                            T, H, W, Cp, ut, us, lrelu, range_flag, umax, C, rows.k, rows.r0);
     };
+#ifdef I2V_MEASURE   // (measurement build only: the production library reads no environment variable on a launch path)
+    mod4_last_form = MOD4_FORM;
+    if (const char* e = getenv("I2V_MOD4_FORM")) {   // bit 0: 16-byte stores, bit 1: frame-ahead loads; 0 is the writer up to round 6
+        auto pick = [&](auto form) {
+            constexpr int F = decltype(form)::value;
+            if (!one && sh) launch(modulate_wino4_kernel<true, false, true, F>);
+            else if (!one && gb) launch(modulate_wino4_kernel<true, false, false, F>);
+            else if (!one) launch(modulate_wino4_kernel<false, false, false, F>);
+            else if (sh) launch(modulate_wino4_kernel<true, true, true, F>);
+            else if (gb) launch(modulate_wino4_kernel<true, true, false, F>);
+            else launch(modulate_wino4_kernel<false, true, false, F>);
+        };
+        mod4_last_form = atoi(e) == 0 ? 0 : atoi(e) == 1 ? 1 : 3;
+        switch (atoi(e)) {   // (2, loads ahead of 8-byte stores, is not built: 16 waves per CU leave it no registers)
+        case 0: pick(std::integral_constant<int, 0>{}); break;
+        case 1: pick(std::integral_constant<int, 1>{}); break;
+        default: pick(std::integral_constant<int, 3>{}); break;
+        }
+        I2V_HIP_CHECK(hipGetLastError());
+        return I2V_OK;
+    }
+#endif
     if (!one && sh) launch(modulate_wino4_kernel<true, false, true>);
     else if (!one && gb) launch(modulate_wino4_kernel<true>);
     else if (!one) launch(modulate_wino4_kernel<false>);
