@@ -89,6 +89,13 @@ struct DevBuf {
     }
     template <class T> T* as() const { return static_cast<T*>(p); }
 };
+// the tail of every weight packer: the packed weights into `w`, the fp32 bias [cout] into `bias` (null: released = no bias)
+inline int upload_packed(DevBuf& w, DevBuf& bias, const void* packed, size_t bytes, const float* bias_src, int cout) {
+    if (int rc = w.upload(packed, bytes)) return rc;
+    if (bias_src) return bias.upload(bias_src, (size_t)cout * 4);
+    bias.release();
+    return I2V_OK;
+}
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
@@ -148,6 +155,8 @@ constexpr int I2V_MAX_DEV = 64;
 // 4 KiB of zeros on the current device (allocated once per device, never freed): conv kernels point the loads of padding
 // rows at it instead of selecting zeros AFTER the load -- a select right behind a prefetch load makes the wave wait for it.
 int zero_page(const char** out);
+// compute units of the current device (256 when no device answers)
+int device_cus();
 inline int ensure_dynamic_lds(const void* kernel, int bytes, bool* done) {
     int dev = 0;
     I2V_HIP_CHECK(hipGetDevice(&dev));

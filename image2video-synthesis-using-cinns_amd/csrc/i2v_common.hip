@@ -27,6 +27,18 @@ int zero_page(const char** out) {
     return I2V_OK;
 }
 
+int device_cus() {
+    static int cus[I2V_MAX_DEV] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= I2V_MAX_DEV) return 256;
+    if (!cus[dev]) {
+        int n = 0;
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+        cus[dev] = n;
+    }
+    return cus[dev];
+}
+
 }  // namespace i2v
 
 extern "C" {

@@ -1,6 +1,7 @@
 // Implicit-GEMM convolution on gfx950 matrix cores (shared declarations).
 #pragma once
 #include "i2v_common.h"
+#include "i2v_wino_pack.h"
 
 namespace i2v {
 
@@ -135,40 +136,26 @@ bool wino16_supported(int cout, int cin, int T, int H, int W, int KT = 3);
 int wino16_forward(const Wino16Weights& wts, const void* v_hl16, float* out, const float* res, int rt, int rs, int B, int T,
                    int H, int W, int epi, hipStream_t st, double* stats = nullptr);
 
-// ---- split-fp16 Winograd F(4,3) along W (i2v_conv16w4.hip): 6 GEMMs per 4 output positions (0.75x the MFMAs of F(2,3)).
-// Input: V = B^T d in hl16 format, [B][T][Cin/16][6][H][W/4][16 channels = 64 B] (modulate_wino4_kernel).
+// ---- Winograd F(4,3) along W (i2v_conv16w4.hip): 6 GEMMs per 4 output positions (0.75x the MFMAs of F(2,3)), in two operand forms.
+// split-fp16 (one = false): V = B^T d in hl16 format, [B][T][Cin/16][6][H][W/4][16 channels = 64 B] (modulate_wino4_kernel).
+// one-term fp16 (one = true; decoder mma = 3, kernels in i2v_conv16w4h.hip): the same conv on fp16 operands, one MFMA per product; V
+// rounded to fp16, [B][T][CinPad/32][6][H][W/4][32 channels = 64 B] (modulate_wino4_kernel<GB, ONE>), CinPad = Cin rounded up to 64.
 struct Wino4Weights {
-    DevBuf w;      // U = G g: [parity][tap (kt,kh)][chunk16][6][CoutPad/32][hi | lo][64 lanes][16 B]
+    DevBuf w;      // U = G g: [parity][tap (kt,kh)][chunk16][6][CoutPad/32][hi | lo][64 lanes][16 B]; one: [chunk32] ... [k-step 0 | 1]
     DevBuf bias;
-    int Cin = 0, Cout = 0, CoutPad = 0, nchunk = 0;
-    int KT = 3;    // temporal taps: 3, or 2 for the temporal-duplication pair
-    int wexp = 0;
+    int Cin = 0, CinPad = 0, Cout = 0, CoutPad = 0, nchunk = 0;   // CinPad: Cin (split) or Cin rounded up to 64 (one)
+    int KT = 3;    // temporal taps: 3, 1, or 2 for the temporal-duplication pair
+    int wexp = 0;  // U is packed as U 2^wexp; the epilogue multiplies by 2^-wexp
     bool tdup = false;
+    bool one = false;
     long set_bytes = 0;
-    int pack(const float* w_src, const float* bias_src, int cout, int cin, double scale, int kt = 3);   // w_src [Cout][Cin][kt][3][3], kt = 3 or 1
-    int pack_tdup(const float* w_src, const float* bias_src, int cout, int cin, double scale);  // from a 3x3x3 kernel
+    int pack(const float* w_src, const float* bias_src, int cout, int cin, double scale, int kt = 3, bool one = false);   // w_src [Cout][Cin][kt][3][3], kt = 3 or 1 (split only)
+    int pack_tdup(const float* w_src, const float* bias_src, int cout, int cin, double scale, bool one = false);  // from a 3x3x3 kernel
 };
 // T = frames of the tensor V was built from (half the output frames for pack_tdup weights); false = use another kernel
-bool wino4_supported(int cout, int cin, int T, int H, int W, int KT);
-int wino4_forward(const Wino4Weights& wts, const void* v_hl16, float* out, const float* res, int rt, int rs, int B, int T,
+bool wino4_supported(int cout, int cin, int T, int H, int W, int KT, bool one = false);
+int wino4_forward(const Wino4Weights& wts, const void* v16, float* out, const float* res, int rt, int rs, int B, int T,
                   int H, int W, int epi, hipStream_t st, double* stats = nullptr);
-
-// ---- one-term fp16 Winograd F(4,3) (i2v_conv16w4h.hip, decoder mma = 3): the same conv on fp16 operands, one MFMA per product.
-// Input: V rounded to fp16, [B][T][CinPad/32][6][H][W/4][32 channels = 64 B] (modulate_wino4h_kernel), CinPad = Cin rounded up to 64.
-struct Wino4hWeights {
-    DevBuf w;      // U = G g in fp16: [parity][tap (kt,kh)][chunk32][6][CoutPad/32][k-step 0 | 1][64 lanes][16 B]
-    DevBuf bias;
-    int Cin = 0, CinPad = 0, Cout = 0, CoutPad = 0, nchunk = 0;
-    int KT = 3;    // temporal taps: 3, or 2 for the temporal-duplication pair
-    int wexp = 0;  // U is packed as U 2^wexp (the split packer's prescale); the epilogue multiplies by 2^-wexp
-    bool tdup = false;
-    long set_bytes = 0;
-    int pack(const float* w_src, const float* bias_src, int cout, int cin, double scale);        // w_src [Cout][Cin][3][3][3]
-    int pack_tdup(const float* w_src, const float* bias_src, int cout, int cin, double scale);   // from a 3x3x3 kernel
-};
-bool wino4h_supported(int cout, int cin, int T, int H, int W, int KT);
-int wino4h_forward(const Wino4hWeights& wts, const void* v16, float* out, const float* res, int rt, int rs, int B, int T,
-                   int H, int W, int epi, hipStream_t st, double* stats = nullptr);
 
 // The same conv with the operand GENERATED in the kernel (conv_wino4g_f16x3_kernel: 8 MFMA waves + 4 producer waves per workgroup):
 // x = the conv's fp32 input BEFORE normalisation / activation, channels-last [B][T][H / us][W / us][Cin]; coef = per-(b,c) (A, B)

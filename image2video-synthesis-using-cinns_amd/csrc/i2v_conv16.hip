@@ -514,84 +514,26 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, WAVES_M * WAVES_N / 4) void
     }
 }
 
+static_assert(CONV16_KC == C16_KC, "the packer's chunk is the kernel's");
+
+// w: [nset][Cout][Cin][ntaps], unscaled (conv16_pack_sets); the sets share one power-of-two prescale
+static int conv16_store(Conv16Weights& o, const std::vector<double>& w, int nset, const float* bias_src, int cout, int cin, int kt, int kh, int kw,
+                        double scale) {
+    const PackedHalfs p = conv16_pack_sets(w, nset, cout, cin, kt * kh * kw, scale);
+    o.Cin = cin; o.Cout = cout; o.KT = kt; o.KH = kh; o.KW = kw;
+    o.CoutPad = p.CoutPad; o.nchunk = p.nchunk; o.wexp = p.wexp;
+    if (nset == 2) { o.tdup = true; o.set_bytes = p.set_bytes; }
+    return upload_packed(o.w, o.bias, p.halfs.data(), p.bytes(), bias_src, cout);
+}
+
 int Conv16Weights::pack(const float* w_src, const float* bias_src, int cout, int cin, int kt, int kh, int kw, double scale) {
-    Cin = cin; Cout = cout; KT = kt; KH = kh; KW = kw;
-    CoutPad = (cout + 31) / 32 * 32;
-    if (CoutPad > 64 && CoutPad % 128) CoutPad = (CoutPad + 127) / 128 * 128;
-    nchunk = (cin + C16_KC - 1) / C16_KC;
-    const int ntaps = kt * kh * kw;
-    // power-of-two pre-scale: largest |w| lands in [2^13, 2^14) so every lo part of a non-negligible weight is a normal
-    // fp16 number (full 2^-22 split precision) and hi stays far from the fp16 overflow threshold
-    double wmax = 0.0;
-    for (size_t i = 0; i < (size_t)cout * cin * ntaps; ++i) wmax = std::max(wmax, std::fabs((double)w_src[i] * scale));
-    wexp = 0;
-    if (wmax > 0.0 && std::isfinite(wmax)) {
-        wexp = (int)std::floor(std::log2(16384.0 / wmax));
-        wexp = std::max(-40, std::min(40, wexp));
-    }
-    const double pre = std::ldexp(1.0, wexp);
-    std::vector<_Float16> p((size_t)(ntaps + 1) * nchunk * CoutPad * 64, (_Float16)0.f);  // + one all-zero tap
-    for (int n = 0; n < cout; ++n)
-        for (int c = 0; c < cin; ++c)
-            for (int tap = 0; tap < ntaps; ++tap) {
-                const float v = (float)((double)w_src[((size_t)n * cin + c) * ntaps + tap] * scale * pre);
-                const _Float16 hi = (_Float16)v;
-                const _Float16 lo = (_Float16)(v - (float)hi);
-                const int chunk = c / C16_KC, g = (c % C16_KC) / 8, j = c % 8;
-                _Float16* row = &p[(((size_t)tap * nchunk + chunk) * CoutPad + n) * 64];
-                row[g * 16 + j] = hi;
-                row[g * 16 + 8 + j] = lo;
-            }
-    int rc = w.upload(p.data(), p.size() * 2);
-    if (rc) return rc;
-    if (bias_src) return bias.upload(bias_src, (size_t)cout * 4);
-    bias.release();
-    return I2V_OK;
+    return conv16_store(*this, std::vector<double>(w_src, w_src + (size_t)cout * cin * kt * kh * kw), 1, bias_src, cout, cin, kt, kh, kw, scale);
 }
 
 int Conv16Weights::pack_tdup(const float* w_src, const float* bias_src, int cout, int cin, double scale) {
-    // two 2x3x3 kernels from one 3x3x3 kernel: parity 0 = (W[0], W[1]+W[2]), parity 1 = (W[0]+W[1], W[2]) along time
-    std::vector<float> w2((size_t)2 * cout * cin * 18);
-    for (int par = 0; par < 2; ++par)
-        for (size_t nc = 0; nc < (size_t)cout * cin; ++nc)
-            for (int hw = 0; hw < 9; ++hw) {
-                const double w0 = w_src[nc * 27 + hw], w1 = w_src[nc * 27 + 9 + hw], w2v = w_src[nc * 27 + 18 + hw];
-                float* dst = &w2[((size_t)par * cout * cin + nc) * 18];
-                dst[hw] = (float)(par == 0 ? w0 : w0 + w1);
-                dst[9 + hw] = (float)(par == 0 ? w1 + w2v : w2v);
-            }
-    // both sets share one power-of-two pre-scale: pack them as one [2*cout] tensor, then split the buffer
-    Conv16Weights tmp;
-    Cin = cin; Cout = cout; KT = 2; KH = 3; KW = 3; tdup = true;
-    CoutPad = (cout + 31) / 32 * 32;
-    if (CoutPad > 64 && CoutPad % 128) CoutPad = (CoutPad + 127) / 128 * 128;
-    nchunk = (cin + C16_KC - 1) / C16_KC;
-    const int ntaps = 18;
-    double wmax = 0.0;
-    for (float v : w2) wmax = std::max(wmax, std::fabs((double)v * scale));
-    wexp = 0;
-    if (wmax > 0.0 && std::isfinite(wmax)) wexp = std::max(-40, std::min(40, (int)std::floor(std::log2(16384.0 / wmax))));
-    const double pre = std::ldexp(1.0, wexp);
-    const size_t set_halfs = (size_t)(ntaps + 1) * nchunk * CoutPad * 64;
-    std::vector<_Float16> p(2 * set_halfs, (_Float16)0.f);
-    for (int par = 0; par < 2; ++par)
-        for (int n = 0; n < cout; ++n)
-            for (int c = 0; c < cin; ++c)
-                for (int tap = 0; tap < ntaps; ++tap) {
-                    const float v = (float)((double)w2[(((size_t)par * cout + n) * cin + c) * 18 + tap] * scale * pre);
-                    const _Float16 hi = (_Float16)v;
-                    const _Float16 lo = (_Float16)(v - (float)hi);
-                    const int chunk = c / C16_KC, g = (c % C16_KC) / 8, j = c % 8;
-                    _Float16* row = &p[par * set_halfs + (((size_t)tap * nchunk + chunk) * CoutPad + n) * 64];
-                    row[g * 16 + j] = hi;
-                    row[g * 16 + 8 + j] = lo;
-                }
-    set_bytes = (long)set_halfs * 2;
-    int rc = w.upload(p.data(), p.size() * 2);
-    if (rc) return rc;
-    if (bias_src) return bias.upload(bias_src, (size_t)cout * 4);
-    bias.release();
-    return I2V_OK;
+    std::vector<double> w2 = tdup_pair_sums(w_src, cout, cin);
+    for (double& v : w2) v = (double)(float)v;   // (this packer rounds the pair sums to fp32 before it scales them; the Winograd ones do not)
+    return conv16_store(*this, w2, 2, bias_src, cout, cin, 2, 3, 3, scale);
 }
 
 // measurement builds (-DC16_TUNE) can switch the clipped staging off (I2V_C16_CLIP=0) for same-box A/Bs; the production build cannot

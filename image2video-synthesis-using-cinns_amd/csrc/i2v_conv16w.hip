@@ -497,43 +497,6 @@ __global__ __launch_bounds__(512, 2) void conv_wino_f16x3_kernel(WinoArgs a) {
 
 // ---- host side ------------------------------------------------------------------------------------------------------
 
-// w3: [nset][Cout][Cin][KT][3][3] already multiplied by `scale`-free fp64 pre-sums; packs U = G g per (kt, kh).
-static int wino_pack_sets(Wino16Weights& o, const std::vector<double>& w3, int nset, int cout, int cin, int kt) {
-    o.Cin = cin; o.Cout = cout; o.KT = kt;
-    o.CoutPad = (cout + 31) / 32 * 32;
-    o.nchunk = cin / W16_KC;
-    const int NT = kt * 3;
-    std::vector<double> u((size_t)nset * cout * cin * NT * 4);
-    double wmax = 0.0;
-    for (size_t i = 0; i < (size_t)nset * cout * cin * NT; ++i) {
-        const double g0 = w3[i * 3], g1 = w3[i * 3 + 1], g2 = w3[i * 3 + 2];
-        double* d = &u[i * 4];
-        d[0] = g0; d[1] = 0.5 * (g0 + g1 + g2); d[2] = 0.5 * (g0 - g1 + g2); d[3] = g2;
-        for (int x = 0; x < 4; ++x) wmax = std::max(wmax, std::fabs(d[x]));
-    }
-    o.wexp = 0;
-    if (wmax > 0.0 && std::isfinite(wmax)) o.wexp = std::max(-40, std::min(40, (int)std::floor(std::log2(16384.0 / wmax))));
-    const double pre = std::ldexp(1.0, o.wexp);
-    const size_t set_halfs = (size_t)NT * o.nchunk * 4 * o.CoutPad * 32;
-    std::vector<_Float16> p((size_t)nset * set_halfs, (_Float16)0.f);
-    for (int s = 0; s < nset; ++s)
-        for (int n = 0; n < cout; ++n)
-            for (int c = 0; c < cin; ++c)
-                for (int tap = 0; tap < NT; ++tap)
-                    for (int x = 0; x < 4; ++x) {
-                        const float v = (float)(u[((((size_t)s * cout + n) * cin + c) * NT + tap) * 4 + x] * pre);
-                        const _Float16 hi = (_Float16)v;
-                        const _Float16 lo = (_Float16)(v - (float)hi);
-                        // fragment-major: [tap][chunk][x][32-channel block][hi | lo][lane = kg * 32 + n % 32][8 halfs]
-                        const int chunk = c / W16_KC, kgq = (c % W16_KC) / 8, j = c % 8;
-                        _Float16* blk = &p[s * set_halfs + ((((size_t)tap * o.nchunk + chunk) * 4 + x) * (o.CoutPad / 32) + n / 32) * 1024];
-                        blk[(kgq * 32 + n % 32) * 8 + j] = hi;
-                        blk[512 + (kgq * 32 + n % 32) * 8 + j] = lo;
-                    }
-    o.set_bytes = (long)set_halfs * 2;
-    return o.w.upload(p.data(), p.size() * 2);
-}
-
 // Brick of 128 Winograd tiles = TT frames x TH rows x TJ = 4 output pairs (the only brick width every shipped and tested
 // shape uses: an MFMA row block is then 8 consecutive rows of one frame).  False when [T, H, W] with a KT-tap temporal
 // kernel cannot be tiled that way or its halo brick does not fit the staged rows -- the caller then runs the direct kernel.
@@ -555,35 +518,21 @@ bool wino16_supported(int cout, int cin, int T, int H, int W, int KT) {
     return wino16_tiling(T, H, W, KT, &TT, &TH, &TJ);
 }
 
+static_assert(WINO_F23.kc == W16_KC, "the packer's chunk is the kernel's");
+
+static int wino16_store(Wino16Weights& o, const PackedHalfs& p, const float* bias_src, int cout, int cin, int kt, bool tdup) {
+    o.Cin = cin; o.Cout = cout; o.KT = kt; o.tdup = tdup;
+    o.CoutPad = p.CoutPad; o.nchunk = p.nchunk; o.wexp = p.wexp; o.set_bytes = p.set_bytes;
+    return upload_packed(o.w, o.bias, p.halfs.data(), p.bytes(), bias_src, cout);
+}
+
 int Wino16Weights::pack(const float* w_src, const float* bias_src, int cout, int cin, int kt, double scale) {
     I2V_REQUIRE(kt == 3 || kt == 1, I2V_E_INVALID, "wino16: temporal kernel size %d", kt);
-    tdup = false;
-    std::vector<double> w3((size_t)cout * cin * kt * 9);
-    for (size_t i = 0; i < w3.size(); ++i) w3[i] = (double)w_src[i] * scale;
-    int rc = wino_pack_sets(*this, w3, 1, cout, cin, kt);
-    if (rc) return rc;
-    if (bias_src) return bias.upload(bias_src, (size_t)cout * 4);
-    bias.release();
-    return I2V_OK;
+    return wino16_store(*this, wino_pack(WINO_F23, w_src, cout, cin, scale, kt, false), bias_src, cout, cin, kt, false);
 }
 
 int Wino16Weights::pack_tdup(const float* w_src, const float* bias_src, int cout, int cin, double scale) {
-    // parity 0 = (W[0], W[1]+W[2]), parity 1 = (W[0]+W[1], W[2]) along time (see Conv16Weights::pack_tdup)
-    std::vector<double> w3((size_t)2 * cout * cin * 18);
-    for (int par = 0; par < 2; ++par)
-        for (size_t nc = 0; nc < (size_t)cout * cin; ++nc)
-            for (int hw = 0; hw < 9; ++hw) {
-                const double w0 = w_src[nc * 27 + hw], w1 = w_src[nc * 27 + 9 + hw], w2 = w_src[nc * 27 + 18 + hw];
-                double* dst = &w3[((size_t)par * cout * cin + nc) * 18];
-                dst[hw] = (par == 0 ? w0 : w0 + w1) * scale;
-                dst[9 + hw] = (par == 0 ? w1 + w2 : w2) * scale;
-            }
-    tdup = true;
-    int rc = wino_pack_sets(*this, w3, 2, cout, cin, 2);
-    if (rc) return rc;
-    if (bias_src) return bias.upload(bias_src, (size_t)cout * 4);
-    bias.release();
-    return I2V_OK;
+    return wino16_store(*this, wino_pack(WINO_F23, w_src, cout, cin, scale, 3, true), bias_src, cout, cin, 2, true);
 }
 
 template <int NT, int BN>

@@ -41,114 +41,28 @@ namespace i2v {
 
 // ---- host side ------------------------------------------------------------------------------------------------------
 
-// w3: [nset][Cout][Cin][NT][3] (fp64, already scaled); packs U = G g per (kt, kh)
-static int wino4_pack_sets(Wino4Weights& o, const std::vector<double>& w3, int nset, int cout, int cin, int kt) {
-    o.Cin = cin; o.Cout = cout; o.KT = kt;
-    o.CoutPad = (cout + 31) / 32 * 32;
-    o.nchunk = cin / W4_KC;
-    const int NT = kt * 3;
-    std::vector<double> u((size_t)nset * cout * cin * NT * 6);
-    double wmax = 0.0;
-    for (size_t i = 0; i < (size_t)nset * cout * cin * NT; ++i) {
-        const double g0 = w3[i * 3], g1 = w3[i * 3 + 1], g2 = w3[i * 3 + 2];
-        double* d = &u[i * 6];
-        d[0] = g0 / 4.0;
-        d[1] = -(g0 + g1 + g2) / 6.0;
-        d[2] = -(g0 - g1 + g2) / 6.0;
-        d[3] = g0 / 24.0 + g1 / 12.0 + g2 / 6.0;
-        d[4] = g0 / 24.0 - g1 / 12.0 + g2 / 6.0;
-        d[5] = g2;
-        for (int x = 0; x < 6; ++x) wmax = std::max(wmax, std::fabs(d[x]));
-    }
-    o.wexp = 0;
-    if (wmax > 0.0 && std::isfinite(wmax)) o.wexp = std::max(-40, std::min(40, (int)std::floor(std::log2(16384.0 / wmax))));
-    const double pre = std::ldexp(1.0, o.wexp);
-    const size_t set_halfs = (size_t)NT * o.nchunk * 6 * o.CoutPad * 32;
-    std::vector<_Float16> p((size_t)nset * set_halfs, (_Float16)0.f);
-    for (int s = 0; s < nset; ++s)
-        for (int n = 0; n < cout; ++n)
-            for (int c = 0; c < cin; ++c)
-                for (int tap = 0; tap < NT; ++tap)
-                    for (int x = 0; x < 6; ++x) {
-                        const float v = (float)(u[((((size_t)s * cout + n) * cin + c) * NT + tap) * 6 + x] * pre);
-                        const _Float16 hi = (_Float16)v;
-                        const _Float16 lo = (_Float16)(v - (float)hi);
-                        // fragment-major: [tap][chunk][x][32-channel block][hi | lo][lane = kg * 32 + n % 32][8 halfs]
-                        const int chunk = c / W4_KC, kgq = (c % W4_KC) / 8, j = c % 8;
-                        _Float16* blk = &p[s * set_halfs + ((((size_t)tap * o.nchunk + chunk) * 6 + x) * (o.CoutPad / 32) + n / 32) * 1024];
-                        blk[(kgq * 32 + n % 32) * 8 + j] = hi;
-                        blk[512 + (kgq * 32 + n % 32) * 8 + j] = lo;
-                    }
-    o.set_bytes = (long)set_halfs * 2;
-    return o.w.upload(p.data(), p.size() * 2);
-}
+static_assert(WINO_F43.kc == W4_KC && WINO_F43_ONE.kc == 2 * W4_KC, "the packer's chunks are the kernels'");
 
-bool wino4_supported(int cout, int cin, int T, int H, int W, int KT) {
-    if (cout % 32 || cin % (2 * W4_KC) || (KT != 3 && KT != 2 && KT != 1)) return false;
+// one: the one-term form (cin % 32 like the split form's chunk pairs -- its packer pads to 64 --, no 1x3x3 variant)
+bool wino4_supported(int cout, int cin, int T, int H, int W, int KT, bool one) {
+    if (cout % 32 || cin % (2 * W4_KC) || (KT != 3 && KT != 2 && (KT != 1 || one))) return false;
     int TT, TH;
     return wino4_tiling(T, H, W, KT, &TT, &TH);
 }
 
-int Wino4Weights::pack(const float* w_src, const float* bias_src, int cout, int cin, double scale, int kt) {
-    I2V_REQUIRE(kt == 3 || kt == 1, I2V_E_INVALID, "wino4: temporal kernel size %d", kt);
-    tdup = false;
-    std::vector<double> w3((size_t)cout * cin * kt * 9);
-    for (size_t i = 0; i < w3.size(); ++i) w3[i] = (double)w_src[i] * scale;
-    int rc = wino4_pack_sets(*this, w3, 1, cout, cin, kt);
-    if (rc) return rc;
-    if (bias_src) return bias.upload(bias_src, (size_t)cout * 4);
-    bias.release();
-    return I2V_OK;
+static int wino4_store(Wino4Weights& o, const PackedHalfs& p, const float* bias_src, int cout, int cin, int kt, bool tdup, bool one) {
+    o.Cin = cin; o.Cout = cout; o.KT = kt; o.tdup = tdup; o.one = one;
+    o.CinPad = p.CinPad; o.CoutPad = p.CoutPad; o.nchunk = p.nchunk; o.wexp = p.wexp; o.set_bytes = p.set_bytes;
+    return upload_packed(o.w, o.bias, p.halfs.data(), p.bytes(), bias_src, cout);
 }
 
-int Wino4Weights::pack_tdup(const float* w_src, const float* bias_src, int cout, int cin, double scale) {
-    // parity 0 = (W[0], W[1]+W[2]), parity 1 = (W[0]+W[1], W[2]) along time (see Conv16Weights::pack_tdup)
-    std::vector<double> w3((size_t)2 * cout * cin * 18);
-    for (int par = 0; par < 2; ++par)
-        for (size_t nc = 0; nc < (size_t)cout * cin; ++nc)
-            for (int hw = 0; hw < 9; ++hw) {
-                const double w0 = w_src[nc * 27 + hw], w1 = w_src[nc * 27 + 9 + hw], w2 = w_src[nc * 27 + 18 + hw];
-                double* dst = &w3[((size_t)par * cout * cin + nc) * 18];
-                dst[hw] = (par == 0 ? w0 : w0 + w1) * scale;
-                dst[9 + hw] = (par == 0 ? w1 + w2 : w2) * scale;
-            }
-    tdup = true;
-    int rc = wino4_pack_sets(*this, w3, 2, cout, cin, 2);
-    if (rc) return rc;
-    if (bias_src) return bias.upload(bias_src, (size_t)cout * 4);
-    bias.release();
-    return I2V_OK;
+int Wino4Weights::pack(const float* w_src, const float* bias_src, int cout, int cin, double scale, int kt, bool one_) {
+    I2V_REQUIRE(kt == 3 || (kt == 1 && !one_), I2V_E_INVALID, "%s: temporal kernel size %d", one_ ? "wino4h" : "wino4", kt);
+    return wino4_store(*this, wino_pack(one_ ? WINO_F43_ONE : WINO_F43, w_src, cout, cin, scale, kt, false), bias_src, cout, cin, kt, false, one_);
 }
 
-template <int NT, int BN, int PIPE, int NTH = 512>
-static int launch_wino4_(const W4Args& a, unsigned grid, size_t lds, hipStream_t st) {
-    auto kern = conv_wino4_f16x3_kernel<NT, BN, PIPE, NTH>;
-    static bool attr_set[I2V_MAX_DEV] = {};
-    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), 160 * 1024, attr_set)) return rc;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NTH), lds, st, a);
-    I2V_HIP_CHECK(hipGetLastError());
-    return I2V_OK;
-}
-
-// compute units of the current device (one persistent workgroup each)
-static int device_cus() {
-    static int cus[I2V_MAX_DEV] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= I2V_MAX_DEV) return 256;
-    if (!cus[dev]) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        cus[dev] = n;
-    }
-    return cus[dev];
-}
-
-// the 32-channel kernel as two 256-thread workgroups per CU (W4Geo<256>): 2 V regions of 576 rows + one table set = 79 616 bytes
-template <int NT>
-static int launch_wino4_thin(W4Args& a, unsigned nblk, hipStream_t st) {
-    a.nvirt = (int)(a.tdup ? 2 * nblk : nblk);
-    a.tofs = 2 * W4Geo<256>::ROWS_A * 64;
-    return launch_wino4_<NT, 32, 0, 256>(a, (unsigned)a.nvirt, (size_t)a.tofs + (size_t)w4_table_bytes<256>(), st);
+int Wino4Weights::pack_tdup(const float* w_src, const float* bias_src, int cout, int cin, double scale, bool one_) {
+    return wino4_store(*this, wino_pack(one_ ? WINO_F43_ONE : WINO_F43, w_src, cout, cin, scale, 3, true), bias_src, cout, cin, 2, true, one_);
 }
 
 // Measurement switches of this kernel.  The PRODUCTION library (no -DI2V_MEASURE) reads no environment variable on a launch path
@@ -157,15 +71,14 @@ static int launch_wino4_thin(W4Args& a, unsigned nblk, hipStream_t st) {
 // the brick -> XCD order (I2V_W4_ORDER) and the launch trace (I2V_W4_TRACE) -- exist in the measurement build only
 // (tools/build_measurement_libs.sh measure -> tools/_tl/libi2v_hip_measure.so, loaded through I2V_LIB_PATH; tools/conv16w_check*
 // are built with the flag too), where they are read per launch so that tests and A/B runs can flip them inside one process.
+// The one-term form has no switches: it always runs the defaults.
 // 32-channel 3x3x3 layers with the V requests issued by four extra waves (i2v_conv16w4g.hip, MODE 2; I2V_W4_LOADER=1 in the measurement
 // build).  Measured neutral to negative (profiles/r06_e_thin_loader_ab.txt: 32 -> 32 0.380 vs 0.384 ms, 64 -> 32 0.561 vs 0.545 ms at B = 8;
 // 1.33 vs 1.31-1.33 and 2.05 vs 1.93-1.97 ms at B = 32): what the thin layers' tap loops gain without ANY operand traffic (-21 % / -34 %) is
 // not the issue cost of the requests but the traffic itself -- 92 KB of V per chunk into an LDS that the operand reads already keep
-// 65 % busy.  Off.
-constexpr int W4_DEFAULT_LOADER = 0;
-struct W4Switches { int pipe, bn, order, nth, skew, trace, loader; };
+// 65 % busy.  Off (W4_DEFAULT_LOADER).
 static W4Switches w4_switches() {
-    W4Switches w{W4_DEFAULT_PIPE, 0, W4_DEFAULT_ORDER, 0, 0, 0, W4_DEFAULT_LOADER};
+    W4Switches w{};
 #ifdef I2V_MEASURE
     if (const char* e = getenv("I2V_W4_PIPE")) w.pipe = atoi(e);
     if (const char* e = getenv("I2V_W4_BN")) w.bn = atoi(e);
@@ -178,120 +91,153 @@ static W4Switches w4_switches() {
     return w;
 }
 
-template <int NT, int BN>
-static int launch_wino4(W4Args& a, unsigned nblk, hipStream_t st, int env_pipe) {
-    a.nvirt = (int)(a.tdup ? 2 * nblk : nblk);
-    const int body = 2 * W4_ROWS_A * 64;   // two V regions (pass B and the epilogue's exchange buffer reuse them)
-    a.tofs = body;
-#if defined(I2V_MEASURE) && !defined(W4_TAPTIME)
-    if (env_pipe != 0) {
-        // one workgroup per CU, a multiple of 8 so that a virtual workgroup keeps its XCD
-        int grid = std::min(a.nvirt, device_cus());
-        if (grid >= 8) grid &= ~7;
-        const size_t lds = (size_t)body + 2 * (size_t)W4_TABLE_BYTES;
-        if (env_pipe == 2) return launch_wino4_<NT, BN, 2>(a, (unsigned)grid, lds, st);
-        return launch_wino4_<NT, BN, 1>(a, (unsigned)grid, lds, st);
-    }
-#else
-    (void)env_pipe;
-#endif
-#ifdef W4_TAPTIME
-    const size_t lds = 160 * 1024;
-#else
-    const size_t lds = (size_t)body + (size_t)W4_TABLE_BYTES;
-#endif
-    return launch_wino4_<NT, BN, 0>(a, (unsigned)a.nvirt, lds, st);
-}
-
-int wino4_forward(const Wino4Weights& wts, const void* v_hl16, float* out, const float* res, int rt, int rs, int B, int T, int H,
-                  int W, int epi, hipStream_t st, double* stats) {
-    I2V_REQUIRE(wts.w.p, I2V_E_STATE, "wino4: weights not packed");
-    I2V_REQUIRE((epi & ~EPI_LRELU) == 0, I2V_E_INVALID, "wino4: unsupported epilogue %d", epi);
-    W4Args a{};
-    if (int rc0 = zero_page(&a.zeros)) return rc0;
-    a.in = static_cast<const char*>(v_hl16); a.wp = wts.w.as<char>(); a.bias = wts.bias.as<float>(); a.res = res; a.out = out;
-    a.stats = stats;
+// The launch plan of every F(4,3) kernel.  Neither the tile width, the brick shape nor the workgroup size enters the accumulation order
+// of an output: the choices below change the speed, never the bits.
+int wino4_plan(W4Plan* p, const Wino4Weights& wts, int B, int T, int H, int W, bool has_res, int rt, int rs, int epi, bool has_stats, int cus,
+               const W4Switches& sw, bool gen) {
+    const char* nm = gen ? "wino4g" : wts.one ? "wino4h" : "wino4";
+    const int KT = wts.KT;
+    I2V_REQUIRE((epi & ~EPI_LRELU) == 0, I2V_E_INVALID, "%s: unsupported epilogue %d", nm, epi);
+    *p = W4Plan{};
+    W4Args& a = p->a;
     a.B = B; a.H = H; a.W = W; a.J = W / 4; a.Cin = wts.Cin; a.Cout = wts.Cout; a.CoutPad = wts.CoutPad; a.nchunk = wts.nchunk;
     a.tdup = wts.tdup ? 1 : 0;
     a.wset_stride = wts.set_bytes;
     if (wts.tdup) {  // T is the OUTPUT frame count; the half-rate input has T / 2 frames
-        I2V_REQUIRE(T % 2 == 0 && !res, I2V_E_INVALID, "wino4: temporal-duplication mode needs an even frame count and no residual");
+        I2V_REQUIRE(T % 2 == 0 && !has_res, I2V_E_INVALID, "%s: temporal-duplication mode needs an even frame count and no residual", nm);
         T /= 2;
     }
     a.T = T;
-    I2V_REQUIRE(wino4_supported(wts.Cout, wts.Cin, T, H, W, wts.KT), I2V_E_INVALID, "wino4: unsupported shape [%d,%d,%d] %d -> %d (kt = %d)",
-                T, H, W, wts.Cin, wts.Cout, wts.KT);
-    a.rt = res ? rt : 1; a.rs = res ? rs : 1; a.epi = epi;
+    I2V_REQUIRE(wino4_supported(wts.Cout, wts.Cin, T, H, W, KT, wts.one), I2V_E_INVALID, "%s: unsupported shape [%d,%d,%d] %d -> %d (kt = %d)", nm,
+                T, H, W, wts.Cin, wts.Cout, KT);
+    a.rt = has_res ? rt : 1; a.rs = has_res ? rs : 1; a.epi = epi;
     I2V_REQUIRE((a.rt == 1 || a.rt == 2 || a.rt == 4) && (a.rs == 1 || a.rs == 2 || a.rs == 4), I2V_E_INVALID,
-                "wino4: residual up-sampling factors %d / %d (1, 2 or 4)", a.rt, a.rs);
+                "%s: residual up-sampling factors %d / %d (1, 2 or 4)", nm, a.rt, a.rs);
     a.rt_shift = a.rt >> 1 == 2 ? 2 : a.rt >> 1; a.rs_shift = a.rs >> 1 == 2 ? 2 : a.rs >> 1;
     a.oscale = (float)std::ldexp(1.0, -wts.wexp);
     int TT = 1, TH = 1;
-    (void)wino4_tiling(T, H, W, wts.KT, &TT, &TH);
-    int BN = a.CoutPad % 64 == 0 ? 64 : 32;  // output channels per workgroup
-    const W4Switches sw = w4_switches();      // (defaults unless built with -DI2V_MEASURE)
-    const int env_bn = sw.bn, env_order = sw.order, env_nth = sw.nth;
-    // 64-channel workgroups that would leave CUs idle (16x16 maps at small batches) become twice as many 32-channel ones: the
-    // accumulation order of every output does not depend on the tile width, so the bits are the same
-    if (BN == 64 && wts.KT != 1 && (long)B * (T / TT) * (H / TH) * (a.J / 4) * (a.CoutPad / 64) * (wts.tdup ? 2 : 1) < device_cus()) BN = 32;
-    if (env_bn == 32 && wts.KT != 1) BN = 32;
-    if (env_bn == 64 && a.CoutPad % 64 == 0) BN = 64;
-    // 32-channel layers: two 256-thread workgroups of 64 tiles per CU instead of one 512-thread workgroup of 128 (W4Geo; same
-    // bits: neither the brick shape nor the workgroup size enters the accumulation order of an output).  I2V_W4_NTH=512 restores
-    // round 4's geometry for A/B runs.
+    (void)wino4_tiling(T, H, W, KT, &TT, &TH);
+    int BN = a.CoutPad % 64 == 0 && !gen ? 64 : 32;  // output channels per workgroup
+#ifdef W4_TAPTIME   // (the per-tap timing build carries the 512-thread one-workgroup-per-brick kernels only)
+    const int pipe = 0;
+    const bool thin_ok = false;
+#else
+    const int pipe = sw.pipe;
+    const bool thin_ok = !gen;
+#endif
+    // 64-channel workgroups that would leave CUs idle (16x16 maps at small batches) become twice as many 32-channel ones
+    if (BN == 64 && KT != 1 && (long)B * (T / TT) * (H / TH) * (a.J / 4) * (a.CoutPad / 64) * (wts.tdup ? 2 : 1) < cus) BN = 32;
+    if (sw.bn == 32 && KT != 1) BN = 32;
+    if (sw.bn == 64 && a.CoutPad % 64 == 0 && !gen) BN = 64;
+    p->form = gen ? W4_GEN : wts.one ? W4_ONE : pipe == 0 ? W4_SPLIT : pipe == 2 ? W4_PERSIST2 : W4_PERSIST1;
     // 32-channel 3x3x3 layers whose map tiles into the 512-thread brick: the loader form (12 waves: the tap loops issue no V request)
-    if (sw.loader && BN == 32 && a.CoutPad == 32 && wts.KT == 3 && !wts.tdup && sw.pipe == 0 && env_nth == 0 && TT == 4 && TH == 8) {
-        a.TT = TT; a.TH = TH; a.TJ = 4; a.nbT = T / TT; a.nbH = H / TH; a.nbJ = a.J / 4;
-        a.th_shift = 3;
-        a.hh_magic = ((1 << 20) + TH + 1) / (TH + 2);
-        a.order = env_order;
-        const long nb = (long)B * a.nbT * a.nbH * a.nbJ;
-        if (wino4_loader_supported(a, wts.KT) && nb > 0 && nb < (1L << 30) && (long)T * a.nchunk * 6 * H * a.J * 64 < (1L << 31) &&
-            (long)B * T * H * W < (1L << 31) && (!stats || (long)TT * TH * 4 <= (long)T * H * a.J))
-            return wino4_loader_launch(a, (unsigned)nb, st, sw.loader);
-    }
+    if (p->form == W4_SPLIT && sw.loader && BN == 32 && a.CoutPad == 32 && KT == 3 && !wts.tdup && sw.nth == 0 && TT == 4 && TH == 8)
+        p->form = sw.loader == 2 ? W4_LOADER2 : W4_LOADER1;
+    // 32-channel layers: two 256-thread workgroups of 64 tiles per CU instead of one 512-thread workgroup of 128 (W4Geo).
+    // Default: only the layers that HAVE 32 output channels (g_4 of the 128 x 128 configs: +3 % on 32 -> 32, +-0 on 64 -> 32,
+    // profiles/r05_c_*); 64-channel layers narrowed for a small grid keep the 512-thread geometry (-2 % at B = 8 with 256).
+    // I2V_W4_NTH=256 forces the 256-thread geometry wherever the brick fits, 512 forbids it (round 4's geometry, for A/B runs).
     bool thin = false;
-    {
-        int TT2 = 1, TH2 = 1;
-        // Default: only the layers that HAVE 32 output channels (g_4 of the 128 x 128 configs: +3 % on 32 -> 32, +-0 on 64 -> 32,
-        // profiles/r05_c_*); 64-channel layers narrowed for a small grid keep the 512-thread geometry (-2 % at B = 8 with 256).
-        // I2V_W4_NTH=256 forces the 256-thread geometry wherever the brick fits, 512 forbids it.
-        if (BN == 32 && wts.KT != 1 && env_nth != 512 && (a.CoutPad % 64 != 0 || env_nth == 256) && sw.pipe == 0 &&
-            wino4_tiling(T, H, W, wts.KT, &TT2, &TH2, W4Geo<256>::TILES, W4Geo<256>::ROWS_A, W4Geo<256>::ROWS_B)) {
-            thin = true; TT = TT2; TH = TH2;
-        }
-    }
+    if (thin_ok && (p->form == W4_SPLIT || p->form == W4_ONE) && BN == 32 && KT != 1 && sw.nth != 512 && (a.CoutPad % 64 != 0 || sw.nth == 256))
+        thin = wino4_tiling(T, H, W, KT, &TT, &TH, W4Geo<256>::TILES, W4Geo<256>::ROWS_A, W4Geo<256>::ROWS_B);
+    I2V_REQUIRE(BN == 64 || KT != 1, I2V_E_INVALID, "%s: the 1x3x3 variant exists for 64-channel tiles only", nm);
     a.TT = TT; a.TH = TH; a.TJ = 4; a.nbT = T / TT; a.nbH = H / TH; a.nbJ = a.J / 4;
     a.th_shift = 0;
     while ((1 << a.th_shift) < TH) ++a.th_shift;
-    I2V_REQUIRE((1 << a.th_shift) == TH, I2V_E_INVALID, "wino4: brick height %d is not a power of two", TH);
+    I2V_REQUIRE((1 << a.th_shift) == TH, I2V_E_INVALID, "%s: brick height %d is not a power of two", nm, TH);
     a.hh_magic = ((1 << 20) + TH + 1) / (TH + 2);
-    I2V_REQUIRE(!stats || (long)TT * TH * 4 <= (long)T * H * a.J, I2V_E_INVALID, "wino4: fused statistics need bricks inside one sample");
-    a.order = env_order;
+    I2V_REQUIRE(!has_stats || (long)TT * TH * 4 <= (long)T * H * a.J, I2V_E_INVALID, "%s: fused statistics need bricks inside one sample", nm);
+    a.order = sw.order;
     a.skew = sw.skew;
     const long nblk = (long)B * a.nbT * a.nbH * a.nbJ * (a.CoutPad / BN);
-    I2V_REQUIRE(nblk > 0 && nblk < (1L << 30), I2V_E_INVALID, "wino4: grid of %ld workgroups", nblk);
+    I2V_REQUIRE(nblk > 0 && nblk < (1L << 30), I2V_E_INVALID, "%s: grid of %ld workgroups", nm, nblk);
     // the kernel's index tables (gpos: V rows, tpos / tres: output and residual positions) are 32-bit
-    I2V_REQUIRE((long)T * a.nchunk * 6 * H * a.J * 64 < (1L << 31), I2V_E_INVALID, "wino4: the V operand of one sample ([%d,%d,%d] x %d chunks) exceeds the 2 GB a buffer descriptor offset can address", T, H, W, a.nchunk);
-    I2V_REQUIRE((long)B * T * a.nchunk * 6 * H * a.J < (1L << 31) && (long)B * (wts.tdup ? 2 * T : T) * H * W < (1L << 31), I2V_E_INVALID,
-                "wino4: batch %d too large for the 32-bit row indices of this kernel ([%d,%d,%d] x %d chunks)", B, T, H, W, a.nchunk);
+    if (!gen) {   // (the generating kernel reads no V tensor)
+        I2V_REQUIRE((long)T * a.nchunk * 6 * H * a.J * 64 < (1L << 31), I2V_E_INVALID, "%s: the V operand of one sample ([%d,%d,%d] x %d chunks) exceeds the 2 GB a buffer descriptor offset can address", nm, T, H, W, a.nchunk);
+        I2V_REQUIRE((long)B * T * a.nchunk * 6 * H * a.J < (1L << 31), I2V_E_INVALID,
+                    "%s: batch %d too large for the 32-bit row indices of this kernel ([%d,%d,%d] x %d chunks)", nm, B, T, H, W, a.nchunk);
+    }
+    I2V_REQUIRE((long)B * (wts.tdup ? 2 * T : T) * H * W < (1L << 31), I2V_E_INVALID,
+                "%s: batch %d too large for the 32-bit row indices of this kernel ([%d,%d,%d] x %d chunks)", nm, B, T, H, W, a.nchunk);
+    a.nvirt = (int)(a.tdup ? 2 * nblk : nblk);   // virtual workgroups = bricks x channel tiles x frame parities
+    p->NT = 3 * KT; p->BN = BN; p->NTH = thin ? 256 : 512; p->PIPE = 0;
+    p->grid = (unsigned)a.nvirt;
+    a.tofs = 2 * W4_ROWS_A * 64;   // two V regions (pass B and the epilogue's exchange buffer reuse them), the index tables behind
+    p->lds_bytes = (size_t)a.tofs + (size_t)W4_TABLE_BYTES;
+    if (thin) {   // two workgroups per CU: 2 V regions of 576 rows + one table set = 79 616 bytes
+        a.tofs = 2 * W4Geo<256>::ROWS_A * 64;
+        p->lds_bytes = (size_t)a.tofs + (size_t)w4_table_bytes<256>();
+    } else if (p->form == W4_PERSIST1 || p->form == W4_PERSIST2) {
+        // one workgroup per CU, a multiple of 8 so that a virtual workgroup keeps its XCD; two table sets
+        p->PIPE = p->form == W4_PERSIST2 ? 2 : 1;
+        int grid = std::min(a.nvirt, cus);
+        if (grid >= 8) grid &= ~7;
+        p->grid = (unsigned)grid;
+        p->lds_bytes += (size_t)W4_TABLE_BYTES;
+    } else if (p->form == W4_GEN || p->form == W4_LOADER1 || p->form == W4_LOADER2) {   // 12 waves; no V row tables (tpos / tres only)
+        p->NTH = W4G_THREADS;
+        p->lds_bytes = (size_t)a.tofs + 5 * W4Geo<512>::TILES * 4;
+    }
+#ifdef W4_TAPTIME
+    if (p->form == W4_SPLIT) p->lds_bytes = 160 * 1024;   // + the per-tap timing slots
+#endif
+    return I2V_OK;
+}
+
+// -DW4_HOST_ONLY (tests/wino_host_check.hip: the packers' bytes and the plans) and the host-side self-test below link this file
+// without the other two translation units and instantiate no kernel
+#if !defined(W4_HOST_ONLY) && !defined(W4_DECODE_SELFTEST)
+template <int NT, int BN, int PIPE, int NTH = 512>
+static int launch_wino4_(const W4Plan& p, hipStream_t st) {
+    auto kern = conv_wino4_f16x3_kernel<NT, BN, PIPE, NTH>;
+    static bool attr_set[I2V_MAX_DEV] = {};
+    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), 160 * 1024, attr_set)) return rc;
+    hipLaunchKernelGGL(kern, dim3(p.grid), dim3(NTH), p.lds_bytes, st, p.a);
+    I2V_HIP_CHECK(hipGetLastError());
+    return I2V_OK;
+}
+
+static int wino4_launch(const W4Plan& p, hipStream_t st) {
+    if (p.form == W4_ONE) return wino4h_launch(p, st);
+    if (p.form == W4_LOADER1 || p.form == W4_LOADER2) return wino4_loader_launch(p, st);
+    // (the order of the cases is the order in which the kernels are instantiated and emitted: keep it, the code object stays the same)
+#define W4_CASE(NT, BN, NTH, PIPE) case w4_key(NT, BN, NTH, PIPE): return launch_wino4_<NT, BN, PIPE, NTH>(p, st);
+#if defined(I2V_MEASURE) && !defined(W4_TAPTIME)   // + the persistent forms
+#define W4_CASES(NT, BN) W4_CASE(NT, BN, 512, 2) W4_CASE(NT, BN, 512, 1) W4_CASE(NT, BN, 512, 0)
+#else
+#define W4_CASES(NT, BN) W4_CASE(NT, BN, 512, 0)
+#endif
+    switch (w4_key(p.NT, p.BN, p.NTH, p.PIPE)) {
+        W4_CASES(9, 64) W4_CASES(6, 64) W4_CASES(3, 64)   // (3 taps: one time slice, SPADE's 2-D convs)
+#ifndef W4_TAPTIME
+        W4_CASE(9, 32, 256, 0) W4_CASE(6, 32, 256, 0)
+#endif
+        W4_CASES(9, 32) W4_CASES(6, 32)
+    }
+#undef W4_CASES
+#undef W4_CASE
+    set_error("wino4: no kernel <%d taps, %d channels, %d threads, pipe %d> in this build", p.NT, p.BN, p.NTH, p.PIPE);
+    return I2V_E_INVALID;
+}
+
+int wino4_forward(const Wino4Weights& wts, const void* v16, float* out, const float* res, int rt, int rs, int B, int T, int H,
+                  int W, int epi, hipStream_t st, double* stats) {
+    I2V_REQUIRE(wts.w.p, I2V_E_STATE, "%s: weights not packed", wts.one ? "wino4h" : "wino4");
+    const W4Switches sw = wts.one ? W4Switches{} : w4_switches();      // (defaults unless built with -DI2V_MEASURE)
+    W4Plan p;
+    if (int rc = wino4_plan(&p, wts, B, T, H, W, res != nullptr, rt, rs, epi, stats != nullptr, device_cus(), sw)) return rc;
+    W4Args& a = p.a;
+    if (int rc = zero_page(&a.zeros)) return rc;
+    a.in = static_cast<const char*>(v16); a.wp = wts.w.as<char>(); a.bias = wts.bias.as<float>(); a.res = res; a.out = out;
+    a.stats = stats;
     if (sw.trace) {
-        fprintf(stderr, "wino4: B %d T %d H %d W %d Cin %d Cout %d pad %d KT %d tdup %d TT %d TH %d res %p rt %d rs %d stats %p epi %d nblk %ld\n", B, T, H, W,
-                a.Cin, a.Cout, a.CoutPad, wts.KT, a.tdup, TT, TH, (const void*)res, a.rt, a.rs, (void*)stats, epi, nblk);
+        fprintf(stderr, "wino4: B %d T %d H %d W %d Cin %d Cout %d pad %d KT %d tdup %d TT %d TH %d res %p rt %d rs %d stats %p epi %d nvirt %d form %d\n", B, a.T, H, W,
+                a.Cin, a.Cout, a.CoutPad, wts.KT, a.tdup, a.TT, a.TH, (const void*)res, a.rt, a.rs, (void*)stats, epi, a.nvirt, (int)p.form);
         (void)hipDeviceSynchronize();
     }
-    if (BN == 64) {
-        if (wts.KT == 3) return launch_wino4<9, 64>(a, (unsigned)nblk, st, sw.pipe);
-        if (wts.KT == 2) return launch_wino4<6, 64>(a, (unsigned)nblk, st, sw.pipe);
-        return launch_wino4<3, 64>(a, (unsigned)nblk, st, sw.pipe);   // one time slice: SPADE's 2-D convs
-    }
-    I2V_REQUIRE(wts.KT != 1, I2V_E_INVALID, "wino4: the 1x3x3 variant exists for 64-channel tiles only");
-#ifndef W4_TAPTIME
-    if (thin) return wts.KT == 3 ? launch_wino4_thin<9>(a, (unsigned)nblk, st) : launch_wino4_thin<6>(a, (unsigned)nblk, st);
-#endif
-    if (wts.KT == 3) return launch_wino4<9, 32>(a, (unsigned)nblk, st, sw.pipe);
-    return launch_wino4<6, 32>(a, (unsigned)nblk, st, sw.pipe);
+    return wino4_launch(p, st);
 }
+#endif
 
 #ifdef W4_TAPTIME
 void w4_taptime_report() {

@@ -1,6 +1,7 @@
 // Device side of the Winograd F(4,3) split-fp16 convolution (see i2v_conv16w4.hip for the design): argument blocks, the tap-loop
 // pass (w4_pass), the brick decode, the index tables and the kernel template -- shared by i2v_conv16w4.hip (the kernels that read
-// the operand V a producer launch wrote) and i2v_conv16w4g.hip (the kernel that generates it in its own producer waves).
+// the operand V a producer launch wrote), i2v_conv16w4h.hip (their one-term fp16 form) and i2v_conv16w4g.hip (the kernel that
+// generates it in its own producer waves); at the end the host-side launch plan (wino4_plan) all three are launched from.
 // A translation unit that defines W4_NO_INSTRUMENT before including this file gets no measurement hooks (timeline stamps,
 // per-tap timing): their device-side buffers live in i2v_conv16w4.hip only.
 #pragma once
@@ -593,8 +594,29 @@ inline bool wino4_tiling(int T, int H, int W, int KT, int* TT_, int* TH_, int ti
 }
 
 
-// the LOADER form of the 32-channel 3x3x3 kernel (i2v_conv16w4g.hip): four extra waves issue the V requests
-bool wino4_loader_supported(const W4Args& a, int KT);
-int wino4_loader_launch(W4Args& a, unsigned nblk, hipStream_t st, int form = 1);
+// ---- the launch plan (i2v_conv16w4.hip): every host-side decision about a launch of one of the F(4,3) kernels, made once
+// Measurement switches (see w4_switches in i2v_conv16w4.hip: the production library always runs the defaults)
+constexpr int W4_DEFAULT_LOADER = 0;
+struct W4Switches { int pipe = W4_DEFAULT_PIPE, bn = 0, order = W4_DEFAULT_ORDER, nth = 0, skew = 0, trace = 0, loader = W4_DEFAULT_LOADER; };
+// Which kernel runs the plan: the split / one-term kernels with one workgroup per brick (i2v_conv16w4.hip / i2v_conv16w4h.hip), the
+// split kernel's persistent forms (I2V_W4_PIPE = 1 / 2), the loader forms and the operand-generating kernel (i2v_conv16w4g.hip)
+enum W4Form : int { W4_SPLIT, W4_ONE, W4_PERSIST1, W4_PERSIST2, W4_LOADER1, W4_LOADER2, W4_GEN };
+struct W4Plan {
+    W4Args a;             // everything but the pointers in / zeros / res / out / stats, which the caller sets
+    int NT, BN, NTH, PIPE;   // the kernel instantiation: (kt, kh) taps, channels and threads per workgroup, persistent form
+    W4Form form;
+    unsigned grid;
+    size_t lds_bytes;
+};
+// T = OUTPUT frames.  cus: compute units of the device.  gen: the plan of the operand-generating kernel (fixed 4 x 8 brick, 32
+// channels per workgroup, no V tensor: wino4g_forward has checked its own preconditions).  Returns an error code and sets the error.
+int wino4_plan(W4Plan* p, const Wino4Weights& wts, int B, int T, int H, int W, bool has_res, int rt, int rs, int epi, bool has_stats, int cus,
+               const W4Switches& sw, bool gen = false);
+// what the other two translation units export: the launch of a plan on their kernels
+int wino4h_launch(const W4Plan& p, hipStream_t st);          // form W4_ONE
+int wino4_loader_launch(const W4Plan& p, hipStream_t st);    // forms W4_LOADER1 / W4_LOADER2
+// key of the one switch over instantiations each translation unit has
+constexpr int w4_key(int NT, int BN, int NTH, int PIPE = 0) { return ((NT * 128 + BN) * 1024 + NTH) * 4 + PIPE; }
+constexpr int W4G_THREADS = 768;   // the 12-wave workgroup of i2v_conv16w4g.hip
 
 }  // namespace i2v

@@ -33,7 +33,7 @@ struct W4GenArgs {
     int gk, gr0;         // MODE 4 (SPADE, realizations): sample b reads the map row (gr0 + b) / gk -- gk samples share a start frame
 };
 
-constexpr int W4G_THREADS = 768, W4G_PROD = 256;
+constexpr int W4G_PROD = 256;   // (W4G_THREADS = 768: i2v_conv16w4_dev.h)
 constexpr int W4G_TT = 4, W4G_TH = 8, W4G_HT = W4G_TT + 2, W4G_HH = W4G_TH + 2;   // brick of the 512-thread geometry, 3 temporal taps
 constexpr int W4G_PLANE = W4G_HT * W4G_HH * 4;                                     // 240 V rows per plane
 constexpr int W4G_SLOTS = (W4G_HT / 2) * W4G_HH * 4 * 4;                           // (frame pair, halo row, tile, channel quad) = 480
@@ -562,37 +562,21 @@ bool wino4g_supported(int cout, int cin, int T, int H, int W, int us) {
 
 int wino4g_forward(const Wino4Weights& wts, const float* x, const float* coef, const float* gb, int us, float* out, const float* res, int rt, int rs,
                    int B, int T, int H, int W, int epi, hipStream_t st, double* stats, int* range_flag, int* umax, GbRows rows) {
-    I2V_REQUIRE(wts.w.p && !wts.tdup && wts.KT == 3, I2V_E_STATE, "wino4g: needs 3x3x3 weights packed for the F(4,3) kernel");
-    I2V_REQUIRE((epi & ~EPI_LRELU) == 0, I2V_E_INVALID, "wino4g: unsupported epilogue %d", epi);
+    I2V_REQUIRE(wts.w.p && !wts.tdup && !wts.one && wts.KT == 3, I2V_E_STATE, "wino4g: needs 3x3x3 weights packed for the F(4,3) kernel");
     I2V_REQUIRE(x && coef && wino4g_supported(wts.Cout, wts.Cin, T, H, W, us) && (gb != nullptr) == (us == 2), I2V_E_INVALID,
                 "wino4g: unsupported shape [%d,%d,%d] %d -> %d (us = %d, gb %p)", T, H, W, wts.Cin, wts.Cout, us, (const void*)gb);
-    W4Args a{};
-    a.in = nullptr; a.zeros = nullptr; a.wp = wts.w.as<char>(); a.bias = wts.bias.as<float>(); a.res = res; a.out = out;
-    a.stats = stats;
-    a.B = B; a.T = T; a.H = H; a.W = W; a.J = W / 4; a.Cin = wts.Cin; a.Cout = wts.Cout; a.CoutPad = wts.CoutPad; a.nchunk = wts.nchunk;
-    a.tdup = 0;
-    a.wset_stride = wts.set_bytes;
-    a.rt = res ? rt : 1; a.rs = res ? rs : 1; a.epi = epi;
-    I2V_REQUIRE((a.rt == 1 || a.rt == 2 || a.rt == 4) && (a.rs == 1 || a.rs == 2 || a.rs == 4), I2V_E_INVALID,
-                "wino4g: residual up-sampling factors %d / %d (1, 2 or 4)", a.rt, a.rs);
-    a.rt_shift = a.rt >> 1 == 2 ? 2 : a.rt >> 1; a.rs_shift = a.rs >> 1 == 2 ? 2 : a.rs >> 1;
-    a.oscale = (float)std::ldexp(1.0, -wts.wexp);
-    a.TT = W4G_TT; a.TH = W4G_TH; a.TJ = 4; a.nbT = T / a.TT; a.nbH = H / a.TH; a.nbJ = a.J / 4;
-    a.th_shift = 3;
-    a.hh_magic = ((1 << 20) + a.TH + 1) / (a.TH + 2);
-    a.order = W4_DEFAULT_ORDER;
-    const long nblk = (long)B * a.nbT * a.nbH * a.nbJ * (a.CoutPad / 32);
-    I2V_REQUIRE(nblk > 0 && nblk < (1L << 30), I2V_E_INVALID, "wino4g: grid of %ld workgroups", nblk);
+    // the producer waves' offsets into the fp32 input and SPADE's maps are 32-bit
     I2V_REQUIRE((long)T * H * W * wts.Cin < (1L << 31) && (long)H * W * 2 * wts.Cin < (1L << 31) && (long)B * T * H * W < (1L << 31), I2V_E_INVALID,
                 "wino4g: tensor too large for the 32-bit offsets of this kernel");
-    a.nvirt = (int)nblk;
-    a.tofs = 2 * W4_ROWS_A * 64;
+    W4Plan p;   // (wino4g_supported: the brick is the 4 x 8 one of the 512-thread geometry; no measurement switches)
+    if (int rc = wino4_plan(&p, wts, B, T, H, W, res != nullptr, rt, rs, epi, stats != nullptr, device_cus(), W4Switches{}, true)) return rc;
+    W4Args& a = p.a;
+    a.wp = wts.w.as<char>(); a.bias = wts.bias.as<float>(); a.res = res; a.out = out; a.stats = stats;
     W4GenArgs g{x, reinterpret_cast<const float2*>(coef), gb, us, range_flag, umax, rows.k, rows.r0};
-    const size_t lds = (size_t)a.tofs + 5 * W4Geo<512>::TILES * 4;
     static bool attr_set[6][I2V_MAX_DEV] = {};
     auto launch = [&](auto kern, bool* done) -> int {
         if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), 160 * 1024, done)) return rc;
-        hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(W4G_THREADS), lds, st, a, g);
+        hipLaunchKernelGGL(kern, dim3(p.grid), dim3(W4G_THREADS), p.lds_bytes, st, a, g);
         return I2V_OK;
     };
     int rcl;
@@ -604,21 +588,14 @@ int wino4g_forward(const Wino4Weights& wts, const float* x, const float* coef, c
     return I2V_OK;
 }
 
-// The LOADER form for the kernels of i2v_conv16w4.hip: `a` as wino4_forward fills it for the 512-thread geometry of a 32-channel 3x3x3
-// layer (TT = 4, TH = 8, no temporal duplication); same V, same bits.
-bool wino4_loader_supported(const W4Args& a, int KT) {
-    return KT == 3 && !a.tdup && a.CoutPad == 32 && a.TT == W4G_TT && a.TH == W4G_TH && a.th_shift == 3;
-}
-
-int wino4_loader_launch(W4Args& a, unsigned nblk, hipStream_t st, int form) {
-    a.nvirt = (int)nblk;
-    a.tofs = 2 * W4_ROWS_A * 64;
-    const size_t lds = (size_t)a.tofs + 5 * W4Geo<512>::TILES * 4;
-    auto kern = form == 2 ? conv_wino4g_f16x3_kernel<9, 32, 3> : conv_wino4g_f16x3_kernel<9, 32, 2>;
+// The LOADER form for the kernels of i2v_conv16w4.hip: the plan of a 32-channel 3x3x3 layer in the 512-thread geometry (TT = 4, TH = 8, no
+// temporal duplication); same V, same bits.
+int wino4_loader_launch(const W4Plan& p, hipStream_t st) {
+    const bool two = p.form == W4_LOADER2;
+    auto kern = two ? conv_wino4g_f16x3_kernel<9, 32, 3> : conv_wino4g_f16x3_kernel<9, 32, 2>;
     static bool attr_set[2][I2V_MAX_DEV] = {};
-    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), 160 * 1024, attr_set[form == 2])) return rc;
-    W4GenArgs g{};
-    hipLaunchKernelGGL(kern, dim3(nblk), dim3(W4G_THREADS), lds, st, a, g);
+    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), 160 * 1024, attr_set[two])) return rc;
+    hipLaunchKernelGGL(kern, dim3(p.grid), dim3(W4G_THREADS), p.lds_bytes, st, p.a, W4GenArgs{});
     I2V_HIP_CHECK(hipGetLastError());
     return I2V_OK;
 }

@@ -739,8 +739,8 @@ struct Conv3 {
     Wino4F32Weights wf;       // exact fp32, Winograd F(4,3) on the fp32 matrix cores (i2v_wino32.hip), next to f32
     Conv16Weights d16;        // split-fp16, direct kernel
     Wino16Weights w23;        // split-fp16, Winograd F(2,3) (packed where the shape allows)
-    Wino4Weights w43;         // split-fp16, Winograd F(4,3) (i2v_conv16w4.hip); packed INSTEAD of the F(2,3) one
-    Wino4hWeights w43h;       // one-term fp16 mode (mma = 3): F(4,3) on fp16 operands (i2v_conv16w4h.hip), packed INSTEAD of w43
+    Wino4Weights w43;         // Winograd F(4,3) (i2v_conv16w4.hip), packed INSTEAD of the F(2,3) one: split-fp16, or (w43.one) the
+                              // one-term fp16 form of mma = 3
 };
 
 struct Block {
@@ -1184,8 +1184,8 @@ struct Conv3In { const float* x; const float* coef; const float* gb; int ut, us;
 // Winograd scratch (null: the direct fp32 kernel is used).
 Conv3Kernel conv3_choose(const i2v_dec* d, const Conv3& c, const Level& l, int layer, const Conv3In& in, const float* m6) {
     if (!d->layer16(layer)) return m6 && c.wf.u[0].w.p && conv3_wants(d, c, l, K_F32_WINO) ? K_F32_WINO : K_F32;
-    if ((c.w43h.w.p || c.w43.w.p) && conv3_wants(d, c, l, K_F43)) {
-        if (c.w43h.w.p) return K_F43_ONE;
+    if (c.w43.w.p && conv3_wants(d, c, l, K_F43)) {
+        if (c.w43.one) return K_F43_ONE;
         // thin F(4,3) layers: the operand is generated by the conv kernel's producer waves (no writer launch, no V tensor).
         // I2V_DEC_GEN = 1: conv_0 and conv_1 of the thin level, 2: conv_1 only.  conv_0 reads SPADE's maps through a x2 spatial
         // up-sampling, conv_1 (ADAIN) through none; neither through a temporal one, and the debug tap wants the V tensor.
@@ -1210,7 +1210,7 @@ int conv3_write_operand(i2v_dec* d, const Conv3& c, Conv3Kernel kn, const Level&
     int* umax = is_split(kn) && flag ? flag + 1 + layer : nullptr;
     const size_t pos = (size_t)B * T * l.H * l.W;
     // (the one-term operand is tapped whole: 3 bytes per activation of CinPad channels)
-    *tap_floats = kn == K_F43_GEN || kn == K_F32_WINO ? 0 : kn == K_F43_ONE ? pos * c.w43h.CinPad * 3 / 4 : pos * c.cin;
+    *tap_floats = kn == K_F43_GEN || kn == K_F32_WINO ? 0 : kn == K_F43_ONE ? pos * c.w43.CinPad * 3 / 4 : pos * c.cin;
     switch (kn) {
     case K_F43_GEN: return I2V_OK;
     case K_F32_WINO: return modulate_wino4_f32(in.x, in.coef, in.gb, a, B, T, l.H, l.W, c.cin, ut, in.us, 1, st, in.rows);
@@ -1241,8 +1241,8 @@ int conv3_run(i2v_dec* d, const Conv3& c, Conv3Kernel kn, const Level& l, int la
     case K_F32_WINO: return wino4f32_forward(c.wf, a, w.m6, out, res, rt, rs, B, l.T, l.H, l.W, epi, st);
     case K_F16: return conv16_forward(c.d16, a, out, res, rt, rs, B, l.T, l.H, l.W, epi, st, stats, nullptr, w.splitk, w.splitk_floats);
     case K_F23: return wino16_forward(c.w23, a, out, res, rt, rs, B, l.T, l.H, l.W, epi, st, stats);
-    case K_F43: return wino4_forward(c.w43, a, out, res, rt, rs, B, l.T, l.H, l.W, epi, st, stats);
-    case K_F43_ONE: return wino4h_forward(c.w43h, a, out, res, rt, rs, B, l.T, l.H, l.W, epi, st, stats);
+    case K_F43:
+    case K_F43_ONE: return wino4_forward(c.w43, a, out, res, rt, rs, B, l.T, l.H, l.W, epi, st, stats);
     case K_F43_GEN: return wino4g_forward(c.w43, in.x, in.coef, in.gb, in.us, out, res, rt, rs, B, l.T, l.H, l.W, epi, st, stats, flag,
                                           flag ? flag + 1 + layer : nullptr, in.rows);
     }
@@ -1384,8 +1384,8 @@ int pack_conv3(const StateDict& sd, const std::string& name, bool spectral, Conv
     // (tdup: packed for the half-rate input, Conv16Weights::pack_tdup)
     if ((variants & bit(K_F16)) && (rc = c.tdup ? c.d16.pack_tdup(w, bias, co, ci, scale) : c.d16.pack(w, bias, co, ci, 3, 3, 3, scale))) return rc;
     if ((variants & bit(K_F23)) && (rc = c.tdup ? c.w23.pack_tdup(w, bias, co, ci, scale) : c.w23.pack(w, bias, co, ci, 3, scale))) return rc;
-    if ((variants & bit(K_F43)) && (rc = c.tdup ? c.w43.pack_tdup(w, bias, co, ci, scale) : c.w43.pack(w, bias, co, ci, scale))) return rc;
-    if ((variants & bit(K_F43_ONE)) && (rc = c.tdup ? c.w43h.pack_tdup(w, bias, co, ci, scale) : c.w43h.pack(w, bias, co, ci, scale))) return rc;
+    const bool one = variants & bit(K_F43_ONE);   // (packed instead of K_F43, never next to it)
+    if ((variants & (bit(K_F43) | bit(K_F43_ONE))) && (rc = c.tdup ? c.w43.pack_tdup(w, bias, co, ci, scale, one) : c.w43.pack(w, bias, co, ci, scale, 3, one))) return rc;
     return I2V_OK;
 }
 

@@ -168,25 +168,9 @@ bool wino4f32_supported(int cout, int cin, int T, int H, int W) {
 
 int Wino4F32Weights::pack(const float* w_src, const float* bias_src, int cout, int cin, double scale) {
     Cin = cin; Cout = cout;
-    std::vector<float> tmp((size_t)cout * cin * 9);
-    for (int x = 0; x < 6; ++x) {
-        for (size_t nc = 0; nc < (size_t)cout * cin; ++nc)
-            for (int th = 0; th < 9; ++th) {   // (kt, kh)
-                const double g0 = (double)w_src[nc * 27 + th * 3] * scale, g1 = (double)w_src[nc * 27 + th * 3 + 1] * scale,
-                             g2 = (double)w_src[nc * 27 + th * 3 + 2] * scale;
-                double u;
-                switch (x) {
-                    case 0: u = g0 / 4.0; break;
-                    case 1: u = -(g0 + g1 + g2) / 6.0; break;
-                    case 2: u = -(g0 - g1 + g2) / 6.0; break;
-                    case 3: u = g0 / 24.0 + g1 / 12.0 + g2 / 6.0; break;
-                    case 4: u = g0 / 24.0 - g1 / 12.0 + g2 / 6.0; break;
-                    default: u = g2; break;
-                }
-                tmp[nc * 9 + th] = (float)u;
-            }
-        if (int rc = u[x].pack(tmp.data(), nullptr, cout, cin, 3, 3, 1, 1.0)) return rc;
-    }
+    const std::vector<float> planes = wino43_planes_f32(w_src, cout, cin, scale);   // U_x = (G g)_x per (kt, kh)
+    for (int x = 0; x < 6; ++x)
+        if (int rc = u[x].pack(&planes[(size_t)x * cout * cin * 9], nullptr, cout, cin, 3, 3, 1, 1.0)) return rc;
     if (bias_src) return bias.upload(bias_src, (size_t)cout * 4);
     bias.release();
     return I2V_OK;

@@ -144,10 +144,10 @@ def test_flow_batch_sizes_and_sharding_property():
     assert rel_l2(zt.reshape(11, 64).cpu(), ztr.reshape(11, 64)) < TOL and np.allclose(ld.cpu(), ldr, rtol=1e-4, atol=1e-4)
 
 
-def _gen(meta):
+def _gen(meta, **cfg):
     from stage1_VAE.modules.decoder import Generator
     gen = Generator({"channel_factor": meta["synth"]["channel_factor"], "z_dim": 64, "upsample_s": meta["upsample_s"],
-                     "upsample_t": meta["upsample_t"], "spectral_norm": True})
+                     "upsample_t": meta["upsample_t"], "spectral_norm": True, **cfg})
     gen.load_state_dict(T(synth.decoder_state_dict(**meta["synth"])))
     return gen.cuda().eval()
 
@@ -420,12 +420,14 @@ def test_generated_operand_kernel_keeps_the_bits(monkeypatch):
     assert torch.equal(outs["0"], outs["1"])
 
 
-def test_f43_tile_width_switch_across_batches():
+@pytest.mark.parametrize("mma", [1, 3])
+def test_f43_tile_width_switch_across_batches(mma):
     """The F(4,3) launcher narrows its workgroups to 32 channels when 64-channel ones would leave CUs idle -- a decision that
     depends on batch x bricks (round-4 advisor finding: only tested through I2V_W4_BN at one batch).  nf = 8 BAIR: g_1's convs have 4
-    workgroups per sample, so B = 1 / 8 run 32-channel workgroups and B = 64 / 96 run 64-channel ones: rows must equal shards."""
+    workgroups per sample, so B = 1 / 8 run 32-channel workgroups and B = 64 / 96 run 64-channel ones: rows must equal shards.
+    Both operand forms (mma = 1 split-fp16, mma = 3 one-term fp16) take the decision from the one launch plan (wino4_plan)."""
     g, meta = load_golden("dec_nf8_bair")
-    gen = _gen(meta)
+    gen = _gen(meta, mma=mma)
     x0, z, _ = synth.bench_inputs(96, g["img"].shape[-1], 64)
     x0, z = x0.cuda(), z.cuda()
     big = gen(x0, z)

@@ -2,7 +2,7 @@
 // split-fp16 kernel (csrc/i2v_conv16.hip) on one layer shape.
 //   conv16w_check B T H W Cin Cout tdup res      (T = output frames; tdup: conv_0 behind a x2 temporal up-sampling)
 // and, where the shape allows it, of the F(4,3) kernel (csrc/i2v_conv16w4.hip) next to them.
-// Build: hipcc -O3 --offload-arch=gfx950 -I<csrc> tools/conv16w_check.hip <csrc>/i2v_conv16w.hip <csrc>/i2v_conv16w4.hip
+// Build: hipcc -O3 --offload-arch=gfx950 -I<csrc> tools/conv16w_check.hip <csrc>/i2v_conv16w.hip <csrc>/i2v_conv16w4.hip <csrc>/i2v_conv16w4h.hip
 //        <csrc>/i2v_conv16.hip <csrc>/i2v_common.hip -o tools/conv16w_check
 // Measurement builds of the F(4,3) kernel (same command plus):
 //   -DW4_TIMELINE   wall-clock stamps per workgroup phase (tables + first brick, pass A, hand-over, pass B, epilogue halves and
