@@ -242,6 +242,12 @@ int i2v_encoder3d_create(const i2v_encoder3d_cfg* cfg, i2v_encoder3d** out) {
     I2V_REQUIRE(cfg->z_dim > 0 && !cfg->use_max_pool, I2V_E_INVALID,
                 "i2v_encoder3d_create: z_dim > 0 required; use_max_pool is false in every shipped config and is not supported");
     I2V_REQUIRE(147 * 3 * cfg->channels[0] * 4 <= 150 * 1024, I2V_E_INVALID, "i2v_encoder3d_create: stem too wide for LDS");
+    // A layer that halves the time extent needs a downsample branch for its residual, and resnet3D.py:180 builds one only for a
+    // spatial stride or a change of width: without it the reference's `out += residual` fails on the time extent.
+    for (int i = 0; i < 4; ++i)
+        I2V_REQUIRE(!(cfg->stride_s[i] == 1 && cfg->stride_t[i] == 2 && cfg->channels[i] == cfg->channels[i + 1]), I2V_E_INVALID,
+                    "i2v_encoder3d_create: layer %d has stride_t 2 with stride_s 1 and equal widths (%d): no downsample branch exists "
+                    "for its half-rate residual", i, cfg->channels[i]);
     int ndev = 0;
     I2V_HIP_CHECK(hipGetDeviceCount(&ndev));
     I2V_REQUIRE(ndev > 0, I2V_E_HIP, "i2v_encoder3d_create: no HIP device");
@@ -357,6 +363,15 @@ int i2v_encoder3d_forward(i2v_encoder3d* e, const float* x, int32_t t, int32_t h
     int rc;
     int T = (t + 2 - 3) / 2 + 1, H = h / 2, W = w / 2, C = e->cfg.channels[0];
     I2V_REQUIRE((T & (T - 1)) == 0, I2V_E_INVALID, "i2v_encoder3d_forward: %d input frames give %d stem frames (need a power of two)", t, T);
+    {   // the layers' geometry, walked before anything is launched
+        int Tf = T, Hf = H, Wf = W;
+        for (int l = 0; l < 4; ++l) {
+            if (e->cfg.stride_t[l] == 2) Tf = (Tf + 1) / 2;
+            Hf /= e->cfg.stride_s[l]; Wf /= e->cfg.stride_s[l];
+        }
+        I2V_REQUIRE(Tf == 1 && Hf == 4 && Wf == 4, I2V_E_INVALID,
+                    "i2v_encoder3d_forward: the feature map is [%d,%d,%d], conv_mu/conv_var need [1,4,4]", Tf, Hf, Wf);
+    }
     {
         static bool attr[I2V_MAX_DEV] = {};
         if (int rc2 = ensure_dynamic_lds(reinterpret_cast<const void*>(enc_stem_kernel), 160 * 1024, attr)) return rc2;
@@ -405,8 +420,6 @@ int i2v_encoder3d_forward(i2v_encoder3d* e, const float* x, int32_t t, int32_t h
         std::swap(x16, y16);
         T = To; H = Ho; W = Wo; C = b.planes;
     }
-    I2V_REQUIRE(T == 1 && H == 4 && W == 4, I2V_E_INVALID,
-                "i2v_encoder3d_forward: the feature map is [%d,%d,%d], conv_mu/conv_var need [1,4,4]", T, H, W);
     if ((rc = conv_forward(e->head, xcur, 16 * C, F(L.ml), nullptr, 1, 1, B, 1, 1, 1, EPI_NONE, st))) return rc;
     hipLaunchKernelGGL(reparam_kernel, dim3((B * e->cfg.z_dim + 255) / 256), dim3(256), 0, st, F(L.ml), eps, sample, mu, logvar, B,
                        e->cfg.z_dim);

@@ -1050,6 +1050,8 @@ class NativeEncoder3D(_Handle):
         if x.dim() != 5 or x.shape[1] != 3:
             raise I2VError(f"encoder: expected x [B,3,T,H,W], got {tuple(x.shape)}")
         B, _, T, H, W = x.shape
+        if eps is not None and tuple(eps.shape) != (B, self.z_dim):
+            raise I2VError(f"encoder: expected eps [{B},{self.z_dim}], got {tuple(eps.shape)}")
         ws = self._ws.get(lib().i2v_encoder3d_workspace_bytes(self._h, B, T, H, W), x.device)
         mu = torch.empty(B, self.z_dim, dtype=torch.float32, device=x.device)
         logvar = torch.empty_like(mu)

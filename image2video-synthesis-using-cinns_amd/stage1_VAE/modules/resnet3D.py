@@ -53,6 +53,11 @@ class Encoder(NativeBacked):
         layers = []
         for i, ch in enumerate(self.channels[1:]):
             down = None
+            if self.stride_s[i] == 1 and self.stride_t[i] == 2 and inplanes == ch:
+                # no downsample branch is built for this layer (next line), so the reference's `out += residual` fails on the
+                # halved time extent (resnet3D.py:132); i2v_encoder3d_create refuses the same configuration
+                raise ValueError(f"Encoder: layer {i} has stride_t 2 with stride_s 1 and equal widths ({ch}): it has no downsample "
+                                 "branch for its half-rate residual")
             if self.stride_s[i] != 1 or inplanes != ch:                      # resnet3D.py:180
                 down = nn.Sequential(ConvParams(inplanes, ch, 3, 3, bias=False), AffineParams(ch))
             layers.append(nn.Sequential(BasicBlock(inplanes, ch, self.stride_s[i], self.stride_t[i], down), BasicBlock(ch, ch)))

@@ -398,7 +398,9 @@ int i2v_fvd_stats_update(const float* feats, int32_t n, int32_t d, double* sum, 
  * Motion encoder of the transfer path (row N3): Encoder.forward -- stage1_VAE/modules/resnet3D.py:138-219
  * (3D ResNet-18, GroupNorm(16), conv_mu / conv_var).  Model.transfer (get_model.py:87) uses mu.
  * Keys: conv1.weight, norm1.*, layer.{L}.{i}.{conv1,conv2}.weight, .bn{1,2}.*, .downsample.{0.weight,1.*},
- * conv_mu.*, conv_var.*.  Frames must be powers of two >= 64 and reduce to a [1,4,4] map.
+ * conv_mu.*, conv_var.*.  Frames must be powers of two >= 64 and reduce to a [1,4,4] map (checked before anything is launched).
+ * Channels: multiples of 16 in [16, 1024], the stem at most 80.  A layer with stride_t 2, stride_s 1 and equal widths has no
+ * downsample branch for its half-rate residual (resnet3D.py:184; the reference fails in `out += residual`): create refuses it.
  * ---------------------------------------------------------------------------------------- */
 typedef struct i2v_encoder3d i2v_encoder3d;
 typedef struct {

@@ -301,6 +301,47 @@ def encoder3d():
         print("   ", name, "|mu| mean", float(mu.abs().mean()), "|logvar| mean", float(logvar.abs().mean()))
 
 
+def save_stable(name, meta, **arrays):
+    """``save`` with a fixed member order and time stamp: the same arrays give the same file, byte for byte."""
+    import io
+    import zipfile
+    arrays = {k: (v.numpy() if isinstance(v, torch.Tensor) else np.asarray(v)) for k, v in arrays.items()}
+    arrays["meta"] = np.frombuffer(json.dumps(meta, sort_keys=True).encode(), dtype=np.uint8)
+    path = os.path.join(HERE, name + ".npz")
+    with zipfile.ZipFile(path, "w") as zf:
+        for k in sorted(arrays):
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asarray(arrays[k], order="C"), allow_pickle=False)
+            info = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            zf.writestr(info, buf.getvalue(), compresslevel=9)
+    print(f"{name}.npz  {os.path.getsize(path) / 1e3:.0f} kB")
+
+
+def encoder3d_cfgs():
+    # N3 at the configurations of tests/encoder_cfgs.py that the reference's Encoder can build (64-channel stem): one file,
+    # <case>_mu / _logvar / _x_head / _x_sum per case, the cases' synthesiser arguments in the meta.  Runs only when named.
+    from stage1_VAE.modules import resnet3D as ref_r3d
+    spec = importlib.util.spec_from_file_location("encoder_cfgs", os.path.join(REPO, "tests", "encoder_cfgs.py"))
+    cfgs = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(cfgs)
+    out, meta = {}, {"cases": {}}
+    for name in cfgs.REF_NAMES:
+        c = cfgs.CASES[name]
+        a = c["synth"]
+        enc = ref_r3d.Encoder({"res_type_encoder": "resnet18", "use_max_pool": False, "z_dim": a["z_dim"], "channels": a["channels"],
+                               "stride_s": a["stride_s"], "stride_t": c["stride_t"], "deterministic": False}).eval()
+        enc.load_state_dict(T(synth.encoder3d_state_dict(**a)))
+        x = 2 * torch.rand(*c["x_shape"], generator=torch.Generator().manual_seed(c["x_seed"])) - 1
+        _, mu, logvar = enc(x)
+        out.update({name + "_mu": mu, name + "_logvar": logvar, name + "_x_head": x.reshape(-1)[:16],
+                    name + "_x_sum": np.float64(x.double().sum())})
+        meta["cases"][name] = {k: c[k] for k in ("synth", "stride_t", "x_seed", "x_shape")}
+        print("   ", name, "|mu| mean", float(mu.abs().mean()), "|logvar| mean", float(logvar.abs().mean()))
+    save_stable("enc3d_cfgs", meta, **out)
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or ["flow_units", "flow_full", "dec_units", "dec_small", "dec_full", "model_small", "encoder3d",
                              "model_t32_128"]
@@ -322,3 +363,5 @@ if __name__ == "__main__":
         encoder3d()
     if "model_t32_128" in which:
         model_t32_128()
+    if "encoder3d_cfgs" in which:   # (not in the default list: the fixtures above are never rewritten by it)
+        encoder3d_cfgs()
