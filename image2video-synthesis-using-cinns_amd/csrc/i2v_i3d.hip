@@ -21,6 +21,14 @@
 // tile it falls in: batch rows equal their single-sample runs bit for bit, and there are no atomics anywhere.
 //
 // Max pools pad with ZEROS that take part in the maximum (ConstantPad3d(.., 0) in front of MaxPool3d(ceil_mode=True)).
+//
+// Second variant on the same handle: the dynamic-texture I3D of metrics/DTFVD/ID3.py (length 16) and ID3_32.py (length 32), the DTFVD
+// and diversity feature network.  Same topology, same kernels; its own state_dict keys (Conv3d_1a_7x7.bn, Mixed_3b.b1a, logits),
+// BatchNorm eps 1e-5, SAME padding by the size % stride rule in all three dimensions (compute_pad; F.pad zeros in front of a
+// floor-mode MaxPool3d -- on a SAME-padded extent floor and ceil agree), AvgPool3d((2, 7, 7)) or ((4, 7, 7)).  The metric reads
+// get_representation, the average pool's output as [B][1024][T']: i2v_i3d_features stops there, no classifier, no time mean.
+// The input stage maps output frame t to source frame t % T_in (calculate_FVD's repeat x 3 then [:16]).
+// i2v_diversity_update: the pair loop of metrics/Diversity/I3D.py in float64, one workgroup, fixed order.
 #include <algorithm>
 #include <cmath>
 #include <memory>
@@ -160,13 +168,16 @@ __global__ __launch_bounds__(256) void i3d_conv_kernel(I3dConvArgs a) {
 
 // FVD_logging.preprocess fused with the layout change: frames [N = B T][3][Hi][Wi] -> channels-last [N][224][224][4] (channel 3
 // zero), bilinear with align_corners=True in the arithmetic of torch's upsample_bilinear2d, then (x + 1) / 2 when `denorm`.
-__global__ __launch_bounds__(256) void i3d_input_kernel(const float* __restrict__ frames, float* __restrict__ out, long N, int Hi, int Wi,
-                                                        int denorm) {
+// Time mapping: output frame t of clip b (N = B Tout) reads source frame b Tin + t % Tin -- DTFVD_Score.calculate_FVD's
+// repeat(1, 3, 1, 1, 1)[:, :16]; Tout <= Tin is plain truncation, Tin = Tout = 1 a flat list of N frames.
+__global__ __launch_bounds__(256) void i3d_input_kernel(const float* __restrict__ frames, float* __restrict__ out, long N, int Tin, int Tout,
+                                                        int Hi, int Wi, int denorm) {
     const long total = N * I3D_SIDE * I3D_SIDE;
     const float sh = (float)(Hi - 1) / (float)(I3D_SIDE - 1), sw = (float)(Wi - 1) / (float)(I3D_SIDE - 1);
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
         const int w = (int)(i % I3D_SIDE), h = (int)((i / I3D_SIDE) % I3D_SIDE);
-        const long n = i / (I3D_SIDE * I3D_SIDE);
+        const long no = i / (I3D_SIDE * I3D_SIDE);
+        const long n = no / Tout * Tin + (int)(no % Tout) % Tin;
         const float fh = sh * h, fw = sw * w;
         const int h0 = (int)fh, w0 = (int)fw;
         const int h1 = h0 + (h0 < Hi - 1 ? 1 : 0), w1 = w0 + (w0 < Wi - 1 ? 1 : 0);
@@ -222,17 +233,20 @@ __global__ __launch_bounds__(256) void i3d_maxpool_kernel(I3dPoolArgs a) {
     }
 }
 
-// AvgPool3d((2, 7, 7), stride 1) on [B][T][7][7][C] -> [B][T - 1][C]; fixed summation order
-__global__ __launch_bounds__(256) void i3d_avgpool_kernel(const float* __restrict__ in, float* __restrict__ out, int B, int T, int C) {
-    const long total = (long)B * (T - 1) * C;
+// AvgPool3d((kT, 7, 7), stride 1) on [B][T][7][7][C] -> [B][T - kT + 1][C], or with `chw` [B][C][T - kT + 1] (get_representation's
+// layout after its two squeeze(3)); fixed summation order
+__global__ __launch_bounds__(256) void i3d_avgpool_kernel(const float* __restrict__ in, float* __restrict__ out, int B, int T, int C, int kT,
+                                                          int chw) {
+    const int To = T - kT + 1, n = 49 * kT;
+    const long total = (long)B * To * C;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
         const int c = (int)(i % C);
-        const int t = (int)((i / C) % (T - 1));
-        const int b = (int)(i / ((long)C * (T - 1)));
+        const int t = (int)((i / C) % To);
+        const int b = (int)(i / ((long)C * To));
         const float* p = in + (((long)b * T + t) * 49) * C + c;
         float s = 0.f;
-        for (int j = 0; j < 98; ++j) s += p[(long)j * C];
-        out[i] = s / 98.f;
+        for (int j = 0; j < n; ++j) s += p[(long)j * C];
+        out[chw ? ((long)b * C + c) * To + t : i] = s / (float)n;
     }
 }
 
@@ -267,9 +281,39 @@ __global__ __launch_bounds__(256) void fvd_stats_kernel(const float* __restrict_
     }
 }
 
+// The pair loop of metrics/Diversity/I3D.py:53-57 on embed [N][R][D]: acc[0] += sum_n sum_{i != j} mean_d (e_ni - e_nj)^2, acc[1] += the
+// number N R (R - 1) of (instance, ordered pair) terms.  ONE workgroup owns the result: thread x sums its columns d = x, x + 256, ... over
+// the instances and the pairs i < j in order (each counted twice: the square is symmetric), in float64 as the reference's float64 array
+// does; then a fixed tree over the 256 partial sums.  Two runs give the same bits.
+__global__ __launch_bounds__(256) void diversity_kernel(const float* __restrict__ e, int N, int R, int D, double* __restrict__ acc) {
+    __shared__ double red[256];
+    const int tid = threadIdx.x;
+    double s = 0.0;
+    for (int n = 0; n < N; ++n) {
+        const float* en = e + (long)n * R * D;
+        for (int i = 0; i < R; ++i)
+            for (int j = i + 1; j < R; ++j)
+                for (int d = tid; d < D; d += 256) {
+                    const double v = (double)en[(long)i * D + d] - (double)en[(long)j * D + d];
+                    s += v * v;
+                }
+    }
+    red[tid] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w) red[tid] += red[tid + w];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        acc[0] += 2.0 * red[0] / (double)D;
+        acc[1] += (double)N * R * (R - 1);
+    }
+}
+
 unsigned grid_for(long total) { return (unsigned)std::min<long>((total + 255) / 256, 1L << 20); }
 
 // "TF SAME" padding of one dimension (get_padding_shape): `mod` = input size % stride for the TIME dimension of a strided unit
+// (Kinetics), for every dimension of a strided unit (dynamic-texture variant: Unit3D.compute_pad, MaxPool3dSamePadding.compute_pad)
 void same_pad(int k, int s, int mod, int* front, int* back) {
     const int along = std::max(mod ? k - mod : k - s, 0);
     *front = along / 2;
@@ -285,10 +329,11 @@ int pool_out(int e, int k, int s) {
 struct Unit {
     DevBuf w, ss;
     int Cin = 0, Cout = 0, CoutPad = 0, BN = 64, K = 1, C4 = 0, nchunk = 0;
-    int pack(const StateDict& sd, const std::string& name, int cin, int cout, int k, bool bn, bool bias);
+    int pack(const StateDict& sd, const std::string& name, int cin, int cout, int k, bool bn, bool bias, const char* bnkey = "batch3d",
+             double eps = 1e-3);
 };
 
-int Unit::pack(const StateDict& sd, const std::string& name, int cin, int cout, int k, bool bn, bool bias) {
+int Unit::pack(const StateDict& sd, const std::string& name, int cin, int cout, int k, bool bn, bool bias, const char* bnkey, double eps) {
     Cin = cin; Cout = cout; K = k;
     const int taps = k * k * k;
     const float* wsrc = sd.f32(name + ".conv3d.weight", (int64_t)cout * cin * taps);
@@ -313,14 +358,16 @@ int Unit::pack(const StateDict& sd, const std::string& name, int cin, int cout, 
     int rc = w.upload(p.data(), p.size() * 4);
     if (rc) return rc;
     std::vector<float> s((size_t)CoutPad * 2, 0.f);
-    if (bn) {   // eval-mode BatchNorm3d, eps = 1e-3 (Unit3Dpy: tf_style_eps): (x - mean) / sqrt(var + eps) * weight + bias
-        const float* g = sd.f32(name + ".batch3d.weight", cout);
-        const float* b = sd.f32(name + ".batch3d.bias", cout);
-        const float* m = sd.f32(name + ".batch3d.running_mean", cout);
-        const float* v = sd.f32(name + ".batch3d.running_var", cout);
+    if (bn) {   // eval-mode BatchNorm3d: (x - mean) / sqrt(var + eps) * weight + bias; eps = 1e-3 under "batch3d" (Unit3Dpy: tf_style_eps),
+                // torch's default 1e-5 under "bn" (ID3.Unit3D)
+        const std::string bk = name + "." + bnkey;
+        const float* g = sd.f32(bk + ".weight", cout);
+        const float* b = sd.f32(bk + ".bias", cout);
+        const float* m = sd.f32(bk + ".running_mean", cout);
+        const float* v = sd.f32(bk + ".running_var", cout);
         if (!g || !b || !m || !v) return I2V_E_MISSING;
         for (int n = 0; n < cout; ++n) {
-            const double a = (double)g[n] / std::sqrt((double)v[n] + 1e-3);
+            const double a = (double)g[n] / std::sqrt((double)v[n] + eps);
             s[2 * n] = (float)a;
             s[2 * n + 1] = (float)((double)b[n] - (double)m[n] * a);
         }
@@ -349,6 +396,8 @@ using namespace i2v;
 
 struct i2v_i3d {
     int num_classes = 0, in_channels = 3, device = 0;
+    int dt = 0;       // 0: Kinetics-400 network (metrics/PyTorch_FVD/I3D.py); 16 / 32: dynamic-texture network of that length (metrics/DTFVD)
+    int pool_t = 2;   // time extent of the average pool: (2, 7, 7), ID3_32: (4, 7, 7)
     bool loaded = false;
     Unit stem, c2b, c2c, head;
     Unit mixed[9][6];   // branch_0, branch_1.0, branch_1.1, branch_2.0, branch_2.1, branch_3.1
@@ -366,14 +415,14 @@ struct Walk {
     size_t act_floats = 0, tmp_floats = 0;   // dry: the largest block-level tensor / branch temporary
 
     int conv(const Unit& u, const float* in, int inCS, int inOff, Dims di, float* out, int outCS, int outOff, Dims dout, int sT, int s,
-             int pT, int pS, bool relu) {
+             int pT, int pS, bool relu, int pW = -1) {
         if (dry) return I2V_OK;
         I3dConvArgs a{};
         a.in = in; a.wp = u.w.as<float>(); a.ss = u.ss.as<float2>(); a.out = out;
         a.M = (long)B * dout.pos();
         a.Ti = di.T; a.Hi = di.H; a.Wi = di.W; a.To = dout.T; a.Ho = dout.H; a.Wo = dout.W;
         a.inCS = inCS; a.inOff = inOff; a.C4 = u.C4; a.G = u.K * u.K * u.K * u.C4; a.nchunk = u.nchunk;
-        a.KH = u.K; a.KW = u.K; a.sT = sT; a.sH = s; a.sW = s; a.pT = pT; a.pH = pS; a.pW = pS;
+        a.KH = u.K; a.KW = u.K; a.sT = sT; a.sH = s; a.sW = s; a.pT = pT; a.pH = pS; a.pW = pW < 0 ? pS : pW;
         a.Cout = u.Cout; a.CoutPad = u.CoutPad; a.outCS = outCS; a.outOff = outOff; a.relu = relu ? 1 : 0;
         I2V_REQUIRE(inCS % 4 == 0 && inOff % 4 == 0 && inOff + 4 * u.C4 <= inCS && outOff + u.Cout <= outCS, I2V_E_INVALID,
                     "i3d conv: channel slice [%d, +%d) of %d -> [%d, +%d) of %d", inOff, 4 * u.C4, inCS, outOff, u.Cout, outCS);
@@ -389,11 +438,11 @@ struct Walk {
     // MaxPool3dTFPadding(kernel (kT, k, k), stride (sT, s, s)); returns the output dims
     int pool(const float* in, float* out, int C, Dims di, int kT, int k, int sT, int s, Dims* dout) {
         I3dPoolArgs a{};
-        int bT, bS;
+        int bT, bH, bW;
         same_pad(kT, sT, sT > 1 ? di.T % sT : 0, &a.pT, &bT);
-        same_pad(k, s, 0, &a.pH, &bS);
-        a.pW = a.pH;
-        a.eT = a.pT + di.T + bT; a.eH = a.pH + di.H + bS; a.eW = a.pW + di.W + bS;
+        same_pad(k, s, net->dt && s > 1 ? di.H % s : 0, &a.pH, &bH);
+        same_pad(k, s, net->dt && s > 1 ? di.W % s : 0, &a.pW, &bW);
+        a.eT = a.pT + di.T + bT; a.eH = a.pH + di.H + bH; a.eW = a.pW + di.W + bW;
         dout->T = pool_out(a.eT, kT, sT); dout->H = pool_out(a.eH, k, s); dout->W = pool_out(a.eW, k, s);
         if (dry) return I2V_OK;
         a.in = in; a.out = out; a.B = B; a.Ti = di.T; a.Hi = di.H; a.Wi = di.W; a.To = dout->T; a.Ho = dout->H; a.Wo = dout->W; a.C = C;
@@ -405,22 +454,26 @@ struct Walk {
 
     void need(size_t* slot, long floats) { *slot = std::max(*slot, (size_t)floats); }
 
-    // frames -> logits.  inp / x / y / tmp / pooled / cls: workspace buffers (null when dry)
-    int run(const float* frames, int T, int H, int W, int denorm, float* inp, float* x, float* y, float* tmp, float* pooled, float* cls,
-            float* logits, int* t_head) {
+    // frames -> logits, or with `features` -> the average pool's output [B][1024][T'] in `logits` (no classifier, no time mean).
+    // T frames enter the network, frame t read from source frame t % Tin.  inp / x / y / tmp / pooled / cls: workspace buffers (null when dry)
+    int run(const float* frames, int Tin, int T, int H, int W, int denorm, float* inp, float* x, float* y, float* tmp, float* pooled, float* cls,
+            float* logits, int* t_head, bool features = false) {
         int rc;
         Dims d{T, I3D_SIDE, I3D_SIDE};
         if (!dry) {
-            hipLaunchKernelGGL(i3d_input_kernel, dim3(grid_for((long)B * T * I3D_SIDE * I3D_SIDE)), dim3(256), 0, st, frames, inp, (long)B * T, H, W,
-                               denorm);
+            hipLaunchKernelGGL(i3d_input_kernel, dim3(grid_for((long)B * T * I3D_SIDE * I3D_SIDE)), dim3(256), 0, st, frames, inp, (long)B * T, Tin, T,
+                               H, W, denorm);
             I2V_HIP_CHECK(hipGetLastError());
         }
-        // conv3d_1a_7x7: stride 2, SAME = (2, 3) per dimension, (3, 3) in time for an odd T
-        int pT, bT;
+        // conv3d_1a_7x7: stride 2, SAME = (2, 3) per dimension, (3, 3) in time for an odd T (and, by the dynamic-texture variant's rule, in
+        // an odd spatial dimension: none at 224)
+        int pT, bT, pH, bH, pW, bW;
         same_pad(7, 2, T % 2, &pT, &bT);
-        Dims o{(T + pT + bT - 7) / 2 + 1, 112, 112};
+        same_pad(7, 2, net->dt ? d.H % 2 : 0, &pH, &bH);
+        same_pad(7, 2, net->dt ? d.W % 2 : 0, &pW, &bW);
+        Dims o{(T + pT + bT - 7) / 2 + 1, (d.H + pH + bH - 7) / 2 + 1, (d.W + pW + bW - 7) / 2 + 1};
         need(&act_floats, (long)B * o.pos() * 64);
-        if ((rc = conv(net->stem, inp, 4, 0, d, x, 64, 0, o, 2, 2, pT, 2, true))) return rc;
+        if ((rc = conv(net->stem, inp, 4, 0, d, x, 64, 0, o, 2, 2, pT, pH, true, pW))) return rc;
         d = o;
         if ((rc = pool(x, y, 64, d, 1, 3, 1, 2, &o))) return rc;                              // maxPool3d_2a_3x3
         d = o;
@@ -450,15 +503,19 @@ struct Walk {
             if (i == 1) { if ((rc = pool(x, y, C, d, 3, 3, 2, 2, &o))) return rc; d = o; std::swap(x, y); }   // maxPool3d_4a_3x3
             if (i == 6) { if ((rc = pool(x, y, C, d, 2, 2, 2, 2, &o))) return rc; d = o; std::swap(x, y); }   // maxPool3d_5a_2x2
         }
-        I2V_REQUIRE(d.H == 7 && d.W == 7 && d.T >= 2, I2V_E_INVALID,
-                    "i3d: %d frames leave a [%d, %d, %d] map in front of AvgPool3d((2, 7, 7)); at least 9 frames are needed", T, d.T, d.H, d.W);
-        *t_head = d.T - 1;
+        const int kT = net->pool_t;
+        I2V_REQUIRE(d.H == 7 && d.W == 7 && d.T >= kT, I2V_E_INVALID,
+                    "i3d: %d frames leave a [%d, %d, %d] map in front of AvgPool3d((%d, 7, 7)); at least %d frames are needed", T, d.T, d.H, d.W, kT,
+                    8 * (kT - 1) + 1);
+        *t_head = d.T - kT + 1;
         if (dry) return I2V_OK;
-        hipLaunchKernelGGL(i3d_avgpool_kernel, dim3(grid_for((long)B * (d.T - 1) * 1024)), dim3(256), 0, st, x, pooled, B, d.T, 1024);
+        hipLaunchKernelGGL(i3d_avgpool_kernel, dim3(grid_for((long)B * (d.T - kT + 1) * 1024)), dim3(256), 0, st, x, features ? logits : pooled, B,
+                           d.T, 1024, kT, features ? 1 : 0);
         I2V_HIP_CHECK(hipGetLastError());
-        const Dims dh{d.T - 1, 1, 1};
+        if (features) return I2V_OK;
+        const Dims dh{d.T - kT + 1, 1, 1};
         if ((rc = conv(net->head, pooled, 1024, 0, dh, cls, net->num_classes, 0, dh, 1, 1, 0, 0, false))) return rc;   // conv3d_0c_1x1
-        hipLaunchKernelGGL(i3d_time_mean_kernel, dim3(grid_for((long)B * net->num_classes)), dim3(256), 0, st, cls, logits, B, d.T - 1,
+        hipLaunchKernelGGL(i3d_time_mean_kernel, dim3(grid_for((long)B * net->num_classes)), dim3(256), 0, st, cls, logits, B, dh.T,
                            net->num_classes);
         I2V_HIP_CHECK(hipGetLastError());
         return I2V_OK;
@@ -467,18 +524,19 @@ struct Walk {
 
 struct I3dWs { size_t inp, x, y, tmp, pooled, cls, total; };
 
-int i3d_ws(const i2v_i3d* net, int B, int T, int H, int W, I3dWs* L) {
+int i3d_ws(const i2v_i3d* net, int B, int T, int H, int W, I3dWs* L, bool features = false, int* t_head = nullptr) {
     Walk wk{net, B, true, nullptr};
     int th = 0;
-    if (int rc = wk.run(nullptr, T, H, W, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &th)) return rc;
+    if (int rc = wk.run(nullptr, T, T, H, W, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &th, features)) return rc;
+    if (t_head) *t_head = th;
     size_t o = 0;
     auto take = [&](size_t floats) { size_t r = o; o = align_up(o + floats * 4, 256); return r; };
     L->inp = take((size_t)B * T * I3D_SIDE * I3D_SIDE * 4);
     L->x = take(wk.act_floats);
     L->y = take(wk.act_floats);
     L->tmp = take(wk.tmp_floats);
-    L->pooled = take((size_t)B * th * 1024);
-    L->cls = take((size_t)B * th * net->num_classes);
+    L->pooled = take(features ? 0 : (size_t)B * th * 1024);
+    L->cls = take(features ? 0 : (size_t)B * th * net->num_classes);
     L->total = o;
     return I2V_OK;
 }
@@ -501,6 +559,14 @@ int i2v_i3d_create(int32_t num_classes, int32_t in_channels, i2v_i3d** out) {
     return I2V_OK;
 }
 
+int i2v_dti3d_create(int32_t num_classes, int32_t length, i2v_i3d** out) {
+    I2V_REQUIRE(length == 16 || length == 32, I2V_E_INVALID, "i2v_dti3d_create: the dynamic-texture I3D exists for length 16 and 32, got %d", length);
+    if (int rc = i2v_i3d_create(num_classes, 3, out)) return rc;
+    (*out)->dt = length;
+    (*out)->pool_t = length == 32 ? 4 : 2;
+    return I2V_OK;
+}
+
 void i2v_i3d_destroy(i2v_i3d* n) { delete n; }
 
 int i2v_i3d_load(i2v_i3d* n, const i2v_tensor* tensors, int32_t n_tensors) {
@@ -509,6 +575,23 @@ int i2v_i3d_load(i2v_i3d* n, const i2v_tensor* tensors, int32_t n_tensors) {
     StateDict sd(tensors, n_tensors);
     int rc;
     n->loaded = false;
+    if (n->dt) {   // ID3.InceptionI3D: Conv3d_* / Mixed_*.{b0,b1a,b1b,b2a,b2b,b3b} / logits, BatchNorm3d under "bn" with eps 1e-5
+        static const char* const BR[6] = {".b0", ".b1a", ".b1b", ".b2a", ".b2b", ".b3b"};
+        if ((rc = n->stem.pack(sd, "Conv3d_1a_7x7", n->in_channels, 64, 7, true, false, "bn", 1e-5))) return rc;
+        if ((rc = n->c2b.pack(sd, "Conv3d_2b_1x1", 64, 64, 1, true, false, "bn", 1e-5))) return rc;
+        if ((rc = n->c2c.pack(sd, "Conv3d_2c_3x3", 64, 192, 3, true, false, "bn", 1e-5))) return rc;
+        for (int i = 0; i < 9; ++i) {
+            const MixedSpec& s = MIXED[i];
+            std::string p = s.name;
+            p[0] = 'M';
+            const int cin[6] = {s.cin, s.cin, s.o[1], s.cin, s.o[3], s.cin};
+            for (int j = 0; j < 6; ++j)
+                if ((rc = n->mixed[i][j].pack(sd, p + BR[j], cin[j], s.o[j], j == 2 || j == 4 ? 3 : 1, true, false, "bn", 1e-5))) return rc;
+        }
+        if ((rc = n->head.pack(sd, "logits", 1024, n->num_classes, 1, false, true))) return rc;   // (i2v_i3d_features never launches it)
+        n->loaded = true;
+        return I2V_OK;
+    }
     if ((rc = n->stem.pack(sd, "conv3d_1a_7x7", n->in_channels, 64, 7, true, false))) return rc;
     if ((rc = n->c2b.pack(sd, "conv3d_2b_1x1", 64, 64, 1, true, false))) return rc;
     if ((rc = n->c2c.pack(sd, "conv3d_2c_3x3", 64, 192, 3, true, false))) return rc;
@@ -551,13 +634,49 @@ int i2v_i3d_forward(i2v_i3d* n, const float* frames, int32_t batch, int32_t t, i
     auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
     Walk wk{n, batch, false, st};
     int th = 0;
-    return wk.run(frames, t, h, w, denorm ? 1 : 0, F(L.inp), F(L.x), F(L.y), F(L.tmp), F(L.pooled), F(L.cls), logits, &th);
+    return wk.run(frames, t, t, h, w, denorm ? 1 : 0, F(L.inp), F(L.x), F(L.y), F(L.tmp), F(L.pooled), F(L.cls), logits, &th);
+}
+
+size_t i2v_i3d_features_workspace_bytes(const i2v_i3d* n, int32_t batch, int32_t t_out, int32_t h, int32_t w) {
+    if (!n || batch <= 0 || t_out <= 0 || h < 2 || w < 2) return 0;
+    I3dWs L;
+    if (i3d_ws(n, batch, t_out, h, w, &L, true)) return 0;
+    return L.total;
+}
+
+int32_t i2v_i3d_feature_steps(const i2v_i3d* n, int32_t t_out) {
+    if (!n || t_out <= 0) return 0;
+    I3dWs L;
+    int th = 0;
+    if (i3d_ws(n, 1, t_out, I3D_SIDE, I3D_SIDE, &L, true, &th)) return 0;
+    return th;
+}
+
+int i2v_i3d_features(i2v_i3d* n, const float* frames, int32_t batch, int32_t t_in, int32_t t_out, int32_t h, int32_t w, int32_t denorm,
+                     float* feats, void* workspace, size_t workspace_bytes, void* stream) {
+    if (n) I2V_REQUIRE_DEVICE(n->device, "i2v_i3d_features");
+    I2V_REQUIRE(n && n->loaded, I2V_E_STATE, "i2v_i3d_features: weights not loaded");
+    I2V_REQUIRE(frames && feats && workspace && batch > 0 && t_in > 0 && t_out > 0 && h >= 2 && w >= 2, I2V_E_INVALID,
+                "i2v_i3d_features: bad argument");
+    I2V_REQUIRE((long)batch * t_out * I3D_SIDE * I3D_SIDE * 64 < (1L << 40) && (long)batch * t_in * 3 * h * w < (1L << 40), I2V_E_INVALID,
+                "i2v_i3d_features: batch %d x %d frames is too large", batch, t_out);
+    I3dWs L;
+    if (int rc = i3d_ws(n, batch, t_out, h, w, &L, true)) return rc;
+    I2V_REQUIRE(workspace_bytes >= L.total, I2V_E_WORKSPACE, "i2v_i3d_features: workspace %zu < required %zu", workspace_bytes, L.total);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rco = n->order.entry(st)) return rco;
+    StreamOrderMark mark{&n->order, st};
+    char* ws = static_cast<char*>(workspace);
+    auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    Walk wk{n, batch, false, st};
+    int th = 0;
+    return wk.run(frames, t_in, t_out, h, w, denorm ? 1 : 0, F(L.inp), F(L.x), F(L.y), F(L.tmp), nullptr, nullptr, feats, &th, true);
 }
 
 int i2v_i3d_input_stage(const float* frames, int32_t n_frames, int32_t h, int32_t w, int32_t denorm, float* out, void* stream) {
     I2V_REQUIRE(frames && out && n_frames > 0 && h >= 2 && w >= 2, I2V_E_INVALID, "i2v_i3d_input_stage: bad argument");
     hipLaunchKernelGGL(i3d_input_kernel, dim3(grid_for((long)n_frames * I3D_SIDE * I3D_SIDE)), dim3(256), 0, static_cast<hipStream_t>(stream), frames,
-                       out, (long)n_frames, h, w, denorm ? 1 : 0);
+                       out, (long)n_frames, 1, 1, h, w, denorm ? 1 : 0);
     I2V_HIP_CHECK(hipGetLastError());
     return I2V_OK;
 }
@@ -565,6 +684,13 @@ int i2v_i3d_input_stage(const float* frames, int32_t n_frames, int32_t h, int32_
 int i2v_fvd_stats_update(const float* feats, int32_t n, int32_t d, double* sum, double* gram, void* stream) {
     I2V_REQUIRE(feats && sum && gram && n > 0 && d > 0, I2V_E_INVALID, "i2v_fvd_stats_update: bad argument");
     hipLaunchKernelGGL(fvd_stats_kernel, dim3(grid_for((long)d * d + d)), dim3(256), 0, static_cast<hipStream_t>(stream), feats, n, d, sum, gram);
+    I2V_HIP_CHECK(hipGetLastError());
+    return I2V_OK;
+}
+
+int i2v_diversity_update(const float* embed, int32_t n, int32_t r, int32_t d, double* acc, void* stream) {
+    I2V_REQUIRE(embed && acc && n > 0 && r > 0 && d > 0, I2V_E_INVALID, "i2v_diversity_update: bad argument");
+    hipLaunchKernelGGL(diversity_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), embed, n, r, d, acc);
     I2V_HIP_CHECK(hipGetLastError());
     return I2V_OK;
 }

@@ -116,6 +116,12 @@ SYMBOLS = {
     "i2v_i3d_forward": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_size_t, c_void_p]),
     "i2v_i3d_input_stage": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "i2v_fvd_stats_update": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "i2v_dti3d_create": (c_int32, [c_int32, c_int32, POINTER(c_void_p)]),
+    "i2v_i3d_features_workspace_bytes": (c_size_t, [c_void_p, c_int32, c_int32, c_int32, c_int32]),
+    "i2v_i3d_feature_steps": (c_int32, [c_void_p, c_int32]),
+    "i2v_i3d_features": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_size_t,
+                                   c_void_p]),
+    "i2v_diversity_update": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "i2v_dec_create": (c_int32, [POINTER(DecCfg), POINTER(c_void_p)]),
     "i2v_dec_destroy": (None, [c_void_p]),
     "i2v_dec_load": (c_int32, [c_void_p, POINTER(_Tensor), c_int32]),
@@ -1063,14 +1069,19 @@ class NativeEncoder3D(_Handle):
 
 
 class NativeI3D(_Handle):
-    """Handle for ``i2v_i3d_*`` (the Kinetics-400 I3D of metrics/PyTorch_FVD/I3D.py with FVD_logging.preprocess as its input stage)."""
+    """Handle for ``i2v_i3d_*`` (the Kinetics-400 I3D of metrics/PyTorch_FVD/I3D.py with FVD_logging.preprocess as its input stage) and,
+    with ``dt_length`` 16 or 32, for the dynamic-texture I3D of metrics/DTFVD/ID3.py / ID3_32.py (``i2v_dti3d_create``)."""
 
-    def __init__(self, num_classes, in_channels=3, device=None):
+    def __init__(self, num_classes, in_channels=3, device=None, dt_length=None):
         h = c_void_p()
         with self._bind(device):
-            _check(lib().i2v_i3d_create(num_classes, in_channels, ctypes.byref(h)), "i2v_i3d_create")
+            if dt_length is None:
+                _check(lib().i2v_i3d_create(num_classes, in_channels, ctypes.byref(h)), "i2v_i3d_create")
+            else:
+                _check(lib().i2v_dti3d_create(num_classes, dt_length, ctypes.byref(h)), "i2v_dti3d_create")
         self._h = h
         self.num_classes = num_classes
+        self.dt_length = dt_length
         self._ws = _Workspace()
 
     def __del__(self):
@@ -1100,6 +1111,27 @@ class NativeI3D(_Handle):
                                      _stream()), "i2v_i3d_forward")
         return out
 
+    @_on_device
+    def features(self, frames, denorm=False, t_out=None):
+        """``i2v_i3d_features``: frames [B, T_in, 3, H, W] -> the average pool's output [B, 1024, T'] (``get_representation``).  ``t_out``
+        frames enter the network, frame t read from source frame t % T_in (None: T_in)."""
+        _require_gpu(frames)
+        if frames.dim() != 5 or frames.shape[2] != 3:
+            raise I2VError(f"i3d: expected frames [B,T,3,H,W], got {tuple(frames.shape)}")
+        B, T, _, H, W = frames.shape
+        t_out = T if t_out is None else int(t_out)
+        steps = lib().i2v_i3d_feature_steps(self._h, t_out)
+        nbytes = lib().i2v_i3d_features_workspace_bytes(self._h, B, t_out, H, W) if steps > 0 else 0
+        if nbytes == 0:
+            need = 25 if self.dt_length == 32 else 9
+            raise I2VError(f"i3d: no plan for frames {tuple(frames.shape)} with {t_out} frames per clip (at least {need} frames of at least "
+                           "2 x 2 pixels are needed)")
+        ws = self._ws.get(nbytes, frames.device)
+        out = torch.empty(B, 1024, steps, dtype=torch.float32, device=frames.device)
+        _check(lib().i2v_i3d_features(self._h, frames.data_ptr(), B, T, t_out, H, W, int(bool(denorm)), out.data_ptr(), ws.data_ptr(),
+                                      ws.numel(), _stream()), "i2v_i3d_features")
+        return out
+
 
 def fvd_stats_update(feats, total, gram):
     """``total`` [D] and ``gram`` [D, D] (float64, device) += the rows of ``feats`` [n, D] fp32 (``i2v_fvd_stats_update``): one owner per
@@ -1111,6 +1143,19 @@ def fvd_stats_update(feats, total, gram):
             raise I2VError(f"fvd_stats_update: expected a contiguous float64 device tensor of shape {shape}")
     with torch.cuda.device(feats.device):
         _check(lib().i2v_fvd_stats_update(feats.data_ptr(), n, d, total.data_ptr(), gram.data_ptr(), _stream()), "i2v_fvd_stats_update")
+
+
+def diversity_update(embed, acc):
+    """``acc`` [2] (float64, device) += (sum over instances and ordered pairs i != j of mean_d (e_i - e_j)^2, number of such terms) of
+    ``embed`` [N, R, D] fp32 (``i2v_diversity_update``): float64, one workgroup, fixed order."""
+    _require_gpu(embed)
+    if embed.dim() != 3 or embed.dtype != torch.float32 or not embed.is_contiguous():
+        raise I2VError(f"diversity_update: expected contiguous fp32 embeddings [N,R,D], got {tuple(embed.shape)} {embed.dtype}")
+    if not acc.is_cuda or acc.dtype != torch.float64 or not acc.is_contiguous() or tuple(acc.shape) != (2,) or acc.device != embed.device:
+        raise I2VError("diversity_update: expected a contiguous float64 device tensor of shape (2,)")
+    n, r, d = embed.shape
+    with torch.cuda.device(embed.device):
+        _check(lib().i2v_diversity_update(embed.data_ptr(), n, r, d, acc.data_ptr(), _stream()), "i2v_diversity_update")
 
 
 def i3d_input_stage(frames, denorm):

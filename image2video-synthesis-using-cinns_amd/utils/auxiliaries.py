@@ -3,8 +3,8 @@ loop that the reference's evaluation runs over a data loader.
 
 Own implementations of the reference behaviour (``utils/auxiliaries.py:15-22`` GIF tiling, ``:53-55`` denormalisation,
 ``:87-101`` the sampling loop of ``evaluate_FVD_prior``) and the FVD evaluation hooks ``evaluate_FVD_prior`` /
-``evaluate_FVD_posterior`` on the device (metrics/PyTorch_FVD); the DTFVD network, wandb logging and video writers of the
-reference are not rebuilt."""
+``evaluate_FVD_posterior`` on the device (metrics/PyTorch_FVD, and with ``mode='DTFVD'`` metrics/DTFVD); wandb logging and video
+writers of the reference are not rebuilt."""
 import numpy as np
 import torch
 
@@ -126,9 +126,17 @@ def sample_prior(dloader, cINN, decoder, z_dim, control=False, generator=None):
 
 
 def _fvd_accumulator(I3D, mode, who):
+    """'FVD' with the Kinetics-400 I3D (metrics/PyTorch_FVD) or 'DTFVD' with a dynamic-texture InceptionI3D (metrics/DTFVD)."""
+    if mode == 'DTFVD':
+        from metrics.DTFVD.DTFVD_Score import DTFVDAccumulator
+        from metrics.DTFVD.ID3 import InceptionI3D
+        if not isinstance(I3D, InceptionI3D):
+            raise NotImplementedError(f"{who}: mode 'DTFVD' needs the dynamic-texture network (metrics.DTFVD.DTFVD_Score.load_model), got "
+                                      f"{type(I3D).__name__}; DTFVD on any other network is not built")
+        return DTFVDAccumulator(I3D)
     if mode != 'FVD':
-        raise NotImplementedError(f"{who}: mode {mode!r} -- only 'FVD' (the Kinetics-400 I3D of metrics/PyTorch_FVD) is built; the DTFVD "
-                                  "network (metrics/DTFVD) is not")
+        raise NotImplementedError(f"{who}: mode {mode!r} -- only 'FVD' (the Kinetics-400 I3D of metrics/PyTorch_FVD) and 'DTFVD' (the "
+                                  "dynamic-texture I3D of metrics/DTFVD) are built")
     from metrics.PyTorch_FVD.FVD_logging import FVDAccumulator
     return FVDAccumulator(I3D)
 
@@ -141,7 +149,7 @@ def evaluate_FVD_prior(dloader, cINN, decoder, I3D, z_dim, opt, epoch, mode, con
     No frame goes to the host: every batch is fed to a ``FVDAccumulator`` on the device as it is decoded.  All clips count (the reference's
     ``calculate_FVD(.., 20)`` drops the ragged last batch of 20).  The reference's side effects -- the GIF of ten random samples
     (``plot_vid``) and ``wandb.log`` -- are left out; ``opt`` and ``epoch`` only served them and are unused."""
-    acc = _fvd_accumulator(I3D, mode, "evaluate_FVD_prior")
+    acc = _fvd_accumulator(I3D, mode, "evaluate_FVD_prior")   # (mode 'DTFVD': the accumulator's default is no de-normalisation)
     for g, o in _prior_batches(dloader, cINN, decoder, z_dim, control):
         acc.update(g, "gen")
         acc.update(o, "orig")

@@ -395,6 +395,35 @@ int i2v_i3d_input_stage(const float* frames, int32_t n_frames, int32_t h, int32_
 int i2v_fvd_stats_update(const float* feats, int32_t n, int32_t d, double* sum, double* gram, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * DTFVD / diversity feature network: the dynamic-texture I3D -- metrics/DTFVD/ID3.py (length 16) and ID3_32.py (length 32):
+ * InceptionI3D.get_representation :351-358, Unit3D :48-119, MaxPool3dSamePadding :12-42, InceptionModule :125-181.  A second
+ * variant on the i2v_i3d handle; what differs from the Kinetics network:
+ *   keys      Conv3d_1a_7x7.conv3d.weight, .bn.{weight,bias,running_mean,running_var}, Conv3d_2b_1x1.*, Conv3d_2c_3x3.*,
+ *             Mixed_{3b,3c,4b..4f,5b,5c}.{b0,b1a,b1b,b2a,b2b,b3b}.*, logits.conv3d.{weight,bias}; num_batches_tracked is ignored
+ *   BatchNorm eps 1e-5 (torch's default), folded at load
+ *   padding   SAME by the size % stride rule in all three dimensions (compute_pad); equal to the Kinetics rule at 224 x 224
+ *   head      AvgPool3d((2, 7, 7)), length 32: ((4, 7, 7)); the metric reads its output, the classifier is never run
+ * i2v_i3d_load, i2v_i3d_destroy and i2v_i3d_forward (logits; not used by DTFVD) work on either variant.
+ * ---------------------------------------------------------------------------------------- */
+/* InceptionI3D.__init__ (ID3.py:224-321, ID3_32.py) as DTFVD_Score.load_model(length) builds it; length 16 or 32 */
+int i2v_dti3d_create(int32_t num_classes, int32_t length, i2v_i3d** out);
+/* Workspace of i2v_i3d_features for t_out frames per clip; 0 if there is no plan (too few frames for the average pool). */
+size_t i2v_i3d_features_workspace_bytes(const i2v_i3d* n, int32_t batch, int32_t t_out, int32_t h, int32_t w);
+/* T' of get_representation for t_out input frames (0: too few; at least 9 frames, length 32: 25) */
+int32_t i2v_i3d_feature_steps(const i2v_i3d* n, int32_t t_out);
+/* InceptionI3D.get_representation behind the input rule of DTFVD_Score.calculate_FVD (:173-176) / embedding_I3D (:205-206):
+ * frames [B][t_in][3][h][w] fp32 are resized to 224 x 224 (bilinear, align_corners=True); frame t of the t_out that enter the
+ * network is source frame t % t_in (repeat(1, 3, 1, 1, 1)[:, :16]; t_out <= t_in is plain truncation); (x + 1) / 2 only when
+ * denorm != 0 (the DTFVD paths pass 0) -> feats [B][1024][T'], the average pool's output after the two squeeze(3).  Either
+ * variant of the handle.  Only enqueues on `stream`. */
+int i2v_i3d_features(i2v_i3d* n, const float* frames, int32_t batch, int32_t t_in, int32_t t_out, int32_t h, int32_t w, int32_t denorm,
+                     float* feats, void* workspace, size_t workspace_bytes, void* stream);
+/* The pair loop of metrics/Diversity/I3D.py compute_DTI3D_diversity (:53-57) on embed [n][r][d] fp32 (instance, realization,
+ * feature): acc[0] += sum over the n instances and all ordered pairs i != j of mean_d (e_i - e_j)^2, acc[1] += n r (r - 1).
+ * float64, one workgroup, fixed order: two runs give the same bits.  acc[0] / acc[1] is the reference's np.mean(div). */
+int i2v_diversity_update(const float* embed, int32_t n, int32_t r, int32_t d, double* acc, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Motion encoder of the transfer path (row N3): Encoder.forward -- stage1_VAE/modules/resnet3D.py:138-219
  * (3D ResNet-18, GroupNorm(16), conv_mu / conv_var).  Model.transfer (get_model.py:87) uses mu.
  * Keys: conv1.weight, norm1.*, layer.{L}.{i}.{conv1,conv2}.weight, .bn{1,2}.*, .downsample.{0.weight,1.*},
