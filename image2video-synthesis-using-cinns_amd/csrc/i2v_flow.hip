@@ -15,7 +15,11 @@
 //
 //   W0x / W0e    state part [S][8][2H][4] and embedding part [R/64][E/4][64][4] of the first layers: every wave load 1 KB
 //
-// Two implementations of the launch chain, both replayed from one hipGraph per direction:
+// What happens between two coupling half-steps -- which Shuffle / ActNorm block, InvLeakyRelu, half swap, which half-step next, for
+// either direction and every skip_* / activation switch -- is decided in ONE place, flow_schedule() in i2v_flow_sched.h (pinned to
+// flow_blocks.py's op order by tests/test_host_flow_sched.py).  A launch chain walks those S + 1 links and only fills its own
+// argument struct from each; a new chain (e.g. a persistent one) must consume the schedule too, never re-derive it.
+// Two implementations of the launch chain, both replayed from one hipGraph per direction (run_chain: the one graph cache):
 //   * i2v_flow_tile.hip (default for the shipped geometry: 64 channels, hidden 128..512, depth >= 1): every Linear on
 //     16 x 16 tiles of v_mfma_f32_16x16x4_f32, tile-major activations, last layer fused into the last hidden layer;
 //   * the generic vector-ALU kernels below (any hidden_dim that is a multiple of 64, depth 0; I2V_FLOW_TILE=0 selects them
@@ -237,11 +241,10 @@ struct i2v_flow {
     bool loaded = false;
     int S = 0;      // half-steps = 2 * n_flows
     int H = 0, E = 0, ld0 = 0, depth = 0;
-    DevBuf W0, W0x, W0e, b0, Wmid, bmid, W3T, b3, an_loc, an_scale, shuf_f, shuf_b;  // W0x: [S][8][2H][4] state part of W0
+    DevBuf W0x, W0e, Wmid, W3T;      // the generic chain's weight matrices; W0x: [S][8][2H][4] state part of the first layers
+    FlowParams par;                  // biases, ActNorm, Shuffle, schedule switches: read in place by both chains
     FlowTilePack tile;               // matrix-core tile chain (i2v_flow_tile.hip); tile.ok: packed and selected
     bool tile_wanted = true;         // env I2V_FLOW_TILE=0: generic vector-ALU chain
-    std::vector<float> an_logdet;
-    std::vector<int> step_cond;  // 1: first layer sees only the embedding (mode 'cond')
     size_t param_bytes = 0;
     // graph cache: one instantiated chain per direction (motion transfer alternates forward and inverse passes)
     hipStream_t cap_stream = nullptr;
@@ -298,125 +301,84 @@ int enqueue_chain(i2v_flow* f, bool reverse, char* ws, int B, hipStream_t st) {
     float* hB = reinterpret_cast<float*>(ws + L.hB);
     const int H = f->H, N2 = 2 * f->H, S = f->S;
     const int Bp = (B + 63) / 64 * 64;
-    const bool act = f->cfg.activation != 0, an = !f->cfg.skip_actnorm, sh = !f->cfg.skip_shuffle;
+    const FlowParams& par = f->par;
 
     if (!reverse) I2V_HIP_CHECK(hipMemsetAsync(logdet, 0, (size_t)B * 4, st));
     {   // embedding part of every first layer, all half-steps at once: preT[b][s][n] = b0 + W0[:, 32:] . embed
         const int R = S * N2, Epad = (f->E + 3) / 4 * 4;
-        hipLaunchKernelGGL(flow_pre_kernel, dim3((R + 255) / 256, (B + PRE_SC - 1) / PRE_SC), dim3(256), 0, st, f->W0e.as<float>(), f->b0.as<float>(), embed,
+        hipLaunchKernelGGL(flow_pre_kernel, dim3((R + 255) / 256, (B + PRE_SC - 1) / PRE_SC), dim3(256), 0, st, f->W0e.as<float>(), par.b0.as<float>(), embed,
                            preT, R, f->E, Epad, B);
         I2V_HIP_CHECK(hipGetLastError());
     }
-    // next_step: half-step whose first layer is evaluated at the end of this launch (-1: none)
-    auto tail = [&](const float* h, int step, int shuf_block, int an_block, bool lrelu, bool swap, int next_step) -> int {
+    // Walk the pass schedule (i2v_flow_sched.h): per link one flow_tail_kernel launch -- last layer + coupling of k.step (its hidden
+    // layers' output in `h`; none in front of the first half-step), the ops up to the next half-step, the first layer of
+    // k.next_step into hA -- then the hidden layers of k.next_step.
+    const float* h = nullptr;
+    for (const FlowLink& k : par.schedule(reverse)) {
         TailArgs t{};
-        if (next_step >= 0) {
-            t.l1 = f->step_cond[next_step] ? 2 : 1;
+        if (k.next_step >= 0) {
+            t.l1 = par.step_cond[k.next_step] ? 2 : 1;
             t.N2 = N2;
-            t.W0x = f->W0x.as<float>() + (size_t)next_step * N2 * 32;
-            t.pre = preT + (size_t)next_step * N2;
+            t.W0x = f->W0x.as<float>() + (size_t)k.next_step * N2 * 32;
+            t.pre = preT + (size_t)k.next_step * N2;
             t.pre_stride = (long)S * N2;
             t.h0 = hA;  // (may alias h: a workgroup only touches column b of either, reads before it writes)
         }
         t.h = h;
-        t.W3T = h ? f->W3T.as<float>() + (size_t)step * H * 64 : nullptr;
-        t.b3 = h ? f->b3.as<float>() + (size_t)step * 64 : nullptr;
+        t.W3T = h ? f->W3T.as<float>() + (size_t)k.step * H * 64 : nullptr;
+        t.b3 = h ? par.b3.as<float>() + (size_t)k.step * 64 : nullptr;
         t.x = x;
         t.logdet = reverse ? nullptr : logdet;
         t.H = H;
         t.B = B;
         t.Bp = Bp;
         t.reverse = reverse ? 1 : 0;
-        t.shuf = shuf_block >= 0 ? (reverse ? f->shuf_b.as<int>() : f->shuf_f.as<int>()) + shuf_block * 64 : nullptr;
-        t.an_loc = an_block >= 0 ? f->an_loc.as<float>() + an_block * 64 : nullptr;
-        t.an_scale = an_block >= 0 ? f->an_scale.as<float>() + an_block * 64 : nullptr;
-        t.an_logdet = an_block >= 0 ? f->an_logdet[an_block] : 0.f;
-        t.do_lrelu = lrelu ? 1 : 0;
-        t.do_swap = swap ? 1 : 0;
+        t.shuf = k.shuf_block >= 0 ? (reverse ? par.shuf_b : par.shuf_f).as<int>() + k.shuf_block * 64 : nullptr;
+        t.an_loc = k.an_block >= 0 ? par.an_loc.as<float>() + k.an_block * 64 : nullptr;
+        t.an_scale = k.an_block >= 0 ? par.an_scale.as<float>() + k.an_block * 64 : nullptr;
+        t.an_logdet = k.an_block >= 0 ? par.an_logdet[k.an_block] : 0.f;
+        t.do_lrelu = k.lrelu ? 1 : 0;
+        t.do_swap = k.swap ? 1 : 0;
         hipLaunchKernelGGL(flow_tail_kernel, dim3(B), dim3(64 * TAIL_WAVES), 0, st, t);
         I2V_HIP_CHECK(hipGetLastError());
-        return I2V_OK;
-    };
-    const int nf = f->cfg.n_flows;
-    // ops in front of the first half-step
-    int rc;
-    auto step_of = [&](int it) {  // forward visits (fl, i) = (0,0),(0,1),(1,0)...; reverse visits (nf-1,1),(nf-1,0),(nf-2,1)...
-        const int fl = reverse ? nf - 1 - it / 2 : it / 2;
-        const int i = reverse ? 1 - it % 2 : it % 2;
-        return fl * 2 + i;
-    };
-    if (!reverse) rc = tail(nullptr, 0, -1, an ? 0 : -1, act, false, step_of(0));
-    else rc = tail(nullptr, 0, sh ? nf - 1 : -1, -1, false, false, step_of(0));
-    if (rc) return rc;
-
-    for (int it = 0; it < S; ++it) {
-        // forward visits (fl, i) = (0,0),(0,1),(1,0)...; reverse visits (nf-1,1),(nf-1,0),(nf-2,1)...
-        const int fl = reverse ? nf - 1 - it / 2 : it / 2;
-        const int i = reverse ? 1 - it % 2 : it % 2;
-        const int step = fl * 2 + i;
-        // layer 0 (K = 32 state channels + the precomputed embedding part as a per-(n,b) bias) was evaluated into hA by the
-        // previous launch of the chain (flow_tail_kernel)
+        if (k.next_step < 0) break;
+        // layer 0 (K = 32 state channels + the precomputed embedding part as a per-(n,b) bias) was evaluated into hA by the tail
         float* cur = hA;
         float* nxt = hB;
         for (int d = 0; d < f->depth; ++d) {
             HidArgs m{};
-            m.W = f->Wmid.as<float>() + ((size_t)step * f->depth + d) * N2 * H;
+            m.W = f->Wmid.as<float>() + ((size_t)k.next_step * f->depth + d) * N2 * H;
             m.ldw = H;
             m.K = H;
             m.in = cur;
             m.in_group_stride = (long)H * Bp;
             m.group_rows = H;
-            m.bias = f->bmid.as<float>() + ((size_t)step * f->depth + d) * N2;
+            m.bias = par.bmid.as<float>() + ((size_t)k.next_step * f->depth + d) * N2;
             m.out = nxt;
             m.N = N2;
             m.Bp = Bp;
             m.slope = 0.01f;
-            if ((rc = launch_hidden(m, st))) return rc;
+            if (int rc = launch_hidden(m, st)) return rc;
             std::swap(cur, nxt);
         }
-        // last layer + coupling + the ops up to the next half-step's first layer
-        int shuf_block = -1, an_block = -1;
-        bool lrelu = false, swap = false;
-        if (!reverse) {
-            if (i == 0) swap = true;  // before half-step 1: cat(chunk[::-1])
-            else {
-                if (sh) shuf_block = fl;
-                if (fl + 1 < nf) { if (an) an_block = fl + 1; lrelu = act; }
-            }
-        } else {
-            if (i == 1) swap = true;  // before half-step 0 (flow_blocks.py:98-99)
-            else {
-                lrelu = act;
-                if (an) an_block = fl;
-                if (fl - 1 >= 0 && sh) shuf_block = fl - 1;
-            }
-        }
-        if ((rc = tail(cur, step, shuf_block, an_block, lrelu, swap, it + 1 < S ? step_of(it + 1) : -1))) return rc;
+        h = cur;
     }
     return I2V_OK;
 }
 
-// Matrix-core tile chain: the caller's tensors are read / written by the chain's own first / last launches through the
-// handle's FlowIo block, so the replayed graph needs no copy kernels around it.
-int run_pass_tile(i2v_flow* f, bool reverse, const float* xin, const float* embed, float* xout, float* logdet, char* ws, int B,
-                  hipStream_t st) {
-    FlowTileChain c{};
-    c.pack = &f->tile;
-    c.b0 = f->b0.as<float>(); c.bmid = f->bmid.as<float>(); c.b3 = f->b3.as<float>();
-    c.an_loc = f->an_loc.as<float>(); c.an_scale = f->an_scale.as<float>(); c.an_logdet_host = f->an_logdet.data();
-    c.shuf_f = f->shuf_f.as<int>(); c.shuf_b = f->shuf_b.as<int>(); c.step_cond = f->step_cond.data();
-    c.n_flows = f->cfg.n_flows;
-    c.use_an = !f->cfg.skip_actnorm; c.use_act = f->cfg.activation != 0; c.use_shuf = !f->cfg.skip_shuffle;
-    int rc = flow_tile_set_io(f->tile, FlowIo{xin, embed, xout, reverse ? nullptr : logdet}, st);
-    if (rc) return rc;
-    if (!f->cfg.use_graph) return flow_tile_enqueue(c, reverse, ws, B, st);
+// One pass = `enqueue(stream)` replayed from a graph: the cached hipGraphExec_t of (direction, B, workspace), or a newly captured one
+// (cfg.use_graph = 0: enqueued on `st` directly).  One instantiated chain per direction: motion transfer alternates forward and
+// inverse passes.
+template <class Enqueue>
+int run_chain(i2v_flow* f, bool reverse, int B, void* ws, hipStream_t st, Enqueue enqueue) {
+    if (!f->cfg.use_graph) return enqueue(st);
     const int d = reverse ? 1 : 0;
     if (!(f->gexec[d] && f->g_B[d] == B && f->g_ws[d] == ws)) {
         if (f->gexec[d]) { (void)hipGraphExecDestroy(f->gexec[d]); f->gexec[d] = nullptr; }
         if (!f->cap_stream) I2V_HIP_CHECK(hipStreamCreateWithFlags(&f->cap_stream, hipStreamNonBlocking));
         hipGraph_t graph = nullptr;
         I2V_HIP_CHECK(hipStreamBeginCapture(f->cap_stream, hipStreamCaptureModeThreadLocal));
-        rc = flow_tile_enqueue(c, reverse, ws, B, f->cap_stream);
+        const int rc = enqueue(f->cap_stream);
         hipError_t e = hipStreamEndCapture(f->cap_stream, &graph);
         if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
         I2V_HIP_CHECK(e);
@@ -440,35 +402,19 @@ int run_pass(i2v_flow* f, bool reverse, const float* xin, const float* embed, fl
     char* ws = static_cast<char*>(workspace);
     if (int rco = f->order.entry(st)) return rco;
     StreamOrderMark mark{&f->order, st};   // records the end of this pass on its stream (also on the error paths)
-    if (f->tile.ok) return run_pass_tile(f, reverse, xin, embed, xout, logdet, ws, B, st);
+    if (f->tile.ok) {
+        // matrix-core tile chain: its own first / last launches read / write the caller's tensors through the handle's FlowIo block,
+        // so the replayed graph needs no copy kernels around it
+        if (int rc = flow_tile_set_io(f->tile, FlowIo{xin, embed, xout, reverse ? nullptr : logdet}, st)) return rc;
+        return run_chain(f, reverse, B, ws, st, [&](hipStream_t s) { return flow_tile_enqueue(f->tile, f->par, reverse, ws, B, s); });
+    }
     {
         const int na = B * 64, nb = B * f->E;
         hipLaunchKernelGGL(flow_copy2_kernel, dim3((na + nb + 255) / 256), dim3(256), 0, st, xin,
                            reinterpret_cast<float*>(ws + L.x), na, embed, reinterpret_cast<float*>(ws + L.embed), nb);
         I2V_HIP_CHECK(hipGetLastError());
     }
-    if (f->cfg.use_graph) {
-        const int d = reverse ? 1 : 0;
-        if (!(f->gexec[d] && f->g_B[d] == B && f->g_ws[d] == workspace)) {
-            if (f->gexec[d]) { (void)hipGraphExecDestroy(f->gexec[d]); f->gexec[d] = nullptr; }
-            if (!f->cap_stream) I2V_HIP_CHECK(hipStreamCreateWithFlags(&f->cap_stream, hipStreamNonBlocking));
-            hipGraph_t graph = nullptr;
-            I2V_HIP_CHECK(hipStreamBeginCapture(f->cap_stream, hipStreamCaptureModeThreadLocal));
-            int rc = enqueue_chain(f, reverse, ws, B, f->cap_stream);
-            hipError_t e = hipStreamEndCapture(f->cap_stream, &graph);
-            if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-            I2V_HIP_CHECK(e);
-            e = hipGraphInstantiate(&f->gexec[d], graph, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(graph);
-            I2V_HIP_CHECK(e);
-            f->g_B[d] = B;
-            f->g_ws[d] = workspace;
-        }
-        I2V_HIP_CHECK(hipGraphLaunch(f->gexec[d], st));
-    } else {
-        int rc = enqueue_chain(f, reverse, ws, B, st);
-        if (rc) return rc;
-    }
+    if (int rc = run_chain(f, reverse, B, ws, st, [&](hipStream_t s) { return enqueue_chain(f, reverse, ws, B, s); })) return rc;
     {
         const int na = B * 64, nb = logdet ? B : 0;
         hipLaunchKernelGGL(flow_copy2_kernel, dim3((na + nb + 255) / 256), dim3(256), 0, st,
@@ -502,6 +448,10 @@ int i2v_flow_create(const i2v_flow_cfg* cfg, i2v_flow** out) {
     f->E = cfg->embedding_dim;
     f->ld0 = 32 + cfg->embedding_dim;
     f->depth = cfg->hidden_depth;
+    f->par.n_flows = cfg->n_flows;
+    f->par.use_an = !cfg->skip_actnorm;
+    f->par.use_act = cfg->activation != 0;
+    f->par.use_shuf = !cfg->skip_shuffle;
     if (const char* e = std::getenv("I2V_FLOW_TILE")) f->tile_wanted = std::atoi(e) != 0;  // 0: generic vector-ALU chain
     *out = f.release();
     return I2V_OK;
@@ -518,12 +468,13 @@ int i2v_flow_load(i2v_flow* f, const i2v_tensor* tensors, int32_t n_tensors) {
         bmid((size_t)S * D * N2), W3T((size_t)S * H * 64), b3((size_t)S * 64), loc((size_t)nf * 64, 0.f),
         scale((size_t)nf * 64, 1.f);
     std::vector<int> sf((size_t)nf * 64), sb((size_t)nf * 64);
-    f->an_logdet.assign(nf, 0.f);
-    f->step_cond.assign(S, 0);
+    FlowParams& par = f->par;
+    par.an_logdet.assign(nf, 0.f);
+    par.step_cond.assign(S, 0);
     size_t pbytes = 0, wfloats = 0;
     for (int fl = 0; fl < nf; ++fl) {
         const std::string p = "sub_layers." + std::to_string(fl) + ".";
-        const bool cond = f->cfg.control == 2 || (f->cfg.control == 1 && fl % 4 != 0);  // flow_blocks.py:24
+        const bool cond = flow_block_cond(f->cfg.control, fl);
         const int dim = cond ? E : 32 + E;
         if (!f->cfg.skip_actnorm) {
             const float* l = sd.f32(p + "norm_layer.loc", 64);
@@ -535,7 +486,7 @@ int i2v_flow_load(i2v_flow* f, const i2v_tensor* tensors, int32_t n_tensors) {
                 scale[fl * 64 + c] = s[c];
                 ld += std::log(std::fabs((double)s[c]));  // modules.py:86-87 with H = W = 1
             }
-            f->an_logdet[fl] = (float)ld;
+            par.an_logdet[fl] = (float)ld;
             pbytes += 2 * 64 * 4;
         }
         if (!f->cfg.skip_shuffle) {
@@ -552,11 +503,11 @@ int i2v_flow_load(i2v_flow* f, const i2v_tensor* tensors, int32_t n_tensors) {
         }
         for (int i = 0; i < 2; ++i) {
             const int step = fl * 2 + i;
-            f->step_cond[step] = cond ? 1 : 0;
+            par.step_cond[step] = cond ? 1 : 0;
             for (int net = 0; net < 2; ++net) {
-                const std::string q = p + "coupling." + (net == 0 ? "s." : "t.") + std::to_string(i) + ".main.";
-                const float* w = sd.f32(q + "0.weight", (int64_t)H * dim);
-                const float* bb = sd.f32(q + "0.bias", H);
+                const std::string q0 = flow_linear_key(fl, net, i, 0);
+                const float* w = sd.f32(q0 + ".weight", (int64_t)H * dim);
+                const float* bb = sd.f32(q0 + ".bias", H);
                 if (!w || !bb) return I2V_E_MISSING;
                 for (int n = 0; n < H; ++n) {
                     float* dst = &W0[((size_t)step * N2 + (size_t)net * H + n) * ld0];
@@ -565,16 +516,16 @@ int i2v_flow_load(i2v_flow* f, const i2v_tensor* tensors, int32_t n_tensors) {
                     b0[(size_t)step * N2 + net * H + n] = bb[n];
                 }
                 for (int d = 0; d < D; ++d) {
-                    const std::string li = std::to_string(2 * (d + 1));
-                    const float* wm = sd.f32(q + li + ".weight", (int64_t)H * H);
-                    const float* bm = sd.f32(q + li + ".bias", H);
+                    const std::string qd = flow_linear_key(fl, net, i, d + 1);
+                    const float* wm = sd.f32(qd + ".weight", (int64_t)H * H);
+                    const float* bm = sd.f32(qd + ".bias", H);
                     if (!wm || !bm) return I2V_E_MISSING;
                     std::memcpy(&Wmid[(((size_t)step * D + d) * N2 + (size_t)net * H) * H], wm, (size_t)H * H * 4);
                     std::memcpy(&bmid[((size_t)step * D + d) * N2 + (size_t)net * H], bm, (size_t)H * 4);
                 }
-                const std::string ll = std::to_string(2 * (D + 1));
-                const float* w3 = sd.f32(q + ll + ".weight", (int64_t)32 * H);
-                const float* bb3 = sd.f32(q + ll + ".bias", 32);
+                const std::string q3 = flow_linear_key(fl, net, i, D + 1);
+                const float* w3 = sd.f32(q3 + ".weight", (int64_t)32 * H);
+                const float* bb3 = sd.f32(q3 + ".bias", 32);
                 if (!w3 || !bb3) return I2V_E_MISSING;
                 for (int c = 0; c < 32; ++c) {
                     for (int k = 0; k < H; ++k) W3T[((size_t)step * H + k) * 64 + net * 32 + c] = w3[(size_t)c * H + k];
@@ -597,18 +548,17 @@ int i2v_flow_load(i2v_flow* f, const i2v_tensor* tensors, int32_t n_tensors) {
     for (size_t r = 0; r < R; ++r)
         for (int k = 0; k < E; ++k) W0e[(((r / 64) * (Epad / 4) + k / 4) * 64 + r % 64) * 4 + k % 4] = W0[r * ld0 + 32 + k];
     int rc;
-    if ((rc = f->W0.upload(W0.data(), W0.size() * 4))) return rc;
     if ((rc = f->W0x.upload(W0x.data(), W0x.size() * 4))) return rc;
     if ((rc = f->W0e.upload(W0e.data(), W0e.size() * 4))) return rc;
-    if ((rc = f->b0.upload(b0.data(), b0.size() * 4))) return rc;
+    if ((rc = par.b0.upload(b0.data(), b0.size() * 4))) return rc;
     if ((rc = f->Wmid.upload(Wmid.data(), Wmid.size() * 4))) return rc;
-    if ((rc = f->bmid.upload(bmid.data(), bmid.size() * 4))) return rc;
+    if ((rc = par.bmid.upload(bmid.data(), bmid.size() * 4))) return rc;
     if ((rc = f->W3T.upload(W3T.data(), W3T.size() * 4))) return rc;
-    if ((rc = f->b3.upload(b3.data(), b3.size() * 4))) return rc;
-    if ((rc = f->an_loc.upload(loc.data(), loc.size() * 4))) return rc;
-    if ((rc = f->an_scale.upload(scale.data(), scale.size() * 4))) return rc;
-    if ((rc = f->shuf_f.upload(sf.data(), sf.size() * 4))) return rc;
-    if ((rc = f->shuf_b.upload(sb.data(), sb.size() * 4))) return rc;
+    if ((rc = par.b3.upload(b3.data(), b3.size() * 4))) return rc;
+    if ((rc = par.an_loc.upload(loc.data(), loc.size() * 4))) return rc;
+    if ((rc = par.an_scale.upload(scale.data(), scale.size() * 4))) return rc;
+    if ((rc = par.shuf_f.upload(sf.data(), sf.size() * 4))) return rc;
+    if ((rc = par.shuf_b.upload(sb.data(), sb.size() * 4))) return rc;
     f->tile.ok = false;
     I2V_REQUIRE(!f->cfg.linear_f16 || (f->tile_wanted && flow_tile_geometry_ok(f->cfg.in_channels, H, D, E)), I2V_E_INVALID,
                 "i2v_flow_load: linear_f16 needs the matrix-core tile chain (64 channels, hidden 128..512 in steps of 128, depth >= 1, E <= 128)");

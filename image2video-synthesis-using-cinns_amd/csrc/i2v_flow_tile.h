@@ -7,6 +7,7 @@
 // coalesced 16-byte load per lane and no transposition anywhere on the chain.
 #pragma once
 #include "i2v_common.h"
+#include "i2v_flow_sched.h"
 
 namespace i2v {
 
@@ -52,21 +53,22 @@ struct FlowTileWs {
 };
 FlowTileWs flow_tile_ws(const FlowTilePack& p, int B);
 
-struct FlowTileChain {
-    const FlowTilePack* pack;
-    const float* b0;     // [S][2H]
-    const float* bmid;   // [S][depth][2H]
-    const float* b3;     // [S][64]
-    const float* an_loc; const float* an_scale;   // [n_flows][64]
-    const float* an_logdet_host;                  // [n_flows] (host)
-    const int* shuf_f; const int* shuf_b;         // [n_flows][64]
-    const int* step_cond;                         // [S] (host): first layer sees only the embedding
-    int n_flows, use_an, use_act, use_shuf;
+// The per-pass parameters that are not weight matrices, owned by the i2v_flow handle (uploaded by i2v_flow_load) and read in place
+// by both launch chains.
+struct FlowParams {
+    DevBuf b0, bmid, b3;              // [S][2H], [S][depth][2H], [S][64]
+    DevBuf an_loc, an_scale;          // [n_flows][64]
+    DevBuf shuf_f, shuf_b;            // [n_flows][64] int
+    std::vector<float> an_logdet;     // [n_flows] (host): sum log|scale| of that ActNorm
+    std::vector<int> step_cond;       // [S] (host) 1: first layer sees only the embedding (mode 'cond')
+    int n_flows = 0;
+    bool use_an = true, use_act = true, use_shuf = true;
+    std::vector<FlowLink> schedule(bool reverse) const { return flow_schedule(n_flows, reverse, use_an, use_act, use_shuf); }
 };
 
 // enqueues the whole pass (pre-GEMM, 1 + S tail launches, S * depth hidden launches) on `st`; reads the caller's tensors
-// through pack->io (see flow_tile_set_io)
-int flow_tile_enqueue(const FlowTileChain& c, bool reverse, char* ws, int B, hipStream_t st);
+// through p.io (see flow_tile_set_io)
+int flow_tile_enqueue(const FlowTilePack& p, const FlowParams& par, bool reverse, char* ws, int B, hipStream_t st);
 // makes the device-side FlowIo match (launches a one-thread kernel on `st` only when something changed)
 int flow_tile_set_io(FlowTilePack& p, const FlowIo& io, hipStream_t st);
 

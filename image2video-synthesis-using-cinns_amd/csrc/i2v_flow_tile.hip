@@ -603,30 +603,41 @@ __global__ __launch_bounds__(512) void flow_first_tile_kernel(const float* WT_, 
 
 __global__ void flow_set_io_kernel(FlowIo* dst, FlowIo v) { *dst = v; }
 
-template <int KPW, bool F16>
-void launch_hid(const HidTileArgs& a, int ns, int groups, hipStream_t st) {
-    const dim3 grid(a.NRT * groups), block(512);
-    if (ns == 1) hipLaunchKernelGGL((flow_hid_tile_kernel<KPW, 1, F16>), grid, block, 0, st, a.WT, a.in, a.bias, a.out, a.W3P, a.P, a.NRT, a.NST, a.seq);
-    else if (ns == 2) hipLaunchKernelGGL((flow_hid_tile_kernel<KPW, 2, F16>), grid, block, 0, st, a.WT, a.in, a.bias, a.out, a.W3P, a.P, a.NRT, a.NST, a.seq);
-    else hipLaunchKernelGGL((flow_hid_tile_kernel<KPW, 4, F16>), grid, block, 0, st, a.WT, a.in, a.bias, a.out, a.W3P, a.P, a.NRT, a.NST, a.seq);
+// One launch of the hidden-layer geometry (grid NRT x sample-tile groups): the hidden layer `m` alone, or -- `t` given, the folded
+// chain -- with the tail in front of it in the same launch (t->h0 unused; t->W0T / pre / l1: the first Linear of m's half-step).
+template <int KPW, int NS, bool F16>
+void launch_layer(const HidTileArgs& m, const TailTileArgs* t, hipStream_t st) {
+    const dim3 grid(m.NRT * ((m.NST + NS - 1) / NS)), block(512);
+    if (!t) {
+        hipLaunchKernelGGL((flow_hid_tile_kernel<KPW, NS, F16>), grid, block, 0, st, m.WT, m.in, m.bias, m.out, m.W3P, m.P, m.NRT, m.NST, m.seq);
+        return;
+    }
+    const int flags = t->io_in | t->ld_init << 2 | t->reverse << 3 | t->do_lrelu << 4 | t->do_swap << 5 | t->l1 << 6;
+    hipLaunchKernelGGL((flow_first_tile_kernel<KPW, NS, F16>), grid, block, 0, st, m.WT, t->P, t->x, t->W0T, t->pre, m.bias, m.NRT, m.NST, flags,
+                       t->b3, t->io, t->xo, t->logdet, t->shuf, t->an_loc, t->an_scale, t->an_logdet, m.out, m.W3P, m.P, t->B, m.seq);
 }
 
-struct FirstTileArgs {
-    HidTileArgs m;      // the hidden layer (m.in unused)
-    TailTileArgs t;     // the tail in front of it (t.h0 unused; t.W0T / t.pre / t.l1: the first Linear of the hidden layer's half-step)
-};
-
+// (f16, kpw = HB / 8 in 1..4, ns in {1, 2, 4}) -> instantiation: the one place where the 24 variants of either kernel are selected
 template <int KPW, bool F16>
-void launch_first(const FirstTileArgs& a, int ns, int groups, hipStream_t st) {
-    const dim3 grid(a.m.NRT * groups), block(512);
-    const TailTileArgs& t = a.t;
-    const int flags = t.io_in | t.ld_init << 2 | t.reverse << 3 | t.do_lrelu << 4 | t.do_swap << 5 | t.l1 << 6;
-#define I2V_FIRST_ARGS a.m.WT, t.P, t.x, t.W0T, t.pre, a.m.bias, a.m.NRT, a.m.NST, flags, t.b3, t.io, t.xo, t.logdet, t.shuf, t.an_loc, t.an_scale, \
-                       t.an_logdet, a.m.out, a.m.W3P, a.m.P, t.B, a.m.seq
-    if (ns == 1) hipLaunchKernelGGL((flow_first_tile_kernel<KPW, 1, F16>), grid, block, 0, st, I2V_FIRST_ARGS);
-    else if (ns == 2) hipLaunchKernelGGL((flow_first_tile_kernel<KPW, 2, F16>), grid, block, 0, st, I2V_FIRST_ARGS);
-    else hipLaunchKernelGGL((flow_first_tile_kernel<KPW, 4, F16>), grid, block, 0, st, I2V_FIRST_ARGS);
-#undef I2V_FIRST_ARGS
+void launch_layer_ns(int ns, const HidTileArgs& m, const TailTileArgs* t, hipStream_t st) {
+    if (ns == 1) launch_layer<KPW, 1, F16>(m, t, st);
+    else if (ns == 2) launch_layer<KPW, 2, F16>(m, t, st);
+    else launch_layer<KPW, 4, F16>(m, t, st);
+}
+template <bool F16>
+void launch_layer_kpw(int kpw, int ns, const HidTileArgs& m, const TailTileArgs* t, hipStream_t st) {
+    switch (kpw) {
+        case 1: launch_layer_ns<1, F16>(ns, m, t, st); break;
+        case 2: launch_layer_ns<2, F16>(ns, m, t, st); break;
+        case 3: launch_layer_ns<3, F16>(ns, m, t, st); break;
+        default: launch_layer_ns<4, F16>(ns, m, t, st); break;
+    }
+}
+int launch_layer(bool f16, int kpw, int ns, const HidTileArgs& m, const TailTileArgs* t, hipStream_t st) {
+    if (f16) launch_layer_kpw<true>(kpw, ns, m, t, st);
+    else launch_layer_kpw<false>(kpw, ns, m, t, st);
+    I2V_HIP_CHECK(hipGetLastError());
+    return I2V_OK;
 }
 
 int env_int(const char* name, int dflt) {
@@ -723,12 +734,10 @@ int flow_tile_set_io(FlowTilePack& p, const FlowIo& io, hipStream_t st) {
     return I2V_OK;
 }
 
-int flow_tile_enqueue(const FlowTileChain& c, bool reverse, char* ws, int B, hipStream_t st) {
-    const FlowTilePack& p = *c.pack;
+int flow_tile_enqueue(const FlowTilePack& p, const FlowParams& par, bool reverse, char* ws, int B, hipStream_t st) {
     const FlowTileWs L = flow_tile_ws(p, B);
-    const int NST = (B + 15) / 16, NRT = p.NRT, HB = p.HB, S = p.S, D = p.depth, N2 = 2 * p.H, nf = c.n_flows;
+    const int NST = (B + 15) / 16, NRT = p.NRT, HB = p.HB, S = p.S, D = p.depth, N2 = 2 * p.H;
     float* xbuf[2] = {reinterpret_cast<float*>(ws + L.x), reinterpret_cast<float*>(ws + L.x2)};   // state, ping-pong per tail
-    int xcur = 0;
     float* logdet = reinterpret_cast<float*>(ws + L.logdet);
     float* pre = reinterpret_cast<float*>(ws + L.pre);
     float* hA = reinterpret_cast<float*>(ws + L.hA);
@@ -737,7 +746,6 @@ int flow_tile_enqueue(const FlowTileChain& c, bool reverse, char* ws, int B, hip
     const FlowIo* io = p.io.as<FlowIo>();
     int ns = NST <= 4 ? 1 : NST <= 8 ? 2 : 4;   // sample tiles per hidden-layer workgroup: keep ~256 workgroups
     if (const int e = p.force_ns) ns = e >= 4 ? 4 : e >= 2 ? 2 : 1;
-    const int groups = (NST + ns - 1) / ns;
     // Folded chain (the tail travels with the first hidden layer's launch: 82 launches per pass) or round 4's 122-launch chain.
     // Same bits either way (test_flow_fold_keeps_the_bits).  Every workgroup of a folded launch redoes the tail of its own sample
     // tiles (128 KB of partial tiles each), so it pays while a workgroup holds ONE sample tile (B <= 64: 508 -> 473 us at B = 64,
@@ -749,140 +757,70 @@ int flow_tile_enqueue(const FlowTileChain& c, bool reverse, char* ws, int B, hip
     {   // embedding part of every first layer of the pass
         PreTileArgs a{};
         a.seq = seq++;
-        a.W0E = p.W0E.as<float>(); a.b0 = c.b0; a.io = io; a.pre = pre;
+        a.W0E = p.W0E.as<float>(); a.b0 = par.b0.as<float>(); a.io = io; a.pre = pre;
         a.NRT = NRT; a.NST = NST; a.KE16 = p.KE16; a.E = p.E; a.B = B; a.Rtiles = S * NRT; a.nblk = (a.Rtiles + 7) / 8;
         if (p.f16) hipLaunchKernelGGL(flow_pre_tile_kernel<true>, dim3(a.nblk * ((NST + PRE_SC - 1) / PRE_SC)), dim3(512), 0, st, a);
         else hipLaunchKernelGGL(flow_pre_tile_kernel<false>, dim3(a.nblk * ((NST + PRE_SC - 1) / PRE_SC)), dim3(512), 0, st, a);
         I2V_HIP_CHECK(hipGetLastError());
     }
-    auto step_of = [&](int it) {  // forward visits (fl, i) = (0,0),(0,1),(1,0)...; reverse visits (nf-1,1),(nf-1,0),(nf-2,1)...
-        const int fl = reverse ? nf - 1 - it / 2 : it / 2;
-        const int i = reverse ? 1 - it % 2 : it % 2;
-        return fl * 2 + i;
-    };
     // hidden layer d of half-step `step`; its input in `cur`, its output in `nxt` (the last one writes partial products into Pout)
     auto hid_args = [&](int step, int d, const float* cur, float* nxt, float* Pout) {
         HidTileArgs m{};
         m.WT = reinterpret_cast<const float*>(p.WT.as<char>() + ((size_t)step * D + d) * NRT * HB * fb);
-        m.bias = c.bmid + ((size_t)step * D + d) * N2;
+        m.bias = par.bmid.as<float>() + ((size_t)step * D + d) * N2;
         m.in = cur;
         m.out = d == D - 1 ? nullptr : nxt;
         m.W3P = d == D - 1 ? reinterpret_cast<const float*>(p.W3P.as<char>() + (size_t)step * NRT * 2 * fb) : nullptr;
         m.P = Pout;
         m.NRT = NRT; m.NST = NST;
+        m.seq = seq++;
         return m;
     };
-    auto launch_hidden = [&](HidTileArgs m) -> int {
-        m.seq = seq++;
-        if (p.f16) {
-            switch (HB / 8) {
-                case 1: launch_hid<1, true>(m, ns, groups, st); break;
-                case 2: launch_hid<2, true>(m, ns, groups, st); break;
-                case 3: launch_hid<3, true>(m, ns, groups, st); break;
-                default: launch_hid<4, true>(m, ns, groups, st); break;
-            }
-        } else {
-            switch (HB / 8) {
-                case 1: launch_hid<1, false>(m, ns, groups, st); break;
-                case 2: launch_hid<2, false>(m, ns, groups, st); break;
-                case 3: launch_hid<3, false>(m, ns, groups, st); break;
-                default: launch_hid<4, false>(m, ns, groups, st); break;
-            }
-        }
-        I2V_HIP_CHECK(hipGetLastError());
-        return I2V_OK;
-    };
-    // the tail between two half-steps: coupling of `step` (partial products in Pin; null in front of the first half-step), block
-    // boundary ops, first Linear of next_step.  folded_hidden: the first hidden layer of next_step runs in the same launch.
-    auto tail = [&](const float* Pin, int step, int shuf_block, int an_block, bool lrelu, bool swap, int next_step, bool first, bool last,
-                    const HidTileArgs* folded_hidden) -> int {
+    // Walk the pass schedule (i2v_flow_sched.h).  Link `it` is the tail between two half-steps: coupling of k.step (the partial
+    // products that half-step it - 1 of the pass left in Pbuf[(it - 1) & 1]; none in front of the first half-step), block boundary
+    // ops, first Linear of k.next_step, which is half-step `it` of the pass; then that half-step's hidden layers.
+    const std::vector<FlowLink> links = par.schedule(reverse);
+    for (int it = 0; it <= S; ++it) {
+        const FlowLink& k = links[it];
         TailTileArgs t{};
-        t.P = Pin;
-        t.b3 = c.b3 + (size_t)step * 64;
-        t.x = xbuf[xcur]; t.xo = xbuf[xcur ^ 1];
-        xcur ^= 1;
+        t.P = k.step >= 0 ? Pbuf[(it - 1) & 1] : nullptr;
+        t.b3 = k.step >= 0 ? par.b3.as<float>() + (size_t)k.step * 64 : nullptr;
+        t.x = xbuf[it & 1]; t.xo = xbuf[(it & 1) ^ 1];
         t.logdet = reverse ? nullptr : logdet;
-        t.io = io; t.io_in = first ? 1 : 0; t.io_out = last ? 1 : 0; t.ld_init = first ? 1 : 0;
+        t.io = io; t.io_in = it == 0 ? 1 : 0; t.io_out = it == S ? 1 : 0; t.ld_init = it == 0 ? 1 : 0;
         t.B = B; t.NST = NST; t.NRT = NRT; t.HB2 = HB / 2; t.reverse = reverse ? 1 : 0;
-        t.shuf = shuf_block >= 0 ? (reverse ? c.shuf_b : c.shuf_f) + shuf_block * 64 : nullptr;
-        t.an_loc = an_block >= 0 ? c.an_loc + an_block * 64 : nullptr;
-        t.an_scale = an_block >= 0 ? c.an_scale + an_block * 64 : nullptr;
-        t.an_logdet = an_block >= 0 ? c.an_logdet_host[an_block] : 0.f;
-        t.do_lrelu = lrelu ? 1 : 0; t.do_swap = swap ? 1 : 0;
-        if (next_step >= 0) {
-            t.l1 = c.step_cond[next_step] ? 2 : 1;
-            t.W0T = reinterpret_cast<const float*>(p.W0T.as<char>() + (size_t)next_step * NRT * 2 * fb);
-            t.pre = pre + (size_t)next_step * NST * NRT * 256;
+        t.shuf = k.shuf_block >= 0 ? (reverse ? par.shuf_b : par.shuf_f).as<int>() + k.shuf_block * 64 : nullptr;
+        t.an_loc = k.an_block >= 0 ? par.an_loc.as<float>() + k.an_block * 64 : nullptr;
+        t.an_scale = k.an_block >= 0 ? par.an_scale.as<float>() + k.an_block * 64 : nullptr;
+        t.an_logdet = k.an_block >= 0 ? par.an_logdet[k.an_block] : 0.f;
+        t.do_lrelu = k.lrelu ? 1 : 0; t.do_swap = k.swap ? 1 : 0;
+        if (k.next_step >= 0) {
+            t.l1 = par.step_cond[k.next_step] ? 2 : 1;
+            t.W0T = reinterpret_cast<const float*>(p.W0T.as<char>() + (size_t)k.next_step * NRT * 2 * fb);
+            t.pre = pre + (size_t)k.next_step * NST * NRT * 256;
             t.h0 = hA;
         }
-        if (folded_hidden) {
-            FirstTileArgs fa{*folded_hidden, t};
-            fa.m.seq = seq++;
-            if (p.f16) {
-                switch (HB / 8) {
-                    case 1: launch_first<1, true>(fa, ns, groups, st); break;
-                    case 2: launch_first<2, true>(fa, ns, groups, st); break;
-                    case 3: launch_first<3, true>(fa, ns, groups, st); break;
-                    default: launch_first<4, true>(fa, ns, groups, st); break;
-                }
-            } else {
-                switch (HB / 8) {
-                    case 1: launch_first<1, false>(fa, ns, groups, st); break;
-                    case 2: launch_first<2, false>(fa, ns, groups, st); break;
-                    case 3: launch_first<3, false>(fa, ns, groups, st); break;
-                    default: launch_first<4, false>(fa, ns, groups, st); break;
-                }
-            }
+        // (folded: the hidden layer 0 of half-step next_step travels with the tail in front of it; its output goes where the
+        //  unfolded chain's layer 0 puts it -- hB -- or, when it is also the last hidden layer, into Pbuf[it & 1])
+        const bool folded = fold && k.next_step >= 0;
+        int rc;
+        if (folded) {
+            if ((rc = launch_layer(p.f16, HB / 8, ns, hid_args(k.next_step, 0, hA, hB, Pbuf[it & 1]), &t, st))) return rc;
+        } else {
+            t.seq = seq++;
+            const int flags = t.io_in | t.io_out << 1 | t.ld_init << 2 | t.reverse << 3 | t.do_lrelu << 4 | t.do_swap << 5 | t.l1 << 6;
+            auto tk = p.f16 ? flow_tail_tile_kernel<true> : flow_tail_tile_kernel<false>;
+            hipLaunchKernelGGL(tk, dim3((NST + 7) / 8 * 64), dim3(512), 0, st, t.P, t.x, t.W0T, t.pre, t.b3, t.NST, t.NRT, t.HB2,
+                               flags, t.io, t.xo, t.logdet, t.shuf, t.an_loc, t.an_scale, t.an_logdet, t.h0, t.B, t.seq);
             I2V_HIP_CHECK(hipGetLastError());
-            return I2V_OK;
         }
-        t.seq = seq++;
-        const int flags = t.io_in | t.io_out << 1 | t.ld_init << 2 | t.reverse << 3 | t.do_lrelu << 4 | t.do_swap << 5 | t.l1 << 6;
-        auto tk = p.f16 ? flow_tail_tile_kernel<true> : flow_tail_tile_kernel<false>;
-        hipLaunchKernelGGL(tk, dim3((NST + 7) / 8 * 64), dim3(512), 0, st, t.P, t.x, t.W0T, t.pre, t.b3, t.NST, t.NRT, t.HB2,
-                           flags, t.io, t.xo, t.logdet, t.shuf, t.an_loc, t.an_scale, t.an_logdet, t.h0, t.B, t.seq);
-        I2V_HIP_CHECK(hipGetLastError());
-        return I2V_OK;
-    };
-    const bool act = c.use_act, an = c.use_an, sh = c.use_shuf;
-    int rc;
-    // (folded: the hidden layer 0 of half-step step_of(it) travels with the tail in front of it; its output goes where the
-    //  unfolded chain's layer 0 puts it -- hB -- or, when it is also the last hidden layer, into Pbuf[it & 1])
-    HidTileArgs h0a = hid_args(step_of(0), 0, hA, hB, Pbuf[0]);
-    if (!reverse) rc = tail(nullptr, 0, -1, an ? 0 : -1, act, false, step_of(0), true, false, fold ? &h0a : nullptr);
-    else rc = tail(nullptr, 0, sh ? nf - 1 : -1, -1, false, false, step_of(0), true, false, fold ? &h0a : nullptr);
-    if (rc) return rc;
-    for (int it = 0; it < S; ++it) {
-        const int fl = reverse ? nf - 1 - it / 2 : it / 2;
-        const int i = reverse ? 1 - it % 2 : it % 2;
-        const int step = fl * 2 + i;
-        const int next_step = it + 1 < S ? step_of(it + 1) : -1;
+        if (k.next_step < 0) break;
         float* cur = hA;
         float* nxt = hB;
         for (int d = 0; d < D; ++d) {
-            if (!(fold && d == 0) && (rc = launch_hidden(hid_args(step, d, cur, nxt, Pbuf[it & 1])))) return rc;
+            if (!(folded && d == 0) && (rc = launch_layer(p.f16, HB / 8, ns, hid_args(k.next_step, d, cur, nxt, Pbuf[it & 1]), nullptr, st))) return rc;
             std::swap(cur, nxt);
         }
-        int shuf_block = -1, an_block = -1;
-        bool lrelu = false, swap = false;
-        if (!reverse) {
-            if (i == 0) swap = true;  // before half-step 1: cat(chunk[::-1]), flow_blocks.py:86
-            else {
-                if (sh) shuf_block = fl;
-                if (fl + 1 < nf) { if (an) an_block = fl + 1; lrelu = act; }
-            }
-        } else {
-            if (i == 1) swap = true;  // before half-step 0 (flow_blocks.py:98-99)
-            else {
-                lrelu = act;
-                if (an) an_block = fl;
-                if (fl - 1 >= 0 && sh) shuf_block = fl - 1;
-            }
-        }
-        HidTileArgs hn{};
-        const bool folded = fold && next_step >= 0;
-        if (folded) hn = hid_args(next_step, 0, hA, hB, Pbuf[(it + 1) & 1]);
-        if ((rc = tail(Pbuf[it & 1], step, shuf_block, an_block, lrelu, swap, next_step, false, it == S - 1, folded ? &hn : nullptr))) return rc;
     }
     return I2V_OK;
 }

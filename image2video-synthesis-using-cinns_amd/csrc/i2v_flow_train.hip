@@ -487,10 +487,7 @@ int i2v_flow_train_create(const i2v_flow_cfg* cfg, i2v_flow_train** out) {
     I2V_HIP_CHECK(hipGetDevice(&f->device));
     f->nfl = cfg->n_flows; f->S = 2 * cfg->n_flows; f->H = cfg->hidden_dim; f->depth = cfg->hidden_depth; f->E = cfg->embedding_dim;
     f->step_cond.resize(f->S);
-    for (int st = 0; st < f->S; ++st) {
-        const int fl = st / 2;
-        f->step_cond[st] = cfg->control == 2 || (cfg->control == 1 && fl % 4 != 0);   // flow_blocks.py:24
-    }
+    for (int st = 0; st < f->S; ++st) f->step_cond[st] = flow_block_cond(cfg->control, st / 2);
     *out = f;
     return I2V_OK;
 }
@@ -526,8 +523,7 @@ int i2v_flow_train_bind(i2v_flow_train* f, const i2v_tensor* params, const i2v_t
         for (int net = 0; net < 2; ++net) {
             for (int l = 0; l < nl; ++l) {
                 const int M = l == nl - 1 ? 32 : H, K = l == 0 ? kin : H;
-                const std::string base = "sub_layers." + std::to_string(fl) + ".coupling." + (net ? "t." : "s.") + std::to_string(i) +
-                                         ".main." + std::to_string(2 * l);
+                const std::string base = flow_linear_key(fl, net, i, l);
                 const float* W = P.f32(base + ".weight", (int64_t)M * K);
                 if (!W) return I2V_E_MISSING;
                 const float* b = P.f32(base + ".bias", M);
