@@ -406,6 +406,16 @@ struct i2v_i3d {
 
 namespace {
 
+// SAME padding in front and output dims of a conv unit with kernel (k, k, k) and stride (s, s, s) on a [T][H][W] map: the size % stride
+// rule on time only (Kinetics), on every dimension (dynamic-texture variant)
+void unit_geom(const i2v_i3d* net, int k, int s, Dims d, int* pT, int* pH, int* pW, Dims* o) {
+    int bT, bH, bW;
+    same_pad(k, s, s > 1 ? d.T % s : 0, pT, &bT);
+    same_pad(k, s, net->dt && s > 1 ? d.H % s : 0, pH, &bH);
+    same_pad(k, s, net->dt && s > 1 ? d.W % s : 0, pW, &bW);
+    *o = Dims{(d.T + *pT + bT - k) / s + 1, (d.H + *pH + bH - k) / s + 1, (d.W + *pW + bW - k) / s + 1};
+}
+
 // One walk of the network serves the workspace size (dry: no buffers, no launches) and the forward.
 struct Walk {
     const i2v_i3d* net;
@@ -435,6 +445,13 @@ struct Walk {
         return I2V_OK;
     }
 
+    // One conv unit at stride (s, s, s) with its own SAME padding (unit_geom); returns the output dims
+    int unit(const Unit& u, int s, const float* in, int inCS, int inOff, Dims di, float* out, int outCS, int outOff, bool relu, Dims* dout) {
+        int pT, pH, pW;
+        unit_geom(net, u.K, s, di, &pT, &pH, &pW, dout);
+        return conv(u, in, inCS, inOff, di, out, outCS, outOff, *dout, s, s, pT, pH, relu, pW);
+    }
+
     // MaxPool3dTFPadding(kernel (kT, k, k), stride (sT, s, s)); returns the output dims
     int pool(const float* in, float* out, int C, Dims di, int kT, int k, int sT, int s, Dims* dout) {
         I3dPoolArgs a{};
@@ -454,6 +471,43 @@ struct Walk {
 
     void need(size_t* slot, long floats) { *slot = std::max(*slot, (size_t)floats); }
 
+    static int mixed_out(int i) { return MIXED[i].o[0] + MIXED[i].o[2] + MIXED[i].o[4] + MIXED[i].o[5]; }
+
+    // Mixed block i: x [B][d][cin] -> y [B][d][Co]; tmp holds one branch temporary at a time
+    int mixed(int i, const float* x, Dims d, float* y, float* tmp) {
+        int rc;
+        const MixedSpec& s = MIXED[i];
+        const Unit* u = net->mixed[i];
+        const int C = s.cin, Co = mixed_out(i);
+        need(&act_floats, (long)B * d.pos() * Co);
+        need(&tmp_floats, (long)B * d.pos() * std::max(std::max(s.o[1], s.o[3]), C));
+        // the branches store into their channel slice of y (torch.cat((out_0, out_1, out_2, out_3), 1))
+        if ((rc = conv(u[0], x, C, 0, d, y, Co, 0, d, 1, 1, 0, 0, true))) return rc;
+        if ((rc = conv(u[1], x, C, 0, d, tmp, s.o[1], 0, d, 1, 1, 0, 0, true))) return rc;
+        if ((rc = conv(u[2], tmp, s.o[1], 0, d, y, Co, s.o[0], d, 1, 1, 1, 1, true))) return rc;
+        if ((rc = conv(u[3], x, C, 0, d, tmp, s.o[3], 0, d, 1, 1, 0, 0, true))) return rc;
+        if ((rc = conv(u[4], tmp, s.o[3], 0, d, y, Co, s.o[0] + s.o[2], d, 1, 1, 1, 1, true))) return rc;
+        Dims po;
+        if ((rc = pool(x, tmp, C, d, 3, 3, 1, 1, &po))) return rc;
+        return conv(u[5], tmp, C, 0, d, y, Co, s.o[0] + s.o[2] + s.o[4], d, 1, 1, 0, 0, true);
+    }
+
+    // AvgPool3d((pool_t, 7, 7)) on x [B][T][7][7][1024] -> pooled [B][T'][1024], conv3d_0c_1x1 -> cls [B][T'][classes], time mean -> logits;
+    // with `features` only the pool, stored as [B][1024][T'] into logits
+    int head(const float* x, int T, float* pooled, float* cls, float* logits, bool features) {
+        const int kT = net->pool_t;
+        hipLaunchKernelGGL(i3d_avgpool_kernel, dim3(grid_for((long)B * (T - kT + 1) * 1024)), dim3(256), 0, st, x, features ? logits : pooled, B,
+                           T, 1024, kT, features ? 1 : 0);
+        I2V_HIP_CHECK(hipGetLastError());
+        if (features) return I2V_OK;
+        const Dims dh{T - kT + 1, 1, 1};
+        if (int rc = conv(net->head, pooled, 1024, 0, dh, cls, net->num_classes, 0, dh, 1, 1, 0, 0, false)) return rc;   // conv3d_0c_1x1
+        hipLaunchKernelGGL(i3d_time_mean_kernel, dim3(grid_for((long)B * net->num_classes)), dim3(256), 0, st, cls, logits, B, dh.T,
+                           net->num_classes);
+        I2V_HIP_CHECK(hipGetLastError());
+        return I2V_OK;
+    }
+
     // frames -> logits, or with `features` -> the average pool's output [B][1024][T'] in `logits` (no classifier, no time mean).
     // T frames enter the network, frame t read from source frame t % Tin.  inp / x / y / tmp / pooled / cls: workspace buffers (null when dry)
     int run(const float* frames, int Tin, int T, int H, int W, int denorm, float* inp, float* x, float* y, float* tmp, float* pooled, float* cls,
@@ -467,13 +521,9 @@ struct Walk {
         }
         // conv3d_1a_7x7: stride 2, SAME = (2, 3) per dimension, (3, 3) in time for an odd T (and, by the dynamic-texture variant's rule, in
         // an odd spatial dimension: none at 224)
-        int pT, bT, pH, bH, pW, bW;
-        same_pad(7, 2, T % 2, &pT, &bT);
-        same_pad(7, 2, net->dt ? d.H % 2 : 0, &pH, &bH);
-        same_pad(7, 2, net->dt ? d.W % 2 : 0, &pW, &bW);
-        Dims o{(T + pT + bT - 7) / 2 + 1, (d.H + pH + bH - 7) / 2 + 1, (d.W + pW + bW - 7) / 2 + 1};
+        Dims o;
+        if ((rc = unit(net->stem, 2, inp, 4, 0, d, x, 64, 0, true, &o))) return rc;
         need(&act_floats, (long)B * o.pos() * 64);
-        if ((rc = conv(net->stem, inp, 4, 0, d, x, 64, 0, o, 2, 2, pT, pH, true, pW))) return rc;
         d = o;
         if ((rc = pool(x, y, 64, d, 1, 3, 1, 2, &o))) return rc;                              // maxPool3d_2a_3x3
         d = o;
@@ -484,22 +534,9 @@ struct Walk {
         d = o;
         int C = 192;
         for (int i = 0; i < 9; ++i) {
-            const MixedSpec& s = MIXED[i];
-            const Unit* u = net->mixed[i];
-            const int Co = s.o[0] + s.o[2] + s.o[4] + s.o[5];
-            need(&act_floats, (long)B * d.pos() * Co);
-            need(&tmp_floats, (long)B * d.pos() * std::max(std::max(s.o[1], s.o[3]), C));
-            // the branches store into their channel slice of y (torch.cat((out_0, out_1, out_2, out_3), 1))
-            if ((rc = conv(u[0], x, C, 0, d, y, Co, 0, d, 1, 1, 0, 0, true))) return rc;
-            if ((rc = conv(u[1], x, C, 0, d, tmp, s.o[1], 0, d, 1, 1, 0, 0, true))) return rc;
-            if ((rc = conv(u[2], tmp, s.o[1], 0, d, y, Co, s.o[0], d, 1, 1, 1, 1, true))) return rc;
-            if ((rc = conv(u[3], x, C, 0, d, tmp, s.o[3], 0, d, 1, 1, 0, 0, true))) return rc;
-            if ((rc = conv(u[4], tmp, s.o[3], 0, d, y, Co, s.o[0] + s.o[2], d, 1, 1, 1, 1, true))) return rc;
-            Dims po;
-            if ((rc = pool(x, tmp, C, d, 3, 3, 1, 1, &po))) return rc;
-            if ((rc = conv(u[5], tmp, C, 0, d, y, Co, s.o[0] + s.o[2] + s.o[4], d, 1, 1, 0, 0, true))) return rc;
+            if ((rc = mixed(i, x, d, y, tmp))) return rc;
             std::swap(x, y);
-            C = Co;
+            C = mixed_out(i);
             if (i == 1) { if ((rc = pool(x, y, C, d, 3, 3, 2, 2, &o))) return rc; d = o; std::swap(x, y); }   // maxPool3d_4a_3x3
             if (i == 6) { if ((rc = pool(x, y, C, d, 2, 2, 2, 2, &o))) return rc; d = o; std::swap(x, y); }   // maxPool3d_5a_2x2
         }
@@ -509,16 +546,7 @@ struct Walk {
                     8 * (kT - 1) + 1);
         *t_head = d.T - kT + 1;
         if (dry) return I2V_OK;
-        hipLaunchKernelGGL(i3d_avgpool_kernel, dim3(grid_for((long)B * (d.T - kT + 1) * 1024)), dim3(256), 0, st, x, features ? logits : pooled, B,
-                           d.T, 1024, kT, features ? 1 : 0);
-        I2V_HIP_CHECK(hipGetLastError());
-        if (features) return I2V_OK;
-        const Dims dh{d.T - kT + 1, 1, 1};
-        if ((rc = conv(net->head, pooled, 1024, 0, dh, cls, net->num_classes, 0, dh, 1, 1, 0, 0, false))) return rc;   // conv3d_0c_1x1
-        hipLaunchKernelGGL(i3d_time_mean_kernel, dim3(grid_for((long)B * net->num_classes)), dim3(256), 0, st, cls, logits, B, dh.T,
-                           net->num_classes);
-        I2V_HIP_CHECK(hipGetLastError());
-        return I2V_OK;
+        return head(x, d.T, pooled, cls, logits, features);
     }
 };
 
@@ -671,6 +699,140 @@ int i2v_i3d_features(i2v_i3d* n, const float* frames, int32_t batch, int32_t t_i
     Walk wk{n, batch, false, st};
     int th = 0;
     return wk.run(frames, t_in, t_out, h, w, denorm ? 1 : 0, F(L.inp), F(L.x), F(L.y), F(L.tmp), nullptr, nullptr, feats, &th, true);
+}
+
+// ---- sub-modules of a loaded handle, individually callable on channels-last tensors (for tests and inspection)
+
+namespace {
+// unit index -> the unit and its stride; null for an unknown index
+const Unit* i3d_unit(const i2v_i3d* n, int unit, int* stride) {
+    *stride = unit == I2V_I3D_UNIT_STEM ? 2 : 1;
+    if (unit == I2V_I3D_UNIT_STEM) return &n->stem;
+    if (unit == I2V_I3D_UNIT_2B) return &n->c2b;
+    if (unit == I2V_I3D_UNIT_2C) return &n->c2c;
+    if (unit == I2V_I3D_UNIT_HEAD) return &n->head;
+    if (unit >= I2V_I3D_UNIT_MIXED && unit < I2V_I3D_UNIT_MIXED + 54) return &n->mixed[(unit - I2V_I3D_UNIT_MIXED) / 6][(unit - I2V_I3D_UNIT_MIXED) % 6];
+    return nullptr;
+}
+constexpr long I3D_SUB_MAX = 1L << 31;   // floats per tensor of a sub-module call
+}  // namespace
+
+int i2v_i3d_unit_shape(const i2v_i3d* n, int32_t unit, int32_t t, int32_t h, int32_t w, int32_t* cin, int32_t* cout, int32_t* out_dims) {
+    I2V_REQUIRE(n, I2V_E_INVALID, "i2v_i3d_unit_shape: null handle");
+    I2V_REQUIRE(n->loaded, I2V_E_STATE, "i2v_i3d_unit_shape: weights not loaded");
+    int s;
+    const Unit* u = i3d_unit(n, unit, &s);
+    I2V_REQUIRE(u && t > 0 && h > 0 && w > 0, I2V_E_INVALID, "i2v_i3d_unit_shape: unit %d on a [%d, %d, %d] map", unit, t, h, w);
+    int pT, pH, pW;
+    Dims o;
+    unit_geom(n, u->K, s, Dims{t, h, w}, &pT, &pH, &pW, &o);
+    if (cin) *cin = 4 * u->C4;
+    if (cout) *cout = u->Cout;
+    if (out_dims) { out_dims[0] = o.T; out_dims[1] = o.H; out_dims[2] = o.W; }
+    return I2V_OK;
+}
+
+int i2v_i3d_unit_forward(i2v_i3d* n, int32_t unit, const float* x, int32_t batch, int32_t t, int32_t h, int32_t w, int32_t in_cs, float* out,
+                         int32_t out_cs, int32_t out_off, size_t out_floats, void* stream) {
+    I2V_REQUIRE(n, I2V_E_INVALID, "i2v_i3d_unit_forward: null handle");
+    I2V_REQUIRE_DEVICE(n->device, "i2v_i3d_unit_forward");
+    I2V_REQUIRE(n && n->loaded, I2V_E_STATE, "i2v_i3d_unit_forward: weights not loaded");
+    int s;
+    const Unit* u = i3d_unit(n, unit, &s);
+    I2V_REQUIRE(u, I2V_E_INVALID, "i2v_i3d_unit_forward: unknown unit %d", unit);
+    I2V_REQUIRE(x && out && batch > 0 && t > 0 && h > 0 && w > 0, I2V_E_INVALID, "i2v_i3d_unit_forward: bad argument");
+    I2V_REQUIRE(in_cs > 0 && in_cs % 4 == 0 && in_cs >= 4 * u->C4 && out_cs > 0 && out_off >= 0 && out_off + u->Cout <= out_cs, I2V_E_INVALID,
+                "i2v_i3d_unit_forward: channels [0, %d) of %d -> [%d, +%d) of %d do not fit", 4 * u->C4, in_cs, out_off, u->Cout, out_cs);
+    int pT, pH, pW;
+    Dims o;
+    unit_geom(n, u->K, s, Dims{t, h, w}, &pT, &pH, &pW, &o);
+    I2V_REQUIRE((long)batch * t * h * w * in_cs < I3D_SUB_MAX && (long)batch * o.pos() * out_cs < I3D_SUB_MAX, I2V_E_INVALID,
+                "i2v_i3d_unit_forward: batch %d x [%d, %d, %d] is too large", batch, t, h, w);
+    I2V_REQUIRE(out_floats >= (size_t)batch * o.pos() * out_cs, I2V_E_WORKSPACE, "i2v_i3d_unit_forward: output of %zu floats < required %zu",
+                out_floats, (size_t)batch * o.pos() * out_cs);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rco = n->order.entry(st)) return rco;
+    StreamOrderMark mark{&n->order, st};
+    Walk wk{n, batch, false, st};
+    return wk.unit(*u, s, x, in_cs, 0, Dims{t, h, w}, out, out_cs, out_off, unit != I2V_I3D_UNIT_HEAD, &o);
+}
+
+size_t i2v_i3d_mixed_workspace_bytes(const i2v_i3d* n, int32_t block, int32_t batch, int32_t t, int32_t h, int32_t w) {
+    if (!n || block < 0 || block >= 9 || batch <= 0 || t <= 0 || h <= 0 || w <= 0) return 0;
+    Walk wk{n, batch, true, nullptr};
+    if (wk.mixed(block, nullptr, Dims{t, h, w}, nullptr, nullptr)) return 0;
+    return align_up(wk.tmp_floats * 4, 256);
+}
+
+int i2v_i3d_mixed_forward(i2v_i3d* n, int32_t block, const float* x, int32_t batch, int32_t t, int32_t h, int32_t w, float* out, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+    I2V_REQUIRE(n, I2V_E_INVALID, "i2v_i3d_mixed_forward: null handle");
+    I2V_REQUIRE_DEVICE(n->device, "i2v_i3d_mixed_forward");
+    I2V_REQUIRE(n && n->loaded, I2V_E_STATE, "i2v_i3d_mixed_forward: weights not loaded");
+    I2V_REQUIRE(block >= 0 && block < 9, I2V_E_INVALID, "i2v_i3d_mixed_forward: unknown block %d", block);
+    I2V_REQUIRE(x && out && workspace && batch > 0 && t > 0 && h > 0 && w > 0, I2V_E_INVALID, "i2v_i3d_mixed_forward: bad argument");
+    I2V_REQUIRE((long)batch * t * h * w * 1024 < I3D_SUB_MAX, I2V_E_INVALID, "i2v_i3d_mixed_forward: batch %d x [%d, %d, %d] is too large", batch, t, h,
+                w);
+    const size_t need = i2v_i3d_mixed_workspace_bytes(n, block, batch, t, h, w);
+    I2V_REQUIRE(workspace_bytes >= need, I2V_E_WORKSPACE, "i2v_i3d_mixed_forward: workspace %zu < required %zu", workspace_bytes, need);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rco = n->order.entry(st)) return rco;
+    StreamOrderMark mark{&n->order, st};
+    Walk wk{n, batch, false, st};
+    return wk.mixed(block, x, Dims{t, h, w}, out, static_cast<float*>(workspace));
+}
+
+int i2v_i3d_maxpool_shape(const i2v_i3d* n, int32_t kt, int32_t k, int32_t st, int32_t s, int32_t t, int32_t h, int32_t w, int32_t* out_dims) {
+    I2V_REQUIRE(n && out_dims && kt > 0 && k > 0 && st > 0 && s > 0 && t > 0 && h > 0 && w > 0, I2V_E_INVALID, "i2v_i3d_maxpool_shape: bad argument");
+    Walk wk{n, 1, true, nullptr};
+    Dims o;
+    if (int rc = wk.pool(nullptr, nullptr, 4, Dims{t, h, w}, kt, k, st, s, &o)) return rc;
+    out_dims[0] = o.T; out_dims[1] = o.H; out_dims[2] = o.W;
+    return I2V_OK;
+}
+
+int i2v_i3d_maxpool_forward(i2v_i3d* n, const float* x, int32_t batch, int32_t t, int32_t h, int32_t w, int32_t c, int32_t kt, int32_t k, int32_t st,
+                            int32_t s, float* out, size_t out_floats, void* stream) {
+    I2V_REQUIRE(n, I2V_E_INVALID, "i2v_i3d_maxpool_forward: null handle");
+    I2V_REQUIRE_DEVICE(n->device, "i2v_i3d_maxpool_forward");
+    I2V_REQUIRE(x && out && batch > 0 && t > 0 && h > 0 && w > 0 && kt > 0 && k > 0 && st > 0 && s > 0, I2V_E_INVALID,
+                "i2v_i3d_maxpool_forward: bad argument");
+    I2V_REQUIRE(c > 0 && c % 4 == 0, I2V_E_INVALID, "i2v_i3d_maxpool_forward: %d channels (a multiple of 4 is needed)", c);
+    int od[3];
+    if (int rc = i2v_i3d_maxpool_shape(n, kt, k, st, s, t, h, w, od)) return rc;
+    I2V_REQUIRE(od[0] > 0 && od[1] > 0 && od[2] > 0 && (long)batch * t * h * w * c < I3D_SUB_MAX && (long)batch * od[0] * od[1] * od[2] * c < I3D_SUB_MAX,
+                I2V_E_INVALID, "i2v_i3d_maxpool_forward: batch %d x [%d, %d, %d] x %d", batch, t, h, w, c);
+    const size_t need = (size_t)batch * od[0] * od[1] * od[2] * c;
+    I2V_REQUIRE(out_floats >= need, I2V_E_WORKSPACE, "i2v_i3d_maxpool_forward: output of %zu floats < required %zu", out_floats, need);
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    if (int rco = n->order.entry(hs)) return rco;
+    StreamOrderMark mark{&n->order, hs};
+    Walk wk{n, batch, false, hs};
+    Dims o;
+    return wk.pool(x, out, c, Dims{t, h, w}, kt, k, st, s, &o);
+}
+
+size_t i2v_i3d_head_workspace_bytes(const i2v_i3d* n, int32_t batch, int32_t t) {
+    if (!n || batch <= 0 || t < n->pool_t) return 0;
+    return align_up((size_t)batch * (t - n->pool_t + 1) * n->num_classes * 4, 256);
+}
+
+int i2v_i3d_head_forward(i2v_i3d* n, const float* x, int32_t batch, int32_t t, float* pooled, float* feats, float* logits, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+    I2V_REQUIRE(n, I2V_E_INVALID, "i2v_i3d_head_forward: null handle");
+    I2V_REQUIRE_DEVICE(n->device, "i2v_i3d_head_forward");
+    I2V_REQUIRE(n && n->loaded, I2V_E_STATE, "i2v_i3d_head_forward: weights not loaded");
+    I2V_REQUIRE(x && pooled && feats && logits && workspace && batch > 0, I2V_E_INVALID, "i2v_i3d_head_forward: bad argument");
+    I2V_REQUIRE(t >= n->pool_t && (long)batch * t * 49 * 1024 < I3D_SUB_MAX, I2V_E_INVALID,
+                "i2v_i3d_head_forward: %d time steps in front of AvgPool3d((%d, 7, 7)), batch %d", t, n->pool_t, batch);
+    const size_t need = i2v_i3d_head_workspace_bytes(n, batch, t);
+    I2V_REQUIRE(workspace_bytes >= need, I2V_E_WORKSPACE, "i2v_i3d_head_forward: workspace %zu < required %zu", workspace_bytes, need);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rco = n->order.entry(st)) return rco;
+    StreamOrderMark mark{&n->order, st};
+    Walk wk{n, batch, false, st};
+    if (int rc = wk.head(x, t, nullptr, nullptr, feats, true)) return rc;
+    return wk.head(x, t, pooled, static_cast<float*>(workspace), logits, false);
 }
 
 int i2v_i3d_input_stage(const float* frames, int32_t n_frames, int32_t h, int32_t w, int32_t denorm, float* out, void* stream) {

@@ -122,6 +122,16 @@ SYMBOLS = {
     "i2v_i3d_features": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_size_t,
                                    c_void_p]),
     "i2v_diversity_update": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "i2v_i3d_unit_shape": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),
+    "i2v_i3d_unit_forward": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_size_t,
+                                       c_void_p]),
+    "i2v_i3d_mixed_workspace_bytes": (c_size_t, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "i2v_i3d_mixed_forward": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "i2v_i3d_maxpool_shape": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32)]),
+    "i2v_i3d_maxpool_forward": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
+                                          c_size_t, c_void_p]),
+    "i2v_i3d_head_workspace_bytes": (c_size_t, [c_void_p, c_int32, c_int32]),
+    "i2v_i3d_head_forward": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "i2v_dec_create": (c_int32, [POINTER(DecCfg), POINTER(c_void_p)]),
     "i2v_dec_destroy": (None, [c_void_p]),
     "i2v_dec_load": (c_int32, [c_void_p, POINTER(_Tensor), c_int32]),
@@ -1131,6 +1141,86 @@ class NativeI3D(_Handle):
         _check(lib().i2v_i3d_features(self._h, frames.data_ptr(), B, T, t_out, H, W, int(bool(denorm)), out.data_ptr(), ws.data_ptr(),
                                       ws.numel(), _stream()), "i2v_i3d_features")
         return out
+
+    # ---- sub-modules on channels-last tensors [B, T, H, W, C] (tests and inspection)
+    UNIT_STEM, UNIT_2B, UNIT_2C, UNIT_MIXED, UNIT_HEAD = 0, 1, 2, 3, 57
+
+    @staticmethod
+    def _require_cl(x, what):
+        _require_gpu(x)
+        if x.dim() != 5 or x.dtype != torch.float32 or not x.is_contiguous():
+            raise I2VError(f"{what}: expected a contiguous fp32 tensor [B,T,H,W,C], got {tuple(x.shape)} {x.dtype}")
+
+    def unit_shape(self, unit, t, h, w):
+        """``i2v_i3d_unit_shape``: (cin, cout, (To, Ho, Wo)) of conv unit ``unit`` on a [t, h, w] map."""
+        cin, cout, od = c_int32(), c_int32(), (c_int32 * 3)()
+        _check(lib().i2v_i3d_unit_shape(self._h, unit, t, h, w, ctypes.byref(cin), ctypes.byref(cout), od), "i2v_i3d_unit_shape")
+        return cin.value, cout.value, tuple(od)
+
+    @_on_device
+    def unit_forward(self, unit, x, out=None, out_off=0):
+        """``i2v_i3d_unit_forward``: x [B, T, H, W, in_cs] -> channels [out_off, out_off + cout) of ``out`` [B, To, Ho, Wo, out_cs] (a new
+        tensor of cout channels when None)."""
+        self._require_cl(x, "i3d unit")
+        B, T, H, W, cs = x.shape
+        _, cout, od = self.unit_shape(unit, T, H, W)
+        if out is None:
+            out = torch.empty(B, *od, cout, dtype=torch.float32, device=x.device)
+        self._require_cl(out, "i3d unit")
+        if tuple(out.shape[:4]) != (B, *od):
+            raise I2VError(f"i3d unit: expected an output [{B},{od[0]},{od[1]},{od[2]},C], got {tuple(out.shape)}")
+        _check(lib().i2v_i3d_unit_forward(self._h, unit, x.data_ptr(), B, T, H, W, cs, out.data_ptr(), out.shape[4], out_off, out.numel(),
+                                          _stream()), "i2v_i3d_unit_forward")
+        return out
+
+    @_on_device
+    def mixed_forward(self, block, x):
+        """``i2v_i3d_mixed_forward``: Mixed block ``block`` (0 = 3b .. 8 = 5c) on x [B, T, H, W, cin] -> [B, T, H, W, Co]."""
+        self._require_cl(x, "i3d mixed")
+        B, T, H, W, cs = x.shape
+        cin = self.unit_shape(self.UNIT_MIXED + 6 * block, T, H, W)[0]
+        if cs != cin:
+            raise I2VError(f"i3d mixed: block {block} reads {cin} channels, got {cs}")
+        co = sum(self.unit_shape(self.UNIT_MIXED + 6 * block + j, T, H, W)[1] for j in (0, 2, 4, 5))
+        ws = self._ws.get(lib().i2v_i3d_mixed_workspace_bytes(self._h, block, B, T, H, W), x.device)
+        out = torch.empty(B, T, H, W, co, dtype=torch.float32, device=x.device)
+        _check(lib().i2v_i3d_mixed_forward(self._h, block, x.data_ptr(), B, T, H, W, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+               "i2v_i3d_mixed_forward")
+        return out
+
+    def maxpool_shape(self, kernel, stride, t, h, w):
+        """``i2v_i3d_maxpool_shape``: (To, Ho, Wo) of the max pool (kT, k, k) / (sT, s, s) on a [t, h, w] map."""
+        od = (c_int32 * 3)()
+        _check(lib().i2v_i3d_maxpool_shape(self._h, kernel[0], kernel[1], stride[0], stride[1], t, h, w, od), "i2v_i3d_maxpool_shape")
+        return tuple(od)
+
+    @_on_device
+    def maxpool_forward(self, x, kernel, stride):
+        """``i2v_i3d_maxpool_forward``: the variant's SAME-padded ceil-mode max pool (kT, k, k) / (sT, s, s) on x [B, T, H, W, C]."""
+        self._require_cl(x, "i3d maxpool")
+        B, T, H, W, C = x.shape
+        od = self.maxpool_shape(kernel, stride, T, H, W)
+        out = torch.empty(B, *od, C, dtype=torch.float32, device=x.device)
+        _check(lib().i2v_i3d_maxpool_forward(self._h, x.data_ptr(), B, T, H, W, C, kernel[0], kernel[1], stride[0], stride[1], out.data_ptr(),
+                                             out.numel(), _stream()), "i2v_i3d_maxpool_forward")
+        return out
+
+    @_on_device
+    def head_forward(self, x):
+        """``i2v_i3d_head_forward``: x [B, T, 7, 7, 1024] -> (pooled [B, T', 1024], feats [B, 1024, T'], logits [B, num_classes])."""
+        self._require_cl(x, "i3d head")
+        B, T = x.shape[:2]
+        nbytes = lib().i2v_i3d_head_workspace_bytes(self._h, B, T)
+        if tuple(x.shape[2:]) != (7, 7, 1024) or nbytes == 0:
+            raise I2VError(f"i3d head: expected [B,T,7,7,1024] with at least the average pool's time steps, got {tuple(x.shape)}")
+        tp = T - (4 if self.dt_length == 32 else 2) + 1
+        ws = self._ws.get(nbytes, x.device)
+        pooled = torch.empty(B, tp, 1024, dtype=torch.float32, device=x.device)
+        feats = torch.empty(B, 1024, tp, dtype=torch.float32, device=x.device)
+        logits = torch.empty(B, self.num_classes, dtype=torch.float32, device=x.device)
+        _check(lib().i2v_i3d_head_forward(self._h, x.data_ptr(), B, T, pooled.data_ptr(), feats.data_ptr(), logits.data_ptr(), ws.data_ptr(),
+                                          ws.numel(), _stream()), "i2v_i3d_head_forward")
+        return pooled, feats, logits
 
 
 def fvd_stats_update(feats, total, gram):

@@ -424,6 +424,42 @@ int i2v_i3d_features(i2v_i3d* n, const float* frames, int32_t batch, int32_t t_i
 int i2v_diversity_update(const float* embed, int32_t n, int32_t r, int32_t d, double* acc, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * I3D sub-modules, individually callable on a LOADED i2v_i3d handle (either variant) at a caller-chosen batch, t, h, w -- for
+ * tests and inspection.  Tensors are channels-last fp32 on the device, [B][T][H][W][C].  The padding and shape arithmetic is the
+ * code the whole-network walk runs: Kinetics rule (size % stride on time only) or dynamic-texture rule (on every dimension) by
+ * the handle's variant.  Bad arguments return I2V_E_INVALID, a short output or workspace I2V_E_WORKSPACE, before any launch.
+ * ---------------------------------------------------------------------------------------- */
+/* Unit index: stem (7x7x7, stride 2; its input carries 4 channels r, g, b, 0), conv3d_2b_1x1, conv3d_2c_3x3, the six units of
+ * Mixed block i in {0 = 3b .. 8 = 5c} as I2V_I3D_UNIT_MIXED + 6 i + j (j: branch_0, branch_1.0, branch_1.1, branch_2.0,
+ * branch_2.1, branch_3.1), the classifier conv3d_0c_1x1 / logits (bias, no BatchNorm, no ReLU). */
+#define I2V_I3D_UNIT_STEM 0
+#define I2V_I3D_UNIT_2B 1
+#define I2V_I3D_UNIT_2C 2
+#define I2V_I3D_UNIT_MIXED 3
+#define I2V_I3D_UNIT_HEAD 57
+/* cin: input channels the unit reads (a multiple of 4), cout, out_dims[3] = (To, Ho, Wo) on a [t][h][w] map; each may be NULL. */
+int i2v_i3d_unit_shape(const i2v_i3d* n, int32_t unit, int32_t t, int32_t h, int32_t w, int32_t* cin, int32_t* cout, int32_t* out_dims);
+/* x [B][t][h][w][in_cs] (channels [0, cin) are read) -> channels [out_off, out_off + cout) of out [B][To][Ho][Wo][out_cs]; the
+ * other channels of out are left as they are.  out_floats: the capacity of out. */
+int i2v_i3d_unit_forward(i2v_i3d* n, int32_t unit, const float* x, int32_t batch, int32_t t, int32_t h, int32_t w, int32_t in_cs, float* out,
+                         int32_t out_cs, int32_t out_off, size_t out_floats, void* stream);
+/* Mixed block (0 = mixed_3b .. 8 = mixed_5c): x [B][t][h][w][cin] -> out [B][t][h][w][Co], the six convs, the 3x3x3 / 1 max pool,
+ * the branch temporaries and the four slice stores as the network runs them. */
+size_t i2v_i3d_mixed_workspace_bytes(const i2v_i3d* n, int32_t block, int32_t batch, int32_t t, int32_t h, int32_t w);
+int i2v_i3d_mixed_forward(i2v_i3d* n, int32_t block, const float* x, int32_t batch, int32_t t, int32_t h, int32_t w, float* out, void* workspace,
+                          size_t workspace_bytes, void* stream);
+/* Max pool (kt, k, k) / (st, s, s) with the variant's SAME zero padding, ceil mode: out_dims[3] = (To, Ho, Wo); x [B][t][h][w][c]
+ * (c % 4 == 0) -> out [B][To][Ho][Wo][c].  out_floats: the capacity of out. */
+int i2v_i3d_maxpool_shape(const i2v_i3d* n, int32_t kt, int32_t k, int32_t st, int32_t s, int32_t t, int32_t h, int32_t w, int32_t* out_dims);
+int i2v_i3d_maxpool_forward(i2v_i3d* n, const float* x, int32_t batch, int32_t t, int32_t h, int32_t w, int32_t c, int32_t kt, int32_t k, int32_t st,
+                            int32_t s, float* out, size_t out_floats, void* stream);
+/* Head on x [B][t][7][7][1024] with T' = t - pool_t + 1: the average pool in both layouts (pooled [B][T'][1024], feats
+ * [B][1024][T'] as i2v_i3d_features returns it), then the classifier and the time mean -> logits [B][num_classes]. */
+size_t i2v_i3d_head_workspace_bytes(const i2v_i3d* n, int32_t batch, int32_t t);
+int i2v_i3d_head_forward(i2v_i3d* n, const float* x, int32_t batch, int32_t t, float* pooled, float* feats, float* logits, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Motion encoder of the transfer path (row N3): Encoder.forward -- stage1_VAE/modules/resnet3D.py:138-219
  * (3D ResNet-18, GroupNorm(16), conv_mu / conv_var).  Model.transfer (get_model.py:87) uses mu.
  * Keys: conv1.weight, norm1.*, layer.{L}.{i}.{conv1,conv2}.weight, .bn{1,2}.*, .downsample.{0.weight,1.*},
