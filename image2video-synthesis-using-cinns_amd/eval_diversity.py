@@ -5,21 +5,22 @@
 
 ``-n_realiz`` videos are sampled per start frame and the mean squared distance between their features is reported.  Built: ``-DTI3D``
 (the features of the dynamic-texture I3D, metrics/Diversity/I3D.py ``compute_DTI3D_diversity``, on the device; the length-32 network
-when ``-seq_length > 16``); it prints the reference's line.  ``-I3D`` (Kinetics I3D through TF-hub) and ``-VGG`` (torchvision VGG) exit
-with a "not built" message.
+when ``-seq_length > 16``); it prints the reference's line.  ``-I3D`` (Kinetics I3D through TF-hub) exits with a "not built" message.
 
 The reference's data package is out of scope, so the start frames come from ``-clips_npy FILE``: ``[N, T, 3, H, W]`` (frame 0 of every
 clip is used, as the reference uses ``seq[:, 0]``) or ``[N, 3, H, W]``, float in [-1, 1].  The reference runs ``-n_realiz`` passes over
 the loader; here the realizations of a batch come from ONE ``Model.sample(x_0, n_realiz)`` call (the start-frame work is done once) and
 stay on the device as [F, R, T, 3, H, W], so the residuals are drawn frame-major instead of pass-major: the same distribution, other
-draws.  ``-i3d_path`` overrides the I3D checkpoint, ``-seed`` the reference's fixed 249; ``-embed_npy`` / ``-embed_seed`` / ``-dec_mma`` as
+draws.  ``-VGG True -vgg_path FILE`` (torchvision's vgg16 state_dict file; nothing is downloaded) runs ``compute_vgg_diversity`` on the same
+videos with the native VGG-16 trunk; without ``-vgg_path`` it exits with the "not built" message.  ``-i3d_path`` overrides the I3D checkpoint, ``-seed`` the reference's fixed 249; ``-embed_npy`` / ``-embed_seed`` / ``-dec_mma`` as
 in ``generate_samples.py``."""
 import argparse
 import os
 import sys
 
-NOT_BUILT = {"I3D": "the Kinetics-I3D diversity embeds with the TensorFlow FVD's TF-hub module (metrics/FVD), which is not built",
-             "VGG": "the VGG diversity needs torchvision's VGG-16 graph and ImageNet weights, which are not part of this package"}
+NOT_BUILT = {"I3D": "the Kinetics-I3D diversity embeds with the TensorFlow FVD's TF-hub module (metrics/FVD), which is not built"}
+NEEDS_PATHS = {"VGG": (("vgg_path",), "the VGG diversity needs torchvision's VGG-16 ImageNet weights, which are not part of this package: pass "
+                                      "-vgg_path FILE (torchvision's vgg16 state_dict, vgg16-397923af.pth)")}
 
 
 def parse(argv=None):
@@ -33,10 +34,11 @@ def parse(argv=None):
     parser.add_argument('-n_realiz', type=int, default=5, help='How many samples should be generated for each test instance')
     parser.add_argument('-bs', type=int, default=6, help='Batchsize')
     parser.add_argument('-I3D', type=bool, help='Evaluation using kinetics I3D backbone (not built)')
-    parser.add_argument('-VGG', type=bool, help='Evaluation using VGG backbone (not built)')
+    parser.add_argument('-VGG', type=bool, help='Evaluation using VGG backbone (needs -vgg_path)')
     parser.add_argument('-DTI3D', type=bool, help='Evaluation using DTDB I3D backbone')
     parser.add_argument('-clips_npy', type=str, help="start frames: clips [N, T, 3, H, W] (frame 0 is used) or [N, 3, H, W], in [-1, 1]")
     parser.add_argument('-i3d_path', type=str, help="checkpoint of the dynamic-texture I3D (I3D_16.pth.tar / I3D_32.pth.tar)")
+    parser.add_argument('-vgg_path', type=str, help="torchvision vgg16 state_dict file (vgg16-397923af.pth) for -VGG; never downloaded")
     parser.add_argument('-seed', type=int, default=249, help="seed of the latent residuals (the reference fixes 249)")
     parser.add_argument('-embed_npy', type=str, help="[N,E] conditioning embeddings (one row per start frame)")
     parser.add_argument('-embed_seed', type=int, help="draw synthetic conditioning embeddings with this seed")
@@ -45,8 +47,12 @@ def parse(argv=None):
     for flag, why in NOT_BUILT.items():
         if getattr(args, flag):
             raise SystemExit(f"eval_diversity: -{flag} is not built: {why}")
-    if not args.DTI3D:
-        raise SystemExit("eval_diversity: nothing to evaluate -- pass -DTI3D True (the only score of this script that is built)")
+    for flag, (paths, why) in NEEDS_PATHS.items():
+        if getattr(args, flag) and not all(getattr(args, p) for p in paths):
+            raise SystemExit(f"eval_diversity: -{flag} is not built: {why}")
+    if not args.DTI3D and not args.VGG:
+        raise SystemExit("eval_diversity: nothing to evaluate -- pass -DTI3D True or -VGG True -vgg_path FILE (the scores of this script that "
+                         "are built)")
     if args.n_realiz < 2:
         parser.error("-n_realiz must be >= 2: the score compares the samples of one start frame with each other")
     if not args.clips_npy:
@@ -88,8 +94,15 @@ def main(argv=None):
     seq1 = torch.cat(seq_fake)
     del model
 
-    I3D = DTFVD_Score.load_model(length=32 if args.seq_length > 16 else 16, path=args.i3d_path).cuda()
-    return compute_DTI3D_diversity(seq1, I3D)
+    result = None
+    if args.VGG:
+        from metrics.Diversity.VGG import compute_vgg_diversity
+        from stage2_cINN.AE.modules.vgg16 import vgg16
+        result = compute_vgg_diversity(seq1, vgg16(path=args.vgg_path).cuda())
+    if args.DTI3D:
+        I3D = DTFVD_Score.load_model(length=32 if args.seq_length > 16 else 16, path=args.i3d_path).cuda()
+        result = compute_DTI3D_diversity(seq1, I3D)
+    return result
 
 
 if __name__ == "__main__":

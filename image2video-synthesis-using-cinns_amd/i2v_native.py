@@ -132,6 +132,19 @@ SYMBOLS = {
                                           c_size_t, c_void_p]),
     "i2v_i3d_head_workspace_bytes": (c_size_t, [c_void_p, c_int32, c_int32]),
     "i2v_i3d_head_forward": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "i2v_vgg_create": (c_int32, [POINTER(c_void_p)]),
+    "i2v_vgg_destroy": (None, [c_void_p]),
+    "i2v_vgg_load": (c_int32, [c_void_p, POINTER(_Tensor), c_int32]),
+    "i2v_vgg_lin": (c_void_p, [c_void_p, c_int32]),
+    "i2v_vgg_workspace_bytes": (c_size_t, [c_void_p, c_int32, c_int32, c_int32]),
+    "i2v_vgg_input_stage": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "i2v_vgg_features": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_size_t, c_void_p]),
+    "i2v_vgg_conv_unit": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "i2v_vgg_maxpool2": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "i2v_vgg_reduce_workspace_bytes": (c_size_t, [c_int32]),
+    "i2v_lpips_layer": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "i2v_vgg_pairdiff_update": (c_int32, [c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
     "i2v_dec_create": (c_int32, [POINTER(DecCfg), POINTER(c_void_p)]),
     "i2v_dec_destroy": (None, [c_void_p]),
     "i2v_dec_load": (c_int32, [c_void_p, POINTER(_Tensor), c_int32]),
@@ -1258,3 +1271,166 @@ def i3d_input_stage(frames, denorm):
     with torch.cuda.device(frames.device):
         _check(lib().i2v_i3d_input_stage(frames.data_ptr(), n, h, w, int(bool(denorm)), out.data_ptr(), _stream()), "i2v_i3d_input_stage")
     return out
+
+
+VGG_TAPS = ("relu1_2", "relu2_2", "relu3_3", "relu4_3", "relu5_3")
+VGG_TAP_CHANNELS = (64, 128, 256, 512, 512)
+VGG_INPUT_LPIPS, VGG_INPUT_DIVERSITY = 0, 1
+
+
+def _require_cl4(x, what):
+    _require_gpu(x)
+    if x.dim() != 4:
+        raise I2VError(f"{what}: expected a contiguous fp32 channels-last tensor [N,H,W,C], got {tuple(x.shape)}")
+
+
+def _reduce_ws(n, device):
+    return torch.empty(lib().i2v_vgg_reduce_workspace_bytes(n), dtype=torch.uint8, device=device)
+
+
+def _require_f64(t, shape, device, what):
+    if not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous() or tuple(t.shape) != shape or t.device != device:
+        raise I2VError(f"{what}: expected a contiguous float64 device tensor of shape {shape}")
+
+
+class NativeVGG(_Handle):
+    """Handle for ``i2v_vgg_*``: the VGG-16 ``features`` trunk of stage2_cINN/AE/modules/vgg16.py up to relu5_3, with the ``lin`` weights of
+    LPIPS.py when the state_dict has them."""
+
+    def __init__(self, device=None):
+        h = c_void_p()
+        with self._bind(device):
+            _check(lib().i2v_vgg_create(ctypes.byref(h)), "i2v_vgg_create")
+        self._h = h
+        self._ws = _Workspace()
+        self.has_lin = False
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.i2v_vgg_destroy(self._h)
+            self._h = None
+
+    @_on_device
+    def load(self, state_dict):
+        """torchvision keys ``features.N.{weight,bias}`` and, optionally, ``lin{0..4}.model.1.weight``; every other key is ignored."""
+        sd = {k: v for k, v in state_dict.items() if k.startswith("features.") or (k.startswith("lin") and k.endswith(".model.1.weight"))}
+        arr, keep = _pack_state_dict(sd)
+        _check(lib().i2v_vgg_load(self._h, arr, len(arr)), "i2v_vgg_load")
+        del keep
+        self.has_lin = bool(lib().i2v_vgg_lin(self._h, 0))
+
+    @staticmethod
+    def tap_shapes(n, h, w):
+        """Channels-last shapes [N, H', W', C] of the five taps for an [h, w] input."""
+        return [(n, h >> k, w >> k, c) for k, c in enumerate(VGG_TAP_CHANNELS)]
+
+    @_on_device
+    def features(self, x, out=None):
+        """``i2v_vgg_features``: x [N, H, W, 4] channels-last (``vgg_input_stage``) -> the five taps, channels-last [N, H', W', C].  ``out``:
+        five caller-owned tensors of those shapes (the call only enqueues: it can be captured into a graph)."""
+        _require_cl4(x, "vgg features")
+        n, h, w, c = x.shape
+        nbytes = lib().i2v_vgg_workspace_bytes(self._h, n, h, w) if c == 4 else 0
+        if nbytes == 0:
+            raise I2VError(f"vgg features: expected [N,H,W,4] with H, W >= 16 (four pools), got {tuple(x.shape)}")
+        ws = self._ws.get(nbytes, x.device)
+        shapes = self.tap_shapes(n, h, w)
+        if out is None:
+            out = [torch.empty(s, dtype=torch.float32, device=x.device) for s in shapes]
+        for t, s in zip(out, shapes):
+            _require_gpu(t)
+            if tuple(t.shape) != s:
+                raise I2VError(f"vgg features: expected a tap of shape {s}, got {tuple(t.shape)}")
+        _check(lib().i2v_vgg_features(self._h, x.data_ptr(), n, h, w, *[t.data_ptr() for t in out], ws.data_ptr(), ws.numel(), _stream()),
+               "i2v_vgg_features")
+        return list(out)
+
+    @_on_device
+    def lpips(self, taps0, taps1):
+        """Sum over the five layers of ``i2v_lpips_layer`` with the loaded ``lin`` weights: taps of two image batches -> float64 [N]."""
+        if not self.has_lin:
+            raise I2VError("lpips: the handle was loaded without lin{0..4}.model.1.weight")
+        n = taps0[0].shape[0]
+        out = torch.zeros(n, dtype=torch.float64, device=taps0[0].device)
+        ws = _reduce_ws(n, out.device)
+        for k, (a, b) in enumerate(zip(taps0, taps1)):
+            _require_cl4(a, "lpips")
+            _require_cl4(b, "lpips")
+            if a.shape != b.shape:
+                raise I2VError(f"lpips: taps of different shapes {tuple(a.shape)} / {tuple(b.shape)}")
+            _check(lib().i2v_lpips_layer(a.data_ptr(), b.data_ptr(), lib().i2v_vgg_lin(self._h, k), n, a.shape[1] * a.shape[2], a.shape[3],
+                                         out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "i2v_lpips_layer")
+        return out
+
+
+def vgg_input_stage(frames, mode, size=None, align_corners=False):
+    """``i2v_vgg_input_stage``: frames [N, 3, H, W] in [-1, 1] on the device -> channels-last [N, Ho, Wo, 4] (channel 3 zero).  ``mode``
+    VGG_INPUT_LPIPS: ScalingLayer, no resize; VGG_INPUT_DIVERSITY: ImageNet normalisation, then bilinear to ``size``."""
+    _require_gpu(frames)
+    if frames.dim() != 4 or frames.shape[1] != 3:
+        raise I2VError(f"vgg_input_stage: expected frames [N,3,H,W], got {tuple(frames.shape)}")
+    n, _, h, w = frames.shape
+    ho, wo = (h, w) if size is None else size
+    out = torch.empty(n, ho, wo, 4, dtype=torch.float32, device=frames.device)
+    with torch.cuda.device(frames.device):
+        _check(lib().i2v_vgg_input_stage(frames.data_ptr(), n, h, w, mode, ho, wo, int(bool(align_corners)), out.data_ptr(), _stream()),
+               "i2v_vgg_input_stage")
+    return out
+
+
+def vgg_conv_unit(x, weight, bias):
+    """``i2v_vgg_conv_unit``: x [N, H, W, cin] channels-last on the device (cin = 3: [N, H, W, 4]), host ``weight`` [cout, cin, 3, 3] and
+    ``bias`` [cout] -> relu(conv + bias) [N, H, W, cout]."""
+    _require_cl4(x, "vgg_conv_unit")
+    w = np.ascontiguousarray(weight.detach().cpu().numpy() if isinstance(weight, torch.Tensor) else weight, dtype=np.float32)
+    b = np.ascontiguousarray(bias.detach().cpu().numpy() if isinstance(bias, torch.Tensor) else bias, dtype=np.float32)
+    if w.ndim != 4 or w.shape[2:] != (3, 3) or b.shape != (w.shape[0],):
+        raise I2VError(f"vgg_conv_unit: expected weight [cout,cin,3,3] and bias [cout], got {w.shape} / {b.shape}")
+    cout, cin = w.shape[:2]
+    n, h, wd, cs = x.shape
+    if cs != (4 if cin == 3 else cin):
+        raise I2VError(f"vgg_conv_unit: {cin} input channels need a tensor of {4 if cin == 3 else cin} stored channels, got {cs}")
+    out = torch.empty(n, h, wd, cout, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _check(lib().i2v_vgg_conv_unit(x.data_ptr(), w.ctypes.data_as(c_void_p), b.ctypes.data_as(c_void_p), n, h, wd, cin, cout, out.data_ptr(),
+                                       _stream()), "i2v_vgg_conv_unit")
+    return out
+
+
+def vgg_maxpool2(x):
+    """``i2v_vgg_maxpool2``: MaxPool2d(2, 2) in floor mode on x [N, H, W, C] channels-last."""
+    _require_cl4(x, "vgg_maxpool2")
+    n, h, w, c = x.shape
+    out = torch.empty(n, h // 2, w // 2, c, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _check(lib().i2v_vgg_maxpool2(x.data_ptr(), n, h, w, c, out.data_ptr(), _stream()), "i2v_vgg_maxpool2")
+    return out
+
+
+def lpips_layer(f0, f1, lin, out):
+    """``out`` [N] (float64, device) += the LPIPS term of one layer (``i2v_lpips_layer``): f0, f1 [N, H, W, C] channels-last taps, lin [C]."""
+    _require_cl4(f0, "lpips_layer")
+    _require_cl4(f1, "lpips_layer")
+    _require_gpu(lin)
+    n, h, w, c = f0.shape
+    if f1.shape != f0.shape or tuple(lin.shape) != (c,):
+        raise I2VError(f"lpips_layer: shapes {tuple(f0.shape)} / {tuple(f1.shape)} / {tuple(lin.shape)}")
+    _require_f64(out, (n,), f0.device, "lpips_layer")
+    ws = _reduce_ws(n, f0.device)
+    with torch.cuda.device(f0.device):
+        _check(lib().i2v_lpips_layer(f0.data_ptr(), f1.data_ptr(), lin.data_ptr(), n, h * w, c, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+               "i2v_lpips_layer")
+
+
+def vgg_pairdiff_update(maps, acc):
+    """``acc`` [2] (float64, device) += (sum over ordered pairs i != j of mean (f_i - f_j)^2, R (R - 1)) of ``maps`` [R, ...] fp32
+    (``i2v_vgg_pairdiff_update``)."""
+    _require_gpu(maps)
+    if maps.dim() < 2:
+        raise I2VError(f"vgg_pairdiff_update: expected maps [R, ...], got {tuple(maps.shape)}")
+    _require_f64(acc, (2,), maps.device, "vgg_pairdiff_update")
+    r = maps.shape[0]
+    ws = _reduce_ws(1, maps.device)
+    with torch.cuda.device(maps.device):
+        _check(lib().i2v_vgg_pairdiff_update(maps.data_ptr(), r, maps.numel() // r, acc.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+               "i2v_vgg_pairdiff_update")

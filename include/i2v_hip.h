@@ -460,6 +460,55 @@ int i2v_i3d_head_forward(i2v_i3d* n, const float* x, int32_t batch, int32_t t, f
                          size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * VGG-16 feature trunk, LPIPS and the VGG diversity score (csrc/i2v_vgg.hip) -- stage2_cINN/AE/modules/vgg16.py (vgg16.forward
+ * :30-42: the `features` trunk of torchvision's configuration D cut into five slices), stage2_cINN/AE/modules/LPIPS.py (LPIPS.forward
+ * :38-52, ScalingLayer :55-62, NetLinLayer :65-72) and metrics/Diversity/VGG.py (compute_vgg_diversity :9-47).
+ * Thirteen 3x3 convolutions (stride 1, pad 1, bias, ReLU) in exact fp32 on the matrix cores and four MaxPool2d(2, 2); activations
+ * are channels-last [N][H][W][C], the 3-channel input is stored as 4 channels (r, g, b, 0).  Single stream: every call only
+ * enqueues on `stream` (i2v_vgg_conv_unit excepted) and can be captured into a graph.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct i2v_vgg i2v_vgg;
+#define I2V_VGG_INPUT_LPIPS 0      /* (x - shift) / scale: ScalingLayer, LPIPS.py:55-62; no resize */
+#define I2V_VGG_INPUT_DIVERSITY 1  /* ((x + 1) / 2 - mean) / std with the ImageNet constants, then bilinear: metrics/Diversity/VGG.py:20-21, 29, 36 */
+/* vgg16.__init__ (vgg16.py:7-28) */
+int i2v_vgg_create(i2v_vgg** out);
+void i2v_vgg_destroy(i2v_vgg* v);
+/* torchvision keys features.{0,2,5,7,10,12,14,17,19,21,24,26,28}.{weight [Cout][Cin][3][3], bias [Cout]} (other keys, the classifier
+ * among them, are ignored) and, optionally, all five lin{0..4}.model.1.weight [1][C][1][1] of LPIPS.py:18-22.  Packed once, here. */
+int i2v_vgg_load(i2v_vgg* v, const i2v_tensor* tensors, int32_t n_tensors);
+/* Device pointer to the loaded lin{layer} weights [C] (NULL: none loaded, or layer outside 0..4). */
+const float* i2v_vgg_lin(const i2v_vgg* v, int32_t layer);
+/* Workspace of i2v_vgg_features; 0 when h or w is below 16 (a pool would leave an empty map). */
+size_t i2v_vgg_workspace_bytes(const i2v_vgg* v, int32_t batch, int32_t h, int32_t w);
+/* frames [n][3][hi][wi] fp32 in [-1, 1] -> out [n][ho][wo][4] channels-last (channel 3 zero).  Every source pixel is normalised by
+ * `mode`, then sampled bilinearly in the arithmetic of torch's upsample_bilinear2d with `align_corners` (the reference's order:
+ * resize(normalize(x))).  I2V_VGG_INPUT_LPIPS needs ho = hi and wo = wi; at equal sizes the sample IS the normalised pixel. */
+int i2v_vgg_input_stage(const float* frames, int32_t n, int32_t hi, int32_t wi, int32_t mode, int32_t ho, int32_t wo, int32_t align_corners,
+                        float* out, void* stream);
+/* vgg16.forward (vgg16.py:30-42): x [batch][h][w][4] -> the five taps, caller-owned and channels-last: relu1_2 [batch][h][w][64],
+ * relu2_2 [..][h/2][w/2][128], relu3_3 [..][h/4][w/4][256], relu4_3 [..][h/8][w/8][512], relu5_3 [..][h/16][w/16][512] (floor). */
+int i2v_vgg_features(i2v_vgg* v, const float* x, int32_t batch, int32_t h, int32_t w, float* relu1_2, float* relu2_2, float* relu3_3, float* relu4_3,
+                     float* relu5_3, void* workspace, size_t workspace_bytes, void* stream);
+/* One convolution of the trunk's kind from raw weights [cout][cin][3][3] and bias [cout] (HOST pointers): x [n][h][w][cin] -> out
+ * [n][h][w][cout] with bias and ReLU.  cin = 3 reads x as [n][h][w][4]; every other cin is a multiple of 16, cout a multiple of 64;
+ * anything else is refused.  Packs per call and synchronises the stream: for the unit tests (nn.Conv2d(3, padding=1) + ReLU). */
+int i2v_vgg_conv_unit(const float* x, const float* weight, const float* bias, int32_t n, int32_t h, int32_t w, int32_t cin, int32_t cout, float* out,
+                      void* stream);
+/* nn.MaxPool2d(kernel_size=2, stride=2), floor mode: x [n][h][w][c] -> out [n][h/2][w/2][c]; c a multiple of 4. */
+int i2v_vgg_maxpool2(const float* x, int32_t n, int32_t h, int32_t w, int32_t c, float* out, void* stream);
+/* Bytes of the partial-sum workspace that i2v_lpips_layer needs for n images; i2v_vgg_pairdiff_update needs what n = 1 gives. */
+size_t i2v_vgg_reduce_workspace_bytes(int32_t n);
+/* One layer of LPIPS.forward (LPIPS.py:44-48; normalize_tensor and spatial_average of vgg16.py:45-52): f0, f1 [n][p][c] fp32
+ * channels-last taps, lin [c] (device):  out[i] += mean_p sum_c lin_c (f0 / (|f0| + 1e-10) - f1 / (|f1| + 1e-10))^2 for image i,
+ * |.| the norm over c, in float64.  Both maps are read once; two fixed-order stages, no atomics.  c in {64, 128, 256, 512}. */
+int i2v_lpips_layer(const float* f0, const float* f1, const float* lin, int32_t n, int32_t p, int32_t c, double* out, void* workspace,
+                    size_t workspace_bytes, void* stream);
+/* The pair loop of metrics/Diversity/VGG.py:38-43 for one layer of one group: maps [r][d] fp32 (r realizations, 2..16):
+ * acc[0] += sum_{i != j} mean_d (f_i - f_j)^2, acc[1] += r (r - 1) -- the convention of i2v_diversity_update -- in float64; every
+ * element is read once; two fixed-order stages, no atomics. */
+int i2v_vgg_pairdiff_update(const float* maps, int32_t r, int64_t d, double* acc, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Motion encoder of the transfer path (row N3): Encoder.forward -- stage1_VAE/modules/resnet3D.py:138-219
  * (3D ResNet-18, GroupNorm(16), conv_mu / conv_var).  Model.transfer (get_model.py:87) uses mu.
  * Keys: conv1.weight, norm1.*, layer.{L}.{i}.{conv1,conv2}.weight, .bn{1,2}.*, .downsample.{0.weight,1.*},
