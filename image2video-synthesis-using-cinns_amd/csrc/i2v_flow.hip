@@ -581,6 +581,21 @@ size_t i2v_flow_workspace_bytes(const i2v_flow* f, int32_t batch) {
 
 size_t i2v_flow_param_bytes(const i2v_flow* f) { return f ? f->param_bytes : 0; }
 
+int i2v_flow_plan(const i2v_flow* f, int32_t batch, int32_t* chain, int32_t* kpw, int32_t* ns, int32_t* fold) {
+    I2V_REQUIRE(f && chain && kpw && ns && fold, I2V_E_INVALID, "i2v_flow_plan: null argument");
+    I2V_REQUIRE(batch > 0, I2V_E_INVALID, "i2v_flow_plan: batch must be positive, got %d", batch);
+    I2V_REQUIRE(f->loaded, I2V_E_STATE, "i2v_flow_plan: weights not loaded (the chain is chosen at load)");
+    *chain = f->tile.ok ? 1 : 0;
+    *kpw = *ns = *fold = 0;
+    if (f->tile.ok) {
+        const FlowTilePlan plan = flow_tile_plan(f->tile, batch);
+        *kpw = plan.kpw;
+        *ns = plan.ns;
+        *fold = plan.fold ? 1 : 0;
+    }
+    return I2V_OK;
+}
+
 int i2v_flow_forward(i2v_flow* f, const float* x, const float* embed, float* zt, float* logdet, void* workspace,
                      size_t workspace_bytes, int32_t batch, void* stream) {
     I2V_REQUIRE(f && logdet, I2V_E_INVALID, "i2v_flow_forward: null argument");

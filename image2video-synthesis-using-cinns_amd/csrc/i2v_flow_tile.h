@@ -66,6 +66,15 @@ struct FlowParams {
     std::vector<FlowLink> schedule(bool reverse) const { return flow_schedule(n_flows, reverse, use_an, use_act, use_shuf); }
 };
 
+// What flow_tile_enqueue launches at batch B: the hidden-layer instantiation (kpw = H / 128 k-blocks per wave, ns = sample tiles per
+// workgroup: 1 up to 4 sample tiles, 2 up to 8, else 4; I2V_FLOW_NS forces) and whether the tail travels folded into the first hidden
+// layer's launch (default: iff ns == 1; I2V_FLOW_FOLD forces).  The one copy of the rule: the launcher calls it, i2v_flow_plan reports it.
+struct FlowTilePlan {
+    int kpw, ns;
+    bool fold;
+};
+FlowTilePlan flow_tile_plan(const FlowTilePack& p, int B);
+
 // enqueues the whole pass (pre-GEMM, 1 + S tail launches, S * depth hidden launches) on `st`; reads the caller's tensors
 // through p.io (see flow_tile_set_io)
 int flow_tile_enqueue(const FlowTilePack& p, const FlowParams& par, bool reverse, char* ws, int B, hipStream_t st);

@@ -734,6 +734,20 @@ int flow_tile_set_io(FlowTilePack& p, const FlowIo& io, hipStream_t st) {
     return I2V_OK;
 }
 
+FlowTilePlan flow_tile_plan(const FlowTilePack& p, int B) {
+    const int NST = (B + 15) / 16;
+    FlowTilePlan plan;
+    plan.kpw = p.HB / 8;
+    plan.ns = NST <= 4 ? 1 : NST <= 8 ? 2 : 4;   // sample tiles per hidden-layer workgroup: keep ~256 workgroups
+    if (const int e = p.force_ns) plan.ns = e >= 4 ? 4 : e >= 2 ? 2 : 1;
+    // Folded chain (the tail travels with the first hidden layer's launch: 82 launches per pass) or round 4's 122-launch chain.
+    // Same bits either way (test_flow_fold_keeps_the_bits).  Every workgroup of a folded launch redoes the tail of its own sample
+    // tiles (128 KB of partial tiles each), so it pays while a workgroup holds ONE sample tile (B <= 64: 508 -> 473 us at B = 64,
+    // 460 -> 439 at B = 8) and loses with four (B = 256: 765 -> 1083 us): default = folded iff ns == 1.  I2V_FLOW_FOLD=0|1 (read when the weights are packed) forces.
+    plan.fold = (p.force_fold >= 0 ? p.force_fold : (plan.ns == 1 ? 1 : 0)) != 0;
+    return plan;
+}
+
 int flow_tile_enqueue(const FlowTilePack& p, const FlowParams& par, bool reverse, char* ws, int B, hipStream_t st) {
     const FlowTileWs L = flow_tile_ws(p, B);
     const int NST = (B + 15) / 16, NRT = p.NRT, HB = p.HB, S = p.S, D = p.depth, N2 = 2 * p.H;
@@ -744,13 +758,9 @@ int flow_tile_enqueue(const FlowTilePack& p, const FlowParams& par, bool reverse
     float* hB = reinterpret_cast<float*>(ws + L.hB);
     float* Pbuf[2] = {reinterpret_cast<float*>(ws + L.P), reinterpret_cast<float*>(ws + L.P2)};   // half-step `it` writes Pbuf[it & 1]
     const FlowIo* io = p.io.as<FlowIo>();
-    int ns = NST <= 4 ? 1 : NST <= 8 ? 2 : 4;   // sample tiles per hidden-layer workgroup: keep ~256 workgroups
-    if (const int e = p.force_ns) ns = e >= 4 ? 4 : e >= 2 ? 2 : 1;
-    // Folded chain (the tail travels with the first hidden layer's launch: 82 launches per pass) or round 4's 122-launch chain.
-    // Same bits either way (test_flow_fold_keeps_the_bits).  Every workgroup of a folded launch redoes the tail of its own sample
-    // tiles (128 KB of partial tiles each), so it pays while a workgroup holds ONE sample tile (B <= 64: 508 -> 473 us at B = 64,
-    // 460 -> 439 at B = 8) and loses with four (B = 256: 765 -> 1083 us): default = folded iff ns == 1.  I2V_FLOW_FOLD=0|1 (read when the weights are packed) forces.
-    const bool fold = (p.force_fold >= 0 ? p.force_fold : (ns == 1 ? 1 : 0)) != 0;
+    const FlowTilePlan plan = flow_tile_plan(p, B);   // the one copy of the ns / fold rule
+    const int ns = plan.ns;
+    const bool fold = plan.fold;
     int seq = 0;   // launch number inside the pass
     const size_t fb = p.f16 ? 512 : 1024;   // bytes per weight fragment
 
@@ -805,7 +815,7 @@ int flow_tile_enqueue(const FlowTilePack& p, const FlowParams& par, bool reverse
         const bool folded = fold && k.next_step >= 0;
         int rc;
         if (folded) {
-            if ((rc = launch_layer(p.f16, HB / 8, ns, hid_args(k.next_step, 0, hA, hB, Pbuf[it & 1]), &t, st))) return rc;
+            if ((rc = launch_layer(p.f16, plan.kpw, ns, hid_args(k.next_step, 0, hA, hB, Pbuf[it & 1]), &t, st))) return rc;
         } else {
             t.seq = seq++;
             const int flags = t.io_in | t.io_out << 1 | t.ld_init << 2 | t.reverse << 3 | t.do_lrelu << 4 | t.do_swap << 5 | t.l1 << 6;
@@ -818,7 +828,7 @@ int flow_tile_enqueue(const FlowTilePack& p, const FlowParams& par, bool reverse
         float* cur = hA;
         float* nxt = hB;
         for (int d = 0; d < D; ++d) {
-            if (!(folded && d == 0) && (rc = launch_layer(p.f16, HB / 8, ns, hid_args(k.next_step, d, cur, nxt, Pbuf[it & 1]), nullptr, st))) return rc;
+            if (!(folded && d == 0) && (rc = launch_layer(p.f16, plan.kpw, ns, hid_args(k.next_step, d, cur, nxt, Pbuf[it & 1]), nullptr, st))) return rc;
             std::swap(cur, nxt);
         }
     }

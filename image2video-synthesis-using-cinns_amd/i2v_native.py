@@ -68,6 +68,7 @@ SYMBOLS = {
     "i2v_flow_load": (c_int32, [c_void_p, POINTER(_Tensor), c_int32]),
     "i2v_flow_workspace_bytes": (c_size_t, [c_void_p, c_int32]),
     "i2v_flow_param_bytes": (c_size_t, [c_void_p]),
+    "i2v_flow_plan": (c_int32, [c_void_p, c_int32, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),
     "i2v_flow_forward": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int32, c_void_p]),
     "i2v_flow_inverse": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int32, c_void_p]),
     "i2v_flow_train_create": (c_int32, [POINTER(FlowCfg), POINTER(c_void_p)]),
@@ -335,6 +336,15 @@ class NativeFlow(_Handle):
     @property
     def param_bytes(self):
         return int(lib().i2v_flow_param_bytes(self._h))
+
+    def plan(self, batch):
+        """What a pass at ``batch`` launches on the loaded handle, asked of the launcher's own rule (host only, nothing runs):
+        {"chain": "tile" | "generic", "kpw": k-blocks per wave, "ns": sample tiles per workgroup, "fold": bool}; kpw = ns = 0 and
+        fold False on the generic chain."""
+        v = [c_int32() for _ in range(4)]
+        _check(lib().i2v_flow_plan(self._h, int(batch), *(ctypes.byref(i) for i in v)), "i2v_flow_plan")
+        chain, kpw, ns, fold = (i.value for i in v)
+        return {"chain": "tile" if chain else "generic", "kpw": kpw, "ns": ns, "fold": bool(fold)}
 
     @_on_device
     def _run(self, x, embed, reverse):

@@ -84,6 +84,11 @@ int i2v_flow_load(i2v_flow* f, const i2v_tensor* tensors, int32_t n_tensors);
 size_t i2v_flow_workspace_bytes(const i2v_flow* f, int32_t batch);
 /* Bytes of parameters streamed per pass (the algorithmic HBM traffic of SURVEY §8d). */
 size_t i2v_flow_param_bytes(const i2v_flow* f);
+/* Host-only query of what a pass at `batch` launches on a LOADED handle (nothing is launched): chain 0 = the generic vector-ALU
+ * chain, 1 = the matrix-core tile chain; for the tile chain kpw = k-blocks per wave (hidden / 128), ns = sample tiles per
+ * hidden-layer workgroup (1, 2 or 4) and fold = 1 when the tail travels with the first hidden layer's launch -- the values
+ * the launcher itself uses; 0, 0, 0 for the generic chain.  I2V_E_INVALID: null argument or batch <= 0. */
+int i2v_flow_plan(const i2v_flow* f, int32_t batch, int32_t* chain, int32_t* kpw, int32_t* ns, int32_t* fold);
 /* ConditionalFlow.forward(x, embedding, reverse=False), flow_blocks.py:42-51.
  * x [B,64], embed [B,E] -> zt [B,64], logdet [B]. */
 int i2v_flow_forward(i2v_flow* f, const float* x, const float* embed, float* zt, float* logdet,
