@@ -464,7 +464,9 @@ static int train_call_checks(const i2v_flow_train* f, const void* saved, size_t 
 
 template <int MODE>
 static void launch_chain(const ChainArgs& a, bool vec, int nets, hipStream_t st) {
-    const dim3 grid((a.M + 15) / 16, (a.B + 63) / 64, nets);
+    // MODE 1 covers every row of Y up to ldy, not only the M rows of W: the rows between hold zeros (dcin in 'cond' mode, where
+    // KP - M >= 32, would otherwise keep whatever `saved` held there)
+    const dim3 grid(((MODE == 1 ? a.ldy : a.M) + 15) / 16, (a.B + 63) / 64, nets);
     if (vec) hipLaunchKernelGGL((chain_gemm<MODE, true>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((chain_gemm<MODE, false>), grid, dim3(256), 0, st, a);
 }
@@ -497,6 +499,21 @@ void i2v_flow_train_destroy(i2v_flow_train* f) { delete f; }
 size_t i2v_flow_train_saved_bytes(const i2v_flow_train* f, int32_t batch) {
     if (!f || batch < 1) return 0;
     return make_layout(batch, f->H, f->depth, f->E, f->nfl).total * sizeof(float);
+}
+
+int i2v_flow_train_saved_layout(int32_t hidden, int32_t depth, int32_t embedding_dim, int32_t n_flows, int32_t batch,
+                                i2v_flow_train_layout* out) {
+    I2V_REQUIRE(out, I2V_E_INVALID, "i2v_flow_train_saved_layout: null argument");
+    I2V_REQUIRE(n_flows >= 1 && batch >= 1, I2V_E_INVALID, "i2v_flow_train_saved_layout: n_flows %d / batch %d", n_flows, batch);
+    I2V_REQUIRE(flow_tile_geometry_ok(64, hidden, depth, embedding_dim), I2V_E_INVALID,
+                "i2v_flow_train_saved_layout: unsupported geometry (hidden_dim %d, hidden_depth %d, embedding_dim %d)", hidden, depth,
+                embedding_dim);
+    const TrainLayout L = make_layout(batch, hidden, depth, embedding_dim, n_flows);
+    out->KP = L.KP; out->step_sz = (int64_t)L.step_sz;
+    out->o_cin = (int64_t)L.o_cin; out->o_act = (int64_t)L.o_act; out->o_out = (int64_t)L.o_out; out->o_dpre = (int64_t)L.o_dpre;
+    out->o_dout = (int64_t)L.o_dout; out->o_xin = (int64_t)L.o_xin; out->o_gan = (int64_t)L.o_gan; out->o_part = (int64_t)L.o_part;
+    out->o_dcin = (int64_t)L.o_dcin; out->total = (int64_t)L.total;
+    return I2V_OK;
 }
 
 int i2v_flow_train_bind(i2v_flow_train* f, const i2v_tensor* params, const i2v_tensor* grads, int32_t n) {

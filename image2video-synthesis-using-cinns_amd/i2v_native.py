@@ -36,6 +36,11 @@ class FlowCfg(ctypes.Structure):
                                       "control", "activation", "skip_actnorm", "skip_shuffle", "use_graph", "linear_f16")]
 
 
+class FlowTrainLayout(ctypes.Structure):
+    _fields_ = [(n, c_int64) for n in ("KP", "step_sz", "o_cin", "o_act", "o_out", "o_dpre", "o_dout", "o_xin", "o_gan", "o_part", "o_dcin",
+                                      "total")]
+
+
 class AdamTensor(ctypes.Structure):
     _fields_ = [("param", c_void_p), ("grad", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p), ("max_exp_avg_sq", c_void_p),
                 ("numel", c_int64)]
@@ -75,6 +80,7 @@ SYMBOLS = {
     "i2v_flow_train_destroy": (None, [c_void_p]),
     "i2v_flow_train_bind": (c_int32, [c_void_p, POINTER(_Tensor), POINTER(_Tensor), c_int32]),
     "i2v_flow_train_saved_bytes": (c_size_t, [c_void_p, c_int32]),
+    "i2v_flow_train_saved_layout": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(FlowTrainLayout)]),
     "i2v_flow_train_forward": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int32, c_void_p]),
     "i2v_flow_train_backward": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
                                           c_void_p]),
@@ -387,6 +393,7 @@ class NativeFlowTrain(_Handle):
             _check(lib().i2v_flow_train_create(ctypes.byref(cfg), ctypes.byref(h)), "i2v_flow_train_create")
         self._h = h
         self.embedding_dim = embedding_dim
+        self._geometry = (hidden_dim, hidden_depth, embedding_dim, n_flows)
         self.flat_numel, self.flat_slices, self.bound_ptrs, self._keep = 0, {}, None, None
 
     def __del__(self):
@@ -431,14 +438,24 @@ class NativeFlowTrain(_Handle):
         self.bound_ptrs = self.pointers(tensors)
         self._keep = (tensors, grads)
 
-    def forward(self, x, embed):
-        """-> (zt [B,64], logdet [B], saved): ``saved`` belongs to this pass and goes to ``backward``."""
+    def saved_layout(self, B):
+        """{field: value} of ``i2v_flow_train_saved_layout`` at batch B: where each region of ``saved`` lies, in floats."""
+        out = FlowTrainLayout()
+        _check(lib().i2v_flow_train_saved_layout(*self._geometry, B, ctypes.byref(out)), "i2v_flow_train_saved_layout")
+        return {n: int(getattr(out, n)) for n, _ in FlowTrainLayout._fields_}
+
+    def forward(self, x, embed, saved=None):
+        """-> (zt [B,64], logdet [B], saved): ``saved`` belongs to this pass and goes to ``backward``.  ``saved``: a uint8 device
+        buffer of at least ``i2v_flow_train_saved_bytes`` to use instead of a fresh one (a test passes a pre-filled one)."""
         _require_gpu(x, embed)
         B = x.shape[0]
         if x.shape != (B, 64) or embed.shape != (B, self.embedding_dim):
             raise I2VError(f"flow: expected x [B,64] and embed [B,{self.embedding_dim}], got {tuple(x.shape)}, {tuple(embed.shape)}")
         with self._on(x, embed):
-            saved = torch.empty(int(lib().i2v_flow_train_saved_bytes(self._h, B)), dtype=torch.uint8, device=x.device)
+            if saved is None:
+                saved = torch.empty(int(lib().i2v_flow_train_saved_bytes(self._h, B)), dtype=torch.uint8, device=x.device)
+            elif saved.dtype != torch.uint8 or not saved.is_cuda or not saved.is_contiguous():
+                raise I2VError("flow training: `saved` must be a contiguous uint8 tensor on a HIP device")
             zt = torch.empty_like(x)
             logdet = torch.empty(B, dtype=torch.float32, device=x.device)
             _check(lib().i2v_flow_train_forward(self._h, x.data_ptr(), embed.data_ptr(), zt.data_ptr(), logdet.data_ptr(), saved.data_ptr(),

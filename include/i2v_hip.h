@@ -120,6 +120,16 @@ int i2v_flow_train_bind(i2v_flow_train* f, const i2v_tensor* params, const i2v_t
 /* Size of the `saved` buffer of one forward / backward pair: MLP inputs, hidden activations, s / t of every half-step
  * and the backward's pre-activation gradients (about 1 MB per sample at 20 flows, hidden 512, depth 2). */
 size_t i2v_flow_train_saved_bytes(const i2v_flow_train* f, int32_t batch);
+/* Where each region of `saved` lies, in floats, for tests that check one kernel at a time.  Per half-step st, at
+ * st * step_sz: xs [B][64] at 0, cin [B][KP] at o_cin, act [2][depth + 1][B][H] at o_act, out [2][B][32] at o_out, dpre
+ * (shaped like act) at o_dpre, dout [2][B][32] at o_dout; then once: xin [n_flows][B][64] at o_xin, gan (same shape) at
+ * o_gan, part [B][64] at o_part, dcin [B][KP] at o_dcin.  A host function: no handle, no device call.  I2V_E_INVALID for
+ * a geometry i2v_flow_train_create refuses. */
+typedef struct {
+    int64_t KP, step_sz, o_cin, o_act, o_out, o_dpre, o_dout, o_xin, o_gan, o_part, o_dcin, total;
+} i2v_flow_train_layout;
+int i2v_flow_train_saved_layout(int32_t hidden, int32_t depth, int32_t embedding_dim, int32_t n_flows, int32_t batch,
+                                i2v_flow_train_layout* out);
 /* ConditionalFlow.forward(x, embedding), flow_blocks.py:42-51, keeping in `saved` what the backward needs:
  * x [B,64], embed [B,E] -> zt [B,64], logdet [B]. */
 int i2v_flow_train_forward(i2v_flow_train* f, const float* x, const float* embed, float* zt, float* logdet, void* saved,

@@ -13,7 +13,7 @@ import i2v_synth as synth
 from conftest import PKG, REPO
 from flow_train_common import load_grad_fixture, oracle_grads, rel
 
-TRAIN_SYMBOLS = ["i2v_flow_train_create", "i2v_flow_train_destroy", "i2v_flow_train_bind", "i2v_flow_train_saved_bytes",
+TRAIN_SYMBOLS = ["i2v_flow_train_create", "i2v_flow_train_destroy", "i2v_flow_train_bind", "i2v_flow_train_saved_bytes", "i2v_flow_train_saved_layout",
                  "i2v_flow_train_forward", "i2v_flow_train_backward", "i2v_adam_step", "i2v_adam_chunk"]
 
 
