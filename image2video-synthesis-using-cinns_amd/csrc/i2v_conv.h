@@ -167,19 +167,23 @@ int wino4g_forward(const Wino4Weights& wts, const float* x, const float* coef, c
                    int rs, int B, int T, int H, int W, int epi, hipStream_t st, double* stats = nullptr, int* range_flag = nullptr,
                    int* umax = nullptr, GbRows rows = {});
 
-// ---- helpers implemented in i2v_dec.hip, shared with the embedder (i2v_embed.hip)
+// ---- normalisation helpers (i2v_norm.hip), shared by the decoder, the embedder and the motion encoder
 // per-(b,c) sum / sum of squares (fp64) of a channels-last tensor [B][P][C]
 int stats_forward(const float* x, double* sums, int B, long P, int C, hipStream_t st);
 // (sum, sumsq) -> per-(b,c) (A, B) pairs with norm(x) == x*A + B (biased variance, eps 1e-5)
 // gw/gb: optional per-channel affine weight / bias folded into the pairs (GroupNorm(affine=True))
+// zl: optional ADAIN source instead, gamma = zl[b * zstride + zoff + c], beta = zl[b * zstride + zoff + C + c]
 int coef_forward(const double* sums, float* coef, int B, int C, int groups, double count, hipStream_t st,
-                 const float* gw = nullptr, const float* gb = nullptr);
+                 const float* gw = nullptr, const float* gb = nullptr, const float* zl = nullptr, int zstride = 0, int zoff = 0);
 // out = act(x * A + B (+ res)) on a channels-last [B][P][C] tensor; coef index = b * cstride + c (i2v_embed.hip)
 // out_hl16 (optional): the same result in the split-fp16 operand format (input of conv16_forward); out may then be null
 int norm_act_forward(const float* x, const float* coef, long cstride, const float* res, float* out, int B, long P, int C, bool relu,
                      hipStream_t st, void* out_hl16 = nullptr);
 // bilinear (align_corners=True) NCHW [B,3,Hi,Wi] -> channels-last [B][Ho][Wo][16] (channels 3..15 zero)
-int resize_forward(const float* img, float* out, int B, int Hi, int Wi, int Ho, int Wo, hipStream_t st);
+// hl16: rows in the split-fp16 operand format, `flag` set to 1 when a value leaves the fp16 range; ibs: floats between the samples of
+// `img` (0: dense)
+int resize_forward(const float* img, float* out, int B, int Hi, int Wi, int Ho, int Wo, hipStream_t st, int hl16 = 0,
+                   int* flag = nullptr, long ibs = 0);
 
 // ---- conv_img (i2v_convimg.hip): Conv3d(nf -> 3) + tanh on the vector ALU, exact fp32
 struct ConvImgWeights {

@@ -125,7 +125,7 @@ __device__ __forceinline__ void w4g_load(const char* xc, const W4GenLane<SPADE>&
 
 // One frame of one chunk: PASS 0 writes the planes 0..3 of the lane's V row, PASS 1 the planes 4, 5.  vbuf: LDS address of the
 // target buffer's row 0; cf = the chunk's (A, B) pairs of the lane's four channels; gc = the sample's gamma' | beta maps at the
-// chunk's channels (SPADE).  The arithmetic follows modulate_wino4_kernel (i2v_dec.hip) expression for expression.
+// chunk's channels (SPADE).  The arithmetic follows modulate_wino4_kernel (i2v_dec_writers.hip) expression for expression.
 template <int CIN, bool SPADE, int PASS>
 __device__ __forceinline__ void w4g_frame(const W4GenLane<SPADE>& L, int fi, const float (&ca)[4], const float (&cb)[4], const char* gc,
                                           const W4GenIn<SPADE>& in, char* vbuf, float& vmaxd, float& vmaxv) {

@@ -1,4 +1,4 @@
-"""The F(4,3) operand writer (modulate_wino4_kernel, csrc/i2v_dec.hip) stores whole 16-byte pieces after a DPP exchange between the two
+"""The F(4,3) operand writer (modulate_wino4_kernel, csrc/i2v_dec_writers.hip) stores whole 16-byte pieces after a DPP exchange between the two
 lanes of a pair (form 1); the measurement build also holds the form that requests the next input frame ahead of the current frame's
 stores (3) and the earlier 8-byte stores (0), selected by I2V_MOD4_FORM.  No form changes a byte of V: tests/writer_forms_worker.py
 -- in a process of its own, on that build -- compares the tapped operands (into NaN-filled buffers) and the frames of every form

@@ -47,7 +47,7 @@ def test_production_library_has_no_launch_path_environment_switches():
         mblob = open(i2v_native.MEASURE_LIB_PATH, "rb").read()
         assert b"I2V_W4_PIPE" in mblob and b"conv_wino4_f16x3_kernelILi9ELi64ELi1ELi512E" in mblob
     # source level: getenv only at creation / pack time (functions named below) or under I2V_MEASURE
-    allowed = {"i2v_dec.hip": ("i2v_dec_create", "i2v_gblock_create"), "i2v_flow.hip": ("i2v_flow_create",),
+    allowed = {"i2v_dec_block.hip": ("read_switches",), "i2v_dec_writers.hip": ("run_modulate_wino4",), "i2v_flow.hip": ("i2v_flow_create",),
                "i2v_flow_tile.hip": ("env_int",), "i2v_conv16w4.hip": ("w4_switches",), "i2v_convimg.hip": ("conv_img_mfma_forward",),
                "i2v_conv16.hip": ("c16_switch",)}     # (under -DC16_TUNE only: the stand-alone tools/conv16_bench build)
     import glob
@@ -56,6 +56,18 @@ def test_production_library_has_no_launch_path_environment_switches():
         if "getenv" not in text:
             continue
         assert os.path.basename(f) in allowed, f
+    # the decoder's switches: read by read_switches alone, which only i2v_dec_create / i2v_gblock_create call; the writers' form switch
+    # under I2V_MEASURE
+    blk = open(os.path.join(PKG, "csrc", "i2v_dec_block.hip")).read()
+    body = blk[blk.index("void read_switches(BlockCtx* d, bool whole) {"):]
+    body = body[:body.index("\n}\n")]
+    assert blk.count("getenv(") == body.count("getenv(") > 0
+    for f, creator in (("i2v_dec.hip", "i2v_dec_create"), ("i2v_gblock.hip", "i2v_gblock_create")):
+        text = open(os.path.join(PKG, "csrc", f)).read()
+        assert text.count("read_switches(") == 1 and text.index("int %s(" % creator) < text.index("read_switches(") < text.index("\n}\n", text.index("int %s(" % creator))
+    wr = open(os.path.join(PKG, "csrc", "i2v_dec_writers.hip")).read()
+    at = wr.index("getenv(")
+    assert wr.count("getenv(") == 1 and wr.rfind("#ifdef I2V_MEASURE", 0, at) > wr.rfind("#endif", 0, at)
     w4 = open(os.path.join(PKG, "csrc", "i2v_conv16w4.hip")).read()
     body = w4[w4.index("static W4Switches w4_switches()"):]
     body = body[:body.index("\n}\n")]

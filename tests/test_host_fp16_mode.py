@@ -114,7 +114,7 @@ def test_fp16_kernel_static_checks(tmp_path):
 def test_fp16_writer_keeps_the_range_guard():
     """The one-term writer is modulate_wino4_kernel<GB, ONE = true>: the same guard (bit 0 on |V| > 65504 or non-finite, the maximum
     |activation| into the layer's slot) as the split writer -- no separate kernel that could drop it."""
-    src = open(os.path.join(PKG, "csrc", "i2v_dec.hip")).read()
+    src = open(os.path.join(PKG, "csrc", "i2v_dec_writers.hip")).read()
     body = src[src.index("__global__ __launch_bounds__(256) void modulate_wino4_kernel("):]
     body = body[:body.index("\n}\n")]
     assert "if constexpr (ONE)" in body and "atomicOr(range_flag, 1)" in body and "publish_umax(umax, vmax)" in body

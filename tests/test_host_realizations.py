@@ -118,7 +118,7 @@ def _kernel_bodies(text):
 def test_shared_map_writers_are_compiled(tmp_path):
     """Every SPADE-consuming operand writer has its shared-map instantiation (SH = true) next to the plain one, and it needs no more
     scratch and no more VGPRs than the plain one (the row index is one division per sample, outside the loops)."""
-    bodies = _kernel_bodies(_asm(tmp_path, "i2v_dec"))
+    bodies = _kernel_bodies(_asm(tmp_path, "i2v_dec_writers"))
     pairs = [("modulate_kernelILb1ELb1E", "modulate_kernelILb1ELb0E"), ("modulate_kernelILb0ELb1E", "modulate_kernelILb0ELb0E"),
              ("modulate_wino_kernelILb1E", "modulate_wino_kernelILb0E"),
              ("modulate_wino4_kernelILb1ELb0ELb1E", "modulate_wino4_kernelILb1ELb0ELb0E"),

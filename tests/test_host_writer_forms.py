@@ -1,4 +1,4 @@
-"""Static checks of the F(4,3) operand writer (modulate_wino4_kernel, csrc/i2v_dec.hip) as the production library compiles it: 16-byte
+"""Static checks of the F(4,3) operand writer (modulate_wino4_kernel, csrc/i2v_dec_writers.hip) as the production library compiles it: 16-byte
 stores behind a DPP pair exchange; no scratch, and registers for the occupancy the writer had
 with 8-byte stores: 3 waves per SIMD where SPADE's maps are held per position (<= 168 VGPRs), 4 where they are not (<= 128)."""
 import os
@@ -16,9 +16,9 @@ def writer_kernels(tmp_path_factory):
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("no hipcc")
-    out = tmp_path_factory.mktemp("asm") / "i2v_dec.s"
+    out = tmp_path_factory.mktemp("asm") / "i2v_dec_writers.s"
     subprocess.run([hipcc, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-I" + os.path.join(PKG, "csrc"), "-S", "--cuda-device-only",
-                    os.path.join(PKG, "csrc", "i2v_dec.hip"), "-o", str(out)], check=True, capture_output=True, timeout=900)
+                    os.path.join(PKG, "csrc", "i2v_dec_writers.hip"), "-o", str(out)], check=True, capture_output=True, timeout=900)
     bodies = dict(re.findall(r"^(\w+):[^\n]*\n(.*?)\.end_amdhsa_kernel", out.read_text(), flags=re.S | re.M))
     return {n: b for n, b in bodies.items() if "modulate_wino4_kernelILb" in n}
 
@@ -49,7 +49,7 @@ def test_writer_store_shape(writer_kernels):
 
 def test_form_switch_only_in_the_measurement_build():
     import i2v_native
-    src = open(os.path.join(PKG, "csrc", "i2v_dec.hip")).read()
+    src = open(os.path.join(PKG, "csrc", "i2v_dec_writers.hip")).read()
     at = src.index('getenv("I2V_MOD4_FORM")')
     assert src.rfind("#ifdef I2V_MEASURE", 0, at) > src.rfind("#endif", 0, at)
     if os.path.exists(i2v_native.LIB_PATH):

@@ -1,6 +1,6 @@
 """Worker of tests/test_gpu_writer_stores.py: runs in a process of its own with I2V_LIB_PATH pointing at the MEASUREMENT build of the
 library (lib/libi2v_hip_measure.so), the only build that reads I2V_MOD4_FORM and carries every store / loop form of the F(4,3) operand
-writer (modulate_wino4_kernel, csrc/i2v_dec.hip): 0 = 8-byte half-piece stores and loads inside the frame (the writer up to round 6),
+writer (modulate_wino4_kernel, csrc/i2v_dec_writers.hip): 0 = 8-byte half-piece stores and loads inside the frame (the writer up to round 6),
 1 = 16-byte stores (what the production library holds), 3 = 16-byte stores + frame-ahead loads.  Unset = the production form.
 
 argv[1] = JSON {"upsample_s", "upsample_t", "img"}.  For the split mode (nf = 32), the one-term mode ("fp16", nf = 32) and the shared-map
