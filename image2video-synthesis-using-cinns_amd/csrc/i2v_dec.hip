@@ -417,6 +417,8 @@ int i2v_dec_set_profile(i2v_dec* d, int32_t on) {
 
 int i2v_dec_debug_tap(i2v_dec* d, int32_t block, int32_t which, float* dst, size_t max_floats) {
     I2V_REQUIRE(d, I2V_E_INVALID, "i2v_dec_debug_tap: null");
+    I2V_REQUIRE(!dst || (block >= 0 && block < 6 && which >= 0 && which <= I2V_DEC_TAP_LAST), I2V_E_INVALID,
+                "i2v_dec_debug_tap: block %d / tap %d (blocks 0..5, taps 0..%d)", block, which, I2V_DEC_TAP_LAST);
     d->ctx.tap_block = block; d->ctx.tap_which = which; d->ctx.tap_dst = dst; d->ctx.tap_max = max_floats;
     return I2V_OK;
 }

@@ -124,8 +124,10 @@ static int conv3_write_operand(BlockCtx* d, const Conv3& c, Conv3Kernel kn, cons
     int* flag = d->status_dev;
     int* umax = is_split(kn) && flag ? flag + 1 + layer : nullptr;
     const size_t pos = (size_t)B * T * l.H * l.W;
-    // (the one-term operand is tapped whole: 3 bytes per activation of CinPad channels)
-    *tap_floats = kn == K_F43_GEN || kn == K_F32_WINO ? 0 : kn == K_F43_ONE ? pos * c.w43.CinPad * 3 / 4 : pos * c.cin;
+    // the whole operand, in floats: 4 bytes per activation in the direct formats (fp32, or fp16 hi | lo), 4 planes per 2 positions in
+    // F(2,3)'s V, 6 per 4 in F(4,3)'s (split and exact fp32), 6 per 4 of 2 bytes over CinPad channels in the one-term V
+    *tap_floats = kn == K_F43_GEN ? 0 : kn == K_F43_ONE ? pos * c.w43.CinPad * 3 / 4 : kn == K_F23 ? pos * c.cin * 2 :
+                  kn == K_F43 || kn == K_F32_WINO ? pos * c.cin * 3 / 2 : pos * c.cin;
     switch (kn) {
     case K_F43_GEN: return I2V_OK;
     case K_F32_WINO: return modulate_wino4_f32(in.x, in.coef, in.gb, a, B, T, l.H, l.W, c.cin, ut, in.us, 1, st, in.rows);
@@ -172,9 +174,11 @@ int block_forward(BlockCtx* d, int k, Block& b, const Level& l, const float* x, 
     double *sums1 = w.sums1, *sums2 = w.sums2;
     double* sums_out = w.sums_out ? w.sums_out : w.sums1;
     int rc;
-    auto tap = [&](int k_, int which, const float* src, size_t count) -> int {
+    // (count in floats; an fp64 pair table is copied as bytes: 4 floats per pair.  The copy is enqueued where the data is complete
+    //  and before the next launch that rewrites the buffer: coef is rewritten three times per block, sums1 by conv_1)
+    auto tap = [&](int k_, int which, const void* src, size_t count, hipStream_t ts) -> int {
         if (d->tap_dst && d->tap_block == k_ && d->tap_which == which)
-            I2V_HIP_CHECK(hipMemcpyAsync(d->tap_dst, src, std::min(count, d->tap_max) * 4, hipMemcpyDeviceToDevice, st));
+            I2V_HIP_CHECK(hipMemcpyAsync(d->tap_dst, src, std::min(count, d->tap_max) * 4, hipMemcpyDeviceToDevice, ts));
         return I2V_OK;
     };
     const int Tl = l.T / l.ut, Hl = l.H / l.us, Wl = l.W / l.us;
@@ -182,7 +186,9 @@ int block_forward(BlockCtx* d, int k, Block& b, const Level& l, const float* x, 
     // GroupNorm statistics of the (virtually upsampled) block input == statistics of the low-res tensor; they are
     // already in sums1 when the previous block's conv_1 accumulated them in its epilogue
     if (!x_stats_ready && (rc = stats_forward(x, sums1, B, Pl, b.n_in, st))) return rc;
+    if ((rc = tap(k, 12, x, (size_t)B * Pl * b.n_in, st)) || (rc = tap(k, 8, sums1, (size_t)B * b.n_in * 4, st))) return rc;
     if ((rc = coef_forward(sums1, coef, B, b.n_in, b.groups_spade, (double)Pl, st))) return rc;
+    if ((rc = tap(k, 9, coef, (size_t)B * b.n_in * 2, st))) return rc;
     // The learned shortcut depends on the block input and its statistics only: on the side stream it runs underneath the
     // modulate / conv_0 / modulate chain below (an HBM-bound GEMM next to matrix-core-bound convs); conv_1 waits for it.
     const bool side_shortcut = b.learned && w.side && w.coef_s;
@@ -190,6 +196,7 @@ int block_forward(BlockCtx* d, int k, Block& b, const Level& l, const float* x, 
         I2V_HIP_CHECK(hipEventRecord(w.ev_x, st));
         I2V_HIP_CHECK(hipStreamWaitEvent(w.side, w.ev_x, 0));
         int rs_ = coef_forward(sums1, w.coef_s, B, b.n_in, 16, (double)Pl, w.side, b.gn_w.as<float>(), b.gn_b.as<float>());
+        if (!rs_) rs_ = tap(k, 11, w.coef_s, (size_t)B * b.n_in * 2, w.side);
         if (!rs_) {
             if (d->aux16() && b.convs16.w.p) rs_ = pointwise16_forward(b.convs16, x, xs_low, nullptr, (long)B * Pl, Pl, EPI_NONE, w.side, w.coef_s, d->status_dev);
             else rs_ = conv_forward(b.convs, x, b.n_in, xs_low, nullptr, 1, 1, B, Tl, Hl, Wl, EPI_NONE, w.side, w.coef_s);
@@ -204,34 +211,37 @@ int block_forward(BlockCtx* d, int k, Block& b, const Level& l, const float* x, 
     const int Bg = rows.shared() ? (rows.r0 + B - 1) / rows.k + 1 : B;
     if (w.gb_ready) gb = const_cast<float*>(w.gb_ready);
     else if ((rc = spade_branch(d, b, l, img, img_h, img_w, ibs, Bg, y0, y1, w.y1v, gb, st))) return rc;
-    if ((rc = tap(k, 0, gb, (size_t)Bg * l.H * l.W * 2 * b.n_in))) return rc;
+    if ((rc = tap(k, 0, gb, (size_t)Bg * l.H * l.W * 2 * b.n_in, st))) return rc;
     // per conv: the kernel it runs in this call, its operand writer, the conv
     const Conv3 &c0 = b.conv[0], &c1 = b.conv[1];
     const Conv3In in0{x, coef, gb, l.ut, l.us, rows}, in1{dx, coef, nullptr, 1, 1, {}};
     const Conv3Kernel k0 = conv3_choose(d, c0, l, 2 * k, in0, w.m6), k1 = conv3_choose(d, c1, l, 2 * k + 1, in1, w.m6);
     size_t tap_floats = 0;
     if ((rc = conv3_write_operand(d, c0, k0, l, 2 * k, in0, a, B, st, &tap_floats))) return rc;
-    if (tap_floats && (rc = tap(k, 1, a, tap_floats))) return rc;
+    if (tap_floats && (rc = tap(k, 1, a, tap_floats, st))) return rc;
     // (statistics fused into the epilogue: split-fp16 kernels only; a tdup conv_0 is launched on the half-rate geometry)
     const bool fuse = is_split(k0) && conv16_can_fuse_stats(c0.tdup ? l.T / 2 : l.T, l.H, l.W);
     if ((rc = conv3_run(d, c0, k0, l, 2 * k, in0, a, dx, nullptr, 1, 1, B, EPI_NONE, fuse ? sums2 : nullptr, w, st))) return rc;
-    if ((rc = tap(k, 2, dx, (size_t)B * P * b.n_mid))) return rc;
+    if ((rc = tap(k, 2, dx, (size_t)B * P * b.n_mid, st))) return rc;
     // ADAIN (normalization_layer.py:47-51) + leaky_relu
     if (!fuse && (rc = stats_forward(dx, sums2, B, P, b.n_mid, st))) return rc;
+    if ((rc = tap(k, 6, sums2, (size_t)B * b.n_mid * 4, st))) return rc;
     if ((rc = coef_forward(sums2, coef, B, b.n_mid, b.n_mid, (double)P, st, nullptr, nullptr, zl, zstride, b.zoff))) return rc;
+    if ((rc = tap(k, 10, coef, (size_t)B * b.n_mid * 2, st))) return rc;
     if ((rc = conv3_write_operand(d, c1, k1, l, 2 * k + 1, in1, a, B, st, &tap_floats))) return rc;
-    if (tap_floats && (rc = tap(k, 3, a, tap_floats))) return rc;
+    if (tap_floats && (rc = tap(k, 3, a, tap_floats, st))) return rc;
     // shortcut (decoder.py:44-49) at low resolution
     const float* res = x;
     if (b.learned && !side_shortcut) {
         if ((rc = coef_forward(sums1, coef, B, b.n_in, 16, (double)Pl, st, b.gn_w.as<float>(), b.gn_b.as<float>()))) return rc;
+        if ((rc = tap(k, 11, coef, (size_t)B * b.n_in * 2, st))) return rc;
         // Norm3D folded into the 1x1x1 conv's loads (no padding taps -> exact): no normalised copy of x is written
         (void)xs_in;
         if (d->aux16() && b.convs16.w.p) rc = pointwise16_forward(b.convs16, x, xs_low, nullptr, (long)B * Pl, Pl, EPI_NONE, st, coef, d->status_dev);
         else rc = conv_forward(b.convs, x, b.n_in, xs_low, nullptr, 1, 1, B, Tl, Hl, Wl, EPI_NONE, st, coef);
         if (rc) return rc;
         res = xs_low;
-        if ((rc = tap(k, 4, xs_low, (size_t)B * Pl * b.n_out))) return rc;
+        if ((rc = tap(k, 4, xs_low, (size_t)B * Pl * b.n_out, st))) return rc;
     } else if (b.learned) {
         res = xs_low;
         I2V_HIP_CHECK(hipStreamWaitEvent(st, w.ev_s, 0));   // enqueued on the side stream at the top of the block
@@ -243,7 +253,8 @@ int block_forward(BlockCtx* d, int k, Block& b, const Level& l, const float* x, 
     if ((rc = conv3_run(d, c1, k1, l, 2 * k + 1, in1, a, xn, res, l.ut, l.us, B, last ? EPI_LRELU : EPI_NONE, fuse_out ? sums_out : nullptr, w, st)))
         return rc;
     x_stats_ready = fuse_out;
-    if ((rc = tap(k, 5, xn, (size_t)B * P * b.n_out))) return rc;
+    if (fuse_out && (rc = tap(k, 7, sums_out, (size_t)B * b.n_out * 4, st))) return rc;
+    if ((rc = tap(k, 5, xn, (size_t)B * P * b.n_out, st))) return rc;
     return I2V_OK;
 }
 

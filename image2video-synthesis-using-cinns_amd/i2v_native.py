@@ -586,6 +586,13 @@ class NativeDecoder(_Handle):
         else:
             _check(lib().i2v_dec_debug_tap(self._h, block, which, dst.data_ptr(), dst.numel()), "i2v_dec_debug_tap")
 
+    def debug_tap_f64(self, block, which, pairs, device):
+        """A NaN-filled float64 CUDA tensor [pairs, 2] set as the destination of one of the fp64 taps (6, 7, 8: (sum, sumsq) pairs, which
+        the hook copies as bytes); read it after the next forward."""
+        dst = torch.full((pairs, 2), float("nan"), dtype=torch.float64, device=device)
+        self.debug_tap(block, which, dst.view(torch.float32).view(-1))
+        return dst
+
     @_on_device
     def set_side_stream(self, stream):
         """i2v_dec_set_side_stream: run the handle's side work (SPADE branches, learned shortcuts, ``prepare``) on ``stream`` (a

@@ -336,6 +336,32 @@ int i2v_dec_get_layer_profile(i2v_dec* d, int32_t layer, char* name, int32_t nam
  * ~2^-12 per value; a warning, as in mma = 1. */
 int i2v_dec_status(i2v_dec* d, int32_t* flags, int32_t reset, void* stream);
 
+/* Test hook: during every following forward, copy one intermediate of block `block` (0 = head_0 .. 5 = g_4) into `dst` (device,
+ * min(size of the intermediate, max_floats) floats, enqueued on the forward's stream where the data is complete and before its
+ * buffer is reused); dst = null switches the hook off.  With a tap set the SPADE branches and the learned shortcut run inline on the
+ * caller's stream and the operand-generating F(4,3) kernel (I2V_DEC_GEN) is not used; nothing else changes -- with no tap set, launch
+ * order and bits are those of a build without the hook.  Activations are channels-last fp32.  `which`:
+ *    0  SPADE's (1 + gamma | beta) maps [F][H][W][2 n_in]
+ *    1  the WHOLE operand conv_0's writer wrote, in the format of the kernel the layer runs (i2v_dec_get_layer_profile's code):
+ *         fp32 direct             [B][T][H][W][C] fp32
+ *         split-fp16 direct       [B][T][H][W][C/8][8 fp16 hi | 8 fp16 lo]   (a temporal-duplication conv_0: T / 2 frames, here and below)
+ *         split-fp16 F(2,3) V     [B][T][C/16][4 planes][H][W/2][c 0-7 hi | lo | c 8-15 hi | lo]      2 floats per activation
+ *         split-fp16 F(4,3) V     [B][T][C/16][6 planes][H][W/4][c 0-7 hi | lo | c 8-15 hi | lo]      3/2 floats per activation
+ *         one-term fp16 F(4,3) V  [B][T][CinPad/32][6][H][W/4][c 0-7 | 16-23 | 8-15 | 24-31], CinPad = C rounded up to 64
+ *         exact-fp32 F(4,3) V     [6 planes][B][T][H][W/4][C] fp32                                    3/2 floats per activation
+ *    2  conv_0's output (with its bias) [B][T][H][W][n_mid]
+ *    3  the whole operand of conv_1, as 1
+ *    4  the learned shortcut at the block input's resolution [B][T/ut][H/us][W/us][n_out] (learned blocks only)
+ *    5  the block output [B][T][H][W][n_out] (g_4: lrelu(.), fused into conv_1's epilogue)
+ *    6  the (sum, sumsq) fp64 pairs [B][n_mid] ADAIN's coefficients are derived from (conv_0's epilogue or the statistics kernel
+ *       filled them), copied as bytes: 4 floats per pair, here and in 7 and 8
+ *    7  the fp64 pairs [B][n_out] of the block output, ONLY where conv_1's epilogue accumulated them (else nothing is copied)
+ *    8  the fp64 pairs [B][n_in] of the block input as this block reads them (the previous block's epilogue or the statistics kernel)
+ *    9  the (A, B) float2 table [B][n_in] handed to conv_0's operand writer (SPADE's group norm: norm(x) = x A + B)
+ *   10  the (A, B) table [B][n_mid] handed to conv_1's operand writer (ADAIN: gamma norm(x) + beta = x A + B)
+ *   11  the (A, B) table [B][n_in] of the learned shortcut's Norm3D (learned blocks only)
+ *   12  the block input [B][T/ut][H/us][W/us][n_in] */
+#define I2V_DEC_TAP_LAST 12
 int i2v_dec_debug_tap(i2v_dec* d, int32_t block, int32_t which, float* dst, size_t max_floats);
 
 /* ------------------------------------------------------------------------------------------

@@ -15,6 +15,7 @@ import torch
 
 import i2v_synth as synth
 from conftest import load_golden, rel_l2
+from dec_units_common import _v_onehot_channels, _v_split_hi
 
 pytestmark = pytest.mark.gpu
 
@@ -104,19 +105,6 @@ def test_fp16_mode_runs_the_one_term_kernel_on_every_f43_layer(golden):
 
 
 # ------------------------------------------------------------------------------------------------ tight pins: writer and conv
-def _v_onehot_channels(raw, B, T, Cp, H, J):
-    """One-term operand bytes -> fp16 [B, T, 6, H, J, Cp] in channel order (pieces of a row: c0-7 | c16-23 | c8-15 | c24-31)."""
-    v = raw.view(torch.float16)[: B * T * Cp // 32 * 6 * H * J * 32].view(B, T, Cp // 32, 6, H, J, 4, 8)
-    v = v[:, :, :, :, :, :, [0, 2, 1, 3], :]
-    return v.permute(0, 1, 3, 4, 5, 2, 6, 7).reshape(B, T, 6, H, J, Cp)
-
-
-def _v_split_hi(raw, B, T, C, H, J, nrows):
-    """Split operand bytes (first nrows rows of 64 B) -> hi parts fp16 [rows of (b, t, chunk16, x, h, j)][16 channels]."""
-    v = raw.view(torch.float16)[: nrows * 32].view(nrows, 4, 8)
-    return v[:, [0, 2], :].reshape(nrows, 16)
-
-
 def _levels(meta):
     """Per block: (T, H, W, ut) of the level it runs at (i2v_dec_create)."""
     ups, upt = meta["upsample_s"], meta["upsample_t"]
