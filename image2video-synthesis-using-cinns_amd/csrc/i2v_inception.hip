@@ -1,0 +1,747 @@
+// FID Inception-v3 trunk (torchvision's Inception3 graph with the pytorch-fid patches) up to the final average pool.
+//
+// Replaces metrics/FID/inception.py (InceptionV3.forward, fid_inception_v3, FIDInceptionA / C / E_1 / E_2 and the torchvision blocks
+// InceptionB / D, BasicConv2d underneath) and the feature half of metrics/FID/FID_Score.py (get_activations); the statistics run on
+// i2v_fvd_stats_update (i2v_i3d.hip) with D = 2048.
+//
+// Convolutions: ONE 2-D implicit-GEMM kernel on the exact-fp32 matrix cores (v_mfma_f32_16x16x4_f32), the scheme of i3d_conv_kernel
+// without the time dimension and with a rectangular window:
+//   Out[m = (n, ho, wo) flattened][c] = relu(scale[c] * sum_k In[gather(m, k)] * W[k][c] + shift[c])
+//   * positions are flattened over N * Ho * Wo, 128 per workgroup, the last tile masked;
+//   * K is flattened over (tap = dh * KW + dw, channel) in groups of 4 channels: a 16-wide chunk of the 3x3 image conv (r, g, b, 0)
+//     holds 4 taps, a chunk of a 1x1 unit 16 channels -- one gather path for 1x1, 3x3, 5x5, 1x7, 7x1, 1x3 and 3x1, stride 1 or 2;
+//   * KH, KW, stride and the padding per dimension are arguments, and so are the channel stride / offset of the input and of the
+//     output: the branches of a Mixed block store straight into their slice, there is no concat kernel;
+//   * epilogue: eval-mode BatchNorm2d(eps = 0.001) folded to (scale, shift) at load, ReLU (BasicConv2d).
+// 4 waves x (32 rows x BN columns) per workgroup, BN in {32, 64, 128} per layer; A and W chunks double-buffered in LDS (rows of 16
+// floats padded to 20: conflict-free ds_read_b128), the next chunk's global loads in flight during the MFMAs, one barrier per chunk.
+// Loads are unconditional with clamped addresses.  The K order of an output element depends on neither the batch nor the tile it
+// falls in: batch rows equal their single-image runs bit for bit.  No atomics.
+//
+// Pools (channels-last, 4 channels per thread, taps in (dh, dw) order):
+//   (a) MaxPool2d(3, stride 2): no padding, floor mode;
+//   (b) max_pool2d(3, stride 1, padding 1): a tap outside the map never wins (-inf, NOT the zeros of the I3D pools);
+//   (c) avg_pool2d(3, stride 1, padding 1, count_include_pad=False): the divisor is the number of taps inside the map;
+//   (d) AdaptiveAvgPool2d((1, 1)): [N][H][W][C] -> [N][C].
+#include <algorithm>
+#include <cmath>
+#include <memory>
+
+#include "i2v_common.h"
+
+namespace i2v {
+namespace {
+
+constexpr int INC_BM = 128;
+constexpr int INC_LS = 20;    // floats per staged row of 16
+constexpr int INC_SIDE = 299;
+constexpr int INC_MIN = 75;   // the smallest input that leaves a 1 x 1 map in front of the final pool
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+struct IncConvArgs {
+    const float* in;     // channels-last [N][Hi][Wi][inCS], the unit reads channels [inOff, inOff + 4 C4)
+    const float* wp;     // [nchunk][CoutPad][16]
+    const float2* ss;    // [CoutPad] (scale, shift)
+    float* out;          // [M][outCS], the unit writes channels [outOff, outOff + Cout)
+    long M;
+    int Hi, Wi, Ho, Wo;
+    int inCS, inOff, C4, G, nchunk;   // C4: groups of 4 input channels, G = taps * C4
+    int KW, sH, sW, pH, pW;
+    int Cout, CoutPad, outCS, outOff;
+};
+
+template <int NT>   // 16-column tiles per wave: BN = 16 NT
+__global__ __launch_bounds__(256) void inc_conv_kernel(IncConvArgs a) {
+    constexpr int BN = 16 * NT;
+    constexpr int WLD = (BN * 4 + 255) / 256;
+    __shared__ __attribute__((aligned(16))) float a_lds[2][INC_BM * INC_LS];
+    __shared__ __attribute__((aligned(16))) float w_lds[2][BN * INC_LS];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lr = lane & 15, kq = lane >> 4;
+    const int nNt = a.CoutPad / BN;
+    const int n0 = (int)(blockIdx.x % nNt) * BN;
+    const long m0 = (long)(blockIdx.x / nNt) * INC_BM;
+    const int q = tid & 3;
+
+    // the two staged rows of this thread: output position -> first input coordinate of its window
+    int rb[2], rh[2], rw[2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        long m = m0 + (tid >> 2) + 64 * u;
+        const bool ok = m < a.M;
+        if (!ok) m = 0;
+        const int wo = (int)(m % a.Wo); m /= a.Wo;
+        const int ho = (int)(m % a.Ho);
+        rb[u] = ok ? (int)(m / a.Ho) : -1;
+        rh[u] = ho * a.sH - a.pH; rw[u] = wo * a.sW - a.pW;
+    }
+
+    static_assert(WLD <= 2, "weight pieces per thread");
+    float4 pa0, pa1, pw0, pw1;   // (named, not arrays: arrays written under a branch go to scratch)
+    pw1 = make_float4(0.f, 0.f, 0.f, 0.f);
+    auto request = [&](int ch) {
+        const int g = ch * 4 + q;
+        const bool gok = g < a.G;
+        const int tap = gok ? g / a.C4 : 0;
+        const int c = (g - tap * a.C4) * 4;
+        const int dh = tap / a.KW, dw = tap - dh * a.KW;
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int h = rh[u] + dh, w = rw[u] + dw;
+            const bool ok = gok && rb[u] >= 0 && (unsigned)h < (unsigned)a.Hi && (unsigned)w < (unsigned)a.Wi;
+            const long off = ok ? (((long)rb[u] * a.Hi + h) * a.Wi + w) * a.inCS + a.inOff + c : 0;
+            const float4 v = *reinterpret_cast<const float4*>(a.in + off);
+            const float4 z = ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
+            if (u == 0) pa0 = z; else pa1 = z;
+        }
+        const float* wsrc = a.wp + ((long)ch * a.CoutPad + n0) * 16;
+        pw0 = *reinterpret_cast<const float4*>(wsrc + (tid < BN * 4 ? tid : 0) * 4);
+        if constexpr (WLD > 1) pw1 = *reinterpret_cast<const float4*>(wsrc + (tid + 256) * 4);
+    };
+    auto park = [&](int buf) {
+        *reinterpret_cast<float4*>(&a_lds[buf][(tid >> 2) * INC_LS + 4 * q]) = pa0;
+        *reinterpret_cast<float4*>(&a_lds[buf][((tid >> 2) + 64) * INC_LS + 4 * q]) = pa1;
+        if (tid < BN * 4) *reinterpret_cast<float4*>(&w_lds[buf][(tid >> 2) * INC_LS + 4 * q]) = pw0;
+        if constexpr (WLD > 1) *reinterpret_cast<float4*>(&w_lds[buf][((tid + 256) >> 2) * INC_LS + 4 * q]) = pw1;
+    };
+
+    f32x4 acc[2][NT];
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    request(0);
+    park(0);
+    __syncthreads();
+    for (int ch = 0; ch < a.nchunk; ++ch) {
+        const int buf = ch & 1;
+        request(ch + 1 < a.nchunk ? ch + 1 : ch);
+        // MFMA k-slot (lane >> 4) of step s carries K element 4 (lane >> 4) + s of the chunk, for both operands
+        float4 av[2], bv[NT];
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) av[mt] = *reinterpret_cast<const float4*>(&a_lds[buf][(wave * 32 + 16 * mt + lr) * INC_LS + 4 * kq]);
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) bv[nt] = *reinterpret_cast<const float4*>(&w_lds[buf][(16 * nt + lr) * INC_LS + 4 * kq]);
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt) {
+                const float as = s == 0 ? av[mt].x : s == 1 ? av[mt].y : s == 2 ? av[mt].z : av[mt].w;
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) {
+                    const float bs = s == 0 ? bv[nt].x : s == 1 ? bv[nt].y : s == 2 ? bv[nt].z : bv[nt].w;
+                    acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(as, bs, acc[mt][nt], 0, 0, 0);
+                }
+            }
+        if (ch + 1 < a.nchunk) park(buf ^ 1);
+        __syncthreads();
+    }
+
+    // C/D layout of the 16x16 MFMA: column = lane & 15, rows 4 (lane >> 4) + r
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+        const int n = n0 + 16 * nt + lr;
+        if (n >= a.Cout) continue;
+        const float2 ss = a.ss[n];
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const long m = m0 + wave * 32 + 16 * mt + 4 * kq + r;
+                if (m >= a.M) continue;
+                a.out[m * a.outCS + a.outOff + n] = fmaxf(fmaf(acc[mt][nt][r], ss.x, ss.y), 0.f);
+            }
+    }
+}
+
+// InceptionV3.forward :144-151 fused with the layout change: frames [N][3][Hi][Wi] -> channels-last [N][Ho][Wo][4] (channel 3 zero),
+// bilinear with align_corners=False in the arithmetic of torch's upsample_bilinear2d (Ho = Hi and Wo = Wi: weights (1, 0), the sample
+// is the pixel itself), then 2 x - 1 when `normalize`.
+__global__ __launch_bounds__(256) void inc_input_kernel(const float* __restrict__ frames, float* __restrict__ out, long N, int Hi, int Wi, int Ho,
+                                                        int Wo, int normalize) {
+    const long total = N * Ho * Wo;
+    const float sh = (float)Hi / (float)Ho, sw = (float)Wi / (float)Wo;   // area_pixel_compute_scale
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const int w = (int)(i % Wo), h = (int)((i / Wo) % Ho);
+        const long n = i / ((long)Wo * Ho);
+        // area_pixel_compute_source_index: max(scale * (dst + 0.5) - 0.5, 0)
+        const float fh = fmaxf(sh * (h + 0.5f) - 0.5f, 0.f), fw = fmaxf(sw * (w + 0.5f) - 0.5f, 0.f);
+        const int h0 = min((int)fh, Hi - 1), w0 = min((int)fw, Wi - 1);
+        const int h1 = h0 + (h0 < Hi - 1 ? 1 : 0), w1 = w0 + (w0 < Wi - 1 ? 1 : 0);
+        const float lh1 = fminf(fmaxf(fh - h0, 0.f), 1.f), lh0 = 1.f - lh1, lw1 = fminf(fmaxf(fw - w0, 0.f), 1.f), lw0 = 1.f - lw1;
+        float v[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float* pl = frames + (n * 3 + c) * (long)Hi * Wi;
+            v[c] = lh0 * (lw0 * pl[(long)h0 * Wi + w0] + lw1 * pl[(long)h0 * Wi + w1]) + lh1 * (lw0 * pl[(long)h1 * Wi + w0] + lw1 * pl[(long)h1 * Wi + w1]);
+            if (normalize) v[c] = 2.0f * v[c] - 1.0f;
+        }
+        *reinterpret_cast<float4*>(out + i * 4) = make_float4(v[0], v[1], v[2], 0.f);
+    }
+}
+
+struct IncPoolArgs {
+    const float* in; float* out;   // [N][Hi][Wi][C] -> channels [outOff, outOff + C) of [N][Ho][Wo][outCS]
+    long N;
+    int Hi, Wi, Ho, Wo, C, stride, pad, avg, outCS, outOff;
+};
+// 3 x 3 window; a tap outside the map takes no part: not in the maximum, not in the sum, not in the divisor
+__global__ __launch_bounds__(256) void inc_pool_kernel(IncPoolArgs a) {
+    const int C4 = a.C >> 2;
+    const long total = a.N * a.Ho * a.Wo * C4;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const int c4 = (int)(i % C4);
+        long p = i / C4;
+        const int wo = (int)(p % a.Wo);
+        const int ho = (int)((p / a.Wo) % a.Ho);
+        const long n = p / ((long)a.Wo * a.Ho);
+        float4 m = a.avg ? make_float4(0.f, 0.f, 0.f, 0.f) : make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+        int cnt = 0;
+        for (int dh = 0; dh < 3; ++dh) {
+            const int h = ho * a.stride - a.pad + dh;
+            if ((unsigned)h >= (unsigned)a.Hi) continue;
+            for (int dw = 0; dw < 3; ++dw) {
+                const int w = wo * a.stride - a.pad + dw;
+                if ((unsigned)w >= (unsigned)a.Wi) continue;
+                const float4 v = *reinterpret_cast<const float4*>(a.in + ((n * a.Hi + h) * a.Wi + w) * a.C + 4 * c4);
+                if (a.avg) { m.x += v.x; m.y += v.y; m.z += v.z; m.w += v.w; }
+                else { m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w); }
+                ++cnt;
+            }
+        }
+        if (a.avg) { const float d = (float)cnt; m.x /= d; m.y /= d; m.z /= d; m.w /= d; }
+        *reinterpret_cast<float4*>(a.out + p * a.outCS + a.outOff + 4 * c4) = m;
+    }
+}
+
+// AdaptiveAvgPool2d((1, 1)): [N][P][C] -> [N][C], the positions in order
+__global__ __launch_bounds__(256) void inc_global_avg_kernel(const float* __restrict__ in, float* __restrict__ out, long N, int P, int C) {
+    const long total = N * C;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const float* p = in + (i / C) * P * C + i % C;
+        float s = 0.f;
+        for (int j = 0; j < P; ++j) s += p[(long)j * C];
+        out[i] = s / (float)P;
+    }
+}
+
+unsigned grid_for(long total) { return (unsigned)std::min<long>((total + 255) / 256, 1L << 20); }
+
+struct Map { int H, W; long pos() const { return (long)H * W; } };
+
+struct ConvSpec { std::string name; int cin, cout, kh, kw, s, ph, pw; };
+
+const char* conv_shape_error(const ConvSpec& c) {
+    if (!(c.cin == 3 || (c.cin > 0 && c.cin % 16 == 0))) return "input channels must be 3 (stored as r, g, b, 0) or a multiple of 16";
+    if (c.cout <= 0) return "no output channels";
+    if (c.kh < 1 || c.kh > 7 || c.kw < 1 || c.kw > 7) return "kernel extents must be 1 to 7";
+    if (c.s != 1 && c.s != 2) return "stride must be 1 or 2";
+    if (c.ph < 0 || c.ph >= c.kh || c.pw < 0 || c.pw >= c.kw) return "padding must be smaller than the kernel";
+    return nullptr;
+}
+
+struct Unit {
+    ConvSpec spec;
+    DevBuf w, ss;
+    int CoutPad = 0, BN = 64, C4 = 0, nchunk = 0;
+    Map out(Map d) const { return Map{(d.H + 2 * spec.ph - spec.kh) / spec.s + 1, (d.W + 2 * spec.pw - spec.kw) / spec.s + 1}; }
+    int pack(const float* wsrc, const float* g, const float* b, const float* m, const float* v);
+    int load(const StateDict& sd);
+};
+
+// [Cout][Cin][KH][KW] -> [nchunk][CoutPad][16] with K = tap * CinP + c; BasicConv2d's BatchNorm2d(eps=0.001) in eval mode folded to
+// (scale, shift): (x - mean) / sqrt(var + eps) * weight + bias
+int Unit::pack(const float* wsrc, const float* g, const float* b, const float* m, const float* v) {
+    const int cin = spec.cin, cout = spec.cout, taps = spec.kh * spec.kw;
+    // column tile: the one that pads Cout least, the wider on a tie
+    int best = 128;
+    for (int bn_ : {64, 32})
+        if ((cout + bn_ - 1) / bn_ * bn_ < (cout + best - 1) / best * best) best = bn_;
+    BN = best;
+    CoutPad = (cout + BN - 1) / BN * BN;
+    const int CinP = (cin + 3) / 4 * 4;
+    C4 = CinP / 4;
+    nchunk = (taps * CinP + 15) / 16;
+    std::vector<float> p((size_t)nchunk * CoutPad * 16, 0.f);
+    for (int n = 0; n < cout; ++n)
+        for (int c = 0; c < cin; ++c)
+            for (int tap = 0; tap < taps; ++tap) {
+                const long kk = (long)tap * CinP + c;
+                p[((size_t)(kk / 16) * CoutPad + n) * 16 + kk % 16] = wsrc[((size_t)n * cin + c) * taps + tap];
+            }
+    if (int rc = w.upload(p.data(), p.size() * 4)) return rc;
+    std::vector<float> s((size_t)CoutPad * 2, 0.f);
+    for (int n = 0; n < cout; ++n) {
+        const double a = (double)g[n] / std::sqrt((double)v[n] + 1e-3);
+        s[2 * n] = (float)a;
+        s[2 * n + 1] = (float)((double)b[n] - (double)m[n] * a);
+    }
+    return ss.upload(s.data(), s.size() * 4);
+}
+
+int Unit::load(const StateDict& sd) {
+    const float* wsrc = sd.f32(spec.name + ".conv.weight", (int64_t)spec.cout * spec.cin * spec.kh * spec.kw);
+    const float* g = sd.f32(spec.name + ".bn.weight", spec.cout);
+    const float* b = sd.f32(spec.name + ".bn.bias", spec.cout);
+    const float* m = sd.f32(spec.name + ".bn.running_mean", spec.cout);
+    const float* v = sd.f32(spec.name + ".bn.running_var", spec.cout);
+    if (!wsrc || !g || !b || !m || !v) return I2V_E_MISSING;
+    return pack(wsrc, g, b, m, v);
+}
+
+// ---- topology: every Mixed block is a short program over the block input X, the block output Y and two temporaries T0, T1
+enum { X = 0, T0 = 1, T1 = 2, Y = 3 };
+enum { OP_CONV = 0, OP_POOL = 1 };
+struct Op { int op, arg, src, dst, off; };   // conv: arg = unit of the block; pool: arg = I2V_INCEPTION_POOL_*; off: channel offset in Y
+struct Block { std::string name; int cin = 0, cout = 0; std::vector<ConvSpec> convs; std::vector<Op> ops; };
+
+ConvSpec cs(const std::string& n, int cin, int cout, int kh = 1, int kw = 1, int s = 1, int ph = 0, int pw = 0) {
+    return ConvSpec{n, cin, cout, kh, kw, s, ph, pw};
+}
+
+// torchvision InceptionA with the FID patch (avg pool without the padding in its divisor); cat: 1x1, 5x5, 3x3dbl, pool
+Block block_a(const std::string& n, int cin, int pf) {
+    Block b{n, cin, 224 + pf};
+    b.convs = {cs(n + ".branch1x1", cin, 64), cs(n + ".branch5x5_1", cin, 48), cs(n + ".branch5x5_2", 48, 64, 5, 5, 1, 2, 2),
+               cs(n + ".branch3x3dbl_1", cin, 64), cs(n + ".branch3x3dbl_2", 64, 96, 3, 3, 1, 1, 1), cs(n + ".branch3x3dbl_3", 96, 96, 3, 3, 1, 1, 1),
+               cs(n + ".branch_pool", cin, pf)};
+    b.ops = {{OP_CONV, 0, X, Y, 0}, {OP_CONV, 1, X, T0, 0}, {OP_CONV, 2, T0, Y, 64}, {OP_CONV, 3, X, T0, 0}, {OP_CONV, 4, T0, T1, 0},
+             {OP_CONV, 5, T1, Y, 128}, {OP_POOL, I2V_INCEPTION_POOL_AVG, X, T0, 0}, {OP_CONV, 6, T0, Y, 224}};
+    return b;
+}
+// torchvision InceptionB (unpatched); cat: 3x3, 3x3dbl, max pool of the input
+Block block_b(const std::string& n, int cin) {
+    Block b{n, cin, 480 + cin};
+    b.convs = {cs(n + ".branch3x3", cin, 384, 3, 3, 2), cs(n + ".branch3x3dbl_1", cin, 64), cs(n + ".branch3x3dbl_2", 64, 96, 3, 3, 1, 1, 1),
+               cs(n + ".branch3x3dbl_3", 96, 96, 3, 3, 2)};
+    b.ops = {{OP_CONV, 0, X, Y, 0}, {OP_CONV, 1, X, T0, 0}, {OP_CONV, 2, T0, T1, 0}, {OP_CONV, 3, T1, Y, 384},
+             {OP_POOL, I2V_INCEPTION_POOL_MAX_S2, X, Y, 480}};
+    return b;
+}
+// InceptionC with the FID patch; cat: 1x1, 7x7, 7x7dbl, pool
+Block block_c(const std::string& n, int cin, int c7) {
+    Block b{n, cin, 768};
+    b.convs = {cs(n + ".branch1x1", cin, 192),
+               cs(n + ".branch7x7_1", cin, c7), cs(n + ".branch7x7_2", c7, c7, 1, 7, 1, 0, 3), cs(n + ".branch7x7_3", c7, 192, 7, 1, 1, 3, 0),
+               cs(n + ".branch7x7dbl_1", cin, c7), cs(n + ".branch7x7dbl_2", c7, c7, 7, 1, 1, 3, 0), cs(n + ".branch7x7dbl_3", c7, c7, 1, 7, 1, 0, 3),
+               cs(n + ".branch7x7dbl_4", c7, c7, 7, 1, 1, 3, 0), cs(n + ".branch7x7dbl_5", c7, 192, 1, 7, 1, 0, 3),
+               cs(n + ".branch_pool", cin, 192)};
+    b.ops = {{OP_CONV, 0, X, Y, 0}, {OP_CONV, 1, X, T0, 0}, {OP_CONV, 2, T0, T1, 0}, {OP_CONV, 3, T1, Y, 192},
+             {OP_CONV, 4, X, T0, 0}, {OP_CONV, 5, T0, T1, 0}, {OP_CONV, 6, T1, T0, 0}, {OP_CONV, 7, T0, T1, 0}, {OP_CONV, 8, T1, Y, 384},
+             {OP_POOL, I2V_INCEPTION_POOL_AVG, X, T0, 0}, {OP_CONV, 9, T0, Y, 576}};
+    return b;
+}
+// torchvision InceptionD (unpatched); cat: 3x3, 7x7x3, max pool of the input
+Block block_d(const std::string& n, int cin) {
+    Block b{n, cin, 512 + cin};
+    b.convs = {cs(n + ".branch3x3_1", cin, 192), cs(n + ".branch3x3_2", 192, 320, 3, 3, 2),
+               cs(n + ".branch7x7x3_1", cin, 192), cs(n + ".branch7x7x3_2", 192, 192, 1, 7, 1, 0, 3), cs(n + ".branch7x7x3_3", 192, 192, 7, 1, 1, 3, 0),
+               cs(n + ".branch7x7x3_4", 192, 192, 3, 3, 2)};
+    b.ops = {{OP_CONV, 0, X, T0, 0}, {OP_CONV, 1, T0, Y, 0}, {OP_CONV, 2, X, T0, 0}, {OP_CONV, 3, T0, T1, 0}, {OP_CONV, 4, T1, T0, 0},
+             {OP_CONV, 5, T0, Y, 320}, {OP_POOL, I2V_INCEPTION_POOL_MAX_S2, X, Y, 512}};
+    return b;
+}
+// InceptionE with the FID patches: E_1 (Mixed_7b) the unpadded-divisor avg pool, E_2 (Mixed_7c) a MAX pool; cat: 1x1, 3x3 (2a, 2b),
+// 3x3dbl (3a, 3b), pool
+Block block_e(const std::string& n, int cin, int pool) {
+    Block b{n, cin, 2048};
+    b.convs = {cs(n + ".branch1x1", cin, 320),
+               cs(n + ".branch3x3_1", cin, 384), cs(n + ".branch3x3_2a", 384, 384, 1, 3, 1, 0, 1), cs(n + ".branch3x3_2b", 384, 384, 3, 1, 1, 1, 0),
+               cs(n + ".branch3x3dbl_1", cin, 448), cs(n + ".branch3x3dbl_2", 448, 384, 3, 3, 1, 1, 1),
+               cs(n + ".branch3x3dbl_3a", 384, 384, 1, 3, 1, 0, 1), cs(n + ".branch3x3dbl_3b", 384, 384, 3, 1, 1, 1, 0),
+               cs(n + ".branch_pool", cin, 192)};
+    b.ops = {{OP_CONV, 0, X, Y, 0}, {OP_CONV, 1, X, T0, 0}, {OP_CONV, 2, T0, Y, 320}, {OP_CONV, 3, T0, Y, 704},
+             {OP_CONV, 4, X, T0, 0}, {OP_CONV, 5, T0, T1, 0}, {OP_CONV, 6, T1, Y, 1088}, {OP_CONV, 7, T1, Y, 1472},
+             {OP_POOL, pool, X, T0, 0}, {OP_CONV, 8, T0, Y, 1856}};
+    return b;
+}
+
+constexpr int N_STEM = 5, N_MIXED = 11;
+constexpr long INC_SUB_MAX = 1L << 31;   // floats per tensor of a sub-module call
+constexpr long INC_MAX_FLOATS = 1L << 40;
+
+}  // namespace
+}  // namespace i2v
+
+using namespace i2v;
+
+struct i2v_inception {
+    int device = 0;
+    bool loaded = false;
+    Unit stem[N_STEM];
+    Block blocks[N_MIXED];
+    std::vector<Unit> units[N_MIXED];
+    StreamOrder order;
+};
+
+namespace {
+
+void pool_geom(int kind, Map d, int* stride, int* pad, Map* o) {
+    *stride = kind == I2V_INCEPTION_POOL_MAX_S2 ? 2 : 1;
+    *pad = kind == I2V_INCEPTION_POOL_MAX_S2 ? 0 : 1;
+    *o = Map{(d.H + 2 * *pad - 3) / *stride + 1, (d.W + 2 * *pad - 3) / *stride + 1};
+}
+
+int conv_launch(const Unit& u, int B, const float* in, int inCS, int inOff, Map di, float* out, int outCS, int outOff, hipStream_t st) {
+    const Map d = u.out(di);
+    I2V_REQUIRE(d.H > 0 && d.W > 0, I2V_E_INVALID, "inception conv %s: a [%d, %d] map is smaller than its window", u.spec.name.c_str(), di.H, di.W);
+    IncConvArgs a{};
+    a.in = in; a.wp = u.w.as<float>(); a.ss = u.ss.as<float2>(); a.out = out;
+    a.M = (long)B * d.pos();
+    a.Hi = di.H; a.Wi = di.W; a.Ho = d.H; a.Wo = d.W;
+    a.inCS = inCS; a.inOff = inOff; a.C4 = u.C4; a.G = u.spec.kh * u.spec.kw * u.C4; a.nchunk = u.nchunk;
+    a.KW = u.spec.kw; a.sH = u.spec.s; a.sW = u.spec.s; a.pH = u.spec.ph; a.pW = u.spec.pw;
+    a.Cout = u.spec.cout; a.CoutPad = u.CoutPad; a.outCS = outCS; a.outOff = outOff;
+    I2V_REQUIRE(inCS % 4 == 0 && inOff % 4 == 0 && inOff >= 0 && inOff + 4 * u.C4 <= inCS && outOff >= 0 && outOff + u.spec.cout <= outCS, I2V_E_INVALID,
+                "inception conv %s: channel slice [%d, +%d) of %d -> [%d, +%d) of %d", u.spec.name.c_str(), inOff, 4 * u.C4, inCS, outOff,
+                u.spec.cout, outCS);
+    const long nblk = (a.M + INC_BM - 1) / INC_BM * (u.CoutPad / u.BN);
+    I2V_REQUIRE(nblk > 0 && nblk < (1L << 31), I2V_E_INVALID, "inception conv %s: grid of %ld workgroups", u.spec.name.c_str(), nblk);
+    if (u.BN == 128) hipLaunchKernelGGL(inc_conv_kernel<8>, dim3((unsigned)nblk), dim3(256), 0, st, a);
+    else if (u.BN == 64) hipLaunchKernelGGL(inc_conv_kernel<4>, dim3((unsigned)nblk), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(inc_conv_kernel<2>, dim3((unsigned)nblk), dim3(256), 0, st, a);
+    I2V_HIP_CHECK(hipGetLastError());
+    return I2V_OK;
+}
+
+int pool_launch(int kind, int B, const float* in, int C, Map di, float* out, int outCS, int outOff, hipStream_t st) {
+    IncPoolArgs a{};
+    Map o;
+    pool_geom(kind, di, &a.stride, &a.pad, &o);
+    I2V_REQUIRE(o.H > 0 && o.W > 0, I2V_E_INVALID, "inception pool: a [%d, %d] map is smaller than the 3 x 3 window", di.H, di.W);
+    I2V_REQUIRE(C > 0 && C % 4 == 0 && outCS % 4 == 0 && outOff % 4 == 0 && outOff >= 0 && outOff + C <= outCS, I2V_E_INVALID,
+                "inception pool: %d channels -> [%d, +%d) of %d (multiples of 4 are needed)", C, outOff, C, outCS);
+    a.in = in; a.out = out; a.N = B; a.Hi = di.H; a.Wi = di.W; a.Ho = o.H; a.Wo = o.W; a.C = C;
+    a.avg = kind == I2V_INCEPTION_POOL_AVG ? 1 : 0; a.outCS = outCS; a.outOff = outOff;
+    hipLaunchKernelGGL(inc_pool_kernel, dim3(grid_for((long)B * o.pos() * (C / 4))), dim3(256), 0, st, a);
+    I2V_HIP_CHECK(hipGetLastError());
+    return I2V_OK;
+}
+
+// One walk of the network serves the block shapes and the workspace size (dry: no buffers, no launches) and the forward.
+struct Walk {
+    const i2v_inception* net;
+    int B;
+    bool dry;
+    hipStream_t st;
+    size_t act_floats = 0, t_floats[2] = {0, 0};   // dry: the largest block-level tensor / the largest use of each temporary
+    Map bdim[4] = {};                              // map of every block output reached
+
+    void need(size_t* slot, long floats) { *slot = std::max(*slot, (size_t)floats); }
+
+    // Mixed block i: x [B][d][cin] -> y [B][*dout][cout]
+    int mixed(int i, const float* x, Map d, float* y, float* t0, float* t1, Map* dout) {
+        const Block& b = net->blocks[i];
+        const float* src[4] = {x, t0, t1, nullptr};
+        float* dst[4] = {nullptr, t0, t1, y};
+        int cs_[4] = {b.cin, 0, 0, b.cout};   // channels of what each buffer holds
+        Map dm[4] = {d, d, d, d};
+        for (const Op& op : b.ops) {
+            Map o;
+            int c;
+            if (op.op == OP_CONV) {
+                const Unit& u = net->units[i][op.arg];
+                o = u.out(dm[op.src]);
+                c = u.spec.cout;
+                I2V_REQUIRE(o.H > 0 && o.W > 0, I2V_E_INVALID, "inception %s: a [%d, %d] map is too small", u.spec.name.c_str(), d.H, d.W);
+                if (!dry)
+                    if (int rc = conv_launch(u, B, src[op.src], cs_[op.src], 0, dm[op.src], dst[op.dst], op.dst == Y ? b.cout : c, op.off, st)) return rc;
+            } else {
+                int s, p;
+                pool_geom(op.arg, dm[op.src], &s, &p, &o);
+                c = cs_[op.src];
+                I2V_REQUIRE(o.H > 0 && o.W > 0, I2V_E_INVALID, "inception %s: a [%d, %d] map is too small", b.name.c_str(), d.H, d.W);
+                if (!dry)
+                    if (int rc = pool_launch(op.arg, B, src[op.src], c, dm[op.src], dst[op.dst], op.dst == Y ? b.cout : c, op.off, st)) return rc;
+            }
+            dm[op.dst] = o;
+            if (op.dst != Y) {
+                cs_[op.dst] = c;
+                need(&t_floats[op.dst - T0], (long)B * o.pos() * c);
+            }
+        }
+        *dout = dm[Y];
+        need(&act_floats, (long)B * dout->pos() * b.cout);
+        return I2V_OK;
+    }
+
+    // x [B][H][W][4] -> the requested blocks; a, b: the ping-pong buffers of block-level tensors (null when dry, as the taps may be)
+    int run(const float* x, int H, int W, float* const* taps, int last, float* a, float* b, float* t0, float* t1) {
+        int rc;
+        Map d{H, W}, o;
+        const float* cur = x;
+        int C = 4;
+        auto other = [&]() { return cur == a ? b : a; };
+        auto conv = [&](const Unit& u, float* dst) {
+            o = u.out(d);
+            if (o.H <= 0 || o.W <= 0) { set_error("inception %s: a [%d, %d] map is too small", u.spec.name.c_str(), d.H, d.W); return (int)I2V_E_INVALID; }
+            need(&act_floats, (long)B * o.pos() * u.spec.cout);
+            if (!dry)
+                if (int r = conv_launch(u, B, cur, C, 0, d, dst, u.spec.cout, 0, st)) return r;
+            cur = dst; d = o; C = u.spec.cout;
+            return (int)I2V_OK;
+        };
+        auto pool_a = [&](float* dst) {   // MaxPool2d(kernel_size=3, stride=2) between the stem blocks
+            int s, p;
+            pool_geom(I2V_INCEPTION_POOL_MAX_S2, d, &s, &p, &o);
+            if (o.H <= 0 || o.W <= 0) { set_error("inception: a [%d, %d] map is too small for MaxPool2d(3, 2)", d.H, d.W); return (int)I2V_E_INVALID; }
+            need(&act_floats, (long)B * o.pos() * C);
+            if (!dry)
+                if (int r = pool_launch(I2V_INCEPTION_POOL_MAX_S2, B, cur, C, d, dst, C, 0, st)) return r;
+            cur = dst; d = o;
+            return (int)I2V_OK;
+        };
+        const Unit* s = net->stem;
+        // block 0: Conv2d_1a_3x3, Conv2d_2a_3x3, Conv2d_2b_3x3, max pool
+        if ((rc = conv(s[0], a)) || (rc = conv(s[1], b)) || (rc = conv(s[2], a)) || (rc = pool_a(taps[0] ? taps[0] : b))) return rc;
+        bdim[0] = d;
+        if (last == 0) return I2V_OK;
+        // block 1: Conv2d_3b_1x1, Conv2d_4a_3x3, max pool
+        if ((rc = conv(s[3], other())) || (rc = conv(s[4], other())) || (rc = pool_a(taps[1] ? taps[1] : other()))) return rc;
+        bdim[1] = d;
+        if (last == 1) return I2V_OK;
+        // block 2: Mixed_5b .. Mixed_6e; block 3: Mixed_7a .. Mixed_7c, the global average
+        for (int i = 0; i < N_MIXED; ++i) {
+            float* y = i == 7 && taps[2] ? taps[2] : other();
+            if ((rc = mixed(i, cur, d, y, t0, t1, &o))) return rc;
+            cur = y; d = o; C = net->blocks[i].cout;
+            if (i == 7) {
+                bdim[2] = d;
+                if (last == 2) return I2V_OK;
+            }
+        }
+        bdim[3] = Map{1, 1};
+        if (dry) return I2V_OK;
+        hipLaunchKernelGGL(inc_global_avg_kernel, dim3(grid_for((long)B * C)), dim3(256), 0, st, cur, taps[3], (long)B, (int)d.pos(), C);
+        I2V_HIP_CHECK(hipGetLastError());
+        return I2V_OK;
+    }
+};
+
+struct IncWs { size_t a, b, t0, t1, total; };
+
+int inc_ws(const i2v_inception* net, int B, int H, int W, int last, IncWs* L, Map* bdim = nullptr) {
+    Walk wk{net, B, true, nullptr};
+    float* none[4] = {nullptr, nullptr, nullptr, nullptr};
+    if (int rc = wk.run(nullptr, H, W, none, last, nullptr, nullptr, nullptr, nullptr)) return rc;
+    if (bdim) std::copy(wk.bdim, wk.bdim + 4, bdim);
+    size_t o = 0;
+    auto take = [&](size_t floats) { size_t r = o; o = align_up(o + floats * 4, 256); return r; };
+    L->a = take(wk.act_floats);
+    L->b = take(wk.act_floats);
+    L->t0 = take(wk.t_floats[0]);
+    L->t1 = take(wk.t_floats[1]);
+    L->total = o;
+    return I2V_OK;
+}
+
+const int BLOCK_C[4] = {64, 192, 768, 2048};
+
+bool inc_dims_ok(int h, int w) { return h >= INC_MIN && w >= INC_MIN; }
+
+}  // namespace
+
+extern "C" {
+
+int i2v_inception_create(i2v_inception** out) {
+    I2V_REQUIRE(out, I2V_E_INVALID, "i2v_inception_create: null argument");
+    int ndev = 0;
+    I2V_HIP_CHECK(hipGetDeviceCount(&ndev));
+    I2V_REQUIRE(ndev > 0, I2V_E_HIP, "i2v_inception_create: no HIP device");
+    auto n = std::make_unique<i2v_inception>();
+    I2V_HIP_CHECK(hipGetDevice(&n->device));
+    n->stem[0].spec = cs("Conv2d_1a_3x3", 3, 32, 3, 3, 2);
+    n->stem[1].spec = cs("Conv2d_2a_3x3", 32, 32, 3, 3);
+    n->stem[2].spec = cs("Conv2d_2b_3x3", 32, 64, 3, 3, 1, 1, 1);
+    n->stem[3].spec = cs("Conv2d_3b_1x1", 64, 80);
+    n->stem[4].spec = cs("Conv2d_4a_3x3", 80, 192, 3, 3);
+    n->blocks[0] = block_a("Mixed_5b", 192, 32);
+    n->blocks[1] = block_a("Mixed_5c", 256, 64);
+    n->blocks[2] = block_a("Mixed_5d", 288, 64);
+    n->blocks[3] = block_b("Mixed_6a", 288);
+    n->blocks[4] = block_c("Mixed_6b", 768, 128);
+    n->blocks[5] = block_c("Mixed_6c", 768, 160);
+    n->blocks[6] = block_c("Mixed_6d", 768, 160);
+    n->blocks[7] = block_c("Mixed_6e", 768, 192);
+    n->blocks[8] = block_d("Mixed_7a", 768);
+    n->blocks[9] = block_e("Mixed_7b", 1280, I2V_INCEPTION_POOL_AVG);
+    n->blocks[10] = block_e("Mixed_7c", 2048, I2V_INCEPTION_POOL_MAX_S1);
+    for (int i = 0; i < N_MIXED; ++i) {
+        n->units[i].resize(n->blocks[i].convs.size());
+        for (size_t j = 0; j < n->units[i].size(); ++j) {
+            n->units[i][j].spec = n->blocks[i].convs[j];
+            if (const char* why = conv_shape_error(n->units[i][j].spec)) {
+                set_error("i2v_inception_create: %s: %s", n->units[i][j].spec.name.c_str(), why);
+                return I2V_E_INVALID;
+            }
+        }
+    }
+    *out = n.release();
+    return I2V_OK;
+}
+
+void i2v_inception_destroy(i2v_inception* n) { delete n; }
+
+int i2v_inception_load(i2v_inception* n, const i2v_tensor* tensors, int32_t n_tensors) {
+    if (n) I2V_REQUIRE_DEVICE(n->device, "i2v_inception_load");
+    I2V_REQUIRE(n && tensors && n_tensors > 0, I2V_E_INVALID, "i2v_inception_load: null argument");
+    StateDict sd(tensors, n_tensors);
+    n->loaded = false;
+    for (Unit& u : n->stem)
+        if (int rc = u.load(sd)) return rc;
+    for (auto& us : n->units)
+        for (Unit& u : us)
+            if (int rc = u.load(sd)) return rc;
+    n->loaded = true;
+    return I2V_OK;
+}
+
+int i2v_inception_block_shape(const i2v_inception* n, int32_t h, int32_t w, int32_t block, int32_t* dims) {
+    I2V_REQUIRE(n && dims && block >= 0 && block <= 3, I2V_E_INVALID, "i2v_inception_block_shape: bad argument");
+    I2V_REQUIRE(inc_dims_ok(h, w), I2V_E_INVALID, "i2v_inception_block_shape: a %d x %d input is too small (at least %d x %d is needed)", h, w, INC_MIN,
+                INC_MIN);
+    IncWs L;
+    Map bd[4];
+    if (int rc = inc_ws(n, 1, h, w, block, &L, bd)) return rc;
+    dims[0] = bd[block].H; dims[1] = bd[block].W; dims[2] = BLOCK_C[block];
+    return I2V_OK;
+}
+
+size_t i2v_inception_workspace_bytes(const i2v_inception* n, int32_t batch, int32_t h, int32_t w, int32_t last_block) {
+    if (!n || batch <= 0 || !inc_dims_ok(h, w) || last_block < 0 || last_block > 3) return 0;
+    IncWs L;
+    if (inc_ws(n, batch, h, w, last_block, &L)) return 0;
+    return L.total;
+}
+
+int i2v_inception_input_stage(const float* frames, int32_t n, int32_t hi, int32_t wi, int32_t resize, int32_t normalize, float* out, void* stream) {
+    I2V_REQUIRE(frames && out && n > 0 && hi > 0 && wi > 0, I2V_E_INVALID, "i2v_inception_input_stage: bad argument");
+    const int ho = resize ? INC_SIDE : hi, wo = resize ? INC_SIDE : wi;
+    I2V_REQUIRE((long)n * 3 * hi * wi < INC_MAX_FLOATS && (long)n * 4 * ho * wo < INC_MAX_FLOATS, I2V_E_INVALID,
+                "i2v_inception_input_stage: %d frames is too large", n);
+    hipLaunchKernelGGL(inc_input_kernel, dim3(grid_for((long)n * ho * wo)), dim3(256), 0, static_cast<hipStream_t>(stream), frames, out, (long)n, hi, wi,
+                       ho, wo, normalize ? 1 : 0);
+    I2V_HIP_CHECK(hipGetLastError());
+    return I2V_OK;
+}
+
+int i2v_inception_features(i2v_inception* n, const float* x, int32_t batch, int32_t h, int32_t w, float* block0, float* block1, float* block2,
+                           float* block3, void* workspace, size_t workspace_bytes, void* stream) {
+    if (n) I2V_REQUIRE_DEVICE(n->device, "i2v_inception_features");
+    I2V_REQUIRE(n && n->loaded, I2V_E_STATE, "i2v_inception_features: weights not loaded");
+    I2V_REQUIRE(x && workspace && batch > 0, I2V_E_INVALID, "i2v_inception_features: bad argument");
+    float* taps[4] = {block0, block1, block2, block3};
+    int last = -1;
+    for (int k = 0; k < 4; ++k)
+        if (taps[k]) last = k;
+    I2V_REQUIRE(last >= 0, I2V_E_INVALID, "i2v_inception_features: no block requested");
+    I2V_REQUIRE(inc_dims_ok(h, w), I2V_E_INVALID,
+                "i2v_inception_features: a %d x %d input is too small: at least %d x %d is needed (the map in front of the final pool would be empty)", h,
+                w, INC_MIN, INC_MIN);
+    I2V_REQUIRE((long)batch * h * w * 32 < INC_MAX_FLOATS, I2V_E_INVALID, "i2v_inception_features: batch %d x [%d, %d] is too large", batch, h, w);
+    IncWs L;
+    if (int rc = inc_ws(n, batch, h, w, last, &L)) return rc;
+    I2V_REQUIRE(workspace_bytes >= L.total, I2V_E_WORKSPACE, "i2v_inception_features: workspace %zu < required %zu", workspace_bytes, L.total);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rco = n->order.entry(st)) return rco;
+    StreamOrderMark mark{&n->order, st};
+    char* ws = static_cast<char*>(workspace);
+    auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    Walk wk{n, batch, false, st};
+    return wk.run(x, h, w, taps, last, F(L.a), F(L.b), F(L.t0), F(L.t1));
+}
+
+// ---- sub-modules, individually callable on channels-last tensors (for tests and inspection)
+
+int i2v_inception_conv_unit(const float* x, int32_t n, int32_t h, int32_t w, int32_t in_cs, int32_t in_off, const float* weight, const float* bn_weight,
+                            const float* bn_bias, const float* bn_mean, const float* bn_var, int32_t cin, int32_t cout, int32_t kh, int32_t kw,
+                            int32_t stride, int32_t pad_h, int32_t pad_w, float* out, int32_t out_cs, int32_t out_off, size_t out_floats, void* stream) {
+    I2V_REQUIRE(x && weight && bn_weight && bn_bias && bn_mean && bn_var && out && n > 0 && h > 0 && w > 0, I2V_E_INVALID,
+                "i2v_inception_conv_unit: bad argument");
+    Unit u;
+    u.spec = ConvSpec{"unit", cin, cout, kh, kw, stride, pad_h, pad_w};
+    if (const char* why = conv_shape_error(u.spec)) {
+        set_error("i2v_inception_conv_unit: %d -> %d channels, kernel (%d, %d), stride %d, padding (%d, %d): %s", cin, cout, kh, kw, stride, pad_h, pad_w, why);
+        return I2V_E_INVALID;
+    }
+    const Map o = u.out(Map{h, w});
+    I2V_REQUIRE(o.H > 0 && o.W > 0, I2V_E_INVALID, "i2v_inception_conv_unit: a [%d, %d] map is smaller than the (%d, %d) window", h, w, kh, kw);
+    I2V_REQUIRE((long)n * h * w * in_cs < INC_SUB_MAX && (long)n * o.pos() * out_cs < INC_SUB_MAX, I2V_E_INVALID,
+                "i2v_inception_conv_unit: batch %d x [%d, %d] is too large", n, h, w);
+    I2V_REQUIRE(out_cs > 0 && out_floats >= (size_t)n * o.pos() * out_cs, I2V_E_WORKSPACE, "i2v_inception_conv_unit: output of %zu floats < required %zu",
+                out_floats, (size_t)n * o.pos() * out_cs);
+    if (int rc = u.pack(weight, bn_weight, bn_bias, bn_mean, bn_var)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rc = conv_launch(u, n, x, in_cs, in_off, Map{h, w}, out, out_cs, out_off, st)) return rc;
+    I2V_HIP_CHECK(hipStreamSynchronize(st));   // the packed weights die with this call
+    return I2V_OK;
+}
+
+int i2v_inception_pool(const float* x, int32_t n, int32_t h, int32_t w, int32_t c, int32_t kind, float* out, int32_t out_cs, int32_t out_off,
+                       size_t out_floats, void* stream) {
+    I2V_REQUIRE(x && out && n > 0 && h > 0 && w > 0, I2V_E_INVALID, "i2v_inception_pool: bad argument");
+    I2V_REQUIRE(kind == I2V_INCEPTION_POOL_MAX_S2 || kind == I2V_INCEPTION_POOL_MAX_S1 || kind == I2V_INCEPTION_POOL_AVG, I2V_E_INVALID,
+                "i2v_inception_pool: unknown kind %d", kind);
+    int s, p;
+    Map o;
+    pool_geom(kind, Map{h, w}, &s, &p, &o);
+    I2V_REQUIRE(o.H > 0 && o.W > 0, I2V_E_INVALID, "i2v_inception_pool: a [%d, %d] map is smaller than the 3 x 3 window", h, w);
+    I2V_REQUIRE(c > 0 && out_cs > 0 && (long)n * h * w * c < INC_SUB_MAX && (long)n * o.pos() * out_cs < INC_SUB_MAX, I2V_E_INVALID,
+                "i2v_inception_pool: batch %d x [%d, %d] x %d is too large", n, h, w, c);
+    I2V_REQUIRE(out_floats >= (size_t)n * o.pos() * out_cs, I2V_E_WORKSPACE, "i2v_inception_pool: output of %zu floats < required %zu", out_floats,
+                (size_t)n * o.pos() * out_cs);
+    return pool_launch(kind, n, x, c, Map{h, w}, out, out_cs, out_off, static_cast<hipStream_t>(stream));
+}
+
+int i2v_inception_global_avg(const float* x, int32_t n, int32_t h, int32_t w, int32_t c, float* out, void* stream) {
+    I2V_REQUIRE(x && out && n > 0 && h > 0 && w > 0 && c > 0, I2V_E_INVALID, "i2v_inception_global_avg: bad argument");
+    I2V_REQUIRE((long)n * h * w * c < INC_SUB_MAX, I2V_E_INVALID, "i2v_inception_global_avg: batch %d x [%d, %d] x %d is too large", n, h, w, c);
+    hipLaunchKernelGGL(inc_global_avg_kernel, dim3(grid_for((long)n * c)), dim3(256), 0, static_cast<hipStream_t>(stream), x, out, (long)n, h * w, c);
+    I2V_HIP_CHECK(hipGetLastError());
+    return I2V_OK;
+}
+
+int i2v_inception_mixed_shape(const i2v_inception* n, int32_t block, int32_t h, int32_t w, int32_t* cin, int32_t* cout, int32_t* out_hw) {
+    I2V_REQUIRE(n && block >= 0 && block < N_MIXED && h > 0 && w > 0, I2V_E_INVALID, "i2v_inception_mixed_shape: block %d on a [%d, %d] map", block, h, w);
+    Walk wk{n, 1, true, nullptr};
+    Map o;
+    if (int rc = wk.mixed(block, nullptr, Map{h, w}, nullptr, nullptr, nullptr, &o)) return rc;
+    if (cin) *cin = n->blocks[block].cin;
+    if (cout) *cout = n->blocks[block].cout;
+    if (out_hw) { out_hw[0] = o.H; out_hw[1] = o.W; }
+    return I2V_OK;
+}
+
+size_t i2v_inception_mixed_workspace_bytes(const i2v_inception* n, int32_t block, int32_t batch, int32_t h, int32_t w) {
+    if (!n || block < 0 || block >= N_MIXED || batch <= 0 || h <= 0 || w <= 0) return 0;
+    Walk wk{n, batch, true, nullptr};
+    Map o;
+    if (wk.mixed(block, nullptr, Map{h, w}, nullptr, nullptr, nullptr, &o)) return 0;
+    return align_up(wk.t_floats[0] * 4, 256) + align_up(wk.t_floats[1] * 4, 256);
+}
+
+int i2v_inception_mixed_forward(i2v_inception* n, int32_t block, const float* x, int32_t batch, int32_t h, int32_t w, float* out, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+    I2V_REQUIRE(n, I2V_E_INVALID, "i2v_inception_mixed_forward: null handle");
+    I2V_REQUIRE_DEVICE(n->device, "i2v_inception_mixed_forward");
+    I2V_REQUIRE(n->loaded, I2V_E_STATE, "i2v_inception_mixed_forward: weights not loaded");
+    I2V_REQUIRE(block >= 0 && block < N_MIXED, I2V_E_INVALID, "i2v_inception_mixed_forward: unknown block %d", block);
+    I2V_REQUIRE(x && out && workspace && batch > 0 && h > 0 && w > 0, I2V_E_INVALID, "i2v_inception_mixed_forward: bad argument");
+    I2V_REQUIRE((long)batch * h * w * 2048 < INC_SUB_MAX, I2V_E_INVALID, "i2v_inception_mixed_forward: batch %d x [%d, %d] is too large", batch, h, w);
+    Walk dry{n, batch, true, nullptr};
+    Map o;
+    if (int rc = dry.mixed(block, nullptr, Map{h, w}, nullptr, nullptr, nullptr, &o)) return rc;
+    const size_t t0b = align_up(dry.t_floats[0] * 4, 256), need = t0b + align_up(dry.t_floats[1] * 4, 256);
+    I2V_REQUIRE(workspace_bytes >= need, I2V_E_WORKSPACE, "i2v_inception_mixed_forward: workspace %zu < required %zu", workspace_bytes, need);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rco = n->order.entry(st)) return rco;
+    StreamOrderMark mark{&n->order, st};
+    Walk wk{n, batch, false, st};
+    char* ws = static_cast<char*>(workspace);
+    return wk.mixed(block, x, Map{h, w}, out, reinterpret_cast<float*>(ws), reinterpret_cast<float*>(ws + t0b), &o);
+}
+
+}  // extern "C"

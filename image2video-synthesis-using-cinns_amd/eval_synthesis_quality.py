@@ -7,8 +7,11 @@ One video is sampled per real clip from its first frame, and the generated set i
 Frechet distance in the features of the dynamic-texture I3D, metrics/DTFVD, on the device; the length-32 network when
 ``-seq_length > 16``) and ``-LPIPS True -vgg_path FILE -lpips_path FILE`` (LPIPS on the native VGG-16 trunk over the compared frames
 flattened to images, the reference's rule: the mean over floor(n / 10) batch means; the files are torchvision's vgg16 state_dict and the
-``vgg.pth`` lin weights of the LPIPS release, nothing is downloaded); they print the reference's lines.  ``-FID`` and ``-FVD`` (the
-TensorFlow FVD) exit with a "not built" message, and so does ``-LPIPS`` without its two paths.
+``vgg.pth`` lin weights of the LPIPS release, nothing is downloaded) and ``-FID True -inception_path FILE`` (the Frechet distance in the
+2048 features of the native FID Inception-v3, metrics/FID, over the compared frames flattened to images in batches of 50 -- the
+reference's ``calculate_FID``, which drops the ragged last batch; the file is pytorch-fid's ``pt_inception-2015-12-05-6726825d.pth``); they
+print the reference's lines.  ``-FVD`` (the TensorFlow FVD) exits with a "not built" message, and so do ``-LPIPS`` and ``-FID`` without
+their paths.
 
 The reference's data package is out of scope, so the real clips come from ``-clips_npy FILE``: ``[N, seq_length + 1, 3, H, W]`` float in
 [-1, 1], what ``get_eval_loader(dataset, seq_length + 1, ...)`` yields.  Which real frames are compared keeps the reference's per-dataset
@@ -22,14 +25,15 @@ import argparse
 import os
 import sys
 
-NOT_BUILT = {"FID": "the Inception-v3 FID (metrics/FID) is not built",
-             "FVD": "the TensorFlow FVD (metrics/FVD, a TF-hub I3D) is not built; the Kinetics FVD on the device is "
+NOT_BUILT = {"FVD": "the TensorFlow FVD (metrics/FVD, a TF-hub I3D) is not built; the Kinetics FVD on the device is "
                     "metrics/PyTorch_FVD (utils.auxiliaries.evaluate_FVD_prior)"}
 
 
 NEEDS_PATHS = {"LPIPS": (("vgg_path", "lpips_path"), "LPIPS needs the VGG-16 ImageNet weights and the LPIPS lin weights, which are not part of this "
                                                      "package: pass -vgg_path FILE (torchvision's vgg16 state_dict) and -lpips_path FILE "
-                                                     "(vgg.pth of the LPIPS release)")}
+                                                     "(vgg.pth of the LPIPS release)"),
+               "FID": (("inception_path",), "FID needs the FID Inception-v3 weights, which are not part of this package and are never downloaded: "
+                                            "pass -inception_path FILE (pytorch-fid's pt_inception-2015-12-05-6726825d.pth)")}
 
 
 def parse(argv=None):
@@ -49,6 +53,7 @@ def parse(argv=None):
     parser.add_argument('-i3d_path', type=str, help="checkpoint of the dynamic-texture I3D (I3D_16.pth.tar / I3D_32.pth.tar)")
     parser.add_argument('-vgg_path', type=str, help="torchvision vgg16 state_dict file (vgg16-397923af.pth) for -LPIPS; never downloaded")
     parser.add_argument('-lpips_path', type=str, help="lin weights of the LPIPS release (vgg.pth: lin{k}.model.1.weight) for -LPIPS; never downloaded")
+    parser.add_argument('-inception_path', type=str, help="FID Inception state_dict file (pt_inception-2015-12-05-6726825d.pth) for -FID; never downloaded")
     parser.add_argument('-seed', type=int, default=249, help="seed of the latent residuals (the reference fixes 249)")
     parser.add_argument('-embed_npy', type=str, help="[N,E] conditioning embeddings (one row per clip)")
     parser.add_argument('-embed_seed', type=int, help="draw synthetic conditioning embeddings with this seed")
@@ -60,9 +65,9 @@ def parse(argv=None):
     for flag, (paths, why) in NEEDS_PATHS.items():
         if getattr(args, flag) and not all(getattr(args, p) for p in paths):
             raise SystemExit(f"eval_synthesis_quality: -{flag} is not built: {why}")
-    if not args.DTFVD and not args.LPIPS:
-        raise SystemExit("eval_synthesis_quality: nothing to evaluate -- pass -DTFVD True or -LPIPS True -vgg_path FILE -lpips_path FILE (the "
-                         "metrics of this script that are built)")
+    if not args.DTFVD and not args.LPIPS and not args.FID:
+        raise SystemExit("eval_synthesis_quality: nothing to evaluate -- pass -DTFVD True or -LPIPS True -vgg_path FILE -lpips_path FILE or "
+                         "-FID True -inception_path FILE (the metrics of this script that are built)")
     if not args.clips_npy:
         raise SystemExit("eval_synthesis_quality: the data loaders are not built -- pass the real clips with -clips_npy FILE "
                          "([N, seq_length + 1, 3, H, W] in [-1, 1])")
@@ -116,11 +121,23 @@ def main(argv=None):
     assert seq2.shape == seq1.shape, (tuple(seq1.shape), tuple(seq2.shape))
 
     result = None
+    if args.FID or args.LPIPS:
+        pd_imgs = seq1.reshape(-1, *seq1.shape[2:])
+        gt_imgs = seq2.reshape(-1, *seq2.shape[2:])
+    if args.FID:
+        from metrics.FID.FID_Score import calculate_FID
+        from metrics.FID.inception import InceptionV3
+        print('Evaluate FID')
+        inception = InceptionV3(path=args.inception_path)   # normalize_input=False as in the reference: the frames enter in [-1, 1]
+        batch_size = 50
+        FID, _ = calculate_FID(inception, pd_imgs, gt_imgs, batch_size, 2048)
+        del inception
+        torch.cuda.empty_cache()
+        print(f'FID score of {FID}')
+        result = FID
     if args.LPIPS:
         from stage2_cINN.AE.modules.LPIPS import LPIPS, lpips_score
         print('Evaluate LPIPS')
-        pd_imgs = seq1.reshape(-1, *seq1.shape[2:])
-        gt_imgs = seq2.reshape(-1, *seq2.shape[2:])
         lpips_vgg = LPIPS(vgg_path=args.vgg_path, lin_path=args.lpips_path).cuda().eval()
         result = lpips_score(lpips_vgg, pd_imgs, gt_imgs)
         del lpips_vgg

@@ -152,6 +152,21 @@ SYMBOLS = {
     "i2v_vgg_reduce_workspace_bytes": (c_size_t, [c_int32]),
     "i2v_lpips_layer": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_size_t, c_void_p]),
     "i2v_vgg_pairdiff_update": (c_int32, [c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "i2v_inception_create": (c_int32, [POINTER(c_void_p)]),
+    "i2v_inception_destroy": (None, [c_void_p]),
+    "i2v_inception_load": (c_int32, [c_void_p, POINTER(_Tensor), c_int32]),
+    "i2v_inception_block_shape": (c_int32, [c_void_p, c_int32, c_int32, c_int32, POINTER(c_int32)]),
+    "i2v_inception_workspace_bytes": (c_size_t, [c_void_p, c_int32, c_int32, c_int32, c_int32]),
+    "i2v_inception_input_stage": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "i2v_inception_features": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                         c_void_p]),
+    "i2v_inception_conv_unit": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_size_t, c_void_p]),
+    "i2v_inception_pool": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_size_t, c_void_p]),
+    "i2v_inception_global_avg": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "i2v_inception_mixed_shape": (c_int32, [c_void_p, c_int32, c_int32, c_int32, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),
+    "i2v_inception_mixed_workspace_bytes": (c_size_t, [c_void_p, c_int32, c_int32, c_int32, c_int32]),
+    "i2v_inception_mixed_forward": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_size_t, c_void_p]),
     "i2v_dec_create": (c_int32, [POINTER(DecCfg), POINTER(c_void_p)]),
     "i2v_dec_destroy": (None, [c_void_p]),
     "i2v_dec_load": (c_int32, [c_void_p, POINTER(_Tensor), c_int32]),
@@ -1468,3 +1483,165 @@ def vgg_pairdiff_update(maps, acc):
     with torch.cuda.device(maps.device):
         _check(lib().i2v_vgg_pairdiff_update(maps.data_ptr(), r, maps.numel() // r, acc.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
                "i2v_vgg_pairdiff_update")
+
+
+INCEPTION_POOL_MAX_S2, INCEPTION_POOL_MAX_S1, INCEPTION_POOL_AVG = 0, 1, 2
+INCEPTION_BLOCKS = ("Mixed_5b", "Mixed_5c", "Mixed_5d", "Mixed_6a", "Mixed_6b", "Mixed_6c", "Mixed_6d", "Mixed_6e", "Mixed_7a", "Mixed_7b", "Mixed_7c")
+INCEPTION_MIN_SIDE = 75
+
+
+class NativeInception(_Handle):
+    """Handle for ``i2v_inception_*``: the FID Inception-v3 trunk of metrics/FID/inception.py (``fid_inception_v3`` cut into the four output
+    blocks of ``InceptionV3``)."""
+
+    def __init__(self, device=None):
+        h = c_void_p()
+        with self._bind(device):
+            _check(lib().i2v_inception_create(ctypes.byref(h)), "i2v_inception_create")
+        self._h = h
+        self._ws = _Workspace()
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.i2v_inception_destroy(self._h)
+            self._h = None
+
+    @_on_device
+    def load(self, state_dict):
+        """torchvision keys ``<unit>.conv.weight`` / ``<unit>.bn.{weight,bias,running_mean,running_var}``; ``num_batches_tracked``, ``fc.*`` and
+        ``AuxLogits.*`` are ignored."""
+        sd = {k: v for k, v in state_dict.items()
+              if not (k.endswith("num_batches_tracked") or k.startswith("fc.") or k.startswith("AuxLogits."))}
+        arr, keep = _pack_state_dict(sd)
+        _check(lib().i2v_inception_load(self._h, arr, len(arr)), "i2v_inception_load")
+        del keep
+
+    def block_shape(self, n, h, w, block):
+        """Channels-last shape of output block 0..3 for an [h, w] trunk input: [N, H', W', C], block 3 [N, 2048]."""
+        dims = (c_int32 * 3)()
+        _check(lib().i2v_inception_block_shape(self._h, h, w, block, dims), "i2v_inception_block_shape")
+        return (n, dims[2]) if block == 3 else (n, dims[0], dims[1], dims[2])
+
+    @_on_device
+    def features(self, x, blocks=(3,), out=None):
+        """``i2v_inception_features``: x [N, H, W, 4] channels-last (``inception_input_stage``) -> the requested blocks, channels-last, in
+        ascending order.  ``out``: caller-owned tensors of those shapes (the call only enqueues: it can be captured into a graph)."""
+        _require_cl4(x, "inception features")
+        n, h, w, c = x.shape
+        blocks = sorted(set(int(b) for b in blocks))
+        if not blocks or blocks[0] < 0 or blocks[-1] > 3:
+            raise I2VError(f"inception features: output blocks must be a non-empty subset of 0..3, got {blocks}")
+        if c != 4 or h < INCEPTION_MIN_SIDE or w < INCEPTION_MIN_SIDE:
+            raise I2VError(f"inception features: expected [N,H,W,4] with H, W >= {INCEPTION_MIN_SIDE} (the minimum that leaves a 1 x 1 map in front of "
+                           f"the final pool), got {tuple(x.shape)}")
+        nbytes = lib().i2v_inception_workspace_bytes(self._h, n, h, w, blocks[-1])
+        if nbytes == 0:
+            raise I2VError(f"inception features: no buffer plan for {tuple(x.shape)}: {lib().i2v_last_error().decode(errors='replace')}")
+        ws = self._ws.get(nbytes, x.device)
+        shapes = [self.block_shape(n, h, w, b) for b in blocks]
+        if out is None:
+            out = [torch.empty(s, dtype=torch.float32, device=x.device) for s in shapes]
+        ptr = [None] * 4
+        for b, t, s in zip(blocks, out, shapes):
+            _require_gpu(t)
+            if tuple(t.shape) != s:
+                raise I2VError(f"inception features: expected block {b} of shape {s}, got {tuple(t.shape)}")
+            ptr[b] = t.data_ptr()
+        _check(lib().i2v_inception_features(self._h, x.data_ptr(), n, h, w, *ptr, ws.data_ptr(), ws.numel(), _stream()), "i2v_inception_features")
+        return list(out)
+
+    def mixed_shape(self, block, h, w):
+        """(cin, cout, (H', W')) of Mixed block ``block`` (index into INCEPTION_BLOCKS) on an [h, w] map."""
+        cin, cout, hw = c_int32(), c_int32(), (c_int32 * 2)()
+        _check(lib().i2v_inception_mixed_shape(self._h, block, h, w, ctypes.byref(cin), ctypes.byref(cout), hw), "i2v_inception_mixed_shape")
+        return cin.value, cout.value, (hw[0], hw[1])
+
+    @_on_device
+    def mixed(self, block, x, out=None):
+        """``i2v_inception_mixed_forward``: x [N, H, W, cin] channels-last -> [N, H', W', cout]; ``out``: a caller-owned tensor (every element of
+        it is written)."""
+        _require_cl4(x, "inception mixed")
+        n, h, w, c = x.shape
+        cin, cout, (ho, wo) = self.mixed_shape(block, h, w)
+        if c != cin:
+            raise I2VError(f"inception mixed: {INCEPTION_BLOCKS[block]} takes {cin} channels, got {c}")
+        if out is None:
+            out = torch.empty(n, ho, wo, cout, dtype=torch.float32, device=x.device)
+        _require_gpu(out)
+        if tuple(out.shape) != (n, ho, wo, cout):
+            raise I2VError(f"inception mixed: expected an output of shape {(n, ho, wo, cout)}, got {tuple(out.shape)}")
+        ws = torch.empty(max(lib().i2v_inception_mixed_workspace_bytes(self._h, block, n, h, w), 256), dtype=torch.uint8, device=x.device)
+        _check(lib().i2v_inception_mixed_forward(self._h, block, x.data_ptr(), n, h, w, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+               "i2v_inception_mixed_forward")
+        return out
+
+
+def inception_input_stage(frames, resize=True, normalize=False):
+    """``i2v_inception_input_stage``: frames [N, 3, H, W] on the device -> channels-last [N, 299, 299, 4] (bilinear, align_corners=False) or, without
+    ``resize``, [N, H, W, 4]; ``normalize``: 2 x - 1 behind the resize.  Channel 3 is zero."""
+    _require_gpu(frames)
+    if frames.dim() != 4 or frames.shape[1] != 3:
+        raise I2VError(f"inception_input_stage: expected frames [N,3,H,W], got {tuple(frames.shape)}")
+    n, _, h, w = frames.shape
+    ho, wo = (299, 299) if resize else (h, w)
+    out = torch.empty(n, ho, wo, 4, dtype=torch.float32, device=frames.device)
+    with torch.cuda.device(frames.device):
+        _check(lib().i2v_inception_input_stage(frames.data_ptr(), n, h, w, int(bool(resize)), int(bool(normalize)), out.data_ptr(), _stream()),
+               "i2v_inception_input_stage")
+    return out
+
+
+def _host_f32(a):
+    return np.ascontiguousarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.float32)
+
+
+def inception_conv_unit(x, weight, bn, stride=1, padding=(0, 0), in_off=0, out=None, out_off=0):
+    """``i2v_inception_conv_unit``: one BasicConv2d.  x [N, H, W, CS] channels-last on the device, of which channels [in_off, in_off + cin) are
+    read (cin = 3: four stored channels); host ``weight`` [cout, cin, kh, kw] and ``bn`` = (weight, bias, running_mean, running_var), each
+    [cout]; eps 0.001.  Writes channels [out_off, out_off + cout) of ``out`` [N, H', W', OCS] (default: a new tensor of cout channels)."""
+    _require_cl4(x, "inception_conv_unit")
+    w = _host_f32(weight)
+    vec = [_host_f32(v) for v in bn]
+    if w.ndim != 4 or len(vec) != 4 or any(v.shape != (w.shape[0],) for v in vec):
+        raise I2VError(f"inception_conv_unit: expected weight [cout,cin,kh,kw] and four BatchNorm vectors [cout], got {w.shape} / {[v.shape for v in vec]}")
+    cout, cin, kh, kw = w.shape
+    n, h, wd, cs = x.shape
+    ph, pw = padding
+    ho, wo = (h + 2 * ph - kh) // stride + 1, (wd + 2 * pw - kw) // stride + 1
+    if out is None:
+        out = torch.empty(n, max(ho, 0), max(wo, 0), cout, dtype=torch.float32, device=x.device)
+    _require_cl4(out, "inception_conv_unit")
+    if tuple(out.shape[:3]) != (n, max(ho, 0), max(wo, 0)):
+        raise I2VError(f"inception_conv_unit: expected an output [N,{ho},{wo},C], got {tuple(out.shape)}")
+    with torch.cuda.device(x.device):
+        _check(lib().i2v_inception_conv_unit(x.data_ptr(), n, h, wd, cs, in_off, w.ctypes.data_as(c_void_p), *[v.ctypes.data_as(c_void_p) for v in vec],
+                                             cin, cout, kh, kw, stride, ph, pw, out.data_ptr(), out.shape[3], out_off, out.numel(), _stream()),
+               "i2v_inception_conv_unit")
+    return out
+
+
+def inception_pool(x, kind, out=None, out_off=0):
+    """``i2v_inception_pool``: one 3 x 3 pool of ``kind`` (INCEPTION_POOL_*) on x [N, H, W, C] channels-last; writes channels
+    [out_off, out_off + C) of ``out`` (default: a new tensor of C channels)."""
+    _require_cl4(x, "inception_pool")
+    n, h, w, c = x.shape
+    s, p = (2, 0) if kind == INCEPTION_POOL_MAX_S2 else (1, 1)
+    ho, wo = (h + 2 * p - 3) // s + 1, (w + 2 * p - 3) // s + 1
+    if out is None:
+        out = torch.empty(n, max(ho, 0), max(wo, 0), c, dtype=torch.float32, device=x.device)
+    _require_cl4(out, "inception_pool")
+    if tuple(out.shape[:3]) != (n, max(ho, 0), max(wo, 0)):
+        raise I2VError(f"inception_pool: expected an output [N,{ho},{wo},C], got {tuple(out.shape)}")
+    with torch.cuda.device(x.device):
+        _check(lib().i2v_inception_pool(x.data_ptr(), n, h, w, c, kind, out.data_ptr(), out.shape[3], out_off, out.numel(), _stream()), "i2v_inception_pool")
+    return out
+
+
+def inception_global_avg(x):
+    """``i2v_inception_global_avg``: AdaptiveAvgPool2d((1, 1)) on x [N, H, W, C] channels-last -> [N, C]."""
+    _require_cl4(x, "inception_global_avg")
+    n, h, w, c = x.shape
+    out = torch.empty(n, c, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _check(lib().i2v_inception_global_avg(x.data_ptr(), n, h, w, c, out.data_ptr(), _stream()), "i2v_inception_global_avg")
+    return out

@@ -127,40 +127,32 @@ def compute_activations(model, data_gen, data_orig, batch_size, cuda=True):
 
 
 # ---------------------------------------------------------------------------------------------- streaming form
-class FVDAccumulator:
-    """Streaming FVD: ``update(frames, which)`` for frames on the device, ``compute()`` at the end.
-
-    Per set ('gen' / 'orig') it keeps n, sum [D] and gram [D, D] in float64 ON THE DEVICE (``i2v_fvd_stats_update``: one owner per element,
-    clips in order, no atomics -- two runs give the same bits); ``compute()`` brings the two triples to the host and evaluates the
-    Frechet distance there.  Unlike ``get_activations`` it uses EVERY clip it is given (there is no ragged-batch drop), so with a set
-    size that is not a multiple of the batch its value differs from the reference's, which ignores the rest.
-    ``state()`` / ``load_state()`` save and restore the triples, so the statistics of the real set can be computed once and reused
-    across epochs (the reference recomputes them every epoch)."""
+class StatsAccumulator:
+    """Streaming Frechet statistics of two sets of D-dimensional features: the part that ``FVDAccumulator``, ``DTFVDAccumulator`` and
+    ``metrics.FID.FID_Score.FIDAccumulator`` share.  Per set ('gen' / 'orig') it keeps n, sum [D] and gram [D, D] in float64 ON THE DEVICE
+    (``i2v_fvd_stats_update``: one owner per element, rows in order, no atomics -- two runs give the same bits); ``compute()`` brings the
+    two triples to the host and evaluates the Frechet distance there.  ``state()`` / ``load_state()`` save and restore the triples, so the
+    statistics of the real set can be computed once and reused across epochs (the reference recomputes them every epoch).  A subclass
+    adds ``update``: its network's features of a batch, handed to ``update_features``."""
 
     SETS = ("gen", "orig")
 
-    def __init__(self, model):
-        self.model = model
-        self.dim = model.num_classes
-        self._n = {k: 0 for k in self.SETS}
-        self._sum = {k: None for k in self.SETS}
-        self._gram = {k: None for k in self.SETS}
+    def __init__(self, dim):
+        self.dim = dim
+        self._n, self._sum, self._gram = {}, {}, {}
+        self.reset()
 
     def reset(self, which=None):
         for k in (self.SETS if which is None else (which,)):
             self._n[k], self._sum[k], self._gram[k] = 0, None, None
 
-    @torch.no_grad()
-    def update(self, frames, which, denorm_input=True):
-        """frames [B, T, 3, H, W] fp32 on the device, ``denorm_input``: the values are in [-1, 1] (the decoder's and the loaders' range)."""
+    def _check_update(self, frames, which):
+        name = type(self).__name__
         if which not in self.SETS:
-            raise ValueError(f"FVDAccumulator.update: which must be one of {self.SETS}, got {which!r}")
+            raise ValueError(f"{name}.update: which must be one of {self.SETS}, got {which!r}")
         if not frames.is_cuda:
-            raise i2v_native.I2VError("FVDAccumulator.update takes frames on a HIP device (no frame goes through the host); this package has "
+            raise i2v_native.I2VError(f"{name}.update takes frames on a HIP device (no frame goes through the host); this package has "
                                       "no CPU fallback")
-        feats = self.model.forward_frames(frames.float().contiguous(), denorm_input)
-        self.update_features(feats, which)
-        return feats
 
     def update_features(self, feats, which):
         if self._sum[which] is None:
@@ -180,10 +172,10 @@ class FVDAccumulator:
     def load_state(self, state, device=None):
         for k, s in state.items():
             if k not in self.SETS:
-                raise ValueError(f"FVDAccumulator.load_state: unknown set {k!r}")
+                raise ValueError(f"{type(self).__name__}.load_state: unknown set {k!r}")
             total, gram = np.asarray(s["sum"], dtype=np.float64), np.asarray(s["gram"], dtype=np.float64)
             if total.shape != (self.dim,) or gram.shape != (self.dim, self.dim):
-                raise ValueError(f"FVDAccumulator.load_state: set {k!r} has shapes {total.shape}, {gram.shape} for {self.dim} features")
+                raise ValueError(f"{type(self).__name__}.load_state: set {k!r} has shapes {total.shape}, {gram.shape} for {self.dim} features")
             self._n[k] = int(s["n"])
             dev = device if device is not None else ("cuda" if torch.cuda.is_available() else "cpu")
             self._sum[k], self._gram[k] = torch.from_numpy(total.copy()).to(dev), torch.from_numpy(gram.copy()).to(dev)
@@ -191,7 +183,25 @@ class FVDAccumulator:
     def compute(self):
         st = self.state()
         if set(st) != set(self.SETS):
-            raise ValueError("FVDAccumulator.compute: both sets need at least one update")
+            raise ValueError(f"{type(self).__name__}.compute: both sets need at least one update")
         m1, s1 = stats_from_sums(st["gen"]["n"], st["gen"]["sum"], st["gen"]["gram"])
         m2, s2 = stats_from_sums(st["orig"]["n"], st["orig"]["sum"], st["orig"]["gram"])
         return calculate_frechet_distance(m1, s1, m2, s2)
+
+
+class FVDAccumulator(StatsAccumulator):
+    """Streaming FVD: ``update(frames, which)`` for frames on the device, ``compute()`` at the end (``StatsAccumulator`` over the logits of
+    the Kinetics I3D).  Unlike ``get_activations`` it uses EVERY clip it is given (there is no ragged-batch drop), so with a set size that
+    is not a multiple of the batch its value differs from the reference's, which ignores the rest."""
+
+    def __init__(self, model):
+        self.model = model
+        super().__init__(model.num_classes)
+
+    @torch.no_grad()
+    def update(self, frames, which, denorm_input=True):
+        """frames [B, T, 3, H, W] fp32 on the device, ``denorm_input``: the values are in [-1, 1] (the decoder's and the loaders' range)."""
+        self._check_update(frames, which)
+        feats = self.model.forward_frames(frames.float().contiguous(), denorm_input)
+        self.update_features(feats, which)
+        return feats

@@ -550,6 +550,60 @@ int i2v_lpips_layer(const float* f0, const float* f1, const float* lin, int32_t 
 int i2v_vgg_pairdiff_update(const float* maps, int32_t r, int64_t d, double* acc, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * FID Inception-v3 trunk (csrc/i2v_inception.hip) -- metrics/FID/inception.py (InceptionV3.forward :129-161, fid_inception_v3
+ * :164-186, FIDInceptionA / C / E_1 / E_2 :189-306 and the torchvision blocks InceptionB / D and BasicConv2d they sit on) and the
+ * feature half of metrics/FID/FID_Score.py (get_activations :98-158; the statistics run on i2v_fvd_stats_update with d = 2048).
+ * 94 BasicConv2d units (Conv2d without bias, BatchNorm2d(eps = 0.001) in eval mode, ReLU) in exact fp32 on the matrix cores: square
+ * 1x1 / 3x3 / 5x5 and rectangular 1x7 / 7x1 / 1x3 / 3x1 windows, stride 1 or 2; three 3x3 pools and the global average.  Activations
+ * are channels-last [N][H][W][C], the 3-channel input is stored as 4 channels (r, g, b, 0); the branches of a Mixed block store into
+ * their channel slice.  Single stream: every call only enqueues on `stream` (i2v_inception_conv_unit excepted) and can be captured
+ * into a graph.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct i2v_inception i2v_inception;
+#define I2V_INCEPTION_POOL_MAX_S2 0  /* nn.MaxPool2d(kernel_size=3, stride=2): no padding, floor mode (inception.py:89, 98; InceptionB / D) */
+#define I2V_INCEPTION_POOL_MAX_S1 1  /* F.max_pool2d(x, 3, stride=1, padding=1): the padding never wins (FIDInceptionE_2.forward, inception.py:302) */
+#define I2V_INCEPTION_POOL_AVG 2     /* F.avg_pool2d(x, 3, stride=1, padding=1, count_include_pad=False) (inception.py:206, 234, 267) */
+#define I2V_INCEPTION_BLOCKS 11      /* Mixed_5b, 5c, 5d, 6a, 6b, 6c, 6d, 6e, 7a, 7b, 7c: the `block` index of i2v_inception_mixed_* */
+/* fid_inception_v3 (inception.py:164-186): the graph, without weights */
+int i2v_inception_create(i2v_inception** out);
+void i2v_inception_destroy(i2v_inception* n);
+/* torchvision keys <unit>.conv.weight [Cout][Cin][KH][KW] and <unit>.bn.{weight, bias, running_mean, running_var} [Cout] of every
+ * BasicConv2d (Conv2d_1a_3x3 ... Mixed_7c.branch_pool); every other key (num_batches_tracked, fc.*, AuxLogits.*) is ignored.  A
+ * missing or mis-shaped entry: I2V_E_MISSING with the key in i2v_last_error.  BatchNorm is folded to (scale, shift) here. */
+int i2v_inception_load(i2v_inception* n, const i2v_tensor* tensors, int32_t n_tensors);
+/* dims = (H', W', C) of output block 0..3 (inception.py:84-124: 64, 192, 768 channels, 2048 at 1 x 1) for an [h][w] trunk input. */
+int i2v_inception_block_shape(const i2v_inception* n, int32_t h, int32_t w, int32_t block, int32_t* dims);
+/* Workspace of i2v_inception_features when `last_block` is the last block requested; 0 when h or w is below 75. */
+size_t i2v_inception_workspace_bytes(const i2v_inception* n, int32_t batch, int32_t h, int32_t w, int32_t last_block);
+/* InceptionV3.forward :144-151: frames [n][3][hi][wi] fp32 -> out channels-last [n][299][299][4] when `resize` (F.interpolate, bilinear,
+ * align_corners=False, in the arithmetic of torch's upsample_bilinear2d), else [n][hi][wi][4]; then 2 x - 1 when `normalize`. */
+int i2v_inception_input_stage(const float* frames, int32_t n, int32_t hi, int32_t wi, int32_t resize, int32_t normalize, float* out, void* stream);
+/* InceptionV3.forward :153-161: x [batch][h][w][4] -> the requested blocks, caller-owned and channels-last (i2v_inception_block_shape);
+ * block3 is [batch][2048].  A NULL block is skipped and the walk stops behind the last one requested.  h, w >= 75. */
+int i2v_inception_features(i2v_inception* n, const float* x, int32_t batch, int32_t h, int32_t w, float* block0, float* block1, float* block2,
+                           float* block3, void* workspace, size_t workspace_bytes, void* stream);
+/* One BasicConv2d (torchvision inception.py) from raw HOST weights [cout][cin][kh][kw] and BatchNorm vectors [cout]: channels
+ * [in_off, in_off + cin) of x [n][h][w][in_cs] -> channels [out_off, out_off + cout) of out [n][h'][w'][out_cs]; the other channels
+ * of out are not touched.  cin = 3 reads 4 stored channels; every other cin is a multiple of 16; kernel extents 1..7, stride 1 or 2,
+ * padding below the kernel; anything else is refused.  Packs per call and synchronises the stream: for the unit tests. */
+int i2v_inception_conv_unit(const float* x, int32_t n, int32_t h, int32_t w, int32_t in_cs, int32_t in_off, const float* weight, const float* bn_weight,
+                            const float* bn_bias, const float* bn_mean, const float* bn_var, int32_t cin, int32_t cout, int32_t kh, int32_t kw,
+                            int32_t stride, int32_t pad_h, int32_t pad_w, float* out, int32_t out_cs, int32_t out_off, size_t out_floats, void* stream);
+/* One 3x3 pool of `kind` (I2V_INCEPTION_POOL_*): x [n][h][w][c] -> channels [out_off, out_off + c) of out [n][h'][w'][out_cs]; c, out_cs
+ * and out_off multiples of 4. */
+int i2v_inception_pool(const float* x, int32_t n, int32_t h, int32_t w, int32_t c, int32_t kind, float* out, int32_t out_cs, int32_t out_off,
+                       size_t out_floats, void* stream);
+/* nn.AdaptiveAvgPool2d((1, 1)) (inception.py:122): x [n][h][w][c] -> out [n][c]. */
+int i2v_inception_global_avg(const float* x, int32_t n, int32_t h, int32_t w, int32_t c, float* out, void* stream);
+/* Mixed block `block` (0 = Mixed_5b ... 10 = Mixed_7c) of a loaded handle on an [h][w] map: its channel counts and output map. */
+int i2v_inception_mixed_shape(const i2v_inception* n, int32_t block, int32_t h, int32_t w, int32_t* cin, int32_t* cout, int32_t* out_hw);
+size_t i2v_inception_mixed_workspace_bytes(const i2v_inception* n, int32_t block, int32_t batch, int32_t h, int32_t w);
+/* FIDInceptionA / InceptionB / FIDInceptionC / InceptionD / FIDInceptionE_1 / E_2 .forward: x [batch][h][w][cin] -> out
+ * [batch][h'][w'][cout], torch.cat(outputs, 1) as channel slices. */
+int i2v_inception_mixed_forward(i2v_inception* n, int32_t block, const float* x, int32_t batch, int32_t h, int32_t w, float* out, void* workspace,
+                                size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Motion encoder of the transfer path (row N3): Encoder.forward -- stage1_VAE/modules/resnet3D.py:138-219
  * (3D ResNet-18, GroupNorm(16), conv_mu / conv_var).  Model.transfer (get_model.py:87) uses mu.
  * Keys: conv1.weight, norm1.*, layer.{L}.{i}.{conv1,conv2}.weight, .bn{1,2}.*, .downsample.{0.weight,1.*},
