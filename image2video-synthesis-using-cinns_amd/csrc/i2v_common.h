@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -98,6 +99,11 @@ inline int upload_packed(DevBuf& w, DevBuf& bias, const void* packed, size_t byt
 }
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// workgroups of 256 threads for a grid-stride loop over `total` elements
+inline unsigned grid_for(long total) { return (unsigned)std::min<long>((total + 255) / 256, 1L << 20); }
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));   // the MFMA accumulator (HIP's float4 is a struct)
 
 // Is `st` capturing a graph right now?  (Errors of the query -- a stream of another context, an old runtime -- count as "no".)
 inline bool stream_is_capturing(hipStream_t st) {

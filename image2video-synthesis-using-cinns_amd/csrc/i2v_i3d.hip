@@ -5,20 +5,8 @@
 // Frames stay on the device: the decoder's [B][T][3][H][W] output is resized (bilinear, align_corners=True) to 224 x 224 and
 // de-normalised in one kernel that writes the channels-last stem input.
 //
-// Convolutions: ONE implicit-GEMM kernel on the exact-fp32 matrix cores (v_mfma_f32_16x16x4_f32).
-//   Out[m = (b,to,ho,wo) flattened][n] = relu(scale[n] * sum_k In[gather(m, k)] * W[k][n] + shift[n])
-// conv_forward (i2v_conv.hip) tiles T, H, W into bricks of 128 positions and pads symmetrically; this network has 14 x 14 and
-// 7 x 7 maps, an asymmetric "TF SAME" stem and Mixed blocks whose branches write channel slices of one tensor.  So here:
-//   * positions are flattened over B * To * Ho * Wo, 128 per workgroup, the last tile masked;
-//   * K is flattened over (tap, channel) in groups of 4 channels: a 16-wide K chunk of the 7x7x7 stem (4 channels: r, g, b, 0)
-//     holds 4 taps, a chunk of a 1x1x1 unit 16 channels -- one gather path for every unit, no padded K work in the stem;
-//   * kernel, stride and per-side padding are arguments; so are the channel stride / offset of the input and of the output
-//     (the four branches of a Mixed block store straight into their slice: there is no concat kernel);
-//   * epilogue: eval-mode BatchNorm3d folded to (scale, shift) at load, ReLU.
-// 4 waves x (32 rows x BN columns) per workgroup, BN in {32, 64, 128}; A and W chunks are double-buffered in LDS (rows of 16
-// floats padded to 20: conflict-free ds_read_b128), the next chunk's global loads are in flight during the MFMAs: one barrier
-// per chunk.  Loads are unconditional with clamped addresses.  The K order of a position does not depend on the batch or on the
-// tile it falls in: batch rows equal their single-sample runs bit for bit, and there are no atomics anywhere.
+// Convolutions: flat_conv_kernel<NT, true> (i2v_flatconv.h) for every unit: cubic windows, stride 1 or 2, the asymmetric "TF SAME"
+// padding as padding in front, eval-mode BatchNorm3d folded to (scale, shift) at load and ReLU; the head conv has a bias and no ReLU.
 //
 // Max pools pad with ZEROS that take part in the maximum (ConstantPad3d(.., 0) in front of MaxPool3d(ceil_mode=True)).
 //
@@ -33,138 +21,12 @@
 #include <cmath>
 #include <memory>
 
-#include "i2v_common.h"
+#include "i2v_flatconv.h"
 
 namespace i2v {
 namespace {
 
-constexpr int I3D_BM = 128;
-constexpr int I3D_LS = 20;    // floats per staged row of 16
 constexpr int I3D_SIDE = 224;
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-struct I3dConvArgs {
-    const float* in;     // channels-last [B][Ti][Hi][Wi][inCS], the unit reads channels [inOff, inOff + 4 C4)
-    const float* wp;     // [nchunk][CoutPad][16]
-    const float2* ss;    // [CoutPad] (scale, shift)
-    float* out;          // [M][outCS], the unit writes channels [outOff, outOff + Cout)
-    long M;
-    int Ti, Hi, Wi, To, Ho, Wo;
-    int inCS, inOff, C4, G, nchunk;   // C4: groups of 4 input channels, G = taps * C4
-    int KH, KW, sT, sH, sW, pT, pH, pW;
-    int Cout, CoutPad, outCS, outOff, relu;
-};
-
-template <int NT>   // 16-column tiles per wave: BN = 16 NT
-__global__ __launch_bounds__(256) void i3d_conv_kernel(I3dConvArgs a) {
-    constexpr int BN = 16 * NT;
-    constexpr int WLD = (BN * 4 + 255) / 256;
-    __shared__ __attribute__((aligned(16))) float a_lds[2][I3D_BM * I3D_LS];
-    __shared__ __attribute__((aligned(16))) float w_lds[2][BN * I3D_LS];
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int lr = lane & 15, kq = lane >> 4;
-    const int nNt = a.CoutPad / BN;
-    const int n0 = (int)(blockIdx.x % nNt) * BN;
-    const long m0 = (long)(blockIdx.x / nNt) * I3D_BM;
-    const int q = tid & 3;
-
-    // the two staged rows of this thread: output position -> first input coordinate of its window
-    int rb[2], rt[2], rh[2], rw[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        long m = m0 + (tid >> 2) + 64 * u;
-        const bool ok = m < a.M;
-        if (!ok) m = 0;
-        const int wo = (int)(m % a.Wo); m /= a.Wo;
-        const int ho = (int)(m % a.Ho); m /= a.Ho;
-        const int to = (int)(m % a.To);
-        rb[u] = ok ? (int)(m / a.To) : -1;
-        rt[u] = to * a.sT - a.pT; rh[u] = ho * a.sH - a.pH; rw[u] = wo * a.sW - a.pW;
-    }
-    const int khw = a.KH * a.KW;
-
-    static_assert(WLD <= 2, "weight pieces per thread");
-    float4 pa0, pa1, pw0, pw1;   // (named, not arrays: arrays written under a branch go to scratch)
-    pw1 = make_float4(0.f, 0.f, 0.f, 0.f);
-    auto request = [&](int ch) {
-        const int g = ch * 4 + q;
-        const bool gok = g < a.G;
-        const int tap = gok ? g / a.C4 : 0;
-        const int c = (g - tap * a.C4) * 4;
-        const int dt = tap / khw, r2 = tap - dt * khw, dh = r2 / a.KW, dw = r2 - dh * a.KW;
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int t = rt[u] + dt, h = rh[u] + dh, w = rw[u] + dw;
-            const bool ok = gok && rb[u] >= 0 && (unsigned)t < (unsigned)a.Ti && (unsigned)h < (unsigned)a.Hi && (unsigned)w < (unsigned)a.Wi;
-            const long off = ok ? ((((long)rb[u] * a.Ti + t) * a.Hi + h) * a.Wi + w) * a.inCS + a.inOff + c : 0;
-            const float4 v = *reinterpret_cast<const float4*>(a.in + off);
-            const float4 z = ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
-            if (u == 0) pa0 = z; else pa1 = z;
-        }
-        const float* wsrc = a.wp + ((long)ch * a.CoutPad + n0) * 16;
-        pw0 = *reinterpret_cast<const float4*>(wsrc + (tid < BN * 4 ? tid : 0) * 4);
-        if constexpr (WLD > 1) pw1 = *reinterpret_cast<const float4*>(wsrc + (tid + 256) * 4);
-    };
-    auto park = [&](int buf) {
-        *reinterpret_cast<float4*>(&a_lds[buf][(tid >> 2) * I3D_LS + 4 * q]) = pa0;
-        *reinterpret_cast<float4*>(&a_lds[buf][((tid >> 2) + 64) * I3D_LS + 4 * q]) = pa1;
-        if (tid < BN * 4) *reinterpret_cast<float4*>(&w_lds[buf][(tid >> 2) * I3D_LS + 4 * q]) = pw0;
-        if constexpr (WLD > 1) *reinterpret_cast<float4*>(&w_lds[buf][((tid + 256) >> 2) * I3D_LS + 4 * q]) = pw1;
-    };
-
-    f32x4 acc[2][NT];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    request(0);
-    park(0);
-    __syncthreads();
-    for (int ch = 0; ch < a.nchunk; ++ch) {
-        const int buf = ch & 1;
-        request(ch + 1 < a.nchunk ? ch + 1 : ch);
-        // MFMA k-slot (lane >> 4) of step s carries K element 4 (lane >> 4) + s of the chunk, for both operands
-        float4 av[2], bv[NT];
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) av[mt] = *reinterpret_cast<const float4*>(&a_lds[buf][(wave * 32 + 16 * mt + lr) * I3D_LS + 4 * kq]);
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) bv[nt] = *reinterpret_cast<const float4*>(&w_lds[buf][(16 * nt + lr) * I3D_LS + 4 * kq]);
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt) {
-                const float as = s == 0 ? av[mt].x : s == 1 ? av[mt].y : s == 2 ? av[mt].z : av[mt].w;
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    const float bs = s == 0 ? bv[nt].x : s == 1 ? bv[nt].y : s == 2 ? bv[nt].z : bv[nt].w;
-                    acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(as, bs, acc[mt][nt], 0, 0, 0);
-                }
-            }
-        if (ch + 1 < a.nchunk) park(buf ^ 1);
-        __syncthreads();
-    }
-
-    // C/D layout of the 16x16 MFMA: column = lane & 15, rows 4 (lane >> 4) + r
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        const int n = n0 + 16 * nt + lr;
-        if (n >= a.Cout) continue;
-        const float2 ss = a.ss[n];
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const long m = m0 + wave * 32 + 16 * mt + 4 * kq + r;
-                if (m >= a.M) continue;
-                float v = fmaf(acc[mt][nt][r], ss.x, ss.y);
-                if (a.relu) v = fmaxf(v, 0.f);
-                a.out[m * a.outCS + a.outOff + n] = v;
-            }
-    }
-}
 
 // FVD_logging.preprocess fused with the layout change: frames [N = B T][3][Hi][Wi] -> channels-last [N][224][224][4] (channel 3
 // zero), bilinear with align_corners=True in the arithmetic of torch's upsample_bilinear2d, then (x + 1) / 2 when `denorm`.
@@ -310,8 +172,6 @@ __global__ __launch_bounds__(256) void diversity_kernel(const float* __restrict_
     }
 }
 
-unsigned grid_for(long total) { return (unsigned)std::min<long>((total + 255) / 256, 1L << 20); }
-
 // "TF SAME" padding of one dimension (get_padding_shape): `mod` = input size % stride for the TIME dimension of a strided unit
 // (Kinetics), for every dimension of a strided unit (dynamic-texture variant: Unit3D.compute_pad, MaxPool3dSamePadding.compute_pad)
 void same_pad(int k, int s, int mod, int* front, int* back) {
@@ -326,58 +186,30 @@ int pool_out(int e, int k, int s) {
     return o;
 }
 
-struct Unit {
-    DevBuf w, ss;
-    int Cin = 0, Cout = 0, CoutPad = 0, BN = 64, K = 1, C4 = 0, nchunk = 0;
+// One conv unit (Unit3Dpy / ID3.Unit3D) of the state_dict: [cout][cin][k][k][k] under <name>.conv3d.weight, and its epilogue: the eval-mode
+// BatchNorm3d under <name>.<bnkey> (eps 1e-3 under "batch3d", 1e-5 under "bn"), else the conv bias, else nothing
+struct Unit : FlatConv {
     int pack(const StateDict& sd, const std::string& name, int cin, int cout, int k, bool bn, bool bias, const char* bnkey = "batch3d",
-             double eps = 1e-3);
-};
-
-int Unit::pack(const StateDict& sd, const std::string& name, int cin, int cout, int k, bool bn, bool bias, const char* bnkey, double eps) {
-    Cin = cin; Cout = cout; K = k;
-    const int taps = k * k * k;
-    const float* wsrc = sd.f32(name + ".conv3d.weight", (int64_t)cout * cin * taps);
-    if (!wsrc) return I2V_E_MISSING;
-    // column tile: the one that pads Cout least, the wider on a tie
-    int best = 128;
-    for (int bn_ : {64, 32})
-        if ((cout + bn_ - 1) / bn_ * bn_ < (cout + best - 1) / best * best) best = bn_;
-    BN = best;
-    CoutPad = (cout + BN - 1) / BN * BN;
-    const int CinP = (cin + 3) / 4 * 4;
-    C4 = CinP / 4;
-    const long Kp = (long)taps * CinP;
-    nchunk = (int)((Kp + 15) / 16);
-    std::vector<float> p((size_t)nchunk * CoutPad * 16, 0.f);
-    for (int n = 0; n < cout; ++n)
-        for (int c = 0; c < cin; ++c)
-            for (int tap = 0; tap < taps; ++tap) {
-                const long kk = (long)tap * CinP + c;
-                p[((size_t)(kk / 16) * CoutPad + n) * 16 + kk % 16] = wsrc[((size_t)n * cin + c) * taps + tap];
-            }
-    int rc = w.upload(p.data(), p.size() * 4);
-    if (rc) return rc;
-    std::vector<float> s((size_t)CoutPad * 2, 0.f);
-    if (bn) {   // eval-mode BatchNorm3d: (x - mean) / sqrt(var + eps) * weight + bias; eps = 1e-3 under "batch3d" (Unit3Dpy: tf_style_eps),
-                // torch's default 1e-5 under "bn" (ID3.Unit3D)
-        const std::string bk = name + "." + bnkey;
-        const float* g = sd.f32(bk + ".weight", cout);
-        const float* b = sd.f32(bk + ".bias", cout);
-        const float* m = sd.f32(bk + ".running_mean", cout);
-        const float* v = sd.f32(bk + ".running_var", cout);
-        if (!g || !b || !m || !v) return I2V_E_MISSING;
-        for (int n = 0; n < cout; ++n) {
-            const double a = (double)g[n] / std::sqrt((double)v[n] + eps);
-            s[2 * n] = (float)a;
-            s[2 * n + 1] = (float)((double)b[n] - (double)m[n] * a);
+             double eps = 1e-3) {
+        const float* wsrc = sd.f32(name + ".conv3d.weight", (int64_t)cout * cin * k * k * k);
+        if (!wsrc) return I2V_E_MISSING;
+        FlatConvPacked p = flatconv_pack(wsrc, cin, cout, k, k, k);
+        if (bn) {
+            const std::string bk = name + "." + bnkey;
+            const float* g = sd.f32(bk + ".weight", cout);
+            const float* b = sd.f32(bk + ".bias", cout);
+            const float* m = sd.f32(bk + ".running_mean", cout);
+            const float* v = sd.f32(bk + ".running_var", cout);
+            if (!g || !b || !m || !v) return I2V_E_MISSING;
+            flatconv_fold_bn(p, g, b, m, v, eps);
+        } else if (bias) {
+            const float* b = sd.f32(name + ".conv3d.bias", cout);
+            if (!b) return I2V_E_MISSING;
+            flatconv_bias(p, b);
         }
-    } else {
-        const float* b = bias ? sd.f32(name + ".conv3d.bias", cout) : nullptr;
-        if (bias && !b) return I2V_E_MISSING;
-        for (int n = 0; n < cout; ++n) { s[2 * n] = 1.f; s[2 * n + 1] = b ? b[n] : 0.f; }
+        return upload(p);
     }
-    return ss.upload(s.data(), s.size() * 4);
-}
+};
 
 struct MixedSpec { const char* name; int cin; int o[6]; };
 const MixedSpec MIXED[9] = {
@@ -427,28 +259,14 @@ struct Walk {
     int conv(const Unit& u, const float* in, int inCS, int inOff, Dims di, float* out, int outCS, int outOff, Dims dout, int sT, int s,
              int pT, int pS, bool relu, int pW = -1) {
         if (dry) return I2V_OK;
-        I3dConvArgs a{};
-        a.in = in; a.wp = u.w.as<float>(); a.ss = u.ss.as<float2>(); a.out = out;
-        a.M = (long)B * dout.pos();
-        a.Ti = di.T; a.Hi = di.H; a.Wi = di.W; a.To = dout.T; a.Ho = dout.H; a.Wo = dout.W;
-        a.inCS = inCS; a.inOff = inOff; a.C4 = u.C4; a.G = u.K * u.K * u.K * u.C4; a.nchunk = u.nchunk;
-        a.KH = u.K; a.KW = u.K; a.sT = sT; a.sH = s; a.sW = s; a.pT = pT; a.pH = pS; a.pW = pW < 0 ? pS : pW;
-        a.Cout = u.Cout; a.CoutPad = u.CoutPad; a.outCS = outCS; a.outOff = outOff; a.relu = relu ? 1 : 0;
-        I2V_REQUIRE(inCS % 4 == 0 && inOff % 4 == 0 && inOff + 4 * u.C4 <= inCS && outOff + u.Cout <= outCS, I2V_E_INVALID,
-                    "i3d conv: channel slice [%d, +%d) of %d -> [%d, +%d) of %d", inOff, 4 * u.C4, inCS, outOff, u.Cout, outCS);
-        const long nblk = (a.M + I3D_BM - 1) / I3D_BM * (u.CoutPad / u.BN);
-        I2V_REQUIRE(nblk > 0 && nblk < (1L << 31), I2V_E_INVALID, "i3d conv: grid of %ld workgroups", nblk);
-        if (u.BN == 128) hipLaunchKernelGGL(i3d_conv_kernel<8>, dim3((unsigned)nblk), dim3(256), 0, st, a);
-        else if (u.BN == 64) hipLaunchKernelGGL(i3d_conv_kernel<4>, dim3((unsigned)nblk), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL(i3d_conv_kernel<2>, dim3((unsigned)nblk), dim3(256), 0, st, a);
-        I2V_HIP_CHECK(hipGetLastError());
-        return I2V_OK;
+        const FlatConvMaps g{B, di.T, di.H, di.W, dout.T, dout.H, dout.W, sT, s, s, pT, pS, pW < 0 ? pS : pW};
+        return flat_conv_launch<true>("i3d conv", u, in, inCS, inOff, out, outCS, outOff, g, relu, st);
     }
 
     // One conv unit at stride (s, s, s) with its own SAME padding (unit_geom); returns the output dims
     int unit(const Unit& u, int s, const float* in, int inCS, int inOff, Dims di, float* out, int outCS, int outOff, bool relu, Dims* dout) {
         int pT, pH, pW;
-        unit_geom(net, u.K, s, di, &pT, &pH, &pW, dout);
+        unit_geom(net, u.kt, s, di, &pT, &pH, &pW, dout);
         return conv(u, in, inCS, inOff, di, out, outCS, outOff, *dout, s, s, pT, pH, relu, pW);
     }
 
@@ -725,7 +543,7 @@ int i2v_i3d_unit_shape(const i2v_i3d* n, int32_t unit, int32_t t, int32_t h, int
     I2V_REQUIRE(u && t > 0 && h > 0 && w > 0, I2V_E_INVALID, "i2v_i3d_unit_shape: unit %d on a [%d, %d, %d] map", unit, t, h, w);
     int pT, pH, pW;
     Dims o;
-    unit_geom(n, u->K, s, Dims{t, h, w}, &pT, &pH, &pW, &o);
+    unit_geom(n, u->kt, s, Dims{t, h, w}, &pT, &pH, &pW, &o);
     if (cin) *cin = 4 * u->C4;
     if (cout) *cout = u->Cout;
     if (out_dims) { out_dims[0] = o.T; out_dims[1] = o.H; out_dims[2] = o.W; }
@@ -745,7 +563,7 @@ int i2v_i3d_unit_forward(i2v_i3d* n, int32_t unit, const float* x, int32_t batch
                 "i2v_i3d_unit_forward: channels [0, %d) of %d -> [%d, +%d) of %d do not fit", 4 * u->C4, in_cs, out_off, u->Cout, out_cs);
     int pT, pH, pW;
     Dims o;
-    unit_geom(n, u->K, s, Dims{t, h, w}, &pT, &pH, &pW, &o);
+    unit_geom(n, u->kt, s, Dims{t, h, w}, &pT, &pH, &pW, &o);
     I2V_REQUIRE((long)batch * t * h * w * in_cs < I3D_SUB_MAX && (long)batch * o.pos() * out_cs < I3D_SUB_MAX, I2V_E_INVALID,
                 "i2v_i3d_unit_forward: batch %d x [%d, %d, %d] is too large", batch, t, h, w);
     I2V_REQUIRE(out_floats >= (size_t)batch * o.pos() * out_cs, I2V_E_WORKSPACE, "i2v_i3d_unit_forward: output of %zu floats < required %zu",

@@ -4,19 +4,8 @@
 // InceptionB / D, BasicConv2d underneath) and the feature half of metrics/FID/FID_Score.py (get_activations); the statistics run on
 // i2v_fvd_stats_update (i2v_i3d.hip) with D = 2048.
 //
-// Convolutions: ONE 2-D implicit-GEMM kernel on the exact-fp32 matrix cores (v_mfma_f32_16x16x4_f32), the scheme of i3d_conv_kernel
-// without the time dimension and with a rectangular window:
-//   Out[m = (n, ho, wo) flattened][c] = relu(scale[c] * sum_k In[gather(m, k)] * W[k][c] + shift[c])
-//   * positions are flattened over N * Ho * Wo, 128 per workgroup, the last tile masked;
-//   * K is flattened over (tap = dh * KW + dw, channel) in groups of 4 channels: a 16-wide chunk of the 3x3 image conv (r, g, b, 0)
-//     holds 4 taps, a chunk of a 1x1 unit 16 channels -- one gather path for 1x1, 3x3, 5x5, 1x7, 7x1, 1x3 and 3x1, stride 1 or 2;
-//   * KH, KW, stride and the padding per dimension are arguments, and so are the channel stride / offset of the input and of the
-//     output: the branches of a Mixed block store straight into their slice, there is no concat kernel;
-//   * epilogue: eval-mode BatchNorm2d(eps = 0.001) folded to (scale, shift) at load, ReLU (BasicConv2d).
-// 4 waves x (32 rows x BN columns) per workgroup, BN in {32, 64, 128} per layer; A and W chunks double-buffered in LDS (rows of 16
-// floats padded to 20: conflict-free ds_read_b128), the next chunk's global loads in flight during the MFMAs, one barrier per chunk.
-// Loads are unconditional with clamped addresses.  The K order of an output element depends on neither the batch nor the tile it
-// falls in: batch rows equal their single-image runs bit for bit.  No atomics.
+// Convolutions: flat_conv_kernel<NT, false> (i2v_flatconv.h), the 2-D unit, for 1x1, 3x3, 5x5, 1x7, 7x1, 1x3 and 3x1 windows at stride
+// 1 or 2 with symmetric padding; BasicConv2d's eval-mode BatchNorm2d(eps = 0.001) folded to (scale, shift) at load, ReLU.
 //
 // Pools (channels-last, 4 channels per thread, taps in (dh, dw) order):
 //   (a) MaxPool2d(3, stride 2): no padding, floor mode;
@@ -27,135 +16,13 @@
 #include <cmath>
 #include <memory>
 
-#include "i2v_common.h"
+#include "i2v_flatconv.h"
 
 namespace i2v {
 namespace {
 
-constexpr int INC_BM = 128;
-constexpr int INC_LS = 20;    // floats per staged row of 16
 constexpr int INC_SIDE = 299;
 constexpr int INC_MIN = 75;   // the smallest input that leaves a 1 x 1 map in front of the final pool
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-struct IncConvArgs {
-    const float* in;     // channels-last [N][Hi][Wi][inCS], the unit reads channels [inOff, inOff + 4 C4)
-    const float* wp;     // [nchunk][CoutPad][16]
-    const float2* ss;    // [CoutPad] (scale, shift)
-    float* out;          // [M][outCS], the unit writes channels [outOff, outOff + Cout)
-    long M;
-    int Hi, Wi, Ho, Wo;
-    int inCS, inOff, C4, G, nchunk;   // C4: groups of 4 input channels, G = taps * C4
-    int KW, sH, sW, pH, pW;
-    int Cout, CoutPad, outCS, outOff;
-};
-
-template <int NT>   // 16-column tiles per wave: BN = 16 NT
-__global__ __launch_bounds__(256) void inc_conv_kernel(IncConvArgs a) {
-    constexpr int BN = 16 * NT;
-    constexpr int WLD = (BN * 4 + 255) / 256;
-    __shared__ __attribute__((aligned(16))) float a_lds[2][INC_BM * INC_LS];
-    __shared__ __attribute__((aligned(16))) float w_lds[2][BN * INC_LS];
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int lr = lane & 15, kq = lane >> 4;
-    const int nNt = a.CoutPad / BN;
-    const int n0 = (int)(blockIdx.x % nNt) * BN;
-    const long m0 = (long)(blockIdx.x / nNt) * INC_BM;
-    const int q = tid & 3;
-
-    // the two staged rows of this thread: output position -> first input coordinate of its window
-    int rb[2], rh[2], rw[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-        long m = m0 + (tid >> 2) + 64 * u;
-        const bool ok = m < a.M;
-        if (!ok) m = 0;
-        const int wo = (int)(m % a.Wo); m /= a.Wo;
-        const int ho = (int)(m % a.Ho);
-        rb[u] = ok ? (int)(m / a.Ho) : -1;
-        rh[u] = ho * a.sH - a.pH; rw[u] = wo * a.sW - a.pW;
-    }
-
-    static_assert(WLD <= 2, "weight pieces per thread");
-    float4 pa0, pa1, pw0, pw1;   // (named, not arrays: arrays written under a branch go to scratch)
-    pw1 = make_float4(0.f, 0.f, 0.f, 0.f);
-    auto request = [&](int ch) {
-        const int g = ch * 4 + q;
-        const bool gok = g < a.G;
-        const int tap = gok ? g / a.C4 : 0;
-        const int c = (g - tap * a.C4) * 4;
-        const int dh = tap / a.KW, dw = tap - dh * a.KW;
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int h = rh[u] + dh, w = rw[u] + dw;
-            const bool ok = gok && rb[u] >= 0 && (unsigned)h < (unsigned)a.Hi && (unsigned)w < (unsigned)a.Wi;
-            const long off = ok ? (((long)rb[u] * a.Hi + h) * a.Wi + w) * a.inCS + a.inOff + c : 0;
-            const float4 v = *reinterpret_cast<const float4*>(a.in + off);
-            const float4 z = ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
-            if (u == 0) pa0 = z; else pa1 = z;
-        }
-        const float* wsrc = a.wp + ((long)ch * a.CoutPad + n0) * 16;
-        pw0 = *reinterpret_cast<const float4*>(wsrc + (tid < BN * 4 ? tid : 0) * 4);
-        if constexpr (WLD > 1) pw1 = *reinterpret_cast<const float4*>(wsrc + (tid + 256) * 4);
-    };
-    auto park = [&](int buf) {
-        *reinterpret_cast<float4*>(&a_lds[buf][(tid >> 2) * INC_LS + 4 * q]) = pa0;
-        *reinterpret_cast<float4*>(&a_lds[buf][((tid >> 2) + 64) * INC_LS + 4 * q]) = pa1;
-        if (tid < BN * 4) *reinterpret_cast<float4*>(&w_lds[buf][(tid >> 2) * INC_LS + 4 * q]) = pw0;
-        if constexpr (WLD > 1) *reinterpret_cast<float4*>(&w_lds[buf][((tid + 256) >> 2) * INC_LS + 4 * q]) = pw1;
-    };
-
-    f32x4 acc[2][NT];
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    request(0);
-    park(0);
-    __syncthreads();
-    for (int ch = 0; ch < a.nchunk; ++ch) {
-        const int buf = ch & 1;
-        request(ch + 1 < a.nchunk ? ch + 1 : ch);
-        // MFMA k-slot (lane >> 4) of step s carries K element 4 (lane >> 4) + s of the chunk, for both operands
-        float4 av[2], bv[NT];
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) av[mt] = *reinterpret_cast<const float4*>(&a_lds[buf][(wave * 32 + 16 * mt + lr) * INC_LS + 4 * kq]);
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) bv[nt] = *reinterpret_cast<const float4*>(&w_lds[buf][(16 * nt + lr) * INC_LS + 4 * kq]);
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt) {
-                const float as = s == 0 ? av[mt].x : s == 1 ? av[mt].y : s == 2 ? av[mt].z : av[mt].w;
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    const float bs = s == 0 ? bv[nt].x : s == 1 ? bv[nt].y : s == 2 ? bv[nt].z : bv[nt].w;
-                    acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(as, bs, acc[mt][nt], 0, 0, 0);
-                }
-            }
-        if (ch + 1 < a.nchunk) park(buf ^ 1);
-        __syncthreads();
-    }
-
-    // C/D layout of the 16x16 MFMA: column = lane & 15, rows 4 (lane >> 4) + r
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        const int n = n0 + 16 * nt + lr;
-        if (n >= a.Cout) continue;
-        const float2 ss = a.ss[n];
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const long m = m0 + wave * 32 + 16 * mt + 4 * kq + r;
-                if (m >= a.M) continue;
-                a.out[m * a.outCS + a.outOff + n] = fmaxf(fmaf(acc[mt][nt][r], ss.x, ss.y), 0.f);
-            }
-    }
-}
 
 // InceptionV3.forward :144-151 fused with the layout change: frames [N][3][Hi][Wi] -> channels-last [N][Ho][Wo][4] (channel 3 zero),
 // bilinear with align_corners=False in the arithmetic of torch's upsample_bilinear2d (Ho = Hi and Wo = Wi: weights (1, 0), the sample
@@ -228,8 +95,6 @@ __global__ __launch_bounds__(256) void inc_global_avg_kernel(const float* __rest
     }
 }
 
-unsigned grid_for(long total) { return (unsigned)std::min<long>((total + 255) / 256, 1L << 20); }
-
 struct Map { int H, W; long pos() const { return (long)H * W; } };
 
 struct ConvSpec { std::string name; int cin, cout, kh, kw, s, ph, pw; };
@@ -243,54 +108,25 @@ const char* conv_shape_error(const ConvSpec& c) {
     return nullptr;
 }
 
-struct Unit {
+// One BasicConv2d: [Cout][Cin][KH][KW] packed as a 2-D flat conv unit, its BatchNorm2d(eps=0.001) in eval mode folded to (scale, shift)
+struct Unit : FlatConv {
     ConvSpec spec;
-    DevBuf w, ss;
-    int CoutPad = 0, BN = 64, C4 = 0, nchunk = 0;
     Map out(Map d) const { return Map{(d.H + 2 * spec.ph - spec.kh) / spec.s + 1, (d.W + 2 * spec.pw - spec.kw) / spec.s + 1}; }
-    int pack(const float* wsrc, const float* g, const float* b, const float* m, const float* v);
-    int load(const StateDict& sd);
-};
-
-// [Cout][Cin][KH][KW] -> [nchunk][CoutPad][16] with K = tap * CinP + c; BasicConv2d's BatchNorm2d(eps=0.001) in eval mode folded to
-// (scale, shift): (x - mean) / sqrt(var + eps) * weight + bias
-int Unit::pack(const float* wsrc, const float* g, const float* b, const float* m, const float* v) {
-    const int cin = spec.cin, cout = spec.cout, taps = spec.kh * spec.kw;
-    // column tile: the one that pads Cout least, the wider on a tie
-    int best = 128;
-    for (int bn_ : {64, 32})
-        if ((cout + bn_ - 1) / bn_ * bn_ < (cout + best - 1) / best * best) best = bn_;
-    BN = best;
-    CoutPad = (cout + BN - 1) / BN * BN;
-    const int CinP = (cin + 3) / 4 * 4;
-    C4 = CinP / 4;
-    nchunk = (taps * CinP + 15) / 16;
-    std::vector<float> p((size_t)nchunk * CoutPad * 16, 0.f);
-    for (int n = 0; n < cout; ++n)
-        for (int c = 0; c < cin; ++c)
-            for (int tap = 0; tap < taps; ++tap) {
-                const long kk = (long)tap * CinP + c;
-                p[((size_t)(kk / 16) * CoutPad + n) * 16 + kk % 16] = wsrc[((size_t)n * cin + c) * taps + tap];
-            }
-    if (int rc = w.upload(p.data(), p.size() * 4)) return rc;
-    std::vector<float> s((size_t)CoutPad * 2, 0.f);
-    for (int n = 0; n < cout; ++n) {
-        const double a = (double)g[n] / std::sqrt((double)v[n] + 1e-3);
-        s[2 * n] = (float)a;
-        s[2 * n + 1] = (float)((double)b[n] - (double)m[n] * a);
+    int pack(const float* wsrc, const float* g, const float* b, const float* m, const float* v) {
+        FlatConvPacked p = flatconv_pack(wsrc, spec.cin, spec.cout, 0, spec.kh, spec.kw);
+        flatconv_fold_bn(p, g, b, m, v, 1e-3);
+        return upload(p);
     }
-    return ss.upload(s.data(), s.size() * 4);
-}
-
-int Unit::load(const StateDict& sd) {
-    const float* wsrc = sd.f32(spec.name + ".conv.weight", (int64_t)spec.cout * spec.cin * spec.kh * spec.kw);
-    const float* g = sd.f32(spec.name + ".bn.weight", spec.cout);
-    const float* b = sd.f32(spec.name + ".bn.bias", spec.cout);
-    const float* m = sd.f32(spec.name + ".bn.running_mean", spec.cout);
-    const float* v = sd.f32(spec.name + ".bn.running_var", spec.cout);
-    if (!wsrc || !g || !b || !m || !v) return I2V_E_MISSING;
-    return pack(wsrc, g, b, m, v);
-}
+    int load(const StateDict& sd) {
+        const float* wsrc = sd.f32(spec.name + ".conv.weight", (int64_t)spec.cout * spec.cin * spec.kh * spec.kw);
+        const float* g = sd.f32(spec.name + ".bn.weight", spec.cout);
+        const float* b = sd.f32(spec.name + ".bn.bias", spec.cout);
+        const float* m = sd.f32(spec.name + ".bn.running_mean", spec.cout);
+        const float* v = sd.f32(spec.name + ".bn.running_var", spec.cout);
+        if (!wsrc || !g || !b || !m || !v) return I2V_E_MISSING;
+        return pack(wsrc, g, b, m, v);
+    }
+};
 
 // ---- topology: every Mixed block is a short program over the block input X, the block output Y and two temporaries T0, T1
 enum { X = 0, T0 = 1, T1 = 2, Y = 3 };
@@ -388,23 +224,8 @@ void pool_geom(int kind, Map d, int* stride, int* pad, Map* o) {
 int conv_launch(const Unit& u, int B, const float* in, int inCS, int inOff, Map di, float* out, int outCS, int outOff, hipStream_t st) {
     const Map d = u.out(di);
     I2V_REQUIRE(d.H > 0 && d.W > 0, I2V_E_INVALID, "inception conv %s: a [%d, %d] map is smaller than its window", u.spec.name.c_str(), di.H, di.W);
-    IncConvArgs a{};
-    a.in = in; a.wp = u.w.as<float>(); a.ss = u.ss.as<float2>(); a.out = out;
-    a.M = (long)B * d.pos();
-    a.Hi = di.H; a.Wi = di.W; a.Ho = d.H; a.Wo = d.W;
-    a.inCS = inCS; a.inOff = inOff; a.C4 = u.C4; a.G = u.spec.kh * u.spec.kw * u.C4; a.nchunk = u.nchunk;
-    a.KW = u.spec.kw; a.sH = u.spec.s; a.sW = u.spec.s; a.pH = u.spec.ph; a.pW = u.spec.pw;
-    a.Cout = u.spec.cout; a.CoutPad = u.CoutPad; a.outCS = outCS; a.outOff = outOff;
-    I2V_REQUIRE(inCS % 4 == 0 && inOff % 4 == 0 && inOff >= 0 && inOff + 4 * u.C4 <= inCS && outOff >= 0 && outOff + u.spec.cout <= outCS, I2V_E_INVALID,
-                "inception conv %s: channel slice [%d, +%d) of %d -> [%d, +%d) of %d", u.spec.name.c_str(), inOff, 4 * u.C4, inCS, outOff,
-                u.spec.cout, outCS);
-    const long nblk = (a.M + INC_BM - 1) / INC_BM * (u.CoutPad / u.BN);
-    I2V_REQUIRE(nblk > 0 && nblk < (1L << 31), I2V_E_INVALID, "inception conv %s: grid of %ld workgroups", u.spec.name.c_str(), nblk);
-    if (u.BN == 128) hipLaunchKernelGGL(inc_conv_kernel<8>, dim3((unsigned)nblk), dim3(256), 0, st, a);
-    else if (u.BN == 64) hipLaunchKernelGGL(inc_conv_kernel<4>, dim3((unsigned)nblk), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(inc_conv_kernel<2>, dim3((unsigned)nblk), dim3(256), 0, st, a);
-    I2V_HIP_CHECK(hipGetLastError());
-    return I2V_OK;
+    const FlatConvMaps g{B, 1, di.H, di.W, 1, d.H, d.W, 1, u.spec.s, u.spec.s, 0, u.spec.ph, u.spec.pw};
+    return flat_conv_launch<false>(("inception conv " + u.spec.name).c_str(), u, in, inCS, inOff, out, outCS, outOff, g, true, st);
 }
 
 int pool_launch(int kind, int B, const float* in, int C, Map di, float* out, int outCS, int outOff, hipStream_t st) {

@@ -8,8 +8,8 @@
 //   A workgroup owns an 8 x 16 tile of output positions (M = 128; wave w the tile rows 2w and 2w + 1, one 16-row MFMA tile per
 //   tile row) and BN = 64 output channels.  Per chunk of CC input channels it stages the 10 x 18 halo of the tile in LDS ONCE; the
 //   A operand of tap (dh, dw) is that same image read at pixel offset dh * 18 + dw -- nine taps, one staged image, no per-tap
-//   gather from global memory (what i3d_conv_kernel does).  The chunk's weights [9][64][CC] are staged next to it.
-//   CC = 16: pixel rows of 16 floats padded to 20 (conflict-free ds_read_b128 as in i2v_i3d.hip), A and W double-buffered, the
+//   gather from global memory (what flat_conv_kernel does).  The chunk's weights [9][64][CC] are staged next to it.
+//   CC = 16: pixel rows of 16 floats padded to 20 (conflict-free ds_read_b128 as in i2v_flatconv.h), A and W double-buffered, the
 //   next chunk's global loads in flight under the MFMAs, one barrier per chunk; 2 x (14400 + 46080) + 16 = 120976 bytes of LDS (the 16: one spare float4 for idle staging slots).
 //   CC = 4: the first layer, stored (r, g, b, 0): one chunk, K = 36, no padded taps; rows of 4 floats, one float per lane and tap.
 //   Loads are unconditional with clamped addresses; the halo outside the map is zero.  The K order of an output element is
@@ -25,8 +25,6 @@
 
 namespace i2v {
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // f(0), f(1), ..., f(N - 1) with the index a compile-time constant: register arrays stay registers
 template <int I, int N, class F>
@@ -347,8 +345,6 @@ __global__ __launch_bounds__(256) void pairdiff_final_kernel(const double* __res
         acc[1] += (double)R * (R - 1);
     }
 }
-
-unsigned grid_for(long total) { return (unsigned)std::min<long>((total + 255) / 256, 1L << 20); }
 
 // torchvision vgg16().features: index of every conv, its widths, and whether a tap / a pool follows its ReLU
 struct LayerSpec { int idx, cin, cout, tap, pool; };

@@ -134,11 +134,14 @@ def test_header_symbols_and_sources():
     for name in FVD_SYMBOLS:
         assert name in declared and name in i2v_native.SYMBOLS and hasattr(lib, name), name
     assert "metrics/PyTorch_FVD/I3D.py" in header and "FVD_logging" in header
-    src = open(os.path.join(PKG, "csrc", "i2v_i3d.hip")).read()
+    i3d = open(os.path.join(PKG, "csrc", "i2v_i3d.hip")).read()
+    assert '#include "i2v_flatconv.h"' in i3d                       # its conv kernel and the packing: checked with it
+    src = i3d + "".join(open(os.path.join(PKG, "csrc", f)).read() for f in ("i2v_flatconv.h", "i2v_flatconv_pack.h"))
     assert "getenv" not in src and "atomic" not in src.replace("no atomics", "")
     assert "mfma_f32_16x16x4f32" in src
     mk = open(os.path.join(PKG, "csrc", "Makefile")).read()
     assert "i2v_i3d.hip" in mk.split("SRCS =")[1].splitlines()[0]
+    assert {"i2v_flatconv.h", "i2v_flatconv_pack.h"} <= set(mk.split("HDRS =")[1].splitlines()[0].split())
     pkg_fvd = open(os.path.join(PKG, "metrics", "PyTorch_FVD", "FVD_logging.py")).read()
     assert not re.search(r"^\s*(import|from) scipy", pkg_fvd, flags=re.M)
 

@@ -1,0 +1,87 @@
+"""Digests of the I3D and Inception-v3 trunks for A/B runs of changes to their conv kernel or its host code: prints one sha256 per case
+over the output bytes of every conv-unit and Mixed case of tests/i3d_units_common.py (both I3D variants) and of tests/fid_common.py, and
+of one whole trunk each at its smallest legal input (2 clips of 9 x 32 x 32 frames through the Kinetics I3D, 2 images of 75 x 75 through
+Inception).  Two builds of the library compute the same function iff the two outputs are equal, e.g.
+
+    python tools/trunk_bits.py > a.txt;  I2V_LIB_PATH=<other build, relative to the repository> python tools/trunk_bits.py > b.txt
+
+The digests depend on the toolchain (fmaf contraction), so they are compared between builds on one machine, never stored."""
+import hashlib
+import os
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (REPO, os.path.join(REPO, "image2video-synthesis-using-cinns_amd"), os.path.join(REPO, "tests")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+import torch   # noqa: E402
+
+import fid_common as fc          # noqa: E402
+import i2v_native                # noqa: E402
+import i3d_units_common as uc    # noqa: E402
+
+SENTINEL = -777.25
+SEED_FID = 91
+
+
+def sha(*tensors):
+    m = hashlib.sha256()
+    for t in tensors:
+        m.update(t.cpu().contiguous().numpy().tobytes())
+    return m.hexdigest()
+
+
+def cl5(x):
+    return x.permute(0, 2, 3, 4, 1).contiguous().cuda()
+
+
+def i3d_cases():
+    nets = {}
+    for v in ("kin", "dt"):
+        nets[v] = i2v_native.NativeI3D(uc.CLASSES[v], dt_length=None if v == "kin" else 16)
+        nets[v].load(uc.state_dict(v))
+    for case in uc.unit_cases():   # into a channel slice of a sentinel-filled buffer, as tests/test_gpu_i3d_units.py does
+        n, unit, x = nets[case["variant"]], case["unit"], uc.unit_input(case)
+        if unit == uc.UNIT_STEM:
+            x = torch.cat([x, uc.randn(case["seed"] + 7, (x.shape[0], 1, *x.shape[2:]))], 1)
+        _, cout, od = n.unit_shape(unit, *x.shape[2:])
+        out = torch.full((x.shape[0], *od, cout + 20), SENTINEL, dtype=torch.float32, device="cuda")
+        n.unit_forward(unit, cl5(x), out, 12)
+        print(f"i3d unit {case['id']} {sha(out)}", flush=True)
+    for case in uc.MIXED_CASES:
+        i = uc.BLOCKS.index(case["block"])
+        x = uc.randn(case["seed"], (case["shape"][0], uc.fc.MIXED[i][1], *case["shape"][1:]))
+        print(f"i3d mixed {case['id']} {sha(nets[case['variant']].mixed_forward(i, cl5(x)))}", flush=True)
+    frames = torch.from_numpy(fc.clips(15001, 2, 9, 32, 32)).cuda().contiguous()
+    print(f"i3d trunk kin 2x9x32x32 {sha(nets['kin'].forward(frames, True))}", flush=True)
+
+
+def inception_cases():
+    for case in fc.conv_cases():   # the channel slices of tests/test_gpu_fid.py
+        x, (w, bn) = fc.conv_input(case), fc.conv_params(case)
+        xc = fc.to_cl(x, pad4=case["cin"] == 3)
+        in_off, out, out_off = 0, None, 0
+        if case["slices"]:
+            in_off, out_off = 8, 12
+            wide = torch.full((*xc.shape[:3], xc.shape[3] + 20), 1e30)
+            wide[..., in_off:in_off + xc.shape[3]] = xc
+            xc = wide
+            (kh, kw), s, (ph, pw), (h, wd) = case["kernel"], case["stride"], case["padding"], case["hw"]
+            out = torch.full((x.shape[0], (h + 2 * ph - kh) // s + 1, (wd + 2 * pw - kw) // s + 1, case["cout"] + 16), SENTINEL, device="cuda")
+        full = i2v_native.inception_conv_unit(xc.cuda(), w, bn, case["stride"], case["padding"], in_off=in_off, out=out, out_off=out_off)
+        print(f"inception conv {case['id']} {sha(full)}", flush=True)
+    net = i2v_native.NativeInception()
+    net.load(fc.fid_state_dict(SEED_FID))
+    for block, batch, hw in fc.MIXED_CASES:
+        bi = fc.BLOCK_NAMES.index(block)
+        x = fc.randn(13000 + bi, (batch, fc.MIXED[bi][2], *hw))
+        print(f"inception mixed {block} {sha(net.mixed(bi, fc.to_cl(x).cuda()))}", flush=True)
+    x = torch.from_numpy(fc.clips(14075, 2, 1, 75, 75))[:, 0].contiguous().cuda()
+    print(f"inception trunk 2x75x75 {sha(*net.features(i2v_native.inception_input_stage(x, resize=False), (0, 1, 2, 3)))}", flush=True)
+
+
+if __name__ == "__main__":
+    torch.set_grad_enabled(False)
+    i3d_cases()
+    inception_cases()
