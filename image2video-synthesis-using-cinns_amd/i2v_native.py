@@ -193,6 +193,12 @@ SYMBOLS = {
                                             POINTER(c_double), POINTER(c_int64), POINTER(c_int32)]),
     "i2v_frames_peak": (c_int32, [c_void_p, POINTER(FramesCfg), c_void_p, c_int32, c_void_p]),
     "i2v_frames_to_u8": (c_int32, [c_void_p, POINTER(FramesCfg), c_void_p, c_void_p, c_int32, c_void_p]),
+    "i2v_recon_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "i2v_recon_range": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int64, c_int64, c_void_p, c_void_p, c_size_t,
+                                  c_void_p]),
+    "i2v_recon_stats": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int64, c_int64, c_void_p, c_double, c_void_p,
+                                  c_void_p, c_void_p, c_size_t, c_void_p]),
+    "i2v_kl_normal": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
 }
 
 
@@ -1645,3 +1651,77 @@ def inception_global_avg(x):
     with torch.cuda.device(x.device):
         _check(lib().i2v_inception_global_avg(x.data_ptr(), n, h, w, c, out.data_ptr(), _stream()), "i2v_inception_global_avg")
     return out
+
+
+def _recon_view(x, what):
+    """(tensor, B, T, C, H, W, batch stride in floats) of a float32 device tensor [B, T, C, H, W] or [N, C, H, W] whose [T, C, H, W] blocks are
+    contiguous (any batch stride: the view ``seq[:, 1:]`` is taken in place); anything else on the device is made contiguous."""
+    if not isinstance(x, torch.Tensor) or x.dim() not in (4, 5):
+        raise I2VError(f"{what}: expected frames [B,T,C,H,W] or [N,C,H,W], got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x)}")
+    if not x.is_cuda:
+        raise I2VError(f"{what}: libi2v_hip kernels need tensors on a HIP device (got a CPU tensor); this package has no CPU fallback")
+    if x.dtype != torch.float32:
+        raise I2VError(f"{what}: expected float32 frames, got {x.dtype}")
+    if x.dim() == 4:
+        x = x.unsqueeze(1)
+    view = NativeDecoder._sample_strided(x, x.shape[1:])
+    if view is None:
+        x = x.contiguous()
+        view = (x.data_ptr(), x[0].numel())
+    return (x, *x.shape, view[1])
+
+
+def _recon_args(pred, target, what):
+    p, t = _recon_view(pred, what), _recon_view(target, what)
+    if p[1:6] != t[1:6] or p[0].device != t[0].device:
+        raise I2VError(f"{what}: pred {tuple(pred.shape)} on {pred.device} and target {tuple(target.shape)} on {target.device} do not match")
+    shape = tuple(int(v) for v in p[1:6])
+    nbytes = int(lib().i2v_recon_workspace_bytes(*shape))
+    if nbytes == 0:
+        raise I2VError(f"{what}: frames of shape {shape} are refused (empty, or too large)")
+    return p[0], t[0], shape, int(p[6]), int(t[6]), torch.empty(nbytes, dtype=torch.uint8, device=p[0].device)
+
+
+def recon_range(pred, target):
+    """``i2v_recon_range``: float64 [4] on the device = min(pred), max(pred), min(target), max(target)."""
+    p, t, shape, pbs, tbs, ws = _recon_args(pred, target, "recon_range")
+    out = torch.empty(4, dtype=torch.float64, device=p.device)
+    with torch.cuda.device(p.device):
+        _check(lib().i2v_recon_range(p.data_ptr(), t.data_ptr(), *shape, pbs, tbs, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+               "i2v_recon_range")
+    return out
+
+
+def recon_stats(pred, target, data_range=None):
+    """``i2v_recon_stats`` (behind ``i2v_recon_range`` when ``data_range`` is None) on two frame tensors [B, T, C, H, W] (or [N, C, H, W]) ->
+    (scalars float64 [5]: L1 mean, MSE, PSNR, SSIM, number of SSIM terms; per_image float64 [N, 3]: sum |p - t|, sum (p - t)^2, sum of the
+    SSIM map; range float64 [4] or None).  Everything stays on the device and nothing synchronises."""
+    fixed = 0.0
+    if data_range is not None:
+        fixed = float(data_range)
+        if not fixed > 0.0:
+            raise I2VError(f"recon_stats: data_range must be a positive number or None, got {data_range!r}")
+    p, t, shape, pbs, tbs, ws = _recon_args(pred, target, "recon_stats")
+    n = shape[0] * shape[1]
+    scalars = torch.empty(5, dtype=torch.float64, device=p.device)
+    per_image = torch.empty(n, 3, dtype=torch.float64, device=p.device)
+    rng = None
+    with torch.cuda.device(p.device):
+        if data_range is None:
+            rng = torch.empty(4, dtype=torch.float64, device=p.device)
+            _check(lib().i2v_recon_range(p.data_ptr(), t.data_ptr(), *shape, pbs, tbs, rng.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+                   "i2v_recon_range")
+        _check(lib().i2v_recon_stats(p.data_ptr(), t.data_ptr(), *shape, pbs, tbs, None if rng is None else rng.data_ptr(), fixed,
+                                     per_image.data_ptr(), scalars.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "i2v_recon_stats")
+    return scalars, per_image, rng
+
+
+def kl_normal(mu, logvar):
+    """``i2v_kl_normal``: -0.5 * mean_b sum_d (1 + logvar - mu^2 - exp(logvar)) of mu, logvar [B, D] fp32 -> float64 0-d on the device."""
+    _require_gpu(mu, logvar)
+    if mu.dim() != 2 or mu.shape != logvar.shape or mu.device != logvar.device:
+        raise I2VError(f"kl_normal: expected mu and logvar [B,D] on one device, got {tuple(mu.shape)} / {tuple(logvar.shape)}")
+    out = torch.empty(1, dtype=torch.float64, device=mu.device)
+    with torch.cuda.device(mu.device):
+        _check(lib().i2v_kl_normal(mu.data_ptr(), logvar.data_ptr(), mu.shape[0], mu.shape[1], out.data_ptr(), _stream()), "i2v_kl_normal")
+    return out[0]

@@ -1,0 +1,118 @@
+"""Stage-1 losses and validation metrics, mirror of the reference's ``stage1_VAE/modules/loss.py``: ``KL``, ``fmap_loss``, ``hinge_loss`` and
+``Backward`` with the reference's ``eval`` (loss.py:183-216).  The training step ``Backward.forward`` is not built.
+
+The reference takes ``psnr`` and ``ssim`` from ``pytorch_lightning.metrics.functional`` (1.2.7).  Here they are two kernel entries of
+csrc/i2v_recon.hip over frames that stay on the device: one range pass and one pass that forms the L1 error, the MSE and the SSIM map in
+float64 (DESIGN §12.4 states the formulas; the row is pinned to them, not to the library).  Argument order as the library's and as the
+reference calls them, ``psnr(seq_orig, seq_gen)``: ``pred`` is the real clip and ``target`` the generated one -- with ``data_range=None``
+only ``target`` sets the range of the PSNR (the 1.2.x rule, kept).
+
+Differences of ``Backward`` from the reference, all of the surface and none of the numbers: no ``wandb.log``; the two returned sequences
+stay on the device; ``lpips`` is an ``LPIPS`` instance the caller builds from files (``LPIPS(vgg_path=..., lin_path=...)``: nothing is
+downloaded), and with ``lpips=None`` the key ``LPIPS`` is left out; the five values reach the host in ONE copy."""
+import math
+
+import torch
+import torch.nn as nn
+
+import i2v_native
+
+
+def KL(mu, logvar):
+    """KL divergence between N(mu, exp(logvar)) and the unit Gaussian (loss.py:10-12).  On a HIP device: ``i2v_kl_normal`` (one
+    workgroup, float64, fixed order) -> float64 0-d device tensor.  CPU tensors are refused (no CPU fallback)."""
+    mu, logvar = mu.reshape(mu.size(0), -1), logvar.reshape(logvar.size(0), -1)
+    return i2v_native.kl_normal(mu.float().contiguous(), logvar.float().contiguous())
+
+
+def fmap_loss(fmap1, fmap2, metric):
+    """Feature-map loss over two lists of discriminator maps (loss.py:14-21)."""
+    recp_loss = 0
+    for a, b in zip(fmap1, fmap2):
+        recp_loss = recp_loss + (torch.mean(torch.abs(a - b)) if metric == "L1" else torch.mean((a - b) ** 2) if metric == "L2" else 0)
+    return recp_loss / len(fmap1)
+
+
+def hinge_loss(fake_data, orig_data, update):
+    """Hinge loss for the discriminator (``update='disc'``) or the generator (``'gen'``) (loss.py:24-32)."""
+    if update == "disc":
+        return (torch.mean(torch.relu(1.0 - orig_data)) + torch.mean(torch.relu(1.0 + fake_data))) / 2
+    elif update == "gen":
+        return -torch.mean(fake_data)
+
+
+def recon_metrics(pred, target, data_range=None, per_image=False):
+    """PSNR, SSIM, L1 and MSE of two frame tensors [B, T, C, H, W] (or [N, C, H, W]) on a HIP device -> dict of float64 0-d device tensors
+    ``l1, mse, psnr, ssim``; nothing synchronises.  ``data_range=None`` is the reference's behaviour (ranges taken from the data: PSNR from
+    ``target`` alone, SSIM from the wider of the two); ``data_range=2.0`` is the fixed-range form for frames in [-1, 1].
+    ``per_image=True`` adds ``psnr_per_image`` and ``ssim_per_image`` [B, T] (the per-frame curves of the prediction literature; the
+    per-image PSNR uses the same R).  A strided view such as ``seq[:, 1:]`` is read in place."""
+    scalars, rows, rng = i2v_native.recon_stats(pred, target, data_range)
+    out = {"l1": scalars[0], "mse": scalars[1], "psnr": scalars[2], "ssim": scalars[3]}
+    if per_image:
+        lead = tuple(pred.shape[:2]) if pred.dim() == 5 else (pred.shape[0],)
+        c, h, w = pred.shape[-3:]
+        r = torch.full((), float(data_range), dtype=torch.float64, device=rows.device) if data_range is not None else rng[3] - rng[2]
+        out["psnr_per_image"] = ((2 * torch.log(r) - torch.log(rows[:, 1] / (c * h * w))) * (10.0 / math.log(10.0))).view(lead)
+        out["ssim_per_image"] = (rows[:, 2] / (c * (h - 10) * (w - 10))).view(lead)
+    return out
+
+
+def psnr(pred, target, data_range=None):
+    """``pytorch_lightning.metrics.functional.psnr(pred, target, data_range)`` at its defaults (base 10, mean over all elements)."""
+    return recon_metrics(pred, target, data_range)["psnr"]
+
+
+def ssim(pred, target, data_range=None):
+    """``pytorch_lightning.metrics.functional.ssim(pred, target, data_range=data_range)`` at its defaults (11 x 11 window, sigma 1.5,
+    k1 = 0.01, k2 = 0.03, mean)."""
+    return recon_metrics(pred, target, data_range)["ssim"]
+
+
+def _section(opt, name):
+    sec = None if opt is None else (opt.get(name) if isinstance(opt, dict) else getattr(opt, name, None))
+    return sec if sec is not None else {}
+
+
+class Backward(nn.Module):
+    """Losses of stage 1 (loss.py:47-216).  ``eval`` is built, ``forward`` (the training step) is not."""
+
+    def __init__(self, opt, lpips=None):
+        super().__init__()
+        self.dic = opt
+        training, data = _section(opt, "Training"), _section(opt, "Data")
+        for attr, key in (("w_kl", "w_kl"), ("gan_loss", "GAN_Loss"), ("w_coup_t", "w_coup_t"), ("w_fmap_t", "w_fmap_t"), ("w_coup_s", "w_coup_s"),
+                          ("subsample_length", "subsample_length"), ("w_mse", "w_recon"), ("w_GP", "w_GP"), ("w_percep", "w_percep"),
+                          ("pretrain", "pretrain")):
+            setattr(self, attr, training.get(key))
+        self.seq_length = data.get("sequence_length")
+        self.lpips = lpips            # the reference builds LPIPS().cuda() here, which downloads its weights
+        self.data_range = None        # None: the reference's data-dependent ranges
+        self.per_image = False        # True: eval() also appends the [B, T] PSNR / SSIM curves (device tensors) to self.curves
+        self.curves = []
+
+    def forward(self, decoder, encoder, disc_t, disc_s, seq_o, optimizers, epoch, logger):
+        raise NotImplementedError("Backward.forward (the stage-1 training step, loss.py:64-180) is not built: it needs the backward passes of "
+                                  "the decoder and of the motion encoder and the two discriminators (patch_disc.NLayerDiscriminator, "
+                                  "resnet3D.Discriminator) with their gradient penalty; Backward.eval is built")
+
+    @torch.no_grad()
+    def eval(self, decoder, encoder, seq_o, logger):
+        """loss.py:183-216: encode ``seq_o[:, 1:]``, decode from ``seq_o[:, 0]``, log Loss_L1, LPIPS, L_KL, PSNR, SSIM of the reconstruction.
+        Returns ``[seq_gen, seq_orig]`` on the device."""
+        seq_orig = seq_o[:, 1:]
+        motion, mu, covar = encoder(seq_orig.transpose(1, 2))
+        seq_gen = decoder(seq_o[:, 0], motion)
+
+        m = recon_metrics(seq_orig, seq_gen, self.data_range, per_image=self.per_image)   # psnr(seq_orig, seq_gen), ssim(seq_orig, seq_gen)
+        values = {"Loss_L1": m["l1"]}
+        if self.lpips is not None:
+            values["LPIPS"] = self.lpips(seq_orig.reshape(-1, *seq_orig.shape[2:]), seq_gen.reshape(-1, *seq_gen.shape[2:])).mean().double()
+        values.update({"L_KL": KL(mu, covar), "PSNR": m["psnr"], "SSIM": m["ssim"]})
+        if self.per_image:
+            self.curves.append((m["psnr_per_image"], m["ssim_per_image"]))
+
+        host = torch.stack(list(values.values())).cpu().tolist()   # the one device-to-host copy
+        loss_dic = dict(zip(values, host))
+        logger.append(loss_dic)
+        return [seq_gen.detach(), seq_orig]

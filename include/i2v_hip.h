@@ -659,6 +659,41 @@ int i2v_frames_peak(const float* x, const i2v_frames_cfg* cfg, float* peak, int3
  * peak = NULL.  Null pointers, non-positive sizes, k not dividing n, a block that does not fit dst: I2V_E_INVALID before any launch. */
 int i2v_frames_to_u8(const float* x, const i2v_frames_cfg* cfg, const float* peak, uint8_t* dst, int32_t mode, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Stage-1 validation metrics (csrc/i2v_recon.hip) -- stage1_VAE/modules/loss.py: Backward.eval :183-216 and KL :10-12.  PSNR, SSIM,
+ * the L1 error and the KL term of a reconstruction, on frames that stay on the device.  The reference takes psnr and ssim from
+ * pytorch_lightning.metrics.functional (1.2.7); this row is pinned to the formulas below, not to that library.
+ * Both frame tensors are fp32 [b][t][c][h][w]; `pred_bstride` / `target_bstride` are the floats between two batch entries (0 = dense,
+ * t*c*h*w), so the view seq[:, 1:] needs no copy.  An image is one [c][h][w] block, N = b*t of them.  Argument order as the reference
+ * calls psnr(seq_orig, seq_gen) / ssim(seq_orig, seq_gen): `pred` is the real clip, `target` the generated one.
+ * Stateless; every call only enqueues on `stream`, reads no environment, accumulates in float64 in two fixed-order stages with one
+ * owner per output element and plain stores (two runs give the same bits).  Bad arguments: I2V_E_INVALID, a short workspace:
+ * I2V_E_WORKSPACE, before any launch.
+ * ---------------------------------------------------------------------------------------- */
+/* Bytes of the workspace of i2v_recon_range and i2v_recon_stats; 0 for a shape they refuse. */
+size_t i2v_recon_workspace_bytes(int32_t b, int32_t t, int32_t c, int32_t h, int32_t w);
+/* range[4] (device doubles) = min(pred), max(pred), min(target), max(target): the data_range=None rule of psnr / ssim
+ * (loss.py:191, :194 pass none). */
+int i2v_recon_range(const float* pred, const float* target, int32_t b, int32_t t, int32_t c, int32_t h, int32_t w, int64_t pred_bstride,
+                    int64_t target_bstride, double* range, void* workspace, size_t workspace_bytes, void* stream);
+/* One pass over both tensors (loss.py:191 psnr, :194 ssim, :199 the L1 error).  R comes from `range` (what i2v_recon_range wrote,
+ * fixed_range = 0) or from the host value fixed_range > 0 (range may then be NULL).
+ *   per_image [N][3]  sum |p - t|, sum (p - t)^2, sum of the SSIM map over its valid positions, of image n
+ *   scalars [5]       mean |p - t|; MSE; PSNR = (2 ln R - ln MSE) * 10 / ln 10 with R = max(target) - min(target) (only the generated
+ *                     frames set it: the 1.2.x rule, kept) or fixed_range; SSIM; the number of SSIM terms N c (h - 10) (w - 10).
+ *                     They come from the per_image rows summed in index order.  Identical inputs: PSNR = +inf.
+ * SSIM: R = max(max p - min p, max t - min t) or fixed_range, c1 = (0.01 R)^2, c2 = (0.03 R)^2; window = outer product of g / sum g,
+ * g_i = exp(-(d_i / 1.5)^2 / 2), d = -5..5, applied per channel to p, t, p^2, t^2, p t (separably, in float64); with mu and
+ * sigma.. = E[..] - mu mu from those five, ssim = (2 mu_p mu_t + c1)(2 sigma_pt + c2) / ((mu_p^2 + mu_t^2 + c1)(sigma_p^2 + sigma_t^2 + c2)),
+ * averaged over the (h - 10) x (w - 10) positions whose window lies inside the image (what the reflect-pad-and-crop of the library
+ * leaves).  h < 11 or w < 11 is refused.  Constant frames (R = 0) give 0 / 0 = NaN as in the reference; nothing synchronises to refuse it. */
+int i2v_recon_stats(const float* pred, const float* target, int32_t b, int32_t t, int32_t c, int32_t h, int32_t w, int64_t pred_bstride,
+                    int64_t target_bstride, const double* range, double fixed_range, double* per_image, double* scalars,
+                    void* workspace, size_t workspace_bytes, void* stream);
+/* KL (loss.py:10-12): out[0] (device double) = -0.5 * mean_b sum_d (1 + logvar - mu^2 - exp(logvar)); mu, logvar [b][d] fp32.
+ * One workgroup, float64, fixed order. */
+int i2v_kl_normal(const float* mu, const float* logvar, int32_t b, int32_t d, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
