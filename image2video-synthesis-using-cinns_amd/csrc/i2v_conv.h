@@ -156,6 +156,9 @@ struct Wino4Weights {
 bool wino4_supported(int cout, int cin, int T, int H, int W, int KT, bool one = false);
 int wino4_forward(const Wino4Weights& wts, const void* v16, float* out, const float* res, int rt, int rs, int B, int T,
                   int H, int W, int epi, hipStream_t st, double* stats = nullptr);
+// Share of the tap loops' MFMAs a wino4_forward launch of this shape issues (T = output frames, as above): 1, or less where the plan
+// picks the kernel that skips the units reading only the clip's temporal zero padding (i2v_conv16w4e.hip)
+double wino4_issued_share(const Wino4Weights& wts, int B, int T, int H, int W);
 
 // The same conv with the operand GENERATED in the kernel (conv_wino4g_f16x3_kernel: 8 MFMA waves + 4 producer waves per workgroup):
 // x = the conv's fp32 input BEFORE normalisation / activation, channels-last [B][T][H / us][W / us][Cin]; coef = per-(b,c) (A, B)

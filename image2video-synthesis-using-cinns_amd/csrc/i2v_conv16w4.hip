@@ -35,6 +35,12 @@
 // requests before the loop (the loop's counts assume the steady state).  tools/check_asm_waits.py replays both compiled loops
 // of every instantiation, checks that each is entered with nothing in flight and that no asm load reads a freshly
 // VALU-written SGPR.
+// Temporal edge units: the 512-thread 3x3x3 and pair launches whose MFMA row blocks lie inside one frame (TT = 4 / TH = 8, TT = 2 /
+// TH = 16 -- every such launch of the shipped configs) run conv_wino4e_f16x3_kernel (i2v_conv16w4e.hip, plan form W4_EDGE): the same
+// template with the (kt, row block) units that read only the clip's temporal zero padding left out of the tap loops at compile time
+// (w4_unit_dead, i2v_conv16w4_edge.h).  Same bits.  The instantiations of this file remain the kernels of every other case -- the 2-D
+// convs, the 256-thread thin layers, the persistent forms -- and, in the measurement build, the A/B and bit reference of the edge
+// kernel (I2V_W4_TSKIP=0).
 #include "i2v_conv16w4_dev.h"
 
 namespace i2v {
@@ -71,7 +77,7 @@ int Wino4Weights::pack_tdup(const float* w_src, const float* bias_src, int cout,
 // the brick -> XCD order (I2V_W4_ORDER) and the launch trace (I2V_W4_TRACE) -- exist in the measurement build only
 // (tools/build_measurement_libs.sh measure -> tools/_tl/libi2v_hip_measure.so, loaded through I2V_LIB_PATH; tools/conv16w_check*
 // are built with the flag too), where they are read per launch so that tests and A/B runs can flip them inside one process.
-// The one-term form has no switches: it always runs the defaults.
+// The one-term form has no structure switches: it always runs the defaults (but for I2V_W4_TSKIP and the trace).
 // 32-channel 3x3x3 layers with the V requests issued by four extra waves (i2v_conv16w4g.hip, MODE 2; I2V_W4_LOADER=1 in the measurement
 // build).  Measured neutral to negative (profiles/r06_e_thin_loader_ab.txt: 32 -> 32 0.380 vs 0.384 ms, 64 -> 32 0.561 vs 0.545 ms at B = 8;
 // 1.33 vs 1.31-1.33 and 2.05 vs 1.93-1.97 ms at B = 32): what the thin layers' tap loops gain without ANY operand traffic (-21 % / -34 %) is
@@ -87,8 +93,18 @@ static W4Switches w4_switches() {
     if (const char* e = getenv("I2V_W4_SKEW")) w.skew = atoi(e);
     w.trace = getenv("I2V_W4_TRACE") != nullptr;
     if (const char* e = getenv("I2V_W4_LOADER")) w.loader = atoi(e);
+    if (const char* e = getenv("I2V_W4_TSKIP")) w.tskip = atoi(e);   // 0: the full tap loops on every brick (A/B and bit reference of i2v_conv16w4e.hip)
 #endif
     return w;
+}
+
+// (the one-term form has no structure switches: of the measurement build's it takes the edge form's A/B switch and the launch trace only)
+static W4Switches w4_plan_switches(const Wino4Weights& wts) {
+    const W4Switches sw = w4_switches();
+    if (!wts.one) return sw;
+    W4Switches d{};
+    d.tskip = sw.tskip; d.trace = sw.trace;
+    return d;
 }
 
 // The launch plan of every F(4,3) kernel.  Neither the tile width, the brick shape nor the workgroup size enters the accumulation order
@@ -178,8 +194,18 @@ int wino4_plan(W4Plan* p, const Wino4Weights& wts, int B, int T, int H, int W, b
         p->NTH = W4G_THREADS;
         p->lds_bytes = (size_t)a.tofs + 5 * W4Geo<512>::TILES * 4;
     }
+    // Temporal edge units (i2v_conv16w4e.hip): the one-workgroup-per-brick 512-thread split kernel whose row blocks lie inside one frame
+    // -- geometry only: 3-D taps, the TT = 4 / TH = 8 and TT = 2 / TH = 16 bricks its masks are compiled for (TT = 1 / TH = 32, odd clips:
+    // no shipped config).  Every such launch has edge bricks (nbT x TT = T).
+    p->issued = 1.0;
+    if ((p->form == W4_SPLIT || p->form == W4_ONE) && sw.tskip && p->NTH == 512 && p->PIPE == 0 && KT >= 2 && TH * 4 >= 32 && (TT == 4 || TT == 2)) {
+        p->form = p->form == W4_ONE ? W4_EDGE_ONE : W4_EDGE;
+        long dead, units;
+        w4_dead_units(a.T, TT, a.th_shift, KT, a.tdup, &dead, &units);
+        p->issued = 1.0 - (double)dead / (double)units;
+    }
 #ifdef W4_TAPTIME
-    if (p->form == W4_SPLIT) p->lds_bytes = 160 * 1024;   // + the per-tap timing slots
+    if (p->form == W4_SPLIT || p->form == W4_EDGE || p->form == W4_EDGE_ONE) p->lds_bytes = 160 * 1024;   // + the per-tap timing slots
 #endif
     return I2V_OK;
 }
@@ -198,6 +224,7 @@ static int launch_wino4_(const W4Plan& p, hipStream_t st) {
 }
 
 static int wino4_launch(const W4Plan& p, hipStream_t st) {
+    if (p.form == W4_EDGE || p.form == W4_EDGE_ONE) return wino4e_launch(p, st);
     if (p.form == W4_ONE) return wino4h_launch(p, st);
     if (p.form == W4_LOADER1 || p.form == W4_LOADER2) return wino4_loader_launch(p, st);
     // (the order of the cases is the order in which the kernels are instantiated and emitted: keep it, the code object stays the same)
@@ -223,7 +250,7 @@ static int wino4_launch(const W4Plan& p, hipStream_t st) {
 int wino4_forward(const Wino4Weights& wts, const void* v16, float* out, const float* res, int rt, int rs, int B, int T, int H,
                   int W, int epi, hipStream_t st, double* stats) {
     I2V_REQUIRE(wts.w.p, I2V_E_STATE, "%s: weights not packed", wts.one ? "wino4h" : "wino4");
-    const W4Switches sw = wts.one ? W4Switches{} : w4_switches();      // (defaults unless built with -DI2V_MEASURE)
+    const W4Switches sw = w4_plan_switches(wts);      // (defaults unless built with -DI2V_MEASURE)
     W4Plan p;
     if (int rc = wino4_plan(&p, wts, B, T, H, W, res != nullptr, rt, rs, epi, stats != nullptr, device_cus(), sw)) return rc;
     W4Args& a = p.a;
@@ -237,6 +264,22 @@ int wino4_forward(const Wino4Weights& wts, const void* v16, float* out, const fl
     }
     return wino4_launch(p, st);
 }
+
+// share of the full tap loops' matrix-core work a launch of this layer issues (the layer profile's issued-MFMA FLOPs): < 1 where the
+// plan picks the edge form
+double wino4_issued_share(const Wino4Weights& wts, int B, int T, int H, int W) {
+    const W4Switches sw = w4_plan_switches(wts);
+    W4Plan p;
+    if (wino4_plan(&p, wts, B, T, H, W, false, 1, 1, EPI_NONE, false, device_cus(), sw)) return 1.0;
+    return p.issued;
+}
+#endif
+
+#if defined(W4_TIMELINE) || defined(W4_TAPTIME)   // instrumented builds: the edge kernel shares this unit's device-side buffers
+}  // namespace i2v
+#define W4E_IN_MAIN
+#include "i2v_conv16w4e.hip"
+namespace i2v {
 #endif
 
 #ifdef W4_TAPTIME

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "i2v_conv.h"
+#include "i2v_conv16w4_edge.h"
 
 #ifdef W4_NO_INSTRUMENT
 #undef W4_TIMELINE
@@ -179,11 +180,15 @@ constexpr int W4_PAD_ROW = 1 << 25;
 // [c0-7 | c16-23 | c8-15 | c24-31], so the two operands a lane reads per row block ("ah" / "al" below) are the k-steps of channels
 // 0..15 and 16..31, and the weight fragment's halves are those two k-steps instead of hi | lo: a tap issues 2 WM MFMAs (ah bh, al bl)
 // instead of 3 WM over twice the channels -- one third per input channel.  Same loads in the same order, same wait counts.
-template <int NT, int WM, int VH0, int VH1, int NTH, bool PRE, bool PREL, int VXP, bool BUF, class Between, bool ONE = false>
+// DEAD (i2v_conv16w4e.hip): compile-time mask over (kt, own row block), bit kt * WM + wm, of the units that read zero padding only
+// (w4_unit_dead).  A dead unit's MFMAs are not emitted, nor its operand's two ds_read_b128 and their address piece; every other piece
+// keeps its slot -- the weight requests, every V request, every wait, both barriers, the priorities -- so the in-order VMEM stream and
+// the hand-counted waits are those of DEAD = 0, and so are the bits: the products left out are exact zeros.
+template <int NT, int WM, int VH0, int VH1, int NTH, bool PRE, bool PREL, int VXP, bool BUF, class Between, bool ONE = false, unsigned DEAD = 0>
 __device__ __forceinline__ void w4_pass(const W4Args& a, char* smem, const int* gpos, const int* gposN, f32x16 (&acc)[WM],
                                         int (&arow)[WM], const char* wfrag, int HH, int tid, int lane, int wave, int rb0, int rb1,
                                         const W4Next& nxt, Between&& between, int w4_tlv_, __amdgpu_buffer_rsrc_t vrsrc,
-                                        std::bool_constant<ONE> = {}) {
+                                        std::bool_constant<ONE> = {}, std::integral_constant<unsigned, DEAD> = {}) {
     constexpr int RPL = NTH / 4;          // V rows staged by one load instruction of the workgroup (4 threads per 64-byte row)
     // GEN (VH0 = VH1 = 0): this pass requests no V at all -- the producer waves of conv_wino4g_f16x3_kernel generate every chunk's
     // brick into the buffer the chunk barrier publishes (same buffers, same barriers); the wait counts then hold only weight loads
@@ -274,11 +279,15 @@ __device__ __forceinline__ void w4_pass(const W4Args& a, char* smem, const int* 
         (o).ah[wm] = *reinterpret_cast<const half8*>(v_lds + adn[wm]);                                               \
         W4_ABL_AL((o).al[wm] = *reinterpret_cast<const half8*>(v_lds + (adn[wm] ^ 16)), (o).al[wm] = (o).ah[wm]);    \
     }
+    /* (DEAD = 0 folds in the front end: the kernels without a mask are compiled from exactly the code they were) */
+#define W4_IS_DEAD(TAP, wm) (DEAD != 0u && (((DEAD) >> (((TAP) / 3) * WM + (wm))) & 1u))
 #define W4_LOAD_A(o, TAP, VB)                                                                                        \
     {                                                                                                                \
         _Pragma("unroll") for (int wm = 0; wm < WM; ++wm) {                                                          \
-            W4_ADDR_A(TAP, VB, wm)                                                                                   \
-            W4_READ_A(o, wm)                                                                                         \
+            if (!W4_IS_DEAD(TAP, wm)) {                                                                              \
+                W4_ADDR_A(TAP, VB, wm)                                                                               \
+                W4_READ_A(o, wm)                                                                                     \
+            }                                                                                                        \
         }                                                                                                            \
     }
     /* weight fragments of one tap: scalar base + the lane's 16 bytes */                                            \
@@ -299,11 +308,12 @@ __device__ __forceinline__ void w4_pass(const W4Args& a, char* smem, const int* 
     // arithmetic and the two ds_read_b128 of the next tap's A operands, then the weight request of tap U + R - 1.
     // MFMAs per row block and tap, and the gap behind which the weight request goes (ONE: behind the last A-operand read)
     constexpr int NTERM = ONE ? 2 : 3, IREQ = ONE ? 2 * WM - 1 : 2 * WM;
-#define W4_MFMA_SPREAD(o, q, onxt, TAPN, VBN, QREQ, TAPR, CHR)                                                       \
+#define W4_MFMA_SPREAD(o, q, TAPC, onxt, TAPN, VBN, QREQ, TAPR, CHR)                                                       \
     {                                                                                                                \
         _Pragma("unroll") for (int i = 0; i < NTERM * WM; ++i) {                                                     \
             const int wm_ = i % WM, term_ = i / WM;                                                                  \
-            if constexpr (ONE)                                                                                       \
+            if (W4_IS_DEAD(TAPC, wm_)) {                                                                             \
+            } else if constexpr (ONE)                                                                                \
                 acc[wm_] = __builtin_amdgcn_mfma_f32_32x32x16_f16(term_ ? (o).al[wm_] : (o).ah[wm_],                 \
                                                                   term_ ? (q).bl : (q).bh, acc[wm_], 0, 0, 0);       \
             else                                                                                                     \
@@ -311,12 +321,12 @@ __device__ __forceinline__ void w4_pass(const W4Args& a, char* smem, const int* 
                                                                   term_ == 1 ? (q).bl : (q).bh, acc[wm_], 0, 0, 0);  \
             __builtin_amdgcn_sched_barrier(0);                                                                       \
             if (WM >= 2) {                                                                                           \
-                if (i < 2 * WM && (i & 1) == 0) W4_ADDR_A(TAPN, VBN, i / 2)                                          \
-                if (i < 2 * WM && (i & 1) == 1) W4_READ_A(onxt, i / 2)                                               \
+                if (i < 2 * WM && (i & 1) == 0 && !W4_IS_DEAD(TAPN, i / 2)) W4_ADDR_A(TAPN, VBN, i / 2)              \
+                if (i < 2 * WM && (i & 1) == 1 && !W4_IS_DEAD(TAPN, i / 2)) W4_READ_A(onxt, i / 2)                   \
                 if (i == IREQ) W4_REQUEST_B(QREQ, TAPR, CHR)                                   \
             } else {                                                                                                 \
-                if (i == 0) W4_ADDR_A(TAPN, VBN, 0)                                                                  \
-                if (i == 1) W4_READ_A(onxt, 0)                                                                       \
+                if (i == 0 && !W4_IS_DEAD(TAPN, 0)) W4_ADDR_A(TAPN, VBN, 0)                                          \
+                if (i == 1 && !W4_IS_DEAD(TAPN, 0)) W4_READ_A(onxt, 0)                                               \
                 if (i == IREQ) W4_REQUEST_B(QREQ, TAPR, CHR)                                   \
             }                                                                                                        \
             __builtin_amdgcn_sched_barrier(0);                                                                       \
@@ -391,8 +401,8 @@ __device__ __forceinline__ void w4_pass(const W4Args& a, char* smem, const int* 
         }                                                                                                            \
         W4_WAIT_B(BCUR, nb_)                                                                                         \
         __builtin_amdgcn_sched_barrier(0);                                                                           \
-        if constexpr (t_ < NT - 1) W4_MFMA_SPREAD(ACUR, BCUR, ANXT, t_ + 1, cp_, BREQ, tn_, ch + cn_)                \
-        else W4_MFMA_SPREAD(ACUR, BCUR, ANXT, 0, 1 - cp_, BREQ, tn_, ch + cn_)                                       \
+        if constexpr (t_ < NT - 1) W4_MFMA_SPREAD(ACUR, BCUR, t_, ANXT, t_ + 1, cp_, BREQ, tn_, ch + cn_)            \
+        else W4_MFMA_SPREAD(ACUR, BCUR, t_, ANXT, 0, 1 - cp_, BREQ, tn_, ch + cn_)                                   \
     }
 #define W4_TAP6(U0)                                                                                                  \
     {                                                                                                                \
@@ -460,6 +470,7 @@ __device__ __forceinline__ void w4_pass(const W4Args& a, char* smem, const int* 
 #undef W4_LOAD_A
 #undef W4_ADDR_A
 #undef W4_READ_A
+#undef W4_IS_DEAD
 #undef W4_MFMA_SPREAD
 #undef W4_REQUEST_B
 #undef W4_WAIT_B
@@ -597,16 +608,18 @@ inline bool wino4_tiling(int T, int H, int W, int KT, int* TT_, int* TH_, int ti
 // ---- the launch plan (i2v_conv16w4.hip): every host-side decision about a launch of one of the F(4,3) kernels, made once
 // Measurement switches (see w4_switches in i2v_conv16w4.hip: the production library always runs the defaults)
 constexpr int W4_DEFAULT_LOADER = 0;
-struct W4Switches { int pipe = W4_DEFAULT_PIPE, bn = 0, order = W4_DEFAULT_ORDER, nth = 0, skew = 0, trace = 0, loader = W4_DEFAULT_LOADER; };
+struct W4Switches { int pipe = W4_DEFAULT_PIPE, bn = 0, order = W4_DEFAULT_ORDER, nth = 0, skew = 0, trace = 0, loader = W4_DEFAULT_LOADER, tskip = 1; };
 // Which kernel runs the plan: the split / one-term kernels with one workgroup per brick (i2v_conv16w4.hip / i2v_conv16w4h.hip), the
-// split kernel's persistent forms (I2V_W4_PIPE = 1 / 2), the loader forms and the operand-generating kernel (i2v_conv16w4g.hip)
-enum W4Form : int { W4_SPLIT, W4_ONE, W4_PERSIST1, W4_PERSIST2, W4_LOADER1, W4_LOADER2, W4_GEN };
+// split kernel's persistent forms (I2V_W4_PIPE = 1 / 2), the loader forms and the operand-generating kernel (i2v_conv16w4g.hip), the
+// split and one-term kernels that skip temporal edge units (i2v_conv16w4e.hip)
+enum W4Form : int { W4_SPLIT, W4_ONE, W4_PERSIST1, W4_PERSIST2, W4_LOADER1, W4_LOADER2, W4_GEN, W4_EDGE, W4_EDGE_ONE };
 struct W4Plan {
     W4Args a;             // everything but the pointers in / zeros / res / out / stats, which the caller sets
     int NT, BN, NTH, PIPE;   // the kernel instantiation: (kt, kh) taps, channels and threads per workgroup, persistent form
     W4Form form;
     unsigned grid;
     size_t lds_bytes;
+    double issued;        // share of the full tap loops' MFMAs this launch issues (< 1: form W4_EDGE, see w4_dead_units)
 };
 // T = OUTPUT frames.  cus: compute units of the device.  gen: the plan of the operand-generating kernel (fixed 4 x 8 brick, 32
 // channels per workgroup, no V tensor: wino4g_forward has checked its own preconditions).  Returns an error code and sets the error.
@@ -615,6 +628,7 @@ int wino4_plan(W4Plan* p, const Wino4Weights& wts, int B, int T, int H, int W, b
 // what the other two translation units export: the launch of a plan on their kernels
 int wino4h_launch(const W4Plan& p, hipStream_t st);          // form W4_ONE
 int wino4_loader_launch(const W4Plan& p, hipStream_t st);    // forms W4_LOADER1 / W4_LOADER2
+int wino4e_launch(const W4Plan& p, hipStream_t st);          // forms W4_EDGE / W4_EDGE_ONE
 // key of the one switch over instantiations each translation unit has
 constexpr int w4_key(int NT, int BN, int NTH, int PIPE = 0) { return ((NT * 128 + BN) * 1024 + NTH) * 4 + PIPE; }
 constexpr int W4G_THREADS = 768;   // the 12-wave workgroup of i2v_conv16w4g.hip

@@ -4,8 +4,24 @@
 //   W4K_NAME conv_wino4_f16_kernel,   W4K_ONE true   one-term fp16 operands, one MFMA per product (i2v_conv16w4h.hip, mma = 3)
 // The two differ in their tap loops only (w4_pass<..., ONE>).  A kernel template rather than a device function both kernels call:
 // wrapping the body changes the register allocation of the split kernel's loops, and this way its code stays what it was.
+//   W4K_NAME conv_wino4e_f16x3_kernel, W4K_ONE false, W4K_EDGE  the split kernel that skips temporal edge units (i2v_conv16w4e.hip)
+//   W4K_NAME conv_wino4e_f16_kernel,   W4K_ONE true,  W4K_EDGE  its one-term form (same file)
+// W4K_EDGE adds a fifth template parameter, the brick's frame count TT (4 or 2: what the compiled dead masks are derived from), and makes
+// each wave pick the instantiation of each pass's tap loop whose dead mask is that of its own row blocks in this brick (w4_dead_mask);
+// a mask no loop was compiled for runs the full loop.  Without it the kernel body is what it was.
+#ifdef W4K_EDGE
+template <int NT, int BN, int PIPE, int NTH, int ETT>
+#else
 template <int NT, int BN, int PIPE, int NTH>
+#endif
 __global__ __launch_bounds__(NTH, 2) void W4K_NAME(W4Args a) {
+#ifdef W4K_EDGE
+    constexpr bool EDGE = true;
+    static_assert(PIPE == 0 && NTH == 512 && NT >= 6 && (ETT == 4 || ETT == 2), "the edge form: one 512-thread workgroup per brick, 3-D taps");
+#else
+    constexpr bool EDGE = false;
+    constexpr int ETT = 4;
+#endif
     constexpr bool ONE = W4K_ONE;
     constexpr bool FULL = PIPE == 1, LITE = PIPE == 2, PERSIST = PIPE != 0;
     static_assert(NTH == 512 || (NTH == 256 && BN == 32 && PIPE == 0), "the 256-thread geometry exists for 32-channel one-brick workgroups");
@@ -14,6 +30,8 @@ __global__ __launch_bounds__(NTH, 2) void W4K_NAME(W4Args a) {
     constexpr int NW = NTH / 64;
     constexpr int WMA = BN == 64 ? 4 : 2, WMB = BN == 64 ? 2 : 1;
     constexpr int KT = NT / 3;
+    constexpr int ETH_SHIFT = ETT == 4 ? 3 : 4, ETDUP = KT == 2 ? 1 : 0;   // (EDGE) the brick the compiled masks stand for: TH = 32 / TT rows
+    (void)ETH_SHIFT; (void)ETDUP;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid0 = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid0 >> 6);
@@ -94,8 +112,24 @@ __global__ __launch_bounds__(NTH, 2) void W4K_NAME(W4Args a) {
                 for (int r = 0; r < 16; ++r) accA[wm][r] = 0.f;
             }
             const W4Next none{gposA, 0u, 0u, 0};
+#define W4K_PASS_A(M)                                                                                                                          \
+            w4_pass<NT, WMA, Geo::VA0, Geo::VA1, NTH, false, PERSIST, 0, BUF>(a, smem, gposA, gposB, accA, arow, wbase + ((long)xa * nblk + (n0 >> 5) + nha) * 2048, HH, tid, \
+                                             lane, wave, rA0, rA1, none, [] {}, w4_tlv_, vrsrc, std::bool_constant<ONE>{}, std::integral_constant<unsigned, (M)>{});
+            if constexpr (!EDGE) {
             w4_pass<NT, WMA, Geo::VA0, Geo::VA1, NTH, false, PERSIST, 0, BUF>(a, smem, gposA, gposB, accA, arow, wbase + ((long)xa * nblk + (n0 >> 5) + nha) * 2048, HH, tid,
                                              lane, wave, rA0, rA1, none, [] {}, w4_tlv_, vrsrc, std::bool_constant<ONE>{});
+            } else {
+                // the wave's own dead mask in this brick (wave-uniform), and the loops compiled for this geometry: front, back, both ends
+                constexpr unsigned MF = w4_dead_mask<WMA>(3 * ETT, ETH_SHIFT, KT, ETDUP, 0, 0, 0);
+                constexpr unsigned MB = w4_dead_mask<WMA>(3 * ETT, ETH_SHIFT, KT, ETDUP, 2 * ETT, ETDUP, 4 - WMA);
+                constexpr unsigned MFB = w4_dead_mask<WMA>(ETT, ETH_SHIFT, KT, ETDUP, 0, 0, 0);
+                const unsigned mk = w4_dead_mask<WMA>(a.T, a.th_shift, KT, a.tdup, bk.t0, bk.par, mha >> 5);
+                if (mk == MF) W4K_PASS_A(MF)
+                else if (mk == MB) W4K_PASS_A(MB)
+                else if (MFB != MF && MFB != MB && mk == MFB) W4K_PASS_A(MFB)
+                else W4K_PASS_A(0u)
+            }
+#undef W4K_PASS_A
         }
         W4_STAMP(2)
         // ---- pass B: planes 4, 5, wave = (plane, 32-channel half, tile half)   [BN = 32: (plane, tile quarter)]
@@ -117,12 +151,27 @@ __global__ __launch_bounds__(NTH, 2) void W4K_NAME(W4Args a) {
             const W4Next nxt{(more ? gposAn : gposA) + (tid >> 2),
                              (unsigned)__builtin_amdgcn_readfirstlane((int)(lds0 + (unsigned)(flip ^ 1) * 65536u + (unsigned)wave * 1024u)),
                              (unsigned)__builtin_amdgcn_readfirstlane((int)(lds0 + (unsigned)flip * 65536u + 30720u)), more ? 1 : 0};   // dump: rows 480..495 of pass B's first buffer (zero padding, never read)
+            if constexpr (!EDGE) {
             w4_pass<NT, WMB, Geo::VB0, Geo::VB1, NTH, true, PERSIST, FULL ? 2 : 0, BUF>(a, smem, gposB, gposB, accB, arow, wbase + ((long)(4 + xb) * nblk + (n0 >> 5) + nhb) * 2048, HH, tid,
                                             lane, wave, rB0, rB1, nxt, [&] {
                                                 // (PIPE) the next brick's tables, built while this pass's first weight fragments
                                                 // travel; published by the barrier in front of the loop
                                                 if constexpr (PERSIST) { if (more) w4_tables<KT, NTH, BUF>(a, bn_, gposAn, tid); }
                                             }, w4_tlv_, vrsrc, std::bool_constant<ONE>{});
+            } else {
+                // (a wave of this pass holds two or one of the brick's row blocks: its mask depends on its tile half / quarter too; every
+                //  variant runs the same barriers)
+#define W4K_PASS_B(M)                                                                                                                          \
+                w4_pass<NT, WMB, Geo::VB0, Geo::VB1, NTH, true, false, 0, BUF>(a, smem, gposB, gposB, accB, arow, wbase + ((long)(4 + xb) * nblk + (n0 >> 5) + nhb) * 2048, HH, tid, \
+                                            lane, wave, rB0, rB1, nxt, [] {}, w4_tlv_, vrsrc, std::bool_constant<ONE>{}, std::integral_constant<unsigned, (M)>{});
+                constexpr unsigned MF = w4_dead_mask<WMB>(3 * ETT, ETH_SHIFT, KT, ETDUP, 0, 0, 0);
+                constexpr unsigned MB = w4_dead_mask<WMB>(3 * ETT, ETH_SHIFT, KT, ETDUP, 2 * ETT, ETDUP, 4 - WMB);
+                const unsigned mk = w4_dead_mask<WMB>(a.T, a.th_shift, KT, a.tdup, bk.t0, bk.par, mhb >> 5);
+                if (mk == MF) W4K_PASS_B(MF)
+                else if (mk == MB) W4K_PASS_B(MB)
+                else W4K_PASS_B(0u)
+#undef W4K_PASS_B
+            }
         }
         W4_STAMP(4)
 
@@ -294,3 +343,4 @@ __global__ __launch_bounds__(NTH, 2) void W4K_NAME(W4Args a) {
 }
 #undef W4K_NAME
 #undef W4K_ONE
+#undef W4K_EDGE

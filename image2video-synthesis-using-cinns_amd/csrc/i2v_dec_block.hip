@@ -147,8 +147,10 @@ static int conv3_run(BlockCtx* d, const Conv3& c, Conv3Kernel kn, const Level& l
     // split-fp16 kernels, one on the one-term kernel; F(2,3): 4 Winograd products per 2 outputs x 3 kw taps (x 2/3), F(4,3): 6 per
     // 4 outputs (x 1/2); 18 instead of 27 taps in temporal-duplication mode (the generating kernel never is)
     const double fl = 2.0 * B * l.T * l.H * l.W * (double)c.cin * c.cout * 27.0, td = c.tdup ? 18.0 / 27.0 : 1.0;
+    // (the split and one-term F(4,3) kernels: minus the units its edge form skips -- temporal taps that read only zero padding)
     const double exec = kn == K_F32 ? fl : kn == K_F32_WINO ? 0.5 * fl : kn == K_F16 ? 3.0 * fl * td : kn == K_F23 ? 3.0 * fl * (2.0 / 3.0) * td :
-                        kn == K_F43 ? 3.0 * fl * 0.5 * td : kn == K_F43_ONE ? fl * 0.5 * td : 3.0 * fl * 0.5;
+                        kn == K_F43 ? 3.0 * fl * 0.5 * td * (d->profile ? wino4_issued_share(c.w43, B, l.T, l.H, l.W) : 1.0) :
+                        kn == K_F43_ONE ? fl * 0.5 * td * (d->profile ? wino4_issued_share(c.w43, B, l.T, l.H, l.W) : 1.0) : 3.0 * fl * 0.5;
     d->prof_cur_layer = layer;
     d->prof_cur_kernel = kn;
     ProfScope ps(d, st, fl, exec);

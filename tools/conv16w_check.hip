@@ -3,7 +3,10 @@
 //   conv16w_check B T H W Cin Cout tdup res      (T = output frames; tdup: conv_0 behind a x2 temporal up-sampling)
 // and, where the shape allows it, of the F(4,3) kernel (csrc/i2v_conv16w4.hip) next to them.
 // Build: hipcc -O3 --offload-arch=gfx950 -I<csrc> tools/conv16w_check.hip <csrc>/i2v_conv16w.hip <csrc>/i2v_conv16w4.hip <csrc>/i2v_conv16w4h.hip
-//        <csrc>/i2v_conv16.hip <csrc>/i2v_common.hip -o tools/conv16w_check
+//        <csrc>/i2v_conv16w4e.hip <csrc>/i2v_conv16.hip <csrc>/i2v_common.hip -o tools/conv16w_check
+// The 512-thread 3-D F(4,3) launches run the edge kernel (conv_wino4e_f16x3_kernel, i2v_conv16w4e.hip); with -DI2V_MEASURE,
+// I2V_W4_TSKIP=0 runs the full tap loops instead.  The -DW4_TIMELINE / -DW4_TAPTIME builds stamp both (the instrumented
+// i2v_conv16w4.hip carries the edge kernel itself; i2v_conv16w4e.hip then compiles to nothing).
 // Measurement builds of the F(4,3) kernel (same command plus):
 //   -DW4_TIMELINE   wall-clock stamps per workgroup phase (tables + first brick, pass A, hand-over, pass B, epilogue halves and
 //                   the sub-phases of the first half), printed as means over the workgroups

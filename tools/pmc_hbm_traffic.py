@@ -36,7 +36,7 @@ def one_pass(outdir, counter, extra, parse_only):
             if "conv_mfma_f16x3_kernel" in k:
                 conv16.append((int(r["Dispatch_Id"]), float(r["Counter_Value"])))
                 continue
-            if "conv_wino4_f16x3_kernel" in k:
+            if "conv_wino4_f16x3_kernel" in k or "conv_wino4e_f16x3_kernel" in k:   # (the edge form: the same F(4,3) 3x3x3 entry)
                 k = "i2v::conv_wino4_f16x3_kernel [3x3x3 Conv3d, Winograd F(4,3)]"
             elif "conv_wino_f16x3_kernel<3," in k:
                 k = "i2v::conv_wino_f16x3_kernel<3, .> [SPADE 3x3 Conv2d, Winograd F(2,3)]"
