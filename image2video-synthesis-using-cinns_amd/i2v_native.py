@@ -152,6 +152,16 @@ SYMBOLS = {
     "i2v_vgg_reduce_workspace_bytes": (c_size_t, [c_int32]),
     "i2v_lpips_layer": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_size_t, c_void_p]),
     "i2v_vgg_pairdiff_update": (c_int32, [c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "i2v_vgg_saved_bytes": (c_size_t, [c_void_p, c_int32, c_int32, c_int32]),
+    "i2v_vgg_backward_workspace_bytes": (c_size_t, [c_void_p, c_int32, c_int32, c_int32]),
+    "i2v_vgg_features_saved": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_size_t, c_void_p, c_size_t, c_void_p]),
+    "i2v_lpips_layer_backward": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "i2v_vgg_backward": (c_int32, [c_void_p, POINTER(c_void_p), POINTER(c_void_p), c_void_p, c_size_t, c_int32, c_int32, c_int32, c_void_p, c_int32,
+                                   c_void_p, c_size_t, c_void_p]),
+    "i2v_vgg_dgrad_unit": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32,
+                                     c_void_p]),
+    "i2v_vgg_maxpool2_backward": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "i2v_inception_create": (c_int32, [POINTER(c_void_p)]),
     "i2v_inception_destroy": (None, [c_void_p]),
     "i2v_inception_load": (c_int32, [c_void_p, POINTER(_Tensor), c_int32]),
@@ -1348,6 +1358,36 @@ def _require_f64(t, shape, device, what):
         raise I2VError(f"{what}: expected a contiguous float64 device tensor of shape {shape}")
 
 
+class VGGSaved:
+    """What ``NativeVGG.backward`` needs of one forward pass: the five taps and the buffer of the eight other post-ReLU activations."""
+
+    # (output channels, tap index or -1, pool behind it) of the thirteen convolutions: the layout of the buffer (csrc/i2v_vgg.hip)
+    LAYERS = ((64, -1, 0), (64, 0, 1), (128, -1, 0), (128, 1, 1), (256, -1, 0), (256, -1, 0), (256, 2, 1), (512, -1, 0), (512, -1, 0), (512, 3, 1),
+              (512, -1, 0), (512, -1, 0), (512, 4, 0))
+
+    def __init__(self, shape, taps, buf):
+        self.shape, self.taps, self.buf = tuple(shape), list(taps), buf
+
+    def activations(self):
+        """The thirteen post-ReLU activations, channels-last [N, H', W', C], as views of the taps and of the buffer."""
+        n, h, w, _ = self.shape
+        acts, off = [], 0
+        for cout, tap, pool in self.LAYERS:
+            if tap >= 0:
+                acts.append(self.taps[tap])
+            else:
+                nbytes = n * h * w * cout * 4
+                acts.append(self.buf[off:off + nbytes].view(torch.float32).view(n, h, w, cout))
+                off += (nbytes + 255) // 256 * 256
+            if pool:
+                h, w = h // 2, w // 2
+        return acts
+
+
+def _ptrs(tensors):
+    return (c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
 class NativeVGG(_Handle):
     """Handle for ``i2v_vgg_*``: the VGG-16 ``features`` trunk of stage2_cINN/AE/modules/vgg16.py up to relu5_3, with the ``lin`` weights of
     LPIPS.py when the state_dict has them."""
@@ -1358,6 +1398,7 @@ class NativeVGG(_Handle):
             _check(lib().i2v_vgg_create(ctypes.byref(h)), "i2v_vgg_create")
         self._h = h
         self._ws = _Workspace()
+        self._bws = _Workspace()
         self.has_lin = False
 
     def __del__(self):
@@ -1380,9 +1421,11 @@ class NativeVGG(_Handle):
         return [(n, h >> k, w >> k, c) for k, c in enumerate(VGG_TAP_CHANNELS)]
 
     @_on_device
-    def features(self, x, out=None):
+    def features(self, x, out=None, save=False, saved_buf=None):
         """``i2v_vgg_features``: x [N, H, W, 4] channels-last (``vgg_input_stage``) -> the five taps, channels-last [N, H', W', C].  ``out``:
-        five caller-owned tensors of those shapes (the call only enqueues: it can be captured into a graph)."""
+        five caller-owned tensors of those shapes (the call only enqueues: it can be captured into a graph).  ``save=True``
+        (``i2v_vgg_features_saved``): returns (taps, ``VGGSaved``) -- the same tap bits, and the state ``backward`` needs (``saved_buf``: a
+        caller-owned uint8 buffer of ``saved_bytes`` for it)."""
         _require_cl4(x, "vgg features")
         n, h, w, c = x.shape
         nbytes = lib().i2v_vgg_workspace_bytes(self._h, n, h, w) if c == 4 else 0
@@ -1396,9 +1439,74 @@ class NativeVGG(_Handle):
             _require_gpu(t)
             if tuple(t.shape) != s:
                 raise I2VError(f"vgg features: expected a tap of shape {s}, got {tuple(t.shape)}")
+        if save:
+            nsaved = lib().i2v_vgg_saved_bytes(self._h, n, h, w)
+            if saved_buf is None:
+                saved_buf = torch.empty(nsaved, dtype=torch.uint8, device=x.device)
+            if not saved_buf.is_cuda or saved_buf.dtype != torch.uint8 or not saved_buf.is_contiguous() or saved_buf.numel() < nsaved:
+                raise I2VError(f"vgg features: the saved-state buffer must be a contiguous uint8 device tensor of at least {nsaved} bytes")
+            _check(lib().i2v_vgg_features_saved(self._h, x.data_ptr(), n, h, w, *[t.data_ptr() for t in out], saved_buf.data_ptr(), saved_buf.numel(),
+                                                ws.data_ptr(), ws.numel(), _stream()), "i2v_vgg_features_saved")
+            return list(out), VGGSaved(x.shape, out, saved_buf)
         _check(lib().i2v_vgg_features(self._h, x.data_ptr(), n, h, w, *[t.data_ptr() for t in out], ws.data_ptr(), ws.numel(), _stream()),
                "i2v_vgg_features")
         return list(out)
+
+    def saved_bytes(self, n, h, w):
+        return lib().i2v_vgg_saved_bytes(self._h, n, h, w)
+
+    @_on_device
+    def backward(self, tap_grads, saved, frames=False, out=None):
+        """``i2v_vgg_backward``: five tap gradients (channels-last, the taps' shapes) and the ``VGGSaved`` of ``features(x, save=True)`` -> the
+        gradient at x [N, H, W, 4], or with ``frames`` at the frames [N, 3, H, W] behind the LPIPS input stage.  Only enqueues (after the
+        handle's first backward call, which packs the backward weights)."""
+        if not isinstance(saved, VGGSaved):
+            raise I2VError("vgg backward: no saved state -- run features(x, save=True); features(x) keeps only the taps")
+        n, h, w, _ = saved.shape
+        tap_grads = list(tap_grads)
+        if len(tap_grads) != 5:
+            raise I2VError(f"vgg backward: expected five tap gradients, got {len(tap_grads)}")
+        for g, t in zip(tap_grads, saved.taps):
+            _require_gpu(g)
+            if g.shape != t.shape:
+                raise I2VError(f"vgg backward: a tap gradient of shape {tuple(g.shape)} for a tap of shape {tuple(t.shape)}")
+        shape = (n, 3, h, w) if frames else (n, h, w, 4)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=saved.buf.device)
+        _require_gpu(out)
+        if tuple(out.shape) != shape:
+            raise I2VError(f"vgg backward: expected an output of shape {shape}, got {tuple(out.shape)}")
+        ws = self._bws.get(lib().i2v_vgg_backward_workspace_bytes(self._h, n, h, w), out.device)
+        _check(lib().i2v_vgg_backward(self._h, _ptrs(saved.taps), _ptrs(tap_grads), saved.buf.data_ptr(), saved.buf.numel(), n, h, w, out.data_ptr(),
+                                      int(bool(frames)), ws.data_ptr(), ws.numel(), _stream()), "i2v_vgg_backward")
+        return out
+
+    @_on_device
+    def lpips_backward(self, taps0, taps1, upstream, need0=True, need1=True, out0=None, out1=None):
+        """``i2v_lpips_layer_backward`` over the five layers: ``upstream`` [N] float64 (the weight of every image's LPIPS value) -> (tap
+        gradients of side 0, of side 1), each a list of five channels-last tensors or None when not needed."""
+        if not self.has_lin:
+            raise I2VError("lpips: the handle was loaded without lin{0..4}.model.1.weight")
+        if not (need0 or need1):
+            raise I2VError("lpips backward: no gradient requested")
+        n = taps0[0].shape[0]
+        _require_f64(upstream, (n,), taps0[0].device, "lpips backward")
+        g0 = ([torch.empty_like(t) for t in taps0] if out0 is None else list(out0)) if need0 else None
+        g1 = ([torch.empty_like(t) for t in taps1] if out1 is None else list(out1)) if need1 else None
+        for k, (a, b) in enumerate(zip(taps0, taps1)):
+            _require_cl4(a, "lpips backward")
+            _require_cl4(b, "lpips backward")
+            if a.shape != b.shape:
+                raise I2VError(f"lpips backward: taps of different shapes {tuple(a.shape)} / {tuple(b.shape)}")
+            for g in (g0, g1):
+                if g is not None:
+                    _require_gpu(g[k])
+                    if g[k].shape != a.shape:
+                        raise I2VError(f"lpips backward: a gradient buffer of shape {tuple(g[k].shape)} for a tap of shape {tuple(a.shape)}")
+            _check(lib().i2v_lpips_layer_backward(a.data_ptr(), b.data_ptr(), lib().i2v_vgg_lin(self._h, k), upstream.data_ptr(), n,
+                                                  a.shape[1] * a.shape[2], a.shape[3], g0[k].data_ptr() if need0 else None,
+                                                  g1[k].data_ptr() if need1 else None, _stream()), "i2v_lpips_layer_backward")
+        return g0, g1
 
     @_on_device
     def lpips(self, taps0, taps1):
@@ -1460,6 +1568,67 @@ def vgg_maxpool2(x):
     with torch.cuda.device(x.device):
         _check(lib().i2v_vgg_maxpool2(x.data_ptr(), n, h, w, c, out.data_ptr(), _stream()), "i2v_vgg_maxpool2")
     return out
+
+
+def vgg_dgrad_unit(g, weight, add=None, ymask=None, frames=False):
+    """``i2v_vgg_dgrad_unit``: the input gradient of one 3x3 convolution of the trunk's kind.  g [N, H, W, cout] channels-last on the device,
+    host ``weight`` [cout, cin, 3, 3] -> (dgrad + add) * (ymask > 0) [N, H, W, cin].  cin = 3 is the first-layer form: [N, H, W, 4], or with
+    ``frames`` [N, 3, H, W] divided by ScalingLayer's scale."""
+    _require_cl4(g, "vgg_dgrad_unit")
+    w = np.ascontiguousarray(weight.detach().cpu().numpy() if isinstance(weight, torch.Tensor) else weight, dtype=np.float32)
+    if w.ndim != 4 or w.shape[2:] != (3, 3):
+        raise I2VError(f"vgg_dgrad_unit: expected weight [cout,cin,3,3], got {w.shape}")
+    cout, cin = w.shape[:2]
+    n, h, wd, cs = g.shape
+    if cs != cout:
+        raise I2VError(f"vgg_dgrad_unit: a gradient of {cs} channels for a weight of {cout} output channels")
+    shape = (n, 3, h, wd) if frames else (n, h, wd, 4 if cin == 3 else cin)
+    for t in (add, ymask):
+        if t is not None:
+            _require_cl4(t, "vgg_dgrad_unit")
+            if tuple(t.shape) != shape:
+                raise I2VError(f"vgg_dgrad_unit: expected an addend / mask of shape {shape}, got {tuple(t.shape)}")
+    out = torch.empty(shape, dtype=torch.float32, device=g.device)
+    with torch.cuda.device(g.device):
+        _check(lib().i2v_vgg_dgrad_unit(g.data_ptr(), w.ctypes.data_as(c_void_p), None if add is None else add.data_ptr(),
+                                        None if ymask is None else ymask.data_ptr(), n, h, wd, cin, cout, out.data_ptr(), int(bool(frames)),
+                                        _stream()), "i2v_vgg_dgrad_unit")
+    return out
+
+
+def vgg_maxpool2_backward(grad, y, add=None, relu_mask=False):
+    """``i2v_vgg_maxpool2_backward``: grad [N, H/2, W/2, C], y [N, H, W, C] (the pool's input) -> [N, H, W, C]: the gradient at the first
+    maximum of every window, zero elsewhere; then + ``add`` and, with ``relu_mask``, * (y > 0)."""
+    _require_cl4(grad, "vgg_maxpool2_backward")
+    _require_cl4(y, "vgg_maxpool2_backward")
+    n, h, w, c = y.shape
+    if tuple(grad.shape) != (n, h // 2, w // 2, c) or (add is not None and add.shape != y.shape):
+        raise I2VError(f"vgg_maxpool2_backward: shapes {tuple(grad.shape)} / {tuple(y.shape)}")
+    if add is not None:
+        _require_cl4(add, "vgg_maxpool2_backward")
+    out = torch.empty_like(y)
+    with torch.cuda.device(y.device):
+        _check(lib().i2v_vgg_maxpool2_backward(grad.data_ptr(), y.data_ptr(), None if add is None else add.data_ptr(), int(bool(relu_mask)), n, h, w, c,
+                                               out.data_ptr(), _stream()), "i2v_vgg_maxpool2_backward")
+    return out
+
+
+def lpips_layer_backward(f0, f1, lin, upstream, need0=True, need1=True):
+    """``i2v_lpips_layer_backward`` for one layer: f0, f1 [N, H, W, C] channels-last taps, lin [C], upstream [N] float64 -> (g0, g1), None
+    where not needed."""
+    _require_cl4(f0, "lpips_layer_backward")
+    _require_cl4(f1, "lpips_layer_backward")
+    _require_gpu(lin)
+    n, h, w, c = f0.shape
+    if f1.shape != f0.shape or tuple(lin.shape) != (c,):
+        raise I2VError(f"lpips_layer_backward: shapes {tuple(f0.shape)} / {tuple(f1.shape)} / {tuple(lin.shape)}")
+    _require_f64(upstream, (n,), f0.device, "lpips_layer_backward")
+    g0, g1 = (torch.empty_like(f0) if need0 else None), (torch.empty_like(f1) if need1 else None)
+    with torch.cuda.device(f0.device):
+        _check(lib().i2v_lpips_layer_backward(f0.data_ptr(), f1.data_ptr(), lin.data_ptr(), upstream.data_ptr(), n, h * w, c,
+                                              None if g0 is None else g0.data_ptr(), None if g1 is None else g1.data_ptr(), _stream()),
+               "i2v_lpips_layer_backward")
+    return g0, g1
 
 
 def lpips_layer(f0, f1, lin, out):

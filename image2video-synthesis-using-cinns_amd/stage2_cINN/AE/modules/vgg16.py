@@ -6,13 +6,15 @@ convolutions in exact fp32 on the matrix cores, four 2x2 max pools) and returns 
 dependency: the graph is written out here and the weights come from torchvision's ``vgg16`` state_dict FILE (keys ``features.N.*``;
 the classifier keys are ignored).  Nothing is ever downloaded: a missing file raises ``FileNotFoundError`` naming it.
 
-The returned tensors are NCHW-shaped views of channels-last memory (the layout the kernels write).  Inference only:
-``requires_grad=True`` is refused."""
+The returned tensors are NCHW-shaped views of channels-last memory (the layout the kernels write).  The weights are frozen:
+``requires_grad=True`` (weight gradients) is refused.  The INPUT gradient exists: with grad mode on and ``X.requires_grad`` the five taps
+are differentiable with respect to ``X`` (``i2v_vgg_backward``: the input-gradient convolutions on the forward kernel, once differentiable)."""
 import os
 from collections import namedtuple
 
 import torch
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 
 import i2v_native
 
@@ -108,14 +110,39 @@ class vgg16(nn.Module):
         """Channels-last input [N, H, W, 4] (``i2v_native.vgg_input_stage``) -> the five channels-last taps [N, H', W', C]."""
         return self.native().features(x_cl)
 
-    @torch.no_grad()
     def forward(self, X):
-        """X [N, 3, H, W], already normalised (as the reference's forward takes it) -> VggOutputs of five NCHW-shaped tensors."""
+        """X [N, 3, H, W], already normalised (as the reference's forward takes it) -> VggOutputs of five NCHW-shaped tensors; they carry a
+        ``grad_fn`` when grad mode is on and ``X.requires_grad``."""
         if X.dim() != 4 or X.shape[1] != 3:
             raise ValueError(f"vgg16.forward: expected [N,3,H,W], got {tuple(X.shape)}")
-        i2v_native._require_gpu(X.float().contiguous())
-        x = torch.cat([X.float().permute(0, 2, 3, 1), X.new_zeros(X.shape[0], X.shape[2], X.shape[3], 1, dtype=torch.float32)], -1).contiguous()
-        return VggOutputs(*[t.permute(0, 3, 1, 2) for t in self.taps(x)])
+        i2v_native._require_gpu(X.detach().float().contiguous())
+        if torch.is_grad_enabled() and X.requires_grad:
+            return VggOutputs(*_TapsFunction.apply(X, self.native()))
+        with torch.no_grad():
+            return VggOutputs(*[t.permute(0, 3, 1, 2) for t in self.taps(_pad4(X))])
+
+
+def _pad4(X):
+    """[N, 3, H, W] -> the channels-last input [N, H, W, 4] of the trunk (channel 3 zero)."""
+    return torch.cat([X.float().permute(0, 2, 3, 1), X.new_zeros(X.shape[0], X.shape[2], X.shape[3], 1, dtype=torch.float32)], -1).contiguous()
+
+
+class _TapsFunction(torch.autograd.Function):
+    """The five taps as a function of X: forward keeps the activations (``features(save=True)``), backward is ``NativeVGG.backward``."""
+
+    @staticmethod
+    def forward(ctx, X, native):
+        taps, ctx.saved = native.features(_pad4(X.detach()), save=True)
+        ctx.native, ctx.dtype = native, X.dtype
+        return tuple(t.permute(0, 3, 1, 2) for t in taps)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        # tap gradients of any stride (NCHW-contiguous ones of a torch graph behind the taps, expanded scalars, ...) -> channels-last
+        cl = [g.float().permute(0, 2, 3, 1).contiguous() for g in grads]
+        gx = ctx.native.backward(cl, ctx.saved)
+        return gx[..., :3].permute(0, 3, 1, 2).to(ctx.dtype), None
 
 
 def normalize_tensor(x, eps=1e-10):

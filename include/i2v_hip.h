@@ -549,6 +549,43 @@ int i2v_lpips_layer(const float* f0, const float* f1, const float* lin, int32_t 
  * element is read once; two fixed-order stages, no atomics. */
 int i2v_vgg_pairdiff_update(const float* maps, int32_t r, int64_t d, double* acc, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- LPIPS as a loss: the gradient at the input of the frozen trunk (stage1_VAE/modules/loss.py:139, 147 `self.lpips(seq_orig, seq_gen).mean()`
+ * in Backward.forward, back-propagated through the second argument; stage2_cINN/AE/modules/loss.py:38 uses the same module).  VGG-16 and the
+ * lin layers carry no gradient (vgg16.py:26-28, LPIPS.py:23-24): only input gradients exist.  Every call below only enqueues on
+ * `stream` (the *_unit entry excepted), uses no atomics, and gives a batch row the bits of its single-image run. */
+/* Bytes of the saved state of i2v_vgg_features_saved: the eight post-ReLU activations that are not taps (the taps themselves are
+ * the other five).  0 when h or w is below 16. */
+size_t i2v_vgg_saved_bytes(const i2v_vgg* v, int32_t batch, int32_t h, int32_t w);
+/* Workspace of i2v_vgg_backward: two gradient maps of relu1_2's size.  0 when h or w is below 16. */
+size_t i2v_vgg_backward_workspace_bytes(const i2v_vgg* v, int32_t batch, int32_t h, int32_t w);
+/* vgg16.forward (vgg16.py:30-42) as i2v_vgg_features, the same kernels and the same tap bits; the intermediate activations go to
+ * `saved` instead of a ping-pong workspace (the ReLU masks of the backward pass; the pool arg-max is read from the taps). */
+int i2v_vgg_features_saved(i2v_vgg* v, const float* x, int32_t batch, int32_t h, int32_t w, float* relu1_2, float* relu2_2, float* relu3_3,
+                           float* relu4_3, float* relu5_3, void* saved, size_t saved_bytes, void* workspace, size_t workspace_bytes, void* stream);
+/* Backward of one layer of LPIPS.forward (LPIPS.py:44-52 with normalize_tensor, vgg16.py:46-48): upstream[i] (float64, device) is
+ * the weight of image i's output.  grad0 / grad1 [n][p][c] fp32 take the gradient at f0 / f1 (null: not wanted; not both).  The two
+ * per-position dot products are float64.  At an all-zero feature vector the result is dn / 1e-10 (finite; torch gives NaN). */
+int i2v_lpips_layer_backward(const float* f0, const float* f1, const float* lin, const double* upstream, int32_t n, int32_t p, int32_t c,
+                             float* grad0, float* grad1, void* stream);
+/* Backward of vgg16.forward (vgg16.py:30-42) at the input: taps[5] the tap buffers of i2v_vgg_features_saved, tap_grads[5] their
+ * gradients (same shapes, channels-last; both arrays of device pointers live on the HOST), `saved` its saved state (NULL: refused).
+ * frames_out = 0: out [batch][h][w][4], the gradient at x (channel 3 zero).  frames_out = 1: out [batch][3][h][w], the gradient at
+ * the frames behind ScalingLayer (LPIPS.py:56-63: divided by scale).  The first backward call of a handle packs the backward
+ * weights (59 MB) and must not be captured; later calls can be. */
+int i2v_vgg_backward(i2v_vgg* v, const float* const* taps, const float* const* tap_grads, const void* saved, size_t saved_bytes, int32_t batch,
+                     int32_t h, int32_t w, float* out, int32_t frames_out, void* workspace, size_t workspace_bytes, void* stream);
+/* Input gradient of one convolution of the trunk's kind (nn.Conv2d(cin, cout, 3, padding=1): the torchvision layers of vgg16.py:9-25) from raw weights
+ * [cout][cin][3][3] (HOST pointer): g [n][h][w][cout] -> out [n][h][w][cin] = (dgrad + add) * (ymask > 0), add and ymask
+ * [n][h][w][cin] optional.  cin a multiple of 64, cout a multiple of 16.  cin = 3 (cout = 64) is the first-layer form: out
+ * [n][h][w][4], or with frames_out [n][3][h][w] divided by ScalingLayer's scale; no add, no mask.  Packs per call and synchronises. */
+int i2v_vgg_dgrad_unit(const float* g, const float* weight, const float* add, const float* ymask, int32_t n, int32_t h, int32_t w, int32_t cin,
+                       int32_t cout, float* out, int32_t frames_out, void* stream);
+/* Backward of nn.MaxPool2d(2, 2) (features.4 / 9 / 16 / 23 of vgg16.py:9-25): grad [n][h/2][w/2][c], y [n][h][w][c] the pool's input -> out [n][h][w][c].  The
+ * gradient goes to the first maximum of a window in row-major order (torch's rule); everything else, the dropped row / column of an
+ * odd map included, is zero.  Then + add [n][h][w][c] (optional) and, with relu_mask, * (y > 0). */
+int i2v_vgg_maxpool2_backward(const float* grad, const float* y, const float* add, int32_t relu_mask, int32_t n, int32_t h, int32_t w, int32_t c,
+                              float* out, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * FID Inception-v3 trunk (csrc/i2v_inception.hip) -- metrics/FID/inception.py (InceptionV3.forward :129-161, fid_inception_v3
  * :164-186, FIDInceptionA / C / E_1 / E_2 :189-306 and the torchvision blocks InceptionB / D and BasicConv2d they sit on) and the

@@ -1,6 +1,6 @@
 """Timing of the native VGG-16 trunk and of LPIPS on one MI355X -> profiles/vgg_ab.md (+ .json).
 
-  python tools/vgg_bench.py [--repeats 5] [--batch 5] [--out DIR] [--step-timeout 240]
+  python tools/vgg_bench.py [--backward] [--repeats 5] [--batch 5] [--out DIR] [--step-timeout 240]
 
 Single-process measurements, each GPU step in a child process of its own under its own ``timeout`` (a step that does not end clean stops
 the script; nothing more is started on the GPU):
@@ -8,6 +8,11 @@ the script; nothing more is started on the GPU):
     timed as a whole; the layers one by one through ``i2v_vgg_conv_unit``, end to end: an upper bound), the fraction of the 157 TFLOP/s
     fp32-MFMA peak, and ms per 224 x 224 image for the whole trunk with its input stage;
   * ``lpips``: ms of ``LPIPS.forward`` on 10 image pairs at 64 x 64 and at 128 x 128.
+  * ``--backward`` (-> profiles/lpips_grad_ab.md): ms of LPIPS forward + backward (``LPIPS(x0, x1).mean().backward()``, the gradient at the
+    second argument as in the stage-1 loss) for 160 frames at 64 x 64 and for 192 frames at 128 x 128 -- the frames per step of the
+    stage-1 configs -- next to the torch-op form of the same network (``F.conv2d`` / ``relu`` / ``max_pool2d`` and the LPIPS formula in
+    fp32 with autograd) on the same GPU in the same process, the two alternating; the two gradients are compared.  A record: this path
+    has no number at the parent commit.
 Events on the stream, 2 warm-up runs, median and spread.  No number of this path appears in any document of the project unless this
 script wrote it."""
 import argparse
@@ -96,16 +101,141 @@ def step_lpips(side, repeats):
     print(json.dumps({"device_name": torch.cuda.get_device_name(0), "side": side, "pairs": 10, "lpips": _time(lambda: m(a, b), repeats)}))
 
 
+def _torch_lpips(sd, lin, x0, x1):
+    """The torch-op form: vgg_common's oracle graph in fp32 on the device (the reference module's arithmetic)."""
+    import torch
+    import torch.nn.functional as F
+    import vgg_common as vc
+    shift, scale = (torch.tensor(v, device=x0.device).view(1, 3, 1, 1) for v in (vc.LPIPS_SHIFT, vc.LPIPS_SCALE))
+    val = 0
+    feats = []
+    for x in (x0, x1):
+        h, taps = (x - shift) / scale, []
+        for idx, _, _ in vc.CONVS:
+            h = torch.relu(F.conv2d(h, sd[f"features.{idx}.weight"], sd[f"features.{idx}.bias"], padding=1))
+            if idx in vc.TAP_AFTER:
+                taps.append(h)
+            if idx in vc.POOL_AFTER:
+                h = F.max_pool2d(h, 2, 2)
+        feats.append(taps)
+    for k, (a, b) in enumerate(zip(*feats)):
+        na = a / (torch.sqrt((a ** 2).sum(1, keepdim=True)) + 1e-10)
+        nb = b / (torch.sqrt((b ** 2).sum(1, keepdim=True)) + 1e-10)
+        val = val + (((na - nb) ** 2) * lin[k].view(1, -1, 1, 1)).sum(1, keepdim=True).mean((2, 3), keepdim=True)
+    return val
+
+
+def step_backward(frames, side, repeats):
+    import torch
+    import vgg_common as vc
+    m = _models(True)
+    sd = {k: torch.from_numpy(v).cuda() for k, v in vc.vgg_state_dict(1).items()}
+    lin = [torch.from_numpy(v).flatten().cuda() for v in vc.lin_state_dict(2).values()]
+    a = torch.from_numpy(vc.clips(5, frames, 1, side, side))[:, 0].contiguous().cuda()
+    b = (0.7 * a + 0.3 * torch.from_numpy(vc.clips(6, frames, 1, side, side))[:, 0].cuda()).contiguous()
+    grads = {}
+
+    def native():
+        x1 = b.clone().requires_grad_(True)
+        m(a, x1).mean().backward()
+        grads["native"] = x1.grad
+
+    def torch_ops():
+        x1 = b.clone().requires_grad_(True)
+        _torch_lpips(sd, lin, a, x1).mean().backward()
+        grads["torch"] = x1.grad
+
+    def forward_only():
+        with torch.no_grad():
+            m(a, b)
+    for fn in (native, torch_ops, forward_only):      # every shape warm before any window
+        for _ in range(2):
+            fn()
+    torch.cuda.synchronize()
+    rel = float((grads["native"].double() - grads["torch"].double()).norm() / grads["torch"].double().norm())
+    ms = {"native": [], "torch": [], "forward": []}
+    for _ in range(repeats):                           # alternating: a drift of the machine hits all three alike
+        for name, fn in (("native", native), ("torch", torch_ops), ("forward", forward_only)):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            ms[name].append(e0.elapsed_time(e1))
+    stat = {k: {"median_ms": statistics.median(v), "min_ms": min(v), "max_ms": max(v), "repeats": len(v)} for k, v in ms.items()}
+    # which of the two is right: float64 on the CPU for the first two pairs, its ReLU masks and pool arg-max those of the native run
+    # (tests/lpips_grad_common.py: the gradient is discontinuous where a pre-activation crosses zero)
+    import lpips_grad_common as lg
+    x1 = b[:2].clone().requires_grad_(True)
+    out = m(a[:2], x1)
+    acts = [lg.to_nchw(t) for t in out.grad_fn.saved[1].activations()]
+    out.mean().backward()
+    t1 = b[:2].clone().requires_grad_(True)
+    _torch_lpips(sd, lin, a[:2], t1).mean().backward()
+    y1 = b[:2].cpu().double().requires_grad_(True)
+    val, _, side1 = lg.lpips_masked(vc.vgg_state_dict(1), vc.lin_state_dict(2), a[:2].cpu().double(), y1, None, acts)
+    val.mean().backward()
+    vs64 = {"native": max(vc.rel_l2_rows(x1.grad.cpu(), y1.grad)), "torch": max(vc.rel_l2_rows(t1.grad.cpu(), y1.grad)),
+            "mask_differences_native_vs_float64": lg.fragile_units(side1[1], acts)[0]}
+    print(json.dumps({"device_name": torch.cuda.get_device_name(0), "frames": frames, "side": side, "grad_rel_l2_native_vs_torch": rel,
+                      "grad_rel_l2_vs_float64_first_two_pairs": vs64,
+                      "peak_alloc_mb": torch.cuda.max_memory_allocated() / 2 ** 20, **stat}))
+
+
+BACKWARD_SHAPES = ((160, 64), (192, 128))      # (frames, side): the frames one stage-1 step puts through LPIPS at 64 x 64 and at 128 x 128
+
+
+def main_backward(args):
+    res = []
+    for frames, side in BACKWARD_SHAPES:
+        r = subprocess.run(["timeout", "-k", "10", str(args.step_timeout), sys.executable, os.path.abspath(__file__), "--step", f"bwd:{frames}:{side}",
+                            "--repeats", str(args.repeats)], capture_output=True, text=True)
+        if r.returncode != 0:
+            sys.stderr.write(r.stdout + r.stderr)
+            raise SystemExit(f"vgg_bench: the backward step at {frames} x {side} ended with status {r.returncode}; nothing more is run")
+        res.append(json.loads(r.stdout.strip().splitlines()[-1]))
+        print(res[-1], flush=True)
+    out = os.path.abspath(args.out)
+    os.makedirs(out, exist_ok=True)
+    fmt = lambda u: f"{u['median_ms']:.2f} ({u['min_ms']:.2f} .. {u['max_ms']:.2f})"  # noqa: E731
+    lines = ["# LPIPS as a loss: forward + backward, native against the torch-op form", "",
+             f"Device: {res[0]['device_name']}.  `tools/vgg_bench.py --backward`, one process per shape, events on the stream around one whole call "
+             f"(`LPIPS(x0, x1).mean().backward()`, the gradient at `x1`; host work of the call included), {args.repeats} repeats after 2 warm-up runs "
+             "of every variant, the variants alternating inside each repeat.  Median (min .. max) in ms.  The torch-op form is the same "
+             "network written with `F.conv2d` / `relu` / `max_pool2d` and the LPIPS formula in fp32 with autograd, on the same GPU.  A record, "
+             "not a gate: this path did not exist at the parent commit.", "",
+             "| frames | size | native fwd + bwd | torch ops fwd + bwd | torch / native | native forward alone (no grad) | gradient rel-L2 native vs torch "
+             "| vs float64: native | vs float64: torch ops |", "|---|---|---|---|---|---|---|---|---|"]
+    for r in res:
+        lines.append(f"| {r['frames']} | {r['side']} x {r['side']} | {fmt(r['native'])} | {fmt(r['torch'])} | "
+                     f"{r['torch']['median_ms'] / r['native']['median_ms']:.2f} x | {fmt(r['forward'])} | {r['grad_rel_l2_native_vs_torch']:.1e} | "
+                     f"{r['grad_rel_l2_vs_float64_first_two_pairs']['native']:.1e} | {r['grad_rel_l2_vs_float64_first_two_pairs']['torch']:.1e} |")
+    lines += ["", "vs float64: the worst relative L2 per image of the gradient of the first two pairs against float64 torch on the CPU whose ReLU masks "
+              "and pool arg-max are those of the native run (`tests/lpips_grad_common.py`).  The two frames of a pair are close (x1 = 0.7 x0 + 0.3 noise), so "
+              "the head's difference of normalised features cancels and magnifies whatever error the features carry."]
+    lines += ["", "Not measured: per-kernel times of the backward pass (no profiler run was made), memory traffic, any share of a peak."]
+    with open(os.path.join(out, "lpips_grad_ab.json"), "w") as f:
+        json.dump(res, f, indent=1)
+    with open(os.path.join(out, "lpips_grad_ab.md"), "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print("wrote", os.path.join(out, "lpips_grad_ab.md"))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--batch", type=int, default=5, help="images per trunk forward (one group of the diversity score: n_realiz)")
     ap.add_argument("--out", default=os.path.join(REPO, "profiles"), help="directory of vgg_ab.md / vgg_ab.json")
     ap.add_argument("--step-timeout", type=int, default=240, help="seconds per GPU step")
+    ap.add_argument("--backward", action="store_true", help="time LPIPS forward + backward instead -> lpips_grad_ab.md / .json")
     ap.add_argument("--step", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.step == "layers":
         return step_layers(args.batch, args.repeats)
+    if args.step and args.step.startswith("bwd:"):
+        return step_backward(*map(int, args.step.split(":")[1:]), args.repeats)
+    if args.backward:
+        return main_backward(args)
     if args.step:
         return step_lpips(int(args.step), args.repeats)
     res = {}
