@@ -75,6 +75,8 @@ int wino4f32_forward(const Wino4F32Weights& wts, const float* V, float* M, float
                      int W, int epi, hipStream_t st);
 
 // ---- 1x1(x1) convs / Linear layers as a plain pipelined GEMM (i2v_pointwise.hip); conv_forward dispatches to it
+// columns of the 128-row tile both GEMMs below run (128, 64 or 32): a function of the rows and the padded output channels
+int pointwise_tile_n(long M, int CoutPad);
 bool pointwise_supported(const ConvWeights& wts, const float* res, int rt, int rs, int epi, int stride, int stride_t);
 // M = rows (B*T*H*W), P = positions per sample (row / P selects the coef row)
 int pointwise_forward(const ConvWeights& wts, const float* in, int cin_act, float* out, const float* res, long M, long P,
@@ -207,5 +209,31 @@ int conv_img_mfma_forward(const ConvImgMfmaWeights& wts, const float* in, float*
                           int* range_flag = nullptr, long out_bstride = 0);
 // in: fp32 channels-last [B][T][H][W][Cin]; out: frames [B][T][3][H][W] with tanh applied
 int conv_img_forward(const ConvImgWeights& wts, const float* in, float* out, int B, int T, int H, int W, hipStream_t st, long out_bstride = 0);
+// output frames one workgroup of the fused kernel keeps its brick for (a function of the launch geometry; the schedule only)
+int conv_img_mfma_tch(int B, int T, int H, int W);
+// ---- conv_img, every form behind one entry: the decoder and the debug entry i2v_conv_img_unit pack, choose and launch through these
+enum ConvImgForm : int {
+    CONVIMG_MFMA = 0,     // fused matrix-core kernel (split-fp16)
+    CONVIMG_GEMM = 1,     // 81-column transposed split-fp16 GEMM + gather (I2V_DEC_IMG16 = 1, Cin >= 64)
+    CONVIMG_VALU = 2,     // vector-ALU kernel, exact fp32
+    CONVIMG_GENERIC = 3,  // conv_forward(EPI_FRAMES), exact fp32: geometries that tile into its 128-position bricks
+};
+bool conv_img_gemm_supported(int C);
+struct ConvImgSet {
+    ConvWeights generic;
+    ConvImgWeights v;
+    ConvImgMfmaWeights m;   // packed only where conv_img_form may choose it, like g16
+    Conv16Weights g16;
+    DevBuf bias81;          // the gather pass adds the bias (g16 carries none)
+    int Cin = 0;
+    // w [3][cin][3][3][3], b [3]; T, H, W: the output geometry; split16: the handle runs split-fp16 kernels; img16: I2V_DEC_IMG16
+    int pack(const float* w, const float* b, int cin, int T, int H, int W, bool split16, int img16);
+};
+// the form a decoder runs (aux16: its auxiliary layers are on the split-fp16 path right now)
+int conv_img_form(const ConvImgSet& s, bool aux16, int T, int H, int W);
+// x: fp32 channels-last [B][T][H][W][Cin]; out: frames [B][T][3][H][W], out_bstride floats apart (0: dense); scratch: B T H W 81 floats
+// (CONVIMG_GEMM only); range_flag: the split-fp16 forms' sticky overflow flag
+int conv_img_run(const ConvImgSet& s, int form, const float* x, float* out, float* scratch, int B, int T, int H, int W, hipStream_t st,
+                 int* range_flag, long out_bstride);
 
 }  // namespace i2v

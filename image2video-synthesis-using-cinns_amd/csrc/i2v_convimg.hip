@@ -312,24 +312,27 @@ bool conv_img_mfma_supported(int T, int H, int W, int C) {
     return T >= 1 && H % CM_TH == 0 && W % CM_TW == 0 && (C == 16 || C == 32 || C == 48 || C == 64);
 }
 
+// Output frames per workgroup: as many as still leave ~2 waves of workgroups per CU slot (3 workgroups of 45 KB LDS per CU); a chunk of
+// TCH output frames reads TCH + 2 input frames.  Depends on the batch, which changes the schedule only (same bits: see the kernel).
+int conv_img_mfma_tch(int B, int T, int H, int W) {
+    int TCH = 1;
+#ifdef I2V_MEASURE   // (measurement build only: the production library reads no environment variable on a launch path)
+    const char* e = getenv("I2V_CONVIMG_TCH");
+#else
+    const char* e = nullptr;
+#endif
+    const long bricks = (long)B * (H / CM_TH) * (W / CM_TW);
+    for (int c = 16; c >= 2; c /= 2)
+        if (T % c == 0 && bricks * (T / c) >= 2 * 768) { TCH = c; break; }
+    if (e && atoi(e) > 0 && T % atoi(e) == 0) TCH = atoi(e);
+    return TCH;
+}
+
 int conv_img_mfma_forward(const ConvImgMfmaWeights& wts, const float* in, float* out, int B, int T, int H, int W, hipStream_t st,
                           int* range_flag, long out_bstride) {
     I2V_REQUIRE(wts.w.p, I2V_E_STATE, "conv_img (MFMA): weights not packed");
     I2V_REQUIRE(conv_img_mfma_supported(T, H, W, wts.Cin), I2V_E_INVALID, "conv_img (MFMA): unsupported geometry");
-    // frames per workgroup: as many as still leave ~2 waves of workgroups per CU slot (3 workgroups of 45 KB LDS per CU); a chunk of
-    // TCH output frames reads TCH + 2 input frames.  Depends on the batch, which changes the schedule only (same bits: see the kernel).
-    int TCH = 1;
-    {
-#ifdef I2V_MEASURE   // (measurement build only: the production library reads no environment variable on a launch path)
-        const char* e = getenv("I2V_CONVIMG_TCH");
-#else
-        const char* e = nullptr;
-#endif
-        const long bricks = (long)B * (H / CM_TH) * (W / CM_TW);
-        for (int c = 16; c >= 2; c /= 2)
-            if (T % c == 0 && bricks * (T / c) >= 2 * 768) { TCH = c; break; }
-        if (e && atoi(e) > 0 && T % atoi(e) == 0) TCH = atoi(e);
-    }
+    const int TCH = conv_img_mfma_tch(B, T, H, W);
     const long nblk = (long)B * (T / TCH) * (H / CM_TH) * (W / CM_TW);
     I2V_REQUIRE(nblk < (1L << 31), I2V_E_INVALID, "conv_img (MFMA): %ld workgroups", nblk);
     const dim3 grid((unsigned)nblk), block(256);
@@ -345,4 +348,133 @@ int conv_img_mfma_forward(const ConvImgMfmaWeights& wts, const float* in, float*
     return I2V_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// conv_img (decoder.py:117: Conv3d(nf, 3, 3, padding 1) + tanh) in split-fp16 mode.  With three output channels a tiled
+// implicit GEMM wastes the matrix cores (N padded to 32) and the vector-ALU kernel is LDS-bound; instead the conv is split
+// into a 1x1x1 GEMM Y[tap * 3 + n][pos] = sum_c x[pos][c] w[n][c][tap] (81 planes, written transposed by
+// pointwise16_forward: HBM-bound) and this gather: out[n][pos] = tanh(bias[n] + sum_tap Y[tap * 3 + n][pos + delta_tap]),
+// zero padding = skipped taps.  Consecutive lanes = consecutive w: every load and store is coalesced.
+// out: frames [B][T][3][H][W].
+__global__ __launch_bounds__(256) void conv_img_gather_kernel(const float* __restrict__ y, const float* __restrict__ bias,
+                                                              float* __restrict__ out, long total, int T, int H, int W, long obs) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const int w = (int)(i % W);
+    long q = i / W;
+    const int h = (int)(q % H); q /= H;
+    const int t = (int)(q % T);
+    const long b = q / T;
+    float s0 = bias[0], s1 = bias[1], s2 = bias[2];
+#pragma unroll
+    for (int kt = 0; kt < 3; ++kt) {
+        const int tt = t + kt - 1;
+        if ((unsigned)tt >= (unsigned)T) continue;
+#pragma unroll
+        for (int kh = 0; kh < 3; ++kh) {
+            const int hh = h + kh - 1;
+            if ((unsigned)hh >= (unsigned)H) continue;
+#pragma unroll
+            for (int kw = 0; kw < 3; ++kw) {
+                const int ww = w + kw - 1;
+                if ((unsigned)ww >= (unsigned)W) continue;
+                const float* p = y + (long)(((kt * 3 + kh) * 3 + kw) * 3) * total + (((b * T + tt) * H + hh) * W + ww);
+                s0 += p[0]; s1 += p[total]; s2 += p[2 * total];
+            }
+        }
+    }
+    const long hw = (long)h * W + w, HW = (long)H * W;
+    float* o = out + b * obs + ((long)t * 3) * HW + hw;
+    o[0] = tanhf(s0); o[HW] = tanhf(s1); o[2 * HW] = tanhf(s2);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Every form of conv_img behind one entry: what the decoder packs at load time, the form it then runs, and the launch.
+// (the debug entry i2v_conv_img_unit below goes through the same three functions)
+bool conv_img_gemm_supported(int C) { return C >= 64 && C % 4 == 0; }
+
+int ConvImgSet::pack(const float* w, const float* b, int cin, int T, int H, int W, bool split16, int img16) {
+    Cin = cin;
+    int rc;
+    if ((rc = generic.pack(w, b, 3, cin, 3, 3, 3, 1.0))) return rc;
+    if ((rc = v.pack(w, b, cin))) return rc;
+    // (measured: 1.3 vs 1.7 ms per B = 64 BAIR pass at nf = 64, but 0.8 ms SLOWER than the vector-ALU kernel per B = 32
+    //  128x128 pass at nf = 32, where the 81 planes outweigh the 32-channel input)
+    if (split16 && img16 == 2 && conv_img_mfma_supported(T, H, W, cin) && (rc = m.pack(w, b, cin))) return rc;
+    if (split16 && img16 == 1 && conv_img_gemm_supported(cin)) {
+        std::vector<float> w81((size_t)81 * cin);   // row tap * 3 + n = w[n][:][tap]
+        for (int n = 0; n < 3; ++n)
+            for (int c = 0; c < cin; ++c)
+                for (int tap = 0; tap < 27; ++tap) w81[(size_t)(tap * 3 + n) * cin + c] = w[((size_t)n * cin + c) * 27 + tap];
+        if ((rc = g16.pack(w81.data(), nullptr, 81, cin, 1, 1, 1, 1.0))) return rc;
+        if ((rc = bias81.upload(b, 3 * 4))) return rc;
+    }
+    return I2V_OK;
+}
+
+int conv_img_form(const ConvImgSet& s, bool aux16, int T, int H, int W) {
+    if (aux16 && s.m.w.p) return CONVIMG_MFMA;
+    if (aux16 && s.g16.w.p) return CONVIMG_GEMM;
+    if (conv_img_supported(T, H, W, s.Cin)) return CONVIMG_VALU;
+    return CONVIMG_GENERIC;
+}
+
+int conv_img_run(const ConvImgSet& s, int form, const float* x, float* out, float* scratch, int B, int T, int H, int W, hipStream_t st,
+                 int* range_flag, long out_bstride) {
+    const long dense = (long)T * 3 * H * W;
+    const long obs = out_bstride ? out_bstride : dense;
+    switch (form) {
+        case CONVIMG_MFMA: return conv_img_mfma_forward(s.m, x, out, B, T, H, W, st, range_flag, obs);
+        case CONVIMG_GEMM: {
+            const long P = (long)T * H * W, tot = (long)B * P;
+            I2V_REQUIRE(s.g16.w.p && scratch, I2V_E_STATE, "conv_img (GEMM + gather): weights not packed or no scratch");
+            I2V_REQUIRE((tot + 255) / 256 < (1L << 31), I2V_E_INVALID, "conv_img: %ld positions", tot);
+            if (int rc = pointwise16_forward(s.g16, x, scratch, nullptr, tot, P, EPI_NONE, st, nullptr, range_flag, true)) return rc;
+            hipLaunchKernelGGL(conv_img_gather_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, scratch, s.bias81.as<float>(), out, tot,
+                               T, H, W, obs);
+            I2V_HIP_CHECK(hipGetLastError());
+            return I2V_OK;
+        }
+        case CONVIMG_VALU: return conv_img_forward(s.v, x, out, B, T, H, W, st, obs);
+        case CONVIMG_GENERIC: return conv_forward(s.generic, x, s.Cin, out, nullptr, 1, 1, B, T, H, W, EPI_FRAMES, st, nullptr, 1, 1, obs);
+    }
+    I2V_REQUIRE(false, I2V_E_INVALID, "conv_img: form %d", form);
+}
+
 }  // namespace i2v
+
+using namespace i2v;
+
+extern "C" int i2v_conv_img_unit(const float* x, const float* weight, const float* bias, int32_t b, int32_t t, int32_t h, int32_t w, int32_t c,
+                                 int32_t form, float* out, int64_t out_bstride, int32_t* form_used, int32_t* tch, int32_t* range_flag,
+                                 void* stream) {
+    I2V_REQUIRE(x && weight && bias && out && b > 0 && t > 0 && h > 0 && w > 0 && c > 0, I2V_E_INVALID, "i2v_conv_img_unit: bad argument");
+    I2V_REQUIRE(form >= -1 && form <= CONVIMG_GENERIC, I2V_E_INVALID, "i2v_conv_img_unit: form %d (-1 = the decoder's choice, 0 .. 3)", form);
+    const long dense = (long)t * 3 * h * w, tot = (long)b * t * h * w;
+    I2V_REQUIRE(out_bstride == 0 || out_bstride >= dense, I2V_E_INVALID, "i2v_conv_img_unit: sample stride %lld below the dense %ld",
+                (long long)out_bstride, dense);
+    I2V_REQUIRE(tot * std::max(c, 81) < (1L << 31), I2V_E_INVALID, "i2v_conv_img_unit: %ld positions x %d channels is too large", tot, c);
+    const bool ok = form == CONVIMG_MFMA ? conv_img_mfma_supported(t, h, w, c)
+                  : form == CONVIMG_GEMM ? conv_img_gemm_supported(c)
+                  : form == CONVIMG_VALU ? conv_img_supported(t, h, w, c) : true;
+    I2V_REQUIRE(ok, I2V_E_INVALID, "i2v_conv_img_unit: form %d does not support [%d, %d, %d] x %d channels", form, t, h, w, c);
+    // pack what a split-fp16 decoder of this geometry packs (I2V_DEC_IMG16 = 1 for the GEMM + gather form, else its default 2)
+    ConvImgSet set;
+    if (int rc = set.pack(weight, bias, c, t, h, w, true, form == CONVIMG_GEMM ? 1 : 2)) return rc;
+    const int f = form < 0 ? conv_img_form(set, true, t, h, w) : form;
+    DevBuf scratch, flag;
+    if (f == CONVIMG_GEMM) I2V_HIP_CHECK(hipMalloc(&scratch.p, (size_t)tot * 81 * 4));
+    I2V_HIP_CHECK(hipMalloc(&flag.p, 4));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    I2V_HIP_CHECK(hipMemsetAsync(flag.p, 0, 4, st));
+    if (int rc = conv_img_run(set, f, x, out, scratch.as<float>(), b, t, h, w, st, flag.as<int>(), out_bstride)) {
+        (void)hipStreamSynchronize(st);
+        return rc;
+    }
+    int fl = 0;
+    I2V_HIP_CHECK(hipMemcpyAsync(&fl, flag.p, 4, hipMemcpyDeviceToHost, st));
+    I2V_HIP_CHECK(hipStreamSynchronize(st));   // the packed weights and the scratch die with this call
+    if (form_used) *form_used = f;
+    if (tch) *tch = f == CONVIMG_MFMA ? conv_img_mfma_tch(b, t, h, w) : 0;
+    if (range_flag) *range_flag = fl;
+    return I2V_OK;
+}

@@ -21,47 +21,6 @@
 
 #include "i2v_dec_block.h"
 
-namespace i2v {
-// conv_img (decoder.py:117: Conv3d(nf, 3, 3, padding 1) + tanh) in split-fp16 mode.  With three output channels a tiled
-// implicit GEMM wastes the matrix cores (N padded to 32) and the vector-ALU kernel is LDS-bound; instead the conv is split
-// into a 1x1x1 GEMM Y[tap * 3 + n][pos] = sum_c x[pos][c] w[n][c][tap] (81 planes, written transposed by
-// pointwise16_forward: HBM-bound) and this gather: out[n][pos] = tanh(bias[n] + sum_tap Y[tap * 3 + n][pos + delta_tap]),
-// zero padding = skipped taps.  Consecutive lanes = consecutive w: every load and store is coalesced.
-// out: frames [B][T][3][H][W].
-__global__ __launch_bounds__(256) void conv_img_gather_kernel(const float* __restrict__ y, const float* __restrict__ bias,
-                                                              float* __restrict__ out, long total, int T, int H, int W, long obs) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= total) return;
-    const int w = (int)(i % W);
-    long q = i / W;
-    const int h = (int)(q % H); q /= H;
-    const int t = (int)(q % T);
-    const long b = q / T;
-    float s0 = bias[0], s1 = bias[1], s2 = bias[2];
-#pragma unroll
-    for (int kt = 0; kt < 3; ++kt) {
-        const int tt = t + kt - 1;
-        if ((unsigned)tt >= (unsigned)T) continue;
-#pragma unroll
-        for (int kh = 0; kh < 3; ++kh) {
-            const int hh = h + kh - 1;
-            if ((unsigned)hh >= (unsigned)H) continue;
-#pragma unroll
-            for (int kw = 0; kw < 3; ++kw) {
-                const int ww = w + kw - 1;
-                if ((unsigned)ww >= (unsigned)W) continue;
-                const float* p = y + (long)(((kt * 3 + kh) * 3 + kw) * 3) * total + (((b * T + tt) * H + hh) * W + ww);
-                s0 += p[0]; s1 += p[total]; s2 += p[2 * total];
-            }
-        }
-    }
-    const long hw = (long)h * W + w, HW = (long)H * W;
-    float* o = out + b * obs + ((long)t * 3) * HW + hw;
-    o[0] = tanhf(s0); o[HW] = tanhf(s1); o[2 * HW] = tanhf(s2);
-}
-
-}  // namespace i2v
-
 using namespace i2v;
 
 namespace {
@@ -159,11 +118,8 @@ struct i2v_dec {
     BlockCtx ctx;
     Block blk[6];
     Level lvl[6];
-    ConvWeights fc, zlin, conv_img;
-    ConvImgWeights conv_img_v;  // vector-ALU variant (used when the output geometry tiles into 4x8x8 bricks)
-    ConvImgMfmaWeights conv_img_m;  // fused matrix-core variant (split-fp16 mode, img16 == 2)
-    Conv16Weights conv_img16;   // split-fp16 mode: the 81-column 1x1x1 GEMM of conv_img_gather_kernel
-    DevBuf conv_img_bias;
+    ConvWeights fc, zlin;
+    ConvImgSet conv_img;        // every packed form of conv_img (i2v_convimg.hip)
     int Nz = 0;
     int auto_reruns = 0;        // mma = auto: forwards that had to be run again (reporting)
     double prof_conv3_ms = 0, prof_conv3_flops = 0, prof_conv3_exec = 0;   // totals of the resolved profile events
@@ -208,7 +164,7 @@ DecWs dec_ws(const i2v_dec* d, int B, int Fg = 0) {
         mx_gb = std::max(mx_gb, (size_t)l.H * l.W * 2 * b.n_in);
         cmax = std::max(cmax, std::max(b.n_in, b.n_mid));
     }
-    if (d->ctx.has16() && d->ctx.img16 == 1 && d->nf >= 64) mx_a = std::max(mx_a, (size_t)d->lvl[5].T * d->lvl[5].H * d->lvl[5].W * 81);  // conv_img's Y
+    if (d->ctx.has16() && d->ctx.img16 == 1 && conv_img_gemm_supported(d->nf)) mx_a = std::max(mx_a, (size_t)d->lvl[5].T * d->lvl[5].H * d->lvl[5].W * 81);  // conv_img's Y
     DecWs L;
     size_t o = 0;
     auto take = [&](size_t floats) { size_t r = o; o = align_up(o + floats * 4, 256); return r; };
@@ -352,20 +308,7 @@ int i2v_dec_load(i2v_dec* d, const i2v_tensor* tensors, int32_t n_tensors) {
         const float* w = sd.f32("conv_img.weight", (int64_t)3 * nf * 27);
         const float* b = sd.f32("conv_img.bias", 3);
         if (!w || !b) return I2V_E_MISSING;
-        if ((rc = d->conv_img.pack(w, b, 3, nf, 3, 3, 3, 1.0))) return rc;
-        if ((rc = d->conv_img_v.pack(w, b, nf))) return rc;
-        // (measured: 1.3 vs 1.7 ms per B = 64 BAIR pass at nf = 64, but 0.8 ms SLOWER than the vector-ALU kernel per B = 32
-        //  128x128 pass at nf = 32, where the 81 planes outweigh the 32-channel input)
-        if (d->ctx.has16() && d->ctx.img16 == 2 && conv_img_mfma_supported(d->lvl[5].T, d->lvl[5].H, d->lvl[5].W, nf) &&
-            (rc = d->conv_img_m.pack(w, b, nf))) return rc;
-        if (d->ctx.has16() && d->ctx.img16 == 1 && nf >= 64 && nf % 4 == 0) {
-            std::vector<float> w81((size_t)81 * nf);   // row tap * 3 + n = w[n][:][tap]
-            for (int n = 0; n < 3; ++n)
-                for (int c = 0; c < nf; ++c)
-                    for (int tap = 0; tap < 27; ++tap) w81[(size_t)(tap * 3 + n) * nf + c] = w[((size_t)n * nf + c) * 27 + tap];
-            if ((rc = d->conv_img16.pack(w81.data(), nullptr, 81, nf, 1, 1, 1, 1.0))) return rc;
-            if ((rc = d->conv_img_bias.upload(b, 3 * 4))) return rc;
-        }
+        if ((rc = d->conv_img.pack(w, b, nf, d->lvl[5].T, d->lvl[5].H, d->lvl[5].W, d->ctx.has16(), d->ctx.img16))) return rc;
     }
     d->loaded = true;
     return I2V_OK;
@@ -462,6 +405,12 @@ int i2v_dec_get_layer_profile(i2v_dec* d, int32_t layer, char* name, int32_t nam
     return I2V_OK;
 }
 
+int i2v_dec_get_spade_form(i2v_dec* d, int32_t block, int32_t* form) {
+    I2V_REQUIRE(d && form && block >= 0 && block < 6, I2V_E_INVALID, "i2v_dec_get_spade_form: block %d (0..5)", block);
+    *form = d->blk[block].spade_form;
+    return I2V_OK;
+}
+
 }  // extern "C"
 
 // The SPADE conditioning branches of all six blocks on the handle's side stream, forked from `st` by an event (everything the
@@ -485,11 +434,11 @@ static int fork_spade(i2v_dec* d, const DecWs& L, char* ws, const float* img, in
     // later levels have the first two blocks' time to get through.  (Own side stream: everything on it, as before.)
     const int k0 = sd.owned ? 0 : 2;
     for (int k = 0; k < k0 && !rc; ++k) {
-        rc = spade_branch(&d->ctx, d->blk[k], d->lvl[k], img, img_h, img_w, ibs, B, F(L.y0), F(L.y1), L.has_y1v ? F(L.y1v) : nullptr, F(L.gbs[k]), st);
+        rc = spade_branch(&d->ctx, d->blk[k], d->lvl[k], img, img_h, img_w, ibs, B, F(L.y0), F(L.y1), L.has_y1v ? F(L.y1v) : nullptr, F(L.gbs[k]), st, k);
         if (!rc && hipEventRecord(sd.ev_lvl[k], st) != hipSuccess) rc = I2V_E_HIP;
     }
     for (int k = k0; k < 6 && !rc; ++k) {
-        rc = spade_branch(&d->ctx, d->blk[k], d->lvl[k], img, img_h, img_w, ibs, B, F(L.py0), F(L.py1), L.has_y1v ? F(L.py1v) : nullptr, F(L.gbs[k]), sd.stream);
+        rc = spade_branch(&d->ctx, d->blk[k], d->lvl[k], img, img_h, img_w, ibs, B, F(L.py0), F(L.py1), L.has_y1v ? F(L.py1v) : nullptr, F(L.gbs[k]), sd.stream, k);
         if (!rc && hipEventRecord(sd.ev_lvl[k], sd.stream) != hipSuccess) rc = I2V_E_HIP;
     }
     // (an error must not leave the caller's stream ahead of work this call put on the side stream)
@@ -607,16 +556,8 @@ static int dec_forward_once(i2v_dec* d, const float* img, int32_t img_h, int32_t
     join.on = false;   // every level's maps and every shortcut have been waited for by their consumers
     {
         const Level& l = d->lvl[5];
-        if (d->ctx.aux16() && d->conv_img_m.w.p) rc = conv_img_mfma_forward(d->conv_img_m, x, out, B, l.T, l.H, l.W, st, d->ctx.status_dev, out_bstride);
-        else if (d->ctx.aux16() && d->conv_img16.w.p) {
-            const long P = (long)l.T * l.H * l.W, tot = (long)B * P;
-            I2V_REQUIRE((tot + 255) / 256 < (1L << 31), I2V_E_INVALID, "conv_img: %ld positions", tot);
-            if ((rc = pointwise16_forward(d->conv_img16, x, a, nullptr, tot, P, EPI_NONE, st, nullptr, d->ctx.status_dev, true))) return rc;
-            hipLaunchKernelGGL(conv_img_gather_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, a,
-                               d->conv_img_bias.as<float>(), out, tot, l.T, l.H, l.W, (long)out_bstride);
-            I2V_HIP_CHECK(hipGetLastError());
-        } else if (conv_img_supported(l.T, l.H, l.W, d->nf)) rc = conv_img_forward(d->conv_img_v, x, out, B, l.T, l.H, l.W, st, out_bstride);
-        else rc = conv_forward(d->conv_img, x, d->nf, out, nullptr, 1, 1, B, l.T, l.H, l.W, EPI_FRAMES, st, nullptr, 1, 1, out_bstride);
+        rc = conv_img_run(d->conv_img, conv_img_form(d->conv_img, d->ctx.aux16(), l.T, l.H, l.W), x, out, a, B, l.T, l.H, l.W, st, d->ctx.status_dev,
+                          out_bstride);
         if (rc) return rc;
     }
     if (d->ctx.has16()) {
@@ -721,7 +662,7 @@ static int dec_prepare(i2v_dec* d, const float* img, int32_t img_h, int32_t img_
     if (int rc = fork_spade(d, L, ws, img, img_h, img_w, 0, Fr, st, &forked)) return rc;
     if (!forked)
         for (int k = 0; k < 6; ++k)
-            if (int rc = spade_branch(&d->ctx, d->blk[k], d->lvl[k], img, img_h, img_w, 0, Fr, F(L.py0), F(L.py1), L.has_y1v ? F(L.py1v) : nullptr, F(L.gbs[k]), st))
+            if (int rc = spade_branch(&d->ctx, d->blk[k], d->lvl[k], img, img_h, img_w, 0, Fr, F(L.py0), F(L.py1), L.has_y1v ? F(L.py1v) : nullptr, F(L.gbs[k]), st, k))
                 return rc;
     d->prep = Prepared{img, B, K, img_h, img_w, (long)3 * img_h * img_w, workspace, forked};
     return I2V_OK;

@@ -41,8 +41,12 @@ struct Block {
     Wino16Weights sp_gb_w;      // SPADE's fused gamma|beta Conv2d(128, 2C, 3) on the Winograd kernel (1x3x3 variant)
     Wino4Weights sp_gb_w4;      // ... on the F(4,3) kernel (packed INSTEAD where the shape allows: W % 16 == 0, H % 32 == 0)
     DevBuf gn_w, gn_b;
+    int spade_form = -1;        // SpadeForm of the last spade_branch call (-1: none yet)
     int zoff = 0;  // offset of this block's ADAIN (gamma|beta) in the z-GEMM output
 };
+
+// The form SPADE's branch takes (spade_branch): the codes i2v_dec_get_spade_form reports
+enum SpadeForm : int { SPADE_F43 = 0, SPADE_F23 = 1, SPADE_DIRECT16 = 2, SPADE_F32 = 3 };
 
 struct Level { int T, H, W, ut, us; };  // resolution a block runs at and the upsample factors in front of it
 
@@ -122,9 +126,10 @@ Conv3Kernel conv3_split_kernel(const BlockCtx* d, const Conv3& c, const Level& l
 bool spade_w4_wanted(const BlockCtx* d, const Block& b, const Level& l);
 bool spade_wino_wanted(const BlockCtx* d, const Block& b, const Level& l);
 
-// ibs: floats between the samples of `img` (0: dense [B][3][H][W])
+// ibs: floats between the samples of `img` (0: dense [B][3][H][W]); k: the decoder block whose debug taps 13 .. 15 the branch serves
+// (-1: none).  Records the form it took in b.spade_form (i2v_dec_get_spade_form).
 int spade_branch(BlockCtx* d, Block& b, const Level& l, const float* img, int img_h, int img_w, long ibs, int B, float* y0, float* y1,
-                 float* y1v, float* gb, hipStream_t st);
+                 float* y1v, float* gb, hipStream_t st, int k = -1);
 int block_forward(BlockCtx* d, int k, Block& b, const Level& l, const float* x, float* xn, const float* img, int img_h, int img_w, long ibs,
                   const float* zl, int zstride, int B, const BlockBufs& w, bool& x_stats_ready, bool last, hipStream_t st);
 

@@ -66,25 +66,43 @@ struct ProfScope {
 // SPADE's conditioning branch of one block (normalization_layer.py:20-23): resize(start frame) -> Conv2d(3, 128) + lrelu ->
 // fused gamma | beta Conv2d(128, 2C) ("+1" folded into the gamma bias) -> gb [B][H][W][2C].  Depends on the start frame only.
 int spade_branch(BlockCtx* d, Block& b, const Level& l, const float* img, int img_h, int img_w, long ibs, int B, float* y0, float* y1,
-                 float* y1v, float* gb, hipStream_t st) {
+                 float* y1v, float* gb, hipStream_t st, int k) {
     int rc;
+    // debug taps 13 .. 15 of block k (k < 0: a stand-alone block, no taps): the branch's intermediates in the form they are stored in
+    auto tap = [&](int which, const void* src, size_t count) -> int {
+        if (k >= 0 && d->tap_dst && d->tap_block == k && d->tap_which == which)
+            I2V_HIP_CHECK(hipMemcpyAsync(d->tap_dst, src, std::min(count, d->tap_max) * 4, hipMemcpyDeviceToDevice, st));
+        return I2V_OK;
+    };
+    const size_t HW = (size_t)B * l.H * l.W;
     if ((rc = resize_forward(img, y0, B, img_h, img_w, l.H, l.W, st, d->aux16() ? 1 : 0, d->status_dev, ibs))) return rc;
+    if ((rc = tap(13, y0, HW * 16))) return rc;
     if (d->aux16() && b.sp_gb_w4.w.p && y1v) {
+        b.spade_form = SPADE_F43;
         if ((rc = conv16_forward(b.sp_conv16, y0, y1, nullptr, 1, 1, B, 1, l.H, l.W, EPI_LRELU, st))) return rc;
+        if ((rc = tap(14, y1, HW * 128))) return rc;
         if ((rc = run_modulate_wino4(y1, nullptr, nullptr, y1v, B, 1, l.H, l.W, 128, 1, 1, 0, st, false, d->status_dev))) return rc;
+        if ((rc = tap(15, y1v, HW * 128 * 3 / 2))) return rc;
         if ((rc = wino4_forward(b.sp_gb_w4, y1v, gb, nullptr, 1, 1, B, 1, l.H, l.W, EPI_NONE, st, nullptr))) return rc;
     } else if (d->aux16() && b.sp_gb_w.w.p && y1v) {
         // gamma | beta conv on the Winograd kernel: the 128-channel activation goes through fp32 once more (the operand
         // writer needs the w-neighbours of every position, which the producing conv's epilogue does not hold)
+        b.spade_form = SPADE_F23;
         if ((rc = conv16_forward(b.sp_conv16, y0, y1, nullptr, 1, 1, B, 1, l.H, l.W, EPI_LRELU, st))) return rc;
+        if ((rc = tap(14, y1, HW * 128))) return rc;
         if ((rc = run_modulate_wino(y1, nullptr, nullptr, y1v, B, 1, l.H, l.W, 128, 1, 1, 0, st, d->status_dev))) return rc;
+        if ((rc = tap(15, y1v, HW * 128 * 2))) return rc;
         if ((rc = wino16_forward(b.sp_gb_w, y1v, gb, nullptr, 1, 1, B, 1, l.H, l.W, EPI_NONE, st, nullptr))) return rc;
     } else if (d->aux16()) {
+        b.spade_form = SPADE_DIRECT16;
         if ((rc = conv16_forward(b.sp_conv16, y0, y1, nullptr, 1, 1, B, 1, l.H, l.W, EPI_LRELU | EPI_HL16, st, nullptr, d->status_dev)))
             return rc;
+        if ((rc = tap(14, y1, HW * 128))) return rc;
         if ((rc = conv16_forward(b.sp_gb16, y1, gb, nullptr, 1, 1, B, 1, l.H, l.W, EPI_NONE, st))) return rc;
     } else {
+        b.spade_form = SPADE_F32;
         if ((rc = conv_forward(b.sp_conv, y0, 16, y1, nullptr, 1, 1, B, 1, l.H, l.W, EPI_LRELU, st))) return rc;
+        if ((rc = tap(14, y1, HW * 128))) return rc;
         if ((rc = conv_forward(b.sp_gb, y1, 128, gb, nullptr, 1, 1, B, 1, l.H, l.W, EPI_NONE, st))) return rc;
     }
     return I2V_OK;
@@ -212,7 +230,7 @@ int block_forward(BlockCtx* d, int k, Block& b, const Level& l, const float* x, 
     const GbRows rows = w.rows;
     const int Bg = rows.shared() ? (rows.r0 + B - 1) / rows.k + 1 : B;
     if (w.gb_ready) gb = const_cast<float*>(w.gb_ready);
-    else if ((rc = spade_branch(d, b, l, img, img_h, img_w, ibs, Bg, y0, y1, w.y1v, gb, st))) return rc;
+    else if ((rc = spade_branch(d, b, l, img, img_h, img_w, ibs, Bg, y0, y1, w.y1v, gb, st, k))) return rc;
     if ((rc = tap(k, 0, gb, (size_t)Bg * l.H * l.W * 2 * b.n_in, st))) return rc;
     // per conv: the kernel it runs in this call, its operand writer, the conv
     const Conv3 &c0 = b.conv[0], &c1 = b.conv[1];

@@ -414,6 +414,16 @@ int pw16_launch(const Pw16Args& a, hipStream_t st) {
 
 }  // namespace
 
+// Tile of both GEMMs: 128 rows, and as wide as CoutPad allows, narrowed while most of the 256 CUs would stay without a workgroup.
+// (A 64 x 64 tile used to follow "BN == 64 and still fewer than 512 workgroups"; the loop leaves BN == 64 only with 512 or more, so
+// it could never be chosen and was removed.)
+int pointwise_tile_n(long M, int CoutPad) {
+    int BN = CoutPad % 128 == 0 ? 128 : (CoutPad % 64 == 0 ? 64 : 32);
+    auto blocks = [&](int bn) { return (M + 127) / 128 * (CoutPad / bn); };
+    while (BN > 32 && blocks(BN) < 512) BN /= 2;
+    return BN;
+}
+
 int pointwise16_forward(const Conv16Weights& wts, const float* in, float* out, const float* res, long M, long P, int epi,
                         hipStream_t st, const float* coef, int* range_flag, bool transposed) {
     I2V_REQUIRE(wts.w.p && wts.KT == 1 && wts.KH == 1 && wts.KW == 1 && !wts.tdup, I2V_E_STATE, "pointwise16: needs 1x1x1 split-fp16 weights");
@@ -428,14 +438,9 @@ int pointwise16_forward(const Conv16Weights& wts, const float* in, float* out, c
         I2V_REQUIRE(a.CoutPad % 128 == 0, I2V_E_INVALID, "pointwise16: transposed output needs CoutPad %% 128 == 0 (have %d)", a.CoutPad);
         return pw16_launch1<2, 2, 2, 2, false, true>(a, st);                     // 128 x 128: the rows are read once
     }
-    int BN = a.CoutPad % 128 == 0 ? 128 : (a.CoutPad % 64 == 0 ? 64 : 32);
-    int BM = 128;
-    auto blocks = [&](int bm, int bn) { return (M + bm - 1) / bm * (a.CoutPad / bn); };
-    while (BN > 32 && blocks(BM, BN) < 512) BN /= 2;
-    if (BN == 64 && blocks(BM, BN) < 512) BM = 64;
+    const int BN = pointwise_tile_n(M, a.CoutPad);
     if (BN == 128) return pw16_launch<2, 2, 2, 2>(a, st);                        // 128 x 128
-    if (BN == 64) return BM == 128 ? pw16_launch<2, 2, 2, 1>(a, st)              // 128 x 64
-                                   : pw16_launch<2, 2, 1, 1>(a, st);             //  64 x 64
+    if (BN == 64) return pw16_launch<2, 2, 2, 1>(a, st);                         // 128 x 64
     return pw16_launch<4, 1, 1, 1>(a, st);                                       // 128 x 32
 }
 
@@ -450,16 +455,45 @@ int pointwise_forward(const ConvWeights& wts, const float* in, int cin_act, floa
     a.in = in; a.wp = wts.w.as<float>(); a.bias = wts.bias.as<float>(); a.res = res; a.coef = coef; a.out = out;
     a.M = M; a.P = P; a.CinAct = cin_act; a.Cin = wts.Cin; a.Cout = wts.Cout; a.CoutPad = wts.CoutPad; a.nchunk16 = wts.nchunk;
     a.epi = epi;
-    // tile: as wide as CoutPad allows, narrowed / shortened while most of the 256 CUs would stay without a workgroup
-    int BN = a.CoutPad % 128 == 0 ? 128 : (a.CoutPad % 64 == 0 ? 64 : 32);
-    int BM = 128;
-    auto blocks = [&](int bm, int bn) { return (M + bm - 1) / bm * (a.CoutPad / bn); };
-    while (BN > 32 && blocks(BM, BN) < 512) BN /= 2;
-    if (BN == 64 && blocks(BM, BN) < 512) BM = 64;
+    const int BN = pointwise_tile_n(M, a.CoutPad);
     if (BN == 128) return pw_launch<2, 2, 2, 2>(a, st);                        // 128 x 128
-    if (BN == 64) return BM == 128 ? pw_launch<2, 2, 2, 1>(a, st)              // 128 x 64
-                                   : pw_launch<2, 2, 1, 1>(a, st);             //  64 x 64
+    if (BN == 64) return pw_launch<2, 2, 2, 1>(a, st);                         // 128 x 64
     return pw_launch<4, 1, 1, 1>(a, st);                                       // 128 x 32
 }
 
 }  // namespace i2v
+
+using namespace i2v;
+
+extern "C" int i2v_pointwise_unit(const float* in, const float* weight, const float* bias, const float* res, const float* coef, float* out,
+                                  int64_t m, int64_t p, int32_t cin, int32_t cout, int32_t lrelu, int32_t split16, int32_t transposed,
+                                  int32_t* tile_n, int32_t* range_flag, void* stream) {
+    I2V_REQUIRE(in && weight && out && m > 0 && p > 0 && cin > 0 && cout > 0, I2V_E_INVALID, "i2v_pointwise_unit: bad argument");
+    I2V_REQUIRE(cin % 4 == 0, I2V_E_INVALID, "i2v_pointwise_unit: %d input channels (a multiple of 4 is needed)", cin);
+    I2V_REQUIRE(!transposed || split16, I2V_E_INVALID, "i2v_pointwise_unit: only the split-fp16 GEMM writes a transposed output");
+    I2V_REQUIRE((long)m * std::max(cin, (cout + 127) / 128 * 128) < (1L << 40), I2V_E_INVALID, "i2v_pointwise_unit: %lld rows is too large", (long long)m);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int epi = lrelu ? EPI_LRELU : EPI_NONE;
+    DevBuf flag;
+    I2V_HIP_CHECK(hipMalloc(&flag.p, 4));
+    I2V_HIP_CHECK(hipMemsetAsync(flag.p, 0, 4, st));
+    ConvWeights w32;
+    Conv16Weights w16;
+    int rc, pad;
+    if (split16) {
+        if ((rc = w16.pack(weight, bias, cout, cin, 1, 1, 1, 1.0))) return rc;
+        pad = w16.CoutPad;
+        rc = pointwise16_forward(w16, in, out, res, m, p, epi, st, coef, flag.as<int>(), transposed != 0);
+    } else {
+        if ((rc = w32.pack(weight, bias, cout, cin, 1, 1, 1, 1.0))) return rc;
+        pad = w32.CoutPad;
+        rc = pointwise_forward(w32, in, cin, out, res, m, p, epi, st, coef);
+    }
+    if (rc) { (void)hipStreamSynchronize(st); return rc; }
+    int fl = 0;
+    I2V_HIP_CHECK(hipMemcpyAsync(&fl, flag.p, 4, hipMemcpyDeviceToHost, st));
+    I2V_HIP_CHECK(hipStreamSynchronize(st));   // the packed weights die with this call
+    if (tile_n) *tile_n = transposed ? 128 : pointwise_tile_n(m, pad);
+    if (range_flag) *range_flag = fl;
+    return I2V_OK;
+}

@@ -197,6 +197,11 @@ SYMBOLS = {
     "i2v_dec_fallback_layers": (c_int32, [c_void_p, POINTER(c_int32), POINTER(c_int32)]),
     "i2v_dec_set_profile": (c_int32, [c_void_p, c_int32]),
     "i2v_dec_debug_tap": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_size_t]),
+    "i2v_dec_get_spade_form": (c_int32, [c_void_p, c_int32, POINTER(c_int32)]),
+    "i2v_conv_img_unit": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64,
+                                    POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), c_void_p]),
+    "i2v_pointwise_unit": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32,
+                                     c_int32, c_int32, POINTER(c_int32), POINTER(c_int32), c_void_p]),
     "i2v_dec_get_profile": (c_int32, [c_void_p, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_int64)]),
     "i2v_dec_status": (c_int32, [c_void_p, POINTER(c_int32), c_int32, c_void_p]),
     "i2v_dec_get_layer_profile": (c_int32, [c_void_p, c_int32, ctypes.c_char_p, c_int32, POINTER(c_double), POINTER(c_double),
@@ -617,6 +622,17 @@ class NativeDecoder(_Handle):
         else:
             _check(lib().i2v_dec_debug_tap(self._h, block, which, dst.data_ptr(), dst.numel()), "i2v_dec_debug_tap")
 
+    SPADE_FORMS = ("f43", "f23", "hl16", "f32")   # i2v_dec_get_spade_form's codes: the gamma | beta conv's kernel (dec_units_common names)
+
+    def spade_forms(self):
+        """The form SPADE's branch of each block took in the last forward (i2v_dec_get_spade_form); None: not run yet."""
+        out = []
+        for k in range(6):
+            f = c_int32(-1)
+            _check(lib().i2v_dec_get_spade_form(self._h, k, ctypes.byref(f)), "i2v_dec_get_spade_form")
+            out.append(self.SPADE_FORMS[f.value] if f.value >= 0 else None)
+        return out
+
     def debug_tap_f64(self, block, which, pairs, device):
         """A NaN-filled float64 CUDA tensor [pairs, 2] set as the destination of one of the fp64 taps (6, 7, 8: (sum, sumsq) pairs, which
         the hook copies as bytes); read it after the next forward."""
@@ -750,6 +766,72 @@ class NativeDecoder(_Handle):
             _check(lib().i2v_dec_forward_realizations(self._h, iv[0], img.shape[2], img.shape[3], iv[1], Fr, K, motion.data_ptr(), ov[0],
                                                       ov[1], ws.data_ptr(), ws.numel(), _stream()), "i2v_dec_forward_realizations")
         return out
+
+
+CONV_IMG_FORMS = ("mfma", "gemm", "valu", "generic")   # i2v_conv_img_unit's form codes 0 .. 3
+
+
+def conv_img_unit(x_cl, weight, bias, form=None, out=None, info=None):
+    """``i2v_conv_img_unit``: the decoder's conv_img + tanh on x_cl [B, T, H, W, C] channels-last (device) with host ``weight``
+    [3, C, 3, 3, 3] / ``bias`` [3] -> frames [B, T, 3, H, W].  form: None = the choice of a split-fp16 decoder, or one of
+    CONV_IMG_FORMS (refused with I2VError where the form does not support the geometry).  out: a [B, T, 3, H, W] view whose samples
+    may lie further apart than dense (stride(0) >= T * 3 * H * W, the rest contiguous).  info (dict): receives form / tch / range_flag."""
+    _require_gpu(x_cl)
+    if x_cl.dim() != 5:
+        raise I2VError(f"conv_img_unit: expected [B, T, H, W, C], got {tuple(x_cl.shape)}")
+    B, T, H, W, C = x_cl.shape
+    w = np.ascontiguousarray(weight.detach().cpu().numpy() if isinstance(weight, torch.Tensor) else weight, dtype=np.float32)
+    b = np.ascontiguousarray(bias.detach().cpu().numpy() if isinstance(bias, torch.Tensor) else bias, dtype=np.float32)
+    if w.shape != (3, C, 3, 3, 3) or b.shape != (3,):
+        raise I2VError(f"conv_img_unit: expected weight [3, {C}, 3, 3, 3] and bias [3], got {w.shape} / {b.shape}")
+    if form is not None and form not in CONV_IMG_FORMS:
+        raise I2VError(f"conv_img_unit: form {form!r} (one of {CONV_IMG_FORMS} or None)")
+    if out is None:
+        out = torch.empty(B, T, 3, H, W, dtype=torch.float32, device=x_cl.device)
+    if (out.dtype != torch.float32 or out.device != x_cl.device or tuple(out.shape) != (B, T, 3, H, W) or not out[0].is_contiguous()
+            or (B > 1 and out.stride(0) < T * 3 * H * W)):
+        raise I2VError("conv_img_unit: out must be a float32 [B, T, 3, H, W] view on the input's device with dense samples")
+    bstride = out.stride(0) if B > 1 else 0
+    used, tch, flag = c_int32(-1), c_int32(0), c_int32(0)
+    with torch.cuda.device(x_cl.device):
+        _check(lib().i2v_conv_img_unit(x_cl.data_ptr(), w.ctypes.data_as(c_void_p), b.ctypes.data_as(c_void_p), B, T, H, W, C,
+                                       -1 if form is None else CONV_IMG_FORMS.index(form), out.data_ptr(), bstride, ctypes.byref(used),
+                                       ctypes.byref(tch), ctypes.byref(flag), _stream()), "i2v_conv_img_unit")
+    if info is not None:
+        info.update(form=CONV_IMG_FORMS[used.value], tch=tch.value, range_flag=flag.value)
+    return out
+
+
+def pointwise_unit(x, weight, bias=None, res=None, coef=None, rows_per_sample=None, lrelu=False, split16=True, transposed=False, info=None):
+    """``i2v_pointwise_unit``: act((x * A + B) @ weight^T + bias + res) on x [M, Cin] (device) with host ``weight`` [Cout, Cin] and ``bias``
+    [Cout]; coef [M / rows_per_sample, Cin, 2] = the (A, B) table (device).  split16: the split-fp16 GEMM, else the exact-fp32 one.
+    transposed: the output as [Cout, M].  info (dict): receives tile_n / range_flag."""
+    _require_gpu(x, res, coef)
+    M, Cin = x.shape
+    w = np.ascontiguousarray(weight.detach().cpu().numpy() if isinstance(weight, torch.Tensor) else weight, dtype=np.float32)
+    if w.ndim != 2 or w.shape[1] != Cin:
+        raise I2VError(f"pointwise_unit: expected weight [Cout, {Cin}], got {w.shape}")
+    Cout = w.shape[0]
+    b = None
+    if bias is not None:
+        b = np.ascontiguousarray(bias.detach().cpu().numpy() if isinstance(bias, torch.Tensor) else bias, dtype=np.float32)
+        if b.shape != (Cout,):
+            raise I2VError(f"pointwise_unit: expected bias [{Cout}], got {b.shape}")
+    P = M if rows_per_sample is None else int(rows_per_sample)
+    if res is not None and tuple(res.shape) != (M, Cout):
+        raise I2VError(f"pointwise_unit: expected res [{M}, {Cout}], got {tuple(res.shape)}")
+    if coef is not None and tuple(coef.shape) != ((M + P - 1) // P, Cin, 2):
+        raise I2VError(f"pointwise_unit: expected coef [{(M + P - 1) // P}, {Cin}, 2], got {tuple(coef.shape)}")
+    out = torch.empty((Cout, M) if transposed else (M, Cout), dtype=torch.float32, device=x.device)
+    tile, flag = c_int32(0), c_int32(0)
+    with torch.cuda.device(x.device):
+        _check(lib().i2v_pointwise_unit(x.data_ptr(), w.ctypes.data_as(c_void_p), None if b is None else b.ctypes.data_as(c_void_p),
+                                        None if res is None else res.data_ptr(), None if coef is None else coef.data_ptr(), out.data_ptr(), M, P,
+                                        Cin, Cout, int(bool(lrelu)), int(bool(split16)), int(bool(transposed)), ctypes.byref(tile),
+                                        ctypes.byref(flag), _stream()), "i2v_pointwise_unit")
+    if info is not None:
+        info.update(tile_n=tile.value, range_flag=flag.value)
+    return out
 
 
 class NativeMLP(_Handle):

@@ -360,9 +360,35 @@ int i2v_dec_status(i2v_dec* d, int32_t* flags, int32_t reset, void* stream);
  *    9  the (A, B) float2 table [B][n_in] handed to conv_0's operand writer (SPADE's group norm: norm(x) = x A + B)
  *   10  the (A, B) table [B][n_mid] handed to conv_1's operand writer (ADAIN: gamma norm(x) + beta = x A + B)
  *   11  the (A, B) table [B][n_in] of the learned shortcut's Norm3D (learned blocks only)
- *   12  the block input [B][T/ut][H/us][W/us][n_in] */
-#define I2V_DEC_TAP_LAST 12
+ *   12  the block input [B][T/ut][H/us][W/us][n_in]
+ *   13  SPADE's branch: the start frames resized to the level (bilinear, align_corners) as 16-channel rows [F][H][W][16], channels 3 .. 15
+ *       zero: fp32, or split-fp16 rows [8 fp16 hi | 8 fp16 lo] x 2 where the branch runs split-fp16 kernels (forms 0 .. 2 below)
+ *   14  SPADE's branch: lrelu(Conv2d(3, 128)(.)) [F][H][W][128]: fp32 (forms 0, 1, 3) or the split-fp16 direct operand (form 2), as tap 1
+ *   15  SPADE's branch, forms 0 and 1 only: the Winograd operand of tap 14, as tap 1 with T = 1 and C = 128 */
+#define I2V_DEC_TAP_LAST 15
 int i2v_dec_debug_tap(i2v_dec* d, int32_t block, int32_t which, float* dst, size_t max_floats);
+/* The form SPADE's branch of `block` took in the last forward / prepare: 0 = split-fp16 F(4,3) gamma | beta conv, 1 = split-fp16 F(2,3),
+ * 2 = direct split-fp16 (the activation handed over in the operand format by the first conv's epilogue), 3 = exact fp32; -1 = not run yet. */
+int i2v_dec_get_spade_form(i2v_dec* d, int32_t block, int32_t* form);
+
+/* Test hooks: the decoder's units outside the blocks, through the functions the decoder itself calls.  Both pack `weight` / `bias`
+ * (host, float32), run on `stream` and synchronise it before they return.
+ * i2v_conv_img_unit: conv_img (decoder.py:117-120): x channels-last [b][t][h][w][c] (device) -> tanh(Conv3d(c -> 3, 3x3x3, pad 1)) as frames
+ * [b][t][3][h][w], out_bstride floats between samples (0: dense).  weight [3][c][3][3][3], bias [3].  form: -1 = what a split-fp16
+ * (mma = 1) decoder of this output geometry runs, 0 = fused matrix-core kernel (c in 16, 32, 48, 64; h % 8 == 0, w % 32 == 0),
+ * 1 = transposed 81-column split-fp16 GEMM + gather (c >= 64; the decoder under I2V_DEC_IMG16=1), 2 = vector-ALU kernel, exact fp32
+ * (t, h, w % 8 == 0, c % 4 == 0), 3 = the generic implicit-GEMM conv, exact fp32 (t, h, w that tile into its 128-position bricks: powers of two).  A named form whose predicate refuses
+ * the geometry returns I2V_E_INVALID.  form_used: the form that ran; tch: output frames per workgroup of form 0 (else 0); range_flag:
+ * the split-fp16 forms' overflow flag after the run (all optional).
+ * i2v_pointwise_unit: out[m][cout] = act((in[m][cin] * A + B) @ weight^T + bias + res): in / res / out (device), weight [cout][cin] and
+ * bias [cout] or null (host), coef = (A, B) float2 table [m / p rows][cin] (device) or null, p = rows per sample.  split16: 1 = the
+ * split-fp16 GEMM (the decoder's shortcut in mma = 1), 0 = the exact-fp32 GEMM.  transposed (split16 only, no res / coef): out[cout][m].
+ * tile_n: columns of the 128-row tile that ran (128, 64 or 32). */
+int i2v_conv_img_unit(const float* x, const float* weight, const float* bias, int32_t b, int32_t t, int32_t h, int32_t w, int32_t c, int32_t form,
+                      float* out, int64_t out_bstride, int32_t* form_used, int32_t* tch, int32_t* range_flag, void* stream);
+int i2v_pointwise_unit(const float* in, const float* weight, const float* bias, const float* res, const float* coef, float* out, int64_t m,
+                       int64_t p, int32_t cin, int32_t cout, int32_t lrelu, int32_t split16, int32_t transposed, int32_t* tile_n,
+                       int32_t* range_flag, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Decoder sub-modules, individually callable with the reference's [B][C][T][H][W] tensors:

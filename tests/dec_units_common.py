@@ -229,23 +229,27 @@ def writer_ref(kind, x, coef, gb, ut, us, dtype=torch.float64, mutate=None):
     """The operand a writer forms, from the tapped block input / conv_0 output x [B, Tl, Hl, Wl, C], the tapped (A, B) table coef
     [B, C, 2] and the tapped maps gb [B, H, W, 2C] (None behind ADAIN): d = lrelu((x A + B) g' + beta) through the nearest map, then
     B^T along W with zero padding.  (ut = 1 on the half-rate operand of a temporal-duplication conv.)  -> (values, S) in `dtype`:
-    [B, T, H, W, C] or [B, T, P, H, J, C]; S = the same expression over absolute values."""
+    [B, T, H, W, C] or [B, T, P, H, J, C]; S = the same expression over absolute values.  coef = None (SPADE's own branch: the
+    128-channel activation goes to the Winograd operand as it is): d = x, no table, no maps, no lrelu."""
     B, Tl, Hl, Wl, C = x.shape
     T, H, W = Tl * ut, Hl * us, Wl * us
     x = x.to(dtype)
     ob1 = mutate == "upsample_off_by_one"
     xu = _nearest(_nearest(_nearest(x, 1, ut, T, ob1), 2, us, H, ob1), 3, us, W, ob1)
-    a = coef[..., 0].to(dtype).view(B, 1, 1, 1, C)
-    b = coef[..., 1].to(dtype).view(B, 1, 1, 1, C)
-    sb = b.abs()
-    if gb is not None:
-        ga, be = gb[..., :C].to(dtype).unsqueeze(1), gb[..., C:].to(dtype).unsqueeze(1)
-        sb = sb * ga.abs() + be.abs()
-        b = b * ga + be
-        a = a * ga
-    r = xu * a + b
-    d = torch.where(r >= 0, r, 0.2 * r)
-    S = xu.abs() * a.abs() + sb
+    if coef is None:
+        d, S = xu, xu.abs()
+    else:
+        a = coef[..., 0].to(dtype).view(B, 1, 1, 1, C)
+        b = coef[..., 1].to(dtype).view(B, 1, 1, 1, C)
+        sb = b.abs()
+        if gb is not None:
+            ga, be = gb[..., :C].to(dtype).unsqueeze(1), gb[..., C:].to(dtype).unsqueeze(1)
+            sb = sb * ga.abs() + be.abs()
+            b = b * ga + be
+            a = a * ga
+        r = xu * a + b
+        d = torch.where(r >= 0, r, 0.2 * r)
+        S = xu.abs() * a.abs() + sb
     if kind in ("f32", "hl16"):
         return d, S.expand_as(d)
     P = PLANES[kind]
@@ -331,7 +335,7 @@ def _corr(x, w, tpad):
 
 def conv_ref(kind, opnd, w, bias, res, rt, rs, lrelu, tdup, dtype=torch.float64, mutate=None):
     """The conv on its decoded operand (float64 [B, Ti, H, W, C] or [B, Ti, P, H, J, C]; Ti = T / 2 for tdup) with the folded
-    weights w [O, C, 3, 3, 3] float64, + bias + the residual read through the (rt, rs) nearest map, optional lrelu.
+    weights w [O, C, KT, 3, 3] float64 (KT = 3, or 1: the 2-D convs of SPADE's branch, no padding in time), + bias + the residual read through the (rt, rs) nearest map, optional lrelu.
     -> (out [B, T, H, W, O], S, S1): S = sum |A^T| sum |U||V| + |bias| + |res|, S1 = sum |A^T| sum |V| (for the weights' subnormal
     floor).  dtype = float32: the host emulation (weights rounded to fp32 as the packers do, fp32 accumulation)."""
     dev = opnd.device
@@ -356,7 +360,7 @@ def conv_ref(kind, opnd, w, bias, res, rt, rs, lrelu, tdup, dtype=torch.float64,
     Ti = x.shape[1]
     outs, Ss, S1s = [], [], []
     for s in range(nset):
-        tpad = (1, 1) if not tdup else ((1, 0) if s == 0 else (0, 1))
+        tpad = ((KT - 1) // 2, (KT - 1) // 2) if not tdup else ((1, 0) if s == 0 else (0, 1))
         if mutate == "tdup_pairs_swapped" and tdup:
             tpad = (0, 1) if s == 0 else (1, 0)
         if P:
@@ -400,13 +404,14 @@ def conv_ref(kind, opnd, w, bias, res, rt, rs, lrelu, tdup, dtype=torch.float64,
     return y, S, S1
 
 
-def conv_chain(kind, cin, tdup):
-    """Length of the fp32 accumulation chain of one output (module docstring)."""
-    kt = 2 if tdup else 3
+def conv_chain(kind, cin, tdup, kt=None):
+    """Length of the fp32 accumulation chain of one output (module docstring).  kt: temporal taps (default 3, 2 for a tdup pair; 1 for
+    the 2-D convs of SPADE's branch)."""
+    kt = kt or (2 if tdup else 3)
     if kind == "f32":
-        return (cin + 1) // 2 * 27 + 2 + 8
+        return (cin + 1) // 2 * 9 * kt + 2 + 8
     if kind == "f43_f32":
-        return (cin + 1) // 2 * 9 + 2 + 8
+        return (cin + 1) // 2 * 3 * kt + 2 + 8
     if kind == "hl16":
         return (cin + 7) // 8 * kt * 9 * 3 + 16 + 8
     if kind == "f43_one":
@@ -414,9 +419,9 @@ def conv_chain(kind, cin, tdup):
     return (cin + 7) // 8 * kt * 3 * 3 + 16 + 8
 
 
-def conv_bound(kind, cin, tdup, w, S, S1):
+def conv_bound(kind, cin, tdup, w, S, S1, kt=None):
     """Element-wise bound of a conv output (module docstring).  w: the folded weights (for the prescale exponent)."""
-    e = gamma(conv_chain(kind, cin, tdup)) * S
+    e = gamma(conv_chain(kind, cin, tdup, kt)) * S
     if kind in ("f32", "f43_f32"):
         return e + 2 * U * S
     if kind == "f43_one":
