@@ -138,11 +138,7 @@ struct StreamOrder {
         if (hipEventRecord(last_done, st) == hipSuccess) { last_stream = st; have_last = true; }
     }
 };
-// records the end of a call on its stream when the scope is left (also on the error paths: whatever was enqueued is ordered)
-struct StreamOrderMark {
-    StreamOrder* o; hipStream_t st;
-    ~StreamOrderMark() { o->exit(st); }
-};
+// (entry / exit are paired by the call's scope, i2v_handle.h: Entry::serialise)
 
 // hipFuncAttributeMaxDynamicSharedMemorySize has to be raised once PER DEVICE (every device has its own copy of the code
 // object); `done` = the call site's static bool[I2V_MAX_DEV].

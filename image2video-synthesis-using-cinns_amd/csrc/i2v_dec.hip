@@ -17,7 +17,6 @@
 // Spectral norm (W / sigma, signed sigma) is folded once at load time (decoder.py:20-25 recomputes it per call).
 #include <algorithm>
 #include <cmath>
-#include <memory>
 
 #include "i2v_dec_block.h"
 
@@ -116,6 +115,7 @@ struct i2v_dec {
     // is run again; an overflow no slot explains (SPADE's own activation, the shortcut GEMM, conv_img) switches the whole handle.
     // In-range checkpoints run exactly the mma = 1 launches.
     BlockCtx ctx;
+    int& device = ctx.device;
     Block blk[6];
     Level lvl[6];
     ConvWeights fc, zlin;
@@ -166,19 +166,18 @@ DecWs dec_ws(const i2v_dec* d, int B, int Fg = 0) {
     }
     if (d->ctx.has16() && d->ctx.img16 == 1 && conv_img_gemm_supported(d->nf)) mx_a = std::max(mx_a, (size_t)d->lvl[5].T * d->lvl[5].H * d->lvl[5].W * 81);  // conv_img's Y
     DecWs L;
-    size_t o = 0;
-    auto take = [&](size_t floats) { size_t r = o; o = align_up(o + floats * 4, 256); return r; };
-    L.xA = take(B * mx_x); L.xB = take(B * mx_x);
-    L.a = take(B * mx_a); L.dx = take(B * mx_dx);
-    L.xs_in = take(B * mx_xsin); L.xs_low = take(B * mx_xslow);
-    L.y0 = take(Fg * mx_y * 16); L.y1 = take(Fg * mx_y * 128); L.gb = take(Fg * mx_gb);
-    L.y1v = take(Fg * mx_yv * 256);  // Winograd operand V of SPADE's 128-channel activation (8 bytes per activation)
+    Carver c;
+    L.xA = c.take_floats(B * mx_x); L.xB = c.take_floats(B * mx_x);
+    L.a = c.take_floats(B * mx_a); L.dx = c.take_floats(B * mx_dx);
+    L.xs_in = c.take_floats(B * mx_xsin); L.xs_low = c.take_floats(B * mx_xslow);
+    L.y0 = c.take_floats(Fg * mx_y * 16); L.y1 = c.take_floats(Fg * mx_y * 128); L.gb = c.take_floats(Fg * mx_gb);
+    L.y1v = c.take_floats(Fg * mx_yv * 256);  // Winograd operand V of SPADE's 128-channel activation (8 bytes per activation)
     L.has_y1v = mx_yv > 0;
-    L.zl = take((size_t)B * d->Nz);
-    L.sums1 = take((size_t)B * cmax * 4); L.sums2 = take((size_t)B * cmax * 4);  // doubles: 2 per channel
-    L.sums3 = take((size_t)B * cmax * 4);   // block output statistics (sums1 / sums3 alternate as a block's input / output statistics)
-    L.coef = take((size_t)B * cmax * 2);
-    L.coef_s = take((size_t)B * cmax * 2);   // the shortcut's Norm3D coefficients when it runs on the side stream
+    L.zl = c.take_floats((size_t)B * d->Nz);
+    L.sums1 = c.take_floats((size_t)B * cmax * 4); L.sums2 = c.take_floats((size_t)B * cmax * 4);  // doubles: 2 per channel
+    L.sums3 = c.take_floats((size_t)B * cmax * 4);   // block output statistics (sums1 / sums3 alternate as a block's input / output statistics)
+    L.coef = c.take_floats((size_t)B * cmax * 2);
+    L.coef_s = c.take_floats((size_t)B * cmax * 2);   // the shortcut's Norm3D coefficients when it runs on the side stream
     {   // split-K scratch of the direct conv kernel (the tiny feature maps of head_0 / g_0): its partial copies of the output
         size_t mx = 0;
         for (int k = 0; k < 6; ++k) {
@@ -187,12 +186,12 @@ DecWs dec_ws(const i2v_dec* d, int B, int Fg = 0) {
             if (f > 1) mx = std::max(mx, (size_t)f * P * std::max(d->blk[k].n_mid, d->blk[k].n_out));
         }
         L.splitk_floats = (size_t)B * mx;
-        L.splitk = take(L.splitk_floats);
+        L.splitk = c.take_floats(L.splitk_floats);
     }
-    for (int k = 0; k < 6; ++k) L.gbs[k] = take((size_t)Fg * d->lvl[k].H * d->lvl[k].W * 2 * d->blk[k].n_in);
-    L.py0 = take(Fg * mx_y * 16); L.py1 = take(Fg * mx_y * 128); L.py1v = take(Fg * mx_yv * 256);
-    L.m6 = take(B * mx_m6);   // exact-fp32 Winograd: the six partial outputs M_x
-    L.total = o;
+    for (int k = 0; k < 6; ++k) L.gbs[k] = c.take_floats((size_t)Fg * d->lvl[k].H * d->lvl[k].W * 2 * d->blk[k].n_in);
+    L.py0 = c.take_floats(Fg * mx_y * 16); L.py1 = c.take_floats(Fg * mx_y * 128); L.py1v = c.take_floats(Fg * mx_yv * 256);
+    L.m6 = c.take_floats(B * mx_m6);   // exact-fp32 Winograd: the six partial outputs M_x
+    L.total = c.total();
     return L;
 }
 
@@ -212,47 +211,41 @@ int i2v_dec_create(const i2v_dec_cfg* cfg, i2v_dec** out) {
                     "i2v_dec_create: upsample factors must be 1, 2 or 4");
     }
     I2V_REQUIRE(cfg->mma >= 0 && cfg->mma <= 3, I2V_E_INVALID, "i2v_dec_create: unknown mma mode %d (0 fp32, 1 split-fp16, 2 auto, 3 fp16)", cfg->mma);
-    int ndev = 0;
-    I2V_HIP_CHECK(hipGetDeviceCount(&ndev));
-    I2V_REQUIRE(ndev > 0, I2V_E_HIP, "i2v_dec_create: no HIP device");
-    auto d = std::make_unique<i2v_dec>();
-    d->cfg = *cfg;
-    d->ctx.mma = cfg->mma;
-    read_switches(&d->ctx, true);
-    if (int rc = init_status(&d->ctx)) return rc;
-    const int nf = d->nf = cfg->channel_factor;
-    const char* names[6] = {"head_0", "g_0", "g_1", "g_2", "g_3", "g_4"};
-    const int cin[6] = {16, 16, 16, 8, 4, 2}, cout[6] = {16, 16, 8, 4, 2, 1};
-    int T = 1, S = 4, zoff = 0;
-    for (int k = 0; k < 6; ++k) {
-        Block& b = d->blk[k];
-        b.name = names[k];
-        b.n_in = cin[k] * nf; b.n_out = cout[k] * nf; b.n_mid = std::min(b.n_in, b.n_out);
-        b.learned = b.n_in != b.n_out;
-        int g = 16;
-        while (b.n_in % g) --g;  // normalization_layer.py:9-10
-        b.groups_spade = g;
-        b.zoff = zoff;
-        zoff += 2 * b.n_mid;
-        int ut = 1, us = 1;
-        if (k >= 1 && k <= 3) { ut = 2; us = 2; }                                  // decoder.py:102-108
-        if (k == 4) { ut = cfg->upsample_t[0]; us = cfg->upsample_s[0]; }          // :111
-        if (k == 5) { ut = cfg->upsample_t[1]; us = cfg->upsample_s[1]; }          // :114
-        T *= ut; S *= us;
-        d->lvl[k] = Level{T, S, S, ut, us};
-        init_convs(b, ut == 2);
-    }
-    d->Nz = zoff;
-    *out = d.release();
-    return I2V_OK;
+    return create_handle("i2v_dec_create", out, [&](i2v_dec* d) {
+        d->cfg = *cfg;
+        d->ctx.mma = cfg->mma;
+        read_switches(&d->ctx, true);
+        if (int rc = init_status(&d->ctx)) return rc;
+        const int nf = d->nf = cfg->channel_factor;
+        const char* names[6] = {"head_0", "g_0", "g_1", "g_2", "g_3", "g_4"};
+        const int cin[6] = {16, 16, 16, 8, 4, 2}, cout[6] = {16, 16, 8, 4, 2, 1};
+        int T = 1, S = 4, zoff = 0;
+        for (int k = 0; k < 6; ++k) {
+            Block& b = d->blk[k];
+            b.name = names[k];
+            b.n_in = cin[k] * nf; b.n_out = cout[k] * nf; b.n_mid = std::min(b.n_in, b.n_out);
+            b.learned = b.n_in != b.n_out;
+            int g = 16;
+            while (b.n_in % g) --g;  // normalization_layer.py:9-10
+            b.groups_spade = g;
+            b.zoff = zoff;
+            zoff += 2 * b.n_mid;
+            int ut = 1, us = 1;
+            if (k >= 1 && k <= 3) { ut = 2; us = 2; }                                  // decoder.py:102-108
+            if (k == 4) { ut = cfg->upsample_t[0]; us = cfg->upsample_s[0]; }          // :111
+            if (k == 5) { ut = cfg->upsample_t[1]; us = cfg->upsample_s[1]; }          // :114
+            T *= ut; S *= us;
+            d->lvl[k] = Level{T, S, S, ut, us};
+            init_convs(b, ut == 2);
+        }
+        d->Nz = zoff;
+        return I2V_OK;
+    });
 }
 
 void i2v_dec_destroy(i2v_dec* d) { delete d; }
 
-int i2v_dec_load(i2v_dec* d, const i2v_tensor* tensors, int32_t n_tensors) {
-    I2V_REQUIRE(d && tensors && n_tensors > 0, I2V_E_INVALID, "i2v_dec_load: null argument");
-    I2V_REQUIRE_DEVICE(d->ctx.device, "i2v_dec_load");
-    StateDict sd(tensors, n_tensors);
+static int dec_pack(i2v_dec* d, const StateDict& sd) {
     const int nf = d->nf, zd = d->cfg.z_dim;
     const bool sn = d->cfg.spectral_norm != 0;
     int rc;
@@ -310,8 +303,11 @@ int i2v_dec_load(i2v_dec* d, const i2v_tensor* tensors, int32_t n_tensors) {
         if (!w || !b) return I2V_E_MISSING;
         if ((rc = d->conv_img.pack(w, b, nf, d->lvl[5].T, d->lvl[5].H, d->lvl[5].W, d->ctx.has16(), d->ctx.img16))) return rc;
     }
-    d->loaded = true;
     return I2V_OK;
+}
+
+int i2v_dec_load(i2v_dec* d, const i2v_tensor* tensors, int32_t n_tensors) {
+    return load_handle("i2v_dec_load", d, tensors, n_tensors, dec_pack);
 }
 
 int i2v_dec_out_shape(const i2v_dec* d, int32_t* t, int32_t* h, int32_t* w) {
@@ -417,14 +413,15 @@ int i2v_dec_get_spade_form(i2v_dec* d, int32_t block, int32_t* form) {
 // caller enqueued on `st` before -- the start frames, an earlier forward on this workspace -- is complete before the side stream
 // touches the workspace); one event per level for the consumer.  *done = false: not possible here (graph capture on `st`, debug tap
 // active, overlap switched off) -- the caller runs the branches inline.
-static int fork_spade(i2v_dec* d, const DecWs& L, char* ws, const float* img, int img_h, int img_w, long ibs, int B, hipStream_t st, bool* done) {
+static int fork_spade(i2v_dec* d, const DecWs& L, void* ws, const float* img, int img_h, int img_w, long ibs, int B, hipStream_t st, bool* done) {
     *done = false;
     if (!d->ctx.overlap || d->ctx.tap_dst) return I2V_OK;
     if (stream_is_capturing(st)) return I2V_OK;
     SideStream& sd = d->side;
     if (sd.stream && sd.stream == st) return I2V_OK;   // the caller runs this call ON the shared side stream: nothing to fork to
     if (int rco = sd.open()) return rco;
-    auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    float* const y1v = L.has_y1v ? Carver::at(ws, L.y1v) : nullptr;
+    float* const py1v = L.has_y1v ? Carver::at(ws, L.py1v) : nullptr;
     I2V_HIP_CHECK(hipEventRecord(sd.ev_fork, st));
     I2V_HIP_CHECK(hipStreamWaitEvent(sd.stream, sd.ev_fork, 0));
     int rc = I2V_OK;
@@ -434,11 +431,11 @@ static int fork_spade(i2v_dec* d, const DecWs& L, char* ws, const float* img, in
     // later levels have the first two blocks' time to get through.  (Own side stream: everything on it, as before.)
     const int k0 = sd.owned ? 0 : 2;
     for (int k = 0; k < k0 && !rc; ++k) {
-        rc = spade_branch(&d->ctx, d->blk[k], d->lvl[k], img, img_h, img_w, ibs, B, F(L.y0), F(L.y1), L.has_y1v ? F(L.y1v) : nullptr, F(L.gbs[k]), st, k);
+        rc = spade_branch(&d->ctx, d->blk[k], d->lvl[k], img, img_h, img_w, ibs, B, Carver::at(ws, L.y0), Carver::at(ws, L.y1), y1v, Carver::at(ws, L.gbs[k]), st, k);
         if (!rc && hipEventRecord(sd.ev_lvl[k], st) != hipSuccess) rc = I2V_E_HIP;
     }
     for (int k = k0; k < 6 && !rc; ++k) {
-        rc = spade_branch(&d->ctx, d->blk[k], d->lvl[k], img, img_h, img_w, ibs, B, F(L.py0), F(L.py1), L.has_y1v ? F(L.py1v) : nullptr, F(L.gbs[k]), sd.stream, k);
+        rc = spade_branch(&d->ctx, d->blk[k], d->lvl[k], img, img_h, img_w, ibs, B, Carver::at(ws, L.py0), Carver::at(ws, L.py1), py1v, Carver::at(ws, L.gbs[k]), sd.stream, k);
         if (!rc && hipEventRecord(sd.ev_lvl[k], sd.stream) != hipSuccess) rc = I2V_E_HIP;
     }
     // (an error must not leave the caller's stream ahead of work this call put on the side stream)
@@ -462,8 +459,8 @@ static int dec_forward_once(i2v_dec* d, const float* img, int32_t img_h, int32_t
                             int64_t out_bstride, void* workspace, size_t workspace_bytes, int32_t batch, int K, void* stream) {
     Prepared prep;   // dropped before anything is checked: Prepared's rule
     if (d) { prep = d->prep; d->prep.drop(); }
-    I2V_REQUIRE(d && d->loaded, I2V_E_STATE, "i2v_dec_forward: weights not loaded");
-    if (int rc0 = check_entry(&d->ctx, "i2v_dec_forward")) return rc0;
+    Entry sc;   // (declared before Join: the end of the call is recorded after the join)
+    if (int rc0 = check_entry(sc, d, Entry::NEEDS_WEIGHTS | Entry::NULL_IS_UNLOADED, "i2v_dec_forward")) return rc0;
     I2V_REQUIRE(img && motion && out && workspace && batch > 0 && img_h > 0 && img_w > 0, I2V_E_INVALID,
                 "i2v_dec_forward: null argument or bad size");
     const int B = batch;
@@ -479,17 +476,15 @@ static int dec_forward_once(i2v_dec* d, const float* img, int32_t img_h, int32_t
         if (out_bstride == 0) out_bstride = out_dense;
     }
     const DecWs L = dec_ws(d, B, Fr);
-    I2V_REQUIRE(workspace_bytes >= L.total, I2V_E_WORKSPACE, "i2v_dec_forward: workspace %zu < required %zu", workspace_bytes,
-                L.total);
+    I2V_REQUIRE_WORKSPACE(workspace_bytes, L.total, "i2v_dec_forward");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (int rco = d->order.entry(st)) return rco;
-    StreamOrderMark mark{&d->order, st};   // (declared before Join: runs after the join)
-    char* ws = static_cast<char*>(workspace);
-    auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-    float *xA = F(L.xA), *xB = F(L.xB), *a = F(L.a), *dx = F(L.dx), *xs_in = F(L.xs_in), *xs_low = F(L.xs_low);
-    float *y0 = F(L.y0), *y1 = F(L.y1), *gb = F(L.gb), *zl = F(L.zl), *coef = F(L.coef);
-    double* sums1 = reinterpret_cast<double*>(ws + L.sums1);
-    double* sums2 = reinterpret_cast<double*>(ws + L.sums2);
+    if (int rco = sc.serialise(d->order, st)) return rco;
+    void* const ws = workspace;
+    float *xA = Carver::at(ws, L.xA), *xB = Carver::at(ws, L.xB), *a = Carver::at(ws, L.a), *dx = Carver::at(ws, L.dx);
+    float *xs_in = Carver::at(ws, L.xs_in), *xs_low = Carver::at(ws, L.xs_low), *y0 = Carver::at(ws, L.y0), *y1 = Carver::at(ws, L.y1);
+    float *gb = Carver::at(ws, L.gb), *zl = Carver::at(ws, L.zl), *coef = Carver::at(ws, L.coef);
+    double* sums1 = Carver::at<double>(ws, L.sums1);
+    double* sums2 = Carver::at<double>(ws, L.sums2);
     int rc;
     // x = fc(motion).reshape(B, 16nf, 1, 4, 4) (decoder.py:99) -- written channels-last [B][1][4][4][16nf]
     if ((rc = conv_forward(d->fc, motion, d->cfg.z_dim, xA, nullptr, 1, 1, B, 1, 1, 1, EPI_NONE, st))) return rc;
@@ -498,7 +493,7 @@ static int dec_forward_once(i2v_dec* d, const float* img, int32_t img_h, int32_t
     float* x = xA;
     float* xn = xB;
     bool x_stats_ready = false;
-    double* sums3 = reinterpret_cast<double*>(ws + L.sums3);
+    double* sums3 = Carver::at<double>(ws, L.sums3);
     // SPADE branches computed ahead by i2v_dec_prepare for exactly these start frames (same pointer, batch, size, workspace)?
     bool prepared = prep.matches(img, B, K, img_h, img_w, img_bstride, workspace);
     // Prepared on the side stream (i2v_dec_prepare), or not prepared at all: then compute the maps on the handle's side stream now,
@@ -539,10 +534,10 @@ static int dec_forward_once(i2v_dec* d, const float* img, int32_t img_h, int32_t
             const int n = std::min(nsub, B - s0);
             const int f0 = s0 / K;   // the sub-batch's first start frame (K = 1: s0)
             BlockBufs bufs{a, dx, xs_in, xs_low, y0, y1, gb, coef, s_in + (size_t)s0 * b.n_in * 2, sums2, s_out + (size_t)s0 * b.n_out * 2,
-                           F(L.splitk), L.splitk_floats, L.has_y1v ? F(L.y1v) : nullptr,
-                           prepared ? F(L.gbs[k]) + (size_t)f0 * l.H * l.W * 2 * b.n_in : nullptr,
-                           d->ctx.has32() && d->ctx.wino32 ? F(L.m6) : nullptr,
-                           forked && nsub == B && d->ctx.overlap >= 1 && !d->ctx.no_side_shortcut ? d->side.stream : nullptr, F(L.coef_s),
+                           Carver::at(ws, L.splitk), L.splitk_floats, L.has_y1v ? Carver::at(ws, L.y1v) : nullptr,
+                           prepared ? Carver::at(ws, L.gbs[k]) + (size_t)f0 * l.H * l.W * 2 * b.n_in : nullptr,
+                           d->ctx.has32() && d->ctx.wino32 ? Carver::at(ws, L.m6) : nullptr,
+                           forked && nsub == B && d->ctx.overlap >= 1 && !d->ctx.no_side_shortcut ? d->side.stream : nullptr, Carver::at(ws, L.coef_s),
                            d->side.ev_x[k], d->side.ev_s[k], GbRows{K, s0 % K}};
             bool ready = x_stats_ready;
             if ((rc = block_forward(&d->ctx, k, d->blk[k], l, x + (size_t)s0 * Pl * b.n_in, xn + (size_t)s0 * P * b.n_out,
@@ -639,18 +634,16 @@ int i2v_dec_fallback_layers(i2v_dec* d, int32_t* mask, int32_t* reruns) {
 // batch = samples of the forward this prepares, K = realizations per start frame: the branches run for the batch / K frames of img
 static int dec_prepare(i2v_dec* d, const float* img, int32_t img_h, int32_t img_w, void* workspace, size_t workspace_bytes, int32_t batch,
                        int K, void* stream) {
-    I2V_REQUIRE(d && d->loaded, I2V_E_STATE, "i2v_dec_prepare: weights not loaded");
-    if (int rc0 = check_entry(&d->ctx, "i2v_dec_prepare")) return rc0;
+    Entry sc;
+    if (int rc0 = check_entry(sc, d, Entry::NEEDS_WEIGHTS | Entry::NULL_IS_UNLOADED, "i2v_dec_prepare")) return rc0;
     I2V_REQUIRE(img && workspace && batch > 0 && img_h > 0 && img_w > 0, I2V_E_INVALID, "i2v_dec_prepare: null argument or bad size");
     I2V_REQUIRE(K >= 1 && batch % K == 0, I2V_E_INVALID, "i2v_dec_prepare: %d samples are not a multiple of %d realizations", batch, K);
     const int B = batch, Fr = batch / K;
     const DecWs L = dec_ws(d, B, Fr);
-    I2V_REQUIRE(workspace_bytes >= L.total, I2V_E_WORKSPACE, "i2v_dec_prepare: workspace %zu < required %zu", workspace_bytes, L.total);
+    I2V_REQUIRE_WORKSPACE(workspace_bytes, L.total, "i2v_dec_prepare");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (int rco = d->order.entry(st)) return rco;
-    StreamOrderMark mark{&d->order, st};
-    char* ws = static_cast<char*>(workspace);
-    auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    if (int rco = sc.serialise(d->order, st)) return rco;
+    void* const ws = workspace;
     // an earlier forked prepare that was never consumed may have been given ANOTHER workspace (or start frames the caller has
     // released since): `st` joins it before this prepare replaces it
     if (d->side.unjoined && (d->prep.img == nullptr || d->prep.ws != workspace))
@@ -662,7 +655,8 @@ static int dec_prepare(i2v_dec* d, const float* img, int32_t img_h, int32_t img_
     if (int rc = fork_spade(d, L, ws, img, img_h, img_w, 0, Fr, st, &forked)) return rc;
     if (!forked)
         for (int k = 0; k < 6; ++k)
-            if (int rc = spade_branch(&d->ctx, d->blk[k], d->lvl[k], img, img_h, img_w, 0, Fr, F(L.py0), F(L.py1), L.has_y1v ? F(L.py1v) : nullptr, F(L.gbs[k]), st, k))
+            if (int rc = spade_branch(&d->ctx, d->blk[k], d->lvl[k], img, img_h, img_w, 0, Fr, Carver::at(ws, L.py0), Carver::at(ws, L.py1), L.has_y1v ? Carver::at(ws, L.py1v) : nullptr,
+                                      Carver::at(ws, L.gbs[k]), st, k))
                 return rc;
     d->prep = Prepared{img, B, K, img_h, img_w, (long)3 * img_h * img_w, workspace, forked};
     return I2V_OK;
@@ -689,8 +683,7 @@ int i2v_dec_prepare_cancel(i2v_dec* d) {
 }
 
 int i2v_dec_set_side_stream(i2v_dec* d, void* side_stream) {
-    I2V_REQUIRE(d, I2V_E_INVALID, "i2v_dec_set_side_stream: null handle");
-    I2V_REQUIRE_DEVICE(d->ctx.device, "i2v_dec_set_side_stream");
+    I2V_ENTER(sc, d, 0, "i2v_dec_set_side_stream");
     hipStream_t ns = static_cast<hipStream_t>(side_stream);
     SideStream& sd = d->side;
     if (sd.stream && sd.stream == ns && !sd.owned) return I2V_OK;
@@ -707,8 +700,7 @@ int i2v_dec_set_side_stream(i2v_dec* d, void* side_stream) {
 }
 
 int i2v_dec_join(i2v_dec* d, void* stream) {
-    I2V_REQUIRE(d, I2V_E_INVALID, "i2v_dec_join: null handle");
-    I2V_REQUIRE_DEVICE(d->ctx.device, "i2v_dec_join");
+    I2V_ENTER(sc, d, 0, "i2v_dec_join");
     hipStream_t st = static_cast<hipStream_t>(stream);
     I2V_REQUIRE(!stream_is_capturing(st), I2V_E_STATE, "i2v_dec_join: the stream is capturing a graph (join before the capture begins)");
     d->prep.drop();

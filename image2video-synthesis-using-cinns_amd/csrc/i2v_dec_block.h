@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "i2v_dec_writers.h"
+#include "i2v_handle.h"
 
 namespace i2v {
 
@@ -77,7 +78,7 @@ struct BlockCtx {
     int sub = 0;   // samples per sub-batch of the last two levels (env I2V_DEC_SUB; 0: the whole batch per launch)
     int overlap = 1;            // env I2V_DEC_OVERLAP=0: no side stream (i2v_dec.hip: SideStream)
     int no_side_shortcut = 0;   // env I2V_DEC_OVERLAP=2: branches on the side stream, shortcuts inline (A/B of the two halves)
-    int device = 0;             // the device the packed weights live on
+    int device = 0;             // the device the packed weights live on (the handle's `device` is a reference to it)
     int* status_dev = nullptr;  // sticky range flag of the hl16 producers (device) ...
     int* status_host = nullptr; // ... and its pinned host mirror, refreshed asynchronously at the end of every forward
     // debug tap: copy one intermediate (channels-last) of one block out of the workspace during forward
@@ -143,6 +144,12 @@ int pack_spade(const StateDict& sd, const std::string& p, Block& b, bool gb16, b
 void read_switches(BlockCtx* d, bool whole);
 void init_convs(Block& b, bool tdup);
 int init_status(BlockCtx* d);
-int check_entry(BlockCtx* d, const char* what);
+int check_range(const BlockCtx* d, const char* what);
+// the entry scope of a decoder / block call that enqueues work: Entry::check (handle, device, weights), then the sticky range flag
+template <class H>
+int check_entry(Entry& sc, const H* h, unsigned flags, const char* what) {
+    if (int rc = sc.check(h, flags, what)) return rc;
+    return check_range(&h->ctx, what);
+}
 
 }  // namespace i2v

@@ -387,9 +387,8 @@ void init_convs(Block& b, bool tdup) {
     b.conv[0].tdup = tdup;
 }
 
-// device binding + the sticky range flag (device word and pinned host mirror)
+// the sticky range flag (device word and pinned host mirror); create_handle has bound the device
 int init_status(BlockCtx* d) {
-    I2V_HIP_CHECK(hipGetDevice(&d->device));
     { const char* zp = nullptr; if (int rcz = zero_page(&zp)) return rcz; }  // the conv kernels' zero page: allocated here, not inside a forward
     I2V_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d->status_dev), I2V_STATUS_WORDS * sizeof(int)));   // [0] flags, [1..] underflow maxima
     I2V_HIP_CHECK(hipMemset(d->status_dev, 0, I2V_STATUS_WORDS * sizeof(int)));
@@ -398,10 +397,9 @@ int init_status(BlockCtx* d) {
     return I2V_OK;
 }
 
-// entry check of every call that enqueues work: right device, and no overflow reported by an earlier call
-int check_entry(BlockCtx* d, const char* what) {
-    I2V_REQUIRE_DEVICE(d->device, what);
-    I2V_REQUIRE(!(*static_cast<volatile int*>(d->status_host) & 1), I2V_E_RANGE,
+// behind Entry::check in every call that enqueues work (check_entry): no overflow reported by an earlier call
+int check_range(const BlockCtx* d, const char* what) {
+    I2V_REQUIRE(!(*static_cast<volatile const int*>(d->status_host) & 1), I2V_E_RANGE,
                 "%s: an earlier call on this handle produced activations outside the fp16 range of the split-fp16 operand "
                 "format (|x| > 65504 or non-finite); its output is invalid.  Use the exact-fp32 mode (mma = 0 / I2V_DEC_MMA=0) "
                 "for this checkpoint, or clear the flag with i2v_dec_status(reset = 1)", what);

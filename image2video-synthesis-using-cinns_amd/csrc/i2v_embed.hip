@@ -11,9 +11,9 @@
 // elementwise pass driven by per-(b,c) (A,B) pairs (InstanceNorm: from fused fp64 statistics; BatchNorm: constants folded
 // at load).
 #include <algorithm>
-#include <memory>
 
 #include "i2v_conv.h"
+#include "i2v_handle.h"
 
 namespace i2v {
 
@@ -152,15 +152,14 @@ struct EmbWs { size_t img, buf[5], sums, coef, pooled, total; size_t bufsz; };
 
 EmbWs emb_ws(int B, int H, int W) {
     EmbWs L;
-    size_t o = 0;
-    auto take = [&](size_t floats) { size_t r = o; o = align_up(o + floats * 4, 256); return r; };
+    Carver c;
     L.bufsz = (size_t)B * H * W * 16;  // = B*(H/2)*(W/2)*64 = B*(H/4)*(W/4)*256: the largest activation
-    L.img = take((size_t)B * H * W * 16);
-    for (auto& b : L.buf) b = take(L.bufsz);
-    L.sums = take((size_t)B * 2048 * 4);
-    L.coef = take((size_t)B * 2048 * 2);
-    L.pooled = take((size_t)B * 2048);
-    L.total = o;
+    L.img = c.take_floats((size_t)B * H * W * 16);
+    for (auto& b : L.buf) b = c.take_floats(L.bufsz);
+    L.sums = c.take_floats((size_t)B * 2048 * 4);
+    L.coef = c.take_floats((size_t)B * 2048 * 2);
+    L.pooled = c.take_floats((size_t)B * 2048);
+    L.total = c.total();
     return L;
 }
 
@@ -190,24 +189,17 @@ extern "C" {
 
 int i2v_embedder_create(int32_t z_dim, int32_t use_batchnorm, i2v_embedder** out) {
     I2V_REQUIRE(out && z_dim > 0, I2V_E_INVALID, "i2v_embedder_create: bad argument");
-    int ndev = 0;
-    I2V_HIP_CHECK(hipGetDeviceCount(&ndev));
-    I2V_REQUIRE(ndev > 0, I2V_E_HIP, "i2v_embedder_create: no HIP device");
-    auto e = std::make_unique<i2v_embedder>();
-    e->E = z_dim;
-    e->bn = use_batchnorm ? 1 : 0;
-    I2V_HIP_CHECK(hipGetDevice(&e->device));
-    { const char* zp = nullptr; if (int rcz = zero_page(&zp)) return rcz; }  // allocated here, not inside a forward
-    *out = e.release();
-    return I2V_OK;
+    return create_handle("i2v_embedder_create", out, [&](i2v_embedder* e) {
+        e->E = z_dim;
+        e->bn = use_batchnorm ? 1 : 0;
+        const char* zp = nullptr;
+        return zero_page(&zp);  // allocated here, not inside a forward
+    });
 }
 
 void i2v_embedder_destroy(i2v_embedder* e) { delete e; }
 
-int i2v_embedder_load(i2v_embedder* e, const i2v_tensor* tensors, int32_t n_tensors) {
-    if (e) I2V_REQUIRE_DEVICE(e->device, "i2v_embedder_load");
-    I2V_REQUIRE(e && tensors && n_tensors > 0, I2V_E_INVALID, "i2v_embedder_load: null argument");
-    StateDict sd(tensors, n_tensors);
+static int embedder_pack(i2v_embedder* e, const StateDict& sd) {
     int rc;
     const float* w = sd.f32("model.conv1.weight", 64 * 3 * 49);
     if (!w) return I2V_E_MISSING;
@@ -252,9 +244,11 @@ int i2v_embedder_load(i2v_embedder* e, const i2v_tensor* tensors, int32_t n_tens
     const float* fw = sd.f32("model.fc.sub_layers.0.weight", (int64_t)2 * e->E * 2048);
     const float* fb = sd.f32("model.fc.sub_layers.0.bias", (int64_t)2 * e->E);
     if (!fw || !fb) return I2V_E_MISSING;
-    if ((rc = e->fc.pack(fw, fb, e->E, 2048, 1, 1, 1, 1.0))) return rc;
-    e->loaded = true;
-    return I2V_OK;
+    return e->fc.pack(fw, fb, e->E, 2048, 1, 1, 1, 1.0);
+}
+
+int i2v_embedder_load(i2v_embedder* e, const i2v_tensor* tensors, int32_t n_tensors) {
+    return load_handle("i2v_embedder_load", e, tensors, n_tensors, embedder_pack);
 }
 
 size_t i2v_embedder_workspace_bytes(const i2v_embedder* e, int32_t batch, int32_t h, int32_t w) {
@@ -264,29 +258,24 @@ size_t i2v_embedder_workspace_bytes(const i2v_embedder* e, int32_t batch, int32_
 
 int i2v_embedder_forward(i2v_embedder* e, const float* img, int32_t h, int32_t w, float* embed, void* workspace,
                          size_t workspace_bytes, int32_t batch, void* stream) {
-    if (e) I2V_REQUIRE_DEVICE(e->device, "i2v_embedder_forward");
-    I2V_REQUIRE(e && e->loaded, I2V_E_STATE, "i2v_embedder_forward: weights not loaded");
+    I2V_ENTER(sc, e, Entry::NEEDS_WEIGHTS | Entry::NULL_IS_UNLOADED, "i2v_embedder_forward");
     I2V_REQUIRE(img && embed && workspace && batch > 0, I2V_E_INVALID, "i2v_embedder_forward: null argument");
     I2V_REQUIRE(h >= 64 && w >= 64 && (h & (h - 1)) == 0 && (w & (w - 1)) == 0, I2V_E_INVALID,
                 "i2v_embedder_forward: image size %dx%d must be a power of two >= 64", h, w);
     const int B = batch;
     const EmbWs L = emb_ws(B, h, w);
-    I2V_REQUIRE(workspace_bytes >= L.total, I2V_E_WORKSPACE, "i2v_embedder_forward: workspace %zu < required %zu", workspace_bytes,
-                L.total);
+    I2V_REQUIRE_WORKSPACE(workspace_bytes, L.total, "i2v_embedder_forward");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (int rco = e->order.entry(st)) return rco;
-    StreamOrderMark mark{&e->order, st};   // records the end of this forward on its stream (also on the error paths)
-    char* ws = static_cast<char*>(workspace);
-    auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    if (int rco = sc.serialise(e->order, st)) return rco;
     float* buf[5];
-    for (int i = 0; i < 5; ++i) buf[i] = F(L.buf[i]);
-    double* sums = reinterpret_cast<double*>(ws + L.sums);
-    float* coef = F(L.coef);
+    for (int i = 0; i < 5; ++i) buf[i] = Carver::at(workspace, L.buf[i]);
+    double* sums = Carver::at<double>(workspace, L.sums);
+    float *coef = Carver::at(workspace, L.coef), *img16 = Carver::at(workspace, L.img), *pooled = Carver::at(workspace, L.pooled);
     int rc;
     // stem: conv1 7x7 s2 -> norm -> ReLU -> MaxPool 3x3 s2
-    if ((rc = resize_forward(img, F(L.img), B, h, w, h, w, st))) return rc;  // NCHW -> channels-last, 3 -> 16 zero-padded
+    if ((rc = resize_forward(img, img16, B, h, w, h, w, st))) return rc;  // NCHW -> channels-last, 3 -> 16 zero-padded
     int H = h / 2, W = w / 2;
-    if ((rc = conv_forward(e->stem, F(L.img), 16, buf[0], nullptr, 1, 1, B, 1, H, W, EPI_NONE, st, nullptr, 2))) return rc;
+    if ((rc = conv_forward(e->stem, img16, 16, buf[0], nullptr, 1, 1, B, 1, H, W, EPI_NONE, st, nullptr, 2))) return rc;
     if ((rc = norm_act(e, e->nstem, buf[0], nullptr, buf[1], B, (long)H * W, 64, true, sums, coef, st))) return rc;
     {
         const long tot = (long)B * (H / 2) * (W / 2) * 16;
@@ -323,10 +312,10 @@ int i2v_embedder_forward(i2v_embedder* e, const float* img, int32_t h, int32_t w
     }
     // AdaptiveAvgPool2d((1,1)) then fc (first E output channels = the mean of the posterior)
     if ((rc = stats_forward(x, sums, B, (long)H * W, C, st))) return rc;
-    hipLaunchKernelGGL(mean_from_sums_kernel, dim3((unsigned)(((long)B * C + 255) / 256)), dim3(256), 0, st, sums, F(L.pooled), (long)B * C,
+    hipLaunchKernelGGL(mean_from_sums_kernel, dim3((unsigned)(((long)B * C + 255) / 256)), dim3(256), 0, st, sums, pooled, (long)B * C,
                        1.0 / ((double)H * W));
     I2V_HIP_CHECK(hipGetLastError());
-    return conv_forward(e->fc, F(L.pooled), C, embed, nullptr, 1, 1, B, 1, 1, 1, EPI_NONE, st);
+    return conv_forward(e->fc, pooled, C, embed, nullptr, 1, 1, B, 1, 1, 1, EPI_NONE, st);
 }
 
 }  // extern "C"

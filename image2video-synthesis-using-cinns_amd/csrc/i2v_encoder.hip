@@ -12,9 +12,9 @@
 // ReLU (+ residual) is one elementwise pass over channels-last activations driven by per-(b,c) (A,B) pairs from fp64
 // statistics; it emits fp32 (residuals) and / or the split-fp16 operand format (next conv).  conv_mu | conv_var: one GEMM.
 #include <algorithm>
-#include <memory>
 
 #include "i2v_conv.h"
+#include "i2v_handle.h"
 
 namespace i2v {
 
@@ -206,14 +206,13 @@ EncWs enc_ws(const i2v_encoder3d* e, int B, int T, int H, int W) {
         mx = std::max(mx, (size_t)t * h * w * e->cfg.channels[l + 1]);
     }
     EncWs L;
-    size_t o = 0;
-    auto take = [&](size_t floats) { size_t r = o; o = align_up(o + floats * 4, 256); return r; };
-    for (auto& b : L.buf) b = take((size_t)B * mx);
-    for (auto& b : L.h16) b = take((size_t)B * mx);
-    L.sums = take((size_t)B * 1024 * 4);
-    L.coef = take((size_t)B * 1024 * 2);
-    L.ml = take((size_t)B * 2 * e->cfg.z_dim);
-    L.total = o;
+    Carver c;
+    for (auto& b : L.buf) b = c.take_floats((size_t)B * mx);
+    for (auto& b : L.h16) b = c.take_floats((size_t)B * mx);
+    L.sums = c.take_floats((size_t)B * 1024 * 4);
+    L.coef = c.take_floats((size_t)B * 1024 * 2);
+    L.ml = c.take_floats((size_t)B * 2 * e->cfg.z_dim);
+    L.total = c.total();
     return L;
 }
 
@@ -248,23 +247,16 @@ int i2v_encoder3d_create(const i2v_encoder3d_cfg* cfg, i2v_encoder3d** out) {
         I2V_REQUIRE(!(cfg->stride_s[i] == 1 && cfg->stride_t[i] == 2 && cfg->channels[i] == cfg->channels[i + 1]), I2V_E_INVALID,
                     "i2v_encoder3d_create: layer %d has stride_t 2 with stride_s 1 and equal widths (%d): no downsample branch exists "
                     "for its half-rate residual", i, cfg->channels[i]);
-    int ndev = 0;
-    I2V_HIP_CHECK(hipGetDeviceCount(&ndev));
-    I2V_REQUIRE(ndev > 0, I2V_E_HIP, "i2v_encoder3d_create: no HIP device");
-    auto e = std::make_unique<i2v_encoder3d>();
-    e->cfg = *cfg;
-    I2V_HIP_CHECK(hipGetDevice(&e->device));
-    { const char* zp = nullptr; if (int rcz = zero_page(&zp)) return rcz; }  // allocated here, not inside a forward
-    *out = e.release();
-    return I2V_OK;
+    return create_handle("i2v_encoder3d_create", out, [&](i2v_encoder3d* e) {
+        e->cfg = *cfg;
+        const char* zp = nullptr;
+        return zero_page(&zp);  // allocated here, not inside a forward
+    });
 }
 
 void i2v_encoder3d_destroy(i2v_encoder3d* e) { delete e; }
 
-int i2v_encoder3d_load(i2v_encoder3d* e, const i2v_tensor* tensors, int32_t n_tensors) {
-    if (e) I2V_REQUIRE_DEVICE(e->device, "i2v_encoder3d_load");
-    I2V_REQUIRE(e && tensors && n_tensors > 0, I2V_E_INVALID, "i2v_encoder3d_load: null argument");
-    StateDict sd(tensors, n_tensors);
+static int encoder3d_pack(i2v_encoder3d* e, const StateDict& sd) {
     const int* ch = e->cfg.channels;
     int rc;
     {   // conv1.weight [c0][3][3][7][7] -> [tap][cin][c0]
@@ -333,8 +325,11 @@ int i2v_encoder3d_load(i2v_encoder3d* e, const i2v_tensor* tensors, int32_t n_te
             }
         if ((rc = e->head.pack(w.data(), bias.data(), 2 * z, 16 * c4, 1, 1, 1, 1.0))) return rc;
     }
-    e->loaded = true;
     return I2V_OK;
+}
+
+int i2v_encoder3d_load(i2v_encoder3d* e, const i2v_tensor* tensors, int32_t n_tensors) {
+    return load_handle("i2v_encoder3d_load", e, tensors, n_tensors, encoder3d_pack);
 }
 
 size_t i2v_encoder3d_workspace_bytes(const i2v_encoder3d* e, int32_t batch, int32_t t, int32_t h, int32_t w) {
@@ -344,22 +339,19 @@ size_t i2v_encoder3d_workspace_bytes(const i2v_encoder3d* e, int32_t batch, int3
 
 int i2v_encoder3d_forward(i2v_encoder3d* e, const float* x, int32_t t, int32_t h, int32_t w, const float* eps, float* sample,
                           float* mu, float* logvar, void* workspace, size_t workspace_bytes, int32_t batch, void* stream) {
-    if (e) I2V_REQUIRE_DEVICE(e->device, "i2v_encoder3d_forward");
-    I2V_REQUIRE(e && e->loaded, I2V_E_STATE, "i2v_encoder3d_forward: weights not loaded");
+    I2V_ENTER(sc, e, Entry::NEEDS_WEIGHTS | Entry::NULL_IS_UNLOADED, "i2v_encoder3d_forward");
     I2V_REQUIRE(x && mu && logvar && workspace && batch > 0 && t >= 1, I2V_E_INVALID, "i2v_encoder3d_forward: bad argument");
     I2V_REQUIRE(!sample || eps, I2V_E_INVALID, "i2v_encoder3d_forward: a sample needs eps");
     I2V_REQUIRE(h >= 64 && w >= 64 && (h & (h - 1)) == 0 && (w & (w - 1)) == 0, I2V_E_INVALID,
                 "i2v_encoder3d_forward: frame size %dx%d must be a power of two >= 64", h, w);
     const int B = batch;
     const EncWs L = enc_ws(e, B, t, h, w);
-    I2V_REQUIRE(workspace_bytes >= L.total, I2V_E_WORKSPACE, "i2v_encoder3d_forward: workspace %zu < required %zu", workspace_bytes,
-                L.total);
+    I2V_REQUIRE_WORKSPACE(workspace_bytes, L.total, "i2v_encoder3d_forward");
     hipStream_t st = static_cast<hipStream_t>(stream);
     char* ws = static_cast<char*>(workspace);
-    auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-    float *b0 = F(L.buf[0]), *b1 = F(L.buf[1]), *b2 = F(L.buf[2]), *b3 = F(L.buf[3]);
-    double* sums = reinterpret_cast<double*>(ws + L.sums);
-    float* coef = F(L.coef);
+    float *b0 = Carver::at(ws, L.buf[0]), *b1 = Carver::at(ws, L.buf[1]), *b2 = Carver::at(ws, L.buf[2]), *b3 = Carver::at(ws, L.buf[3]);
+    double* sums = Carver::at<double>(ws, L.sums);
+    float *coef = Carver::at(ws, L.coef), *ml = Carver::at(ws, L.ml);
     int rc;
     int T = (t + 2 - 3) / 2 + 1, H = h / 2, W = w / 2, C = e->cfg.channels[0];
     I2V_REQUIRE((T & (T - 1)) == 0, I2V_E_INVALID, "i2v_encoder3d_forward: %d input frames give %d stem frames (need a power of two)", t, T);
@@ -420,8 +412,8 @@ int i2v_encoder3d_forward(i2v_encoder3d* e, const float* x, int32_t t, int32_t h
         std::swap(x16, y16);
         T = To; H = Ho; W = Wo; C = b.planes;
     }
-    if ((rc = conv_forward(e->head, xcur, 16 * C, F(L.ml), nullptr, 1, 1, B, 1, 1, 1, EPI_NONE, st))) return rc;
-    hipLaunchKernelGGL(reparam_kernel, dim3((B * e->cfg.z_dim + 255) / 256), dim3(256), 0, st, F(L.ml), eps, sample, mu, logvar, B,
+    if ((rc = conv_forward(e->head, xcur, 16 * C, ml, nullptr, 1, 1, B, 1, 1, 1, EPI_NONE, st))) return rc;
+    hipLaunchKernelGGL(reparam_kernel, dim3((B * e->cfg.z_dim + 255) / 256), dim3(256), 0, st, ml, eps, sample, mu, logvar, B,
                        e->cfg.z_dim);
     I2V_HIP_CHECK(hipGetLastError());
     return I2V_OK;

@@ -34,13 +34,12 @@
 //                        as a lane permute :152-154, ActNorm modules.py:80/100, InvLeakyRelu :180-187, half swap),
 //                        then the NEXT half-step's first Linear (K = the 32 state channels just produced).
 //   (flow_linear_kernel in i2v_linear.h serves the stand-alone MLP / Linear entry points.)
-#include "i2v_common.h"
+#include "i2v_handle.h"
 #include "i2v_linear.h"
 #include "i2v_flow_tile.h"
 
 #include <cmath>
 #include <cstdlib>
-#include <memory>
 
 namespace i2v {
 
@@ -276,16 +275,15 @@ struct WsLayout {
 
 WsLayout ws_layout(const i2v_flow* f, int B) {
     WsLayout L;
-    size_t o = 0;
-    auto take = [&](size_t n) { size_t r = o; o = align_up(o + n, 256); return r; };
-    L.x = take((size_t)B * 64 * 4);
-    L.embed = take((size_t)B * f->E * 4);
-    L.logdet = take((size_t)B * 4);
-    L.preT = take((size_t)f->S * 2 * f->H * B * 4);
+    Carver c;
+    L.x = c.take_bytes((size_t)B * 64 * 4);
+    L.embed = c.take_bytes((size_t)B * f->E * 4);
+    L.logdet = c.take_bytes((size_t)B * 4);
+    L.preT = c.take_bytes((size_t)f->S * 2 * f->H * B * 4);
     const size_t Bp = (size_t)(B + 63) / 64 * 64;  // hidden activations are [2H][Bp]
-    L.hA = take((size_t)2 * f->H * Bp * 4);
-    L.hB = take((size_t)2 * f->H * Bp * 4);
-    L.total = o;
+    L.hA = c.take_bytes((size_t)2 * f->H * Bp * 4);
+    L.hB = c.take_bytes((size_t)2 * f->H * Bp * 4);
+    L.total = c.total();
     if (f->tile.ok) L.total = std::max(L.total, flow_tile_ws(f->tile, B).total);  // either chain may use the buffer
     return L;
 }
@@ -293,12 +291,12 @@ WsLayout ws_layout(const i2v_flow* f, int B) {
 // The launch chain of one pass on `st`, reading/writing only workspace memory.
 int enqueue_chain(i2v_flow* f, bool reverse, char* ws, int B, hipStream_t st) {
     const WsLayout L = ws_layout(f, B);
-    float* x = reinterpret_cast<float*>(ws + L.x);
-    const float* embed = reinterpret_cast<const float*>(ws + L.embed);
-    float* logdet = reinterpret_cast<float*>(ws + L.logdet);
-    float* preT = reinterpret_cast<float*>(ws + L.preT);
-    float* hA = reinterpret_cast<float*>(ws + L.hA);
-    float* hB = reinterpret_cast<float*>(ws + L.hB);
+    float* x = Carver::at(ws, L.x);
+    const float* embed = Carver::at(ws, L.embed);
+    float* logdet = Carver::at(ws, L.logdet);
+    float* preT = Carver::at(ws, L.preT);
+    float* hA = Carver::at(ws, L.hA);
+    float* hB = Carver::at(ws, L.hB);
     const int H = f->H, N2 = 2 * f->H, S = f->S;
     const int Bp = (B + 63) / 64 * 64;
     const FlowParams& par = f->par;
@@ -392,16 +390,14 @@ int run_chain(i2v_flow* f, bool reverse, int B, void* ws, hipStream_t st, Enqueu
     return I2V_OK;
 }
 
-int run_pass(i2v_flow* f, bool reverse, const float* xin, const float* embed, float* xout, float* logdet,
+int run_pass(const char* what, i2v_flow* f, bool reverse, const float* xin, const float* embed, float* xout, float* logdet,
              void* workspace, size_t workspace_bytes, int B, hipStream_t st) {
-    I2V_REQUIRE(f && f->loaded, I2V_E_STATE, "i2v_flow: weights not loaded");
-    I2V_REQUIRE(B > 0 && xin && embed && xout && workspace, I2V_E_INVALID, "i2v_flow: null argument or batch <= 0");
+    I2V_ENTER(sc, f, Entry::NEEDS_WEIGHTS, what);
+    I2V_REQUIRE(B > 0 && xin && embed && xout && workspace, I2V_E_INVALID, "%s: null argument or batch <= 0", what);
     const WsLayout L = ws_layout(f, B);
-    I2V_REQUIRE(workspace_bytes >= L.total, I2V_E_WORKSPACE, "i2v_flow: workspace %zu < required %zu",
-                workspace_bytes, L.total);
+    I2V_REQUIRE_WORKSPACE(workspace_bytes, L.total, what);
     char* ws = static_cast<char*>(workspace);
-    if (int rco = f->order.entry(st)) return rco;
-    StreamOrderMark mark{&f->order, st};   // records the end of this pass on its stream (also on the error paths)
+    if (int rco = sc.serialise(f->order, st)) return rco;
     if (f->tile.ok) {
         // matrix-core tile chain: its own first / last launches read / write the caller's tensors through the handle's FlowIo block,
         // so the replayed graph needs no copy kernels around it
@@ -411,15 +407,14 @@ int run_pass(i2v_flow* f, bool reverse, const float* xin, const float* embed, fl
     {
         const int na = B * 64, nb = B * f->E;
         hipLaunchKernelGGL(flow_copy2_kernel, dim3((na + nb + 255) / 256), dim3(256), 0, st, xin,
-                           reinterpret_cast<float*>(ws + L.x), na, embed, reinterpret_cast<float*>(ws + L.embed), nb);
+                           Carver::at(ws, L.x), na, embed, Carver::at(ws, L.embed), nb);
         I2V_HIP_CHECK(hipGetLastError());
     }
     if (int rc = run_chain(f, reverse, B, ws, st, [&](hipStream_t s) { return enqueue_chain(f, reverse, ws, B, s); })) return rc;
     {
         const int na = B * 64, nb = logdet ? B : 0;
         hipLaunchKernelGGL(flow_copy2_kernel, dim3((na + nb + 255) / 256), dim3(256), 0, st,
-                           reinterpret_cast<const float*>(ws + L.x), xout, na, reinterpret_cast<const float*>(ws + L.logdet),
-                           logdet, nb);
+                           Carver::at(ws, L.x), xout, na, Carver::at(ws, L.logdet), logdet, nb);
         I2V_HIP_CHECK(hipGetLastError());
     }
     return I2V_OK;
@@ -437,32 +432,25 @@ int i2v_flow_create(const i2v_flow_cfg* cfg, i2v_flow** out) {
                 "i2v_flow_create: hidden_dim must be a multiple of 64 in [64, %d], got %d", LIN_MAXK, cfg->hidden_dim);
     I2V_REQUIRE(cfg->embedding_dim > 0 && cfg->embedding_dim <= PRE_EMAX && cfg->hidden_depth >= 0 && cfg->n_flows > 0, I2V_E_INVALID,
                 "i2v_flow_create: bad embedding_dim/hidden_depth/n_flows");
-    int ndev = 0;
-    I2V_HIP_CHECK(hipGetDeviceCount(&ndev));
-    I2V_REQUIRE(ndev > 0, I2V_E_HIP, "i2v_flow_create: no HIP device");
-    auto f = std::make_unique<i2v_flow>();
-    f->cfg = *cfg;
-    I2V_HIP_CHECK(hipGetDevice(&f->device));
-    f->S = 2 * cfg->n_flows;
-    f->H = cfg->hidden_dim;
-    f->E = cfg->embedding_dim;
-    f->ld0 = 32 + cfg->embedding_dim;
-    f->depth = cfg->hidden_depth;
-    f->par.n_flows = cfg->n_flows;
-    f->par.use_an = !cfg->skip_actnorm;
-    f->par.use_act = cfg->activation != 0;
-    f->par.use_shuf = !cfg->skip_shuffle;
-    if (const char* e = std::getenv("I2V_FLOW_TILE")) f->tile_wanted = std::atoi(e) != 0;  // 0: generic vector-ALU chain
-    *out = f.release();
-    return I2V_OK;
+    return create_handle("i2v_flow_create", out, [&](i2v_flow* f) {
+        f->cfg = *cfg;
+        f->S = 2 * cfg->n_flows;
+        f->H = cfg->hidden_dim;
+        f->E = cfg->embedding_dim;
+        f->ld0 = 32 + cfg->embedding_dim;
+        f->depth = cfg->hidden_depth;
+        f->par.n_flows = cfg->n_flows;
+        f->par.use_an = !cfg->skip_actnorm;
+        f->par.use_act = cfg->activation != 0;
+        f->par.use_shuf = !cfg->skip_shuffle;
+        if (const char* e = std::getenv("I2V_FLOW_TILE")) f->tile_wanted = std::atoi(e) != 0;  // 0: generic vector-ALU chain
+        return I2V_OK;
+    });
 }
 
 void i2v_flow_destroy(i2v_flow* f) { delete f; }
 
-int i2v_flow_load(i2v_flow* f, const i2v_tensor* tensors, int32_t n_tensors) {
-    if (f) I2V_REQUIRE_DEVICE(f->device, "i2v_flow_load");
-    I2V_REQUIRE(f && tensors && n_tensors > 0, I2V_E_INVALID, "i2v_flow_load: null argument");
-    StateDict sd(tensors, n_tensors);
+static int flow_pack(i2v_flow* f, const StateDict& sd) {
     const int nf = f->cfg.n_flows, H = f->H, E = f->E, ld0 = f->ld0, D = f->depth, S = f->S, N2 = 2 * H;
     std::vector<float> W0((size_t)S * N2 * ld0, 0.f), b0((size_t)S * N2), Wmid((size_t)S * D * N2 * H),
         bmid((size_t)S * D * N2), W3T((size_t)S * H * 64), b3((size_t)S * 64), loc((size_t)nf * 64, 0.f),
@@ -569,9 +557,12 @@ int i2v_flow_load(i2v_flow* f, const i2v_tensor* tensors, int32_t n_tensors) {
         pbytes -= wfloats * 2;
     }
     f->param_bytes = pbytes;
-    f->loaded = true;
     f->drop_graphs();
     return I2V_OK;
+}
+
+int i2v_flow_load(i2v_flow* f, const i2v_tensor* tensors, int32_t n_tensors) {
+    return load_handle("i2v_flow_load", f, tensors, n_tensors, flow_pack);
 }
 
 size_t i2v_flow_workspace_bytes(const i2v_flow* f, int32_t batch) {
@@ -599,15 +590,12 @@ int i2v_flow_plan(const i2v_flow* f, int32_t batch, int32_t* chain, int32_t* kpw
 int i2v_flow_forward(i2v_flow* f, const float* x, const float* embed, float* zt, float* logdet, void* workspace,
                      size_t workspace_bytes, int32_t batch, void* stream) {
     I2V_REQUIRE(f && logdet, I2V_E_INVALID, "i2v_flow_forward: null argument");
-    I2V_REQUIRE_DEVICE(f->device, "i2v_flow_forward");
-    return run_pass(f, false, x, embed, zt, logdet, workspace, workspace_bytes, batch, static_cast<hipStream_t>(stream));
+    return run_pass("i2v_flow_forward", f, false, x, embed, zt, logdet, workspace, workspace_bytes, batch, static_cast<hipStream_t>(stream));
 }
 
 int i2v_flow_inverse(i2v_flow* f, const float* residual, const float* embed, float* z, void* workspace,
                      size_t workspace_bytes, int32_t batch, void* stream) {
-    I2V_REQUIRE(f, I2V_E_INVALID, "i2v_flow_inverse: null handle");
-    I2V_REQUIRE_DEVICE(f->device, "i2v_flow_inverse");
-    return run_pass(f, true, residual, embed, z, nullptr, workspace, workspace_bytes, batch,
+    return run_pass("i2v_flow_inverse", f, true, residual, embed, z, nullptr, workspace, workspace_bytes, batch,
                     static_cast<hipStream_t>(stream));
 }
 

@@ -22,6 +22,7 @@
 // launch's weight tiles of their XCD ("L2 warming") made the pass 43 us SLOWER at B = 64; with every layer reading the same
 // (L2-resident) weights the pass is only 23 us faster, i.e. the weight fetch is not what a launch waits for.
 #include "i2v_flow_tile.h"
+#include "i2v_handle.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -711,17 +712,16 @@ int flow_tile_pack(FlowTilePack& p, int S, int H, int depth, int E, const float*
 FlowTileWs flow_tile_ws(const FlowTilePack& p, int B) {
     FlowTileWs L;
     const size_t NST = (size_t)(B + 15) / 16;
-    size_t o = 0;
-    auto take = [&](size_t n) { size_t r = o; o = align_up(o + n, 256); return r; };
-    L.x = take(NST * 16 * 64 * 4);
-    L.x2 = take(NST * 16 * 64 * 4);
-    L.logdet = take(NST * 16 * 4);
-    L.pre = take((size_t)p.S * NST * p.NRT * 1024);
-    L.hA = take(NST * p.NRT * 1024);
-    L.hB = take(NST * p.NRT * 1024);
-    L.P = take(NST * p.NRT * 2 * 1024);
-    L.P2 = take(NST * p.NRT * 2 * 1024);
-    L.total = o;
+    Carver c;
+    L.x = c.take_bytes(NST * 16 * 64 * 4);
+    L.x2 = c.take_bytes(NST * 16 * 64 * 4);
+    L.logdet = c.take_bytes(NST * 16 * 4);
+    L.pre = c.take_bytes((size_t)p.S * NST * p.NRT * 1024);
+    L.hA = c.take_bytes(NST * p.NRT * 1024);
+    L.hB = c.take_bytes(NST * p.NRT * 1024);
+    L.P = c.take_bytes(NST * p.NRT * 2 * 1024);
+    L.P2 = c.take_bytes(NST * p.NRT * 2 * 1024);
+    L.total = c.total();
     return L;
 }
 

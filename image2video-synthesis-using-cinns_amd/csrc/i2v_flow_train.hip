@@ -14,8 +14,8 @@
 // fixed summation order, so two runs give the same bits.
 #include <cmath>
 
-#include "i2v_common.h"
 #include "i2v_flow_tile.h"
+#include "i2v_handle.h"
 
 namespace i2v {
 namespace {
@@ -600,9 +600,8 @@ int i2v_flow_train_forward(i2v_flow_train* f, const float* x, const float* embed
     I2V_REQUIRE(x && embed && zt && logdet, I2V_E_INVALID, "i2v_flow_train_forward: null tensor");
     I2V_REQUIRE_DEVICE(f->device, "i2v_flow_train_forward");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    rc = f->order.entry(s);
-    if (rc) return rc;
-    StreamOrderMark mark{&f->order, s};
+    Entry sc;
+    if ((rc = sc.serialise(f->order, s))) return rc;
     const TrainLayout L = make_layout(batch, f->H, f->depth, f->E, f->nfl);
     float* sv = static_cast<float*>(saved);
     const int H = f->H, depth = f->depth, B = batch;
@@ -651,9 +650,8 @@ int i2v_flow_train_backward(i2v_flow_train* f, const float* d_zt, const float* d
     I2V_REQUIRE((reinterpret_cast<size_t>(grad_base) & 15) == 0, I2V_E_INVALID, "i2v_flow_train_backward: grad_base is not 16-byte aligned");
     I2V_REQUIRE_DEVICE(f->device, "i2v_flow_train_backward");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    rc = f->order.entry(s);
-    if (rc) return rc;
-    StreamOrderMark mark{&f->order, s};
+    Entry sc;
+    if ((rc = sc.serialise(f->order, s))) return rc;
     const TrainLayout L = make_layout(batch, f->H, f->depth, f->E, f->nfl);
     float* sv = static_cast<float*>(saved);
     char* gbase = static_cast<char*>(grad_base);

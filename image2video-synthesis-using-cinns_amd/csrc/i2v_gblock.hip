@@ -1,7 +1,6 @@
 // Stand-alone GeneratorBlock / Spade / ADAIN / Norm3D (reference tensors [B][C][T][H][W] in and out): one block of the decoder
 // (i2v_dec_block.h) behind a handle of its own, for the sub-module entry points of stage1_VAE/modules.
 #include <algorithm>
-#include <memory>
 
 #include "i2v_dec_block.h"
 
@@ -31,6 +30,8 @@ using namespace i2v;
 
 struct i2v_gblock {
     BlockCtx ctx;
+    int& device = ctx.device;
+    bool loaded = false;   // a load has succeeded; which groups of keys it carried: has_*
     Block b;
     ConvWeights zlin;  // this block's ADAIN Linear(z_dim, 2*n_mid)
     int z_dim = 0;
@@ -46,14 +47,13 @@ GbWs gb_ws(const i2v_gblock* g, int B, int T, int H, int W) {
     const Block& b = g->b;
     const size_t P = (size_t)T * H * W, cm = std::max(b.n_in, std::max(b.n_mid, b.n_out));
     GbWs L;
-    size_t o = 0;
-    auto take = [&](size_t floats) { size_t r = o; o = align_up(o + floats * 4, 256); return r; };
-    L.x_cl = take(B * P * cm); L.out_cl = take(B * P * cm); L.a = take(B * P * cm * 2); L.dx = take(B * P * b.n_mid);
-    L.xs_in = take(B * P * b.n_in); L.xs_low = take(B * P * b.n_out);
-    L.y0 = take((size_t)B * H * W * 16); L.y1 = take((size_t)B * H * W * 128); L.gb = take((size_t)B * H * W * 2 * b.n_in);
-    L.zl = take((size_t)B * 2 * b.n_mid);
-    L.sums1 = take((size_t)B * cm * 4); L.sums2 = take((size_t)B * cm * 4); L.coef = take((size_t)B * cm * 2);
-    L.total = o;
+    Carver c;
+    L.x_cl = c.take_floats(B * P * cm); L.out_cl = c.take_floats(B * P * cm); L.a = c.take_floats(B * P * cm * 2); L.dx = c.take_floats(B * P * b.n_mid);
+    L.xs_in = c.take_floats(B * P * b.n_in); L.xs_low = c.take_floats(B * P * b.n_out);
+    L.y0 = c.take_floats((size_t)B * H * W * 16); L.y1 = c.take_floats((size_t)B * H * W * 128); L.gb = c.take_floats((size_t)B * H * W * 2 * b.n_in);
+    L.zl = c.take_floats((size_t)B * 2 * b.n_mid);
+    L.sums1 = c.take_floats((size_t)B * cm * 4); L.sums2 = c.take_floats((size_t)B * cm * 4); L.coef = c.take_floats((size_t)B * cm * 2);
+    L.total = c.total();
     return L;
 }
 
@@ -75,34 +75,28 @@ int i2v_gblock_create(int32_t n_in, int32_t n_out, int32_t z_dim, int32_t spectr
     // the learned shortcut's Norm3D is GroupNorm(16, n_in) (normalization_layer.py:31), which needs n_in % 16 == 0
     I2V_REQUIRE(n_in == n_out || n_in % 16 == 0, I2V_E_INVALID,
                 "i2v_gblock_create: a learned shortcut needs n_in %% 16 == 0 (GroupNorm(16, n_in)), got n_in %d", n_in);
-    int ndev = 0;
-    I2V_HIP_CHECK(hipGetDeviceCount(&ndev));
-    I2V_REQUIRE(ndev > 0, I2V_E_HIP, "i2v_gblock_create: no HIP device");
-    auto g = std::make_unique<i2v_gblock>();
-    g->ctx.mma = mma;
-    g->spectral_norm = spectral_norm != 0;
-    read_switches(&g->ctx, false);
-    if (int rc = init_status(&g->ctx)) return rc;
-    g->z_dim = z_dim;
-    Block& b = g->b;
-    b.name = "";
-    b.n_in = n_in; b.n_out = n_out; b.n_mid = std::min(n_in, n_out);
-    b.learned = n_in != n_out;
-    int grp = 16;
-    while (n_in % grp) --grp;
-    b.groups_spade = grp;
-    b.zoff = 0;
-    init_convs(b, false);
-    *out = g.release();
-    return I2V_OK;
+    return create_handle("i2v_gblock_create", out, [&](i2v_gblock* g) {
+        g->ctx.mma = mma;
+        g->spectral_norm = spectral_norm != 0;
+        read_switches(&g->ctx, false);
+        if (int rc = init_status(&g->ctx)) return rc;
+        g->z_dim = z_dim;
+        Block& b = g->b;
+        b.name = "";
+        b.n_in = n_in; b.n_out = n_out; b.n_mid = std::min(n_in, n_out);
+        b.learned = n_in != n_out;
+        int grp = 16;
+        while (n_in % grp) --grp;
+        b.groups_spade = grp;
+        b.zoff = 0;
+        init_convs(b, false);
+        return I2V_OK;
+    });
 }
 
 void i2v_gblock_destroy(i2v_gblock* g) { delete g; }
 
-int i2v_gblock_load(i2v_gblock* g, const i2v_tensor* tensors, int32_t n_tensors) {
-    I2V_REQUIRE(g && tensors && n_tensors > 0, I2V_E_INVALID, "i2v_gblock_load: null argument");
-    I2V_REQUIRE_DEVICE(g->ctx.device, "i2v_gblock_load");
-    StateDict sd(tensors, n_tensors);
+static int gblock_pack(i2v_gblock* g, const StateDict& sd) {
     Block& b = g->b;
     const bool sn = g->spectral_norm, f16 = g->ctx.has16(), one = g->ctx.one16();
     int rc;
@@ -147,6 +141,10 @@ int i2v_gblock_load(i2v_gblock* g, const i2v_tensor* tensors, int32_t n_tensors)
     return I2V_OK;
 }
 
+int i2v_gblock_load(i2v_gblock* g, const i2v_tensor* tensors, int32_t n_tensors) {
+    return load_handle("i2v_gblock_load", g, tensors, n_tensors, gblock_pack);
+}
+
 size_t i2v_gblock_workspace_bytes(const i2v_gblock* g, int32_t batch, int32_t t, int32_t h, int32_t w) {
     if (!g || batch <= 0 || t <= 0 || h <= 0 || w <= 0) return 0;
     return gb_ws(g, batch, t, h, w).total;
@@ -154,28 +152,29 @@ size_t i2v_gblock_workspace_bytes(const i2v_gblock* g, int32_t batch, int32_t t,
 
 int i2v_gblock_forward(i2v_gblock* g, const float* x, const float* z, const float* img, int32_t img_h, int32_t img_w, float* out,
                        void* workspace, size_t workspace_bytes, int32_t batch, int32_t t, int32_t h, int32_t w, void* stream) {
-    I2V_REQUIRE(g && g->has_convs && g->has_spade && g->has_adain && (!g->b.learned || g->has_norm_s), I2V_E_STATE,
+    Entry sc;
+    if (int rc0 = check_entry(sc, g, Entry::NEEDS_WEIGHTS | Entry::NULL_IS_UNLOADED, "i2v_gblock_forward")) return rc0;
+    I2V_REQUIRE(g->has_convs && g->has_spade && g->has_adain && (!g->b.learned || g->has_norm_s), I2V_E_STATE,
                 "i2v_gblock_forward: block weights not (fully) loaded");
     I2V_REQUIRE(x && z && img && out && workspace && batch > 0, I2V_E_INVALID, "i2v_gblock_forward: null argument");
-    if (int rc0 = check_entry(&g->ctx, "i2v_gblock_forward")) return rc0;
     const GbWs L = gb_ws(g, batch, t, h, w);
-    I2V_REQUIRE(workspace_bytes >= L.total, I2V_E_WORKSPACE, "i2v_gblock_forward: workspace %zu < required %zu", workspace_bytes, L.total);
+    I2V_REQUIRE_WORKSPACE(workspace_bytes, L.total, "i2v_gblock_forward");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(workspace);
-    auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    void* const ws = workspace;
+    float *x_cl = Carver::at(ws, L.x_cl), *out_cl = Carver::at(ws, L.out_cl), *zl = Carver::at(ws, L.zl);
     const long P = (long)t * h * w;
     Block& b = g->b;
     int rc;
-    if ((rc = run_transpose(x, F(L.x_cl), batch, b.n_in, P, true, st))) return rc;
-    if ((rc = conv_forward(g->zlin, z, g->z_dim, F(L.zl), nullptr, 1, 1, batch, 1, 1, 1, EPI_NONE, st))) return rc;
-    BlockBufs bufs{F(L.a), F(L.dx), F(L.xs_in), F(L.xs_low), F(L.y0), F(L.y1), F(L.gb), F(L.coef),
-                   reinterpret_cast<double*>(ws + L.sums1), reinterpret_cast<double*>(ws + L.sums2)};
+    if ((rc = run_transpose(x, x_cl, batch, b.n_in, P, true, st))) return rc;
+    if ((rc = conv_forward(g->zlin, z, g->z_dim, zl, nullptr, 1, 1, batch, 1, 1, 1, EPI_NONE, st))) return rc;
+    BlockBufs bufs{Carver::at(ws, L.a), Carver::at(ws, L.dx), Carver::at(ws, L.xs_in), Carver::at(ws, L.xs_low), Carver::at(ws, L.y0),
+                   Carver::at(ws, L.y1), Carver::at(ws, L.gb), Carver::at(ws, L.coef), Carver::at<double>(ws, L.sums1),
+                   Carver::at<double>(ws, L.sums2)};
     bool ready = false;
     const Level l{t, h, w, 1, 1};
-    if ((rc = block_forward(&g->ctx, 0, b, l, F(L.x_cl), F(L.out_cl), img, img_h, img_w, 0, F(L.zl), 2 * b.n_mid, batch, bufs, ready,
-                            false, st)))
+    if ((rc = block_forward(&g->ctx, 0, b, l, x_cl, out_cl, img, img_h, img_w, 0, zl, 2 * b.n_mid, batch, bufs, ready, false, st)))
         return rc;
-    if ((rc = run_transpose(F(L.out_cl), out, batch, b.n_out, P, false, st))) return rc;
+    if ((rc = run_transpose(out_cl, out, batch, b.n_out, P, false, st))) return rc;
     if (g->ctx.has16()) {
         if ((rc = status_finish(g->ctx.status_dev, st))) return rc;
         I2V_HIP_CHECK(hipMemcpyAsync(g->ctx.status_host, g->ctx.status_dev, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -190,18 +189,18 @@ int i2v_gblock_status(i2v_gblock* g, int32_t* flags, int32_t reset, void* stream
 
 int i2v_gblock_norm(i2v_gblock* g, int32_t part, const float* x, const float* cond, int32_t img_h, int32_t img_w, float* out,
                     void* workspace, size_t workspace_bytes, int32_t batch, int32_t t, int32_t h, int32_t w, void* stream) {
-    I2V_REQUIRE(g && x && out && workspace && batch > 0 && part >= 0 && part <= 2, I2V_E_INVALID, "i2v_gblock_norm: bad argument");
-    if (int rc0 = check_entry(&g->ctx, "i2v_gblock_norm")) return rc0;
+    Entry sc;
+    if (int rc0 = check_entry(sc, g, Entry::NEEDS_WEIGHTS, "i2v_gblock_norm")) return rc0;
+    I2V_REQUIRE(x && out && workspace && batch > 0 && part >= 0 && part <= 2, I2V_E_INVALID, "i2v_gblock_norm: bad argument");
     const GbWs L = gb_ws(g, batch, t, h, w);
-    I2V_REQUIRE(workspace_bytes >= L.total, I2V_E_WORKSPACE, "i2v_gblock_norm: workspace %zu < required %zu", workspace_bytes, L.total);
+    I2V_REQUIRE_WORKSPACE(workspace_bytes, L.total, "i2v_gblock_norm");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(workspace);
-    auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    void* const ws = workspace;
     const long P = (long)t * h * w;
     Block& b = g->b;
     const int B = batch;
-    double* sums = reinterpret_cast<double*>(ws + L.sums1);
-    float *x_cl = F(L.x_cl), *a = F(L.a), *coef = F(L.coef);
+    double* sums = Carver::at<double>(ws, L.sums1);
+    float *x_cl = Carver::at(ws, L.x_cl), *a = Carver::at(ws, L.a), *coef = Carver::at(ws, L.coef), *zl = Carver::at(ws, L.zl), *gb = Carver::at(ws, L.gb);
     int rc;
     const int C = part == 1 ? b.n_mid : b.n_in;
     if ((rc = run_transpose(x, x_cl, B, C, P, true, st))) return rc;
@@ -209,12 +208,12 @@ int i2v_gblock_norm(i2v_gblock* g, int32_t part, const float* x, const float* co
     if (part == 0) {        // Spade.forward(x, img), normalization_layer.py:18-24
         I2V_REQUIRE(g->has_spade && cond, I2V_E_STATE, "i2v_gblock_norm: Spade weights not loaded / no start frame");
         if ((rc = coef_forward(sums, coef, B, C, b.groups_spade, (double)P, st))) return rc;
-        if ((rc = spade_branch(&g->ctx, b, Level{t, h, w, 1, 1}, cond, img_h, img_w, 0, B, F(L.y0), F(L.y1), nullptr, F(L.gb), st))) return rc;
-        if ((rc = run_modulate(x_cl, coef, F(L.gb), a, B, t, h, w, C, 1, 1, 0, st))) return rc;
+        if ((rc = spade_branch(&g->ctx, b, Level{t, h, w, 1, 1}, cond, img_h, img_w, 0, B, Carver::at(ws, L.y0), Carver::at(ws, L.y1), nullptr, gb, st))) return rc;
+        if ((rc = run_modulate(x_cl, coef, gb, a, B, t, h, w, C, 1, 1, 0, st))) return rc;
     } else if (part == 1) { // ADAIN.forward(x, z), normalization_layer.py:47-51
         I2V_REQUIRE(g->has_adain && cond, I2V_E_STATE, "i2v_gblock_norm: ADAIN weights not loaded / no latent");
-        if ((rc = conv_forward(g->zlin, cond, g->z_dim, F(L.zl), nullptr, 1, 1, B, 1, 1, 1, EPI_NONE, st))) return rc;
-        if ((rc = coef_forward(sums, coef, B, C, C, (double)P, st, nullptr, nullptr, F(L.zl), 2 * b.n_mid, 0))) return rc;
+        if ((rc = conv_forward(g->zlin, cond, g->z_dim, zl, nullptr, 1, 1, B, 1, 1, 1, EPI_NONE, st))) return rc;
+        if ((rc = coef_forward(sums, coef, B, C, C, (double)P, st, nullptr, nullptr, zl, 2 * b.n_mid, 0))) return rc;
         if ((rc = run_modulate(x_cl, coef, nullptr, a, B, t, h, w, C, 1, 1, 0, st))) return rc;
     } else {                // Norm3D.forward(x), normalization_layer.py:33-35
         I2V_REQUIRE(C % 16 == 0, I2V_E_INVALID, "i2v_gblock_norm: Norm3D is GroupNorm(16, C), needs C %% 16 == 0, got %d", C);

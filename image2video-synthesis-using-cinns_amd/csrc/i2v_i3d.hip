@@ -19,9 +19,9 @@
 // i2v_diversity_update: the pair loop of metrics/Diversity/I3D.py in float64, one workgroup, fixed order.
 #include <algorithm>
 #include <cmath>
-#include <memory>
 
 #include "i2v_flatconv.h"
+#include "i2v_handle.h"
 
 namespace i2v {
 namespace {
@@ -375,15 +375,14 @@ int i3d_ws(const i2v_i3d* net, int B, int T, int H, int W, I3dWs* L, bool featur
     int th = 0;
     if (int rc = wk.run(nullptr, T, T, H, W, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &th, features)) return rc;
     if (t_head) *t_head = th;
-    size_t o = 0;
-    auto take = [&](size_t floats) { size_t r = o; o = align_up(o + floats * 4, 256); return r; };
-    L->inp = take((size_t)B * T * I3D_SIDE * I3D_SIDE * 4);
-    L->x = take(wk.act_floats);
-    L->y = take(wk.act_floats);
-    L->tmp = take(wk.tmp_floats);
-    L->pooled = take(features ? 0 : (size_t)B * th * 1024);
-    L->cls = take(features ? 0 : (size_t)B * th * net->num_classes);
-    L->total = o;
+    Carver c;
+    L->inp = c.take_floats((size_t)B * T * I3D_SIDE * I3D_SIDE * 4);
+    L->x = c.take_floats(wk.act_floats);
+    L->y = c.take_floats(wk.act_floats);
+    L->tmp = c.take_floats(wk.tmp_floats);
+    L->pooled = c.take_floats(features ? 0 : (size_t)B * th * 1024);
+    L->cls = c.take_floats(features ? 0 : (size_t)B * th * net->num_classes);
+    L->total = c.total();
     return I2V_OK;
 }
 
@@ -394,15 +393,11 @@ extern "C" {
 int i2v_i3d_create(int32_t num_classes, int32_t in_channels, i2v_i3d** out) {
     I2V_REQUIRE(out && num_classes > 0, I2V_E_INVALID, "i2v_i3d_create: bad argument");
     I2V_REQUIRE(in_channels == 3, I2V_E_INVALID, "i2v_i3d_create: only the rgb network (3 input channels) is built, got %d", in_channels);
-    int ndev = 0;
-    I2V_HIP_CHECK(hipGetDeviceCount(&ndev));
-    I2V_REQUIRE(ndev > 0, I2V_E_HIP, "i2v_i3d_create: no HIP device");
-    auto n = std::make_unique<i2v_i3d>();
-    n->num_classes = num_classes;
-    n->in_channels = in_channels;
-    I2V_HIP_CHECK(hipGetDevice(&n->device));
-    *out = n.release();
-    return I2V_OK;
+    return create_handle("i2v_i3d_create", out, [&](i2v_i3d* n) {
+        n->num_classes = num_classes;
+        n->in_channels = in_channels;
+        return I2V_OK;
+    });
 }
 
 int i2v_dti3d_create(int32_t num_classes, int32_t length, i2v_i3d** out) {
@@ -415,12 +410,8 @@ int i2v_dti3d_create(int32_t num_classes, int32_t length, i2v_i3d** out) {
 
 void i2v_i3d_destroy(i2v_i3d* n) { delete n; }
 
-int i2v_i3d_load(i2v_i3d* n, const i2v_tensor* tensors, int32_t n_tensors) {
-    if (n) I2V_REQUIRE_DEVICE(n->device, "i2v_i3d_load");
-    I2V_REQUIRE(n && tensors && n_tensors > 0, I2V_E_INVALID, "i2v_i3d_load: null argument");
-    StateDict sd(tensors, n_tensors);
+static int i3d_pack(i2v_i3d* n, const StateDict& sd) {
     int rc;
-    n->loaded = false;
     if (n->dt) {   // ID3.InceptionI3D: Conv3d_* / Mixed_*.{b0,b1a,b1b,b2a,b2b,b3b} / logits, BatchNorm3d under "bn" with eps 1e-5
         static const char* const BR[6] = {".b0", ".b1a", ".b1b", ".b2a", ".b2b", ".b3b"};
         if ((rc = n->stem.pack(sd, "Conv3d_1a_7x7", n->in_channels, 64, 7, true, false, "bn", 1e-5))) return rc;
@@ -434,9 +425,7 @@ int i2v_i3d_load(i2v_i3d* n, const i2v_tensor* tensors, int32_t n_tensors) {
             for (int j = 0; j < 6; ++j)
                 if ((rc = n->mixed[i][j].pack(sd, p + BR[j], cin[j], s.o[j], j == 2 || j == 4 ? 3 : 1, true, false, "bn", 1e-5))) return rc;
         }
-        if ((rc = n->head.pack(sd, "logits", 1024, n->num_classes, 1, false, true))) return rc;   // (i2v_i3d_features never launches it)
-        n->loaded = true;
-        return I2V_OK;
+        return n->head.pack(sd, "logits", 1024, n->num_classes, 1, false, true);   // (i2v_i3d_features never launches it)
     }
     if ((rc = n->stem.pack(sd, "conv3d_1a_7x7", n->in_channels, 64, 7, true, false))) return rc;
     if ((rc = n->c2b.pack(sd, "conv3d_2b_1x1", 64, 64, 1, true, false))) return rc;
@@ -452,9 +441,11 @@ int i2v_i3d_load(i2v_i3d* n, const i2v_tensor* tensors, int32_t n_tensors) {
         if ((rc = u[4].pack(sd, p + "branch_2.1", s.o[3], s.o[4], 3, true, false))) return rc;
         if ((rc = u[5].pack(sd, p + "branch_3.1", s.cin, s.o[5], 1, true, false))) return rc;
     }
-    if ((rc = n->head.pack(sd, "conv3d_0c_1x1", 1024, n->num_classes, 1, false, true))) return rc;
-    n->loaded = true;
-    return I2V_OK;
+    return n->head.pack(sd, "conv3d_0c_1x1", 1024, n->num_classes, 1, false, true);
+}
+
+int i2v_i3d_load(i2v_i3d* n, const i2v_tensor* tensors, int32_t n_tensors) {
+    return load_handle("i2v_i3d_load", n, tensors, n_tensors, i3d_pack);
 }
 
 size_t i2v_i3d_workspace_bytes(const i2v_i3d* n, int32_t batch, int32_t t, int32_t h, int32_t w) {
@@ -466,21 +457,19 @@ size_t i2v_i3d_workspace_bytes(const i2v_i3d* n, int32_t batch, int32_t t, int32
 
 int i2v_i3d_forward(i2v_i3d* n, const float* frames, int32_t batch, int32_t t, int32_t h, int32_t w, int32_t denorm, float* logits,
                     void* workspace, size_t workspace_bytes, void* stream) {
-    if (n) I2V_REQUIRE_DEVICE(n->device, "i2v_i3d_forward");
-    I2V_REQUIRE(n && n->loaded, I2V_E_STATE, "i2v_i3d_forward: weights not loaded");
+    I2V_ENTER(sc, n, Entry::NEEDS_WEIGHTS | Entry::NULL_IS_UNLOADED, "i2v_i3d_forward");
     I2V_REQUIRE(frames && logits && workspace && batch > 0 && t > 0 && h >= 2 && w >= 2, I2V_E_INVALID, "i2v_i3d_forward: bad argument");
     I2V_REQUIRE((long)batch * t * I3D_SIDE * I3D_SIDE * 64 < (1L << 40), I2V_E_INVALID, "i2v_i3d_forward: batch %d x %d frames is too large", batch, t);
     I3dWs L;
     if (int rc = i3d_ws(n, batch, t, h, w, &L)) return rc;
-    I2V_REQUIRE(workspace_bytes >= L.total, I2V_E_WORKSPACE, "i2v_i3d_forward: workspace %zu < required %zu", workspace_bytes, L.total);
+    I2V_REQUIRE_WORKSPACE(workspace_bytes, L.total, "i2v_i3d_forward");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (int rco = n->order.entry(st)) return rco;
-    StreamOrderMark mark{&n->order, st};
-    char* ws = static_cast<char*>(workspace);
-    auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    if (int rco = sc.serialise(n->order, st)) return rco;
+    void* const ws = workspace;
     Walk wk{n, batch, false, st};
     int th = 0;
-    return wk.run(frames, t, t, h, w, denorm ? 1 : 0, F(L.inp), F(L.x), F(L.y), F(L.tmp), F(L.pooled), F(L.cls), logits, &th);
+    return wk.run(frames, t, t, h, w, denorm ? 1 : 0, Carver::at(ws, L.inp), Carver::at(ws, L.x), Carver::at(ws, L.y), Carver::at(ws, L.tmp),
+                  Carver::at(ws, L.pooled), Carver::at(ws, L.cls), logits, &th);
 }
 
 size_t i2v_i3d_features_workspace_bytes(const i2v_i3d* n, int32_t batch, int32_t t_out, int32_t h, int32_t w) {
@@ -500,23 +489,21 @@ int32_t i2v_i3d_feature_steps(const i2v_i3d* n, int32_t t_out) {
 
 int i2v_i3d_features(i2v_i3d* n, const float* frames, int32_t batch, int32_t t_in, int32_t t_out, int32_t h, int32_t w, int32_t denorm,
                      float* feats, void* workspace, size_t workspace_bytes, void* stream) {
-    if (n) I2V_REQUIRE_DEVICE(n->device, "i2v_i3d_features");
-    I2V_REQUIRE(n && n->loaded, I2V_E_STATE, "i2v_i3d_features: weights not loaded");
+    I2V_ENTER(sc, n, Entry::NEEDS_WEIGHTS | Entry::NULL_IS_UNLOADED, "i2v_i3d_features");
     I2V_REQUIRE(frames && feats && workspace && batch > 0 && t_in > 0 && t_out > 0 && h >= 2 && w >= 2, I2V_E_INVALID,
                 "i2v_i3d_features: bad argument");
     I2V_REQUIRE((long)batch * t_out * I3D_SIDE * I3D_SIDE * 64 < (1L << 40) && (long)batch * t_in * 3 * h * w < (1L << 40), I2V_E_INVALID,
                 "i2v_i3d_features: batch %d x %d frames is too large", batch, t_out);
     I3dWs L;
     if (int rc = i3d_ws(n, batch, t_out, h, w, &L, true)) return rc;
-    I2V_REQUIRE(workspace_bytes >= L.total, I2V_E_WORKSPACE, "i2v_i3d_features: workspace %zu < required %zu", workspace_bytes, L.total);
+    I2V_REQUIRE_WORKSPACE(workspace_bytes, L.total, "i2v_i3d_features");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (int rco = n->order.entry(st)) return rco;
-    StreamOrderMark mark{&n->order, st};
-    char* ws = static_cast<char*>(workspace);
-    auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    if (int rco = sc.serialise(n->order, st)) return rco;
+    void* const ws = workspace;
     Walk wk{n, batch, false, st};
     int th = 0;
-    return wk.run(frames, t_in, t_out, h, w, denorm ? 1 : 0, F(L.inp), F(L.x), F(L.y), F(L.tmp), nullptr, nullptr, feats, &th, true);
+    return wk.run(frames, t_in, t_out, h, w, denorm ? 1 : 0, Carver::at(ws, L.inp), Carver::at(ws, L.x), Carver::at(ws, L.y), Carver::at(ws, L.tmp),
+                  nullptr, nullptr, feats, &th, true);
 }
 
 // ---- sub-modules of a loaded handle, individually callable on channels-last tensors (for tests and inspection)
@@ -552,9 +539,7 @@ int i2v_i3d_unit_shape(const i2v_i3d* n, int32_t unit, int32_t t, int32_t h, int
 
 int i2v_i3d_unit_forward(i2v_i3d* n, int32_t unit, const float* x, int32_t batch, int32_t t, int32_t h, int32_t w, int32_t in_cs, float* out,
                          int32_t out_cs, int32_t out_off, size_t out_floats, void* stream) {
-    I2V_REQUIRE(n, I2V_E_INVALID, "i2v_i3d_unit_forward: null handle");
-    I2V_REQUIRE_DEVICE(n->device, "i2v_i3d_unit_forward");
-    I2V_REQUIRE(n && n->loaded, I2V_E_STATE, "i2v_i3d_unit_forward: weights not loaded");
+    I2V_ENTER(sc, n, Entry::NEEDS_WEIGHTS, "i2v_i3d_unit_forward");
     int s;
     const Unit* u = i3d_unit(n, unit, &s);
     I2V_REQUIRE(u, I2V_E_INVALID, "i2v_i3d_unit_forward: unknown unit %d", unit);
@@ -569,8 +554,7 @@ int i2v_i3d_unit_forward(i2v_i3d* n, int32_t unit, const float* x, int32_t batch
     I2V_REQUIRE(out_floats >= (size_t)batch * o.pos() * out_cs, I2V_E_WORKSPACE, "i2v_i3d_unit_forward: output of %zu floats < required %zu",
                 out_floats, (size_t)batch * o.pos() * out_cs);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (int rco = n->order.entry(st)) return rco;
-    StreamOrderMark mark{&n->order, st};
+    if (int rco = sc.serialise(n->order, st)) return rco;
     Walk wk{n, batch, false, st};
     return wk.unit(*u, s, x, in_cs, 0, Dims{t, h, w}, out, out_cs, out_off, unit != I2V_I3D_UNIT_HEAD, &o);
 }
@@ -584,18 +568,15 @@ size_t i2v_i3d_mixed_workspace_bytes(const i2v_i3d* n, int32_t block, int32_t ba
 
 int i2v_i3d_mixed_forward(i2v_i3d* n, int32_t block, const float* x, int32_t batch, int32_t t, int32_t h, int32_t w, float* out, void* workspace,
                           size_t workspace_bytes, void* stream) {
-    I2V_REQUIRE(n, I2V_E_INVALID, "i2v_i3d_mixed_forward: null handle");
-    I2V_REQUIRE_DEVICE(n->device, "i2v_i3d_mixed_forward");
-    I2V_REQUIRE(n && n->loaded, I2V_E_STATE, "i2v_i3d_mixed_forward: weights not loaded");
+    I2V_ENTER(sc, n, Entry::NEEDS_WEIGHTS, "i2v_i3d_mixed_forward");
     I2V_REQUIRE(block >= 0 && block < 9, I2V_E_INVALID, "i2v_i3d_mixed_forward: unknown block %d", block);
     I2V_REQUIRE(x && out && workspace && batch > 0 && t > 0 && h > 0 && w > 0, I2V_E_INVALID, "i2v_i3d_mixed_forward: bad argument");
     I2V_REQUIRE((long)batch * t * h * w * 1024 < I3D_SUB_MAX, I2V_E_INVALID, "i2v_i3d_mixed_forward: batch %d x [%d, %d, %d] is too large", batch, t, h,
                 w);
     const size_t need = i2v_i3d_mixed_workspace_bytes(n, block, batch, t, h, w);
-    I2V_REQUIRE(workspace_bytes >= need, I2V_E_WORKSPACE, "i2v_i3d_mixed_forward: workspace %zu < required %zu", workspace_bytes, need);
+    I2V_REQUIRE_WORKSPACE(workspace_bytes, need, "i2v_i3d_mixed_forward");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (int rco = n->order.entry(st)) return rco;
-    StreamOrderMark mark{&n->order, st};
+    if (int rco = sc.serialise(n->order, st)) return rco;
     Walk wk{n, batch, false, st};
     return wk.mixed(block, x, Dims{t, h, w}, out, static_cast<float*>(workspace));
 }
@@ -611,8 +592,7 @@ int i2v_i3d_maxpool_shape(const i2v_i3d* n, int32_t kt, int32_t k, int32_t st, i
 
 int i2v_i3d_maxpool_forward(i2v_i3d* n, const float* x, int32_t batch, int32_t t, int32_t h, int32_t w, int32_t c, int32_t kt, int32_t k, int32_t st,
                             int32_t s, float* out, size_t out_floats, void* stream) {
-    I2V_REQUIRE(n, I2V_E_INVALID, "i2v_i3d_maxpool_forward: null handle");
-    I2V_REQUIRE_DEVICE(n->device, "i2v_i3d_maxpool_forward");
+    I2V_ENTER(sc, n, 0, "i2v_i3d_maxpool_forward");
     I2V_REQUIRE(x && out && batch > 0 && t > 0 && h > 0 && w > 0 && kt > 0 && k > 0 && st > 0 && s > 0, I2V_E_INVALID,
                 "i2v_i3d_maxpool_forward: bad argument");
     I2V_REQUIRE(c > 0 && c % 4 == 0, I2V_E_INVALID, "i2v_i3d_maxpool_forward: %d channels (a multiple of 4 is needed)", c);
@@ -623,8 +603,7 @@ int i2v_i3d_maxpool_forward(i2v_i3d* n, const float* x, int32_t batch, int32_t t
     const size_t need = (size_t)batch * od[0] * od[1] * od[2] * c;
     I2V_REQUIRE(out_floats >= need, I2V_E_WORKSPACE, "i2v_i3d_maxpool_forward: output of %zu floats < required %zu", out_floats, need);
     hipStream_t hs = static_cast<hipStream_t>(stream);
-    if (int rco = n->order.entry(hs)) return rco;
-    StreamOrderMark mark{&n->order, hs};
+    if (int rco = sc.serialise(n->order, hs)) return rco;
     Walk wk{n, batch, false, hs};
     Dims o;
     return wk.pool(x, out, c, Dims{t, h, w}, kt, k, st, s, &o);
@@ -637,17 +616,14 @@ size_t i2v_i3d_head_workspace_bytes(const i2v_i3d* n, int32_t batch, int32_t t) 
 
 int i2v_i3d_head_forward(i2v_i3d* n, const float* x, int32_t batch, int32_t t, float* pooled, float* feats, float* logits, void* workspace,
                          size_t workspace_bytes, void* stream) {
-    I2V_REQUIRE(n, I2V_E_INVALID, "i2v_i3d_head_forward: null handle");
-    I2V_REQUIRE_DEVICE(n->device, "i2v_i3d_head_forward");
-    I2V_REQUIRE(n && n->loaded, I2V_E_STATE, "i2v_i3d_head_forward: weights not loaded");
+    I2V_ENTER(sc, n, Entry::NEEDS_WEIGHTS, "i2v_i3d_head_forward");
     I2V_REQUIRE(x && pooled && feats && logits && workspace && batch > 0, I2V_E_INVALID, "i2v_i3d_head_forward: bad argument");
     I2V_REQUIRE(t >= n->pool_t && (long)batch * t * 49 * 1024 < I3D_SUB_MAX, I2V_E_INVALID,
                 "i2v_i3d_head_forward: %d time steps in front of AvgPool3d((%d, 7, 7)), batch %d", t, n->pool_t, batch);
     const size_t need = i2v_i3d_head_workspace_bytes(n, batch, t);
-    I2V_REQUIRE(workspace_bytes >= need, I2V_E_WORKSPACE, "i2v_i3d_head_forward: workspace %zu < required %zu", workspace_bytes, need);
+    I2V_REQUIRE_WORKSPACE(workspace_bytes, need, "i2v_i3d_head_forward");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (int rco = n->order.entry(st)) return rco;
-    StreamOrderMark mark{&n->order, st};
+    if (int rco = sc.serialise(n->order, st)) return rco;
     Walk wk{n, batch, false, st};
     if (int rc = wk.head(x, t, nullptr, nullptr, feats, true)) return rc;
     return wk.head(x, t, pooled, static_cast<float*>(workspace), logits, false);

@@ -14,9 +14,9 @@
 //   (d) AdaptiveAvgPool2d((1, 1)): [N][H][W][C] -> [N][C].
 #include <algorithm>
 #include <cmath>
-#include <memory>
 
 #include "i2v_flatconv.h"
+#include "i2v_handle.h"
 
 namespace i2v {
 namespace {
@@ -349,13 +349,12 @@ int inc_ws(const i2v_inception* net, int B, int H, int W, int last, IncWs* L, Ma
     float* none[4] = {nullptr, nullptr, nullptr, nullptr};
     if (int rc = wk.run(nullptr, H, W, none, last, nullptr, nullptr, nullptr, nullptr)) return rc;
     if (bdim) std::copy(wk.bdim, wk.bdim + 4, bdim);
-    size_t o = 0;
-    auto take = [&](size_t floats) { size_t r = o; o = align_up(o + floats * 4, 256); return r; };
-    L->a = take(wk.act_floats);
-    L->b = take(wk.act_floats);
-    L->t0 = take(wk.t_floats[0]);
-    L->t1 = take(wk.t_floats[1]);
-    L->total = o;
+    Carver c;
+    L->a = c.take_floats(wk.act_floats);
+    L->b = c.take_floats(wk.act_floats);
+    L->t0 = c.take_floats(wk.t_floats[0]);
+    L->t1 = c.take_floats(wk.t_floats[1]);
+    L->total = c.total();
     return I2V_OK;
 }
 
@@ -367,13 +366,8 @@ bool inc_dims_ok(int h, int w) { return h >= INC_MIN && w >= INC_MIN; }
 
 extern "C" {
 
-int i2v_inception_create(i2v_inception** out) {
-    I2V_REQUIRE(out, I2V_E_INVALID, "i2v_inception_create: null argument");
-    int ndev = 0;
-    I2V_HIP_CHECK(hipGetDeviceCount(&ndev));
-    I2V_REQUIRE(ndev > 0, I2V_E_HIP, "i2v_inception_create: no HIP device");
-    auto n = std::make_unique<i2v_inception>();
-    I2V_HIP_CHECK(hipGetDevice(&n->device));
+// fid_inception_v3's graph, without weights
+static int inception_graph(i2v_inception* n) {
     n->stem[0].spec = cs("Conv2d_1a_3x3", 3, 32, 3, 3, 2);
     n->stem[1].spec = cs("Conv2d_2a_3x3", 32, 32, 3, 3);
     n->stem[2].spec = cs("Conv2d_2b_3x3", 32, 64, 3, 3, 1, 1, 1);
@@ -400,24 +394,24 @@ int i2v_inception_create(i2v_inception** out) {
             }
         }
     }
-    *out = n.release();
     return I2V_OK;
 }
 
+int i2v_inception_create(i2v_inception** out) { return create_handle("i2v_inception_create", out, inception_graph); }
+
 void i2v_inception_destroy(i2v_inception* n) { delete n; }
 
-int i2v_inception_load(i2v_inception* n, const i2v_tensor* tensors, int32_t n_tensors) {
-    if (n) I2V_REQUIRE_DEVICE(n->device, "i2v_inception_load");
-    I2V_REQUIRE(n && tensors && n_tensors > 0, I2V_E_INVALID, "i2v_inception_load: null argument");
-    StateDict sd(tensors, n_tensors);
-    n->loaded = false;
+static int inception_pack(i2v_inception* n, const StateDict& sd) {
     for (Unit& u : n->stem)
         if (int rc = u.load(sd)) return rc;
     for (auto& us : n->units)
         for (Unit& u : us)
             if (int rc = u.load(sd)) return rc;
-    n->loaded = true;
     return I2V_OK;
+}
+
+int i2v_inception_load(i2v_inception* n, const i2v_tensor* tensors, int32_t n_tensors) {
+    return load_handle("i2v_inception_load", n, tensors, n_tensors, inception_pack);
 }
 
 int i2v_inception_block_shape(const i2v_inception* n, int32_t h, int32_t w, int32_t block, int32_t* dims) {
@@ -451,8 +445,7 @@ int i2v_inception_input_stage(const float* frames, int32_t n, int32_t hi, int32_
 
 int i2v_inception_features(i2v_inception* n, const float* x, int32_t batch, int32_t h, int32_t w, float* block0, float* block1, float* block2,
                            float* block3, void* workspace, size_t workspace_bytes, void* stream) {
-    if (n) I2V_REQUIRE_DEVICE(n->device, "i2v_inception_features");
-    I2V_REQUIRE(n && n->loaded, I2V_E_STATE, "i2v_inception_features: weights not loaded");
+    I2V_ENTER(sc, n, Entry::NEEDS_WEIGHTS | Entry::NULL_IS_UNLOADED, "i2v_inception_features");
     I2V_REQUIRE(x && workspace && batch > 0, I2V_E_INVALID, "i2v_inception_features: bad argument");
     float* taps[4] = {block0, block1, block2, block3};
     int last = -1;
@@ -465,14 +458,12 @@ int i2v_inception_features(i2v_inception* n, const float* x, int32_t batch, int3
     I2V_REQUIRE((long)batch * h * w * 32 < INC_MAX_FLOATS, I2V_E_INVALID, "i2v_inception_features: batch %d x [%d, %d] is too large", batch, h, w);
     IncWs L;
     if (int rc = inc_ws(n, batch, h, w, last, &L)) return rc;
-    I2V_REQUIRE(workspace_bytes >= L.total, I2V_E_WORKSPACE, "i2v_inception_features: workspace %zu < required %zu", workspace_bytes, L.total);
+    I2V_REQUIRE_WORKSPACE(workspace_bytes, L.total, "i2v_inception_features");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (int rco = n->order.entry(st)) return rco;
-    StreamOrderMark mark{&n->order, st};
-    char* ws = static_cast<char*>(workspace);
-    auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    if (int rco = sc.serialise(n->order, st)) return rco;
+    void* const ws = workspace;
     Walk wk{n, batch, false, st};
-    return wk.run(x, h, w, taps, last, F(L.a), F(L.b), F(L.t0), F(L.t1));
+    return wk.run(x, h, w, taps, last, Carver::at(ws, L.a), Carver::at(ws, L.b), Carver::at(ws, L.t0), Carver::at(ws, L.t1));
 }
 
 // ---- sub-modules, individually callable on channels-last tensors (for tests and inspection)
@@ -546,9 +537,7 @@ size_t i2v_inception_mixed_workspace_bytes(const i2v_inception* n, int32_t block
 
 int i2v_inception_mixed_forward(i2v_inception* n, int32_t block, const float* x, int32_t batch, int32_t h, int32_t w, float* out, void* workspace,
                                 size_t workspace_bytes, void* stream) {
-    I2V_REQUIRE(n, I2V_E_INVALID, "i2v_inception_mixed_forward: null handle");
-    I2V_REQUIRE_DEVICE(n->device, "i2v_inception_mixed_forward");
-    I2V_REQUIRE(n->loaded, I2V_E_STATE, "i2v_inception_mixed_forward: weights not loaded");
+    I2V_ENTER(sc, n, Entry::NEEDS_WEIGHTS, "i2v_inception_mixed_forward");
     I2V_REQUIRE(block >= 0 && block < N_MIXED, I2V_E_INVALID, "i2v_inception_mixed_forward: unknown block %d", block);
     I2V_REQUIRE(x && out && workspace && batch > 0 && h > 0 && w > 0, I2V_E_INVALID, "i2v_inception_mixed_forward: bad argument");
     I2V_REQUIRE((long)batch * h * w * 2048 < INC_SUB_MAX, I2V_E_INVALID, "i2v_inception_mixed_forward: batch %d x [%d, %d] is too large", batch, h, w);
@@ -556,13 +545,11 @@ int i2v_inception_mixed_forward(i2v_inception* n, int32_t block, const float* x,
     Map o;
     if (int rc = dry.mixed(block, nullptr, Map{h, w}, nullptr, nullptr, nullptr, &o)) return rc;
     const size_t t0b = align_up(dry.t_floats[0] * 4, 256), need = t0b + align_up(dry.t_floats[1] * 4, 256);
-    I2V_REQUIRE(workspace_bytes >= need, I2V_E_WORKSPACE, "i2v_inception_mixed_forward: workspace %zu < required %zu", workspace_bytes, need);
+    I2V_REQUIRE_WORKSPACE(workspace_bytes, need, "i2v_inception_mixed_forward");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (int rco = n->order.entry(st)) return rco;
-    StreamOrderMark mark{&n->order, st};
+    if (int rco = sc.serialise(n->order, st)) return rco;
     Walk wk{n, batch, false, st};
-    char* ws = static_cast<char*>(workspace);
-    return wk.mixed(block, x, Map{h, w}, out, reinterpret_cast<float*>(ws), reinterpret_cast<float*>(ws + t0b), &o);
+    return wk.mixed(block, x, Map{h, w}, out, Carver::at(workspace, 0), Carver::at(workspace, t0b), &o);
 }
 
 }  // extern "C"

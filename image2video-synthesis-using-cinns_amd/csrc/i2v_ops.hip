@@ -1,8 +1,8 @@
 // Leaf modules of the cINN, individually callable: BasicFullyConnectedNet, ActNorm, InvLeakyRelu, Shuffle and the
 // ActNorm data-dependent initialisation statistics (reference: stage2_cINN/modules/modules.py, flow_blocks.py:142-187).
 #include <algorithm>
-#include <memory>
 
+#include "i2v_handle.h"
 #include "i2v_linear.h"
 
 namespace i2v {
@@ -117,24 +117,17 @@ extern "C" {
 
 int i2v_mlp_create(int32_t dim, int32_t hidden_dim, int32_t depth, int32_t out_dim, i2v_mlp** out) {
     I2V_REQUIRE(out && dim > 0 && hidden_dim > 0 && depth >= 0 && out_dim > 0, I2V_E_INVALID, "i2v_mlp_create: bad argument");
-    int ndev = 0;
-    I2V_HIP_CHECK(hipGetDeviceCount(&ndev));
-    I2V_REQUIRE(ndev > 0, I2V_E_HIP, "i2v_mlp_create: no HIP device");
-    auto m = std::make_unique<i2v_mlp>();
-    m->dim = dim; m->hidden = hidden_dim; m->depth = depth; m->out_dim = out_dim;
-    m->W.resize(depth + 2);
-    m->b.resize(depth + 2);
-    I2V_HIP_CHECK(hipGetDevice(&m->device));
-    *out = m.release();
-    return I2V_OK;
+    return create_handle("i2v_mlp_create", out, [&](i2v_mlp* m) {
+        m->dim = dim; m->hidden = hidden_dim; m->depth = depth; m->out_dim = out_dim;
+        m->W.resize(depth + 2);
+        m->b.resize(depth + 2);
+        return I2V_OK;
+    });
 }
 
 void i2v_mlp_destroy(i2v_mlp* m) { delete m; }
 
-int i2v_mlp_load(i2v_mlp* m, const i2v_tensor* tensors, int32_t n_tensors) {
-    if (m) I2V_REQUIRE_DEVICE(m->device, "i2v_mlp_load");
-    I2V_REQUIRE(m && tensors && n_tensors > 0, I2V_E_INVALID, "i2v_mlp_load: null argument");
-    StateDict sd(tensors, n_tensors);
+static int mlp_pack(i2v_mlp* m, const StateDict& sd) {
     for (int li = 0; li < m->depth + 2; ++li) {
         const int in = li == 0 ? m->dim : m->hidden, outd = li == m->depth + 1 ? m->out_dim : m->hidden;
         const std::string key = "main." + std::to_string(2 * li);
@@ -145,8 +138,11 @@ int i2v_mlp_load(i2v_mlp* m, const i2v_tensor* tensors, int32_t n_tensors) {
         if ((rc = m->W[li].upload(w, (size_t)in * outd * 4))) return rc;
         if ((rc = m->b[li].upload(b, (size_t)outd * 4))) return rc;
     }
-    m->loaded = true;
     return I2V_OK;
+}
+
+int i2v_mlp_load(i2v_mlp* m, const i2v_tensor* tensors, int32_t n_tensors) {
+    return load_handle("i2v_mlp_load", m, tensors, n_tensors, mlp_pack);
 }
 
 size_t i2v_mlp_workspace_bytes(const i2v_mlp* m, int32_t batch) {
@@ -156,10 +152,9 @@ size_t i2v_mlp_workspace_bytes(const i2v_mlp* m, int32_t batch) {
 
 int i2v_mlp_forward(i2v_mlp* m, const float* x, float* y, void* workspace, size_t workspace_bytes, int32_t batch,
                     void* stream) {
-    if (m) I2V_REQUIRE_DEVICE(m->device, "i2v_mlp_forward");
-    I2V_REQUIRE(m && m->loaded, I2V_E_STATE, "i2v_mlp_forward: weights not loaded");
+    I2V_ENTER(sc, m, Entry::NEEDS_WEIGHTS | Entry::NULL_IS_UNLOADED, "i2v_mlp_forward");
     I2V_REQUIRE(x && y && workspace && batch > 0, I2V_E_INVALID, "i2v_mlp_forward: null argument");
-    I2V_REQUIRE(workspace_bytes >= i2v_mlp_workspace_bytes(m, batch), I2V_E_WORKSPACE, "i2v_mlp_forward: workspace too small");
+    I2V_REQUIRE_WORKSPACE(workspace_bytes, i2v_mlp_workspace_bytes(m, batch), "i2v_mlp_forward");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int B = batch, H = m->hidden;
     float* hA = static_cast<float*>(workspace);

@@ -21,10 +21,9 @@
 // LPIPS as a loss (stage1_VAE/modules/loss.py: w_percep * LPIPS(seq_orig, seq_gen).mean()): the input gradient of the frozen trunk and of
 // the LPIPS head, see "backward (input gradient)" below.
 #include <algorithm>
-#include <memory>
 #include <type_traits>
 
-#include "i2v_common.h"
+#include "i2v_handle.h"
 
 namespace i2v {
 namespace {
@@ -744,23 +743,12 @@ bool vgg_dims_ok(int h, int w) { return (h >> 4) > 0 && (w >> 4) > 0; }
 extern "C" {
 
 int i2v_vgg_create(i2v_vgg** out) {
-    I2V_REQUIRE(out, I2V_E_INVALID, "i2v_vgg_create: null argument");
-    int ndev = 0;
-    I2V_HIP_CHECK(hipGetDeviceCount(&ndev));
-    I2V_REQUIRE(ndev > 0, I2V_E_HIP, "i2v_vgg_create: no HIP device");
-    auto v = std::make_unique<i2v_vgg>();
-    I2V_HIP_CHECK(hipGetDevice(&v->device));
-    *out = v.release();
-    return I2V_OK;
+    return create_handle("i2v_vgg_create", out, [](i2v_vgg*) { return I2V_OK; });
 }
 
 void i2v_vgg_destroy(i2v_vgg* v) { delete v; }
 
-int i2v_vgg_load(i2v_vgg* v, const i2v_tensor* tensors, int32_t n_tensors) {
-    if (v) I2V_REQUIRE_DEVICE(v->device, "i2v_vgg_load");
-    I2V_REQUIRE(v && tensors && n_tensors > 0, I2V_E_INVALID, "i2v_vgg_load: null argument");
-    StateDict sd(tensors, n_tensors);
-    v->loaded = false;
+static int vgg_pack(i2v_vgg* v, const StateDict& sd) {
     v->have_lin = false;
     v->dgrad_ready = false;
     for (int l = 0; l < 13; ++l) v->dgrad_w[l].release();
@@ -780,8 +768,11 @@ int i2v_vgg_load(i2v_vgg* v, const i2v_tensor* tensors, int32_t n_tensors) {
         }
         v->have_lin = true;
     }
-    v->loaded = true;
     return I2V_OK;
+}
+
+int i2v_vgg_load(i2v_vgg* v, const i2v_tensor* tensors, int32_t n_tensors) {
+    return load_handle("i2v_vgg_load", v, tensors, n_tensors, vgg_pack);
 }
 
 const float* i2v_vgg_lin(const i2v_vgg* v, int32_t layer) {
@@ -811,15 +802,14 @@ int i2v_vgg_input_stage(const float* frames, int32_t n, int32_t hi, int32_t wi, 
 
 int i2v_vgg_features(i2v_vgg* v, const float* x, int32_t batch, int32_t h, int32_t w, float* relu1_2, float* relu2_2, float* relu3_3, float* relu4_3,
                      float* relu5_3, void* workspace, size_t workspace_bytes, void* stream) {
-    if (v) I2V_REQUIRE_DEVICE(v->device, "i2v_vgg_features");
-    I2V_REQUIRE(v && v->loaded, I2V_E_STATE, "i2v_vgg_features: weights not loaded");
+    I2V_ENTER(sc, v, Entry::NEEDS_WEIGHTS | Entry::NULL_IS_UNLOADED, "i2v_vgg_features");
     I2V_REQUIRE(x && relu1_2 && relu2_2 && relu3_3 && relu4_3 && relu5_3 && workspace && batch > 0, I2V_E_INVALID, "i2v_vgg_features: bad argument");
     I2V_REQUIRE(vgg_dims_ok(h, w), I2V_E_INVALID, "i2v_vgg_features: a %d x %d input leaves an empty map after four pools (at least 16 x 16 is needed)", h, w);
     I2V_REQUIRE((long)batch * h * w * 64 < VGG_MAX_FLOATS, I2V_E_INVALID, "i2v_vgg_features: batch %d x [%d, %d] is too large", batch, h, w);
     size_t af, bf;
     vgg_ws_floats(batch, h, w, &af, &bf);
     const size_t need = align_up(af * 4, 256) + align_up(bf * 4, 256);
-    I2V_REQUIRE(workspace_bytes >= need, I2V_E_WORKSPACE, "i2v_vgg_features: workspace %zu < required %zu", workspace_bytes, need);
+    I2V_REQUIRE_WORKSPACE(workspace_bytes, need, "i2v_vgg_features");
     float* a = static_cast<float*>(workspace);
     float* b = reinterpret_cast<float*>(static_cast<char*>(workspace) + align_up(af * 4, 256));
     float* taps[5] = {relu1_2, relu2_2, relu3_3, relu4_3, relu5_3};
@@ -839,8 +829,7 @@ size_t i2v_vgg_backward_workspace_bytes(const i2v_vgg* v, int32_t batch, int32_t
 
 int i2v_vgg_features_saved(i2v_vgg* v, const float* x, int32_t batch, int32_t h, int32_t w, float* relu1_2, float* relu2_2, float* relu3_3,
                            float* relu4_3, float* relu5_3, void* saved, size_t saved_bytes, void* workspace, size_t workspace_bytes, void* stream) {
-    if (v) I2V_REQUIRE_DEVICE(v->device, "i2v_vgg_features_saved");
-    I2V_REQUIRE(v && v->loaded, I2V_E_STATE, "i2v_vgg_features_saved: weights not loaded");
+    I2V_ENTER(sc, v, Entry::NEEDS_WEIGHTS | Entry::NULL_IS_UNLOADED, "i2v_vgg_features_saved");
     I2V_REQUIRE(x && relu1_2 && relu2_2 && relu3_3 && relu4_3 && relu5_3 && saved && workspace && batch > 0, I2V_E_INVALID,
                 "i2v_vgg_features_saved: bad argument");
     I2V_REQUIRE(vgg_dims_ok(h, w), I2V_E_INVALID,
@@ -849,7 +838,7 @@ int i2v_vgg_features_saved(i2v_vgg* v, const float* x, int32_t batch, int32_t h,
     size_t af, bf, off[13];
     vgg_ws_floats(batch, h, w, &af, &bf);
     const size_t need = align_up(af * 4, 256) + align_up(bf * 4, 256), need_saved = vgg_saved_offsets(batch, h, w, off);
-    I2V_REQUIRE(workspace_bytes >= need, I2V_E_WORKSPACE, "i2v_vgg_features_saved: workspace %zu < required %zu", workspace_bytes, need);
+    I2V_REQUIRE_WORKSPACE(workspace_bytes, need, "i2v_vgg_features_saved");
     I2V_REQUIRE(saved_bytes >= need_saved, I2V_E_WORKSPACE, "i2v_vgg_features_saved: saved state %zu < required %zu", saved_bytes, need_saved);
     float* a = static_cast<float*>(workspace);
     float* b = reinterpret_cast<float*>(static_cast<char*>(workspace) + align_up(af * 4, 256));
@@ -859,8 +848,7 @@ int i2v_vgg_features_saved(i2v_vgg* v, const float* x, int32_t batch, int32_t h,
 
 int i2v_vgg_backward(i2v_vgg* v, const float* const* taps, const float* const* tap_grads, const void* saved, size_t saved_bytes, int32_t batch,
                      int32_t h, int32_t w, float* out, int32_t frames_out, void* workspace, size_t workspace_bytes, void* stream) {
-    if (v) I2V_REQUIRE_DEVICE(v->device, "i2v_vgg_backward");
-    I2V_REQUIRE(v && v->loaded, I2V_E_STATE, "i2v_vgg_backward: weights not loaded");
+    I2V_ENTER(sc, v, Entry::NEEDS_WEIGHTS | Entry::NULL_IS_UNLOADED, "i2v_vgg_backward");
     I2V_REQUIRE(saved, I2V_E_STATE, "i2v_vgg_backward: no saved state (run i2v_vgg_features_saved first: i2v_vgg_features keeps only the taps)");
     I2V_REQUIRE(taps && tap_grads && out && workspace && batch > 0, I2V_E_INVALID, "i2v_vgg_backward: bad argument");
     for (int k = 0; k < 5; ++k) I2V_REQUIRE(taps[k] && tap_grads[k], I2V_E_INVALID, "i2v_vgg_backward: tap %d or its gradient is null", k);
@@ -870,7 +858,7 @@ int i2v_vgg_backward(i2v_vgg* v, const float* const* taps, const float* const* t
     size_t off[13];
     const size_t need_saved = vgg_saved_offsets(batch, h, w, off), half = align_up((size_t)batch * h * w * 64 * 4, 256);
     I2V_REQUIRE(saved_bytes >= need_saved, I2V_E_WORKSPACE, "i2v_vgg_backward: saved state %zu < required %zu", saved_bytes, need_saved);
-    I2V_REQUIRE(workspace_bytes >= 2 * half, I2V_E_WORKSPACE, "i2v_vgg_backward: workspace %zu < required %zu", workspace_bytes, 2 * half);
+    I2V_REQUIRE_WORKSPACE(workspace_bytes, 2 * half, "i2v_vgg_backward");
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (int rc = ensure_dgrad(v, st)) return rc;
 

@@ -271,6 +271,11 @@ def _require_gpu(*tensors):
             raise I2VError(f"expected a contiguous float32 tensor, got {t.dtype} contiguous={t.is_contiguous()}")
 
 
+def _call(name, *args):
+    """One status-returning entry of the library; a non-zero code raises I2VError with the library's message."""
+    _check(getattr(lib(), name)(*args), name)
+
+
 def _stream():
     return c_void_p(torch.cuda.current_stream().cuda_stream)
 
@@ -288,10 +293,61 @@ def _device_of(device):
     return torch.device("cuda", device.index if device.index is not None else torch.cuda.current_device())
 
 
+class _Workspace:
+    """Caller-owned device scratch, cached per (device, size class) so its address is stable across calls."""
+
+    def __init__(self):
+        self.buf = None
+
+    def get(self, nbytes, device):
+        if self.buf is None or self.buf.numel() < nbytes or self.buf.device != device:
+            self.buf = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+        return self.buf
+
+
+def _on_device(fn):
+    """Method decorator of the native handles: reject tensors that live on another GPU, run with the handle's device current."""
+    @functools.wraps(fn)
+    def wrapper(self, *args, **kwargs):
+        tensors = [t for t in list(args) + list(kwargs.values()) if isinstance(t, torch.Tensor)]
+        with self._on(*tensors):
+            return fn(self, *args, **kwargs)
+    return wrapper
+
+
 class _Handle:
-    """Common part of the native handles: the device binding.  Creation, load and every call run with the handle's device
-    current (``torch.cuda.device``), so the weights, the launches and the stream all belong to the GPU the tensors live on;
-    tensors on another device are rejected (the C side checks the same thing and returns I2V_E_INVALID)."""
+    """Common part of the native handles: the lifecycle (``<_PREFIX>_create`` / ``_load`` / ``_destroy``), the cached workspace and
+    the device binding.  Creation, load and every call run with the handle's device current (``torch.cuda.device``), so the
+    weights, the launches and the stream all belong to the GPU the tensors live on; tensors on another device are rejected (the
+    C side checks the same thing and returns I2V_E_INVALID)."""
+    _PREFIX = None   # "i2v_mlp", ...
+    _h = None
+
+    def _create(self, device, *args, symbol=None):
+        """``<_PREFIX>_create(*args, &handle)`` (or ``symbol``) with ``device`` current."""
+        h = c_void_p()
+        with self._bind(device):
+            _call(symbol or self._PREFIX + "_create", *args, ctypes.byref(h))
+        self._h = h
+        self._ws = _Workspace()
+
+    def __del__(self):   # (the attributes -- a decoder's shared side stream, which its destroy synchronises -- are released after this)
+        if self._h and _lib is not None:
+            getattr(_lib, self._PREFIX + "_destroy")(self._h)
+            self._h = None
+
+    @_on_device
+    def load(self, state_dict):
+        """``<_PREFIX>_load``.  A load that fails leaves the handle unloaded: its next forward raises (I2V_E_STATE)."""
+        arr, keep = _pack_state_dict(state_dict)
+        _call(self._PREFIX + "_load", self._h, arr, len(arr))
+        del keep
+
+    def _scratch(self, nbytes, device, ws=None):
+        """(pointer, size) of the handle's cached workspace (``ws``: another cache than ``_ws``), grown to ``nbytes``: the two
+        arguments every forward passes as ``*ws``."""
+        buf = (ws or self._ws).get(nbytes, device)
+        return buf.data_ptr(), buf.numel()
 
     def _bind(self, device):
         self.device = _device_of(device)
@@ -327,53 +383,17 @@ def _pack_state_dict(sd):
     return arr, keep
 
 
-class _Workspace:
-    """Caller-owned device scratch, cached per (device, size class) so its address is stable across calls."""
-
-    def __init__(self):
-        self.buf = None
-
-    def get(self, nbytes, device):
-        if self.buf is None or self.buf.numel() < nbytes or self.buf.device != device:
-            self.buf = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
-        return self.buf
-
-
-def _on_device(fn):
-    """Method decorator of the native handles: reject tensors that live on another GPU, run with the handle's device current."""
-    @functools.wraps(fn)
-    def wrapper(self, *args, **kwargs):
-        tensors = [t for t in list(args) + list(kwargs.values()) if isinstance(t, torch.Tensor)]
-        with self._on(*tensors):
-            return fn(self, *args, **kwargs)
-    return wrapper
-
-
 class NativeFlow(_Handle):
     """Handle for ``i2v_flow_*`` (ConditionalFlow, flow_blocks.py:8-60)."""
+    _PREFIX = "i2v_flow"
 
     def __init__(self, in_channels, embedding_dim, hidden_dim, hidden_depth, n_flows, control=False,
                  activation="lrelu", skip_actnorm=False, skip_shuffle=False, use_graph=True, device=None, linear_f16=None):
         self.linear_f16 = default_flow_f16() if linear_f16 is None else int(bool(linear_f16))
         cfg = FlowCfg(in_channels, embedding_dim, hidden_dim, hidden_depth, n_flows, int(control),
                       1 if activation == "lrelu" else 0, int(skip_actnorm), int(skip_shuffle), int(use_graph), self.linear_f16)
-        h = c_void_p()
-        with self._bind(device):
-            _check(lib().i2v_flow_create(ctypes.byref(cfg), ctypes.byref(h)), "i2v_flow_create")
-        self._h = h
+        self._create(device, ctypes.byref(cfg))
         self.embedding_dim = embedding_dim
-        self._ws = _Workspace()
-
-    def __del__(self):
-        if getattr(self, "_h", None) and _lib is not None:
-            _lib.i2v_flow_destroy(self._h)
-            self._h = None
-
-    @_on_device
-    def load(self, state_dict):
-        arr, keep = _pack_state_dict(state_dict)
-        _check(lib().i2v_flow_load(self._h, arr, len(arr)), "i2v_flow_load")
-        del keep
 
     @property
     def param_bytes(self):
@@ -384,7 +404,7 @@ class NativeFlow(_Handle):
         {"chain": "tile" | "generic", "kpw": k-blocks per wave, "ns": sample tiles per workgroup, "fold": bool}; kpw = ns = 0 and
         fold False on the generic chain."""
         v = [c_int32() for _ in range(4)]
-        _check(lib().i2v_flow_plan(self._h, int(batch), *(ctypes.byref(i) for i in v)), "i2v_flow_plan")
+        _call("i2v_flow_plan", self._h, int(batch), *(ctypes.byref(i) for i in v))
         chain, kpw, ns, fold = (i.value for i in v)
         return {"chain": "tile" if chain else "generic", "kpw": kpw, "ns": ns, "fold": bool(fold)}
 
@@ -395,15 +415,14 @@ class NativeFlow(_Handle):
         if x.shape != (B, 64) or embed.shape != (B, self.embedding_dim):
             raise I2VError(f"flow: expected x [B,64] and embed [B,{self.embedding_dim}], got {tuple(x.shape)}, {tuple(embed.shape)}")
         nbytes = lib().i2v_flow_workspace_bytes(self._h, B)
-        ws = self._ws.get(nbytes, x.device)
+        ws = self._scratch(nbytes, x.device)
         out = torch.empty_like(x)
         if reverse:
-            _check(lib().i2v_flow_inverse(self._h, x.data_ptr(), embed.data_ptr(), out.data_ptr(), ws.data_ptr(),
-                                          ws.numel(), B, _stream()), "i2v_flow_inverse")
+            _call("i2v_flow_inverse", self._h, x.data_ptr(), embed.data_ptr(), out.data_ptr(), *ws, B, _stream())
             return out
         logdet = torch.empty(B, dtype=torch.float32, device=x.device)
-        _check(lib().i2v_flow_forward(self._h, x.data_ptr(), embed.data_ptr(), out.data_ptr(), logdet.data_ptr(),
-                                      ws.data_ptr(), ws.numel(), B, _stream()), "i2v_flow_forward")
+        _call("i2v_flow_forward", self._h, x.data_ptr(), embed.data_ptr(), out.data_ptr(), logdet.data_ptr(),
+                                  *ws, B, _stream())
         return out, logdet
 
     @_on_device
@@ -419,23 +438,19 @@ class NativeFlowTrain(_Handle):
     nothing: ``bind`` hands over the DEVICE pointers of the module's own parameters, which the kernels read in place, so an
     optimiser step on them needs no re-load.  Gradients go either into bound tensors (``bind(..., grads=...)``) or into one flat
     buffer per backward call whose layout ``bind`` fixes (``flat_numel`` floats, ``flat_slices[name] = (offset, numel)``)."""
+    _PREFIX = "i2v_flow_train"
 
     def __init__(self, in_channels, embedding_dim, hidden_dim, hidden_depth, n_flows, control=0, activation="lrelu",
                  skip_actnorm=False, skip_shuffle=False, device=None, linear_f16=0):
         cfg = FlowCfg(in_channels, embedding_dim, hidden_dim, hidden_depth, n_flows, int(control),
                       1 if activation == "lrelu" else 0, int(skip_actnorm), int(skip_shuffle), 0, int(bool(linear_f16)))
-        h = c_void_p()
-        with self._bind(device):
-            _check(lib().i2v_flow_train_create(ctypes.byref(cfg), ctypes.byref(h)), "i2v_flow_train_create")
-        self._h = h
+        self._create(device, ctypes.byref(cfg))
         self.embedding_dim = embedding_dim
         self._geometry = (hidden_dim, hidden_depth, embedding_dim, n_flows)
         self.flat_numel, self.flat_slices, self.bound_ptrs, self._keep = 0, {}, None, None
 
-    def __del__(self):
-        if getattr(self, "_h", None) and _lib is not None:
-            _lib.i2v_flow_train_destroy(self._h)
-            self._h = None
+    def load(self, state_dict):
+        raise I2VError("NativeFlowTrain packs nothing: bind() hands over the module's own parameters")
 
     @staticmethod
     def pointers(tensors):
@@ -469,7 +484,7 @@ class NativeFlowTrain(_Handle):
                     gitems.append(_Tensor(kb, g.data_ptr(), g.numel(), I2V_F32))
             n = len(items)
             gitems += [_Tensor(b"", None, 0, I2V_U8)] * (n - len(gitems))
-            _check(lib().i2v_flow_train_bind(self._h, (_Tensor * n)(*items), (_Tensor * n)(*gitems), n), "i2v_flow_train_bind")
+            _call("i2v_flow_train_bind", self._h, (_Tensor * n)(*items), (_Tensor * n)(*gitems), n)
         self.flat_numel, self.flat_slices = (off, slices) if grads is None else (0, {})
         self.bound_ptrs = self.pointers(tensors)
         self._keep = (tensors, grads)
@@ -477,7 +492,7 @@ class NativeFlowTrain(_Handle):
     def saved_layout(self, B):
         """{field: value} of ``i2v_flow_train_saved_layout`` at batch B: where each region of ``saved`` lies, in floats."""
         out = FlowTrainLayout()
-        _check(lib().i2v_flow_train_saved_layout(*self._geometry, B, ctypes.byref(out)), "i2v_flow_train_saved_layout")
+        _call("i2v_flow_train_saved_layout", *self._geometry, B, ctypes.byref(out))
         return {n: int(getattr(out, n)) for n, _ in FlowTrainLayout._fields_}
 
     def forward(self, x, embed, saved=None):
@@ -494,8 +509,8 @@ class NativeFlowTrain(_Handle):
                 raise I2VError("flow training: `saved` must be a contiguous uint8 tensor on a HIP device")
             zt = torch.empty_like(x)
             logdet = torch.empty(B, dtype=torch.float32, device=x.device)
-            _check(lib().i2v_flow_train_forward(self._h, x.data_ptr(), embed.data_ptr(), zt.data_ptr(), logdet.data_ptr(), saved.data_ptr(),
-                                                saved.numel(), B, _stream()), "i2v_flow_train_forward")
+            _call("i2v_flow_train_forward", self._h, x.data_ptr(), embed.data_ptr(), zt.data_ptr(), logdet.data_ptr(), saved.data_ptr(),
+                                            saved.numel(), B, _stream())
         return zt, logdet, saved
 
     def backward(self, d_zt, d_logdet, saved, flat_grads=None, accumulate=False, need_dx=False, need_dembed=False):
@@ -508,18 +523,17 @@ class NativeFlowTrain(_Handle):
         with self._on(d_zt, d_logdet, saved, flat_grads):
             dx = torch.empty(B, 64, dtype=torch.float32, device=d_zt.device) if need_dx else None
             de = torch.empty(B, self.embedding_dim, dtype=torch.float32, device=d_zt.device) if need_dembed else None
-            _check(lib().i2v_flow_train_backward(self._h, d_zt.data_ptr(), d_logdet.data_ptr(), saved.data_ptr(), saved.numel(),
-                                                 None if dx is None else dx.data_ptr(), None if de is None else de.data_ptr(),
-                                                 None if flat_grads is None else flat_grads.data_ptr(), int(bool(accumulate)), B, _stream()),
-                   "i2v_flow_train_backward")
+            _call("i2v_flow_train_backward", self._h, d_zt.data_ptr(), d_logdet.data_ptr(), saved.data_ptr(), saved.numel(),
+                                             None if dx is None else dx.data_ptr(), None if de is None else de.data_ptr(),
+                                             None if flat_grads is None else flat_grads.data_ptr(), int(bool(accumulate)), B, _stream())
         return dx, de
 
 
 def adam_step(table, chunks, lr, beta1, beta2, eps, weight_decay, amsgrad, step):
     """One fused Adam launch over a device table of ``AdamTensor`` rows (uint8 tensor) and its chunk list (int32 [n, 2])."""
     with torch.cuda.device(table.device):
-        _check(lib().i2v_adam_step(table.data_ptr(), chunks.data_ptr(), chunks.shape[0], lr, beta1, beta2, eps, weight_decay,
-                                   int(bool(amsgrad)), int(step), _stream()), "i2v_adam_step")
+        _call("i2v_adam_step", table.data_ptr(), chunks.data_ptr(), chunks.shape[0], lr, beta1, beta2, eps, weight_decay,
+                               int(bool(amsgrad)), int(step), _stream())
 
 
 def check_realizations(img, motion, z_dim, realizations):
@@ -538,44 +552,28 @@ def check_realizations(img, motion, z_dim, realizations):
 
 class NativeDecoder(_Handle):
     """Handle for ``i2v_dec_*`` (Generator, decoder.py:55-120)."""
+    _PREFIX = "i2v_dec"
 
     def __init__(self, channel_factor, z_dim, upsample_s, upsample_t, spectral_norm=True, mma=0, device=None):
         cfg = DecCfg(channel_factor, z_dim, (c_int32 * 2)(*upsample_s), (c_int32 * 2)(*upsample_t),
                      int(bool(spectral_norm)), mma)
-        h = c_void_p()
-        with self._bind(device):
-            _check(lib().i2v_dec_create(ctypes.byref(cfg), ctypes.byref(h)), "i2v_dec_create")
-        self._h = h
+        self._create(device, ctypes.byref(cfg))
         self.z_dim = z_dim
-        self._ws = _Workspace()
         t, hh, w = c_int32(), c_int32(), c_int32()
-        _check(lib().i2v_dec_out_shape(self._h, ctypes.byref(t), ctypes.byref(hh), ctypes.byref(w)), "i2v_dec_out_shape")
+        _call("i2v_dec_out_shape", self._h, ctypes.byref(t), ctypes.byref(hh), ctypes.byref(w))
         self.out_shape = (t.value, hh.value, w.value)
-
-    def __del__(self):
-        if getattr(self, "_h", None) and _lib is not None:
-            _lib.i2v_dec_destroy(self._h)     # (synchronises the side stream; a shared one is still alive: _side_stream is released below)
-            self._h = None
-        self._side_stream = None
-
-    @_on_device
-    def load(self, state_dict):
-        arr, keep = _pack_state_dict(state_dict)
-        _check(lib().i2v_dec_load(self._h, arr, len(arr)), "i2v_dec_load")
-        del keep
 
     def flops_per_sample(self, img_h, img_w):
         return float(lib().i2v_dec_flops_per_sample(self._h, img_h, img_w))
 
     @_on_device
     def set_profile(self, on):
-        _check(lib().i2v_dec_set_profile(self._h, int(on)), "i2v_dec_set_profile")
+        _call("i2v_dec_set_profile", self._h, int(on))
 
     @_on_device
     def get_profile(self):
         a, b, e, c = c_double(), c_double(), c_double(), c_int64()
-        _check(lib().i2v_dec_get_profile(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(e), ctypes.byref(c)),
-               "i2v_dec_get_profile")
+        _call("i2v_dec_get_profile", self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(e), ctypes.byref(c))
         return {"conv3_ms": a.value, "conv3_flops": b.value, "conv3_mfma_flops": e.value, "conv3_launches": c.value}
 
     # i2v_dec_get_layer_profile's kernel code -> name
@@ -589,8 +587,8 @@ class NativeDecoder(_Handle):
         for layer in range(12):
             name = ctypes.create_string_buffer(48)
             ms, fl, ex, n, k = c_double(), c_double(), c_double(), c_int64(), c_int32()
-            _check(lib().i2v_dec_get_layer_profile(self._h, layer, name, 48, ctypes.byref(ms), ctypes.byref(fl), ctypes.byref(ex),
-                                                   ctypes.byref(n), ctypes.byref(k)), "i2v_dec_get_layer_profile")
+            _call("i2v_dec_get_layer_profile", self._h, layer, name, 48, ctypes.byref(ms), ctypes.byref(fl), ctypes.byref(ex),
+                                               ctypes.byref(n), ctypes.byref(k))
             if n.value:
                 rows.append({"layer": name.value.decode(), "kernel": self.KERNEL_NAMES[k.value],
                              "launches": int(n.value), "ms": ms.value, "flops": fl.value, "mfma_flops": ex.value})
@@ -601,7 +599,7 @@ class NativeDecoder(_Handle):
         """Range guard of the split-fp16 operand format (i2v_dec_status): synchronises the current stream and returns the
         sticky flag word (bit 0: an activation left the fp16 range, the outputs since then are invalid)."""
         flags = c_int32()
-        _check(lib().i2v_dec_status(self._h, ctypes.byref(flags), int(bool(reset)), _stream()), "i2v_dec_status")
+        _call("i2v_dec_status", self._h, ctypes.byref(flags), int(bool(reset)), _stream())
         return int(flags.value)
 
     LAYER_NAMES = tuple(f"{b}.conv_{i}" for b in ("head_0", "g_0", "g_1", "g_2", "g_3", "g_4") for i in (0, 1))
@@ -610,7 +608,7 @@ class NativeDecoder(_Handle):
         """mma = auto (i2v_dec_fallback_layers): the 3x3x3 convs the range guard has switched to the exact-fp32 kernels so far, as
         ``{"layers": [names], "whole_handle": bool, "reruns": n}``.  Empty for a checkpoint inside the split format's window."""
         mask, reruns = c_int32(), c_int32()
-        _check(lib().i2v_dec_fallback_layers(self._h, ctypes.byref(mask), ctypes.byref(reruns)), "i2v_dec_fallback_layers")
+        _call("i2v_dec_fallback_layers", self._h, ctypes.byref(mask), ctypes.byref(reruns))
         return {"layers": [n for i, n in enumerate(self.LAYER_NAMES) if mask.value >> i & 1], "whole_handle": bool(mask.value >> 30 & 1),
                 "reruns": int(reruns.value)}
 
@@ -618,9 +616,9 @@ class NativeDecoder(_Handle):
     def debug_tap(self, block, which, dst):
         """Test hook (i2v_dec_debug_tap): dst = float32 CUDA tensor or None."""
         if dst is None:
-            _check(lib().i2v_dec_debug_tap(self._h, -1, -1, None, 0), "i2v_dec_debug_tap")
+            _call("i2v_dec_debug_tap", self._h, -1, -1, None, 0)
         else:
-            _check(lib().i2v_dec_debug_tap(self._h, block, which, dst.data_ptr(), dst.numel()), "i2v_dec_debug_tap")
+            _call("i2v_dec_debug_tap", self._h, block, which, dst.data_ptr(), dst.numel())
 
     SPADE_FORMS = ("f43", "f23", "hl16", "f32")   # i2v_dec_get_spade_form's codes: the gamma | beta conv's kernel (dec_units_common names)
 
@@ -629,7 +627,7 @@ class NativeDecoder(_Handle):
         out = []
         for k in range(6):
             f = c_int32(-1)
-            _check(lib().i2v_dec_get_spade_form(self._h, k, ctypes.byref(f)), "i2v_dec_get_spade_form")
+            _call("i2v_dec_get_spade_form", self._h, k, ctypes.byref(f))
             out.append(self.SPADE_FORMS[f.value] if f.value >= 0 else None)
         return out
 
@@ -647,19 +645,18 @@ class NativeDecoder(_Handle):
         The binding keeps the stream object alive for as long as the handle uses it."""
         if stream is not None and stream.device != self.device:
             raise I2VError(f"side stream on {stream.device} for a handle on {self.device}")
-        _check(lib().i2v_dec_set_side_stream(self._h, c_void_p(stream.cuda_stream) if stream is not None else None),
-               "i2v_dec_set_side_stream")
+        _call("i2v_dec_set_side_stream", self._h, c_void_p(stream.cuda_stream) if stream is not None else None)
         self._side_stream = stream
         self._prep = None
 
-    def _workspace(self, nbytes, device):
+    def _scratch(self, nbytes, device):
         """The handle's workspace; before it is REPLACED by a larger one, the current stream joins the handle's side stream (a forked
         prepare may still be writing the old buffer: i2v_dec_join), so the caching allocator's stream-ordered free is safe."""
         buf = self._ws.buf
         if buf is not None and (buf.numel() < nbytes or buf.device != device):
-            _check(lib().i2v_dec_join(self._h, _stream()), "i2v_dec_join")
+            _call("i2v_dec_join", self._h, _stream())
             self._prep = None
-        return self._ws.get(nbytes, device)
+        return super()._scratch(nbytes, device)
 
     @staticmethod
     def _version(t):
@@ -684,7 +681,7 @@ class NativeDecoder(_Handle):
         # every check BEFORE any state changes: a raise must leave the Python side and the C side agreeing (nothing prepared)
         if getattr(self, "_prep", None) is not None:
             self._prep = None
-            _check(lib().i2v_dec_prepare_cancel(self._h), "i2v_dec_prepare_cancel")
+            _call("i2v_dec_prepare_cancel", self._h)
         K = check_realizations(None, None, None, realizations)
         _require_gpu(img)
         B = img.shape[0]
@@ -695,14 +692,13 @@ class NativeDecoder(_Handle):
             return
         if K == 1:
             nbytes = lib().i2v_dec_workspace_bytes(self._h, B, img.shape[2], img.shape[3])
-            ws = self._workspace(nbytes, img.device)
-            _check(lib().i2v_dec_prepare(self._h, img.data_ptr(), img.shape[2], img.shape[3], ws.data_ptr(), ws.numel(), B, _stream()),
-                   "i2v_dec_prepare")
+            ws = self._scratch(nbytes, img.device)
+            _call("i2v_dec_prepare", self._h, img.data_ptr(), img.shape[2], img.shape[3], *ws, B, _stream())
         else:
             nbytes = lib().i2v_dec_workspace_bytes_realizations(self._h, B, K, img.shape[2], img.shape[3])
-            ws = self._workspace(nbytes, img.device)
-            _check(lib().i2v_dec_prepare_realizations(self._h, img.data_ptr(), img.shape[2], img.shape[3], B, K, ws.data_ptr(), ws.numel(),
-                                                      _stream()), "i2v_dec_prepare_realizations")
+            ws = self._scratch(nbytes, img.device)
+            _call("i2v_dec_prepare_realizations", self._h, img.data_ptr(), img.shape[2], img.shape[3], B, K, *ws,
+                                                  _stream())
         # the C side recognises the prepared frames by ADDRESS; a caching allocator hands the same address to the next same-size
         # tensor and a buffer refilled in place keeps it, so the binding also remembers WHICH tensor (weak) and its version
         self._prep = (weakref.ref(img), ver)
@@ -736,7 +732,7 @@ class NativeDecoder(_Handle):
                 raise I2VError(f"expected float32 tensors, got {t.dtype}")
         prep, self._prep = getattr(self, "_prep", None), None
         if prep is not None and (prep[0]() is not img or prep[1] != self._version(img)):
-            _check(lib().i2v_dec_prepare_cancel(self._h), "i2v_dec_prepare_cancel")   # another tensor, or this one was written since
+            _call("i2v_dec_prepare_cancel", self._h)   # another tensor, or this one was written since
         Fr = img.shape[0]
         B = Fr * K
         if img.dim() != 4 or img.shape[1] != 3 or motion.shape != (B, self.z_dim):
@@ -751,7 +747,7 @@ class NativeDecoder(_Handle):
             nbytes = lib().i2v_dec_workspace_bytes(self._h, B, img.shape[2], img.shape[3])
         else:
             nbytes = lib().i2v_dec_workspace_bytes_realizations(self._h, Fr, K, img.shape[2], img.shape[3])
-        ws = self._workspace(nbytes, img.device)
+        ws = self._scratch(nbytes, img.device)
         T, H, W = self.out_shape
         if out is None:
             out = torch.empty(B, T, 3, H, W, dtype=torch.float32, device=img.device)
@@ -760,11 +756,11 @@ class NativeDecoder(_Handle):
             raise I2VError(f"decoder: out must be a float32 [B={B},{T},3,{H},{W}] view on {img.device} with contiguous sample blocks, "
                            f"got {tuple(out.shape)} strides {out.stride()}")
         if K == 1:
-            _check(lib().i2v_dec_forward_strided(self._h, iv[0], img.shape[2], img.shape[3], iv[1], motion.data_ptr(), ov[0], ov[1],
-                                                 ws.data_ptr(), ws.numel(), B, _stream()), "i2v_dec_forward_strided")
+            _call("i2v_dec_forward_strided", self._h, iv[0], img.shape[2], img.shape[3], iv[1], motion.data_ptr(), ov[0], ov[1],
+                                             *ws, B, _stream())
         else:
-            _check(lib().i2v_dec_forward_realizations(self._h, iv[0], img.shape[2], img.shape[3], iv[1], Fr, K, motion.data_ptr(), ov[0],
-                                                      ov[1], ws.data_ptr(), ws.numel(), _stream()), "i2v_dec_forward_realizations")
+            _call("i2v_dec_forward_realizations", self._h, iv[0], img.shape[2], img.shape[3], iv[1], Fr, K, motion.data_ptr(), ov[0],
+                                                  ov[1], *ws, _stream())
         return out
 
 
@@ -794,9 +790,9 @@ def conv_img_unit(x_cl, weight, bias, form=None, out=None, info=None):
     bstride = out.stride(0) if B > 1 else 0
     used, tch, flag = c_int32(-1), c_int32(0), c_int32(0)
     with torch.cuda.device(x_cl.device):
-        _check(lib().i2v_conv_img_unit(x_cl.data_ptr(), w.ctypes.data_as(c_void_p), b.ctypes.data_as(c_void_p), B, T, H, W, C,
-                                       -1 if form is None else CONV_IMG_FORMS.index(form), out.data_ptr(), bstride, ctypes.byref(used),
-                                       ctypes.byref(tch), ctypes.byref(flag), _stream()), "i2v_conv_img_unit")
+        _call("i2v_conv_img_unit", x_cl.data_ptr(), w.ctypes.data_as(c_void_p), b.ctypes.data_as(c_void_p), B, T, H, W, C,
+                                   -1 if form is None else CONV_IMG_FORMS.index(form), out.data_ptr(), bstride, ctypes.byref(used),
+                                   ctypes.byref(tch), ctypes.byref(flag), _stream())
     if info is not None:
         info.update(form=CONV_IMG_FORMS[used.value], tch=tch.value, range_flag=flag.value)
     return out
@@ -825,10 +821,10 @@ def pointwise_unit(x, weight, bias=None, res=None, coef=None, rows_per_sample=No
     out = torch.empty((Cout, M) if transposed else (M, Cout), dtype=torch.float32, device=x.device)
     tile, flag = c_int32(0), c_int32(0)
     with torch.cuda.device(x.device):
-        _check(lib().i2v_pointwise_unit(x.data_ptr(), w.ctypes.data_as(c_void_p), None if b is None else b.ctypes.data_as(c_void_p),
-                                        None if res is None else res.data_ptr(), None if coef is None else coef.data_ptr(), out.data_ptr(), M, P,
-                                        Cin, Cout, int(bool(lrelu)), int(bool(split16)), int(bool(transposed)), ctypes.byref(tile),
-                                        ctypes.byref(flag), _stream()), "i2v_pointwise_unit")
+        _call("i2v_pointwise_unit", x.data_ptr(), w.ctypes.data_as(c_void_p), None if b is None else b.ctypes.data_as(c_void_p),
+                                    None if res is None else res.data_ptr(), None if coef is None else coef.data_ptr(), out.data_ptr(), M, P,
+                                    Cin, Cout, int(bool(lrelu)), int(bool(split16)), int(bool(transposed)), ctypes.byref(tile),
+                                    ctypes.byref(flag), _stream())
     if info is not None:
         info.update(tile_n=tile.value, range_flag=flag.value)
     return out
@@ -836,25 +832,11 @@ def pointwise_unit(x, weight, bias=None, res=None, coef=None, rows_per_sample=No
 
 class NativeMLP(_Handle):
     """Handle for ``i2v_mlp_*`` (BasicFullyConnectedNet, modules.py:9-30)."""
+    _PREFIX = "i2v_mlp"
 
     def __init__(self, dim, hidden_dim, depth, out_dim, device=None):
-        h = c_void_p()
-        with self._bind(device):
-            _check(lib().i2v_mlp_create(dim, hidden_dim, depth, out_dim, ctypes.byref(h)), "i2v_mlp_create")
-        self._h = h
+        self._create(device, dim, hidden_dim, depth, out_dim)
         self.dim, self.out_dim = dim, out_dim
-        self._ws = _Workspace()
-
-    def __del__(self):
-        if getattr(self, "_h", None) and _lib is not None:
-            _lib.i2v_mlp_destroy(self._h)
-            self._h = None
-
-    @_on_device
-    def load(self, state_dict):
-        arr, keep = _pack_state_dict(state_dict)
-        _check(lib().i2v_mlp_load(self._h, arr, len(arr)), "i2v_mlp_load")
-        del keep
 
     @_on_device
     def forward(self, x):
@@ -862,10 +844,9 @@ class NativeMLP(_Handle):
         if x.dim() != 2 or x.shape[1] != self.dim:
             raise I2VError(f"mlp: expected x [B,{self.dim}], got {tuple(x.shape)}")
         B = x.shape[0]
-        ws = self._ws.get(lib().i2v_mlp_workspace_bytes(self._h, B), x.device)
+        ws = self._scratch(lib().i2v_mlp_workspace_bytes(self._h, B), x.device)
         y = torch.empty(B, self.out_dim, dtype=torch.float32, device=x.device)
-        _check(lib().i2v_mlp_forward(self._h, x.data_ptr(), y.data_ptr(), ws.data_ptr(), ws.numel(), B, _stream()),
-               "i2v_mlp_forward")
+        _call("i2v_mlp_forward", self._h, x.data_ptr(), y.data_ptr(), *ws, B, _stream())
         return y
 
 
@@ -880,9 +861,9 @@ def _channel_op(op, x, p0=None, p1=None, idx=None, alpha=0.0):
     inner = x.numel() // (B * C)
     out = torch.empty_like(x)
     with torch.cuda.device(x.device):
-        _check(lib().i2v_channel_op(op, x.data_ptr(), out.data_ptr(), B, C, inner,
-                                    p0.data_ptr() if p0 is not None else None, p1.data_ptr() if p1 is not None else None,
-                                    idx.data_ptr() if idx is not None else None, float(alpha), _stream()), "i2v_channel_op")
+        _call("i2v_channel_op", op, x.data_ptr(), out.data_ptr(), B, C, inner,
+                                p0.data_ptr() if p0 is not None else None, p1.data_ptr() if p1 is not None else None,
+                                idx.data_ptr() if idx is not None else None, float(alpha), _stream())
     return out
 
 
@@ -899,8 +880,7 @@ def actnorm_logdet(scale, hw, batch):
     _require_gpu(scale)
     out = torch.empty(batch, dtype=torch.float32, device=scale.device)
     with torch.cuda.device(scale.device):
-        _check(lib().i2v_actnorm_logdet(scale.data_ptr(), scale.numel(), float(hw), out.data_ptr(), batch, _stream()),
-               "i2v_actnorm_logdet")
+        _call("i2v_actnorm_logdet", scale.data_ptr(), scale.numel(), float(hw), out.data_ptr(), batch, _stream())
     return out
 
 
@@ -915,8 +895,7 @@ def probe_mfma_f16(device, workgroups=2048, iters=4096, reps=3):
         for r in range(reps + 1):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            _check(lib().i2v_probe_mfma_f16(workgroups, iters, scratch.data_ptr(), ctypes.byref(flops), _stream()),
-                   "i2v_probe_mfma_f16")
+            _call("i2v_probe_mfma_f16", workgroups, iters, scratch.data_ptr(), ctypes.byref(flops), _stream())
             e1.record()
             e1.synchronize()
             if r:
@@ -943,7 +922,7 @@ def channel_mean_std(flat):
     mean = torch.empty(C, dtype=torch.float32, device=flat.device)
     std = torch.empty(C, dtype=torch.float32, device=flat.device)
     with torch.cuda.device(flat.device):
-        _check(lib().i2v_row_mean_std(flat.data_ptr(), C, N, mean.data_ptr(), std.data_ptr(), _stream()), "i2v_row_mean_std")
+        _call("i2v_row_mean_std", flat.data_ptr(), C, N, mean.data_ptr(), std.data_ptr(), _stream())
     return mean, std
 
 
@@ -1002,7 +981,7 @@ def frames_peak(x, out=None, accumulate=False):
     out = _frames_peak_cell(out, x.device)
     cfg = FramesCfg(n=n, t=t, h=h, w=w, n_stride=ns, k=1)
     with torch.cuda.device(x.device):
-        _check(lib().i2v_frames_peak(x.data_ptr(), ctypes.byref(cfg), out.data_ptr(), int(bool(accumulate)), _stream()), "i2v_frames_peak")
+        _call("i2v_frames_peak", x.data_ptr(), ctypes.byref(cfg), out.data_ptr(), int(bool(accumulate)), _stream())
     return out
 
 
@@ -1050,8 +1029,8 @@ def frames_to_u8(x, peak=None, out=None, mode="peak", layout="strip", row0=0, co
     if layout == "strip":
         cfg.dst_row_bytes, cfg.dst_frame_bytes = out.shape[2] * 3, out.shape[1] * out.shape[2] * 3
     with torch.cuda.device(x.device):
-        _check(lib().i2v_frames_to_u8(x.data_ptr(), ctypes.byref(cfg), peak.data_ptr() if peak is not None else None, out.data_ptr(),
-                                      FRAMES_PEAK if mode == "peak" else FRAMES_UNIT, _stream()), "i2v_frames_to_u8")
+        _call("i2v_frames_to_u8", x.data_ptr(), ctypes.byref(cfg), peak.data_ptr() if peak is not None else None, out.data_ptr(),
+                                  FRAMES_PEAK if mode == "peak" else FRAMES_UNIT, _stream())
     return out
 
 
@@ -1082,34 +1061,20 @@ def default_mma():
 
 class NativeGBlock(_Handle):
     """Handle for ``i2v_gblock_*`` (GeneratorBlock, decoder.py:7-52; tensors in the reference layout [B,C,T,H,W])."""
+    _PREFIX = "i2v_gblock"
 
     def __init__(self, n_in, n_out, z_dim, spectral_norm=True, mma=None, device=None):
-        h = c_void_p()
         mma = default_mma() if mma is None else parse_mma(mma)
         if mma == 2:   # auto: a stand-alone block has no re-run loop behind the range guard; it runs split-fp16 (status() reports)
             mma = 1
-        with self._bind(device):
-            _check(lib().i2v_gblock_create(n_in, n_out, z_dim, int(bool(spectral_norm)), mma, ctypes.byref(h)), "i2v_gblock_create")
-        self._h = h
+        self._create(device, n_in, n_out, z_dim, int(bool(spectral_norm)), mma)
         self.n_in, self.n_out, self.n_mid, self.z_dim = n_in, n_out, min(n_in, n_out), z_dim
-        self._ws = _Workspace()
-
-    def __del__(self):
-        if getattr(self, "_h", None) and _lib is not None:
-            _lib.i2v_gblock_destroy(self._h)
-            self._h = None
-
-    @_on_device
-    def load(self, state_dict):
-        arr, keep = _pack_state_dict(state_dict)
-        _check(lib().i2v_gblock_load(self._h, arr, len(arr)), "i2v_gblock_load")
-        del keep
 
     def _geom(self, x, channels):
         if x.dim() != 5 or x.shape[1] != channels:
             raise I2VError(f"expected x [B,{channels},T,H,W], got {tuple(x.shape)}")
         B, _, T, H, W = x.shape
-        ws = self._ws.get(lib().i2v_gblock_workspace_bytes(self._h, B, T, H, W), x.device)
+        ws = self._scratch(lib().i2v_gblock_workspace_bytes(self._h, B, T, H, W), x.device)
         return B, T, H, W, ws
 
     @_on_device
@@ -1119,15 +1084,15 @@ class NativeGBlock(_Handle):
         if z.shape != (B, self.z_dim) or img.dim() != 4 or img.shape[:2] != (B, 3):
             raise I2VError(f"GeneratorBlock: expected z [B,{self.z_dim}] and img [B,3,h,w], got {tuple(z.shape)}, {tuple(img.shape)}")
         out = torch.empty(B, self.n_out, T, H, W, dtype=torch.float32, device=x.device)
-        _check(lib().i2v_gblock_forward(self._h, x.data_ptr(), z.data_ptr(), img.data_ptr(), img.shape[2], img.shape[3],
-                                        out.data_ptr(), ws.data_ptr(), ws.numel(), B, T, H, W, _stream()), "i2v_gblock_forward")
+        _call("i2v_gblock_forward", self._h, x.data_ptr(), z.data_ptr(), img.data_ptr(), img.shape[2], img.shape[3],
+                                    out.data_ptr(), *ws, B, T, H, W, _stream())
         return out
 
     @_on_device
     def status(self, reset=False):
         """Range guard of this block's split-fp16 operand writers (i2v_gblock_status): synchronises, returns the flag word."""
         flags = c_int32()
-        _check(lib().i2v_gblock_status(self._h, ctypes.byref(flags), int(bool(reset)), _stream()), "i2v_gblock_status")
+        _call("i2v_gblock_status", self._h, ctypes.byref(flags), int(bool(reset)), _stream())
         return int(flags.value)
 
     @_on_device
@@ -1142,8 +1107,8 @@ class NativeGBlock(_Handle):
         if part == 1 and (cond is None or cond.shape != (B, self.z_dim)):
             raise I2VError(f"ADAIN: expected z [B,{self.z_dim}]")
         out = torch.empty_like(x)
-        _check(lib().i2v_gblock_norm(self._h, part, x.data_ptr(), cond.data_ptr() if cond is not None else None, ih, iw,
-                                     out.data_ptr(), ws.data_ptr(), ws.numel(), B, T, H, W, _stream()), "i2v_gblock_norm")
+        _call("i2v_gblock_norm", self._h, part, x.data_ptr(), cond.data_ptr() if cond is not None else None, ih, iw,
+                                 out.data_ptr(), *ws, B, T, H, W, _stream())
         return out
 
 
@@ -1164,25 +1129,11 @@ class NativeNorm:
 
 class NativeEmbedder(_Handle):
     """Handle for ``i2v_embedder_*`` (ResnetEncoder.encode(x).mode(), AE.py:91-166)."""
+    _PREFIX = "i2v_embedder"
 
     def __init__(self, z_dim, use_batchnorm, device=None):
-        h = c_void_p()
-        with self._bind(device):
-            _check(lib().i2v_embedder_create(z_dim, int(bool(use_batchnorm)), ctypes.byref(h)), "i2v_embedder_create")
-        self._h = h
+        self._create(device, z_dim, int(bool(use_batchnorm)))
         self.z_dim = z_dim
-        self._ws = _Workspace()
-
-    def __del__(self):
-        if getattr(self, "_h", None) and _lib is not None:
-            _lib.i2v_embedder_destroy(self._h)
-            self._h = None
-
-    @_on_device
-    def load(self, state_dict):
-        arr, keep = _pack_state_dict(state_dict)
-        _check(lib().i2v_embedder_load(self._h, arr, len(arr)), "i2v_embedder_load")
-        del keep
 
     @_on_device
     def forward(self, img):
@@ -1190,35 +1141,20 @@ class NativeEmbedder(_Handle):
         if img.dim() != 4 or img.shape[1] != 3:
             raise I2VError(f"embedder: expected img [B,3,H,W], got {tuple(img.shape)}")
         B, _, H, W = img.shape
-        ws = self._ws.get(lib().i2v_embedder_workspace_bytes(self._h, B, H, W), img.device)
+        ws = self._scratch(lib().i2v_embedder_workspace_bytes(self._h, B, H, W), img.device)
         out = torch.empty(B, self.z_dim, dtype=torch.float32, device=img.device)
-        _check(lib().i2v_embedder_forward(self._h, img.data_ptr(), H, W, out.data_ptr(), ws.data_ptr(), ws.numel(), B, _stream()),
-               "i2v_embedder_forward")
+        _call("i2v_embedder_forward", self._h, img.data_ptr(), H, W, out.data_ptr(), *ws, B, _stream())
         return out
 
 
 class NativeEncoder3D(_Handle):
     """Handle for ``i2v_encoder3d_*`` (Encoder.forward, resnet3D.py:138-219)."""
+    _PREFIX = "i2v_encoder3d"
 
     def __init__(self, z_dim, channels, stride_s, stride_t, device=None):
         cfg = Enc3dCfg(z_dim, (c_int32 * 5)(*channels), (c_int32 * 4)(*stride_s), (c_int32 * 4)(*stride_t), 0)
-        h = c_void_p()
-        with self._bind(device):
-            _check(lib().i2v_encoder3d_create(ctypes.byref(cfg), ctypes.byref(h)), "i2v_encoder3d_create")
-        self._h = h
+        self._create(device, ctypes.byref(cfg))
         self.z_dim = z_dim
-        self._ws = _Workspace()
-
-    def __del__(self):
-        if getattr(self, "_h", None) and _lib is not None:
-            _lib.i2v_encoder3d_destroy(self._h)
-            self._h = None
-
-    @_on_device
-    def load(self, state_dict):
-        arr, keep = _pack_state_dict(state_dict)
-        _check(lib().i2v_encoder3d_load(self._h, arr, len(arr)), "i2v_encoder3d_load")
-        del keep
 
     @_on_device
     def forward(self, x, eps=None):
@@ -1228,42 +1164,28 @@ class NativeEncoder3D(_Handle):
         B, _, T, H, W = x.shape
         if eps is not None and tuple(eps.shape) != (B, self.z_dim):
             raise I2VError(f"encoder: expected eps [{B},{self.z_dim}], got {tuple(eps.shape)}")
-        ws = self._ws.get(lib().i2v_encoder3d_workspace_bytes(self._h, B, T, H, W), x.device)
+        ws = self._scratch(lib().i2v_encoder3d_workspace_bytes(self._h, B, T, H, W), x.device)
         mu = torch.empty(B, self.z_dim, dtype=torch.float32, device=x.device)
         logvar = torch.empty_like(mu)
         sample = torch.empty_like(mu) if eps is not None else None
-        _check(lib().i2v_encoder3d_forward(self._h, x.data_ptr(), T, H, W, eps.data_ptr() if eps is not None else None,
-                                           sample.data_ptr() if sample is not None else None, mu.data_ptr(), logvar.data_ptr(),
-                                           ws.data_ptr(), ws.numel(), B, _stream()), "i2v_encoder3d_forward")
+        _call("i2v_encoder3d_forward", self._h, x.data_ptr(), T, H, W, eps.data_ptr() if eps is not None else None,
+                                       sample.data_ptr() if sample is not None else None, mu.data_ptr(), logvar.data_ptr(),
+                                       *ws, B, _stream())
         return sample, mu, logvar
 
 
 class NativeI3D(_Handle):
     """Handle for ``i2v_i3d_*`` (the Kinetics-400 I3D of metrics/PyTorch_FVD/I3D.py with FVD_logging.preprocess as its input stage) and,
     with ``dt_length`` 16 or 32, for the dynamic-texture I3D of metrics/DTFVD/ID3.py / ID3_32.py (``i2v_dti3d_create``)."""
+    _PREFIX = "i2v_i3d"
 
     def __init__(self, num_classes, in_channels=3, device=None, dt_length=None):
-        h = c_void_p()
-        with self._bind(device):
-            if dt_length is None:
-                _check(lib().i2v_i3d_create(num_classes, in_channels, ctypes.byref(h)), "i2v_i3d_create")
-            else:
-                _check(lib().i2v_dti3d_create(num_classes, dt_length, ctypes.byref(h)), "i2v_dti3d_create")
-        self._h = h
+        if dt_length is None:
+            self._create(device, num_classes, in_channels)
+        else:
+            self._create(device, num_classes, dt_length, symbol="i2v_dti3d_create")
         self.num_classes = num_classes
         self.dt_length = dt_length
-        self._ws = _Workspace()
-
-    def __del__(self):
-        if getattr(self, "_h", None) and _lib is not None:
-            _lib.i2v_i3d_destroy(self._h)
-            self._h = None
-
-    @_on_device
-    def load(self, state_dict):
-        arr, keep = _pack_state_dict(state_dict)
-        _check(lib().i2v_i3d_load(self._h, arr, len(arr)), "i2v_i3d_load")
-        del keep
 
     @_on_device
     def forward(self, frames, denorm):
@@ -1275,10 +1197,10 @@ class NativeI3D(_Handle):
         nbytes = lib().i2v_i3d_workspace_bytes(self._h, B, T, H, W)
         if nbytes == 0:
             raise I2VError(f"i3d: no plan for frames {tuple(frames.shape)} (at least 9 frames of at least 2 x 2 pixels are needed)")
-        ws = self._ws.get(nbytes, frames.device)
+        ws = self._scratch(nbytes, frames.device)
         out = torch.empty(B, self.num_classes, dtype=torch.float32, device=frames.device)
-        _check(lib().i2v_i3d_forward(self._h, frames.data_ptr(), B, T, H, W, int(bool(denorm)), out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                     _stream()), "i2v_i3d_forward")
+        _call("i2v_i3d_forward", self._h, frames.data_ptr(), B, T, H, W, int(bool(denorm)), out.data_ptr(), *ws,
+                                 _stream())
         return out
 
     @_on_device
@@ -1296,10 +1218,9 @@ class NativeI3D(_Handle):
             need = 25 if self.dt_length == 32 else 9
             raise I2VError(f"i3d: no plan for frames {tuple(frames.shape)} with {t_out} frames per clip (at least {need} frames of at least "
                            "2 x 2 pixels are needed)")
-        ws = self._ws.get(nbytes, frames.device)
+        ws = self._scratch(nbytes, frames.device)
         out = torch.empty(B, 1024, steps, dtype=torch.float32, device=frames.device)
-        _check(lib().i2v_i3d_features(self._h, frames.data_ptr(), B, T, t_out, H, W, int(bool(denorm)), out.data_ptr(), ws.data_ptr(),
-                                      ws.numel(), _stream()), "i2v_i3d_features")
+        _call("i2v_i3d_features", self._h, frames.data_ptr(), B, T, t_out, H, W, int(bool(denorm)), out.data_ptr(), *ws, _stream())
         return out
 
     # ---- sub-modules on channels-last tensors [B, T, H, W, C] (tests and inspection)
@@ -1314,7 +1235,7 @@ class NativeI3D(_Handle):
     def unit_shape(self, unit, t, h, w):
         """``i2v_i3d_unit_shape``: (cin, cout, (To, Ho, Wo)) of conv unit ``unit`` on a [t, h, w] map."""
         cin, cout, od = c_int32(), c_int32(), (c_int32 * 3)()
-        _check(lib().i2v_i3d_unit_shape(self._h, unit, t, h, w, ctypes.byref(cin), ctypes.byref(cout), od), "i2v_i3d_unit_shape")
+        _call("i2v_i3d_unit_shape", self._h, unit, t, h, w, ctypes.byref(cin), ctypes.byref(cout), od)
         return cin.value, cout.value, tuple(od)
 
     @_on_device
@@ -1329,8 +1250,8 @@ class NativeI3D(_Handle):
         self._require_cl(out, "i3d unit")
         if tuple(out.shape[:4]) != (B, *od):
             raise I2VError(f"i3d unit: expected an output [{B},{od[0]},{od[1]},{od[2]},C], got {tuple(out.shape)}")
-        _check(lib().i2v_i3d_unit_forward(self._h, unit, x.data_ptr(), B, T, H, W, cs, out.data_ptr(), out.shape[4], out_off, out.numel(),
-                                          _stream()), "i2v_i3d_unit_forward")
+        _call("i2v_i3d_unit_forward", self._h, unit, x.data_ptr(), B, T, H, W, cs, out.data_ptr(), out.shape[4], out_off, out.numel(),
+                                      _stream())
         return out
 
     @_on_device
@@ -1342,16 +1263,15 @@ class NativeI3D(_Handle):
         if cs != cin:
             raise I2VError(f"i3d mixed: block {block} reads {cin} channels, got {cs}")
         co = sum(self.unit_shape(self.UNIT_MIXED + 6 * block + j, T, H, W)[1] for j in (0, 2, 4, 5))
-        ws = self._ws.get(lib().i2v_i3d_mixed_workspace_bytes(self._h, block, B, T, H, W), x.device)
+        ws = self._scratch(lib().i2v_i3d_mixed_workspace_bytes(self._h, block, B, T, H, W), x.device)
         out = torch.empty(B, T, H, W, co, dtype=torch.float32, device=x.device)
-        _check(lib().i2v_i3d_mixed_forward(self._h, block, x.data_ptr(), B, T, H, W, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
-               "i2v_i3d_mixed_forward")
+        _call("i2v_i3d_mixed_forward", self._h, block, x.data_ptr(), B, T, H, W, out.data_ptr(), *ws, _stream())
         return out
 
     def maxpool_shape(self, kernel, stride, t, h, w):
         """``i2v_i3d_maxpool_shape``: (To, Ho, Wo) of the max pool (kT, k, k) / (sT, s, s) on a [t, h, w] map."""
         od = (c_int32 * 3)()
-        _check(lib().i2v_i3d_maxpool_shape(self._h, kernel[0], kernel[1], stride[0], stride[1], t, h, w, od), "i2v_i3d_maxpool_shape")
+        _call("i2v_i3d_maxpool_shape", self._h, kernel[0], kernel[1], stride[0], stride[1], t, h, w, od)
         return tuple(od)
 
     @_on_device
@@ -1361,8 +1281,8 @@ class NativeI3D(_Handle):
         B, T, H, W, C = x.shape
         od = self.maxpool_shape(kernel, stride, T, H, W)
         out = torch.empty(B, *od, C, dtype=torch.float32, device=x.device)
-        _check(lib().i2v_i3d_maxpool_forward(self._h, x.data_ptr(), B, T, H, W, C, kernel[0], kernel[1], stride[0], stride[1], out.data_ptr(),
-                                             out.numel(), _stream()), "i2v_i3d_maxpool_forward")
+        _call("i2v_i3d_maxpool_forward", self._h, x.data_ptr(), B, T, H, W, C, kernel[0], kernel[1], stride[0], stride[1], out.data_ptr(),
+                                         out.numel(), _stream())
         return out
 
     @_on_device
@@ -1374,12 +1294,11 @@ class NativeI3D(_Handle):
         if tuple(x.shape[2:]) != (7, 7, 1024) or nbytes == 0:
             raise I2VError(f"i3d head: expected [B,T,7,7,1024] with at least the average pool's time steps, got {tuple(x.shape)}")
         tp = T - (4 if self.dt_length == 32 else 2) + 1
-        ws = self._ws.get(nbytes, x.device)
+        ws = self._scratch(nbytes, x.device)
         pooled = torch.empty(B, tp, 1024, dtype=torch.float32, device=x.device)
         feats = torch.empty(B, 1024, tp, dtype=torch.float32, device=x.device)
         logits = torch.empty(B, self.num_classes, dtype=torch.float32, device=x.device)
-        _check(lib().i2v_i3d_head_forward(self._h, x.data_ptr(), B, T, pooled.data_ptr(), feats.data_ptr(), logits.data_ptr(), ws.data_ptr(),
-                                          ws.numel(), _stream()), "i2v_i3d_head_forward")
+        _call("i2v_i3d_head_forward", self._h, x.data_ptr(), B, T, pooled.data_ptr(), feats.data_ptr(), logits.data_ptr(), *ws, _stream())
         return pooled, feats, logits
 
 
@@ -1392,7 +1311,7 @@ def fvd_stats_update(feats, total, gram):
         if not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous() or tuple(t.shape) != shape or t.device != feats.device:
             raise I2VError(f"fvd_stats_update: expected a contiguous float64 device tensor of shape {shape}")
     with torch.cuda.device(feats.device):
-        _check(lib().i2v_fvd_stats_update(feats.data_ptr(), n, d, total.data_ptr(), gram.data_ptr(), _stream()), "i2v_fvd_stats_update")
+        _call("i2v_fvd_stats_update", feats.data_ptr(), n, d, total.data_ptr(), gram.data_ptr(), _stream())
 
 
 def diversity_update(embed, acc):
@@ -1405,7 +1324,7 @@ def diversity_update(embed, acc):
         raise I2VError("diversity_update: expected a contiguous float64 device tensor of shape (2,)")
     n, r, d = embed.shape
     with torch.cuda.device(embed.device):
-        _check(lib().i2v_diversity_update(embed.data_ptr(), n, r, d, acc.data_ptr(), _stream()), "i2v_diversity_update")
+        _call("i2v_diversity_update", embed.data_ptr(), n, r, d, acc.data_ptr(), _stream())
 
 
 def i3d_input_stage(frames, denorm):
@@ -1416,7 +1335,7 @@ def i3d_input_stage(frames, denorm):
     n, _, h, w = frames.shape
     out = torch.empty(n, 224, 224, 4, dtype=torch.float32, device=frames.device)
     with torch.cuda.device(frames.device):
-        _check(lib().i2v_i3d_input_stage(frames.data_ptr(), n, h, w, int(bool(denorm)), out.data_ptr(), _stream()), "i2v_i3d_input_stage")
+        _call("i2v_i3d_input_stage", frames.data_ptr(), n, h, w, int(bool(denorm)), out.data_ptr(), _stream())
     return out
 
 
@@ -1473,28 +1392,18 @@ def _ptrs(tensors):
 class NativeVGG(_Handle):
     """Handle for ``i2v_vgg_*``: the VGG-16 ``features`` trunk of stage2_cINN/AE/modules/vgg16.py up to relu5_3, with the ``lin`` weights of
     LPIPS.py when the state_dict has them."""
+    _PREFIX = "i2v_vgg"
 
     def __init__(self, device=None):
-        h = c_void_p()
-        with self._bind(device):
-            _check(lib().i2v_vgg_create(ctypes.byref(h)), "i2v_vgg_create")
-        self._h = h
-        self._ws = _Workspace()
+        self._create(device)
         self._bws = _Workspace()
         self.has_lin = False
 
-    def __del__(self):
-        if getattr(self, "_h", None) and _lib is not None:
-            _lib.i2v_vgg_destroy(self._h)
-            self._h = None
-
-    @_on_device
     def load(self, state_dict):
         """torchvision keys ``features.N.{weight,bias}`` and, optionally, ``lin{0..4}.model.1.weight``; every other key is ignored."""
-        sd = {k: v for k, v in state_dict.items() if k.startswith("features.") or (k.startswith("lin") and k.endswith(".model.1.weight"))}
-        arr, keep = _pack_state_dict(sd)
-        _check(lib().i2v_vgg_load(self._h, arr, len(arr)), "i2v_vgg_load")
-        del keep
+        self.has_lin = False
+        super().load({k: v for k, v in state_dict.items()
+                      if k.startswith("features.") or (k.startswith("lin") and k.endswith(".model.1.weight"))})
         self.has_lin = bool(lib().i2v_vgg_lin(self._h, 0))
 
     @staticmethod
@@ -1513,7 +1422,7 @@ class NativeVGG(_Handle):
         nbytes = lib().i2v_vgg_workspace_bytes(self._h, n, h, w) if c == 4 else 0
         if nbytes == 0:
             raise I2VError(f"vgg features: expected [N,H,W,4] with H, W >= 16 (four pools), got {tuple(x.shape)}")
-        ws = self._ws.get(nbytes, x.device)
+        ws = self._scratch(nbytes, x.device)
         shapes = self.tap_shapes(n, h, w)
         if out is None:
             out = [torch.empty(s, dtype=torch.float32, device=x.device) for s in shapes]
@@ -1527,11 +1436,10 @@ class NativeVGG(_Handle):
                 saved_buf = torch.empty(nsaved, dtype=torch.uint8, device=x.device)
             if not saved_buf.is_cuda or saved_buf.dtype != torch.uint8 or not saved_buf.is_contiguous() or saved_buf.numel() < nsaved:
                 raise I2VError(f"vgg features: the saved-state buffer must be a contiguous uint8 device tensor of at least {nsaved} bytes")
-            _check(lib().i2v_vgg_features_saved(self._h, x.data_ptr(), n, h, w, *[t.data_ptr() for t in out], saved_buf.data_ptr(), saved_buf.numel(),
-                                                ws.data_ptr(), ws.numel(), _stream()), "i2v_vgg_features_saved")
+            _call("i2v_vgg_features_saved", self._h, x.data_ptr(), n, h, w, *[t.data_ptr() for t in out], saved_buf.data_ptr(), saved_buf.numel(),
+                                            *ws, _stream())
             return list(out), VGGSaved(x.shape, out, saved_buf)
-        _check(lib().i2v_vgg_features(self._h, x.data_ptr(), n, h, w, *[t.data_ptr() for t in out], ws.data_ptr(), ws.numel(), _stream()),
-               "i2v_vgg_features")
+        _call("i2v_vgg_features", self._h, x.data_ptr(), n, h, w, *[t.data_ptr() for t in out], *ws, _stream())
         return list(out)
 
     def saved_bytes(self, n, h, w):
@@ -1558,9 +1466,9 @@ class NativeVGG(_Handle):
         _require_gpu(out)
         if tuple(out.shape) != shape:
             raise I2VError(f"vgg backward: expected an output of shape {shape}, got {tuple(out.shape)}")
-        ws = self._bws.get(lib().i2v_vgg_backward_workspace_bytes(self._h, n, h, w), out.device)
-        _check(lib().i2v_vgg_backward(self._h, _ptrs(saved.taps), _ptrs(tap_grads), saved.buf.data_ptr(), saved.buf.numel(), n, h, w, out.data_ptr(),
-                                      int(bool(frames)), ws.data_ptr(), ws.numel(), _stream()), "i2v_vgg_backward")
+        ws = self._scratch(lib().i2v_vgg_backward_workspace_bytes(self._h, n, h, w), out.device, self._bws)
+        _call("i2v_vgg_backward", self._h, _ptrs(saved.taps), _ptrs(tap_grads), saved.buf.data_ptr(), saved.buf.numel(), n, h, w, out.data_ptr(),
+                                  int(bool(frames)), *ws, _stream())
         return out
 
     @_on_device
@@ -1585,9 +1493,9 @@ class NativeVGG(_Handle):
                     _require_gpu(g[k])
                     if g[k].shape != a.shape:
                         raise I2VError(f"lpips backward: a gradient buffer of shape {tuple(g[k].shape)} for a tap of shape {tuple(a.shape)}")
-            _check(lib().i2v_lpips_layer_backward(a.data_ptr(), b.data_ptr(), lib().i2v_vgg_lin(self._h, k), upstream.data_ptr(), n,
-                                                  a.shape[1] * a.shape[2], a.shape[3], g0[k].data_ptr() if need0 else None,
-                                                  g1[k].data_ptr() if need1 else None, _stream()), "i2v_lpips_layer_backward")
+            _call("i2v_lpips_layer_backward", a.data_ptr(), b.data_ptr(), lib().i2v_vgg_lin(self._h, k), upstream.data_ptr(), n,
+                                              a.shape[1] * a.shape[2], a.shape[3], g0[k].data_ptr() if need0 else None,
+                                              g1[k].data_ptr() if need1 else None, _stream())
         return g0, g1
 
     @_on_device
@@ -1603,8 +1511,8 @@ class NativeVGG(_Handle):
             _require_cl4(b, "lpips")
             if a.shape != b.shape:
                 raise I2VError(f"lpips: taps of different shapes {tuple(a.shape)} / {tuple(b.shape)}")
-            _check(lib().i2v_lpips_layer(a.data_ptr(), b.data_ptr(), lib().i2v_vgg_lin(self._h, k), n, a.shape[1] * a.shape[2], a.shape[3],
-                                         out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "i2v_lpips_layer")
+            _call("i2v_lpips_layer", a.data_ptr(), b.data_ptr(), lib().i2v_vgg_lin(self._h, k), n, a.shape[1] * a.shape[2], a.shape[3],
+                                     out.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
         return out
 
 
@@ -1618,8 +1526,7 @@ def vgg_input_stage(frames, mode, size=None, align_corners=False):
     ho, wo = (h, w) if size is None else size
     out = torch.empty(n, ho, wo, 4, dtype=torch.float32, device=frames.device)
     with torch.cuda.device(frames.device):
-        _check(lib().i2v_vgg_input_stage(frames.data_ptr(), n, h, w, mode, ho, wo, int(bool(align_corners)), out.data_ptr(), _stream()),
-               "i2v_vgg_input_stage")
+        _call("i2v_vgg_input_stage", frames.data_ptr(), n, h, w, mode, ho, wo, int(bool(align_corners)), out.data_ptr(), _stream())
     return out
 
 
@@ -1637,8 +1544,8 @@ def vgg_conv_unit(x, weight, bias):
         raise I2VError(f"vgg_conv_unit: {cin} input channels need a tensor of {4 if cin == 3 else cin} stored channels, got {cs}")
     out = torch.empty(n, h, wd, cout, dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
-        _check(lib().i2v_vgg_conv_unit(x.data_ptr(), w.ctypes.data_as(c_void_p), b.ctypes.data_as(c_void_p), n, h, wd, cin, cout, out.data_ptr(),
-                                       _stream()), "i2v_vgg_conv_unit")
+        _call("i2v_vgg_conv_unit", x.data_ptr(), w.ctypes.data_as(c_void_p), b.ctypes.data_as(c_void_p), n, h, wd, cin, cout, out.data_ptr(),
+                                   _stream())
     return out
 
 
@@ -1648,7 +1555,7 @@ def vgg_maxpool2(x):
     n, h, w, c = x.shape
     out = torch.empty(n, h // 2, w // 2, c, dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
-        _check(lib().i2v_vgg_maxpool2(x.data_ptr(), n, h, w, c, out.data_ptr(), _stream()), "i2v_vgg_maxpool2")
+        _call("i2v_vgg_maxpool2", x.data_ptr(), n, h, w, c, out.data_ptr(), _stream())
     return out
 
 
@@ -1672,9 +1579,9 @@ def vgg_dgrad_unit(g, weight, add=None, ymask=None, frames=False):
                 raise I2VError(f"vgg_dgrad_unit: expected an addend / mask of shape {shape}, got {tuple(t.shape)}")
     out = torch.empty(shape, dtype=torch.float32, device=g.device)
     with torch.cuda.device(g.device):
-        _check(lib().i2v_vgg_dgrad_unit(g.data_ptr(), w.ctypes.data_as(c_void_p), None if add is None else add.data_ptr(),
-                                        None if ymask is None else ymask.data_ptr(), n, h, wd, cin, cout, out.data_ptr(), int(bool(frames)),
-                                        _stream()), "i2v_vgg_dgrad_unit")
+        _call("i2v_vgg_dgrad_unit", g.data_ptr(), w.ctypes.data_as(c_void_p), None if add is None else add.data_ptr(),
+                                    None if ymask is None else ymask.data_ptr(), n, h, wd, cin, cout, out.data_ptr(), int(bool(frames)),
+                                    _stream())
     return out
 
 
@@ -1690,8 +1597,8 @@ def vgg_maxpool2_backward(grad, y, add=None, relu_mask=False):
         _require_cl4(add, "vgg_maxpool2_backward")
     out = torch.empty_like(y)
     with torch.cuda.device(y.device):
-        _check(lib().i2v_vgg_maxpool2_backward(grad.data_ptr(), y.data_ptr(), None if add is None else add.data_ptr(), int(bool(relu_mask)), n, h, w, c,
-                                               out.data_ptr(), _stream()), "i2v_vgg_maxpool2_backward")
+        _call("i2v_vgg_maxpool2_backward", grad.data_ptr(), y.data_ptr(), None if add is None else add.data_ptr(), int(bool(relu_mask)), n, h, w, c,
+                                           out.data_ptr(), _stream())
     return out
 
 
@@ -1707,9 +1614,8 @@ def lpips_layer_backward(f0, f1, lin, upstream, need0=True, need1=True):
     _require_f64(upstream, (n,), f0.device, "lpips_layer_backward")
     g0, g1 = (torch.empty_like(f0) if need0 else None), (torch.empty_like(f1) if need1 else None)
     with torch.cuda.device(f0.device):
-        _check(lib().i2v_lpips_layer_backward(f0.data_ptr(), f1.data_ptr(), lin.data_ptr(), upstream.data_ptr(), n, h * w, c,
-                                              None if g0 is None else g0.data_ptr(), None if g1 is None else g1.data_ptr(), _stream()),
-               "i2v_lpips_layer_backward")
+        _call("i2v_lpips_layer_backward", f0.data_ptr(), f1.data_ptr(), lin.data_ptr(), upstream.data_ptr(), n, h * w, c,
+                                          None if g0 is None else g0.data_ptr(), None if g1 is None else g1.data_ptr(), _stream())
     return g0, g1
 
 
@@ -1724,8 +1630,7 @@ def lpips_layer(f0, f1, lin, out):
     _require_f64(out, (n,), f0.device, "lpips_layer")
     ws = _reduce_ws(n, f0.device)
     with torch.cuda.device(f0.device):
-        _check(lib().i2v_lpips_layer(f0.data_ptr(), f1.data_ptr(), lin.data_ptr(), n, h * w, c, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
-               "i2v_lpips_layer")
+        _call("i2v_lpips_layer", f0.data_ptr(), f1.data_ptr(), lin.data_ptr(), n, h * w, c, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
 
 
 def vgg_pairdiff_update(maps, acc):
@@ -1738,8 +1643,7 @@ def vgg_pairdiff_update(maps, acc):
     r = maps.shape[0]
     ws = _reduce_ws(1, maps.device)
     with torch.cuda.device(maps.device):
-        _check(lib().i2v_vgg_pairdiff_update(maps.data_ptr(), r, maps.numel() // r, acc.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
-               "i2v_vgg_pairdiff_update")
+        _call("i2v_vgg_pairdiff_update", maps.data_ptr(), r, maps.numel() // r, acc.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
 
 
 INCEPTION_POOL_MAX_S2, INCEPTION_POOL_MAX_S1, INCEPTION_POOL_AVG = 0, 1, 2
@@ -1750,33 +1654,21 @@ INCEPTION_MIN_SIDE = 75
 class NativeInception(_Handle):
     """Handle for ``i2v_inception_*``: the FID Inception-v3 trunk of metrics/FID/inception.py (``fid_inception_v3`` cut into the four output
     blocks of ``InceptionV3``)."""
+    _PREFIX = "i2v_inception"
 
     def __init__(self, device=None):
-        h = c_void_p()
-        with self._bind(device):
-            _check(lib().i2v_inception_create(ctypes.byref(h)), "i2v_inception_create")
-        self._h = h
-        self._ws = _Workspace()
+        self._create(device)
 
-    def __del__(self):
-        if getattr(self, "_h", None) and _lib is not None:
-            _lib.i2v_inception_destroy(self._h)
-            self._h = None
-
-    @_on_device
     def load(self, state_dict):
         """torchvision keys ``<unit>.conv.weight`` / ``<unit>.bn.{weight,bias,running_mean,running_var}``; ``num_batches_tracked``, ``fc.*`` and
         ``AuxLogits.*`` are ignored."""
-        sd = {k: v for k, v in state_dict.items()
-              if not (k.endswith("num_batches_tracked") or k.startswith("fc.") or k.startswith("AuxLogits."))}
-        arr, keep = _pack_state_dict(sd)
-        _check(lib().i2v_inception_load(self._h, arr, len(arr)), "i2v_inception_load")
-        del keep
+        super().load({k: v for k, v in state_dict.items()
+                      if not (k.endswith("num_batches_tracked") or k.startswith("fc.") or k.startswith("AuxLogits."))})
 
     def block_shape(self, n, h, w, block):
         """Channels-last shape of output block 0..3 for an [h, w] trunk input: [N, H', W', C], block 3 [N, 2048]."""
         dims = (c_int32 * 3)()
-        _check(lib().i2v_inception_block_shape(self._h, h, w, block, dims), "i2v_inception_block_shape")
+        _call("i2v_inception_block_shape", self._h, h, w, block, dims)
         return (n, dims[2]) if block == 3 else (n, dims[0], dims[1], dims[2])
 
     @_on_device
@@ -1794,7 +1686,7 @@ class NativeInception(_Handle):
         nbytes = lib().i2v_inception_workspace_bytes(self._h, n, h, w, blocks[-1])
         if nbytes == 0:
             raise I2VError(f"inception features: no buffer plan for {tuple(x.shape)}: {lib().i2v_last_error().decode(errors='replace')}")
-        ws = self._ws.get(nbytes, x.device)
+        ws = self._scratch(nbytes, x.device)
         shapes = [self.block_shape(n, h, w, b) for b in blocks]
         if out is None:
             out = [torch.empty(s, dtype=torch.float32, device=x.device) for s in shapes]
@@ -1804,13 +1696,13 @@ class NativeInception(_Handle):
             if tuple(t.shape) != s:
                 raise I2VError(f"inception features: expected block {b} of shape {s}, got {tuple(t.shape)}")
             ptr[b] = t.data_ptr()
-        _check(lib().i2v_inception_features(self._h, x.data_ptr(), n, h, w, *ptr, ws.data_ptr(), ws.numel(), _stream()), "i2v_inception_features")
+        _call("i2v_inception_features", self._h, x.data_ptr(), n, h, w, *ptr, *ws, _stream())
         return list(out)
 
     def mixed_shape(self, block, h, w):
         """(cin, cout, (H', W')) of Mixed block ``block`` (index into INCEPTION_BLOCKS) on an [h, w] map."""
         cin, cout, hw = c_int32(), c_int32(), (c_int32 * 2)()
-        _check(lib().i2v_inception_mixed_shape(self._h, block, h, w, ctypes.byref(cin), ctypes.byref(cout), hw), "i2v_inception_mixed_shape")
+        _call("i2v_inception_mixed_shape", self._h, block, h, w, ctypes.byref(cin), ctypes.byref(cout), hw)
         return cin.value, cout.value, (hw[0], hw[1])
 
     @_on_device
@@ -1828,8 +1720,7 @@ class NativeInception(_Handle):
         if tuple(out.shape) != (n, ho, wo, cout):
             raise I2VError(f"inception mixed: expected an output of shape {(n, ho, wo, cout)}, got {tuple(out.shape)}")
         ws = torch.empty(max(lib().i2v_inception_mixed_workspace_bytes(self._h, block, n, h, w), 256), dtype=torch.uint8, device=x.device)
-        _check(lib().i2v_inception_mixed_forward(self._h, block, x.data_ptr(), n, h, w, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
-               "i2v_inception_mixed_forward")
+        _call("i2v_inception_mixed_forward", self._h, block, x.data_ptr(), n, h, w, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
         return out
 
 
@@ -1843,8 +1734,7 @@ def inception_input_stage(frames, resize=True, normalize=False):
     ho, wo = (299, 299) if resize else (h, w)
     out = torch.empty(n, ho, wo, 4, dtype=torch.float32, device=frames.device)
     with torch.cuda.device(frames.device):
-        _check(lib().i2v_inception_input_stage(frames.data_ptr(), n, h, w, int(bool(resize)), int(bool(normalize)), out.data_ptr(), _stream()),
-               "i2v_inception_input_stage")
+        _call("i2v_inception_input_stage", frames.data_ptr(), n, h, w, int(bool(resize)), int(bool(normalize)), out.data_ptr(), _stream())
     return out
 
 
@@ -1871,9 +1761,8 @@ def inception_conv_unit(x, weight, bn, stride=1, padding=(0, 0), in_off=0, out=N
     if tuple(out.shape[:3]) != (n, max(ho, 0), max(wo, 0)):
         raise I2VError(f"inception_conv_unit: expected an output [N,{ho},{wo},C], got {tuple(out.shape)}")
     with torch.cuda.device(x.device):
-        _check(lib().i2v_inception_conv_unit(x.data_ptr(), n, h, wd, cs, in_off, w.ctypes.data_as(c_void_p), *[v.ctypes.data_as(c_void_p) for v in vec],
-                                             cin, cout, kh, kw, stride, ph, pw, out.data_ptr(), out.shape[3], out_off, out.numel(), _stream()),
-               "i2v_inception_conv_unit")
+        _call("i2v_inception_conv_unit", x.data_ptr(), n, h, wd, cs, in_off, w.ctypes.data_as(c_void_p), *[v.ctypes.data_as(c_void_p) for v in vec],
+                                         cin, cout, kh, kw, stride, ph, pw, out.data_ptr(), out.shape[3], out_off, out.numel(), _stream())
     return out
 
 
@@ -1890,7 +1779,7 @@ def inception_pool(x, kind, out=None, out_off=0):
     if tuple(out.shape[:3]) != (n, max(ho, 0), max(wo, 0)):
         raise I2VError(f"inception_pool: expected an output [N,{ho},{wo},C], got {tuple(out.shape)}")
     with torch.cuda.device(x.device):
-        _check(lib().i2v_inception_pool(x.data_ptr(), n, h, w, c, kind, out.data_ptr(), out.shape[3], out_off, out.numel(), _stream()), "i2v_inception_pool")
+        _call("i2v_inception_pool", x.data_ptr(), n, h, w, c, kind, out.data_ptr(), out.shape[3], out_off, out.numel(), _stream())
     return out
 
 
@@ -1900,7 +1789,7 @@ def inception_global_avg(x):
     n, h, w, c = x.shape
     out = torch.empty(n, c, dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
-        _check(lib().i2v_inception_global_avg(x.data_ptr(), n, h, w, c, out.data_ptr(), _stream()), "i2v_inception_global_avg")
+        _call("i2v_inception_global_avg", x.data_ptr(), n, h, w, c, out.data_ptr(), _stream())
     return out
 
 
@@ -1938,8 +1827,7 @@ def recon_range(pred, target):
     p, t, shape, pbs, tbs, ws = _recon_args(pred, target, "recon_range")
     out = torch.empty(4, dtype=torch.float64, device=p.device)
     with torch.cuda.device(p.device):
-        _check(lib().i2v_recon_range(p.data_ptr(), t.data_ptr(), *shape, pbs, tbs, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
-               "i2v_recon_range")
+        _call("i2v_recon_range", p.data_ptr(), t.data_ptr(), *shape, pbs, tbs, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
     return out
 
 
@@ -1960,10 +1848,9 @@ def recon_stats(pred, target, data_range=None):
     with torch.cuda.device(p.device):
         if data_range is None:
             rng = torch.empty(4, dtype=torch.float64, device=p.device)
-            _check(lib().i2v_recon_range(p.data_ptr(), t.data_ptr(), *shape, pbs, tbs, rng.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
-                   "i2v_recon_range")
-        _check(lib().i2v_recon_stats(p.data_ptr(), t.data_ptr(), *shape, pbs, tbs, None if rng is None else rng.data_ptr(), fixed,
-                                     per_image.data_ptr(), scalars.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "i2v_recon_stats")
+            _call("i2v_recon_range", p.data_ptr(), t.data_ptr(), *shape, pbs, tbs, rng.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+        _call("i2v_recon_stats", p.data_ptr(), t.data_ptr(), *shape, pbs, tbs, None if rng is None else rng.data_ptr(), fixed,
+                                 per_image.data_ptr(), scalars.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
     return scalars, per_image, rng
 
 
@@ -1974,5 +1861,5 @@ def kl_normal(mu, logvar):
         raise I2VError(f"kl_normal: expected mu and logvar [B,D] on one device, got {tuple(mu.shape)} / {tuple(logvar.shape)}")
     out = torch.empty(1, dtype=torch.float64, device=mu.device)
     with torch.cuda.device(mu.device):
-        _check(lib().i2v_kl_normal(mu.data_ptr(), logvar.data_ptr(), mu.shape[0], mu.shape[1], out.data_ptr(), _stream()), "i2v_kl_normal")
+        _call("i2v_kl_normal", mu.data_ptr(), logvar.data_ptr(), mu.shape[0], mu.shape[1], out.data_ptr(), _stream())
     return out[0]

@@ -17,6 +17,10 @@
  *     is not re-entrant, and must be used from one stream at a time.
  *   - return value: 0 = ok, negative = error (I2V_E_*); i2v_last_error() gives the message of
  *     the last failure on the calling thread.
+ *   - *_load may be called again to replace the weights.  A load that fails (I2V_E_MISSING, a
+ *     failed upload, ...) leaves the handle UNLOADED, whatever it held before: part of the
+ *     packed weights may already be the new ones, so every call that needs weights returns
+ *     I2V_E_STATE until a load succeeds.  This holds for every handle type.
  */
 #ifndef I2V_HIP_H
 #define I2V_HIP_H
@@ -33,7 +37,7 @@ extern "C" {
 #define I2V_E_MISSING (-2)   /* a state_dict key is missing or has the wrong size */
 #define I2V_E_HIP (-3)       /* a HIP runtime call failed */
 #define I2V_E_WORKSPACE (-4) /* workspace too small */
-#define I2V_E_STATE (-5)     /* weights not loaded */
+#define I2V_E_STATE (-5)     /* weights not loaded (never, or the last load failed) */
 #define I2V_E_RANGE (-6)     /* an activation left the fp16 range of the split-fp16 operand format (see i2v_dec_status) */
 
 #define I2V_F32 0
@@ -80,6 +84,7 @@ void i2v_flow_destroy(i2v_flow* f);
 /* Packs the 80 MLPs, ActNorm and Shuffle parameters of ConditionalFlow.state_dict() into the
  * streaming layout and uploads them.  Keys: sub_layers.{i}.{norm_layer.{loc,scale},
  * coupling.{s,t}.{0,1}.main.{0,2,4,6}.{weight,bias}, shuffle.{forward,backward}_shuffle_idx}. */
+/* (a failed load leaves the handle unloaded: its next forward returns I2V_E_STATE -- see Conventions) */
 int i2v_flow_load(i2v_flow* f, const i2v_tensor* tensors, int32_t n_tensors);
 size_t i2v_flow_workspace_bytes(const i2v_flow* f, int32_t batch);
 /* Bytes of parameters streamed per pass (the algorithmic HBM traffic of SURVEY §8d). */
@@ -170,6 +175,7 @@ int i2v_adam_step(const i2v_adam_tensor* table, const int32_t* chunks, int32_t n
 typedef struct i2v_mlp i2v_mlp;
 int i2v_mlp_create(int32_t dim, int32_t hidden_dim, int32_t depth, int32_t out_dim, i2v_mlp** out);
 void i2v_mlp_destroy(i2v_mlp* m);
+/* (a failed load leaves the handle unloaded: its next forward returns I2V_E_STATE -- see Conventions) */
 int i2v_mlp_load(i2v_mlp* m, const i2v_tensor* tensors, int32_t n_tensors);
 size_t i2v_mlp_workspace_bytes(const i2v_mlp* m, int32_t batch);
 /* x [B,dim] -> y [B,out_dim] */
@@ -226,6 +232,7 @@ void i2v_dec_destroy(i2v_dec* d);
  * Generator.state_dict(): fc.*, {head_0,g_0..g_4}.{conv_0,conv_1,conv_s}.{weight_orig,weight_u,
  * weight_v,bias} (or .weight when spectral_norm = 0), .norm_0.{conv,conv_gamma,conv_beta}.*,
  * .norm_1.linear.*, .norm_s.bn.*, conv_img.*. */
+/* (a failed load leaves the handle unloaded: its next forward returns I2V_E_STATE -- see Conventions) */
 int i2v_dec_load(i2v_dec* d, const i2v_tensor* tensors, int32_t n_tensors);
 /* Output geometry [T, H, W] of one decoder pass (T = 16 for every shipped config). */
 int i2v_dec_out_shape(const i2v_dec* d, int32_t* t, int32_t* h, int32_t* w);
@@ -402,6 +409,7 @@ int i2v_gblock_create(int32_t n_in, int32_t n_out, int32_t z_dim, int32_t spectr
 void i2v_gblock_destroy(i2v_gblock* g);
 /* Keys relative to the block: conv_{0,1,s}.*, norm_0.{conv,conv_gamma,conv_beta}.*, norm_1.linear.*, norm_s.bn.*.
  * Groups of keys that are absent are skipped, so a handle can carry a lone Spade / ADAIN / Norm3D. */
+/* (a failed load leaves the handle unloaded: its next forward returns I2V_E_STATE -- see Conventions) */
 int i2v_gblock_load(i2v_gblock* g, const i2v_tensor* tensors, int32_t n_tensors);
 size_t i2v_gblock_workspace_bytes(const i2v_gblock* g, int32_t batch, int32_t t, int32_t h, int32_t w);
 /* GeneratorBlock.forward(x, cond1 = z, cond2 = img): x [B,n_in,T,H,W] -> out [B,n_out,T,H,W]. */
@@ -427,6 +435,7 @@ int i2v_gblock_norm(i2v_gblock* g, int32_t part, const float* x, const float* co
 typedef struct i2v_embedder i2v_embedder;
 int i2v_embedder_create(int32_t z_dim, int32_t use_batchnorm, i2v_embedder** out);
 void i2v_embedder_destroy(i2v_embedder* e);
+/* (a failed load leaves the handle unloaded: its next forward returns I2V_E_STATE -- see Conventions) */
 int i2v_embedder_load(i2v_embedder* e, const i2v_tensor* tensors, int32_t n_tensors);
 size_t i2v_embedder_workspace_bytes(const i2v_embedder* e, int32_t batch, int32_t h, int32_t w);
 /* img [B,3,h,w] in [-1,1] (NCHW) -> embed [B, z_dim] */
@@ -447,6 +456,7 @@ typedef struct i2v_i3d i2v_i3d;
 int i2v_i3d_create(int32_t num_classes, int32_t in_channels, i2v_i3d** out);
 void i2v_i3d_destroy(i2v_i3d* n);
 /* Module.load_state_dict of the reference module (FVD_logging.load_model :208-214) */
+/* (a failed load leaves the handle unloaded: its next forward returns I2V_E_STATE -- see Conventions) */
 int i2v_i3d_load(i2v_i3d* n, const i2v_tensor* tensors, int32_t n_tensors);
 size_t i2v_i3d_workspace_bytes(const i2v_i3d* n, int32_t batch, int32_t t, int32_t h, int32_t w);
 /* FVD_logging.preprocess + I3D.forward: frames [B][t][3][h][w] fp32 (the decoder's output layout), denorm != 0: the values are
@@ -542,6 +552,7 @@ int i2v_vgg_create(i2v_vgg** out);
 void i2v_vgg_destroy(i2v_vgg* v);
 /* torchvision keys features.{0,2,5,7,10,12,14,17,19,21,24,26,28}.{weight [Cout][Cin][3][3], bias [Cout]} (other keys, the classifier
  * among them, are ignored) and, optionally, all five lin{0..4}.model.1.weight [1][C][1][1] of LPIPS.py:18-22.  Packed once, here. */
+/* (a failed load leaves the handle unloaded: its next forward returns I2V_E_STATE -- see Conventions) */
 int i2v_vgg_load(i2v_vgg* v, const i2v_tensor* tensors, int32_t n_tensors);
 /* Device pointer to the loaded lin{layer} weights [C] (NULL: none loaded, or layer outside 0..4). */
 const float* i2v_vgg_lin(const i2v_vgg* v, int32_t layer);
@@ -633,6 +644,7 @@ void i2v_inception_destroy(i2v_inception* n);
 /* torchvision keys <unit>.conv.weight [Cout][Cin][KH][KW] and <unit>.bn.{weight, bias, running_mean, running_var} [Cout] of every
  * BasicConv2d (Conv2d_1a_3x3 ... Mixed_7c.branch_pool); every other key (num_batches_tracked, fc.*, AuxLogits.*) is ignored.  A
  * missing or mis-shaped entry: I2V_E_MISSING with the key in i2v_last_error.  BatchNorm is folded to (scale, shift) here. */
+/* (a failed load leaves the handle unloaded: its next forward returns I2V_E_STATE -- see Conventions) */
 int i2v_inception_load(i2v_inception* n, const i2v_tensor* tensors, int32_t n_tensors);
 /* dims = (H', W', C) of output block 0..3 (inception.py:84-124: 64, 192, 768 channels, 2048 at 1 x 1) for an [h][w] trunk input. */
 int i2v_inception_block_shape(const i2v_inception* n, int32_t h, int32_t w, int32_t block, int32_t* dims);
@@ -684,6 +696,7 @@ typedef struct {
 } i2v_encoder3d_cfg;
 int i2v_encoder3d_create(const i2v_encoder3d_cfg* cfg, i2v_encoder3d** out);
 void i2v_encoder3d_destroy(i2v_encoder3d* e);
+/* (a failed load leaves the handle unloaded: its next forward returns I2V_E_STATE -- see Conventions) */
 int i2v_encoder3d_load(i2v_encoder3d* e, const i2v_tensor* tensors, int32_t n_tensors);
 size_t i2v_encoder3d_workspace_bytes(const i2v_encoder3d* e, int32_t batch, int32_t t, int32_t h, int32_t w);
 /* x [B,3,t,h,w] -> mu [B,z], logvar [B,z]; sample = eps * exp(0.5 logvar) + mu when sample != NULL (eps [B,z]). */
