@@ -1,8 +1,9 @@
-// VGG-16 `features` trunk (torchvision configuration D), the LPIPS layer reduction and the pair reduction of the VGG diversity score.
+// VGG-16 `features` trunk (torchvision configuration D): the handle, its weights, the forward and the input gradient.  The layer
+// table and the one walk over it (maps, buffers, sizes) are i2v_vgg_plan.h; the float64 reductions that consume the taps (the LPIPS
+// layer term and its backward, the pair reduction of the VGG diversity score) are i2v_lpips.hip.
 //
 // Replaces stage2_cINN/AE/modules/vgg16.py (vgg16.forward: the five slices up to relu1_2, relu2_2, relu3_3, relu4_3, relu5_3),
-// stage2_cINN/AE/modules/LPIPS.py (ScalingLayer, normalize_tensor, the lin layers, spatial_average) and the host path of
-// metrics/Diversity/VGG.py (kornia Normalize + Resize, the pair loop with one .cpu().item() per term).
+// ScalingLayer of stage2_cINN/AE/modules/LPIPS.py and kornia Normalize + Resize of metrics/Diversity/VGG.py (the input stage).
 //
 // Convolution: 3x3, stride 1, pad 1, bias, ReLU, channels-last [N][H][W][C], exact fp32 on v_mfma_f32_16x16x4_f32.
 //   A workgroup owns an 8 x 16 tile of output positions (M = 128; wave w the tile rows 2w and 2w + 1, one 16-row MFMA tile per
@@ -15,15 +16,13 @@
 //   Loads are unconditional with clamped addresses; the halo outside the map is zero.  The K order of an output element is
 //   (chunk, tap, channel): it depends on neither batch nor tile, so batch rows equal their single-image runs bit for bit.  No atomics.
 //
-// The reductions (lpips_layer, pairdiff) accumulate in float64 in two fixed-order stages: per-workgroup partial sums, then one
-// workgroup that adds them in index order.  The grid is a function of the shapes alone: two runs give the same bits.
-//
-// LPIPS as a loss (stage1_VAE/modules/loss.py: w_percep * LPIPS(seq_orig, seq_gen).mean()): the input gradient of the frozen trunk and of
-// the LPIPS head, see "backward (input gradient)" below.
+// LPIPS as a loss (stage1_VAE/modules/loss.py: w_percep * LPIPS(seq_orig, seq_gen).mean()): the input gradient of the frozen trunk, see
+// "backward (input gradient)" below (that of the LPIPS head: i2v_lpips.hip).
 #include <algorithm>
 #include <type_traits>
 
 #include "i2v_handle.h"
+#include "i2v_vgg_plan.h"
 
 namespace i2v {
 namespace {
@@ -262,113 +261,12 @@ __global__ __launch_bounds__(256) void vgg_input_kernel(const float* __restrict_
     }
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {   // fixed butterfly: every lane ends with the same bits
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-constexpr int LPIPS_G = 64;     // partial sums per image
-constexpr int PAIR_G = 1024;    // partial sums of the pair reduction
-constexpr int PAIR_RMAX = 16;
-
-// LPIPS.forward :44-48 for one layer: f0, f1 [N][P][C] fp32, lin [C].  One wave per position: the C = 64 KC channels of both maps go into
-// registers once, the two norms and sum_c w_c (f0 / (|f0| + 1e-10) - f1 / (|f1| + 1e-10))^2 are formed in float64.  Workgroup (n, g) sums
-// the positions 4 g + wave, + 4 G, ... of image n in order -> partial[n][g].
-template <int KC>
-__global__ __launch_bounds__(256) void lpips_partial_kernel(const float* __restrict__ f0, const float* __restrict__ f1, const float* __restrict__ lin,
-                                                            int P, int G, double* __restrict__ partial) {
-    __shared__ double red[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n = blockIdx.x / G, g = blockIdx.x % G;
-    constexpr int C = 64 * KC;
-    float w[KC];
-#pragma unroll
-    for (int k = 0; k < KC; ++k) w[k] = lin[lane + 64 * k];
-    double s = 0.0;
-    for (int p = 4 * g + wave; p < P; p += 4 * G) {
-        const float* a = f0 + ((long)n * P + p) * C;
-        const float* b = f1 + ((long)n * P + p) * C;
-        float x[KC], y[KC];
-        double sx = 0.0, sy = 0.0;
-#pragma unroll
-        for (int k = 0; k < KC; ++k) {
-            x[k] = a[lane + 64 * k]; y[k] = b[lane + 64 * k];
-            sx += (double)x[k] * (double)x[k]; sy += (double)y[k] * (double)y[k];
-        }
-        const double ix = 1.0 / (sqrt(wave_sum_f64(sx)) + 1e-10), iy = 1.0 / (sqrt(wave_sum_f64(sy)) + 1e-10);
-        double d = 0.0;
-#pragma unroll
-        for (int k = 0; k < KC; ++k) {
-            const double v = (double)x[k] * ix - (double)y[k] * iy;
-            d += (double)w[k] * v * v;
-        }
-        s += wave_sum_f64(d);
-    }
-    if (lane == 0) red[wave] = s;
-    __syncthreads();
-    if (tid == 0) partial[(long)n * G + g] = ((red[0] + red[1]) + red[2]) + red[3];
-}
-// out[n] += (sum_g partial[n][g]) / P: spatial_average
-__global__ __launch_bounds__(256) void lpips_final_kernel(const double* __restrict__ partial, int N, int P, int G, double* __restrict__ out) {
-    for (int n = threadIdx.x; n < N; n += 256) {
-        double s = 0.0;
-        for (int g = 0; g < G; ++g) s += partial[(long)n * G + g];
-        out[n] += s / (double)P;
-    }
-}
-
-// metrics/Diversity/VGG.py:38-43 for one group of R feature maps f [R][D]: every element is read once, the R values of index d sit in
-// registers and all pairs i < j are formed from them in float64.  Workgroup g sums d = 256 g + tid, + 256 G, ... in order -> partial[g].
-__global__ __launch_bounds__(256) void pairdiff_partial_kernel(const float* __restrict__ f, int R, long D, int G, double* __restrict__ partial) {
-    __shared__ double red[256];
-    const int tid = threadIdx.x;
-    double s = 0.0;
-    for (long d = (long)blockIdx.x * 256 + tid; d < D; d += (long)G * 256) {
-        float v[PAIR_RMAX];
-#pragma unroll
-        for (int i = 0; i < PAIR_RMAX; ++i) v[i] = i < R ? f[i * D + d] : 0.f;
-#pragma unroll
-        for (int i = 0; i < PAIR_RMAX; ++i)
-#pragma unroll
-            for (int j = i + 1; j < PAIR_RMAX; ++j)
-                if (j < R) {
-                    const double t = (double)v[i] - (double)v[j];
-                    s += t * t;
-                }
-    }
-    red[tid] = s;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (tid < w) red[tid] += red[tid + w];
-        __syncthreads();
-    }
-    if (tid == 0) partial[blockIdx.x] = red[0];
-}
-// acc[0] += 2 (sum_g partial[g]) / D (each unordered pair counts twice: the square is symmetric; .mean() over the map), acc[1] += R (R - 1)
-__global__ __launch_bounds__(256) void pairdiff_final_kernel(const double* __restrict__ partial, int G, int R, long D, double* __restrict__ acc) {
-    __shared__ double red[256];
-    const int tid = threadIdx.x;
-    double s = 0.0;
-    for (int g = tid; g < G; g += 256) s += partial[g];
-    red[tid] = s;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (tid < w) red[tid] += red[tid + w];
-        __syncthreads();
-    }
-    if (tid == 0) {
-        acc[0] += 2.0 * red[0] / (double)D;
-        acc[1] += (double)R * (R - 1);
-    }
-}
-
 // ------------------------------------------------------------------------------------------------------------ backward (input gradient)
 // The trunk is frozen: only the gradient at the input is formed.  The input gradient of a 3x3 / stride 1 / pad 1 convolution is the same
 // convolution over the output gradient with the kernel transposed (Cin <-> Cout) and the taps flipped, so twelve of the thirteen backward
 // convolutions are vgg_conv_kernel<16, VGG_EPI_DGRAD> on weights re-packed once per handle (dgrad_repack_kernel).  The first layer
 // (64 -> 3) has its own narrow kernel.  Everything else is one fused memory-bound pass per pool (vgg_maxpool2_bwd_kernel: routing, the
-// tap gradient that enters there, the ReLU mask), one pass per LPIPS layer (lpips_bwd_kernel) and one masked copy of the relu5_3 gradient.
+// tap gradient that enters there, the ReLU mask), one pass per LPIPS layer (lpips_bwd_kernel, i2v_lpips.hip) and one masked copy of the relu5_3 gradient.
 
 // forward-packed [nchunk_in][9][Cout][16] -> dgrad-packed [Cout / 16][9 flipped][Cin][16]: element (co, ci, tap) of the forward weight
 // sits at tap 8 - tap, "output" channel ci, "input" channel co of the backward convolution
@@ -493,57 +391,6 @@ __global__ __launch_bounds__(256) void vgg_relu_mask_kernel(const float* __restr
     }
 }
 
-// Backward of lpips_partial_kernel for one layer: with s = |f| over c, n = f / (s + eps), d = n0 - n1 and out[i] = sum_p sum_c lin d^2 / P,
-// an upstream weight u[i] gives dn0 = 2 u[i] / P lin d (dn1 = -dn0) and df = dn / (s + eps) - f (f . dn) / (s (s + eps)^2).  One wave per
-// position as in the forward: both feature vectors go into registers once, |f|^2 and f . dn are float64 wave sums, the result is rounded
-// to fp32 once.  s = 0 (an all-zero feature vector): the second term is dropped, df = dn / eps (torch's sqrt backward gives NaN there).
-// g0 / g1 null: that side's gradient is not written.  No reduction across positions: nothing to order.
-template <int KC>
-__global__ __launch_bounds__(256) void lpips_bwd_kernel(const float* __restrict__ f0, const float* __restrict__ f1, const float* __restrict__ lin,
-                                                        const double* __restrict__ u, int P, long NP, float* __restrict__ g0, float* __restrict__ g1) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    constexpr int C = 64 * KC;
-    constexpr double eps = 1e-10;
-    float w[KC];
-#pragma unroll
-    for (int k = 0; k < KC; ++k) w[k] = lin[lane + 64 * k];
-    for (long q = (long)blockIdx.x * 4 + wave; q < NP; q += (long)gridDim.x * 4) {
-        const double coef = 2.0 * u[q / P] / (double)P;
-        float x[KC], y[KC];
-        double sx = 0.0, sy = 0.0;
-#pragma unroll
-        for (int k = 0; k < KC; ++k) {
-            x[k] = f0[q * C + lane + 64 * k]; y[k] = f1[q * C + lane + 64 * k];
-            sx += (double)x[k] * (double)x[k]; sy += (double)y[k] * (double)y[k];
-        }
-        const double s0 = sqrt(wave_sum_f64(sx)), s1 = sqrt(wave_sum_f64(sy));
-        const double i0 = 1.0 / (s0 + eps), i1 = 1.0 / (s1 + eps);
-        double dn[KC], dx = 0.0, dy = 0.0;
-#pragma unroll
-        for (int k = 0; k < KC; ++k) {
-            dn[k] = coef * (double)w[k] * ((double)x[k] * i0 - (double)y[k] * i1);
-            dx += (double)x[k] * dn[k]; dy += (double)y[k] * dn[k];
-        }
-        dx = wave_sum_f64(dx); dy = wave_sum_f64(dy);
-        const double r0 = s0 > 0.0 ? dx * i0 * i0 / s0 : 0.0, r1 = s1 > 0.0 ? dy * i1 * i1 / s1 : 0.0;
-#pragma unroll
-        for (int k = 0; k < KC; ++k) {
-            if (g0) g0[q * C + lane + 64 * k] = (float)(dn[k] * i0 - (double)x[k] * r0);
-            if (g1) g1[q * C + lane + 64 * k] = (float)(-(dn[k] * i1 - (double)y[k] * r1));
-        }
-    }
-}
-
-// torchvision vgg16().features: index of every conv, its widths, and whether a tap / a pool follows its ReLU
-struct LayerSpec { int idx, cin, cout, tap, pool; };
-const LayerSpec VGG_LAYERS[13] = {
-    {0, 3, 64, -1, 0},    {2, 64, 64, 0, 1},                             // slice1: relu1_2, then MaxPool (features.4, head of slice2)
-    {5, 64, 128, -1, 0},  {7, 128, 128, 1, 1},                           // relu2_2
-    {10, 128, 256, -1, 0}, {12, 256, 256, -1, 0}, {14, 256, 256, 2, 1},  // relu3_3
-    {17, 256, 512, -1, 0}, {19, 512, 512, -1, 0}, {21, 512, 512, 3, 1},  // relu4_3
-    {24, 512, 512, -1, 0}, {26, 512, 512, -1, 0}, {28, 512, 512, 4, 0}}; // relu5_3 (features.30, the last pool, is not part of slice5)
-const int VGG_TAP_C[5] = {64, 128, 256, 512, 512};
-
 struct Conv {
     DevBuf w, bias;
     int Cin = 0, CinS = 0, Cout = 0, CC = 16, nchunk = 0;   // CinS: stored input channels (3 -> 4)
@@ -585,38 +432,36 @@ int Conv::pack(const float* wsrc, const float* bsrc, int cin, int cout) {
     return upload_packed(w, bias, p.data(), p.size() * 4, bsrc, cout);
 }
 
-int conv_launch(const Conv& c, const float* in, float* out, int N, int H, int W, hipStream_t st) {
-    VggConvArgs a{};
-    a.in = in; a.wp = c.w.as<float>(); a.bias = c.bias.as<float>(); a.out = out;
-    a.H = H; a.W = W; a.Cin = c.CinS; a.Cout = c.Cout; a.nchunk = c.nchunk;
-    a.tilesH = (H + VGG_TH - 1) / VGG_TH; a.tilesW = (W + VGG_TW - 1) / VGG_TW;
-    const long nblk = (long)N * a.tilesH * a.tilesW * (c.Cout / VGG_BN);
-    I2V_REQUIRE(nblk > 0 && nblk < (1L << 31), I2V_E_INVALID, "vgg conv: grid of %ld workgroups", nblk);
-    if (c.CC == 16) {
+// The one launch of vgg_conv_kernel<CC, EPI>: a (all but the tile counts filled in) over N maps.  CC = 16 needs more LDS than a
+// kernel gets by default: raised once per instantiation and device.
+template <int CC, int EPI>
+int conv_launch(VggConvArgs a, int N, const char* what, hipStream_t st) {
+    a.tilesH = (a.H + VGG_TH - 1) / VGG_TH; a.tilesW = (a.W + VGG_TW - 1) / VGG_TW;
+    const long nblk = (long)N * a.tilesH * a.tilesW * (a.Cout / VGG_BN);
+    I2V_REQUIRE(nblk > 0 && nblk < (1L << 31), I2V_E_INVALID, "%s: grid of %ld workgroups", what, nblk);
+    if constexpr (CC == 16) {
         static bool done[I2V_MAX_DEV];
-        if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(&vgg_conv_kernel<16>), vgg_lds_bytes(16), done)) return rc;
-        hipLaunchKernelGGL(vgg_conv_kernel<16>, dim3((unsigned)nblk), dim3(256), vgg_lds_bytes(16), st, a);
-    } else {
-        hipLaunchKernelGGL(vgg_conv_kernel<4>, dim3((unsigned)nblk), dim3(256), vgg_lds_bytes(4), st, a);
+        if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(&vgg_conv_kernel<CC, EPI>), vgg_lds_bytes(CC), done)) return rc;
     }
+    hipLaunchKernelGGL((vgg_conv_kernel<CC, EPI>), dim3((unsigned)nblk), dim3(256), vgg_lds_bytes(CC), st, a);
     I2V_HIP_CHECK(hipGetLastError());
     return I2V_OK;
 }
 
+int conv_fwd(const Conv& c, const float* in, float* out, int N, int H, int W, hipStream_t st) {
+    VggConvArgs a{};
+    a.in = in; a.wp = c.w.as<float>(); a.bias = c.bias.as<float>(); a.out = out;
+    a.H = H; a.W = W; a.Cin = c.CinS; a.Cout = c.Cout; a.nchunk = c.nchunk;
+    return c.CC == 16 ? conv_launch<16, VGG_EPI_FWD>(a, N, "vgg conv", st) : conv_launch<4, VGG_EPI_FWD>(a, N, "vgg conv", st);
+}
+
 // Input gradient of a forward conv cin -> cout: g [N][H][W][cout] -> out [N][H][W][cin] on the forward kernel with the DGRAD epilogue
-int dgrad_launch(const float* wb, int cin, int cout, const float* g, float* out, const float* add, const float* ymask, int N, int H, int W,
-                 hipStream_t st) {
+int conv_dgrad(const float* wb, int cin, int cout, const float* g, float* out, const float* add, const float* ymask, int N, int H, int W,
+               hipStream_t st) {
     VggConvArgs a{};
     a.in = g; a.wp = wb; a.bias = nullptr; a.out = out; a.add = add; a.ymask = ymask;
     a.H = H; a.W = W; a.Cin = cout; a.Cout = cin; a.nchunk = cout / 16;
-    a.tilesH = (H + VGG_TH - 1) / VGG_TH; a.tilesW = (W + VGG_TW - 1) / VGG_TW;
-    const long nblk = (long)N * a.tilesH * a.tilesW * (cin / VGG_BN);
-    I2V_REQUIRE(nblk > 0 && nblk < (1L << 31), I2V_E_INVALID, "vgg dgrad: grid of %ld workgroups", nblk);
-    static bool done[I2V_MAX_DEV];
-    if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(&vgg_conv_kernel<16, VGG_EPI_DGRAD>), vgg_lds_bytes(16), done)) return rc;
-    hipLaunchKernelGGL((vgg_conv_kernel<16, VGG_EPI_DGRAD>), dim3((unsigned)nblk), dim3(256), vgg_lds_bytes(16), st, a);
-    I2V_HIP_CHECK(hipGetLastError());
-    return I2V_OK;
+    return conv_launch<16, VGG_EPI_DGRAD>(a, N, "vgg dgrad", st);
 }
 
 int dgrad_first_launch(const float* w0, const float* g, float* out, int N, int H, int W, int nchw, hipStream_t st) {
@@ -638,8 +483,6 @@ int pool_launch(const float* in, float* out, int N, int H, int W, int C, hipStre
     return I2V_OK;
 }
 
-constexpr long VGG_MAX_FLOATS = 1L << 40;
-
 }  // namespace
 }  // namespace i2v
 
@@ -655,64 +498,6 @@ struct i2v_vgg {
 };
 
 namespace {
-
-// Buffer plan of the trunk: a conv that feeds a tap writes the caller's tap buffer; every other conv writes workspace buffer a, or b
-// when it reads a; a pool always writes a (its source is a tap buffer).  vgg_ws_floats sizes a and b by the same rule.
-void vgg_ws_floats(int N, int H, int W, size_t* a_floats, size_t* b_floats) {
-    size_t af = 0, bf = 0;
-    int h = H, w = W;
-    bool cur_is_a = false;
-    for (int l = 0; l < 13; ++l) {
-        const LayerSpec& s = VGG_LAYERS[l];
-        const size_t of = (size_t)N * h * w * s.cout;
-        if (s.tap < 0) {
-            if (cur_is_a) bf = std::max(bf, of); else af = std::max(af, of);
-            cur_is_a = !cur_is_a;
-        } else {
-            cur_is_a = false;
-        }
-        if (s.pool) {
-            h /= 2; w /= 2;
-            af = std::max(af, (size_t)N * h * w * s.cout);
-            cur_is_a = true;
-        }
-    }
-    *a_floats = af; *b_floats = bf;
-}
-
-// Saved state of the backward pass: the eight post-ReLU activations that are not taps, in layer order, each 256-byte aligned (the
-// five taps stay with the caller).  off[l]: byte offset of layer l (taps: unused); returns the total.
-size_t vgg_saved_offsets(int N, int H, int W, size_t* off) {
-    size_t total = 0;
-    int h = H, w = W;
-    for (int l = 0; l < 13; ++l) {
-        const LayerSpec& s = VGG_LAYERS[l];
-        off[l] = total;
-        if (s.tap < 0) total += align_up((size_t)N * h * w * s.cout * 4, 256);
-        if (s.pool) { h /= 2; w /= 2; }
-    }
-    return total;
-}
-
-// x: channels-last input [N][H][W][4]; a, b: the workspace buffers; saved (or null): where the non-tap activations are kept instead
-int vgg_run(const i2v_vgg* v, const float* x, int N, int H, int W, float* const* taps, float* a, float* b, char* saved, hipStream_t st) {
-    const float* cur = x;
-    int h = H, w = W;
-    size_t off[13];
-    vgg_saved_offsets(N, H, W, off);
-    for (int l = 0; l < 13; ++l) {
-        const LayerSpec& s = VGG_LAYERS[l];
-        float* dst = s.tap >= 0 ? taps[s.tap] : saved ? reinterpret_cast<float*>(saved + off[l]) : cur == a ? b : a;
-        if (int rc = conv_launch(v->conv[l], cur, dst, N, h, w, st)) return rc;
-        cur = dst;
-        if (s.pool) {
-            if (int rc = pool_launch(cur, a, N, h, w, s.cout, st)) return rc;
-            cur = a;
-            h /= 2; w /= 2;
-        }
-    }
-    return I2V_OK;
-}
 
 // The backward packing of layers 1..12 (14.7 M floats, 59 MB), made from the forward packing on the device by the first backward call
 // of a handle.  That call allocates; every later one only enqueues.  (Layer 0 needs none: vgg_dgrad_first_kernel reads the forward
@@ -736,7 +521,40 @@ int ensure_dgrad(i2v_vgg* v, hipStream_t st) {
     return I2V_OK;
 }
 
-bool vgg_dims_ok(int h, int w) { return (h >> 4) > 0 && (w >> 4) > 0; }
+// what every entry that runs the trunk asks of its shape (behind its own "bad argument" check, which covers batch > 0)
+int vgg_shape_check(const char* what, int batch, int h, int w) {
+    I2V_REQUIRE(vgg_dims_ok(h, w), I2V_E_INVALID, "%s: a %d x %d input leaves an empty map after four pools (at least 16 x 16 is needed)", what, h, w);
+    I2V_REQUIRE((long)batch * h * w * 64 < VGG_MAX_FLOATS, I2V_E_INVALID, "%s: batch %d x [%d, %d] is too large", what, batch, h, w);
+    return I2V_OK;
+}
+
+// i2v_vgg_features (saved_wanted false: saved is not looked at) and i2v_vgg_features_saved.  x: channels-last input
+// [batch][h][w][4]; saved: where the non-tap activations are kept instead of the workspace slots
+int vgg_features(const char* what, i2v_vgg* v, const float* x, int batch, int h, int w, float* const (&taps)[5], bool saved_wanted, void* saved,
+                 size_t saved_bytes, void* workspace, size_t workspace_bytes, hipStream_t st) {
+    I2V_ENTER(sc, v, Entry::NEEDS_WEIGHTS | Entry::NULL_IS_UNLOADED, what);
+    I2V_REQUIRE(x && taps[0] && taps[1] && taps[2] && taps[3] && taps[4] && (saved || !saved_wanted) && workspace && batch > 0, I2V_E_INVALID,
+                "%s: bad argument", what);
+    if (int rc = vgg_shape_check(what, batch, h, w)) return rc;
+    const VggPlan p = vgg_plan<Carver>(batch, h, w);
+    I2V_REQUIRE_WORKSPACE(workspace_bytes, p.ws_bytes, what);
+    I2V_REQUIRE(!saved_wanted || saved_bytes >= p.saved_bytes, I2V_E_WORKSPACE, "%s: saved state %zu < required %zu", what, saved_bytes, p.saved_bytes);
+    const float* cur = x;
+    for (int l = 0; l < 13; ++l) {
+        const VggLayerPlan& L = p.layer[l];
+        auto at = [&](VggBuf b) {
+            return b == VGG_BUF_TAP ? taps[L.tap] : b == VGG_BUF_SAVED ? Carver::at(saved, L.saved_off) : Carver::at(workspace, b == VGG_BUF_A ? p.ws_a : p.ws_b);
+        };
+        float* const out = at(L.dst(saved_wanted));
+        if (int rc = conv_fwd(v->conv[l], cur, out, batch, L.h, L.w, st)) return rc;
+        cur = out;
+        if (L.pool) {
+            if (int rc = pool_launch(out, at(L.pool_dst), batch, L.h, L.w, L.cout, st)) return rc;
+            cur = at(L.pool_dst);
+        }
+    }
+    return I2V_OK;
+}
 
 }  // namespace
 
@@ -781,10 +599,7 @@ const float* i2v_vgg_lin(const i2v_vgg* v, int32_t layer) {
 }
 
 size_t i2v_vgg_workspace_bytes(const i2v_vgg* v, int32_t batch, int32_t h, int32_t w) {
-    if (!v || batch <= 0 || !vgg_dims_ok(h, w)) return 0;
-    size_t af, bf;
-    vgg_ws_floats(batch, h, w, &af, &bf);
-    return align_up(af * 4, 256) + align_up(bf * 4, 256);
+    return v ? vgg_plan<Carver>(batch, h, w).ws_bytes : 0;   // (a shape the entries refuse has an empty plan)
 }
 
 int i2v_vgg_input_stage(const float* frames, int32_t n, int32_t hi, int32_t wi, int32_t mode, int32_t ho, int32_t wo, int32_t align_corners,
@@ -802,48 +617,30 @@ int i2v_vgg_input_stage(const float* frames, int32_t n, int32_t hi, int32_t wi, 
 
 int i2v_vgg_features(i2v_vgg* v, const float* x, int32_t batch, int32_t h, int32_t w, float* relu1_2, float* relu2_2, float* relu3_3, float* relu4_3,
                      float* relu5_3, void* workspace, size_t workspace_bytes, void* stream) {
-    I2V_ENTER(sc, v, Entry::NEEDS_WEIGHTS | Entry::NULL_IS_UNLOADED, "i2v_vgg_features");
-    I2V_REQUIRE(x && relu1_2 && relu2_2 && relu3_3 && relu4_3 && relu5_3 && workspace && batch > 0, I2V_E_INVALID, "i2v_vgg_features: bad argument");
-    I2V_REQUIRE(vgg_dims_ok(h, w), I2V_E_INVALID, "i2v_vgg_features: a %d x %d input leaves an empty map after four pools (at least 16 x 16 is needed)", h, w);
-    I2V_REQUIRE((long)batch * h * w * 64 < VGG_MAX_FLOATS, I2V_E_INVALID, "i2v_vgg_features: batch %d x [%d, %d] is too large", batch, h, w);
-    size_t af, bf;
-    vgg_ws_floats(batch, h, w, &af, &bf);
-    const size_t need = align_up(af * 4, 256) + align_up(bf * 4, 256);
-    I2V_REQUIRE_WORKSPACE(workspace_bytes, need, "i2v_vgg_features");
-    float* a = static_cast<float*>(workspace);
-    float* b = reinterpret_cast<float*>(static_cast<char*>(workspace) + align_up(af * 4, 256));
-    float* taps[5] = {relu1_2, relu2_2, relu3_3, relu4_3, relu5_3};
-    return vgg_run(v, x, batch, h, w, taps, a, b, nullptr, static_cast<hipStream_t>(stream));
+    return vgg_features("i2v_vgg_features", v, x, batch, h, w, {relu1_2, relu2_2, relu3_3, relu4_3, relu5_3}, false, nullptr, 0, workspace,
+                        workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
 size_t i2v_vgg_saved_bytes(const i2v_vgg* v, int32_t batch, int32_t h, int32_t w) {
-    if (!v || batch <= 0 || !vgg_dims_ok(h, w)) return 0;
-    size_t off[13];
-    return vgg_saved_offsets(batch, h, w, off);
+    return v ? vgg_plan<Carver>(batch, h, w).saved_bytes : 0;
 }
 
 size_t i2v_vgg_backward_workspace_bytes(const i2v_vgg* v, int32_t batch, int32_t h, int32_t w) {
-    if (!v || batch <= 0 || !vgg_dims_ok(h, w)) return 0;
-    return 2 * align_up((size_t)batch * h * w * 64 * 4, 256);   // two gradient maps of the largest size (relu1_x)
+    return v ? vgg_plan<Carver>(batch, h, w).bwd_bytes : 0;
+}
+
+int i2v_vgg_saved_layout(int32_t batch, int32_t h, int32_t w, i2v_vgg_layer* out) {
+    I2V_REQUIRE(out && batch > 0, I2V_E_INVALID, "i2v_vgg_saved_layout: bad argument");
+    if (int rc = vgg_shape_check("i2v_vgg_saved_layout", batch, h, w)) return rc;
+    const VggPlan p = vgg_plan<Carver>(batch, h, w);
+    for (int l = 0; l < 13; ++l) out[l] = {p.layer[l].h, p.layer[l].w, p.layer[l].cout, p.layer[l].tap, (int64_t)p.layer[l].saved_off};
+    return I2V_OK;
 }
 
 int i2v_vgg_features_saved(i2v_vgg* v, const float* x, int32_t batch, int32_t h, int32_t w, float* relu1_2, float* relu2_2, float* relu3_3,
                            float* relu4_3, float* relu5_3, void* saved, size_t saved_bytes, void* workspace, size_t workspace_bytes, void* stream) {
-    I2V_ENTER(sc, v, Entry::NEEDS_WEIGHTS | Entry::NULL_IS_UNLOADED, "i2v_vgg_features_saved");
-    I2V_REQUIRE(x && relu1_2 && relu2_2 && relu3_3 && relu4_3 && relu5_3 && saved && workspace && batch > 0, I2V_E_INVALID,
-                "i2v_vgg_features_saved: bad argument");
-    I2V_REQUIRE(vgg_dims_ok(h, w), I2V_E_INVALID,
-                "i2v_vgg_features_saved: a %d x %d input leaves an empty map after four pools (at least 16 x 16 is needed)", h, w);
-    I2V_REQUIRE((long)batch * h * w * 64 < VGG_MAX_FLOATS, I2V_E_INVALID, "i2v_vgg_features_saved: batch %d x [%d, %d] is too large", batch, h, w);
-    size_t af, bf, off[13];
-    vgg_ws_floats(batch, h, w, &af, &bf);
-    const size_t need = align_up(af * 4, 256) + align_up(bf * 4, 256), need_saved = vgg_saved_offsets(batch, h, w, off);
-    I2V_REQUIRE_WORKSPACE(workspace_bytes, need, "i2v_vgg_features_saved");
-    I2V_REQUIRE(saved_bytes >= need_saved, I2V_E_WORKSPACE, "i2v_vgg_features_saved: saved state %zu < required %zu", saved_bytes, need_saved);
-    float* a = static_cast<float*>(workspace);
-    float* b = reinterpret_cast<float*>(static_cast<char*>(workspace) + align_up(af * 4, 256));
-    float* taps[5] = {relu1_2, relu2_2, relu3_3, relu4_3, relu5_3};
-    return vgg_run(v, x, batch, h, w, taps, a, b, static_cast<char*>(saved), static_cast<hipStream_t>(stream));
+    return vgg_features("i2v_vgg_features_saved", v, x, batch, h, w, {relu1_2, relu2_2, relu3_3, relu4_3, relu5_3}, true, saved, saved_bytes,
+                        workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
 int i2v_vgg_backward(i2v_vgg* v, const float* const* taps, const float* const* tap_grads, const void* saved, size_t saved_bytes, int32_t batch,
@@ -852,41 +649,34 @@ int i2v_vgg_backward(i2v_vgg* v, const float* const* taps, const float* const* t
     I2V_REQUIRE(saved, I2V_E_STATE, "i2v_vgg_backward: no saved state (run i2v_vgg_features_saved first: i2v_vgg_features keeps only the taps)");
     I2V_REQUIRE(taps && tap_grads && out && workspace && batch > 0, I2V_E_INVALID, "i2v_vgg_backward: bad argument");
     for (int k = 0; k < 5; ++k) I2V_REQUIRE(taps[k] && tap_grads[k], I2V_E_INVALID, "i2v_vgg_backward: tap %d or its gradient is null", k);
-    I2V_REQUIRE(vgg_dims_ok(h, w), I2V_E_INVALID, "i2v_vgg_backward: a %d x %d input leaves an empty map after four pools (at least 16 x 16 is needed)",
-                h, w);
-    I2V_REQUIRE((long)batch * h * w * 64 < VGG_MAX_FLOATS, I2V_E_INVALID, "i2v_vgg_backward: batch %d x [%d, %d] is too large", batch, h, w);
-    size_t off[13];
-    const size_t need_saved = vgg_saved_offsets(batch, h, w, off), half = align_up((size_t)batch * h * w * 64 * 4, 256);
-    I2V_REQUIRE(saved_bytes >= need_saved, I2V_E_WORKSPACE, "i2v_vgg_backward: saved state %zu < required %zu", saved_bytes, need_saved);
-    I2V_REQUIRE_WORKSPACE(workspace_bytes, 2 * half, "i2v_vgg_backward");
+    if (int rc = vgg_shape_check("i2v_vgg_backward", batch, h, w)) return rc;
+    const VggPlan p = vgg_plan<Carver>(batch, h, w);
+    I2V_REQUIRE(saved_bytes >= p.saved_bytes, I2V_E_WORKSPACE, "i2v_vgg_backward: saved state %zu < required %zu", saved_bytes, p.saved_bytes);
+    I2V_REQUIRE_WORKSPACE(workspace_bytes, p.bwd_bytes, "i2v_vgg_backward");
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (int rc = ensure_dgrad(v, st)) return rc;
 
-    int hl[13], wl[13];
-    const float* y[13];
-    for (int l = 0, hh = h, ww = w; l < 13; ++l) {
-        const LayerSpec& s = VGG_LAYERS[l];
-        hl[l] = hh; wl[l] = ww;
-        y[l] = s.tap >= 0 ? taps[s.tap] : reinterpret_cast<const float*>(static_cast<const char*>(saved) + off[l]);
-        if (s.pool) { hh /= 2; ww /= 2; }
-    }
-    float* const A = static_cast<float*>(workspace);
-    float* const B = reinterpret_cast<float*>(static_cast<char*>(workspace) + half);
-    // cur: the gradient at the pre-activation of layer l, [batch][hl][wl][cout_l]
+    // y(l): the post-ReLU activation of layer l, where the forward left it
+    auto y = [&](int l) {
+        const VggLayerPlan& L = p.layer[l];
+        return L.tap >= 0 ? taps[L.tap] : Carver::at<const float>(const_cast<void*>(saved), L.saved_off);
+    };
+    float* const A = Carver::at(workspace, p.bwd_a);
+    float* const B = Carver::at(workspace, p.bwd_b);
+    // cur: the gradient at the pre-activation of layer l, [batch][h_l][w_l][cout_l]
     float* cur = A;
-    const long top4 = (long)batch * hl[12] * wl[12] * (512 / 4);
-    hipLaunchKernelGGL(vgg_relu_mask_kernel, dim3(grid_for(top4)), dim3(256), 0, st, tap_grads[4], y[12], cur, top4);
+    const long top4 = (long)batch * p.layer[12].h * p.layer[12].w * (512 / 4);
+    hipLaunchKernelGGL(vgg_relu_mask_kernel, dim3(grid_for(top4)), dim3(256), 0, st, tap_grads[4], y(12), cur, top4);
     I2V_HIP_CHECK(hipGetLastError());
     for (int l = 12; l >= 1; --l) {
-        const LayerSpec& s = VGG_LAYERS[l];
-        const LayerSpec& prev = VGG_LAYERS[l - 1];
+        const VggLayerPlan& s = p.layer[l];
+        const VggLayerPlan& prev = p.layer[l - 1];
         float* other = cur == A ? B : A;
-        const float* wb = v->dgrad_w[l].as<float>();
-        if (prev.pool) {   // the pooled gradient, then routing + the tap gradient that enters at y[l - 1] + its ReLU mask in one pass
-            if (int rc = dgrad_launch(wb, s.cin, s.cout, cur, other, nullptr, nullptr, batch, hl[l], wl[l], st)) return rc;
-            if (int rc = pool_bwd_launch(other, y[l - 1], tap_grads[prev.tap], cur, batch, hl[l - 1], wl[l - 1], prev.cout, 1, st)) return rc;
+        // inside a slice the ReLU mask of y(l - 1) rides on the dgrad conv; in front of a pool the pool's backward applies it
+        if (int rc = conv_dgrad(v->dgrad_w[l].as<float>(), s.cin, s.cout, cur, other, nullptr, prev.pool ? nullptr : y(l - 1), batch, s.h, s.w, st)) return rc;
+        if (prev.pool) {   // the pooled gradient is in `other`: routing + the tap gradient that enters at y(l - 1) + its ReLU mask in one pass
+            if (int rc = pool_bwd_launch(other, y(l - 1), tap_grads[prev.tap], cur, batch, prev.h, prev.w, prev.cout, 1, st)) return rc;
         } else {
-            if (int rc = dgrad_launch(wb, s.cin, s.cout, cur, other, nullptr, y[l - 1], batch, hl[l], wl[l], st)) return rc;
             cur = other;
         }
     }
@@ -904,19 +694,18 @@ int i2v_vgg_dgrad_unit(const float* g, const float* weight, const float* add, co
     I2V_REQUIRE(cin == 3 || !frames_out, I2V_E_INVALID, "i2v_vgg_dgrad_unit: only the first-layer form writes frames");
     I2V_REQUIRE((long)n * h * w * std::max(cin, cout) < (1L << 31), I2V_E_INVALID, "i2v_vgg_dgrad_unit: batch %d x [%d, %d] is too large", n, h, w);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    DevBuf wb;
+    Conv c;      // the first-layer form reads the forward packing,
+    DevBuf wb;   // every other one the backward packing
     if (cin == 3) {
-        Conv c;
         std::vector<float> zero(cout, 0.f);
         if (int rc = c.pack(weight, zero.data(), cin, cout)) return rc;
         if (int rc = dgrad_first_launch(c.w.as<float>(), g, out, n, h, w, frames_out ? 1 : 0, st)) return rc;
-        I2V_HIP_CHECK(hipStreamSynchronize(st));   // the packed weights die with this call
-        return I2V_OK;
+    } else {
+        const std::vector<float> p = pack_dgrad_host(weight, cin, cout);
+        if (int rc = wb.upload(p.data(), p.size() * 4)) return rc;
+        if (int rc = conv_dgrad(wb.as<float>(), cin, cout, g, out, add, ymask, n, h, w, st)) return rc;
     }
-    const std::vector<float> p = pack_dgrad_host(weight, cin, cout);
-    if (int rc = wb.upload(p.data(), p.size() * 4)) return rc;
-    if (int rc = dgrad_launch(wb.as<float>(), cin, cout, g, out, add, ymask, n, h, w, st)) return rc;
-    I2V_HIP_CHECK(hipStreamSynchronize(st));
+    I2V_HIP_CHECK(hipStreamSynchronize(st));   // the packed weights die with this call
     return I2V_OK;
 }
 
@@ -927,24 +716,6 @@ int i2v_vgg_maxpool2_backward(const float* grad, const float* y, const float* ad
     I2V_REQUIRE(c > 0 && c % 4 == 0, I2V_E_INVALID, "i2v_vgg_maxpool2_backward: %d channels (a multiple of 4 is needed)", c);
     I2V_REQUIRE((long)n * h * w * c < VGG_MAX_FLOATS, I2V_E_INVALID, "i2v_vgg_maxpool2_backward: batch %d x [%d, %d] x %d is too large", n, h, w, c);
     return pool_bwd_launch(grad, y, add, out, n, h, w, c, relu_mask ? 1 : 0, static_cast<hipStream_t>(stream));
-}
-
-int i2v_lpips_layer_backward(const float* f0, const float* f1, const float* lin, const double* upstream, int32_t n, int32_t p, int32_t c,
-                             float* grad0, float* grad1, void* stream) {
-    I2V_REQUIRE(f0 && f1 && lin && upstream && n > 0 && p > 0, I2V_E_INVALID, "i2v_lpips_layer_backward: bad argument");
-    I2V_REQUIRE(grad0 || grad1, I2V_E_INVALID, "i2v_lpips_layer_backward: no gradient requested (grad0 and grad1 are both null)");
-    I2V_REQUIRE(c == 64 || c == 128 || c == 256 || c == 512, I2V_E_INVALID,
-                "i2v_lpips_layer_backward: %d channels (64, 128, 256 or 512: the VGG-16 taps)", c);
-    I2V_REQUIRE((long)n * p * c < VGG_MAX_FLOATS && n <= (1 << 20), I2V_E_INVALID, "i2v_lpips_layer_backward: %d maps of %d positions is too large", n, p);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const long np = (long)n * p;
-    const dim3 grid((unsigned)std::min<long>((np + 3) / 4, 1L << 20));
-    if (c == 64) hipLaunchKernelGGL(lpips_bwd_kernel<1>, grid, dim3(256), 0, st, f0, f1, lin, upstream, p, np, grad0, grad1);
-    else if (c == 128) hipLaunchKernelGGL(lpips_bwd_kernel<2>, grid, dim3(256), 0, st, f0, f1, lin, upstream, p, np, grad0, grad1);
-    else if (c == 256) hipLaunchKernelGGL(lpips_bwd_kernel<4>, grid, dim3(256), 0, st, f0, f1, lin, upstream, p, np, grad0, grad1);
-    else hipLaunchKernelGGL(lpips_bwd_kernel<8>, grid, dim3(256), 0, st, f0, f1, lin, upstream, p, np, grad0, grad1);
-    I2V_HIP_CHECK(hipGetLastError());
-    return I2V_OK;
 }
 
 int i2v_vgg_conv_unit(const float* x, const float* weight, const float* bias, int32_t n, int32_t h, int32_t w, int32_t cin, int32_t cout, float* out,
@@ -958,7 +729,7 @@ int i2v_vgg_conv_unit(const float* x, const float* weight, const float* bias, in
     Conv c;
     if (int rc = c.pack(weight, bias, cin, cout)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (int rc = conv_launch(c, x, out, n, h, w, st)) return rc;
+    if (int rc = conv_fwd(c, x, out, n, h, w, st)) return rc;
     I2V_HIP_CHECK(hipStreamSynchronize(st));   // the packed weights die with this call
     return I2V_OK;
 }
@@ -968,46 +739,6 @@ int i2v_vgg_maxpool2(const float* x, int32_t n, int32_t h, int32_t w, int32_t c,
     I2V_REQUIRE(c > 0 && c % 4 == 0, I2V_E_INVALID, "i2v_vgg_maxpool2: %d channels (a multiple of 4 is needed)", c);
     I2V_REQUIRE((long)n * h * w * c < VGG_MAX_FLOATS, I2V_E_INVALID, "i2v_vgg_maxpool2: batch %d x [%d, %d] x %d is too large", n, h, w, c);
     return pool_launch(x, out, n, h, w, c, static_cast<hipStream_t>(stream));
-}
-
-size_t i2v_vgg_reduce_workspace_bytes(int32_t n) { return n > 0 ? (size_t)std::max(n * LPIPS_G, PAIR_G) * sizeof(double) : 0; }
-
-int i2v_lpips_layer(const float* f0, const float* f1, const float* lin, int32_t n, int32_t p, int32_t c, double* out, void* workspace,
-                    size_t workspace_bytes, void* stream) {
-    I2V_REQUIRE(f0 && f1 && lin && out && workspace && n > 0 && p > 0, I2V_E_INVALID, "i2v_lpips_layer: bad argument");
-    I2V_REQUIRE(c == 64 || c == 128 || c == 256 || c == 512, I2V_E_INVALID, "i2v_lpips_layer: %d channels (64, 128, 256 or 512: the VGG-16 taps)", c);
-    I2V_REQUIRE((long)n * p * c < VGG_MAX_FLOATS && n <= (1 << 20), I2V_E_INVALID, "i2v_lpips_layer: %d maps of %d positions is too large", n, p);
-    const int G = std::min((p + 3) / 4, LPIPS_G);
-    I2V_REQUIRE(workspace_bytes >= (size_t)n * G * sizeof(double), I2V_E_WORKSPACE, "i2v_lpips_layer: workspace %zu < required %zu", workspace_bytes,
-                (size_t)n * G * sizeof(double));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    double* partial = static_cast<double*>(workspace);
-    const dim3 grid((unsigned)(n * G));
-    if (c == 64) hipLaunchKernelGGL(lpips_partial_kernel<1>, grid, dim3(256), 0, st, f0, f1, lin, p, G, partial);
-    else if (c == 128) hipLaunchKernelGGL(lpips_partial_kernel<2>, grid, dim3(256), 0, st, f0, f1, lin, p, G, partial);
-    else if (c == 256) hipLaunchKernelGGL(lpips_partial_kernel<4>, grid, dim3(256), 0, st, f0, f1, lin, p, G, partial);
-    else hipLaunchKernelGGL(lpips_partial_kernel<8>, grid, dim3(256), 0, st, f0, f1, lin, p, G, partial);
-    I2V_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(lpips_final_kernel, dim3(1), dim3(256), 0, st, partial, n, p, G, out);
-    I2V_HIP_CHECK(hipGetLastError());
-    return I2V_OK;
-}
-
-int i2v_vgg_pairdiff_update(const float* maps, int32_t r, int64_t d, double* acc, void* workspace, size_t workspace_bytes, void* stream) {
-    I2V_REQUIRE(maps && acc && workspace && d > 0, I2V_E_INVALID, "i2v_vgg_pairdiff_update: bad argument");
-    I2V_REQUIRE(r >= 2 && r <= PAIR_RMAX, I2V_E_INVALID, "i2v_vgg_pairdiff_update: %d maps (2 to %d: a pair needs two, the kernel holds %d in registers)", r,
-                PAIR_RMAX, PAIR_RMAX);
-    I2V_REQUIRE((long)r * d < VGG_MAX_FLOATS, I2V_E_INVALID, "i2v_vgg_pairdiff_update: %d maps of %lld elements is too large", r, (long long)d);
-    const int G = (int)std::min<long>((d + 255) / 256, PAIR_G);
-    I2V_REQUIRE(workspace_bytes >= (size_t)G * sizeof(double), I2V_E_WORKSPACE, "i2v_vgg_pairdiff_update: workspace %zu < required %zu", workspace_bytes,
-                (size_t)G * sizeof(double));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    double* partial = static_cast<double*>(workspace);
-    hipLaunchKernelGGL(pairdiff_partial_kernel, dim3((unsigned)G), dim3(256), 0, st, maps, r, (long)d, G, partial);
-    I2V_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(pairdiff_final_kernel, dim3(1), dim3(256), 0, st, partial, G, r, (long)d, acc);
-    I2V_HIP_CHECK(hipGetLastError());
-    return I2V_OK;
 }
 
 }  // extern "C"

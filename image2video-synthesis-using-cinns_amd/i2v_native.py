@@ -61,6 +61,10 @@ class Enc3dCfg(ctypes.Structure):
                 ("use_max_pool", c_int32)]
 
 
+class VGGLayer(ctypes.Structure):
+    _fields_ = [("h", c_int32), ("w", c_int32), ("cout", c_int32), ("tap", c_int32), ("offset", c_int64)]
+
+
 _lib = None
 
 # symbol -> (restype, argtypes); also the list the CPU test-suite checks the .so exports
@@ -154,6 +158,7 @@ SYMBOLS = {
     "i2v_vgg_pairdiff_update": (c_int32, [c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
     "i2v_vgg_saved_bytes": (c_size_t, [c_void_p, c_int32, c_int32, c_int32]),
     "i2v_vgg_backward_workspace_bytes": (c_size_t, [c_void_p, c_int32, c_int32, c_int32]),
+    "i2v_vgg_saved_layout": (c_int32, [c_int32, c_int32, c_int32, POINTER(VGGLayer)]),
     "i2v_vgg_features_saved": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_size_t, c_void_p, c_size_t, c_void_p]),
     "i2v_lpips_layer_backward": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
@@ -1362,27 +1367,17 @@ def _require_f64(t, shape, device, what):
 class VGGSaved:
     """What ``NativeVGG.backward`` needs of one forward pass: the five taps and the buffer of the eight other post-ReLU activations."""
 
-    # (output channels, tap index or -1, pool behind it) of the thirteen convolutions: the layout of the buffer (csrc/i2v_vgg.hip)
-    LAYERS = ((64, -1, 0), (64, 0, 1), (128, -1, 0), (128, 1, 1), (256, -1, 0), (256, -1, 0), (256, 2, 1), (512, -1, 0), (512, -1, 0), (512, 3, 1),
-              (512, -1, 0), (512, -1, 0), (512, 4, 0))
-
     def __init__(self, shape, taps, buf):
         self.shape, self.taps, self.buf = tuple(shape), list(taps), buf
 
     def activations(self):
-        """The thirteen post-ReLU activations, channels-last [N, H', W', C], as views of the taps and of the buffer."""
-        n, h, w, _ = self.shape
-        acts, off = [], 0
-        for cout, tap, pool in self.LAYERS:
-            if tap >= 0:
-                acts.append(self.taps[tap])
-            else:
-                nbytes = n * h * w * cout * 4
-                acts.append(self.buf[off:off + nbytes].view(torch.float32).view(n, h, w, cout))
-                off += (nbytes + 255) // 256 * 256
-            if pool:
-                h, w = h // 2, w // 2
-        return acts
+        """The thirteen post-ReLU activations, channels-last [N, H', W', C], as views of the taps and of the buffer (where each lies:
+        ``i2v_vgg_saved_layout``, the layer plan of csrc/i2v_vgg_plan.h)."""
+        n = self.shape[0]
+        lay = (VGGLayer * 13)()
+        _call("i2v_vgg_saved_layout", n, self.shape[1], self.shape[2], lay)
+        return [self.taps[L.tap] if L.tap >= 0 else
+                self.buf[L.offset:L.offset + n * L.h * L.w * L.cout * 4].view(torch.float32).view(n, L.h, L.w, L.cout) for L in lay]
 
 
 def _ptrs(tensors):
@@ -1479,24 +1474,9 @@ class NativeVGG(_Handle):
             raise I2VError("lpips: the handle was loaded without lin{0..4}.model.1.weight")
         if not (need0 or need1):
             raise I2VError("lpips backward: no gradient requested")
-        n = taps0[0].shape[0]
-        _require_f64(upstream, (n,), taps0[0].device, "lpips backward")
-        g0 = ([torch.empty_like(t) for t in taps0] if out0 is None else list(out0)) if need0 else None
-        g1 = ([torch.empty_like(t) for t in taps1] if out1 is None else list(out1)) if need1 else None
-        for k, (a, b) in enumerate(zip(taps0, taps1)):
-            _require_cl4(a, "lpips backward")
-            _require_cl4(b, "lpips backward")
-            if a.shape != b.shape:
-                raise I2VError(f"lpips backward: taps of different shapes {tuple(a.shape)} / {tuple(b.shape)}")
-            for g in (g0, g1):
-                if g is not None:
-                    _require_gpu(g[k])
-                    if g[k].shape != a.shape:
-                        raise I2VError(f"lpips backward: a gradient buffer of shape {tuple(g[k].shape)} for a tap of shape {tuple(a.shape)}")
-            _call("i2v_lpips_layer_backward", a.data_ptr(), b.data_ptr(), lib().i2v_vgg_lin(self._h, k), upstream.data_ptr(), n,
-                                              a.shape[1] * a.shape[2], a.shape[3], g0[k].data_ptr() if need0 else None,
-                                              g1[k].data_ptr() if need1 else None, _stream())
-        return g0, g1
+        g = [lpips_layer_backward(a, b, lib().i2v_vgg_lin(self._h, k), upstream, need0, need1, None if out0 is None else out0[k],
+                                  None if out1 is None else out1[k]) for k, (a, b) in enumerate(zip(taps0, taps1))]
+        return [g0 for g0, _ in g] if need0 else None, [g1 for _, g1 in g] if need1 else None
 
     @_on_device
     def lpips(self, taps0, taps1):
@@ -1507,12 +1487,7 @@ class NativeVGG(_Handle):
         out = torch.zeros(n, dtype=torch.float64, device=taps0[0].device)
         ws = _reduce_ws(n, out.device)
         for k, (a, b) in enumerate(zip(taps0, taps1)):
-            _require_cl4(a, "lpips")
-            _require_cl4(b, "lpips")
-            if a.shape != b.shape:
-                raise I2VError(f"lpips: taps of different shapes {tuple(a.shape)} / {tuple(b.shape)}")
-            _call("i2v_lpips_layer", a.data_ptr(), b.data_ptr(), lib().i2v_vgg_lin(self._h, k), n, a.shape[1] * a.shape[2], a.shape[3],
-                                     out.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+            lpips_layer(a, b, lib().i2v_vgg_lin(self._h, k), out, ws)
         return out
 
 
@@ -1530,12 +1505,15 @@ def vgg_input_stage(frames, mode, size=None, align_corners=False):
     return out
 
 
+def _host_f32(a):
+    return np.ascontiguousarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.float32)
+
+
 def vgg_conv_unit(x, weight, bias):
     """``i2v_vgg_conv_unit``: x [N, H, W, cin] channels-last on the device (cin = 3: [N, H, W, 4]), host ``weight`` [cout, cin, 3, 3] and
     ``bias`` [cout] -> relu(conv + bias) [N, H, W, cout]."""
     _require_cl4(x, "vgg_conv_unit")
-    w = np.ascontiguousarray(weight.detach().cpu().numpy() if isinstance(weight, torch.Tensor) else weight, dtype=np.float32)
-    b = np.ascontiguousarray(bias.detach().cpu().numpy() if isinstance(bias, torch.Tensor) else bias, dtype=np.float32)
+    w, b = _host_f32(weight), _host_f32(bias)
     if w.ndim != 4 or w.shape[2:] != (3, 3) or b.shape != (w.shape[0],):
         raise I2VError(f"vgg_conv_unit: expected weight [cout,cin,3,3] and bias [cout], got {w.shape} / {b.shape}")
     cout, cin = w.shape[:2]
@@ -1564,7 +1542,7 @@ def vgg_dgrad_unit(g, weight, add=None, ymask=None, frames=False):
     host ``weight`` [cout, cin, 3, 3] -> (dgrad + add) * (ymask > 0) [N, H, W, cin].  cin = 3 is the first-layer form: [N, H, W, 4], or with
     ``frames`` [N, 3, H, W] divided by ScalingLayer's scale."""
     _require_cl4(g, "vgg_dgrad_unit")
-    w = np.ascontiguousarray(weight.detach().cpu().numpy() if isinstance(weight, torch.Tensor) else weight, dtype=np.float32)
+    w = _host_f32(weight)
     if w.ndim != 4 or w.shape[2:] != (3, 3):
         raise I2VError(f"vgg_dgrad_unit: expected weight [cout,cin,3,3], got {w.shape}")
     cout, cin = w.shape[:2]
@@ -1602,35 +1580,47 @@ def vgg_maxpool2_backward(grad, y, add=None, relu_mask=False):
     return out
 
 
-def lpips_layer_backward(f0, f1, lin, upstream, need0=True, need1=True):
-    """``i2v_lpips_layer_backward`` for one layer: f0, f1 [N, H, W, C] channels-last taps, lin [C], upstream [N] float64 -> (g0, g1), None
-    where not needed."""
-    _require_cl4(f0, "lpips_layer_backward")
-    _require_cl4(f1, "lpips_layer_backward")
-    _require_gpu(lin)
+def _lpips_layer_args(f0, f1, lin, what):
+    """What the two one-layer calls check alike: f0, f1 channels-last taps of one shape; ``lin`` [C] a device tensor, or the device
+    pointer ``i2v_vgg_lin`` gave (nothing to check).  -> (N, H * W, C, the pointer of lin)."""
+    _require_cl4(f0, what)
+    _require_cl4(f1, what)
     n, h, w, c = f0.shape
-    if f1.shape != f0.shape or tuple(lin.shape) != (c,):
-        raise I2VError(f"lpips_layer_backward: shapes {tuple(f0.shape)} / {tuple(f1.shape)} / {tuple(lin.shape)}")
+    lin_shape = tuple(lin.shape) if isinstance(lin, torch.Tensor) else (c,)
+    if isinstance(lin, torch.Tensor):
+        _require_gpu(lin)
+        lin = lin.data_ptr()
+    if f1.shape != f0.shape or lin_shape != (c,):
+        raise I2VError(f"{what}: shapes {tuple(f0.shape)} / {tuple(f1.shape)} / {lin_shape}")
+    return n, h * w, c, lin
+
+
+def lpips_layer_backward(f0, f1, lin, upstream, need0=True, need1=True, out0=None, out1=None):
+    """``i2v_lpips_layer_backward`` for one layer: f0, f1 [N, H, W, C] channels-last taps, lin [C] (or its pointer from ``i2v_vgg_lin``),
+    upstream [N] float64 -> (g0, g1), None where not needed.  ``out0`` / ``out1``: caller-owned buffers of the taps' shape."""
+    n, p, c, lin = _lpips_layer_args(f0, f1, lin, "lpips_layer_backward")
     _require_f64(upstream, (n,), f0.device, "lpips_layer_backward")
-    g0, g1 = (torch.empty_like(f0) if need0 else None), (torch.empty_like(f1) if need1 else None)
+    g = [(torch.empty_like(f0) if out is None else out) if need else None for need, out in ((need0, out0), (need1, out1))]
+    for t in g:
+        if t is not None:
+            _require_gpu(t)
+            if t.shape != f0.shape:
+                raise I2VError(f"lpips_layer_backward: a gradient buffer of shape {tuple(t.shape)} for a tap of shape {tuple(f0.shape)}")
     with torch.cuda.device(f0.device):
-        _call("i2v_lpips_layer_backward", f0.data_ptr(), f1.data_ptr(), lin.data_ptr(), upstream.data_ptr(), n, h * w, c,
-                                          None if g0 is None else g0.data_ptr(), None if g1 is None else g1.data_ptr(), _stream())
-    return g0, g1
+        _call("i2v_lpips_layer_backward", f0.data_ptr(), f1.data_ptr(), lin, upstream.data_ptr(), n, p, c,
+                                          *[None if t is None else t.data_ptr() for t in g], _stream())
+    return tuple(g)
 
 
-def lpips_layer(f0, f1, lin, out):
-    """``out`` [N] (float64, device) += the LPIPS term of one layer (``i2v_lpips_layer``): f0, f1 [N, H, W, C] channels-last taps, lin [C]."""
-    _require_cl4(f0, "lpips_layer")
-    _require_cl4(f1, "lpips_layer")
-    _require_gpu(lin)
-    n, h, w, c = f0.shape
-    if f1.shape != f0.shape or tuple(lin.shape) != (c,):
-        raise I2VError(f"lpips_layer: shapes {tuple(f0.shape)} / {tuple(f1.shape)} / {tuple(lin.shape)}")
+def lpips_layer(f0, f1, lin, out, ws=None):
+    """``out`` [N] (float64, device) += the LPIPS term of one layer (``i2v_lpips_layer``): f0, f1 [N, H, W, C] channels-last taps, lin [C]
+    (or its pointer from ``i2v_vgg_lin``).  ``ws``: the reduction scratch of ``_reduce_ws(N)`` when the caller holds one."""
+    n, p, c, lin = _lpips_layer_args(f0, f1, lin, "lpips_layer")
     _require_f64(out, (n,), f0.device, "lpips_layer")
-    ws = _reduce_ws(n, f0.device)
+    if ws is None:
+        ws = _reduce_ws(n, f0.device)
     with torch.cuda.device(f0.device):
-        _call("i2v_lpips_layer", f0.data_ptr(), f1.data_ptr(), lin.data_ptr(), n, h * w, c, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+        _call("i2v_lpips_layer", f0.data_ptr(), f1.data_ptr(), lin, n, p, c, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
 
 
 def vgg_pairdiff_update(maps, acc):
@@ -1736,10 +1726,6 @@ def inception_input_stage(frames, resize=True, normalize=False):
     with torch.cuda.device(frames.device):
         _call("i2v_inception_input_stage", frames.data_ptr(), n, h, w, int(bool(resize)), int(bool(normalize)), out.data_ptr(), _stream())
     return out
-
-
-def _host_f32(a):
-    return np.ascontiguousarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.float32)
 
 
 def inception_conv_unit(x, weight, bn, stride=1, padding=(0, 0), in_off=0, out=None, out_off=0):

@@ -3,7 +3,7 @@ https://github.com/richzhang/PerceptualSimilarity): a metric and, with frozen we
 
 ``LPIPS`` keeps the reference's ``state_dict`` keys (``scaling_layer.shift/scale``, ``net.slice*``, ``lin{k}.model.1.weight``).  ``forward``
 keeps the frames on the device: ScalingLayer and the layout change are one kernel, both images go through the native VGG-16 trunk,
-and every layer's normalise / difference / 1x1 conv / spatial mean is ONE reduction in float64 (``i2v_lpips_layer``).  Dropout is the
+and every layer's normalise / difference / 1x1 conv / spatial mean is ONE reduction in float64 (``i2v_lpips_layer``, csrc/i2v_lpips.hip).  Dropout is the
 identity (the metric is evaluated in eval mode).  Weights come from files: ``vgg_path`` (torchvision's vgg16 state_dict) and ``lin_path``
 (the ``vgg.pth`` of the LPIPS release: ``lin{k}.model.1.weight``); nothing is downloaded, there is no ``ckpt_util``.
 
@@ -55,7 +55,7 @@ class LPIPS(nn.Module):
         if input.shape != target.shape or input.dim() != 4 or input.shape[1] != 3:
             raise ValueError(f"LPIPS.forward: expected two [N,3,H,W] batches, got {tuple(input.shape)} / {tuple(target.shape)}")
         if not input.is_cuda or not target.is_cuda:
-            raise i2v_native.I2VError("LPIPS runs on a HIP device only (csrc/i2v_vgg.hip); this package has no CPU fallback")
+            raise i2v_native.I2VError("LPIPS runs on a HIP device only (csrc/i2v_vgg.hip, csrc/i2v_lpips.hip); this package has no CPU fallback")
         with torch.no_grad():
             self.net._lin = [w.reshape(-1) for w in self._lins()]
             native = self.net.native()

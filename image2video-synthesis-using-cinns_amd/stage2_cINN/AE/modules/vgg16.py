@@ -1,7 +1,7 @@
 """VGG-16 feature trunk: own implementation of the reference's ``stage2_cINN/AE/modules/vgg16.py`` surface.
 
 ``vgg16`` is a parameter holder with the reference's ``state_dict`` keys (``slice1.0.weight`` ... ``slice5.28.bias``: the ``features`` part
-of torchvision's configuration D cut into five slices); ``forward`` runs on the device through ``csrc/i2v_vgg.hip`` (thirteen 3x3
+of torchvision's configuration D cut into five slices); ``forward`` runs on the device through ``csrc/i2v_vgg.hip`` (its layer plan: ``csrc/i2v_vgg_plan.h``; thirteen 3x3
 convolutions in exact fp32 on the matrix cores, four 2x2 max pools) and returns the reference's namedtuple.  torchvision is not a
 dependency: the graph is written out here and the weights come from torchvision's ``vgg16`` state_dict FILE (keys ``features.N.*``;
 the classifier keys are ignored).  Nothing is ever downloaded: a missing file raises ``FileNotFoundError`` naming it.

@@ -537,7 +537,8 @@ int i2v_i3d_head_forward(i2v_i3d* n, const float* x, int32_t batch, int32_t t, f
                          size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * VGG-16 feature trunk, LPIPS and the VGG diversity score (csrc/i2v_vgg.hip) -- stage2_cINN/AE/modules/vgg16.py (vgg16.forward
+ * VGG-16 feature trunk (csrc/i2v_vgg.hip; its layer plan: csrc/i2v_vgg_plan.h), LPIPS and the VGG diversity score (the reductions:
+ * csrc/i2v_lpips.hip) -- stage2_cINN/AE/modules/vgg16.py (vgg16.forward
  * :30-42: the `features` trunk of torchvision's configuration D cut into five slices), stage2_cINN/AE/modules/LPIPS.py (LPIPS.forward
  * :38-52, ScalingLayer :55-62, NetLinLayer :65-72) and metrics/Diversity/VGG.py (compute_vgg_diversity :9-47).
  * Thirteen 3x3 convolutions (stride 1, pad 1, bias, ReLU) in exact fp32 on the matrix cores and four MaxPool2d(2, 2); activations
@@ -595,6 +596,14 @@ int i2v_vgg_pairdiff_update(const float* maps, int32_t r, int64_t d, double* acc
 size_t i2v_vgg_saved_bytes(const i2v_vgg* v, int32_t batch, int32_t h, int32_t w);
 /* Workspace of i2v_vgg_backward: two gradient maps of relu1_2's size.  0 when h or w is below 16. */
 size_t i2v_vgg_backward_workspace_bytes(const i2v_vgg* v, int32_t batch, int32_t h, int32_t w);
+/* Where the thirteen post-ReLU activations of one i2v_vgg_features_saved pass lie: out[13] in layer order, each [batch][h][w][cout]
+ * fp32; tap >= 0: it is that tap (the caller's buffer), else it starts at byte `offset` of `saved`.  A host function: no handle, no
+ * device call.  I2V_E_INVALID for a shape i2v_vgg_features_saved refuses. */
+typedef struct {
+    int32_t h, w, cout, tap;
+    int64_t offset;
+} i2v_vgg_layer;
+int i2v_vgg_saved_layout(int32_t batch, int32_t h, int32_t w, i2v_vgg_layer* out);
 /* vgg16.forward (vgg16.py:30-42) as i2v_vgg_features, the same kernels and the same tap bits; the intermediate activations go to
  * `saved` instead of a ping-pong workspace (the ReLU masks of the backward pass; the pool arg-max is read from the taps). */
 int i2v_vgg_features_saved(i2v_vgg* v, const float* x, int32_t batch, int32_t h, int32_t w, float* relu1_2, float* relu2_2, float* relu3_3,

@@ -1,4 +1,4 @@
-"""GPU checks of the LPIPS backward pass (csrc/i2v_vgg.hip): the input-gradient convolution and its first-layer form against float64 at
+"""GPU checks of the LPIPS backward pass (csrc/i2v_vgg.hip, csrc/i2v_lpips.hip): the input-gradient convolution and its first-layer form against float64 at
 the dot-product bound, the max-pool backward bit for bit against torch, the LPIPS head backward against its closed form, and
 ``LPIPS(x0, x1).backward()`` / ``vgg16(X)`` end to end against the float64 graph that takes its ReLU masks and pool arg-max from the GPU's
 own saved activations, and against the gradients of the reference's module (tests/golden/vgg_lpips_grad.npz).  Run with ``-s`` to see the

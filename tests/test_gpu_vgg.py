@@ -1,4 +1,4 @@
-"""GPU checks of the native VGG-16 trunk (csrc/i2v_vgg.hip): one convolution against the float64 oracle at the element-wise dot-product
+"""GPU checks of the native VGG-16 trunk (csrc/i2v_vgg.hip) and the reductions on its taps (csrc/i2v_lpips.hip): one convolution against the float64 oracle at the element-wise dot-product
 bound over ragged tiles, batches and chunk counts; the max pool bit for bit; the input stage; the five taps, LPIPS and the diversity
 score against the fixtures written from the reference's own modules (tests/golden/make_golden_vgg.py); repeatability and graph capture."""
 import numpy as np

@@ -22,7 +22,7 @@ SCALARS = {"int": ctypes.c_int32, "int32_t": ctypes.c_int32, "int64_t": ctypes.c
            "double": ctypes.c_double}
 STRUCTS = {"i2v_tensor": i2v_native._Tensor, "i2v_flow_cfg": i2v_native.FlowCfg, "i2v_flow_train_layout": i2v_native.FlowTrainLayout,
            "i2v_adam_tensor": i2v_native.AdamTensor, "i2v_dec_cfg": i2v_native.DecCfg, "i2v_frames_cfg": i2v_native.FramesCfg,
-           "i2v_encoder3d_cfg": i2v_native.Enc3dCfg}
+           "i2v_encoder3d_cfg": i2v_native.Enc3dCfg, "i2v_vgg_layer": i2v_native.VGGLayer}
 HANDLES = ("i2v_flow", "i2v_flow_train", "i2v_mlp", "i2v_gblock", "i2v_dec", "i2v_embedder", "i2v_encoder3d", "i2v_i3d", "i2v_vgg", "i2v_inception")
 
 
@@ -119,9 +119,9 @@ def test_symbol_table_and_structures_match_the_header():
     scalar type, array length.  The comparer is shown not to be blind: an entry with an argument dropped and one with c_int32 swapped
     for c_int64 are both flagged, and so is a Structure with a field of the wrong width."""
     funcs, structs = parse_header()
-    assert len(funcs) == 128 and set(funcs) == set(i2v_native.SYMBOLS)
+    assert len(funcs) == 129 and set(funcs) == set(i2v_native.SYMBOLS)
     assert compare_functions(funcs, i2v_native.SYMBOLS) == []
-    assert len(structs) == 7 and compare_structs(structs) == []
+    assert len(structs) == 8 and compare_structs(structs) == []
 
     res, args = i2v_native.SYMBOLS["i2v_dec_forward_strided"]
     assert ctypes.c_int32 in args

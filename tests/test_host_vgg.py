@@ -2,6 +2,7 @@
 own modules, the deliberate errors the gates have to catch, the new native symbols, the holders' key lists, the refusals and the CLIs."""
 import os
 import re
+import shutil
 import subprocess
 import sys
 
@@ -17,7 +18,7 @@ from stage2_cINN.AE.modules import LPIPS as lpips_mod
 from stage2_cINN.AE.modules import vgg16 as vgg_mod
 
 NEW_SYMBOLS = ["i2v_vgg_create", "i2v_vgg_destroy", "i2v_vgg_load", "i2v_vgg_lin", "i2v_vgg_workspace_bytes", "i2v_vgg_input_stage", "i2v_vgg_features",
-               "i2v_vgg_conv_unit", "i2v_vgg_maxpool2", "i2v_vgg_reduce_workspace_bytes", "i2v_lpips_layer", "i2v_vgg_pairdiff_update"]
+               "i2v_vgg_conv_unit", "i2v_vgg_maxpool2", "i2v_vgg_reduce_workspace_bytes", "i2v_lpips_layer", "i2v_vgg_pairdiff_update", "i2v_vgg_saved_layout"]
 
 
 # ---------------------------------------------------------------------------------------------------------------- oracle vs fixtures
@@ -126,11 +127,61 @@ def test_header_symbols_are_declared_listed_and_exported():
         assert name in declared and name in i2v_native.SYMBOLS and hasattr(lib, name), name
     for ref in ("stage2_cINN/AE/modules/vgg16.py", "stage2_cINN/AE/modules/LPIPS.py", "metrics/Diversity/VGG.py", "ScalingLayer", "normalize_tensor"):
         assert ref in header, ref
-    assert "i2v_vgg.hip" in open(os.path.join(PKG, "csrc", "Makefile")).read()
+    makefile = open(os.path.join(PKG, "csrc", "Makefile")).read()
+    assert "i2v_vgg.hip" in makefile and "i2v_lpips.hip" in makefile and "i2v_vgg_plan.h" in makefile
     for name in ("vgg16.py", "LPIPS.py"):
         text = open(os.path.join(PKG, "stage2_cINN", "AE", "modules", name)).read()
         assert not re.search(r"^\s*(import|from) (torchvision|requests|kornia|lpips)", text, flags=re.M), name
     assert not os.path.exists(os.path.join(PKG, "stage2_cINN", "AE", "modules", "ckpt_util.py"))
+
+
+@pytest.mark.parametrize("san", [False, True], ids=["plain", "asan_ubsan"])
+def test_layer_plan_equals_the_rules_the_entries_spelled_out(tmp_path, san):
+    """tests/vgg_plan_host_check.cpp: vgg_plan of csrc/i2v_vgg_plan.h at 4 batch sizes x 10 x 10 maps against the slot-sizing loop, the
+    saved-offset loop, the forward's pointer comparison and the backward's two halves, written out independently -- the three byte
+    totals, every offset, every layer's map and the destination of every conv and pool with and without saved state.  A stand-alone
+    host program; with the sanitizers it is built with them and run directly.  `--perturb` (slots a and b of one layer swapped) has
+    to be counted: the check is not blind."""
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("no hipcc")
+    exe = tmp_path / "vgg_plan_host_check"
+    flags = ["-O1", "-g", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all"] if san else ["-O1"]
+    r = subprocess.run([hipcc, "-std=c++17", "-Wall", "-Werror", "--offload-arch=gfx950"] + flags + ["-I" + os.path.join(PKG, "csrc"), "-I" + os.path.join(REPO, "include"),
+                        "-x", "hip", os.path.join(REPO, "tests", "vgg_plan_host_check.cpp"), "-o", str(exe)], capture_output=True, text=True, timeout=900)
+    if san and r.returncode != 0 and re.search(r"cannot find -l(asan|ubsan)|libclang_rt\.\w+san", r.stderr):
+        pytest.skip("this compiler has no sanitizer runtime")
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and out.stderr == "", out.stdout + out.stderr
+    m = re.search(r"(\d+) shapes, (\d+) checks, 0 mismatches: ok", out.stdout)
+    assert m and int(m.group(1)) == 4 * 10 * 10 and int(m.group(2)) > 200 * int(m.group(1)), out.stdout
+    bad = subprocess.run([str(exe), "--perturb"], capture_output=True, text=True, timeout=300)
+    m = re.search(r"(\d+) shapes, \d+ checks, (\d+) mismatches: FAILED", bad.stdout)
+    assert bad.returncode != 0 and m and int(m.group(2)) >= int(m.group(1)), bad.stdout + bad.stderr
+
+
+@pytest.mark.parametrize("n,h,w", [(3, 16, 16), (2, 35, 29), (1, 24, 40)])
+def test_saved_layout_query_equals_the_rule_the_binding_used_to_carry(n, h, w):
+    """i2v_vgg_saved_layout (a host function: no device) against the table and the 256-byte rule VGGSaved.activations spelled out
+    before it asked the library, and against tap_shapes."""
+    if not os.path.exists(i2v_native.LIB_PATH):
+        pytest.skip("library not built")
+    lay = (i2v_native.VGGLayer * 13)()
+    assert i2v_native.lib().i2v_vgg_saved_layout(n, h, w, lay) == 0
+    layers = ((64, -1, 0), (64, 0, 1), (128, -1, 0), (128, 1, 1), (256, -1, 0), (256, -1, 0), (256, 2, 1), (512, -1, 0), (512, -1, 0), (512, 3, 1),
+              (512, -1, 0), (512, -1, 0), (512, 4, 0))
+    shapes, off, hh, ww = i2v_native.NativeVGG.tap_shapes(n, h, w), 0, h, w
+    for l, (cout, tap, pool) in enumerate(layers):
+        assert (lay[l].h, lay[l].w, lay[l].cout, lay[l].tap, lay[l].offset) == (hh, ww, cout, tap, off), l
+        if tap >= 0:
+            assert shapes[tap] == (n, hh, ww, cout)
+        else:
+            off += (n * hh * ww * cout * 4 + 255) // 256 * 256
+        if pool:
+            hh, ww = hh // 2, ww // 2
+    assert i2v_native.lib().i2v_vgg_saved_layout(n, 15, w, lay) != 0 and i2v_native.lib().i2v_vgg_saved_layout(0, h, w, lay) != 0
+    assert i2v_native.lib().i2v_vgg_saved_layout(n, h, w, None) != 0
 
 
 def test_holders_keep_the_reference_keys_and_load_files(tmp_path):

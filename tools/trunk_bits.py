@@ -1,7 +1,9 @@
-"""Digests of the I3D and Inception-v3 trunks for A/B runs of changes to their conv kernel or its host code: prints one sha256 per case
-over the output bytes of every conv-unit and Mixed case of tests/i3d_units_common.py (both I3D variants) and of tests/fid_common.py, and
-of one whole trunk each at its smallest legal input (2 clips of 9 x 32 x 32 frames through the Kinetics I3D, 2 images of 75 x 75 through
-Inception).  Two builds of the library compute the same function iff the two outputs are equal, e.g.
+"""Digests of the I3D, Inception-v3 and VGG-16 trunks for A/B runs of changes to their conv kernels or their host code: prints one sha256
+per case over the output bytes of every conv-unit and Mixed case of tests/i3d_units_common.py (both I3D variants) and of
+tests/fid_common.py, and of one whole trunk each at its smallest legal input (2 clips of 9 x 32 x 32 frames through the Kinetics I3D, 2
+images of 75 x 75 through Inception).  ``vgg`` as the only argument prints the VGG-16 / LPIPS group alone: every conv and dgrad unit case
+of tests/vgg_common.py and tests/lpips_grad_common.py, the taps (and the saved buffer) at three shapes, LPIPS and its frame gradient,
+one pair reduction and the three size queries.  Two builds of the library compute the same function iff the two outputs are equal, e.g.
 
     python tools/trunk_bits.py > a.txt;  I2V_LIB_PATH=<other build, relative to the repository> python tools/trunk_bits.py > b.txt
 
@@ -20,6 +22,8 @@ import torch   # noqa: E402
 import fid_common as fc          # noqa: E402
 import i2v_native                # noqa: E402
 import i3d_units_common as uc    # noqa: E402
+import lpips_grad_common as lg   # noqa: E402
+import vgg_common as vc          # noqa: E402
 
 SENTINEL = -777.25
 SEED_FID = 91
@@ -81,7 +85,56 @@ def inception_cases():
     print(f"inception trunk 2x75x75 {sha(*net.features(i2v_native.inception_input_stage(x, resize=False), (0, 1, 2, 3)))}", flush=True)
 
 
+def vgg_cases():
+    from stage2_cINN.AE.modules.LPIPS import LPIPS
+    cl = lambda t: None if t is None else vc.to_cl(t).cuda()  # noqa: E731
+    for case in vc.conv_cases():
+        x, (w, b) = vc.conv_input(case), vc.conv_params(case)
+        print(f"vgg conv {case['id']} {sha(i2v_native.vgg_conv_unit(vc.to_cl(x, pad4=case['cin'] == 3).cuda(), w, b))}", flush=True)
+    for case in lg.dgrad_cases():
+        g, w, add, y, _ = lg.dgrad_inputs(case)
+        print(f"vgg dgrad {case['id']} {sha(i2v_native.vgg_dgrad_unit(cl(g), w, cl(add), cl(y)))}", flush=True)
+    for case in lg.first_cases():
+        g, w, _, _, _ = lg.dgrad_inputs(case)
+        print(f"vgg dgrad {case['id']} {sha(i2v_native.vgg_dgrad_unit(cl(g), w, frames=bool(case['frames'])))}", flush=True)
+    sd = {k: torch.from_numpy(v) for k, v in vc.vgg_state_dict(lg.SEED_W).items()}
+    sd.update({k: torch.from_numpy(v) for k, v in vc.lin_state_dict(lg.SEED_LIN).items()})
+    net = i2v_native.NativeVGG()
+    net.load(sd)
+    shapes = ((3, 16, 16), (2, 35, 29), (1, 24, 40))
+    for i, (n, h, w) in enumerate(shapes):
+        x = vc.to_cl(vc.randn(8600 + i, (n, 3, h, w)), pad4=True).cuda()
+        print(f"vgg taps {n}x{h}x{w} {sha(*net.features(x))}", flush=True)
+        taps, saved = net.features(x, save=True)
+        print(f"vgg taps saved {n}x{h}x{w} {sha(*taps)} buffer {sha(saved.buf)}", flush=True)
+        print(f"vgg sizes {n}x{h}x{w} workspace {i2v_native.lib().i2v_vgg_workspace_bytes(net._h, n, h, w)} saved {net.saved_bytes(n, h, w)} "
+              f"backward {i2v_native.lib().i2v_vgg_backward_workspace_bytes(net._h, n, h, w)}", flush=True)
+    m = LPIPS()
+    m.load_state_dict(_lpips_module_state(sd), strict=False)
+    m = m.cuda().eval()
+    x0 = torch.from_numpy(vc.clips(8700, 2, 1, 35, 29))[:, 0].contiguous().cuda()
+    x1 = torch.from_numpy(vc.clips(8701, 2, 1, 35, 29))[:, 0].contiguous().cuda().requires_grad_(True)
+    with torch.enable_grad():
+        val = m(x0, x1)
+        val.mean().backward()
+    print(f"vgg lpips 2x35x29 values {sha(val.detach())} frame gradient {sha(x1.grad)}", flush=True)
+    acc = torch.zeros(2, dtype=torch.float64, device="cuda")
+    i2v_native.vgg_pairdiff_update(vc.randn(8800, (5, 3, 7, 64)).cuda(), acc)
+    print(f"vgg pairdiff R5 {sha(acc)}", flush=True)
+
+
+def _lpips_module_state(sd):
+    """The native state_dict under the keys of the LPIPS holder module (its trunk's parameters live under ``net.``)."""
+    out = {"net." + hk: sd[k] for hk, k in zip(vc.holder_keys(), vc.vgg_state_dict(lg.SEED_W))}
+    out.update({k: v for k, v in sd.items() if k.startswith("lin")})
+    return out
+
+
 if __name__ == "__main__":
     torch.set_grad_enabled(False)
-    i3d_cases()
-    inception_cases()
+    if sys.argv[1:] == ["vgg"]:
+        vgg_cases()
+    else:
+        i3d_cases()
+        inception_cases()
+        vgg_cases()
