@@ -172,6 +172,28 @@ struct FlatConv {
         if (int rc = w.upload(p.w.data(), p.w.size() * 4)) return rc;
         return ss.upload(p.ss.data(), p.ss.size() * 4);
     }
+    // One unit of a state_dict: the weight [cout][cin][kt kh kw] under `wkey` (kt = 0: [cout][cin][kh][kw]) and its epilogue -- the
+    // eval-mode BatchNorm under <bn>.weight / .bias / .running_mean / .running_var with `eps` when `bn` is given, else the bias
+    // under `bias` when that is given, else the identity -- packed and uploaded
+    int load(const StateDict& sd, const std::string& wkey, int cin, int cout, int kt_, int kh_, int kw_, const std::string& bn, double eps,
+             const std::string& bias = "") {
+        const float* wsrc = sd.f32(wkey, (int64_t)cout * cin * (kt_ > 0 ? kt_ : 1) * kh_ * kw_);
+        if (!wsrc) return I2V_E_MISSING;
+        FlatConvPacked p = flatconv_pack(wsrc, cin, cout, kt_, kh_, kw_);
+        if (!bn.empty()) {
+            const float* g = sd.f32(bn + ".weight", cout);
+            const float* b = sd.f32(bn + ".bias", cout);
+            const float* m = sd.f32(bn + ".running_mean", cout);
+            const float* v = sd.f32(bn + ".running_var", cout);
+            if (!g || !b || !m || !v) return I2V_E_MISSING;
+            flatconv_fold_bn(p, g, b, m, v, eps);
+        } else if (!bias.empty()) {
+            const float* b = sd.f32(bias, cout);
+            if (!b) return I2V_E_MISSING;
+            flatconv_bias(p, b);
+        }
+        return upload(p);
+    }
 };
 
 // input and output map of one launch with the stride and the padding in FRONT per dimension; a 2-D unit: Ti = To = 1, sT = 1, pT = 0

@@ -78,6 +78,13 @@ struct Entry {
 #define I2V_REQUIRE_WORKSPACE(have, need, what) \
     I2V_REQUIRE((have) >= (need), I2V_E_WORKSPACE, "%s: workspace %zu < required %zu", what, (size_t)(have), (size_t)(need))
 
+// A launch plan built on the host (i2v_trunk_plan.h) that refused its shape: its message and code become the call's
+template <class Plan>
+int plan_refusal(const Plan& p) {
+    set_error("%s", p.error);
+    return p.status;
+}
+
 // Carves a workspace into slots: every take returns the slot's byte offset, and the next slot starts 256-byte aligned behind it
 // (a zero-sized slot takes no room and shares its offset with the next one).
 struct Carver {

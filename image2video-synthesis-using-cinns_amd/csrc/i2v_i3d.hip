@@ -22,11 +22,10 @@
 
 #include "i2v_flatconv.h"
 #include "i2v_handle.h"
+#include "i2v_trunk_plan.h"
 
 namespace i2v {
 namespace {
-
-constexpr int I3D_SIDE = 224;
 
 // FVD_logging.preprocess fused with the layout change: frames [N = B T][3][Hi][Wi] -> channels-last [N][224][224][4] (channel 3
 // zero), bilinear with align_corners=True in the arithmetic of torch's upsample_bilinear2d, then (x + 1) / 2 when `denorm`.
@@ -172,54 +171,13 @@ __global__ __launch_bounds__(256) void diversity_kernel(const float* __restrict_
     }
 }
 
-// "TF SAME" padding of one dimension (get_padding_shape): `mod` = input size % stride for the TIME dimension of a strided unit
-// (Kinetics), for every dimension of a strided unit (dynamic-texture variant: Unit3D.compute_pad, MaxPool3dSamePadding.compute_pad)
-void same_pad(int k, int s, int mod, int* front, int* back) {
-    const int along = std::max(mod ? k - mod : k - s, 0);
-    *front = along / 2;
-    *back = along - along / 2;
-}
-// MaxPool3d(ceil_mode=True, padding 0) on an extent e
-int pool_out(int e, int k, int s) {
-    int o = (e - k + s - 1) / s + 1;
-    if ((o - 1) * s >= e) --o;
-    return o;
-}
-
 // One conv unit (Unit3Dpy / ID3.Unit3D) of the state_dict: [cout][cin][k][k][k] under <name>.conv3d.weight, and its epilogue: the eval-mode
-// BatchNorm3d under <name>.<bnkey> (eps 1e-3 under "batch3d", 1e-5 under "bn"), else the conv bias, else nothing
+// BatchNorm3d under <name>.<bnkey> (eps 1e-3 under "batch3d", 1e-5 under "bn"), or without a bnkey the conv bias
 struct Unit : FlatConv {
-    int pack(const StateDict& sd, const std::string& name, int cin, int cout, int k, bool bn, bool bias, const char* bnkey = "batch3d",
-             double eps = 1e-3) {
-        const float* wsrc = sd.f32(name + ".conv3d.weight", (int64_t)cout * cin * k * k * k);
-        if (!wsrc) return I2V_E_MISSING;
-        FlatConvPacked p = flatconv_pack(wsrc, cin, cout, k, k, k);
-        if (bn) {
-            const std::string bk = name + "." + bnkey;
-            const float* g = sd.f32(bk + ".weight", cout);
-            const float* b = sd.f32(bk + ".bias", cout);
-            const float* m = sd.f32(bk + ".running_mean", cout);
-            const float* v = sd.f32(bk + ".running_var", cout);
-            if (!g || !b || !m || !v) return I2V_E_MISSING;
-            flatconv_fold_bn(p, g, b, m, v, eps);
-        } else if (bias) {
-            const float* b = sd.f32(name + ".conv3d.bias", cout);
-            if (!b) return I2V_E_MISSING;
-            flatconv_bias(p, b);
-        }
-        return upload(p);
+    int pack(const StateDict& sd, const std::string& name, int cin, int cout, int k, const char* bnkey, double eps) {
+        return load(sd, name + ".conv3d.weight", cin, cout, k, k, k, bnkey ? name + "." + bnkey : "", eps, name + ".conv3d.bias");
     }
 };
-
-struct MixedSpec { const char* name; int cin; int o[6]; };
-const MixedSpec MIXED[9] = {
-    {"mixed_3b", 192, {64, 96, 128, 16, 32, 32}},   {"mixed_3c", 256, {128, 128, 192, 32, 96, 64}},
-    {"mixed_4b", 480, {192, 96, 208, 16, 48, 64}},  {"mixed_4c", 512, {160, 112, 224, 24, 64, 64}},
-    {"mixed_4d", 512, {128, 128, 256, 24, 64, 64}}, {"mixed_4e", 512, {112, 144, 288, 32, 64, 64}},
-    {"mixed_4f", 528, {256, 160, 320, 32, 128, 128}}, {"mixed_5b", 832, {256, 160, 320, 32, 128, 128}},
-    {"mixed_5c", 832, {384, 192, 384, 48, 128, 128}}};
-
-struct Dims { int T, H, W; long pos() const { return (long)T * H * W; } };
 
 }  // namespace
 }  // namespace i2v
@@ -227,163 +185,94 @@ struct Dims { int T, H, W; long pos() const { return (long)T * H * W; } };
 using namespace i2v;
 
 struct i2v_i3d {
-    int num_classes = 0, in_channels = 3, device = 0;
-    int dt = 0;       // 0: Kinetics-400 network (metrics/PyTorch_FVD/I3D.py); 16 / 32: dynamic-texture network of that length (metrics/DTFVD)
-    int pool_t = 2;   // time extent of the average pool: (2, 7, 7), ID3_32: (4, 7, 7)
+    I3dVariant v{0, 2, 0};   // Kinetics-400 network (metrics/PyTorch_FVD/I3D.py) with AvgPool3d((2, 7, 7)); i2v_dti3d_create: metrics/DTFVD
+    int in_channels = 3, device = 0;
     bool loaded = false;
-    Unit stem, c2b, c2c, head;
-    Unit mixed[9][6];   // branch_0, branch_1.0, branch_1.1, branch_2.0, branch_2.1, branch_3.1
+    Unit units[I2V_I3D_UNIT_HEAD + 1];   // by I2V_I3D_UNIT_*
     StreamOrder order;
 };
 
 namespace {
 
-// SAME padding in front and output dims of a conv unit with kernel (k, k, k) and stride (s, s, s) on a [T][H][W] map: the size % stride
-// rule on time only (Kinetics), on every dimension (dynamic-texture variant)
-void unit_geom(const i2v_i3d* net, int k, int s, Dims d, int* pT, int* pH, int* pW, Dims* o) {
-    int bT, bH, bW;
-    same_pad(k, s, s > 1 ? d.T % s : 0, pT, &bT);
-    same_pad(k, s, net->dt && s > 1 ? d.H % s : 0, pH, &bH);
-    same_pad(k, s, net->dt && s > 1 ? d.W % s : 0, pW, &bW);
-    *o = Dims{(d.T + *pT + bT - k) / s + 1, (d.H + *pH + bH - k) / s + 1, (d.W + *pW + bW - k) / s + 1};
+// The launches of a plan (i2v_trunk_plan.h), in order
+int launch(const i2v_i3d* n, const TrunkPlan& p, const TrunkBufs& buf, int denorm, hipStream_t st) {
+    const int B = p.B;
+    for (const Step& s : p.steps) {
+        const float* in = buf.p[s.src];
+        float* out = buf.p[s.dst];
+        switch (s.kind) {
+        case STEP_INPUT:
+            hipLaunchKernelGGL(i3d_input_kernel, dim3(grid_for((long)B * s.out.T * I3D_SIDE * I3D_SIDE)), dim3(256), 0, st, in, out, (long)B * s.out.T,
+                               s.in.T, s.out.T, s.in.H, s.in.W, denorm);
+            break;
+        case STEP_CONV: {
+            const FlatConvMaps g{B, s.in.T, s.in.H, s.in.W, s.out.T, s.out.H, s.out.W, s.s[0], s.s[1], s.s[2], s.p[0], s.p[1], s.p[2]};
+            if (int rc = flat_conv_launch<true>("i3d conv", n->units[s.unit], in, s.inCS, s.inOff, out, s.outCS, s.outOff, g, s.relu, st)) return rc;
+            continue;
+        }
+        case STEP_I3D_POOL: {
+            const I3dPoolArgs a{in, out, B, s.in.T, s.in.H, s.in.W, s.out.T, s.out.H, s.out.W, s.C, s.k[0], s.k[1], s.k[2], s.s[0], s.s[1], s.s[2],
+                                s.p[0], s.p[1], s.p[2], s.e[0], s.e[1], s.e[2]};
+            hipLaunchKernelGGL(i3d_maxpool_kernel, dim3(grid_for((long)B * s.out.pos() * (s.C / 4))), dim3(256), 0, st, a);
+            break;
+        }
+        case STEP_AVGPOOL:
+            hipLaunchKernelGGL(i3d_avgpool_kernel, dim3(grid_for((long)B * s.out.T * s.C)), dim3(256), 0, st, in, out, B, s.in.T, s.C, s.k[0],
+                               s.chw ? 1 : 0);
+            break;
+        case STEP_TIME_MEAN:
+            hipLaunchKernelGGL(i3d_time_mean_kernel, dim3(grid_for((long)B * s.C)), dim3(256), 0, st, in, out, B, s.in.T, s.C);
+            break;
+        default:
+            I2V_REQUIRE(false, I2V_E_INVALID, "i3d: step kind %d", s.kind);
+        }
+        I2V_HIP_CHECK(hipGetLastError());
+    }
+    return I2V_OK;
 }
 
-// One walk of the network serves the workspace size (dry: no buffers, no launches) and the forward.
-struct Walk {
-    const i2v_i3d* net;
-    int B;
-    bool dry;
-    hipStream_t st;
-    size_t act_floats = 0, tmp_floats = 0;   // dry: the largest block-level tensor / branch temporary
+// plans of the sub-module entries: the caller's tensor in BUF_IN, its output in BUF_OUT
+TrunkPlan unit_plan(const i2v_i3d* n, int unit, int B, Map3 d, int in_cs, int out_cs, int out_off) {
+    TrunkPlan p(B);
+    i3d_unit(p, n->v, unit, BUF_IN, in_cs, d, BUF_OUT, out_cs, out_off, unit != I2V_I3D_UNIT_HEAD);
+    return p;
+}
+TrunkPlan mixed_plan(const i2v_i3d* n, int block, int B, Map3 d) {
+    TrunkPlan p(B);
+    i3d_mixed(p, n->v, block, BUF_IN, d, BUF_OUT);
+    p.carve<Carver>();
+    return p;
+}
+TrunkPlan pool_plan(const i2v_i3d* n, int B, int C, Map3 d, int kt, int k, int st, int s) {
+    TrunkPlan p(B);
+    i3d_pool(p, n->v, BUF_IN, BUF_OUT, C, d, kt, k, st, s);
+    return p;
+}
+TrunkPlan head_plan(const i2v_i3d* n, int B, int T, bool features) {
+    TrunkPlan p(B);
+    i3d_head(p, n->v, BUF_IN, T, features);
+    return p;
+}
 
-    int conv(const Unit& u, const float* in, int inCS, int inOff, Dims di, float* out, int outCS, int outOff, Dims dout, int sT, int s,
-             int pT, int pS, bool relu, int pW = -1) {
-        if (dry) return I2V_OK;
-        const FlatConvMaps g{B, di.T, di.H, di.W, dout.T, dout.H, dout.W, sT, s, s, pT, pS, pW < 0 ? pS : pW};
-        return flat_conv_launch<true>("i3d conv", u, in, inCS, inOff, out, outCS, outOff, g, relu, st);
-    }
+size_t trunk_bytes(const i2v_i3d* n, int batch, int t, int h, int w, bool features) {
+    if (!n || batch <= 0 || t <= 0 || h < 2 || w < 2) return 0;
+    const TrunkPlan p = i3d_plan<Carver>(n->v, batch, t, t, h, w, features);
+    return p.status ? (plan_refusal(p), 0) : p.total;   // a refused shape answers 0 and leaves its message
+}
 
-    // One conv unit at stride (s, s, s) with its own SAME padding (unit_geom); returns the output dims
-    int unit(const Unit& u, int s, const float* in, int inCS, int inOff, Dims di, float* out, int outCS, int outOff, bool relu, Dims* dout) {
-        int pT, pH, pW;
-        unit_geom(net, u.kt, s, di, &pT, &pH, &pW, dout);
-        return conv(u, in, inCS, inOff, di, out, outCS, outOff, *dout, s, s, pT, pH, relu, pW);
-    }
-
-    // MaxPool3dTFPadding(kernel (kT, k, k), stride (sT, s, s)); returns the output dims
-    int pool(const float* in, float* out, int C, Dims di, int kT, int k, int sT, int s, Dims* dout) {
-        I3dPoolArgs a{};
-        int bT, bH, bW;
-        same_pad(kT, sT, sT > 1 ? di.T % sT : 0, &a.pT, &bT);
-        same_pad(k, s, net->dt && s > 1 ? di.H % s : 0, &a.pH, &bH);
-        same_pad(k, s, net->dt && s > 1 ? di.W % s : 0, &a.pW, &bW);
-        a.eT = a.pT + di.T + bT; a.eH = a.pH + di.H + bH; a.eW = a.pW + di.W + bW;
-        dout->T = pool_out(a.eT, kT, sT); dout->H = pool_out(a.eH, k, s); dout->W = pool_out(a.eW, k, s);
-        if (dry) return I2V_OK;
-        a.in = in; a.out = out; a.B = B; a.Ti = di.T; a.Hi = di.H; a.Wi = di.W; a.To = dout->T; a.Ho = dout->H; a.Wo = dout->W; a.C = C;
-        a.kT = kT; a.kH = k; a.kW = k; a.sT = sT; a.sH = s; a.sW = s;
-        hipLaunchKernelGGL(i3d_maxpool_kernel, dim3(grid_for((long)B * dout->pos() * (C / 4))), dim3(256), 0, st, a);
-        I2V_HIP_CHECK(hipGetLastError());
-        return I2V_OK;
-    }
-
-    void need(size_t* slot, long floats) { *slot = std::max(*slot, (size_t)floats); }
-
-    static int mixed_out(int i) { return MIXED[i].o[0] + MIXED[i].o[2] + MIXED[i].o[4] + MIXED[i].o[5]; }
-
-    // Mixed block i: x [B][d][cin] -> y [B][d][Co]; tmp holds one branch temporary at a time
-    int mixed(int i, const float* x, Dims d, float* y, float* tmp) {
-        int rc;
-        const MixedSpec& s = MIXED[i];
-        const Unit* u = net->mixed[i];
-        const int C = s.cin, Co = mixed_out(i);
-        need(&act_floats, (long)B * d.pos() * Co);
-        need(&tmp_floats, (long)B * d.pos() * std::max(std::max(s.o[1], s.o[3]), C));
-        // the branches store into their channel slice of y (torch.cat((out_0, out_1, out_2, out_3), 1))
-        if ((rc = conv(u[0], x, C, 0, d, y, Co, 0, d, 1, 1, 0, 0, true))) return rc;
-        if ((rc = conv(u[1], x, C, 0, d, tmp, s.o[1], 0, d, 1, 1, 0, 0, true))) return rc;
-        if ((rc = conv(u[2], tmp, s.o[1], 0, d, y, Co, s.o[0], d, 1, 1, 1, 1, true))) return rc;
-        if ((rc = conv(u[3], x, C, 0, d, tmp, s.o[3], 0, d, 1, 1, 0, 0, true))) return rc;
-        if ((rc = conv(u[4], tmp, s.o[3], 0, d, y, Co, s.o[0] + s.o[2], d, 1, 1, 1, 1, true))) return rc;
-        Dims po;
-        if ((rc = pool(x, tmp, C, d, 3, 3, 1, 1, &po))) return rc;
-        return conv(u[5], tmp, C, 0, d, y, Co, s.o[0] + s.o[2] + s.o[4], d, 1, 1, 0, 0, true);
-    }
-
-    // AvgPool3d((pool_t, 7, 7)) on x [B][T][7][7][1024] -> pooled [B][T'][1024], conv3d_0c_1x1 -> cls [B][T'][classes], time mean -> logits;
-    // with `features` only the pool, stored as [B][1024][T'] into logits
-    int head(const float* x, int T, float* pooled, float* cls, float* logits, bool features) {
-        const int kT = net->pool_t;
-        hipLaunchKernelGGL(i3d_avgpool_kernel, dim3(grid_for((long)B * (T - kT + 1) * 1024)), dim3(256), 0, st, x, features ? logits : pooled, B,
-                           T, 1024, kT, features ? 1 : 0);
-        I2V_HIP_CHECK(hipGetLastError());
-        if (features) return I2V_OK;
-        const Dims dh{T - kT + 1, 1, 1};
-        if (int rc = conv(net->head, pooled, 1024, 0, dh, cls, net->num_classes, 0, dh, 1, 1, 0, 0, false)) return rc;   // conv3d_0c_1x1
-        hipLaunchKernelGGL(i3d_time_mean_kernel, dim3(grid_for((long)B * net->num_classes)), dim3(256), 0, st, cls, logits, B, dh.T,
-                           net->num_classes);
-        I2V_HIP_CHECK(hipGetLastError());
-        return I2V_OK;
-    }
-
-    // frames -> logits, or with `features` -> the average pool's output [B][1024][T'] in `logits` (no classifier, no time mean).
-    // T frames enter the network, frame t read from source frame t % Tin.  inp / x / y / tmp / pooled / cls: workspace buffers (null when dry)
-    int run(const float* frames, int Tin, int T, int H, int W, int denorm, float* inp, float* x, float* y, float* tmp, float* pooled, float* cls,
-            float* logits, int* t_head, bool features = false) {
-        int rc;
-        Dims d{T, I3D_SIDE, I3D_SIDE};
-        if (!dry) {
-            hipLaunchKernelGGL(i3d_input_kernel, dim3(grid_for((long)B * T * I3D_SIDE * I3D_SIDE)), dim3(256), 0, st, frames, inp, (long)B * T, Tin, T,
-                               H, W, denorm);
-            I2V_HIP_CHECK(hipGetLastError());
-        }
-        // conv3d_1a_7x7: stride 2, SAME = (2, 3) per dimension, (3, 3) in time for an odd T (and, by the dynamic-texture variant's rule, in
-        // an odd spatial dimension: none at 224)
-        Dims o;
-        if ((rc = unit(net->stem, 2, inp, 4, 0, d, x, 64, 0, true, &o))) return rc;
-        need(&act_floats, (long)B * o.pos() * 64);
-        d = o;
-        if ((rc = pool(x, y, 64, d, 1, 3, 1, 2, &o))) return rc;                              // maxPool3d_2a_3x3
-        d = o;
-        if ((rc = conv(net->c2b, y, 64, 0, d, x, 64, 0, d, 1, 1, 0, 0, true))) return rc;      // conv3d_2b_1x1
-        need(&act_floats, (long)B * d.pos() * 192);
-        if ((rc = conv(net->c2c, x, 64, 0, d, y, 192, 0, d, 1, 1, 1, 1, true))) return rc;     // conv3d_2c_3x3
-        if ((rc = pool(y, x, 192, d, 1, 3, 1, 2, &o))) return rc;                             // maxPool3d_3a_3x3
-        d = o;
-        int C = 192;
-        for (int i = 0; i < 9; ++i) {
-            if ((rc = mixed(i, x, d, y, tmp))) return rc;
-            std::swap(x, y);
-            C = mixed_out(i);
-            if (i == 1) { if ((rc = pool(x, y, C, d, 3, 3, 2, 2, &o))) return rc; d = o; std::swap(x, y); }   // maxPool3d_4a_3x3
-            if (i == 6) { if ((rc = pool(x, y, C, d, 2, 2, 2, 2, &o))) return rc; d = o; std::swap(x, y); }   // maxPool3d_5a_2x2
-        }
-        const int kT = net->pool_t;
-        I2V_REQUIRE(d.H == 7 && d.W == 7 && d.T >= kT, I2V_E_INVALID,
-                    "i3d: %d frames leave a [%d, %d, %d] map in front of AvgPool3d((%d, 7, 7)); at least %d frames are needed", T, d.T, d.H, d.W, kT,
-                    8 * (kT - 1) + 1);
-        *t_head = d.T - kT + 1;
-        if (dry) return I2V_OK;
-        return head(x, d.T, pooled, cls, logits, features);
-    }
-};
-
-struct I3dWs { size_t inp, x, y, tmp, pooled, cls, total; };
-
-int i3d_ws(const i2v_i3d* net, int B, int T, int H, int W, I3dWs* L, bool features = false, int* t_head = nullptr) {
-    Walk wk{net, B, true, nullptr};
-    int th = 0;
-    if (int rc = wk.run(nullptr, T, T, H, W, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &th, features)) return rc;
-    if (t_head) *t_head = th;
-    Carver c;
-    L->inp = c.take_floats((size_t)B * T * I3D_SIDE * I3D_SIDE * 4);
-    L->x = c.take_floats(wk.act_floats);
-    L->y = c.take_floats(wk.act_floats);
-    L->tmp = c.take_floats(wk.tmp_floats);
-    L->pooled = c.take_floats(features ? 0 : (size_t)B * th * 1024);
-    L->cls = c.take_floats(features ? 0 : (size_t)B * th * net->num_classes);
-    L->total = c.total();
-    return I2V_OK;
+// i2v_i3d_forward (t_in = t_out, logits) and i2v_i3d_features
+int trunk_forward(const char* what, bool features, i2v_i3d* n, const float* frames, int batch, int t_in, int t_out, int h, int w, int denorm,
+                  float* out, void* workspace, size_t workspace_bytes, void* stream) {
+    I2V_ENTER(sc, n, Entry::NEEDS_WEIGHTS | Entry::NULL_IS_UNLOADED, what);
+    I2V_REQUIRE(frames && out && workspace && batch > 0 && t_in > 0 && t_out > 0 && h >= 2 && w >= 2, I2V_E_INVALID, "%s: bad argument", what);
+    I2V_REQUIRE((long)batch * t_out * I3D_SIDE * I3D_SIDE * 64 < (1L << 40) && (!features || (long)batch * t_in * 3 * h * w < (1L << 40)),
+                I2V_E_INVALID, "%s: batch %d x %d frames is too large", what, batch, t_out);
+    const TrunkPlan p = i3d_plan<Carver>(n->v, batch, t_in, t_out, h, w, features);
+    if (p.status) return plan_refusal(p);
+    I2V_REQUIRE_WORKSPACE(workspace_bytes, p.total, what);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (int rco = sc.serialise(n->order, st)) return rco;
+    return launch(n, p, TrunkBufs(frames, out).carve(p, workspace), denorm ? 1 : 0, st);
 }
 
 }  // namespace
@@ -394,7 +283,7 @@ int i2v_i3d_create(int32_t num_classes, int32_t in_channels, i2v_i3d** out) {
     I2V_REQUIRE(out && num_classes > 0, I2V_E_INVALID, "i2v_i3d_create: bad argument");
     I2V_REQUIRE(in_channels == 3, I2V_E_INVALID, "i2v_i3d_create: only the rgb network (3 input channels) is built, got %d", in_channels);
     return create_handle("i2v_i3d_create", out, [&](i2v_i3d* n) {
-        n->num_classes = num_classes;
+        n->v.num_classes = num_classes;
         n->in_channels = in_channels;
         return I2V_OK;
     });
@@ -403,136 +292,69 @@ int i2v_i3d_create(int32_t num_classes, int32_t in_channels, i2v_i3d** out) {
 int i2v_dti3d_create(int32_t num_classes, int32_t length, i2v_i3d** out) {
     I2V_REQUIRE(length == 16 || length == 32, I2V_E_INVALID, "i2v_dti3d_create: the dynamic-texture I3D exists for length 16 and 32, got %d", length);
     if (int rc = i2v_i3d_create(num_classes, 3, out)) return rc;
-    (*out)->dt = length;
-    (*out)->pool_t = length == 32 ? 4 : 2;
+    (*out)->v.dt = length;
+    (*out)->v.pool_t = length == 32 ? 4 : 2;   // ID3_32: AvgPool3d((4, 7, 7))
     return I2V_OK;
 }
 
 void i2v_i3d_destroy(i2v_i3d* n) { delete n; }
 
+// Kinetics: conv3d_* / mixed_*.branch_* / conv3d_0c_1x1, BatchNorm3d under "batch3d" with eps 1e-3; ID3.InceptionI3D: Conv3d_* /
+// Mixed_*.{b0,b1a,b1b,b2a,b2b,b3b} / logits, BatchNorm3d under "bn" with eps 1e-5.  The head has a bias and no norm
+// (i2v_i3d_features never launches it).
 static int i3d_pack(i2v_i3d* n, const StateDict& sd) {
-    int rc;
-    if (n->dt) {   // ID3.InceptionI3D: Conv3d_* / Mixed_*.{b0,b1a,b1b,b2a,b2b,b3b} / logits, BatchNorm3d under "bn" with eps 1e-5
-        static const char* const BR[6] = {".b0", ".b1a", ".b1b", ".b2a", ".b2b", ".b3b"};
-        if ((rc = n->stem.pack(sd, "Conv3d_1a_7x7", n->in_channels, 64, 7, true, false, "bn", 1e-5))) return rc;
-        if ((rc = n->c2b.pack(sd, "Conv3d_2b_1x1", 64, 64, 1, true, false, "bn", 1e-5))) return rc;
-        if ((rc = n->c2c.pack(sd, "Conv3d_2c_3x3", 64, 192, 3, true, false, "bn", 1e-5))) return rc;
-        for (int i = 0; i < 9; ++i) {
-            const MixedSpec& s = MIXED[i];
-            std::string p = s.name;
-            p[0] = 'M';
-            const int cin[6] = {s.cin, s.cin, s.o[1], s.cin, s.o[3], s.cin};
-            for (int j = 0; j < 6; ++j)
-                if ((rc = n->mixed[i][j].pack(sd, p + BR[j], cin[j], s.o[j], j == 2 || j == 4 ? 3 : 1, true, false, "bn", 1e-5))) return rc;
-        }
-        return n->head.pack(sd, "logits", 1024, n->num_classes, 1, false, true);   // (i2v_i3d_features never launches it)
+    static const char* const BR[2][6] = {{".branch_0", ".branch_1.0", ".branch_1.1", ".branch_2.0", ".branch_2.1", ".branch_3.1"},
+                                         {".b0", ".b1a", ".b1b", ".b2a", ".b2b", ".b3b"}};
+    const bool dt = n->v.dt != 0;
+    for (int unit = 0; unit <= I2V_I3D_UNIT_HEAD; ++unit) {
+        I3dUnitSpec u;
+        i3d_unit_spec(n->v, unit, &u);
+        const bool head = unit == I2V_I3D_UNIT_HEAD;
+        std::string name = unit == I2V_I3D_UNIT_STEM ? "conv3d_1a_7x7" : unit == I2V_I3D_UNIT_2B ? "conv3d_2b_1x1" : unit == I2V_I3D_UNIT_2C ? "conv3d_2c_3x3"
+                           : head ? (dt ? "logits" : "conv3d_0c_1x1")
+                                  : std::string(MIXED[(unit - I2V_I3D_UNIT_MIXED) / 6].name) + BR[dt][(unit - I2V_I3D_UNIT_MIXED) % 6];
+        if (dt && !head) name[0] = (char)(name[0] - 'a' + 'A');
+        if (int rc = n->units[unit].pack(sd, name, u.cin, u.cout, u.k, head ? nullptr : dt ? "bn" : "batch3d", dt ? 1e-5 : 1e-3)) return rc;
     }
-    if ((rc = n->stem.pack(sd, "conv3d_1a_7x7", n->in_channels, 64, 7, true, false))) return rc;
-    if ((rc = n->c2b.pack(sd, "conv3d_2b_1x1", 64, 64, 1, true, false))) return rc;
-    if ((rc = n->c2c.pack(sd, "conv3d_2c_3x3", 64, 192, 3, true, false))) return rc;
-    for (int i = 0; i < 9; ++i) {
-        const MixedSpec& s = MIXED[i];
-        const std::string p = std::string(s.name) + ".";
-        Unit* u = n->mixed[i];
-        if ((rc = u[0].pack(sd, p + "branch_0", s.cin, s.o[0], 1, true, false))) return rc;
-        if ((rc = u[1].pack(sd, p + "branch_1.0", s.cin, s.o[1], 1, true, false))) return rc;
-        if ((rc = u[2].pack(sd, p + "branch_1.1", s.o[1], s.o[2], 3, true, false))) return rc;
-        if ((rc = u[3].pack(sd, p + "branch_2.0", s.cin, s.o[3], 1, true, false))) return rc;
-        if ((rc = u[4].pack(sd, p + "branch_2.1", s.o[3], s.o[4], 3, true, false))) return rc;
-        if ((rc = u[5].pack(sd, p + "branch_3.1", s.cin, s.o[5], 1, true, false))) return rc;
-    }
-    return n->head.pack(sd, "conv3d_0c_1x1", 1024, n->num_classes, 1, false, true);
+    return I2V_OK;
 }
 
 int i2v_i3d_load(i2v_i3d* n, const i2v_tensor* tensors, int32_t n_tensors) {
     return load_handle("i2v_i3d_load", n, tensors, n_tensors, i3d_pack);
 }
 
-size_t i2v_i3d_workspace_bytes(const i2v_i3d* n, int32_t batch, int32_t t, int32_t h, int32_t w) {
-    if (!n || batch <= 0 || t <= 0 || h < 2 || w < 2) return 0;
-    I3dWs L;
-    if (i3d_ws(n, batch, t, h, w, &L)) return 0;
-    return L.total;
-}
+size_t i2v_i3d_workspace_bytes(const i2v_i3d* n, int32_t batch, int32_t t, int32_t h, int32_t w) { return trunk_bytes(n, batch, t, h, w, false); }
 
 int i2v_i3d_forward(i2v_i3d* n, const float* frames, int32_t batch, int32_t t, int32_t h, int32_t w, int32_t denorm, float* logits,
                     void* workspace, size_t workspace_bytes, void* stream) {
-    I2V_ENTER(sc, n, Entry::NEEDS_WEIGHTS | Entry::NULL_IS_UNLOADED, "i2v_i3d_forward");
-    I2V_REQUIRE(frames && logits && workspace && batch > 0 && t > 0 && h >= 2 && w >= 2, I2V_E_INVALID, "i2v_i3d_forward: bad argument");
-    I2V_REQUIRE((long)batch * t * I3D_SIDE * I3D_SIDE * 64 < (1L << 40), I2V_E_INVALID, "i2v_i3d_forward: batch %d x %d frames is too large", batch, t);
-    I3dWs L;
-    if (int rc = i3d_ws(n, batch, t, h, w, &L)) return rc;
-    I2V_REQUIRE_WORKSPACE(workspace_bytes, L.total, "i2v_i3d_forward");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (int rco = sc.serialise(n->order, st)) return rco;
-    void* const ws = workspace;
-    Walk wk{n, batch, false, st};
-    int th = 0;
-    return wk.run(frames, t, t, h, w, denorm ? 1 : 0, Carver::at(ws, L.inp), Carver::at(ws, L.x), Carver::at(ws, L.y), Carver::at(ws, L.tmp),
-                  Carver::at(ws, L.pooled), Carver::at(ws, L.cls), logits, &th);
+    return trunk_forward("i2v_i3d_forward", false, n, frames, batch, t, t, h, w, denorm, logits, workspace, workspace_bytes, stream);
 }
 
 size_t i2v_i3d_features_workspace_bytes(const i2v_i3d* n, int32_t batch, int32_t t_out, int32_t h, int32_t w) {
-    if (!n || batch <= 0 || t_out <= 0 || h < 2 || w < 2) return 0;
-    I3dWs L;
-    if (i3d_ws(n, batch, t_out, h, w, &L, true)) return 0;
-    return L.total;
+    return trunk_bytes(n, batch, t_out, h, w, true);
 }
 
 int32_t i2v_i3d_feature_steps(const i2v_i3d* n, int32_t t_out) {
     if (!n || t_out <= 0) return 0;
-    I3dWs L;
-    int th = 0;
-    if (i3d_ws(n, 1, t_out, I3D_SIDE, I3D_SIDE, &L, true, &th)) return 0;
-    return th;
+    const TrunkPlan p = i3d_plan<Carver>(n->v, 1, t_out, t_out, I3D_SIDE, I3D_SIDE, true);
+    return p.status ? (plan_refusal(p), 0) : p.t_head;
 }
 
 int i2v_i3d_features(i2v_i3d* n, const float* frames, int32_t batch, int32_t t_in, int32_t t_out, int32_t h, int32_t w, int32_t denorm,
                      float* feats, void* workspace, size_t workspace_bytes, void* stream) {
-    I2V_ENTER(sc, n, Entry::NEEDS_WEIGHTS | Entry::NULL_IS_UNLOADED, "i2v_i3d_features");
-    I2V_REQUIRE(frames && feats && workspace && batch > 0 && t_in > 0 && t_out > 0 && h >= 2 && w >= 2, I2V_E_INVALID,
-                "i2v_i3d_features: bad argument");
-    I2V_REQUIRE((long)batch * t_out * I3D_SIDE * I3D_SIDE * 64 < (1L << 40) && (long)batch * t_in * 3 * h * w < (1L << 40), I2V_E_INVALID,
-                "i2v_i3d_features: batch %d x %d frames is too large", batch, t_out);
-    I3dWs L;
-    if (int rc = i3d_ws(n, batch, t_out, h, w, &L, true)) return rc;
-    I2V_REQUIRE_WORKSPACE(workspace_bytes, L.total, "i2v_i3d_features");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (int rco = sc.serialise(n->order, st)) return rco;
-    void* const ws = workspace;
-    Walk wk{n, batch, false, st};
-    int th = 0;
-    return wk.run(frames, t_in, t_out, h, w, denorm ? 1 : 0, Carver::at(ws, L.inp), Carver::at(ws, L.x), Carver::at(ws, L.y), Carver::at(ws, L.tmp),
-                  nullptr, nullptr, feats, &th, true);
+    return trunk_forward("i2v_i3d_features", true, n, frames, batch, t_in, t_out, h, w, denorm, feats, workspace, workspace_bytes, stream);
 }
 
 // ---- sub-modules of a loaded handle, individually callable on channels-last tensors (for tests and inspection)
 
-namespace {
-// unit index -> the unit and its stride; null for an unknown index
-const Unit* i3d_unit(const i2v_i3d* n, int unit, int* stride) {
-    *stride = unit == I2V_I3D_UNIT_STEM ? 2 : 1;
-    if (unit == I2V_I3D_UNIT_STEM) return &n->stem;
-    if (unit == I2V_I3D_UNIT_2B) return &n->c2b;
-    if (unit == I2V_I3D_UNIT_2C) return &n->c2c;
-    if (unit == I2V_I3D_UNIT_HEAD) return &n->head;
-    if (unit >= I2V_I3D_UNIT_MIXED && unit < I2V_I3D_UNIT_MIXED + 54) return &n->mixed[(unit - I2V_I3D_UNIT_MIXED) / 6][(unit - I2V_I3D_UNIT_MIXED) % 6];
-    return nullptr;
-}
-constexpr long I3D_SUB_MAX = 1L << 31;   // floats per tensor of a sub-module call
-}  // namespace
-
 int i2v_i3d_unit_shape(const i2v_i3d* n, int32_t unit, int32_t t, int32_t h, int32_t w, int32_t* cin, int32_t* cout, int32_t* out_dims) {
     I2V_REQUIRE(n, I2V_E_INVALID, "i2v_i3d_unit_shape: null handle");
     I2V_REQUIRE(n->loaded, I2V_E_STATE, "i2v_i3d_unit_shape: weights not loaded");
-    int s;
-    const Unit* u = i3d_unit(n, unit, &s);
-    I2V_REQUIRE(u && t > 0 && h > 0 && w > 0, I2V_E_INVALID, "i2v_i3d_unit_shape: unit %d on a [%d, %d, %d] map", unit, t, h, w);
-    int pT, pH, pW;
-    Dims o;
-    unit_geom(n, u->kt, s, Dims{t, h, w}, &pT, &pH, &pW, &o);
-    if (cin) *cin = 4 * u->C4;
-    if (cout) *cout = u->Cout;
+    const bool known = unit >= 0 && unit <= I2V_I3D_UNIT_HEAD;
+    I2V_REQUIRE(known && t > 0 && h > 0 && w > 0, I2V_E_INVALID, "i2v_i3d_unit_shape: unit %d on a [%d, %d, %d] map", unit, t, h, w);
+    const Map3 o = unit_plan(n, unit, 1, Map3{t, h, w}, 0, 0, 0).out;
+    if (cin) *cin = 4 * n->units[unit].C4;
+    if (cout) *cout = n->units[unit].Cout;
     if (out_dims) { out_dims[0] = o.T; out_dims[1] = o.H; out_dims[2] = o.W; }
     return I2V_OK;
 }
@@ -540,30 +362,25 @@ int i2v_i3d_unit_shape(const i2v_i3d* n, int32_t unit, int32_t t, int32_t h, int
 int i2v_i3d_unit_forward(i2v_i3d* n, int32_t unit, const float* x, int32_t batch, int32_t t, int32_t h, int32_t w, int32_t in_cs, float* out,
                          int32_t out_cs, int32_t out_off, size_t out_floats, void* stream) {
     I2V_ENTER(sc, n, Entry::NEEDS_WEIGHTS, "i2v_i3d_unit_forward");
-    int s;
-    const Unit* u = i3d_unit(n, unit, &s);
-    I2V_REQUIRE(u, I2V_E_INVALID, "i2v_i3d_unit_forward: unknown unit %d", unit);
+    I2V_REQUIRE(unit >= 0 && unit <= I2V_I3D_UNIT_HEAD, I2V_E_INVALID, "i2v_i3d_unit_forward: unknown unit %d", unit);
+    const Unit* u = &n->units[unit];
     I2V_REQUIRE(x && out && batch > 0 && t > 0 && h > 0 && w > 0, I2V_E_INVALID, "i2v_i3d_unit_forward: bad argument");
     I2V_REQUIRE(in_cs > 0 && in_cs % 4 == 0 && in_cs >= 4 * u->C4 && out_cs > 0 && out_off >= 0 && out_off + u->Cout <= out_cs, I2V_E_INVALID,
                 "i2v_i3d_unit_forward: channels [0, %d) of %d -> [%d, +%d) of %d do not fit", 4 * u->C4, in_cs, out_off, u->Cout, out_cs);
-    int pT, pH, pW;
-    Dims o;
-    unit_geom(n, u->kt, s, Dims{t, h, w}, &pT, &pH, &pW, &o);
-    I2V_REQUIRE((long)batch * t * h * w * in_cs < I3D_SUB_MAX && (long)batch * o.pos() * out_cs < I3D_SUB_MAX, I2V_E_INVALID,
+    const TrunkPlan p = unit_plan(n, unit, batch, Map3{t, h, w}, in_cs, out_cs, out_off);
+    const Map3 o = p.out;
+    I2V_REQUIRE((long)batch * t * h * w * in_cs < TRUNK_SUB_MAX && (long)batch * o.pos() * out_cs < TRUNK_SUB_MAX, I2V_E_INVALID,
                 "i2v_i3d_unit_forward: batch %d x [%d, %d, %d] is too large", batch, t, h, w);
     I2V_REQUIRE(out_floats >= (size_t)batch * o.pos() * out_cs, I2V_E_WORKSPACE, "i2v_i3d_unit_forward: output of %zu floats < required %zu",
                 out_floats, (size_t)batch * o.pos() * out_cs);
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (int rco = sc.serialise(n->order, st)) return rco;
-    Walk wk{n, batch, false, st};
-    return wk.unit(*u, s, x, in_cs, 0, Dims{t, h, w}, out, out_cs, out_off, unit != I2V_I3D_UNIT_HEAD, &o);
+    return launch(n, p, TrunkBufs(x, out), 0, st);
 }
 
 size_t i2v_i3d_mixed_workspace_bytes(const i2v_i3d* n, int32_t block, int32_t batch, int32_t t, int32_t h, int32_t w) {
     if (!n || block < 0 || block >= 9 || batch <= 0 || t <= 0 || h <= 0 || w <= 0) return 0;
-    Walk wk{n, batch, true, nullptr};
-    if (wk.mixed(block, nullptr, Dims{t, h, w}, nullptr, nullptr)) return 0;
-    return align_up(wk.tmp_floats * 4, 256);
+    return mixed_plan(n, block, batch, Map3{t, h, w}).total;
 }
 
 int i2v_i3d_mixed_forward(i2v_i3d* n, int32_t block, const float* x, int32_t batch, int32_t t, int32_t h, int32_t w, float* out, void* workspace,
@@ -571,21 +388,18 @@ int i2v_i3d_mixed_forward(i2v_i3d* n, int32_t block, const float* x, int32_t bat
     I2V_ENTER(sc, n, Entry::NEEDS_WEIGHTS, "i2v_i3d_mixed_forward");
     I2V_REQUIRE(block >= 0 && block < 9, I2V_E_INVALID, "i2v_i3d_mixed_forward: unknown block %d", block);
     I2V_REQUIRE(x && out && workspace && batch > 0 && t > 0 && h > 0 && w > 0, I2V_E_INVALID, "i2v_i3d_mixed_forward: bad argument");
-    I2V_REQUIRE((long)batch * t * h * w * 1024 < I3D_SUB_MAX, I2V_E_INVALID, "i2v_i3d_mixed_forward: batch %d x [%d, %d, %d] is too large", batch, t, h,
+    I2V_REQUIRE((long)batch * t * h * w * 1024 < TRUNK_SUB_MAX, I2V_E_INVALID, "i2v_i3d_mixed_forward: batch %d x [%d, %d, %d] is too large", batch, t, h,
                 w);
-    const size_t need = i2v_i3d_mixed_workspace_bytes(n, block, batch, t, h, w);
-    I2V_REQUIRE_WORKSPACE(workspace_bytes, need, "i2v_i3d_mixed_forward");
+    const TrunkPlan p = mixed_plan(n, block, batch, Map3{t, h, w});
+    I2V_REQUIRE_WORKSPACE(workspace_bytes, p.total, "i2v_i3d_mixed_forward");
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (int rco = sc.serialise(n->order, st)) return rco;
-    Walk wk{n, batch, false, st};
-    return wk.mixed(block, x, Dims{t, h, w}, out, static_cast<float*>(workspace));
+    return launch(n, p, TrunkBufs(x, out).carve(p, workspace), 0, st);
 }
 
 int i2v_i3d_maxpool_shape(const i2v_i3d* n, int32_t kt, int32_t k, int32_t st, int32_t s, int32_t t, int32_t h, int32_t w, int32_t* out_dims) {
     I2V_REQUIRE(n && out_dims && kt > 0 && k > 0 && st > 0 && s > 0 && t > 0 && h > 0 && w > 0, I2V_E_INVALID, "i2v_i3d_maxpool_shape: bad argument");
-    Walk wk{n, 1, true, nullptr};
-    Dims o;
-    if (int rc = wk.pool(nullptr, nullptr, 4, Dims{t, h, w}, kt, k, st, s, &o)) return rc;
+    const Map3 o = pool_plan(n, 1, 4, Map3{t, h, w}, kt, k, st, s).out;
     out_dims[0] = o.T; out_dims[1] = o.H; out_dims[2] = o.W;
     return I2V_OK;
 }
@@ -596,37 +410,38 @@ int i2v_i3d_maxpool_forward(i2v_i3d* n, const float* x, int32_t batch, int32_t t
     I2V_REQUIRE(x && out && batch > 0 && t > 0 && h > 0 && w > 0 && kt > 0 && k > 0 && st > 0 && s > 0, I2V_E_INVALID,
                 "i2v_i3d_maxpool_forward: bad argument");
     I2V_REQUIRE(c > 0 && c % 4 == 0, I2V_E_INVALID, "i2v_i3d_maxpool_forward: %d channels (a multiple of 4 is needed)", c);
-    int od[3];
-    if (int rc = i2v_i3d_maxpool_shape(n, kt, k, st, s, t, h, w, od)) return rc;
-    I2V_REQUIRE(od[0] > 0 && od[1] > 0 && od[2] > 0 && (long)batch * t * h * w * c < I3D_SUB_MAX && (long)batch * od[0] * od[1] * od[2] * c < I3D_SUB_MAX,
+    const TrunkPlan p = pool_plan(n, batch, c, Map3{t, h, w}, kt, k, st, s);
+    const Map3 o = p.out;
+    I2V_REQUIRE(o.T > 0 && o.H > 0 && o.W > 0 && (long)batch * t * h * w * c < TRUNK_SUB_MAX && (long)batch * o.pos() * c < TRUNK_SUB_MAX,
                 I2V_E_INVALID, "i2v_i3d_maxpool_forward: batch %d x [%d, %d, %d] x %d", batch, t, h, w, c);
-    const size_t need = (size_t)batch * od[0] * od[1] * od[2] * c;
+    const size_t need = (size_t)batch * o.pos() * c;
     I2V_REQUIRE(out_floats >= need, I2V_E_WORKSPACE, "i2v_i3d_maxpool_forward: output of %zu floats < required %zu", out_floats, need);
     hipStream_t hs = static_cast<hipStream_t>(stream);
     if (int rco = sc.serialise(n->order, hs)) return rco;
-    Walk wk{n, batch, false, hs};
-    Dims o;
-    return wk.pool(x, out, c, Dims{t, h, w}, kt, k, st, s, &o);
+    return launch(n, p, TrunkBufs(x, out), 0, hs);
 }
 
+// the head's workspace is its I3D_CLS slot; the caller brings I3D_POOLED
 size_t i2v_i3d_head_workspace_bytes(const i2v_i3d* n, int32_t batch, int32_t t) {
-    if (!n || batch <= 0 || t < n->pool_t) return 0;
-    return align_up((size_t)batch * (t - n->pool_t + 1) * n->num_classes * 4, 256);
+    if (!n || batch <= 0 || t < n->v.pool_t) return 0;
+    return align_up(head_plan(n, batch, t, false).floats[I3D_CLS] * 4, 256);
 }
 
 int i2v_i3d_head_forward(i2v_i3d* n, const float* x, int32_t batch, int32_t t, float* pooled, float* feats, float* logits, void* workspace,
                          size_t workspace_bytes, void* stream) {
     I2V_ENTER(sc, n, Entry::NEEDS_WEIGHTS, "i2v_i3d_head_forward");
     I2V_REQUIRE(x && pooled && feats && logits && workspace && batch > 0, I2V_E_INVALID, "i2v_i3d_head_forward: bad argument");
-    I2V_REQUIRE(t >= n->pool_t && (long)batch * t * 49 * 1024 < I3D_SUB_MAX, I2V_E_INVALID,
-                "i2v_i3d_head_forward: %d time steps in front of AvgPool3d((%d, 7, 7)), batch %d", t, n->pool_t, batch);
-    const size_t need = i2v_i3d_head_workspace_bytes(n, batch, t);
-    I2V_REQUIRE_WORKSPACE(workspace_bytes, need, "i2v_i3d_head_forward");
+    I2V_REQUIRE(t >= n->v.pool_t && (long)batch * t * 49 * 1024 < TRUNK_SUB_MAX, I2V_E_INVALID,
+                "i2v_i3d_head_forward: %d time steps in front of AvgPool3d((%d, 7, 7)), batch %d", t, n->v.pool_t, batch);
+    const TrunkPlan p = head_plan(n, batch, t, false);
+    I2V_REQUIRE_WORKSPACE(workspace_bytes, align_up(p.floats[I3D_CLS] * 4, 256), "i2v_i3d_head_forward");
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (int rco = sc.serialise(n->order, st)) return rco;
-    Walk wk{n, batch, false, st};
-    if (int rc = wk.head(x, t, nullptr, nullptr, feats, true)) return rc;
-    return wk.head(x, t, pooled, static_cast<float*>(workspace), logits, false);
+    if (int rc = launch(n, head_plan(n, batch, t, true), TrunkBufs(x, feats), 0, st)) return rc;
+    TrunkBufs buf(x, logits);
+    buf.p[I3D_POOLED] = pooled;
+    buf.p[I3D_CLS] = static_cast<float*>(workspace);
+    return launch(n, p, buf, 0, st);
 }
 
 int i2v_i3d_input_stage(const float* frames, int32_t n_frames, int32_t h, int32_t w, int32_t denorm, float* out, void* stream) {

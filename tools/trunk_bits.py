@@ -1,7 +1,7 @@
 """Digests of the I3D, Inception-v3 and VGG-16 trunks for A/B runs of changes to their conv kernels or their host code: prints one sha256
 per case over the output bytes of every conv-unit and Mixed case of tests/i3d_units_common.py (both I3D variants) and of
-tests/fid_common.py, and of one whole trunk each at its smallest legal input (2 clips of 9 x 32 x 32 frames through the Kinetics I3D, 2
-images of 75 x 75 through Inception).  ``vgg`` as the only argument prints the VGG-16 / LPIPS group alone: every conv and dgrad unit case
+tests/fid_common.py, and of one whole trunk each at its smallest legal input (2 clips of 9 x 32 x 32 frames through the Kinetics I3D and,
+repeated to 16 and 32 frames, through the two dynamic-texture I3Ds; 2 images of 75 x 75 through Inception) with the trunks' size queries.  ``vgg`` as the only argument prints the VGG-16 / LPIPS group alone: every conv and dgrad unit case
 of tests/vgg_common.py and tests/lpips_grad_common.py, the taps (and the saved buffer) at three shapes, LPIPS and its frame gradient,
 one pair reduction and the three size queries.  Two builds of the library compute the same function iff the two outputs are equal, e.g.
 
@@ -59,6 +59,15 @@ def i3d_cases():
         print(f"i3d mixed {case['id']} {sha(nets[case['variant']].mixed_forward(i, cl5(x)))}", flush=True)
     frames = torch.from_numpy(fc.clips(15001, 2, 9, 32, 32)).cuda().contiguous()
     print(f"i3d trunk kin 2x9x32x32 {sha(nets['kin'].forward(frames, True))}", flush=True)
+    L = i2v_native.lib()
+    print(f"i3d sizes kin 2x9x32x32 workspace {L.i2v_i3d_workspace_bytes(nets['kin']._h, 2, 9, 32, 32)} features "
+          f"{L.i2v_i3d_features_workspace_bytes(nets['kin']._h, 2, 9, 32, 32)} steps {L.i2v_i3d_feature_steps(nets['kin']._h, 9)}", flush=True)
+    nets[32] = i2v_native.NativeI3D(uc.CLASSES["dt"], dt_length=32)
+    nets[32].load(uc.state_dict("dt"))
+    for length, n in ((16, nets["dt"]), (32, nets[32])):   # the dynamic-texture trunks: 9 source frames repeated to the network's length
+        print(f"i3d trunk dt{length} 2x9x32x32 t_out {length} {sha(n.features(frames, True, length))}", flush=True)
+        print(f"i3d sizes dt{length} 2x{length}x32x32 features {L.i2v_i3d_features_workspace_bytes(n._h, 2, length, 32, 32)} steps "
+              f"{L.i2v_i3d_feature_steps(n._h, length)}", flush=True)
 
 
 def inception_cases():
@@ -83,6 +92,8 @@ def inception_cases():
         print(f"inception mixed {block} {sha(net.mixed(bi, fc.to_cl(x).cuda()))}", flush=True)
     x = torch.from_numpy(fc.clips(14075, 2, 1, 75, 75))[:, 0].contiguous().cuda()
     print(f"inception trunk 2x75x75 {sha(*net.features(i2v_native.inception_input_stage(x, resize=False), (0, 1, 2, 3)))}", flush=True)
+    print(f"inception sizes 2x75x75 workspace {[i2v_native.lib().i2v_inception_workspace_bytes(net._h, 2, 75, 75, b) for b in range(4)]} blocks "
+          f"{[net.block_shape(2, 75, 75, b) for b in range(4)]}", flush=True)
 
 
 def vgg_cases():
