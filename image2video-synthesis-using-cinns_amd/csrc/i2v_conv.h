@@ -180,7 +180,7 @@ int stats_forward(const float* x, double* sums, int B, long P, int C, hipStream_
 // zl: optional ADAIN source instead, gamma = zl[b * zstride + zoff + c], beta = zl[b * zstride + zoff + C + c]
 int coef_forward(const double* sums, float* coef, int B, int C, int groups, double count, hipStream_t st,
                  const float* gw = nullptr, const float* gb = nullptr, const float* zl = nullptr, int zstride = 0, int zoff = 0);
-// out = act(x * A + B (+ res)) on a channels-last [B][P][C] tensor; coef index = b * cstride + c (i2v_embed.hip)
+// out = act(x * A + B (+ res)) on a channels-last [B][P][C] tensor; coef index = b * cstride + c (cstride 0: constants for all b)
 // out_hl16 (optional): the same result in the split-fp16 operand format (input of conv16_forward); out may then be null
 int norm_act_forward(const float* x, const float* coef, long cstride, const float* res, float* out, int B, long P, int C, bool relu,
                      hipStream_t st, void* out_hl16 = nullptr);

@@ -2,6 +2,7 @@
 //   stats_forward    per-(b,c) sum / sum of squares of a channels-last tensor (fp64 accumulation)
 //   coef_forward     the statistics folded with the affine / ADAIN parameters into one (A, B) pair per (b,c)
 //   resize_forward   bilinear resize of the start frames into the conv kernels' 16-channel rows
+//   norm_act_forward act(x * A + B (+ residual)) in fp32 and / or the split-fp16 operand format
 #include <algorithm>
 
 #include "i2v_conv.h"
@@ -145,6 +146,45 @@ __global__ void resize_kernel(const float* __restrict__ img, float* __restrict__
     if (bad && range_flag) atomicOr(range_flag, 1);
 }
 
+// out = act(x * A + B (+ res)); coef index = b * cstride + c (cstride = C for per-sample norms, 0 for BatchNorm constants).
+// out16 (optional, C % 8 == 0): the same values in the split-fp16 operand format of i2v_conv16.hip (per 8 channels: 8 x fp16
+// hi | 8 x fp16 lo); out may then be null when only the next convolution reads the result.
+__global__ __launch_bounds__(256) void norm_act_kernel(const float* __restrict__ x, const float2* __restrict__ coef, long cstride,
+                                                       const float* __restrict__ res, float* __restrict__ out,
+                                                       char* __restrict__ out16, long per, int C, int relu) {
+    const int C4 = C >> 2;
+    const int b = blockIdx.y;
+    const float2* cp = coef + (long)b * cstride;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < per; i += (long)gridDim.x * 256) {
+        const int c4 = (int)(i % C4);
+        const long off = (long)b * per * 4 + i * 4;
+        const float4 v = *reinterpret_cast<const float4*>(x + off);
+        const float4 ab0 = *reinterpret_cast<const float4*>(cp + 4 * c4), ab1 = *reinterpret_cast<const float4*>(cp + 4 * c4 + 2);
+        float4 r = make_float4(fmaf(v.x, ab0.x, ab0.y), fmaf(v.y, ab0.z, ab0.w), fmaf(v.z, ab1.x, ab1.y), fmaf(v.w, ab1.z, ab1.w));
+        if (res) {
+            const float4 q = *reinterpret_cast<const float4*>(res + off);
+            r.x += q.x; r.y += q.y; r.z += q.z; r.w += q.w;
+        }
+        if (relu) { r.x = fmaxf(r.x, 0.f); r.y = fmaxf(r.y, 0.f); r.z = fmaxf(r.z, 0.f); r.w = fmaxf(r.w, 0.f); }
+        if (out) *reinterpret_cast<float4*>(out + off) = r;
+        if (out16) {
+            typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
+            const float rr[4] = {r.x, r.y, r.z, r.w};
+            half4_t hi, lo;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const _Float16 hh = (_Float16)rr[j];
+                hi[j] = hh;
+                lo[j] = (_Float16)(rr[j] - (float)hh);
+            }
+            // element index (b, pos, c4): the 8-channel group c4 / 2 occupies 32 bytes, this thread owns half of each 16-byte part
+            char* o = out16 + ((long)b * per + (i - c4)) * 16 + (c4 >> 1) * 32 + (c4 & 1) * 8;
+            *reinterpret_cast<half4_t*>(o) = hi;
+            *reinterpret_cast<half4_t*>(o + 16) = lo;
+        }
+    }
+}
+
 int stats_forward(const float* x, double* sums, int B, long P, int C, hipStream_t st) {
     I2V_REQUIRE(C % 4 == 0 && (C <= 1024 || C % 1024 == 0), I2V_E_INVALID, "stats: unsupported channel count %d", C);
     I2V_HIP_CHECK(hipMemsetAsync(sums, 0, (size_t)B * C * 16, st));
@@ -172,6 +212,17 @@ int resize_forward(const float* img, float* out, int B, int Hi, int Wi, int Ho, 
     const long tot = (long)B * Ho * Wo;
     hipLaunchKernelGGL(resize_kernel, dim3((unsigned)std::min<long>((tot + 255) / 256, 65536)), dim3(256), 0, st, img, out, B, Hi, Wi,
                        Ho, Wo, hl16, flag, ibs);
+    I2V_HIP_CHECK(hipGetLastError());
+    return I2V_OK;
+}
+
+int norm_act_forward(const float* x, const float* coef, long cstride, const float* res, float* out, int B, long P, int C, bool relu,
+                     hipStream_t st, void* out_hl16) {
+    I2V_REQUIRE(out || out_hl16, I2V_E_INVALID, "norm_act: no output");
+    I2V_REQUIRE(!out_hl16 || C % 8 == 0, I2V_E_INVALID, "norm_act: the split-fp16 output needs C %% 8 == 0 (C = %d)", C);
+    const long per = P * (C / 4);
+    hipLaunchKernelGGL(norm_act_kernel, dim3((unsigned)std::min<long>((per + 255) / 256, 4096), B), dim3(256), 0, st, x,
+                       reinterpret_cast<const float2*>(coef), cstride, res, out, static_cast<char*>(out_hl16), per, C, relu ? 1 : 0);
     I2V_HIP_CHECK(hipGetLastError());
     return I2V_OK;
 }
