@@ -65,6 +65,10 @@ class VGGLayer(ctypes.Structure):
     _fields_ = [("h", c_int32), ("w", c_int32), ("cout", c_int32), ("tap", c_int32), ("offset", c_int64)]
 
 
+class PatchDiscCfg(ctypes.Structure):
+    _fields_ = [(n, c_int32) for n in ("in_channels", "ndf", "n_layers", "use_actnorm", "spectral_norm")]
+
+
 _lib = None
 
 # symbol -> (restype, argtypes); also the list the CPU test-suite checks the .so exports
@@ -221,6 +225,37 @@ SYMBOLS = {
     "i2v_kl_normal": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
 }
 
+# The entries of include/i2v_hip_disc.h (the patch discriminator of stage-1 training), a table of its own: SYMBOLS is the list of
+# include/i2v_hip.h, one to one.
+DISC_SYMBOLS = {
+    "i2v_patchdisc_create": (c_int32, [POINTER(PatchDiscCfg), POINTER(c_void_p)]),
+    "i2v_patchdisc_destroy": (None, [c_void_p]),
+    "i2v_patchdisc_bind": (c_int32, [c_void_p, POINTER(_Tensor), c_int32]),
+    "i2v_patchdisc_bind_grads": (c_int32, [c_void_p, POINTER(_Tensor), c_int32]),
+    "i2v_patchdisc_out_shape": (c_int32, [c_void_p, c_int32, c_int32, POINTER(c_int32), POINTER(c_int32)]),
+    "i2v_patchdisc_saved_bytes": (c_size_t, [c_void_p, c_int32, c_int32, c_int32]),
+    "i2v_patchdisc_workspace_bytes": (c_size_t, [c_void_p, c_int32, c_int32, c_int32]),
+    "i2v_patchdisc_saved_layout": (c_int32, [c_void_p, c_int32, c_int32, c_int32, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), POINTER(c_int32),
+                                             POINTER(c_int64), POINTER(c_int64)]),
+    "i2v_patchdisc_forward": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t,
+                                        c_void_p]),
+    "i2v_patchdisc_backward": (c_int32, [c_void_p, c_void_p, c_void_p, c_size_t, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p,
+                                         c_size_t, c_void_p]),
+    "i2v_patchdisc_hinge": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "i2v_patchdisc_wgrad_plan": (c_int32, [c_int32, c_int32, c_int64, POINTER(c_int32), POINTER(c_int32)]),
+    "i2v_patchdisc_unit_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "i2v_patchdisc_conv_unit": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                          c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "i2v_patchdisc_dgrad_unit": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
+                                           c_int32, c_void_p, c_size_t, c_void_p]),
+    "i2v_patchdisc_wgrad_unit": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
+                                           c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "i2v_patchdisc_head_unit": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_size_t, c_void_p]),
+    "i2v_patchdisc_power_iteration_unit": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "i2v_patchdisc_actnorm_init_unit": (c_int32, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
+}
+
 
 def build(force=False):
     """Compile ``libi2v_hip.so`` for gfx950 in-tree (``make`` in csrc/; hipcc cross-compiles without a GPU)."""
@@ -252,7 +287,7 @@ def lib():
             raise I2VError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                            f"or `make -C {CSRC}`; this package has no CPU/eager fallback")
         l = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
+        for name, (res, args) in list(SYMBOLS.items()) + list(DISC_SYMBOLS.items()):
             fn = getattr(l, name)
             fn.restype = res
             fn.argtypes = args
@@ -1849,3 +1884,210 @@ def kl_normal(mu, logvar):
     with torch.cuda.device(mu.device):
         _call("i2v_kl_normal", mu.data_ptr(), logvar.data_ptr(), mu.shape[0], mu.shape[1], out.data_ptr(), _stream())
     return out[0]
+
+
+# ---------------------------------------------------------------------------------------------------- patch discriminator (stage 1)
+PATCHDISC_ITERATE, PATCHDISC_INIT_ACTNORM, PATCHDISC_SAVE = 1, 2, 4
+HINGE_DISC, HINGE_GEN = 0, 1
+
+
+def _opt(t):
+    return None if t is None else t.data_ptr()
+
+
+class NativePatchDisc(_Handle):
+    """Handle for ``i2v_patchdisc_*`` (include/i2v_hip_disc.h): NLayerDiscriminator forward and backward.  It packs nothing on the
+    host: ``bind`` hands over the DEVICE pointers of the module's parameters and buffers (read in place; ``weight_u``, ``weight_v``,
+    ``loc`` and ``scale`` are updated in place) and of their gradient tensors."""
+    _PREFIX = "i2v_patchdisc"
+
+    def __init__(self, in_channels=3, ndf=64, n_layers=3, use_actnorm=True, spectral_norm=True, device=None):
+        cfg = PatchDiscCfg(int(in_channels), int(ndf), int(n_layers), int(bool(use_actnorm)), int(bool(spectral_norm)))
+        self._create(device, ctypes.byref(cfg))
+        self.bound_ptrs, self.bound_grad_ptrs, self._keep, self._keep_grads = None, None, None, None
+
+    def load(self, state_dict):
+        raise I2VError("NativePatchDisc packs nothing: bind() hands over the module's own parameters")
+
+    @staticmethod
+    def _items(tensors):
+        keep = [k.encode() for k in tensors]
+        for t in tensors.values():
+            _require_gpu(t)
+        return (_Tensor * len(keep))(*[_Tensor(kb, t.data_ptr(), t.numel(), I2V_F32) for kb, t in zip(keep, tensors.values())]), keep
+
+    def bind(self, tensors):
+        """tensors: {state_dict key: float32 device tensor} of the parameters and the spectral-norm buffers."""
+        with self._on(*tensors.values()):
+            arr, keep = self._items(tensors)
+            _call("i2v_patchdisc_bind", self._h, arr, len(keep))
+        self.bound_ptrs = tuple(t.data_ptr() for t in tensors.values())
+        self._keep = tensors
+
+    def bind_grads(self, grads):
+        """grads: {key: gradient tensor} of the trained parameters, or None.  Bound apart from the parameters: a fresh gradient buffer per
+        backward re-binds these alone."""
+        if grads is None:
+            _call("i2v_patchdisc_bind_grads", self._h, None, 0)
+        else:
+            with self._on(*grads.values()):
+                arr, keep = self._items(grads)
+                _call("i2v_patchdisc_bind_grads", self._h, arr, len(keep))
+        self.bound_grad_ptrs = None if grads is None else tuple(g.data_ptr() for g in grads.values())
+        self._keep_grads = grads
+
+    def out_shape(self, h, w):
+        ho, wo = c_int32(), c_int32()
+        _call("i2v_patchdisc_out_shape", self._h, int(h), int(w), ctypes.byref(ho), ctypes.byref(wo))
+        return ho.value, wo.value
+
+    def _shape(self, x):
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise I2VError(f"patch discriminator: expected frames [N, 3, H, W], got {tuple(x.shape)}")
+        n, _, h, w = x.shape
+        return n, h, w, self.out_shape(h, w)
+
+    def saved_bytes(self, n, h, w):
+        return int(lib().i2v_patchdisc_saved_bytes(self._h, n, h, w))
+
+    def saved_activations(self, saved, shape):
+        """[(activation, pre-ActNorm output or None) per conv but the last], views of ``saved`` [N, Ho, Wo, Cout], for the tests."""
+        n, _, h, w = shape
+        nc, ho, wo, co = c_int32(), (c_int32 * 8)(), (c_int32 * 8)(), (c_int32 * 8)()
+        ao, po = (c_int64 * 8)(), (c_int64 * 8)()
+        _call("i2v_patchdisc_saved_layout", self._h, n, h, w, ctypes.byref(nc), ho, wo, co, ao, po)
+        flat = saved.view(torch.float32)
+        view = lambda off, i: None if off < 0 else flat[off // 4: off // 4 + n * ho[i] * wo[i] * co[i]].view(n, ho[i], wo[i], co[i])
+        return [(view(ao[i], i), view(po[i], i)) for i in range(nc.value - 1)]
+
+    @_on_device
+    def forward(self, x, iterate=False, init_actnorm=False, save=False):
+        """-> pred [N, 1, Ho, Wo], or (pred, saved) with ``save``: the uint8 buffer that belongs to this pass and goes to ``backward``."""
+        _require_gpu(x)
+        n, h, w, (ho, wo) = self._shape(x)
+        ws = self._scratch(lib().i2v_patchdisc_workspace_bytes(self._h, n, h, w), x.device)
+        saved = torch.empty(self.saved_bytes(n, h, w), dtype=torch.uint8, device=x.device) if save else None
+        pred = torch.empty(n, 1, ho, wo, dtype=torch.float32, device=x.device)
+        flags = (PATCHDISC_ITERATE if iterate else 0) | (PATCHDISC_INIT_ACTNORM if init_actnorm else 0) | (PATCHDISC_SAVE if save else 0)
+        _call("i2v_patchdisc_forward", self._h, x.data_ptr(), n, h, w, flags, pred.data_ptr(), _opt(saved), 0 if saved is None else saved.numel(), *ws,
+              _stream())
+        return (pred, saved) if save else pred
+
+    @_on_device
+    def backward(self, d_pred, saved, shape, need_dx=True, param_grads=True, accumulate=False):
+        """``shape``: the (N, 3, H, W) of the forward's input.  -> d_x [N, 3, H, W] or None; the parameter gradients go to the bound
+        gradient tensors, written or (``accumulate``) added."""
+        _require_gpu(d_pred)
+        n, _, h, w = shape
+        ws = self._scratch(lib().i2v_patchdisc_workspace_bytes(self._h, n, h, w), d_pred.device)
+        dx = torch.empty(n, 3, h, w, dtype=torch.float32, device=d_pred.device) if need_dx else None
+        _call("i2v_patchdisc_backward", self._h, d_pred.data_ptr(), saved.data_ptr(), saved.numel(), n, h, w, _opt(dx), int(bool(param_grads)),
+              int(bool(accumulate)), *ws, _stream())
+        return dx
+
+
+def patchdisc_hinge(fake, real=None, mode="disc", need_grads=True):
+    """``hinge_loss`` with its gradient -> (out, d_fake, d_real): out float64 [3] = (loss, mean(real), mean(fake)) on the device."""
+    _require_gpu(fake, real)
+    if (mode == "disc") != (real is not None) or (real is not None and real.shape != fake.shape):
+        raise I2VError("patchdisc_hinge: 'disc' takes fake and real of one shape, 'gen' fake alone")
+    with torch.cuda.device(fake.device):
+        out = torch.zeros(3, dtype=torch.float64, device=fake.device)
+        d_fake = torch.empty_like(fake) if need_grads else None
+        d_real = torch.empty_like(real) if need_grads and real is not None else None
+        _call("i2v_patchdisc_hinge", fake.data_ptr(), _opt(real), fake.numel(), HINGE_DISC if mode == "disc" else HINGE_GEN, out.data_ptr(),
+              _opt(d_fake), _opt(d_real), _stream())
+    return out, d_fake, d_real
+
+
+def patchdisc_wgrad_plan(cout, cin, positions):
+    """(slices, slice_len) of the weight gradient's position split: a pure host function of the shape."""
+    s, l = c_int32(), c_int32()
+    _call("i2v_patchdisc_wgrad_plan", int(cout), int(cin), int(positions), ctypes.byref(s), ctypes.byref(l))
+    return s.value, l.value
+
+
+def _pd_ws(n, hi, wi, cin, cout, device):
+    return torch.empty(int(lib().i2v_patchdisc_unit_workspace_bytes(n, hi, wi, cin, cout)), dtype=torch.uint8, device=device)
+
+
+def _pd_geom(x, weight, stride):
+    n, hi, wi, cs = x.shape
+    cout, cin = weight.shape[:2]
+    if cs != (4 if cin == 3 else cin) or tuple(weight.shape[2:]) != (4, 4):
+        raise I2VError(f"patch discriminator unit: map {tuple(x.shape)} against weight {tuple(weight.shape)}")
+    return n, hi, wi, cin, cout, (hi - 2) // stride + 1, (wi - 2) // stride + 1
+
+
+def patchdisc_conv_unit(x, weight, bias, loc=None, scale=None, stride=2, lrelu=False, want_pre=False):
+    """x [N, H, W, C] channels-last (C = 4 for cin 3) -> out [N, Ho, Wo, Cout] (and the pre-ActNorm conv output with ``want_pre``)."""
+    _require_gpu(x, weight, bias, loc, scale)
+    n, hi, wi, cin, cout, ho, wo = _pd_geom(x, weight, stride)
+    with torch.cuda.device(x.device):
+        ws = _pd_ws(n, hi, wi, cin, cout, x.device)
+        out = torch.empty(n, ho, wo, cout, dtype=torch.float32, device=x.device)
+        pre = torch.empty_like(out) if want_pre else None
+        _call("i2v_patchdisc_conv_unit", x.data_ptr(), weight.data_ptr(), bias.data_ptr(), _opt(loc), _opt(scale), n, hi, wi, cin, cout, stride,
+              int(bool(lrelu)), out.data_ptr(), _opt(pre), ws.data_ptr(), ws.numel(), _stream())
+    return (out, pre) if want_pre else out
+
+
+def patchdisc_dgrad_unit(g, weight, in_hw, act=None, scale=None, stride=2, frames=False):
+    """g [N, Ho, Wo, Cout] -> the gradient at the conv's input [N, H, W, Cin] (cin 3: 4 channels, or [N, 3, H, W] with ``frames``)."""
+    _require_gpu(g, weight, act, scale)
+    n, (hi, wi), (cout, cin) = g.shape[0], in_hw, weight.shape[:2]
+    with torch.cuda.device(g.device):
+        ws = _pd_ws(n, hi, wi, cin, cout, g.device)
+        out = torch.empty((n, 3, hi, wi) if frames else (n, hi, wi, 4 if cin == 3 else cin), dtype=torch.float32, device=g.device)
+        _call("i2v_patchdisc_dgrad_unit", g.data_ptr(), weight.data_ptr(), _opt(act), _opt(scale), n, hi, wi, cin, cout, stride, out.data_ptr(),
+              int(bool(frames)), ws.data_ptr(), ws.numel(), _stream())
+    return out
+
+
+def patchdisc_wgrad_unit(g, x, weight, act=None, scale=None, u=None, v=None, sigma=None, stride=2, dweight=None, dbias=None):
+    """-> (dweight [Cout, Cin, 4, 4], dbias [Cout]); given ``dweight`` / ``dbias`` the result is ADDED to them."""
+    _require_gpu(g, x, weight, act, scale, u, v, sigma, dweight, dbias)
+    n, hi, wi, cin, cout, _, _ = _pd_geom(x, weight, stride)
+    accumulate = dweight is not None
+    with torch.cuda.device(g.device):
+        ws = _pd_ws(n, hi, wi, cin, cout, g.device)
+        if not accumulate:
+            dweight, dbias = torch.empty_like(weight), torch.empty(cout, dtype=torch.float32, device=g.device)
+        _call("i2v_patchdisc_wgrad_unit", g.data_ptr(), _opt(act), _opt(scale), x.data_ptr(), weight.data_ptr(), _opt(u), _opt(v), _opt(sigma), n, hi, wi,
+              cin, cout, stride, int(accumulate), dweight.data_ptr(), dbias.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+    return dweight, dbias
+
+
+def patchdisc_head_unit(x, weight, bias, g=None):
+    """The cout = 1 conv: x [N, H, W, C] -> out [N, H-1, W-1]; with g also (dx, dweight, dbias)."""
+    _require_gpu(x, weight, bias, g)
+    n, hi, wi, cin = x.shape
+    with torch.cuda.device(x.device):
+        ws = _pd_ws(n, hi, wi, cin, 1, x.device)
+        out = torch.empty(n, hi - 1, wi - 1, dtype=torch.float32, device=x.device)
+        dx, dw, db = (torch.empty_like(x), torch.empty_like(weight), torch.empty(1, dtype=torch.float32, device=x.device)) if g is not None else (None,) * 3
+        _call("i2v_patchdisc_head_unit", x.data_ptr(), weight.data_ptr(), bias.data_ptr(), _opt(g), n, hi, wi, cin, out.data_ptr(), _opt(dx), _opt(dw),
+              _opt(db), ws.data_ptr(), ws.numel(), _stream())
+    return out if g is None else (out, dx, dw, db)
+
+
+def patchdisc_power_iteration_unit(weight, u, v, iterate=True):
+    """weight [rows, cols]; u, v updated in place when ``iterate``; -> sigma [1]."""
+    _require_gpu(weight, u, v)
+    rows, cols = weight.shape
+    with torch.cuda.device(weight.device):
+        ws = torch.empty(8 * (rows + cols) + 1024, dtype=torch.uint8, device=weight.device)
+        sigma = torch.empty(1, dtype=torch.float32, device=weight.device)
+        _call("i2v_patchdisc_power_iteration_unit", weight.data_ptr(), u.data_ptr(), v.data_ptr(), rows, cols, int(bool(iterate)), sigma.data_ptr(),
+              ws.data_ptr(), ws.numel(), _stream())
+    return sigma
+
+
+def patchdisc_actnorm_init_unit(pre):
+    """pre [M, C] -> (loc [C], scale [C])."""
+    _require_gpu(pre)
+    m, c = pre.shape
+    with torch.cuda.device(pre.device):
+        loc, scale = torch.empty(c, dtype=torch.float32, device=pre.device), torch.empty(c, dtype=torch.float32, device=pre.device)
+        _call("i2v_patchdisc_actnorm_init_unit", pre.data_ptr(), m, c, loc.data_ptr(), scale.data_ptr(), _stream())
+    return loc, scale

@@ -1,6 +1,7 @@
-"""Training the cINN natively: ``FusedAdam`` (``torch.optim.Adam`` semantics in one multi-tensor HIP launch, ``i2v_adam_step``)
-and ``FlowTrainer`` (forward, loss gradient, backward and optimiser step of the stage-2 trainer, reference
-stage2_cINN/main.py:22-46, without autograd in between).  No CPU fallback: parameters and gradients live on a HIP device."""
+"""Training natively: ``FusedAdam`` (``torch.optim.Adam`` semantics in one multi-tensor HIP launch, ``i2v_adam_step``),
+``FlowTrainer`` (forward, loss gradient, backward and optimiser step of the stage-2 trainer, reference
+stage2_cINN/main.py:22-46, without autograd in between) and ``PatchDiscTrainer`` (the spatial-discriminator lines of the stage-1
+step, reference stage1_VAE/modules/loss.py:111-125).  No CPU fallback: parameters and gradients live on a HIP device."""
 import ctypes
 
 import numpy as np
@@ -149,3 +150,42 @@ class FlowTrainer:
             reference_nll_loss = 0.5 * torch.randn_like(zt).pow(2).sum(1).mean()
         return {"Loss": nll_loss + nlogdet_loss, "reference_nll_loss": reference_nll_loss, "nlogdet_loss": nlogdet_loss,
                 "nll_loss": nll_loss}
+
+
+class PatchDiscTrainer:
+    """The spatial-discriminator part of the stage-1 step without autograd.  ``step(data_fake, data_real)`` is loss.py:112-118: two
+    forwards (each with its own power iteration; the first one initialises ActNorm), the hinge loss, two backwards that accumulate
+    into ``.grad``, and the fused Adam step.  ``generator_loss(data_fake)`` is loss.py:122-123: a third forward and the gradient of
+    ``-mean(pred)`` at the frames, with no weight-gradient launch.  Everything is enqueued on the current stream; nothing
+    synchronises.  Defaults: stage1_VAE/main.py:103 and the shipped configs."""
+
+    def __init__(self, disc, lr=2e-4, betas=(0.5, 0.9), weight_decay=1e-5, eps=1e-8):
+        self.disc = disc
+        self.optimizer = FusedAdam(disc.parameters(), lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+
+    def _grads(self):
+        for p in self.disc.parameters():
+            if p.grad is None:
+                p.grad = torch.zeros_like(p)
+        return {k: p.grad for k, p in self.disc.named_parameters()}
+
+    @torch.no_grad()
+    def step(self, data_fake, data_real):
+        """-> (L_d_s, mean real logit, mean fake logit) as float64 0-d device tensors."""
+        disc, grads = self.disc, self._grads()
+        pred_f, saved_f = disc._run(data_fake, save=True, grads=grads)
+        pred_r, saved_r = disc._run(data_real, save=True, grads=grads)
+        out, d_f, d_r = native.patchdisc_hinge(pred_f, pred_r, "disc")
+        h = disc._handle(grads)
+        h.backward(d_f, saved_f, tuple(data_fake.shape), need_dx=False, param_grads=True, accumulate=False)
+        h.backward(d_r, saved_r, tuple(data_real.shape), need_dx=False, param_grads=True, accumulate=True)
+        self.optimizer.step()
+        return out[0], out[1], out[2]
+
+    @torch.no_grad()
+    def generator_loss(self, data_fake):
+        """-> (loss_gen_s as a float64 0-d device tensor, its gradient at ``data_fake`` [N, 3, H, W]); ``.grad`` is left untouched."""
+        pred, saved = self.disc._run(data_fake, save=True)
+        out, d_f, _ = native.patchdisc_hinge(pred, None, "gen")
+        dx = self.disc._handle().backward(d_f, saved, tuple(data_fake.shape), need_dx=True, param_grads=False)   # (the gradient binding of step() stays)
+        return out[0], dx
