@@ -1,0 +1,1466 @@
+// The temporal discriminator of stage-1 training: resnet3D.Discriminator (stage1_VAE/modules/resnet3D.py:222-301) forward and backward,
+// spectral norm in training mode on block 0 of every layer, GroupNorm(16), the max pool, the head, the feature-map loss (loss.py:14-21).
+// The C ABI is include/i2v_hip_disc3d.h.  Conventions of i2v_patchdisc.hip: exact fp32 on v_mfma_f32_16x16x4_f32; every sum has one owner
+// and a fixed order, so two runs give the same bits.
+//   * Activations are channels-last [N][T][H][W][C]; the clip is stored with 4 channels (r, g, b, 0).
+//   * A forward packs W (/ sigma where the conv is spectral-normed) of every conv once, on the device, into wf [tap][cout][cin] and
+//     wd [tap][cin][cout].  With I2V_DISC3D_SAVE they live in `saved` with that call's u, v and sigma.
+//   * conv forward: implicit GEMM, 128 or 64 positions x BN channels per workgroup, K over (tap, channel) in chunks of 16 double-buffered
+//     in LDS; windows (3, 3, 3) pad 1 and (3, 7, 7) pad (1, 3, 3); the last chunk of the stem (147 taps x 4 channels) is masked.
+//   * dgrad: the same GEMM as a gather over input positions.  Along an axis of stride 2 a coordinate receives the taps of its parity
+//     (window 3: one tap for an even coordinate, two for an odd one; window 7: three and four), so the positions are processed in
+//     stride_t x stride_s x stride_s parity classes (blockIdx.y), each with its own tap list: no structural zero is multiplied.
+//   * wgrad: per tap a [cout] x [cin] GEMM over the positions, cut into slices by d3_wgrad_plan; the four waves of a workgroup take a
+//     quarter of a slice each and are summed in wave order; d3_finish_a adds the slices in slice order, d3_finish_dot forms <dWn, W> once,
+//     d3_finish_b applies the projection.
+//   * GroupNorm: float64 statistics per (sample, group) from slices added in slice order; one apply pass; the backward's per-channel sums
+//     likewise, then the two per-(sample, group) sums, then dx.
+#include "i2v_handle.h"
+#include "i2v_power_iter.h"
+#include "../../include/i2v_hip_disc3d.h"
+
+#include <string>
+
+namespace i2v {
+namespace {
+
+constexpr int D3_MAXCONV = 21;   // stem + 4 layers x (2 + 1 + 2)
+constexpr int D3_LS = 20;        // floats per staged row of 16
+constexpr int D3_GROUPS = 16;
+constexpr int D3_GN_SLICES = 32;
+constexpr int D3_FMAP_BLOCKS = 64;
+
+struct D3Conv { int cin, cinp, cind, cout, kh, kw, st, ss, sn; };   // cinp: channels of the stored input map; cind: columns of the dgrad GEMM
+struct D3Geo { int ti, hi, wi, to, ho, wo; long mi, mo; };
+
+// ------------------------------------------------------------------------------------------------------------------ small kernels
+__global__ __launch_bounds__(256) void d3_input4_kernel(const float* __restrict__ x, float* __restrict__ out, long npix, long thw) {
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < npix; i += gridDim.x * 256L) {
+        const long n = i / thw, p = i - n * thw;
+        const float* s = x + n * 3 * thw + p;
+        *reinterpret_cast<float4*>(out + 4 * i) = make_float4(s[0], s[thw], s[2 * thw], 0.f);
+    }
+}
+
+__global__ __launch_bounds__(256) void d3_add_kernel(float* __restrict__ dst, const float* __restrict__ src, long total) {
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += gridDim.x * 256L) dst[i] += src[i];
+}
+
+// W (/ sigma) into the two operand layouts
+struct D3PackConv { const float* w; const float* sigma; float* wf; float* wd; int cout, cin, cinp, cind, ntap; long first; };
+struct D3PackArgs { D3PackConv c[D3_MAXCONV]; int nconv; long total; };
+
+__global__ __launch_bounds__(256) void d3_pack_kernel(D3PackArgs a) {
+    for (long e = blockIdx.x * 256L + threadIdx.x; e < a.total; e += gridDim.x * 256L) {
+        int ci = 0;
+        while (ci + 1 < a.nconv && e >= a.c[ci + 1].first) ++ci;
+        const D3PackConv& c = a.c[ci];
+        long r = e - c.first;                       // ((co * cind) + cip) * ntap + tap
+        const int tap = (int)(r % c.ntap); r /= c.ntap;
+        const int cip = (int)(r % c.cind), co = (int)(r / c.cind);
+        float val = 0.f;
+        if (cip < c.cin) {
+            val = c.w[((long)co * c.cin + cip) * c.ntap + tap];
+            if (c.sigma) val = val / *c.sigma;
+        }
+        if (cip < c.cinp) c.wf[((long)tap * c.cout + co) * c.cinp + cip] = val;
+        if (c.wd) c.wd[((long)tap * c.cind + cip) * c.cout + co] = val;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------ conv forward
+struct D3ConvArgs {
+    const float* in;     // [N][Ti][Hi][Wi][cinp]
+    const float* wf;     // [ntap][cout][cinp]
+    float* out;          // [M][cout]
+    long M;
+    int Ti, Hi, Wi, To, Ho, Wo, cinp, C4, nchunk, ntap, kh, kw, st, ss, cout;
+};
+
+template <int NT, int MR>   // BN = 16 NT columns, BM = 64 MR rows per workgroup
+__global__ __launch_bounds__(256) void d3_conv_kernel(D3ConvArgs a) {
+    constexpr int BN = 16 * NT, BM = 64 * MR;
+    __shared__ __attribute__((aligned(16))) float a_lds[2][BM * D3_LS];
+    __shared__ __attribute__((aligned(16))) float w_lds[2][BN * D3_LS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lr = lane & 15, kq = lane >> 4, q = tid & 3;
+    const int nNt = a.cout / BN;
+    const int n0 = (int)(blockIdx.x % nNt) * BN;
+    const long m0 = (long)(blockIdx.x / nNt) * BM;
+    const int khw = a.kh * a.kw, ph = a.kh >> 1, pw = a.kw >> 1;
+
+    int rb[MR], rt[MR], rh[MR], rw[MR];
+#pragma unroll
+    for (int u = 0; u < MR; ++u) {
+        long m = m0 + (tid >> 2) + 64 * u;
+        const bool ok = m < a.M;
+        if (!ok) m = 0;
+        const int wo = (int)(m % a.Wo); m /= a.Wo;
+        const int ho = (int)(m % a.Ho); m /= a.Ho;
+        const int to = (int)(m % a.To); m /= a.To;
+        rb[u] = ok ? (int)m : -1;
+        rt[u] = to * a.st - 1; rh[u] = ho * a.ss - ph; rw[u] = wo * a.ss - pw;
+    }
+    float4 pa0, pa1, pw0;
+    pa1 = pw0 = make_float4(0.f, 0.f, 0.f, 0.f);
+    auto request = [&](int ch) {
+        const int g = ch * 4 + q;
+        const int tap = g / a.C4, c = (g - tap * a.C4) * 4;
+        const bool tok = tap < a.ntap;   // the stem's last chunk
+        const int dt = tap / khw, rr = tap - dt * khw;
+        const int dh = rr / a.kw, dw = rr - dh * a.kw;
+#pragma unroll
+        for (int u = 0; u < MR; ++u) {
+            const int t = rt[u] + dt, h = rh[u] + dh, w = rw[u] + dw;
+            const bool ok = tok && rb[u] >= 0 && (unsigned)t < (unsigned)a.Ti && (unsigned)h < (unsigned)a.Hi && (unsigned)w < (unsigned)a.Wi;
+            const long off = ok ? ((((long)rb[u] * a.Ti + t) * a.Hi + h) * a.Wi + w) * a.cinp + c : 0;
+            const float4 v = *reinterpret_cast<const float4*>(a.in + off);
+            const float4 z = ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
+            if (u == 0) pa0 = z; else pa1 = z;
+        }
+        if (tid < BN * 4) {
+            const float4 v = *reinterpret_cast<const float4*>(a.wf + (tok ? ((long)tap * a.cout + n0 + (tid >> 2)) * a.cinp + c : 0));
+            pw0 = tok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    };
+    auto park = [&](int buf) {
+        *reinterpret_cast<float4*>(&a_lds[buf][(tid >> 2) * D3_LS + 4 * q]) = pa0;
+        if constexpr (MR == 2) *reinterpret_cast<float4*>(&a_lds[buf][((tid >> 2) + 64) * D3_LS + 4 * q]) = pa1;
+        if (tid < BN * 4) *reinterpret_cast<float4*>(&w_lds[buf][(tid >> 2) * D3_LS + 4 * q]) = pw0;
+    };
+
+    f32x4 acc[MR][NT];
+#pragma unroll
+    for (int mt = 0; mt < MR; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    request(0);
+    park(0);
+    __syncthreads();
+    for (int ch = 0; ch < a.nchunk; ++ch) {
+        const int buf = ch & 1;
+        request(ch + 1 < a.nchunk ? ch + 1 : ch);
+        // MFMA k-slot (lane >> 4) of step s carries K element 4 (lane >> 4) + s of the chunk, for both operands
+        float4 av[MR], bv[NT];
+#pragma unroll
+        for (int mt = 0; mt < MR; ++mt) av[mt] = *reinterpret_cast<const float4*>(&a_lds[buf][(wave * 16 * MR + 16 * mt + lr) * D3_LS + 4 * kq]);
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) bv[nt] = *reinterpret_cast<const float4*>(&w_lds[buf][(16 * nt + lr) * D3_LS + 4 * kq]);
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+#pragma unroll
+            for (int mt = 0; mt < MR; ++mt) {
+                const float as = s == 0 ? av[mt].x : s == 1 ? av[mt].y : s == 2 ? av[mt].z : av[mt].w;
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) {
+                    const float bs = s == 0 ? bv[nt].x : s == 1 ? bv[nt].y : s == 2 ? bv[nt].z : bv[nt].w;
+                    acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(as, bs, acc[mt][nt], 0, 0, 0);
+                }
+            }
+        if (ch + 1 < a.nchunk) park(buf ^ 1);
+        __syncthreads();
+    }
+
+    // C/D layout of the 16x16 MFMA: column = lane & 15, rows 4 (lane >> 4) + r
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+        const int n = n0 + 16 * nt + lr;
+#pragma unroll
+        for (int mt = 0; mt < MR; ++mt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const long m = m0 + wave * 16 * MR + 16 * mt + 4 * kq + r;
+                if (m < a.M) a.out[m * a.cout + n] = acc[mt][nt][r];
+            }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------ input gradient
+struct D3DgradArgs {
+    const float* g;      // [N][To][Ho][Wo][cout], the gradient at the conv's output
+    const float* act;    // a ReLU mask of g's shape (g counts where act > 0) or null
+    const float* wd;     // [ntap][cind][cout]
+    const float *add, *add_mask;   // of out's shape or null: out = result + add [add_mask > 0]
+    float* out;          // [N][Ti][Hi][Wi][cin]; frames: [N][3][Ti][Hi][Wi]
+    int N, Ti, Hi, Wi, To, Ho, Wo, cout, C4o, kh, kw, st, ss, cin, cind, frames;
+};
+
+template <int NT, int MR>
+__global__ __launch_bounds__(256) void d3_dgrad_kernel(D3DgradArgs a) {
+    constexpr int BN = 16 * NT, BM = 64 * MR;
+    __shared__ __attribute__((aligned(16))) float a_lds[2][BM * D3_LS];
+    __shared__ __attribute__((aligned(16))) float w_lds[2][BN * D3_LS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lr = lane & 15, kq = lane >> 4, q = tid & 3;
+    // the parity class of this workgroup: (pt, ph, pw), each 0 where its axis has stride 1
+    const int cls = blockIdx.y;
+    const int pw_ = cls % a.ss, ph_ = (cls / a.ss) % a.ss, pt_ = cls / (a.ss * a.ss);
+    const int Tc = (a.Ti - pt_ + a.st - 1) / a.st, Hc = (a.Hi - ph_ + a.ss - 1) / a.ss, Wc = (a.Wi - pw_ + a.ss - 1) / a.ss;
+    const long Mc = (long)a.N * Tc * Hc * Wc;
+    const int nNt = a.cind / BN;
+    const int n0 = (int)(blockIdx.x % nNt) * BN;
+    const long m0 = (long)(blockIdx.x / nNt) * BM;
+    if (m0 >= Mc) return;
+    // taps of the class along an axis of window k, pad p, stride s: k_j = kb + s j with kb = (parity + p) % s
+    const int padh = a.kh >> 1, padw = a.kw >> 1;
+    const int ktb = (pt_ + 1) % a.st, khb = (ph_ + padh) % a.ss, kwb = (pw_ + padw) % a.ss;
+    const int ntt = (3 - ktb + a.st - 1) / a.st, nth = (a.kh - khb + a.ss - 1) / a.ss, ntw = (a.kw - kwb + a.ss - 1) / a.ss;
+    const int nchunk = ntt * nth * ntw * a.C4o / 4;
+
+    int rb[MR], rt[MR], rh[MR], rw[MR];   // batch row (-1: masked), t + 1, h + pad, w + pad
+#pragma unroll
+    for (int u = 0; u < MR; ++u) {
+        long m = m0 + (tid >> 2) + 64 * u;
+        const bool ok = m < Mc;
+        if (!ok) m = 0;
+        const int wc = (int)(m % Wc); m /= Wc;
+        const int hc = (int)(m % Hc); m /= Hc;
+        const int tc = (int)(m % Tc); m /= Tc;
+        rb[u] = ok ? (int)m : -1;
+        rt[u] = tc * a.st + pt_ + 1; rh[u] = hc * a.ss + ph_ + padh; rw[u] = wc * a.ss + pw_ + padw;
+    }
+    float4 pa0, pa1, pw0;
+    pa1 = pw0 = make_float4(0.f, 0.f, 0.f, 0.f);
+    auto request = [&](int ch) {
+        const int g = ch * 4 + q;
+        const int tj = g / a.C4o, c = (g - tj * a.C4o) * 4;
+        const int jt = tj / (nth * ntw), jr = tj - jt * nth * ntw, jh = jr / ntw, jw = jr - jh * ntw;
+        const int kt = ktb + a.st * jt, kh = khb + a.ss * jh, kw = kwb + a.ss * jw;
+#pragma unroll
+        for (int u = 0; u < MR; ++u) {
+            const int dt = rt[u] - kt, dh = rh[u] - kh, dw = rw[u] - kw;   // multiples of the strides by the choice of the taps
+            const int to = dt / a.st, ho = dh / a.ss, wo = dw / a.ss;
+            const bool ok = rb[u] >= 0 && dt >= 0 && dh >= 0 && dw >= 0 && to < a.To && ho < a.Ho && wo < a.Wo;
+            const long off = ok ? ((((long)rb[u] * a.To + to) * a.Ho + ho) * a.Wo + wo) * a.cout + c : 0;
+            float4 v = *reinterpret_cast<const float4*>(a.g + off);
+            if (a.act) {
+                const float4 y = *reinterpret_cast<const float4*>(a.act + off);
+                v.x = y.x > 0.f ? v.x : 0.f; v.y = y.y > 0.f ? v.y : 0.f; v.z = y.z > 0.f ? v.z : 0.f; v.w = y.w > 0.f ? v.w : 0.f;
+            }
+            const float4 z = ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
+            if (u == 0) pa0 = z; else pa1 = z;
+        }
+        if (tid < BN * 4) pw0 = *reinterpret_cast<const float4*>(a.wd + ((long)((kt * a.kh + kh) * a.kw + kw) * a.cind + n0 + (tid >> 2)) * a.cout + c);
+    };
+    auto park = [&](int buf) {
+        *reinterpret_cast<float4*>(&a_lds[buf][(tid >> 2) * D3_LS + 4 * q]) = pa0;
+        if constexpr (MR == 2) *reinterpret_cast<float4*>(&a_lds[buf][((tid >> 2) + 64) * D3_LS + 4 * q]) = pa1;
+        if (tid < BN * 4) *reinterpret_cast<float4*>(&w_lds[buf][(tid >> 2) * D3_LS + 4 * q]) = pw0;
+    };
+
+    f32x4 acc[MR][NT];
+#pragma unroll
+    for (int mt = 0; mt < MR; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    request(0);
+    park(0);
+    __syncthreads();
+    for (int ch = 0; ch < nchunk; ++ch) {
+        const int buf = ch & 1;
+        request(ch + 1 < nchunk ? ch + 1 : ch);
+        float4 av[MR], bv[NT];
+#pragma unroll
+        for (int mt = 0; mt < MR; ++mt) av[mt] = *reinterpret_cast<const float4*>(&a_lds[buf][(wave * 16 * MR + 16 * mt + lr) * D3_LS + 4 * kq]);
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) bv[nt] = *reinterpret_cast<const float4*>(&w_lds[buf][(16 * nt + lr) * D3_LS + 4 * kq]);
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+#pragma unroll
+            for (int mt = 0; mt < MR; ++mt) {
+                const float as = s == 0 ? av[mt].x : s == 1 ? av[mt].y : s == 2 ? av[mt].z : av[mt].w;
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) {
+                    const float bs = s == 0 ? bv[nt].x : s == 1 ? bv[nt].y : s == 2 ? bv[nt].z : bv[nt].w;
+                    acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(as, bs, acc[mt][nt], 0, 0, 0);
+                }
+            }
+        if (ch + 1 < nchunk) park(buf ^ 1);
+        __syncthreads();
+    }
+
+#pragma unroll
+    for (int mt = 0; mt < MR; ++mt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            long m = m0 + wave * 16 * MR + 16 * mt + 4 * kq + r;
+            if (m >= Mc) continue;
+            const int wc = (int)(m % Wc); m /= Wc;
+            const int hc = (int)(m % Hc); m /= Hc;
+            const int tc = (int)(m % Tc); m /= Tc;
+            const int t = tc * a.st + pt_, h = hc * a.ss + ph_, w = wc * a.ss + pw_;
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) {
+                const int n = n0 + 16 * nt + lr;
+                if (a.frames) {
+                    if (n < 3) a.out[(((m * 3 + n) * a.Ti + t) * a.Hi + h) * a.Wi + w] = acc[mt][nt][r];
+                } else if (n < a.cin) {
+                    const long o = (((m * a.Ti + t) * a.Hi + h) * a.Wi + w) * a.cin + n;
+                    float v = acc[mt][nt][r];
+                    if (a.add) v += a.add_mask ? (a.add_mask[o] > 0.f ? a.add[o] : 0.f) : a.add[o];
+                    a.out[o] = v;
+                }
+            }
+        }
+}
+
+// ------------------------------------------------------------------------------------------------------------------ weight gradient
+struct D3WgradArgs {
+    const float *g, *act;   // as D3DgradArgs
+    const float* x;         // the conv's input [N][Ti][Hi][Wi][cinp]
+    float* part;            // [slices][ntap][cout][CP]
+    long P;                 // positions N To Ho Wo
+    int Ti, Hi, Wi, To, Ho, Wo, cinp, cout, CP, kh, kw, st, ss, slice_len;
+};
+
+template <int MT, int NT>
+__global__ __launch_bounds__(256) void d3_wgrad_kernel(D3WgradArgs a) {
+    __shared__ float red[3][MT * NT * 4 * 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lr = lane & 15, kq = lane >> 4;
+    const int nCi = a.CP / (16 * NT);
+    const int co0 = (int)(blockIdx.x / nCi) * 16 * MT, ci0 = (int)(blockIdx.x % nCi) * 16 * NT;
+    const int tap = blockIdx.y, khw = a.kh * a.kw;
+    const int kt = tap / khw, kh = (tap - kt * khw) / a.kw, kw = tap - kt * khw - kh * a.kw;
+    const int sl = blockIdx.z, quarter = a.slice_len / 4;
+    const long begin = (long)sl * a.slice_len + (long)wave * quarter;
+    const long end = begin + quarter < a.P ? begin + quarter : a.P;
+
+    f32x4 acc[MT][NT];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    // A[i = co][k = position], B[k = position][j = ci]: k-slot (lane >> 4) of a step is position mb + (lane >> 4)
+    for (long mb = begin; mb < end; mb += 4) {
+        long m = mb + kq;
+        const bool ok = m < end;
+        if (!ok) m = 0;
+        const long mrow = m;
+        const int wo = (int)(m % a.Wo); m /= a.Wo;
+        const int ho = (int)(m % a.Ho); m /= a.Ho;
+        const int to = (int)(m % a.To); m /= a.To;
+        const int t = to * a.st - 1 + kt, h = ho * a.ss - (a.kh >> 1) + kh, w = wo * a.ss - (a.kw >> 1) + kw;
+        const bool xok = ok && (unsigned)t < (unsigned)a.Ti && (unsigned)h < (unsigned)a.Hi && (unsigned)w < (unsigned)a.Wi;
+        const long pix = xok ? ((m * a.Ti + t) * a.Hi + h) * a.Wi + w : 0;
+        float av[MT], bv[NT];
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+            const int co = co0 + 16 * mt + lr;
+            float v = a.g[mrow * a.cout + co];
+            if (a.act) v = a.act[mrow * a.cout + co] > 0.f ? v : 0.f;
+            av[mt] = ok ? v : 0.f;
+        }
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            const int ci = ci0 + 16 * nt + lr;
+            const bool cok = xok && ci < a.cinp;
+            const float v = a.x[cok ? pix * a.cinp + ci : 0];
+            bv[nt] = cok ? v : 0.f;
+        }
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mt], bv[nt], acc[mt][nt], 0, 0, 0);
+    }
+
+    // the four waves' sums in wave order
+    if (wave > 0) {
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) red[wave - 1][((mt * NT + nt) * 4 + r) * 64 + lane] = acc[mt][nt][r];
+    }
+    __syncthreads();
+    if (wave > 0) return;
+    float* dst = a.part + ((long)sl * gridDim.y + tap) * a.cout * a.CP;
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float v = acc[mt][nt][r];
+                for (int w = 0; w < 3; ++w) v += red[w][((mt * NT + nt) * 4 + r) * 64 + lane];
+                dst[(long)(co0 + 16 * mt + 4 * kq + r) * a.CP + ci0 + 16 * nt + lr] = v;
+            }
+}
+
+struct D3FinishArgs {
+    const float* part;   // [S][ntap][cout][CP]
+    const float* w;      // weight_orig [cout][cin][ntap]
+    const float *u, *v, *sigma;   // this forward's values; sigma null: no projection
+    float* dwn;          // [cout][cin][ntap]
+    double* dotp;        // [nblk + 1]: the workgroups' sums of dWn * W, then their total
+    float* grad;
+    long E;
+    int S, cout, cin, CP, ntap, nblk, accumulate;
+};
+
+// dWn = the slices' partial sums in slice order; per workgroup sum of dWn * W in float64
+__global__ __launch_bounds__(256) void d3_finish_a_kernel(D3FinishArgs a) {
+    __shared__ double red[256];
+    const long e = blockIdx.x * 256L + threadIdx.x;
+    double d = 0.0;
+    if (e < a.E) {
+        const int K = a.cin * a.ntap;
+        const int co = (int)(e / K), k = (int)(e % K), ci = k / a.ntap, tap = k - ci * a.ntap;
+        float sum = 0.f;
+        for (int s = 0; s < a.S; ++s) sum += a.part[(((long)s * a.ntap + tap) * a.cout + co) * a.CP + ci];
+        a.dwn[e] = sum;
+        d = (double)sum * (double)a.w[e];
+    }
+    d = block_sum(d, red);
+    if (threadIdx.x == 0) a.dotp[blockIdx.x] = d;
+}
+
+// <dWn, W> = the workgroups' sums in block order, once for the whole tensor: dotp[nblk]
+__global__ __launch_bounds__(256) void d3_finish_dot_kernel(D3FinishArgs a) {
+    __shared__ double red[256];
+    double d = 0.0;
+    for (int i = threadIdx.x; i < a.nblk; i += 256) d += a.dotp[i];
+    d = block_sum(d, red);
+    if (threadIdx.x == 0) a.dotp[a.nblk] = d;
+}
+
+// dW_orig = (dWn - <dWn, W / sigma> u v^T) / sigma, written or accumulated
+__global__ __launch_bounds__(256) void d3_finish_b_kernel(D3FinishArgs a) {
+    const long e = blockIdx.x * 256L + threadIdx.x;
+    if (e >= a.E) return;
+    float gv = a.dwn[e];
+    if (a.sigma) {
+        const float sg = *a.sigma;
+        const float proj = (float)(a.dotp[a.nblk] / (double)sg);
+        const int K = a.cin * a.ntap;
+        gv = (gv - proj * a.u[e / K] * a.v[e % K]) / sg;
+    }
+    a.grad[e] = a.accumulate ? a.grad[e] + gv : gv;
+}
+
+// ------------------------------------------------------------------------------------------------------------------ GroupNorm(16)
+struct D3GnArgs {
+    const float *x, *res, *weight, *bias;   // forward: x [N][P][C], res of the same shape or null
+    const float *g, *mask;                  // backward: g at the output, mask (the activated output; g counts where mask > 0) or null
+    float *out, *dweight, *dbias;           // out: the forward's output or the backward's dx
+    double *stats;                          // [N][16][2]: mean, 1 / sqrt(var + eps)
+    double *partial, *ab, *gs;              // slices' sums; backward: [N][C][2] per-channel sums, [N][16][2] per-group sums
+    long P, rows_per;
+    int N, C, cpg, R, relu, accumulate;
+};
+
+// sum and sum of squares of one (sample, group) over a slice of the positions
+__global__ __launch_bounds__(256) void d3_gn_stats_kernel(D3GnArgs a) {
+    __shared__ double red[256];
+    const int grp = blockIdx.x, n = blockIdx.y, r = blockIdx.z;
+    const long p0 = r * a.rows_per, p1 = p0 + a.rows_per < a.P ? p0 + a.rows_per : a.P;
+    const long cnt = p1 > p0 ? (p1 - p0) * a.cpg : 0;
+    const float* base = a.x + (long)n * a.P * a.C + grp * a.cpg;
+    double s = 0.0, q = 0.0;
+    for (long i = threadIdx.x; i < cnt; i += 256) {
+        const long p = p0 + i / a.cpg;
+        const double v = (double)base[p * a.C + (int)(i % a.cpg)];
+        s += v; q += v * v;
+    }
+    s = block_sum(s, red);
+    q = block_sum(q, red);
+    if (threadIdx.x == 0) {
+        double* dst = a.partial + (((long)n * D3_GROUPS + grp) * a.R + r) * 2;
+        dst[0] = s; dst[1] = q;
+    }
+}
+
+__global__ __launch_bounds__(256) void d3_gn_stats_final_kernel(D3GnArgs a) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.N * D3_GROUPS) return;
+    double s = 0.0, q = 0.0;
+    for (int r = 0; r < a.R; ++r) { s += a.partial[((long)i * a.R + r) * 2]; q += a.partial[((long)i * a.R + r) * 2 + 1]; }
+    const double m = (double)a.P * a.cpg, mean = s / m;
+    const double var = fmax(q / m - mean * mean, 0.0);
+    a.stats[2 * i] = mean;
+    a.stats[2 * i + 1] = 1.0 / sqrt(var + 1e-5);
+}
+
+__global__ __launch_bounds__(256) void d3_gn_apply_kernel(D3GnArgs a) {
+    const long total4 = (long)a.N * a.P * a.C / 4, pc4 = a.P * a.C / 4;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < total4; i += gridDim.x * 256L) {
+        const int n = (int)(i / pc4), c = (int)((i * 4) % a.C);
+        const float4 xv = *reinterpret_cast<const float4*>(a.x + 4 * i);
+        const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
+        float ys[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const double* st = a.stats + ((long)n * D3_GROUPS + (c + j) / a.cpg) * 2;
+            ys[j] = fmaf((float)(((double)xs[j] - st[0]) * st[1]), a.weight[c + j], a.bias[c + j]);
+        }
+        if (a.res) {
+            const float4 rv = *reinterpret_cast<const float4*>(a.res + 4 * i);
+            ys[0] += rv.x; ys[1] += rv.y; ys[2] += rv.z; ys[3] += rv.w;
+        }
+        if (a.relu) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) ys[j] = ys[j] > 0.f ? ys[j] : 0.f;
+        }
+        *reinterpret_cast<float4*>(a.out + 4 * i) = make_float4(ys[0], ys[1], ys[2], ys[3]);
+    }
+}
+
+// per (sample, channel) over a slice of the positions: sum of dy and of dy * xhat, dy = g [mask > 0]; 16 channels x 16 rows per workgroup
+__global__ __launch_bounds__(256) void d3_gn_bwd_partial_kernel(D3GnArgs a) {
+    __shared__ double red[2][256];
+    const int tid = threadIdx.x, c = blockIdx.x * 16 + (tid & 15), n = blockIdx.y, r = blockIdx.z;
+    const long p0 = r * a.rows_per, p1 = p0 + a.rows_per < a.P ? p0 + a.rows_per : a.P;
+    const double* st = a.stats + ((long)n * D3_GROUPS + c / a.cpg) * 2;
+    const double mean = st[0], rstd = st[1];
+    double s1 = 0.0, s2 = 0.0;
+    for (long p = p0 + (tid >> 4); p < p1; p += 16) {
+        const long o = ((long)n * a.P + p) * a.C + c;
+        float dy = a.g[o];
+        if (a.mask) dy = a.mask[o] > 0.f ? dy : 0.f;
+        s1 += (double)dy;
+        s2 += (double)dy * (((double)a.x[o] - mean) * rstd);
+    }
+    red[0][tid] = s1; red[1][tid] = s2;
+    __syncthreads();
+    if (tid >= 16) return;
+    double t1 = 0.0, t2 = 0.0;
+    for (int j = 0; j < 16; ++j) { t1 += red[0][j * 16 + tid]; t2 += red[1][j * 16 + tid]; }
+    double* dst = a.partial + (((long)n * a.R + r) * a.C + c) * 2;
+    dst[0] = t1; dst[1] = t2;
+}
+
+// one workgroup per sample: the slices in slice order -> ab [n][c]; then per group sum of weight * ab -> gs [n][group]
+__global__ __launch_bounds__(256) void d3_gn_bwd_reduce_kernel(D3GnArgs a) {
+    const int n = blockIdx.x, tid = threadIdx.x;
+    for (int c = tid; c < a.C; c += 256) {
+        double t1 = 0.0, t2 = 0.0;
+        for (int r = 0; r < a.R; ++r) {
+            const double* src = a.partial + (((long)n * a.R + r) * a.C + c) * 2;
+            t1 += src[0]; t2 += src[1];
+        }
+        a.ab[((long)n * a.C + c) * 2] = t1;
+        a.ab[((long)n * a.C + c) * 2 + 1] = t2;
+    }
+    __syncthreads();
+    if (tid < D3_GROUPS) {
+        double s1 = 0.0, s2 = 0.0;
+        for (int j = 0; j < a.cpg; ++j) {
+            const int c = tid * a.cpg + j;
+            const double w = (double)a.weight[c];
+            s1 += w * a.ab[((long)n * a.C + c) * 2];
+            s2 += w * a.ab[((long)n * a.C + c) * 2 + 1];
+        }
+        a.gs[((long)n * D3_GROUPS + tid) * 2] = s1;
+        a.gs[((long)n * D3_GROUPS + tid) * 2 + 1] = s2;
+    }
+}
+
+__global__ __launch_bounds__(256) void d3_gn_bwd_param_kernel(D3GnArgs a) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= a.C) return;
+    double t1 = 0.0, t2 = 0.0;
+    for (int n = 0; n < a.N; ++n) { t1 += a.ab[((long)n * a.C + c) * 2]; t2 += a.ab[((long)n * a.C + c) * 2 + 1]; }
+    a.dbias[c] = a.accumulate ? a.dbias[c] + (float)t1 : (float)t1;
+    a.dweight[c] = a.accumulate ? a.dweight[c] + (float)t2 : (float)t2;
+}
+
+// dx = rstd (dy w - s1 / m - xhat s2 / m)
+__global__ __launch_bounds__(256) void d3_gn_bwd_dx_kernel(D3GnArgs a) {
+    const long total = (long)a.N * a.P * a.C, pc = a.P * a.C;
+    const double inv_m = 1.0 / ((double)a.P * a.cpg);
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += gridDim.x * 256L) {
+        const int n = (int)(i / pc), c = (int)(i % a.C), grp = c / a.cpg;
+        const double* st = a.stats + ((long)n * D3_GROUPS + grp) * 2;
+        const double* gs = a.gs + ((long)n * D3_GROUPS + grp) * 2;
+        float dy = a.g[i];
+        if (a.mask) dy = a.mask[i] > 0.f ? dy : 0.f;
+        const double xhat = ((double)a.x[i] - st[0]) * st[1];
+        a.out[i] = (float)(st[1] * ((double)dy * (double)a.weight[c] - gs[0] * inv_m - xhat * gs[1] * inv_m));
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------ max pool
+// MaxPool3d(3, stride (1, 2, 2), pad 1); the first maximum in (t, h, w) scan order wins
+__global__ __launch_bounds__(256) void d3_maxpool_kernel(const float* __restrict__ x, float* __restrict__ out, int* __restrict__ arg, long total, int T,
+                                                         int H, int W, int Ho, int Wo, int C) {
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += gridDim.x * 256L) {
+        const int c = (int)(i % C);
+        long p = i / C;
+        const int wo = (int)(p % Wo); p /= Wo;
+        const int ho = (int)(p % Ho); p /= Ho;
+        const int to = (int)(p % T); p /= T;
+        float best = 0.f;
+        int bi = -1;
+        for (int dt = -1; dt <= 1; ++dt) {
+            const int t = to + dt;
+            if ((unsigned)t >= (unsigned)T) continue;
+            for (int dh = -1; dh <= 1; ++dh) {
+                const int h = 2 * ho + dh;
+                if ((unsigned)h >= (unsigned)H) continue;
+                for (int dw = -1; dw <= 1; ++dw) {
+                    const int w = 2 * wo + dw;
+                    if ((unsigned)w >= (unsigned)W) continue;
+                    const int idx = (t * H + h) * W + w;
+                    const float v = x[(p * (long)T * H * W + idx) * C + c];
+                    if (bi < 0 || v > best) { best = v; bi = idx; }
+                }
+            }
+        }
+        out[i] = best;
+        arg[i] = bi;
+    }
+}
+
+// a gather: the windows overlap, so an input sums the gradients of the windows that chose it, in the windows' scan order
+__global__ __launch_bounds__(256) void d3_maxpool_bwd_kernel(const float* __restrict__ g, const int* __restrict__ arg, float* __restrict__ dx, long total,
+                                                             int T, int H, int W, int Ho, int Wo, int C) {
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += gridDim.x * 256L) {
+        const int c = (int)(i % C);
+        long p = i / C;
+        const int w = (int)(p % W); p /= W;
+        const int h = (int)(p % H); p /= H;
+        const int t = (int)(p % T); p /= T;
+        const int idx = (t * H + h) * W + w;
+        const int ho0 = h / 2, ho1 = (h + 1) / 2, wo0 = w / 2, wo1 = (w + 1) / 2;   // 2 o - 1 <= i <= 2 o + 1
+        float acc = 0.f;
+        for (int to = t - 1; to <= t + 1; ++to) {
+            if ((unsigned)to >= (unsigned)T) continue;
+            for (int ho = ho0; ho <= ho1 && ho < Ho; ++ho)
+                for (int wo = wo0; wo <= wo1 && wo < Wo; ++wo) {
+                    const long o = (((p * T + to) * Ho + ho) * Wo + wo) * C + c;
+                    if (arg[o] == idx) acc += g[o];
+                }
+        }
+        dx[i] = acc;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------ head
+// AvgPool3d((1, 4, 4)) over the [1, 4, 4] map, then fc: one workgroup per sample
+__global__ __launch_bounds__(256) void d3_head_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w, float* __restrict__ pred, int C) {
+    __shared__ double red[256];
+    const int n = blockIdx.x;
+    double acc = 0.0;
+    for (int c = threadIdx.x; c < C; c += 256) {
+        float s = 0.f;
+        for (int p = 0; p < 16; ++p) s += x[((long)n * 16 + p) * C + c];
+        acc += (double)(s * 0.0625f) * (double)w[c];
+    }
+    acc = block_sum(acc, red);
+    if (threadIdx.x == 0) pred[n] = (float)acc;
+}
+
+// thread = channel: dx [n][16][c] = g[n] w[c] / 16; dweight[c] = sum over n (in order) of g[n] * pooled[n][c]
+__global__ __launch_bounds__(256) void d3_head_bwd_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ g,
+                                                          float* __restrict__ dx, float* __restrict__ dw, int N, int C, int accumulate) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    const float wc = w[c] * 0.0625f;
+    double acc = 0.0;
+    for (int n = 0; n < N; ++n) {
+        float s = 0.f;
+        for (int p = 0; p < 16; ++p) {
+            s += x[((long)n * 16 + p) * C + c];
+            if (dx) dx[((long)n * 16 + p) * C + c] = g[n] * wc;
+        }
+        acc += (double)g[n] * (double)(s * 0.0625f);
+    }
+    if (dw) dw[c] = accumulate ? dw[c] + (float)acc : (float)acc;
+}
+
+// ------------------------------------------------------------------------------------------------------------------ feature-map loss
+__global__ __launch_bounds__(256) void d3_fmap_partial_kernel(const float* __restrict__ x, const float* __restrict__ y, long n, int metric, float coef,
+                                                              float* __restrict__ dx, double* __restrict__ partial) {
+    __shared__ double red[256];
+    double s = 0.0;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += gridDim.x * 256L) {
+        const float d = x[i] - y[i];
+        if (metric == I2V_FMAP_L1) {
+            s += (double)fabsf(d);
+            if (dx) dx[i] = d > 0.f ? coef : d < 0.f ? -coef : 0.f;
+        } else {
+            s += (double)d * (double)d;
+            if (dx) dx[i] = 2.f * d * coef;
+        }
+    }
+    s = block_sum(s, red);
+    if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+struct D3FmapFinal { long numel[4]; int nblk[4]; int nl; };
+__global__ void d3_fmap_final_kernel(D3FmapFinal f, const double* __restrict__ partial, double* __restrict__ out) {
+    if (threadIdx.x != 0) return;
+    double total = 0.0;
+    for (int l = 0; l < f.nl; ++l) {
+        double s = 0.0;
+        for (int b = 0; b < f.nblk[l]; ++b) s += partial[l * D3_FMAP_BLOCKS + b];
+        out[1 + l] = s / (double)f.numel[l];
+        total += out[1 + l];
+    }
+    for (int l = f.nl; l < 4; ++l) out[1 + l] = 0.0;
+    out[0] = total / (double)f.nl;
+}
+
+__global__ __launch_bounds__(256) void d3_sumsq_kernel(const float* __restrict__ x, long per, double* __restrict__ out) {
+    __shared__ double red[256];
+    const float* s = x + blockIdx.x * per;
+    double q = 0.0;
+    for (long i = threadIdx.x; i < per; i += 256) q += (double)s[i] * (double)s[i];
+    q = block_sum(q, red);
+    if (threadIdx.x == 0) out[blockIdx.x] = q;
+}
+
+// =================================================================================================================== host side
+int bn_of(int c) { return c % 64 == 0 ? 64 : c % 32 == 0 ? 32 : 16; }
+// rows per workgroup of the two GEMM kernels: 128, or 64 where 128 would leave the device's compute units without two workgroups each
+// (a function of the shape alone: the same shape always runs the same kernel)
+int rows_of(long rows, int column_tiles) { return (rows + 127) / 128 * column_tiles >= 512 ? 128 : 64; }
+
+int ntap_of(const D3Conv& c) { return 3 * c.kh * c.kw; }
+
+D3Conv make_conv(int cin, int cout, bool stem, int st, int ss, int sn) {
+    return D3Conv{cin, cin == 3 ? 4 : cin, cin == 3 ? 16 : cin, cout, stem ? 7 : 3, stem ? 7 : 3, st, ss, sn};
+}
+int out_extent(int n, int k, int s) { return n + 2 * (k / 2) - k < 0 ? 0 : (n + 2 * (k / 2) - k) / s + 1; }
+D3Geo make_geo(int n, int ti, int hi, int wi, const D3Conv& c) {
+    D3Geo m{};
+    m.ti = ti; m.hi = hi; m.wi = wi;
+    m.to = out_extent(ti, 3, c.st); m.ho = out_extent(hi, c.kh, c.ss); m.wo = out_extent(wi, c.kw, c.ss);
+    m.mi = (long)n * ti * hi * wi; m.mo = (long)n * m.to * m.ho * m.wo;
+    return m;
+}
+size_t pack_elems(const D3Conv& c) { return (size_t)c.cout * c.cind * ntap_of(c); }
+
+// the slice plan of the weight gradient: enough workgroups to fill the device, slices of at least 64 positions
+void d3_wgrad_plan(int cout, int cin, int ntap, long P, int* slices, int* slice_len) {
+    const int CP = (int)align_up(cin == 3 ? 4 : cin, 16);
+    const long tiles = (long)ntap * (cout / bn_of(cout)) * (CP / bn_of(CP));
+    const long S = std::min<long>(std::max<long>((1024 + tiles - 1) / tiles, 1), std::max<long>((P + 63) / 64, 1));
+    const long L = (long)align_up((size_t)((P + S - 1) / S), 16);
+    *slice_len = (int)L;
+    *slices = (int)((P + L - 1) / L);
+}
+
+int launch_conv(const D3Conv& c, const float* in, const float* wf, float* out, const D3Geo& mp, hipStream_t st) {
+    D3ConvArgs a{};
+    a.in = in; a.wf = wf; a.out = out;
+    a.M = mp.mo; a.Ti = mp.ti; a.Hi = mp.hi; a.Wi = mp.wi; a.To = mp.to; a.Ho = mp.ho; a.Wo = mp.wo;
+    a.cinp = c.cinp; a.C4 = c.cinp / 4; a.ntap = ntap_of(c); a.nchunk = (a.ntap * a.C4 + 3) / 4; a.kh = c.kh; a.kw = c.kw; a.st = c.st; a.ss = c.ss;
+    a.cout = c.cout;
+    const int BN = bn_of(c.cout);
+    const int BM = rows_of(a.M, c.cout / BN);
+    const long nblk = (a.M + BM - 1) / BM * (c.cout / BN);
+    I2V_REQUIRE(nblk > 0 && nblk < (1L << 31), I2V_E_INVALID, "temporal discriminator: conv grid of %ld workgroups", nblk);
+    const dim3 grid((unsigned)nblk);
+    if (BM == 128) {
+        if (BN == 64) hipLaunchKernelGGL((d3_conv_kernel<4, 2>), grid, dim3(256), 0, st, a);
+        else if (BN == 32) hipLaunchKernelGGL((d3_conv_kernel<2, 2>), grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((d3_conv_kernel<1, 2>), grid, dim3(256), 0, st, a);
+    } else {
+        if (BN == 64) hipLaunchKernelGGL((d3_conv_kernel<4, 1>), grid, dim3(256), 0, st, a);
+        else if (BN == 32) hipLaunchKernelGGL((d3_conv_kernel<2, 1>), grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((d3_conv_kernel<1, 1>), grid, dim3(256), 0, st, a);
+    }
+    PD_LAUNCHED();
+    return I2V_OK;
+}
+
+int launch_dgrad(const D3Conv& c, const float* g, const float* act, const float* wd, const float* add, const float* add_mask, float* out, bool frames,
+                 int N, const D3Geo& mp, hipStream_t st) {
+    D3DgradArgs a{};
+    a.g = g; a.act = act; a.wd = wd; a.add = add; a.add_mask = add_mask; a.out = out;
+    a.N = N; a.Ti = mp.ti; a.Hi = mp.hi; a.Wi = mp.wi; a.To = mp.to; a.Ho = mp.ho; a.Wo = mp.wo;
+    a.cout = c.cout; a.C4o = c.cout / 4; a.kh = c.kh; a.kw = c.kw; a.st = c.st; a.ss = c.ss;
+    a.cin = c.cin == 3 && !frames ? 4 : c.cin; a.cind = c.cind; a.frames = frames ? 1 : 0;
+    const int BN = bn_of(c.cind);
+    const int classes = c.st * c.ss * c.ss;
+    const long mc = (long)N * ((mp.ti + c.st - 1) / c.st) * ((mp.hi + c.ss - 1) / c.ss) * ((mp.wi + c.ss - 1) / c.ss);   // the largest parity class
+    const int BM = rows_of(mc * classes, c.cind / BN);
+    const long nblk = (mc + BM - 1) / BM * (c.cind / BN);
+    I2V_REQUIRE(nblk > 0 && nblk < (1L << 31), I2V_E_INVALID, "temporal discriminator: dgrad grid of %ld workgroups", nblk);
+    const dim3 grid((unsigned)nblk, classes);
+    if (BM == 128) {
+        if (BN == 64) hipLaunchKernelGGL((d3_dgrad_kernel<4, 2>), grid, dim3(256), 0, st, a);
+        else if (BN == 32) hipLaunchKernelGGL((d3_dgrad_kernel<2, 2>), grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((d3_dgrad_kernel<1, 2>), grid, dim3(256), 0, st, a);
+    } else {
+        if (BN == 64) hipLaunchKernelGGL((d3_dgrad_kernel<4, 1>), grid, dim3(256), 0, st, a);
+        else if (BN == 32) hipLaunchKernelGGL((d3_dgrad_kernel<2, 1>), grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((d3_dgrad_kernel<1, 1>), grid, dim3(256), 0, st, a);
+    }
+    PD_LAUNCHED();
+    return I2V_OK;
+}
+
+template <int MT>
+void launch_wgrad_nt(int nt, dim3 grid, hipStream_t st, const D3WgradArgs& a) {
+    if (nt == 4) hipLaunchKernelGGL((d3_wgrad_kernel<MT, 4>), grid, dim3(256), 0, st, a);
+    else if (nt == 2) hipLaunchKernelGGL((d3_wgrad_kernel<MT, 2>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((d3_wgrad_kernel<MT, 1>), grid, dim3(256), 0, st, a);
+}
+
+size_t wgrad_part_floats(const D3Conv& c, long P) {
+    int S, L;
+    d3_wgrad_plan(c.cout, c.cin, ntap_of(c), P, &S, &L);
+    return (size_t)S * ntap_of(c) * c.cout * align_up(c.cinp, 16);
+}
+size_t finish_blocks(const D3Conv& c) { return ((size_t)c.cout * c.cin * ntap_of(c) + 255) / 256; }
+
+// partial sums -> dwn -> grad (written or accumulated)
+int launch_wgrad(const D3Conv& c, const float* g, const float* act, const float* x, const float* w, const float* u, const float* v, const float* sigma,
+                 float* part, float* dwn, double* dotp, float* grad, bool accumulate, const D3Geo& mp, hipStream_t st) {
+    int S, L;
+    const int ntap = ntap_of(c);
+    d3_wgrad_plan(c.cout, c.cin, ntap, mp.mo, &S, &L);
+    D3WgradArgs a{};
+    a.g = g; a.act = act; a.x = x; a.part = part; a.P = mp.mo;
+    a.Ti = mp.ti; a.Hi = mp.hi; a.Wi = mp.wi; a.To = mp.to; a.Ho = mp.ho; a.Wo = mp.wo; a.cinp = c.cinp; a.cout = c.cout; a.CP = (int)align_up(c.cinp, 16);
+    a.kh = c.kh; a.kw = c.kw; a.st = c.st; a.ss = c.ss; a.slice_len = L;
+    const int mt = bn_of(c.cout) / 16, nt = bn_of(a.CP) / 16;
+    const dim3 grid((unsigned)((c.cout / (16 * mt)) * (a.CP / (16 * nt))), ntap, (unsigned)S);
+    if (mt == 4) launch_wgrad_nt<4>(nt, grid, st, a);
+    else if (mt == 2) launch_wgrad_nt<2>(nt, grid, st, a);
+    else launch_wgrad_nt<1>(nt, grid, st, a);
+    PD_LAUNCHED();
+    D3FinishArgs f{};
+    f.part = part; f.w = w; f.u = u; f.v = v; f.sigma = sigma; f.dwn = dwn; f.dotp = dotp; f.grad = grad;
+    f.E = (long)c.cout * c.cin * ntap; f.S = S; f.cout = c.cout; f.cin = c.cin; f.CP = a.CP; f.ntap = ntap; f.nblk = (int)finish_blocks(c);
+    f.accumulate = accumulate ? 1 : 0;
+    hipLaunchKernelGGL(d3_finish_a_kernel, dim3(f.nblk), dim3(256), 0, st, f);
+    PD_LAUNCHED();
+    if (sigma) {
+        hipLaunchKernelGGL(d3_finish_dot_kernel, dim3(1), dim3(256), 0, st, f);
+        PD_LAUNCHED();
+    }
+    hipLaunchKernelGGL(d3_finish_b_kernel, dim3(f.nblk), dim3(256), 0, st, f);
+    PD_LAUNCHED();
+    return I2V_OK;
+}
+
+// GroupNorm scratch: `partial` serves the forward's statistics ([N][16][R][2]) and the backward's channel sums ([N][R][C][2])
+struct D3GnWs { size_t partial, ab, gs, total; };
+D3GnWs gn_ws(int n, int c) {
+    Carver k;
+    D3GnWs y{};
+    y.partial = k.take_bytes((size_t)n * D3_GN_SLICES * std::max(c, D3_GROUPS) * 2 * 8);
+    y.ab = k.take_bytes((size_t)n * c * 2 * 8);
+    y.gs = k.take_bytes((size_t)n * D3_GROUPS * 2 * 8);
+    y.total = k.total();
+    return y;
+}
+int gn_slices(long P, int per_row) { return (int)std::min<long>(std::max<long>(P * per_row / 4096, 1), D3_GN_SLICES); }
+
+int launch_gn(const float* x, const float* res, const float* weight, const float* bias, int N, long P, int C, bool relu, float* out, double* stats,
+              void* ws, hipStream_t st) {
+    const D3GnWs k = gn_ws(N, C);
+    D3GnArgs a{};
+    a.x = x; a.res = res; a.weight = weight; a.bias = bias; a.out = out; a.stats = stats; a.partial = Carver::at<double>(ws, k.partial);
+    a.P = P; a.N = N; a.C = C; a.cpg = C / D3_GROUPS; a.R = gn_slices(P, a.cpg); a.rows_per = (P + a.R - 1) / a.R; a.relu = relu ? 1 : 0;
+    hipLaunchKernelGGL(d3_gn_stats_kernel, dim3(D3_GROUPS, N, a.R), dim3(256), 0, st, a);
+    PD_LAUNCHED();
+    hipLaunchKernelGGL(d3_gn_stats_final_kernel, dim3((N * D3_GROUPS + 255) / 256), dim3(256), 0, st, a);
+    PD_LAUNCHED();
+    hipLaunchKernelGGL(d3_gn_apply_kernel, dim3(grid_for((long)N * P * C / 4)), dim3(256), 0, st, a);
+    PD_LAUNCHED();
+    return I2V_OK;
+}
+
+int launch_gn_bwd(const float* g, const float* mask, const float* x, const double* stats, const float* weight, int N, long P, int C, float* dx,
+                  float* dweight, float* dbias, bool accumulate, void* ws, hipStream_t st) {
+    const D3GnWs k = gn_ws(N, C);
+    D3GnArgs a{};
+    a.g = g; a.mask = mask; a.x = x; a.stats = const_cast<double*>(stats); a.weight = weight; a.out = dx; a.dweight = dweight; a.dbias = dbias;
+    a.partial = Carver::at<double>(ws, k.partial); a.ab = Carver::at<double>(ws, k.ab); a.gs = Carver::at<double>(ws, k.gs);
+    a.P = P; a.N = N; a.C = C; a.cpg = C / D3_GROUPS; a.R = gn_slices(P, 16); a.rows_per = (P + a.R - 1) / a.R; a.accumulate = accumulate ? 1 : 0;
+    hipLaunchKernelGGL(d3_gn_bwd_partial_kernel, dim3(C / 16, N, a.R), dim3(256), 0, st, a);
+    PD_LAUNCHED();
+    hipLaunchKernelGGL(d3_gn_bwd_reduce_kernel, dim3(N), dim3(256), 0, st, a);
+    PD_LAUNCHED();
+    if (dweight) {
+        hipLaunchKernelGGL(d3_gn_bwd_param_kernel, dim3((C + 255) / 256), dim3(256), 0, st, a);
+        PD_LAUNCHED();
+    }
+    hipLaunchKernelGGL(d3_gn_bwd_dx_kernel, dim3(grid_for((long)N * P * C)), dim3(256), 0, st, a);
+    PD_LAUNCHED();
+    return I2V_OK;
+}
+
+}  // namespace
+}  // namespace i2v
+
+using namespace i2v;
+
+struct D3Block { int c1, c2, cd, in; };   // conv indices (cd -1: no downsample branch); in: the conv whose activation enters (-1: the pool's output)
+
+struct i2v_disc3d {
+    int device = 0;
+    bool loaded = false;   // parameters bound
+    bool have_grads = false;
+    int nconv = 0, pool = 0, sn = 0;
+    D3Conv L[D3_MAXCONV];
+    std::string wkey[D3_MAXCONV], nkey[D3_MAXCONV];   // state-dict prefixes of the conv and of its GroupNorm
+    D3Block B[8];
+    float *w[D3_MAXCONV] = {}, *u[D3_MAXCONV] = {}, *v[D3_MAXCONV] = {}, *nw[D3_MAXCONV] = {}, *nb[D3_MAXCONV] = {}, *fc = nullptr;
+    float *gw[D3_MAXCONV] = {}, *gnw[D3_MAXCONV] = {}, *gnb[D3_MAXCONV] = {}, *gfc = nullptr;
+};
+
+namespace {
+
+// Where everything lies for one input shape: `saved` (offsets from its base) and the workspace
+struct D3Layout {
+    bool ok = false;
+    char why[160] = "";
+    D3Geo geo[D3_MAXCONV];
+    int pt = 0, ph = 0, pw = 0, pho = 0, pwo = 0;   // the pool's input and output map
+    long pool_in = 0, pool_out = 0;                 // positions
+    size_t x4 = 0, pre[D3_MAXCONV] = {}, act[D3_MAXCONV] = {}, stats[D3_MAXCONV] = {}, wf[D3_MAXCONV] = {}, wd[D3_MAXCONV] = {}, sigma[D3_MAXCONV] = {},
+           us[D3_MAXCONV] = {}, vs[D3_MAXCONV] = {}, pout = 0, parg = 0, saved_total = 0;
+    size_t pi_t[D3_MAXCONV] = {}, pi_s[D3_MAXCONV] = {}, fwd = 0, gbuf[4] = {}, dc[2] = {}, part = 0, dwn = 0, dotp = 0, gn = 0, ws_total = 0;
+};
+
+D3Layout d3_layout(const i2v_disc3d* d, int n, int t, int h, int w) {
+    D3Layout y;
+    if (n <= 0 || t <= 0 || h <= 0 || w <= 0) {
+        snprintf(y.why, sizeof y.why, "batch %d, clip %d x %d x %d", n, t, h, w);
+        return y;
+    }
+    // the maps, conv by conv
+    y.geo[0] = make_geo(n, t, h, w, d->L[0]);
+    int ct = y.geo[0].to, chh = y.geo[0].ho, cw = y.geo[0].wo;
+    if (d->pool && ct > 0 && chh > 0 && cw > 0) {
+        y.pt = ct; y.ph = chh; y.pw = cw; y.pho = (chh - 1) / 2 + 1; y.pwo = (cw - 1) / 2 + 1;
+        y.pool_in = (long)n * ct * chh * cw; y.pool_out = (long)n * ct * y.pho * y.pwo;
+        chh = y.pho; cw = y.pwo;
+    }
+    for (int b = 0; b < 8; ++b) {
+        const D3Block& k = d->B[b];
+        if (ct < 1 || chh < 1 || cw < 1) break;
+        y.geo[k.c1] = make_geo(n, ct, chh, cw, d->L[k.c1]);
+        if (k.cd >= 0) y.geo[k.cd] = make_geo(n, ct, chh, cw, d->L[k.cd]);
+        ct = y.geo[k.c1].to; chh = y.geo[k.c1].ho; cw = y.geo[k.c1].wo;
+        y.geo[k.c2] = make_geo(n, ct, chh, cw, d->L[k.c2]);
+    }
+    if (ct != 1 || chh != 4 || cw != 4) {
+        snprintf(y.why, sizeof y.why, "a clip of %d frames of %d x %d ends on a [%d, %d, %d] map, not on the [1, 4, 4] that fc takes", t, h, w, ct, chh, cw);
+        return y;
+    }
+    Carver s;
+    y.x4 = s.take_floats((size_t)y.geo[0].mi * 4);
+    size_t gmax = 0, pmax = 0, emax = 0, bmax = 0, cmax = 0;
+    for (int i = 0; i < d->nconv; ++i) {
+        const D3Conv& c = d->L[i];
+        const size_t elems = (size_t)y.geo[i].mo * c.cout;
+        y.pre[i] = s.take_floats(elems);
+        y.act[i] = s.take_floats(elems);
+        y.stats[i] = s.take_bytes((size_t)n * D3_GROUPS * 2 * 8);
+        y.wf[i] = s.take_floats((size_t)ntap_of(c) * c.cout * c.cinp);
+        y.wd[i] = s.take_floats(pack_elems(c));
+        y.sigma[i] = s.take_floats(c.sn ? 1 : 0);
+        y.us[i] = s.take_floats(c.sn ? c.cout : 0);
+        y.vs[i] = s.take_floats(c.sn ? (size_t)c.cin * ntap_of(c) : 0);
+        gmax = std::max(gmax, std::max(elems, (size_t)y.geo[i].mi * c.cinp));
+        pmax = std::max(pmax, wgrad_part_floats(c, y.geo[i].mo));
+        emax = std::max(emax, (size_t)c.cout * c.cin * ntap_of(c));
+        bmax = std::max(bmax, finish_blocks(c));
+        cmax = std::max(cmax, (size_t)c.cout);
+    }
+    if (d->pool) {
+        y.pout = s.take_floats((size_t)y.pool_out * d->L[0].cout);
+        y.parg = s.take_floats((size_t)y.pool_out * d->L[0].cout);
+    }
+    y.saved_total = s.total();
+    Carver k;
+    for (int i = 0; i < d->nconv; ++i) {
+        y.pi_t[i] = k.take_bytes(d->L[i].sn ? (size_t)d->L[i].cin * ntap_of(d->L[i]) * 8 : 0);
+        y.pi_s[i] = k.take_bytes(d->L[i].sn ? (size_t)d->L[i].cout * 8 : 0);
+    }
+    y.fwd = k.take_bytes(y.saved_total);
+    for (int i = 0; i < 4; ++i) y.gbuf[i] = k.take_floats(gmax);
+    for (int i = 0; i < 2; ++i) y.dc[i] = k.take_floats(gmax);
+    y.part = k.take_floats(pmax);
+    y.dwn = k.take_floats(emax);
+    y.dotp = k.take_bytes((bmax + 1) * 8);
+    y.gn = k.take_bytes(gn_ws(n, (int)cmax).total);
+    y.ws_total = k.total();
+    y.ok = true;
+    return y;
+}
+
+int refuse(const char* what, const D3Layout& y) {
+    set_error("%s: %s", what, y.why);
+    return I2V_E_INVALID;
+}
+
+int check_unit(const char* what, int n, int ti, int hi, int wi, int cin, int cout, int stem, int st, int ss) {
+    I2V_REQUIRE(n > 0 && ti >= 1 && hi >= 1 && wi >= 1 && (st == 1 || st == 2) && (ss == 1 || ss == 2), I2V_E_INVALID,
+                "%s: n %d, map %d x %d x %d, strides %d, %d", what, n, ti, hi, wi, st, ss);
+    I2V_REQUIRE((stem ? cin == 3 : (cin > 0 && cin % 16 == 0)) && cout > 0 && cout % 16 == 0, I2V_E_INVALID,
+                "%s: cin %d (a multiple of 16; the stem: 3), cout %d (a multiple of 16)", what, cin, cout);
+    return I2V_OK;
+}
+
+// workspace of the unit entries
+struct D3UnitWs { size_t wf, wd, part, dwn, dotp, total; };
+D3UnitWs unit_ws(int n, int ti, int hi, int wi, int cin, int cout, int stem) {
+    const D3Conv c = make_conv(cin, cout, stem, 1, 1, 0);
+    const D3Geo m = make_geo(n, ti, hi, wi, c);   // stride 1 has the most positions
+    Carver k;
+    D3UnitWs y{};
+    y.wf = k.take_floats((size_t)ntap_of(c) * cout * c.cinp);
+    y.wd = k.take_floats(pack_elems(c));
+    y.part = k.take_floats(wgrad_part_floats(c, std::max<long>(m.mo, 1)) * 2);   // (a strided conv has fewer positions but may plan other slices)
+    y.dwn = k.take_floats((size_t)cout * cin * ntap_of(c));
+    y.dotp = k.take_bytes((finish_blocks(c) + 1) * 8);
+    y.total = k.total();
+    return y;
+}
+
+int pack_unit(const D3Conv& c, const float* weight, float* wf, float* wd, hipStream_t st) {
+    D3PackArgs p{};
+    p.nconv = 1; p.total = (long)pack_elems(c);
+    p.c[0] = D3PackConv{weight, nullptr, wf, wd, c.cout, c.cin, c.cinp, c.cind, ntap_of(c), 0};
+    hipLaunchKernelGGL(d3_pack_kernel, dim3(grid_for(p.total)), dim3(256), 0, st, p);
+    PD_LAUNCHED();
+    return I2V_OK;
+}
+
+bool bound_ptr(const StateDict& s, const std::string& key, int64_t numel, float** out) {
+    const float* p = s.f32(key, numel);
+    *out = const_cast<float*>(p);
+    return p != nullptr;
+}
+
+}  // namespace
+
+extern "C" {
+
+int i2v_disc3d_create(const i2v_disc3d_cfg* cfg, i2v_disc3d** out) {
+    const char* what = "i2v_disc3d_create";
+    I2V_REQUIRE(cfg && out, I2V_E_INVALID, "%s: null argument", what);
+    I2V_REQUIRE(cfg->res_type == 18, I2V_E_INVALID, "%s: res type %d (only resnet18 is built)", what, cfg->res_type);
+    for (int i = 0; i < 5; ++i)
+        I2V_REQUIRE(cfg->channels[i] > 0 && cfg->channels[i] % 16 == 0, I2V_E_INVALID, "%s: channels[%d] = %d is not a positive multiple of 16", what, i,
+                    cfg->channels[i]);
+    for (int i = 0; i < 4; ++i)
+        I2V_REQUIRE((cfg->stride_s[i] == 1 || cfg->stride_s[i] == 2) && (cfg->stride_t[i] == 1 || cfg->stride_t[i] == 2), I2V_E_INVALID,
+                    "%s: layer %d has strides (t %d, s %d) outside {1, 2}", what, i, cfg->stride_t[i], cfg->stride_s[i]);
+    const i2v_disc3d_cfg c = *cfg;
+    return create_handle(what, out, [c](i2v_disc3d* d) {
+        d->pool = c.use_max_pool ? 1 : 0;
+        d->sn = c.spectral_norm ? 1 : 0;
+        int k = 0;
+        d->L[k] = make_conv(3, c.channels[0], true, 1, 2, 0);
+        d->wkey[k] = "conv1"; d->nkey[k] = "norm1";
+        ++k;
+        int inplanes = c.channels[0], prev = d->pool ? -1 : 0;
+        for (int l = 0; l < 4; ++l) {
+            const int planes = c.channels[l + 1], ss = c.stride_s[l], st = c.stride_t[l];
+            const std::string p0 = "layer." + std::to_string(l) + ".0.", p1 = "layer." + std::to_string(l) + ".1.";
+            D3Block b0{}, b1{};
+            b0.in = prev;
+            b0.c1 = k; d->L[k] = make_conv(inplanes, planes, false, st, ss, d->sn); d->wkey[k] = p0 + "conv1"; d->nkey[k] = p0 + "bn1"; ++k;
+            b0.c2 = k; d->L[k] = make_conv(planes, planes, false, 1, 1, d->sn); d->wkey[k] = p0 + "conv2"; d->nkey[k] = p0 + "bn2"; ++k;
+            b0.cd = -1;
+            if (ss != 1 || inplanes != planes || st != 1) {   // resnet3D.py:265: the discriminator's rule has the stride_t term
+                b0.cd = k; d->L[k] = make_conv(inplanes, planes, false, st, ss, 1); d->wkey[k] = p0 + "downsample.0"; d->nkey[k] = p0 + "downsample.1"; ++k;
+            }
+            b1.in = b0.c2;
+            b1.c1 = k; d->L[k] = make_conv(planes, planes, false, 1, 1, 0); d->wkey[k] = p1 + "conv1"; d->nkey[k] = p1 + "bn1"; ++k;
+            b1.c2 = k; d->L[k] = make_conv(planes, planes, false, 1, 1, 0); d->wkey[k] = p1 + "conv2"; d->nkey[k] = p1 + "bn2"; ++k;
+            b1.cd = -1;
+            d->B[2 * l] = b0; d->B[2 * l + 1] = b1;
+            prev = b1.c2;
+            inplanes = planes;
+        }
+        d->nconv = k;
+        return I2V_OK;
+    });
+}
+
+void i2v_disc3d_destroy(i2v_disc3d* d) { delete d; }
+
+int i2v_disc3d_bind(i2v_disc3d* d, const i2v_tensor* params, int32_t n) {
+    I2V_REQUIRE(d && params && n > 0, I2V_E_INVALID, "i2v_disc3d_bind: null argument");
+    d->loaded = false;
+    const StateDict sd(params, n);
+    for (int i = 0; i < d->nconv; ++i) {
+        const D3Conv& c = d->L[i];
+        const int64_t wn = (int64_t)c.cout * c.cin * ntap_of(c);
+        if (!bound_ptr(sd, d->wkey[i] + (c.sn ? ".weight_orig" : ".weight"), wn, &d->w[i])) return I2V_E_MISSING;
+        if (c.sn && (!bound_ptr(sd, d->wkey[i] + ".weight_u", c.cout, &d->u[i]) || !bound_ptr(sd, d->wkey[i] + ".weight_v", wn / c.cout, &d->v[i])))
+            return I2V_E_MISSING;
+        if (!bound_ptr(sd, d->nkey[i] + ".weight", c.cout, &d->nw[i]) || !bound_ptr(sd, d->nkey[i] + ".bias", c.cout, &d->nb[i])) return I2V_E_MISSING;
+    }
+    if (!bound_ptr(sd, "fc.weight", d->L[d->nconv - 1].cout, &d->fc)) return I2V_E_MISSING;
+    d->loaded = true;
+    return I2V_OK;
+}
+
+int i2v_disc3d_bind_grads(i2v_disc3d* d, const i2v_tensor* grads, int32_t n) {
+    I2V_REQUIRE(d && (grads ? n > 0 : n == 0), I2V_E_INVALID, "i2v_disc3d_bind_grads: null handle, or a count without tensors");
+    d->have_grads = false;
+    if (!grads) return I2V_OK;
+    const StateDict gd(grads, n);
+    for (int i = 0; i < d->nconv; ++i) {
+        const D3Conv& c = d->L[i];
+        if (!bound_ptr(gd, d->wkey[i] + (c.sn ? ".weight_orig" : ".weight"), (int64_t)c.cout * c.cin * ntap_of(c), &d->gw[i])) return I2V_E_MISSING;
+        if (!bound_ptr(gd, d->nkey[i] + ".weight", c.cout, &d->gnw[i]) || !bound_ptr(gd, d->nkey[i] + ".bias", c.cout, &d->gnb[i])) return I2V_E_MISSING;
+    }
+    if (!bound_ptr(gd, "fc.weight", d->L[d->nconv - 1].cout, &d->gfc)) return I2V_E_MISSING;
+    d->have_grads = true;
+    return I2V_OK;
+}
+
+int i2v_disc3d_out_shape(const i2v_disc3d* d, int32_t t, int32_t h, int32_t w, int32_t* shapes) {
+    I2V_REQUIRE(d && shapes, I2V_E_INVALID, "i2v_disc3d_out_shape: null argument");
+    const D3Layout y = d3_layout(d, 1, t, h, w);
+    if (!y.ok) return refuse("i2v_disc3d_out_shape", y);
+    for (int l = 0; l < 4; ++l) {
+        const int i = d->B[2 * l + 1].c2;
+        shapes[4 * l] = y.geo[i].to; shapes[4 * l + 1] = y.geo[i].ho; shapes[4 * l + 2] = y.geo[i].wo; shapes[4 * l + 3] = d->L[i].cout;
+    }
+    return I2V_OK;
+}
+
+size_t i2v_disc3d_saved_bytes(const i2v_disc3d* d, int32_t n, int32_t t, int32_t h, int32_t w) { return d ? d3_layout(d, n, t, h, w).saved_total : 0; }
+size_t i2v_disc3d_workspace_bytes(const i2v_disc3d* d, int32_t n, int32_t t, int32_t h, int32_t w) { return d ? d3_layout(d, n, t, h, w).ws_total : 0; }
+
+int i2v_disc3d_saved_layout(const i2v_disc3d* d, int32_t n, int32_t t, int32_t h, int32_t w, int32_t* count, int32_t* kind, int32_t* conv,
+                            int32_t* dims, int64_t* offset) {
+    I2V_REQUIRE(d && count && kind && conv && dims && offset, I2V_E_INVALID, "i2v_disc3d_saved_layout: null argument");
+    const D3Layout y = d3_layout(d, n, t, h, w);
+    if (!y.ok) return refuse("i2v_disc3d_saved_layout", y);
+    int e = 0;
+    auto put = [&](int kd, int ci, int mt, int mh, int mw, int mc, size_t off) {
+        kind[e] = kd; conv[e] = ci; dims[4 * e] = mt; dims[4 * e + 1] = mh; dims[4 * e + 2] = mw; dims[4 * e + 3] = mc; offset[e] = (int64_t)off;
+        ++e;
+    };
+    for (int i = 0; i < d->nconv; ++i) {
+        put(I2V_DISC3D_CONV_OUT, i, y.geo[i].to, y.geo[i].ho, y.geo[i].wo, d->L[i].cout, y.pre[i]);
+        put(I2V_DISC3D_ACT, i, y.geo[i].to, y.geo[i].ho, y.geo[i].wo, d->L[i].cout, y.act[i]);
+    }
+    if (d->pool) {
+        put(I2V_DISC3D_POOL_OUT, -1, y.pt, y.pho, y.pwo, d->L[0].cout, y.pout);
+        put(I2V_DISC3D_POOL_ARGMAX, -1, y.pt, y.pho, y.pwo, d->L[0].cout, y.parg);
+    }
+    *count = e;
+    return I2V_OK;
+}
+
+int i2v_disc3d_forward(i2v_disc3d* d, const float* x, int32_t n, int32_t t, int32_t h, int32_t w, int32_t flags, float* pred, float* const* fmaps,
+                       void* saved, size_t saved_bytes, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* what = "i2v_disc3d_forward";
+    I2V_ENTER(sc, d, Entry::NEEDS_WEIGHTS, what);
+    I2V_REQUIRE(x && pred && workspace, I2V_E_INVALID, "%s: null argument", what);
+    const D3Layout y = d3_layout(d, n, t, h, w);
+    if (!y.ok) return refuse(what, y);
+    I2V_REQUIRE_WORKSPACE(workspace_bytes, y.ws_total, what);
+    const bool save = flags & I2V_DISC3D_SAVE;
+    if (save) {
+        I2V_REQUIRE(saved, I2V_E_INVALID, "%s: I2V_DISC3D_SAVE without a saved buffer", what);
+        I2V_REQUIRE_WORKSPACE(saved_bytes, y.saved_total, what);
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    void* sv = save ? saved : Carver::at<char>(workspace, y.fwd);
+    void* gnws = Carver::at<char>(workspace, y.gn);
+    const int nc = d->nconv;
+
+    float* x4 = Carver::at(sv, y.x4);
+    hipLaunchKernelGGL(d3_input4_kernel, dim3(grid_for(y.geo[0].mi)), dim3(256), 0, st, x, x4, y.geo[0].mi, (long)t * h * w);
+    PD_LAUNCHED();
+
+    // spectral norm, PD_MAXCONV convs per group of launches
+    PdPiArgs pi{};
+    pi.iterate = flags & I2V_DISC3D_ITERATE ? 1 : 0;
+    for (int i = 0; i < nc; ++i) {
+        const D3Conv& c = d->L[i];
+        if (c.sn) {
+            const int cols = c.cin * ntap_of(c);
+            pi.c[pi.nconv++] = PdPiConv{d->w[i], d->u[i], d->v[i], Carver::at(sv, y.sigma[i]), Carver::at(sv, y.us[i]), Carver::at(sv, y.vs[i]),
+                                        Carver::at<double>(workspace, y.pi_t[i]), Carver::at<double>(workspace, y.pi_s[i]), c.cout, cols, pi.btotal, pi.rtotal};
+            pi.btotal += (cols + 63) / 64; pi.rtotal += c.cout;
+        }
+        if (pi.nconv == PD_MAXCONV || (i + 1 == nc && pi.nconv > 0)) {
+            if (int rc = launch_power_iteration(pi, st)) return rc;
+            pi.nconv = pi.btotal = pi.rtotal = 0;
+        }
+    }
+    D3PackArgs pk{};
+    pk.nconv = nc;
+    for (int i = 0; i < nc; ++i) {
+        const D3Conv& c = d->L[i];
+        pk.c[i] = D3PackConv{d->w[i], c.sn ? Carver::at(sv, y.sigma[i]) : nullptr, Carver::at(sv, y.wf[i]), Carver::at(sv, y.wd[i]),
+                             c.cout, c.cin, c.cinp, c.cind, ntap_of(c), pk.total};
+        pk.total += (long)pack_elems(c);
+    }
+    hipLaunchKernelGGL(d3_pack_kernel, dim3(grid_for(pk.total)), dim3(256), 0, st, pk);
+    PD_LAUNCHED();
+
+    // conv i on `in`, then its GroupNorm (+ res) (ReLU) -> act[i]
+    auto conv_gn = [&](int i, const float* in, const float* res, bool relu) -> int {
+        const D3Conv& c = d->L[i];
+        float* pre = Carver::at(sv, y.pre[i]);
+        if (int rc = launch_conv(c, in, Carver::at(sv, y.wf[i]), pre, y.geo[i], st)) return rc;
+        return launch_gn(pre, res, d->nw[i], d->nb[i], n, y.geo[i].mo / n, c.cout, relu, Carver::at(sv, y.act[i]), Carver::at<double>(sv, y.stats[i]),
+                         gnws, st);
+    };
+    if (int rc = conv_gn(0, x4, nullptr, true)) return rc;
+    if (d->pool) {
+        const long total = y.pool_out * d->L[0].cout;
+        hipLaunchKernelGGL(d3_maxpool_kernel, dim3(grid_for(total)), dim3(256), 0, st, Carver::at(sv, y.act[0]), Carver::at(sv, y.pout),
+                           Carver::at<int>(sv, y.parg), total, y.pt, y.ph, y.pw, y.pho, y.pwo, d->L[0].cout);
+        PD_LAUNCHED();
+    }
+    for (int b = 0; b < 8; ++b) {
+        const D3Block& k = d->B[b];
+        const float* in = k.in < 0 ? Carver::at(sv, y.pout) : Carver::at(sv, y.act[k.in]);
+        if (int rc = conv_gn(k.c1, in, nullptr, true)) return rc;
+        const float* res = in;
+        if (k.cd >= 0) {
+            if (int rc = conv_gn(k.cd, in, nullptr, false)) return rc;
+            res = Carver::at(sv, y.act[k.cd]);
+        }
+        if (int rc = conv_gn(k.c2, Carver::at(sv, y.act[k.c1]), res, true)) return rc;
+        if ((b & 1) && fmaps && fmaps[b / 2])
+            I2V_HIP_CHECK(hipMemcpyAsync(fmaps[b / 2], Carver::at(sv, y.act[k.c2]), (size_t)y.geo[k.c2].mo * d->L[k.c2].cout * 4, hipMemcpyDeviceToDevice, st));
+    }
+    const int last = d->B[7].c2;
+    hipLaunchKernelGGL(d3_head_fwd_kernel, dim3(n), dim3(256), 0, st, Carver::at(sv, y.act[last]), d->fc, pred, d->L[last].cout);
+    PD_LAUNCHED();
+    return I2V_OK;
+}
+
+int i2v_disc3d_backward(i2v_disc3d* d, const float* d_pred, const float* const* d_fmaps, const void* saved, size_t saved_bytes, int32_t n, int32_t t,
+                        int32_t h, int32_t w, float* d_x, int32_t param_grads, int32_t accumulate, void* workspace, size_t workspace_bytes,
+                        void* stream) {
+    const char* what = "i2v_disc3d_backward";
+    I2V_ENTER(sc, d, Entry::NEEDS_WEIGHTS, what);
+    I2V_REQUIRE(saved && workspace, I2V_E_INVALID, "%s: null argument", what);
+    I2V_REQUIRE(d_x || param_grads, I2V_E_INVALID, "%s: neither the input gradient nor the parameter gradients are asked for", what);
+    bool any = d_pred != nullptr;
+    for (int l = 0; l < 4 && d_fmaps; ++l) any = any || d_fmaps[l];
+    I2V_REQUIRE(any, I2V_E_INVALID, "%s: no upstream gradient (d_pred and every d_fmaps entry are null)", what);
+    I2V_REQUIRE(!param_grads || d->have_grads, I2V_E_STATE, "%s: no gradient tensors are bound", what);
+    const D3Layout y = d3_layout(d, n, t, h, w);
+    if (!y.ok) return refuse(what, y);
+    I2V_REQUIRE_WORKSPACE(workspace_bytes, y.ws_total, what);
+    I2V_REQUIRE_WORKSPACE(saved_bytes, y.saved_total, what);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    void* sv = const_cast<void*>(saved);
+    const bool acc = accumulate != 0, pg = param_grads != 0;
+    float* part = Carver::at(workspace, y.part);
+    float* dwn = Carver::at(workspace, y.dwn);
+    double* dotp = Carver::at<double>(workspace, y.dotp);
+    void* gnws = Carver::at<char>(workspace, y.gn);
+    float* G = Carver::at(workspace, y.gbuf[0]);      // the gradient at the current block's output
+    float* Gn = Carver::at(workspace, y.gbuf[1]);     // ... at its input
+    float* H1 = Carver::at(workspace, y.gbuf[2]);     // ... at conv1's activation
+    float* X2 = Carver::at(workspace, y.gbuf[3]);     // the downsample branch's share of Gn
+    float* DC = Carver::at(workspace, y.dc[0]);       // ... at a conv's output
+    float* DC2 = Carver::at(workspace, y.dc[1]);
+
+    // GroupNorm of conv i backwards: g (masked by `mask`) -> dc; then the conv's weight gradient
+    auto norm_conv_bwd = [&](int i, const float* g, const float* mask, const float* xin, float* dc) -> int {
+        const D3Conv& c = d->L[i];
+        if (int rc = launch_gn_bwd(g, mask, Carver::at(sv, y.pre[i]), Carver::at<double>(sv, y.stats[i]), d->nw[i], n, y.geo[i].mo / n, c.cout, dc,
+                                   pg ? d->gnw[i] : nullptr, pg ? d->gnb[i] : nullptr, acc, gnws, st))
+            return rc;
+        if (!pg) return I2V_OK;
+        return launch_wgrad(c, dc, nullptr, xin, d->w[i], c.sn ? Carver::at(sv, y.us[i]) : nullptr, c.sn ? Carver::at(sv, y.vs[i]) : nullptr,
+                            c.sn ? Carver::at(sv, y.sigma[i]) : nullptr, part, dwn, dotp, d->gw[i], acc, y.geo[i], st);
+    };
+    auto add_fmap = [&](int l, float* g, size_t elems) -> int {
+        if (!d_fmaps || !d_fmaps[l]) return I2V_OK;
+        hipLaunchKernelGGL(d3_add_kernel, dim3(grid_for((long)elems)), dim3(256), 0, st, g, d_fmaps[l], (long)elems);
+        PD_LAUNCHED();
+        return I2V_OK;
+    };
+
+    // the head
+    const int last = d->B[7].c2;
+    {
+        const int C = d->L[last].cout;
+        const size_t elems = (size_t)n * 16 * C;
+        if (d_pred) {
+            hipLaunchKernelGGL(d3_head_bwd_kernel, dim3((C + 255) / 256), dim3(256), 0, st, Carver::at(sv, y.act[last]), d->fc, d_pred, G,
+                               pg ? d->gfc : nullptr, n, C, acc ? 1 : 0);
+            PD_LAUNCHED();
+        } else {
+            I2V_HIP_CHECK(hipMemsetAsync(G, 0, elems * 4, st));
+            if (pg && !acc) I2V_HIP_CHECK(hipMemsetAsync(d->gfc, 0, (size_t)C * 4, st));
+        }
+        if (int rc = add_fmap(3, G, elems)) return rc;
+    }
+    for (int b = 7; b >= 0; --b) {
+        const D3Block& k = d->B[b];
+        const float* out = Carver::at(sv, y.act[k.c2]);
+        const float* xin = k.in < 0 ? Carver::at(sv, y.pout) : Carver::at(sv, y.act[k.in]);
+        const float* h1 = Carver::at(sv, y.act[k.c1]);
+        if (int rc = norm_conv_bwd(k.c2, G, out, h1, DC)) return rc;
+        if (int rc = launch_dgrad(d->L[k.c2], DC, nullptr, Carver::at(sv, y.wd[k.c2]), nullptr, nullptr, H1, false, n, y.geo[k.c2], st)) return rc;
+        if (int rc = norm_conv_bwd(k.c1, H1, h1, xin, DC)) return rc;
+        if (k.cd >= 0) {
+            if (int rc = norm_conv_bwd(k.cd, G, out, xin, DC2)) return rc;
+            if (int rc = launch_dgrad(d->L[k.cd], DC2, nullptr, Carver::at(sv, y.wd[k.cd]), nullptr, nullptr, X2, false, n, y.geo[k.cd], st)) return rc;
+            if (int rc = launch_dgrad(d->L[k.c1], DC, nullptr, Carver::at(sv, y.wd[k.c1]), X2, nullptr, Gn, false, n, y.geo[k.c1], st)) return rc;
+        } else if (int rc = launch_dgrad(d->L[k.c1], DC, nullptr, Carver::at(sv, y.wd[k.c1]), G, out, Gn, false, n, y.geo[k.c1], st)) {
+            return rc;
+        }
+        std::swap(G, Gn);
+        if (!(b & 1) && b > 0)
+            if (int rc = add_fmap(b / 2 - 1, G, (size_t)y.geo[k.c1].mi * d->L[k.c1].cin)) return rc;
+    }
+    // G: the gradient at the pool's output (or at the stem's activation)
+    if (d->pool) {
+        const long total = y.pool_in * d->L[0].cout;
+        hipLaunchKernelGGL(d3_maxpool_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, st, G, Carver::at<int>(sv, y.parg), Gn, total, y.pt, y.ph, y.pw,
+                           y.pho, y.pwo, d->L[0].cout);
+        PD_LAUNCHED();
+        std::swap(G, Gn);
+    }
+    if (int rc = norm_conv_bwd(0, G, Carver::at(sv, y.act[0]), Carver::at(sv, y.x4), DC)) return rc;
+    if (d_x)
+        if (int rc = launch_dgrad(d->L[0], DC, nullptr, Carver::at(sv, y.wd[0]), nullptr, nullptr, d_x, true, n, y.geo[0], st)) return rc;
+    return I2V_OK;
+}
+
+size_t i2v_disc3d_fmap_loss_workspace_bytes(void) { return (size_t)4 * D3_FMAP_BLOCKS * 8; }
+
+int i2v_disc3d_fmap_loss(const float* const* a, const float* const* b, const int64_t* numel, int32_t n_layers, int32_t metric, float grad_scale, double* out,
+                         float* const* d_a, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* what = "i2v_disc3d_fmap_loss";
+    I2V_REQUIRE(a && b && numel && out && workspace && n_layers >= 1 && n_layers <= 4 && (metric == I2V_FMAP_L1 || metric == I2V_FMAP_L2), I2V_E_INVALID,
+                "%s: null argument, %d layers or metric %d", what, n_layers, metric);
+    I2V_REQUIRE_WORKSPACE(workspace_bytes, i2v_disc3d_fmap_loss_workspace_bytes(), what);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    D3FmapFinal f{};
+    f.nl = n_layers;
+    for (int l = 0; l < n_layers; ++l) {
+        I2V_REQUIRE(a[l] && b[l] && numel[l] > 0, I2V_E_INVALID, "%s: layer %d is null or empty", what, l);
+        f.numel[l] = numel[l];
+        f.nblk[l] = (int)std::min<long>((numel[l] + 255) / 256, D3_FMAP_BLOCKS);
+        const float coef = (float)((double)grad_scale / ((double)numel[l] * n_layers));
+        hipLaunchKernelGGL(d3_fmap_partial_kernel, dim3(f.nblk[l]), dim3(256), 0, st, a[l], b[l], (long)numel[l], metric, coef, d_a ? d_a[l] : nullptr,
+                           Carver::at<double>(workspace, 0) + l * D3_FMAP_BLOCKS);
+        PD_LAUNCHED();
+    }
+    hipLaunchKernelGGL(d3_fmap_final_kernel, dim3(1), dim3(64), 0, st, f, Carver::at<double>(workspace, 0), out);
+    PD_LAUNCHED();
+    return I2V_OK;
+}
+
+int i2v_disc3d_sumsq(const float* x, int32_t n, int64_t per, double* out, void* stream) {
+    I2V_REQUIRE(x && out && n > 0 && per > 0, I2V_E_INVALID, "i2v_disc3d_sumsq: null argument, %d rows of %lld", n, (long long)per);
+    hipLaunchKernelGGL(d3_sumsq_kernel, dim3(n), dim3(256), 0, static_cast<hipStream_t>(stream), x, (long)per, out);
+    PD_LAUNCHED();
+    return I2V_OK;
+}
+
+int i2v_disc3d_wgrad_plan(int32_t cout, int32_t cin, int32_t taps, int64_t positions, int32_t* slices, int32_t* slice_len) {
+    I2V_REQUIRE(slices && slice_len && positions > 0 && cout > 0 && cout % 16 == 0 && (cin == 3 || (cin > 0 && cin % 16 == 0)) && (taps == 27 || taps == 147),
+                I2V_E_INVALID, "i2v_disc3d_wgrad_plan: cout %d, cin %d, %d taps, %lld positions", cout, cin, taps, (long long)positions);
+    d3_wgrad_plan(cout, cin, taps, positions, slices, slice_len);
+    return I2V_OK;
+}
+
+size_t i2v_disc3d_unit_workspace_bytes(int32_t n, int32_t ti, int32_t hi, int32_t wi, int32_t cin, int32_t cout, int32_t stem) {
+    if (n <= 0 || ti < 1 || hi < 1 || wi < 1 || cin <= 0 || cout <= 0) return 0;
+    return unit_ws(n, ti, hi, wi, cin, cout, stem).total;
+}
+
+int i2v_disc3d_conv_unit(const float* x, const float* weight, int32_t n, int32_t ti, int32_t hi, int32_t wi, int32_t cin, int32_t cout, int32_t stem,
+                         int32_t stride_t, int32_t stride_s, float* out, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* what = "i2v_disc3d_conv_unit";
+    if (int rc = check_unit(what, n, ti, hi, wi, cin, cout, stem, stride_t, stride_s)) return rc;
+    I2V_REQUIRE(x && weight && out && workspace, I2V_E_INVALID, "%s: null argument", what);
+    const D3UnitWs k = unit_ws(n, ti, hi, wi, cin, cout, stem);
+    I2V_REQUIRE_WORKSPACE(workspace_bytes, k.total, what);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const D3Conv c = make_conv(cin, cout, stem, stride_t, stride_s, 0);
+    if (int rc = pack_unit(c, weight, Carver::at(workspace, k.wf), Carver::at(workspace, k.wd), st)) return rc;
+    return launch_conv(c, x, Carver::at(workspace, k.wf), out, make_geo(n, ti, hi, wi, c), st);
+}
+
+int i2v_disc3d_dgrad_unit(const float* g, const float* weight, const float* act, const float* add, const float* add_mask, int32_t n, int32_t ti, int32_t hi,
+                          int32_t wi, int32_t cin, int32_t cout, int32_t stem, int32_t stride_t, int32_t stride_s, float* out, int32_t frames_out,
+                          void* workspace, size_t workspace_bytes, void* stream) {
+    const char* what = "i2v_disc3d_dgrad_unit";
+    if (int rc = check_unit(what, n, ti, hi, wi, cin, cout, stem, stride_t, stride_s)) return rc;
+    I2V_REQUIRE(g && weight && out && workspace && (!frames_out || (cin == 3 && !add)) && (add || !add_mask), I2V_E_INVALID,
+                "%s: null argument, frames_out with cin %d or with add, or add_mask without add", what, cin);
+    const D3UnitWs k = unit_ws(n, ti, hi, wi, cin, cout, stem);
+    I2V_REQUIRE_WORKSPACE(workspace_bytes, k.total, what);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const D3Conv c = make_conv(cin, cout, stem, stride_t, stride_s, 0);
+    if (int rc = pack_unit(c, weight, Carver::at(workspace, k.wf), Carver::at(workspace, k.wd), st)) return rc;
+    return launch_dgrad(c, g, act, Carver::at(workspace, k.wd), add, add_mask, out, frames_out != 0, n, make_geo(n, ti, hi, wi, c), st);
+}
+
+int i2v_disc3d_wgrad_unit(const float* g, const float* act, const float* x, const float* weight, const float* u, const float* v, const float* sigma,
+                          int32_t n, int32_t ti, int32_t hi, int32_t wi, int32_t cin, int32_t cout, int32_t stem, int32_t stride_t, int32_t stride_s,
+                          int32_t accumulate, float* dweight, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* what = "i2v_disc3d_wgrad_unit";
+    if (int rc = check_unit(what, n, ti, hi, wi, cin, cout, stem, stride_t, stride_s)) return rc;
+    I2V_REQUIRE(g && x && weight && dweight && workspace && !u == !v && !u == !sigma, I2V_E_INVALID, "%s: null argument", what);
+    const D3UnitWs k = unit_ws(n, ti, hi, wi, cin, cout, stem);
+    I2V_REQUIRE_WORKSPACE(workspace_bytes, k.total, what);
+    const D3Conv c = make_conv(cin, cout, stem, stride_t, stride_s, 0);
+    return launch_wgrad(c, g, act, x, weight, u, v, sigma, Carver::at(workspace, k.part), Carver::at(workspace, k.dwn),
+                        Carver::at<double>(workspace, k.dotp), dweight, accumulate != 0, make_geo(n, ti, hi, wi, c), static_cast<hipStream_t>(stream));
+}
+
+size_t i2v_disc3d_groupnorm_workspace_bytes(int32_t n, int32_t c) { return n > 0 && c > 0 ? gn_ws(n, c).total : 0; }
+
+int i2v_disc3d_groupnorm_unit(const float* x, const float* res, const float* weight, const float* bias, int32_t n, int64_t positions, int32_t c,
+                              int32_t relu, float* out, double* stats, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* what = "i2v_disc3d_groupnorm_unit";
+    I2V_REQUIRE(x && weight && bias && out && stats && workspace && n > 0 && positions > 0 && c > 0 && c % 16 == 0, I2V_E_INVALID,
+                "%s: null argument, n %d, %lld positions or %d channels", what, n, (long long)positions, c);
+    I2V_REQUIRE_WORKSPACE(workspace_bytes, gn_ws(n, c).total, what);
+    return launch_gn(x, res, weight, bias, n, positions, c, relu != 0, out, stats, workspace, static_cast<hipStream_t>(stream));
+}
+
+int i2v_disc3d_groupnorm_backward_unit(const float* g, const float* mask, const float* x, const double* stats, const float* weight, int32_t n,
+                                       int64_t positions, int32_t c, float* dx, float* dweight, float* dbias, int32_t accumulate, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+    const char* what = "i2v_disc3d_groupnorm_backward_unit";
+    I2V_REQUIRE(g && x && stats && weight && dx && workspace && !dweight == !dbias && n > 0 && positions > 0 && c > 0 && c % 16 == 0, I2V_E_INVALID,
+                "%s: null argument, n %d, %lld positions or %d channels", what, n, (long long)positions, c);
+    I2V_REQUIRE_WORKSPACE(workspace_bytes, gn_ws(n, c).total, what);
+    return launch_gn_bwd(g, mask, x, stats, weight, n, positions, c, dx, dweight, dbias, accumulate != 0, workspace, static_cast<hipStream_t>(stream));
+}
+
+int i2v_disc3d_maxpool_unit(const float* x, int32_t n, int32_t t, int32_t h, int32_t w, int32_t c, float* out, int32_t* argmax, void* stream) {
+    I2V_REQUIRE(x && out && argmax && n > 0 && t > 0 && h > 0 && w > 0 && c > 0, I2V_E_INVALID, "i2v_disc3d_maxpool_unit: null argument or an empty map");
+    const int ho = (h - 1) / 2 + 1, wo = (w - 1) / 2 + 1;
+    const long total = (long)n * t * ho * wo * c;
+    hipLaunchKernelGGL(d3_maxpool_kernel, dim3(grid_for(total)), dim3(256), 0, static_cast<hipStream_t>(stream), x, out, argmax, total, t, h, w, ho, wo, c);
+    PD_LAUNCHED();
+    return I2V_OK;
+}
+
+int i2v_disc3d_maxpool_backward_unit(const float* g, const int32_t* argmax, int32_t n, int32_t t, int32_t h, int32_t w, int32_t c, float* dx, void* stream) {
+    I2V_REQUIRE(g && argmax && dx && n > 0 && t > 0 && h > 0 && w > 0 && c > 0, I2V_E_INVALID, "i2v_disc3d_maxpool_backward_unit: null argument or an empty map");
+    const int ho = (h - 1) / 2 + 1, wo = (w - 1) / 2 + 1;
+    const long total = (long)n * t * h * w * c;
+    hipLaunchKernelGGL(d3_maxpool_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, static_cast<hipStream_t>(stream), g, argmax, dx, total, t, h, w, ho, wo, c);
+    PD_LAUNCHED();
+    return I2V_OK;
+}
+
+int i2v_disc3d_head_unit(const float* x, const float* weight, const float* g, int32_t n, int32_t c, float* pred, float* dx, float* dweight, void* stream) {
+    I2V_REQUIRE(x && weight && pred && n > 0 && c > 0 && (g ? dx != nullptr : !dx && !dweight), I2V_E_INVALID, "i2v_disc3d_head_unit: null argument");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(d3_head_fwd_kernel, dim3(n), dim3(256), 0, st, x, weight, pred, c);
+    PD_LAUNCHED();
+    if (!g) return I2V_OK;
+    hipLaunchKernelGGL(d3_head_bwd_kernel, dim3((c + 255) / 256), dim3(256), 0, st, x, weight, g, dx, dweight, n, c, 0);
+    PD_LAUNCHED();
+    return I2V_OK;
+}
+
+}  // extern "C"

@@ -69,6 +69,11 @@ class PatchDiscCfg(ctypes.Structure):
     _fields_ = [(n, c_int32) for n in ("in_channels", "ndf", "n_layers", "use_actnorm", "spectral_norm")]
 
 
+class Disc3DCfg(ctypes.Structure):
+    _fields_ = [("res_type", c_int32), ("channels", c_int32 * 5), ("stride_s", c_int32 * 4), ("stride_t", c_int32 * 4), ("use_max_pool", c_int32),
+                ("spectral_norm", c_int32)]
+
+
 _lib = None
 
 # symbol -> (restype, argtypes); also the list the CPU test-suite checks the .so exports
@@ -256,6 +261,43 @@ DISC_SYMBOLS = {
     "i2v_patchdisc_actnorm_init_unit": (c_int32, [c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
 }
 
+# The entries of include/i2v_hip_disc3d.h (the temporal discriminator of stage-1 training), one to one.
+_PP = POINTER(c_void_p)
+DISC3D_SYMBOLS = {
+    "i2v_disc3d_create": (c_int32, [POINTER(Disc3DCfg), POINTER(c_void_p)]),
+    "i2v_disc3d_destroy": (None, [c_void_p]),
+    "i2v_disc3d_bind": (c_int32, [c_void_p, POINTER(_Tensor), c_int32]),
+    "i2v_disc3d_bind_grads": (c_int32, [c_void_p, POINTER(_Tensor), c_int32]),
+    "i2v_disc3d_out_shape": (c_int32, [c_void_p, c_int32, c_int32, c_int32, POINTER(c_int32)]),
+    "i2v_disc3d_saved_bytes": (c_size_t, [c_void_p, c_int32, c_int32, c_int32, c_int32]),
+    "i2v_disc3d_workspace_bytes": (c_size_t, [c_void_p, c_int32, c_int32, c_int32, c_int32]),
+    "i2v_disc3d_saved_layout": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32),
+                                          POINTER(c_int32), POINTER(c_int64)]),
+    "i2v_disc3d_forward": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, _PP, c_void_p, c_size_t, c_void_p,
+                                     c_size_t, c_void_p]),
+    "i2v_disc3d_backward": (c_int32, [c_void_p, c_void_p, _PP, c_void_p, c_size_t, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32,
+                                      c_void_p, c_size_t, c_void_p]),
+    "i2v_disc3d_fmap_loss_workspace_bytes": (c_size_t, []),
+    "i2v_disc3d_fmap_loss": (c_int32, [_PP, _PP, POINTER(c_int64), c_int32, c_int32, c_float, c_void_p, _PP, c_void_p, c_size_t, c_void_p]),
+    "i2v_disc3d_sumsq": (c_int32, [c_void_p, c_int32, c_int64, c_void_p, c_void_p]),
+    "i2v_disc3d_wgrad_plan": (c_int32, [c_int32, c_int32, c_int32, c_int64, POINTER(c_int32), POINTER(c_int32)]),
+    "i2v_disc3d_unit_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "i2v_disc3d_conv_unit": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
+                                       c_void_p, c_size_t, c_void_p]),
+    "i2v_disc3d_dgrad_unit": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                        c_int32, c_int32, c_void_p, c_int32, c_void_p, c_size_t, c_void_p]),
+    "i2v_disc3d_wgrad_unit": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
+                                        c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "i2v_disc3d_groupnorm_workspace_bytes": (c_size_t, [c_int32, c_int32]),
+    "i2v_disc3d_groupnorm_unit": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                            c_size_t, c_void_p]),
+    "i2v_disc3d_groupnorm_backward_unit": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_void_p, c_void_p,
+                                                     c_void_p, c_int32, c_void_p, c_size_t, c_void_p]),
+    "i2v_disc3d_maxpool_unit": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "i2v_disc3d_maxpool_backward_unit": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "i2v_disc3d_head_unit": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+}
+
 
 def build(force=False):
     """Compile ``libi2v_hip.so`` for gfx950 in-tree (``make`` in csrc/; hipcc cross-compiles without a GPU)."""
@@ -287,7 +329,7 @@ def lib():
             raise I2VError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                            f"or `make -C {CSRC}`; this package has no CPU/eager fallback")
         l = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SYMBOLS.items()) + list(DISC_SYMBOLS.items()):
+        for name, (res, args) in list(SYMBOLS.items()) + list(DISC_SYMBOLS.items()) + list(DISC3D_SYMBOLS.items()):
             fn = getattr(l, name)
             fn.restype = res
             fn.argtypes = args
@@ -2091,3 +2133,265 @@ def patchdisc_actnorm_init_unit(pre):
         loc, scale = torch.empty(c, dtype=torch.float32, device=pre.device), torch.empty(c, dtype=torch.float32, device=pre.device)
         _call("i2v_patchdisc_actnorm_init_unit", pre.data_ptr(), m, c, loc.data_ptr(), scale.data_ptr(), _stream())
     return loc, scale
+
+
+# ---------------------------------------------------------------------------------------------------------------- temporal discriminator
+DISC3D_ITERATE, DISC3D_SAVE = 1, 2
+DISC3D_CONV_OUT, DISC3D_ACT, DISC3D_POOL_OUT, DISC3D_POOL_ARGMAX = 0, 1, 2, 3
+FMAP_METRICS = {"L1": 0, "L2": 1}
+
+
+def _ptr_array(tensors, count=4):
+    """void*[count] of the tensors' device pointers (None -> NULL), or None when ``tensors`` is None."""
+    if tensors is None:
+        return None
+    return (c_void_p * count)(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+class NativeDisc3D(_Handle):
+    """Handle for ``i2v_disc3d_*`` (include/i2v_hip_disc3d.h): resnet3D.Discriminator forward and backward.  It packs nothing on the
+    host: ``bind`` hands over the DEVICE pointers of the module's parameters and buffers (read in place; ``weight_u`` and ``weight_v``
+    are updated in place) and ``bind_grads`` those of their gradient tensors.  Feature maps are channels-last [N, T, H, W, C]."""
+    _PREFIX = "i2v_disc3d"
+
+    def __init__(self, channels, stride_s, stride_t, use_max_pool=True, spectral_norm=True, res_type=18, device=None):
+        if len(channels) != 5 or len(stride_s) != 4 or len(stride_t) != 4:
+            raise I2VError(f"temporal discriminator: {len(channels)} widths with {len(stride_s)} / {len(stride_t)} strides (5 and 4 are built)")
+        cfg = Disc3DCfg(int(res_type), (c_int32 * 5)(*map(int, channels)), (c_int32 * 4)(*map(int, stride_s)), (c_int32 * 4)(*map(int, stride_t)),
+                        int(bool(use_max_pool)), int(bool(spectral_norm)))
+        self._create(device, ctypes.byref(cfg))
+        self.bound_ptrs, self.bound_grad_ptrs, self._keep, self._keep_grads = None, None, None, None
+
+    def load(self, state_dict):
+        raise I2VError("NativeDisc3D packs nothing: bind() hands over the module's own parameters")
+
+    def bind(self, tensors):
+        """tensors: {state_dict key: float32 device tensor} of the parameters and the spectral-norm buffers."""
+        with self._on(*tensors.values()):
+            arr, keep = NativePatchDisc._items(tensors)
+            _call("i2v_disc3d_bind", self._h, arr, len(keep))
+        self.bound_ptrs = tuple(t.data_ptr() for t in tensors.values())
+        self._keep = tensors
+
+    def bind_grads(self, grads):
+        """grads: {key: gradient tensor} of the parameters, or None."""
+        if grads is None:
+            _call("i2v_disc3d_bind_grads", self._h, None, 0)
+        else:
+            with self._on(*grads.values()):
+                arr, keep = NativePatchDisc._items(grads)
+                _call("i2v_disc3d_bind_grads", self._h, arr, len(keep))
+        self.bound_grad_ptrs = None if grads is None else tuple(g.data_ptr() for g in grads.values())
+        self._keep_grads = grads
+
+    def out_shape(self, t, h, w):
+        """[(t, h, w, c)] of the four feature maps; raises with the final map in the message unless the net ends on [1, 4, 4]."""
+        s = (c_int32 * 16)()
+        _call("i2v_disc3d_out_shape", self._h, int(t), int(h), int(w), s)
+        return [tuple(s[4 * i: 4 * i + 4]) for i in range(4)]
+
+    def _shape(self, x):
+        if x.dim() != 5 or x.shape[1] != 3:
+            raise I2VError(f"temporal discriminator: expected clips [N, 3, T, H, W], got {tuple(x.shape)}")
+        n, _, t, h, w = x.shape
+        return n, t, h, w
+
+    def saved_bytes(self, n, t, h, w):
+        return int(lib().i2v_disc3d_saved_bytes(self._h, n, t, h, w))
+
+    def workspace_bytes(self, n, t, h, w):
+        return int(lib().i2v_disc3d_workspace_bytes(self._h, n, t, h, w))
+
+    def saved_maps(self, saved, shape):
+        """{(kind, conv): view of ``saved`` [N, T, H, W, C]} (kinds DISC3D_*; the pool's maps have conv -1; the argmax is int32), for the tests."""
+        n, _, t, h, w = shape
+        cnt, kind, conv, dims, off = c_int32(), (c_int32 * 64)(), (c_int32 * 64)(), (c_int32 * 256)(), (c_int64 * 64)()
+        _call("i2v_disc3d_saved_layout", self._h, n, t, h, w, ctypes.byref(cnt), kind, conv, dims, off)
+        out = {}
+        for e in range(cnt.value):
+            shp = (n, *dims[4 * e: 4 * e + 4])
+            flat = saved.view(torch.int32 if kind[e] == DISC3D_POOL_ARGMAX else torch.float32)
+            out[(kind[e], conv[e])] = flat[off[e] // 4: off[e] // 4 + int(np.prod(shp))].view(shp)
+        return out
+
+    @_on_device
+    def forward(self, x, iterate=False, save=False, want_fmaps=True):
+        """x [N, 3, T, H, W] -> (pred [N, 1], fmaps or None, saved or None)."""
+        _require_gpu(x)
+        n, t, h, w = self._shape(x)
+        shapes = self.out_shape(t, h, w)
+        ws = self._scratch(self.workspace_bytes(n, t, h, w), x.device)
+        saved = torch.empty(self.saved_bytes(n, t, h, w), dtype=torch.uint8, device=x.device) if save else None
+        pred = torch.empty(n, 1, dtype=torch.float32, device=x.device)
+        fmaps = [torch.empty(n, *s, dtype=torch.float32, device=x.device) for s in shapes] if want_fmaps else None
+        flags = (DISC3D_ITERATE if iterate else 0) | (DISC3D_SAVE if save else 0)
+        _call("i2v_disc3d_forward", self._h, x.data_ptr(), n, t, h, w, flags, pred.data_ptr(), _ptr_array(fmaps), _opt(saved),
+              0 if saved is None else saved.numel(), *ws, _stream())
+        return pred, fmaps, saved
+
+    @_on_device
+    def backward(self, d_pred, d_fmaps, saved, shape, need_dx=True, param_grads=True, accumulate=False):
+        """``shape``: the (N, 3, T, H, W) of the forward's input; d_pred [N, 1] or None; d_fmaps: None or four channels-last tensors / None.
+        -> d_x [N, 3, T, H, W] or None; the parameter gradients go to the bound gradient tensors, written or (``accumulate``) added."""
+        _require_gpu(d_pred, *(d_fmaps or ()))
+        n, _, t, h, w = shape
+        ws = self._scratch(self.workspace_bytes(n, t, h, w), saved.device)
+        dx = torch.empty(n, 3, t, h, w, dtype=torch.float32, device=saved.device) if need_dx else None
+        _call("i2v_disc3d_backward", self._h, _opt(d_pred), _ptr_array(d_fmaps), saved.data_ptr(), saved.numel(), n, t, h, w, _opt(dx),
+              int(bool(param_grads)), int(bool(accumulate)), *ws, _stream())
+        return dx
+
+
+def disc3d_fmap_loss(fmap1, fmap2, metric="L1", need_grads=True, grad_scale=1.0):
+    """``fmap_loss`` (loss.py:14-21) over two lists of same-layout device maps -> (out float64 [5] = (loss, the layers' own means),
+    [d loss / d fmap1[i] * grad_scale] or None)."""
+    if len(fmap1) != len(fmap2) or not 1 <= len(fmap1) <= 4 or metric not in FMAP_METRICS:
+        raise I2VError(f"disc3d_fmap_loss: {len(fmap1)} against {len(fmap2)} maps (1..4), metric {metric!r} ('L1' or 'L2')")
+    _require_gpu(*fmap1, *fmap2)
+    for a, b in zip(fmap1, fmap2):
+        if a.shape != b.shape:
+            raise I2VError(f"disc3d_fmap_loss: map {tuple(a.shape)} against {tuple(b.shape)}")
+    dev, nl = fmap1[0].device, len(fmap1)
+    with torch.cuda.device(dev):
+        out = torch.empty(5, dtype=torch.float64, device=dev)
+        ws = torch.empty(int(lib().i2v_disc3d_fmap_loss_workspace_bytes()), dtype=torch.uint8, device=dev)
+        grads = [torch.empty_like(a) for a in fmap1] if need_grads else None
+        _call("i2v_disc3d_fmap_loss", _ptr_array(fmap1, nl), _ptr_array(fmap2, nl), (c_int64 * nl)(*[a.numel() for a in fmap1]), nl, FMAP_METRICS[metric],
+              float(grad_scale), out.data_ptr(), _ptr_array(grads, nl), ws.data_ptr(), ws.numel(), _stream())
+    return out, grads
+
+
+def disc3d_sumsq(x):
+    """x [N, ...] -> float64 [N]: the sum of squares of each sample."""
+    _require_gpu(x)
+    with torch.cuda.device(x.device):
+        out = torch.empty(x.shape[0], dtype=torch.float64, device=x.device)
+        _call("i2v_disc3d_sumsq", x.data_ptr(), x.shape[0], x[0].numel(), out.data_ptr(), _stream())
+    return out
+
+
+def disc3d_wgrad_plan(cout, cin, positions, taps=27):
+    """(slices, slice_len) of the weight gradient's position split: a pure host function of the shape."""
+    s, l = c_int32(), c_int32()
+    _call("i2v_disc3d_wgrad_plan", int(cout), int(cin), int(taps), int(positions), ctypes.byref(s), ctypes.byref(l))
+    return s.value, l.value
+
+
+def disc3d_out_extent(n, k, s):
+    return (n + 2 * (k // 2) - k) // s + 1
+
+
+def _d3_geom(x, weight):
+    n, ti, hi, wi, cs = x.shape
+    cout, cin, kt, kh, kw = weight.shape
+    stem = (kh, kw) == (7, 7)
+    if cs != (4 if cin == 3 else cin) or kt != 3 or (kh, kw) not in ((3, 3), (7, 7)):
+        raise I2VError(f"temporal discriminator unit: map {tuple(x.shape)} against weight {tuple(weight.shape)}")
+    return n, ti, hi, wi, cin, cout, int(stem)
+
+
+def _d3_ws(n, ti, hi, wi, cin, cout, stem, device):
+    return torch.empty(int(lib().i2v_disc3d_unit_workspace_bytes(n, ti, hi, wi, cin, cout, stem)), dtype=torch.uint8, device=device)
+
+
+def disc3d_conv_unit(x, weight, stride_t=1, stride_s=1):
+    """x [N, T, H, W, C] channels-last (C = 4 for cin 3), weight [Cout, Cin, 3, k, k] -> [N, To, Ho, Wo, Cout]."""
+    _require_gpu(x, weight)
+    n, ti, hi, wi, cin, cout, stem = _d3_geom(x, weight)
+    k = weight.shape[-1]
+    with torch.cuda.device(x.device):
+        ws = _d3_ws(n, ti, hi, wi, cin, cout, stem, x.device)
+        out = torch.empty(n, disc3d_out_extent(ti, 3, stride_t), disc3d_out_extent(hi, k, stride_s), disc3d_out_extent(wi, k, stride_s), cout,
+                          dtype=torch.float32, device=x.device)
+        _call("i2v_disc3d_conv_unit", x.data_ptr(), weight.data_ptr(), n, ti, hi, wi, cin, cout, stem, stride_t, stride_s, out.data_ptr(), ws.data_ptr(),
+              ws.numel(), _stream())
+    return out
+
+
+def disc3d_dgrad_unit(g, weight, in_thw, act=None, add=None, add_mask=None, stride_t=1, stride_s=1, frames=False):
+    """g [N, To, Ho, Wo, Cout] -> the gradient at the conv's input [N, T, H, W, Cin] (cin 3: 4 channels, or [N, 3, T, H, W] with ``frames``)."""
+    _require_gpu(g, weight, act, add, add_mask)
+    n, (ti, hi, wi), (cout, cin) = g.shape[0], in_thw, weight.shape[:2]
+    stem = int(weight.shape[-1] == 7)
+    with torch.cuda.device(g.device):
+        ws = _d3_ws(n, ti, hi, wi, cin, cout, stem, g.device)
+        out = torch.empty((n, 3, ti, hi, wi) if frames else (n, ti, hi, wi, 4 if cin == 3 else cin), dtype=torch.float32, device=g.device)
+        _call("i2v_disc3d_dgrad_unit", g.data_ptr(), weight.data_ptr(), _opt(act), _opt(add), _opt(add_mask), n, ti, hi, wi, cin, cout, stem, stride_t,
+              stride_s, out.data_ptr(), int(bool(frames)), ws.data_ptr(), ws.numel(), _stream())
+    return out
+
+
+def disc3d_wgrad_unit(g, x, weight, act=None, u=None, v=None, sigma=None, stride_t=1, stride_s=1, dweight=None):
+    """-> dweight [Cout, Cin, 3, k, k]; given ``dweight`` the result is ADDED to it."""
+    _require_gpu(g, x, weight, act, u, v, sigma, dweight)
+    n, ti, hi, wi, cin, cout, stem = _d3_geom(x, weight)
+    accumulate = dweight is not None
+    with torch.cuda.device(g.device):
+        ws = _d3_ws(n, ti, hi, wi, cin, cout, stem, g.device)
+        if not accumulate:
+            dweight = torch.empty_like(weight)
+        _call("i2v_disc3d_wgrad_unit", g.data_ptr(), _opt(act), x.data_ptr(), weight.data_ptr(), _opt(u), _opt(v), _opt(sigma), n, ti, hi, wi, cin, cout,
+              stem, stride_t, stride_s, int(accumulate), dweight.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+    return dweight
+
+
+def _gn_ws(n, c, device):
+    return torch.empty(int(lib().i2v_disc3d_groupnorm_workspace_bytes(n, c)), dtype=torch.uint8, device=device)
+
+
+def disc3d_groupnorm_unit(x, weight, bias, res=None, relu=False):
+    """GroupNorm(16) over x [N, ..., C] channels-last -> (out, stats float64 [N, 16, 2] = (mean, rstd))."""
+    _require_gpu(x, weight, bias, res)
+    n, c = x.shape[0], x.shape[-1]
+    with torch.cuda.device(x.device):
+        ws = _gn_ws(n, c, x.device)
+        out, stats = torch.empty_like(x), torch.empty(n, 16, 2, dtype=torch.float64, device=x.device)
+        _call("i2v_disc3d_groupnorm_unit", x.data_ptr(), _opt(res), weight.data_ptr(), bias.data_ptr(), n, x[0].numel() // c, c, int(bool(relu)),
+              out.data_ptr(), stats.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+    return out, stats
+
+
+def disc3d_groupnorm_backward_unit(g, x, stats, weight, mask=None, dweight=None, dbias=None, param_grads=True):
+    """-> (dx, dweight, dbias); given ``dweight`` / ``dbias`` the parameter gradients are ADDED to them."""
+    _require_gpu(g, x, weight, mask, dweight, dbias)
+    n, c = x.shape[0], x.shape[-1]
+    accumulate = dweight is not None
+    with torch.cuda.device(x.device):
+        ws = _gn_ws(n, c, x.device)
+        dx = torch.empty_like(x)
+        if param_grads and not accumulate:
+            dweight, dbias = torch.empty_like(weight), torch.empty_like(weight)
+        _call("i2v_disc3d_groupnorm_backward_unit", g.data_ptr(), _opt(mask), x.data_ptr(), stats.data_ptr(), weight.data_ptr(), n, x[0].numel() // c, c,
+              dx.data_ptr(), _opt(dweight), _opt(dbias), int(accumulate), ws.data_ptr(), ws.numel(), _stream())
+    return dx, dweight, dbias
+
+
+def disc3d_maxpool_unit(x):
+    """MaxPool3d(3, stride (1, 2, 2), pad 1) on x [N, T, H, W, C] -> (out, argmax int32)."""
+    _require_gpu(x)
+    n, t, h, w, c = x.shape
+    with torch.cuda.device(x.device):
+        out = torch.empty(n, t, (h - 1) // 2 + 1, (w - 1) // 2 + 1, c, dtype=torch.float32, device=x.device)
+        arg = torch.empty(out.shape, dtype=torch.int32, device=x.device)
+        _call("i2v_disc3d_maxpool_unit", x.data_ptr(), n, t, h, w, c, out.data_ptr(), arg.data_ptr(), _stream())
+    return out, arg
+
+
+def disc3d_maxpool_backward_unit(g, argmax, in_shape):
+    _require_gpu(g)
+    n, t, h, w, c = in_shape
+    with torch.cuda.device(g.device):
+        dx = torch.empty(in_shape, dtype=torch.float32, device=g.device)
+        _call("i2v_disc3d_maxpool_backward_unit", g.data_ptr(), argmax.data_ptr(), n, t, h, w, c, dx.data_ptr(), _stream())
+    return dx
+
+
+def disc3d_head_unit(x, weight, g=None):
+    """x [N, 1, 4, 4, C], weight [1, C] -> pred [N, 1]; with g [N, 1] also (dx, dweight)."""
+    _require_gpu(x, weight, g)
+    n, c = x.shape[0], x.shape[-1]
+    with torch.cuda.device(x.device):
+        pred = torch.empty(n, 1, dtype=torch.float32, device=x.device)
+        dx, dw = (torch.empty_like(x), torch.empty_like(weight)) if g is not None else (None, None)
+        _call("i2v_disc3d_head_unit", x.data_ptr(), weight.data_ptr(), _opt(g), n, c, pred.data_ptr(), _opt(dx), _opt(dw), _stream())
+    return pred if g is None else (pred, dx, dw)

@@ -189,3 +189,74 @@ class PatchDiscTrainer:
         out, d_f, _ = native.patchdisc_hinge(pred, None, "gen")
         dx = self.disc._handle().backward(d_f, saved, tuple(data_fake.shape), need_dx=True, param_grads=False)   # (the gradient binding of step() stays)
         return out[0], dx
+
+
+class TemporalDiscTrainer:
+    """The temporal-discriminator part of the stage-1 step without autograd, on ``resnet3D.Discriminator``.  Clips are [B, T, 3, H, W] as
+    the step holds them (or [B, 3, T, H, W]; the module transposes as the reference does).  Everything is enqueued on the current
+    stream; no method synchronises the host.  Defaults: stage1_VAE/main.py and the shipped configs.
+
+    ``w_GP != 0`` is refused: the penalty's gradient needs the double backward of the whole network, which is not built (nor are the
+    decoder's and the motion encoder's backward, nor ``Backward.forward``).  ``gradient_penalty`` returns the penalty's VALUE, which is a
+    first-order quantity."""
+
+    def __init__(self, disc, lr=2e-4, betas=(0.5, 0.9), weight_decay=1e-5, w_GP=0, eps=1e-8, optimizer=None):
+        """``optimizer``: an optimiser over ``disc.parameters()`` to step instead of the fused Adam (the tests step plain SGD)."""
+        if w_GP:
+            raise NotImplementedError(f"TemporalDiscTrainer: w_GP = {w_GP} needs the gradient of the gradient penalty, i.e. the double backward of "
+                                      "resnet3D.Discriminator, which is not built; gradient_penalty() gives the penalty's value only")
+        self.disc = disc
+        self.optimizer = optimizer or FusedAdam(disc.parameters(), lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        self._ones = {}
+
+    def _grads(self):
+        for p in self.disc.parameters():
+            if p.grad is None:
+                p.grad = torch.zeros_like(p)
+        return {k: p.grad for k, p in self.disc.named_parameters()}
+
+    @staticmethod
+    def _shape(seq):
+        n, a, b, h, w = seq.shape
+        return (n, b, a, h, w) if a > b else (n, a, b, h, w)
+
+    @torch.no_grad()
+    def step(self, seq_fake, seq_real):
+        """loss.py:98-109 without the penalty: two forwards (each with its own power iteration), the hinge loss, two backwards that
+        accumulate into ``.grad``, the fused Adam step.  -> (L_d_t, mean real logit, mean fake logit) as float64 0-d device tensors."""
+        disc, grads = self.disc, self._grads()
+        pred_f, _, saved_f = disc._run(seq_fake, save=True, grads=grads, want_fmaps=False)
+        pred_r, _, saved_r = disc._run(seq_real, save=True, grads=grads, want_fmaps=False)
+        out, d_f, d_r = native.patchdisc_hinge(pred_f, pred_r, "disc")
+        h = disc._handle(grads)
+        h.backward(d_f, None, saved_f, self._shape(seq_fake), need_dx=False, param_grads=True, accumulate=False)
+        h.backward(d_r, None, saved_r, self._shape(seq_real), need_dx=False, param_grads=True, accumulate=True)
+        self.optimizer.step()
+        return out[0], out[1], out[2]
+
+    @torch.no_grad()
+    def generator_loss(self, seq_fake, seq_real, w_coup_t=1, w_fmap_t=10):
+        """loss.py:127-135: both forwards iterate the spectral norm, as the reference's do.  -> ((coup_t, L_fmap_t, L_temp) as float64 0-d
+        device tensors, the gradient of L_temp at ``seq_fake`` [B, 3, T, H, W]); ``.grad`` is left untouched."""
+        disc = self.disc
+        pred_f, fmap_f, saved = disc._run(seq_fake, save=True)
+        _, fmap_r, _ = disc._run(seq_real, save=False)
+        hinge, d_pred, _ = native.patchdisc_hinge(pred_f, None, "gen")
+        fm, d_fmaps = native.disc3d_fmap_loss(fmap_f, fmap_r, "L1", need_grads=True, grad_scale=float(w_fmap_t))
+        if w_coup_t != 1:
+            d_pred = d_pred * float(w_coup_t)
+        dx = disc._handle().backward(d_pred, d_fmaps, saved, self._shape(seq_fake), need_dx=True, param_grads=False)
+        return (hinge[0], fm[0], w_coup_t * hinge[0] + w_fmap_t * fm[0]), dx
+
+    @torch.no_grad()
+    def gradient_penalty(self, seq_real):
+        """The value of ``gradient_penalty(pred, x)`` (loss.py:35-43): the mean over the samples of the squared norm of the gradient of
+        ``mean(pred)`` at the clips, from one saved forward (it iterates in training mode, as a forward of the step does) and one
+        input-gradient backward.  -> float64 0-d device tensor."""
+        pred, _, saved = self.disc._run(seq_real, save=True, want_fmaps=False)
+        n = pred.shape[0]
+        d_pred = self._ones.get((n, pred.device))
+        if d_pred is None:
+            d_pred = self._ones[(n, pred.device)] = torch.full((n, 1), 1.0 / n, dtype=torch.float32, device=pred.device)
+        dx = self.disc._handle().backward(d_pred, None, saved, self._shape(seq_real), need_dx=True, param_grads=False)
+        return native.disc3d_sumsq(dx).mean()

@@ -1,6 +1,9 @@
 """Stage-1 losses and validation metrics, mirror of the reference's ``stage1_VAE/modules/loss.py``: ``KL``, ``fmap_loss``, ``hinge_loss`` and
 ``Backward`` with the reference's ``eval`` (loss.py:183-216).  The training step ``Backward.forward`` is not built; its
-spatial-discriminator lines (loss.py:111-125) are ``i2v_train.PatchDiscTrainer`` on ``patch_disc.NLayerDiscriminator``.
+spatial-discriminator lines (loss.py:111-125) are ``i2v_train.PatchDiscTrainer`` on ``patch_disc.NLayerDiscriminator``, its
+temporal-discriminator lines (loss.py:94-109 without the penalty, 127-135) ``i2v_train.TemporalDiscTrainer`` on ``resnet3D.Discriminator``.
+``fmap_loss`` and ``hinge_loss`` here are the reference's functions on torch tensors (they differentiate through the discriminators'
+autograd Functions); the trainers use the kernel forms ``i2v_native.disc3d_fmap_loss`` and ``i2v_native.patchdisc_hinge``.
 
 The reference takes ``psnr`` and ``ssim`` from ``pytorch_lightning.metrics.functional`` (1.2.7).  Here they are two kernel entries of
 csrc/i2v_recon.hip over frames that stay on the device: one range pass and one pass that forms the L1 error, the MSE and the SSIM map in
@@ -94,9 +97,10 @@ class Backward(nn.Module):
 
     def forward(self, decoder, encoder, disc_t, disc_s, seq_o, optimizers, epoch, logger):
         raise NotImplementedError("Backward.forward (the stage-1 training step, loss.py:64-180) is not built: it needs the backward passes of "
-                                  "the decoder and of the motion encoder and both discriminators.  Of the two discriminators the spatial one is "
-                                  "built (patch_disc.NLayerDiscriminator with i2v_train.PatchDiscTrainer: loss.py:111-125), and so is the LPIPS "
-                                  "gradient; the temporal one (resnet3D.Discriminator) with its gradient penalty is not; Backward.eval is built")
+                                  "the decoder and of the motion encoder and both discriminators.  The two discriminators are built "
+                                  "(patch_disc.NLayerDiscriminator with i2v_train.PatchDiscTrainer: loss.py:111-125; resnet3D.Discriminator with "
+                                  "i2v_train.TemporalDiscTrainer: loss.py:94-109, 127-135), and so is the LPIPS gradient; the gradient penalty's "
+                                  "double backward (w_GP) is not; Backward.eval is built")
 
     @torch.no_grad()
     def eval(self, decoder, encoder, seq_o, logger):

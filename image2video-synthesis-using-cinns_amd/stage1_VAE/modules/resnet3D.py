@@ -2,7 +2,7 @@
 of the coverage contract): 3D ResNet-18 with GroupNorm(16), ``conv_mu`` / ``conv_var`` heads.  The modules carry the
 reference's state_dict keys (``conv1.weight``, ``norm1.*``, ``layer.{L}.{i}.conv{1,2}.weight``, ``.bn{1,2}.*``,
 ``.downsample.{0.weight,1.*}``, ``conv_mu.*``, ``conv_var.*``); the arithmetic runs in libi2v_hip.so (csrc/i2v_encoder.hip).
-The discriminators of the same reference file are training-only and out of scope."""
+The temporal discriminator of the same reference file (``Discriminator``, lines 222-301) follows below the Encoder, on csrc/i2v_disc3d.hip."""
 import torch
 import torch.nn as nn
 
@@ -79,3 +79,188 @@ class Encoder(NativeBacked):
         x = x.contiguous()
         eps = torch.randn(x.size(0), self.z_dim).to(x.device)
         return self.native().forward(x, eps)
+
+
+# ---------------------------------------------------------------------------------------------------------------- Discriminator
+# The temporal discriminator ``disc_t`` of stage-1 training (reference resnet3D.py:222-301) on csrc/i2v_disc3d.hip (C ABI:
+# include/i2v_hip_disc3d.h).  State-dict keys, shapes and dtypes are the reference's, so a ``latest_checkpoint_DISC_t.pth`` loads unchanged:
+# ``conv1.weight``, ``norm1.*``, ``layer.L.0.conv{1,2}.{weight_orig,weight_u,weight_v}``, ``layer.L.1.conv{1,2}.weight``,
+# ``layer.L.i.bn{1,2}.*``, ``layer.L.0.downsample.0.{weight_orig,weight_u,weight_v}``, ``layer.L.0.downsample.1.*``, ``fc.weight``.
+# Semantics kept:
+#   * spectral norm covers conv1 / conv2 of block 0 of a layer (``spectral_norm`` of the config) and the downsample conv (always); block
+#     1, the stem and ``fc`` are plain.  Training mode does one power iteration per wrapped conv and forward, in place; eval mode uses the
+#     stored vectors.  A backward uses the u, v and sigma of ITS forward; ``weight_orig`` and the GroupNorm weights are read when the
+#     backward runs, so they must not change between a forward and its backward;
+#   * the downsample branch exists when ``stride != 1 or inplanes != planes or stride_t != 1`` (the Encoder's rule lacks the last term);
+#   * ``nn.init.orthogonal_`` reaches ``m.weight`` of every Conv3d; on a spectral-normed conv that attribute is ``weight_orig.data`` (what
+#     ``spectral_norm`` leaves there until the first forward), so the in-place init lands in ``weight_orig`` as well.  The constructor makes
+#     the reference's draws in the reference's order (the default init of every conv and the u, v draws come first and are overwritten);
+#   * ``x`` is transposed when ``x.size(1) > x.size(2)``.
+# One difference: the reference starts the layers from ``inplanes = 64`` whatever ``channels[0]`` is (so it only runs with a 64-wide stem,
+# as in every shipped config); here the first layer takes ``channels[0]`` inputs, which is the same network at 64 and a working one below.
+# In grad mode ``forward`` returns tensors with a ``grad_fn`` (once differentiable: the gradient penalty's double backward is not built);
+# the parameters are inputs of the Function; a frozen module skips the weight-gradient launches.  CPU tensors raise ``I2VError``.
+
+
+class _DiscInside(_NoForward):
+    pass
+
+
+class _DiscConv(_DiscInside):
+    """nn.Conv3d(cin, cout, kernel, bias=False) with its default init, optionally as torch.nn.utils.spectral_norm leaves it."""
+
+    def __init__(self, cin, cout, kernel=(3, 3, 3)):
+        super().__init__()
+        self.weight = nn.Parameter(nn.Conv3d(cin, cout, kernel_size=kernel, bias=False).weight.data)
+        self.spectral = False
+
+    def wrap_spectral(self, eps=1e-12):
+        w = self.weight
+        del self.weight
+        self.register_parameter("weight_orig", w)
+        with torch.no_grad():
+            u = nn.functional.normalize(w.new_empty(w.shape[0]).normal_(0, 1), dim=0, eps=eps)
+            v = nn.functional.normalize(w.new_empty(w[0].numel()).normal_(0, 1), dim=0, eps=eps)
+        self.register_buffer("weight_u", u)
+        self.register_buffer("weight_v", v)
+        self.spectral = True
+        return self
+
+    def init_orthogonal(self):
+        """``m.weight = nn.init.orthogonal_(m.weight)`` (resnet3D.py:259-261): on a wrapped conv ``m.weight`` shares ``weight_orig``'s storage."""
+        with torch.no_grad():
+            nn.init.orthogonal_(self.weight_orig if self.spectral else self.weight)
+
+
+class DiscBasicBlock(_DiscInside):
+    """BasicBlock as the Discriminator builds it (resnet3D.py:101-117): registration order conv1, bn1, conv2, bn2, downsample."""
+    expansion = 1
+
+    def __init__(self, inplanes, planes, stride=1, stride_t=1, downsample=None, spectral=False):
+        super().__init__()
+        self.conv1 = _DiscConv(inplanes, planes)
+        self.bn1 = AffineParams(planes)
+        self.conv2 = _DiscConv(planes, planes)
+        self.bn2 = AffineParams(planes)
+        if downsample is not None:
+            self.downsample = downsample
+        self.stride, self.stride_t = stride, stride_t
+        if spectral:
+            self.conv1.wrap_spectral()
+            self.conv2.wrap_spectral()
+
+
+class _Disc3DFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, module, x, *params):
+        pred, fmaps, saved = module._run(x, save=True)
+        ctx.module, ctx.saved, ctx.shape = module, saved, tuple(x.shape)
+        return (pred, *[f.permute(0, 4, 1, 2, 3) for f in fmaps])
+
+    @staticmethod
+    def backward(ctx, d_pred, *d_fmaps):
+        if torch.is_grad_enabled():   # create_graph=True: a graph through this backward is asked for
+            raise NotImplementedError("resnet3D.Discriminator is once differentiable: the double backward (create_graph=True, the gradient "
+                                      "penalty's gradient) is not built")
+        module = ctx.module
+        want = ctx.needs_input_grad[2:]
+        grads = None
+        if any(want):
+            names = [k for k, _ in module.named_parameters()]
+            sizes = [(p.numel() + 3) // 4 * 4 for p in module.parameters()]
+            flat = torch.empty(sum(sizes), dtype=torch.float32, device=ctx.saved.device)
+            views = [v[:p.numel()].view(p.shape) for v, p in zip(flat.split(sizes), module.parameters())]
+            grads = dict(zip(names, views))
+        h = module._handle(grads)
+        cl = [None if g is None else g.permute(0, 2, 3, 4, 1).contiguous().float() for g in d_fmaps]
+        dx = h.backward(None if d_pred is None else d_pred.contiguous().float(), cl, ctx.saved, ctx.shape, need_dx=ctx.needs_input_grad[1],
+                        param_grads=grads is not None, accumulate=False)
+        out = [None] * len(want) if grads is None else [g if w else None for g, w in zip(grads.values(), want)]
+        return (None, dx, *out)
+
+
+class Discriminator(nn.Module):
+    """resnet3D.Discriminator(dic) (reference resnet3D.py:222-301): ``forward(x) -> (pred [B, 1], [fmap0 .. fmap3])``."""
+
+    def __init__(self, dic):
+        super().__init__()
+        if dic["res_type_encoder"] != "resnet18":
+            raise NotImplementedError(f"Discriminator: res_type_encoder {dic['res_type_encoder']!r} is not built (every shipped config uses 'resnet18')")
+        self.use_spectral_norm = bool(dic["spectral_norm"])
+        self.use_max_pool = bool(dic["use_max_pool"])
+        channels, stride_s, stride_t = list(dic["channels"]), list(dic["stride_s"]), list(dic["stride_t"])
+        assert len(channels) - 1 == len(stride_t)
+        assert len(channels) - 1 == len(stride_s)
+        if len(channels) != 5 or any(c <= 0 or c % 16 for c in channels) or any(s not in (1, 2) for s in stride_s + stride_t):
+            raise native.I2VError(f"Discriminator: channels {channels} (five multiples of 16) or strides {stride_s} / {stride_t} (1 or 2) are not built")
+        self.cfg = dict(channels=channels, stride_s=stride_s, stride_t=stride_t, use_max_pool=self.use_max_pool, spectral_norm=self.use_spectral_norm)
+
+        self.conv1 = _DiscConv(3, channels[0], (3, 7, 7))
+        self.norm1 = AffineParams(channels[0])
+        self.inplanes = channels[0]
+        layers = []
+        for i, ch in enumerate(channels[1:]):
+            layers.append(self._make_layer(ch, 2, stride=stride_s[i], stride_t=stride_t[i]))
+        self.layer = nn.Sequential(*layers)
+        self.fc = _DiscInside()
+        self.fc.weight = nn.Parameter(nn.Linear(channels[-1], 1, bias=False).weight.data)
+        for m in self.modules():
+            if isinstance(m, _DiscConv):
+                m.init_orthogonal()
+        object.__setattr__(self, "_native", None)
+
+    def _make_layer(self, planes, blocks, stride=1, stride_t=1):
+        downsample = None
+        if stride != 1 or self.inplanes != planes or stride_t != 1:
+            downsample = nn.Sequential(_DiscConv(self.inplanes, planes).wrap_spectral(), AffineParams(planes))
+        layers = [DiscBasicBlock(self.inplanes, planes, stride, stride_t, downsample, self.use_spectral_norm)]
+        self.inplanes = planes
+        for _ in range(1, blocks):
+            layers.append(DiscBasicBlock(self.inplanes, planes))
+        return nn.Sequential(*layers)
+
+    def __getstate__(self):
+        state = dict(super().__getstate__() if hasattr(super(), "__getstate__") else self.__dict__)
+        state["_native"] = None
+        return state
+
+    # ---- native side
+    def _tensors(self):
+        return {k: t for k, t in list(self.named_parameters()) + list(self.named_buffers()) if t.dtype == torch.float32}
+
+    def _handle(self, grads=None):
+        """The handle, bound to the storage of the parameters as it is now and, when ``grads`` ({parameter name: tensor}) is given, to
+        those gradient tensors; the two bindings are kept apart."""
+        tensors = self._tensors()
+        for t in tensors.values():
+            if not t.is_cuda:
+                raise native.I2VError("Discriminator runs on a HIP device only: move the module to 'cuda' (this package has no CPU fallback)")
+        h = self._native
+        dev = next(iter(tensors.values())).device
+        if h is None or h.device != dev:
+            h = native.NativeDisc3D(device=dev, **self.cfg)
+            object.__setattr__(self, "_native", h)
+        if h.bound_ptrs != tuple(t.data_ptr() for t in tensors.values()):
+            h.bind({k: t.detach().view(-1) for k, t in tensors.items()})
+        if grads is not None and h.bound_grad_ptrs != tuple(g.data_ptr() for g in grads.values()):
+            h.bind_grads({k: g.detach().view(-1) for k, g in grads.items()})
+        return h
+
+    def _run(self, x, save, grads=None, want_fmaps=True):
+        """x [B, 3, T, H, W] -> (pred, channels-last feature maps or None, saved or None); training mode iterates the spectral norm."""
+        if not x.is_cuda:
+            raise native.I2VError("Discriminator got a CPU tensor: its kernels run on a HIP device only (this package has no CPU fallback)")
+        if x.size(1) > x.size(2):
+            x = x.transpose(1, 2)
+        with torch.no_grad():
+            return self._handle(grads).forward(x.detach().float().contiguous(), iterate=self.training, save=save, want_fmaps=want_fmaps)
+
+    def forward(self, x):
+        if x.dim() == 5 and x.size(1) > x.size(2):
+            x = x.transpose(1, 2)
+        params = list(self.parameters())
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
+            pred, *fmaps = _Disc3DFunction.apply(self, x, *params)
+            return pred, list(fmaps)
+        pred, fmaps, _ = self._run(x, save=False)
+        return pred, [f.permute(0, 4, 1, 2, 3) for f in fmaps]
