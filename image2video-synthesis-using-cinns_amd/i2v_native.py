@@ -74,6 +74,10 @@ class Disc3DCfg(ctypes.Structure):
                 ("spectral_norm", c_int32)]
 
 
+class Enc3dTrainCfg(ctypes.Structure):
+    _fields_ = [("z_dim", c_int32), ("channels", c_int32 * 5), ("stride_s", c_int32 * 4), ("stride_t", c_int32 * 4), ("use_max_pool", c_int32)]
+
+
 _lib = None
 
 # symbol -> (restype, argtypes); also the list the CPU test-suite checks the .so exports
@@ -298,6 +302,30 @@ DISC3D_SYMBOLS = {
     "i2v_disc3d_head_unit": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
+# The entries of include/i2v_hip_enc3d_train.h (the training path of the motion encoder), one to one.
+ENC3D_TRAIN_SYMBOLS = {
+    "i2v_enc3d_train_create": (c_int32, [POINTER(Enc3dTrainCfg), POINTER(c_void_p)]),
+    "i2v_enc3d_train_destroy": (None, [c_void_p]),
+    "i2v_enc3d_train_bind": (c_int32, [c_void_p, POINTER(_Tensor), c_int32]),
+    "i2v_enc3d_train_bind_grads": (c_int32, [c_void_p, POINTER(_Tensor), c_int32]),
+    "i2v_enc3d_train_out_shape": (c_int32, [c_void_p, c_int32, c_int32, c_int32, POINTER(c_int32)]),
+    "i2v_enc3d_train_saved_bytes": (c_size_t, [c_void_p, c_int32, c_int32, c_int32, c_int32]),
+    "i2v_enc3d_train_workspace_bytes": (c_size_t, [c_void_p, c_int32, c_int32, c_int32, c_int32]),
+    "i2v_enc3d_train_saved_layout": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32),
+                                               POINTER(c_int32), POINTER(c_int64)]),
+    "i2v_enc3d_train_forward": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
+    "i2v_enc3d_train_backward": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_size_t, c_int32, c_int32, c_int32, c_int32,
+                                           c_void_p, c_int32, c_int32, c_void_p, c_size_t, c_void_p]),
+    "i2v_enc3d_kl_backward": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_float, c_void_p, c_void_p, c_void_p]),
+    "i2v_enc3d_head_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
+    "i2v_enc3d_head_forward_unit": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                              c_void_p, c_void_p, c_size_t, c_void_p]),
+    "i2v_enc3d_head_backward_unit": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
+                                               c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_size_t,
+                                               c_void_p]),
+}
+
 
 def build(force=False):
     """Compile ``libi2v_hip.so`` for gfx950 in-tree (``make`` in csrc/; hipcc cross-compiles without a GPU)."""
@@ -329,7 +357,7 @@ def lib():
             raise I2VError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                            f"or `make -C {CSRC}`; this package has no CPU/eager fallback")
         l = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SYMBOLS.items()) + list(DISC_SYMBOLS.items()) + list(DISC3D_SYMBOLS.items()):
+        for name, (res, args) in list(SYMBOLS.items()) + list(DISC_SYMBOLS.items()) + list(DISC3D_SYMBOLS.items()) + list(ENC3D_TRAIN_SYMBOLS.items()):
             fn = getattr(l, name)
             fn.restype = res
             fn.argtypes = args
@@ -2395,3 +2423,151 @@ def disc3d_head_unit(x, weight, g=None):
         dx, dw = (torch.empty_like(x), torch.empty_like(weight)) if g is not None else (None, None)
         _call("i2v_disc3d_head_unit", x.data_ptr(), weight.data_ptr(), _opt(g), n, c, pred.data_ptr(), _opt(dx), _opt(dw), _stream())
     return pred if g is None else (pred, dx, dw)
+
+
+# ---------------------------------------------------------------------------------------------------------------- motion encoder, training path
+ENC3D_TRAIN_SAVE = 1
+ENC3D_TRAIN_CONV_OUT, ENC3D_TRAIN_ACT = 0, 1
+
+
+class NativeEnc3DTrain(_Handle):
+    """Handle for ``i2v_enc3d_train_*`` (include/i2v_hip_enc3d_train.h): resnet3D.Encoder forward and backward with the posterior head and
+    the KL gradient.  It packs nothing on the host: ``bind`` hands over the DEVICE pointers of the module's parameters (read in place, so
+    an optimiser step is seen by the next call) and ``bind_grads`` those of their gradient tensors."""
+    _PREFIX = "i2v_enc3d_train"
+
+    def __init__(self, z_dim, channels, stride_s, stride_t, use_max_pool=False, device=None):
+        if len(channels) != 5 or len(stride_s) != 4 or len(stride_t) != 4:
+            raise I2VError(f"motion encoder: {len(channels)} widths with {len(stride_s)} / {len(stride_t)} strides (5 and 4 are built)")
+        cfg = Enc3dTrainCfg(int(z_dim), (c_int32 * 5)(*map(int, channels)), (c_int32 * 4)(*map(int, stride_s)), (c_int32 * 4)(*map(int, stride_t)),
+                            int(bool(use_max_pool)))
+        self._create(device, ctypes.byref(cfg))
+        self.z_dim = int(z_dim)
+        self.bound_ptrs, self.bound_grad_ptrs, self._keep, self._keep_grads = None, None, None, None
+
+    def load(self, state_dict):
+        raise I2VError("NativeEnc3DTrain packs nothing: bind() hands over the module's own parameters")
+
+    def bind(self, tensors):
+        """tensors: {state_dict key: float32 device tensor} of the parameters."""
+        with self._on(*tensors.values()):
+            arr, keep = NativePatchDisc._items(tensors)
+            _call("i2v_enc3d_train_bind", self._h, arr, len(keep))
+        self.bound_ptrs = tuple(t.data_ptr() for t in tensors.values())
+        self._keep = tensors
+
+    def bind_grads(self, grads):
+        """grads: {key: gradient tensor} of the parameters, or None."""
+        if grads is None:
+            _call("i2v_enc3d_train_bind_grads", self._h, None, 0)
+        else:
+            with self._on(*grads.values()):
+                arr, keep = NativePatchDisc._items(grads)
+                _call("i2v_enc3d_train_bind_grads", self._h, arr, len(keep))
+        self.bound_grad_ptrs = None if grads is None else tuple(g.data_ptr() for g in grads.values())
+        self._keep_grads = grads
+
+    def out_shape(self, t, h, w):
+        """(t, h, w, c) of the trunk's last map; raises with the map in the message unless it is [1, 4, 4]."""
+        s = (c_int32 * 4)()
+        _call("i2v_enc3d_train_out_shape", self._h, int(t), int(h), int(w), s)
+        return tuple(s)
+
+    def _shape(self, x):
+        if x.dim() != 5 or x.shape[1] != 3:
+            raise I2VError(f"motion encoder: expected clips [N, 3, T, H, W], got {tuple(x.shape)}")
+        n, _, t, h, w = x.shape
+        return n, t, h, w
+
+    def saved_bytes(self, n, t, h, w):
+        return int(lib().i2v_enc3d_train_saved_bytes(self._h, n, t, h, w))
+
+    def workspace_bytes(self, n, t, h, w):
+        return int(lib().i2v_enc3d_train_workspace_bytes(self._h, n, t, h, w))
+
+    def saved_maps(self, saved, shape):
+        """{(kind, conv): view of ``saved`` [N, T, H, W, C]} (kinds ENC3D_TRAIN_*), for the tests."""
+        n, _, t, h, w = shape
+        cnt, kind, conv, dims, off = c_int32(), (c_int32 * 64)(), (c_int32 * 64)(), (c_int32 * 256)(), (c_int64 * 64)()
+        _call("i2v_enc3d_train_saved_layout", self._h, n, t, h, w, ctypes.byref(cnt), kind, conv, dims, off)
+        out, flat = {}, saved.view(torch.float32)
+        for e in range(cnt.value):
+            shp = (n, *dims[4 * e: 4 * e + 4])
+            out[(kind[e], conv[e])] = flat[off[e] // 4: off[e] // 4 + int(np.prod(shp))].view(shp)
+        return out
+
+    @_on_device
+    def forward(self, x, eps=None, save=False):
+        """x [N, 3, T, H, W], eps [N, z] or None -> (sample or None, mu, logvar, saved or None)."""
+        _require_gpu(x, eps)
+        n, t, h, w = self._shape(x)
+        if eps is not None and tuple(eps.shape) != (n, self.z_dim):
+            raise I2VError(f"motion encoder: expected eps [{n},{self.z_dim}], got {tuple(eps.shape)}")
+        self.out_shape(t, h, w)
+        ws = self._scratch(self.workspace_bytes(n, t, h, w), x.device)
+        saved = torch.empty(self.saved_bytes(n, t, h, w), dtype=torch.uint8, device=x.device) if save else None
+        mu = torch.empty(n, self.z_dim, dtype=torch.float32, device=x.device)
+        logvar = torch.empty_like(mu)
+        sample = torch.empty_like(mu) if eps is not None else None
+        _call("i2v_enc3d_train_forward", self._h, x.data_ptr(), _opt(eps), n, t, h, w, ENC3D_TRAIN_SAVE if save else 0, _opt(sample), mu.data_ptr(),
+              logvar.data_ptr(), _opt(saved), 0 if saved is None else saved.numel(), *ws, _stream())
+        return sample, mu, logvar, saved
+
+    @_on_device
+    def backward(self, d_sample, d_mu, d_logvar, saved, shape, kl_scale=0.0, need_dx=True, param_grads=True, accumulate=False):
+        """``shape``: the (N, 3, T, H, W) of the forward's input; the upstream gradients [N, z] or None -> d_x [N, 3, T, H, W] or None; the
+        parameter gradients go to the bound gradient tensors, written or (``accumulate``) added."""
+        _require_gpu(d_sample, d_mu, d_logvar)
+        n, _, t, h, w = shape
+        ws = self._scratch(self.workspace_bytes(n, t, h, w), saved.device)
+        dx = torch.empty(n, 3, t, h, w, dtype=torch.float32, device=saved.device) if need_dx else None
+        _call("i2v_enc3d_train_backward", self._h, _opt(d_sample), _opt(d_mu), _opt(d_logvar), float(kl_scale), saved.data_ptr(), saved.numel(), n, t, h,
+              w, _opt(dx), int(bool(param_grads)), int(bool(accumulate)), *ws, _stream())
+        return dx
+
+
+def enc3d_kl_backward(mu, logvar, scale=1.0):
+    """The gradient of ``scale * KL(mu, logvar)`` (loss.py:10-12) -> (d_mu, d_logvar) fp32 [N, z]."""
+    _require_gpu(mu, logvar)
+    n, z = mu.shape
+    with torch.cuda.device(mu.device):
+        d_mu, d_lv = torch.empty_like(mu), torch.empty_like(logvar)
+        _call("i2v_enc3d_kl_backward", mu.data_ptr(), logvar.data_ptr(), n, z, float(scale), d_mu.data_ptr(), d_lv.data_ptr(), _stream())
+    return d_mu, d_lv
+
+
+def _enc3d_head_ws(n, c, z, device):
+    return torch.empty(int(lib().i2v_enc3d_head_workspace_bytes(n, c, z)), dtype=torch.uint8, device=device)
+
+
+def enc3d_head_forward_unit(emb, w_mu, b_mu, w_var, b_var, eps=None):
+    """emb [N, 16, C] channels-last, weights [z, C, 4, 4], biases [z] -> (sample or None, mu, logvar) [N, z]."""
+    _require_gpu(emb, w_mu, b_mu, w_var, b_var, eps)
+    n, c, z = emb.shape[0], emb.shape[-1], w_mu.shape[0]
+    with torch.cuda.device(emb.device):
+        ws = _enc3d_head_ws(n, c, z, emb.device)
+        mu = torch.empty(n, z, dtype=torch.float32, device=emb.device)
+        logvar = torch.empty_like(mu)
+        sample = torch.empty_like(mu) if eps is not None else None
+        _call("i2v_enc3d_head_forward_unit", emb.data_ptr(), w_mu.data_ptr(), b_mu.data_ptr(), w_var.data_ptr(), b_var.data_ptr(), _opt(eps), n, c, z,
+              _opt(sample), mu.data_ptr(), logvar.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+    return sample, mu, logvar
+
+
+def enc3d_head_backward_unit(emb, w_mu, w_var, mu, logvar, eps=None, d_sample=None, d_mu=None, d_logvar=None, kl_scale=0.0, param_grads=True,
+                             into=None):
+    """-> (d_emb [N, 16, C], dw_mu, db_mu, dw_var, db_var); given ``into`` (those four tensors) the parameter gradients are ADDED to them."""
+    _require_gpu(emb, w_mu, w_var, mu, logvar, eps, d_sample, d_mu, d_logvar)
+    n, c, z = emb.shape[0], emb.shape[-1], w_mu.shape[0]
+    with torch.cuda.device(emb.device):
+        ws = _enc3d_head_ws(n, c, z, emb.device)
+        d_emb = torch.empty_like(emb)
+        grads = into
+        if param_grads and into is None:
+            grads = (torch.empty_like(w_mu), torch.empty(z, dtype=torch.float32, device=emb.device), torch.empty_like(w_var),
+                     torch.empty(z, dtype=torch.float32, device=emb.device))
+        g = grads if param_grads else (None,) * 4
+        _call("i2v_enc3d_head_backward_unit", emb.data_ptr(), w_mu.data_ptr(), w_var.data_ptr(), mu.data_ptr(), logvar.data_ptr(), _opt(eps),
+              _opt(d_sample), _opt(d_mu), _opt(d_logvar), float(kl_scale), n, c, z, d_emb.data_ptr(), *[_opt(t) for t in g], int(into is not None),
+              ws.data_ptr(), ws.numel(), _stream())
+    return (d_emb, *g)

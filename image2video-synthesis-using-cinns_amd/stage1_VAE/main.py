@@ -9,8 +9,9 @@ try:
 except ImportError:  # progress bars are optional
     tqdm = None
 
-NOT_BUILT = ("stage-1 training is not built: Backward.forward needs the backward passes of the decoder and of the motion encoder and the two "
-             "discriminators (stage1_VAE/modules/loss.py); validation is -- build the models (stage1_VAE.modules.decoder.Generator, "
+NOT_BUILT = ("stage-1 training is not built: of the backward passes Backward.forward needs, those of the motion encoder and of the two "
+             "discriminators exist, the decoder's and the gradient penalty's double backward do not (stage1_VAE/modules/loss.py); validation "
+             "is -- build the models (stage1_VAE.modules.decoder.Generator, "
              "resnet3D.Encoder), a Backward(opt, lpips) and call validator(...) on your own iterable of {'seq': ...} batches, or run "
              "eval_reconstruction.py on a stage-1 checkpoint directory (README: Scoring a stage-1 checkpoint)")
 

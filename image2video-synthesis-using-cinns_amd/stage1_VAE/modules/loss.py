@@ -1,5 +1,6 @@
 """Stage-1 losses and validation metrics, mirror of the reference's ``stage1_VAE/modules/loss.py``: ``KL``, ``fmap_loss``, ``hinge_loss`` and
-``Backward`` with the reference's ``eval`` (loss.py:183-216).  The training step ``Backward.forward`` is not built; its
+``Backward`` with the reference's ``eval`` (loss.py:183-216).  The training step ``Backward.forward`` is not built (the decoder backward and
+the penalty's double backward are missing; the motion encoder trains through ``resnet3D.Encoder.differentiable``, ``KL`` has a gradient); its
 spatial-discriminator lines (loss.py:111-125) are ``i2v_train.PatchDiscTrainer`` on ``patch_disc.NLayerDiscriminator``, its
 temporal-discriminator lines (loss.py:94-109 without the penalty, 127-135) ``i2v_train.TemporalDiscTrainer`` on ``resnet3D.Discriminator``.
 ``fmap_loss`` and ``hinge_loss`` here are the reference's functions on torch tensors (they differentiate through the discriminators'
@@ -22,11 +23,32 @@ import torch.nn as nn
 import i2v_native
 
 
+class _KLFunction(torch.autograd.Function):
+    """``i2v_kl_normal`` with the kernel gradient ``i2v_enc3d_kl_backward``: mu / n and (e^logvar - 1) / (2 n), fp32 [B, z]."""
+
+    @staticmethod
+    def forward(ctx, mu, logvar):
+        ctx.save_for_backward(mu, logvar)
+        return i2v_native.kl_normal(mu, logvar)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        mu, logvar = ctx.saved_tensors
+        d_mu, d_lv = i2v_native.enc3d_kl_backward(mu, logvar, 1.0)
+        g = g.to(torch.float32)
+        return (d_mu * g if ctx.needs_input_grad[0] else None), (d_lv * g if ctx.needs_input_grad[1] else None)
+
+
 def KL(mu, logvar):
     """KL divergence between N(mu, exp(logvar)) and the unit Gaussian (loss.py:10-12).  On a HIP device: ``i2v_kl_normal`` (one
-    workgroup, float64, fixed order) -> float64 0-d device tensor.  CPU tensors are refused (no CPU fallback)."""
+    workgroup, float64, fixed order) -> float64 0-d device tensor.  CPU tensors are refused (no CPU fallback).  In grad mode, with an
+    argument that requires grad, the same value carries a ``grad_fn`` (the kernel gradient of ``i2v_enc3d_kl_backward``)."""
     mu, logvar = mu.reshape(mu.size(0), -1), logvar.reshape(logvar.size(0), -1)
-    return i2v_native.kl_normal(mu.float().contiguous(), logvar.float().contiguous())
+    mu, logvar = mu.float().contiguous(), logvar.float().contiguous()
+    if torch.is_grad_enabled() and (mu.requires_grad or logvar.requires_grad):
+        return _KLFunction.apply(mu, logvar)
+    return i2v_native.kl_normal(mu, logvar)
 
 
 def fmap_loss(fmap1, fmap2, metric):
@@ -96,11 +118,12 @@ class Backward(nn.Module):
         self.curves = []
 
     def forward(self, decoder, encoder, disc_t, disc_s, seq_o, optimizers, epoch, logger):
-        raise NotImplementedError("Backward.forward (the stage-1 training step, loss.py:64-180) is not built: it needs the backward passes of "
-                                  "the decoder and of the motion encoder and both discriminators.  The two discriminators are built "
-                                  "(patch_disc.NLayerDiscriminator with i2v_train.PatchDiscTrainer: loss.py:111-125; resnet3D.Discriminator with "
-                                  "i2v_train.TemporalDiscTrainer: loss.py:94-109, 127-135), and so is the LPIPS gradient; the gradient penalty's "
-                                  "double backward (w_GP) is not; Backward.eval is built")
+        raise NotImplementedError("Backward.forward (the stage-1 training step, loss.py:64-180) is not built: of the backward passes it needs, "
+                                  "the decoder's and the gradient penalty's double backward (w_GP) are still missing.  Built are the two "
+                                  "discriminators (patch_disc.NLayerDiscriminator with i2v_train.PatchDiscTrainer: loss.py:111-125; "
+                                  "resnet3D.Discriminator with i2v_train.TemporalDiscTrainer: loss.py:94-109, 127-135), the LPIPS gradient, and the "
+                                  "motion-encoder backward with the KL gradient (resnet3D.Encoder.differentiable = True; KL returns a grad_fn); "
+                                  "Backward.eval is built")
 
     @torch.no_grad()
     def eval(self, decoder, encoder, seq_o, logger):

@@ -2,7 +2,8 @@
 of the coverage contract): 3D ResNet-18 with GroupNorm(16), ``conv_mu`` / ``conv_var`` heads.  The modules carry the
 reference's state_dict keys (``conv1.weight``, ``norm1.*``, ``layer.{L}.{i}.conv{1,2}.weight``, ``.bn{1,2}.*``,
 ``.downsample.{0.weight,1.*}``, ``conv_mu.*``, ``conv_var.*``); the arithmetic runs in libi2v_hip.so (csrc/i2v_encoder.hip).
-The temporal discriminator of the same reference file (``Discriminator``, lines 222-301) follows below the Encoder, on csrc/i2v_disc3d.hip."""
+The temporal discriminator of the same reference file (``Discriminator``, lines 222-301) follows below the Encoder, on csrc/i2v_disc3d.hip;
+below it, the Encoder's opt-in training path (``Encoder.differentiable``) on csrc/i2v_encoder_train.hip."""
 import torch
 import torch.nn as nn
 
@@ -264,3 +265,110 @@ class Discriminator(nn.Module):
             return pred, list(fmaps)
         pred, fmaps, _ = self._run(x, save=False)
         return pred, [f.permute(0, 4, 1, 2, 3) for f in fmaps]
+
+
+# ---------------------------------------------------------------------------------------------------------------- Encoder, training path
+# ``Encoder`` as the package exports it: the class above (the packed, forward-only handle of csrc/i2v_encoder.hip) plus the opt-in
+# training path on csrc/i2v_encoder_train.hip (C ABI: include/i2v_hip_enc3d_train.h).  ``differentiable`` is a plain attribute, default
+# False, not a constructor argument (as ``ConditionalFlow.differentiable``): while it is False every call runs the inference handle
+# exactly as before, in grad mode too.  With ``differentiable = True`` every forward runs on the training handle, which reads the
+# parameters in place (an optimiser step is seen by the next call, no refresh); in grad mode it returns ``(sample, mu, logvar)`` with a
+# ``grad_fn`` from a Function that takes the parameters as inputs; a frozen module skips the weight-gradient launches;
+# ``create_graph=True`` raises.  Setting it back to False calls ``refresh_native()``, so the packed handle is rebuilt from the current
+# parameters.  ``eps`` is drawn as above (``torch.randn(B, z)`` on the CPU generator) unless the caller passes ``eps=``.
+
+_PackedEncoder = Encoder
+
+
+class _Enc3DTrainFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, module, x, eps, *params):
+        sample, mu, logvar, saved = module._train_handle().forward(x, eps, save=True)
+        ctx.module, ctx.saved, ctx.shape = module, saved, tuple(x.shape)
+        ctx.set_materialize_grads(False)   # an output that the loss does not use arrives as None, not as zeros
+        return sample, mu, logvar
+
+    @staticmethod
+    def backward(ctx, d_sample, d_mu, d_logvar):
+        if torch.is_grad_enabled():   # create_graph=True: a graph through this backward is asked for
+            raise NotImplementedError("resnet3D.Encoder is once differentiable: the double backward (create_graph=True) is not built")
+        module = ctx.module
+        want = ctx.needs_input_grad[3:]
+        ups = [None if g is None else g.contiguous().float() for g in (d_sample, d_mu, d_logvar)]
+        if all(g is None for g in ups):
+            return (None,) * (3 + len(want))
+        grads = None
+        if any(want):
+            names = [k for k, _ in module.named_parameters()]
+            sizes = [(p.numel() + 3) // 4 * 4 for p in module.parameters()]
+            flat = torch.empty(sum(sizes), dtype=torch.float32, device=ctx.saved.device)
+            views = [v[:p.numel()].view(p.shape) for v, p in zip(flat.split(sizes), module.parameters())]
+            grads = dict(zip(names, views))
+        h = module._train_handle(grads)
+        dx = h.backward(*ups, ctx.saved, ctx.shape, need_dx=ctx.needs_input_grad[1] or grads is None, param_grads=grads is not None, accumulate=False)
+        out = [None] * len(want) if grads is None else [g if w else None for g, w in zip(grads.values(), want)]
+        return (None, dx if ctx.needs_input_grad[1] else None, None, *out)
+
+
+class Encoder(_PackedEncoder):
+    def __init__(self, dic):
+        super().__init__(dic)
+        object.__setattr__(self, "_train_native", None)
+        object.__setattr__(self, "_differentiable", False)
+
+    @property
+    def differentiable(self):
+        return self.__dict__.get("_differentiable", False)
+
+    @differentiable.setter
+    def differentiable(self, value):
+        value = bool(value)
+        if not value and self.differentiable:
+            self.refresh_native()
+        object.__setattr__(self, "_differentiable", value)
+
+    def _drop_native(self):
+        super()._drop_native()
+        object.__setattr__(self, "_train_native", None)
+
+    def __getstate__(self):
+        state = dict(super().__getstate__() if hasattr(super(), "__getstate__") else self.__dict__)
+        state["_native"] = state["_train_native"] = None
+        return state
+
+    def _train_handle(self, grads=None):
+        """The training handle, bound to the storage of the parameters as it is now and, when ``grads`` ({parameter name: tensor}) is
+        given, to those gradient tensors."""
+        tensors = dict(self.named_parameters())
+        for t in tensors.values():
+            if not t.is_cuda:
+                raise native.I2VError("Encoder runs on a HIP device only: move the module to 'cuda' (this package has no CPU fallback)")
+        h = self.__dict__.get("_train_native")
+        dev = next(iter(tensors.values())).device
+        if h is None or h.device != dev:
+            h = native.NativeEnc3DTrain(self.z_dim, self.channels, self.stride_s, self.stride_t, device=dev)
+            object.__setattr__(self, "_train_native", h)
+        if h.bound_ptrs != tuple(t.data_ptr() for t in tensors.values()):
+            h.bind({k: t.detach().view(-1) for k, t in tensors.items()})
+        if grads is not None and h.bound_grad_ptrs != tuple(g.data_ptr() for g in grads.values()):
+            h.bind_grads({k: g.detach().view(-1) for k, g in grads.items()})
+        return h
+
+    def forward(self, x, eps=None):
+        """As the inference forward; ``eps`` [B, z]: the reparameterisation's draw, when the caller supplies it."""
+        if not self.differentiable and eps is None:
+            return super().forward(x)
+        if x.size(1) > x.size(2):
+            x = x.transpose(1, 2)
+        if not x.is_cuda:
+            raise native.I2VError("Encoder got a CPU tensor: its kernels run on a HIP device only (this package has no CPU fallback)")
+        if eps is None:
+            eps = torch.randn(x.size(0), self.z_dim)
+        eps = eps.detach().to(x.device, torch.float32).contiguous()
+        if not self.differentiable:
+            return self.native().forward(x.detach().float().contiguous(), eps)
+        params = list(self.parameters())
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
+            return _Enc3DTrainFunction.apply(self, x.float().contiguous(), eps, *params)
+        with torch.no_grad():
+            return self._train_handle().forward(x.detach().float().contiguous(), eps)[:3]
