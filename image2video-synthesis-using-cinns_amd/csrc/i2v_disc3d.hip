@@ -2,9 +2,10 @@
 // spectral norm in training mode on block 0 of every layer, GroupNorm(16), the max pool, the head, the feature-map loss (loss.py:14-21).
 // The C ABI is include/i2v_hip_disc3d.h.  Conventions of i2v_patchdisc.hip: exact fp32 on v_mfma_f32_16x16x4_f32; every sum has one owner
 // and a fixed order, so two runs give the same bits.
-// The trunk's kernels (conv, dgrad, wgrad, finish, GroupNorm: __builtin_amdgcn_mfma_f32_16x16x4f32), their launchers and plan helpers are in
-// i2v_res3d_trunk.h, shared with the motion encoder's training path (i2v_encoder_train.hip); the pool, the head, the feature-map loss, the
-// spectral-norm bookkeeping and the walks over the blocks are here.
+// The trunk's kernels (conv, dgrad, wgrad, finish, GroupNorm: __builtin_amdgcn_mfma_f32_16x16x4f32; the pool), their launchers and plan
+// helpers are in i2v_res3d_trunk.h; the plan of the convs and blocks, the binding, the layout of `saved` and of the workspace, the
+// spectral-norm bookkeeping and the forward and backward walks are in i2v_res3d_net.h.  Both are shared with the motion encoder's
+// training path (i2v_encoder_train.hip).  Here: the head, the feature-map loss, the unit entries and the C entries.
 //   * Activations are channels-last [N][T][H][W][C]; the clip is stored with 4 channels (r, g, b, 0).
 //   * A forward packs W (/ sigma where the conv is spectral-normed) of every conv once, on the device, into wf [tap][cout][cin] and
 //     wd [tap][cin][cout].  With I2V_DISC3D_SAVE they live in `saved` with that call's u, v and sigma.
@@ -21,70 +22,13 @@
 #include "i2v_handle.h"
 #include "i2v_power_iter.h"
 #include "i2v_res3d_trunk.h"
+#include "i2v_res3d_net.h"
 #include "../../include/i2v_hip_disc3d.h"
-
-#include <string>
 
 namespace i2v {
 namespace {
 
 constexpr int D3_FMAP_BLOCKS = 64;
-
-// ------------------------------------------------------------------------------------------------------------------ max pool
-// MaxPool3d(3, stride (1, 2, 2), pad 1); the first maximum in (t, h, w) scan order wins
-__global__ __launch_bounds__(256) void d3_maxpool_kernel(const float* __restrict__ x, float* __restrict__ out, int* __restrict__ arg, long total, int T,
-                                                         int H, int W, int Ho, int Wo, int C) {
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += gridDim.x * 256L) {
-        const int c = (int)(i % C);
-        long p = i / C;
-        const int wo = (int)(p % Wo); p /= Wo;
-        const int ho = (int)(p % Ho); p /= Ho;
-        const int to = (int)(p % T); p /= T;
-        float best = 0.f;
-        int bi = -1;
-        for (int dt = -1; dt <= 1; ++dt) {
-            const int t = to + dt;
-            if ((unsigned)t >= (unsigned)T) continue;
-            for (int dh = -1; dh <= 1; ++dh) {
-                const int h = 2 * ho + dh;
-                if ((unsigned)h >= (unsigned)H) continue;
-                for (int dw = -1; dw <= 1; ++dw) {
-                    const int w = 2 * wo + dw;
-                    if ((unsigned)w >= (unsigned)W) continue;
-                    const int idx = (t * H + h) * W + w;
-                    const float v = x[(p * (long)T * H * W + idx) * C + c];
-                    if (bi < 0 || v > best) { best = v; bi = idx; }
-                }
-            }
-        }
-        out[i] = best;
-        arg[i] = bi;
-    }
-}
-
-// a gather: the windows overlap, so an input sums the gradients of the windows that chose it, in the windows' scan order
-__global__ __launch_bounds__(256) void d3_maxpool_bwd_kernel(const float* __restrict__ g, const int* __restrict__ arg, float* __restrict__ dx, long total,
-                                                             int T, int H, int W, int Ho, int Wo, int C) {
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += gridDim.x * 256L) {
-        const int c = (int)(i % C);
-        long p = i / C;
-        const int w = (int)(p % W); p /= W;
-        const int h = (int)(p % H); p /= H;
-        const int t = (int)(p % T); p /= T;
-        const int idx = (t * H + h) * W + w;
-        const int ho0 = h / 2, ho1 = (h + 1) / 2, wo0 = w / 2, wo1 = (w + 1) / 2;   // 2 o - 1 <= i <= 2 o + 1
-        float acc = 0.f;
-        for (int to = t - 1; to <= t + 1; ++to) {
-            if ((unsigned)to >= (unsigned)T) continue;
-            for (int ho = ho0; ho <= ho1 && ho < Ho; ++ho)
-                for (int wo = wo0; wo <= wo1 && wo < Wo; ++wo) {
-                    const long o = (((p * T + to) * Ho + ho) * Wo + wo) * C + c;
-                    if (arg[o] == idx) acc += g[o];
-                }
-        }
-        dx[i] = acc;
-    }
-}
 
 // ------------------------------------------------------------------------------------------------------------------ head
 // AvgPool3d((1, 4, 4)) over the [1, 4, 4] map, then fc: one workgroup per sample
@@ -161,112 +105,22 @@ __global__ __launch_bounds__(256) void d3_sumsq_kernel(const float* __restrict__
     if (threadIdx.x == 0) out[blockIdx.x] = q;
 }
 
-
 }  // namespace
 }  // namespace i2v
 
 using namespace i2v;
 
-struct D3Block { int c1, c2, cd, in; };   // conv indices (cd -1: no downsample branch); in: the conv whose activation enters (-1: the pool's output)
-
 struct i2v_disc3d {
     int device = 0;
     bool loaded = false;   // parameters bound
     bool have_grads = false;
-    int nconv = 0, pool = 0, sn = 0;
-    D3Conv L[D3_MAXCONV];
-    std::string wkey[D3_MAXCONV], nkey[D3_MAXCONV];   // state-dict prefixes of the conv and of its GroupNorm
-    D3Block B[8];
-    float *w[D3_MAXCONV] = {}, *u[D3_MAXCONV] = {}, *v[D3_MAXCONV] = {}, *nw[D3_MAXCONV] = {}, *nb[D3_MAXCONV] = {}, *fc = nullptr;
-    float *gw[D3_MAXCONV] = {}, *gnw[D3_MAXCONV] = {}, *gnb[D3_MAXCONV] = {}, *gfc = nullptr;
+    R3Trunk trunk;
+    float *fc = nullptr, *gfc = nullptr;
 };
 
 namespace {
 
-// Where everything lies for one input shape: `saved` (offsets from its base) and the workspace
-struct D3Layout {
-    bool ok = false;
-    char why[160] = "";
-    D3Geo geo[D3_MAXCONV];
-    int pt = 0, ph = 0, pw = 0, pho = 0, pwo = 0;   // the pool's input and output map
-    long pool_in = 0, pool_out = 0;                 // positions
-    size_t x4 = 0, pre[D3_MAXCONV] = {}, act[D3_MAXCONV] = {}, stats[D3_MAXCONV] = {}, wf[D3_MAXCONV] = {}, wd[D3_MAXCONV] = {}, sigma[D3_MAXCONV] = {},
-           us[D3_MAXCONV] = {}, vs[D3_MAXCONV] = {}, pout = 0, parg = 0, saved_total = 0;
-    size_t pi_t[D3_MAXCONV] = {}, pi_s[D3_MAXCONV] = {}, fwd = 0, gbuf[4] = {}, dc[2] = {}, part = 0, dwn = 0, dotp = 0, gn = 0, ws_total = 0;
-};
-
-D3Layout d3_layout(const i2v_disc3d* d, int n, int t, int h, int w) {
-    D3Layout y;
-    if (n <= 0 || t <= 0 || h <= 0 || w <= 0) {
-        snprintf(y.why, sizeof y.why, "batch %d, clip %d x %d x %d", n, t, h, w);
-        return y;
-    }
-    // the maps, conv by conv
-    y.geo[0] = make_geo(n, t, h, w, d->L[0]);
-    int ct = y.geo[0].to, chh = y.geo[0].ho, cw = y.geo[0].wo;
-    if (d->pool && ct > 0 && chh > 0 && cw > 0) {
-        y.pt = ct; y.ph = chh; y.pw = cw; y.pho = (chh - 1) / 2 + 1; y.pwo = (cw - 1) / 2 + 1;
-        y.pool_in = (long)n * ct * chh * cw; y.pool_out = (long)n * ct * y.pho * y.pwo;
-        chh = y.pho; cw = y.pwo;
-    }
-    for (int b = 0; b < 8; ++b) {
-        const D3Block& k = d->B[b];
-        if (ct < 1 || chh < 1 || cw < 1) break;
-        y.geo[k.c1] = make_geo(n, ct, chh, cw, d->L[k.c1]);
-        if (k.cd >= 0) y.geo[k.cd] = make_geo(n, ct, chh, cw, d->L[k.cd]);
-        ct = y.geo[k.c1].to; chh = y.geo[k.c1].ho; cw = y.geo[k.c1].wo;
-        y.geo[k.c2] = make_geo(n, ct, chh, cw, d->L[k.c2]);
-    }
-    if (ct != 1 || chh != 4 || cw != 4) {
-        snprintf(y.why, sizeof y.why, "a clip of %d frames of %d x %d ends on a [%d, %d, %d] map, not on the [1, 4, 4] that fc takes", t, h, w, ct, chh, cw);
-        return y;
-    }
-    Carver s;
-    y.x4 = s.take_floats((size_t)y.geo[0].mi * 4);
-    size_t gmax = 0, pmax = 0, emax = 0, bmax = 0, cmax = 0;
-    for (int i = 0; i < d->nconv; ++i) {
-        const D3Conv& c = d->L[i];
-        const size_t elems = (size_t)y.geo[i].mo * c.cout;
-        y.pre[i] = s.take_floats(elems);
-        y.act[i] = s.take_floats(elems);
-        y.stats[i] = s.take_bytes((size_t)n * D3_GROUPS * 2 * 8);
-        y.wf[i] = s.take_floats((size_t)ntap_of(c) * c.cout * c.cinp);
-        y.wd[i] = s.take_floats(pack_elems(c));
-        y.sigma[i] = s.take_floats(c.sn ? 1 : 0);
-        y.us[i] = s.take_floats(c.sn ? c.cout : 0);
-        y.vs[i] = s.take_floats(c.sn ? (size_t)c.cin * ntap_of(c) : 0);
-        gmax = std::max(gmax, std::max(elems, (size_t)y.geo[i].mi * c.cinp));
-        pmax = std::max(pmax, wgrad_part_floats(c, y.geo[i].mo));
-        emax = std::max(emax, (size_t)c.cout * c.cin * ntap_of(c));
-        bmax = std::max(bmax, finish_blocks(c));
-        cmax = std::max(cmax, (size_t)c.cout);
-    }
-    if (d->pool) {
-        y.pout = s.take_floats((size_t)y.pool_out * d->L[0].cout);
-        y.parg = s.take_floats((size_t)y.pool_out * d->L[0].cout);
-    }
-    y.saved_total = s.total();
-    Carver k;
-    for (int i = 0; i < d->nconv; ++i) {
-        y.pi_t[i] = k.take_bytes(d->L[i].sn ? (size_t)d->L[i].cin * ntap_of(d->L[i]) * 8 : 0);
-        y.pi_s[i] = k.take_bytes(d->L[i].sn ? (size_t)d->L[i].cout * 8 : 0);
-    }
-    y.fwd = k.take_bytes(y.saved_total);
-    for (int i = 0; i < 4; ++i) y.gbuf[i] = k.take_floats(gmax);
-    for (int i = 0; i < 2; ++i) y.dc[i] = k.take_floats(gmax);
-    y.part = k.take_floats(pmax);
-    y.dwn = k.take_floats(emax);
-    y.dotp = k.take_bytes((bmax + 1) * 8);
-    y.gn = k.take_bytes(gn_ws(n, (int)cmax).total);
-    y.ws_total = k.total();
-    y.ok = true;
-    return y;
-}
-
-int refuse(const char* what, const D3Layout& y) {
-    set_error("%s: %s", what, y.why);
-    return I2V_E_INVALID;
-}
+R3Layout d3_layout(const i2v_disc3d* d, int n, int t, int h, int w) { return r3_layout(d->trunk, n, t, h, w, R3Extra{"fc takes", {0, 0, 0}, 0}); }
 
 int check_unit(const char* what, int n, int ti, int hi, int wi, int cin, int cout, int stem, int st, int ss) {
     I2V_REQUIRE(n > 0 && ti >= 1 && hi >= 1 && wi >= 1 && (st == 1 || st == 2) && (ss == 1 || ss == 2), I2V_E_INVALID,
@@ -301,12 +155,6 @@ int pack_unit(const D3Conv& c, const float* weight, float* wf, float* wd, hipStr
     return I2V_OK;
 }
 
-bool bound_ptr(const StateDict& s, const std::string& key, int64_t numel, float** out) {
-    const float* p = s.f32(key, numel);
-    *out = const_cast<float*>(p);
-    return p != nullptr;
-}
-
 }  // namespace
 
 extern "C" {
@@ -323,33 +171,7 @@ int i2v_disc3d_create(const i2v_disc3d_cfg* cfg, i2v_disc3d** out) {
                     "%s: layer %d has strides (t %d, s %d) outside {1, 2}", what, i, cfg->stride_t[i], cfg->stride_s[i]);
     const i2v_disc3d_cfg c = *cfg;
     return create_handle(what, out, [c](i2v_disc3d* d) {
-        d->pool = c.use_max_pool ? 1 : 0;
-        d->sn = c.spectral_norm ? 1 : 0;
-        int k = 0;
-        d->L[k] = make_conv(3, c.channels[0], true, 1, 2, 0);
-        d->wkey[k] = "conv1"; d->nkey[k] = "norm1";
-        ++k;
-        int inplanes = c.channels[0], prev = d->pool ? -1 : 0;
-        for (int l = 0; l < 4; ++l) {
-            const int planes = c.channels[l + 1], ss = c.stride_s[l], st = c.stride_t[l];
-            const std::string p0 = "layer." + std::to_string(l) + ".0.", p1 = "layer." + std::to_string(l) + ".1.";
-            D3Block b0{}, b1{};
-            b0.in = prev;
-            b0.c1 = k; d->L[k] = make_conv(inplanes, planes, false, st, ss, d->sn); d->wkey[k] = p0 + "conv1"; d->nkey[k] = p0 + "bn1"; ++k;
-            b0.c2 = k; d->L[k] = make_conv(planes, planes, false, 1, 1, d->sn); d->wkey[k] = p0 + "conv2"; d->nkey[k] = p0 + "bn2"; ++k;
-            b0.cd = -1;
-            if (ss != 1 || inplanes != planes || st != 1) {   // resnet3D.py:265: the discriminator's rule has the stride_t term
-                b0.cd = k; d->L[k] = make_conv(inplanes, planes, false, st, ss, 1); d->wkey[k] = p0 + "downsample.0"; d->nkey[k] = p0 + "downsample.1"; ++k;
-            }
-            b1.in = b0.c2;
-            b1.c1 = k; d->L[k] = make_conv(planes, planes, false, 1, 1, 0); d->wkey[k] = p1 + "conv1"; d->nkey[k] = p1 + "bn1"; ++k;
-            b1.c2 = k; d->L[k] = make_conv(planes, planes, false, 1, 1, 0); d->wkey[k] = p1 + "conv2"; d->nkey[k] = p1 + "bn2"; ++k;
-            b1.cd = -1;
-            d->B[2 * l] = b0; d->B[2 * l + 1] = b1;
-            prev = b1.c2;
-            inplanes = planes;
-        }
-        d->nconv = k;
+        r3_build(d->trunk, c.channels, c.stride_s, c.stride_t, R3Rules{1, 2, c.spectral_norm ? 1 : 0, 1, c.use_max_pool ? 1 : 0, true});
         return I2V_OK;
     });
 }
@@ -360,15 +182,8 @@ int i2v_disc3d_bind(i2v_disc3d* d, const i2v_tensor* params, int32_t n) {
     I2V_REQUIRE(d && params && n > 0, I2V_E_INVALID, "i2v_disc3d_bind: null argument");
     d->loaded = false;
     const StateDict sd(params, n);
-    for (int i = 0; i < d->nconv; ++i) {
-        const D3Conv& c = d->L[i];
-        const int64_t wn = (int64_t)c.cout * c.cin * ntap_of(c);
-        if (!bound_ptr(sd, d->wkey[i] + (c.sn ? ".weight_orig" : ".weight"), wn, &d->w[i])) return I2V_E_MISSING;
-        if (c.sn && (!bound_ptr(sd, d->wkey[i] + ".weight_u", c.cout, &d->u[i]) || !bound_ptr(sd, d->wkey[i] + ".weight_v", wn / c.cout, &d->v[i])))
-            return I2V_E_MISSING;
-        if (!bound_ptr(sd, d->nkey[i] + ".weight", c.cout, &d->nw[i]) || !bound_ptr(sd, d->nkey[i] + ".bias", c.cout, &d->nb[i])) return I2V_E_MISSING;
-    }
-    if (!bound_ptr(sd, "fc.weight", d->L[d->nconv - 1].cout, &d->fc)) return I2V_E_MISSING;
+    if (int rc = r3_bind(d->trunk, sd)) return rc;
+    if (!bound_ptr(sd, "fc.weight", d->trunk.L[d->trunk.last()].cout, &d->fc)) return I2V_E_MISSING;
     d->loaded = true;
     return I2V_OK;
 }
@@ -378,23 +193,19 @@ int i2v_disc3d_bind_grads(i2v_disc3d* d, const i2v_tensor* grads, int32_t n) {
     d->have_grads = false;
     if (!grads) return I2V_OK;
     const StateDict gd(grads, n);
-    for (int i = 0; i < d->nconv; ++i) {
-        const D3Conv& c = d->L[i];
-        if (!bound_ptr(gd, d->wkey[i] + (c.sn ? ".weight_orig" : ".weight"), (int64_t)c.cout * c.cin * ntap_of(c), &d->gw[i])) return I2V_E_MISSING;
-        if (!bound_ptr(gd, d->nkey[i] + ".weight", c.cout, &d->gnw[i]) || !bound_ptr(gd, d->nkey[i] + ".bias", c.cout, &d->gnb[i])) return I2V_E_MISSING;
-    }
-    if (!bound_ptr(gd, "fc.weight", d->L[d->nconv - 1].cout, &d->gfc)) return I2V_E_MISSING;
+    if (int rc = r3_bind_grads(d->trunk, gd)) return rc;
+    if (!bound_ptr(gd, "fc.weight", d->trunk.L[d->trunk.last()].cout, &d->gfc)) return I2V_E_MISSING;
     d->have_grads = true;
     return I2V_OK;
 }
 
 int i2v_disc3d_out_shape(const i2v_disc3d* d, int32_t t, int32_t h, int32_t w, int32_t* shapes) {
     I2V_REQUIRE(d && shapes, I2V_E_INVALID, "i2v_disc3d_out_shape: null argument");
-    const D3Layout y = d3_layout(d, 1, t, h, w);
-    if (!y.ok) return refuse("i2v_disc3d_out_shape", y);
+    const R3Layout y = d3_layout(d, 1, t, h, w);
+    if (!y.ok) return r3_refuse("i2v_disc3d_out_shape", y);
     for (int l = 0; l < 4; ++l) {
-        const int i = d->B[2 * l + 1].c2;
-        shapes[4 * l] = y.geo[i].to; shapes[4 * l + 1] = y.geo[i].ho; shapes[4 * l + 2] = y.geo[i].wo; shapes[4 * l + 3] = d->L[i].cout;
+        const int i = d->trunk.B[2 * l + 1].c2;
+        shapes[4 * l] = y.geo[i].to; shapes[4 * l + 1] = y.geo[i].ho; shapes[4 * l + 2] = y.geo[i].wo; shapes[4 * l + 3] = d->trunk.L[i].cout;
     }
     return I2V_OK;
 }
@@ -405,22 +216,15 @@ size_t i2v_disc3d_workspace_bytes(const i2v_disc3d* d, int32_t n, int32_t t, int
 int i2v_disc3d_saved_layout(const i2v_disc3d* d, int32_t n, int32_t t, int32_t h, int32_t w, int32_t* count, int32_t* kind, int32_t* conv,
                             int32_t* dims, int64_t* offset) {
     I2V_REQUIRE(d && count && kind && conv && dims && offset, I2V_E_INVALID, "i2v_disc3d_saved_layout: null argument");
-    const D3Layout y = d3_layout(d, n, t, h, w);
-    if (!y.ok) return refuse("i2v_disc3d_saved_layout", y);
-    int e = 0;
-    auto put = [&](int kd, int ci, int mt, int mh, int mw, int mc, size_t off) {
-        kind[e] = kd; conv[e] = ci; dims[4 * e] = mt; dims[4 * e + 1] = mh; dims[4 * e + 2] = mw; dims[4 * e + 3] = mc; offset[e] = (int64_t)off;
-        ++e;
-    };
-    for (int i = 0; i < d->nconv; ++i) {
-        put(I2V_DISC3D_CONV_OUT, i, y.geo[i].to, y.geo[i].ho, y.geo[i].wo, d->L[i].cout, y.pre[i]);
-        put(I2V_DISC3D_ACT, i, y.geo[i].to, y.geo[i].ho, y.geo[i].wo, d->L[i].cout, y.act[i]);
+    const R3Layout y = d3_layout(d, n, t, h, w);
+    if (!y.ok) return r3_refuse("i2v_disc3d_saved_layout", y);
+    R3Table tab{kind, conv, dims, offset};
+    tab.put_convs(d->trunk, y, I2V_DISC3D_CONV_OUT, I2V_DISC3D_ACT);
+    if (d->trunk.pool) {
+        tab.put(I2V_DISC3D_POOL_OUT, -1, y.pt, y.pho, y.pwo, d->trunk.L[0].cout, y.pout);
+        tab.put(I2V_DISC3D_POOL_ARGMAX, -1, y.pt, y.pho, y.pwo, d->trunk.L[0].cout, y.parg);
     }
-    if (d->pool) {
-        put(I2V_DISC3D_POOL_OUT, -1, y.pt, y.pho, y.pwo, d->L[0].cout, y.pout);
-        put(I2V_DISC3D_POOL_ARGMAX, -1, y.pt, y.pho, y.pwo, d->L[0].cout, y.parg);
-    }
-    *count = e;
+    *count = tab.count;
     return I2V_OK;
 }
 
@@ -429,8 +233,8 @@ int i2v_disc3d_forward(i2v_disc3d* d, const float* x, int32_t n, int32_t t, int3
     const char* what = "i2v_disc3d_forward";
     I2V_ENTER(sc, d, Entry::NEEDS_WEIGHTS, what);
     I2V_REQUIRE(x && pred && workspace, I2V_E_INVALID, "%s: null argument", what);
-    const D3Layout y = d3_layout(d, n, t, h, w);
-    if (!y.ok) return refuse(what, y);
+    const R3Layout y = d3_layout(d, n, t, h, w);
+    if (!y.ok) return r3_refuse(what, y);
     I2V_REQUIRE_WORKSPACE(workspace_bytes, y.ws_total, what);
     const bool save = flags & I2V_DISC3D_SAVE;
     if (save) {
@@ -439,70 +243,9 @@ int i2v_disc3d_forward(i2v_disc3d* d, const float* x, int32_t n, int32_t t, int3
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
     void* sv = save ? saved : Carver::at<char>(workspace, y.fwd);
-    void* gnws = Carver::at<char>(workspace, y.gn);
-    const int nc = d->nconv;
-
-    float* x4 = Carver::at(sv, y.x4);
-    hipLaunchKernelGGL(d3_input4_kernel, dim3(grid_for(y.geo[0].mi)), dim3(256), 0, st, x, x4, y.geo[0].mi, (long)t * h * w);
-    PD_LAUNCHED();
-
-    // spectral norm, PD_MAXCONV convs per group of launches
-    PdPiArgs pi{};
-    pi.iterate = flags & I2V_DISC3D_ITERATE ? 1 : 0;
-    for (int i = 0; i < nc; ++i) {
-        const D3Conv& c = d->L[i];
-        if (c.sn) {
-            const int cols = c.cin * ntap_of(c);
-            pi.c[pi.nconv++] = PdPiConv{d->w[i], d->u[i], d->v[i], Carver::at(sv, y.sigma[i]), Carver::at(sv, y.us[i]), Carver::at(sv, y.vs[i]),
-                                        Carver::at<double>(workspace, y.pi_t[i]), Carver::at<double>(workspace, y.pi_s[i]), c.cout, cols, pi.btotal, pi.rtotal};
-            pi.btotal += (cols + 63) / 64; pi.rtotal += c.cout;
-        }
-        if (pi.nconv == PD_MAXCONV || (i + 1 == nc && pi.nconv > 0)) {
-            if (int rc = launch_power_iteration(pi, st)) return rc;
-            pi.nconv = pi.btotal = pi.rtotal = 0;
-        }
-    }
-    D3PackArgs pk{};
-    pk.nconv = nc;
-    for (int i = 0; i < nc; ++i) {
-        const D3Conv& c = d->L[i];
-        pk.c[i] = D3PackConv{d->w[i], c.sn ? Carver::at(sv, y.sigma[i]) : nullptr, Carver::at(sv, y.wf[i]), Carver::at(sv, y.wd[i]),
-                             c.cout, c.cin, c.cinp, c.cind, ntap_of(c), pk.total};
-        pk.total += (long)pack_elems(c);
-    }
-    hipLaunchKernelGGL(d3_pack_kernel, dim3(grid_for(pk.total)), dim3(256), 0, st, pk);
-    PD_LAUNCHED();
-
-    // conv i on `in`, then its GroupNorm (+ res) (ReLU) -> act[i]
-    auto conv_gn = [&](int i, const float* in, const float* res, bool relu) -> int {
-        const D3Conv& c = d->L[i];
-        float* pre = Carver::at(sv, y.pre[i]);
-        if (int rc = launch_conv(c, in, Carver::at(sv, y.wf[i]), pre, y.geo[i], st)) return rc;
-        return launch_gn(pre, res, d->nw[i], d->nb[i], n, y.geo[i].mo / n, c.cout, relu, Carver::at(sv, y.act[i]), Carver::at<double>(sv, y.stats[i]),
-                         gnws, st);
-    };
-    if (int rc = conv_gn(0, x4, nullptr, true)) return rc;
-    if (d->pool) {
-        const long total = y.pool_out * d->L[0].cout;
-        hipLaunchKernelGGL(d3_maxpool_kernel, dim3(grid_for(total)), dim3(256), 0, st, Carver::at(sv, y.act[0]), Carver::at(sv, y.pout),
-                           Carver::at<int>(sv, y.parg), total, y.pt, y.ph, y.pw, y.pho, y.pwo, d->L[0].cout);
-        PD_LAUNCHED();
-    }
-    for (int b = 0; b < 8; ++b) {
-        const D3Block& k = d->B[b];
-        const float* in = k.in < 0 ? Carver::at(sv, y.pout) : Carver::at(sv, y.act[k.in]);
-        if (int rc = conv_gn(k.c1, in, nullptr, true)) return rc;
-        const float* res = in;
-        if (k.cd >= 0) {
-            if (int rc = conv_gn(k.cd, in, nullptr, false)) return rc;
-            res = Carver::at(sv, y.act[k.cd]);
-        }
-        if (int rc = conv_gn(k.c2, Carver::at(sv, y.act[k.c1]), res, true)) return rc;
-        if ((b & 1) && fmaps && fmaps[b / 2])
-            I2V_HIP_CHECK(hipMemcpyAsync(fmaps[b / 2], Carver::at(sv, y.act[k.c2]), (size_t)y.geo[k.c2].mo * d->L[k.c2].cout * 4, hipMemcpyDeviceToDevice, st));
-    }
-    const int last = d->B[7].c2;
-    hipLaunchKernelGGL(d3_head_fwd_kernel, dim3(n), dim3(256), 0, st, Carver::at(sv, y.act[last]), d->fc, pred, d->L[last].cout);
+    if (int rc = r3_forward(d->trunk, y, x, flags & I2V_DISC3D_ITERATE, fmaps, sv, workspace, st)) return rc;
+    const int last = d->trunk.last();
+    hipLaunchKernelGGL(d3_head_fwd_kernel, dim3(n), dim3(256), 0, st, Carver::at(sv, y.act[last]), d->fc, pred, d->trunk.L[last].cout);
     PD_LAUNCHED();
     return I2V_OK;
 }
@@ -518,87 +261,26 @@ int i2v_disc3d_backward(i2v_disc3d* d, const float* d_pred, const float* const* 
     for (int l = 0; l < 4 && d_fmaps; ++l) any = any || d_fmaps[l];
     I2V_REQUIRE(any, I2V_E_INVALID, "%s: no upstream gradient (d_pred and every d_fmaps entry are null)", what);
     I2V_REQUIRE(!param_grads || d->have_grads, I2V_E_STATE, "%s: no gradient tensors are bound", what);
-    const D3Layout y = d3_layout(d, n, t, h, w);
-    if (!y.ok) return refuse(what, y);
+    const R3Layout y = d3_layout(d, n, t, h, w);
+    if (!y.ok) return r3_refuse(what, y);
     I2V_REQUIRE_WORKSPACE(workspace_bytes, y.ws_total, what);
     I2V_REQUIRE_WORKSPACE(saved_bytes, y.saved_total, what);
     hipStream_t st = static_cast<hipStream_t>(stream);
     void* sv = const_cast<void*>(saved);
     const bool acc = accumulate != 0, pg = param_grads != 0;
-    float* part = Carver::at(workspace, y.part);
-    float* dwn = Carver::at(workspace, y.dwn);
-    double* dotp = Carver::at<double>(workspace, y.dotp);
-    void* gnws = Carver::at<char>(workspace, y.gn);
-    float* G = Carver::at(workspace, y.gbuf[0]);      // the gradient at the current block's output
-    float* Gn = Carver::at(workspace, y.gbuf[1]);     // ... at its input
-    float* H1 = Carver::at(workspace, y.gbuf[2]);     // ... at conv1's activation
-    float* X2 = Carver::at(workspace, y.gbuf[3]);     // the downsample branch's share of Gn
-    float* DC = Carver::at(workspace, y.dc[0]);       // ... at a conv's output
-    float* DC2 = Carver::at(workspace, y.dc[1]);
 
-    // GroupNorm of conv i backwards: g (masked by `mask`) -> dc; then the conv's weight gradient
-    auto norm_conv_bwd = [&](int i, const float* g, const float* mask, const float* xin, float* dc) -> int {
-        const D3Conv& c = d->L[i];
-        if (int rc = launch_gn_bwd(g, mask, Carver::at(sv, y.pre[i]), Carver::at<double>(sv, y.stats[i]), d->nw[i], n, y.geo[i].mo / n, c.cout, dc,
-                                   pg ? d->gnw[i] : nullptr, pg ? d->gnb[i] : nullptr, acc, gnws, st))
-            return rc;
-        if (!pg) return I2V_OK;
-        return launch_wgrad(c, dc, nullptr, xin, d->w[i], c.sn ? Carver::at(sv, y.us[i]) : nullptr, c.sn ? Carver::at(sv, y.vs[i]) : nullptr,
-                            c.sn ? Carver::at(sv, y.sigma[i]) : nullptr, part, dwn, dotp, d->gw[i], acc, y.geo[i], st);
-    };
-    auto add_fmap = [&](int l, float* g, size_t elems) -> int {
-        if (!d_fmaps || !d_fmaps[l]) return I2V_OK;
-        hipLaunchKernelGGL(d3_add_kernel, dim3(grid_for((long)elems)), dim3(256), 0, st, g, d_fmaps[l], (long)elems);
+    // the head: the gradient at the last activation -> gbuf[0]
+    const int last = d->trunk.last(), C = d->trunk.L[last].cout;
+    float* G = Carver::at(workspace, y.gbuf[0]);
+    if (d_pred) {
+        hipLaunchKernelGGL(d3_head_bwd_kernel, dim3((C + 255) / 256), dim3(256), 0, st, Carver::at(sv, y.act[last]), d->fc, d_pred, G,
+                           pg ? d->gfc : nullptr, n, C, acc ? 1 : 0);
         PD_LAUNCHED();
-        return I2V_OK;
-    };
-
-    // the head
-    const int last = d->B[7].c2;
-    {
-        const int C = d->L[last].cout;
-        const size_t elems = (size_t)n * 16 * C;
-        if (d_pred) {
-            hipLaunchKernelGGL(d3_head_bwd_kernel, dim3((C + 255) / 256), dim3(256), 0, st, Carver::at(sv, y.act[last]), d->fc, d_pred, G,
-                               pg ? d->gfc : nullptr, n, C, acc ? 1 : 0);
-            PD_LAUNCHED();
-        } else {
-            I2V_HIP_CHECK(hipMemsetAsync(G, 0, elems * 4, st));
-            if (pg && !acc) I2V_HIP_CHECK(hipMemsetAsync(d->gfc, 0, (size_t)C * 4, st));
-        }
-        if (int rc = add_fmap(3, G, elems)) return rc;
+    } else {
+        I2V_HIP_CHECK(hipMemsetAsync(G, 0, (size_t)n * 16 * C * 4, st));
+        if (pg && !acc) I2V_HIP_CHECK(hipMemsetAsync(d->gfc, 0, (size_t)C * 4, st));
     }
-    for (int b = 7; b >= 0; --b) {
-        const D3Block& k = d->B[b];
-        const float* out = Carver::at(sv, y.act[k.c2]);
-        const float* xin = k.in < 0 ? Carver::at(sv, y.pout) : Carver::at(sv, y.act[k.in]);
-        const float* h1 = Carver::at(sv, y.act[k.c1]);
-        if (int rc = norm_conv_bwd(k.c2, G, out, h1, DC)) return rc;
-        if (int rc = launch_dgrad(d->L[k.c2], DC, nullptr, Carver::at(sv, y.wd[k.c2]), nullptr, nullptr, H1, false, n, y.geo[k.c2], st)) return rc;
-        if (int rc = norm_conv_bwd(k.c1, H1, h1, xin, DC)) return rc;
-        if (k.cd >= 0) {
-            if (int rc = norm_conv_bwd(k.cd, G, out, xin, DC2)) return rc;
-            if (int rc = launch_dgrad(d->L[k.cd], DC2, nullptr, Carver::at(sv, y.wd[k.cd]), nullptr, nullptr, X2, false, n, y.geo[k.cd], st)) return rc;
-            if (int rc = launch_dgrad(d->L[k.c1], DC, nullptr, Carver::at(sv, y.wd[k.c1]), X2, nullptr, Gn, false, n, y.geo[k.c1], st)) return rc;
-        } else if (int rc = launch_dgrad(d->L[k.c1], DC, nullptr, Carver::at(sv, y.wd[k.c1]), G, out, Gn, false, n, y.geo[k.c1], st)) {
-            return rc;
-        }
-        std::swap(G, Gn);
-        if (!(b & 1) && b > 0)
-            if (int rc = add_fmap(b / 2 - 1, G, (size_t)y.geo[k.c1].mi * d->L[k.c1].cin)) return rc;
-    }
-    // G: the gradient at the pool's output (or at the stem's activation)
-    if (d->pool) {
-        const long total = y.pool_in * d->L[0].cout;
-        hipLaunchKernelGGL(d3_maxpool_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, st, G, Carver::at<int>(sv, y.parg), Gn, total, y.pt, y.ph, y.pw,
-                           y.pho, y.pwo, d->L[0].cout);
-        PD_LAUNCHED();
-        std::swap(G, Gn);
-    }
-    if (int rc = norm_conv_bwd(0, G, Carver::at(sv, y.act[0]), Carver::at(sv, y.x4), DC)) return rc;
-    if (d_x)
-        if (int rc = launch_dgrad(d->L[0], DC, nullptr, Carver::at(sv, y.wd[0]), nullptr, nullptr, d_x, true, n, y.geo[0], st)) return rc;
-    return I2V_OK;
+    return r3_backward(d->trunk, y, d_fmaps, sv, d_x, pg, acc, workspace, st);
 }
 
 size_t i2v_disc3d_fmap_loss_workspace_bytes(void) { return (size_t)4 * D3_FMAP_BLOCKS * 8; }

@@ -1,6 +1,7 @@
 // The training path of the motion encoder of stage 1: resnet3D.Encoder (stage1_VAE/modules/resnet3D.py:138-219) forward and backward with
-// the parameters read in place -- the 3-D ResNet-18 trunk with GroupNorm(16) on the kernels of i2v_res3d_trunk.h (the temporal
-// discriminator's), and the posterior head: conv_mu, conv_var, the reparameterisation and the KL gradient (loss.py:10-12).
+// the parameters read in place -- the 3-D ResNet-18 trunk with GroupNorm(16) that it shares with the temporal discriminator (kernels and
+// launchers: i2v_res3d_trunk.h; plan, binding, layout and the two walks: i2v_res3d_net.h), and, here, the posterior head: conv_mu,
+// conv_var, the reparameterisation and the KL gradient (loss.py:10-12).
 // The C ABI is include/i2v_hip_enc3d_train.h.  Exact fp32 on v_mfma_f32_16x16x4_f32; every sum has one owner and a fixed order.
 //   * The trunk differs from the discriminator's in its stem (stride (2, 2, 2)), in the downsample rule (no stride_t term,
 //     resnet3D.py:184), and in having neither spectral norm nor a pool.  Its last activation is [N][16][C] (the [1, 4, 4] map).
@@ -13,10 +14,10 @@
 //     wave order); the weight gradient a sum over the n samples, each element written once; the bias gradient a float64 sum over n.
 #include "i2v_handle.h"
 #include "i2v_res3d_trunk.h"
+#include "i2v_res3d_net.h"
 #include "../../include/i2v_hip_enc3d_train.h"
 
 #include <cstdint>
-#include <string>
 
 namespace i2v {
 namespace {
@@ -239,99 +240,33 @@ int launch_head_bwd(E3HeadArgs a, E3FoldArgs f, void* ws, hipStream_t st) {
 
 using namespace i2v;
 
-struct E3Block { int c1, c2, cd, in; };   // conv indices (cd -1: no downsample branch); in: the conv whose activation enters
-
 struct i2v_enc3d_train {
     int device = 0;
     bool loaded = false;   // parameters bound
     bool have_grads = false;
-    int nconv = 0, z = 0;
-    D3Conv L[D3_MAXCONV];
-    std::string wkey[D3_MAXCONV], nkey[D3_MAXCONV];
-    E3Block B[8];
-    float *w[D3_MAXCONV] = {}, *nw[D3_MAXCONV] = {}, *nb[D3_MAXCONV] = {}, *wmu = nullptr, *bmu = nullptr, *wvar = nullptr, *bvar = nullptr;
-    float *gw[D3_MAXCONV] = {}, *gnw[D3_MAXCONV] = {}, *gnb[D3_MAXCONV] = {}, *gwmu = nullptr, *gbmu = nullptr, *gwvar = nullptr, *gbvar = nullptr;
+    int z = 0;
+    R3Trunk trunk;
+    float *wmu = nullptr, *bmu = nullptr, *wvar = nullptr, *bvar = nullptr;
+    float *gwmu = nullptr, *gbmu = nullptr, *gwvar = nullptr, *gbvar = nullptr;
 };
 
 namespace {
 
-// Where everything lies for one input shape: `saved` (offsets from its base) and the workspace
-struct E3Layout {
-    bool ok = false;
-    char why[160] = "";
-    D3Geo geo[D3_MAXCONV];
-    int lt = 0, lh = 0, lw = 0;   // the last map
-    size_t x4 = 0, pre[D3_MAXCONV] = {}, act[D3_MAXCONV] = {}, stats[D3_MAXCONV] = {}, wf[D3_MAXCONV] = {}, wd[D3_MAXCONV] = {}, eps = 0, mu = 0, lv = 0,
-           saved_total = 0;
-    size_t fwd = 0, gbuf[4] = {}, dc[2] = {}, part = 0, dwn = 0, dotp = 0, gn = 0, head = 0, ws_total = 0;
-};
-
-E3Layout e3_layout(const i2v_enc3d_train* d, int n, int t, int h, int w) {
-    E3Layout y;
-    if (n <= 0 || t <= 0 || h <= 0 || w <= 0) {
-        snprintf(y.why, sizeof y.why, "batch %d, clip %d x %d x %d", n, t, h, w);
-        return y;
+// behind the trunk's entries: eps, mu and logvar in `saved` (y.tail[0 .. 2]), the head's scratch in the workspace (y.ws_tail)
+R3Layout e3_layout(const i2v_enc3d_train* d, int n, int t, int h, int w) {
+    R3Extra x{"conv_mu and conv_var take", {0, 0, 0}, 0};
+    if (n > 0) {
+        x.saved[0] = x.saved[1] = x.saved[2] = (size_t)n * d->z * 4;
+        x.ws = head_ws(n, d->trunk.L[d->trunk.last()].cout, d->z).total;
     }
-    y.geo[0] = make_geo(n, t, h, w, d->L[0]);
-    int ct = y.geo[0].to, chh = y.geo[0].ho, cw = y.geo[0].wo;
-    for (int b = 0; b < 8; ++b) {
-        const E3Block& k = d->B[b];
-        if (ct < 1 || chh < 1 || cw < 1) break;
-        y.geo[k.c1] = make_geo(n, ct, chh, cw, d->L[k.c1]);
-        if (k.cd >= 0) y.geo[k.cd] = make_geo(n, ct, chh, cw, d->L[k.cd]);
-        ct = y.geo[k.c1].to; chh = y.geo[k.c1].ho; cw = y.geo[k.c1].wo;
-        y.geo[k.c2] = make_geo(n, ct, chh, cw, d->L[k.c2]);
-    }
-    y.lt = ct; y.lh = chh; y.lw = cw;
-    if (ct != 1 || chh != 4 || cw != 4) {
-        snprintf(y.why, sizeof y.why, "a clip of %d frames of %d x %d ends on a [%d, %d, %d] map, not on the [1, 4, 4] that conv_mu and conv_var take", t, h,
-                 w, ct, chh, cw);
-        return y;
-    }
-    Carver s;
-    y.x4 = s.take_floats((size_t)y.geo[0].mi * 4);
-    size_t gmax = 0, pmax = 0, emax = 0, bmax = 0, cmax = 0;
-    for (int i = 0; i < d->nconv; ++i) {
-        const D3Conv& c = d->L[i];
-        const size_t elems = (size_t)y.geo[i].mo * c.cout;
-        y.pre[i] = s.take_floats(elems);
-        y.act[i] = s.take_floats(elems);
-        y.stats[i] = s.take_bytes((size_t)n * D3_GROUPS * 2 * 8);
-        y.wf[i] = s.take_floats((size_t)ntap_of(c) * c.cout * c.cinp);
-        y.wd[i] = s.take_floats(pack_elems(c));
-        gmax = std::max(gmax, std::max(elems, (size_t)y.geo[i].mi * c.cinp));
-        pmax = std::max(pmax, wgrad_part_floats(c, y.geo[i].mo));
-        emax = std::max(emax, (size_t)c.cout * c.cin * ntap_of(c));
-        bmax = std::max(bmax, finish_blocks(c));
-        cmax = std::max(cmax, (size_t)c.cout);
-    }
-    y.eps = s.take_floats((size_t)n * d->z);
-    y.mu = s.take_floats((size_t)n * d->z);
-    y.lv = s.take_floats((size_t)n * d->z);
-    y.saved_total = s.total();
-    Carver k;
-    y.fwd = k.take_bytes(y.saved_total);
-    for (int i = 0; i < 4; ++i) y.gbuf[i] = k.take_floats(gmax);
-    for (int i = 0; i < 2; ++i) y.dc[i] = k.take_floats(gmax);
-    y.part = k.take_floats(pmax);
-    y.dwn = k.take_floats(emax);
-    y.dotp = k.take_bytes((bmax + 1) * 8);
-    y.gn = k.take_bytes(gn_ws(n, (int)cmax).total);
-    y.head = k.take_bytes(head_ws(n, d->L[d->nconv - 1].cout, d->z).total);
-    y.ws_total = k.total();
-    y.ok = true;
-    return y;
+    return r3_layout(d->trunk, n, t, h, w, x);
 }
 
-int e3_refuse(const char* what, const E3Layout& y) {
-    set_error("%s: %s", what, y.why);
-    return I2V_E_INVALID;
-}
-
-bool e3_bound(const StateDict& s, const std::string& key, int64_t numel, float** out) {
-    const float* p = s.f32(key, numel);
-    *out = const_cast<float*>(p);
-    return p != nullptr;
+// the four head tensors of a state dict or of a gradient dict
+bool bind_head(const i2v_enc3d_train* d, const StateDict& s, float** wmu, float** bmu, float** wvar, float** bvar) {
+    const int64_t hw = (int64_t)d->z * d->trunk.L[d->trunk.last()].cout * 16;
+    return bound_ptr(s, "conv_mu.weight", hw, wmu) && bound_ptr(s, "conv_mu.bias", d->z, bmu) && bound_ptr(s, "conv_var.weight", hw, wvar) &&
+           bound_ptr(s, "conv_var.bias", d->z, bvar);
 }
 
 int check_head_unit(const char* what, int n, int c, int z) {
@@ -361,31 +296,7 @@ int i2v_enc3d_train_create(const i2v_enc3d_train_cfg* cfg, i2v_enc3d_train** out
     const i2v_enc3d_train_cfg c = *cfg;
     return create_handle(what, out, [c](i2v_enc3d_train* d) {
         d->z = c.z_dim;
-        int k = 0;
-        d->L[k] = make_conv(3, c.channels[0], true, 2, 2, 0);
-        d->wkey[k] = "conv1"; d->nkey[k] = "norm1";
-        ++k;
-        int inplanes = c.channels[0], prev = 0;
-        for (int l = 0; l < 4; ++l) {
-            const int planes = c.channels[l + 1], ss = c.stride_s[l], st = c.stride_t[l];
-            const std::string p0 = "layer." + std::to_string(l) + ".0.", p1 = "layer." + std::to_string(l) + ".1.";
-            E3Block b0{}, b1{};
-            b0.in = prev;
-            b0.c1 = k; d->L[k] = make_conv(inplanes, planes, false, st, ss, 0); d->wkey[k] = p0 + "conv1"; d->nkey[k] = p0 + "bn1"; ++k;
-            b0.c2 = k; d->L[k] = make_conv(planes, planes, false, 1, 1, 0); d->wkey[k] = p0 + "conv2"; d->nkey[k] = p0 + "bn2"; ++k;
-            b0.cd = -1;
-            if (ss != 1 || inplanes != planes) {   // resnet3D.py:184: the encoder's rule has no stride_t term
-                b0.cd = k; d->L[k] = make_conv(inplanes, planes, false, st, ss, 0); d->wkey[k] = p0 + "downsample.0"; d->nkey[k] = p0 + "downsample.1"; ++k;
-            }
-            b1.in = b0.c2;
-            b1.c1 = k; d->L[k] = make_conv(planes, planes, false, 1, 1, 0); d->wkey[k] = p1 + "conv1"; d->nkey[k] = p1 + "bn1"; ++k;
-            b1.c2 = k; d->L[k] = make_conv(planes, planes, false, 1, 1, 0); d->wkey[k] = p1 + "conv2"; d->nkey[k] = p1 + "bn2"; ++k;
-            b1.cd = -1;
-            d->B[2 * l] = b0; d->B[2 * l + 1] = b1;
-            prev = b1.c2;
-            inplanes = planes;
-        }
-        d->nconv = k;
+        r3_build(d->trunk, c.channels, c.stride_s, c.stride_t, R3Rules{2, 2, 0, 0, 0, false});
         return I2V_OK;
     });
 }
@@ -396,15 +307,8 @@ int i2v_enc3d_train_bind(i2v_enc3d_train* d, const i2v_tensor* params, int32_t n
     I2V_REQUIRE(d && params && n > 0, I2V_E_INVALID, "i2v_enc3d_train_bind: null argument");
     d->loaded = false;
     const StateDict sd(params, n);
-    for (int i = 0; i < d->nconv; ++i) {
-        const D3Conv& c = d->L[i];
-        if (!e3_bound(sd, d->wkey[i] + ".weight", (int64_t)c.cout * c.cin * ntap_of(c), &d->w[i])) return I2V_E_MISSING;
-        if (!e3_bound(sd, d->nkey[i] + ".weight", c.cout, &d->nw[i]) || !e3_bound(sd, d->nkey[i] + ".bias", c.cout, &d->nb[i])) return I2V_E_MISSING;
-    }
-    const int64_t hw = (int64_t)d->z * d->L[d->nconv - 1].cout * 16;
-    if (!e3_bound(sd, "conv_mu.weight", hw, &d->wmu) || !e3_bound(sd, "conv_mu.bias", d->z, &d->bmu) || !e3_bound(sd, "conv_var.weight", hw, &d->wvar) ||
-        !e3_bound(sd, "conv_var.bias", d->z, &d->bvar))
-        return I2V_E_MISSING;
+    if (int rc = r3_bind(d->trunk, sd)) return rc;
+    if (!bind_head(d, sd, &d->wmu, &d->bmu, &d->wvar, &d->bvar)) return I2V_E_MISSING;
     I2V_REQUIRE(aligned16(d->wmu) && aligned16(d->wvar), I2V_E_INVALID, "i2v_enc3d_train_bind: conv_mu.weight and conv_var.weight must be 16-byte aligned");
     d->loaded = true;
     return I2V_OK;
@@ -415,24 +319,18 @@ int i2v_enc3d_train_bind_grads(i2v_enc3d_train* d, const i2v_tensor* grads, int3
     d->have_grads = false;
     if (!grads) return I2V_OK;
     const StateDict gd(grads, n);
-    for (int i = 0; i < d->nconv; ++i) {
-        const D3Conv& c = d->L[i];
-        if (!e3_bound(gd, d->wkey[i] + ".weight", (int64_t)c.cout * c.cin * ntap_of(c), &d->gw[i])) return I2V_E_MISSING;
-        if (!e3_bound(gd, d->nkey[i] + ".weight", c.cout, &d->gnw[i]) || !e3_bound(gd, d->nkey[i] + ".bias", c.cout, &d->gnb[i])) return I2V_E_MISSING;
-    }
-    const int64_t hw = (int64_t)d->z * d->L[d->nconv - 1].cout * 16;
-    if (!e3_bound(gd, "conv_mu.weight", hw, &d->gwmu) || !e3_bound(gd, "conv_mu.bias", d->z, &d->gbmu) || !e3_bound(gd, "conv_var.weight", hw, &d->gwvar) ||
-        !e3_bound(gd, "conv_var.bias", d->z, &d->gbvar))
-        return I2V_E_MISSING;
+    if (int rc = r3_bind_grads(d->trunk, gd)) return rc;
+    if (!bind_head(d, gd, &d->gwmu, &d->gbmu, &d->gwvar, &d->gbvar)) return I2V_E_MISSING;
     d->have_grads = true;
     return I2V_OK;
 }
 
 int i2v_enc3d_train_out_shape(const i2v_enc3d_train* d, int32_t t, int32_t h, int32_t w, int32_t* shape) {
     I2V_REQUIRE(d && shape, I2V_E_INVALID, "i2v_enc3d_train_out_shape: null argument");
-    const E3Layout y = e3_layout(d, 1, t, h, w);
-    if (!y.ok) return e3_refuse("i2v_enc3d_train_out_shape", y);
-    shape[0] = y.lt; shape[1] = y.lh; shape[2] = y.lw; shape[3] = d->L[d->nconv - 1].cout;
+    const R3Layout y = e3_layout(d, 1, t, h, w);
+    if (!y.ok) return r3_refuse("i2v_enc3d_train_out_shape", y);
+    const int last = d->trunk.last();
+    shape[0] = y.geo[last].to; shape[1] = y.geo[last].ho; shape[2] = y.geo[last].wo; shape[3] = d->trunk.L[last].cout;
     return I2V_OK;
 }
 
@@ -446,19 +344,11 @@ size_t i2v_enc3d_train_workspace_bytes(const i2v_enc3d_train* d, int32_t n, int3
 int i2v_enc3d_train_saved_layout(const i2v_enc3d_train* d, int32_t n, int32_t t, int32_t h, int32_t w, int32_t* count, int32_t* kind, int32_t* conv,
                                  int32_t* dims, int64_t* offset) {
     I2V_REQUIRE(d && count && kind && conv && dims && offset, I2V_E_INVALID, "i2v_enc3d_train_saved_layout: null argument");
-    const E3Layout y = e3_layout(d, n, t, h, w);
-    if (!y.ok) return e3_refuse("i2v_enc3d_train_saved_layout", y);
-    int e = 0;
-    auto put = [&](int kd, int ci, size_t off) {
-        kind[e] = kd; conv[e] = ci; dims[4 * e] = y.geo[ci].to; dims[4 * e + 1] = y.geo[ci].ho; dims[4 * e + 2] = y.geo[ci].wo; dims[4 * e + 3] = d->L[ci].cout;
-        offset[e] = (int64_t)off;
-        ++e;
-    };
-    for (int i = 0; i < d->nconv; ++i) {
-        put(I2V_ENC3D_TRAIN_CONV_OUT, i, y.pre[i]);
-        put(I2V_ENC3D_TRAIN_ACT, i, y.act[i]);
-    }
-    *count = e;
+    const R3Layout y = e3_layout(d, n, t, h, w);
+    if (!y.ok) return r3_refuse("i2v_enc3d_train_saved_layout", y);
+    R3Table tab{kind, conv, dims, offset};
+    tab.put_convs(d->trunk, y, I2V_ENC3D_TRAIN_CONV_OUT, I2V_ENC3D_TRAIN_ACT);
+    *count = tab.count;
     return I2V_OK;
 }
 
@@ -468,8 +358,8 @@ int i2v_enc3d_train_forward(i2v_enc3d_train* d, const float* x, const float* eps
     const char* what = "i2v_enc3d_train_forward";
     I2V_ENTER(sc, d, Entry::NEEDS_WEIGHTS, what);
     I2V_REQUIRE(x && mu && logvar && workspace && !eps == !sample, I2V_E_INVALID, "%s: null argument, or eps without sample (or the reverse)", what);
-    const E3Layout y = e3_layout(d, n, t, h, w);
-    if (!y.ok) return e3_refuse(what, y);
+    const R3Layout y = e3_layout(d, n, t, h, w);
+    if (!y.ok) return r3_refuse(what, y);
     I2V_REQUIRE_WORKSPACE(workspace_bytes, y.ws_total, what);
     const bool save = flags & I2V_ENC3D_TRAIN_SAVE;
     if (save) {
@@ -478,54 +368,20 @@ int i2v_enc3d_train_forward(i2v_enc3d_train* d, const float* x, const float* eps
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
     void* sv = save ? saved : Carver::at<char>(workspace, y.fwd);
-    void* gnws = Carver::at<char>(workspace, y.gn);
-    const int nc = d->nconv;
-
-    float* x4 = Carver::at(sv, y.x4);
-    hipLaunchKernelGGL(d3_input4_kernel, dim3(grid_for(y.geo[0].mi)), dim3(256), 0, st, x, x4, y.geo[0].mi, (long)t * h * w);
-    PD_LAUNCHED();
-    D3PackArgs pk{};
-    pk.nconv = nc;
-    for (int i = 0; i < nc; ++i) {
-        const D3Conv& c = d->L[i];
-        pk.c[i] = D3PackConv{d->w[i], nullptr, Carver::at(sv, y.wf[i]), Carver::at(sv, y.wd[i]), c.cout, c.cin, c.cinp, c.cind, ntap_of(c), pk.total};
-        pk.total += (long)pack_elems(c);
-    }
-    hipLaunchKernelGGL(d3_pack_kernel, dim3(grid_for(pk.total)), dim3(256), 0, st, pk);
-    PD_LAUNCHED();
-
-    // conv i on `in`, then its GroupNorm (+ res) (ReLU) -> act[i]
-    auto conv_gn = [&](int i, const float* in, const float* res, bool relu) -> int {
-        const D3Conv& c = d->L[i];
-        float* pre = Carver::at(sv, y.pre[i]);
-        if (int rc = launch_conv(c, in, Carver::at(sv, y.wf[i]), pre, y.geo[i], st)) return rc;
-        return launch_gn(pre, res, d->nw[i], d->nb[i], n, y.geo[i].mo / n, c.cout, relu, Carver::at(sv, y.act[i]), Carver::at<double>(sv, y.stats[i]),
-                         gnws, st);
-    };
-    if (int rc = conv_gn(0, x4, nullptr, true)) return rc;
-    for (int b = 0; b < 8; ++b) {
-        const E3Block& k = d->B[b];
-        const float* in = Carver::at(sv, y.act[k.in]);
-        if (int rc = conv_gn(k.c1, in, nullptr, true)) return rc;
-        const float* res = in;
-        if (k.cd >= 0) {
-            if (int rc = conv_gn(k.cd, in, nullptr, false)) return rc;
-            res = Carver::at(sv, y.act[k.cd]);
-        }
-        if (int rc = conv_gn(k.c2, Carver::at(sv, y.act[k.c1]), res, true)) return rc;
-    }
-    const int last = d->B[7].c2;
-    float* smu = Carver::at(sv, y.mu);
-    float* slv = Carver::at(sv, y.lv);
+    if (int rc = r3_forward(d->trunk, y, x, false, nullptr, sv, workspace, st)) return rc;
+    const int last = d->trunk.last();
+    float* seps = Carver::at(sv, y.tail[0]);
+    float* smu = Carver::at(sv, y.tail[1]);
+    float* slv = Carver::at(sv, y.tail[2]);
     E3HeadArgs a{};
     a.emb = Carver::at(sv, y.act[last]); a.w_mu = d->wmu; a.w_var = d->wvar; a.b_mu = d->bmu; a.b_var = d->bvar; a.eps = eps;
-    a.sample = sample; a.mu = smu; a.logvar = slv; a.n = n; a.C = d->L[last].cout; a.z = d->z;
-    if (int rc = launch_head_fwd(a, Carver::at<char>(workspace, y.head), st)) return rc;
+    a.sample = sample; a.mu = smu; a.logvar = slv; a.n = n; a.C = d->trunk.L[last].cout; a.z = d->z;
+    if (int rc = launch_head_fwd(a, Carver::at<char>(workspace, y.ws_tail), st)) return rc;
     const size_t zb = (size_t)n * d->z * 4;
     I2V_HIP_CHECK(hipMemcpyAsync(mu, smu, zb, hipMemcpyDeviceToDevice, st));
     I2V_HIP_CHECK(hipMemcpyAsync(logvar, slv, zb, hipMemcpyDeviceToDevice, st));
-    if (eps) I2V_HIP_CHECK(hipMemcpyAsync(Carver::at(sv, y.eps), eps, zb, hipMemcpyDeviceToDevice, st));
-    else I2V_HIP_CHECK(hipMemsetAsync(Carver::at(sv, y.eps), 0, zb, st));
+    if (eps) I2V_HIP_CHECK(hipMemcpyAsync(seps, eps, zb, hipMemcpyDeviceToDevice, st));
+    else I2V_HIP_CHECK(hipMemsetAsync(seps, 0, zb, st));
     return I2V_OK;
 }
 
@@ -539,68 +395,26 @@ int i2v_enc3d_train_backward(i2v_enc3d_train* d, const float* d_sample, const fl
     I2V_REQUIRE(d_sample || d_mu || d_logvar || kl_scale != 0.f, I2V_E_INVALID,
                 "%s: no upstream gradient (d_sample, d_mu and d_logvar are null and kl_scale is 0)", what);
     I2V_REQUIRE(!param_grads || d->have_grads, I2V_E_STATE, "%s: no gradient tensors are bound", what);
-    const E3Layout y = e3_layout(d, n, t, h, w);
-    if (!y.ok) return e3_refuse(what, y);
+    const R3Layout y = e3_layout(d, n, t, h, w);
+    if (!y.ok) return r3_refuse(what, y);
     I2V_REQUIRE_WORKSPACE(workspace_bytes, y.ws_total, what);
     I2V_REQUIRE_WORKSPACE(saved_bytes, y.saved_total, what);
     hipStream_t st = static_cast<hipStream_t>(stream);
     void* sv = const_cast<void*>(saved);
     const bool acc = accumulate != 0, pg = param_grads != 0;
-    float* part = Carver::at(workspace, y.part);
-    float* dwn = Carver::at(workspace, y.dwn);
-    double* dotp = Carver::at<double>(workspace, y.dotp);
-    void* gnws = Carver::at<char>(workspace, y.gn);
-    float* G = Carver::at(workspace, y.gbuf[0]);      // the gradient at the current block's output
-    float* Gn = Carver::at(workspace, y.gbuf[1]);     // ... at its input
-    float* H1 = Carver::at(workspace, y.gbuf[2]);     // ... at conv1's activation
-    float* X2 = Carver::at(workspace, y.gbuf[3]);     // the downsample branch's share of Gn
-    float* DC = Carver::at(workspace, y.dc[0]);       // ... at a conv's output
-    float* DC2 = Carver::at(workspace, y.dc[1]);
 
-    // GroupNorm of conv i backwards: g (masked by `mask`) -> dc; then the conv's weight gradient
-    auto norm_conv_bwd = [&](int i, const float* g, const float* mask, const float* xin, float* dc) -> int {
-        const D3Conv& c = d->L[i];
-        if (int rc = launch_gn_bwd(g, mask, Carver::at(sv, y.pre[i]), Carver::at<double>(sv, y.stats[i]), d->nw[i], n, y.geo[i].mo / n, c.cout, dc,
-                                   pg ? d->gnw[i] : nullptr, pg ? d->gnb[i] : nullptr, acc, gnws, st))
-            return rc;
-        if (!pg) return I2V_OK;
-        return launch_wgrad(c, dc, nullptr, xin, d->w[i], nullptr, nullptr, nullptr, part, dwn, dotp, d->gw[i], acc, y.geo[i], st);
-    };
-
-    // the head: G = the gradient at the last activation
-    const int last = d->B[7].c2;
-    {
-        E3HeadArgs a{};
-        a.emb = Carver::at(sv, y.act[last]); a.w_mu = d->wmu; a.w_var = d->wvar; a.n = n; a.C = d->L[last].cout; a.z = d->z; a.d_emb = G;
-        if (pg) { a.dw_mu = d->gwmu; a.db_mu = d->gbmu; a.dw_var = d->gwvar; a.db_var = d->gbvar; }
-        a.accumulate = acc ? 1 : 0;
-        E3FoldArgs f{};
-        f.mu = Carver::at(sv, y.mu); f.logvar = Carver::at(sv, y.lv); f.eps = Carver::at(sv, y.eps);
-        f.d_sample = d_sample; f.d_mu = d_mu; f.d_logvar = d_logvar; f.kl_scale = kl_scale;
-        if (int rc = launch_head_bwd(a, f, Carver::at<char>(workspace, y.head), st)) return rc;
-    }
-    for (int b = 7; b >= 0; --b) {
-        const E3Block& k = d->B[b];
-        const float* out = Carver::at(sv, y.act[k.c2]);
-        const float* xin = Carver::at(sv, y.act[k.in]);
-        const float* h1 = Carver::at(sv, y.act[k.c1]);
-        if (int rc = norm_conv_bwd(k.c2, G, out, h1, DC)) return rc;
-        if (int rc = launch_dgrad(d->L[k.c2], DC, nullptr, Carver::at(sv, y.wd[k.c2]), nullptr, nullptr, H1, false, n, y.geo[k.c2], st)) return rc;
-        if (int rc = norm_conv_bwd(k.c1, H1, h1, xin, DC)) return rc;
-        if (k.cd >= 0) {
-            if (int rc = norm_conv_bwd(k.cd, G, out, xin, DC2)) return rc;
-            if (int rc = launch_dgrad(d->L[k.cd], DC2, nullptr, Carver::at(sv, y.wd[k.cd]), nullptr, nullptr, X2, false, n, y.geo[k.cd], st)) return rc;
-            if (int rc = launch_dgrad(d->L[k.c1], DC, nullptr, Carver::at(sv, y.wd[k.c1]), X2, nullptr, Gn, false, n, y.geo[k.c1], st)) return rc;
-        } else if (int rc = launch_dgrad(d->L[k.c1], DC, nullptr, Carver::at(sv, y.wd[k.c1]), G, out, Gn, false, n, y.geo[k.c1], st)) {
-            return rc;
-        }
-        std::swap(G, Gn);
-    }
-    // G: the gradient at the stem's activation
-    if (int rc = norm_conv_bwd(0, G, Carver::at(sv, y.act[0]), Carver::at(sv, y.x4), DC)) return rc;
-    if (d_x)
-        if (int rc = launch_dgrad(d->L[0], DC, nullptr, Carver::at(sv, y.wd[0]), nullptr, nullptr, d_x, true, n, y.geo[0], st)) return rc;
-    return I2V_OK;
+    // the head: the gradient at the last activation -> gbuf[0]
+    const int last = d->trunk.last();
+    E3HeadArgs a{};
+    a.emb = Carver::at(sv, y.act[last]); a.w_mu = d->wmu; a.w_var = d->wvar; a.n = n; a.C = d->trunk.L[last].cout; a.z = d->z;
+    a.d_emb = Carver::at(workspace, y.gbuf[0]);
+    if (pg) { a.dw_mu = d->gwmu; a.db_mu = d->gbmu; a.dw_var = d->gwvar; a.db_var = d->gbvar; }
+    a.accumulate = acc ? 1 : 0;
+    E3FoldArgs f{};
+    f.eps = Carver::at(sv, y.tail[0]); f.mu = Carver::at(sv, y.tail[1]); f.logvar = Carver::at(sv, y.tail[2]);
+    f.d_sample = d_sample; f.d_mu = d_mu; f.d_logvar = d_logvar; f.kl_scale = kl_scale;
+    if (int rc = launch_head_bwd(a, f, Carver::at<char>(workspace, y.ws_tail), st)) return rc;
+    return r3_backward(d->trunk, y, nullptr, sv, d_x, pg, acc, workspace, st);
 }
 
 int i2v_enc3d_kl_backward(const float* mu, const float* logvar, int32_t n, int32_t z, float scale, float* d_mu, float* d_logvar, void* stream) {

@@ -1,7 +1,8 @@
 // The 3-D ResNet-18 trunk with GroupNorm(16) that the temporal discriminator (i2v_disc3d.hip) and the motion encoder's training path
-// (i2v_encoder_train.hip) share: the conv, input-gradient, weight-gradient, finish and GroupNorm kernels, their launchers and the plan
-// helpers, moved here unchanged from i2v_disc3d.hip (whose head comment describes them).  Included into the anonymous namespace of its
-// users, as i2v_power_iter.h is.
+// (i2v_encoder_train.hip) share: the conv, input-gradient, weight-gradient, finish, GroupNorm and pool kernels, their launchers and the
+// plan helpers, moved here unchanged from i2v_disc3d.hip (whose head comment describes them).  The host side of the trunk as a whole --
+// plan, binding, layout and the two walks -- is i2v_res3d_net.h.  Included into the anonymous namespace of its users, as
+// i2v_power_iter.h is.
 #pragma once
 #include "i2v_handle.h"
 #include "i2v_power_iter.h"
@@ -30,6 +31,63 @@ __global__ __launch_bounds__(256) void d3_add_kernel(float* __restrict__ dst, co
     for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += gridDim.x * 256L) dst[i] += src[i];
 }
 
+// ------------------------------------------------------------------------------------------------------------------ max pool
+// MaxPool3d(3, stride (1, 2, 2), pad 1); the first maximum in (t, h, w) scan order wins
+__global__ __launch_bounds__(256) void d3_maxpool_kernel(const float* __restrict__ x, float* __restrict__ out, int* __restrict__ arg, long total, int T,
+                                                         int H, int W, int Ho, int Wo, int C) {
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += gridDim.x * 256L) {
+        const int c = (int)(i % C);
+        long p = i / C;
+        const int wo = (int)(p % Wo); p /= Wo;
+        const int ho = (int)(p % Ho); p /= Ho;
+        const int to = (int)(p % T); p /= T;
+        float best = 0.f;
+        int bi = -1;
+        for (int dt = -1; dt <= 1; ++dt) {
+            const int t = to + dt;
+            if ((unsigned)t >= (unsigned)T) continue;
+            for (int dh = -1; dh <= 1; ++dh) {
+                const int h = 2 * ho + dh;
+                if ((unsigned)h >= (unsigned)H) continue;
+                for (int dw = -1; dw <= 1; ++dw) {
+                    const int w = 2 * wo + dw;
+                    if ((unsigned)w >= (unsigned)W) continue;
+                    const int idx = (t * H + h) * W + w;
+                    const float v = x[(p * (long)T * H * W + idx) * C + c];
+                    if (bi < 0 || v > best) { best = v; bi = idx; }
+                }
+            }
+        }
+        out[i] = best;
+        arg[i] = bi;
+    }
+}
+
+// a gather: the windows overlap, so an input sums the gradients of the windows that chose it, in the windows' scan order
+__global__ __launch_bounds__(256) void d3_maxpool_bwd_kernel(const float* __restrict__ g, const int* __restrict__ arg, float* __restrict__ dx, long total,
+                                                             int T, int H, int W, int Ho, int Wo, int C) {
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < total; i += gridDim.x * 256L) {
+        const int c = (int)(i % C);
+        long p = i / C;
+        const int w = (int)(p % W); p /= W;
+        const int h = (int)(p % H); p /= H;
+        const int t = (int)(p % T); p /= T;
+        const int idx = (t * H + h) * W + w;
+        const int ho0 = h / 2, ho1 = (h + 1) / 2, wo0 = w / 2, wo1 = (w + 1) / 2;   // 2 o - 1 <= i <= 2 o + 1
+        float acc = 0.f;
+        for (int to = t - 1; to <= t + 1; ++to) {
+            if ((unsigned)to >= (unsigned)T) continue;
+            for (int ho = ho0; ho <= ho1 && ho < Ho; ++ho)
+                for (int wo = wo0; wo <= wo1 && wo < Wo; ++wo) {
+                    const long o = (((p * T + to) * Ho + ho) * Wo + wo) * C + c;
+                    if (arg[o] == idx) acc += g[o];
+                }
+        }
+        dx[i] = acc;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------ weight packing
 // W (/ sigma) into the two operand layouts
 struct D3PackConv { const float* w; const float* sigma; float* wf; float* wd; int cout, cin, cinp, cind, ntap; long first; };
 struct D3PackArgs { D3PackConv c[D3_MAXCONV]; int nconv; long total; };

@@ -1965,19 +1965,15 @@ def _opt(t):
     return None if t is None else t.data_ptr()
 
 
-class NativePatchDisc(_Handle):
-    """Handle for ``i2v_patchdisc_*`` (include/i2v_hip_disc.h): NLayerDiscriminator forward and backward.  It packs nothing on the
-    host: ``bind`` hands over the DEVICE pointers of the module's parameters and buffers (read in place; ``weight_u``, ``weight_v``,
-    ``loc`` and ``scale`` are updated in place) and of their gradient tensors."""
-    _PREFIX = "i2v_patchdisc"
-
-    def __init__(self, in_channels=3, ndf=64, n_layers=3, use_actnorm=True, spectral_norm=True, device=None):
-        cfg = PatchDiscCfg(int(in_channels), int(ndf), int(n_layers), int(bool(use_actnorm)), int(bool(spectral_norm)))
-        self._create(device, ctypes.byref(cfg))
-        self.bound_ptrs, self.bound_grad_ptrs, self._keep, self._keep_grads = None, None, None, None
+class _BoundHandle(_Handle):
+    """A handle that packs nothing on the host: ``bind`` hands over the DEVICE pointers of the module's parameters and buffers (read in
+    place) and ``bind_grads`` those of their gradient tensors.  The two are bound apart: a fresh gradient buffer per backward re-binds
+    the gradients alone.  ``bound_ptrs`` / ``bound_grad_ptrs`` are the pointers last handed over; ``_keep`` / ``_keep_grads`` keep their
+    tensors alive."""
+    bound_ptrs = bound_grad_ptrs = _keep = _keep_grads = None
 
     def load(self, state_dict):
-        raise I2VError("NativePatchDisc packs nothing: bind() hands over the module's own parameters")
+        raise I2VError(f"{type(self).__name__} packs nothing: bind() hands over the module's own parameters")
 
     @staticmethod
     def _items(tensors):
@@ -1990,21 +1986,80 @@ class NativePatchDisc(_Handle):
         """tensors: {state_dict key: float32 device tensor} of the parameters and the spectral-norm buffers."""
         with self._on(*tensors.values()):
             arr, keep = self._items(tensors)
-            _call("i2v_patchdisc_bind", self._h, arr, len(keep))
+            _call(f"{self._PREFIX}_bind", self._h, arr, len(keep))
         self.bound_ptrs = tuple(t.data_ptr() for t in tensors.values())
         self._keep = tensors
 
     def bind_grads(self, grads):
-        """grads: {key: gradient tensor} of the trained parameters, or None.  Bound apart from the parameters: a fresh gradient buffer per
-        backward re-binds these alone."""
+        """grads: {key: gradient tensor} of the trained parameters, or None."""
         if grads is None:
-            _call("i2v_patchdisc_bind_grads", self._h, None, 0)
+            _call(f"{self._PREFIX}_bind_grads", self._h, None, 0)
         else:
             with self._on(*grads.values()):
                 arr, keep = self._items(grads)
-                _call("i2v_patchdisc_bind_grads", self._h, arr, len(keep))
+                _call(f"{self._PREFIX}_bind_grads", self._h, arr, len(keep))
         self.bound_grad_ptrs = None if grads is None else tuple(g.data_ptr() for g in grads.values())
         self._keep_grads = grads
+
+
+class _Res3DHandle(_BoundHandle):
+    """What the two handles on the 3-D ResNet training trunk (csrc/i2v_res3d_net.h) share: the clip check and the views of ``saved``."""
+    _NAME = None                  # the network, for messages
+    _INT32_KINDS = frozenset()    # the kinds of ``saved_maps`` that hold int32
+
+    def _shape(self, x):
+        if x.dim() != 5 or x.shape[1] != 3:
+            raise I2VError(f"{self._NAME}: expected clips [N, 3, T, H, W], got {tuple(x.shape)}")
+        n, _, t, h, w = x.shape
+        return n, t, h, w
+
+    def saved_bytes(self, n, t, h, w):
+        return int(getattr(lib(), self._PREFIX + "_saved_bytes")(self._h, n, t, h, w))
+
+    def workspace_bytes(self, n, t, h, w):
+        return int(getattr(lib(), self._PREFIX + "_workspace_bytes")(self._h, n, t, h, w))
+
+    def saved_maps(self, saved, shape):
+        """{(kind, conv): view of ``saved`` [N, T, H, W, C]} (the network's kinds; the pool's maps have conv -1), for the tests."""
+        n, _, t, h, w = shape
+        cnt, kind, conv, dims, off = c_int32(), (c_int32 * 64)(), (c_int32 * 64)(), (c_int32 * 256)(), (c_int64 * 64)()
+        _call(self._PREFIX + "_saved_layout", self._h, n, t, h, w, ctypes.byref(cnt), kind, conv, dims, off)
+        out = {}
+        for e in range(cnt.value):
+            shp = (n, *dims[4 * e: 4 * e + 4])
+            flat = saved.view(torch.int32 if kind[e] in self._INT32_KINDS else torch.float32)
+            out[(kind[e], conv[e])] = flat[off[e] // 4: off[e] // 4 + int(np.prod(shp))].view(shp)
+        return out
+
+
+def flat_param_grads(module, device):
+    """{parameter name: gradient tensor} for every parameter of ``module``: views of one flat fp32 allocation on ``device``, each
+    starting on a multiple of 4 floats."""
+    sizes = [(p.numel() + 3) // 4 * 4 for p in module.parameters()]
+    flat = torch.empty(sum(sizes), dtype=torch.float32, device=device)
+    return {k: v[:p.numel()].view(p.shape) for (k, p), v in zip(module.named_parameters(), flat.split(sizes))}
+
+
+def bind_in_place(handle, tensors, grads=None):
+    """Binds a _BoundHandle to the storage of ``tensors`` as it is now and, when ``grads`` ({parameter name: tensor}) is given, to those
+    gradient tensors, each only if its pointers moved; the two bindings are kept apart, so a forward never re-binds because of a
+    backward's gradient buffer."""
+    if handle.bound_ptrs != tuple(t.data_ptr() for t in tensors.values()):
+        handle.bind({k: t.detach().view(-1) for k, t in tensors.items()})
+    if grads is not None and handle.bound_grad_ptrs != tuple(g.data_ptr() for g in grads.values()):
+        handle.bind_grads({k: g.detach().view(-1) for k, g in grads.items()})
+    return handle
+
+
+class NativePatchDisc(_BoundHandle):
+    """Handle for ``i2v_patchdisc_*`` (include/i2v_hip_disc.h): NLayerDiscriminator forward and backward.  It packs nothing on the
+    host: ``bind`` hands over the DEVICE pointers of the module's parameters and buffers (read in place; ``weight_u``, ``weight_v``,
+    ``loc`` and ``scale`` are updated in place) and of their gradient tensors."""
+    _PREFIX = "i2v_patchdisc"
+
+    def __init__(self, in_channels=3, ndf=64, n_layers=3, use_actnorm=True, spectral_norm=True, device=None):
+        cfg = PatchDiscCfg(int(in_channels), int(ndf), int(n_layers), int(bool(use_actnorm)), int(bool(spectral_norm)))
+        self._create(device, ctypes.byref(cfg))
 
     def out_shape(self, h, w):
         ho, wo = c_int32(), c_int32()
@@ -2176,11 +2231,11 @@ def _ptr_array(tensors, count=4):
     return (c_void_p * count)(*[None if t is None else t.data_ptr() for t in tensors])
 
 
-class NativeDisc3D(_Handle):
+class NativeDisc3D(_Res3DHandle):
     """Handle for ``i2v_disc3d_*`` (include/i2v_hip_disc3d.h): resnet3D.Discriminator forward and backward.  It packs nothing on the
     host: ``bind`` hands over the DEVICE pointers of the module's parameters and buffers (read in place; ``weight_u`` and ``weight_v``
     are updated in place) and ``bind_grads`` those of their gradient tensors.  Feature maps are channels-last [N, T, H, W, C]."""
-    _PREFIX = "i2v_disc3d"
+    _PREFIX, _NAME, _INT32_KINDS = "i2v_disc3d", "temporal discriminator", frozenset({DISC3D_POOL_ARGMAX})
 
     def __init__(self, channels, stride_s, stride_t, use_max_pool=True, spectral_norm=True, res_type=18, device=None):
         if len(channels) != 5 or len(stride_s) != 4 or len(stride_t) != 4:
@@ -2188,59 +2243,12 @@ class NativeDisc3D(_Handle):
         cfg = Disc3DCfg(int(res_type), (c_int32 * 5)(*map(int, channels)), (c_int32 * 4)(*map(int, stride_s)), (c_int32 * 4)(*map(int, stride_t)),
                         int(bool(use_max_pool)), int(bool(spectral_norm)))
         self._create(device, ctypes.byref(cfg))
-        self.bound_ptrs, self.bound_grad_ptrs, self._keep, self._keep_grads = None, None, None, None
-
-    def load(self, state_dict):
-        raise I2VError("NativeDisc3D packs nothing: bind() hands over the module's own parameters")
-
-    def bind(self, tensors):
-        """tensors: {state_dict key: float32 device tensor} of the parameters and the spectral-norm buffers."""
-        with self._on(*tensors.values()):
-            arr, keep = NativePatchDisc._items(tensors)
-            _call("i2v_disc3d_bind", self._h, arr, len(keep))
-        self.bound_ptrs = tuple(t.data_ptr() for t in tensors.values())
-        self._keep = tensors
-
-    def bind_grads(self, grads):
-        """grads: {key: gradient tensor} of the parameters, or None."""
-        if grads is None:
-            _call("i2v_disc3d_bind_grads", self._h, None, 0)
-        else:
-            with self._on(*grads.values()):
-                arr, keep = NativePatchDisc._items(grads)
-                _call("i2v_disc3d_bind_grads", self._h, arr, len(keep))
-        self.bound_grad_ptrs = None if grads is None else tuple(g.data_ptr() for g in grads.values())
-        self._keep_grads = grads
 
     def out_shape(self, t, h, w):
         """[(t, h, w, c)] of the four feature maps; raises with the final map in the message unless the net ends on [1, 4, 4]."""
         s = (c_int32 * 16)()
         _call("i2v_disc3d_out_shape", self._h, int(t), int(h), int(w), s)
         return [tuple(s[4 * i: 4 * i + 4]) for i in range(4)]
-
-    def _shape(self, x):
-        if x.dim() != 5 or x.shape[1] != 3:
-            raise I2VError(f"temporal discriminator: expected clips [N, 3, T, H, W], got {tuple(x.shape)}")
-        n, _, t, h, w = x.shape
-        return n, t, h, w
-
-    def saved_bytes(self, n, t, h, w):
-        return int(lib().i2v_disc3d_saved_bytes(self._h, n, t, h, w))
-
-    def workspace_bytes(self, n, t, h, w):
-        return int(lib().i2v_disc3d_workspace_bytes(self._h, n, t, h, w))
-
-    def saved_maps(self, saved, shape):
-        """{(kind, conv): view of ``saved`` [N, T, H, W, C]} (kinds DISC3D_*; the pool's maps have conv -1; the argmax is int32), for the tests."""
-        n, _, t, h, w = shape
-        cnt, kind, conv, dims, off = c_int32(), (c_int32 * 64)(), (c_int32 * 64)(), (c_int32 * 256)(), (c_int64 * 64)()
-        _call("i2v_disc3d_saved_layout", self._h, n, t, h, w, ctypes.byref(cnt), kind, conv, dims, off)
-        out = {}
-        for e in range(cnt.value):
-            shp = (n, *dims[4 * e: 4 * e + 4])
-            flat = saved.view(torch.int32 if kind[e] == DISC3D_POOL_ARGMAX else torch.float32)
-            out[(kind[e], conv[e])] = flat[off[e] // 4: off[e] // 4 + int(np.prod(shp))].view(shp)
-        return out
 
     @_on_device
     def forward(self, x, iterate=False, save=False, want_fmaps=True):
@@ -2430,11 +2438,11 @@ ENC3D_TRAIN_SAVE = 1
 ENC3D_TRAIN_CONV_OUT, ENC3D_TRAIN_ACT = 0, 1
 
 
-class NativeEnc3DTrain(_Handle):
+class NativeEnc3DTrain(_Res3DHandle):
     """Handle for ``i2v_enc3d_train_*`` (include/i2v_hip_enc3d_train.h): resnet3D.Encoder forward and backward with the posterior head and
     the KL gradient.  It packs nothing on the host: ``bind`` hands over the DEVICE pointers of the module's parameters (read in place, so
     an optimiser step is seen by the next call) and ``bind_grads`` those of their gradient tensors."""
-    _PREFIX = "i2v_enc3d_train"
+    _PREFIX, _NAME = "i2v_enc3d_train", "motion encoder"
 
     def __init__(self, z_dim, channels, stride_s, stride_t, use_max_pool=False, device=None):
         if len(channels) != 5 or len(stride_s) != 4 or len(stride_t) != 4:
@@ -2443,58 +2451,12 @@ class NativeEnc3DTrain(_Handle):
                             int(bool(use_max_pool)))
         self._create(device, ctypes.byref(cfg))
         self.z_dim = int(z_dim)
-        self.bound_ptrs, self.bound_grad_ptrs, self._keep, self._keep_grads = None, None, None, None
-
-    def load(self, state_dict):
-        raise I2VError("NativeEnc3DTrain packs nothing: bind() hands over the module's own parameters")
-
-    def bind(self, tensors):
-        """tensors: {state_dict key: float32 device tensor} of the parameters."""
-        with self._on(*tensors.values()):
-            arr, keep = NativePatchDisc._items(tensors)
-            _call("i2v_enc3d_train_bind", self._h, arr, len(keep))
-        self.bound_ptrs = tuple(t.data_ptr() for t in tensors.values())
-        self._keep = tensors
-
-    def bind_grads(self, grads):
-        """grads: {key: gradient tensor} of the parameters, or None."""
-        if grads is None:
-            _call("i2v_enc3d_train_bind_grads", self._h, None, 0)
-        else:
-            with self._on(*grads.values()):
-                arr, keep = NativePatchDisc._items(grads)
-                _call("i2v_enc3d_train_bind_grads", self._h, arr, len(keep))
-        self.bound_grad_ptrs = None if grads is None else tuple(g.data_ptr() for g in grads.values())
-        self._keep_grads = grads
 
     def out_shape(self, t, h, w):
         """(t, h, w, c) of the trunk's last map; raises with the map in the message unless it is [1, 4, 4]."""
         s = (c_int32 * 4)()
         _call("i2v_enc3d_train_out_shape", self._h, int(t), int(h), int(w), s)
         return tuple(s)
-
-    def _shape(self, x):
-        if x.dim() != 5 or x.shape[1] != 3:
-            raise I2VError(f"motion encoder: expected clips [N, 3, T, H, W], got {tuple(x.shape)}")
-        n, _, t, h, w = x.shape
-        return n, t, h, w
-
-    def saved_bytes(self, n, t, h, w):
-        return int(lib().i2v_enc3d_train_saved_bytes(self._h, n, t, h, w))
-
-    def workspace_bytes(self, n, t, h, w):
-        return int(lib().i2v_enc3d_train_workspace_bytes(self._h, n, t, h, w))
-
-    def saved_maps(self, saved, shape):
-        """{(kind, conv): view of ``saved`` [N, T, H, W, C]} (kinds ENC3D_TRAIN_*), for the tests."""
-        n, _, t, h, w = shape
-        cnt, kind, conv, dims, off = c_int32(), (c_int32 * 64)(), (c_int32 * 64)(), (c_int32 * 256)(), (c_int64 * 64)()
-        _call("i2v_enc3d_train_saved_layout", self._h, n, t, h, w, ctypes.byref(cnt), kind, conv, dims, off)
-        out, flat = {}, saved.view(torch.float32)
-        for e in range(cnt.value):
-            shp = (n, *dims[4 * e: 4 * e + 4])
-            out[(kind[e], conv[e])] = flat[off[e] // 4: off[e] // 4 + int(np.prod(shp))].view(shp)
-        return out
 
     @_on_device
     def forward(self, x, eps=None, save=False):

@@ -90,13 +90,7 @@ class _PatchDiscFunction(torch.autograd.Function):
     def backward(ctx, d_pred):
         module = ctx.module
         want = ctx.needs_input_grad[2:]
-        grads = None
-        if any(want):
-            names = [k for k, _ in module.named_parameters()]
-            sizes = [(p.numel() + 3) // 4 * 4 for p in module.parameters()]
-            flat = torch.empty(sum(sizes), dtype=torch.float32, device=d_pred.device)
-            views = [v[:p.numel()].view(p.shape) for v, p in zip(flat.split(sizes), module.parameters())]
-            grads = dict(zip(names, views))
+        grads = native.flat_param_grads(module, d_pred.device) if any(want) else None
         h = module._handle(grads)
         dx = h.backward(d_pred.contiguous(), ctx.saved, ctx.shape, need_dx=ctx.needs_input_grad[1], param_grads=grads is not None, accumulate=False)
         out = [None] * len(want) if grads is None else [g if w else None for g, w in zip(grads.values(), want)]
@@ -165,11 +159,7 @@ class NLayerDiscriminator(nn.Module):
         if h is None or h.device != dev:
             h = native.NativePatchDisc(device=dev, **self.cfg)
             object.__setattr__(self, "_native", h)
-        if h.bound_ptrs != tuple(t.data_ptr() for t in tensors.values()):
-            h.bind({k: t.detach().view(-1) for k, t in tensors.items()})
-        if grads is not None and h.bound_grad_ptrs != tuple(g.data_ptr() for g in grads.values()):
-            h.bind_grads({k: g.detach().view(-1) for k, g in grads.items()})
-        return h
+        return native.bind_in_place(h, tensors, grads)
 
     def _needs_init(self):
         """Training mode with ActNorm not initialised yet (the buffers are read once, then the answer is remembered on the host)."""

@@ -165,13 +165,7 @@ class _Disc3DFunction(torch.autograd.Function):
                                       "penalty's gradient) is not built")
         module = ctx.module
         want = ctx.needs_input_grad[2:]
-        grads = None
-        if any(want):
-            names = [k for k, _ in module.named_parameters()]
-            sizes = [(p.numel() + 3) // 4 * 4 for p in module.parameters()]
-            flat = torch.empty(sum(sizes), dtype=torch.float32, device=ctx.saved.device)
-            views = [v[:p.numel()].view(p.shape) for v, p in zip(flat.split(sizes), module.parameters())]
-            grads = dict(zip(names, views))
+        grads = native.flat_param_grads(module, ctx.saved.device) if any(want) else None
         h = module._handle(grads)
         cl = [None if g is None else g.permute(0, 2, 3, 4, 1).contiguous().float() for g in d_fmaps]
         dx = h.backward(None if d_pred is None else d_pred.contiguous().float(), cl, ctx.saved, ctx.shape, need_dx=ctx.needs_input_grad[1],
@@ -241,11 +235,7 @@ class Discriminator(nn.Module):
         if h is None or h.device != dev:
             h = native.NativeDisc3D(device=dev, **self.cfg)
             object.__setattr__(self, "_native", h)
-        if h.bound_ptrs != tuple(t.data_ptr() for t in tensors.values()):
-            h.bind({k: t.detach().view(-1) for k, t in tensors.items()})
-        if grads is not None and h.bound_grad_ptrs != tuple(g.data_ptr() for g in grads.values()):
-            h.bind_grads({k: g.detach().view(-1) for k, g in grads.items()})
-        return h
+        return native.bind_in_place(h, tensors, grads)
 
     def _run(self, x, save, grads=None, want_fmaps=True):
         """x [B, 3, T, H, W] -> (pred, channels-last feature maps or None, saved or None); training mode iterates the spectral norm."""
@@ -297,13 +287,7 @@ class _Enc3DTrainFunction(torch.autograd.Function):
         ups = [None if g is None else g.contiguous().float() for g in (d_sample, d_mu, d_logvar)]
         if all(g is None for g in ups):
             return (None,) * (3 + len(want))
-        grads = None
-        if any(want):
-            names = [k for k, _ in module.named_parameters()]
-            sizes = [(p.numel() + 3) // 4 * 4 for p in module.parameters()]
-            flat = torch.empty(sum(sizes), dtype=torch.float32, device=ctx.saved.device)
-            views = [v[:p.numel()].view(p.shape) for v, p in zip(flat.split(sizes), module.parameters())]
-            grads = dict(zip(names, views))
+        grads = native.flat_param_grads(module, ctx.saved.device) if any(want) else None
         h = module._train_handle(grads)
         dx = h.backward(*ups, ctx.saved, ctx.shape, need_dx=ctx.needs_input_grad[1] or grads is None, param_grads=grads is not None, accumulate=False)
         out = [None] * len(want) if grads is None else [g if w else None for g, w in zip(grads.values(), want)]
@@ -348,11 +332,7 @@ class Encoder(_PackedEncoder):
         if h is None or h.device != dev:
             h = native.NativeEnc3DTrain(self.z_dim, self.channels, self.stride_s, self.stride_t, device=dev)
             object.__setattr__(self, "_train_native", h)
-        if h.bound_ptrs != tuple(t.data_ptr() for t in tensors.values()):
-            h.bind({k: t.detach().view(-1) for k, t in tensors.items()})
-        if grads is not None and h.bound_grad_ptrs != tuple(g.data_ptr() for g in grads.values()):
-            h.bind_grads({k: g.detach().view(-1) for k, g in grads.items()})
-        return h
+        return native.bind_in_place(h, tensors, grads)
 
     def forward(self, x, eps=None):
         """As the inference forward; ``eps`` [B, z]: the reparameterisation's draw, when the caller supplies it."""

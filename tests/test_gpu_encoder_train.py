@@ -243,6 +243,23 @@ def test_oracle_on_the_gpus_decisions(tag):
     against_oracle(tag.upper(), cfg, ec.synthetic_state(cfg, seed), x, eps, coefs, ec.KL_WEIGHT)
 
 
+@pytest.mark.parametrize("tag", ["a", "b"])
+def test_saved_layout_is_consistent(tag):
+    """The entries of ``saved_maps``: inside ``saved``, on 256-byte offsets, disjoint, two per conv; the workspace holds a forward that
+    does not save."""
+    cfg, clip, seed = FIXTURES[tag]
+    x, eps, *_ = dev(*ec.inputs(cfg, clip, seed))
+    h = module(cfg, ec.synthetic_state(cfg, seed))._train_handle()
+    n, _, t, hh, w = clip
+    saved = h.forward(x, eps, save=True)[3]
+    assert saved.numel() == h.saved_bytes(n, t, hh, w) <= h.workspace_bytes(n, t, hh, w)
+    maps = h.saved_maps(saved, clip)
+    assert len(maps) == 2 * (1 + sum(3 if b["ds"] else 2 for b in ec.blocks(cfg)))
+    spans = sorted((m.data_ptr() - saved.data_ptr(), m.data_ptr() - saved.data_ptr() + m.numel() * m.element_size()) for m in maps.values())
+    assert all(a % 256 == 0 and 0 <= a < b <= saved.numel() for a, b in spans)
+    assert all(p[1] <= q[0] for p, q in zip(spans, spans[1:]))          # sorted by their starts: no two overlap
+
+
 def test_refusal_names_the_final_map():
     net = module(ec.CFG_B, ec.synthetic_state(ec.CFG_B, ec.SEED_B))
     with pytest.raises(i2v_native.I2VError, match=r"\[1, 8, 8\] map"):

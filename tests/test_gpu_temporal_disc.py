@@ -350,6 +350,25 @@ def test_refusal_names_the_final_map(fxa):
     assert big.out_shape(12, 128, 128)[3][:3] == (1, 4, 4)
 
 
+@pytest.mark.parametrize("cfg,clips", ((tc.CFG_A, lambda: tc.clips_a()[0]), (tc.CFG_B, tc.clips_b), (tc.CFG_C, tc.clips_c)), ids=("A", "B", "C-no-pool"))
+def test_saved_layout_is_consistent(cfg, clips):
+    """The entries of ``saved_maps``: inside ``saved``, on 256-byte offsets, disjoint, two per conv plus the pool's two; the last conv's
+    activation is the fourth feature map; the workspace holds a forward that does not save."""
+    net = module(cfg, tc.synthetic_state(cfg, tc.SEED_B)).eval()
+    x = clips().to(DEV)
+    n, _, t, hh, w = shape = tuple(x.shape)
+    _, fmaps, saved = net._run(x, save=True)
+    h = net._handle()
+    assert saved.numel() == h.saved_bytes(n, t, hh, w) <= h.workspace_bytes(n, t, hh, w)
+    maps = h.saved_maps(saved, shape)
+    nconv = 1 + sum(3 if b["ds"] else 2 for b in tc.blocks(cfg))
+    assert len(maps) == 2 * nconv + (2 if cfg["use_max_pool"] else 0)
+    spans = sorted((m.data_ptr() - saved.data_ptr(), m.data_ptr() - saved.data_ptr() + m.numel() * m.element_size()) for m in maps.values())
+    assert all(a % 256 == 0 and 0 <= a < b <= saved.numel() for a, b in spans)
+    assert all(p[1] <= q[0] for p, q in zip(spans, spans[1:]))          # sorted by their starts: no two overlap
+    assert torch.equal(maps[(i2v_native.DISC3D_ACT, nconv - 1)], fmaps[3])
+
+
 # ---------------------------------------------------------------------------------------------------------------- oracle on the GPU's decisions
 
 def gpu_decisions(handle, saved, shape, cfg):

@@ -139,6 +139,19 @@ def test_sources_are_built_share_the_trunk_and_read_no_environment():
     for kernel in ("d3_conv_kernel", "d3_dgrad_kernel", "d3_wgrad_kernel", "d3_gn_bwd_dx_kernel"):      # one definition, in the shared header
         assert f"void {kernel}(" in trunk and f"void {kernel}(" not in disc and f"void {kernel}(" not in enc
     assert "mfma_f32_16x16x4f32" in enc
+    # the plan, the layout and the two walks exist once, in i2v_res3d_net.h
+    assert "i2v_res3d_net.h" in hdrs
+    net = open(os.path.join(PKG, "csrc", "i2v_res3d_net.h")).read()
+    assert "getenv" not in net and "atomic" not in net.lower()
+    assert '#include "i2v_res3d_net.h"' in enc and '#include "i2v_res3d_net.h"' in disc
+    for src in (enc, disc):
+        for gone in ("struct D3Block", "struct E3Block", "D3Layout", "E3Layout", "e3_bound", "e3_refuse"):
+            assert gone not in src, gone
+    for launcher in ("launch_conv(", "launch_dgrad(", "launch_gn_bwd(", "launch_wgrad("):     # the discriminator's: its unit entry
+        assert disc.count(launcher) == 1 and enc.count(launcher) == 0 and net.count(launcher) >= 1, launcher
+    assert net.count("hipLaunchKernelGGL(d3_pack_kernel") == 1 and "d3_pack_kernel" not in enc
+    assert disc.count("d3_pack_kernel") == 1 and "d3_pack_kernel" in disc[disc.index("int pack_unit("):disc.index("}  // namespace", disc.index("int pack_unit("))]
+    assert "void d3_maxpool_kernel(" in trunk and "void d3_maxpool_kernel(" not in disc and "void d3_maxpool_kernel(" not in enc
 
 
 def test_state_dict_keys_are_the_existing_encoder_s_and_the_reference_s():
