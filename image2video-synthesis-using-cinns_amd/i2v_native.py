@@ -326,6 +326,31 @@ ENC3D_TRAIN_SYMBOLS = {
                                                c_void_p]),
 }
 
+# The entries of include/i2v_hip_gblock_train.h (the training path of one GeneratorBlock), one to one.
+GBLOCK_TRAIN_SYMBOLS = {
+    "i2v_gblock_train_create": (c_int32, [c_int32, c_int32, c_int32, c_int32, POINTER(c_void_p)]),
+    "i2v_gblock_train_destroy": (None, [c_void_p]),
+    "i2v_gblock_train_bind": (c_int32, [c_void_p, POINTER(_Tensor), c_int32]),
+    "i2v_gblock_train_bind_grads": (c_int32, [c_void_p, POINTER(_Tensor), c_int32]),
+    "i2v_gblock_train_saved_bytes": (c_size_t, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "i2v_gblock_train_workspace_bytes": (c_size_t, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "i2v_gblock_train_forward": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                           c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),
+    "i2v_gblock_train_backward": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                            c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_size_t, c_void_p]),
+    "i2v_gblock_train_unit_workspace_bytes": (c_size_t, [c_int32, c_int64, c_int32]),
+    "i2v_gblock_train_modnorm_backward_unit": (c_int32, [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "i2v_gblock_train_pointwise_unit": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
+    "i2v_gblock_train_pointwise_wgrad_unit": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32,
+                                                        c_void_p, c_void_p, c_size_t, c_void_p]),
+    "i2v_gblock_train_bias_grad_unit": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "i2v_gblock_train_linear_backward_unit": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                                        c_void_p]),
+    "i2v_gblock_train_conv2d_unit": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                               c_void_p, c_size_t, c_void_p]),
+}
+
 
 def build(force=False):
     """Compile ``libi2v_hip.so`` for gfx950 in-tree (``make`` in csrc/; hipcc cross-compiles without a GPU)."""
@@ -357,7 +382,8 @@ def lib():
             raise I2VError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                            f"or `make -C {CSRC}`; this package has no CPU/eager fallback")
         l = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in list(SYMBOLS.items()) + list(DISC_SYMBOLS.items()) + list(DISC3D_SYMBOLS.items()) + list(ENC3D_TRAIN_SYMBOLS.items()):
+        for name, (res, args) in (list(SYMBOLS.items()) + list(DISC_SYMBOLS.items()) + list(DISC3D_SYMBOLS.items()) + list(ENC3D_TRAIN_SYMBOLS.items())
+                                 + list(GBLOCK_TRAIN_SYMBOLS.items())):
             fn = getattr(l, name)
             fn.restype = res
             fn.argtypes = args
@@ -2533,3 +2559,143 @@ def enc3d_head_backward_unit(emb, w_mu, w_var, mu, logvar, eps=None, d_sample=No
               _opt(d_sample), _opt(d_mu), _opt(d_logvar), float(kl_scale), n, c, z, d_emb.data_ptr(), *[_opt(t) for t in g], int(into is not None),
               ws.data_ptr(), ws.numel(), _stream())
     return (d_emb, *g)
+
+
+# ---------------------------------------------------------------------------------------------------------------- GeneratorBlock, training path
+GBLOCK_TRAIN_SAVE, GBLOCK_TRAIN_TRAIN = 1, 2
+GBLOCK_TRAIN_SPADE, GBLOCK_TRAIN_ADAIN = 0, 1
+
+
+class NativeGBlockTrain(_BoundHandle):
+    """Handle for ``i2v_gblock_train_*`` (include/i2v_hip_gblock_train.h): one GeneratorBlock forward and backward in exact fp32.  It packs
+    nothing on the host: ``bind`` hands over the DEVICE pointers of the module's parameters and spectral-norm buffers (read in place, so an
+    optimiser step is seen by the next call; ``weight_u`` / ``weight_v`` are iterated in place) and ``bind_grads`` those of the gradients."""
+    _PREFIX = "i2v_gblock_train"
+
+    def __init__(self, n_in, n_out, z_dim, spectral_norm=True, device=None):
+        self._create(device, int(n_in), int(n_out), int(z_dim), int(bool(spectral_norm)))
+        self.n_in, self.n_out, self.n_mid, self.z_dim = int(n_in), int(n_out), min(int(n_in), int(n_out)), int(z_dim)
+
+    def _geom(self, shape, img_shape):
+        B, _, T, H, W = shape
+        return B, T, H, W, int(img_shape[2]), int(img_shape[3])
+
+    def saved_bytes(self, *geom):
+        return int(lib().i2v_gblock_train_saved_bytes(self._h, *geom))
+
+    def workspace_bytes(self, *geom):
+        return int(lib().i2v_gblock_train_workspace_bytes(self._h, *geom))
+
+    @_on_device
+    def forward(self, x, z, img, train=False, save=False):
+        """x [B, n_in, T, H, W], z [B, z_dim], img [B, 3, h, w] -> (out [B, n_out, T, H, W], saved or None)."""
+        _require_gpu(x, z, img)
+        if x.dim() != 5 or x.shape[1] != self.n_in:
+            raise I2VError(f"GeneratorBlock: expected x [B,{self.n_in},T,H,W], got {tuple(x.shape)}")
+        B = x.shape[0]
+        if z.shape != (B, self.z_dim) or img.dim() != 4 or img.shape[:2] != (B, 3):
+            raise I2VError(f"GeneratorBlock: expected z [B,{self.z_dim}] and img [B,3,h,w], got {tuple(z.shape)}, {tuple(img.shape)}")
+        geom = self._geom(x.shape, img.shape)
+        ws = self._scratch(self.workspace_bytes(*geom), x.device)
+        saved = torch.empty(self.saved_bytes(*geom), dtype=torch.uint8, device=x.device) if save else None
+        out = torch.empty(B, self.n_out, *x.shape[2:], dtype=torch.float32, device=x.device)
+        flags = (GBLOCK_TRAIN_SAVE if save else 0) | (GBLOCK_TRAIN_TRAIN if train else 0)
+        _call("i2v_gblock_train_forward", self._h, x.data_ptr(), z.data_ptr(), img.data_ptr(), *geom, flags, out.data_ptr(), _opt(saved),
+              0 if saved is None else saved.numel(), *ws, _stream())
+        return out, saved
+
+    @_on_device
+    def backward(self, g_out, z, saved, shape, img_shape, need_dx=True, need_dz=True, param_grads=True, accumulate=False):
+        """``shape`` / ``img_shape``: those of the forward's x and img -> (dx or None, dz or None); the parameter gradients go to the bound
+        gradient tensors, written or (``accumulate``) added."""
+        _require_gpu(g_out, z)
+        geom = self._geom(shape, img_shape)
+        ws = self._scratch(self.workspace_bytes(*geom), saved.device)
+        dx = torch.empty(shape, dtype=torch.float32, device=saved.device) if need_dx else None
+        dz = torch.empty(shape[0], self.z_dim, dtype=torch.float32, device=saved.device) if need_dz else None
+        _call("i2v_gblock_train_backward", self._h, g_out.data_ptr(), z.data_ptr(), saved.data_ptr(), saved.numel(), *geom, _opt(dx), _opt(dz),
+              int(bool(param_grads)), int(bool(accumulate)), *ws, _stream())
+        return dx, dz
+
+
+def _gbt_ws(batch, rows, c, device):
+    return torch.empty(int(lib().i2v_gblock_train_unit_workspace_bytes(int(batch), int(rows), int(c))), dtype=torch.uint8, device=device)
+
+
+def gblock_train_modnorm_backward_unit(mode, g, act, x, mod, add=None, want_dx=True, want_maps=True):
+    """g, act, x [B, T, H, W, C] channels-last.  Spade (mode 0): mod = gamma [B, H, W, C] -> (dx, dgamma, dbeta [B, H, W, C]); ADAIN (mode 1):
+    mod = lin [B, 2 C] -> (dx, d_lin [B, 2 C], None).  What is not wanted comes back as None."""
+    _require_gpu(g, act, x, mod, add)
+    B, T, H, W, C = x.shape
+    with torch.cuda.device(x.device):
+        ws = _gbt_ws(B, x.numel() // C, C, x.device)
+        dx = torch.empty_like(x) if want_dx else None
+        dgamma = torch.empty_like(mod) if want_maps else None
+        dbeta = torch.empty_like(mod) if want_maps and mode == GBLOCK_TRAIN_SPADE else None
+        _call("i2v_gblock_train_modnorm_backward_unit", int(mode), g.data_ptr(), act.data_ptr(), x.data_ptr(), mod.data_ptr(), B, T, H, W, C, _opt(add),
+              _opt(dx), _opt(dgamma), _opt(dbeta), ws.data_ptr(), ws.numel(), _stream())
+    return dx, dgamma, dbeta
+
+
+def gblock_train_pointwise_unit(a, w, add=None):
+    """a [..., K] channels-last, w [N, K] -> a . w^T (+ add) [..., N]."""
+    _require_gpu(a, w, add)
+    k, n = a.shape[-1], w.shape[0]
+    with torch.cuda.device(a.device):
+        out = torch.empty(*a.shape[:-1], n, dtype=torch.float32, device=a.device)
+        _call("i2v_gblock_train_pointwise_unit", a.data_ptr(), w.data_ptr(), _opt(add), a.numel() // k, k, n, out.data_ptr(), _stream())
+    return out
+
+
+def gblock_train_pointwise_wgrad_unit(g, x, w, u=None, v=None, sigma=None, dweight=None):
+    """g [..., Cout], x [..., Cin], w [Cout, Cin] -> dweight; given ``dweight`` the result is ADDED to it."""
+    _require_gpu(g, x, w, u, v, sigma, dweight)
+    cout, cin = w.shape
+    accumulate = dweight is not None
+    with torch.cuda.device(g.device):
+        ws = _gbt_ws(1, g.numel() // cout, max(cout, cin), g.device)
+        if not accumulate:
+            dweight = torch.empty_like(w)
+        _call("i2v_gblock_train_pointwise_wgrad_unit", g.data_ptr(), x.data_ptr(), w.data_ptr(), _opt(u), _opt(v), _opt(sigma), g.numel() // cout, cout,
+              cin, int(accumulate), dweight.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+    return dweight
+
+
+def gblock_train_bias_grad_unit(g, dbias=None):
+    """g [..., C] -> the float64 sum over the rows, rounded once; given ``dbias`` the result is ADDED to it."""
+    _require_gpu(g, dbias)
+    c = g.shape[-1]
+    accumulate = dbias is not None
+    with torch.cuda.device(g.device):
+        ws = _gbt_ws(1, g.numel() // c, c, g.device)
+        if not accumulate:
+            dbias = torch.empty(c, dtype=torch.float32, device=g.device)
+        _call("i2v_gblock_train_bias_grad_unit", g.data_ptr(), g.numel() // c, c, int(accumulate), dbias.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+    return dbias
+
+
+def gblock_train_linear_backward_unit(d_lin, z, w, want=(True, True, True)):
+    """d_lin [B, J], z [B, K], w [J, K] -> (dw, db, dz), each None where ``want`` says so."""
+    _require_gpu(d_lin, z, w)
+    (B, J), K = d_lin.shape, z.shape[1]
+    with torch.cuda.device(z.device):
+        dw = torch.empty_like(w) if want[0] else None
+        db = torch.empty(J, dtype=torch.float32, device=z.device) if want[1] else None
+        dz = torch.empty_like(z) if want[2] else None
+        _call("i2v_gblock_train_linear_backward_unit", d_lin.data_ptr(), z.data_ptr(), w.data_ptr(), B, J, K, 0, _opt(dw), _opt(db), _opt(dz), _stream())
+    return dw, db, dz
+
+
+def gblock_train_conv2d_unit(x, w, g=None, want=(True, True, True)):
+    """x [B, H, W, Cin] channels-last (4 channels for Cin = 3), w [Cout, Cin, 3, 3], g [B, H, W, Cout] -> (y, dx, dw), None where unwanted."""
+    _require_gpu(x, w, g)
+    B, H, W, _ = x.shape
+    cout, cin = w.shape[:2]
+    with torch.cuda.device(x.device):
+        ws = _gbt_ws(B, B * H * W, max(cout, cin, 16), x.device)
+        y = torch.empty(B, H, W, cout, dtype=torch.float32, device=x.device) if want[0] else None
+        dx = torch.empty(B, H, W, cin, dtype=torch.float32, device=x.device) if want[1] and g is not None else None
+        dw = torch.empty_like(w) if want[2] and g is not None else None
+        _call("i2v_gblock_train_conv2d_unit", x.data_ptr(), w.data_ptr(), _opt(g), B, H, W, cin, cout, _opt(y), _opt(dx), _opt(dw), ws.data_ptr(),
+              ws.numel(), _stream())
+    return y, dx, dw

@@ -12,8 +12,38 @@ from i2v_params import ConvParams, LinearParams, NativeBacked
 from stage1_VAE.modules.normalization_layer import ADAIN, Norm3D, Spade
 
 
+class _GBlockTrainFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, module, x, cond1, cond2, *params):
+        out, saved = module._train_handle().forward(x, cond1, cond2, train=module.training, save=True)
+        ctx.module, ctx.saved, ctx.z, ctx.shape, ctx.img_shape = module, saved, cond1, tuple(x.shape), tuple(cond2.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        if torch.is_grad_enabled():   # create_graph=True: a graph through this backward is asked for
+            raise NotImplementedError("GeneratorBlock is once differentiable: the double backward (create_graph=True) is not built")
+        module = ctx.module
+        want = ctx.needs_input_grad[4:]
+        grads = native.flat_param_grads(module, ctx.saved.device) if any(want) else None
+        h = module._train_handle(grads)
+        need_dx, need_dz = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        dx, dz = h.backward(g_out.contiguous().float(), ctx.z, ctx.saved, ctx.shape, ctx.img_shape, need_dx=need_dx or (grads is None and not need_dz),
+                            need_dz=need_dz, param_grads=grads is not None, accumulate=False)
+        out = [None] * len(want) if grads is None else [g if w else None for g, w in zip(grads.values(), want)]
+        return (None, dx if need_dx else None, dz, None, *out)
+
+
 class GeneratorBlock(NativeBacked):
-    """out = shortcut(x) + conv_1(lrelu(ADAIN(conv_0(lrelu(Spade(x, img))), z)))   (reference decoder.py:7-52)."""
+    """out = shortcut(x) + conv_1(lrelu(ADAIN(conv_0(lrelu(Spade(x, img))), z)))   (reference decoder.py:7-52).
+
+    ``differentiable`` (a plain attribute, default False; not a reference argument): while it is False every call runs the packed inference
+    handle (csrc/i2v_gblock.hip), in grad mode too.  With ``differentiable = True`` every forward runs on the training handle
+    (csrc/i2v_gblock_train.hip, exact fp32), which reads the parameters in place and, in ``.train()`` mode, iterates ``weight_u`` /
+    ``weight_v`` in place as torch's spectral norm does; in grad mode it returns a tensor with a ``grad_fn`` from a Function whose inputs
+    are ``x``, ``cond1`` and the parameters.  A frozen module skips the weight-gradient launches; ``create_graph=True`` raises, and so does
+    a ``cond2`` that requires grad (no gradient is formed at the start frame).  Setting it back to False rebuilds the packed handle from
+    the current parameters."""
 
     def __init__(self, n_in, n_out, use_spectral, z_dim, mma=None):
         super().__init__()
@@ -29,14 +59,62 @@ class GeneratorBlock(NativeBacked):
         self.norm_1 = ADAIN(n_middle, z_dim)
         if self.learned_shortcut:
             self.norm_s = Norm3D(n_in)
+        object.__setattr__(self, "_train_native", None)
+        object.__setattr__(self, "_differentiable", False)
+
+    @property
+    def differentiable(self):
+        return self.__dict__.get("_differentiable", False)
+
+    @differentiable.setter
+    def differentiable(self, value):
+        value = bool(value)
+        if not value and self.differentiable:
+            self.refresh_native()
+        object.__setattr__(self, "_differentiable", value)
+
+    def _drop_native(self):
+        super()._drop_native()
+        object.__setattr__(self, "_train_native", None)
+
+    def __getstate__(self):
+        state = dict(super().__getstate__() if hasattr(super(), "__getstate__") else self.__dict__)
+        state["_native"] = state["_train_native"] = None
+        return state
 
     def _build_native(self):
         h = native.NativeGBlock(self.n_in, self.n_out, self.z_dim, self.use_spectral, mma=self.mma, device=self.module_device())
         h.load(self.state_dict())
         return h
 
+    def _train_handle(self, grads=None):
+        """The training handle, bound to the storage of the parameters and spectral-norm buffers as it is now and, when ``grads``
+        ({parameter name: tensor}) is given, to those gradient tensors."""
+        tensors = {k: t for k, t in list(self.named_parameters()) + list(self.named_buffers()) if t.dtype == torch.float32}
+        for t in tensors.values():
+            if not t.is_cuda:
+                raise native.I2VError("GeneratorBlock runs on a HIP device only: move the module to 'cuda' (this package has no CPU fallback)")
+        h = self.__dict__.get("_train_native")
+        dev = next(iter(tensors.values())).device
+        if h is None or h.device != dev:
+            h = native.NativeGBlockTrain(self.n_in, self.n_out, self.z_dim, self.use_spectral, device=dev)
+            object.__setattr__(self, "_train_native", h)
+        return native.bind_in_place(h, tensors, grads)
+
     def forward(self, x, cond1, cond2):
-        return self.native().forward(x.contiguous(), cond1.contiguous(), cond2.contiguous())
+        if not self.differentiable:
+            return self.native().forward(x.contiguous(), cond1.contiguous(), cond2.contiguous())
+        if not (x.is_cuda and cond1.is_cuda and cond2.is_cuda):
+            raise native.I2VError("GeneratorBlock got a CPU tensor: its kernels run on a HIP device only (this package has no CPU fallback)")
+        params = list(self.parameters())
+        if torch.is_grad_enabled():
+            if cond2.requires_grad:
+                raise NotImplementedError("GeneratorBlock forms no gradient at the start frame (cond2): the reference never asks for one")
+            if x.requires_grad or cond1.requires_grad or any(p.requires_grad for p in params):
+                return _GBlockTrainFunction.apply(self, x.float().contiguous(), cond1.float().contiguous(), cond2.detach().float().contiguous(), *params)
+        with torch.no_grad():
+            return self._train_handle().forward(x.detach().float().contiguous(), cond1.detach().float().contiguous(),
+                                                cond2.detach().float().contiguous(), train=self.training)[0]
 
 
 class Generator(NativeBacked):
