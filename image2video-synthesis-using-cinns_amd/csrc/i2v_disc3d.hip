@@ -2,10 +2,11 @@
 // spectral norm in training mode on block 0 of every layer, GroupNorm(16), the max pool, the head, the feature-map loss (loss.py:14-21).
 // The C ABI is include/i2v_hip_disc3d.h.  Conventions of i2v_patchdisc.hip: exact fp32 on v_mfma_f32_16x16x4_f32; every sum has one owner
 // and a fixed order, so two runs give the same bits.
-// The trunk's kernels (conv, dgrad, wgrad, finish, GroupNorm: __builtin_amdgcn_mfma_f32_16x16x4f32; the pool), their launchers and plan
-// helpers are in i2v_res3d_trunk.h; the plan of the convs and blocks, the binding, the layout of `saved` and of the workspace, the
-// spectral-norm bookkeeping and the forward and backward walks are in i2v_res3d_net.h.  Both are shared with the motion encoder's
-// training path (i2v_encoder_train.hip).  Here: the head, the feature-map loss, the unit entries and the C entries.
+// The trunk's conv, dgrad, wgrad, finish and pack kernels (__builtin_amdgcn_mfma_f32_16x16x4f32), their launchers and plan helpers are the
+// Trunk3d family of i2v_train_conv.h, shared with the patch discriminator; GroupNorm and the pool are in i2v_res3d_trunk.h; the plan of
+// the convs and blocks, the binding, the layout of `saved` and of the workspace, the spectral-norm bookkeeping and the forward and
+// backward walks are in i2v_res3d_net.h.  The last two are shared with the motion encoder's training path (i2v_encoder_train.hip).
+// Here: the head, the feature-map loss, the unit entries and the C entries.
 //   * Activations are channels-last [N][T][H][W][C]; the clip is stored with 4 channels (r, g, b, 0).
 //   * A forward packs W (/ sigma where the conv is spectral-normed) of every conv once, on the device, into wf [tap][cout][cin] and
 //     wd [tap][cin][cout].  With I2V_DISC3D_SAVE they live in `saved` with that call's u, v and sigma.
@@ -14,9 +15,9 @@
 //   * dgrad: the same GEMM as a gather over input positions.  Along an axis of stride 2 a coordinate receives the taps of its parity
 //     (window 3: one tap for an even coordinate, two for an odd one; window 7: three and four), so the positions are processed in
 //     stride_t x stride_s x stride_s parity classes (blockIdx.y), each with its own tap list: no structural zero is multiplied.
-//   * wgrad: per tap a [cout] x [cin] GEMM over the positions, cut into slices by d3_wgrad_plan; the four waves of a workgroup take a
-//     quarter of a slice each and are summed in wave order; d3_finish_a adds the slices in slice order, d3_finish_dot forms <dWn, W> once,
-//     d3_finish_b applies the projection.
+//   * wgrad: per tap a [cout] x [cin] GEMM over the positions, cut into slices by wgrad_plan; the four waves of a workgroup take a
+//     quarter of a slice each and are summed in wave order; tc_finish_a adds the slices in slice order, tc_finish_dot forms <dWn, W> once,
+//     tc_finish_b applies the projection.
 //   * GroupNorm: float64 statistics per (sample, group) from slices added in slice order; one apply pass; the backward's per-channel sums
 //     likewise, then the two per-(sample, group) sums, then dx.
 #include "i2v_handle.h"
@@ -133,8 +134,8 @@ int check_unit(const char* what, int n, int ti, int hi, int wi, int cin, int cou
 // workspace of the unit entries
 struct D3UnitWs { size_t wf, wd, part, dwn, dotp, total; };
 D3UnitWs unit_ws(int n, int ti, int hi, int wi, int cin, int cout, int stem) {
-    const D3Conv c = make_conv(cin, cout, stem, 1, 1, 0);
-    const D3Geo m = make_geo(n, ti, hi, wi, c);   // stride 1 has the most positions
+    const TcConv c = make_conv(cin, cout, stem, 1, 1, 0);
+    const TcGeo m = make_geo(n, ti, hi, wi, c);   // stride 1 has the most positions
     Carver k;
     D3UnitWs y{};
     y.wf = k.take_floats((size_t)ntap_of(c) * cout * c.cinp);
@@ -146,13 +147,11 @@ D3UnitWs unit_ws(int n, int ti, int hi, int wi, int cin, int cout, int stem) {
     return y;
 }
 
-int pack_unit(const D3Conv& c, const float* weight, float* wf, float* wd, hipStream_t st) {
-    D3PackArgs p{};
+int pack_unit(const TcConv& c, const float* weight, float* wf, float* wd, hipStream_t st) {
+    TcPackArgs p{};
     p.nconv = 1; p.total = (long)pack_elems(c);
-    p.c[0] = D3PackConv{weight, nullptr, wf, wd, c.cout, c.cin, c.cinp, c.cind, ntap_of(c), 0};
-    hipLaunchKernelGGL(d3_pack_kernel, dim3(grid_for(p.total)), dim3(256), 0, st, p);
-    PD_LAUNCHED();
-    return I2V_OK;
+    p.c[0] = TcPackConv{weight, nullptr, wf, wd, c.cout, c.cin, c.cinp, c.cind, ntap_of(c), 0};
+    return launch_pack<Trunk3d>(p, st);
 }
 
 }  // namespace
@@ -246,7 +245,7 @@ int i2v_disc3d_forward(i2v_disc3d* d, const float* x, int32_t n, int32_t t, int3
     if (int rc = r3_forward(d->trunk, y, x, flags & I2V_DISC3D_ITERATE, fmaps, sv, workspace, st)) return rc;
     const int last = d->trunk.last();
     hipLaunchKernelGGL(d3_head_fwd_kernel, dim3(n), dim3(256), 0, st, Carver::at(sv, y.act[last]), d->fc, pred, d->trunk.L[last].cout);
-    PD_LAUNCHED();
+    I2V_LAUNCHED();
     return I2V_OK;
 }
 
@@ -275,7 +274,7 @@ int i2v_disc3d_backward(i2v_disc3d* d, const float* d_pred, const float* const* 
     if (d_pred) {
         hipLaunchKernelGGL(d3_head_bwd_kernel, dim3((C + 255) / 256), dim3(256), 0, st, Carver::at(sv, y.act[last]), d->fc, d_pred, G,
                            pg ? d->gfc : nullptr, n, C, acc ? 1 : 0);
-        PD_LAUNCHED();
+        I2V_LAUNCHED();
     } else {
         I2V_HIP_CHECK(hipMemsetAsync(G, 0, (size_t)n * 16 * C * 4, st));
         if (pg && !acc) I2V_HIP_CHECK(hipMemsetAsync(d->gfc, 0, (size_t)C * 4, st));
@@ -301,24 +300,24 @@ int i2v_disc3d_fmap_loss(const float* const* a, const float* const* b, const int
         const float coef = (float)((double)grad_scale / ((double)numel[l] * n_layers));
         hipLaunchKernelGGL(d3_fmap_partial_kernel, dim3(f.nblk[l]), dim3(256), 0, st, a[l], b[l], (long)numel[l], metric, coef, d_a ? d_a[l] : nullptr,
                            Carver::at<double>(workspace, 0) + l * D3_FMAP_BLOCKS);
-        PD_LAUNCHED();
+        I2V_LAUNCHED();
     }
     hipLaunchKernelGGL(d3_fmap_final_kernel, dim3(1), dim3(64), 0, st, f, Carver::at<double>(workspace, 0), out);
-    PD_LAUNCHED();
+    I2V_LAUNCHED();
     return I2V_OK;
 }
 
 int i2v_disc3d_sumsq(const float* x, int32_t n, int64_t per, double* out, void* stream) {
     I2V_REQUIRE(x && out && n > 0 && per > 0, I2V_E_INVALID, "i2v_disc3d_sumsq: null argument, %d rows of %lld", n, (long long)per);
     hipLaunchKernelGGL(d3_sumsq_kernel, dim3(n), dim3(256), 0, static_cast<hipStream_t>(stream), x, (long)per, out);
-    PD_LAUNCHED();
+    I2V_LAUNCHED();
     return I2V_OK;
 }
 
 int i2v_disc3d_wgrad_plan(int32_t cout, int32_t cin, int32_t taps, int64_t positions, int32_t* slices, int32_t* slice_len) {
     I2V_REQUIRE(slices && slice_len && positions > 0 && cout > 0 && cout % 16 == 0 && (cin == 3 || (cin > 0 && cin % 16 == 0)) && (taps == 27 || taps == 147),
                 I2V_E_INVALID, "i2v_disc3d_wgrad_plan: cout %d, cin %d, %d taps, %lld positions", cout, cin, taps, (long long)positions);
-    d3_wgrad_plan(cout, cin, taps, positions, slices, slice_len);
+    wgrad_plan(cout, cin, taps, positions, slices, slice_len);
     return I2V_OK;
 }
 
@@ -335,9 +334,9 @@ int i2v_disc3d_conv_unit(const float* x, const float* weight, int32_t n, int32_t
     const D3UnitWs k = unit_ws(n, ti, hi, wi, cin, cout, stem);
     I2V_REQUIRE_WORKSPACE(workspace_bytes, k.total, what);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const D3Conv c = make_conv(cin, cout, stem, stride_t, stride_s, 0);
+    const TcConv c = make_conv(cin, cout, stem, stride_t, stride_s, 0);
     if (int rc = pack_unit(c, weight, Carver::at(workspace, k.wf), Carver::at(workspace, k.wd), st)) return rc;
-    return launch_conv(c, x, Carver::at(workspace, k.wf), out, make_geo(n, ti, hi, wi, c), st);
+    return launch_conv<Trunk3d>(c, x, Carver::at(workspace, k.wf), out, make_geo(n, ti, hi, wi, c), st);
 }
 
 int i2v_disc3d_dgrad_unit(const float* g, const float* weight, const float* act, const float* add, const float* add_mask, int32_t n, int32_t ti, int32_t hi,
@@ -350,9 +349,9 @@ int i2v_disc3d_dgrad_unit(const float* g, const float* weight, const float* act,
     const D3UnitWs k = unit_ws(n, ti, hi, wi, cin, cout, stem);
     I2V_REQUIRE_WORKSPACE(workspace_bytes, k.total, what);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const D3Conv c = make_conv(cin, cout, stem, stride_t, stride_s, 0);
+    const TcConv c = make_conv(cin, cout, stem, stride_t, stride_s, 0);
     if (int rc = pack_unit(c, weight, Carver::at(workspace, k.wf), Carver::at(workspace, k.wd), st)) return rc;
-    return launch_dgrad(c, g, act, Carver::at(workspace, k.wd), add, add_mask, out, frames_out != 0, n, make_geo(n, ti, hi, wi, c), st);
+    return launch_dgrad<Trunk3d>(c, g, act, nullptr, Carver::at(workspace, k.wd), add, add_mask, out, frames_out != 0, n, make_geo(n, ti, hi, wi, c), st);
 }
 
 int i2v_disc3d_wgrad_unit(const float* g, const float* act, const float* x, const float* weight, const float* u, const float* v, const float* sigma,
@@ -363,8 +362,8 @@ int i2v_disc3d_wgrad_unit(const float* g, const float* act, const float* x, cons
     I2V_REQUIRE(g && x && weight && dweight && workspace && !u == !v && !u == !sigma, I2V_E_INVALID, "%s: null argument", what);
     const D3UnitWs k = unit_ws(n, ti, hi, wi, cin, cout, stem);
     I2V_REQUIRE_WORKSPACE(workspace_bytes, k.total, what);
-    const D3Conv c = make_conv(cin, cout, stem, stride_t, stride_s, 0);
-    return launch_wgrad(c, g, act, x, weight, u, v, sigma, Carver::at(workspace, k.part), Carver::at(workspace, k.dwn),
+    const TcConv c = make_conv(cin, cout, stem, stride_t, stride_s, 0);
+    return launch_wgrad<Trunk3d>(c, g, act, nullptr, x, weight, u, v, sigma, Carver::at(workspace, k.part), Carver::at(workspace, k.dwn),
                         Carver::at<double>(workspace, k.dotp), dweight, accumulate != 0, make_geo(n, ti, hi, wi, c), static_cast<hipStream_t>(stream));
 }
 
@@ -394,7 +393,7 @@ int i2v_disc3d_maxpool_unit(const float* x, int32_t n, int32_t t, int32_t h, int
     const int ho = (h - 1) / 2 + 1, wo = (w - 1) / 2 + 1;
     const long total = (long)n * t * ho * wo * c;
     hipLaunchKernelGGL(d3_maxpool_kernel, dim3(grid_for(total)), dim3(256), 0, static_cast<hipStream_t>(stream), x, out, argmax, total, t, h, w, ho, wo, c);
-    PD_LAUNCHED();
+    I2V_LAUNCHED();
     return I2V_OK;
 }
 
@@ -403,7 +402,7 @@ int i2v_disc3d_maxpool_backward_unit(const float* g, const int32_t* argmax, int3
     const int ho = (h - 1) / 2 + 1, wo = (w - 1) / 2 + 1;
     const long total = (long)n * t * h * w * c;
     hipLaunchKernelGGL(d3_maxpool_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, static_cast<hipStream_t>(stream), g, argmax, dx, total, t, h, w, ho, wo, c);
-    PD_LAUNCHED();
+    I2V_LAUNCHED();
     return I2V_OK;
 }
 
@@ -411,10 +410,10 @@ int i2v_disc3d_head_unit(const float* x, const float* weight, const float* g, in
     I2V_REQUIRE(x && weight && pred && n > 0 && c > 0 && (g ? dx != nullptr : !dx && !dweight), I2V_E_INVALID, "i2v_disc3d_head_unit: null argument");
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(d3_head_fwd_kernel, dim3(n), dim3(256), 0, st, x, weight, pred, c);
-    PD_LAUNCHED();
+    I2V_LAUNCHED();
     if (!g) return I2V_OK;
     hipLaunchKernelGGL(d3_head_bwd_kernel, dim3((c + 255) / 256), dim3(256), 0, st, x, weight, g, dx, dweight, n, c, 0);
-    PD_LAUNCHED();
+    I2V_LAUNCHED();
     return I2V_OK;
 }
 

@@ -206,15 +206,15 @@ int launch_head_fwd(E3HeadArgs a, void* ws, hipStream_t st) {
     const E3HeadWs k = head_ws(a.n, a.C, a.z);
     a.part = Carver::at(ws, k.part); a.NR = k.NR; a.NC = k.NC;
     hipLaunchKernelGGL(e3_head_fwd_kernel, dim3(a.C / 16, k.NC / 16, k.NR / 16), dim3(256), 0, st, a);
-    PD_LAUNCHED();
+    I2V_LAUNCHED();
     hipLaunchKernelGGL(e3_head_finish_kernel, dim3(grid_for((long)a.n * a.z)), dim3(256), 0, st, a);
-    PD_LAUNCHED();
+    I2V_LAUNCHED();
     return I2V_OK;
 }
 
 int launch_fold(const E3FoldArgs& f, hipStream_t st) {
     hipLaunchKernelGGL(e3_fold_kernel, dim3(grid_for((long)f.n * f.z)), dim3(256), 0, st, f);
-    PD_LAUNCHED();
+    I2V_LAUNCHED();
     return I2V_OK;
 }
 
@@ -226,12 +226,12 @@ int launch_head_bwd(E3HeadArgs a, E3FoldArgs f, void* ws, hipStream_t st) {
     if (int rc = launch_fold(f, st)) return rc;
     a.g = g;
     hipLaunchKernelGGL(e3_head_dgrad_kernel, dim3(a.C / 4, k.NR / 16), dim3(256), 0, st, a);
-    PD_LAUNCHED();
+    I2V_LAUNCHED();
     if (!a.dw_mu) return I2V_OK;
     hipLaunchKernelGGL(e3_head_wgrad_kernel, dim3(grid_for(2L * a.z * a.C * 16)), dim3(256), 0, st, a);
-    PD_LAUNCHED();
+    I2V_LAUNCHED();
     hipLaunchKernelGGL(e3_head_bias_kernel, dim3((2 * a.z + 255) / 256), dim3(256), 0, st, a);
-    PD_LAUNCHED();
+    I2V_LAUNCHED();
     return I2V_OK;
 }
 

@@ -450,13 +450,13 @@ int slices_of(long rows) { return (int)std::min<long>(std::max<long>(rows / 64, 
 int launch_transpose(const float* in, float* out, int B, int R, long S, hipStream_t st) {
     I2V_REQUIRE(B <= 65535 && (R + 31) / 32 <= 65535, I2V_E_INVALID, "generator block: transpose grid (%d, %d)", B, (R + 31) / 32);
     hipLaunchKernelGGL(gt_transpose_kernel, dim3((unsigned)((S + 31) / 32), (R + 31) / 32, B), dim3(256), 0, st, in, out, R, (int)S);
-    PD_LAUNCHED();
+    I2V_LAUNCHED();
     return I2V_OK;
 }
 
 int launch_bias_act(float* y, const float* bias, long rows, int C, bool act, hipStream_t st) {
     hipLaunchKernelGGL(gt_bias_act_kernel, dim3(grid_for(rows * C / 4)), dim3(256), 0, st, y, bias, rows * C / 4, C, act ? 1 : 0);
-    PD_LAUNCHED();
+    I2V_LAUNCHED();
     return I2V_OK;
 }
 
@@ -467,9 +467,9 @@ int launch_gn_stats(const float* x, int N, long P, int C, double* stats, void* w
     a.x = x; a.stats = stats; a.partial = Carver::at<double>(ws, k.partial);
     a.P = P; a.N = N; a.C = C; a.cpg = C / D3_GROUPS; a.R = gn_slices(P, a.cpg); a.rows_per = (P + a.R - 1) / a.R;
     hipLaunchKernelGGL(d3_gn_stats_kernel, dim3(D3_GROUPS, N, a.R), dim3(256), 0, st, a);
-    PD_LAUNCHED();
+    I2V_LAUNCHED();
     hipLaunchKernelGGL(d3_gn_stats_final_kernel, dim3((N * D3_GROUPS + 255) / 256), dim3(256), 0, st, a);
-    PD_LAUNCHED();
+    I2V_LAUNCHED();
     return I2V_OK;
 }
 
@@ -492,9 +492,9 @@ int launch_in_stats(const float* x, int B, long P, int C, double* stats, void* w
     a.x = x; a.partial = Carver::at<double>(ws, k.partial); a.stats = stats;
     a.P = P; a.B = B; a.C = C; a.R = slices_of(P); a.rows_per = (P + a.R - 1) / a.R;
     hipLaunchKernelGGL(gt_in_stats_partial_kernel, dim3(C / 16, B, a.R), dim3(256), 0, st, a);
-    PD_LAUNCHED();
+    I2V_LAUNCHED();
     hipLaunchKernelGGL(gt_in_stats_final_kernel, dim3((B * C + 255) / 256), dim3(256), 0, st, a);
-    PD_LAUNCHED();
+    I2V_LAUNCHED();
     return I2V_OK;
 }
 
@@ -504,7 +504,7 @@ int launch_modulate(const float* x, const double* stats, const float* gamma, con
     a.x = x; a.gamma = gamma; a.beta = beta; a.lin = lin; a.stats = stats; a.out = out;
     a.P = P; a.HW = HW; a.B = B; a.C = C; a.adain = adain ? 1 : 0; a.G = adain ? C : D3_GROUPS; a.cpg = C / a.G;
     hipLaunchKernelGGL(gt_modulate_kernel, dim3(grid_for((long)B * P * C / 4)), dim3(256), 0, st, a);
-    PD_LAUNCHED();
+    I2V_LAUNCHED();
     return I2V_OK;
 }
 
@@ -520,12 +520,12 @@ int launch_modnorm_bwd(bool adain, const float* g, const float* act, const float
     const long rows = adain ? a.P : HW;
     a.R = slices_of(rows); a.rows_per = (rows + a.R - 1) / a.R;
     hipLaunchKernelGGL(gt_nb_partial_kernel, dim3(C / 16, B, a.R), dim3(256), 0, st, a);
-    PD_LAUNCHED();
+    I2V_LAUNCHED();
     hipLaunchKernelGGL(gt_nb_reduce_kernel, dim3(B), dim3(256), 0, st, a);
-    PD_LAUNCHED();
+    I2V_LAUNCHED();
     if (dx) {
         hipLaunchKernelGGL(gt_nb_apply_kernel, dim3(grid_for((long)B * a.P * C / 4)), dim3(256), 0, st, a);
-        PD_LAUNCHED();
+        I2V_LAUNCHED();
     }
     return I2V_OK;
 }
@@ -539,7 +539,7 @@ int launch_gemm(const float* A, const float* Bt, const float* add, long M, int K
     if (BN == 64) hipLaunchKernelGGL((gt_gemm_kernel<4>), grid, dim3(256), 0, st, a);
     else if (BN == 32) hipLaunchKernelGGL((gt_gemm_kernel<2>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((gt_gemm_kernel<1>), grid, dim3(256), 0, st, a);
-    PD_LAUNCHED();
+    I2V_LAUNCHED();
     return I2V_OK;
 }
 
@@ -564,29 +564,17 @@ int launch_wgrad1(const float* g, const float* x, const float* w, const float* u
     I2V_REQUIRE(S <= 65535, I2V_E_INVALID, "generator block: %d weight-gradient slices", S);
     GtWg1Args a{g, x, part, P, cout, cin, L};
     hipLaunchKernelGGL(gt_wgrad1_kernel, dim3((unsigned)((cout / 16) * (cin / 16)), (unsigned)S), dim3(256), 0, st, a);
-    PD_LAUNCHED();
-    D3FinishArgs f{};
-    f.part = part; f.w = w; f.u = u; f.v = v; f.sigma = sigma; f.dwn = dwn; f.dotp = dotp; f.grad = grad;
-    f.E = (long)cout * cin; f.S = S; f.cout = cout; f.cin = cin; f.CP = cin; f.ntap = 1; f.nblk = (int)((f.E + 255) / 256);
-    f.accumulate = accumulate ? 1 : 0;
-    hipLaunchKernelGGL(d3_finish_a_kernel, dim3(f.nblk), dim3(256), 0, st, f);
-    PD_LAUNCHED();
-    if (sigma) {
-        hipLaunchKernelGGL(d3_finish_dot_kernel, dim3(1), dim3(256), 0, st, f);
-        PD_LAUNCHED();
-    }
-    hipLaunchKernelGGL(d3_finish_b_kernel, dim3(f.nblk), dim3(256), 0, st, f);
-    PD_LAUNCHED();
-    return I2V_OK;
+    I2V_LAUNCHED();
+    return launch_finish(part, S, cin, cout, cin, 1, w, u, v, sigma, dwn, dotp, grad, accumulate, st);
 }
 
 int launch_bias_grad(const float* g, long M, int C, float* db, bool accumulate, double* partial, hipStream_t st) {
     GtBgArgs a{};
     a.g = g; a.partial = partial; a.db = db; a.M = M; a.C = C; a.R = slices_of(M); a.rows_per = (M + a.R - 1) / a.R; a.accumulate = accumulate ? 1 : 0;
     hipLaunchKernelGGL(gt_bias_partial_kernel, dim3(C / 16, a.R), dim3(256), 0, st, a);
-    PD_LAUNCHED();
+    I2V_LAUNCHED();
     hipLaunchKernelGGL(gt_bias_final_kernel, dim3((C + 255) / 256), dim3(256), 0, st, a);
-    PD_LAUNCHED();
+    I2V_LAUNCHED();
     return I2V_OK;
 }
 
@@ -594,13 +582,13 @@ int launch_linear_bwd(const float* d_lin, const float* z, const float* w, int B,
                       hipStream_t st) {
     const long total = (long)J * K + J + (long)B * K;
     hipLaunchKernelGGL(gt_linear_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, d_lin, z, w, dw, db, dz, B, J, K, accumulate ? 1 : 0);
-    PD_LAUNCHED();
+    I2V_LAUNCHED();
     return I2V_OK;
 }
 
 // a 3x3 2-D conv as the trunk's conv: window (3, 1, 3) over [T' = H][H' = 1][W' = W]
-D3Conv conv2d_of(int cin, int cout) { return D3Conv{cin, cin == 3 ? 4 : cin, cin == 3 ? 16 : cin, cout, 1, 3, 1, 1, 0}; }
-D3Conv conv3d_of(int cin, int cout, int sn) { return D3Conv{cin, cin, cin, cout, 3, 3, 1, 1, sn}; }
+TcConv conv2d_of(int cin, int cout) { return TcConv{cin, cin == 3 ? 4 : cin, cin == 3 ? 16 : cin, cout, 3, 1, 3, 1, 1, 0}; }
+TcConv conv3d_of(int cin, int cout, int sn) { return TcConv{cin, cin, cin, cout, 3, 3, 3, 1, 1, sn}; }
 
 bool bound_ptr_(const StateDict& s, const std::string& key, int64_t numel, float** out) {
     const float* p = s.f32(key, numel);
@@ -621,7 +609,7 @@ struct i2v_gblock_train {
     bool loaded = false, have_grads = false;
     int n_in = 0, n_out = 0, n_mid = 0, z_dim = 0;
     bool sn = false, learned = false;
-    D3Conv L[GC_N];   // GC_S: the 1x1x1 conv, described with one tap (cout, cin, sn only)
+    TcConv L[GC_N];   // GC_S: the 1x1x1 conv, described with one tap (cout, cin, sn only)
     float *w[GC_N] = {}, *b[GC_N] = {}, *u[GC_N] = {}, *v[GC_N] = {}, *nsw = nullptr, *nsb = nullptr, *lw = nullptr, *lb = nullptr;
     float *gw[GC_N] = {}, *gb[GC_N] = {}, *gnsw = nullptr, *gnsb = nullptr, *glw = nullptr, *glb = nullptr;
 };
@@ -637,7 +625,7 @@ struct GtLayout {
     bool ok = false;
     int B = 0, T = 0, H = 0, W = 0, ih = 0, iw = 0;
     long P = 0, HW = 0;
-    D3Geo geo[GC_N];
+    TcGeo geo[GC_N];
     // saved
     size_t x_cl = 0, img4 = 0, y1 = 0, gamma = 0, beta = 0, a0 = 0, y0 = 0, lin = 0, a1 = 0, xn = 0, stats0 = 0, stats1 = 0, stats_s = 0;
     size_t wf[GC_N] = {}, wd[GC_N] = {}, sigma[GC_N] = {}, us[GC_N] = {}, vs[GC_N] = {}, saved_total = 0;
@@ -673,7 +661,7 @@ GtLayout gt_layout(const i2v_gblock_train* g, int B, int T, int H, int W, int ih
     size_t pmax = 0, emax = 0;
     for (int i = 0; i < GC_N; ++i) {
         if (!has_gc(g, i)) continue;
-        const D3Conv& c = g->L[i];
+        const TcConv& c = g->L[i];
         const int ntap = ntap_gc(g, i);
         y.wf[i] = s.take_floats((size_t)ntap * c.cout * c.cinp);
         y.wd[i] = s.take_floats(i == GC_SP ? 0 : (size_t)ntap * c.cind * c.cout);
@@ -707,7 +695,7 @@ bool bind_keys(const i2v_gblock_train* g, const StateDict& sd, bool grads, float
                float** lw, float** lb) {
     for (int i = 0; i < GC_N; ++i) {
         if (!has_gc(g, i)) continue;
-        const D3Conv& c = g->L[i];
+        const TcConv& c = g->L[i];
         const std::string key = GC_KEY[i];
         const int64_t wn = (int64_t)c.cout * c.cin * ntap_gc(g, i);
         if (!bound_ptr_(sd, key + (c.sn ? ".weight_orig" : ".weight"), wn, &w[i])) return false;
@@ -728,10 +716,10 @@ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 
 int gt_prepare_weights(const i2v_gblock_train* g, const GtLayout& y, bool iterate, void* sv, void* ws, hipStream_t st) {
     PdPiArgs pi{};
     pi.iterate = iterate ? 1 : 0;
-    D3PackArgs pk{};
+    TcPackArgs pk{};
     for (int i = 0; i < GC_N; ++i) {
         if (!has_gc(g, i)) continue;
-        const D3Conv& c = g->L[i];
+        const TcConv& c = g->L[i];
         const int ntap = ntap_gc(g, i);
         if (c.sn) {
             const int cols = c.cin * ntap;
@@ -739,15 +727,13 @@ int gt_prepare_weights(const i2v_gblock_train* g, const GtLayout& y, bool iterat
                                         Carver::at<double>(ws, y.pi_t[i]), Carver::at<double>(ws, y.pi_s[i]), c.cout, cols, pi.btotal, pi.rtotal};
             pi.btotal += (cols + 63) / 64; pi.rtotal += c.cout;
         }
-        pk.c[pk.nconv++] = D3PackConv{g->w[i], c.sn ? Carver::at(sv, y.sigma[i]) : nullptr, Carver::at(sv, y.wf[i]),
+        pk.c[pk.nconv++] = TcPackConv{g->w[i], c.sn ? Carver::at(sv, y.sigma[i]) : nullptr, Carver::at(sv, y.wf[i]),
                                       i == GC_SP ? nullptr : Carver::at(sv, y.wd[i]), c.cout, c.cin, c.cinp, c.cind, ntap, pk.total};
         pk.total += (long)c.cout * c.cind * ntap;
     }
     if (pi.nconv > 0)
         if (int rc = launch_power_iteration(pi, st)) return rc;
-    hipLaunchKernelGGL(d3_pack_kernel, dim3(grid_for(pk.total)), dim3(256), 0, st, pk);
-    PD_LAUNCHED();
-    return I2V_OK;
+    return launch_pack<Trunk3d>(pk, st);
 }
 
 }  // namespace
@@ -768,7 +754,7 @@ int i2v_gblock_train_create(int32_t n_in, int32_t n_out, int32_t z_dim, int32_t 
         g->L[GC_SP] = conv2d_of(3, 128);
         g->L[GC_G] = conv2d_of(128, n_in);
         g->L[GC_B] = conv2d_of(128, n_in);
-        g->L[GC_S] = D3Conv{n_in, n_in, n_in, n_out, 1, 1, 1, 1, g->sn};
+        g->L[GC_S] = TcConv{n_in, n_in, n_in, n_out, 1, 1, 1, 1, 1, g->sn};
         return I2V_OK;
     });
 }
@@ -834,24 +820,24 @@ int i2v_gblock_train_forward(i2v_gblock_train* g, const float* x, const float* z
     if ((rc = gt_prepare_weights(g, y, flags & I2V_GBLOCK_TRAIN_TRAIN, sv, ws, st))) return rc;
     // Spade's branch on the resized start frame
     hipLaunchKernelGGL(gt_resize_kernel, dim3(grid_for(BHW)), dim3(256), 0, st, img, img4, BHW, img_h, img_w, h, w);
-    PD_LAUNCHED();
-    if ((rc = launch_conv(g->L[GC_SP], img4, Carver::at(sv, y.wf[GC_SP]), y1, y.geo[GC_SP], st))) return rc;
+    I2V_LAUNCHED();
+    if ((rc = launch_conv<Trunk3d>(g->L[GC_SP], img4, Carver::at(sv, y.wf[GC_SP]), y1, y.geo[GC_SP], st))) return rc;
     if ((rc = launch_bias_act(y1, g->b[GC_SP], BHW, 128, true, st))) return rc;
-    if ((rc = launch_conv(g->L[GC_G], y1, Carver::at(sv, y.wf[GC_G]), gamma, y.geo[GC_G], st))) return rc;
+    if ((rc = launch_conv<Trunk3d>(g->L[GC_G], y1, Carver::at(sv, y.wf[GC_G]), gamma, y.geo[GC_G], st))) return rc;
     if ((rc = launch_bias_act(gamma, g->b[GC_G], BHW, Cin, false, st))) return rc;
-    if ((rc = launch_conv(g->L[GC_B], y1, Carver::at(sv, y.wf[GC_B]), beta, y.geo[GC_B], st))) return rc;
+    if ((rc = launch_conv<Trunk3d>(g->L[GC_B], y1, Carver::at(sv, y.wf[GC_B]), beta, y.geo[GC_B], st))) return rc;
     if ((rc = launch_bias_act(beta, g->b[GC_B], BHW, Cin, false, st))) return rc;
     // a0 = lrelu(Spade(x)), y0 = conv_0(a0)
     if ((rc = launch_gn_stats(x_cl, B, P, Cin, stats0, gnws, st))) return rc;
     if ((rc = launch_modulate(x_cl, stats0, gamma, beta, nullptr, B, P, HW, Cin, false, a0, st))) return rc;
-    if ((rc = launch_conv(g->L[GC_0], a0, Carver::at(sv, y.wf[GC_0]), y0, y.geo[GC_0], st))) return rc;
+    if ((rc = launch_conv<Trunk3d>(g->L[GC_0], a0, Carver::at(sv, y.wf[GC_0]), y0, y.geo[GC_0], st))) return rc;
     if ((rc = launch_bias_act(y0, g->b[GC_0], BP, Cm, false, st))) return rc;
     // a1 = lrelu(ADAIN(y0, z)), dx1 = conv_1(a1)
     if ((rc = launch_in_stats(y0, B, P, Cm, stats1, nws, st))) return rc;
     hipLaunchKernelGGL(gt_linear_fwd_kernel, dim3((B * 2 * Cm + 255) / 256), dim3(256), 0, st, z, g->lw, g->lb, lin, B, 2 * Cm, g->z_dim);
-    PD_LAUNCHED();
+    I2V_LAUNCHED();
     if ((rc = launch_modulate(y0, stats1, nullptr, nullptr, lin, B, P, HW, Cm, true, a1, st))) return rc;
-    if ((rc = launch_conv(g->L[GC_1], a1, Carver::at(sv, y.wf[GC_1]), dx1, y.geo[GC_1], st))) return rc;
+    if ((rc = launch_conv<Trunk3d>(g->L[GC_1], a1, Carver::at(sv, y.wf[GC_1]), dx1, y.geo[GC_1], st))) return rc;
     if ((rc = launch_bias_act(dx1, g->b[GC_1], BP, Co, false, st))) return rc;
     // the shortcut and the sum
     if (g->learned) {
@@ -860,7 +846,7 @@ int i2v_gblock_train_forward(i2v_gblock_train* g, const float* x, const float* z
         if ((rc = launch_gemm(xn, Carver::at(sv, y.wf[GC_S]), dx1, BP, Cin, Co, out_cl, st))) return rc;
     } else {
         hipLaunchKernelGGL(d3_add_kernel, dim3(grid_for(BP * Co)), dim3(256), 0, st, dx1, x_cl, BP * Co);
-        PD_LAUNCHED();
+        I2V_LAUNCHED();
         out_cl = dx1;
     }
     return launch_transpose(out_cl, out, B, (int)P, Co, st);
@@ -895,12 +881,12 @@ int i2v_gblock_train_backward(i2v_gblock_train* g, const float* g_out, const flo
     void* gnws = Carver::at<char>(ws, y.gn);
     double* bpart = Carver::at<double>(nws, 0);
     auto wgrad = [&](int i, const float* gy, const float* xin) -> int {
-        const D3Conv& c = g->L[i];
-        return launch_wgrad(c, gy, nullptr, xin, g->w[i], c.sn ? Carver::at(sv, y.us[i]) : nullptr, c.sn ? Carver::at(sv, y.vs[i]) : nullptr,
+        const TcConv& c = g->L[i];
+        return launch_wgrad<Trunk3d>(c, gy, nullptr, nullptr, xin, g->w[i], c.sn ? Carver::at(sv, y.us[i]) : nullptr, c.sn ? Carver::at(sv, y.vs[i]) : nullptr,
                             c.sn ? Carver::at(sv, y.sigma[i]) : nullptr, part, dwn, dotp, g->gw[i], acc, y.geo[i], st);
     };
     auto dgrad = [&](int i, const float* gy, const float* add, float* dst) -> int {
-        return launch_dgrad(g->L[i], gy, nullptr, Carver::at(sv, y.wd[i]), add, nullptr, dst, false, B, y.geo[i], st);
+        return launch_dgrad<Trunk3d>(g->L[i], gy, nullptr, nullptr, Carver::at(sv, y.wd[i]), add, nullptr, dst, false, B, y.geo[i], st);
     };
     int rc;
     if ((rc = launch_transpose(g_out, G, B, Co, P, st))) return rc;
@@ -927,7 +913,7 @@ int i2v_gblock_train_backward(i2v_gblock_train* g, const float* g_out, const flo
     if (g->learned) {
         if ((rc = launch_gemm(G, Carver::at(sv, y.wd[GC_S]), nullptr, BP, Co, Cin, E1, st))) return rc;
         if (pg) {
-            const D3Conv& c = g->L[GC_S];
+            const TcConv& c = g->L[GC_S];
             if ((rc = launch_wgrad1(G, Carver::at(sv, y.xn), g->w[GC_S], c.sn ? Carver::at(sv, y.us[GC_S]) : nullptr,
                                     c.sn ? Carver::at(sv, y.vs[GC_S]) : nullptr, c.sn ? Carver::at(sv, y.sigma[GC_S]) : nullptr, BP, Co, Cin, part, dwn,
                                     dotp, g->gw[GC_S], acc, st)))
@@ -953,7 +939,7 @@ int i2v_gblock_train_backward(i2v_gblock_train* g, const float* g_out, const flo
     if ((rc = dgrad(GC_G, E1, nullptr, D3))) return rc;
     if ((rc = dgrad(GC_B, E2, D3, G))) return rc;
     hipLaunchKernelGGL(gt_lrelu_bwd_kernel, dim3(grid_for(BHW * 128 / 4)), dim3(256), 0, st, G, y1, BHW * 128 / 4);
-    PD_LAUNCHED();
+    I2V_LAUNCHED();
     if ((rc = launch_bias_grad(G, BHW, 128, g->gb[GC_SP], acc, bpart, st))) return rc;
     return wgrad(GC_SP, G, img4);
 }
@@ -961,7 +947,7 @@ int i2v_gblock_train_backward(i2v_gblock_train* g, const float* g_out, const flo
 // ---------------------------------------------------------------------------------------------------------------- unit entries
 size_t i2v_gblock_train_unit_workspace_bytes(int32_t batch, int64_t rows, int32_t c) {
     if (batch <= 0 || rows <= 0 || c <= 0 || c % 16) return 0;
-    const D3Conv cc = conv2d_of(c, c), c3 = conv2d_of(3, c);
+    const TcConv cc = conv2d_of(c, c), c3 = conv2d_of(3, c);
     const size_t E = (size_t)c * c * 9;
     Carver k;
     k.take_bytes(norm_ws(batch, c).total);
@@ -1037,24 +1023,23 @@ int i2v_gblock_train_conv2d_unit(const float* x, const float* w, const float* g,
     I2V_REQUIRE(x && w && workspace && batch > 0 && h > 0 && w_ > 0 && cout > 0 && cout % 16 == 0 && (cin == 3 || (cin > 0 && cin % 16 == 0)) &&
                     (y || dx || dw) && (g || !(dx || dw)) && !(dx && cin == 3),
                 I2V_E_INVALID, "%s: bad argument", what);
-    const D3Conv c = conv2d_of(cin, cout);
-    const D3Geo geo = make_geo(batch, h, 1, w_, c);
+    const TcConv c = conv2d_of(cin, cout);
+    const TcGeo geo = make_geo(batch, h, 1, w_, c);
     const size_t E = (size_t)cout * cin * 9;
     Carver k;
     const size_t o_wf = k.take_floats((size_t)9 * cout * c.cinp), o_wd = k.take_floats((size_t)9 * c.cind * cout),
                  o_part = k.take_floats(wgrad_part_floats(c, geo.mo)), o_dwn = k.take_floats(E), o_dot = k.take_bytes(((E + 255) / 256 + 1) * 8);
     I2V_REQUIRE_WORKSPACE(workspace_bytes, k.total(), what);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    D3PackArgs pk{};
+    TcPackArgs pk{};
     pk.nconv = 1;
-    pk.c[0] = D3PackConv{w, nullptr, Carver::at(workspace, o_wf), Carver::at(workspace, o_wd), cout, cin, c.cinp, c.cind, 9, 0};
+    pk.c[0] = TcPackConv{w, nullptr, Carver::at(workspace, o_wf), Carver::at(workspace, o_wd), cout, cin, c.cinp, c.cind, 9, 0};
     pk.total = (long)cout * c.cind * 9;
-    hipLaunchKernelGGL(d3_pack_kernel, dim3(grid_for(pk.total)), dim3(256), 0, st, pk);
-    PD_LAUNCHED();
-    int rc;
-    if (y && (rc = launch_conv(c, x, Carver::at(workspace, o_wf), y, geo, st))) return rc;
-    if (dx && (rc = launch_dgrad(c, g, nullptr, Carver::at(workspace, o_wd), nullptr, nullptr, dx, false, batch, geo, st))) return rc;
-    if (dw && (rc = launch_wgrad(c, g, nullptr, x, w, nullptr, nullptr, nullptr, Carver::at(workspace, o_part), Carver::at(workspace, o_dwn),
+    int rc = launch_pack<Trunk3d>(pk, st);
+    if (rc) return rc;
+    if (y && (rc = launch_conv<Trunk3d>(c, x, Carver::at(workspace, o_wf), y, geo, st))) return rc;
+    if (dx && (rc = launch_dgrad<Trunk3d>(c, g, nullptr, nullptr, Carver::at(workspace, o_wd), nullptr, nullptr, dx, false, batch, geo, st))) return rc;
+    if (dw && (rc = launch_wgrad<Trunk3d>(c, g, nullptr, nullptr, x, w, nullptr, nullptr, nullptr, Carver::at(workspace, o_part), Carver::at(workspace, o_dwn),
                                  Carver::at<double>(workspace, o_dot), dw, false, geo, st)))
         return rc;
     return I2V_OK;

@@ -7,170 +7,27 @@
 //     (tap, channel)) and wd [tap][cin][cout] (input gradient: K over (tap, output channel)).  With I2V_PATCHDISC_SAVE they live in
 //     `saved` together with that call's u, v and sigma: a backward uses those values of ITS forward.  weight_orig (the projection),
 //     loc and scale are read from the bound parameters at backward time: they must not change between a forward and its backward.
+//   The kernels of the next three points are the Patch2d family of i2v_train_conv.h, shared with the 3-D ResNet trunk; here are ActNorm,
+//   the channel gradients, the cout = 1 head, the hinge, the layout and the C entries.
 //   * conv forward: the flat implicit GEMM of i2v_flatconv.h (128 or 64 positions x BN channels per workgroup, chunks of 16 K elements
 //     double-buffered in LDS) with the window fixed at 4 x 4 pad 1 and the epilogue bias -> [pre] -> ActNorm -> LeakyReLU.
 //   * dgrad: the same GEMM as a gather over input pixels.  At stride 2 a pixel receives the 2 x 2 taps of its parity, so the pixels
 //     are processed in four parity classes (blockIdx.y), each with its own taps: K = 4 cout.  The upstream gradient passes through
 //     the LeakyReLU mask and ActNorm's scale while it is loaded.
 //   * wgrad: per tap a [cout] x [cin] GEMM over the positions, operands straight from global memory.  The position range is cut into
-//     slices (pd_wgrad_plan, a pure function of the shape); the four waves of a workgroup take a quarter of a slice each and are
-//     summed in LDS in wave order; the slices' partial sums are added in slice order by pd_finish_a, which also forms the blocks
-//     of <dWn, W>; pd_finish_b adds those in block order, applies the spectral-norm projection and writes or accumulates.
+//     slices (wgrad_plan, a pure function of the shape); the four waves of a workgroup take a quarter of a slice each and are
+//     summed in LDS in wave order; the slices' partial sums are added in slice order by tc_finish_a, which also forms the blocks
+//     of <dWn, W>; tc_finish_dot adds those in block order; tc_finish_b applies the spectral-norm projection and writes or accumulates.
 //   * the cout = 1 head is a dot product per position (one wave), with thread-per-element gradient forms.
 #include "i2v_handle.h"
-#include "i2v_power_iter.h"
+#include "i2v_train_conv.h"
 #include "../../include/i2v_hip_disc.h"
 
 namespace i2v {
 namespace {
 
-constexpr int PD_LS = 20;   // floats per staged row of 16
-
-struct PdConv { int cin, cinp, cind, cout, stride, actnorm, lrelu, key; };   // cinp: channels of the stored input map; cind: columns of the dgrad GEMM
-struct PdMap { int hi, wi, ho, wo; long mi, mo; };
-
-__device__ __forceinline__ float lrelu_slope(float a) { return a > 0.f ? 1.f : 0.2f; }
-
-// ------------------------------------------------------------------------------------------------------------------ input stage
-__global__ __launch_bounds__(256) void pd_input4_kernel(const float* __restrict__ x, float* __restrict__ out, long npix, long hw) {
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < npix; i += gridDim.x * 256L) {
-        const long n = i / hw, p = i - n * hw;
-        const float* s = x + n * 3 * hw + p;
-        *reinterpret_cast<float4*>(out + 4 * i) = make_float4(s[0], s[hw], s[2 * hw], 0.f);
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------------------ spectral norm
-// (the power iteration: i2v_power_iter.h)  W / sigma into the two operand layouts
-struct PdPackConv { const float* w; const float* sigma; float* wf; float* wd; int cout, cin, cinp, cind; long first; };
-struct PdPackArgs { PdPackConv c[PD_MAXCONV]; int nconv; long total; };
-
-__global__ __launch_bounds__(256) void pd_pack_kernel(PdPackArgs a) {
-    for (long e = blockIdx.x * 256L + threadIdx.x; e < a.total; e += gridDim.x * 256L) {
-        int ci = 0;
-        while (ci + 1 < a.nconv && e >= a.c[ci + 1].first) ++ci;
-        const PdPackConv& c = a.c[ci];
-        long r = e - c.first;                       // ((co * cind) + cip) * 16 + tap
-        const int tap = (int)(r & 15); r >>= 4;
-        const int cip = (int)(r % c.cind), co = (int)(r / c.cind);
-        float val = 0.f;
-        if (cip < c.cin) {
-            val = c.w[((long)co * c.cin + cip) * 16 + tap];
-            if (c.sigma) val = val / *c.sigma;
-        }
-        if (cip < c.cinp) c.wf[((long)tap * c.cout + co) * c.cinp + cip] = val;
-        if (c.wd) c.wd[((long)tap * c.cind + cip) * c.cout + co] = val;
-    }
-}
-
-// ------------------------------------------------------------------------------------------------------------------ conv forward
-struct PdConvArgs {
-    const float* in;     // [N][Hi][Wi][cinp]
-    const float* wf;     // [16][cout][cinp]
-    const float *bias, *loc, *scale;   // loc / scale null: no ActNorm
-    float *out, *pre;    // [M][cout]; either may be null
-    long M;
-    int Hi, Wi, Ho, Wo, cinp, C4, nchunk, stride, cout, lrelu;
-};
-
-template <int NT, int MR>   // BN = 16 NT columns, BM = 64 MR rows per workgroup
-__global__ __launch_bounds__(256) void pd_conv_kernel(PdConvArgs a) {
-    constexpr int BN = 16 * NT, BM = 64 * MR;
-    __shared__ __attribute__((aligned(16))) float a_lds[2][BM * PD_LS];
-    __shared__ __attribute__((aligned(16))) float w_lds[2][BN * PD_LS];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int lr = lane & 15, kq = lane >> 4, q = tid & 3;
-    const int nNt = a.cout / BN;
-    const int n0 = (int)(blockIdx.x % nNt) * BN;
-    const long m0 = (long)(blockIdx.x / nNt) * BM;
-
-    int rb[MR], rh[MR], rw[MR];
-#pragma unroll
-    for (int u = 0; u < MR; ++u) {
-        long m = m0 + (tid >> 2) + 64 * u;
-        const bool ok = m < a.M;
-        if (!ok) m = 0;
-        const int wo = (int)(m % a.Wo); m /= a.Wo;
-        const int ho = (int)(m % a.Ho); m /= a.Ho;
-        rb[u] = ok ? (int)m : -1;
-        rh[u] = ho * a.stride - 1; rw[u] = wo * a.stride - 1;
-    }
-    float4 pa0, pa1, pw0;
-    pa1 = pw0 = make_float4(0.f, 0.f, 0.f, 0.f);
-    auto request = [&](int ch) {
-        const int g = ch * 4 + q;
-        const int tap = g / a.C4, c = (g - tap * a.C4) * 4;
-        const int dh = tap >> 2, dw = tap & 3;
-#pragma unroll
-        for (int u = 0; u < MR; ++u) {
-            const int h = rh[u] + dh, w = rw[u] + dw;
-            const bool ok = rb[u] >= 0 && (unsigned)h < (unsigned)a.Hi && (unsigned)w < (unsigned)a.Wi;
-            const long off = ok ? (((long)rb[u] * a.Hi + h) * a.Wi + w) * a.cinp + c : 0;
-            const float4 v = *reinterpret_cast<const float4*>(a.in + off);
-            const float4 z = ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
-            if (u == 0) pa0 = z; else pa1 = z;
-        }
-        if (tid < BN * 4) pw0 = *reinterpret_cast<const float4*>(a.wf + ((long)tap * a.cout + n0 + (tid >> 2)) * a.cinp + c);
-    };
-    auto park = [&](int buf) {
-        *reinterpret_cast<float4*>(&a_lds[buf][(tid >> 2) * PD_LS + 4 * q]) = pa0;
-        if constexpr (MR == 2) *reinterpret_cast<float4*>(&a_lds[buf][((tid >> 2) + 64) * PD_LS + 4 * q]) = pa1;
-        if (tid < BN * 4) *reinterpret_cast<float4*>(&w_lds[buf][(tid >> 2) * PD_LS + 4 * q]) = pw0;
-    };
-
-    f32x4 acc[MR][NT];
-#pragma unroll
-    for (int mt = 0; mt < MR; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    request(0);
-    park(0);
-    __syncthreads();
-    for (int ch = 0; ch < a.nchunk; ++ch) {
-        const int buf = ch & 1;
-        request(ch + 1 < a.nchunk ? ch + 1 : ch);
-        // MFMA k-slot (lane >> 4) of step s carries K element 4 (lane >> 4) + s of the chunk, for both operands
-        float4 av[MR], bv[NT];
-#pragma unroll
-        for (int mt = 0; mt < MR; ++mt) av[mt] = *reinterpret_cast<const float4*>(&a_lds[buf][(wave * 16 * MR + 16 * mt + lr) * PD_LS + 4 * kq]);
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) bv[nt] = *reinterpret_cast<const float4*>(&w_lds[buf][(16 * nt + lr) * PD_LS + 4 * kq]);
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-            for (int mt = 0; mt < MR; ++mt) {
-                const float as = s == 0 ? av[mt].x : s == 1 ? av[mt].y : s == 2 ? av[mt].z : av[mt].w;
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    const float bs = s == 0 ? bv[nt].x : s == 1 ? bv[nt].y : s == 2 ? bv[nt].z : bv[nt].w;
-                    acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(as, bs, acc[mt][nt], 0, 0, 0);
-                }
-            }
-        if (ch + 1 < a.nchunk) park(buf ^ 1);
-        __syncthreads();
-    }
-
-    // C/D layout of the 16x16 MFMA: column = lane & 15, rows 4 (lane >> 4) + r
-#pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        const int n = n0 + 16 * nt + lr;
-        const float b = a.bias[n];
-        const float lc = a.loc ? a.loc[n] : 0.f, sc = a.loc ? a.scale[n] : 1.f;
-#pragma unroll
-        for (int mt = 0; mt < MR; ++mt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const long m = m0 + wave * 16 * MR + 16 * mt + 4 * kq + r;
-                if (m >= a.M) continue;
-                float y = acc[mt][nt][r] + b;
-                if (a.pre) a.pre[m * a.cout + n] = y;
-                if (a.loc) y = sc * (y + lc);
-                if (a.lrelu) y = y > 0.f ? y : 0.2f * y;
-                if (a.out) a.out[m * a.cout + n] = y;
-            }
-    }
-}
+static_assert(PD_MAXCONV <= TC_MAXCONV, "one pack launch takes every conv of the network");
+struct PdLayer : TcConv { int actnorm, lrelu, key; };   // a conv of the network, its ActNorm and LeakyReLU, its index in `main`
 
 // h = LeakyReLU(scale * (pre + loc)): the forward that initialises ActNorm computes the conv first and applies the norm afterwards
 __global__ __launch_bounds__(256) void pd_actnorm_apply_kernel(const float* __restrict__ pre, const float* __restrict__ loc, const float* __restrict__ scale,
@@ -212,265 +69,6 @@ __global__ __launch_bounds__(256) void pd_actnorm_init_kernel(const float* __res
         loc[c] = (float)(-mean);
         scale[c] = (float)(1.0 / (sqrt(t / (double)(M - 1)) + 1e-6));
     }
-}
-
-// ------------------------------------------------------------------------------------------------------------------ input gradient
-struct PdDgradArgs {
-    const float* g;      // [N][Ho][Wo][cout], the gradient at the layer's activation
-    const float* act;    // the activation itself (the LeakyReLU mask) or null
-    const float* scale;  // ActNorm's scale [cout] or null
-    const float* wd;     // [16][cind][cout]
-    float* out;          // [N][Hi][Wi][cin]; frames: [N][3][Hi][Wi]
-    int N, Hi, Wi, Ho, Wo, cout, C4o, stride, cin, cind, frames;
-};
-
-template <int NT, int MR>
-__global__ __launch_bounds__(256) void pd_dgrad_kernel(PdDgradArgs a) {
-    constexpr int BN = 16 * NT, BM = 64 * MR;
-    __shared__ __attribute__((aligned(16))) float a_lds[2][BM * PD_LS];
-    __shared__ __attribute__((aligned(16))) float w_lds[2][BN * PD_LS];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int lr = lane & 15, kq = lane >> 4, q = tid & 3;
-    // the pixels of one parity class (stride 2) or all of them (stride 1)
-    const int s2 = a.stride == 2;
-    const int ph = s2 ? (int)(blockIdx.y >> 1) : 0, pw = s2 ? (int)(blockIdx.y & 1) : 0;
-    const int Hc = s2 ? (a.Hi + 1 - ph) / 2 : a.Hi, Wc = s2 ? (a.Wi + 1 - pw) / 2 : a.Wi;
-    const long Mc = (long)a.N * Hc * Wc;
-    const int nNt = a.cind / BN;
-    const int n0 = (int)(blockIdx.x % nNt) * BN;
-    const long m0 = (long)(blockIdx.x / nNt) * BM;
-    if (m0 >= Mc) return;
-    const int khb = s2 ? (ph + 1) & 1 : 0, kwb = s2 ? (pw + 1) & 1 : 0;
-    const int ntap = s2 ? 4 : 16;
-    const int nchunk = ntap * a.C4o / 4;
-
-    int rb[MR], rh[MR], rw[MR];   // batch row (-1: masked), h + 1, w + 1
-#pragma unroll
-    for (int u = 0; u < MR; ++u) {
-        long m = m0 + (tid >> 2) + 64 * u;
-        const bool ok = m < Mc;
-        if (!ok) m = 0;
-        const int wc = (int)(m % Wc); m /= Wc;
-        const int hc = (int)(m % Hc); m /= Hc;
-        rb[u] = ok ? (int)m : -1;
-        rh[u] = (s2 ? 2 * hc + ph : hc) + 1; rw[u] = (s2 ? 2 * wc + pw : wc) + 1;
-    }
-    float4 pa0, pa1, pw0;
-    pa1 = pw0 = make_float4(0.f, 0.f, 0.f, 0.f);
-    auto request = [&](int ch) {
-        const int g = ch * 4 + q;
-        const int tj = g / a.C4o, c = (g - tj * a.C4o) * 4;
-        const int kh = s2 ? khb + 2 * (tj >> 1) : tj >> 2, kw = s2 ? kwb + 2 * (tj & 1) : tj & 3;
-#pragma unroll
-        for (int u = 0; u < MR; ++u) {
-            const int th = rh[u] - kh, tw = rw[u] - kw;   // even at stride 2 by the choice of the taps
-            const int ho = s2 ? th >> 1 : th, wo = s2 ? tw >> 1 : tw;
-            const bool ok = rb[u] >= 0 && th >= 0 && tw >= 0 && ho < a.Ho && wo < a.Wo;
-            const long off = ok ? (((long)rb[u] * a.Ho + ho) * a.Wo + wo) * a.cout + c : 0;
-            float4 v = *reinterpret_cast<const float4*>(a.g + off);
-            if (a.act) {
-                const float4 y = *reinterpret_cast<const float4*>(a.act + off);
-                v.x *= lrelu_slope(y.x); v.y *= lrelu_slope(y.y); v.z *= lrelu_slope(y.z); v.w *= lrelu_slope(y.w);
-            }
-            if (a.scale) {
-                const float4 sc = *reinterpret_cast<const float4*>(a.scale + c);
-                v.x *= sc.x; v.y *= sc.y; v.z *= sc.z; v.w *= sc.w;
-            }
-            const float4 z = ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
-            if (u == 0) pa0 = z; else pa1 = z;
-        }
-        if (tid < BN * 4) pw0 = *reinterpret_cast<const float4*>(a.wd + ((long)(kh * 4 + kw) * a.cind + n0 + (tid >> 2)) * a.cout + c);
-    };
-    auto park = [&](int buf) {
-        *reinterpret_cast<float4*>(&a_lds[buf][(tid >> 2) * PD_LS + 4 * q]) = pa0;
-        if constexpr (MR == 2) *reinterpret_cast<float4*>(&a_lds[buf][((tid >> 2) + 64) * PD_LS + 4 * q]) = pa1;
-        if (tid < BN * 4) *reinterpret_cast<float4*>(&w_lds[buf][(tid >> 2) * PD_LS + 4 * q]) = pw0;
-    };
-
-    f32x4 acc[MR][NT];
-#pragma unroll
-    for (int mt = 0; mt < MR; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    request(0);
-    park(0);
-    __syncthreads();
-    for (int ch = 0; ch < nchunk; ++ch) {
-        const int buf = ch & 1;
-        request(ch + 1 < nchunk ? ch + 1 : ch);
-        float4 av[MR], bv[NT];
-#pragma unroll
-        for (int mt = 0; mt < MR; ++mt) av[mt] = *reinterpret_cast<const float4*>(&a_lds[buf][(wave * 16 * MR + 16 * mt + lr) * PD_LS + 4 * kq]);
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) bv[nt] = *reinterpret_cast<const float4*>(&w_lds[buf][(16 * nt + lr) * PD_LS + 4 * kq]);
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-            for (int mt = 0; mt < MR; ++mt) {
-                const float as = s == 0 ? av[mt].x : s == 1 ? av[mt].y : s == 2 ? av[mt].z : av[mt].w;
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    const float bs = s == 0 ? bv[nt].x : s == 1 ? bv[nt].y : s == 2 ? bv[nt].z : bv[nt].w;
-                    acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(as, bs, acc[mt][nt], 0, 0, 0);
-                }
-            }
-        if (ch + 1 < nchunk) park(buf ^ 1);
-        __syncthreads();
-    }
-
-#pragma unroll
-    for (int mt = 0; mt < MR; ++mt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            long m = m0 + wave * 16 * MR + 16 * mt + 4 * kq + r;
-            if (m >= Mc) continue;
-            const int wc = (int)(m % Wc); m /= Wc;
-            const int hc = (int)(m % Hc); m /= Hc;
-            const int h = s2 ? 2 * hc + ph : hc, w = s2 ? 2 * wc + pw : wc;
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                const int n = n0 + 16 * nt + lr;
-                if (a.frames) {
-                    if (n < 3) a.out[((m * 3 + n) * a.Hi + h) * a.Wi + w] = acc[mt][nt][r];
-                } else if (n < a.cin) {
-                    a.out[((m * a.Hi + h) * a.Wi + w) * a.cin + n] = acc[mt][nt][r];
-                }
-            }
-        }
-}
-
-// ------------------------------------------------------------------------------------------------------------------ weight gradient
-struct PdWgradArgs {
-    const float *g, *act, *scale;   // as PdDgradArgs
-    const float* x;                 // the conv's input [N][Hi][Wi][cinp]
-    float* part;                    // [slices][16][cout][CP]
-    long P;                         // positions N Ho Wo
-    int Hi, Wi, Ho, Wo, cinp, cout, CP, stride, slice_len;
-};
-
-template <int MT, int NT>
-__global__ __launch_bounds__(256) void pd_wgrad_kernel(PdWgradArgs a) {
-    __shared__ float red[3][MT * NT * 4 * 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int lr = lane & 15, kq = lane >> 4;
-    const int nCi = a.CP / (16 * NT);
-    const int co0 = (int)(blockIdx.x / nCi) * 16 * MT, ci0 = (int)(blockIdx.x % nCi) * 16 * NT;
-    const int tap = blockIdx.y, kh = tap >> 2, kw = tap & 3;
-    const int sl = blockIdx.z, quarter = a.slice_len / 4;
-    const long begin = (long)sl * a.slice_len + (long)wave * quarter;
-    const long end = begin + quarter < a.P ? begin + quarter : a.P;
-
-    f32x4 acc[MT][NT];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    // A[i = co][k = position], B[k = position][j = ci]: k-slot (lane >> 4) of a step is position mb + (lane >> 4)
-    for (long mb = begin; mb < end; mb += 4) {
-        long m = mb + kq;
-        const bool ok = m < end;
-        if (!ok) m = 0;
-        const long mrow = m;
-        const int wo = (int)(m % a.Wo); m /= a.Wo;
-        const int ho = (int)(m % a.Ho); m /= a.Ho;
-        const int h = ho * a.stride - 1 + kh, w = wo * a.stride - 1 + kw;
-        const bool xok = ok && (unsigned)h < (unsigned)a.Hi && (unsigned)w < (unsigned)a.Wi;
-        const long pix = xok ? (m * a.Hi + h) * a.Wi + w : 0;
-        float av[MT], bv[NT];
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            const int co = co0 + 16 * mt + lr;
-            float v = a.g[mrow * a.cout + co];
-            if (a.act) v *= lrelu_slope(a.act[mrow * a.cout + co]);
-            if (a.scale) v *= a.scale[co];
-            av[mt] = ok ? v : 0.f;
-        }
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const int ci = ci0 + 16 * nt + lr;
-            const bool cok = xok && ci < a.cinp;
-            const float v = a.x[cok ? pix * a.cinp + ci : 0];
-            bv[nt] = cok ? v : 0.f;
-        }
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mt], bv[nt], acc[mt][nt], 0, 0, 0);
-    }
-
-    // the four waves' sums in wave order
-    if (wave > 0) {
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) red[wave - 1][((mt * NT + nt) * 4 + r) * 64 + lane] = acc[mt][nt][r];
-    }
-    __syncthreads();
-    if (wave > 0) return;
-    float* dst = a.part + ((long)sl * 16 + tap) * a.cout * a.CP;
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float v = acc[mt][nt][r];
-                for (int w = 0; w < 3; ++w) v += red[w][((mt * NT + nt) * 4 + r) * 64 + lane];
-                dst[(long)(co0 + 16 * mt + 4 * kq + r) * a.CP + ci0 + 16 * nt + lr] = v;
-            }
-}
-
-struct PdFinishArgs {
-    const float* part;   // [S][16][cout][CP]
-    const float* w;      // weight_orig [cout][cin][16]
-    const float *u, *v, *sigma;   // this forward's values; sigma null: no projection
-    float* dwn;          // [cout][cin][16]
-    double* dotp;        // [nblk]
-    float* grad;
-    long E;
-    int S, cout, cin, CP, nblk, accumulate;
-};
-
-// dWn = the slices' partial sums in slice order; per workgroup sum of dWn * W in float64
-__global__ __launch_bounds__(256) void pd_finish_a_kernel(PdFinishArgs a) {
-    __shared__ double red[256];
-    const long e = blockIdx.x * 256L + threadIdx.x;
-    double d = 0.0;
-    if (e < a.E) {
-        const int K = a.cin * 16;
-        const int co = (int)(e / K), k = (int)(e % K), ci = k >> 4, tap = k & 15;
-        float sum = 0.f;
-        for (int s = 0; s < a.S; ++s) sum += a.part[(((long)s * 16 + tap) * a.cout + co) * a.CP + ci];
-        a.dwn[e] = sum;
-        d = (double)sum * (double)a.w[e];
-    }
-    d = block_sum(d, red);
-    if (threadIdx.x == 0) a.dotp[blockIdx.x] = d;
-}
-
-// dW_orig = (dWn - <dWn, W / sigma> u v^T) / sigma, written or accumulated
-__global__ __launch_bounds__(256) void pd_finish_b_kernel(PdFinishArgs a) {
-    __shared__ double red[256];
-    float proj = 0.f, sg = 1.f;
-    if (a.sigma) {
-        double d = 0.0;
-        for (int i = threadIdx.x; i < a.nblk; i += 256) d += a.dotp[i];
-        d = block_sum(d, red);
-        sg = *a.sigma;
-        proj = (float)(d / (double)sg);
-    }
-    const long e = blockIdx.x * 256L + threadIdx.x;
-    if (e >= a.E) return;
-    float gv = a.dwn[e];
-    if (a.sigma) {
-        const int K = a.cin * 16;
-        gv = (gv - proj * a.u[e / K] * a.v[e % K]) / sg;
-    }
-    a.grad[e] = a.accumulate ? a.grad[e] + gv : gv;
 }
 
 // per channel over the M rows: dh = g * mask; dbias = scale * sum dh, d_loc = scale * sum dh, d_scale = sum dh * (pre + loc); float64.
@@ -613,120 +211,6 @@ __global__ __launch_bounds__(256) void pd_hinge_kernel(const float* __restrict__
 
 // =================================================================================================================== host side
 
-int bn_of(int c) { return c % 64 == 0 ? 64 : c % 32 == 0 ? 32 : 16; }
-// rows per workgroup of the two GEMM kernels: 128, or 64 where 128 would leave the device's compute units without two workgroups each
-// (a function of the shape alone: the same shape always runs the same kernel)
-int rows_of(long rows, int column_tiles) { return (rows + 127) / 128 * column_tiles >= 512 ? 128 : 64; }
-
-// the slice plan of the weight gradient: enough workgroups to fill the device, slices of at least 64 positions
-void pd_wgrad_plan(int cout, int cin, long P, int* slices, int* slice_len) {
-    long S;
-    if (cout == 1) {
-        S = std::min<long>(std::max<long>((P + 63) / 64, 1), 128);
-    } else {
-        const int CP = (int)align_up(cin == 3 ? 4 : cin, 16);
-        const long tiles = 16L * (cout / bn_of(cout)) * (CP / bn_of(CP));
-        S = std::min<long>(std::max<long>((1024 + tiles - 1) / tiles, 1), std::max<long>((P + 63) / 64, 1));
-    }
-    const long L = (long)align_up((size_t)((P + S - 1) / S), 16);
-    *slice_len = (int)L;
-    *slices = (int)((P + L - 1) / L);
-}
-
-int launch_conv(const PdConv& c, const float* in, const float* wf, const float* bias, const float* loc, const float* scale, float* out, float* pre,
-                int N, const PdMap& mp, bool lrelu, hipStream_t st) {
-    PdConvArgs a{};
-    a.in = in; a.wf = wf; a.bias = bias; a.loc = loc; a.scale = scale; a.out = out; a.pre = pre;
-    a.M = mp.mo; a.Hi = mp.hi; a.Wi = mp.wi; a.Ho = mp.ho; a.Wo = mp.wo;
-    a.cinp = c.cinp; a.C4 = c.cinp / 4; a.nchunk = 4 * a.C4; a.stride = c.stride; a.cout = c.cout; a.lrelu = lrelu ? 1 : 0;
-    const int BN = bn_of(c.cout);
-    const int BM = rows_of(a.M, c.cout / BN);
-    const long nblk = (a.M + BM - 1) / BM * (c.cout / BN);
-    I2V_REQUIRE(nblk > 0 && nblk < (1L << 31), I2V_E_INVALID, "patch discriminator: conv grid of %ld workgroups", nblk);
-    const dim3 grid((unsigned)nblk);
-    if (BM == 128) {
-        if (BN == 64) hipLaunchKernelGGL((pd_conv_kernel<4, 2>), grid, dim3(256), 0, st, a);
-        else if (BN == 32) hipLaunchKernelGGL((pd_conv_kernel<2, 2>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((pd_conv_kernel<1, 2>), grid, dim3(256), 0, st, a);
-    } else {
-        if (BN == 64) hipLaunchKernelGGL((pd_conv_kernel<4, 1>), grid, dim3(256), 0, st, a);
-        else if (BN == 32) hipLaunchKernelGGL((pd_conv_kernel<2, 1>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((pd_conv_kernel<1, 1>), grid, dim3(256), 0, st, a);
-    }
-    PD_LAUNCHED();
-    return I2V_OK;
-}
-
-int launch_dgrad(const PdConv& c, const float* g, const float* act, const float* scale, const float* wd, float* out, bool frames, int N, const PdMap& mp,
-                 hipStream_t st) {
-    PdDgradArgs a{};
-    a.g = g; a.act = act; a.scale = scale; a.wd = wd; a.out = out;
-    a.N = N; a.Hi = mp.hi; a.Wi = mp.wi; a.Ho = mp.ho; a.Wo = mp.wo;
-    a.cout = c.cout; a.C4o = c.cout / 4; a.stride = c.stride; a.cin = c.cin == 3 && !frames ? 4 : c.cin; a.cind = c.cind; a.frames = frames ? 1 : 0;
-    const int BN = bn_of(c.cind);
-    const long mc = c.stride == 2 ? (long)N * ((mp.hi + 1) / 2) * ((mp.wi + 1) / 2) : mp.mi;   // the largest parity class
-    const int BM = rows_of(mc * (c.stride == 2 ? 4 : 1), c.cind / BN);
-    const long nblk = (mc + BM - 1) / BM * (c.cind / BN);
-    I2V_REQUIRE(nblk > 0 && nblk < (1L << 31), I2V_E_INVALID, "patch discriminator: dgrad grid of %ld workgroups", nblk);
-    const dim3 grid((unsigned)nblk, c.stride == 2 ? 4 : 1);
-    if (BM == 128) {
-        if (BN == 64) hipLaunchKernelGGL((pd_dgrad_kernel<4, 2>), grid, dim3(256), 0, st, a);
-        else if (BN == 32) hipLaunchKernelGGL((pd_dgrad_kernel<2, 2>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((pd_dgrad_kernel<1, 2>), grid, dim3(256), 0, st, a);
-    } else {
-        if (BN == 64) hipLaunchKernelGGL((pd_dgrad_kernel<4, 1>), grid, dim3(256), 0, st, a);
-        else if (BN == 32) hipLaunchKernelGGL((pd_dgrad_kernel<2, 1>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((pd_dgrad_kernel<1, 1>), grid, dim3(256), 0, st, a);
-    }
-    PD_LAUNCHED();
-    return I2V_OK;
-}
-
-template <int MT>
-void launch_wgrad_nt(int nt, dim3 grid, hipStream_t st, const PdWgradArgs& a) {
-    if (nt == 4) hipLaunchKernelGGL((pd_wgrad_kernel<MT, 4>), grid, dim3(256), 0, st, a);
-    else if (nt == 2) hipLaunchKernelGGL((pd_wgrad_kernel<MT, 2>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((pd_wgrad_kernel<MT, 1>), grid, dim3(256), 0, st, a);
-}
-
-size_t wgrad_part_floats(const PdConv& c, long P) {
-    int S, L;
-    pd_wgrad_plan(c.cout, c.cin, P, &S, &L);
-    return (size_t)S * 16 * c.cout * (c.cout == 1 ? c.cin : align_up(c.cinp, 16));
-}
-size_t finish_blocks(const PdConv& c) { return ((size_t)c.cout * c.cin * 16 + 255) / 256; }
-
-// partial sums -> dwn -> grad (written or accumulated): g masked and scaled as in the dgrad
-int launch_wgrad(const PdConv& c, const float* g, const float* act, const float* scale, const float* x, const float* w, const float* u, const float* v,
-                 const float* sigma, float* part, float* dwn, double* dotp, float* grad, bool accumulate, const PdMap& mp, hipStream_t st) {
-    int S, L;
-    pd_wgrad_plan(c.cout, c.cin, mp.mo, &S, &L);
-    PdFinishArgs f{};
-    if (c.cout == 1) {
-        hipLaunchKernelGGL(pd_head_wgrad_kernel, dim3((c.cin + 255) / 256, 16, S), dim3(256), 0, st, g, x, part, mp.mo, mp.hi, mp.wi, c.cin, L);
-        f.CP = c.cin;
-    } else {
-        PdWgradArgs a{};
-        a.g = g; a.act = act; a.scale = scale; a.x = x; a.part = part; a.P = mp.mo;
-        a.Hi = mp.hi; a.Wi = mp.wi; a.Ho = mp.ho; a.Wo = mp.wo; a.cinp = c.cinp; a.cout = c.cout; a.CP = (int)align_up(c.cinp, 16);
-        a.stride = c.stride; a.slice_len = L;
-        const int mt = bn_of(c.cout) / 16, nt = bn_of(a.CP) / 16;
-        const dim3 grid((unsigned)((c.cout / (16 * mt)) * (a.CP / (16 * nt))), 16, (unsigned)S);
-        if (mt == 4) launch_wgrad_nt<4>(nt, grid, st, a);
-        else if (mt == 2) launch_wgrad_nt<2>(nt, grid, st, a);
-        else launch_wgrad_nt<1>(nt, grid, st, a);
-        f.CP = a.CP;
-    }
-    PD_LAUNCHED();
-    f.part = part; f.w = w; f.u = u; f.v = v; f.sigma = sigma; f.dwn = dwn; f.dotp = dotp; f.grad = grad;
-    f.E = (long)c.cout * c.cin * 16; f.S = S; f.cout = c.cout; f.cin = c.cin; f.nblk = (int)finish_blocks(c); f.accumulate = accumulate ? 1 : 0;
-    hipLaunchKernelGGL(pd_finish_a_kernel, dim3(f.nblk), dim3(256), 0, st, f);
-    PD_LAUNCHED();
-    hipLaunchKernelGGL(pd_finish_b_kernel, dim3(f.nblk), dim3(256), 0, st, f);
-    PD_LAUNCHED();
-    return I2V_OK;
-}
-
 constexpr int PD_CHAN_SLICES = 64;
 size_t chan_partial_bytes(int C) { return (size_t)PD_CHAN_SLICES * C * 2 * 8; }
 
@@ -735,30 +219,42 @@ int launch_chan_grads(const float* g, const float* act, const float* pre, const 
     const int R = (int)std::min<long>(std::max<long>((M + 1023) / 1024, 1), PD_CHAN_SLICES);
     PdChanArgs a{g, act, pre, loc, scale, dbias, dloc, dscale, partial, M, (M + R - 1) / R, C, R, accumulate ? 1 : 0};
     hipLaunchKernelGGL(pd_chan_partial_kernel, dim3(C >= 16 ? C / 16 : C, R), dim3(256), 0, st, a);
-    PD_LAUNCHED();
+    I2V_LAUNCHED();
     hipLaunchKernelGGL(pd_chan_final_kernel, dim3((C + 255) / 256), dim3(256), 0, st, a);
-    PD_LAUNCHED();
+    I2V_LAUNCHED();
     return I2V_OK;
 }
 
-int launch_pack(const PdPackArgs& a, hipStream_t st) {
-    hipLaunchKernelGGL(pd_pack_kernel, dim3(grid_for(a.total)), dim3(256), 0, st, a);
-    PD_LAUNCHED();
-    return I2V_OK;
+// the head's branch of the weight gradient's slice plan, its partial sums [slices][16][cin] and its launch
+void head_wgrad_plan(long P, int* slices, int* slice_len) { cut_slices(P, std::min<long>(std::max<long>((P + 63) / 64, 1), 128), slices, slice_len); }
+size_t part_floats(const TcConv& c, long P) {
+    if (c.cout > 1) return wgrad_part_floats(c, P);
+    int S, L;
+    head_wgrad_plan(P, &S, &L);
+    return (size_t)S * 16 * c.cin;
+}
+int launch_head_wgrad(const TcConv& c, const float* g, const float* x, const float* w, const float* u, const float* v, const float* sigma, float* part,
+                      float* dwn, double* dotp, float* grad, bool accumulate, const TcGeo& mp, hipStream_t st) {
+    int S, L;
+    head_wgrad_plan(mp.mo, &S, &L);
+    hipLaunchKernelGGL(pd_head_wgrad_kernel, dim3((c.cin + 255) / 256, 16, S), dim3(256), 0, st, g, x, part, mp.mo, mp.hi, mp.wi, c.cin, L);
+    I2V_LAUNCHED();
+    return launch_finish(part, S, c.cin, 1, c.cin, 16, w, u, v, sigma, dwn, dotp, grad, accumulate, st);
 }
 
-PdConv make_conv(int cin, int cout, int stride, int actnorm, int lrelu, int key) {
-    return PdConv{cin, cin == 3 ? 4 : cin, cin == 3 ? 16 : cin, cout, stride, actnorm, lrelu, key};
+// the window of Win2: 4 x 4, pad 1, no time axis (sn: set by the network; a unit entry is told by its u, v, sigma arguments)
+PdLayer make_conv(int cin, int cout, int stride, int actnorm, int lrelu, int key) {
+    return PdLayer{TcConv{cin, cin == 3 ? 4 : cin, cin == 3 ? 16 : cin, cout, 1, 4, 4, 1, stride, 0}, actnorm, lrelu, key};
 }
-PdMap make_map(int n, int hi, int wi, int stride) {
-    PdMap m{};
+TcGeo make_map(int n, int hi, int wi, int stride) {
+    TcGeo m{};
+    m.ti = m.to = 1;
     m.hi = hi; m.wi = wi; m.ho = (hi + 2 - 4) / stride + 1; m.wo = (wi + 2 - 4) / stride + 1;
     if (hi < 2) m.ho = 0;
     if (wi < 2) m.wo = 0;
     m.mi = (long)n * hi * wi; m.mo = (long)n * m.ho * m.wo;
     return m;
 }
-size_t pack_elems(const PdConv& c) { return (size_t)c.cout * c.cind * 16; }
 
 }  // namespace
 }  // namespace i2v
@@ -770,7 +266,7 @@ struct i2v_patchdisc {
     bool loaded = false;   // parameters bound
     bool have_grads = false;
     int nconv = 0, sn = 1;
-    PdConv L[PD_MAXCONV];
+    PdLayer L[PD_MAXCONV];
     float *w[PD_MAXCONV] = {}, *b[PD_MAXCONV] = {}, *u[PD_MAXCONV] = {}, *v[PD_MAXCONV] = {}, *loc[PD_MAXCONV] = {}, *scale[PD_MAXCONV] = {};
     float *gw[PD_MAXCONV] = {}, *gb[PD_MAXCONV] = {}, *gloc[PD_MAXCONV] = {}, *gscale[PD_MAXCONV] = {};
 };
@@ -780,7 +276,7 @@ namespace {
 // Where everything lies for one input shape: `saved` (offsets from its base) and the workspace
 struct PdLayout {
     bool ok = false;
-    PdMap map[PD_MAXCONV];
+    TcGeo map[PD_MAXCONV];
     size_t x4 = 0, act[PD_MAXCONV] = {}, pre[PD_MAXCONV] = {}, wf[PD_MAXCONV] = {}, wd[PD_MAXCONV] = {}, sigma[PD_MAXCONV] = {}, us[PD_MAXCONV] = {},
            vs[PD_MAXCONV] = {}, saved_total = 0;
     size_t pi_t[PD_MAXCONV] = {}, pi_s[PD_MAXCONV] = {}, fwd = 0, ga = 0, gb = 0, part = 0, dwn = 0, dotp = 0, chan = 0, ws_total = 0;
@@ -791,7 +287,7 @@ PdLayout pd_layout(const i2v_patchdisc* d, int n, int h, int w) {
     if (n <= 0 || h <= 0 || w <= 0) return y;
     int hi = h, wi = w;
     for (int i = 0; i < d->nconv; ++i) {
-        y.map[i] = make_map(n, hi, wi, d->L[i].stride);
+        y.map[i] = make_map(n, hi, wi, d->L[i].ss);
         if (y.map[i].ho < 1 || y.map[i].wo < 1) return y;
         hi = y.map[i].ho; wi = y.map[i].wo;
     }
@@ -799,7 +295,7 @@ PdLayout pd_layout(const i2v_patchdisc* d, int n, int h, int w) {
     y.x4 = s.take_floats((size_t)y.map[0].mi * 4);
     size_t gmax = 0, pmax = 0, emax = 0, bmax = 0, cmax = 0;
     for (int i = 0; i < d->nconv; ++i) {
-        const PdConv& c = d->L[i];
+        const PdLayer& c = d->L[i];
         if (i + 1 < d->nconv) {
             y.act[i] = s.take_floats((size_t)y.map[i].mo * c.cout);
             y.pre[i] = s.take_floats(c.actnorm ? (size_t)y.map[i].mo * c.cout : 0);
@@ -810,7 +306,7 @@ PdLayout pd_layout(const i2v_patchdisc* d, int n, int h, int w) {
         y.sigma[i] = s.take_floats(1);
         y.us[i] = s.take_floats(c.cout);
         y.vs[i] = s.take_floats((size_t)c.cin * 16);
-        pmax = std::max(pmax, wgrad_part_floats(c, y.map[i].mo));
+        pmax = std::max(pmax, part_floats(c, y.map[i].mo));
         emax = std::max(emax, (size_t)c.cout * c.cin * 16);
         bmax = std::max(bmax, finish_blocks(c));
         cmax = std::max(cmax, chan_partial_bytes(c.cout));
@@ -837,7 +333,7 @@ int check_unit(const char* what, int n, int hi, int wi, int cin, int cout, int s
     I2V_REQUIRE(n > 0 && hi >= 2 && wi >= 2 && (stride == 1 || stride == 2), I2V_E_INVALID, "%s: n %d, map %d x %d, stride %d", what, n, hi, wi, stride);
     I2V_REQUIRE((cin == 3 || (cin > 0 && cin % 16 == 0)) && cout > 0 && cout % 16 == 0, I2V_E_INVALID,
                 "%s: cin %d (3 or a multiple of 16), cout %d (a multiple of 16)", what, cin, cout);
-    const PdMap m = make_map(n, hi, wi, stride);
+    const TcGeo m = make_map(n, hi, wi, stride);
     I2V_REQUIRE(m.ho >= 1 && m.wo >= 1, I2V_E_INVALID, "%s: a %d x %d map leaves no output", what, hi, wi);
     return I2V_OK;
 }
@@ -845,13 +341,13 @@ int check_unit(const char* what, int n, int hi, int wi, int cin, int cout, int s
 // workspace of the unit entries: wf, wd, part, dwn, dotp, the power iteration's t and s
 struct PdUnitWs { size_t wf, wd, part, dwn, dotp, chan, t, s, sig, total; };
 PdUnitWs unit_ws(int n, int hi, int wi, int cin, int cout) {
-    const PdConv c = make_conv(cin, cout, 1, 0, 0, 0);
-    const PdMap m = make_map(n, hi, wi, 1);   // stride 1 has the most positions
+    const PdLayer c = make_conv(cin, cout, 1, 0, 0, 0);
+    const TcGeo m = make_map(n, hi, wi, 1);   // stride 1 has the most positions
     Carver k;
     PdUnitWs y{};
     y.wf = k.take_floats((size_t)16 * cout * c.cinp);
     y.wd = k.take_floats(pack_elems(c));
-    y.part = k.take_floats(wgrad_part_floats(c, std::max<long>(m.mo, 1)) + wgrad_part_floats(make_conv(cin, cout, 2, 0, 0, 0), std::max<long>(m.mo, 1)));
+    y.part = k.take_floats(part_floats(c, std::max<long>(m.mo, 1)) + part_floats(make_conv(cin, cout, 2, 0, 0, 0), std::max<long>(m.mo, 1)));
     y.dwn = k.take_floats((size_t)cout * cin * 16);
     y.dotp = k.take_bytes(finish_blocks(c) * 8);
     y.chan = k.take_bytes(chan_partial_bytes(cout));
@@ -864,11 +360,11 @@ PdUnitWs unit_ws(int n, int hi, int wi, int cin, int cout) {
 
 // workspace of the head unit, from the cout = 1 conv's own plan
 PdUnitWs head_ws(int n, int hi, int wi, int cin) {
-    const PdConv c = make_conv(cin, 1, 1, 0, 0, 0);
+    const PdLayer c = make_conv(cin, 1, 1, 0, 0, 0);
     Carver k;
     PdUnitWs y{};
     y.wf = k.take_floats((size_t)16 * cin);
-    y.part = k.take_floats(wgrad_part_floats(c, std::max<long>(make_map(n, hi, wi, 1).mo, 1)));
+    y.part = k.take_floats(part_floats(c, std::max<long>(make_map(n, hi, wi, 1).mo, 1)));
     y.dwn = k.take_floats((size_t)cin * 16);
     y.dotp = k.take_bytes(finish_blocks(c) * 8);
     y.chan = k.take_bytes(chan_partial_bytes(1));
@@ -876,11 +372,11 @@ PdUnitWs head_ws(int n, int hi, int wi, int cin) {
     return y;
 }
 
-int pack_unit(const PdConv& c, const float* weight, float* wf, float* wd, hipStream_t st) {
-    PdPackArgs p{};
+int pack_unit(const PdLayer& c, const float* weight, float* wf, float* wd, hipStream_t st) {
+    TcPackArgs p{};
     p.nconv = 1; p.total = (long)pack_elems(c);
-    p.c[0] = PdPackConv{weight, nullptr, wf, wd, c.cout, c.cin, c.cinp, c.cind, 0};
-    return launch_pack(p, st);
+    p.c[0] = TcPackConv{weight, nullptr, wf, wd, c.cout, c.cin, c.cinp, c.cind, 16, 0};
+    return launch_pack<Patch2d>(p, st);
 }
 
 }  // namespace
@@ -906,6 +402,7 @@ int i2v_patchdisc_create(const i2v_patchdisc_cfg* cfg, i2v_patchdisc** out) {
         }
         d->L[k++] = make_conv(c.ndf * mult, 1, 1, 0, 0, 2 + 3 * c.n_layers);
         d->nconv = k;
+        for (int i = 0; i < k; ++i) d->L[i].sn = d->sn;
         return I2V_OK;
     });
 }
@@ -924,7 +421,7 @@ int i2v_patchdisc_bind(i2v_patchdisc* d, const i2v_tensor* params, int32_t n) {
     d->loaded = false;
     const StateDict sd(params, n);
     for (int i = 0; i < d->nconv; ++i) {
-        const PdConv& c = d->L[i];
+        const PdLayer& c = d->L[i];
         const std::string m = "main." + std::to_string(c.key);
         if (!bound_ptr(sd, m + (d->sn ? ".weight_orig" : ".weight"), (int64_t)c.cout * c.cin * 16, &d->w[i]) || !bound_ptr(sd, m + ".bias", c.cout, &d->b[i]))
             return I2V_E_MISSING;
@@ -944,7 +441,7 @@ int i2v_patchdisc_bind_grads(i2v_patchdisc* d, const i2v_tensor* grads, int32_t 
     if (!grads) return I2V_OK;
     const StateDict gd(grads, n);
     for (int i = 0; i < d->nconv; ++i) {
-        const PdConv& c = d->L[i];
+        const PdLayer& c = d->L[i];
         const std::string m = "main." + std::to_string(c.key);
         if (!bound_ptr(gd, m + (d->sn ? ".weight_orig" : ".weight"), (int64_t)c.cout * c.cin * 16, &d->gw[i]) || !bound_ptr(gd, m + ".bias", c.cout, &d->gb[i]))
             return I2V_E_MISSING;
@@ -1000,16 +497,16 @@ int i2v_patchdisc_forward(i2v_patchdisc* d, const float* x, int32_t n, int32_t h
     const int nc = d->nconv;
 
     float* x4 = Carver::at(sv, y.x4);
-    hipLaunchKernelGGL(pd_input4_kernel, dim3(grid_for(y.map[0].mi)), dim3(256), 0, st, x, x4, y.map[0].mi, (long)h * w);
-    PD_LAUNCHED();
+    hipLaunchKernelGGL(tc_input4_kernel, dim3(grid_for(y.map[0].mi)), dim3(256), 0, st, x, x4, y.map[0].mi, (long)h * w);
+    I2V_LAUNCHED();
 
-    PdPackArgs pk{};
+    TcPackArgs pk{};
     pk.nconv = nc;
     if (d->sn) {
         PdPiArgs pi{};
         pi.nconv = nc; pi.iterate = flags & I2V_PATCHDISC_ITERATE ? 1 : 0;
         for (int i = 0; i < nc; ++i) {
-            const PdConv& c = d->L[i];
+            const PdLayer& c = d->L[i];
             pi.c[i] = PdPiConv{d->w[i], d->u[i], d->v[i], Carver::at(sv, y.sigma[i]), Carver::at(sv, y.us[i]), Carver::at(sv, y.vs[i]),
                                Carver::at<double>(workspace, y.pi_t[i]), Carver::at<double>(workspace, y.pi_s[i]), c.cout, c.cin * 16, pi.btotal, pi.rtotal};
             pi.btotal += (c.cin * 16 + 63) / 64; pi.rtotal += c.cout;
@@ -1017,35 +514,35 @@ int i2v_patchdisc_forward(i2v_patchdisc* d, const float* x, int32_t n, int32_t h
         if (int rc = launch_power_iteration(pi, st)) return rc;
     }
     for (int i = 0; i < nc; ++i) {
-        const PdConv& c = d->L[i];
-        pk.c[i] = PdPackConv{d->w[i], d->sn ? Carver::at(sv, y.sigma[i]) : nullptr, Carver::at(sv, y.wf[i]), c.cout == 1 ? nullptr : Carver::at(sv, y.wd[i]),
-                             c.cout, c.cin, c.cinp, c.cind, pk.total};
+        const PdLayer& c = d->L[i];
+        pk.c[i] = TcPackConv{d->w[i], d->sn ? Carver::at(sv, y.sigma[i]) : nullptr, Carver::at(sv, y.wf[i]), c.cout == 1 ? nullptr : Carver::at(sv, y.wd[i]),
+                             c.cout, c.cin, c.cinp, c.cind, 16, pk.total};
         pk.total += (long)pack_elems(c);
     }
-    if (int rc = launch_pack(pk, st)) return rc;
+    if (int rc = launch_pack<Patch2d>(pk, st)) return rc;
 
     const float* in = x4;
     for (int i = 0; i + 1 < nc; ++i) {
-        const PdConv& c = d->L[i];
+        const PdLayer& c = d->L[i];
         float* act = Carver::at(sv, y.act[i]);
         float* pre = c.actnorm && (save || init) ? Carver::at(sv, y.pre[i]) : nullptr;
         if (c.actnorm && init) {
-            if (int rc = launch_conv(c, in, Carver::at(sv, y.wf[i]), d->b[i], nullptr, nullptr, nullptr, pre, n, y.map[i], false, st)) return rc;
+            if (int rc = launch_conv<Patch2d>(c, in, Carver::at(sv, y.wf[i]), nullptr, y.map[i], st, {d->b[i], nullptr, nullptr, pre, false})) return rc;
             hipLaunchKernelGGL(pd_actnorm_init_kernel, dim3(c.cout / 4), dim3(256), 0, st, pre, y.map[i].mo, c.cout, d->loc[i], d->scale[i]);
-            PD_LAUNCHED();
+            I2V_LAUNCHED();
             const long total = y.map[i].mo * c.cout;
             hipLaunchKernelGGL(pd_actnorm_apply_kernel, dim3(grid_for(total)), dim3(256), 0, st, pre, d->loc[i], d->scale[i], act, total, c.cout);
-            PD_LAUNCHED();
-        } else if (int rc = launch_conv(c, in, Carver::at(sv, y.wf[i]), d->b[i], c.actnorm ? d->loc[i] : nullptr, c.actnorm ? d->scale[i] : nullptr, act,
-                                        pre, n, y.map[i], c.lrelu, st)) {
+            I2V_LAUNCHED();
+        } else if (int rc = launch_conv<Patch2d>(c, in, Carver::at(sv, y.wf[i]), act, y.map[i], st,
+                                                 {d->b[i], c.actnorm ? d->loc[i] : nullptr, c.actnorm ? d->scale[i] : nullptr, pre, c.lrelu != 0})) {
             return rc;
         }
         in = act;
     }
-    const PdMap& hm = y.map[nc - 1];
+    const TcGeo& hm = y.map[nc - 1];
     hipLaunchKernelGGL(pd_head_fwd_kernel, dim3((unsigned)((hm.mo + 3) / 4)), dim3(256), 0, st, in, Carver::at(sv, y.wf[nc - 1]), d->b[nc - 1], pred, hm.mo,
                        hm.hi, hm.wi, d->L[nc - 1].cin);
-    PD_LAUNCHED();
+    I2V_LAUNCHED();
     return I2V_OK;
 }
 
@@ -1078,20 +575,20 @@ int i2v_patchdisc_backward(i2v_patchdisc* d, const float* d_pred, const void* sa
     // the head
     {
         const int i = nc - 1;
-        const PdConv& c = d->L[i];
+        const PdLayer& c = d->L[i];
         const float* xin = Carver::at(sv, y.act[i - 1]);
         if (param_grads) {
             if (int rc = launch_chan_grads(d_pred, nullptr, nullptr, nullptr, nullptr, d->gb[i], nullptr, nullptr, chan, y.map[i].mo, 1, acc, st)) return rc;
             snap(i, &us, &vs, &sg);
-            if (int rc = launch_wgrad(c, d_pred, nullptr, nullptr, xin, d->w[i], us, vs, sg, part, dwn, dotp, d->gw[i], acc, y.map[i], st)) return rc;
+            if (int rc = launch_head_wgrad(c, d_pred, xin, d->w[i], us, vs, sg, part, dwn, dotp, d->gw[i], acc, y.map[i], st)) return rc;
         }
         const long total = y.map[i].mi * c.cin;
         hipLaunchKernelGGL(pd_head_dgrad_kernel, dim3(grid_for(total)), dim3(256), 0, st, d_pred, Carver::at(sv, y.wf[i]), ga, total, y.map[i].hi, y.map[i].wi,
                            c.cin);
-        PD_LAUNCHED();
+        I2V_LAUNCHED();
     }
     for (int i = nc - 2; i >= 0; --i) {
-        const PdConv& c = d->L[i];
+        const PdLayer& c = d->L[i];
         const float* act = Carver::at(sv, y.act[i]);
         const float* scale = c.actnorm ? d->scale[i] : nullptr;
         const float* xin = i == 0 ? Carver::at(sv, y.x4) : Carver::at(sv, y.act[i - 1]);
@@ -1100,10 +597,11 @@ int i2v_patchdisc_backward(i2v_patchdisc* d, const float* d_pred, const void* sa
                                            d->gloc[i], d->gscale[i], chan, y.map[i].mo, c.cout, acc, st))
                 return rc;
             snap(i, &us, &vs, &sg);
-            if (int rc = launch_wgrad(c, ga, act, scale, xin, d->w[i], us, vs, sg, part, dwn, dotp, d->gw[i], acc, y.map[i], st)) return rc;
+            if (int rc = launch_wgrad<Patch2d>(c, ga, act, scale, xin, d->w[i], us, vs, sg, part, dwn, dotp, d->gw[i], acc, y.map[i], st)) return rc;
         }
         if (i == 0 && !d_x) break;
-        if (int rc = launch_dgrad(c, ga, act, scale, Carver::at(sv, y.wd[i]), i == 0 ? d_x : gb, i == 0, n, y.map[i], st)) return rc;
+        if (int rc = launch_dgrad<Patch2d>(c, ga, act, scale, Carver::at(sv, y.wd[i]), nullptr, nullptr, i == 0 ? d_x : gb, i == 0, n, y.map[i], st))
+            return rc;
         std::swap(ga, gb);
     }
     return I2V_OK;
@@ -1113,14 +611,15 @@ int i2v_patchdisc_hinge(const float* fake, const float* real, int64_t numel, int
     I2V_REQUIRE(fake && out && numel > 0 && (mode == I2V_HINGE_GEN || (mode == I2V_HINGE_DISC && real)), I2V_E_INVALID,
                 "i2v_patchdisc_hinge: null argument, numel %lld or mode %d", (long long)numel, mode);
     hipLaunchKernelGGL(pd_hinge_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), fake, real, (long)numel, mode, out, d_fake, d_real);
-    PD_LAUNCHED();
+    I2V_LAUNCHED();
     return I2V_OK;
 }
 
 int i2v_patchdisc_wgrad_plan(int32_t cout, int32_t cin, int64_t positions, int32_t* slices, int32_t* slice_len) {
     I2V_REQUIRE(slices && slice_len && positions > 0 && (cout == 1 || (cout > 0 && cout % 16 == 0)) && (cin == 3 || (cin > 0 && cin % 16 == 0)), I2V_E_INVALID,
                 "i2v_patchdisc_wgrad_plan: cout %d, cin %d, %lld positions", cout, cin, (long long)positions);
-    pd_wgrad_plan(cout, cin, positions, slices, slice_len);
+    if (cout == 1) head_wgrad_plan(positions, slices, slice_len);
+    else wgrad_plan(cout, cin, 16, positions, slices, slice_len);
     return I2V_OK;
 }
 
@@ -1138,9 +637,9 @@ int i2v_patchdisc_conv_unit(const float* x, const float* weight, const float* bi
     const PdUnitWs k = unit_ws(n, hi, wi, cin, cout);
     I2V_REQUIRE_WORKSPACE(workspace_bytes, k.total, what);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const PdConv c = make_conv(cin, cout, stride, loc != nullptr, lrelu, 0);
+    const PdLayer c = make_conv(cin, cout, stride, loc != nullptr, lrelu, 0);
     if (int rc = pack_unit(c, weight, Carver::at(workspace, k.wf), nullptr, st)) return rc;
-    return launch_conv(c, x, Carver::at(workspace, k.wf), bias, loc, scale, out, pre, n, make_map(n, hi, wi, stride), lrelu != 0, st);
+    return launch_conv<Patch2d>(c, x, Carver::at(workspace, k.wf), out, make_map(n, hi, wi, stride), st, {bias, loc, scale, pre, lrelu != 0});
 }
 
 int i2v_patchdisc_dgrad_unit(const float* g, const float* weight, const float* act, const float* scale, int32_t n, int32_t hi, int32_t wi, int32_t cin,
@@ -1151,9 +650,9 @@ int i2v_patchdisc_dgrad_unit(const float* g, const float* weight, const float* a
     const PdUnitWs k = unit_ws(n, hi, wi, cin, cout);
     I2V_REQUIRE_WORKSPACE(workspace_bytes, k.total, what);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const PdConv c = make_conv(cin, cout, stride, 0, 0, 0);
+    const PdLayer c = make_conv(cin, cout, stride, 0, 0, 0);
     if (int rc = pack_unit(c, weight, Carver::at(workspace, k.wf), Carver::at(workspace, k.wd), st)) return rc;
-    return launch_dgrad(c, g, act, scale, Carver::at(workspace, k.wd), out, frames_out != 0, n, make_map(n, hi, wi, stride), st);
+    return launch_dgrad<Patch2d>(c, g, act, scale, Carver::at(workspace, k.wd), nullptr, nullptr, out, frames_out != 0, n, make_map(n, hi, wi, stride), st);
 }
 
 int i2v_patchdisc_wgrad_unit(const float* g, const float* act, const float* scale, const float* x, const float* weight, const float* u, const float* v,
@@ -1165,11 +664,11 @@ int i2v_patchdisc_wgrad_unit(const float* g, const float* act, const float* scal
     const PdUnitWs k = unit_ws(n, hi, wi, cin, cout);
     I2V_REQUIRE_WORKSPACE(workspace_bytes, k.total, what);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const PdConv c = make_conv(cin, cout, stride, 0, 0, 0);
-    const PdMap mp = make_map(n, hi, wi, stride);
+    const PdLayer c = make_conv(cin, cout, stride, 0, 0, 0);
+    const TcGeo mp = make_map(n, hi, wi, stride);
     if (int rc = launch_chan_grads(g, act, nullptr, nullptr, scale, dbias, nullptr, nullptr, Carver::at<double>(workspace, k.chan), mp.mo, cout, accumulate != 0, st)) return rc;
-    return launch_wgrad(c, g, act, scale, x, weight, u, v, sigma, Carver::at(workspace, k.part), Carver::at(workspace, k.dwn),
-                        Carver::at<double>(workspace, k.dotp), dweight, accumulate != 0, mp, st);
+    return launch_wgrad<Patch2d>(c, g, act, scale, x, weight, u, v, sigma, Carver::at(workspace, k.part), Carver::at(workspace, k.dwn),
+                                 Carver::at<double>(workspace, k.dotp), dweight, accumulate != 0, mp, st);
 }
 
 int i2v_patchdisc_head_unit(const float* x, const float* weight, const float* bias, const float* g, int32_t n, int32_t hi, int32_t wi, int32_t cin,
@@ -1180,20 +679,20 @@ int i2v_patchdisc_head_unit(const float* x, const float* weight, const float* bi
     const PdUnitWs k = head_ws(n, hi, wi, cin);
     I2V_REQUIRE_WORKSPACE(workspace_bytes, k.total, what);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const PdConv c = make_conv(cin, 1, 1, 0, 0, 0);
-    const PdMap mp = make_map(n, hi, wi, 1);
+    const PdLayer c = make_conv(cin, 1, 1, 0, 0, 0);
+    const TcGeo mp = make_map(n, hi, wi, 1);
     float* wf = Carver::at(workspace, k.wf);
     if (int rc = pack_unit(c, weight, wf, nullptr, st)) return rc;
     hipLaunchKernelGGL(pd_head_fwd_kernel, dim3((unsigned)((mp.mo + 3) / 4)), dim3(256), 0, st, x, wf, bias, out, mp.mo, hi, wi, cin);
-    PD_LAUNCHED();
+    I2V_LAUNCHED();
     if (!g) return I2V_OK;
     if (int rc = launch_chan_grads(g, nullptr, nullptr, nullptr, nullptr, dbias, nullptr, nullptr, Carver::at<double>(workspace, k.chan), mp.mo, 1, false, st)) return rc;
-    if (int rc = launch_wgrad(c, g, nullptr, nullptr, x, weight, nullptr, nullptr, nullptr, Carver::at(workspace, k.part), Carver::at(workspace, k.dwn),
-                              Carver::at<double>(workspace, k.dotp), dweight, false, mp, st))
+    if (int rc = launch_head_wgrad(c, g, x, weight, nullptr, nullptr, nullptr, Carver::at(workspace, k.part), Carver::at(workspace, k.dwn),
+                                   Carver::at<double>(workspace, k.dotp), dweight, false, mp, st))
         return rc;
     const long total = mp.mi * cin;
     hipLaunchKernelGGL(pd_head_dgrad_kernel, dim3(grid_for(total)), dim3(256), 0, st, g, wf, dx, total, hi, wi, cin);
-    PD_LAUNCHED();
+    I2V_LAUNCHED();
     return I2V_OK;
 }
 
@@ -1214,7 +713,7 @@ int i2v_patchdisc_actnorm_init_unit(const float* pre, int64_t m, int32_t c, floa
     I2V_REQUIRE(pre && loc && scale && m > 1 && c > 0 && c % 4 == 0, I2V_E_INVALID, "i2v_patchdisc_actnorm_init_unit: null argument, %lld rows or %d channels",
                 (long long)m, c);
     hipLaunchKernelGGL(pd_actnorm_init_kernel, dim3(c / 4), dim3(256), 0, static_cast<hipStream_t>(stream), pre, (long)m, c, loc, scale);
-    PD_LAUNCHED();
+    I2V_LAUNCHED();
     return I2V_OK;
 }
 

@@ -95,18 +95,18 @@ __global__ __launch_bounds__(256) void pd_pi_sigma_kernel(PdPiArgs a) {
     if (tid == 0) *c.sigma = (float)sg;
 }
 
-#define PD_LAUNCHED() I2V_HIP_CHECK(hipGetLastError())
+#define I2V_LAUNCHED() I2V_HIP_CHECK(hipGetLastError())
 
 // the three launches of the spectral norm over the convs of `a` (all of them in one go)
 int launch_power_iteration(const PdPiArgs& a, hipStream_t st) {
     if (a.iterate) {
         hipLaunchKernelGGL(pd_pi_wtu_kernel, dim3(a.btotal), dim3(256), 0, st, a);
-        PD_LAUNCHED();
+        I2V_LAUNCHED();
     }
     hipLaunchKernelGGL(pd_pi_wv_kernel, dim3(a.rtotal), dim3(256), 0, st, a);
-    PD_LAUNCHED();
+    I2V_LAUNCHED();
     hipLaunchKernelGGL(pd_pi_sigma_kernel, dim3(a.nconv), dim3(256), 0, st, a);
-    PD_LAUNCHED();
+    I2V_LAUNCHED();
     return I2V_OK;
 }
 

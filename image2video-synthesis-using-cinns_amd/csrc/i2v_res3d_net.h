@@ -14,7 +14,7 @@ struct R3Block { int c1, c2, cd, in; };   // conv indices (cd -1: no downsample 
 
 struct R3Trunk {
     int nconv = 0, pool = 0;
-    D3Conv L[D3_MAXCONV];
+    TcConv L[D3_MAXCONV];
     std::string wkey[D3_MAXCONV], nkey[D3_MAXCONV];   // state-dict prefixes of the conv and of its GroupNorm
     R3Block B[8];
     float *w[D3_MAXCONV] = {}, *u[D3_MAXCONV] = {}, *v[D3_MAXCONV] = {}, *nw[D3_MAXCONV] = {}, *nb[D3_MAXCONV] = {};
@@ -33,7 +33,7 @@ struct R3Rules {
 void r3_build(R3Trunk& k, const int32_t* channels, const int32_t* stride_s, const int32_t* stride_t, const R3Rules& r) {
     k.pool = r.pool;
     int n = 0;
-    auto add = [&](const D3Conv& c, const std::string& conv, const std::string& norm) {
+    auto add = [&](const TcConv& c, const std::string& conv, const std::string& norm) {
         k.L[n] = c; k.wkey[n] = conv; k.nkey[n] = norm;
         return n++;
     };
@@ -70,7 +70,7 @@ bool bound_ptr(const StateDict& s, const std::string& key, int64_t numel, float*
 // the trunk's keys; the callers bind their head's afterwards
 int r3_bind(R3Trunk& k, const StateDict& sd) {
     for (int i = 0; i < k.nconv; ++i) {
-        const D3Conv& c = k.L[i];
+        const TcConv& c = k.L[i];
         const int64_t wn = (int64_t)c.cout * c.cin * ntap_of(c);
         if (!bound_ptr(sd, k.wkey[i] + (c.sn ? ".weight_orig" : ".weight"), wn, &k.w[i])) return I2V_E_MISSING;
         if (c.sn && (!bound_ptr(sd, k.wkey[i] + ".weight_u", c.cout, &k.u[i]) || !bound_ptr(sd, k.wkey[i] + ".weight_v", wn / c.cout, &k.v[i])))
@@ -82,7 +82,7 @@ int r3_bind(R3Trunk& k, const StateDict& sd) {
 
 int r3_bind_grads(R3Trunk& k, const StateDict& gd) {
     for (int i = 0; i < k.nconv; ++i) {
-        const D3Conv& c = k.L[i];
+        const TcConv& c = k.L[i];
         if (!bound_ptr(gd, k.wkey[i] + (c.sn ? ".weight_orig" : ".weight"), (int64_t)c.cout * c.cin * ntap_of(c), &k.gw[i])) return I2V_E_MISSING;
         if (!bound_ptr(gd, k.nkey[i] + ".weight", c.cout, &k.gnw[i]) || !bound_ptr(gd, k.nkey[i] + ".bias", c.cout, &k.gnb[i])) return I2V_E_MISSING;
     }
@@ -98,7 +98,7 @@ struct R3Layout {
     bool ok = false;
     char why[160] = "";
     int n = 0;
-    D3Geo geo[D3_MAXCONV];
+    TcGeo geo[D3_MAXCONV];
     int pt = 0, ph = 0, pw = 0, pho = 0, pwo = 0;   // the pool's input and output map
     long pool_in = 0, pool_out = 0;                 // positions
     size_t x4 = 0, pre[D3_MAXCONV] = {}, act[D3_MAXCONV] = {}, stats[D3_MAXCONV] = {}, wf[D3_MAXCONV] = {}, wd[D3_MAXCONV] = {}, sigma[D3_MAXCONV] = {},
@@ -138,7 +138,7 @@ R3Layout r3_layout(const R3Trunk& d, int n, int t, int h, int w, const R3Extra& 
     y.x4 = s.take_floats((size_t)y.geo[0].mi * 4);
     size_t gmax = 0, pmax = 0, emax = 0, bmax = 0, cmax = 0;
     for (int i = 0; i < d.nconv; ++i) {
-        const D3Conv& c = d.L[i];
+        const TcConv& c = d.L[i];
         const size_t elems = (size_t)y.geo[i].mo * c.cout;
         y.pre[i] = s.take_floats(elems);
         y.act[i] = s.take_floats(elems);
@@ -208,14 +208,14 @@ int r3_forward(const R3Trunk& d, const R3Layout& y, const float* x, bool iterate
     const int nc = d.nconv, n = y.n;
 
     float* x4 = Carver::at(sv, y.x4);
-    hipLaunchKernelGGL(d3_input4_kernel, dim3(grid_for(y.geo[0].mi)), dim3(256), 0, st, x, x4, y.geo[0].mi, y.geo[0].mi / n);
-    PD_LAUNCHED();
+    hipLaunchKernelGGL(tc_input4_kernel, dim3(grid_for(y.geo[0].mi)), dim3(256), 0, st, x, x4, y.geo[0].mi, y.geo[0].mi / n);
+    I2V_LAUNCHED();
 
     // spectral norm, PD_MAXCONV convs per group of launches
     PdPiArgs pi{};
     pi.iterate = iterate ? 1 : 0;
     for (int i = 0; i < nc; ++i) {
-        const D3Conv& c = d.L[i];
+        const TcConv& c = d.L[i];
         if (c.sn) {
             const int cols = c.cin * ntap_of(c);
             pi.c[pi.nconv++] = PdPiConv{d.w[i], d.u[i], d.v[i], Carver::at(sv, y.sigma[i]), Carver::at(sv, y.us[i]), Carver::at(sv, y.vs[i]),
@@ -227,22 +227,21 @@ int r3_forward(const R3Trunk& d, const R3Layout& y, const float* x, bool iterate
             pi.nconv = pi.btotal = pi.rtotal = 0;
         }
     }
-    D3PackArgs pk{};
+    TcPackArgs pk{};
     pk.nconv = nc;
     for (int i = 0; i < nc; ++i) {
-        const D3Conv& c = d.L[i];
-        pk.c[i] = D3PackConv{d.w[i], c.sn ? Carver::at(sv, y.sigma[i]) : nullptr, Carver::at(sv, y.wf[i]), Carver::at(sv, y.wd[i]),
+        const TcConv& c = d.L[i];
+        pk.c[i] = TcPackConv{d.w[i], c.sn ? Carver::at(sv, y.sigma[i]) : nullptr, Carver::at(sv, y.wf[i]), Carver::at(sv, y.wd[i]),
                              c.cout, c.cin, c.cinp, c.cind, ntap_of(c), pk.total};
         pk.total += (long)pack_elems(c);
     }
-    hipLaunchKernelGGL(d3_pack_kernel, dim3(grid_for(pk.total)), dim3(256), 0, st, pk);
-    PD_LAUNCHED();
+    if (int rc = launch_pack<Trunk3d>(pk, st)) return rc;
 
     // conv i on `in`, then its GroupNorm (+ res) (ReLU) -> act[i]
     auto conv_gn = [&](int i, const float* in, const float* res, bool relu) -> int {
-        const D3Conv& c = d.L[i];
+        const TcConv& c = d.L[i];
         float* pre = Carver::at(sv, y.pre[i]);
-        if (int rc = launch_conv(c, in, Carver::at(sv, y.wf[i]), pre, y.geo[i], st)) return rc;
+        if (int rc = launch_conv<Trunk3d>(c, in, Carver::at(sv, y.wf[i]), pre, y.geo[i], st)) return rc;
         return launch_gn(pre, res, d.nw[i], d.nb[i], n, y.geo[i].mo / n, c.cout, relu, Carver::at(sv, y.act[i]), Carver::at<double>(sv, y.stats[i]),
                          gnws, st);
     };
@@ -251,7 +250,7 @@ int r3_forward(const R3Trunk& d, const R3Layout& y, const float* x, bool iterate
         const long total = y.pool_out * d.L[0].cout;
         hipLaunchKernelGGL(d3_maxpool_kernel, dim3(grid_for(total)), dim3(256), 0, st, Carver::at(sv, y.act[0]), Carver::at(sv, y.pout),
                            Carver::at<int>(sv, y.parg), total, y.pt, y.ph, y.pw, y.pho, y.pwo, d.L[0].cout);
-        PD_LAUNCHED();
+        I2V_LAUNCHED();
     }
     for (int b = 0; b < 8; ++b) {
         const R3Block& k = d.B[b];
@@ -288,12 +287,12 @@ int r3_backward(const R3Trunk& d, const R3Layout& y, const float* const* d_fmaps
 
     // GroupNorm of conv i backwards: g (masked by `mask`) -> dc; then the conv's weight gradient
     auto norm_conv_bwd = [&](int i, const float* g, const float* mask, const float* xin, float* dc) -> int {
-        const D3Conv& c = d.L[i];
+        const TcConv& c = d.L[i];
         if (int rc = launch_gn_bwd(g, mask, Carver::at(sv, y.pre[i]), Carver::at<double>(sv, y.stats[i]), d.nw[i], n, y.geo[i].mo / n, c.cout, dc,
                                    pg ? d.gnw[i] : nullptr, pg ? d.gnb[i] : nullptr, acc, gnws, st))
             return rc;
         if (!pg) return I2V_OK;
-        return launch_wgrad(c, dc, nullptr, xin, d.w[i], c.sn ? Carver::at(sv, y.us[i]) : nullptr, c.sn ? Carver::at(sv, y.vs[i]) : nullptr,
+        return launch_wgrad<Trunk3d>(c, dc, nullptr, nullptr, xin, d.w[i], c.sn ? Carver::at(sv, y.us[i]) : nullptr, c.sn ? Carver::at(sv, y.vs[i]) : nullptr,
                             c.sn ? Carver::at(sv, y.sigma[i]) : nullptr, part, dwn, dotp, d.gw[i], acc, y.geo[i], st);
     };
     for (int b = 7; b >= 0; --b) {
@@ -301,19 +300,19 @@ int r3_backward(const R3Trunk& d, const R3Layout& y, const float* const* d_fmaps
         if ((b & 1) && d_fmaps && d_fmaps[b / 2]) {   // G is at the activation behind layer b / 2
             const long elems = y.geo[k.c2].mo * d.L[k.c2].cout;
             hipLaunchKernelGGL(d3_add_kernel, dim3(grid_for(elems)), dim3(256), 0, st, G, d_fmaps[b / 2], elems);
-            PD_LAUNCHED();
+            I2V_LAUNCHED();
         }
         const float* out = Carver::at(sv, y.act[k.c2]);
         const float* xin = k.in < 0 ? Carver::at(sv, y.pout) : Carver::at(sv, y.act[k.in]);
         const float* h1 = Carver::at(sv, y.act[k.c1]);
         if (int rc = norm_conv_bwd(k.c2, G, out, h1, DC)) return rc;
-        if (int rc = launch_dgrad(d.L[k.c2], DC, nullptr, Carver::at(sv, y.wd[k.c2]), nullptr, nullptr, H1, false, n, y.geo[k.c2], st)) return rc;
+        if (int rc = launch_dgrad<Trunk3d>(d.L[k.c2], DC, nullptr, nullptr, Carver::at(sv, y.wd[k.c2]), nullptr, nullptr, H1, false, n, y.geo[k.c2], st)) return rc;
         if (int rc = norm_conv_bwd(k.c1, H1, h1, xin, DC)) return rc;
         if (k.cd >= 0) {
             if (int rc = norm_conv_bwd(k.cd, G, out, xin, DC2)) return rc;
-            if (int rc = launch_dgrad(d.L[k.cd], DC2, nullptr, Carver::at(sv, y.wd[k.cd]), nullptr, nullptr, X2, false, n, y.geo[k.cd], st)) return rc;
-            if (int rc = launch_dgrad(d.L[k.c1], DC, nullptr, Carver::at(sv, y.wd[k.c1]), X2, nullptr, Gn, false, n, y.geo[k.c1], st)) return rc;
-        } else if (int rc = launch_dgrad(d.L[k.c1], DC, nullptr, Carver::at(sv, y.wd[k.c1]), G, out, Gn, false, n, y.geo[k.c1], st)) {
+            if (int rc = launch_dgrad<Trunk3d>(d.L[k.cd], DC2, nullptr, nullptr, Carver::at(sv, y.wd[k.cd]), nullptr, nullptr, X2, false, n, y.geo[k.cd], st)) return rc;
+            if (int rc = launch_dgrad<Trunk3d>(d.L[k.c1], DC, nullptr, nullptr, Carver::at(sv, y.wd[k.c1]), X2, nullptr, Gn, false, n, y.geo[k.c1], st)) return rc;
+        } else if (int rc = launch_dgrad<Trunk3d>(d.L[k.c1], DC, nullptr, nullptr, Carver::at(sv, y.wd[k.c1]), G, out, Gn, false, n, y.geo[k.c1], st)) {
             return rc;
         }
         std::swap(G, Gn);
@@ -323,12 +322,12 @@ int r3_backward(const R3Trunk& d, const R3Layout& y, const float* const* d_fmaps
         const long total = y.pool_in * d.L[0].cout;
         hipLaunchKernelGGL(d3_maxpool_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, st, G, Carver::at<int>(sv, y.parg), Gn, total, y.pt, y.ph, y.pw,
                            y.pho, y.pwo, d.L[0].cout);
-        PD_LAUNCHED();
+        I2V_LAUNCHED();
         std::swap(G, Gn);
     }
     if (int rc = norm_conv_bwd(0, G, Carver::at(sv, y.act[0]), Carver::at(sv, y.x4), DC)) return rc;
     if (d_x)
-        if (int rc = launch_dgrad(d.L[0], DC, nullptr, Carver::at(sv, y.wd[0]), nullptr, nullptr, d_x, true, n, y.geo[0], st)) return rc;
+        if (int rc = launch_dgrad<Trunk3d>(d.L[0], DC, nullptr, nullptr, Carver::at(sv, y.wd[0]), nullptr, nullptr, d_x, true, n, y.geo[0], st)) return rc;
     return I2V_OK;
 }
 

@@ -350,7 +350,7 @@ def bn_of(c):
 
 
 def wgrad_plan(cout, cin, ntap, rows):
-    """(slices, slice length) of the trunk's weight gradient: csrc/i2v_res3d_trunk.h d3_wgrad_plan."""
+    """(slices, slice length) of the trunk's weight gradient: csrc/i2v_train_conv.h wgrad_plan."""
     CP = -(-(4 if cin == 3 else cin) // 16) * 16
     tiles = ntap * (cout // bn_of(cout)) * (CP // bn_of(CP))
     S = min(max(-(-1024 // tiles), 1), max(-(-rows // 64), 1))

@@ -266,7 +266,7 @@ def big_cases():
 
 
 def rows_per_workgroup(rows, column_tiles):
-    """The tile choice of the two GEMM kernels (csrc/i2v_patchdisc.hip, rows_of), restated so that the tests can say which they ran."""
+    """The tile choice of the two GEMM kernels (csrc/i2v_train_conv.h, rows_of), restated so that the tests can say which they ran."""
     return 128 if (rows + 127) // 128 * column_tiles >= 512 else 64
 
 

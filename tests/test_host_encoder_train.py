@@ -129,14 +129,20 @@ def test_sources_are_built_share_the_trunk_and_read_no_environment():
     mk = open(os.path.join(PKG, "csrc", "Makefile")).read()
     assert "i2v_encoder_train.hip" in mk.split("SRCS =")[1].splitlines()[0]
     hdrs = mk.split("HDRS =")[1].splitlines()[0].split()
-    assert "../../include/i2v_hip_enc3d_train.h" in hdrs and "i2v_res3d_trunk.h" in hdrs
+    assert "../../include/i2v_hip_enc3d_train.h" in hdrs and "i2v_res3d_trunk.h" in hdrs and "i2v_train_conv.h" in hdrs
     enc = open(os.path.join(PKG, "csrc", "i2v_encoder_train.hip")).read()
     disc = open(os.path.join(PKG, "csrc", "i2v_disc3d.hip")).read()
     trunk = open(os.path.join(PKG, "csrc", "i2v_res3d_trunk.h")).read()
-    for src in (enc, trunk):
+    conv = open(os.path.join(PKG, "csrc", "i2v_train_conv.h")).read()
+    patch = open(os.path.join(PKG, "csrc", "i2v_patchdisc.hip")).read()
+    for src in (enc, trunk, conv):
         assert "getenv" not in src and "atomic" not in src.lower()
-    assert '#include "i2v_res3d_trunk.h"' in enc and '#include "i2v_res3d_trunk.h"' in disc
-    for kernel in ("d3_conv_kernel", "d3_dgrad_kernel", "d3_wgrad_kernel", "d3_gn_bwd_dx_kernel"):      # one definition, in the shared header
+    assert '#include "i2v_res3d_trunk.h"' in enc and '#include "i2v_res3d_trunk.h"' in disc and '#include "i2v_train_conv.h"' in trunk
+    for kernel in ("conv_kernel", "dgrad_kernel", "wgrad_kernel"):      # one definition, in the header shared with the patch discriminator
+        assert conv.count(f"void tc_{kernel}(") == 1
+        for src in (patch, trunk, disc, enc):
+            assert not any(f"void {family}_{kernel}(" in src for family in ("tc", "d3", "pd")) and "a_lds" not in src
+    for kernel in ("d3_gn_bwd_dx_kernel",):                             # one definition, in the trunk's header
         assert f"void {kernel}(" in trunk and f"void {kernel}(" not in disc and f"void {kernel}(" not in enc
     assert "mfma_f32_16x16x4f32" in enc
     # the plan, the layout and the two walks exist once, in i2v_res3d_net.h
@@ -147,10 +153,13 @@ def test_sources_are_built_share_the_trunk_and_read_no_environment():
     for src in (enc, disc):
         for gone in ("struct D3Block", "struct E3Block", "D3Layout", "E3Layout", "e3_bound", "e3_refuse"):
             assert gone not in src, gone
-    for launcher in ("launch_conv(", "launch_dgrad(", "launch_gn_bwd(", "launch_wgrad("):     # the discriminator's: its unit entry
+    for launcher in ("launch_conv<Trunk3d>(", "launch_dgrad<Trunk3d>(", "launch_gn_bwd(", "launch_wgrad<Trunk3d>("):     # the discriminator's: its unit entry
         assert disc.count(launcher) == 1 and enc.count(launcher) == 0 and net.count(launcher) >= 1, launcher
-    assert net.count("hipLaunchKernelGGL(d3_pack_kernel") == 1 and "d3_pack_kernel" not in enc
-    assert disc.count("d3_pack_kernel") == 1 and "d3_pack_kernel" in disc[disc.index("int pack_unit("):disc.index("}  // namespace", disc.index("int pack_unit("))]
+    assert conv.count("hipLaunchKernelGGL((tc_pack_kernel<") == 1 and conv.count("void tc_pack_kernel(") == 1
+    assert net.count("launch_pack<") == 1 and "launch_pack<" not in enc and "pack_kernel" not in enc + net + disc + patch
+    assert disc.count("launch_pack<") == 1 and patch.count("launch_pack<") == 2      # (the patch discriminator's forward packs its own network)
+    for src in (disc, patch):
+        assert "launch_pack<" in src[src.index("int pack_unit("):src.index("}  // namespace", src.index("int pack_unit("))]
     assert "void d3_maxpool_kernel(" in trunk and "void d3_maxpool_kernel(" not in disc and "void d3_maxpool_kernel(" not in enc
 
 

@@ -82,7 +82,7 @@ def test_makefile_lists_the_source_and_the_header():
     mk = open(os.path.join(PKG, "csrc", "Makefile")).read()
     assert "i2v_gblock_train.hip" in mk.split("SRCS =")[1].splitlines()[0].split()
     hdrs = mk.split("HDRS =")[1].splitlines()[0].split()
-    assert "../../include/i2v_hip_gblock_train.h" in hdrs and "i2v_res3d_trunk.h" in hdrs and "i2v_power_iter.h" in hdrs
+    assert "../../include/i2v_hip_gblock_train.h" in hdrs and "i2v_res3d_trunk.h" in hdrs and "i2v_train_conv.h" in hdrs and "i2v_power_iter.h" in hdrs
 
 
 @pytest.mark.parametrize("tag", sorted(gc.FIXTURES))

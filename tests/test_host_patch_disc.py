@@ -251,10 +251,14 @@ def test_disc_header_matches_the_second_table_and_the_first_is_untouched():
 def test_source_is_built_and_reads_no_environment():
     mk = open(os.path.join(PKG, "csrc", "Makefile")).read()
     assert "i2v_patchdisc.hip" in mk.split("SRCS =")[1].splitlines()[0]
-    assert "../../include/i2v_hip_disc.h" in mk.split("HDRS =")[1].splitlines()[0].split()
+    hdrs = mk.split("HDRS =")[1].splitlines()[0].split()
+    assert "../../include/i2v_hip_disc.h" in hdrs and "i2v_train_conv.h" in hdrs
     src = open(os.path.join(PKG, "csrc", "i2v_patchdisc.hip")).read()
-    assert "getenv" not in src and "atomic" not in src.lower()
-    assert "mfma_f32_16x16x4f32" in src
+    conv = open(os.path.join(PKG, "csrc", "i2v_train_conv.h")).read()
+    for text in (src, conv):
+        assert "getenv" not in text and "atomic" not in text.lower()
+    assert '#include "i2v_train_conv.h"' in src and "mfma_f32_16x16x4f32" in conv
+    assert "a_lds" not in src and "a_lds" in conv      # the staged-GEMM loop is the shared header's
 
 
 def test_refusals_need_no_gpu():
