@@ -39,8 +39,7 @@
 // TH = 16 -- every such launch of the shipped configs) run conv_wino4e_f16x3_kernel (i2v_conv16w4e.hip, plan form W4_EDGE): the same
 // template with the (kt, row block) units that read only the clip's temporal zero padding left out of the tap loops at compile time
 // (w4_unit_dead, i2v_conv16w4_edge.h).  Same bits.  The instantiations of this file remain the kernels of every other case -- the 2-D
-// convs, the 256-thread thin layers, the persistent forms -- and, in the measurement build, the A/B and bit reference of the edge
-// kernel (I2V_W4_TSKIP=0).
+// convs, the 256-thread thin layers -- and, in the measurement build, the A/B and bit reference of the edge kernel (I2V_W4_TSKIP=0).
 #include "i2v_conv16w4_dev.h"
 
 namespace i2v {
@@ -71,28 +70,19 @@ int Wino4Weights::pack_tdup(const float* w_src, const float* bias_src, int cout,
     return wino4_store(*this, wino_pack(one_ ? WINO_F43_ONE : WINO_F43, w_src, cout, cin, scale, 3, true), bias_src, cout, cin, 2, true, one_);
 }
 
-// Measurement switches of this kernel.  The PRODUCTION library (no -DI2V_MEASURE) reads no environment variable on a launch path
-// and carries only the one-workgroup-per-brick kernels; the structure switches -- the software-pipelined persistent kernels
-// (I2V_W4_PIPE), the start skew of their workgroups (I2V_W4_SKEW), forced tile widths / workgroup sizes (I2V_W4_BN, I2V_W4_NTH),
-// the brick -> XCD order (I2V_W4_ORDER) and the launch trace (I2V_W4_TRACE) -- exist in the measurement build only
-// (tools/build_measurement_libs.sh measure -> tools/_tl/libi2v_hip_measure.so, loaded through I2V_LIB_PATH; tools/conv16w_check*
-// are built with the flag too), where they are read per launch so that tests and A/B runs can flip them inside one process.
+// Measurement switches of this kernel.  The PRODUCTION library (no -DI2V_MEASURE) reads no environment variable on a launch path;
+// the structure switches -- forced tile widths / workgroup sizes (I2V_W4_BN, I2V_W4_NTH), the brick -> XCD order (I2V_W4_ORDER), the
+// full tap loops instead of the edge form (I2V_W4_TSKIP) and the launch trace (I2V_W4_TRACE) -- exist in the measurement build only
+// (make measure -> lib/libi2v_hip_measure.so, loaded through I2V_LIB_PATH; tools/conv16w_check* are built with the flag too), where
+// they are read per launch so that tests and A/B runs can flip them inside one process.  They choose among the kernels that ship.
 // The one-term form has no structure switches: it always runs the defaults (but for I2V_W4_TSKIP and the trace).
-// 32-channel 3x3x3 layers with the V requests issued by four extra waves (i2v_conv16w4g.hip, MODE 2; I2V_W4_LOADER=1 in the measurement
-// build).  Measured neutral to negative (profiles/r06_e_thin_loader_ab.txt: 32 -> 32 0.380 vs 0.384 ms, 64 -> 32 0.561 vs 0.545 ms at B = 8;
-// 1.33 vs 1.31-1.33 and 2.05 vs 1.93-1.97 ms at B = 32): what the thin layers' tap loops gain without ANY operand traffic (-21 % / -34 %) is
-// not the issue cost of the requests but the traffic itself -- 92 KB of V per chunk into an LDS that the operand reads already keep
-// 65 % busy.  Off (W4_DEFAULT_LOADER).
 static W4Switches w4_switches() {
     W4Switches w{};
 #ifdef I2V_MEASURE
-    if (const char* e = getenv("I2V_W4_PIPE")) w.pipe = atoi(e);
     if (const char* e = getenv("I2V_W4_BN")) w.bn = atoi(e);
     if (const char* e = getenv("I2V_W4_ORDER")) w.order = atoi(e);
     if (const char* e = getenv("I2V_W4_NTH")) w.nth = atoi(e);
-    if (const char* e = getenv("I2V_W4_SKEW")) w.skew = atoi(e);
     w.trace = getenv("I2V_W4_TRACE") != nullptr;
-    if (const char* e = getenv("I2V_W4_LOADER")) w.loader = atoi(e);
     if (const char* e = getenv("I2V_W4_TSKIP")) w.tskip = atoi(e);   // 0: the full tap loops on every brick (A/B and bit reference of i2v_conv16w4e.hip)
 #endif
     return w;
@@ -134,21 +124,16 @@ int wino4_plan(W4Plan* p, const Wino4Weights& wts, int B, int T, int H, int W, b
     int TT = 1, TH = 1;
     (void)wino4_tiling(T, H, W, KT, &TT, &TH);
     int BN = a.CoutPad % 64 == 0 && !gen ? 64 : 32;  // output channels per workgroup
-#ifdef W4_TAPTIME   // (the per-tap timing build carries the 512-thread one-workgroup-per-brick kernels only)
-    const int pipe = 0;
+#ifdef W4_TAPTIME   // (the per-tap timing build carries the 512-thread kernels only)
     const bool thin_ok = false;
 #else
-    const int pipe = sw.pipe;
     const bool thin_ok = !gen;
 #endif
     // 64-channel workgroups that would leave CUs idle (16x16 maps at small batches) become twice as many 32-channel ones
     if (BN == 64 && KT != 1 && (long)B * (T / TT) * (H / TH) * (a.J / 4) * (a.CoutPad / 64) * (wts.tdup ? 2 : 1) < cus) BN = 32;
     if (sw.bn == 32 && KT != 1) BN = 32;
     if (sw.bn == 64 && a.CoutPad % 64 == 0 && !gen) BN = 64;
-    p->form = gen ? W4_GEN : wts.one ? W4_ONE : pipe == 0 ? W4_SPLIT : pipe == 2 ? W4_PERSIST2 : W4_PERSIST1;
-    // 32-channel 3x3x3 layers whose map tiles into the 512-thread brick: the loader form (12 waves: the tap loops issue no V request)
-    if (p->form == W4_SPLIT && sw.loader && BN == 32 && a.CoutPad == 32 && KT == 3 && !wts.tdup && sw.nth == 0 && TT == 4 && TH == 8)
-        p->form = sw.loader == 2 ? W4_LOADER2 : W4_LOADER1;
+    p->form = gen ? W4_GEN : wts.one ? W4_ONE : W4_SPLIT;
     // 32-channel layers: two 256-thread workgroups of 64 tiles per CU instead of one 512-thread workgroup of 128 (W4Geo).
     // Default: only the layers that HAVE 32 output channels (g_4 of the 128 x 128 configs: +3 % on 32 -> 32, +-0 on 64 -> 32,
     // profiles/r05_c_*); 64-channel layers narrowed for a small grid keep the 512-thread geometry (-2 % at B = 8 with 256).
@@ -164,7 +149,6 @@ int wino4_plan(W4Plan* p, const Wino4Weights& wts, int B, int T, int H, int W, b
     a.hh_magic = ((1 << 20) + TH + 1) / (TH + 2);
     I2V_REQUIRE(!has_stats || (long)TT * TH * 4 <= (long)T * H * a.J, I2V_E_INVALID, "%s: fused statistics need bricks inside one sample", nm);
     a.order = sw.order;
-    a.skew = sw.skew;
     const long nblk = (long)B * a.nbT * a.nbH * a.nbJ * (a.CoutPad / BN);
     I2V_REQUIRE(nblk > 0 && nblk < (1L << 30), I2V_E_INVALID, "%s: grid of %ld workgroups", nm, nblk);
     // the kernel's index tables (gpos: V rows, tpos / tres: output and residual positions) are 32-bit
@@ -175,30 +159,23 @@ int wino4_plan(W4Plan* p, const Wino4Weights& wts, int B, int T, int H, int W, b
     }
     I2V_REQUIRE((long)B * (wts.tdup ? 2 * T : T) * H * W < (1L << 31), I2V_E_INVALID,
                 "%s: batch %d too large for the 32-bit row indices of this kernel ([%d,%d,%d] x %d chunks)", nm, B, T, H, W, a.nchunk);
-    a.nvirt = (int)(a.tdup ? 2 * nblk : nblk);   // virtual workgroups = bricks x channel tiles x frame parities
-    p->NT = 3 * KT; p->BN = BN; p->NTH = thin ? 256 : 512; p->PIPE = 0;
+    a.nvirt = (int)(a.tdup ? 2 * nblk : nblk);   // workgroups = bricks x channel tiles x frame parities
+    p->NT = 3 * KT; p->BN = BN; p->NTH = thin ? 256 : 512;
     p->grid = (unsigned)a.nvirt;
     a.tofs = 2 * W4_ROWS_A * 64;   // two V regions (pass B and the epilogue's exchange buffer reuse them), the index tables behind
     p->lds_bytes = (size_t)a.tofs + (size_t)W4_TABLE_BYTES;
     if (thin) {   // two workgroups per CU: 2 V regions of 576 rows + one table set = 79 616 bytes
         a.tofs = 2 * W4Geo<256>::ROWS_A * 64;
         p->lds_bytes = (size_t)a.tofs + (size_t)w4_table_bytes<256>();
-    } else if (p->form == W4_PERSIST1 || p->form == W4_PERSIST2) {
-        // one workgroup per CU, a multiple of 8 so that a virtual workgroup keeps its XCD; two table sets
-        p->PIPE = p->form == W4_PERSIST2 ? 2 : 1;
-        int grid = std::min(a.nvirt, cus);
-        if (grid >= 8) grid &= ~7;
-        p->grid = (unsigned)grid;
-        p->lds_bytes += (size_t)W4_TABLE_BYTES;
-    } else if (p->form == W4_GEN || p->form == W4_LOADER1 || p->form == W4_LOADER2) {   // 12 waves; no V row tables (tpos / tres only)
+    } else if (p->form == W4_GEN) {   // 12 waves; no V row tables (tpos / tres only)
         p->NTH = W4G_THREADS;
         p->lds_bytes = (size_t)a.tofs + 5 * W4Geo<512>::TILES * 4;
     }
-    // Temporal edge units (i2v_conv16w4e.hip): the one-workgroup-per-brick 512-thread split kernel whose row blocks lie inside one frame
+    // Temporal edge units (i2v_conv16w4e.hip): the 512-thread kernels whose row blocks lie inside one frame
     // -- geometry only: 3-D taps, the TT = 4 / TH = 8 and TT = 2 / TH = 16 bricks its masks are compiled for (TT = 1 / TH = 32, odd clips:
     // no shipped config).  Every such launch has edge bricks (nbT x TT = T).
     p->issued = 1.0;
-    if ((p->form == W4_SPLIT || p->form == W4_ONE) && sw.tskip && p->NTH == 512 && p->PIPE == 0 && KT >= 2 && TH * 4 >= 32 && (TT == 4 || TT == 2)) {
+    if ((p->form == W4_SPLIT || p->form == W4_ONE) && sw.tskip && p->NTH == 512 && KT >= 2 && TH * 4 >= 32 && (TT == 4 || TT == 2)) {
         p->form = p->form == W4_ONE ? W4_EDGE_ONE : W4_EDGE;
         long dead, units;
         w4_dead_units(a.T, TT, a.th_shift, KT, a.tdup, &dead, &units);
@@ -213,9 +190,9 @@ int wino4_plan(W4Plan* p, const Wino4Weights& wts, int B, int T, int H, int W, b
 // -DW4_HOST_ONLY (tests/wino_host_check.hip: the packers' bytes and the plans) and the host-side self-test below link this file
 // without the other two translation units and instantiate no kernel
 #if !defined(W4_HOST_ONLY) && !defined(W4_DECODE_SELFTEST)
-template <int NT, int BN, int PIPE, int NTH = 512>
+template <int NT, int BN, int NTH>
 static int launch_wino4_(const W4Plan& p, hipStream_t st) {
-    auto kern = conv_wino4_f16x3_kernel<NT, BN, PIPE, NTH>;
+    auto kern = conv_wino4_f16x3_kernel<NT, BN, NTH>;
     static bool attr_set[I2V_MAX_DEV] = {};
     if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), 160 * 1024, attr_set)) return rc;
     hipLaunchKernelGGL(kern, dim3(p.grid), dim3(NTH), p.lds_bytes, st, p.a);
@@ -226,24 +203,17 @@ static int launch_wino4_(const W4Plan& p, hipStream_t st) {
 static int wino4_launch(const W4Plan& p, hipStream_t st) {
     if (p.form == W4_EDGE || p.form == W4_EDGE_ONE) return wino4e_launch(p, st);
     if (p.form == W4_ONE) return wino4h_launch(p, st);
-    if (p.form == W4_LOADER1 || p.form == W4_LOADER2) return wino4_loader_launch(p, st);
     // (the order of the cases is the order in which the kernels are instantiated and emitted: keep it, the code object stays the same)
-#define W4_CASE(NT, BN, NTH, PIPE) case w4_key(NT, BN, NTH, PIPE): return launch_wino4_<NT, BN, PIPE, NTH>(p, st);
-#if defined(I2V_MEASURE) && !defined(W4_TAPTIME)   // + the persistent forms
-#define W4_CASES(NT, BN) W4_CASE(NT, BN, 512, 2) W4_CASE(NT, BN, 512, 1) W4_CASE(NT, BN, 512, 0)
-#else
-#define W4_CASES(NT, BN) W4_CASE(NT, BN, 512, 0)
-#endif
-    switch (w4_key(p.NT, p.BN, p.NTH, p.PIPE)) {
-        W4_CASES(9, 64) W4_CASES(6, 64) W4_CASES(3, 64)   // (3 taps: one time slice, SPADE's 2-D convs)
+#define W4_CASE(NT, BN, NTH) case w4_key(NT, BN, NTH): return launch_wino4_<NT, BN, NTH>(p, st);
+    switch (w4_key(p.NT, p.BN, p.NTH)) {
+        W4_CASE(9, 64, 512) W4_CASE(6, 64, 512) W4_CASE(3, 64, 512)   // (3 taps: one time slice, SPADE's 2-D convs)
 #ifndef W4_TAPTIME
-        W4_CASE(9, 32, 256, 0) W4_CASE(6, 32, 256, 0)
+        W4_CASE(9, 32, 256) W4_CASE(6, 32, 256)
 #endif
-        W4_CASES(9, 32) W4_CASES(6, 32)
+        W4_CASE(9, 32, 512) W4_CASE(6, 32, 512)
     }
-#undef W4_CASES
 #undef W4_CASE
-    set_error("wino4: no kernel <%d taps, %d channels, %d threads, pipe %d> in this build", p.NT, p.BN, p.NTH, p.PIPE);
+    set_error("wino4: no kernel <%d taps, %d channels, %d threads> in this build", p.NT, p.BN, p.NTH);
     return I2V_E_INVALID;
 }
 
@@ -254,7 +224,6 @@ int wino4_forward(const Wino4Weights& wts, const void* v16, float* out, const fl
     W4Plan p;
     if (int rc = wino4_plan(&p, wts, B, T, H, W, res != nullptr, rt, rs, epi, stats != nullptr, device_cus(), sw)) return rc;
     W4Args& a = p.a;
-    if (int rc = zero_page(&a.zeros)) return rc;
     a.in = static_cast<const char*>(v16); a.wp = wts.w.as<char>(); a.bias = wts.bias.as<float>(); a.res = res; a.out = out;
     a.stats = stats;
     if (sw.trace) {

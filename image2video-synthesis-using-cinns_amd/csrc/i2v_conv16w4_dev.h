@@ -28,7 +28,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #ifdef W4_TIMELINE   // measurement builds (tools/conv16w_check): per-workgroup phase stamps, 100 MHz wall clock
 __device__ unsigned long long w4_tl[8192 * 16];
-#define W4_STAMP(i) { if (tid == 0 && w4_tlv_ < 8192) w4_tl[w4_tlv_ * 16 + (i)] = wall_clock64(); }   // w4_tlv_: the virtual workgroup
+#define W4_STAMP(i) { if (tid == 0 && w4_tlv_ < 8192) w4_tl[w4_tlv_ * 16 + (i)] = wall_clock64(); }   // w4_tlv_: the workgroup
 #else
 #define W4_STAMP(i) {}
 #endif
@@ -53,14 +53,6 @@ __device__ unsigned long long w4_tt[2 * 8 * 18 * 2];   // [pass][wave][tap slot]
 #else
 #define W4_TT(U)
 #endif
-// Structure of the kernel (I2V_W4_PIPE, measurement build only -- see w4_switches): 0 one workgroup per brick (round 3's structure, the default); 1 the software-pipelined
-// persistent kernel; 2 its "lite" form (see the kernel's comment).  All three give the same bits and pass the static checks.
-// Measured (profiles/r04_b_*, r04_l_*): 1 removes 1.9 us of prologue and 1.0 us of pass A per workgroup of the 128 -> 128 layer
-// and pays 0.7 us (tables under pass B's prologue), 1.5 us (pass B with the extra loads) and 1.4 us (four-quarter epilogue):
-// 81.9 -> 82.7 us.  2 gains 2.3 % there (82.3 -> 80.4 us) and loses 11 % on 64 -> 64, where both tap loops slow down: the 256
-// persistent workgroups run the same phase at the same time, which the hardware dispatcher of the default kernel avoids.
-// Whole steps +-1 % either way, so the default stays 0.
-constexpr int W4_DEFAULT_PIPE = 0;
 constexpr int W4_DEFAULT_ORDER = 2;   // brick -> XCD order (kernel comment); I2V_W4_ORDER overrides for A/B runs
 // Cache-policy experiments (measurement builds, tools/build_measurement_libs.sh nt): -DW4_V_NT marks the V stream (LDS-DMA loads)
 // non-temporal so that it does not turn the weight fragments out of the 4 MB L2; -DW4_OUT_NT stores the output non-temporally.
@@ -79,9 +71,8 @@ constexpr int W4_ROWS_A = 1024; // staged V rows per buffer, pass A (4 planes); 
 // wave = (plane, tile half) with two row blocks per weight fragment; pass B: (plane, tile quarter) with one): splitting it into two
 // workgroups keeps every wave's loop exactly as it was -- same fragments per MFMA, same accumulation order, same bits -- and lets
 // the CU run one workgroup's tables / first brick / hand-over / epilogue (10 of 22 us per 128 tiles on the 64 -> 32 layer at 128 x 128,
-// matrix pipe idle) underneath the other one's tap loops, which one workgroup per CU cannot do and the software-pipelined
-// persistent variants did not manage to do by hand.  The halo brick of 64 tiles has 4 x 144 rows per chunk (36 KB) instead of
-// 4 x 240: 1.2 x the V bytes through L2 per tile.
+// matrix pipe idle) underneath the other one's tap loops, which one workgroup per CU cannot do.  The halo brick of 64 tiles has
+// 4 x 144 rows per chunk (36 KB) instead of 4 x 240: 1.2 x the V bytes through L2 per tile.
 // A workgroup load instruction (global_load_lds_dwordx4, one per thread) stages NTH / 4 rows of 64 bytes; a chunk's brick is
 // requested in two half-requests of V0 and V1 such instructions.
 template <int NTH> struct W4Geo;
@@ -112,7 +103,6 @@ template <int NTH> __device__ __forceinline__ int w4_row_tile(int l31) {
 
 struct W4Args {
     const char* in;     // V: hl16 [B][T][Cin/16][6][H][J][64 B], J = W / 4
-    const char* zeros;  // >= 64 zero bytes
     const char* wp;     // U: [parity][tap][chunk][6][CoutPad/32][hi | lo][64 lanes][16 B]
     const float* bias;
     const float* res;
@@ -127,8 +117,7 @@ struct W4Args {
     float oscale;
     int tofs;           // LDS byte offset of the index tables
     int order;          // brick -> XCD order (see w4_decode): 0 round-robin over the flat brick index, 1 / 2 one w-column per XCD
-    int skew;           // persistent kernels: start delay of workgroup i in units of ~5 us x ((i >> 3) & 3) (measurement, I2V_W4_SKEW)
-    int nvirt;          // virtual workgroups = bricks x channel tiles x frame parities (PIPE: looped over by gridDim.x workgroups)
+    int nvirt;          // virtual workgroups = bricks x channel tiles x frame parities = the grid
 };
 
 // Wave priority inside a chunk.  The two waves of a SIMD share the matrix pipe, arbitrated by priority, then age: at equal
@@ -149,32 +138,18 @@ constexpr int w4_count(int t, int R, int NT, int h) {
 
 // One pass of the K loop over NPL = VH planes... (VH = 16-byte V pieces per thread and half-request: 4 -> 1024 staged rows =
 // four planes, 2 -> 512 rows = two planes).  WM = MFMA row blocks of this wave.  arow[wm]: LDS row of the lane's tile (tap
-// (0,0)) inside the pass's brick; gpos: global V row (chunk 0) of every staged row, -1 = zero padding; wlane: this wave's
+// (0,0)) inside the pass's brick; gpos: V row (chunk 0, inside the sample) of every staged row, W4_PAD_ROW = zero padding; wfrag: this wave's
 // weight fragments (tap 0, chunk 0).
 // gposN / PRE: hand-over between the passes.  The request a chunk issues for "the next chunk" is a harmless repeat behind the
-// LAST chunk; pass A instead requests chunk 0 of pass B's brick there (table gposN: its rows in front, -1 behind), into the
+// LAST chunk; pass A instead requests chunk 0 of pass B's brick there (table gposN: its rows in front, padding behind), into the
 // buffer pass B reads first, so that pass B (PRE = true) starts without a V round trip.
-// PIPE (software-pipelined persistent kernel): the pass's two V buffers start at the LDS rows rb0 / rb1 (they alternate
-// between the two 64 KB regions from brick to brick), chunk 0 of pass A's brick is already in LDS when the pass starts (it was
-// requested during the PREVIOUS brick's pass B), `between` runs between the prologue's weight requests and their wait (the next
-// brick's index tables are built there), and pass B carries the next brick's first V brick as two extra LDS-DMA loads per
-// half-request: in its first two chunks they are the eight 16-byte pieces per thread of that brick (table nq, destination
-// ndst = the region this brick's pass B does not use), behind them -- and when there is no next brick -- zero-page reads into a
-// 1 KB dump row, so that the loop body and its wait counts stay the same for every chunk.
-struct W4Next {
-    const int* nq;      // next brick's gposA table + (tid >> 2), or the current one when there is no next brick
-    unsigned ndst;      // LDS byte address of the wave's slice of the free region
-    unsigned dump;      // LDS byte address of the dump row
-    int valid;          // there is a next brick
-};
-
-// BUF (round 5; the one-brick-per-workgroup kernels): the V requests go through a raw buffer descriptor of the brick's SAMPLE
-// (`vrsrc`: base = the sample's V tensor, num_records = its bytes < 2^31) instead of 64-bit addresses: the table holds the row index
-// inside the sample (padding rows: W4_PAD_ROW = 2^25, i.e. byte offset 2^31, out of range under any reading of the range check, and
-// an out-of-range lane of `buffer_load ... lds` writes ZEROS into LDS: tools/bufload_lds_test), the lane's offset is ONE
-// v_lshl_or_b32, the chunk goes into the scalar offset -- 5 instead of 13 instructions per load in front of the first MFMAs of
-// taps 0 / 1, where profiles/r05_n_f43_inloop_idle_analysis.md finds most of the tap loops' idle cycles.  Same loads, same order,
-// same wait counts.
+// rb0 / rb1: the LDS rows at which the pass's two V buffers start.
+// The V requests go through a raw buffer descriptor of the brick's SAMPLE (`vrsrc`: base = the sample's V tensor, num_records = its
+// bytes < 2^31): the table holds the row index inside the sample (padding rows: W4_PAD_ROW = 2^25, i.e. byte offset 2^31, out of range
+// under any reading of the range check, and an out-of-range lane of `buffer_load ... lds` writes ZEROS into LDS:
+// tools/bufload_lds_test), the lane's offset is ONE v_lshl_or_b32, the chunk goes into the scalar offset -- 5 instead of the 13
+// instructions per load of a 64-bit address in front of the first MFMAs of taps 0 / 1, where
+// profiles/r05_n_f43_inloop_idle_analysis.md finds most of the tap loops' idle cycles.
 constexpr int W4_PAD_ROW = 1 << 25;
 // ONE (i2v_conv16w4h.hip, mma = 3): the one-term fp16 form.  A 64-byte V row then holds the fp16 values of 32 channels, pieces
 // [c0-7 | c16-23 | c8-15 | c24-31], so the two operands a lane reads per row block ("ah" / "al" below) are the k-steps of channels
@@ -184,17 +159,15 @@ constexpr int W4_PAD_ROW = 1 << 25;
 // (w4_unit_dead).  A dead unit's MFMAs are not emitted, nor its operand's two ds_read_b128 and their address piece; every other piece
 // keeps its slot -- the weight requests, every V request, every wait, both barriers, the priorities -- so the in-order VMEM stream and
 // the hand-counted waits are those of DEAD = 0, and so are the bits: the products left out are exact zeros.
-template <int NT, int WM, int VH0, int VH1, int NTH, bool PRE, bool PREL, int VXP, bool BUF, class Between, bool ONE = false, unsigned DEAD = 0>
+template <int NT, int WM, int VH0, int VH1, int NTH, bool PRE, bool ONE = false, unsigned DEAD = 0>
 __device__ __forceinline__ void w4_pass(const W4Args& a, char* smem, const int* gpos, const int* gposN, f32x16 (&acc)[WM],
                                         int (&arow)[WM], const char* wfrag, int HH, int tid, int lane, int wave, int rb0, int rb1,
-                                        const W4Next& nxt, Between&& between, int w4_tlv_, __amdgpu_buffer_rsrc_t vrsrc,
+                                        int w4_tlv_, __amdgpu_buffer_rsrc_t vrsrc,
                                         std::bool_constant<ONE> = {}, std::integral_constant<unsigned, DEAD> = {}) {
     constexpr int RPL = NTH / 4;          // V rows staged by one load instruction of the workgroup (4 threads per 64-byte row)
     // GEN (VH0 = VH1 = 0): this pass requests no V at all -- the producer waves of conv_wino4g_f16x3_kernel generate every chunk's
     // brick into the buffer the chunk barrier publishes (same buffers, same barriers); the wait counts then hold only weight loads
     constexpr bool GEN = VH0 == 0 && VH1 == 0;
-    static_assert(VXP == 0 || (VH0 == VH1 && NTH == 512), "PIPE needs the 512-thread geometry");
-    constexpr int VX = PRE ? VXP : 0;   // extra LDS-DMA loads per half-request (the next brick's first V brick; PREL: this brick's was preloaded)
     const int kg = lane >> 5;
     char* v_lds = smem;
     const long cstride = (long)a.CoutPad * 384;          // bytes per (tap, chunk): 6 planes x CoutPad x 64
@@ -204,22 +177,14 @@ __device__ __forceinline__ void w4_pass(const W4Args& a, char* smem, const int* 
     const unsigned voff0 = __builtin_amdgcn_readfirstlane(rb0 * 64), voff1 = __builtin_amdgcn_readfirstlane(rb1 * 64);   // byte offsets of the two V buffers
     const int* gq = gpos + (tid >> 2);
     const int* gqn = gposN + (tid >> 2);
-    const long vpiece = (long)((tid & 3) ^ ((tid >> 4) & 3)) * 16;
-    const long vchunk = (long)6 * a.H * a.J * 64;        // bytes between the K chunks of one frame
-    const unsigned vpiece32 = (unsigned)vpiece;
-    const unsigned vchunk32 = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)vchunk);
+    const unsigned vpiece32 = (unsigned)(((tid & 3) ^ ((tid >> 4) & 3)) * 16);   // the thread's 16-byte piece of a V row (XOR swizzle)
+    const unsigned vchunk32 = (unsigned)__builtin_amdgcn_readfirstlane(6 * a.H * a.J * 64);   // bytes between the K chunks of one frame
     const unsigned wofs = lane * 16;                     // the lane's piece of a weight fragment (the rest of the address is scalar)
     {   // the fragment base goes into the loads' scalar address operand: make its uniformity explicit
         const unsigned long w_ = (unsigned long)wfrag;
         const unsigned lo_ = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)w_);          // (the builtin returns int:
         const unsigned hi_ = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(w_ >> 32));  //  no sign extension)
         wfrag = reinterpret_cast<const char*>((unsigned long)lo_ | ((unsigned long)hi_ << 32));
-    }
-#define W4_GLDS(src_, dst_)                                                                                          \
-    {                                                                                                                \
-        unsigned keep_;                                                                                              \
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off" W4_V_POLICY "\n\ts_mov_b32 m0, %0" \
-                     : "=&s"(keep_) : "v"(src_), "s"(dst_) : "memory");                                              \
     }
 #define W4_BLDS(off_, soff_, dst_)                                                                                   \
     {                                                                                                                \
@@ -234,29 +199,10 @@ __device__ __forceinline__ void w4_pass(const W4Args& a, char* smem, const int* 
         constexpr int nv_ = (HF) ? VH1 : VH0, v0_ = (HF) ? VH0 : 0;   /* this half-request's load instructions */     \
         int gp_[nv_];                                                                                                \
         _Pragma("unroll") for (int u = 0; u < nv_; ++u) gp_[u] = gt_[RPL * (v0_ + u)];                               \
-        if constexpr (BUF) {                                                                                         \
-            const unsigned so_ = (unsigned)(nx_ ? 0 : (ch_)) * vchunk32;                                             \
-            _Pragma("unroll") for (int u = 0; u < nv_; ++u) {                                                        \
-                const unsigned o_ = ((unsigned)gp_[u] << 6) | vpiece32;                                              \
-                W4_BLDS(o_, so_, vdst + ((VB) ? voff1 : voff0) + (unsigned)((v0_ + u) * (NTH * 16)))                  \
-            }                                                                                                        \
-        } else {                                                                                                     \
-        const char* vb_ = a.in + (long)(nx_ ? 0 : (ch_)) * vchunk + vpiece;                                          \
+        const unsigned so_ = (unsigned)(nx_ ? 0 : (ch_)) * vchunk32;                                                 \
         _Pragma("unroll") for (int u = 0; u < nv_; ++u) {                                                            \
-            const char* s_ = gp_[u] >= 0 ? vb_ + (long)gp_[u] * 64 : a.zeros;                     \
-            W4_GLDS(s_, vdst + ((VB) ? voff1 : voff0) + (unsigned)((v0_ + u) * (NTH * 16)))                           \
-        }                                                                                                            \
-        }                                                                                                            \
-        if constexpr (VX > 0) {   /* the next brick's first V brick, pieces (chunk parity, half, u); real in chunks 0, 1 */ \
-            constexpr int pc_ = ((1 - (VB)) * 2 + (HF)) * 2;   /* (the requesting chunk's parity is 1 - VB) */         \
-            const bool real_ = nxt.valid && (ch_) <= 2;        /* requested by chunks 0 and 1 */                       \
-            int gx_[2];                                                                                              \
-            _Pragma("unroll") for (int u = 0; u < 2; ++u) gx_[u] = nxt.nq[128 * (pc_ + u)];                          \
-            _Pragma("unroll") for (int u = 0; u < 2; ++u) {                                                          \
-                const char* s_ = real_ && gx_[u] >= 0 ? a.in + vpiece + (long)gx_[u] * 64 : a.zeros;                 \
-                const unsigned d_ = real_ ? nxt.ndst + (unsigned)((pc_ + u) * 8192) : nxt.dump;                      \
-                W4_GLDS(s_, d_)                                                                                      \
-            }                                                                                                        \
+            const unsigned o_ = ((unsigned)gp_[u] << 6) | vpiece32;                                                  \
+            W4_BLDS(o_, so_, vdst + ((VB) ? voff1 : voff0) + (unsigned)((v0_ + u) * (NTH * 16)))                      \
         }                                                                                                            \
     }
     struct AOps { half8 ah[WM], al[WM]; };
@@ -345,12 +291,11 @@ __device__ __forceinline__ void w4_pass(const W4Args& a, char* smem, const int* 
         W4_REQUEST_B(bq6, 6 % NT, 6 / NT)
         W4_REQUEST_B(bq7, 7 % NT, 7 / NT)
     }
-    if constexpr (!PRE && !PREL && !GEN) {
+    if constexpr (!PRE && !GEN) {
         __syncthreads();  // tables written
         W4_REQUEST_V(0, 0, 0)
         W4_REQUEST_V(0, 0, 1)
     }
-    between();
     if constexpr (R == 9) {
         asm volatile("s_waitcnt vmcnt(0)"
                      : "+v"(bq0.bh), "+v"(bq0.bl), "+v"(bq1.bh), "+v"(bq1.bl), "+v"(bq2.bh), "+v"(bq2.bl), "+v"(bq3.bh),
@@ -385,7 +330,7 @@ __device__ __forceinline__ void w4_pass(const W4Args& a, char* smem, const int* 
     {                                                                                                                \
         constexpr int cp_ = (U) / NT, t_ = (U) % NT;                                                                 \
         constexpr int un_ = (U) + R - 1, cn_ = un_ / NT, tn_ = un_ % NT;                                             \
-        constexpr int nb_ = 2 * (R - 2) + (VH0 + VX) * w4_count(t_, R - 1, NT, 0) + (VH1 + VX) * w4_count(t_, R - 1, NT, VT1);  \
+        constexpr int nb_ = 2 * (R - 2) + VH0 * w4_count(t_, R - 1, NT, 0) + VH1 * w4_count(t_, R - 1, NT, VT1);  \
         W4_TT(U)                                                                                                     \
         if constexpr (W4_PRIO && (t_ == 0 || w4_prio(t_, NT) != w4_prio(t_ - 1, NT)))                                \
             __builtin_amdgcn_s_setprio(w4_prio(t_, NT));                                                             \
@@ -464,7 +409,6 @@ __device__ __forceinline__ void w4_pass(const W4Args& a, char* smem, const int* 
         atomicAdd(&w4_tt[(((PRE ? 8 : 0) + wave) * 18 + lane) * 2 + 1], (unsigned long long)tt_cnt[lane]);
     }
 #endif
-#undef W4_GLDS
 #undef W4_BLDS
 #undef W4_REQUEST_V
 #undef W4_LOAD_A
@@ -480,7 +424,7 @@ __device__ __forceinline__ void w4_pass(const W4Args& a, char* smem, const int* 
 #undef W4_TAP18R9
 }
 
-// Workgroup -> (brick, channel tile, frame parity).  All (virtual) workgroups that read the same V brick (channel tiles, frame
+// Workgroup -> (brick, channel tile, frame parity).  All workgroups that read the same V brick (channel tiles, frame
 // parities) take consecutive slots of ONE XCD (workgroup i runs on XCD i % 8).  Which bricks an XCD gets decides what its 4 MB L2
 // can share between them (every brick re-reads a t-halo of 2 / TT and an h-halo of 2 / TH of its rows):
 //   order 0  XCD x owns the flat brick indices x, x + 8, ... (bj fastest, then bh): one w-column and every SECOND bh -- the
@@ -527,11 +471,10 @@ __host__ __device__ __forceinline__ W4Brick w4_decode(const W4Args& a, int v) {
     return W4Brick{par, ntile, b0, bt * a.TT, bh * a.TH, bj * 4};
 }
 
-// index tables of one brick: gposA [1024] (planes 0..3), gposB [1024] (planes 4, 5 in rows 0..511, -1 = zero page behind),
-// tpos [128] (output position of a tile's first column), tres [128][4] (residual rows of the tile's four columns)
-// REL: V rows relative to the brick's sample and W4_PAD_ROW for padding (the buffer-descriptor requests of the one-brick kernels);
-// else global row indices and -1
-template <int KT, int NTH, bool REL>
+// index tables of one brick: gposA [1024] (planes 0..3), gposB [1024] (planes 4, 5 in rows 0..511, padding behind),
+// tpos [128] (output position of a tile's first column), tres [128][4] (residual rows of the tile's four columns).
+// gpos: V rows relative to the brick's sample, W4_PAD_ROW for zero padding (the buffer-descriptor requests of w4_pass)
+template <int KT, int NTH>
 __device__ __forceinline__ void w4_tables(const W4Args& a, const W4Brick& k, int* gposA, int tid) {
     constexpr int ROWS_A = W4Geo<NTH>::ROWS_A, TILES = W4Geo<NTH>::TILES;
     int* gposB = gposA + ROWS_A;
@@ -562,28 +505,15 @@ __device__ __forceinline__ void w4_tables(const W4Args& a, const W4Brick& k, int
         const int t = k.t0 + q - pt, h = k.h0 + ih - 1, j = k.j0 + ij;
         const bool ok = x < (pb ? 2 : 4) && (unsigned)t < (unsigned)a.T && (unsigned)h < (unsigned)a.H;
         const int xg = pb ? 4 + x : x;
-        if constexpr (REL) (pb ? gposB : gposA)[rr] = ok ? (((t * a.nchunk * 6 + xg) * a.H + h) * a.J + j) : W4_PAD_ROW;   // chunk 0; 64-byte rows
-        else (pb ? gposB : gposA)[rr] = ok ? ((((k.b0 * a.T + t) * a.nchunk * 6 + xg) * a.H + h) * a.J + j) : -1;
+        (pb ? gposB : gposA)[rr] = ok ? (((t * a.nchunk * 6 + xg) * a.H + h) * a.J + j) : W4_PAD_ROW;   // chunk 0; 64-byte rows
     }
 }
 
-constexpr int W4_TABLE_BYTES = w4_table_bytes<512>();   // one table set of the 512-thread kernels
+constexpr int W4_TABLE_BYTES = w4_table_bytes<512>();   // the index tables of the 512-thread kernels
 
 // NT: (kt, kh) taps: 9 = 3x3x3, 6 = temporal-duplication pair kernels (2x3x3), 3 = one time slice (1x3x3: Conv2d).
 // BN: output channels per workgroup.  64: as described above.  32 (layers with 32 output channels): pass A wave = (plane,
 // tile half) with 2 row blocks, pass B wave = (plane, tile quarter) with 1 row block.
-// PIPE: software-pipelined persistent kernel -- one workgroup per CU loops over the virtual workgroups v = blockIdx.x + i *
-// gridDim.x (gridDim.x a multiple of 8: the XCD of a virtual workgroup does not change).  What a brick's workgroup used to do
-// between its loops with the matrix pipe idle (20-33 % of its time) is moved underneath the loops of its neighbours in time:
-//   * the index tables of brick i + 1 are built while brick i's pass B waits for its first weight fragments,
-//   * the first V brick of brick i + 1 travels as two extra LDS-DMA loads per half-request of brick i's pass B into the 64 KB
-//     region that pass B (two 30 KB buffers) does not use; the two regions swap roles from brick to brick (rb0 / rb1),
-//   * the epilogue therefore works in FOUR passes (32-channel half x 64-tile half: E = 6 x 64 x 32 fp32 = 48 KB) inside pass
-//     B's region and leaves the other one alone.
-// LDS (PIPE): [0, 64 K) [64 K, 128 K) the two regions, then two table sets; statistics partials behind E; one dump row.
-// PIPE = 2 ("lite"): the persistent loop with only what was free in the measurement of PIPE = 1: the next brick's tables under pass
-// B's prologue, and its first V brick requested right behind the epilogue's last read of the exchange buffer (in front of the
-// statistics tail), into the fixed first region -- pass B and the two-half epilogue are those of the default kernel.
 // NTH: threads per workgroup (W4Geo): 512, or 256 = the 32-channel kernel as two workgroups per CU.
 #define W4K_NAME conv_wino4_f16x3_kernel
 #define W4K_ONE false
@@ -599,7 +529,7 @@ inline bool wino4_tiling(int T, int H, int W, int KT, int* TT_, int* TH_, int ti
     const int TH = tiles / (TT * 4);
     if (TH < 4 || TH > H || H % TH || TH * 4 % 16) return false;       // (16 consecutive tiles = 16 consecutive V rows: conflict-free ds_read_b128)
     if (4 * (TT + KT - 1) * (TH + 2) * 4 > rows_a) return false;       // pass A's halo brick
-    if (2 * (TT + KT - 1) * (TH + 2) * 4 > rows_b) return false;       // pass B's (512-thread kernels keep 16 padding rows: PIPE's dump row)
+    if (2 * (TT + KT - 1) * (TH + 2) * 4 > rows_b) return false;       // pass B's (the 512-thread kernels' buffer keeps 16 rows free)
     *TT_ = TT; *TH_ = TH;
     return true;
 }
@@ -607,15 +537,14 @@ inline bool wino4_tiling(int T, int H, int W, int KT, int* TT_, int* TH_, int ti
 
 // ---- the launch plan (i2v_conv16w4.hip): every host-side decision about a launch of one of the F(4,3) kernels, made once
 // Measurement switches (see w4_switches in i2v_conv16w4.hip: the production library always runs the defaults)
-constexpr int W4_DEFAULT_LOADER = 0;
-struct W4Switches { int pipe = W4_DEFAULT_PIPE, bn = 0, order = W4_DEFAULT_ORDER, nth = 0, skew = 0, trace = 0, loader = W4_DEFAULT_LOADER, tskip = 1; };
-// Which kernel runs the plan: the split / one-term kernels with one workgroup per brick (i2v_conv16w4.hip / i2v_conv16w4h.hip), the
-// split kernel's persistent forms (I2V_W4_PIPE = 1 / 2), the loader forms and the operand-generating kernel (i2v_conv16w4g.hip), the
-// split and one-term kernels that skip temporal edge units (i2v_conv16w4e.hip)
-enum W4Form : int { W4_SPLIT, W4_ONE, W4_PERSIST1, W4_PERSIST2, W4_LOADER1, W4_LOADER2, W4_GEN, W4_EDGE, W4_EDGE_ONE };
+struct W4Switches { int bn = 0, order = W4_DEFAULT_ORDER, nth = 0, trace = 0, tskip = 1; };
+// Which kernel runs the plan: the split / one-term kernels (i2v_conv16w4.hip / i2v_conv16w4h.hip), the operand-generating kernel
+// (i2v_conv16w4g.hip), the split and one-term kernels that skip temporal edge units (i2v_conv16w4e.hip)
+// (the values are what the launch trace prints and tests/f43_tskip_worker.py reads: they stay what they were)
+enum W4Form : int { W4_SPLIT = 0, W4_ONE = 1, W4_GEN = 6, W4_EDGE = 7, W4_EDGE_ONE = 8 };
 struct W4Plan {
-    W4Args a;             // everything but the pointers in / zeros / res / out / stats, which the caller sets
-    int NT, BN, NTH, PIPE;   // the kernel instantiation: (kt, kh) taps, channels and threads per workgroup, persistent form
+    W4Args a;             // everything but the pointers in / wp / bias / res / out / stats, which the caller sets
+    int NT, BN, NTH;      // the kernel instantiation: (kt, kh) taps, channels and threads per workgroup
     W4Form form;
     unsigned grid;
     size_t lds_bytes;
@@ -627,10 +556,9 @@ int wino4_plan(W4Plan* p, const Wino4Weights& wts, int B, int T, int H, int W, b
                const W4Switches& sw, bool gen = false);
 // what the other two translation units export: the launch of a plan on their kernels
 int wino4h_launch(const W4Plan& p, hipStream_t st);          // form W4_ONE
-int wino4_loader_launch(const W4Plan& p, hipStream_t st);    // forms W4_LOADER1 / W4_LOADER2
 int wino4e_launch(const W4Plan& p, hipStream_t st);          // forms W4_EDGE / W4_EDGE_ONE
 // key of the one switch over instantiations each translation unit has
-constexpr int w4_key(int NT, int BN, int NTH, int PIPE = 0) { return ((NT * 128 + BN) * 1024 + NTH) * 4 + PIPE; }
+constexpr int w4_key(int NT, int BN, int NTH) { return (NT * 128 + BN) * 1024 + NTH; }
 constexpr int W4G_THREADS = 768;   // the 12-wave workgroup of i2v_conv16w4g.hip
 
 }  // namespace i2v

@@ -41,7 +41,7 @@ namespace i2v {
 
 template <int NT, int BN, int ETT, bool ONE>
 static int launch_wino4e(const W4Plan& p, hipStream_t st) {
-    auto kern = ONE ? conv_wino4e_f16_kernel<NT, BN, 0, 512, ETT> : conv_wino4e_f16x3_kernel<NT, BN, 0, 512, ETT>;
+    auto kern = ONE ? conv_wino4e_f16_kernel<NT, BN, 512, ETT> : conv_wino4e_f16x3_kernel<NT, BN, 512, ETT>;
     static bool attr_set[I2V_MAX_DEV] = {};
     if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), 160 * 1024, attr_set)) return rc;
     hipLaunchKernelGGL(kern, dim3(p.grid), dim3(512), p.lds_bytes, st, p.a);
@@ -49,12 +49,12 @@ static int launch_wino4e(const W4Plan& p, hipStream_t st) {
     return I2V_OK;
 }
 
-// The plan is wino4_plan's (forms W4_EDGE / W4_EDGE_ONE: 512 threads, one workgroup per brick, TT = 4 / TH = 8 or TT = 2 / TH = 16).
+// The plan is wino4_plan's (forms W4_EDGE / W4_EDGE_ONE: 512 threads, TT = 4 / TH = 8 or TT = 2 / TH = 16).
 int wino4e_launch(const W4Plan& p, hipStream_t st) {
 #define W4_CASE(NT, BN, ETT)                                                                                         \
     case w4_key(NT, BN, 512) * 8 + ETT:                                                                              \
         return p.form == W4_EDGE_ONE ? launch_wino4e<NT, BN, ETT, true>(p, st) : launch_wino4e<NT, BN, ETT, false>(p, st);
-    if (p.NTH == 512 && p.PIPE == 0 && p.a.TT * p.a.TH == 32) switch (w4_key(p.NT, p.BN, 512) * 8 + p.a.TT) {
+    if (p.NTH == 512 && p.a.TT * p.a.TH == 32) switch (w4_key(p.NT, p.BN, 512) * 8 + p.a.TT) {
         W4_CASE(9, 64, 4) W4_CASE(6, 64, 4) W4_CASE(9, 32, 4) W4_CASE(6, 32, 4)
         W4_CASE(6, 64, 2) W4_CASE(6, 32, 2)   // (a 3x3x3 halo brick of 2 x 16 rows does not fit the V buffers: wino4_tiling)
     }

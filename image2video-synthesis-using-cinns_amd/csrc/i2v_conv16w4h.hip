@@ -12,7 +12,7 @@
 // CinPad = Cin rounded up to 64 (the loop takes chunks in pairs): the 32-channel input of g_4.conv_1 at nf = 32 is padded with zero
 // channels by the writer and zero weights by the packer (WINO_F43_ONE, i2v_wino_pack.h).
 // The epilogue is the split kernel's: A^T M in fp32, 2^-wexp, bias, residual through the up-sampling map, optional lrelu, fused fp64
-// statistics.  Same kernel template (i2v_conv16w4_kernel.h), one-brick-per-workgroup form only, no measurement switches.
+// statistics.  Same kernel template (i2v_conv16w4_kernel.h), no structure switches.
 // Host side: Wino4Weights packed with one = true, wino4_forward (i2v_conv16w4.hip) plans the launch; this file exports the launch only.
 #define W4_NO_INSTRUMENT
 #include "i2v_conv16w4_dev.h"
@@ -25,7 +25,7 @@ namespace i2v {
 
 template <int NT, int BN, int NTH>
 static int launch_wino4h(const W4Plan& p, hipStream_t st) {
-    auto kern = conv_wino4_f16_kernel<NT, BN, 0, NTH>;
+    auto kern = conv_wino4_f16_kernel<NT, BN, NTH>;
     static bool attr_set[I2V_MAX_DEV] = {};
     if (int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kern), 160 * 1024, attr_set)) return rc;
     hipLaunchKernelGGL(kern, dim3(p.grid), dim3(NTH), p.lds_bytes, st, p.a);
@@ -36,7 +36,7 @@ static int launch_wino4h(const W4Plan& p, hipStream_t st) {
 // The plan is wino4_plan's (i2v_conv16w4.hip): the geometry of the split kernel, with default switches.
 int wino4h_launch(const W4Plan& p, hipStream_t st) {
 #define W4_CASE(NT, BN, NTH) case w4_key(NT, BN, NTH): return launch_wino4h<NT, BN, NTH>(p, st);
-    switch (w4_key(p.NT, p.BN, p.NTH, p.PIPE)) {
+    switch (w4_key(p.NT, p.BN, p.NTH)) {
         W4_CASE(9, 32, 256) W4_CASE(6, 32, 256) W4_CASE(9, 64, 512) W4_CASE(6, 64, 512) W4_CASE(9, 32, 512) W4_CASE(6, 32, 512)
     }
 #undef W4_CASE

@@ -32,20 +32,22 @@ def test_library_exports_every_declared_symbol():
 def test_production_library_has_no_launch_path_environment_switches():
     """Round-5 review item: an environment variable silently changing the production kernel is not a drop-in property.  The F(4,3)
     kernel's structure switches (I2V_W4_*) and conv_img's frames-per-workgroup switch exist in the measurement build only
-    (`make measure`, -DI2V_MEASURE); the production library neither contains their names nor the persistent-kernel instantiations,
-    and every `getenv` left in csrc/ sits in a handle-creation / weight-packing function or inside `#ifdef I2V_MEASURE`."""
+    (`make measure`, -DI2V_MEASURE); the production library does not contain their names, and every `getenv` left in csrc/ sits in a
+    handle-creation / weight-packing function or inside `#ifdef I2V_MEASURE`.  The switches of the retired persistent and loader forms
+    (PIPE, SKEW, LOADER) are in neither build."""
     import i2v_native
     if not os.path.exists(i2v_native.LIB_PATH):
         i2v_native.build()
     blob = open(i2v_native.LIB_PATH, "rb").read()
-    for name in (b"I2V_W4_PIPE", b"I2V_W4_BN", b"I2V_W4_ORDER", b"I2V_W4_NTH", b"I2V_W4_SKEW", b"I2V_W4_TRACE", b"I2V_W4_LOADER", b"I2V_CONVIMG_TCH", b"I2V_C16_"):
+    retired = (b"I2V_W4_PIPE", b"I2V_W4_SKEW", b"I2V_W4_LOADER")
+    for name in (b"I2V_W4_", b"I2V_W4_BN", b"I2V_W4_ORDER", b"I2V_W4_NTH", b"I2V_W4_TRACE", b"I2V_W4_TSKIP", b"I2V_CONVIMG_TCH", b"I2V_C16_") + retired:
         assert name not in blob, name
-    assert b"conv_wino4_f16x3_kernelILi9ELi64ELi0ELi512E" in blob
-    for pipe in (1, 2):
-        assert b"conv_wino4_f16x3_kernelILi9ELi64ELi%dELi512E" % pipe not in blob
+    assert b"conv_wino4_f16x3_kernelILi9ELi64ELi512E" in blob
     if os.path.exists(i2v_native.MEASURE_LIB_PATH):
         mblob = open(i2v_native.MEASURE_LIB_PATH, "rb").read()
-        assert b"I2V_W4_PIPE" in mblob and b"conv_wino4_f16x3_kernelILi9ELi64ELi1ELi512E" in mblob
+        assert b"I2V_W4_BN" in mblob and b"conv_wino4_f16x3_kernelILi9ELi64ELi512E" in mblob
+        for name in retired:
+            assert name not in mblob, name
     # source level: getenv only at creation / pack time (functions named below) or under I2V_MEASURE
     allowed = {"i2v_dec_block.hip": ("read_switches",), "i2v_dec_writers.hip": ("run_modulate_wino4",), "i2v_flow.hip": ("i2v_flow_create",),
                "i2v_flow_tile.hip": ("env_int",), "i2v_conv16w4.hip": ("w4_switches",), "i2v_convimg.hip": ("conv_img_mfma_forward",),
@@ -410,8 +412,8 @@ def test_f43_kernel_keeps_its_hand_counted_waits_valid(tmp_path, measure):
     """The same static checks for the Winograd F(4,3) kernel (csrc/i2v_conv16w4.hip): every instantiation has TWO tap loops
     (pass A: planes 0..3, pass B: planes 4, 5), no scratch, exactly the loads the macros issue, and the replay of each
     compiled loop against the in-order VMEM queue finds no hazard while a wait relaxed by one does.  Both builds: the production
-    library (7 one-workgroup-per-brick instantiations, no `getenv` in the object) and the measurement build (-DI2V_MEASURE: + the
-    ten persistent-kernel instantiations behind I2V_W4_PIPE)."""
+    library and the measurement build (-DI2V_MEASURE) carry the same 7 instantiations -- the host-side `getenv`s of the measurement
+    build must not reach the device code."""
     import shutil
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
@@ -423,29 +425,26 @@ def test_f43_kernel_keeps_its_hand_counted_waits_valid(tmp_path, measure):
     text = asm.read_text()
     sys.path.insert(0, os.path.join(REPO, "tools"))
     import check_asm_waits as caw
-    kernels = re.findall(r"^(_ZN3i2v23conv_wino4_f16x3_kernelILi(\d)ELi(\d+)ELi(\d)ELi(\d+)EEEvNS_6W4ArgsE):[^\n]*\n(.*?)\.end_amdhsa_kernel", text,
+    kernels = re.findall(r"^(_ZN3i2v23conv_wino4_f16x3_kernelILi(\d)ELi(\d+)ELi(\d+)EEEvNS_6W4ArgsE):[^\n]*\n(.*?)\.end_amdhsa_kernel", text,
                          flags=re.S | re.M)
-    # <9,64> <6,64> <3,64> (SPADE's 2-D convs) <9,32> <6,32>, each as round 3's one-workgroup-per-brick kernel (PIPE = 0), as the
-    # software-pipelined persistent kernel (PIPE = 1) and as its "lite" form (PIPE = 2); round 5: <9,32> <6,32> as 256-thread
-    # workgroups of 64 tiles (two per CU), whose half-requests are 5 + 4 (pass A) and 3 + 2 (pass B) load instructions
-    assert len(kernels) == (17 if measure else 7), [k[0] for k in kernels]
-    assert measure or all(k[3] == "0" for k in kernels)   # production: PIPE = 0 only
-    assert sorted(k[0] for k in kernels if k[4] == "256") == sorted(
-        "_ZN3i2v23conv_wino4_f16x3_kernelILi%dELi32ELi0ELi256EEEvNS_6W4ArgsE" % n for n in (9, 6))
-    for name, nt, bn, pipe, nth, whole in kernels:
+    # <9,64> <6,64> <3,64> (SPADE's 2-D convs) <9,32> <6,32> with 512 threads; round 5: <9,32> <6,32> as 256-thread workgroups of 64
+    # tiles (two per CU), whose half-requests are 5 + 4 (pass A) and 3 + 2 (pass B) load instructions
+    assert len(kernels) == 7, [k[0] for k in kernels]
+    assert sorted(k[0] for k in kernels if k[3] == "256") == sorted(
+        "_ZN3i2v23conv_wino4_f16x3_kernelILi%dELi32ELi256EEEvNS_6W4ArgsE" % n for n in (9, 6))
+    for name, nt, bn, nth, whole in kernels:
         nt = int(nt)
         assert "scratch_" not in whole and re.search(r"\.amdhsa_private_segment_fixed_size 0\b", whole), name
         loops = [mm.group(2) for mm in re.finditer(r"^(\.LBB\d+_\d+):[^\n]*\n((?:(?!^\.LBB).)*?)s_cbranch_\w+ \1\n", whole, flags=re.S | re.M)
                  if "v_mfma" in mm.group(2)]
         assert len(loops) == 2, (name, len(loops))
-        # PIPE: pass B's half-requests carry two extra loads (the next brick's first V brick)
         # V load instructions per chunk (both half-requests)
-        for loop, wm, vh2 in zip(loops, (4, 2) if bn == "64" else (2, 1), (9, 5) if nth == "256" else ((8, 8) if pipe == "1" else (8, 4))):
+        for loop, wm, vh2 in zip(loops, (4, 2) if bn == "64" else (2, 1), (9, 5) if nth == "256" else (8, 4)):
             taps = 2 * nt
             assert loop.count("v_mfma_f32_32x32x16_f16") == taps * 3 * wm, name
-            # two chunks per loop iteration; the one-brick kernels (PIPE = 0) request V through a buffer descriptor since round 5
-            lds_dma = loop.count("global_load_lds_dwordx4") + len(re.findall(r"buffer_load_dwordx4 [^\n]* lds", loop))
-            assert lds_dma == 2 * vh2 and (loop.count("global_load_lds_dwordx4") == 0) == (pipe == "0"), name
+            # two chunks per loop iteration; V is requested through a buffer descriptor since round 5
+            lds_dma = len(re.findall(r"buffer_load_dwordx4 [^\n]* lds", loop))
+            assert lds_dma == 2 * vh2 and loop.count("global_load_lds_dwordx4") == 0, name
             assert len(re.findall(r"global_load_dwordx4", loop)) == taps * 2, name
             assert loop.count("s_barrier") == 2, name
             assert caw.check_loop(loop) == [], name
@@ -475,10 +474,10 @@ def test_generating_f43_kernel_static_checks(tmp_path):
     text = asm.read_text()
     sys.path.insert(0, os.path.join(REPO, "tools"))
     import check_asm_waits as caw
-    kernels = re.findall(r"^(_ZN3i2v24conv_wino4g_f16x3_kernelILi9ELi(\d+)ELi([012])EEEvNS_6W4ArgsENS_9W4GenArgsE):[^\n]*\n(.*?)\.end_amdhsa_kernel", text,
+    kernels = re.findall(r"^(_ZN3i2v24conv_wino4g_f16x3_kernelILi9ELi(\d+)ELi(\d)EEEvNS_6W4ArgsENS_9W4GenArgsE):[^\n]*\n(.*?)\.end_amdhsa_kernel", text,
                          flags=re.S | re.M)
-    # (channels, mode): 0 / 1 generate the operand (ADAIN / SPADE form), 2 = the LOADER form (four extra waves issue the V requests)
-    assert sorted((k[1], k[2]) for k in kernels) == [("32", "0"), ("32", "1"), ("32", "2"), ("64", "0"), ("64", "1")], [k[0] for k in kernels]
+    # (channels, mode): 0 / 1 generate the operand (ADAIN / SPADE form), 4 = the SPADE form on maps shared by realizations
+    assert sorted((k[1], k[2]) for k in kernels) == [("32", "0"), ("32", "1"), ("32", "4"), ("64", "0"), ("64", "1"), ("64", "4")], [k[0] for k in kernels]
     for name, cin, spade, whole in kernels:
         assert "scratch_" not in whole and re.search(r"\.amdhsa_private_segment_fixed_size 0\b", whole), name
         assert int(re.search(r"\.amdhsa_next_free_vgpr (\d+)", whole).group(1)) <= 168, name      # 12 waves per CU = 3 per SIMD
@@ -494,16 +493,13 @@ def test_generating_f43_kernel_static_checks(tmp_path):
             b_wait = max(waits_of(loop))
             mutated = re.sub(r"s_waitcnt vmcnt\(%d\)" % b_wait, "s_waitcnt vmcnt(%d)" % (b_wait + 1), loop)
             assert caw.check_loop(mutated) != [], (name, b_wait)
-        if spade == "2":   # the loader role: 16 + 8 LDS-DMA requests per chunk, each behind its own m0, all waited for before the barrier
-            dma = re.findall(r"buffer_load_dwordx4 [^\n]* lds", whole)
-            assert len(dma) >= 24 and whole.count("s_waitcnt vmcnt(0)") >= 4, (name, len(dma))
     assert caw.check_loop_entries(text, "conv_wino4g_f16x3_kernel") == []
     assert caw.check_scalar_operands(text, "conv_wino4g_f16x3_kernel") == []
 
 
 def test_f43_virtual_workgroup_map_is_a_bijection(tmp_path):
     """The F(4,3) kernel turns a (virtual) workgroup index into (sample, brick, channel tile, frame parity) -- per XCD, in one of
-    three orders, also when the persistent variants loop over it.  A wrong map would skip or double bricks silently for the
+    three orders.  A wrong map would skip or double bricks silently for the
     geometries no parity test happens to cover, so the map is compiled for the HOST (-DW4_DECODE_SELFTEST) and enumerated over a
     sweep of geometries: it must hit every work item exactly once."""
     import shutil

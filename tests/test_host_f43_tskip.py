@@ -75,7 +75,7 @@ def test_edge_kernel_loops_hold_what_the_rule_says(tmp_path):
     sys.path.insert(0, os.path.join(REPO, "tools"))
     import check_asm_waits as caw
     assert "conv_wino4_f16x3_kernel" not in text        # the pinned kernel is instantiated in its own unit only
-    kernels = re.findall(r"^(_ZN3i2v2[42]conv_wino4e_f16(x3|)_kernelILi(\d)ELi(\d+)ELi0ELi512ELi(\d)EEEvNS_6W4ArgsE):[^\n]*\n(.*?)\.end_amdhsa_kernel", text,
+    kernels = re.findall(r"^(_ZN3i2v2[42]conv_wino4e_f16(x3|)_kernelILi(\d)ELi(\d+)ELi512ELi(\d)EEEvNS_6W4ArgsE):[^\n]*\n(.*?)\.end_amdhsa_kernel", text,
                          flags=re.S | re.M)
     # <9,64> <6,64> <9,32> <6,32> on the 4 x 8 brick; the pair kernels also on the 2 x 16 brick of two-frame inputs
     assert sorted((k[1], k[2], k[3], k[4]) for k in kernels) == sorted(
@@ -124,8 +124,8 @@ def test_libraries_carry_the_edge_kernel_and_only_the_measurement_build_its_swit
         pytest.skip("library not built")
     blob = open(lib, "rb").read()
     for nt, bn, tt in ((9, 64, 4), (6, 64, 4), (9, 32, 4), (6, 32, 4), (6, 64, 2), (6, 32, 2)):
-        assert b"conv_wino4e_f16x3_kernelILi%dELi%dELi0ELi512ELi%dE" % (nt, bn, tt) in blob
-        assert b"conv_wino4e_f16_kernelILi%dELi%dELi0ELi512ELi%dE" % (nt, bn, tt) in blob
-    assert b"conv_wino4_f16x3_kernelILi9ELi64ELi0ELi512E" in blob and b"I2V_W4_TSKIP" not in blob
+        assert b"conv_wino4e_f16x3_kernelILi%dELi%dELi512ELi%dE" % (nt, bn, tt) in blob
+        assert b"conv_wino4e_f16_kernelILi%dELi%dELi512ELi%dE" % (nt, bn, tt) in blob
+    assert b"conv_wino4_f16x3_kernelILi9ELi64ELi512E" in blob and b"I2V_W4_TSKIP" not in blob
     if os.path.exists(mlib):
         assert b"I2V_W4_TSKIP" in open(mlib, "rb").read()

@@ -43,7 +43,7 @@ def test_fp16_kernel_symbol_in_production_library():
     if not os.path.exists(lib):
         pytest.skip("library not built")
     data = open(lib, "rb").read()
-    assert b"_ZN3i2v21conv_wino4_f16_kernelILi9ELi64ELi0ELi512EEEvNS_6W4ArgsE" in data
+    assert b"_ZN3i2v21conv_wino4_f16_kernelILi9ELi64ELi512EEEvNS_6W4ArgsE" in data
     assert data.count(b"_ZN3i2v21conv_wino4_f16_kernel") >= 6
 
 
@@ -75,7 +75,7 @@ def test_fp16_kernel_static_checks(tmp_path):
     sys.path.insert(0, os.path.join(REPO, "tools"))
     import check_asm_waits as caw
     text = _asm(tmp_path, "i2v_conv16w4h")
-    kernels = re.findall(r"^(_ZN3i2v21conv_wino4_f16_kernelILi(\d)ELi(\d+)ELi0ELi(\d+)EEEvNS_6W4ArgsE):[^\n]*\n(.*?)\.end_amdhsa_kernel",
+    kernels = re.findall(r"^(_ZN3i2v21conv_wino4_f16_kernelILi(\d)ELi(\d+)ELi(\d+)EEEvNS_6W4ArgsE):[^\n]*\n(.*?)\.end_amdhsa_kernel",
                          text, flags=re.S | re.M)
     assert sorted((k[1], k[2], k[3]) for k in kernels) == sorted(
         [("9", "64", "512"), ("6", "64", "512"), ("9", "32", "512"), ("6", "32", "512"), ("9", "32", "256"), ("6", "32", "256")])
@@ -103,7 +103,7 @@ def test_fp16_kernel_static_checks(tmp_path):
     # against the split kernel: an iteration of either loop covers two K chunks -- 2 x 16 channels split, 2 x 32 one-term
     split = _asm(tmp_path, "i2v_conv16w4")
     for (nt, bn, nth), ns in mfma_per_chunk.items():
-        m = re.search(r"^_ZN3i2v23conv_wino4_f16x3_kernelILi%dELi%sELi0ELi%sEEEvNS_6W4ArgsE:[^\n]*\n(.*?)\.end_amdhsa_kernel" % (nt, bn, nth),
+        m = re.search(r"^_ZN3i2v23conv_wino4_f16x3_kernelILi%dELi%sELi%sEEEvNS_6W4ArgsE:[^\n]*\n(.*?)\.end_amdhsa_kernel" % (nt, bn, nth),
                       split, flags=re.S | re.M)
         n_split = [lp.count("v_mfma_f32_32x32x16_f16") for lp in _loops(m.group(1))]
         assert len(n_split) == len(ns) == 2

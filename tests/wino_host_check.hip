@@ -101,10 +101,11 @@ static void plan_case(const char* dec, const char* layer, bool one, int cout, in
     const W4Args& a = p.a;
     unsigned ob;
     std::memcpy(&ob, &a.oscale, 4);
+    // (skew=0: a field of the persistent kernels, retired since; the recorded plans keep its place)
     printf("B=%d T=%d H=%d W=%d J=%d Cin=%d Cout=%d CoutPad=%d nchunk=%d tdup=%d wset_stride=%ld TT=%d TH=%d TJ=%d nbT=%d nbH=%d nbJ=%d th_shift=%d rt_shift=%d "
-           "rs_shift=%d hh_magic=%d rt=%d rs=%d epi=%d oscale=%08x tofs=%d order=%d skew=%d nvirt=%d NT=%d BN=%d NTH=%d grid=%u lds=%zu\n",
+           "rs_shift=%d hh_magic=%d rt=%d rs=%d epi=%d oscale=%08x tofs=%d order=%d skew=0 nvirt=%d NT=%d BN=%d NTH=%d grid=%u lds=%zu\n",
            a.B, a.T, a.H, a.W, a.J, a.Cin, a.Cout, a.CoutPad, a.nchunk, a.tdup, a.wset_stride, a.TT, a.TH, a.TJ, a.nbT, a.nbH, a.nbJ, a.th_shift, a.rt_shift,
-           a.rs_shift, a.hh_magic, a.rt, a.rs, a.epi, ob, a.tofs, a.order, a.skew, a.nvirt, p.NT, p.BN, p.NTH, p.grid, p.lds_bytes);
+           a.rs_shift, a.hh_magic, a.rt, a.rs, a.epi, ob, a.tofs, a.order, a.nvirt, p.NT, p.BN, p.NTH, p.grid, p.lds_bytes);
 }
 
 // blocks g_1 .. g_4 of a decoder: channels (16, 8, 4, 2) nf -> (8, 4, 2, 1) nf; g_1 .. g_3 up-sample x2 in time and space (conv_0 is a

@@ -4,7 +4,7 @@
 #   tools/_tl/libi2v_hip_flowtl.so   the library with -DFLOW_TIMELINE (per-launch / per-phase stamps of the cINN tile chain,
 #                                    read by tools/flow_timeline.py)
 #   tools/conv16w_check[_tl|_tt]     the conv check tool: plain, -DW4_TIMELINE, -DW4_TAPTIME (all with -DI2V_MEASURE: the I2V_W4_* switches)
-# The build that reads the F(4,3) structure switches (I2V_W4_PIPE / SKEW / ORDER / BN / NTH / TRACE, I2V_CONVIMG_TCH) is
+# The build that reads the F(4,3) structure switches (I2V_W4_ORDER / BN / NTH / TSKIP / TRACE, I2V_CONVIMG_TCH) is
 #   image2video-synthesis-using-cinns_amd/lib/libi2v_hip_measure.so   (make -C .../csrc measure; also built by __graft_entry__.build())
 # -- the production library reads no environment variable on a launch path.
 set -e
