@@ -352,6 +352,34 @@ GBLOCK_TRAIN_SYMBOLS = {
 }
 
 
+# The entries of include/i2v_hip_gen_train.h (the training path of the Generator around its blocks: fc, up-sampling, image head), one to one.
+GEN_TRAIN_SYMBOLS = {
+    "i2v_gen_train_create": (c_int32, [c_int32, c_int32, POINTER(c_void_p)]),
+    "i2v_gen_train_destroy": (None, [c_void_p]),
+    "i2v_gen_train_bind": (c_int32, [c_void_p, POINTER(_Tensor), c_int32]),
+    "i2v_gen_train_bind_grads": (c_int32, [c_void_p, POINTER(_Tensor), c_int32]),
+    "i2v_gen_train_fc_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
+    "i2v_gen_train_head_saved_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "i2v_gen_train_head_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "i2v_gen_train_fc_slices": (c_int32, [c_int32]),
+    "i2v_gen_train_fc_forward": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
+    "i2v_gen_train_fc_backward": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_size_t, c_void_p]),
+    "i2v_gen_train_head_forward": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_size_t, c_void_p,
+                                             c_size_t, c_void_p]),
+    "i2v_gen_train_head_backward": (c_int32, [c_void_p, c_void_p, c_void_p, c_size_t, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32,
+                                              c_void_p, c_size_t, c_void_p]),
+    "i2v_gen_train_upsample_forward": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "i2v_gen_train_upsample_backward": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "i2v_gen_train_fc_forward_unit": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "i2v_gen_train_fc_backward_unit": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                                 c_void_p, c_size_t, c_void_p]),
+    "i2v_gen_train_head_forward_unit": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                                  c_size_t, c_void_p, c_size_t, c_void_p]),
+    "i2v_gen_train_head_backward_unit": (c_int32, [c_void_p, c_void_p, c_size_t, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                                   c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+}
+
+
 def build(force=False):
     """Compile ``libi2v_hip.so`` for gfx950 in-tree (``make`` in csrc/; hipcc cross-compiles without a GPU)."""
     if force:
@@ -383,7 +411,7 @@ def lib():
                            f"or `make -C {CSRC}`; this package has no CPU/eager fallback")
         l = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(SYMBOLS.items()) + list(DISC_SYMBOLS.items()) + list(DISC3D_SYMBOLS.items()) + list(ENC3D_TRAIN_SYMBOLS.items())
-                                 + list(GBLOCK_TRAIN_SYMBOLS.items())):
+                                 + list(GBLOCK_TRAIN_SYMBOLS.items()) + list(GEN_TRAIN_SYMBOLS.items())):
             fn = getattr(l, name)
             fn.restype = res
             fn.argtypes = args
@@ -2699,3 +2727,156 @@ def gblock_train_conv2d_unit(x, w, g=None, want=(True, True, True)):
         _call("i2v_gblock_train_conv2d_unit", x.data_ptr(), w.data_ptr(), _opt(g), B, H, W, cin, cout, _opt(y), _opt(dx), _opt(dw), ws.data_ptr(),
               ws.numel(), _stream())
     return y, dx, dw
+
+
+# ---------------------------------------------------------------------------------------------------------------- Generator, training path
+GEN_TRAIN_SAVE = 1
+UPSAMPLE_FACTORS = (1, 2, 4)
+
+
+class NativeGenTrain(_BoundHandle):
+    """Handle for ``i2v_gen_train_*`` (include/i2v_hip_gen_train.h): what the Generator's training path runs between and around its six
+    GeneratorBlocks -- ``fc`` and the image head ``tanh(conv_img(lrelu(x)))``, forward and backward in exact fp32.  It packs nothing on the
+    host: ``bind`` hands over the DEVICE pointers of ``fc.{weight,bias}`` and ``conv_img.{weight,bias}`` (read in place, so an optimiser step
+    is seen by the next call) and ``bind_grads`` those of their gradients."""
+    _PREFIX = "i2v_gen_train"
+
+    def __init__(self, channel_factor, z_dim, device=None):
+        self._create(device, int(channel_factor), int(z_dim))
+        self.nf, self.z_dim = int(channel_factor), int(z_dim)
+
+    @_on_device
+    def fc_forward(self, z):
+        """z [B, z_dim] -> [B, 256 nf] (the reshape to [B, 16 nf, 1, 4, 4] is a view)."""
+        _require_gpu(z)
+        if z.dim() != 2 or z.shape[1] != self.z_dim:
+            raise I2VError(f"Generator: expected motion [B,{self.z_dim}], got {tuple(z.shape)}")
+        out = torch.empty(z.shape[0], 256 * self.nf, dtype=torch.float32, device=z.device)
+        _call("i2v_gen_train_fc_forward", self._h, z.data_ptr(), z.shape[0], out.data_ptr(), _stream())
+        return out
+
+    @_on_device
+    def fc_backward(self, g_out, z, need_dz=True, param_grads=True, accumulate=False):
+        """g_out [B, 256 nf] -> dz [B, z_dim] or None; the parameter gradients go to the bound gradient tensors."""
+        _require_gpu(g_out, z)
+        B = z.shape[0]
+        ws = self._scratch(int(lib().i2v_gen_train_fc_workspace_bytes(B, 256 * self.nf, self.z_dim)), z.device)
+        dz = torch.empty(B, self.z_dim, dtype=torch.float32, device=z.device) if need_dz else None
+        _call("i2v_gen_train_fc_backward", self._h, g_out.data_ptr(), z.data_ptr(), B, _opt(dz), int(bool(param_grads)), int(bool(accumulate)), *ws,
+              _stream())
+        return dz
+
+    def _head_geom(self, shape):
+        B, C, T, H, W = shape
+        if C != self.nf:
+            raise I2VError(f"Generator: expected x [B,{self.nf},T,H,W] in front of conv_img, got {tuple(shape)}")
+        return int(B), int(T), int(H), int(W)
+
+    @_on_device
+    def head_forward(self, x, save=False):
+        """x [B, nf, T, H, W] -> (frames [B, T, 3, H, W], saved or None)."""
+        _require_gpu(x)
+        geom = self._head_geom(x.shape)
+        ws = self._scratch(int(lib().i2v_gen_train_head_workspace_bytes(self.nf, *geom)), x.device)
+        saved = torch.empty(int(lib().i2v_gen_train_head_saved_bytes(self.nf, *geom)), dtype=torch.uint8, device=x.device) if save else None
+        B, T, H, W = geom
+        out = torch.empty(B, T, 3, H, W, dtype=torch.float32, device=x.device)
+        _call("i2v_gen_train_head_forward", self._h, x.data_ptr(), *geom, GEN_TRAIN_SAVE if save else 0, out.data_ptr(), _opt(saved),
+              0 if saved is None else saved.numel(), *ws, _stream())
+        return out, saved
+
+    @_on_device
+    def head_backward(self, g_out, saved, shape, need_dx=True, param_grads=True, accumulate=False):
+        """``shape``: that of the forward's x -> dx or None; the parameter gradients go to the bound gradient tensors."""
+        _require_gpu(g_out)
+        geom = self._head_geom(shape)
+        ws = self._scratch(int(lib().i2v_gen_train_head_workspace_bytes(self.nf, *geom)), saved.device)
+        dx = torch.empty(tuple(shape), dtype=torch.float32, device=saved.device) if need_dx else None
+        _call("i2v_gen_train_head_backward", self._h, g_out.data_ptr(), saved.data_ptr(), saved.numel(), *geom, _opt(dx), int(bool(param_grads)),
+              int(bool(accumulate)), *ws, _stream())
+        return dx
+
+
+def gen_train_fc_slices(j):
+    """The slices of the ``j`` rows that the fc backward's dz adds in slice order."""
+    return int(lib().i2v_gen_train_fc_slices(int(j)))
+
+
+def _up_factors(ut, us):
+    if int(ut) not in UPSAMPLE_FACTORS or int(us) not in UPSAMPLE_FACTORS:
+        raise I2VError(f"nearest up-sampling by ({ut}, {us}, {us}): each factor must be one of {UPSAMPLE_FACTORS}")
+    return int(ut), int(us)
+
+
+def gen_train_upsample(x, ut, us):
+    """x [B, C, T, H, W] -> [B, C, ut T, us H, us W], ``F.interpolate(x, scale_factor=(ut, us, us))`` bit for bit."""
+    _require_gpu(x)
+    ut, us = _up_factors(ut, us)
+    B, C, T, H, W = x.shape
+    with torch.cuda.device(x.device):
+        out = torch.empty(B, C, T * ut, H * us, W * us, dtype=torch.float32, device=x.device)
+        _call("i2v_gen_train_upsample_forward", x.data_ptr(), B * C, T, H, W, ut, us, out.data_ptr(), _stream())
+    return out
+
+
+def gen_train_upsample_backward(g, ut, us):
+    """g [B, C, ut T, us H, us W] -> [B, C, T, H, W]: the box sums in fp32 in (dt, dh, dw) order."""
+    _require_gpu(g)
+    ut, us = _up_factors(ut, us)
+    B, C, To, Ho, Wo = g.shape
+    if To % ut or Ho % us or Wo % us:
+        raise I2VError(f"up-sampling backward: {tuple(g.shape)} is not a map up-sampled by ({ut}, {us}, {us})")
+    with torch.cuda.device(g.device):
+        dx = torch.empty(B, C, To // ut, Ho // us, Wo // us, dtype=torch.float32, device=g.device)
+        _call("i2v_gen_train_upsample_backward", g.data_ptr(), B * C, To // ut, Ho // us, Wo // us, ut, us, dx.data_ptr(), _stream())
+    return dx
+
+
+def gen_train_fc_forward_unit(z, w, bias):
+    """z [B, K], w [J, K], bias [J] -> [B, J]."""
+    _require_gpu(z, w, bias)
+    with torch.cuda.device(z.device):
+        out = torch.empty(z.shape[0], w.shape[0], dtype=torch.float32, device=z.device)
+        _call("i2v_gen_train_fc_forward_unit", z.data_ptr(), w.data_ptr(), bias.data_ptr(), z.shape[0], w.shape[0], w.shape[1], out.data_ptr(), _stream())
+    return out
+
+
+def gen_train_fc_backward_unit(g, z, w, want_params=True, want_dz=True):
+    """g [B, J], z [B, K], w [J, K] -> (dw, db, dz), None where unwanted."""
+    _require_gpu(g, z, w)
+    (B, J), K = g.shape, z.shape[1]
+    with torch.cuda.device(z.device):
+        ws = torch.empty(int(lib().i2v_gen_train_fc_workspace_bytes(B, J, K)), dtype=torch.uint8, device=z.device)
+        dw = torch.empty_like(w) if want_params else None
+        db = torch.empty(J, dtype=torch.float32, device=z.device) if want_params else None
+        dz = torch.empty_like(z) if want_dz else None
+        _call("i2v_gen_train_fc_backward_unit", g.data_ptr(), z.data_ptr(), w.data_ptr(), B, J, K, 0, _opt(dw), _opt(db), _opt(dz), ws.data_ptr(),
+              ws.numel(), _stream())
+    return dw, db, dz
+
+
+def gen_train_head_forward_unit(x, w, bias, save=True):
+    """x [B, nf, T, H, W], w [3, nf, 3, 3, 3], bias [3] -> (frames [B, T, 3, H, W], saved or None)."""
+    _require_gpu(x, w, bias)
+    B, nf, T, H, W = x.shape
+    with torch.cuda.device(x.device):
+        ws = torch.empty(int(lib().i2v_gen_train_head_workspace_bytes(nf, B, T, H, W)), dtype=torch.uint8, device=x.device)
+        saved = torch.empty(int(lib().i2v_gen_train_head_saved_bytes(nf, B, T, H, W)), dtype=torch.uint8, device=x.device) if save else None
+        out = torch.empty(B, T, 3, H, W, dtype=torch.float32, device=x.device)
+        _call("i2v_gen_train_head_forward_unit", x.data_ptr(), w.data_ptr(), bias.data_ptr(), nf, B, T, H, W, out.data_ptr(), _opt(saved),
+              0 if saved is None else saved.numel(), ws.data_ptr(), ws.numel(), _stream())
+    return out, saved
+
+
+def gen_train_head_backward_unit(g, saved, w, shape, want_dx=True, want_params=True):
+    """g [B, T, 3, H, W], ``saved`` of the forward, ``shape`` that of its x -> (dx, dw, db), None where unwanted."""
+    _require_gpu(g, w)
+    B, nf, T, H, W = shape
+    with torch.cuda.device(g.device):
+        ws = torch.empty(int(lib().i2v_gen_train_head_workspace_bytes(nf, B, T, H, W)), dtype=torch.uint8, device=g.device)
+        dx = torch.empty(tuple(shape), dtype=torch.float32, device=g.device) if want_dx else None
+        dw = torch.empty_like(w) if want_params else None
+        db = torch.empty(3, dtype=torch.float32, device=g.device) if want_params else None
+        _call("i2v_gen_train_head_backward_unit", g.data_ptr(), saved.data_ptr(), saved.numel(), w.data_ptr(), nf, B, T, H, W, 0, _opt(dx), _opt(dw),
+              _opt(db), ws.data_ptr(), ws.numel(), _stream())
+    return dx, dw, db

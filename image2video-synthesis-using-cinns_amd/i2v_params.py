@@ -80,6 +80,11 @@ def _adopt(parent, value):
                 object.__setattr__(m, "_native_parent", parent)
 
 
+def _refresh_after_load(module, incompatible):
+    """load_state_dict post hook of every NativeBacked module (a module-level function: a module that holds a lambda cannot be pickled)."""
+    module.refresh_native()
+
+
 class NativeBacked(nn.Module):
     """Mixin: lazily builds the native handle from the module's own state_dict and drops it whenever the
     parameters may have changed (load_state_dict, .to()/.cuda(), explicit refresh_native())."""
@@ -88,7 +93,7 @@ class NativeBacked(nn.Module):
         super().__init__()
         object.__setattr__(self, "_native", None)
         object.__setattr__(self, "_native_parent", None)
-        self.register_load_state_dict_post_hook(lambda module, incompatible: module.refresh_native())
+        self.register_load_state_dict_post_hook(_refresh_after_load)
 
     def __setattr__(self, name, value):
         super().__setattr__(name, value)

@@ -117,10 +117,71 @@ class GeneratorBlock(NativeBacked):
                                                 cond2.detach().float().contiguous(), train=self.training)[0]
 
 
+def _once_differentiable(what):
+    if torch.is_grad_enabled():   # create_graph=True: a graph through this backward is asked for
+        raise NotImplementedError(f"{what} is once differentiable: the double backward (create_graph=True) is not built")
+
+
+class _GenFcFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, module, z, weight, bias):
+        ctx.module, ctx.z = module, z
+        return module._train_handle().fc_forward(z)
+
+    @staticmethod
+    def backward(ctx, g_out):
+        _once_differentiable("Generator")
+        need_dz, want = ctx.needs_input_grad[1], ctx.needs_input_grad[2:]
+        if not (need_dz or any(want)):
+            return None, None, None, None
+        grads = ctx.module._glue_grads(g_out.device) if any(want) else None
+        dz = ctx.module._train_handle(grads).fc_backward(g_out.contiguous().float(), ctx.z, need_dz=need_dz, param_grads=grads is not None)
+        return None, dz, grads["fc.weight"] if want[0] else None, grads["fc.bias"] if want[1] else None
+
+
+class _UpsampleFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, ut, us):
+        ctx.factors = (ut, us)
+        return native.gen_train_upsample(x, ut, us)
+
+    @staticmethod
+    def backward(ctx, g_out):
+        _once_differentiable("Generator")
+        return native.gen_train_upsample_backward(g_out.contiguous().float(), *ctx.factors), None, None
+
+
+class _GenHeadFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, module, x, weight, bias):
+        out, saved = module._train_handle().head_forward(x, save=True)
+        ctx.module, ctx.saved, ctx.shape = module, saved, tuple(x.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        _once_differentiable("Generator")
+        need_dx, want = ctx.needs_input_grad[1], ctx.needs_input_grad[2:]
+        if not (need_dx or any(want)):
+            return None, None, None, None
+        grads = ctx.module._glue_grads(g_out.device) if any(want) else None
+        dx = ctx.module._train_handle(grads).head_backward(g_out.contiguous().float(), ctx.saved, ctx.shape, need_dx=need_dx,
+                                                           param_grads=grads is not None)
+        return None, dx, grads["conv_img.weight"] if want[0] else None, grads["conv_img.bias"] if want[1] else None
+
+
 class Generator(NativeBacked):
     """fc -> head_0 -> (x2, g_0) -> (x2, g_1) -> (x2, g_2) -> (up, g_3) -> (up, g_4) -> lrelu -> conv_img -> tanh
     (reference decoder.py:55-120).  Returns ``[B, 16, 3, H, W]`` (contiguous; the reference returns a transposed
-    view of a [B,3,16,H,W] buffer)."""
+    view of a [B,3,16,H,W] buffer).
+
+    ``differentiable`` (a plain attribute, default False; not a reference argument): while it is False every call is the packed inference
+    handle, in grad mode too.  Setting it True sets every block's ``differentiable`` and ``forward(img, motion)`` then runs the chain in
+    exact fp32 with the parameters read in place: the ``fc`` Function, ``head_0``, five (up-sampling Function, block) pairs and the image
+    head Function (csrc/i2v_gen_train.hip around the six block Functions of csrc/i2v_gblock_train.hip).  In grad mode the frames carry a
+    ``grad_fn``; ``motion.grad`` is the sum of fc's and the six blocks' contributions; no gradient is formed at ``img``.  ``.train()``
+    iterates every block's ``weight_u`` / ``weight_v`` once per forward.  ``out=``, ``realizations != 1`` and ``prepare()`` are the inference
+    handle's and raise here.  Setting it back to False resets the blocks and rebuilds the packed decoder from the current parameters."""
 
     def __init__(self, dic):
         super().__init__()
@@ -144,6 +205,88 @@ class Generator(NativeBacked):
         # fp32-class accuracy, ~5x the rate).  Not a reference key: taken from dic["mma"] or the I2V_DEC_MMA env var.
         mma = dic.get("mma", None) if hasattr(dic, "get") else None
         self.mma = native.default_mma() if mma is None else native.parse_mma(mma)   # 0, 1, 2 or "auto" (= 2)
+        object.__setattr__(self, "_train_native", None)
+        object.__setattr__(self, "_differentiable", False)
+
+    def _blocks(self):
+        return (self.head_0, self.g_0, self.g_1, self.g_2, self.g_3, self.g_4)
+
+    @property
+    def differentiable(self):
+        return self.__dict__.get("_differentiable", False)
+
+    @differentiable.setter
+    def differentiable(self, value):
+        value = bool(value)
+        was = self.differentiable
+        object.__setattr__(self, "_differentiable", value)
+        for blk in self._blocks():
+            blk.differentiable = value
+        if was and not value:
+            self.refresh_native()
+
+    def _drop_native(self):
+        super()._drop_native()
+        object.__setattr__(self, "_train_native", None)
+
+    def __getstate__(self):
+        state = dict(super().__getstate__() if hasattr(super(), "__getstate__") else self.__dict__)
+        state["_native"] = state["_train_native"] = None
+        return state
+
+    _GLUE_KEYS = ("fc.weight", "fc.bias", "conv_img.weight", "conv_img.bias")
+
+    def _glue_params(self):
+        return {"fc.weight": self.fc.weight, "fc.bias": self.fc.bias, "conv_img.weight": self.conv_img.weight, "conv_img.bias": self.conv_img.bias}
+
+    def _glue_grads(self, device):
+        """{key: gradient tensor} of fc and conv_img: views of one flat fp32 allocation, each starting on a multiple of 4 floats."""
+        params = self._glue_params()
+        sizes = [(p.numel() + 3) // 4 * 4 for p in params.values()]
+        flat = torch.empty(sum(sizes), dtype=torch.float32, device=device)
+        return {k: v[:p.numel()].view(p.shape) for (k, p), v in zip(params.items(), flat.split(sizes))}
+
+    def _train_handle(self, grads=None):
+        """The training handle of fc and the image head, bound to the storage of their parameters as it is now and, when ``grads`` is
+        given, to those gradient tensors."""
+        tensors = self._glue_params()
+        for t in tensors.values():
+            if not t.is_cuda:
+                raise native.I2VError("Generator runs on a HIP device only: move the module to 'cuda' (this package has no CPU fallback)")
+        h = self.__dict__.get("_train_native")
+        dev = tensors["fc.weight"].device
+        if h is None or h.device != dev:
+            h = native.NativeGenTrain(self.channel_factor, self.z_dim, device=dev)
+            object.__setattr__(self, "_train_native", h)
+        return native.bind_in_place(h, tensors, grads)
+
+    def _forward_differentiable(self, img, motion):
+        if not (img.is_cuda and motion.is_cuda):
+            raise native.I2VError("Generator got a CPU tensor: its kernels run on a HIP device only (this package has no CPU fallback)")
+        if motion.dim() != 2 or motion.shape[1] != self.z_dim or img.dim() != 4 or img.shape[0] != motion.shape[0] or img.shape[1] != 3:
+            raise native.I2VError(f"Generator: expected img [B,3,h,w] and motion [B,{self.z_dim}], got {tuple(img.shape)}, {tuple(motion.shape)}")
+        grad = torch.is_grad_enabled()
+        if grad and img.requires_grad:
+            raise NotImplementedError("Generator forms no gradient at the start frame (img): the reference never asks for one")
+        img, z = img.detach().float().contiguous(), motion.float().contiguous()
+        B, up = z.shape[0], native.gen_train_upsample
+        factors = [(2, 2), (2, 2), (2, 2)] + [(int(t), int(s)) for t, s in zip(self.upsample_t, self.upsample_s)]
+        fc = (self.fc.weight, self.fc.bias)
+        if grad and (z.requires_grad or any(p.requires_grad for p in fc)):
+            x = _GenFcFunction.apply(self, z, *fc)
+        else:
+            with torch.no_grad():
+                x = self._train_handle().fc_forward(z.detach())
+        x = self.head_0(x.view(B, 16 * self.channel_factor, 1, 4, 4), z, img)
+        for blk, (ut, us) in zip(self._blocks()[1:], factors):
+            if (ut, us) != (1, 1):
+                x = _UpsampleFunction.apply(x, ut, us) if grad and x.requires_grad else up(x.detach(), ut, us)
+            x = blk(x, z, img)
+        head = (self.conv_img.weight, self.conv_img.bias)
+        if grad and (x.requires_grad or any(p.requires_grad for p in head)):
+            return _GenHeadFunction.apply(self, x.contiguous(), *head)
+        with torch.no_grad():
+            return self._train_handle().head_forward(x.detach().contiguous())[0]
 
     def _build_native(self):
         h = native.NativeDecoder(self.channel_factor, self.z_dim, self.upsample_s, self.upsample_t, self.use_spectral,
@@ -159,6 +302,11 @@ class Generator(NativeBacked):
         ``Model.forward`` (get_model.py:68-73) run without ``torch.cat`` / ``.contiguous()`` copies.
         ``realizations`` (not a reference argument) = K: ``img`` holds F start frames and ``motion`` F*K latents; sample f*K + k is
         realization k of frame f.  Same bits as ``forward(img.repeat_interleave(K, 0), motion)``; the SPADE branches run once per frame."""
+        if self.differentiable:
+            if out is not None or realizations != 1:
+                raise NotImplementedError("Generator.differentiable is True: out= and realizations != 1 belong to the inference handle "
+                                          "(set differentiable = False)")
+            return self._forward_differentiable(img, motion)
         K = native.check_realizations(img, motion, self.z_dim, realizations)
         if K == 1:
             return self.native().forward(img, motion, out=out)
@@ -202,6 +350,8 @@ class Generator(NativeBacked):
         ``forward(img, z)`` with the SAME contiguous tensor waits for them level by level instead of computing them
         (i2v_dec_prepare); ``get_model.Model.synthesize`` uses it to fill the time the cINN pass takes.  ``realizations`` = K: for
         ``forward(img, z, realizations=K)`` (the branches of the F frames, once each)."""
+        if self.differentiable:
+            raise NotImplementedError("Generator.differentiable is True: prepare() belongs to the inference handle (set differentiable = False)")
         K = native.check_realizations(None, None, None, realizations)
         if K == 1:
             self.native().prepare(img.contiguous())
