@@ -6,7 +6,8 @@
 // Trunk3d family of i2v_train_conv.h, shared with the patch discriminator; GroupNorm and the pool are in i2v_res3d_trunk.h; the plan of
 // the convs and blocks, the binding, the layout of `saved` and of the workspace, the spectral-norm bookkeeping and the forward and
 // backward walks are in i2v_res3d_net.h.  The last two are shared with the motion encoder's training path (i2v_encoder_train.hip).
-// Here: the head, the feature-map loss, the unit entries and the C entries.
+// Here: the head, the feature-map loss, the unit entries and the C entries.  The gradient penalty's gradient (include/i2v_hip_disc3d_gp.h)
+// is the pair of walks of i2v_res3d_gp.h; its entries are at the end of this file.
 //   * Activations are channels-last [N][T][H][W][C]; the clip is stored with 4 channels (r, g, b, 0).
 //   * A forward packs W (/ sigma where the conv is spectral-normed) of every conv once, on the device, into wf [tap][cout][cin] and
 //     wd [tap][cin][cout].  With I2V_DISC3D_SAVE they live in `saved` with that call's u, v and sigma.
@@ -24,7 +25,9 @@
 #include "i2v_power_iter.h"
 #include "i2v_res3d_trunk.h"
 #include "i2v_res3d_net.h"
+#include "i2v_res3d_gp.h"
 #include "../../include/i2v_hip_disc3d.h"
+#include "../../include/i2v_hip_disc3d_gp.h"
 
 namespace i2v {
 namespace {
@@ -413,6 +416,148 @@ int i2v_disc3d_head_unit(const float* x, const float* weight, const float* g, in
     I2V_LAUNCHED();
     if (!g) return I2V_OK;
     hipLaunchKernelGGL(d3_head_bwd_kernel, dim3((c + 255) / 256), dim3(256), 0, st, x, weight, g, dx, dweight, n, c, 0);
+    I2V_LAUNCHED();
+    return I2V_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------------ gradient penalty
+namespace {
+
+int gp_backward(const char* what, i2v_disc3d* d, const void* saved, size_t saved_bytes, int n, int t, int h, int w, float scale, const float* scale_dev,
+                void* gp_saved, size_t gp_saved_bytes, double* l_gp, int accumulate, void* workspace, size_t workspace_bytes, void* stream) {
+    I2V_ENTER(sc, d, Entry::NEEDS_WEIGHTS, what);
+    I2V_REQUIRE(saved && gp_saved && l_gp && workspace, I2V_E_INVALID, "%s: null argument", what);
+    I2V_REQUIRE(d->have_grads, I2V_E_STATE, "%s: no gradient tensors are bound", what);
+    const R3Layout y = d3_layout(d, n, t, h, w);
+    if (!y.ok) return r3_refuse(what, y);
+    const R3GpLayout p = r3_gp_layout(d->trunk, y);
+    I2V_REQUIRE_WORKSPACE(workspace_bytes, p.ws_total, what);
+    I2V_REQUIRE_WORKSPACE(saved_bytes, y.saved_total, what);
+    I2V_REQUIRE_WORKSPACE(gp_saved_bytes, p.saved_total, what);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    void* sv = const_cast<void*>(saved);
+    const bool acc = accumulate != 0;
+    const int last = d->trunk.last(), C = d->trunk.L[last].cout;
+
+    // g = the gradient of mean(pred) at the clips, and the penalty's value
+    float* seed = Carver::at(workspace, p.seed);
+    float* dxf = Carver::at(workspace, p.dxf);
+    double* sq = Carver::at<double>(workspace, p.sq);
+    hipLaunchKernelGGL(d3g_seed_kernel, dim3((n + 255) / 256), dim3(256), 0, st, seed, n);
+    I2V_LAUNCHED();
+    hipLaunchKernelGGL(d3_head_bwd_kernel, dim3((C + 255) / 256), dim3(256), 0, st, Carver::at(sv, y.act[last]), d->fc, seed,
+                       Carver::at(workspace, y.gbuf[0]), static_cast<float*>(nullptr), n, C, 0);
+    I2V_LAUNCHED();
+    if (int rc = r3_backward(d->trunk, y, nullptr, sv, dxf, false, false, workspace, st)) return rc;
+    const long thw = y.geo[0].mi / n;
+    hipLaunchKernelGGL(d3_sumsq_kernel, dim3(n), dim3(256), 0, st, dxf, 3 * thw, sq);
+    I2V_LAUNCHED();
+    hipLaunchKernelGGL(d3g_lgp_kernel, dim3(1), dim3(64), 0, st, sq, n, l_gp);
+    I2V_LAUNCHED();
+
+    // the tangent forward along (2 scale / n) g
+    hipLaunchKernelGGL(d3g_tangent_input_kernel, dim3(grid_for(y.geo[0].mi)), dim3(256), 0, st, dxf, Carver::at(gp_saved, p.x4), y.geo[0].mi, thw, scale,
+                       scale_dev, n);
+    I2V_LAUNCHED();
+    if (int rc = r3_tangent_forward(d->trunk, y, p, sv, gp_saved, workspace, st)) return rc;
+
+    // the head: Pdot = (1 / n) sum_b fc . avg(a'_b) is the quantity differentiated; its adjoint is 1
+    hipLaunchKernelGGL(d3g_head_dual_kernel, dim3((C + 255) / 256), dim3(256), 0, st, Carver::at(gp_saved, p.act[last]), d->fc, 1.f,
+                       Carver::at(workspace, y.gbuf[0]), Carver::at(workspace, p.gbuf[0]), d->gfc, n, C, acc ? 1 : 0);
+    I2V_LAUNCHED();
+    return r3_dual_backward(d->trunk, y, p, sv, gp_saved, acc, workspace, st);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t i2v_disc3d_gp_saved_bytes(const i2v_disc3d* d, int32_t n, int32_t t, int32_t h, int32_t w) {
+    if (!d) return 0;
+    const R3Layout y = d3_layout(d, n, t, h, w);
+    return y.ok ? r3_gp_layout(d->trunk, y).saved_total : 0;
+}
+
+size_t i2v_disc3d_gp_workspace_bytes(const i2v_disc3d* d, int32_t n, int32_t t, int32_t h, int32_t w) {
+    if (!d) return 0;
+    const R3Layout y = d3_layout(d, n, t, h, w);
+    return y.ok ? r3_gp_layout(d->trunk, y).ws_total : 0;
+}
+
+int i2v_disc3d_gp_saved_layout(const i2v_disc3d* d, int32_t n, int32_t t, int32_t h, int32_t w, int32_t* count, int32_t* kind, int32_t* conv,
+                               int32_t* dims, int64_t* offset) {
+    I2V_REQUIRE(d && count && kind && conv && dims && offset, I2V_E_INVALID, "i2v_disc3d_gp_saved_layout: null argument");
+    const R3Layout y = d3_layout(d, n, t, h, w);
+    if (!y.ok) return r3_refuse("i2v_disc3d_gp_saved_layout", y);
+    const R3GpLayout p = r3_gp_layout(d->trunk, y);
+    R3Table tab{kind, conv, dims, offset};
+    for (int i = 0; i < d->trunk.nconv; ++i) {
+        tab.put(I2V_DISC3D_GP_CONV_OUT, i, y.geo[i].to, y.geo[i].ho, y.geo[i].wo, d->trunk.L[i].cout, p.pre[i]);
+        tab.put(I2V_DISC3D_GP_ACT, i, y.geo[i].to, y.geo[i].ho, y.geo[i].wo, d->trunk.L[i].cout, p.act[i]);
+    }
+    if (d->trunk.pool) tab.put(I2V_DISC3D_GP_POOL_OUT, -1, y.pt, y.pho, y.pwo, d->trunk.L[0].cout, p.pout);
+    tab.put(I2V_DISC3D_GP_INPUT, -1, y.geo[0].ti, y.geo[0].hi, y.geo[0].wi, 4, p.x4);
+    *count = tab.count;
+    return I2V_OK;
+}
+
+int i2v_disc3d_gp_backward(i2v_disc3d* d, const void* saved, size_t saved_bytes, int32_t n, int32_t t, int32_t h, int32_t w, float scale,
+                           void* gp_saved, size_t gp_saved_bytes, double* l_gp, int32_t accumulate, void* workspace, size_t workspace_bytes,
+                           void* stream) {
+    return gp_backward("i2v_disc3d_gp_backward", d, saved, saved_bytes, n, t, h, w, scale, nullptr, gp_saved, gp_saved_bytes, l_gp, accumulate, workspace,
+                       workspace_bytes, stream);
+}
+
+int i2v_disc3d_gp_backward_dev(i2v_disc3d* d, const void* saved, size_t saved_bytes, int32_t n, int32_t t, int32_t h, int32_t w, float scale,
+                               const float* scale_dev, void* gp_saved, size_t gp_saved_bytes, double* l_gp, int32_t accumulate, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+    I2V_REQUIRE(scale_dev, I2V_E_INVALID, "i2v_disc3d_gp_backward_dev: null argument");
+    return gp_backward("i2v_disc3d_gp_backward_dev", d, saved, saved_bytes, n, t, h, w, scale, scale_dev, gp_saved, gp_saved_bytes, l_gp, accumulate,
+                       workspace, workspace_bytes, stream);
+}
+
+size_t i2v_disc3d_gp_groupnorm_workspace_bytes(int32_t n, int32_t c) { return n > 0 && c > 0 ? gp_gn_ws(n, c).total : 0; }
+
+int i2v_disc3d_gp_groupnorm_tangent_unit(const float* x, const float* xd, const double* stats, const float* resd, const float* mask,
+                                         const float* weight, int32_t n, int64_t positions, int32_t c, float* out, double* tstats, void* workspace,
+                                         size_t workspace_bytes, void* stream) {
+    const char* what = "i2v_disc3d_gp_groupnorm_tangent_unit";
+    I2V_REQUIRE(x && xd && stats && weight && out && tstats && workspace && n > 0 && positions > 0 && c > 0 && c % 16 == 0, I2V_E_INVALID,
+                "%s: null argument, n %d, %lld positions or %d channels", what, n, (long long)positions, c);
+    I2V_REQUIRE_WORKSPACE(workspace_bytes, gp_gn_ws(n, c).total, what);
+    return launch_gn_tangent(x, xd, stats, resd, mask, weight, n, positions, c, out, tstats, workspace, static_cast<hipStream_t>(stream));
+}
+
+int i2v_disc3d_gp_groupnorm_dual_backward_unit(const float* g, const float* gd, const float* mask, const float* x, const float* xd,
+                                               const double* stats, const double* tstats, const float* weight, int32_t n, int64_t positions,
+                                               int32_t c, float* dx, float* dxd, float* dweight, float* dbias, int32_t accumulate, void* workspace,
+                                               size_t workspace_bytes, void* stream) {
+    const char* what = "i2v_disc3d_gp_groupnorm_dual_backward_unit";
+    I2V_REQUIRE(g && gd && x && xd && stats && tstats && weight && dx && dxd && workspace && !dweight == !dbias && n > 0 && positions > 0 && c > 0 &&
+                    c % 16 == 0,
+                I2V_E_INVALID, "%s: null argument, n %d, %lld positions or %d channels", what, n, (long long)positions, c);
+    I2V_REQUIRE_WORKSPACE(workspace_bytes, gp_gn_ws(n, c).total, what);
+    return launch_gn_dual_bwd(g, gd, mask, x, xd, stats, tstats, weight, n, positions, c, dx, dxd, dweight, dbias, accumulate != 0, workspace,
+                              static_cast<hipStream_t>(stream));
+}
+
+int i2v_disc3d_gp_maxpool_tangent_unit(const float* xd, const int32_t* argmax, int32_t n, int32_t t, int32_t h, int32_t w, int32_t c, float* out,
+                                       void* stream) {
+    I2V_REQUIRE(xd && argmax && out && n > 0 && t > 0 && h > 0 && w > 0 && c > 0, I2V_E_INVALID,
+                "i2v_disc3d_gp_maxpool_tangent_unit: null argument or an empty map");
+    const long ho = (h - 1) / 2 + 1, wo = (w - 1) / 2 + 1;
+    return launch_maxpool_tangent(xd, argmax, out, n, (long)t * ho * wo, (long)t * h * w, c, static_cast<hipStream_t>(stream));
+}
+
+int i2v_disc3d_gp_head_dual_unit(const float* xd, const float* weight, float s, int32_t n, int32_t c, float* pdot, float* dx, float* dxd,
+                                 float* dweight, void* stream) {
+    I2V_REQUIRE(xd && weight && pdot && dx && dxd && n > 0 && c > 0, I2V_E_INVALID, "i2v_disc3d_gp_head_dual_unit: null argument");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(d3_head_fwd_kernel, dim3(n), dim3(256), 0, st, xd, weight, pdot, c);
+    I2V_LAUNCHED();
+    hipLaunchKernelGGL(d3g_head_dual_kernel, dim3((c + 255) / 256), dim3(256), 0, st, xd, weight, s, dx, dxd, dweight, n, c, 0);
     I2V_LAUNCHED();
     return I2V_OK;
 }

@@ -302,6 +302,26 @@ DISC3D_SYMBOLS = {
     "i2v_disc3d_head_unit": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
+# The entries of include/i2v_hip_disc3d_gp.h (the temporal discriminator's gradient penalty with its gradient), one to one.
+DISC3D_GP_SYMBOLS = {
+    "i2v_disc3d_gp_saved_bytes": (c_size_t, [c_void_p, c_int32, c_int32, c_int32, c_int32]),
+    "i2v_disc3d_gp_workspace_bytes": (c_size_t, [c_void_p, c_int32, c_int32, c_int32, c_int32]),
+    "i2v_disc3d_gp_saved_layout": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32),
+                                             POINTER(c_int32), POINTER(c_int64)]),
+    "i2v_disc3d_gp_backward": (c_int32, [c_void_p, c_void_p, c_size_t, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_size_t, c_void_p,
+                                         c_int32, c_void_p, c_size_t, c_void_p]),
+    "i2v_disc3d_gp_backward_dev": (c_int32, [c_void_p, c_void_p, c_size_t, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p, c_size_t,
+                                             c_void_p, c_int32, c_void_p, c_size_t, c_void_p]),
+    "i2v_disc3d_gp_groupnorm_workspace_bytes": (c_size_t, [c_int32, c_int32]),
+    "i2v_disc3d_gp_groupnorm_tangent_unit": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_void_p,
+                                                       c_void_p, c_void_p, c_size_t, c_void_p]),
+    "i2v_disc3d_gp_groupnorm_dual_backward_unit": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                                                             c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_size_t,
+                                                             c_void_p]),
+    "i2v_disc3d_gp_maxpool_tangent_unit": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "i2v_disc3d_gp_head_dual_unit": (c_int32, [c_void_p, c_void_p, c_float, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+}
+
 # The entries of include/i2v_hip_enc3d_train.h (the training path of the motion encoder), one to one.
 ENC3D_TRAIN_SYMBOLS = {
     "i2v_enc3d_train_create": (c_int32, [POINTER(Enc3dTrainCfg), POINTER(c_void_p)]),
@@ -411,7 +431,7 @@ def lib():
                            f"or `make -C {CSRC}`; this package has no CPU/eager fallback")
         l = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(SYMBOLS.items()) + list(DISC_SYMBOLS.items()) + list(DISC3D_SYMBOLS.items()) + list(ENC3D_TRAIN_SYMBOLS.items())
-                                 + list(GBLOCK_TRAIN_SYMBOLS.items()) + list(GEN_TRAIN_SYMBOLS.items())):
+                                 + list(GBLOCK_TRAIN_SYMBOLS.items()) + list(GEN_TRAIN_SYMBOLS.items()) + list(DISC3D_GP_SYMBOLS.items())):
             fn = getattr(l, name)
             fn.restype = res
             fn.argtypes = args
@@ -2330,6 +2350,109 @@ class NativeDisc3D(_Res3DHandle):
         _call("i2v_disc3d_backward", self._h, _opt(d_pred), _ptr_array(d_fmaps), saved.data_ptr(), saved.numel(), n, t, h, w, _opt(dx),
               int(bool(param_grads)), int(bool(accumulate)), *ws, _stream())
         return dx
+
+    # ---- the gradient penalty with its gradient (include/i2v_hip_disc3d_gp.h)
+    def gp_saved_bytes(self, n, t, h, w):
+        return int(lib().i2v_disc3d_gp_saved_bytes(self._h, n, t, h, w))
+
+    def gp_workspace_bytes(self, n, t, h, w):
+        return int(lib().i2v_disc3d_gp_workspace_bytes(self._h, n, t, h, w))
+
+    @_on_device
+    def gp_backward(self, saved, shape, scale=1.0, scale_dev=None, accumulate=False, gp_saved=None, l_gp=None):
+        """From the ``saved`` of a saved forward on clips of ``shape`` (N, 3, T, H, W): the penalty's value and ``scale`` (times the
+        device float ``scale_dev`` [1] when given) times its gradient at every parameter, written or (``accumulate``) added to the bound
+        gradient tensors.  -> (L_GP as a float64 0-d device tensor, gp_saved: the tangent's maps, see ``gp_saved_maps``).  ``gp_saved`` /
+        ``l_gp``: buffers to use instead of fresh ones.  Nothing synchronises."""
+        n, _, t, h, w = shape
+        if not saved.is_cuda:
+            raise I2VError("gp_backward: `saved` is a CPU tensor; libi2v_hip kernels need tensors on a HIP device (this package has no CPU fallback)")
+        if saved.numel() != self.saved_bytes(n, t, h, w):
+            raise I2VError(f"gp_backward: `saved` holds {saved.numel()} bytes, a saved forward on clips {tuple(shape)} holds {self.saved_bytes(n, t, h, w)}")
+        need = self.gp_saved_bytes(n, t, h, w)
+        if gp_saved is None:
+            gp_saved = torch.empty(need, dtype=torch.uint8, device=saved.device)
+        elif not gp_saved.is_cuda or gp_saved.numel() < need:
+            raise I2VError(f"gp_backward: `gp_saved` must be a device buffer of at least {need} bytes")
+        if l_gp is None:
+            l_gp = torch.empty((), dtype=torch.float64, device=saved.device)
+        ws = self._scratch(self.gp_workspace_bytes(n, t, h, w), saved.device)
+        if scale_dev is None:
+            _call("i2v_disc3d_gp_backward", self._h, saved.data_ptr(), saved.numel(), n, t, h, w, float(scale), gp_saved.data_ptr(), gp_saved.numel(),
+                  l_gp.data_ptr(), int(bool(accumulate)), *ws, _stream())
+        else:
+            _require_gpu(scale_dev)
+            _call("i2v_disc3d_gp_backward_dev", self._h, saved.data_ptr(), saved.numel(), n, t, h, w, float(scale), scale_dev.data_ptr(),
+                  gp_saved.data_ptr(), gp_saved.numel(), l_gp.data_ptr(), int(bool(accumulate)), *ws, _stream())
+        return l_gp, gp_saved
+
+    def gp_saved_maps(self, gp_saved, shape):
+        """{(kind, conv): view of ``gp_saved`` [N, T, H, W, C]} of the tangent maps (kinds DISC3D_GP_*; conv -1: the pool's, the input)."""
+        n, _, t, h, w = shape
+        cnt, kind, conv, dims, off = c_int32(), (c_int32 * 64)(), (c_int32 * 64)(), (c_int32 * 256)(), (c_int64 * 64)()
+        _call("i2v_disc3d_gp_saved_layout", self._h, n, t, h, w, ctypes.byref(cnt), kind, conv, dims, off)
+        out, flat = {}, gp_saved.view(torch.float32)
+        for e in range(cnt.value):
+            shp = (n, *dims[4 * e: 4 * e + 4])
+            out[(kind[e], conv[e])] = flat[off[e] // 4: off[e] // 4 + int(np.prod(shp))].view(shp)
+        return out
+
+
+DISC3D_GP_CONV_OUT, DISC3D_GP_ACT, DISC3D_GP_POOL_OUT, DISC3D_GP_INPUT = 0, 1, 2, 3
+
+
+def _gp_gn_ws(n, c, device):
+    return torch.empty(int(lib().i2v_disc3d_gp_groupnorm_workspace_bytes(n, c)), dtype=torch.uint8, device=device)
+
+
+def disc3d_gp_groupnorm_tangent_unit(x, xd, stats, weight, resd=None, mask=None):
+    """GroupNorm's tangent over channels-last maps [N, ..., C]: x, stats of the primal -> (out, tstats float64 [N, 16, 2] = (M(xd), C(xd)))."""
+    _require_gpu(x, xd, weight, resd, mask)
+    n, c = x.shape[0], x.shape[-1]
+    with torch.cuda.device(x.device):
+        ws = _gp_gn_ws(n, c, x.device)
+        out, tstats = torch.empty_like(x), torch.empty(n, 16, 2, dtype=torch.float64, device=x.device)
+        _call("i2v_disc3d_gp_groupnorm_tangent_unit", x.data_ptr(), xd.data_ptr(), stats.data_ptr(), _opt(resd), _opt(mask), weight.data_ptr(), n,
+              x[0].numel() // c, c, out.data_ptr(), tstats.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+    return out, tstats
+
+
+def disc3d_gp_groupnorm_dual_backward_unit(g, gd, x, xd, stats, tstats, weight, mask=None, dweight=None, dbias=None, param_grads=True):
+    """-> (dx, dxd, dweight, dbias); given ``dweight`` / ``dbias`` the parameter gradients are ADDED to them."""
+    _require_gpu(g, gd, x, xd, weight, mask, dweight, dbias)
+    n, c = x.shape[0], x.shape[-1]
+    accumulate = dweight is not None
+    with torch.cuda.device(x.device):
+        ws = _gp_gn_ws(n, c, x.device)
+        dx, dxd = torch.empty_like(x), torch.empty_like(x)
+        if param_grads and not accumulate:
+            dweight, dbias = torch.empty_like(weight), torch.empty_like(weight)
+        _call("i2v_disc3d_gp_groupnorm_dual_backward_unit", g.data_ptr(), gd.data_ptr(), _opt(mask), x.data_ptr(), xd.data_ptr(), stats.data_ptr(),
+              tstats.data_ptr(), weight.data_ptr(), n, x[0].numel() // c, c, dx.data_ptr(), dxd.data_ptr(), _opt(dweight), _opt(dbias), int(accumulate),
+              ws.data_ptr(), ws.numel(), _stream())
+    return dx, dxd, dweight, dbias
+
+
+def disc3d_gp_maxpool_tangent_unit(xd, argmax):
+    """xd [N, T, H, W, C], argmax int32 [N, T, Ho, Wo, C] of the primal's pool -> the tangent of the pool's output."""
+    _require_gpu(xd)
+    n, t, h, w, c = xd.shape
+    with torch.cuda.device(xd.device):
+        out = torch.empty(argmax.shape, dtype=torch.float32, device=xd.device)
+        _call("i2v_disc3d_gp_maxpool_tangent_unit", xd.data_ptr(), argmax.data_ptr(), n, t, h, w, c, out.data_ptr(), _stream())
+    return out
+
+
+def disc3d_gp_head_dual_unit(xd, weight, s=1.0):
+    """xd [N, 1, 4, 4, C], weight [1, C] -> (pdot [N, 1], dx, dxd, dweight): the head's tangent and its reverse for the seed scale ``s``."""
+    _require_gpu(xd, weight)
+    n, c = xd.shape[0], xd.shape[-1]
+    with torch.cuda.device(xd.device):
+        pdot = torch.empty(n, 1, dtype=torch.float32, device=xd.device)
+        dx, dxd, dw = torch.empty_like(xd), torch.empty_like(xd), torch.empty_like(weight)
+        _call("i2v_disc3d_gp_head_dual_unit", xd.data_ptr(), weight.data_ptr(), float(s), n, c, pdot.data_ptr(), dx.data_ptr(), dxd.data_ptr(),
+              dw.data_ptr(), _stream())
+    return pdot, dx, dxd, dw
 
 
 def disc3d_fmap_loss(fmap1, fmap2, metric="L1", need_grads=True, grad_scale=1.0):

@@ -1,7 +1,8 @@
 """Training natively: ``FusedAdam`` (``torch.optim.Adam`` semantics in one multi-tensor HIP launch, ``i2v_adam_step``),
 ``FlowTrainer`` (forward, loss gradient, backward and optimiser step of the stage-2 trainer, reference
-stage2_cINN/main.py:22-46, without autograd in between) and ``PatchDiscTrainer`` (the spatial-discriminator lines of the stage-1
-step, reference stage1_VAE/modules/loss.py:111-125).  No CPU fallback: parameters and gradients live on a HIP device."""
+stage2_cINN/main.py:22-46, without autograd in between), ``PatchDiscTrainer`` (the spatial-discriminator lines of the stage-1
+step, reference stage1_VAE/modules/loss.py:111-125), ``TemporalDiscTrainer`` (the temporal-discriminator lines 94-109 without the
+gradient penalty, 127-135) and ``TemporalDiscPenaltyTrainer`` (lines 94-109 complete, ``w_GP`` included).  No CPU fallback: parameters and gradients live on a HIP device."""
 import ctypes
 
 import numpy as np
@@ -196,15 +197,16 @@ class TemporalDiscTrainer:
     the step holds them (or [B, 3, T, H, W]; the module transposes as the reference does).  Everything is enqueued on the current
     stream; no method synchronises the host.  Defaults: stage1_VAE/main.py and the shipped configs.
 
-    ``w_GP != 0`` is refused: the penalty's gradient needs the double backward of the whole network, which is not built (nor are the
-    decoder's and the motion encoder's backward, nor ``Backward.forward``).  ``gradient_penalty`` returns the penalty's VALUE, which is a
-    first-order quantity."""
+    ``w_GP != 0`` is refused here: this class has no double backward.  ``TemporalDiscPenaltyTrainer`` below is the step with the penalty
+    (the penalty's gradient as a tangent forward and one reverse pass over the pair, csrc/i2v_res3d_gp.h).  ``gradient_penalty`` returns
+    the penalty's VALUE, which is a first-order quantity."""
 
     def __init__(self, disc, lr=2e-4, betas=(0.5, 0.9), weight_decay=1e-5, w_GP=0, eps=1e-8, optimizer=None):
         """``optimizer``: an optimiser over ``disc.parameters()`` to step instead of the fused Adam (the tests step plain SGD)."""
         if w_GP:
-            raise NotImplementedError(f"TemporalDiscTrainer: w_GP = {w_GP} needs the gradient of the gradient penalty, i.e. the double backward of "
-                                      "resnet3D.Discriminator, which is not built; gradient_penalty() gives the penalty's value only")
+            raise NotImplementedError(f"TemporalDiscTrainer: w_GP = {w_GP} needs the gradient of the gradient penalty, which this class does not "
+                                      "form (it has no double backward of resnet3D.Discriminator; gradient_penalty() gives the penalty's value "
+                                      "only): use i2v_train.TemporalDiscPenaltyTrainer, the same step with the penalty's gradient")
         self.disc = disc
         self.optimizer = optimizer or FusedAdam(disc.parameters(), lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         self._ones = {}
@@ -260,3 +262,40 @@ class TemporalDiscTrainer:
             d_pred = self._ones[(n, pred.device)] = torch.full((n, 1), 1.0 / n, dtype=torch.float32, device=pred.device)
         dx = self.disc._handle().backward(d_pred, None, saved, self._shape(seq_real), need_dx=True, param_grads=False)
         return native.disc3d_sumsq(dx).mean()
+
+
+class TemporalDiscPenaltyTrainer(TemporalDiscTrainer):
+    """``TemporalDiscTrainer`` with the gradient penalty's gradient: ``step`` is loss.py:95-109 complete,
+    ``(L_d_t + w_GP * L_GP).backward()`` and the optimiser step.  The penalty's gradient is no general double backward: a tangent forward
+    along ``(2 w_GP / n) grad_x mean(pred)`` and one reverse pass over the pair (``NativeDisc3D.gp_backward``, csrc/i2v_res3d_gp.h), from
+    the SAME saved forward on the real clips that the hinge loss uses, so each step iterates the spectral norm twice, as the reference's
+    does.  ``generator_loss`` and ``gradient_penalty`` are inherited.  No method synchronises the host."""
+
+    def __init__(self, disc, lr=2e-4, betas=(0.5, 0.9), weight_decay=1e-5, w_GP=10, eps=1e-8, optimizer=None):
+        super().__init__(disc, lr=lr, betas=betas, weight_decay=weight_decay, w_GP=0, eps=eps, optimizer=optimizer)
+        self.w_GP = float(w_GP)
+        self._gp_saved = None
+
+    @torch.no_grad()
+    def step(self, seq_fake, seq_real):
+        """-> (L_d_t, mean real logit, mean fake logit, L_GP) as float64 0-d device tensors; ``w_GP = 0`` runs the parent's step and
+        returns ``L_GP = 0``."""
+        if not self.w_GP:
+            out = super().step(seq_fake, seq_real)
+            return out[0], out[1], out[2], torch.zeros((), dtype=torch.float64, device=out[0].device)
+        disc, grads = self.disc, self._grads()
+        pred_f, _, saved_f = disc._run(seq_fake, save=True, grads=grads, want_fmaps=False)
+        pred_r, _, saved_r = disc._run(seq_real, save=True, grads=grads, want_fmaps=False)
+        out, d_f, d_r = native.patchdisc_hinge(pred_f, pred_r, "disc")
+        h = disc._handle(grads)
+        shape_r = self._shape(seq_real)
+        # the real clips first, the penalty onto them, then the fake clips: the sum autograd forms for
+        # (hinge_loss(pred_f, pred_r, 'disc') + w_GP * L_GP).backward() over forward() and forward_with_penalty(), bit for bit
+        h.backward(d_r, None, saved_r, shape_r, need_dx=False, param_grads=True, accumulate=False)
+        need = h.gp_saved_bytes(shape_r[0], *shape_r[2:])
+        if self._gp_saved is None or self._gp_saved.numel() < need or self._gp_saved.device != saved_r.device:
+            self._gp_saved = torch.empty(need, dtype=torch.uint8, device=saved_r.device)
+        l_gp, _ = h.gp_backward(saved_r, shape_r, scale=self.w_GP, accumulate=True, gp_saved=self._gp_saved)
+        h.backward(d_f, None, saved_f, self._shape(seq_fake), need_dx=False, param_grads=True, accumulate=True)
+        self.optimizer.step()
+        return out[0], out[1], out[2], l_gp

@@ -1,8 +1,10 @@
 """Stage-1 losses and validation metrics, mirror of the reference's ``stage1_VAE/modules/loss.py``: ``KL``, ``fmap_loss``, ``hinge_loss`` and
-``Backward`` with the reference's ``eval`` (loss.py:183-216).  The training step ``Backward.forward`` is not built (the decoder backward and
-the penalty's double backward are missing; the motion encoder trains through ``resnet3D.Encoder.differentiable``, ``KL`` has a gradient); its
-spatial-discriminator lines (loss.py:111-125) are ``i2v_train.PatchDiscTrainer`` on ``patch_disc.NLayerDiscriminator``, its
-temporal-discriminator lines (loss.py:94-109 without the penalty, 127-135) ``i2v_train.TemporalDiscTrainer`` on ``resnet3D.Discriminator``.
+``gradient_penalty`` and ``Backward`` with the reference's ``eval`` (loss.py:183-216).  The training step ``Backward.forward`` is not built:
+every backward pass it needs exists (the Generator, the motion encoder through ``resnet3D.Encoder.differentiable``, ``KL`` and LPIPS with
+gradients, both discriminators, and the gradient penalty's gradient without a general double backward), so only its composition remains, the
+one open piece of stage-1 training.  Its spatial-discriminator lines (loss.py:111-125) are ``i2v_train.PatchDiscTrainer`` on
+``patch_disc.NLayerDiscriminator``, its temporal-discriminator lines ``i2v_train.TemporalDiscTrainer`` (loss.py:94-109 without the penalty,
+127-135) and ``i2v_train.TemporalDiscPenaltyTrainer`` (94-109 complete, ``w_GP`` included) on ``resnet3D.Discriminator``.
 ``fmap_loss`` and ``hinge_loss`` here are the reference's functions on torch tensors (they differentiate through the discriminators'
 autograd Functions); the trainers use the kernel forms ``i2v_native.disc3d_fmap_loss`` and ``i2v_native.patchdisc_hinge``.
 
@@ -67,6 +69,19 @@ def hinge_loss(fake_data, orig_data, update):
         return -torch.mean(fake_data)
 
 
+def gradient_penalty(disc, x):
+    """The reference's ``gradient_penalty(pred, x)`` (loss.py:35-43): the mean over the samples of the squared norm of the gradient of
+    ``mean(pred)`` at ``x``.  -> ``(pred, fmaps, L_GP)`` of ``disc.forward_with_penalty(x)``.
+
+    The signature differs from the reference's ``(pred, x)``: there ``pred`` carries an autograd graph from which
+    ``torch.autograd.grad(..., create_graph=True)`` builds the double backward.  Here the network is one autograd Function over HIP kernels
+    with no graph inside to differentiate twice, so the penalty has to come out of the SAME forward call that makes ``pred`` -- the module
+    and the clips go in, and ``pred`` comes out next to ``L_GP``.  In grad mode ``L_GP`` carries a ``grad_fn`` whose backward is the tangent
+    forward and the reverse pass over the pair (csrc/i2v_res3d_gp.h); loss.py:98-108 is then
+    ``pred_r, _, L_GP = gradient_penalty(disc_t, seq_real); (hinge_loss(pred_f, pred_r, 'disc') + w_GP * L_GP).backward()``."""
+    return disc.forward_with_penalty(x)
+
+
 def recon_metrics(pred, target, data_range=None, per_image=False):
     """PSNR, SSIM, L1 and MSE of two frame tensors [B, T, C, H, W] (or [N, C, H, W]) on a HIP device -> dict of float64 0-d device tensors
     ``l1, mse, psnr, ssim``; nothing synchronises.  ``data_range=None`` is the reference's behaviour (ranges taken from the data: PSNR from
@@ -101,7 +116,7 @@ def _section(opt, name):
 
 
 class Backward(nn.Module):
-    """Losses of stage 1 (loss.py:47-216).  ``eval`` is built, ``forward`` (the training step) is not."""
+    """Losses of stage 1 (loss.py:47-216).  ``eval`` is built; of ``forward`` (the training step) only the composition is missing."""
 
     def __init__(self, opt, lpips=None):
         super().__init__()
@@ -118,11 +133,13 @@ class Backward(nn.Module):
         self.curves = []
 
     def forward(self, decoder, encoder, disc_t, disc_s, seq_o, optimizers, epoch, logger):
-        raise NotImplementedError("Backward.forward (the stage-1 training step, loss.py:64-180) is not built: of the backward passes it needs, "
-                                  "the decoder's and the gradient penalty's double backward (w_GP) are still missing.  Built are the two "
-                                  "discriminators (patch_disc.NLayerDiscriminator with i2v_train.PatchDiscTrainer: loss.py:111-125; "
-                                  "resnet3D.Discriminator with i2v_train.TemporalDiscTrainer: loss.py:94-109, 127-135), the LPIPS gradient, and the "
-                                  "motion-encoder backward with the KL gradient (resnet3D.Encoder.differentiable = True; KL returns a grad_fn); "
+        raise NotImplementedError("Backward.forward (the stage-1 training step, loss.py:64-180) is not built: only its composition remains.  "
+                                  "All of the backward passes it needs are built: the Generator (the decoder), the two discriminators "
+                                  "(patch_disc.NLayerDiscriminator with i2v_train.PatchDiscTrainer: loss.py:111-125; resnet3D.Discriminator with "
+                                  "i2v_train.TemporalDiscTrainer / TemporalDiscPenaltyTrainer: loss.py:94-109, 127-135), the gradient penalty's "
+                                  "gradient (w_GP; a tangent forward and one reverse pass, no general double backward: "
+                                  "Discriminator.forward_with_penalty, loss.gradient_penalty), the LPIPS gradient, and the motion-encoder "
+                                  "backward with the KL gradient (resnet3D.Encoder.differentiable = True; KL returns a grad_fn); "
                                   "Backward.eval is built")
 
     @torch.no_grad()

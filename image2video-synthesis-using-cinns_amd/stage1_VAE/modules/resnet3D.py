@@ -99,7 +99,8 @@ class Encoder(NativeBacked):
 #   * ``x`` is transposed when ``x.size(1) > x.size(2)``.
 # One difference: the reference starts the layers from ``inplanes = 64`` whatever ``channels[0]`` is (so it only runs with a 64-wide stem,
 # as in every shipped config); here the first layer takes ``channels[0]`` inputs, which is the same network at 64 and a working one below.
-# In grad mode ``forward`` returns tensors with a ``grad_fn`` (once differentiable: the gradient penalty's double backward is not built);
+# In grad mode ``forward`` returns tensors with a ``grad_fn`` (once differentiable: ``create_graph=True`` raises; the gradient penalty with
+# its gradient is ``forward_with_penalty``, which needs no general double backward);
 # the parameters are inputs of the Function; a frozen module skips the weight-gradient launches.  CPU tensors raise ``I2VError``.
 
 
@@ -170,6 +171,47 @@ class _Disc3DFunction(torch.autograd.Function):
         cl = [None if g is None else g.permute(0, 2, 3, 4, 1).contiguous().float() for g in d_fmaps]
         dx = h.backward(None if d_pred is None else d_pred.contiguous().float(), cl, ctx.saved, ctx.shape, need_dx=ctx.needs_input_grad[1],
                         param_grads=grads is not None, accumulate=False)
+        out = [None] * len(want) if grads is None else [g if w else None for g, w in zip(grads.values(), want)]
+        return (None, dx, *out)
+
+
+class _Disc3DPenaltyFunction(torch.autograd.Function):
+    """``forward_with_penalty``: the module's forward plus the penalty of ``mean(pred)`` at ``x`` from the same saved forward.  Backward:
+    the existing backward for ``d_pred`` / ``d_fmaps``, plus ``gp_backward`` scaled by the upstream of ``L_GP``, which stays a device
+    scalar.  The penalty's value is formed in ``forward`` by the input-gradient backward and ``disc3d_sumsq`` (the bits of
+    ``TemporalDiscTrainer.gradient_penalty``); ``gp_backward`` forms the gradient at the clips again, one input-gradient pass in exchange
+    for holding no second clip-sized tensor between forward and backward."""
+
+    @staticmethod
+    def forward(ctx, module, x, *params):
+        pred, fmaps, saved = module._run(x, save=True)
+        shape = tuple(x.shape)
+        dx = module._handle().backward(module._penalty_seed(pred), None, saved, shape, need_dx=True, param_grads=False)
+        l_gp = native.disc3d_sumsq(dx).mean()
+        ctx.module, ctx.saved, ctx.shape = module, saved, shape
+        ctx.set_materialize_grads(False)
+        return (pred, l_gp, *[f.permute(0, 4, 1, 2, 3) for f in fmaps])
+
+    @staticmethod
+    def backward(ctx, d_pred, d_lgp, *d_fmaps):
+        if torch.is_grad_enabled():   # create_graph=True: a graph through this backward is asked for
+            raise NotImplementedError("resnet3D.Discriminator.forward_with_penalty is once differentiable: a general double backward "
+                                      "(create_graph=True) is not built")
+        module = ctx.module
+        want = ctx.needs_input_grad[2:]
+        first = d_pred is not None or any(g is not None for g in d_fmaps)
+        grads = native.flat_param_grads(module, ctx.saved.device) if any(want) else None
+        h = module._handle(grads)
+        dx = None
+        if first and (grads is not None or ctx.needs_input_grad[1]):
+            cl = [None if g is None else g.permute(0, 2, 3, 4, 1).contiguous().float() for g in d_fmaps]
+            dx = h.backward(None if d_pred is None else d_pred.contiguous().float(), cl, ctx.saved, ctx.shape, need_dx=ctx.needs_input_grad[1],
+                            param_grads=grads is not None, accumulate=False)
+        elif grads is not None:
+            for g in grads.values():
+                g.zero_()
+        if d_lgp is not None and grads is not None:   # (the penalty has no gradient at the clips: the reference's seq_real is data)
+            h.gp_backward(ctx.saved, ctx.shape, scale=1.0, scale_dev=d_lgp.detach().to(torch.float32).reshape(1).contiguous(), accumulate=True)
         out = [None] * len(want) if grads is None else [g if w else None for g, w in zip(grads.values(), want)]
         return (None, dx, *out)
 
@@ -255,6 +297,28 @@ class Discriminator(nn.Module):
             return pred, list(fmaps)
         pred, fmaps, _ = self._run(x, save=False)
         return pred, [f.permute(0, 4, 1, 2, 3) for f in fmaps]
+
+    @staticmethod
+    def _penalty_seed(pred):
+        """d mean(pred) / d pred"""
+        return torch.full((pred.shape[0], 1), 1.0 / pred.shape[0], dtype=torch.float32, device=pred.device)
+
+    def forward_with_penalty(self, x):
+        """-> (pred [B, 1], [fmap0 .. fmap3], L_GP): ``forward(x)`` plus ``gradient_penalty(pred, x)`` of the reference (loss.py:35-43) from
+        the SAME forward, so one power iteration as in the reference.  In grad mode all three carry the ``grad_fn`` of one Function, so
+        loss.py:98-108 reads ``(hinge_loss(pred_f, pred_r, 'disc') + w_GP * L_GP).backward()`` and any optimiser steps the module.  Once
+        differentiable; a frozen module returns the values and launches no weight-gradient kernel; ``x.grad`` receives the ``pred`` /
+        ``fmaps`` part only (the penalty's gradient at the clips is not formed: the reference's ``seq_real`` is data)."""
+        if x.dim() == 5 and x.size(1) > x.size(2):
+            x = x.transpose(1, 2)
+        params = list(self.parameters())
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
+            pred, l_gp, *fmaps = _Disc3DPenaltyFunction.apply(self, x, *params)
+            return pred, list(fmaps), l_gp
+        with torch.no_grad():
+            pred, fmaps, saved = self._run(x, save=True)
+            dx = self._handle().backward(self._penalty_seed(pred), None, saved, tuple(x.shape), need_dx=True, param_grads=False)
+        return pred, [f.permute(0, 4, 1, 2, 3) for f in fmaps], native.disc3d_sumsq(dx).mean()
 
 
 # ---------------------------------------------------------------------------------------------------------------- Encoder, training path
